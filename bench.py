@@ -14,13 +14,17 @@ merge, folds, leaf hashes and lower Merkle levels are block-local with global in
 all-gathered (stark_mlwe_amd.dist.ShardedTrace).  `value` = trace rows per second of that one job, work per
 GPU fixed => "weak".
 
-Side sections (outside the timed region, rank 0): HIP-event kernel timings for the roofline blocks (Fr-NTT
-against HBM, the Poseidon leaf kernel against the live-measured integer MAC issue rate), end-to-end
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the step's roots).
+--full adds, outside the timed region: the roots against the committed goldens (`roots_match_golden`,
+`roots_match_one_gpu_run`) and, on rank 0, the side sections: HIP-event kernel timings for the roofline blocks
+(Fr-NTT against HBM, the Poseidon leaf kernel against the live-measured integer MAC issue rate), end-to-end
 `deep_fri_prove` at the reference's bench shape and at 2^20, and the CPU baseline (the C++ oracle — a port of
 the reference's algorithm, the Rust reference cannot be built in this image — on a bounded sample).
 
 Usage: python bench.py --gpus N --steps K --warmup W   (N>1: launched by torch.distributed.run)
-       --steps-only   only the timed steps (what `rocprofv3 --kernel-trace --stats` should see)
+       --full                 the golden checks and side sections above
+       --steps-only           with --full: the golden checks but no side sections
+       --dump-outputs DIR     write the last timed step's layer roots to DIR/roots.npy (see dump_outputs)
 """
 import argparse
 import ctypes as C
@@ -100,6 +104,21 @@ def roots_hex(roots):
     return ["".join(f"{int(x):016x}" for x in r[::-1]) for r in roots]
 
 
+def roots_words(roots):
+    """The L+1 layer roots (four u64 Montgomery limbs each) as a float64 [L+1, 8] array of their 32-bit words, least significant
+    first: every word is exact in float64, so two runs' files compare bit for bit."""
+    import numpy as np
+    w = np.stack([np.asarray(r, dtype="<u8") for r in roots]).view("<u4")
+    return w.astype(np.float64)
+
+
+def dump_outputs(path, roots):
+    """--dump-outputs: what the timed path hands its caller, from the last timed step — the layer roots (roots_words)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "roots.npy"), roots_words(roots))
+
+
 def golden_step_roots(log_n, seed):
     """Roots the CPU oracle produced ONCE for this step (tools/gen_golden.py step:K -> tests/golden/step_roots_kK.json), or None when
     no golden exists for this size / seed.  A committed data file: the oracle itself is not touched here."""
@@ -118,13 +137,19 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--log-trace", type=int, default=LOG_TRACE)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--steps-only", action="store_true", help="only the timed steps and the headline fields (for rocprofv3 kernel stats)")
-    ap.add_argument("--e2e-log", type=int, default=20, help="log2 rows of the end-to-end deep_fri_prove section (0 disables)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--steps-only", action="store_true", help="with --full: the golden checks of the roots but no side sections (a plain run is steps only already)")
+    ap.add_argument("--e2e-log", type=int, default=20, help="with --full: log2 rows of the end-to-end deep_fri_prove section (0 disables)")
     ap.add_argument("--synth-seed", type=lambda x: int(x, 0), default=None, help="seed of the synthetic trace (default 0x5EED0000 + log-trace); lets a 1-GPU run reproduce the trace of an N-GPU run")
     ap.add_argument("--save-roots", default=None, help="write the step's roots (with the parameters that define the step) to this JSON file: a ONE-GPU run of a trace size that has no oracle golden, kept under tests/golden/step_roots_k<K>_one_gpu.json for the N > 1 runs of the same trace to compare with")
-    ap.add_argument("--csv", default=None, help="also write the reference's benchmarkdata.csv schema (end_to_end.rs:42-44) for the reference-input proves")
+    ap.add_argument("--csv", default=None, help="with --full: also write the reference's benchmarkdata.csv schema (end_to_end.rs:42-44) for the reference-input proves")
+    ap.add_argument("--full", action="store_true", help="after the timed steps: the roots against the committed goldens, kernel rooflines, end-to-end proves, the reference's bench shapes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's layer roots to DIR/roots.npy (float64 [L+1, 8]: 32-bit words, least significant first)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.csv and not args.full:
+        ap.error("--csv writes rows of the --full sections: add --full")
 
     import numpy as np
     import torch
@@ -229,6 +254,21 @@ def main():
                    "log_trace_per_gpu": log_n, "log_blowup": LOG_BLOWUP, "schedule": SCHEDULE, "field": "pallas_fr", "sharding": sharding},
         "roots": roots_hex(roots),
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, roots)
+    if args.save_roots and rank == 0 and world == 1:
+        with open(args.save_roots, "w") as f:
+            json.dump({"log_trace": log_total, "log_blowup": LOG_BLOWUP, "schedule": SCHEDULE, "seed_z": SEED_Z, "synth_seed": seed, "coset": STEP_COSET, "z": STEP_Z,
+                       "roots": out["roots"], "generator": "bench.py --save-roots on ONE MI355X (the product, not the oracle)"}, f, indent=1)
+            f.write("\n")
+    if not args.full:       # a plain run: the headline line only
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     gold = golden_step_roots(log_total, seed)      # N > 1: the sharded step commits to the same 2^log_total-row trace as one GPU would (same roots)
     # True / False against the committed oracle golden of exactly this step; null when no golden exists for this size, seed or N
     out["roots_match_golden"] = None if gold is None else (out["roots"] == gold)
@@ -242,11 +282,6 @@ def main():
             if g1.get("synth_seed") == seed and g1.get("schedule") == SCHEDULE and g1.get("seed_z") == SEED_Z and g1.get("log_blowup") == LOG_BLOWUP and g1.get("coset") == STEP_COSET and g1.get("z") == STEP_Z:
                 one = out["roots"] == g1["roots"]
     out["roots_match_one_gpu_run"] = one
-    if args.save_roots and rank == 0 and world == 1:
-        with open(args.save_roots, "w") as f:
-            json.dump({"log_trace": log_total, "log_blowup": LOG_BLOWUP, "schedule": SCHEDULE, "seed_z": SEED_Z, "synth_seed": seed, "coset": STEP_COSET, "z": STEP_Z,
-                       "roots": out["roots"], "generator": "bench.py --save-roots on ONE MI355X (the product, not the oracle)"}, f, indent=1)
-            f.write("\n")
     if args.steps_only:
         if rank == 0:
             print(json.dumps(out), flush=True)

@@ -15,7 +15,7 @@ R=${1:-rXX}
 OUT=$PWD/gpurun_out
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q --durations=8 > $OUT/gpu_tests_$R.log 2>&1; rc=$?; echo "tests exit $rc"; tail -14 $OUT/gpu_tests_$R.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 500 python bench.py --steps 10 --warmup 2 --csv $OUT/benchmarkdata_$R.csv > $OUT/bench_$R.json 2> $OUT/bench_$R.err; rc=$?; echo "bench exit $rc"; cut -c1-400 $OUT/bench_$R.json; tail -3 $OUT/bench_$R.err
+timeout -k 10 500 python bench.py --full --steps 10 --warmup 2 --csv $OUT/benchmarkdata_$R.csv > $OUT/bench_$R.json 2> $OUT/bench_$R.err; rc=$?; echo "bench exit $rc"; cut -c1-400 $OUT/bench_$R.json; tail -3 $OUT/bench_$R.err
 [ $rc -eq 0 ] || exit $rc
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$R -- python3 $OUT/../bench.py --steps-only --steps 3 --warmup 1 > $OUT/rocprof_bench_$R.log 2>&1; echo "rocprof stats exit $?") &&
 (mkdir -p $OUT/prof_$R && find /tmp/prof_$R -name "*stats*.csv" -exec cp {} $OUT/prof_$R/ \; ; ls $OUT/prof_$R)
@@ -34,5 +34,5 @@ timeout -k 10 300 python tools/latency_timing.py 2>/dev/null | grep one_wave > $
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/ptrace_$R -- python3 $OUT/../tools/prove_trace.py 16 3 > $OUT/ptrace_$R.log 2>&1; echo "prove trace exit $?") &&
 (f=$(find /tmp/ptrace_$R -name "*kernel_trace.csv" | head -1); python tools/prove_trace.py summarize "$f" > $OUT/prove_trace_k16_$R.txt; tail -2 $OUT/prove_trace_k16_$R.txt)
 for m in 1 0 1 0; do timeout -k 10 120 python tools/variant_bench.py stark_mlwe_amd/libstark_mlwe_hip.so merged$m ntt_merged_coset=$m ntt 2>/dev/null | grep variant | cut -c1-330; done > $OUT/ntt_merged_ab_$R.jsonl; cat $OUT/ntt_merged_ab_$R.jsonl
-(STARK_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 1 --warmup 1 --log-trace 19 --no-cpu-baseline > $OUT/bench2_gloo_$R.json 2> $OUT/bench2_gloo_$R.err; echo "bench2 exit $?"; cut -c1-300 $OUT/bench2_gloo_$R.json)
+(STARK_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 2 --steps 1 --warmup 1 --log-trace 19 --no-cpu-baseline > $OUT/bench2_gloo_$R.json 2> $OUT/bench2_gloo_$R.err; echo "bench2 exit $?"; cut -c1-300 $OUT/bench2_gloo_$R.json)
 echo "session done"
