@@ -18,15 +18,46 @@ using namespace stark;
 static const size_t kMaxLds = 160 * 1024;
 static inline int poseidon_block(int t) { return (size_t)t * 32 * 64 <= kMaxLds ? 64 : 32; }
 static inline size_t poseidon_lds(int t, int block) { return (size_t)t * 32 * block; }
-// the wave-pair kernels (poseidon_pair.hpp) serve the hot widths; the "poseidon_lane_only" option selects the one-lane-per-sponge form (diagnostic)
-static inline bool use_pair(const stark_ctx* ctx, int t) { return !ctx->opt_poseidon_lane_only && (t == 9 || t == 17); }
-// Small batches of t = 17 sponges take the five-wave latency form of poseidon_chain.hpp (one workgroup per sponge, one resident per CU): Merkle levels of up
-// to 256 nodes (two permutations: 155 us against 290 us on one wave each; equal from 512 nodes on), leaf layers of up to 2048 leaves (one permutation:
-// 80 us per 256 leaves against the 0.77 ms a launch of the wave-pair throughput kernel takes whatever its size).  tools/latency_timing.py;
-// option "sponge_one_wave" keeps them on the one-wave / wave-pair kernels (comparison).
-constexpr size_t kChainMaxNodes = 256, kChainMaxLeaves = 2048, kCoopMaxLeaves = 4096, kCoopMaxNodes = 4096;      // leaf layers above kChainMaxLeaves: one wave per leaf up to kCoopMaxLeaves
-static inline bool use_chain(const stark_ctx* ctx, const PoseidonDev& d, size_t n, size_t n_max) {
-    return !ctx->opt_poseidon_lane_only && !ctx->opt_sponge_one_wave && d.t == 17 && d.rf == 8 && d.rp == 64 && d.chain_a && n <= n_max;
+// ---- which kernel form runs a Poseidon operation of n sponges ---------------------------------------------------------------------------------
+//   Lane      one lane per sponge, state in LDS (poseidon_dev.hpp): any width; the option "poseidon_lane_only" forces it (diagnostic)
+//   WavePair  two waves per 64 sponges (poseidon_pair.hpp): the throughput form of the hot widths t = 9, 17
+//   OneWave   one wave per sponge (poseidon_coop.hpp): few or long sponges, t = 9, 17
+//   FiveWave  five waves per sponge (poseidon_chain.hpp), one workgroup resident per CU: the latency form, t = 17 with the chain tables
+//   Wide      one wave per sponge for t = 33, 65, 129 (poseidon_wave.hpp)
+// Small batches of t = 17 sponges take the five-wave form: Merkle levels of up to 256 nodes (two permutations: 155 us against 290 us on one wave each;
+// equal from 512 nodes on), leaf layers of up to 2048 leaves (one permutation: 80 us per 256 leaves against the 0.77 ms a launch of the wave-pair
+// throughput kernel takes whatever its size), transcript hashes of up to 512 sponges (up to two resident workgroups per CU; 72 us per permutation
+// against 142 us on one wave).  Above that one wave per node / leaf / sponge up to 4096, then the wave pair (Merkle levels, leaf layers) or a lane per
+// sponge (transcript hashes).  The Merkle and leaf crossovers were measured by tools/latency_timing.py; the option "sponge_one_wave" keeps the small
+// batches on the one-wave / wave-pair kernels (comparison).
+// The mapping is kept exactly as measured, including where operations differ: under "sponge_one_wave" a Merkle level of <= 4096 nodes runs one wave per
+// node but a leaf layer of <= 4096 leaves the wave pair, and the column sponges ignore "poseidon_lane_only".
+enum class PoseidonForm { Lane, WavePair, OneWave, FiveWave, Wide };
+enum class PoseidonOp { MerkleLevel, LeafLayer, TrHash, ColumnSponges, DeviceTranscript };
+constexpr size_t kChainMaxNodes = 256, kChainMaxLeaves = 2048, kChainMaxSponges = 512, kCoopMaxNodes = 4096, kCoopMaxLeaves = 4096, kCoopMaxSponges = 4096;
+static PoseidonForm poseidon_form(const stark_ctx* ctx, const stark_params* p, PoseidonOp op, size_t n) {
+    const PoseidonDev& d = p->dev;
+    const bool lane_only = ctx->opt_poseidon_lane_only, one_wave = ctx->opt_sponge_one_wave;
+    const bool chain = !lane_only && !one_wave && d.t == 17 && d.rf == 8 && d.rp == 64 && d.chain_a;
+    switch (op) {
+    case PoseidonOp::MerkleLevel:
+        if (chain && n <= kChainMaxNodes) return PoseidonForm::FiveWave;
+        if (!lane_only && (d.t == 9 || d.t == 17)) return n <= kCoopMaxNodes ? PoseidonForm::OneWave : PoseidonForm::WavePair;
+        if (!lane_only && (d.t == 33 || d.t == 65 || d.t == 129) && n <= 0x7fffffffu) return PoseidonForm::Wide;     // one block per node
+        return PoseidonForm::Lane;
+    case PoseidonOp::LeafLayer:
+        if (chain && n <= kChainMaxLeaves) return PoseidonForm::FiveWave;
+        if (!lane_only && !one_wave && n <= kCoopMaxLeaves) return PoseidonForm::OneWave;
+        return lane_only ? PoseidonForm::Lane : PoseidonForm::WavePair;
+    case PoseidonOp::TrHash:
+        if (chain && n <= kChainMaxSponges) return PoseidonForm::FiveWave;
+        return !lane_only && n <= kCoopMaxSponges ? PoseidonForm::OneWave : PoseidonForm::Lane;
+    case PoseidonOp::ColumnSponges:
+        return d.chain_a && !one_wave ? PoseidonForm::FiveWave : PoseidonForm::OneWave;
+    case PoseidonOp::DeviceTranscript:
+        return chain ? PoseidonForm::FiveWave : PoseidonForm::OneWave;
+    }
+    return PoseidonForm::Lane;
 }
 static inline row::Consts row_consts_of(const stark_ctx* ctx) {
     const RowConstsHost h = row_consts_host(); row::Consts RK; for (int i = 0; i < 9; ++i) RK.ni[i] = h.ni[i]; for (int i = 0; i < 5; ++i) RK.t[i] = h.t[i]; RK.dbg = (uint32_t)ctx->opt_sponge_debug; return RK;
@@ -138,83 +169,58 @@ int32_t ctx_merkle_params(stark_ctx* ctx, int t, stark_params** out) {
     *out = it->second; return STARK_OK;
 }
 
-// Transcript framing for `tr_hash_fields_tagged(tag, xs)` (fri.rs:28-35 over transcript/src/lib.rs:55-101):
-// absorbed stream = [AB, w("FRI/FS"), AB, words(tag).., xs.., CH, AB, w("out")], capacity lane = INIT.
-static int32_t tr_frame(stark_ctx* ctx, const char* label, const char* tag, const char* out_label, fr_t** dev, int* np, int* ns) {
-    std::string key = std::string(label) + "\x01" + tag + "\x01" + out_label;
+// The device copy of host::tr_hash_frame(tag), cached per tag: frame = prefix || suffix, np + ns elements.
+static int32_t tr_frame(stark_ctx* ctx, const char* tag, fr_t** dev, int* np, int* ns) {
+    const std::string key(tag);
     auto it = ctx->tr_frames.find(key);
     if (it == ctx->tr_frames.end()) {
-        std::vector<fr_t> fr; const fr_t AB = host::h_tag("FSv1-ABSORB-BYTES"), CH = host::h_tag("FSv1-CHALLENGE");
-        fr.push_back(AB); for (auto& w : host::h_words(label)) fr.push_back(w);
-        fr.push_back(AB); for (auto& w : host::h_words(tag)) fr.push_back(w);
-        int p = (int)fr.size();
-        fr.push_back(CH); fr.push_back(AB); for (auto& w : host::h_words(out_label)) fr.push_back(w);
-        int s = (int)fr.size() - p;
+        std::vector<fr_t> fr; const int p = host::tr_hash_frame(tag, fr);
         fr_t* d = nullptr; STARK_HIP(ctx, hipMalloc((void**)&d, fr.size() * sizeof(fr_t)));
         STARK_HIP(ctx, hipMemcpyAsync(d, fr.data(), fr.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
         STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->tr_frames[key] = d; ctx->tr_frame_dims[key] = {p, s};
+        ctx->tr_frames[key] = d; ctx->tr_frame_dims[key] = {p, (int)fr.size() - p};
         it = ctx->tr_frames.find(key);
     }
     *dev = it->second; *np = ctx->tr_frame_dims[key].first; *ns = ctx->tr_frame_dims[key].second; return STARK_OK;
 }
-static int32_t launch_column_sponges(stark_ctx* ctx, stark_params* tp, const TrMultiJob& J, unsigned nblocks, fr_t* out_dev);
+static int32_t launch_tr_hash(stark_ctx* ctx, stark_params* tp, PoseidonForm form, const TrStream& T, fr_t* out_dev) {
+    switch (form) {
+    case PoseidonForm::FiveWave:
+        hipLaunchKernelGGL(k_tr_hash_chain, dim3((unsigned)T.n), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, T, row_consts_of(ctx), out_dev); break;
+    case PoseidonForm::OneWave:
+        if (T.layout == TrStream::Equal) hipLaunchKernelGGL(k_tr_hash_coop<false>, dim3((unsigned)T.n), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T, out_dev);
+        else hipLaunchKernelGGL(k_tr_hash_coop<true>, dim3((unsigned)T.n), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T, out_dev);
+        break;
+    default: {
+        const int block = 64;
+        hipLaunchKernelGGL(k_tr_hash, dim3((unsigned)((T.n + block - 1) / block)), dim3(block), poseidon_lds(17, block), ctx->stream, tp->dev, T, out_dev);
+    } }
+    STARK_HIP(ctx, hipGetLastError());
+    return STARK_OK;
+}
 int32_t tr_hash_dev(stark_ctx* ctx, const char* tag, const fr_t* fields_dev, size_t k, size_t n, fr_t* out_dev) {
-    hipStream_t st = ctx->stream;
     stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
-    fr_t* frame = nullptr; int np = 0, ns = 0; STARK_TRY(tr_frame(ctx, "FRI/FS", tag, "out", &frame, &np, &ns));
+    fr_t* frame = nullptr; int np = 0, ns = 0; STARK_TRY(tr_frame(ctx, tag, &frame, &np, &ns));
     if (n == 0) return STARK_OK;
-    TrJob J; J.prefix = frame; J.np = np; J.suffix = frame + np; J.ns = ns; J.cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); J.k = k; J.n = n;
-    if (!ctx->opt_poseidon_lane_only && !ctx->opt_sponge_one_wave && tp->dev.chain_a && n <= 512) {
-        // up to two resident workgroups per CU: five waves per sponge (poseidon_chain.hpp), 72 us per permutation against 142 us on one wave —
-        // a column digest of a sharded prove, a long Fiat-Shamir input, and the short challenge hashes of the query phase alike
-        TrMultiJob M; M.cap = J.cap; M.batch = nullptr; M.stride = k;
-        for (int c = 0; c < 4; ++c) { M.prefix[c] = frame; M.np[c] = np; M.suffix[c] = frame + np; M.ns[c] = ns; M.fields[c] = fields_dev; M.k[c] = k; }
-        return launch_column_sponges(ctx, tp, M, (unsigned)n, out_dev);
-    }
-    if (!ctx->opt_poseidon_lane_only && n <= 4096) {
-        // few (or one, possibly very long) sponges: one wave per sponge, latency-oriented (poseidon_coop.hpp)
-        hipLaunchKernelGGL(k_tr_hash_coop, dim3((unsigned)n), dim3(64), coop_lds_bytes(17), st, tp->dev, J, fields_dev, out_dev);
-        STARK_HIP(ctx, hipGetLastError());
-        return STARK_OK;
-    }
-    const int block = 64; const size_t lds = poseidon_lds(17, block);
-    hipLaunchKernelGGL(k_tr_hash, dim3((unsigned)((n + block - 1) / block)), dim3(block), lds, st, tp->dev, J, fields_dev, out_dev);
-    STARK_HIP(ctx, hipGetLastError());
-    return STARK_OK;
+    const TrStream T = TrStream::equal(frame, np, ns, fields_dev, k, n, host::h_tag("FSv1-TRANSCRIPT-INIT"));
+    return launch_tr_hash(ctx, tp, poseidon_form(ctx, tp, PoseidonOp::TrHash, n), T, out_dev);
 }
-// Long serial sponges: five waves per chain (poseidon_chain.hpp) unless the option "sponge_one_wave" asks for the round-2 one-wave form.
-static int32_t launch_column_sponges(stark_ctx* ctx, stark_params* tp, const TrMultiJob& J, unsigned nblocks, fr_t* out_dev) {
-    if (tp->dev.chain_a && !ctx->opt_sponge_one_wave) {
-        const row::Consts RK = row_consts_of(ctx);
-        hipLaunchKernelGGL(k_tr_hash_chain, dim3(nblocks), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, J, RK, out_dev);
-    } else {
-        hipLaunchKernelGGL(k_tr_hash_coop_multi, dim3(nblocks), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, J, out_dev);
+// The serial column sponges of DeepAliRealBuilder::build_f0 (fri.rs:551-554), one block each: the four columns of one trace (ptrs_dev == nullptr) or
+// of B independent traces (ptrs_dev[4 * p + c] = column c of trace p, a device array of device pointers).
+static int32_t tr_hash_columns(stark_ctx* ctx, const char* const tags[4], const fr_t* const cols[4], const fr_t* const* ptrs_dev, size_t nblocks, size_t n0, fr_t* out_dev) {
+    stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
+    TrStream T{}; T.layout = ptrs_dev ? TrStream::BatchColumns : TrStream::Columns; T.n = nblocks; T.batch = ptrs_dev; T.cap = host::h_tag("FSv1-TRANSCRIPT-INIT");
+    for (int c = 0; c < 4; ++c) {
+        fr_t* frame = nullptr; int np = 0, ns = 0; STARK_TRY(tr_frame(ctx, tags[c], &frame, &np, &ns));
+        T.prefix[c] = frame; T.np[c] = np; T.suffix[c] = frame + np; T.ns[c] = ns; T.fields[c] = cols ? cols[c] : nullptr; T.k[c] = n0;
     }
-    STARK_HIP(ctx, hipGetLastError());
-    return STARK_OK;
+    return launch_tr_hash(ctx, tp, poseidon_form(ctx, tp, PoseidonOp::ColumnSponges, nblocks), T, out_dev);
 }
-// The four column sponges of DeepAliRealBuilder::build_f0 (fri.rs:551-554) as one launch of four blocks.
 int32_t tr_hash_columns4_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const cols[4], size_t n0, fr_t* out4_dev) {
-    stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
-    TrMultiJob J; J.cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); J.batch = nullptr; J.stride = 0;
-    for (int c = 0; c < 4; ++c) {
-        fr_t* frame = nullptr; int np = 0, ns = 0; STARK_TRY(tr_frame(ctx, "FRI/FS", tags[c], "out", &frame, &np, &ns));
-        J.prefix[c] = frame; J.np[c] = np; J.suffix[c] = frame + np; J.ns[c] = ns; J.fields[c] = cols[c]; J.k[c] = n0;
-    }
-    STARK_TRY(launch_column_sponges(ctx, tp, J, 4, out4_dev));
-    return STARK_OK;
+    return tr_hash_columns(ctx, tags, cols, nullptr, 4, n0, out4_dev);
 }
-// The same for B independent traces: 4 * B chains, one block each, in one launch.  ptrs_dev[4 * p + c] = column c of trace p (device array of device pointers).
 int32_t tr_hash_columns_batch_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const* ptrs_dev, size_t batch, size_t n0, fr_t* out_dev) {
-    stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
-    TrMultiJob J; J.cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); J.batch = ptrs_dev; J.stride = 0;
-    for (int c = 0; c < 4; ++c) {
-        fr_t* frame = nullptr; int np = 0, ns = 0; STARK_TRY(tr_frame(ctx, "FRI/FS", tags[c], "out", &frame, &np, &ns));
-        J.prefix[c] = frame; J.np[c] = np; J.suffix[c] = frame + np; J.ns[c] = ns; J.fields[c] = nullptr; J.k[c] = n0;
-    }
-    STARK_TRY(launch_column_sponges(ctx, tp, J, (unsigned)(4 * batch), out_dev));
-    return STARK_OK;
+    return tr_hash_columns(ctx, tags, nullptr, ptrs_dev, 4 * batch, n0, out_dev);
 }
 int32_t tr_hash_host1(stark_ctx* ctx, const char* tag, const std::vector<fr_t>& fields, fr_t* out) {
     DevBuf in, o; STARK_HIP(ctx, in.alloc(ctx, fields.size() * sizeof(fr_t))); STARK_HIP(ctx, o.alloc(ctx, sizeof(fr_t)));
@@ -256,6 +262,11 @@ static int32_t ctx_leaf_init(stark_ctx* ctx, fr_t** out) {
     *out = ctx->leaf_init; return STARK_OK;
 }
 
+namespace {   // sumcheck_impl.hpp, included at the end of this file
+__global__ void k_tr_stream_chain(PoseidonDev P, row::Consts RK, fr_t* __restrict__ state, uint32_t* __restrict__ pos_io, const fr_t* __restrict__ fields, uint64_t n, int finish,
+                                  fr_t* __restrict__ out);
+}
+
 extern "C" {
 
 int32_t stark_version(void) { return 1; }
@@ -283,6 +294,7 @@ int32_t stark_ctx_create(int32_t device, void* stream, stark_ctx_t** out) {
     (void)hipFuncSetAttribute((const void*)k_tr_hash_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_hash_ds_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_leaf_pair_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_tr_stream_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     *out = c; return STARK_OK;
 }
 }  // extern "C"
@@ -486,35 +498,28 @@ int32_t stark_poseidon_hash_with_ds(stark_ctx_t* ctx, stark_params_t* p, const u
 }
 static int32_t launch_hash_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, int mode, size_t arity, uint32_t level, uint64_t pos0, uint64_t label,
                               const fr_t* in0, const fr_t* in1, size_t n_in, fr_t* out, size_t cp_div = 1, const uint64_t* pos_list = nullptr, size_t chunk = 0) {
-    DsJob J; J.pos_list = pos_list; J.arity_f = host::h_u64(arity); J.level_f = host::h_u64(level); J.label_f = host::h_u64(label); J.pos0 = pos0; J.arity = arity; J.n_in = n_in; J.mode = mode; J.cp_div = cp_div ? cp_div : 1;
-    if (chunk) J.arity = chunk;          // the verifier's groups: DS field `arity` as given, `chunk` children per hash (a short last chunk of the proof's level)
-    J.n_out = mode == 1 ? n_in : (n_in + J.arity - 1) / J.arity;
-    if (!J.n_out) return STARK_OK;
-    if (use_chain(ctx, p->dev, J.n_out, kChainMaxNodes)) {
-        hipLaunchKernelGGL(k_hash_ds_chain, dim3((unsigned)J.n_out), dim3(320), chain_lds_bytes(), st, p->dev, J, row_consts_of(ctx), in0, in1, out);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    if (use_pair(ctx, p->dev.t) && J.n_out <= kCoopMaxNodes) {
-        // small level: one wave per node (latency form); a batch of 64 nodes per wave pair only pays off above that
-        if (p->dev.t == 17) hipLaunchKernelGGL(k_hash_ds_coop<17>, dim3((unsigned)J.n_out), dim3(64), coop_lds_bytes(17), st, p->dev, J, in0, in1, out);
-        else hipLaunchKernelGGL(k_hash_ds_coop<9>, dim3((unsigned)J.n_out), dim3(64), coop_lds_bytes(9), st, p->dev, J, in0, in1, out);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    if (use_pair(ctx, p->dev.t)) {
-        if (p->dev.t == 17) hipLaunchKernelGGL(k_hash_ds2<17>, dim3((unsigned)((J.n_out + 63) / 64)), dim3(128), pair_lds_bytes(17), st, p->dev, J, in0, in1, out);
-        else hipLaunchKernelGGL(k_hash_ds2<9>, dim3((unsigned)((J.n_out + 63) / 64)), dim3(128), pair_lds_bytes(9), st, p->dev, J, in0, in1, out);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    if (!ctx->opt_poseidon_lane_only && (p->dev.t == 33 || p->dev.t == 65 || p->dev.t == 129) && J.n_out <= 0x7fffffffu) {
-        // wide states (arity 32 / 64 / 128): one wave per node (poseidon_wave.hpp) — a lane per node walks a 17 ms permutation alone
-        const dim3 grid((unsigned)J.n_out), blk(64); const size_t lds = wave_lds_bytes(p->dev.t);
-        if (p->dev.t == 33) hipLaunchKernelGGL(k_hash_ds_wave<33>, grid, blk, lds, st, p->dev, J, in0, in1, out);
-        else if (p->dev.t == 65) hipLaunchKernelGGL(k_hash_ds_wave<65>, grid, blk, lds, st, p->dev, J, in0, in1, out);
-        else hipLaunchKernelGGL(k_hash_ds_wave<129>, grid, blk, lds, st, p->dev, J, in0, in1, out);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    const int block = poseidon_block(p->dev.t);
-    hipLaunchKernelGGL(k_hash_ds, dim3((unsigned)((J.n_out + block - 1) / block)), dim3(block), poseidon_lds(p->dev.t, block), st, p->dev, J, in0, in1, out);
+    const DsStream D = DsStream::make(mode, arity, level, pos0, label, in0, in1, n_in, cp_div, pos_list, chunk);
+    if (!D.n_out) return STARK_OK;
+    const int t = p->dev.t; const unsigned nodes = (unsigned)D.n_out, pairs = (unsigned)((D.n_out + 63) / 64);
+    switch (poseidon_form(ctx, p, PoseidonOp::MerkleLevel, D.n_out)) {
+    case PoseidonForm::FiveWave: hipLaunchKernelGGL(k_hash_ds_chain, dim3(nodes), dim3(320), chain_lds_bytes(), st, p->dev, D, row_consts_of(ctx), out); break;
+    case PoseidonForm::OneWave:
+        if (t == 17) hipLaunchKernelGGL(k_hash_ds_coop<17>, dim3(nodes), dim3(64), coop_lds_bytes(17), st, p->dev, D, out);
+        else hipLaunchKernelGGL(k_hash_ds_coop<9>, dim3(nodes), dim3(64), coop_lds_bytes(9), st, p->dev, D, out);
+        break;
+    case PoseidonForm::WavePair:
+        if (t == 17) hipLaunchKernelGGL(k_hash_ds2<17>, dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D, out);
+        else hipLaunchKernelGGL(k_hash_ds2<9>, dim3(pairs), dim3(128), pair_lds_bytes(9), st, p->dev, D, out);
+        break;
+    case PoseidonForm::Wide:
+        if (t == 33) hipLaunchKernelGGL(k_hash_ds_wave<33>, dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
+        else if (t == 65) hipLaunchKernelGGL(k_hash_ds_wave<65>, dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
+        else hipLaunchKernelGGL(k_hash_ds_wave<129>, dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
+        break;
+    case PoseidonForm::Lane: {
+        const int block = poseidon_block(t);
+        hipLaunchKernelGGL(k_hash_ds, dim3((unsigned)((D.n_out + block - 1) / block)), dim3(block), poseidon_lds(t, block), st, p->dev, D, out);
+    } }
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
 }
 }  // extern "C"
@@ -555,20 +560,13 @@ int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const f
     if (!n) return STARK_OK;
     stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
     fr_t* init = nullptr; STARK_TRY(ctx_leaf_init(ctx, &init));
-    if (use_chain(ctx, tp->dev, n, kChainMaxLeaves)) {
-        hipLaunchKernelGGL(k_leaf_pair_chain, dim3((unsigned)n), dim3(320), chain_lds_bytes(), st, tp->dev, row_consts_of(ctx), (const fr_t*)init, f, f_next, m, h);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    const LeafStream L{init, f, f_next, m, n};
+    switch (poseidon_form(ctx, tp, PoseidonOp::LeafLayer, n)) {
+    case PoseidonForm::FiveWave: hipLaunchKernelGGL(k_leaf_pair_chain, dim3((unsigned)n), dim3(320), chain_lds_bytes(), st, tp->dev, row_consts_of(ctx), L, h); break;
+    case PoseidonForm::OneWave: hipLaunchKernelGGL(k_leaf_pair_coop, dim3((unsigned)n), dim3(64), coop_lds_bytes(17), st, tp->dev, L, h); break;
+    case PoseidonForm::WavePair: hipLaunchKernelGGL(k_leaf_pair2, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, init + 17, f, f_next, n, m, h); break;
+    default: hipLaunchKernelGGL(k_leaf_pair, dim3((unsigned)((n + 63) / 64)), dim3(64), poseidon_lds(17, 64), st, tp->dev, L, h);
     }
-    if (use_pair(ctx, 17) && !ctx->opt_sponge_one_wave && n <= kCoopMaxLeaves) {
-        hipLaunchKernelGGL(k_leaf_pair_coop, dim3((unsigned)n), dim3(64), coop_lds_bytes(17), st, tp->dev, (const fr_t*)init, f, f_next, m, h);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    if (use_pair(ctx, 17)) {
-        hipLaunchKernelGGL(k_leaf_pair2, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, init + 17, f, f_next, n, m, h);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    const int block = 64;
-    hipLaunchKernelGGL(k_leaf_pair, dim3((unsigned)((n + block - 1) / block)), dim3(block), poseidon_lds(17, block), st, tp->dev, init, f, f_next, n, m, h);
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
 }
 }  // namespace stark

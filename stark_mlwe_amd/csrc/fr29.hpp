@@ -155,6 +155,25 @@ template <class F, bool MAC_POW2 = false> FR_HD fr_t fr_wide29_reduce(fr_wide29&
     uint32_t l[9]; fr_wide29_mont<F, MAC_POW2>(w, l);
     return fr29_pack_reduce<F>(l);
 }
+// value below 2^261 -> below 2r + epsilon, still >= 0: subtract k * r with k = floor(value / 2^254) - 1  (r = 2^254 + t, t < 2^126).
+// 64-bit signed limbs during the pass: k * r_i reaches 2^36.
+template <class F> FR_HD void lazy_reduce29(fr29_t& a) {
+    const uint32_t q = a.l[8] >> 22; const int64_t k = q ? (int64_t)q - 1 : 0;
+    int64_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const int64_t d = (int64_t)a.l[i] - k * (int64_t)fr_p29<F>(i) + carry;
+        if (i < 8) { a.l[i] = (uint32_t)d & FR_M29; carry = d >> 29; } else a.l[8] = (uint32_t)d;
+    }
+}
+// nine lazy limbs (limbs below 2^29, any value below 2^261) -> canonical fr_t: below 2r + epsilon after lazy_reduce29, so the pack's
+// conditional subtraction is followed by a second one (it fires with probability ~2^-125)
+template <class F> FR_HD fr_t fr29_canon_lazy(fr29_t v) {
+    lazy_reduce29<F>(v);
+    fr_t z = fr29_pack_reduce<F>(v.l);
+    fr_cond_sub<F>(z.v, 0u);
+    return z;
+}
 
 // ---- the S-box in radix 2^29 ---------------------------------------------------------------------------------
 // x^5 = x * (x^2)^2 with two SQUARINGS: in radix 2^29 a doubled limb still fits the 32-bit multiplier operand, so a

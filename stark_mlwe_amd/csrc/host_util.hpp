@@ -153,6 +153,18 @@ inline std::vector<fr_t> h_words(const char* s) {
     for (size_t off = 0; off < n; off += 31) { uint8_t le[32] = {0}; size_t c = n - off < 31 ? n - off : 31; memcpy(le, s + off, c); out.push_back(h_from_le_bytes_mod_order(le, 32)); }
     return out;
 }
+// The frame of tr_hash_fields_tagged(tag, xs) (fri.rs:28-35 over transcript/src/lib.rs:55-101): the absorbed stream is
+// [AB, w("FRI/FS"), AB, words(tag)..] || xs || [CH, AB, w("out")] under the capacity FSv1-TRANSCRIPT-INIT.  frame = prefix || suffix;
+// returns the prefix length.
+inline int tr_hash_frame(const char* tag, std::vector<fr_t>& frame) {
+    const fr_t AB = h_tag("FSv1-ABSORB-BYTES"), CH = h_tag("FSv1-CHALLENGE");
+    frame.clear();
+    frame.push_back(AB); for (auto& w : h_words("FRI/FS")) frame.push_back(w);
+    frame.push_back(AB); for (auto& w : h_words(tag)) frame.push_back(w);
+    const int np = (int)frame.size();
+    frame.push_back(CH); frame.push_back(AB); for (auto& w : h_words("out")) frame.push_back(w);
+    return np;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Poseidon constants in the reference's form (poseidon/src/lib.rs:104-114, 176-216, 318-356).

@@ -220,30 +220,29 @@ int hc_leaf_pair(void* tparams, const uint64_t* f, const uint64_t* f_next, size_
     fr_t init[17]; for (auto& x : init) x = host::h_zero();
     init[0] = AB; init[1] = host::h_words("FRI/leaf/poseidon")[0]; init[2] = AB; init[3] = host::h_words("FRI/leaf")[0];
     init[6] = CH; init[7] = AB; init[8] = host::h_words("leaf")[0]; init[16] = host::h_tag("FSv1-TRANSCRIPT-INIT");
+    std::vector<fr_t> fv(n), nv(f_next ? (n + m - 1) / m : 0);
+    for (size_t i = 0; i < fv.size(); ++i) fv[i] = ld4(f + 4 * i);
+    for (size_t i = 0; i < nv.size(); ++i) nv[i] = ld4(f_next + 4 * i);
+    const LeafStream L{init, fv.data(), f_next ? nv.data() : nullptr, m, n};
     fr_t st[17];
-    for (size_t i = 0; i < n; ++i) { ArrayState s{st}; st4(hout + 4 * i, leaf_pair_body(s, P->dev, init, ld4(f + 4 * i), f_next ? ld4(f_next + 4 * (i / m)) : host::h_zero())); }
+    for (size_t i = 0; i < n; ++i) { ArrayState s{st}; st4(hout + 4 * i, leaf_pair_body(s, P->dev, L, i)); }
     return 0;
 }
 int hc_hash_ds_level(void* params, int mode, size_t arity, uint32_t level, uint64_t pos0, uint64_t label, const uint64_t* in0, const uint64_t* in1, size_t n_in, uint64_t* out) {
     HcParams* P = (HcParams*)params;
-    DsJob J; J.arity_f = host::h_u64(arity); J.level_f = host::h_u64(level); J.label_f = host::h_u64(label); J.pos0 = pos0; J.arity = arity; J.n_in = n_in; J.mode = mode; J.cp_div = 1;
-    J.n_out = mode == 1 ? n_in : (n_in + arity - 1) / arity;
     std::vector<fr_t> a(n_in), b(in1 ? n_in : 0), st(P->dev.t);
     for (size_t i = 0; i < n_in; ++i) { a[i] = ld4(in0 + 4 * i); if (in1) b[i] = ld4(in1 + 4 * i); }
-    for (size_t k = 0; k < J.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, J, a.data(), in1 ? b.data() : nullptr, k)); }
+    const DsStream D = DsStream::make(mode, arity, level, pos0, label, a.data(), in1 ? b.data() : nullptr, n_in);
+    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, D, k)); }
     return 0;
 }
 int hc_tr_hash(void* tparams, const char* tag, const uint64_t* fields, size_t k, size_t n, uint64_t* out) {
     HcParams* P = (HcParams*)tparams;
-    std::vector<fr_t> fr; const fr_t AB = host::h_tag("FSv1-ABSORB-BYTES"), CH = host::h_tag("FSv1-CHALLENGE");
-    fr.push_back(AB); for (auto& w : host::h_words("FRI/FS")) fr.push_back(w);
-    fr.push_back(AB); for (auto& w : host::h_words(tag)) fr.push_back(w);
-    int np = (int)fr.size();
-    fr.push_back(CH); fr.push_back(AB); for (auto& w : host::h_words("out")) fr.push_back(w);
-    TrJob J; J.prefix = fr.data(); J.np = np; J.suffix = fr.data() + np; J.ns = (int)fr.size() - np; J.cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); J.k = k; J.n = n;
+    std::vector<fr_t> fr; const int np = host::tr_hash_frame(tag, fr);
     std::vector<fr_t> fl(n * k); for (size_t i = 0; i < n * k; ++i) fl[i] = ld4(fields + 4 * i);
+    const TrStream T = TrStream::equal(fr.data(), np, (int)fr.size() - np, fl.data(), k, n, host::h_tag("FSv1-TRANSCRIPT-INIT"));
     fr_t st[17];
-    for (size_t i = 0; i < n; ++i) { ArrayState s{st}; st4(out + 4 * i, tr_hash_body(s, P->dev, J, fl.data(), i)); }
+    for (size_t i = 0; i < n; ++i) { ArrayState s{st}; st4(out + 4 * i, tr_hash_body(s, P->dev, T, i)); }
     return 0;
 }
 int hc_hash_stream(void* params, int mode, const uint64_t* a, size_t na, const uint64_t* b, size_t nb, const uint64_t* tag, size_t n, uint64_t* out) {
@@ -306,14 +305,14 @@ struct HcVerifyHasher : VerifyHasher {
     }
     int32_t ds_nodes(size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions, const fr_t* children, size_t n, fr_t* out) override {
         HcParams* P = params(arity); std::vector<fr_t> st(P->dev.t);
-        DsJob J; J.arity_f = host::h_u64(arity); J.level_f = host::h_u64(level); J.label_f = host::h_u64(label); J.pos0 = 0; J.arity = chunk; J.n_in = n * chunk; J.n_out = n; J.mode = 0; J.pos_list = positions;
-        for (size_t k = 0; k < n; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, P->dev, J, children, nullptr, k); }
+        const DsStream D = DsStream::make(0, arity, level, 0, label, children, nullptr, n * chunk, 1, positions, chunk);
+        for (size_t k = 0; k < n; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, P->dev, D, k); }
         return 0;
     }
     int32_t ds_pair_leaves(size_t arity, uint64_t label, const uint64_t* positions, const fr_t* f, const fr_t* cp, size_t n, fr_t* out) override {
         HcParams* P = params(arity); std::vector<fr_t> st(P->dev.t);
-        DsJob J; J.arity_f = host::h_u64(arity); J.level_f = host::h_u64(0xFFFFFFFFu); J.label_f = host::h_u64(label); J.pos0 = 0; J.arity = arity; J.n_in = n; J.n_out = n; J.mode = 1; J.pos_list = positions;
-        for (size_t k = 0; k < n; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, P->dev, J, f, cp, k); }
+        const DsStream D = DsStream::make(1, arity, 0xFFFFFFFFu, 0, label, f, cp, n, 1, positions);
+        for (size_t k = 0; k < n; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, P->dev, D, k); }
         return 0;
     }
 };

@@ -26,7 +26,8 @@
 #include "fr29.hpp"
 #include "poseidon_params.hpp"
 #if defined(__HIPCC__)
-#include "poseidon_coop.hpp"      // full rounds on one wave, nine-limb helpers, TrMultiJob
+#include "poseidon_coop.hpp"      // full rounds on one wave, nine-limb helpers
+#include "poseidon_streams.hpp"
 #endif
 
 namespace stark {
@@ -195,26 +196,6 @@ __device__ __forceinline__ void chain_read_row(const uint32_t* rowp, fr29_t& v) 
     const uint4 a = *reinterpret_cast<const uint4*>(rowp), b = *reinterpret_cast<const uint4*>(rowp + 4);
     v.l[0] = a.x; v.l[1] = a.y; v.l[2] = a.z; v.l[3] = a.w; v.l[4] = b.x; v.l[5] = b.y; v.l[6] = b.z; v.l[7] = b.w; v.l[8] = rowp[8];
 }
-// nine lazy limbs (any value below 2^261) -> canonical fr_t
-__device__ __forceinline__ fr_t chain_canon(fr29_t v) {
-    carry29(v); lazy_reduce29<PF>(v);
-    uint32_t tt[9];
-#pragma unroll
-    for (int wd = 0; wd < 8; ++wd) {
-        const int lo = 32 * wd, i = lo / 29, sh = lo - 29 * i;
-        uint32_t x = v.l[i] >> sh;
-        if (i + 1 < 9) x |= v.l[i + 1] << (29 - sh);
-        if (29 - sh + 29 < 32 && i + 2 < 9) x |= v.l[i + 2] << (58 - sh);
-        tt[wd] = x;
-    }
-    tt[8] = 0;
-    fr_cond_sub<PF>(tt, 0u); fr_cond_sub<PF>(tt, 0u);
-    fr_t s;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s.v[i] = tt[i];
-    return s;
-}
-
 // State between the rounds of a sponge: ROW FORM on five waves — element e on row e & 3 of wave e >> 2, limb c on lane c of the row, lazily reduced
 // (limbs below 2^31, values below 11 r), never canonical inside a sponge.
 // One full round: all 17 S-boxes at once in row form, both factors of every product a row's own (three products of ~135 instructions + one LDS-crossbar
@@ -426,7 +407,7 @@ __device__ __forceinline__ void chain_sponge_ex(const PoseidonDev& P, const row:
     __syncthreads();
     if (threadIdx.x < 17 && (state_out || threadIdx.x == 0)) {
         fr29_t v; for (int i = 0; i < 9; ++i) v.l[i] = C.sfin[threadIdx.x * 16 + i];
-        fr_t s = chain_canon(v);
+        carry29(v); fr_t s = fr29_canon_lazy<PF>(v);
         if (lds_vload(C.flag + 3)) s = fr_zero<PF>();                    // a timed-out wait (never seen) must not pass for a digest
         if (state_out) stg(state_out + threadIdx.x, s);
         if (threadIdx.x == 0 && out_slot) stg(out_slot, s);
@@ -437,39 +418,25 @@ __device__ __forceinline__ void chain_sponge(const PoseidonDev& P, const row::Co
     chain_sponge_ex(P, RK, lds, total, cap, elem, out_slot, nullptr, true, nullptr);
 }
 
-// The column sponges of build_f0 (and any other long tr_hash_fields_tagged chain): one workgroup of five waves per chain.  Same job description as
-// k_tr_hash_coop_multi (block b: column b, or with J.batch column b & 3 of trace b >> 2).
-__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_hash_chain(PoseidonDev P, TrMultiJob J, row::Consts RK, fr_t* __restrict__ out) {
+// tr_hash_fields_tagged: one workgroup of five waves per sponge of the stream — the column sponges of build_f0, and any other long chain.
+__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_hash_chain(PoseidonDev P, TrStream T, row::Consts RK, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
-    const int b = blockIdx.x, c = J.batch ? (b & 3) : (J.stride ? 0 : b);
-    const fr_t* prefix = J.prefix[c]; const fr_t* suffix = J.suffix[c]; const fr_t* fields = J.batch ? J.batch[b] : (J.stride ? J.fields[0] + (size_t)b * J.stride : J.fields[c]);
-    const size_t np = J.np[c], kk = J.k[c], total = np + kk + (size_t)J.ns[c];
-    chain_sponge(P, RK, lds, total, J.cap, [&](size_t q) -> fr_t { return q < np ? ldg(prefix + q) : (q < np + kk ? ldg(fields + (q - np)) : ldg(suffix + (q - np - kk))); }, out + b);
+    const TrStream::Sponge sp = T.sponge(blockIdx.x);
+    chain_sponge(P, RK, lds, sp.total(), T.cap, [&](size_t q) -> fr_t { return sp.elem(q); }, out + blockIdx.x);
 }
 
 // SMALL Merkle levels and leaf layers, where the launch is one permutation's latency whatever the kernel: the same five waves per NODE (72 us per
-// permutation against 142 us on one wave and ~0.4 ms in the wave-pair throughput form).  Jobs as k_hash_ds_coop / k_leaf_pair2.
-__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_hash_ds_chain(PoseidonDev P, DsJob J, row::Consts RK, const fr_t* __restrict__ in0, const fr_t* __restrict__ in1, fr_t* __restrict__ out) {
+// permutation against 142 us on one wave and ~0.4 ms in the wave-pair throughput form).
+__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_hash_ds_chain(PoseidonDev P, DsStream D, row::Consts RK, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     const size_t k = blockIdx.x;
-    const size_t cnt = J.mode == 1 ? 2 : ((k + 1) * J.arity <= J.n_in ? J.arity : J.n_in - k * J.arity);
-    const size_t total = 4 + cnt + 1;                                                // ds || children || 1, zero padded
-    chain_sponge(P, RK, lds, total, fr_zero<PF>(), [&](size_t q) -> fr_t {
-        if (q == 0) return J.arity_f; if (q == 1) return J.level_f; if (q == 2) return fr_from_u64<PF>(ds_position(J, k)); if (q == 3) return J.label_f;
-        if (q == total - 1) return fr_one<PF>();
-        const size_t c = q - 4; return J.mode == 1 ? ds_pair_child(J, in0, in1, k, c) : ldg(in0 + k * J.arity + c);
-    }, out + k);
+    chain_sponge(P, RK, lds, D.total(k), fr_zero<PF>(), [&](size_t q) -> fr_t { return D.elem(k, q); }, out + k);
 }
-// hash_leaf_pair (fri.rs:38-44): init = the 17-element template of capi_core.hip ctx_leaf_init (elements 4, 5 are the slots of f_i and s_i, element 16 the capacity)
-__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_leaf_pair_chain(PoseidonDev P, row::Consts RK, const fr_t* __restrict__ init, const fr_t* __restrict__ f,
-                                                                                                   const fr_t* __restrict__ f_next, size_t m, fr_t* __restrict__ h) {
+// hash_leaf_pair (fri.rs:38-44), one leaf per five waves
+__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_leaf_pair_chain(PoseidonDev P, row::Consts RK, LeafStream L, fr_t* __restrict__ h) {
     extern __shared__ uint4 lds[];
     const size_t i = blockIdx.x;
-    chain_sponge(P, RK, lds, 9, ldg(init + 16), [&](size_t q) -> fr_t {
-        if (q == 4) return ldg(f + i);
-        if (q == 5) return f_next ? ldg(f_next + i / m) : fr_zero<PF>();
-        return ldg(init + q);
-    }, h + i);
+    chain_sponge(P, RK, lds, L.total(i), L.cap(), [&](size_t q) -> fr_t { return L.elem(i, q); }, h + i);
 }
 #endif
 

@@ -17,24 +17,13 @@
 #include "fr.hpp"
 #include "dev_common.hpp"
 #include "poseidon_params.hpp"
-#include "poseidon_dev.hpp"   // TrJob, c29
+#include "poseidon_dev.hpp"   // c29
+#include "poseidon_streams.hpp"
 #include "fr29.hpp"
 
 #if defined(__HIPCC__)
 namespace stark {
 
-__device__ __forceinline__ fr_t shfl_fr(const fr_t& x, int src) {
-    fr_t r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.v[i] = (uint32_t)__shfl((int)x.v[i], src, 64);
-    return r;
-}
-__device__ __forceinline__ fr_t shfl_down_fr(const fr_t& x, int d) {
-    fr_t r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.v[i] = (uint32_t)__shfl_down((int)x.v[i], d, 64);
-    return r;
-}
 // broadcast of one lane's element through SGPRs (v_readlane: no LDS-crossbar round trip); src is wave-uniform
 __device__ __forceinline__ fr_t bcast_fr(const fr_t& x, int src) {
     fr_t r;
@@ -76,17 +65,6 @@ __device__ __forceinline__ fr29_t add29(const fr29_t& a, const fr29_t& b) {     
 #pragma unroll
     for (int i = 0; i < 9; ++i) r.l[i] = a.l[i] + b.l[i];
     return r;
-}
-// value below 2^261 -> below 2r + epsilon, still >= 0: subtract k * r with k = floor(value / 2^254) - 1  (r = 2^254 + t, t < 2^126).
-// 64-bit signed limbs during the pass: k * r_i reaches 2^36.
-template <class F> __device__ __forceinline__ void lazy_reduce29(fr29_t& a) {
-    const uint32_t q = a.l[8] >> 22; const int64_t k = q ? (int64_t)q - 1 : 0;
-    int64_t carry = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const int64_t d = (int64_t)a.l[i] - k * (int64_t)fr_p29<F>(i) + carry;
-        if (i < 8) { a.l[i] = (uint32_t)d & FR_M29; carry = d >> 29; } else a.l[8] = (uint32_t)d;
-    }
 }
 template <class F> __device__ __forceinline__ fr29_t ld29(const uint32_t* p) {   // nine limbs of a table entry; p == nullptr: zero
     fr29_t r;
@@ -152,7 +130,7 @@ __device__ __forceinline__ void coop_full_round(fr_t& s, int r, const uint32_t* 
     }
     fr_t tot = part;
 #pragma unroll
-    for (int k = 1; k < NS; ++k) { fr_t o = shfl_fr(part, (lane + k * T) & 63); tot = fr_add<PF>(tot, o); }
+    for (int k = 1; k < NS; ++k) { fr_t o = shfl_idx_fr(part, (lane + k * T) & 63); tot = fr_add<PF>(tot, o); }
     if (elem) s = tot;
     __builtin_amdgcn_wave_barrier();
 }
@@ -229,104 +207,59 @@ __device__ __forceinline__ fr_t coop_permute(fr_t s, const PoseidonDev& P, const
     }
 #pragma unroll
     for (int i = 0; i < 9; ++i) sl.l[i] = lane == 0 ? s0l.l[i] : sl.l[i];
-    lazy_reduce29<PF>(sl);
-    {   // below 2r + epsilon: pack, then two conditional subtractions (the second one fires with probability ~2^-125)
-        uint32_t tt[9];
-#pragma unroll
-        for (int wd = 0; wd < 8; ++wd) {
-            const int lo = 32 * wd, i = lo / 29, sh = lo - 29 * i;
-            uint32_t v = sl.l[i] >> sh;
-            if (i + 1 < 9) v |= sl.l[i + 1] << (29 - sh);
-            if (29 - sh + 29 < 32 && i + 2 < 9) v |= sl.l[i + 2] << (58 - sh);
-            tt[wd] = v;
-        }
-        tt[8] = 0;
-        fr_cond_sub<PF>(tt, 0u); fr_cond_sub<PF>(tt, 0u);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s.v[i] = tt[i];
-    }
+    s = fr29_canon_lazy<PF>(sl);
     for (int r = half; r < P.rf; ++r) full_round(r, L.mds, true);
     return s;
 }
 
-// tr_hash_fields_tagged over the stream prefix || fields_i || suffix, one 64-lane block per hash i.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_hash_coop(PoseidonDev P, TrJob J, const fr_t* __restrict__ fields, fr_t* __restrict__ out) {
+// tr_hash_fields_tagged, one 64-lane block per sponge b of the stream (the lazy duplex: permute only before absorbing more, once at the end).
+// PREFETCH: the next rate block is loaded BEFORE the permutation, so that its HBM latency hides under it — the long column sponges (the
+// Columns / BatchColumns layouts).  It costs registers (189 VGPRs against 162): the Equal layout (many short sponges) launches the
+// instantiation without it, which keeps 3 waves per SIMD up to 4096 sponges.
+template <bool PREFETCH>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_hash_coop(PoseidonDev P, TrStream T, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     CoopLds L = coop_setup<17>(lds, P);
-    const int lane = threadIdx.x; const size_t i = blockIdx.x;
-    fr_t s = lane == 16 ? J.cap : fr_zero<PF>();
-    const size_t total = (size_t)J.np + J.k + (size_t)J.ns;
-    for (size_t base = 0; base < total; base += 16) {                                // one rate-16 block per iteration
-        if (base) s = coop_permute<17>(s, P, L, lane);                               // lazy permute: only before absorbing more
-        const size_t e = base + lane;
-        if (lane < 16 && e < total) {
-            fr_t x = e < (size_t)J.np ? ldg(J.prefix + e) : (e < (size_t)J.np + J.k ? ldg(fields + i * J.k + (e - J.np)) : ldg(J.suffix + (e - J.np - J.k)));
-            s = fr_add<PF>(s, x);
-        }
-    }
-    s = coop_permute<17>(s, P, L, lane);
-    if (lane == 0) stg(out + i, s);
-}
-
-// hash_leaf_pair (fri.rs:38-44), one wave per leaf: for layers too long for the five-wave kernel's one workgroup per CU and too short to fill the wave-pair
-// throughput kernel, whose launch takes 0.77 ms whatever its size (2049 .. 8192 leaves).  init = the 17-element template of capi_core.hip ctx_leaf_init.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_leaf_pair_coop(PoseidonDev P, const fr_t* __restrict__ init, const fr_t* __restrict__ f,
-                                                                                                 const fr_t* __restrict__ f_next, size_t m, fr_t* __restrict__ h) {
-    extern __shared__ uint4 lds[];
-    CoopLds L = coop_setup<17>(lds, P);
-    const int lane = threadIdx.x; const size_t i = blockIdx.x;
-    fr_t s = fr_zero<PF>();
-    if (lane < 17) s = lane == 4 ? ldg(f + i) : (lane == 5 ? (f_next ? ldg(f_next + i / m) : fr_zero<PF>()) : ldg(init + lane));
-    s = coop_permute<17>(s, P, L, lane);
-    if (lane == 0) stg(h + i, s);
-}
-
-// Up to 4 independent long sponges in ONE launch (one block each): the four column chains of build_f0.
-// With `batch` set, block b hashes column b & 3 of trace b >> 2 (stark_deep_fri_prove_batch_dev: the 4 * B chains of B independent traces
-// in one launch — each is serial, together they fill the chip); its fields pointer comes from the device array batch[b].
-// With `stride` set (and batch null), block b hashes the k[0] fields at fields[0] + b * stride under tag 0 (tr_hash_dev: n equal-length sponges).
-struct TrMultiJob { const fr_t* prefix[4]; int np[4]; const fr_t* suffix[4]; int ns[4]; const fr_t* fields[4]; size_t k[4]; fr_t cap; const fr_t* const* batch; size_t stride; };
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_hash_coop_multi(PoseidonDev P, TrMultiJob J, fr_t* __restrict__ out) {
-    extern __shared__ uint4 lds[];
-    CoopLds L = coop_setup<17>(lds, P);
-    const int lane = threadIdx.x, b = blockIdx.x, c = J.batch ? (b & 3) : (J.stride ? 0 : b);
-    const fr_t* prefix = J.prefix[c]; const fr_t* suffix = J.suffix[c]; const fr_t* fields = J.batch ? J.batch[b] : (J.stride ? J.fields[0] + (size_t)b * J.stride : J.fields[c]);
-    const size_t np = J.np[c], kk = J.k[c], total = np + kk + (size_t)J.ns[c];
-    fr_t s = lane == 16 ? J.cap : fr_zero<PF>();
+    const int lane = threadIdx.x; const size_t b = blockIdx.x;
+    const TrStream::Sponge sp = T.sponge(b); const size_t total = sp.total();
+    fr_t s = lane == 16 ? T.cap : fr_zero<PF>();
     auto fetch = [&](size_t base) -> fr_t {                                                // this lane's element of the rate block starting at `base`
         const size_t e = base + lane;
-        if (lane < 16 && e < total) return e < np ? ldg(prefix + e) : (e < np + kk ? ldg(fields + (e - np)) : ldg(suffix + (e - np - kk)));
-        return fr_zero<PF>();
+        return lane < 16 && e < total ? sp.elem(e) : fr_zero<PF>();
     };
-    fr_t nxt = fetch(0);
+    fr_t nxt = PREFETCH ? fetch(0) : fr_zero<PF>();
     for (size_t base = 0; base < total; base += 16) {
-        const fr_t cur = nxt;
-        if (base + 16 < total) nxt = fetch(base + 16);                                    // issued BEFORE the permutation: the HBM latency of the next block hides under it
+        const fr_t cur = PREFETCH ? nxt : fr_zero<PF>();
+        if (PREFETCH && base + 16 < total) nxt = fetch(base + 16);
         if (base) s = coop_permute<17>(s, P, L, lane);
-        s = fr_add<PF>(s, cur);
+        s = fr_add<PF>(s, PREFETCH ? cur : fetch(base));
     }
     s = coop_permute<17>(s, P, L, lane);
     if (lane == 0) stg(out + b, s);
 }
 
-// One Merkle node per wave (small levels: latency matters, not throughput).  Same job as k_hash_ds.
+// hash_leaf_pair (fri.rs:38-44), one wave per leaf: for layers too long for the five-wave kernel's one workgroup per CU and too short to fill the wave-pair
+// throughput kernel, whose launch takes 0.77 ms whatever its size (2049 .. 8192 leaves).
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_leaf_pair_coop(PoseidonDev P, LeafStream LS, fr_t* __restrict__ h) {
+    extern __shared__ uint4 lds[];
+    CoopLds L = coop_setup<17>(lds, P);
+    const int lane = threadIdx.x; const size_t i = blockIdx.x;
+    fr_t s = fr_zero<PF>();
+    if (lane < 9) s = LS.elem(i, lane); else if (lane == 16) s = LS.cap();
+    s = coop_permute<17>(s, P, L, lane);
+    if (lane == 0) stg(h + i, s);
+}
+
+// One Merkle node per wave (small levels: latency matters, not throughput).
 template <int T>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_hash_ds_coop(PoseidonDev P, DsJob J, const fr_t* __restrict__ in0, const fr_t* __restrict__ in1, fr_t* __restrict__ out) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_hash_ds_coop(PoseidonDev P, DsStream D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     CoopLds L = coop_setup<T>(lds, P);
-    const int lane = threadIdx.x, rate = T - 1; const size_t k = blockIdx.x;
-    const size_t cnt = J.mode == 1 ? 2 : ((k + 1) * J.arity <= J.n_in ? J.arity : J.n_in - k * J.arity);
-    const size_t total = 4 + cnt + 1;                                                // ds || children || 1, zero padded
+    const int lane = threadIdx.x, rate = T - 1; const size_t k = blockIdx.x, total = D.total(k);
     fr_t s = fr_zero<PF>();
     for (size_t base = 0; base < total; base += rate) {                              // eager sponge: permute after every full (or final) block
         const size_t q = base + lane;
-        if (lane < rate && q < total) {
-            fr_t x;
-            if (q == 0) x = J.arity_f; else if (q == 1) x = J.level_f; else if (q == 2) x = fr_from_u64<PF>(ds_position(J, k)); else if (q == 3) x = J.label_f;
-            else if (q == total - 1) x = fr_one<PF>();
-            else { size_t c = q - 4; x = J.mode == 1 ? ds_pair_child(J, in0, in1, k, c) : ldg(in0 + k * J.arity + c); }
-            s = fr_add<PF>(s, x);
-        }
+        if (lane < rate && q < total) s = fr_add<PF>(s, D.elem(k, q));
         s = coop_permute<T>(s, P, L, lane);
     }
     if (lane == 0) stg(out + k, s);

@@ -22,10 +22,9 @@
 #include "fr29.hpp"
 #include "dev_common.hpp"
 #include "poseidon_params.hpp"
+#include "poseidon_streams.hpp"
 
 namespace stark {
-
-typedef PallasFr PF;   // the prover field
 
 // Plain-array state (host-check library).
 struct ArrayState {
@@ -119,54 +118,35 @@ template <class S> FR_HD fr_t permute_core(const S& s, const PoseidonDev& P, boo
     return s.ld(0);
 }
 
-// ---- sponge bodies (one call = the work of one lane) ---------------------------------------------------
-// hash_leaf_pair(f, s): one t=17 permutation of the constant template `init`
-// with lanes 4,5 = (f, s).
-template <class S> FR_HD fr_t leaf_pair_body(const S& s, const PoseidonDev& P, const fr_t* init, const fr_t& f, const fr_t& sv) {
-    for (int j = 0; j < 17; ++j) s.st(j, init[j]);
-    s.st(4, f); s.st(5, sv);
+// ---- sponge bodies (one call = the work of one lane; the streams of poseidon_streams.hpp) ----------------------
+// hash_leaf_pair: one permutation of the template with elements 4, 5 = (f_i, s_i).
+template <class S> FR_HD fr_t leaf_pair_body(const S& s, const PoseidonDev& P, const LeafStream& L, size_t i) {
+    for (int j = 0; j < 16; ++j) s.st(j, j < 9 ? L.elem(i, j) : fr_zero<PF>());
+    s.st(16, L.cap());
     return permute_core(s, P, true);
 }
-// hash_with_ds_dynamic([arity, level, pos0+k, label], children_k)  (merkle/src/lib.rs:167-176).
-//   mode 0 (node level): children_k = in0[k*arity .. min((k+1)*arity, n_in))
-//   mode 1 (pair leaf) : children_k = {in0[k], in1[k / cp_div]}  (merkle/src/lib.rs:380-388); in1 == nullptr: the second
-//                        child is zero (fri.rs:266).  cp_div = m serves commit_pairs(f_l, s_l) with s_l the view f_{l+1}[i/m].
-//   pos_list != nullptr: hash k carries DS position pos_list[k] instead of pos0 + k (the verifier's union-of-paths levels, whose
-//                        parents are scattered; merkle/src/lib.rs:683-689).
-struct DsJob { fr_t arity_f, level_f, label_f; uint64_t pos0; size_t arity, n_in, n_out; int mode; size_t cp_div = 1; const uint64_t* pos_list = nullptr; };
-FR_HD uint64_t ds_position(const DsJob& J, size_t k) { return J.pos_list ? J.pos_list[k] : J.pos0 + k; }
-FR_HD fr_t ds_pair_child(const DsJob& J, const fr_t* in0, const fr_t* in1, size_t k, size_t c) {
-    if (c == 0) return ldg(in0 + k);
-    return in1 ? ldg(in1 + k / J.cp_div) : fr_zero<PF>();
-}
-template <class S> FR_HD fr_t hash_ds_body(const S& s, const PoseidonDev& P, const DsJob& J, const fr_t* in0, const fr_t* in1, size_t k) {
+// hash_with_ds_dynamic: eager sponge (permute after every full rate block and after the final one).
+template <class S> FR_HD fr_t hash_ds_body(const S& s, const PoseidonDev& P, const DsStream& D, size_t k) {
     const int t = P.t, rate = t - 1;
     for (int j = 0; j < t; ++j) s.st(j, fr_zero<PF>());
-    size_t cnt = J.mode == 1 ? 2 : ((k + 1) * J.arity <= J.n_in ? J.arity : J.n_in - k * J.arity);
-    size_t total = 4 + cnt + 1;                       // ds || children || 1, then implicit zero padding
+    const size_t total = D.total(k);
     size_t nperm = (total + rate - 1) / rate, done = 0;
     int cur = 0; fr_t res = fr_zero<PF>();
     for (size_t q = 0; q < total; ++q) {
-        fr_t x;
-        if (q == 0) x = J.arity_f; else if (q == 1) x = J.level_f; else if (q == 2) x = fr_from_u64<PF>(ds_position(J, k)); else if (q == 3) x = J.label_f;
-        else if (q == total - 1) x = fr_one<PF>();
-        else { size_t c = q - 4; x = J.mode == 1 ? ds_pair_child(J, in0, in1, k, c) : ldg(in0 + k * J.arity + c); }
-        s.st(cur, fr_add<PF>(s.ld(cur), x));
+        s.st(cur, fr_add<PF>(s.ld(cur), D.elem(k, q)));
         if (++cur == rate) { cur = 0; ++done; res = permute_core(s, P, done == nperm); }
     }
     if (cur != 0) res = permute_core(s, P, true);
     return res;
 }
-// Transcript-style duplex (t=17, rate 16, lazy permute) over the stream  prefix || fields_i || suffix,
-// state[16] = cap.  Covers tr_hash_fields_tagged (fri.rs:28-35).
-struct TrJob { const fr_t* prefix; int np; const fr_t* suffix; int ns; fr_t cap; size_t k; size_t n; };
-template <class S> FR_HD fr_t tr_hash_body(const S& s, const PoseidonDev& P, const TrJob& J, const fr_t* fields, size_t i) {
+// Transcript-style duplex (t=17, rate 16, lazy permute: only before absorbing more, once at the end), state[16] = cap.
+template <class S> FR_HD fr_t tr_hash_body(const S& s, const PoseidonDev& P, const TrStream& T, size_t i) {
     for (int j = 0; j < 16; ++j) s.st(j, fr_zero<PF>());
-    s.st(16, J.cap);
-    const size_t total = (size_t)J.np + J.k + (size_t)J.ns;
+    s.st(16, T.cap);
+    const TrStream::Sponge sp = T.sponge(i);
     int pos = 0;
-    for (size_t q = 0; q < total; ++q) {
-        fr_t x = q < (size_t)J.np ? J.prefix[q] : (q < (size_t)J.np + J.k ? ldg(fields + i * J.k + (q - J.np)) : J.suffix[q - J.np - J.k]);
+    for (size_t q = 0; q < sp.total(); ++q) {
+        const fr_t x = sp.elem(q);
         if (pos == 16) { permute_core(s, P, false); pos = 0; }
         s.st(pos, fr_add<PF>(s.ld(pos), x)); ++pos;
     }
@@ -212,22 +192,21 @@ struct LdsState {
     }
 };
 // ---- kernels ---------------------------------------------------------------------------------------
-// K3: h[i] = hash_leaf_pair(f[i], s_i), s_i = f_next[i/m] (zero when f_next == nullptr: fri.rs:266).
-__global__ void __launch_bounds__(64) k_leaf_pair(PoseidonDev P, const fr_t* __restrict__ init, const fr_t* __restrict__ f,
-                                                  const fr_t* __restrict__ f_next, size_t n, size_t m, fr_t* __restrict__ h) {
+// K3: h[i] = hash_leaf_pair(f[i], s_i).
+__global__ void __launch_bounds__(64) k_leaf_pair(PoseidonDev P, LeafStream L, fr_t* __restrict__ h) {
     extern __shared__ uint4 lds[];
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= L.n) return;
     LdsState s{lds, (int)blockDim.x, (int)threadIdx.x};
-    stg(h + i, leaf_pair_body(s, P, init, ldg(f + i), f_next ? ldg(f_next + i / m) : fr_zero<PF>()));
+    stg(h + i, leaf_pair_body(s, P, L, i));
 }
 // K4: one Merkle level / the pair-leaf level.
-__global__ void __launch_bounds__(64) k_hash_ds(PoseidonDev P, DsJob J, const fr_t* __restrict__ in0, const fr_t* __restrict__ in1, fr_t* __restrict__ out) {
+__global__ void __launch_bounds__(64) k_hash_ds(PoseidonDev P, DsStream D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= J.n_out) return;
+    if (k >= D.n_out) return;
     LdsState s{lds, (int)blockDim.x, (int)threadIdx.x};
-    stg(out + k, hash_ds_body(s, P, J, in0, in1, k));
+    stg(out + k, hash_ds_body(s, P, D, k));
 }
 // permute / permute_dynamic over a batch of AoS states (poseidon/src/lib.rs:31,219).
 __global__ void __launch_bounds__(64) k_permute_batch(PoseidonDev P, fr_t* __restrict__ states, size_t n) {
@@ -241,12 +220,12 @@ __global__ void __launch_bounds__(64) k_permute_batch(PoseidonDev P, fr_t* __res
 }
 // Batch of independent transcript hashes (index seeds, z seeds); with n == 1 a whole column
 // (the serial sponge of build_f0, fri.rs:551-554).
-__global__ void __launch_bounds__(64) k_tr_hash(PoseidonDev P, TrJob J, const fr_t* __restrict__ fields, fr_t* __restrict__ out) {
+__global__ void __launch_bounds__(64) k_tr_hash(PoseidonDev P, TrStream T, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= J.n) return;
+    if (i >= T.n) return;
     LdsState s{lds, (int)blockDim.x, (int)threadIdx.x};
-    stg(out + i, tr_hash_body(s, P, J, fields, i));
+    stg(out + i, tr_hash_body(s, P, T, i));
 }
 __global__ void __launch_bounds__(64) k_hash_stream(PoseidonDev P, int mode, const fr_t* __restrict__ a, size_t na, const fr_t* __restrict__ b, size_t nb,
                                                     fr_t tag, size_t n, fr_t* __restrict__ out) {

@@ -24,7 +24,8 @@
 #include "fr.hpp"
 #include "dev_common.hpp"
 #include "poseidon_params.hpp"
-#include "poseidon_dev.hpp"   // DsJob
+#include "poseidon_dev.hpp"
+#include "poseidon_streams.hpp"
 
 #if defined(__HIPCC__)
 namespace stark {
@@ -314,24 +315,23 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
     if (live && !s.isY) stg(h + i, out);
 }
 
-// K4 (pair form): one Merkle level / the pair-leaf level (DsJob as in poseidon_dev.hpp).
+// K4 (pair form): one Merkle level / the pair-leaf level.
 template <int T>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_hash_ds2(PoseidonDev P, DsJob J, const fr_t* __restrict__ in0, const fr_t* __restrict__ in1, fr_t* __restrict__ out) {
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_hash_ds2(PoseidonDev P, DsStream D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     constexpr int rate = T - 1;
     PairState s = pair_setup(lds);
-    const size_t k0 = (size_t)blockIdx.x * 64 + s.lane; const bool live = k0 < J.n_out; const size_t k = live ? k0 : J.n_out - 1;
+    const size_t k0 = (size_t)blockIdx.x * 64 + s.lane; const bool live = k0 < D.n_out; const size_t k = live ? k0 : D.n_out - 1;
     const int o0 = s.isY ? PairCfg<T>::NX : 0, o1 = s.isY ? T : PairCfg<T>::NX;      // elements this wave fills / absorbs into
     for (int j = o0; j < o1; ++j) s.sto(j, fr_zero<PF>());
     __syncthreads();
-    const size_t cnt = J.mode == 1 ? 2 : ((k + 1) * J.arity <= J.n_in ? J.arity : J.n_in - k * J.arity);
-    const size_t total = 4 + cnt + 1, nperm = (total + rate - 1) / rate;
+    const size_t total = D.total(k), nperm = (total + rate - 1) / rate;
     // The widest stream in the block decides how many permutations every lane walks through (barriers are wave-level: both waves
     // of the pair must execute the same sequence).  A lane with a SHORTER stream (the ragged last node of a level) sits out the
     // first max_perm - nperm of them — it permutes a dead state, clears it, and starts absorbing late — so that EVERY lane's result
     // is lane 0 of the last permutation: nothing has to be carried in registers across the permutations (the kernel sits at the
     // 256-VGPR limit; carrying a per-lane result across pair_permute spilled 118 VGPRs to scratch).
-    const size_t max_total = 4 + (J.mode == 1 ? 2 : J.arity) + 1, max_perm = (max_total + rate - 1) / rate;
+    const size_t max_perm = (D.max_total() + rate - 1) / rate;
     const size_t skip = max_perm - nperm;
     size_t q = 0; fr_t res = fr_zero<PF>();
     for (size_t pidx = 0; pidx < max_perm; ++pidx) {
@@ -339,11 +339,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
             if (skip && pidx == skip) for (int j = o0; j < o1; ++j) s.sto(j, fr_zero<PF>());       // the dead permutations left garbage behind
             for (int cur = 0; cur < rate && q < total; ++cur, ++q) {
                 if (cur < o0 || cur >= o1) continue;
-                fr_t x;
-                if (q == 0) x = J.arity_f; else if (q == 1) x = J.level_f; else if (q == 2) x = fr_from_u64<PF>(ds_position(J, k)); else if (q == 3) x = J.label_f;
-                else if (q == total - 1) x = fr_one<PF>();
-                else { size_t c = q - 4; x = J.mode == 1 ? ds_pair_child(J, in0, in1, k, c) : ldg(in0 + k * J.arity + c); }
-                s.sto(cur, fr_add<PF>(s.ld(cur), x));
+                s.sto(cur, fr_add<PF>(s.ld(cur), D.elem(k, q)));
             }
         }
         __syncthreads();

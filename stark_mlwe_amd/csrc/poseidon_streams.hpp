@@ -1,0 +1,88 @@
+// stark_mlwe_amd/csrc/poseidon_streams.hpp — what the Poseidon sponges absorb, written once for every kernel form (host and device).
+//
+// A stream describes a batch of sponges: sponge k absorbs total(k) elements, element q read by elem(k, q), into a state whose capacity
+// element starts as the stream's `cap` (TrStream resolves sponge k first: sponge(k).total(), sponge(k).elem(q)).  The lane bodies (poseidon_dev.hpp, also instantiated on the host by the host-check library), the
+// one-wave (poseidon_coop.hpp), wave-pair (poseidon_pair.hpp), five-wave (poseidon_chain.hpp) and wide (poseidon_wave.hpp) kernels all read
+// their inputs through these types; only the absorb schedule (eager or lazy permute) and the arithmetic differ between them.
+#pragma once
+#include "fr.hpp"
+#include "dev_common.hpp"
+
+namespace stark {
+
+typedef PallasFr PF;   // the prover field
+
+// hash_with_ds_dynamic([arity, level, pos0 + k, label] || children_k || 1)  (merkle/src/lib.rs:167-176), eager sponge, zero padded, cap 0.
+//   mode 0 (node level): children_k = in0[k*arity .. min((k+1)*arity, n_in))  (the last node of a level may be ragged)
+//   mode 1 (pair leaf) : children_k = {in0[k], in1[k / cp_div]}  (merkle/src/lib.rs:380-388); in1 == nullptr: the second child is zero
+//                        (fri.rs:266).  cp_div = m serves commit_pairs(f_l, s_l) with s_l the view f_{l+1}[i/m].
+//   pos_list != nullptr: hash k carries DS position pos_list[k] instead of pos0 + k (the verifier's union-of-paths levels, whose parents are
+//                        scattered; merkle/src/lib.rs:683-689).
+//   chunk != 0         : `chunk` children per hash while the DS field stays `arity` (the verifier's groups: a short last chunk of the proof's level).
+struct DsStream {
+    fr_t arity_f, level_f, label_f; uint64_t pos0; size_t arity, n_in, n_out; int mode; size_t cp_div; const uint64_t* pos_list;
+    const fr_t* in0; const fr_t* in1;
+    static inline DsStream make(int mode, size_t arity, uint32_t level, uint64_t pos0, uint64_t label, const fr_t* in0, const fr_t* in1, size_t n_in,
+                                size_t cp_div = 1, const uint64_t* pos_list = nullptr, size_t chunk = 0) {
+        DsStream D;
+        D.arity_f = fr_from_u64<PF>(arity); D.level_f = fr_from_u64<PF>(level); D.label_f = fr_from_u64<PF>(label); D.pos0 = pos0;
+        D.arity = chunk ? chunk : arity; D.n_in = n_in; D.mode = mode; D.cp_div = cp_div ? cp_div : 1; D.pos_list = pos_list; D.in0 = in0; D.in1 = in1;
+        D.n_out = mode == 1 ? n_in : (n_in + D.arity - 1) / D.arity;
+        return D;
+    }
+    FR_HD uint64_t position(size_t k) const { return pos_list ? pos_list[k] : pos0 + k; }
+    FR_HD size_t total(size_t k) const { return 4 + (mode == 1 ? 2 : ((k + 1) * arity <= n_in ? arity : n_in - k * arity)) + 1; }
+    FR_HD size_t max_total() const { return 4 + (mode == 1 ? 2 : arity) + 1; }      // the widest sponge of the batch
+    FR_HD fr_t elem(size_t k, size_t q) const {
+        if (q < 4) return q == 0 ? arity_f : (q == 1 ? level_f : (q == 2 ? fr_from_u64<PF>(position(k)) : label_f));
+        if (q == total(k) - 1) return fr_one<PF>();
+        const size_t c = q - 4;
+        if (mode == 1) return c == 0 ? ldg(in0 + k) : (in1 ? ldg(in1 + k / cp_div) : fr_zero<PF>());
+        return ldg(in0 + k * arity + c);
+    }
+};
+
+// tr_hash_fields_tagged (fri.rs:28-35): the stream prefix || fields || suffix under the capacity FSv1-TRANSCRIPT-INIT (lazy duplex,
+// transcript/src/lib.rs:79-101).  Frames (prefix, suffix) per column c < 4; the layout says which sponge reads which frame and fields:
+//   Equal        : n sponges of k[0] fields at fields[0] + b * k[0], all under column 0's frame (one tag)
+//   Columns      : sponge b < 4 is column b, fields[b] (k[b] of them)
+//   BatchColumns : sponge b is column b & 3 of trace b >> 2, its k[b & 3] fields at batch[b] (a device array of device pointers)
+struct TrStream {
+    enum Layout { Equal, Columns, BatchColumns };
+    Layout layout; size_t n;
+    const fr_t* prefix[4]; int np[4]; const fr_t* suffix[4]; int ns[4]; const fr_t* fields[4]; size_t k[4];
+    const fr_t* const* batch; fr_t cap;
+    // n sponges of k fields each under one frame (frame = prefix || suffix, np + ns elements)
+    static inline TrStream equal(const fr_t* frame, int np, int ns, const fr_t* fields, size_t k, size_t n, const fr_t& cap) {
+        TrStream T{}; T.layout = Equal; T.n = n; T.cap = cap; T.batch = nullptr;
+        T.prefix[0] = frame; T.np[0] = np; T.suffix[0] = frame + np; T.ns[0] = ns; T.fields[0] = fields; T.k[0] = k;
+        return T;
+    }
+    // sponge b with its frame and fields resolved: kernels take this once per sponge, outside their absorb loops
+    struct Sponge {
+        const fr_t* prefix; const fr_t* fields; const fr_t* suffix; size_t np, k, n_total;
+        FR_HD size_t total() const { return n_total; }
+        FR_HD fr_t elem(size_t q) const { return q < np ? ldg(prefix + q) : (q < np + k ? ldg(fields + (q - np)) : ldg(suffix + (q - np - k))); }
+    };
+    FR_HD Sponge sponge(size_t b) const {
+        const int c = layout == Equal ? 0 : (int)(b & 3);
+        const fr_t* f = layout == Equal ? fields[0] + b * k[0] : (layout == Columns ? fields[b] : batch[b]);
+        return Sponge{prefix[c], f, suffix[c], (size_t)np[c], k[c], (size_t)np[c] + k[c] + (size_t)ns[c]};
+    }
+};
+
+// hash_leaf_pair(f_i, s_i) (fri.rs:38-44): ONE t = 17 permutation of the template `init` (capi_core.hip ctx_leaf_init)
+// with elements 4, 5 = (f[i], s_i), s_i = f_next[i / m] (zero when f_next == nullptr: fri.rs:266).  Elements 0..8 are the absorbed ones,
+// 9..15 of the template are zero, element 16 is the capacity.
+struct LeafStream {
+    const fr_t* init; const fr_t* f; const fr_t* f_next; size_t m, n;
+    FR_HD size_t total(size_t) const { return 9; }
+    FR_HD fr_t cap() const { return ldg(init + 16); }
+    FR_HD fr_t elem(size_t i, size_t q) const {
+        if (q == 4) return ldg(f + i);
+        if (q == 5) return f_next ? ldg(f_next + i / m) : fr_zero<PF>();
+        return ldg(init + q);
+    }
+};
+
+}  // namespace stark

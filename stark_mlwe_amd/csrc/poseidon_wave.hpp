@@ -16,8 +16,8 @@
 #include "fr29.hpp"
 #include "dev_common.hpp"
 #include "poseidon_params.hpp"
-#include "poseidon_dev.hpp"    // DsJob, ds_position
-#include "poseidon_coop.hpp"   // nine-limb helpers (add29, carry29, lazy_reduce29, shfl_xor29)
+#include "poseidon_streams.hpp"
+#include "poseidon_coop.hpp"   // nine-limb helpers (add29, carry29, shfl_xor29)
 
 #if defined(__HIPCC__)
 namespace stark {
@@ -119,23 +119,17 @@ __device__ __forceinline__ void wave_permute(const WaveLds& L, const PoseidonDev
 
 // K4 (wave form): one Merkle node per wave — hash_with_ds_dynamic([arity, level, position, label], children), eager sponge of rate T - 1.
 template <int T>
-__global__ void __launch_bounds__(64) k_hash_ds_wave(PoseidonDev P, DsJob J, const fr_t* __restrict__ in0, const fr_t* __restrict__ in1, fr_t* __restrict__ out) {
+__global__ void __launch_bounds__(64) k_hash_ds_wave(PoseidonDev P, DsStream D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     WaveLds L; L.st = reinterpret_cast<uint32_t*>(lds); L.x = L.st + T * 9; L.part = L.x + T * 9;
-    const int lane = threadIdx.x, rate = T - 1; const size_t k = blockIdx.x;
-    const size_t cnt = J.mode == 1 ? 2 : ((k + 1) * J.arity <= J.n_in ? J.arity : J.n_in - k * J.arity);
-    const size_t total = 4 + cnt + 1;                                                // ds || children || 1, zero padded
+    const int lane = threadIdx.x, rate = T - 1; const size_t k = blockIdx.x, total = D.total(k);
     for (int e = lane; e < T; e += 64) { fr29_t z; _Pragma("unroll") for (int i = 0; i < 9; ++i) z.l[i] = 0; wv_st(L.st + 9 * e, z); }
     wv_sync();
     for (size_t base = 0; base < total; base += rate) {                              // eager sponge: permute after every full (or final) block
         for (int cur = lane; cur < rate; cur += 64) {
             const size_t q = base + cur;
             if (q < total) {
-                fr_t x;
-                if (q == 0) x = J.arity_f; else if (q == 1) x = J.level_f; else if (q == 2) x = fr_from_u64<PF>(ds_position(J, k)); else if (q == 3) x = J.label_f;
-                else if (q == total - 1) x = fr_one<PF>();
-                else { const size_t c = q - 4; x = J.mode == 1 ? ds_pair_child(J, in0, in1, k, c) : ldg(in0 + k * J.arity + c); }
-                fr29_t s = add29(wv_ld(L.st + 9 * cur), fr29_unpack(x)); carry29(s);
+                fr29_t s = add29(wv_ld(L.st + 9 * cur), fr29_unpack(D.elem(k, q))); carry29(s);
                 wv_st(L.st + 9 * cur, s);
             }
         }
@@ -143,19 +137,8 @@ __global__ void __launch_bounds__(64) k_hash_ds_wave(PoseidonDev P, DsJob J, con
         wave_permute<T>(L, P, lane);
     }
     if (lane == 0) {
-        fr29_t v = wv_ld(L.st); carry29(v); lazy_reduce29<PF>(v);
-        uint32_t tt[9];
-#pragma unroll
-        for (int wd = 0; wd < 8; ++wd) {
-            const int lo = 32 * wd, i = lo / 29, sh = lo - 29 * i;
-            uint32_t xw = v.l[i] >> sh;
-            if (i + 1 < 9) xw |= v.l[i + 1] << (29 - sh);
-            if (29 - sh + 29 < 32 && i + 2 < 9) xw |= v.l[i + 2] << (58 - sh);
-            tt[wd] = xw;
-        }
-        tt[8] = 0;
-        fr_cond_sub<PF>(tt, 0u); fr_cond_sub<PF>(tt, 0u);
-        fr_t s; _Pragma("unroll") for (int i = 0; i < 8; ++i) s.v[i] = tt[i];
+        fr29_t v = wv_ld(L.st); carry29(v);
+        const fr_t s = fr29_canon_lazy<PF>(v);
         stg(out + k, s);
     }
 }

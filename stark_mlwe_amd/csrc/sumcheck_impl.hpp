@@ -112,11 +112,10 @@ struct DevTranscript {
     int32_t run(bool finish, fr_t* result) {
         DevBuf f; const size_t n = pending.size();
         if (n) { STARK_HIP(ctx, f.alloc(ctx, n * sizeof(fr_t))); STARK_HIP(ctx, hipMemcpyAsync(f.p, pending.data(), n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream)); }
-        if (use_chain(ctx, tp->dev, 1, 1)) {
-            (void)hipFuncSetAttribute((const void*)k_tr_stream_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+        if (poseidon_form(ctx, tp, PoseidonOp::DeviceTranscript, 1) == PoseidonForm::FiveWave)
             hipLaunchKernelGGL(k_tr_stream_chain, dim3(1), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, row_consts_of(ctx), state.fr(), (uint32_t*)posb.p, (const fr_t*)f.fr(), (uint64_t)n, finish ? 1 : 0, finish ? out.fr() : (fr_t*)nullptr);
-        } else
-        hipLaunchKernelGGL(k_tr_stream, dim3(1), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, state.fr(), (uint32_t*)posb.p, (const fr_t*)f.fr(), (uint64_t)n, finish ? 1 : 0, finish ? out.fr() : (fr_t*)nullptr);
+        else
+            hipLaunchKernelGGL(k_tr_stream, dim3(1), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, state.fr(), (uint32_t*)posb.p, (const fr_t*)f.fr(), (uint64_t)n, finish ? 1 : 0, finish ? out.fr() : (fr_t*)nullptr);
         STARK_HIP(ctx, hipGetLastError());
         if (finish && result) STARK_HIP(ctx, hipMemcpyAsync(result, out.p, sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
         STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));                                 // `pending` is host memory; a challenge is needed on the host anyway

@@ -102,6 +102,11 @@ def test_tr_hash_body(oracle, hostcheck):
     got = hostcheck.tr_hash(h, b"FRI/index", batch, n=5)
     for i in range(5):
         assert (got[i] == oracle.tr_hash_fields_tagged(b"FRI/index", batch[3 * i:3 * i + 3])).all()
+    # k = 0, n = 5: five equal sponges of no fields, every one under the same frame (the Equal layout of TrStream)
+    empty = oracle.tr_hash_fields_tagged(b"FRI/index", np.zeros((0, 4), np.uint64))
+    got = hostcheck.tr_hash(h, b"FRI/index", np.zeros((0, 4), np.uint64), n=5)
+    for i in range(5):
+        assert (got[i] == empty).all()
     hostcheck.params_free(h)
 
 
