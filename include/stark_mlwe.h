@@ -55,6 +55,7 @@ typedef struct stark_fri_state stark_fri_state_t;
 typedef struct stark_proof stark_proof_t;
 typedef struct stark_fri_plan stark_fri_plan_t;
 typedef struct stark_transcript stark_transcript_t;
+typedef struct stark_fri_shard stark_fri_shard_t;
 
 /* ---- context / memory ------------------------------------------------------------------------- */
 int32_t stark_version(void);
@@ -276,6 +277,46 @@ size_t  stark_fri_plan_num_requests(stark_fri_plan_t* p);
 int32_t stark_fri_plan_requests(stark_fri_plan_t* p, uint32_t* kind, uint32_t* which, uint32_t* level, uint64_t* index);
 int32_t stark_fri_plan_assemble(stark_fri_plan_t* p, const uint64_t* values, size_t n_values, stark_proof_t** out);
 int32_t stark_fri_plan_free(stark_fri_plan_t* p);
+/* The commit and query phases of a sharded deep_fri_prove as ONE collective call each (stark_mlwe_amd/dist.py's DistProver behind the boundary), so
+ * that a host without Python drives a multi-GPU prove with one call per prove.  W = stark_comm_size of the context's communicator, or 1 when
+ * stark_comm_init was never called; rank q holds the natural-order rows [q*n0/W, (q+1)*n0/W).  Collective calls must be made by every rank with
+ * the same (n0, schedule, r, seed_z): every argument check happens before the first collective, and the first collective all-gathers a small
+ * header of those values — when any two ranks' headers differ, EVERY rank returns STARK_ERR_INVALID_ARG (nobody is left waiting).  Every rank
+ * issues the same sequence of collectives whatever its local data.
+ *  - stark_fri_build_sharded_dev: fri_build_transcript (fri.rs:231-312) over the ranks.  Layers are folded block-locally while they stay
+ *    shardable (hashed arity, whole Merkle and fold groups per block: stark_fri_shard_layout); the first layer that is not is all-gathered once and
+ *    every later layer is replicated and committed as on one GPU (commit_pairs for arities that are not hashed).  A sharded layer's leaf
+ *    hashes and lower Merkle levels are block-local with global DS positions (merkle/src/lib.rs:164-179, first_pos = q*n_l/W); the one level
+ *    that crosses rank boundaries is all-gathered and every rank finishes the top identically.  Returns a handle whose L+1 roots are the same
+ *    on every rank and equal stark_fri_build_dev's on the whole f0.
+ *  - stark_fri_shard_prove_queries: fri_prove_queries + encoding (fri.rs:355-466, 613-640).  Every rank derives the plan from the roots; each
+ *    fills the values it owns into a device table (zeros elsewhere), one stark_comm_all_reduce_u64_dev completes it, one download, and every
+ *    rank receives the same canonical proof bytes.
+ *  - stark_deep_fri_prove_sharded_dev: deep_fri_prove (fri.rs:601-641) from this rank's blocks of a, s, e, t: build_f0 (fri.rs:535-569; column c
+ *    is gathered to rank c mod W for its serial sponge, the four digests are all-reduced, the merge is block-local), the commit, the queries.
+ *    f0_opt (this rank's block of f0) skips build_f0 as in stark_deep_fri_prove_dev.  stark_proof_stage_ms 0/1/2 are filled.  At W = 1 the bytes
+ *    equal stark_deep_fri_prove_dev's.
+ *  - stark_diag_*_emulated_dev: diagnostic twins that run the same phase code for `nranks` VIRTUAL ranks on this one GPU, every collective as
+ *    device copies (as stark_diag_lde_sharded_emulated_dev).  Inputs are the WHOLE vectors.  roots_out: nranks x (L+1) x 4 words, the roots as
+ *    every virtual rank sees them; out: a host array of nranks proof handles, one per virtual rank.
+ *  - stark_fri_shard_layout: the planner the calls above use (host-only, no context): sharded[l] = 1 when layer l stays block-local over nranks
+ *    ranks, stop_len[l] = the local length of the level at which its lower tree stops (1 for a replicated layer, whose tree is built to its
+ *    root on every rank); STARK_ERR_INVALID_ARG when nranks is not a power of two, does not divide n0, or the schedule does not divide n0.
+ * STATUS: W > 1 has run only as the emulation (no multi-GPU node was available to the build). */
+int32_t stark_fri_build_sharded_dev(stark_ctx_t* ctx, const uint64_t* f0_block, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_shard_t** out);
+int32_t stark_fri_shard_num_layers(stark_fri_shard_t* h);
+int32_t stark_fri_shard_root(stark_fri_shard_t* h, int32_t l, uint64_t* out4);
+int32_t stark_fri_shard_is_sharded(stark_fri_shard_t* h, int32_t l);
+int32_t stark_fri_shard_free(stark_fri_shard_t* h);
+int32_t stark_fri_shard_prove_queries(stark_fri_shard_t* h, size_t r, stark_proof_t** out);
+int32_t stark_deep_fri_prove_sharded_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, const uint64_t* f0_opt, size_t n0,
+                                         const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out);
+int32_t stark_diag_fri_build_sharded_emulated_dev(stark_ctx_t* ctx, int32_t nranks, const uint64_t* f0_whole, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z,
+                                                  uint64_t* roots_out);
+int32_t stark_diag_deep_fri_prove_sharded_emulated_dev(stark_ctx_t* ctx, int32_t nranks, const uint64_t* a_whole, const uint64_t* s_whole, const uint64_t* e_whole,
+                                                       const uint64_t* t_whole, const uint64_t* f0_opt_whole, size_t n0, const size_t* schedule, size_t L, size_t r,
+                                                       uint64_t seed_z, stark_proof_t** out);
+int32_t stark_fri_shard_layout(size_t n0, const size_t* schedule, size_t L, int32_t nranks, int32_t* sharded, size_t* stop_len);
 
 /* ---- field helpers (crates/field/src/lib.rs) ------------------------------------------------------ */
 /* F::get_root_of_unity(2^log_n) — Domain::new's omega (field/src/lib.rs:43-53), FriDomain::new_radix2 (fri.rs:53-56).  Host-only. */

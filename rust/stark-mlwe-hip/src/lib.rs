@@ -276,6 +276,18 @@ pub mod fri {
         unsafe { stark_proof_free(raw); }
         (bytes, est)
     }
+    /// `deep_fri_prove` of ONE trace block-sharded over the ranks of the context's communicator (`stark_comm_init`; one rank without it):
+    /// `a, s, e, t` are this rank's DEVICE blocks of `n0 / W` rows.  Collective: every rank calls it with the same `n0, schedule, r, seed_z`
+    /// and receives the same canonical proof bytes (those of `deep_fri_prove` on the whole trace).
+    pub unsafe fn deep_fri_prove_sharded_dev(ctx: &Ctx, a: *const u64, s: *const u64, e: *const u64, t: *const u64, n0: usize, schedule: &[usize], r: usize, seed_z: u64) -> (Vec<u8>, usize) {
+        let mut raw: *mut stark_proof_t = ptr::null_mut();
+        ctx.chk(stark_deep_fri_prove_sharded_dev(ctx.raw, a, s, e, t, ptr::null(), n0, schedule.as_ptr(), schedule.len(), r, seed_z, &mut raw));
+        let mut bytes = vec![0u8; stark_proof_len(raw)];
+        ctx.chk(stark_proof_bytes(raw, bytes.as_mut_ptr()));
+        let est = stark_proof_size_estimate(raw);
+        stark_proof_free(raw);
+        (bytes, est)
+    }
     /// The bench loop of `channel/benches/end_to_end.rs:229-309` proves one trace after another; `traces[p] = (a, s, e, t)` as DEVICE
     /// pointers of independent n0-row traces are proven in one call: the 4 * B serial column sponges of `build_f0` (fri.rs:548-557) run
     /// concurrently, every proof is byte-identical to `deep_fri_prove` of that trace alone.

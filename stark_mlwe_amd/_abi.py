@@ -110,6 +110,16 @@ SIGNATURES = {
     "stark_fri_plan_requests": (i32, [vp, vp, vp, vp, vp]),
     "stark_fri_plan_assemble": (i32, [vp, vp, sz, vpp]),
     "stark_fri_plan_free": (i32, [vp]),
+    "stark_fri_build_sharded_dev": (i32, [vp, vp, sz, vp, sz, u64, vpp]),
+    "stark_fri_shard_num_layers": (i32, [vp]),
+    "stark_fri_shard_root": (i32, [vp, i32, vp]),
+    "stark_fri_shard_is_sharded": (i32, [vp, i32]),
+    "stark_fri_shard_free": (i32, [vp]),
+    "stark_fri_shard_prove_queries": (i32, [vp, sz, vpp]),
+    "stark_deep_fri_prove_sharded_dev": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, sz, sz, u64, vpp]),
+    "stark_diag_fri_build_sharded_emulated_dev": (i32, [vp, i32, vp, sz, vp, sz, u64, vp]),
+    "stark_diag_deep_fri_prove_sharded_emulated_dev": (i32, [vp, i32, vp, vp, vp, vp, vp, sz, vp, sz, sz, u64, vp]),
+    "stark_fri_shard_layout": (i32, [sz, vp, sz, i32, vp, vp]),
     "stark_root_of_unity": (i32, [i32, sz, vp]),
     "stark_compute_powers": (i32, [vp, i32, vp, sz, vp]),
     "stark_compute_powers_dev": (i32, [vp, i32, vp, sz, vp]),

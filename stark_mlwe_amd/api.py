@@ -173,6 +173,61 @@ class FriQueryPlan:
             self.h = None
 
 
+class FriShardState:
+    """stark_fri_shard_t: this rank's part of a sharded commit phase (fri.rs:231-312); the roots are the same on every rank."""
+
+    def __init__(self, ctx, handle, schedule):
+        self.ctx, self.h, self.schedule = ctx, handle, list(schedule)
+
+    @property
+    def num_layers(self):
+        return self.ctx.lib.stark_fri_shard_num_layers(self.h)
+
+    def root(self, l):
+        out = np.zeros(4, np.uint64)
+        self.ctx._chk(self.ctx.lib.stark_fri_shard_root(self.h, l, _ptr(out)))
+        return out
+
+    def roots(self):
+        return np.stack([self.root(l) for l in range(self.num_layers)])
+
+    def is_sharded(self, l):
+        v = self.ctx.lib.stark_fri_shard_is_sharded(self.h, l)
+        if v < 0:
+            raise StarkError(v, "layer out of range")
+        return bool(v)
+
+    def prove_queries(self, r):
+        """Collective: the query phase (fri.rs:355-466, 613-640) -> (canonical proof bytes, size estimate), the same on every rank."""
+        h = C.c_void_p()
+        self.ctx._chk(self.ctx.lib.stark_fri_shard_prove_queries(self.h, r, C.byref(h)))
+        return self.ctx._proof_out(h)
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.stark_fri_shard_free(self.h)
+            self.h = None
+
+
+def fri_shard_layout(n0, schedule, nranks):
+    """The shard planner of the sharded commit phase (host-only): (sharded[l], stop_len[l]) for the L+1 layers; StarkError(-1) when
+    nranks is not a power of two, does not divide n0, or the schedule does not divide n0."""
+    lib = load_library()
+    sch = np.ascontiguousarray(schedule, dtype=np.uint64)
+    sharded = np.zeros(len(sch) + 1, np.int32); stop = np.zeros(len(sch) + 1, np.uint64)
+    rc = lib.stark_fri_shard_layout(n0, _ptr(sch), len(sch), nranks, _ptr(sharded), _ptr(stop))
+    if rc != 0:
+        raise StarkError(rc, "stark_fri_shard_layout")
+    return [bool(x) for x in sharded], [int(x) for x in stop]
+
+
+def _dptr(x):
+    """A device pointer: an int, None, or anything with data_ptr() (a torch CUDA tensor)."""
+    if x is None:
+        return None
+    return C.c_void_p(x if isinstance(x, int) else x.data_ptr())
+
+
 class Transcript:
     """transcript/src/lib.rs:48-117 (device-resident state; absorbs run with the next challenge)."""
 
@@ -548,6 +603,41 @@ class Context:
         h = C.c_void_p()
         self._chk(self.lib.stark_fri_plan_create(self.h, _ptr(rt), n0, _ptr(sch), len(sch), r, C.byref(h)))
         return FriQueryPlan(self, h)
+
+    def fri_build_sharded(self, f0_block, n0, schedule, seed_z):
+        """Collective: the commit phase of one trace block-sharded over the context's communicator (one rank without it); f0_block =
+        this rank's DEVICE block of n0 / W elements.  -> FriShardState."""
+        sch = np.ascontiguousarray(schedule, dtype=np.uint64)
+        h = C.c_void_p()
+        self._chk(self.lib.stark_fri_build_sharded_dev(self.h, _dptr(f0_block), n0, _ptr(sch), len(sch), seed_z, C.byref(h)))
+        return FriShardState(self, h, schedule)
+
+    def deep_fri_prove_sharded(self, a, s, e, t, n0, params: DeepFriParams, f0=None):
+        """Collective: deep_fri_prove (fri.rs:601-641) of one trace block-sharded over the context's communicator; a, s, e, t (or f0) =
+        this rank's DEVICE blocks.  -> (canonical proof bytes, size estimate, stage ms), the same bytes on every rank."""
+        sch = np.ascontiguousarray(params.schedule, dtype=np.uint64)
+        h = C.c_void_p()
+        self._chk(self.lib.stark_deep_fri_prove_sharded_dev(self.h, _dptr(a), _dptr(s), _dptr(e), _dptr(t), _dptr(f0), n0, _ptr(sch), len(sch),
+                                                            params.r, params.seed_z, C.byref(h)))
+        ms = [self.lib.stark_proof_stage_ms(h, i) for i in range(3)]
+        return self._proof_out(h) + (ms,)
+
+    def diag_fri_build_sharded_emulated(self, nranks, f0_whole, n0, schedule, seed_z):
+        """Diagnostic: the sharded commit phase for `nranks` virtual ranks on this GPU (collectives as device copies) over the WHOLE f0 (device).
+        -> roots as every virtual rank sees them, uint64 [nranks, L+1, 4]."""
+        sch = np.ascontiguousarray(schedule, dtype=np.uint64)
+        roots = np.zeros((nranks, len(sch) + 1, 4), np.uint64)
+        self._chk(self.lib.stark_diag_fri_build_sharded_emulated_dev(self.h, nranks, _dptr(f0_whole), n0, _ptr(sch), len(sch), seed_z, _ptr(roots)))
+        return roots
+
+    def diag_deep_fri_prove_sharded_emulated(self, nranks, a, s, e, t, n0, params: DeepFriParams, f0=None):
+        """Diagnostic: the sharded deep_fri_prove for `nranks` virtual ranks on this GPU over the WHOLE columns (device).
+        -> one (proof bytes, size estimate) per virtual rank."""
+        sch = np.ascontiguousarray(params.schedule, dtype=np.uint64)
+        out = (C.c_void_p * nranks)()
+        self._chk(self.lib.stark_diag_deep_fri_prove_sharded_emulated_dev(self.h, nranks, _dptr(a), _dptr(s), _dptr(e), _dptr(t), _dptr(f0), n0, _ptr(sch), len(sch),
+                                                                          params.r, params.seed_z, out))
+        return [self._proof_out(C.c_void_p(out[q])) for q in range(nranks)]
 
     # ---- field helpers (crates/field/src/lib.rs) ----------------------------------------------------------
     def compute_powers(self, base, n, field=PALLAS_FR):

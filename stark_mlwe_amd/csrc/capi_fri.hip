@@ -574,3 +574,5 @@ int32_t stark_fri_plan_assemble(stark_fri_plan_t* p, const uint64_t* values, siz
 int32_t stark_fri_plan_free(stark_fri_plan_t* p) { if (!p) return STARK_ERR_INVALID_ARG; delete p; return STARK_OK; }
 
 }  // extern "C"
+
+#include "fri_shard_impl.hpp"

@@ -168,6 +168,19 @@ static __global__ void k_gather_multi(const fr_t* const* __restrict__ base, cons
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < k) stg(out + i, ldg(base[src[i]] + index[i]));
 }
+// The query table of a SHARDED prove: request i of this rank writes element index[i] of base[src[i]] (its own layer block, a level of its
+// lower tree, or a replicated layer / tree top) into row[i] of a zeroed nreq-row table.  Rows other ranks own stay zero, so one all-reduce
+// SUM completes the table on every rank.  Row and index bounds are checked on the host.
+static __global__ void k_gather_rows(const fr_t* const* __restrict__ base, const uint32_t* __restrict__ src, const uint64_t* __restrict__ index,
+                                     const uint64_t* __restrict__ row, uint64_t k, fr_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < k) stg(out + row[i], ldg(base[src[i]] + index[i]));
+}
+// dst[i] += src[i] on uint64 words (wrapping): the SUM of an all-reduce when several ranks are emulated on one GPU.
+static __global__ void k_add_u64(uint64_t* __restrict__ dst, const uint64_t* __restrict__ src, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] += src[i];
+}
 // dst[a][b][c] (contiguous, dims Da x Db x Dc) = src[a*sa + b*sb + c*sc]: the layout changes around the all-to-all exchanges
 // of the six-step NTT (32-byte elements, so even the transposing cases move whole 32-B units).
 static __global__ void k_permute3(const fr_t* __restrict__ src, fr_t* __restrict__ dst, uint64_t Da, uint64_t Db, uint64_t Dc, uint64_t sa, uint64_t sb, uint64_t sc) {
