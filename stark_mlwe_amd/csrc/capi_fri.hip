@@ -17,7 +17,7 @@ struct stark_fri_state {
     std::vector<size_t> schedule;
     std::vector<fr_t*> f; std::vector<size_t> n;           // L+1 layers (device, pooled)
     std::vector<fr_t> z;                                    // L fold challenges
-    std::vector<stark_tree*> trees; std::vector<char> hashed; std::vector<size_t> arity;
+    std::vector<stark_tree*> trees; std::vector<size_t> arity;
     std::vector<fr_t> roots;                                // fetched on first use (one download + one sync for all L+1)
     ~stark_fri_state() { for (auto p : f) if (p) ctx_release(ctx, p); for (auto t : trees) if (t) stark_merkle_free(t); }
 };
@@ -25,6 +25,8 @@ struct stark_proof { std::vector<uint8_t> bytes; size_t size_estimate = 0; doubl
 
 static inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 static inline int ilog2(size_t x) { return ilog2_ceil(x); }
+using Clock = std::chrono::steady_clock;
+static double ms_between(Clock::time_point x, Clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); }
 
 // fold on `st` with the z-power table zp (m entries, device)
 static int32_t fold_launch(stark_ctx* ctx, hipStream_t st, const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out) {
@@ -88,24 +90,49 @@ static int32_t state_roots(stark_fri_state* S) {
     S->roots = r; return STARK_OK;
 }
 
+// The layers of a commit phase: their sizes under the schedule (fri.rs:150) and their Merkle arities (fri.rs:220-229).
+static bool fri_layer_shape(size_t n0, const size_t* sched, size_t L, std::vector<size_t>& n, std::vector<size_t>& arity, std::string& err) {
+    if (!n0) { err = "empty layer"; return false; }
+    n.assign(1, n0);
+    for (size_t l = 0; l < L; ++l) { if (sched[l] < 2 || n[l] % sched[l]) { err = "schedule not dividing domain size"; return false; } n.push_back(n[l] / sched[l]); }
+    arity.clear(); for (size_t l = 0; l <= L; ++l) arity.push_back(pick_arity_for_layer(n[l], l < L ? sched[l] : 1));
+    return true;
+}
+// Everything of a commit phase that may upload constants (and synchronise doing so), to run before its first launch: the transcript parameters,
+// the Merkle parameters of every layer (MerkleChannelCfg::new(arity), fri.rs:277) and the fold challenges (fri.rs:250).  After the first call
+// these are all cached.
+static int32_t fri_prelude(stark_ctx* ctx, const std::vector<size_t>& n, const std::vector<size_t>& arity, uint64_t seed_z, std::vector<stark_params*>& mps,
+                           std::vector<fr_t>& z) {
+    stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
+    mps.assign(arity.size(), nullptr);
+    for (size_t l = 0; l < arity.size(); ++l) STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity[l]), &mps[l]));
+    z.assign(n.size() - 1, host::h_zero());
+    for (size_t l = 0; l + 1 < n.size(); ++l) STARK_TRY(sample_z(ctx, seed_z, l, n[l], &z[l]));
+    return STARK_OK;
+}
+// The commitment of layer l on `st`.  A hashed arity hashes the leaf pairs (f[i], s[i] = f_next[i / m]; zeros on the last layer, fri.rs:266, 283)
+// and adopts the digests as level 0; any other arity is commit_pairs(f, s) (fri.rs:289).  The n leaves sit at DS positions pos0 onwards, and the
+// tree climbs until a level of `stop` nodes (0: to the root).
+static int32_t commit_layer_on(stark_ctx* ctx, hipStream_t st, stark_params* mp, size_t arity, size_t l, const fr_t* f, const fr_t* f_next, size_t n, size_t m,
+                               uint64_t pos0, size_t stop, stark_tree** out) {
+    if (!hashed_arity(arity)) return merkle_build_on(ctx, st, mp, arity, (uint64_t)l, f, n, 1, f_next, m, pos0, 0, stop, false, out);
+    void* h = nullptr; STARK_TRY(ctx_alloc(ctx, n * sizeof(fr_t), &h));
+    stark_tree* T = nullptr;
+    int32_t rc = leaf_pair_hash_on(ctx, st, f, f_next, n, m, (fr_t*)h);
+    if (rc == STARK_OK) rc = merkle_build_on(ctx, st, mp, arity, (uint64_t)l, (const fr_t*)h, n, 0, nullptr, 1, pos0, 0, stop, /*adopt=*/true, &T);
+    if (rc) { if (!T) ctx_release(ctx, h); return rc; }
+    *out = T; return STARK_OK;
+}
+
 static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state** out) {
-    if (!n0) return ctx->fail(STARK_ERR_INVALID_ARG, "empty layer");
-    { size_t n = n0; for (size_t l = 0; l < L; ++l) { if (schedule[l] < 2 || n % schedule[l]) return ctx->fail(STARK_ERR_INVALID_ARG, "schedule not dividing domain size"); n /= schedule[l]; } }   // fri.rs:150
     stark_fri_state* S = new stark_fri_state(); S->ref_.bind(ctx); S->ctx = ctx; S->schedule.assign(schedule, schedule + L);
     auto bail = [&](int32_t rc) { delete S; return rc; };
-    // Everything that may upload constants (and synchronise doing so) happens BEFORE any stream is forked: transcript
-    // parameters, the leaf template, the Merkle parameters of every layer, the challenges.  After the first call these are all cached.
-    S->n.push_back(n0); for (size_t l = 0; l < L; ++l) S->n.push_back(S->n[l] / schedule[l]);
-    S->arity.assign(L + 1, 0); S->hashed.assign(L + 1, 0); S->trees.assign(L + 1, nullptr);
-    std::vector<stark_params*> mps(L + 1, nullptr);
-    { stark_params* tp = nullptr; int32_t rc = ctx_transcript_params(ctx, &tp); if (rc) return bail(rc); }
-    for (size_t l = 0; l <= L; ++l) {
-        const size_t m_l = l < L ? schedule[l] : 1;
-        S->arity[l] = pick_arity_for_layer(S->n[l], m_l); S->hashed[l] = hashed_arity(S->arity[l]) ? 1 : 0;
-        int32_t rc = ctx_merkle_params(ctx, host::width_for_arity(S->arity[l]), &mps[l]); if (rc) return bail(rc);     // MerkleChannelCfg::new(arity), fri.rs:277
-    }
-    size_t zp_total = 0;
-    for (size_t l = 0; l < L; ++l) { fr_t z; int32_t rc = sample_z(ctx, seed_z, l, S->n[l], &z); if (rc) return bail(rc); S->z.push_back(z); zp_total += schedule[l]; }
+    { std::string err; if (!fri_layer_shape(n0, schedule, L, S->n, S->arity, err)) return bail(ctx->fail(STARK_ERR_INVALID_ARG, err)); }
+    S->trees.assign(L + 1, nullptr);
+    // The prelude runs BEFORE any stream is forked.
+    std::vector<stark_params*> mps;
+    { int32_t rc = fri_prelude(ctx, S->n, S->arity, seed_z, mps, S->z); if (rc) return bail(rc); }
+    size_t zp_total = 0; for (size_t l = 0; l < L; ++l) zp_total += schedule[l];
     hipStream_t main_stream = ctx->stream, side = nullptr;
     { int32_t rc = ctx_side_stream(ctx, &side); if (rc) return bail(rc); }
     // layer 0 copy + folds back to back (the challenges do not depend on any commitment: fri.rs:250)
@@ -123,20 +150,8 @@ static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, con
     // underneath layer 0 instead of after it.  The streams are passed explicitly; the side stream is forked from and joined back
     // into the main one with events, so nothing here synchronises the host.
     if (hipEventRecord(ctx->ev_fork, main_stream) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_fork, 0) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "fork"));
-    auto commit_layer = [&](size_t l, hipStream_t st) -> int32_t {
-        const size_t n = S->n[l], m_l = l < L ? schedule[l] : 1, arity = S->arity[l];
-        stark_tree* T = nullptr;
-        if (S->hashed[l]) {
-            void* h = nullptr; STARK_TRY(ctx_alloc(ctx, n * sizeof(fr_t), &h));
-            int32_t rc = leaf_pair_hash_on(ctx, st, S->f[l], l < L ? S->f[l + 1] : nullptr, n, m_l, (fr_t*)h);        // fri.rs:283 (s = f_{l+1}[i/m] view)
-            if (rc == STARK_OK) rc = merkle_build_on(ctx, st, mps[l], arity, (uint64_t)l, (const fr_t*)h, n, 0, nullptr, 1, 0, 0, 0, /*adopt=*/true, &T);   // the digests become level 0
-            if (rc) { if (!T) ctx_release(ctx, h); return rc; }
-        } else {
-            // commit_pairs(f_l, s_l) (fri.rs:289): s_l is the m-fold replication of f_{l+1} (read as the view f_{l+1}[i / m]), or zeros on the last layer (fri.rs:266)
-            STARK_TRY(merkle_build_on(ctx, st, mps[l], arity, (uint64_t)l, S->f[l], n, 1, l < L ? S->f[l + 1] : nullptr, m_l, 0, 0, 0, false, &T));
-        }
-        S->trees[l] = T;
-        return STARK_OK;
+    auto commit_layer = [&](size_t l, hipStream_t st) {
+        return commit_layer_on(ctx, st, mps[l], S->arity[l], l, S->f[l], l < L ? S->f[l + 1] : nullptr, S->n[l], l < L ? schedule[l] : 1, 0, 0, &S->trees[l]);
     };
     int32_t crc = STARK_OK;
     for (size_t l = L; l >= 1 && crc == STARK_OK; --l) crc = commit_layer(l, side);
@@ -189,12 +204,6 @@ static int32_t ali_merge_dev_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, 
     return STARK_OK;
 }
 
-// ali_sample_z_beta_fs (fri.rs:511-533).
-static void ali_z_beta_from_fused(const fr_t& fused, size_t n0, const fr_t& roots_seed, fr_t* z, fr_t* beta);
-static int32_t ali_sample_z_beta(stark_ctx* ctx, const char* tag, size_t n0, const fr_t& roots_seed, fr_t* z, fr_t* beta) {
-    fr_t fused; STARK_TRY(tr_hash_host1(ctx, tag, {roots_seed, host::h_u64(n0)}, &fused));
-    ali_z_beta_from_fused(fused, n0, roots_seed, z, beta); return STARK_OK;
-}
 // the RNG part of ali_sample_z_beta_fs (fri.rs:516-532): beta, then the first candidate outside H
 static void ali_z_beta_from_fused(const fr_t& fused, size_t n0, const fr_t& roots_seed, fr_t* z, fr_t* beta) {
     uint8_t seed[32]; host::h_to_bytes_le(fused, seed); host::ChaCha12Rng rng(seed);
@@ -209,6 +218,13 @@ static void ali_z_beta_from_fused(const fr_t& fused, size_t n0, const fr_t& root
         }
     }
 }
+// The challenges of build_f0 from the four column digests (fri.rs:556-560): seed_f = H("ALI/seed", [h_a, h_s, h_e, h_t, n0]), then
+// ali_sample_z_beta_fs (fri.rs:511-533) under the tag "ALI/DEEP".
+static int32_t ali_challenges(stark_ctx* ctx, const fr_t h[4], size_t n0, fr_t* seed_f, fr_t* z, fr_t* beta) {
+    STARK_TRY(tr_hash_host1(ctx, "ALI/seed", {h[0], h[1], h[2], h[3], host::h_u64(n0)}, seed_f));
+    fr_t fused; STARK_TRY(tr_hash_host1(ctx, "ALI/DEEP", {*seed_f, host::h_u64(n0)}, &fused));
+    ali_z_beta_from_fused(fused, n0, *seed_f, z, beta); return STARK_OK;
+}
 // DeepAliRealBuilder::build_f0 (fri.rs:535-569), default builder: no blinding, ds_tag "ALI/DEEP".
 static int32_t build_f0_dev_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, size_t n0, fr_t* f0, fr_t* aux7) {
     if (n0 <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 > 1");
@@ -216,10 +232,8 @@ static int32_t build_f0_dev_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, c
     DevBuf dig; STARK_HIP(ctx, dig.alloc(ctx, 4 * sizeof(fr_t)));
     const fr_t* cols[4] = {a, s, e, t}; const char* tags[4] = {"ALI/A", "ALI/S", "ALI/E", "ALI/T"};
     STARK_TRY(tr_hash_columns4_dev(ctx, tags, cols, n0, dig.fr()));           // the chains are independent: one launch, four concurrent blocks
-    fr_t h[5]; STARK_HIP(ctx, hipMemcpyAsync(h, dig.p, 4 * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    h[4] = host::h_u64(n0);
-    fr_t seed_f; STARK_TRY(tr_hash_host1(ctx, "ALI/seed", std::vector<fr_t>(h, h + 5), &seed_f));
-    fr_t z, beta; STARK_TRY(ali_sample_z_beta(ctx, "ALI/DEEP", n0, seed_f, &z, &beta));
+    fr_t h[4]; STARK_HIP(ctx, hipMemcpyAsync(h, dig.p, 4 * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    fr_t seed_f, z, beta; STARK_TRY(ali_challenges(ctx, h, n0, &seed_f, &z, &beta));
     if (aux7) { for (int c = 0; c < 4; ++c) aux7[c] = h[c]; aux7[4] = seed_f; aux7[5] = z; aux7[6] = beta; }
     fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));         // FriDomain::new_radix2(n0).omega (fri.rs:53-56); Radix2EvaluationDomain::new rounds n0 up to a power of two, as ilog2 does
     return ali_merge_dev_impl(ctx, a, s, e, t, nullptr, host::h_zero(), omega, z, n0, f0, nullptr);
@@ -271,6 +285,37 @@ struct MemoHasher : TrHasher {
         memcpy((void*)out, it->second.data(), n * sizeof(fr_t)); return 0;
     }
 };
+// Where a request of the query plan reads: a device array (a layer or a tree level), its length, the rank that holds the value, the index there.
+struct FriOpening { const fr_t* src; size_t len; uint64_t owner, index; };
+// The values of the plan's requests that `rank` owns, into their rows of the nreq-row device table `out`, with ONE gather launch over a table of
+// source arrays; resolve(request, opening) locates each request.  host (optional) receives a download of the whole table.  Returns synchronised:
+// the host index arrays end here.
+template <class Resolve>
+static int32_t gather_openings(stark_ctx* ctx, const FriPlan& plan, uint64_t rank, Resolve resolve, fr_t* out, fr_t* host) {
+    std::vector<const fr_t*> base; std::map<const fr_t*, uint32_t> slot; std::vector<uint32_t> src; std::vector<uint64_t> idx, row;
+    for (size_t i = 0; i < plan.req.size(); ++i) {
+        FriOpening o; STARK_TRY(resolve(plan.req[i], o));
+        if (o.owner != rank) continue;
+        if (o.index >= o.len) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: opening index out of range");
+        auto it = slot.emplace(o.src, (uint32_t)base.size()).first;
+        if (it->second == base.size()) base.push_back(o.src);
+        src.push_back(it->second); idx.push_back(o.index); row.push_back(i);
+    }
+    const size_t k = src.size();
+    if (!k) return STARK_OK;
+    DevBuf db, ds, di, dr;
+    STARK_HIP(ctx, db.alloc(ctx, base.size() * sizeof(void*))); STARK_HIP(ctx, ds.alloc(ctx, k * 4)); STARK_HIP(ctx, di.alloc(ctx, k * 8)); STARK_HIP(ctx, dr.alloc(ctx, k * 8));
+    STARK_HIP(ctx, hipMemcpyAsync(db.p, base.data(), base.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    STARK_HIP(ctx, hipMemcpyAsync(ds.p, src.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
+    STARK_HIP(ctx, hipMemcpyAsync(di.p, idx.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
+    STARK_HIP(ctx, hipMemcpyAsync(dr.p, row.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)db.p, (const uint32_t*)ds.p, (const uint64_t*)di.p,
+                       (const uint64_t*)dr.p, (uint64_t)k, out);
+    STARK_HIP(ctx, hipGetLastError());
+    if (host) STARK_HIP(ctx, hipMemcpyAsync(host, out, plan.req.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
+    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return STARK_OK;
+}
 // fri_prove_queries + payload assembly + canonical encoding (fri.rs:355-466, 613-640).  The indices of every opened value depend
 // only on the roots, so the query phase first RECORDS what it will read (fri_plan.hpp: the same code against a recording source),
 // fetches all of it — a few thousand layer elements and tree nodes spread over every layer and level — with ONE gather launch and
@@ -282,31 +327,17 @@ static int32_t prove_queries_encode(stark_ctx* ctx, stark_fri_state* S, size_t n
     const size_t nreq = plan.req.size();
     std::vector<fr_t> vals(nreq);
     if (nreq) {
-        // source table: layers first, then the levels of every tree
-        std::vector<const fr_t*> base; std::vector<size_t> lens; std::map<std::pair<uint32_t, uint32_t>, uint32_t> tree_slot;
-        for (size_t l = 0; l < S->f.size(); ++l) { base.push_back(S->f[l]); lens.push_back(S->n[l]); }
-        std::vector<uint32_t> src(nreq); std::vector<uint64_t> idx(nreq);
-        for (size_t i = 0; i < nreq; ++i) {
-            const FriRequest& q = plan.req[i];
-            if (q.kind == 0) { if (q.which >= S->f.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range"); src[i] = q.which; }
-            else {
-                if (q.which >= S->trees.size() || q.level >= S->trees[q.which]->levels.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
-                auto key = std::make_pair(q.which, q.level); auto it = tree_slot.find(key);
-                if (it == tree_slot.end()) { it = tree_slot.emplace(key, (uint32_t)base.size()).first; base.push_back(S->trees[q.which]->levels[q.level]); lens.push_back(S->trees[q.which]->lens[q.level]); }
-                src[i] = it->second;
+        auto resolve = [&](const FriRequest& q, FriOpening& o) -> int32_t {              // every value is on this GPU
+            if (q.kind == 0) {
+                if (q.which >= S->f.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range");
+                o = {S->f[q.which], S->n[q.which], 0, q.index}; return STARK_OK;
             }
-            if (q.index >= lens[src[i]]) return ctx->fail(STARK_ERR_INVALID_ARG, "opening index out of range");
-            idx[i] = q.index;
-        }
-        DevBuf db, ds, di, dout;
-        STARK_HIP(ctx, db.alloc(ctx, base.size() * sizeof(void*))); STARK_HIP(ctx, ds.alloc(ctx, nreq * 4)); STARK_HIP(ctx, di.alloc(ctx, nreq * 8)); STARK_HIP(ctx, dout.alloc(ctx, nreq * sizeof(fr_t)));
-        STARK_HIP(ctx, hipMemcpyAsync(db.p, base.data(), base.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
-        STARK_HIP(ctx, hipMemcpyAsync(ds.p, src.data(), nreq * 4, hipMemcpyHostToDevice, ctx->stream));
-        STARK_HIP(ctx, hipMemcpyAsync(di.p, idx.data(), nreq * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_gather_multi, dim3((unsigned)((nreq + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)db.p, (const uint32_t*)ds.p, (const uint64_t*)di.p, (uint64_t)nreq, dout.fr());
-        STARK_HIP(ctx, hipGetLastError());
-        STARK_HIP(ctx, hipMemcpyAsync(vals.data(), dout.p, nreq * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (q.which >= S->trees.size() || q.level >= S->trees[q.which]->levels.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
+            const stark_tree* T = S->trees[q.which];
+            o = {T->levels[q.level], T->lens[q.level], 0, q.index}; return STARK_OK;
+        };
+        DevBuf dout; STARK_HIP(ctx, dout.alloc(ctx, nreq * sizeof(fr_t)));
+        STARK_TRY(gather_openings(ctx, plan, 0, resolve, dout.fr(), vals.data()));
     }
     ReplaySource rep(vals.data(), vals.size());
     int32_t rc = assemble_proof(plan.shape, r, H, rep, P->bytes, P->size_estimate);
@@ -320,20 +351,19 @@ struct stark_fri_plan { CtxRef ref_; stark_ctx* ctx = nullptr; FriPlan plan; };
 static int32_t prove_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t* f0_in, size_t n0,
                           const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
     if (!is_pow2(n0)) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two (radix-2 domain)");
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    stark_proof* P = new stark_proof(); auto t0 = now();
+    stark_proof* P = new stark_proof(); auto t0 = Clock::now();
     DevBuf f0buf; const fr_t* f0 = f0_in;
     if (!f0) {
         if (f0buf.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) { delete P; return ctx->fail(STARK_ERR_OOM, "f0"); }
         int32_t rc = build_f0_dev_impl(ctx, a, s, e, t, n0, f0buf.fr(), nullptr); if (rc) { delete P; return rc; }
         f0 = f0buf.fr();
     }
-    auto t1 = now();
+    auto t1 = Clock::now();
     stark_fri_state* S = nullptr; { int32_t rc = fri_build_impl(ctx, f0, n0, schedule, L, seed_z, &S); if (rc) { delete P; return rc; } }
-    auto t2 = now();
+    auto t2 = Clock::now();
     { int32_t rc = prove_queries_encode(ctx, S, n0, r, P); delete S; if (rc) { delete P; return rc; } }
-    auto t3 = now();
-    P->ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count(); P->ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count(); P->ms[2] = std::chrono::duration<double, std::milli>(t3 - t2).count();
+    auto t3 = Clock::now();
+    P->ms[0] = ms_between(t0, t1); P->ms[1] = ms_between(t1, t2); P->ms[2] = ms_between(t2, t3);
     *out = P; return STARK_OK;
 }
 
@@ -346,10 +376,8 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
                                 const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
     if (!is_pow2(n0)) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two (radix-2 domain)");
     if (n0 <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 > 1");
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms_of = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
     for (size_t p = 0; p < B; ++p) out[p] = nullptr;
-    auto t0 = now();
+    auto t0 = Clock::now();
     // (1) all column digests: 4 * B serial sponges, concurrently
     std::vector<const fr_t*> ptrs(4 * B);
     for (size_t p = 0; p < B; ++p) { ptrs[4 * p] = as_fr(a[p]); ptrs[4 * p + 1] = as_fr(s[p]); ptrs[4 * p + 2] = as_fr(e[p]); ptrs[4 * p + 3] = as_fr(t[p]); }
@@ -374,12 +402,12 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
     STARK_TRY(tr_hash_dev(ctx, "ALI/DEEP", deep_in.fr(), 2, B, fused.fr()));
     std::vector<fr_t> fu(B);
     STARK_HIP(ctx, hipMemcpyAsync(fu.data(), fused.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    auto t1 = now();
+    auto t1 = Clock::now();
     // (3) per trace: merge, commit phase, query phase.  These tails are latency-bound (a few ms of small dependent launches each), so up to four of them run
     // side by side: worker contexts of this context (same device, private streams, own pools), one host thread each, traces dealt round-robin.  The inputs
     // are resident and this context's stream is idle (synchronised above), so the workers' streams may read them.
     const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));
-    const double shared_ms = ms_of(t0, t1);
+    const double shared_ms = ms_between(t0, t1);
     const size_t NT = std::min<size_t>(B, 4);
     std::vector<stark_ctx*> cx(NT); for (size_t w = 0; w < NT; ++w) STARK_TRY(ctx_aux(ctx, w, &cx[w]));
     std::vector<int32_t> rcs(NT, STARK_OK);
@@ -388,17 +416,17 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
         int32_t rc = ctx_enter(c); if (rc) { rcs[w] = rc; return; }
         DevBuf f0buf; if (f0buf.alloc(c, n0 * sizeof(fr_t)) != hipSuccess) { rcs[w] = c->fail(STARK_ERR_OOM, "f0"); return; }
         for (size_t p = w; p < B; p += NT) {
-            auto u0 = now();
+            auto u0 = Clock::now();
             fr_t z, beta; ali_z_beta_from_fused(fu[p], n0, seed_f[p], &z, &beta);
             rc = ali_merge_dev_impl(c, as_fr(a[p]), as_fr(s[p]), as_fr(e[p]), as_fr(t[p]), nullptr, host::h_zero(), omega, z, n0, f0buf.fr(), nullptr); if (rc) { rcs[w] = rc; return; }
-            auto u1 = now();
+            auto u1 = Clock::now();
             stark_fri_state* S = nullptr; rc = fri_build_impl(c, f0buf.fr(), n0, schedule, L, seed_z, &S); if (rc) { rcs[w] = rc; return; }
-            auto u2 = now();
+            auto u2 = Clock::now();
             stark_proof* P = new stark_proof();
             rc = prove_queries_encode(c, S, n0, r, P); delete S; if (rc) { delete P; rcs[w] = rc; return; }
-            auto u3 = now();
-            P->ms[0] = shared_ms + ms_of(u0, u1);          // the shared sponge stage (whole batch) + this trace's merge
-            P->ms[1] = ms_of(u1, u2); P->ms[2] = ms_of(u2, u3);
+            auto u3 = Clock::now();
+            P->ms[0] = shared_ms + ms_between(u0, u1);          // the shared sponge stage (whole batch) + this trace's merge
+            P->ms[1] = ms_between(u1, u2); P->ms[2] = ms_between(u2, u3);
             out[p] = P;
         }
         (void)hipStreamSynchronize(c->stream);
@@ -539,9 +567,8 @@ int32_t stark_ali_cstar_from_partials(stark_ctx_t* ctx, const uint64_t* partials
 int32_t stark_ali_challenges(stark_ctx_t* ctx, const uint64_t* digests16, size_t n0, uint64_t* aux12) {
     if (!ctx || !digests16 || !aux12 || n0 <= 1) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    fr_t h[5]; for (int c = 0; c < 4; ++c) h[c] = load_fr(digests16 + 4 * c); h[4] = host::h_u64(n0);
-    fr_t seed_f; STARK_TRY(tr_hash_host1(ctx, "ALI/seed", std::vector<fr_t>(h, h + 5), &seed_f));                       // fri.rs:556-557
-    fr_t z, beta; STARK_TRY(ali_sample_z_beta(ctx, "ALI/DEEP", n0, seed_f, &z, &beta));
+    fr_t h[4]; for (int c = 0; c < 4; ++c) h[c] = load_fr(digests16 + 4 * c);
+    fr_t seed_f, z, beta; STARK_TRY(ali_challenges(ctx, h, n0, &seed_f, &z, &beta));
     store_fr(aux12, seed_f); store_fr(aux12 + 4, z); store_fr(aux12 + 8, beta); return STARK_OK;
 }
 int32_t stark_fri_plan_create(stark_ctx_t* ctx, const uint64_t* roots, size_t n0, const size_t* schedule, size_t L, size_t r, stark_fri_plan_t** out) {

@@ -5,6 +5,7 @@
 #include <cstring>
 #include "ctx.hpp"
 #include "fri_dev.hpp"
+#include "shard_coll.hpp"
 
 using namespace stark;
 
@@ -291,21 +292,17 @@ static int32_t rows_coset_run(stark_ctx* ctx, const fr_t* src, fr_t* dst, uint64
 
 // ---- one column of a trace block-sharded over the ranks of the context's communicator: the LDE as ONE call (dist.py ShardedLde in C++) ----------
 // A host without Python composes nothing: rank q passes its natural-order block [q n/W, (q+1) n/W) of the 2^log_n evaluations and receives its block of the
-// 2^(log_n + log_blowup) evaluations on shift * <w_N>.  Four all-to-alls (stark_comm_all_to_all_dev; a device copy when there is one rank and no
-// communicator), whatever the blow-up: natural rows -> column blocks; the inverse transform's transpose; ONE exchange for the first-phase outputs of all
-// cosets; ONE to natural blocks.  Between them only local phases (columns_run, ntt_run rows, rows_coset_run) and the pack kernel.
+// 2^(log_n + log_blowup) evaluations on shift * <w_N>.  Four all-to-alls (ShardColl, shard_coll.hpp), whatever the blow-up: natural rows -> column
+// blocks; the inverse transform's transpose; ONE exchange for the first-phase outputs of all cosets; ONE to natural blocks.  Between them only local
+// phases (columns_run, ntt_run rows, rows_coset_run) and the pack kernel.
 static int32_t pack3(stark_ctx* ctx, const fr_t* src, fr_t* dst, uint64_t d0, uint64_t d1, uint64_t d2, int p0, int p1, int p2) {
     const uint64_t d[3] = {d0, d1, d2}, st[3] = {d1 * d2, d2, 1}; const int pm[3] = {p0, p1, p2};
     const uint64_t tot = d0 * d1 * d2; if (!tot) return STARK_OK;
     hipLaunchKernelGGL(k_permute3, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, src, dst, d[pm[0]], d[pm[1]], d[pm[2]], st[pm[0]], st[pm[1]], st[pm[2]]);
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
 }
-static int32_t exchange(stark_ctx* ctx, int W, const fr_t* send, fr_t* recv, size_t elems_per_peer) {
-    if (W == 1 && !ctx->comm) { STARK_HIP(ctx, hipMemcpyAsync(recv, send, elems_per_peer * sizeof(fr_t), hipMemcpyDeviceToDevice, ctx->stream)); return STARK_OK; }
-    return stark_comm_all_to_all_dev(ctx, send, recv, elems_per_peer * sizeof(fr_t));
-}
-// One rank's buffers and the five local phases between the four exchanges.  The same code runs under the real communicator (lde_sharded_run) and under
-// the in-process emulation of W ranks on one GPU (stark_diag_lde_sharded_emulated_dev: what checks the W > 1 index arithmetic without a second GPU).
+// One rank's buffers and the five local phases between the four exchanges.  One driver (lde_sharded) runs them for the local ranks of a ShardColl:
+// the communicator's rank (stark_lde_sharded_dev) or W ranks emulated on one GPU (stark_diag_lde_sharded_emulated_dev).
 struct ShardPlan { int W, log_n, lb, log_rows, log_cols; uint64_t R, Cc, b, nrl, ncl, nl; };
 struct ShardRank { int rank; const fr_t* block; fr_t* out; DevBuf t0, t1, big0, big1; };
 static int32_t shard_plan(stark_ctx* ctx, int W, int log_n, int lb, ShardPlan& P) {
@@ -351,31 +348,21 @@ static int32_t shard_phase(stark_ctx* ctx, const ShardPlan& P, ShardRank& K, int
         return pack3(ctx, K.big0.fr(), K.out, W, nrl, ncl * b, 1, 0, 2);
     }
 }
+// block / out: this rank's blocks, or the whole arrays when C is emulated
 template <class F>
-static int32_t lde_sharded_run(stark_ctx* ctx, const fr_t* block, int log_n, int lb, const fr_t& shift, fr_t* out) {
-    const int W = ctx->comm ? stark_comm_size(ctx) : 1, rank = ctx->comm ? stark_comm_rank(ctx) : 0;
-    ShardPlan P; STARK_TRY(shard_plan(ctx, W, log_n, lb, P));
-    ShardRank K; K.rank = rank; K.block = block; K.out = out; STARK_TRY(shard_alloc(ctx, P, K));
-    for (int phase = 0; phase < 5; ++phase) {
-        STARK_TRY((shard_phase<F>(ctx, P, K, phase, shift)));
-        if (phase < 4) STARK_TRY(exchange(ctx, W, shard_send(K, phase), shard_recv(K, phase), shard_per_peer(P, phase)));
+static int32_t lde_sharded(const ShardColl& C, const fr_t* block, int log_n, int lb, const fr_t& shift, fr_t* out) {
+    stark_ctx* ctx = C.ctx;
+    ShardPlan P; STARK_TRY(shard_plan(ctx, C.W, log_n, lb, P));
+    std::vector<ShardRank> K(C.local());
+    for (size_t i = 0; i < K.size(); ++i) {
+        K[i].rank = C.rank(i); K[i].block = block + C.block(i) * P.nl; K[i].out = out + (C.block(i) * P.nl << lb); STARK_TRY(shard_alloc(ctx, P, K[i]));
     }
-    return STARK_OK;
-}
-// W virtual ranks on ONE GPU: the phases of every rank in turn, each exchange as device copies (chunk q of rank p's send buffer -> chunk p of rank q's
-// receive buffer).  Exactly the code and index arithmetic of the real W-rank run, minus RCCL.
-template <class F>
-static int32_t lde_sharded_emulated(stark_ctx* ctx, int W, const fr_t* evals, int log_n, int lb, const fr_t& shift, fr_t* out) {
-    ShardPlan P; STARK_TRY(shard_plan(ctx, W, log_n, lb, P));
-    std::vector<ShardRank> K(W);
-    for (int r = 0; r < W; ++r) { K[r].rank = r; K[r].block = evals + (size_t)r * P.nl; K[r].out = out + ((size_t)r * P.nl << lb); STARK_TRY(shard_alloc(ctx, P, K[r])); }
     for (int phase = 0; phase < 5; ++phase) {
-        for (int r = 0; r < W; ++r) STARK_TRY((shard_phase<F>(ctx, P, K[r], phase, shift)));
-        if (phase < 4) {
-            const uint64_t per = shard_per_peer(P, phase);
-            for (int p = 0; p < W; ++p) for (int q = 0; q < W; ++q)
-                STARK_HIP(ctx, hipMemcpyAsync(shard_recv(K[q], phase) + (size_t)p * per, shard_send(K[p], phase) + (size_t)q * per, per * sizeof(fr_t), hipMemcpyDeviceToDevice, ctx->stream));
-        }
+        for (auto& k : K) STARK_TRY((shard_phase<F>(ctx, P, k, phase, shift)));
+        if (phase == 4) break;
+        std::vector<const void*> send; std::vector<void*> recv;
+        for (auto& k : K) { send.push_back(shard_send(k, phase)); recv.push_back(shard_recv(k, phase)); }
+        STARK_TRY(C.all_to_all(send, recv, shard_per_peer(P, phase) * sizeof(fr_t)));
     }
     return STARK_OK;
 }
@@ -385,17 +372,17 @@ extern "C" {
 int32_t stark_lde_sharded_dev(stark_ctx_t* ctx, int32_t field_id, const uint64_t* block, size_t log_n, size_t log_blowup, const uint64_t* shift4, uint64_t* out) {
     if (!ctx || !block || !out || !shift4 || block == out) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    const fr_t sh = load_fr(shift4);
-    if (field_id == STARK_FIELD_PALLAS_FR) return lde_sharded_run<PallasFr>(ctx, as_fr(block), (int)log_n, (int)log_blowup, sh, as_fr(out));
-    if (field_id == STARK_FIELD_BLS12_381_FR) return lde_sharded_run<Bls12381Fr>(ctx, as_fr(block), (int)log_n, (int)log_blowup, sh, as_fr(out));
+    const fr_t sh = load_fr(shift4); ShardColl C = ShardColl::real(ctx);
+    if (field_id == STARK_FIELD_PALLAS_FR) return lde_sharded<PallasFr>(C, as_fr(block), (int)log_n, (int)log_blowup, sh, as_fr(out));
+    if (field_id == STARK_FIELD_BLS12_381_FR) return lde_sharded<Bls12381Fr>(C, as_fr(block), (int)log_n, (int)log_blowup, sh, as_fr(out));
     return ctx->fail(STARK_ERR_INVALID_ARG, "unknown field id");
 }
 int32_t stark_diag_lde_sharded_emulated_dev(stark_ctx_t* ctx, int32_t field_id, int32_t nranks, const uint64_t* evals, size_t log_n, size_t log_blowup, const uint64_t* shift4, uint64_t* out) {
     if (!ctx || !evals || !out || !shift4 || evals == out || nranks < 1) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    const fr_t sh = load_fr(shift4);
-    if (field_id == STARK_FIELD_PALLAS_FR) return lde_sharded_emulated<PallasFr>(ctx, nranks, as_fr(evals), (int)log_n, (int)log_blowup, sh, as_fr(out));
-    if (field_id == STARK_FIELD_BLS12_381_FR) return lde_sharded_emulated<Bls12381Fr>(ctx, nranks, as_fr(evals), (int)log_n, (int)log_blowup, sh, as_fr(out));
+    const fr_t sh = load_fr(shift4); ShardColl C = ShardColl::emulate(ctx, nranks);
+    if (field_id == STARK_FIELD_PALLAS_FR) return lde_sharded<PallasFr>(C, as_fr(evals), (int)log_n, (int)log_blowup, sh, as_fr(out));
+    if (field_id == STARK_FIELD_BLS12_381_FR) return lde_sharded<Bls12381Fr>(C, as_fr(evals), (int)log_n, (int)log_blowup, sh, as_fr(out));
     return ctx->fail(STARK_ERR_INVALID_ARG, "unknown field id");
 }
 int32_t stark_ntt_rows_coset_dev(stark_ctx_t* ctx, int32_t field_id, const uint64_t* src, uint64_t* dst, size_t nrows, size_t log_cols, size_t row0, size_t log_n, const uint64_t* shift4) {

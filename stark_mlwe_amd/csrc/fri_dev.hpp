@@ -162,15 +162,9 @@ static __global__ void k_gather(const fr_t* __restrict__ src, const uint64_t* __
     if (i < k) stg(out + i, ldg(src + idx[i]));
 }
 
-// Batched opening reads of the query phase: request i reads element index[i] of the array base[src[i]] (layers and tree levels of a
-// whole proof in ONE launch instead of one synchronised gather per level).
-static __global__ void k_gather_multi(const fr_t* const* __restrict__ base, const uint32_t* __restrict__ src, const uint64_t* __restrict__ index, uint64_t k, fr_t* __restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < k) stg(out + i, ldg(base[src[i]] + index[i]));
-}
-// The query table of a SHARDED prove: request i of this rank writes element index[i] of base[src[i]] (its own layer block, a level of its
-// lower tree, or a replicated layer / tree top) into row[i] of a zeroed nreq-row table.  Rows other ranks own stay zero, so one all-reduce
-// SUM completes the table on every rank.  Row and index bounds are checked on the host.
+// Batched opening reads of the query phase: request i reads element index[i] of the array base[src[i]] (a layer or a tree level) into
+// row[i] of the table (layers and tree levels of a whole proof in ONE launch instead of one synchronised gather per level).  A sharded
+// prove writes only the rows its rank owns into a zeroed table, so that one all-reduce SUM completes it.  Bounds are checked on the host.
 static __global__ void k_gather_rows(const fr_t* const* __restrict__ base, const uint32_t* __restrict__ src, const uint64_t* __restrict__ index,
                                      const uint64_t* __restrict__ row, uint64_t k, fr_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

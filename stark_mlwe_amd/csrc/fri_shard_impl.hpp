@@ -4,9 +4,9 @@
 // Included at the end of capi_fri.hip (it uses that file's fold / challenge / merge / query helpers).
 //
 // Structure (as the sharded LDE in capi_ntt.hip): a shard PLAN that every rank derives identically from (n0, schedule, W), per-rank STATE,
-// and numbered PHASES of local work between two collectives.  The collectives go through `ShardColl`: the real communicator (one local
-// rank; without a communicator and W = 1 they reduce to nothing or device copies) or the emulation of W virtual ranks on one GPU (every
-// collective as device copies).  The drivers below are the same code for both, so the W > 1 index arithmetic the emulation tests reach is
+// and numbered PHASES of local work between two collectives.  The collectives go through `ShardColl` (shard_coll.hpp): the communicator's
+// one local rank, or W virtual ranks emulated on one GPU.  One driver per operation (shard_build, shard_prove) runs for the local ranks of
+// either; each real entry point and its diagnostic twin only build the ShardColl, so the W > 1 index arithmetic the emulation tests reach is
 // what runs with RCCL.
 //
 // Rules that keep the collectives safe: every argument check happens before the first collective; the first collective of each entry point
@@ -14,12 +14,13 @@
 // of collectives depends only on that header, never on local data.
 
 #include <array>
+#include "shard_coll.hpp"
 
 // ---- the plan: which layers stay block-local, and where each lower tree stops ------------------------------------------------------------
 struct FriShardPlan {
     int W = 1; size_t n0 = 0, L = 0, T = 0;          // T: the first replicated layer (L + 1: every layer sharded)
     std::vector<size_t> sched, n, arity, stop;       // stop[l]: local length of the level at which a sharded layer's lower tree stops (1: replicated)
-    std::vector<char> hashed, sharded;
+    std::vector<char> sharded;
     size_t m(size_t l) const { return l < L ? sched[l] : 1; }
     size_t here(size_t l) const { return sharded[l] ? n[l] / W : n[l]; }   // elements of layer l one rank holds
     size_t zoff(size_t l) const { size_t o = 0; for (size_t j = 0; j < l; ++j) o += sched[j]; return o; }   // layer l's z-powers in the fold table
@@ -31,12 +32,11 @@ static bool fri_shard_plan(size_t n0, const size_t* sched, size_t L, int W, FriS
     if (!n0) { err = "empty layer"; return false; }
     if (n0 % (size_t)W) { err = "n0 must divide over the ranks"; return false; }
     if (L && !sched) { err = "schedule"; return false; }
-    P = FriShardPlan(); P.W = W; P.n0 = n0; P.L = L; P.sched.assign(sched, sched + L); P.n.assign(1, n0);
-    for (size_t l = 0; l < L; ++l) { if (sched[l] < 2 || P.n[l] % sched[l]) { err = "schedule not dividing domain size"; return false; } P.n.push_back(P.n[l] / sched[l]); }   // fri.rs:150
+    P = FriShardPlan(); P.W = W; P.n0 = n0; P.L = L; P.sched.assign(sched, sched + L);
+    if (!fri_layer_shape(n0, sched, L, P.n, P.arity, err)) return false;
     bool prev = true; P.T = L + 1;
     for (size_t l = 0; l <= L; ++l) {
-        const size_t m = P.m(l), a = pick_arity_for_layer(P.n[l], m);
-        P.arity.push_back(a); P.hashed.push_back(hashed_arity(a) ? 1 : 0);
+        const size_t m = P.m(l), a = P.arity[l];
         bool now = prev && hashed_arity(a) && P.n[l] % (size_t)W == 0;
         if (now) { const size_t nl = P.n[l] / W; now = nl % a == 0 && (l == L || nl % m == 0); }
         if (!now && P.T == L + 1) P.T = l;
@@ -64,93 +64,56 @@ static int32_t coll_alloc(stark_ctx* ctx, FriShardRank& K, size_t bytes) {
     STARK_HIP(ctx, K.coll.alloc(ctx, bytes)); return STARK_OK;
 }
 
-// ---- the collectives ------------------------------------------------------------------------------------------------------------------------
-struct ShardColl {
-    stark_ctx* ctx; int W; bool emulated;
-    // in place: buf[i] (local rank R[i]) holds W chunks of `bytes`; its own chunk is at rank * bytes
-    int32_t all_gather(const std::vector<FriShardRank*>& R, const std::vector<void*>& buf, size_t bytes) {
-        if (!bytes) return STARK_OK;
-        if (!emulated) {
-            if (W == 1 && !ctx->comm) return STARK_OK;
-            return stark_comm_all_gather_dev(ctx, (const char*)buf[0] + (size_t)R[0]->rank * bytes, buf[0], bytes);
-        }
-        for (int p = 0; p < W; ++p) for (int q = 0; q < W; ++q) if (p != q)
-            STARK_HIP(ctx, hipMemcpyAsync((char*)buf[q] + (size_t)p * bytes, (const char*)buf[p] + (size_t)p * bytes, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        return STARK_OK;
-    }
-    // SUM of `count` uint64 words, in place
-    int32_t all_reduce(const std::vector<void*>& buf, size_t count) {
-        if (!count) return STARK_OK;
-        if (!emulated) {
-            if (W == 1 && !ctx->comm) return STARK_OK;
-            return stark_comm_all_reduce_u64_dev(ctx, buf[0], buf[0], count);
-        }
-        for (int q = 1; q < W; ++q) { hipLaunchKernelGGL(k_add_u64, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, (uint64_t*)buf[0], (const uint64_t*)buf[q], (uint64_t)count); STARK_HIP(ctx, hipGetLastError()); }
-        for (int q = 1; q < W; ++q) STARK_HIP(ctx, hipMemcpyAsync(buf[q], buf[0], count * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        return STARK_OK;
-    }
-    // send[i] (`bytes`, local rank R[i]) to rank `root`; recv: the root's buffer of W chunks, or null when the root is not local
-    int32_t gather(const std::vector<FriShardRank*>& R, const std::vector<const void*>& send, void* recv, size_t bytes, int root) {
-        if (!bytes) return STARK_OK;
-        if (!emulated) {
-            if (W == 1 && !ctx->comm) { STARK_HIP(ctx, hipMemcpyAsync(recv, send[0], bytes, hipMemcpyDeviceToDevice, ctx->stream)); return STARK_OK; }
-            return stark_comm_gather_dev(ctx, send[0], R[0]->rank == root ? recv : nullptr, bytes, root);
-        }
-        for (int p = 0; p < W; ++p) STARK_HIP(ctx, hipMemcpyAsync((char*)recv + (size_t)p * bytes, send[p], bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        return STARK_OK;
-    }
-};
-
 // ---- collective 0 of every entry point: all ranks hold the same arguments ------------------------------------------------------------------
 static constexpr size_t SHARD_HDR_WORDS = 72;         // magic, n0, L, r, seed_z, f0 given, schedule[0..64) (a dividing schedule has L <= 63), pad
-static int32_t shard_header_agree(stark_ctx* ctx, ShardColl& C, const std::vector<FriShardRank*>& R, size_t n0, const size_t* sched, size_t L, size_t r,
-                                  uint64_t seed_z, int f0_given) {
+static int32_t shard_header_agree(const ShardColl& C, std::vector<FriShardRank>& K, const FriShardPlan& P, size_t r, uint64_t seed_z, int f0_given) {
+    stark_ctx* ctx = C.ctx;
     std::vector<uint64_t> h(SHARD_HDR_WORDS, 0);
-    h[0] = 0x5348415244465249ull; h[1] = n0; h[2] = L; h[3] = r; h[4] = seed_z; h[5] = (uint64_t)f0_given;
-    for (size_t l = 0; l < L && l < 64; ++l) h[6 + l] = sched[l];
+    h[0] = 0x5348415244465249ull; h[1] = P.n0; h[2] = P.L; h[3] = r; h[4] = seed_z; h[5] = (uint64_t)f0_given;
+    for (size_t l = 0; l < P.L && l < 64; ++l) h[6 + l] = P.sched[l];
     const size_t bytes = SHARD_HDR_WORDS * 8;
     std::vector<void*> buf;
-    for (auto* K : R) {
-        STARK_TRY(coll_alloc(ctx, *K, (size_t)C.W * bytes));
-        STARK_HIP(ctx, hipMemcpyAsync((char*)K->coll.p + (size_t)K->rank * bytes, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-        buf.push_back(K->coll.p);
+    for (auto& k : K) {
+        STARK_TRY(coll_alloc(ctx, k, (size_t)C.W * bytes));
+        STARK_HIP(ctx, hipMemcpyAsync((char*)k.coll.p + (size_t)k.rank * bytes, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        buf.push_back(k.coll.p);
     }
-    STARK_TRY(C.all_gather(R, buf, bytes));
+    STARK_TRY(C.all_gather(buf, bytes));
     std::vector<uint64_t> all((size_t)C.W * SHARD_HDR_WORDS);
     bool same = true;
-    for (auto* K : R) {
-        STARK_HIP(ctx, hipMemcpyAsync(all.data(), K->coll.p, (size_t)C.W * bytes, hipMemcpyDeviceToHost, ctx->stream));
+    for (auto& k : K) {
+        STARK_HIP(ctx, hipMemcpyAsync(all.data(), k.coll.p, (size_t)C.W * bytes, hipMemcpyDeviceToHost, ctx->stream));
         STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t q = 0; q < (size_t)C.W; ++q) if (memcmp(all.data() + q * SHARD_HDR_WORDS, h.data(), bytes) != 0) same = false;
-        ctx_release(ctx, K->coll.release());
+        ctx_release(ctx, k.coll.release());
     }
     if (!same) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: the ranks disagree on (n0, L, schedule, r, seed_z, f0)");
     return STARK_OK;
 }
 
 // ---- build_f0 (fri.rs:535-569), sharded: column c is gathered to rank c mod W, the four digests are all-reduced, the merge is block-local ------
-// cols[i][c]: column c of local rank R[i] (its block of n0 / W rows); f0[i]: its block of f0.
-static int32_t shard_build_f0(stark_ctx* ctx, ShardColl& C, const std::vector<FriShardRank*>& R, size_t n0, const std::vector<std::array<const fr_t*, 4>>& cols,
+// cols[i][c]: column c of local rank i (its block of n0 / W rows); f0[i]: its block of f0.
+static int32_t shard_build_f0(const ShardColl& C, std::vector<FriShardRank>& K, size_t n0, const std::vector<std::array<const fr_t*, 4>>& cols,
                               const std::vector<fr_t*>& f0) {
-    const int W = C.W; const size_t nl = n0 / W;
+    stark_ctx* ctx = C.ctx; const int W = C.W; const size_t nl = n0 / W;
     static const char* const TAGS[4] = {"ALI/A", "ALI/S", "ALI/E", "ALI/T"};                                          // fri.rs:551-554
     // collectives 1-4: every column to the rank that runs its serial sponge
-    std::vector<DevBuf> whole(4 * R.size());
+    std::vector<DevBuf> whole(4 * K.size());
     for (int c = 0; c < 4; ++c) {
         const int root = c % W; void* recv = nullptr; std::vector<const void*> send;
-        for (size_t i = 0; i < R.size(); ++i) {
+        for (size_t i = 0; i < K.size(); ++i) {
             send.push_back(cols[i][c]);
-            if (R[i]->rank == root) { STARK_HIP(ctx, whole[4 * i + c].alloc(ctx, n0 * sizeof(fr_t))); recv = whole[4 * i + c].p; }
+            if (K[i].rank == root) { STARK_HIP(ctx, whole[4 * i + c].alloc(ctx, n0 * sizeof(fr_t))); recv = whole[4 * i + c].p; }
         }
-        STARK_TRY(C.gather(R, send, recv, nl * sizeof(fr_t), root));
+        STARK_TRY(C.gather(send, recv, nl * sizeof(fr_t), root));
     }
     // phase: the digests of the owned columns (one launch of four concurrent chains; a rank that owns fewer repeats its first column), in
     // rows c of a zeroed 4 x 4-word table
-    std::vector<DevBuf> dig(R.size()); std::vector<void*> buf;
-    for (size_t i = 0; i < R.size(); ++i) {
+    std::vector<DevBuf> dig(K.size()); std::vector<void*> buf;
+    for (size_t i = 0; i < K.size(); ++i) {
         STARK_HIP(ctx, dig[i].alloc(ctx, 8 * sizeof(fr_t)));          // rows 0..3: the table; 4..7: the four chains' outputs
         STARK_HIP(ctx, hipMemsetAsync(dig[i].p, 0, 4 * sizeof(fr_t), ctx->stream));
-        std::vector<int> own; for (int c = 0; c < 4; ++c) if (c % W == R[i]->rank) own.push_back(c);
+        std::vector<int> own; for (int c = 0; c < 4; ++c) if (c % W == K[i].rank) own.push_back(c);
         if (!own.empty()) {
             const char* tags[4]; const fr_t* cp[4];
             for (int j = 0; j < 4; ++j) { const int c = own[j < (int)own.size() ? j : 0]; tags[j] = TAGS[c]; cp[j] = whole[4 * i + c].fr(); }
@@ -162,19 +125,16 @@ static int32_t shard_build_f0(stark_ctx* ctx, ShardColl& C, const std::vector<Fr
     // collective 5: every row is non-zero on exactly one rank, so the SUM is the selection
     STARK_TRY(C.all_reduce(buf, 16));
     for (auto& w : whole) if (w.p) ctx_release(ctx, w.release());
-    // phase: (seed, z, beta) from the four digests (fri.rs:556-560), then the block-local merge at global positions
+    // phase: (seed, z, beta) from the four digests, then the block-local merge at global positions
     const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));                                             // FriDomain::new_radix2(n0).omega, fri.rs:53-56
-    for (size_t i = 0; i < R.size(); ++i) {
-        fr_t h[5]; STARK_HIP(ctx, hipMemcpyAsync(h, dig[i].p, 4 * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        h[4] = host::h_u64(n0);
-        fr_t seed_f; STARK_TRY(tr_hash_host1(ctx, "ALI/seed", std::vector<fr_t>(h, h + 5), &seed_f));
-        fr_t z, beta; STARK_TRY(ali_sample_z_beta(ctx, "ALI/DEEP", n0, seed_f, &z, &beta));
+    for (size_t i = 0; i < K.size(); ++i) {
+        fr_t h[4]; STARK_HIP(ctx, hipMemcpyAsync(h, dig[i].p, 4 * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        fr_t seed_f, z, beta; STARK_TRY(ali_challenges(ctx, h, n0, &seed_f, &z, &beta));
         STARK_TRY(ali_merge_dev_impl(ctx, cols[i][0], cols[i][1], cols[i][2], cols[i][3], nullptr, host::h_zero(), omega, z, nl, f0[i], nullptr,
-                                     (uint64_t)R[i]->rank * nl, n0, false));
+                                     (uint64_t)K[i].rank * nl, n0, false));
     }
     return STARK_OK;
 }
-
 // ---- the commit phase (fri.rs:231-312; DistProver.commit) ------------------------------------------------------------------------------------
 // phase 0: layer buffers, the copy of f0 and the block-local folds; the transition layer T is folded straight into this rank's chunk of the
 //          whole layer.  Collective 6: all-gather of layer T (in place).
@@ -205,30 +165,15 @@ static int32_t shard_commit_phase(stark_ctx* ctx, const FriShardPlan& P, FriShar
         top_words = 0; for (size_t l = 0; l <= L; ++l) if (P.sharded[l]) top_words += P.stop[l];
         if (top_words) STARK_TRY(coll_alloc(ctx, K, W * top_words * sizeof(fr_t)));
         size_t toff = 0;
-        for (size_t l = 0; l <= L; ++l) {
-            const size_t m = P.m(l), arity = P.arity[l];
-            stark_tree* T = nullptr;
-            if (P.sharded[l]) {
-                const size_t nl = P.n[l] / W;
-                const fr_t* f_next = l == L ? nullptr : P.sharded[l + 1] ? K.f[l + 1] : K.f[l + 1] + q * (nl / m);        // this block's parents, fri.rs:283
-                void* h = nullptr; STARK_TRY(ctx_alloc(ctx, nl * sizeof(fr_t), &h));
-                int32_t rc = leaf_pair_hash_on(ctx, st, K.f[l], f_next, nl, m, (fr_t*)h);
-                if (rc == STARK_OK) rc = merkle_build_on(ctx, st, mps[l], arity, (uint64_t)l, (const fr_t*)h, nl, 0, nullptr, 1, (uint64_t)q * nl, 0, P.stop[l], /*adopt=*/true, &T);
-                if (rc) { if (!T) ctx_release(ctx, h); return rc; }
-                K.tree[l] = T;
-                if (T->lens.back() != P.stop[l]) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: lower tree stopped at an unplanned level");
-                STARK_HIP(ctx, hipMemcpyAsync(K.coll.fr() + q * top_words + toff, T->levels.back(), P.stop[l] * sizeof(fr_t), hipMemcpyDeviceToDevice, st));
-                toff += P.stop[l];
-            } else if (P.hashed[l]) {
-                void* h = nullptr; STARK_TRY(ctx_alloc(ctx, P.n[l] * sizeof(fr_t), &h));
-                int32_t rc = leaf_pair_hash_on(ctx, st, K.f[l], l < L ? K.f[l + 1] : nullptr, P.n[l], m, (fr_t*)h);
-                if (rc == STARK_OK) rc = merkle_build_on(ctx, st, mps[l], arity, (uint64_t)l, (const fr_t*)h, P.n[l], 0, nullptr, 1, 0, 0, 0, true, &T);
-                if (rc) { if (!T) ctx_release(ctx, h); return rc; }
-                K.tree[l] = T;
-            } else {                                              // commit_pairs(f_l, s_l), fri.rs:289 (s_l = f_{l+1}[i / m], zeros on the last layer)
-                STARK_TRY(merkle_build_on(ctx, st, mps[l], arity, (uint64_t)l, K.f[l], P.n[l], 1, l < L ? K.f[l + 1] : nullptr, m, 0, 0, 0, false, &T));
-                K.tree[l] = T;
-            }
+        for (size_t l = 0; l <= L; ++l) {                         // a sharded layer: its lower tree at global DS positions; a replicated one: the whole tree
+            const bool sh = P.sharded[l]; const size_t nl = P.here(l), m = P.m(l);
+            const fr_t* f_next = l == L ? nullptr : !sh || P.sharded[l + 1] ? K.f[l + 1] : K.f[l + 1] + q * (nl / m);    // this block's parents, fri.rs:283
+            STARK_TRY(commit_layer_on(ctx, st, mps[l], P.arity[l], l, K.f[l], f_next, nl, m, sh ? q * nl : 0, sh ? P.stop[l] : 0, &K.tree[l]));
+            if (!sh) continue;
+            const stark_tree* T = K.tree[l];
+            if (T->lens.back() != P.stop[l]) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: lower tree stopped at an unplanned level");
+            STARK_HIP(ctx, hipMemcpyAsync(K.coll.fr() + q * top_words + toff, T->levels.back(), P.stop[l] * sizeof(fr_t), hipMemcpyDeviceToDevice, st));
+            toff += P.stop[l];
         }
         return STARK_OK;
     }
@@ -254,25 +199,21 @@ static int32_t shard_commit_phase(stark_ctx* ctx, const FriShardPlan& P, FriShar
     if (K.coll.p) ctx_release(ctx, K.coll.release());
     return STARK_OK;
 }
-static int32_t shard_commit(stark_ctx* ctx, ShardColl& C, const FriShardPlan& P, const std::vector<FriShardRank*>& R, const std::vector<const fr_t*>& f0_local, uint64_t seed_z) {
-    const size_t L = P.L;
-    // everything that may upload constants (and synchronise doing so) first: transcript and Merkle parameters, the challenges (fri.rs:250)
-    stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
-    std::vector<stark_params*> mps(L + 1, nullptr);
-    for (size_t l = 0; l <= L; ++l) STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(P.arity[l]), &mps[l]));   // MerkleChannelCfg::new(arity), fri.rs:277
-    std::vector<fr_t> z(L); for (size_t l = 0; l < L; ++l) STARK_TRY(sample_z(ctx, seed_z, l, P.n[l], &z[l]));
+static int32_t shard_commit(const ShardColl& C, const FriShardPlan& P, std::vector<FriShardRank>& K, const std::vector<const fr_t*>& f0_local, uint64_t seed_z) {
+    stark_ctx* ctx = C.ctx; const size_t L = P.L;
+    std::vector<stark_params*> mps; std::vector<fr_t> z; STARK_TRY(fri_prelude(ctx, P.n, P.arity, seed_z, mps, z));
     size_t top_words = 0;
-    for (size_t i = 0; i < R.size(); ++i) STARK_TRY(shard_commit_phase(ctx, P, *R[i], 0, f0_local[i], z, mps, top_words));
+    for (size_t i = 0; i < K.size(); ++i) STARK_TRY(shard_commit_phase(ctx, P, K[i], 0, f0_local[i], z, mps, top_words));
     if (P.T <= L) {                                                                        // collective 6: the first replicated layer
-        std::vector<void*> buf; for (auto* K : R) buf.push_back(K->f[P.T]);
-        STARK_TRY(C.all_gather(R, buf, P.n[P.T] / P.W * sizeof(fr_t)));
+        std::vector<void*> buf; for (auto& k : K) buf.push_back(k.f[P.T]);
+        STARK_TRY(C.all_gather(buf, P.n[P.T] / P.W * sizeof(fr_t)));
     }
-    for (size_t i = 0; i < R.size(); ++i) STARK_TRY(shard_commit_phase(ctx, P, *R[i], 1, f0_local[i], z, mps, top_words));
+    for (size_t i = 0; i < K.size(); ++i) STARK_TRY(shard_commit_phase(ctx, P, K[i], 1, f0_local[i], z, mps, top_words));
     if (top_words) {                                                                       // collective 7: the crossing levels of every sharded layer
-        std::vector<void*> buf; for (auto* K : R) buf.push_back(K->coll.p);
-        STARK_TRY(C.all_gather(R, buf, top_words * sizeof(fr_t)));
+        std::vector<void*> buf; for (auto& k : K) buf.push_back(k.coll.p);
+        STARK_TRY(C.all_gather(buf, top_words * sizeof(fr_t)));
     }
-    for (size_t i = 0; i < R.size(); ++i) STARK_TRY(shard_commit_phase(ctx, P, *R[i], 2, f0_local[i], z, mps, top_words));
+    for (size_t i = 0; i < K.size(); ++i) STARK_TRY(shard_commit_phase(ctx, P, K[i], 2, f0_local[i], z, mps, top_words));
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));                                     // the roots are on the host
     return STARK_OK;
 }
@@ -281,74 +222,53 @@ static int32_t shard_commit(stark_ctx* ctx, ShardColl& C, const FriShardPlan& P,
 // phase 3: the plan from the roots (the same on every rank); this rank's requests into their rows of a zeroed nreq x 4 table, one launch.
 // Collective 8: all-reduce SUM.  Phase 4: one download, then assemble_proof (the same canonical bytes on every rank).
 static int32_t shard_query_fill(stark_ctx* ctx, const FriShardPlan& P, FriShardRank& K, const FriPlan& plan) {
-    const size_t nreq = plan.req.size(), W = P.W; const uint64_t q = (uint64_t)K.rank;
+    const size_t nreq = plan.req.size();
     STARK_TRY(coll_alloc(ctx, K, std::max<size_t>(nreq, 1) * sizeof(fr_t)));
     STARK_HIP(ctx, hipMemsetAsync(K.coll.p, 0, nreq * sizeof(fr_t), ctx->stream));
-    std::vector<const fr_t*> base; std::vector<size_t> lens; std::map<std::pair<uint32_t, uint32_t>, uint32_t> slot;   // (tree id, level) -> source
-    for (size_t l = 0; l <= P.L; ++l) { base.push_back(K.f[l]); lens.push_back(P.here(l)); }
-    auto level_src = [&](stark_tree* T, uint32_t tid, uint32_t v) {
-        auto it = slot.find({tid, v});
-        if (it == slot.end()) { it = slot.emplace(std::make_pair(tid, v), (uint32_t)base.size()).first; base.push_back(T->levels[v]); lens.push_back(T->lens[v]); }
-        return it->second;
-    };
-    std::vector<uint32_t> src; std::vector<uint64_t> idx, row;
-    for (size_t i = 0; i < nreq; ++i) {
-        const FriRequest& r = plan.req[i];
+    // a value of a sharded layer or of a lower tree is owned by the rank whose block holds it, any other (replicated layer, tree top) by rank 0
+    auto resolve = [&](const FriRequest& r, FriOpening& o) -> int32_t {
         if (r.which > P.L) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: layer out of range");
-        const size_t l = r.which; uint64_t owner = 0, loc = r.index; uint32_t s = 0;
+        const size_t l = r.which;
         if (r.kind == 0) {
-            if (P.sharded[l]) { const uint64_t nl = P.n[l] / W; owner = r.index / nl; loc = r.index % nl; }
-            s = (uint32_t)l;
-        } else {
-            stark_tree* T = K.tree[l]; const uint32_t nlev = (uint32_t)T->levels.size();
-            if (P.sharded[l] && r.level + 1 < nlev) { const uint64_t ln = T->lens[r.level]; owner = r.index / ln; loc = r.index % ln; s = level_src(T, 2 * (uint32_t)l, r.level); }
-            else if (P.sharded[l]) {
-                stark_tree* U = K.top[l]; const uint32_t v = r.level - (nlev - 1);
-                if (v >= U->levels.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: tree level out of range");
-                s = level_src(U, 2 * (uint32_t)l + 1, v);
-            } else {
-                if (r.level >= nlev) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: tree level out of range");
-                s = level_src(T, 2 * (uint32_t)l, r.level);
-            }
+            o = {K.f[l], P.here(l), 0, r.index};
+            if (P.sharded[l]) { const uint64_t nl = P.n[l] / P.W; o.owner = r.index / nl; o.index = r.index % nl; }
+            return STARK_OK;
         }
-        if (owner != q) continue;
-        if (loc >= lens[s]) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: opening index out of range");
-        src.push_back(s); idx.push_back(loc); row.push_back(i);
-    }
-    const size_t k = src.size();
-    if (!k) return STARK_OK;
-    DevBuf db, ds, di, dr;
-    STARK_HIP(ctx, db.alloc(ctx, base.size() * sizeof(void*))); STARK_HIP(ctx, ds.alloc(ctx, k * 4)); STARK_HIP(ctx, di.alloc(ctx, k * 8)); STARK_HIP(ctx, dr.alloc(ctx, k * 8));
-    STARK_HIP(ctx, hipMemcpyAsync(db.p, base.data(), base.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
-    STARK_HIP(ctx, hipMemcpyAsync(ds.p, src.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
-    STARK_HIP(ctx, hipMemcpyAsync(di.p, idx.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
-    STARK_HIP(ctx, hipMemcpyAsync(dr.p, row.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)db.p, (const uint32_t*)ds.p, (const uint64_t*)di.p,
-                       (const uint64_t*)dr.p, (uint64_t)k, K.coll.fr());
-    STARK_HIP(ctx, hipGetLastError());
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the host index arrays above go out of scope
-    return STARK_OK;
+        const stark_tree* T = K.tree[l]; const uint32_t nlev = (uint32_t)T->levels.size();
+        if (P.sharded[l] && r.level + 1 < nlev) { const uint64_t ln = T->lens[r.level]; o = {T->levels[r.level], T->lens[r.level], r.index / ln, r.index % ln}; }
+        else if (P.sharded[l]) {
+            const stark_tree* U = K.top[l]; const uint32_t v = r.level - (nlev - 1);
+            if (v >= U->levels.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: tree level out of range");
+            o = {U->levels[v], U->lens[v], 0, r.index};
+        } else {
+            if (r.level >= nlev) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: tree level out of range");
+            o = {T->levels[r.level], T->lens[r.level], 0, r.index};
+        }
+        return STARK_OK;
+    };
+    return gather_openings(ctx, plan, (uint64_t)K.rank, resolve, K.coll.fr(), nullptr);
 }
-static int32_t shard_queries(stark_ctx* ctx, ShardColl& C, const FriShardPlan& P, const std::vector<FriShardRank*>& R, size_t r, std::vector<stark_proof*>& out) {
+static int32_t shard_queries(const ShardColl& C, const FriShardPlan& P, std::vector<FriShardRank>& K, size_t r, std::vector<stark_proof*>& out) {
+    stark_ctx* ctx = C.ctx;
     FriPlan plan; plan.r = r;
-    { std::string err; if (!plan.shape.make(P.n0, P.sched.data(), P.L, R[0]->roots.data(), err)) return ctx->fail(STARK_ERR_INVALID_ARG, err); }
+    { std::string err; if (!plan.shape.make(P.n0, P.sched.data(), P.L, K[0].roots.data(), err)) return ctx->fail(STARK_ERR_INVALID_ARG, err); }
     DeviceHasher H0(ctx); MemoHasher H(H0);
     { int32_t rc = fri_plan_make(plan, H); if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: bad index"); if (rc) return rc; }
     const size_t nreq = plan.req.size();
     std::vector<void*> buf;
-    for (auto* K : R) {
-        if (memcmp(K->roots.data(), R[0]->roots.data(), K->roots.size() * sizeof(fr_t)) != 0) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: virtual ranks hold different roots");
-        STARK_TRY(shard_query_fill(ctx, P, *K, plan)); buf.push_back(K->coll.p);
+    for (auto& k : K) {
+        if (memcmp(k.roots.data(), K[0].roots.data(), k.roots.size() * sizeof(fr_t)) != 0) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: virtual ranks hold different roots");
+        STARK_TRY(shard_query_fill(ctx, P, k, plan)); buf.push_back(k.coll.p);
     }
     STARK_TRY(C.all_reduce(buf, nreq * 4));                                                                // collective 8
-    for (auto* K : R) {
-        K->table.assign(nreq, host::h_zero());
-        if (nreq) STARK_HIP(ctx, hipMemcpyAsync(K->table.data(), K->coll.p, nreq * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
+    for (auto& k : K) {
+        k.table.assign(nreq, host::h_zero());
+        if (nreq) STARK_HIP(ctx, hipMemcpyAsync(k.table.data(), k.coll.p, nreq * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (auto* K : R) {
-        ctx_release(ctx, K->coll.release());
-        ReplaySource rep(K->table.data(), nreq);
+    for (auto& k : K) {
+        ctx_release(ctx, k.coll.release());
+        ReplaySource rep(k.table.data(), nreq);
         stark_proof* Pf = new stark_proof();
         int32_t rc = assemble_proof(plan.shape, r, H, rep, Pf->bytes, Pf->size_estimate);
         if (rc == -1 || (rc == 0 && rep.pos != nreq)) rc = ctx->fail(STARK_ERR_INVALID_ARG, "query phase: value list does not match the plan");
@@ -358,58 +278,67 @@ static int32_t shard_queries(stark_ctx* ctx, ShardColl& C, const FriShardPlan& P
     return STARK_OK;
 }
 
-// ---- handles and drivers ---------------------------------------------------------------------------------------------------------------------
-struct stark_fri_shard {
-    CtxRef ref_;
-    stark_ctx* ctx = nullptr; uint64_t seed_z = 0;
-    FriShardPlan P; FriShardRank K;
-};
-
-// checks that need neither a device nor a peer: done by every rank before its first collective
+// ---- the drivers: one per operation, for the local ranks of a ShardColl -------------------------------------------------------------------
+// Array arguments are this rank's blocks, or the whole arrays when C is emulated (ShardColl::block).  Every argument check runs before the
+// first collective.
 static int32_t shard_args(stark_ctx* ctx, int W, size_t n0, const size_t* sched, size_t L, FriShardPlan& P) {
     std::string err;
     if (!fri_shard_plan(n0, sched, L, W, P, err)) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: " + err);
     return STARK_OK;
 }
-static void shard_world(stark_ctx* ctx, int& W, int& rank) { W = ctx->comm ? stark_comm_size(ctx) : 1; rank = ctx->comm ? stark_comm_rank(ctx) : 0; }
-
-static int32_t shard_build_run(stark_ctx* ctx, const fr_t* f0_block, size_t n0, const size_t* sched, size_t L, uint64_t seed_z, stark_fri_shard** out) {
-    int W, rank; shard_world(ctx, W, rank);
-    stark_fri_shard* S = new stark_fri_shard(); S->ref_.bind(ctx); S->ctx = ctx; S->seed_z = seed_z; S->K.ctx = ctx; S->K.rank = rank;
-    int32_t rc = shard_args(ctx, W, n0, sched, L, S->P);
-    ShardColl C{ctx, W, false}; std::vector<FriShardRank*> R{&S->K};
-    if (rc == STARK_OK) rc = shard_header_agree(ctx, C, R, n0, sched, L, 0, seed_z, 1);
-    if (rc == STARK_OK) rc = shard_commit(ctx, C, S->P, R, std::vector<const fr_t*>{f0_block}, seed_z);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); delete S; return rc; }
-    *out = S; return STARK_OK;
+static void shard_ranks(const ShardColl& C, std::vector<FriShardRank>& K) {
+    K = std::vector<FriShardRank>(C.local());
+    for (size_t i = 0; i < K.size(); ++i) { K[i].ctx = C.ctx; K[i].rank = C.rank(i); }
 }
-static int32_t shard_prove_run(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t* f0_opt, size_t n0, const size_t* sched, size_t L,
-                               size_t r, uint64_t seed_z, stark_proof** out) {
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-    int W, rank; shard_world(ctx, W, rank);
-    FriShardPlan P; STARK_TRY(shard_args(ctx, W, n0, sched, L, P));
+// the commit phase: P and K (one state per local rank) hold the result
+static int32_t shard_build(const ShardColl& C, const fr_t* f0, size_t n0, const size_t* sched, size_t L, uint64_t seed_z, FriShardPlan& P, std::vector<FriShardRank>& K) {
+    STARK_TRY(shard_args(C.ctx, C.W, n0, sched, L, P));
+    shard_ranks(C, K);
+    std::vector<const fr_t*> f0s; for (size_t i = 0; i < K.size(); ++i) f0s.push_back(f0 + C.block(i) * (n0 / C.W));
+    int32_t rc = shard_header_agree(C, K, P, 0, seed_z, 1);
+    if (rc == STARK_OK) rc = shard_commit(C, P, K, f0s, seed_z);
+    if (rc) (void)hipStreamSynchronize(C.ctx->stream);                                     // before the caller frees the state
+    return rc;
+}
+// the prove, from f0 or from the four columns: out[i] receives local rank i's proof (the same bytes on every rank)
+static int32_t shard_prove(const ShardColl& C, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t* f0_opt, size_t n0, const size_t* sched, size_t L,
+                           size_t r, uint64_t seed_z, stark_proof** out) {
+    stark_ctx* ctx = C.ctx;
+    FriShardPlan P; STARK_TRY(shard_args(ctx, C.W, n0, sched, L, P));
     if (!is_pow2(n0) || n0 <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two (radix-2 domain)");
     if (!r) return ctx->fail(STARK_ERR_INVALID_ARG, "r >= 1");
-    const auto t0 = now();
-    FriShardRank K; K.ctx = ctx; K.rank = rank;
-    ShardColl C{ctx, W, false}; std::vector<FriShardRank*> R{&K};
-    STARK_TRY(shard_header_agree(ctx, C, R, n0, sched, L, r, seed_z, f0_opt ? 1 : 0));
-    DevBuf f0buf; const fr_t* f0 = f0_opt;
-    if (!f0) {
-        STARK_HIP(ctx, f0buf.alloc(ctx, n0 / W * sizeof(fr_t)));
-        STARK_TRY(shard_build_f0(ctx, C, R, n0, {std::array<const fr_t*, 4>{a, s, e, t}}, {f0buf.fr()}));
-        f0 = f0buf.fr();
+    const size_t nl = n0 / C.W;
+    for (size_t i = 0; i < C.local(); ++i) out[i] = nullptr;
+    const auto t0 = Clock::now();
+    std::vector<FriShardRank> K; shard_ranks(C, K);
+    STARK_TRY(shard_header_agree(C, K, P, r, seed_z, f0_opt ? 1 : 0));
+    DevBuf f0buf; std::vector<const fr_t*> f0;
+    if (f0_opt) { for (size_t i = 0; i < K.size(); ++i) f0.push_back(f0_opt + C.block(i) * nl); }
+    else {
+        STARK_HIP(ctx, f0buf.alloc(ctx, K.size() * nl * sizeof(fr_t)));
+        std::vector<std::array<const fr_t*, 4>> cols; std::vector<fr_t*> dst;
+        for (size_t i = 0; i < K.size(); ++i) {
+            const size_t o = C.block(i) * nl;
+            cols.push_back({a + o, s + o, e + o, t + o}); dst.push_back(f0buf.fr() + i * nl); f0.push_back(dst.back());
+        }
+        STARK_TRY(shard_build_f0(C, K, n0, cols, dst));
     }
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const auto t1 = now();
-    STARK_TRY(shard_commit(ctx, C, P, R, {f0}, seed_z));
-    const auto t2 = now();
-    std::vector<stark_proof*> pf; STARK_TRY(shard_queries(ctx, C, P, R, r, pf));
-    const auto t3 = now();
-    pf[0]->ms[0] = ms(t0, t1); pf[0]->ms[1] = ms(t1, t2); pf[0]->ms[2] = ms(t2, t3);
-    *out = pf[0]; return STARK_OK;
+    const auto t1 = Clock::now();
+    STARK_TRY(shard_commit(C, P, K, f0, seed_z));
+    const auto t2 = Clock::now();
+    std::vector<stark_proof*> pf; STARK_TRY(shard_queries(C, P, K, r, pf));
+    const auto t3 = Clock::now();
+    for (size_t i = 0; i < pf.size(); ++i) { pf[i]->ms[0] = ms_between(t0, t1); pf[i]->ms[1] = ms_between(t1, t2); pf[i]->ms[2] = ms_between(t2, t3); out[i] = pf[i]; }
+    return STARK_OK;
 }
+
+struct stark_fri_shard {
+    CtxRef ref_;
+    ShardColl C; uint64_t seed_z = 0;                        // the collective of the build, which the query phase reuses
+    FriShardPlan P; std::vector<FriShardRank> K;             // K: the one local rank
+    stark_fri_shard(stark_ctx* ctx, uint64_t z) : C(ShardColl::real(ctx)), seed_z(z) { ref_.bind(ctx); }
+};
 
 extern "C" {
 
@@ -423,82 +352,48 @@ int32_t stark_fri_shard_layout(size_t n0, const size_t* schedule, size_t L, int3
 int32_t stark_fri_build_sharded_dev(stark_ctx_t* ctx, const uint64_t* f0_block, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_shard_t** out) {
     if (!ctx || !f0_block || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return shard_build_run(ctx, as_fr(f0_block), n0, schedule, L, seed_z, out);
+    stark_fri_shard* S = new stark_fri_shard(ctx, seed_z);
+    int32_t rc = shard_build(S->C, as_fr(f0_block), n0, schedule, L, seed_z, S->P, S->K);
+    if (rc) { delete S; return rc; }
+    *out = S; return STARK_OK;
 }
 int32_t stark_fri_shard_num_layers(stark_fri_shard_t* h) { return h ? (int32_t)(h->P.L + 1) : STARK_ERR_INVALID_ARG; }
 int32_t stark_fri_shard_root(stark_fri_shard_t* h, int32_t l, uint64_t* out4) {
     if (!h || !out4 || l < 0 || (size_t)l > h->P.L) return STARK_ERR_INVALID_ARG;
-    store_fr(out4, h->K.roots[l]); return STARK_OK;
+    store_fr(out4, h->K[0].roots[l]); return STARK_OK;
 }
 int32_t stark_fri_shard_is_sharded(stark_fri_shard_t* h, int32_t l) { return (h && l >= 0 && (size_t)l <= h->P.L) ? (int32_t)h->P.sharded[l] : STARK_ERR_INVALID_ARG; }
 int32_t stark_fri_shard_free(stark_fri_shard_t* h) { if (!h) return STARK_ERR_INVALID_ARG; delete h; return STARK_OK; }   // layers and levels return to the pool
 int32_t stark_fri_shard_prove_queries(stark_fri_shard_t* h, size_t r, stark_proof_t** out) {
     if (!h || !out) return STARK_ERR_INVALID_ARG;
-    stark_ctx* ctx = h->ctx; STARK_TRY(ctx_enter(ctx));
+    stark_ctx* ctx = h->C.ctx; STARK_TRY(ctx_enter(ctx));
     if (!r) return ctx->fail(STARK_ERR_INVALID_ARG, "r >= 1");
-    ShardColl C{ctx, h->P.W, false}; std::vector<FriShardRank*> R{&h->K};
-    STARK_TRY(shard_header_agree(ctx, C, R, h->P.n0, h->P.sched.data(), h->P.L, r, h->seed_z, 1));
-    std::vector<stark_proof*> pf; STARK_TRY(shard_queries(ctx, C, h->P, R, r, pf));
+    STARK_TRY(shard_header_agree(h->C, h->K, h->P, r, h->seed_z, 1));
+    std::vector<stark_proof*> pf; STARK_TRY(shard_queries(h->C, h->P, h->K, r, pf));
     *out = pf[0]; return STARK_OK;
 }
 int32_t stark_deep_fri_prove_sharded_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, const uint64_t* f0_opt, size_t n0,
                                          const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out) {
     if (!ctx || !out || (!schedule && L) || (!f0_opt && (!a || !s || !e || !t))) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return shard_prove_run(ctx, as_fr(a), as_fr(s), as_fr(e), as_fr(t), as_fr(f0_opt), n0, schedule, L, r, seed_z, out);
+    return shard_prove(ShardColl::real(ctx), as_fr(a), as_fr(s), as_fr(e), as_fr(t), as_fr(f0_opt), n0, schedule, L, r, seed_z, out);
 }
 
-// Diagnostic twins: `nranks` virtual ranks on this one GPU, the same phases, every collective as device copies.
+// Diagnostic twins: `nranks` virtual ranks on this one GPU, the same drivers, every collective as device copies.
 int32_t stark_diag_fri_build_sharded_emulated_dev(stark_ctx_t* ctx, int32_t nranks, const uint64_t* f0_whole, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z,
                                                   uint64_t* roots_out) {
     if (!ctx || !f0_whole || !roots_out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    FriShardPlan P; STARK_TRY(shard_args(ctx, nranks, n0, schedule, L, P));
-    const int W = nranks; const size_t nl = n0 / W;
-    std::vector<FriShardRank> K(W); std::vector<FriShardRank*> R; std::vector<const fr_t*> f0;
-    for (int q = 0; q < W; ++q) { K[q].ctx = ctx; K[q].rank = q; R.push_back(&K[q]); f0.push_back(as_fr(f0_whole) + (size_t)q * nl); }
-    ShardColl C{ctx, W, true};
-    STARK_TRY(shard_header_agree(ctx, C, R, n0, schedule, L, 0, seed_z, 1));
-    int32_t rc = shard_commit(ctx, C, P, R, f0, seed_z);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    for (int q = 0; q < W; ++q) for (size_t l = 0; l <= L; ++l) store_fr(roots_out + ((size_t)q * (L + 1) + l) * 4, K[q].roots[l]);
+    FriShardPlan P; std::vector<FriShardRank> K;
+    STARK_TRY(shard_build(ShardColl::emulate(ctx, nranks), as_fr(f0_whole), n0, schedule, L, seed_z, P, K));
+    for (size_t q = 0; q < K.size(); ++q) for (size_t l = 0; l <= L; ++l) store_fr(roots_out + (q * (L + 1) + l) * 4, K[q].roots[l]);
     return STARK_OK;
 }
 int32_t stark_diag_deep_fri_prove_sharded_emulated_dev(stark_ctx_t* ctx, int32_t nranks, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t,
                                                        const uint64_t* f0_opt, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out) {
     if (!ctx || !out || (!schedule && L) || (!f0_opt && (!a || !s || !e || !t))) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    FriShardPlan P; STARK_TRY(shard_args(ctx, nranks, n0, schedule, L, P));
-    if (!is_pow2(n0) || n0 <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two (radix-2 domain)");
-    if (!r) return ctx->fail(STARK_ERR_INVALID_ARG, "r >= 1");
-    const int W = nranks; const size_t nl = n0 / W;
-    for (int q = 0; q < W; ++q) out[q] = nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
-    const auto t0 = now();
-    std::vector<FriShardRank> K(W); std::vector<FriShardRank*> R; std::vector<const fr_t*> f0;
-    for (int q = 0; q < W; ++q) { K[q].ctx = ctx; K[q].rank = q; R.push_back(&K[q]); }
-    ShardColl C{ctx, W, true};
-    STARK_TRY(shard_header_agree(ctx, C, R, n0, schedule, L, r, seed_z, f0_opt ? 1 : 0));
-    DevBuf f0buf;
-    if (f0_opt) { for (int q = 0; q < W; ++q) f0.push_back(as_fr(f0_opt) + (size_t)q * nl); }
-    else {
-        STARK_HIP(ctx, f0buf.alloc(ctx, n0 * sizeof(fr_t)));
-        std::vector<std::array<const fr_t*, 4>> cols; std::vector<fr_t*> dst;
-        for (int q = 0; q < W; ++q) {
-            const size_t o = (size_t)q * nl;
-            cols.push_back({as_fr(a) + o, as_fr(s) + o, as_fr(e) + o, as_fr(t) + o}); dst.push_back(f0buf.fr() + o); f0.push_back(f0buf.fr() + o);
-        }
-        STARK_TRY(shard_build_f0(ctx, C, R, n0, cols, dst));
-    }
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const auto t1 = now();
-    STARK_TRY(shard_commit(ctx, C, P, R, f0, seed_z));
-    const auto t2 = now();
-    std::vector<stark_proof*> pf; STARK_TRY(shard_queries(ctx, C, P, R, r, pf));
-    const auto t3 = now();
-    for (int q = 0; q < W; ++q) { pf[q]->ms[0] = ms(t0, t1); pf[q]->ms[1] = ms(t1, t2); pf[q]->ms[2] = ms(t2, t3); out[q] = pf[q]; }
-    return STARK_OK;
+    return shard_prove(ShardColl::emulate(ctx, nranks), as_fr(a), as_fr(s), as_fr(e), as_fr(t), as_fr(f0_opt), n0, schedule, L, r, seed_z, out);
 }
 
 }  // extern "C"
