@@ -212,6 +212,15 @@ int32_t stark_proof_free(stark_proof_t* p);
  * DeepFriParams.seed_z, carried for signature parity (the reference's verifier does not read it).  Host index logic in the
  * library, every hash (leaf pairs, DS nodes) batched onto the GPU kernels of the prover. */
 int32_t stark_deep_fri_verify(stark_ctx_t* ctx, const uint8_t* proof, size_t len, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, int32_t* accepted);
+/* deep_fri_verify (fri.rs:643-762) over `batch` canonical proofs at once; accepted[i] == what stark_deep_fri_verify answers for proofs[i]
+ * alone, for every input (honest, tampered, truncated, empty, other n0).  The proofs share one schedule and r; each proof's n0 is read from
+ * its own bytes.  The host plans every hash of every proof (they depend on the indices inside the proofs, never on hash values); the
+ * device runs the openings of all proofs that sit at the same tree depth in one launch per Poseidon width, then compares the roots, and
+ * the decisions come back with one synchronisation.  A proof that does not decode or fails a structural check is a rejection, never an
+ * error.  batch == 0 returns STARK_OK.  STARK_ERR_INVALID_ARG: a null ctx or accepted (batch > 0), null proofs or lens, a null proofs[i]
+ * with lens[i] != 0, a null schedule with L > 0.  On any error every accepted[i] is 0.  seed_z is carried but unused, as above. */
+int32_t stark_deep_fri_verify_batch(stark_ctx_t* ctx, size_t batch, const uint8_t* const* proofs, const size_t* lens, const size_t* schedule, size_t L, size_t r,
+                                    uint64_t seed_z, int32_t* accepted);
 /* MerkleProver::new(MerkleChannelCfg::new(cfg_arity).with_tree_label(tree_label)).verify_single / .verify_pairs
  * (merkle/src/lib.rs:800-812, 841-855 over verify_many_ds :587-722 and verify_pairs_ds :723-773); `proof` = the canonical
  * MerkleProof encoding stark_merkle_open returns. */

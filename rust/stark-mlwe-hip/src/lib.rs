@@ -310,6 +310,14 @@ pub mod fri {
         ctx.chk(unsafe { stark_deep_fri_verify(ctx.raw, proof_bytes.as_ptr(), proof_bytes.len(), schedule.as_ptr(), schedule.len(), r, seed_z, &mut ok) });
         ok == 1
     }
+    /// `deep_fri_verify` over many proofs of one schedule and r in one device pass: element i == `deep_fri_verify(ctx, schedule, r, seed_z, proofs[i])`.
+    pub fn deep_fri_verify_batch(ctx: &Ctx, schedule: &[usize], r: usize, seed_z: u64, proofs: &[&[u8]]) -> Vec<bool> {
+        let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+        let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let mut ok = vec![0i32; proofs.len()];
+        ctx.chk(unsafe { stark_deep_fri_verify_batch(ctx.raw, proofs.len(), ptrs.as_ptr(), lens.as_ptr(), schedule.as_ptr(), schedule.len(), r, seed_z, ok.as_mut_ptr()) });
+        ok.into_iter().map(|a| a == 1).collect()
+    }
     /// `deep_ali_merge_evals(a, s, e, t, omega, z) -> (f0, z, c*)` — deep_ali/src/lib.rs:48-105.
     pub fn deep_ali_merge_evals(ctx: &Ctx, a: &[F], s: &[F], e: &[F], t: &[F], omega: F, z: F) -> (Vec<F>, F, F) {
         let n = a.len();

@@ -91,6 +91,7 @@ SIGNATURES = {
     "stark_proof_stage_ms": (C.c_double, [vp, i32]),
     "stark_proof_free": (i32, [vp]),
     "stark_deep_fri_verify": (i32, [vp, vp, sz, vp, sz, sz, u64, C.POINTER(i32)]),
+    "stark_deep_fri_verify_batch": (i32, [vp, sz, vp, vp, vp, sz, sz, u64, vp]),
     "stark_merkle_verify_many_ds": (i32, [vp, sz, u64, vp, vp, sz, vp, vp, sz, C.POINTER(i32)]),
     "stark_merkle_verify_pairs_ds": (i32, [vp, sz, u64, vp, vp, sz, vp, vp, vp, sz, C.POINTER(i32)]),
     "stark_commitment_commit": (i32, [vp, u64, vp, sz, vpp]),

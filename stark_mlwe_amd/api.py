@@ -515,6 +515,19 @@ class Context:
         self._chk(self.lib.stark_deep_fri_verify(self.h, buf, len(proof), _ptr(sch), len(sch), params.r, params.seed_z, C.byref(ok)))
         return bool(ok.value)
 
+    def deep_fri_verify_batch(self, params: DeepFriParams, proofs) -> list:
+        """deep_fri_verify (fri.rs:643-762) on each of `proofs` (canonical bytes, one schedule and r), in one device pass; one bool per proof."""
+        n = len(proofs)
+        if n == 0:
+            return []
+        sch = np.ascontiguousarray(params.schedule, dtype=np.uint64)
+        bufs = [(C.c_uint8 * max(1, len(p))).from_buffer_copy(bytes(p) or b"\0") for p in proofs]
+        ptrs = (C.c_void_p * n)(*[C.cast(b, C.c_void_p) for b in bufs])
+        lens = (C.c_size_t * n)(*[len(p) for p in proofs])
+        acc = (C.c_int32 * n)()
+        self._chk(self.lib.stark_deep_fri_verify_batch(self.h, n, ptrs, lens, _ptr(sch), len(sch), params.r, params.seed_z, acc))
+        return [bool(acc[i]) for i in range(n)]
+
     def merkle_verify_single(self, cfg, root, indices, leaves, proof: bytes) -> bool:
         """MerkleProver::verify_single (merkle/src/lib.rs:800-812)."""
         ix = np.ascontiguousarray(indices, dtype=np.uint64); lv = _arr(leaves)

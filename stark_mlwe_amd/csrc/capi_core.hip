@@ -284,15 +284,19 @@ int32_t stark_ctx_create(int32_t device, void* stream, stark_ctx_t** out) {
     stark::ntt_set_attrs();
     // allow the full 160 KiB of LDS per workgroup for the kernels that stage through it
     (void)hipFuncSetAttribute((const void*)k_leaf_pair, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    (void)hipFuncSetAttribute((const void*)k_hash_ds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_hash_ds<DsStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_hash_ds<DsGatherStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_permute_batch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_tr_hash, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_hash_stream, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_leaf_pair2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    (void)hipFuncSetAttribute((const void*)k_hash_ds2<17>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    (void)hipFuncSetAttribute((const void*)k_hash_ds2<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_hash_ds2<17, DsStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_hash_ds2<9, DsStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_hash_ds2<17, DsGatherStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_hash_ds2<9, DsGatherStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_tr_hash_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
-    (void)hipFuncSetAttribute((const void*)k_hash_ds_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_hash_ds_chain<DsStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_hash_ds_chain<DsGatherStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_leaf_pair_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_tr_stream_chain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     *out = c; return STARK_OK;
@@ -496,33 +500,42 @@ int32_t stark_poseidon_hash_with_ds(stark_ctx_t* ctx, stark_params_t* p, const u
     if (p->dev.t != 17) return ctx->fail(STARK_ERR_INVALID_ARG, "hash_with_ds is the fixed t=17 sponge");
     return hash_stream(ctx, p, 1, nullptr, 0, in, cnt, load_fr(ds_tag), 1, out);
 }
-static int32_t launch_hash_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, int mode, size_t arity, uint32_t level, uint64_t pos0, uint64_t label,
-                              const fr_t* in0, const fr_t* in1, size_t n_in, fr_t* out, size_t cp_div = 1, const uint64_t* pos_list = nullptr, size_t chunk = 0) {
-    const DsStream D = DsStream::make(mode, arity, level, pos0, label, in0, in1, n_in, cp_div, pos_list, chunk);
+}  // extern "C"
+// One launch of hash_with_ds_dynamic over the hashes of a DS stream (DsStream: a Merkle level / pair-leaf level; DsGatherStream: one
+// (width, depth) step of the batch verifier), in the form poseidon_form picks for a Merkle level of that many nodes.
+template <class DS>
+static int32_t launch_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, const DS& D, fr_t* out) {
     if (!D.n_out) return STARK_OK;
     const int t = p->dev.t; const unsigned nodes = (unsigned)D.n_out, pairs = (unsigned)((D.n_out + 63) / 64);
     switch (poseidon_form(ctx, p, PoseidonOp::MerkleLevel, D.n_out)) {
-    case PoseidonForm::FiveWave: hipLaunchKernelGGL(k_hash_ds_chain, dim3(nodes), dim3(320), chain_lds_bytes(), st, p->dev, D, row_consts_of(ctx), out); break;
+    case PoseidonForm::FiveWave: hipLaunchKernelGGL(k_hash_ds_chain<DS>, dim3(nodes), dim3(320), chain_lds_bytes(), st, p->dev, D, row_consts_of(ctx), out); break;
     case PoseidonForm::OneWave:
-        if (t == 17) hipLaunchKernelGGL(k_hash_ds_coop<17>, dim3(nodes), dim3(64), coop_lds_bytes(17), st, p->dev, D, out);
-        else hipLaunchKernelGGL(k_hash_ds_coop<9>, dim3(nodes), dim3(64), coop_lds_bytes(9), st, p->dev, D, out);
+        if (t == 17) hipLaunchKernelGGL((k_hash_ds_coop<17, DS>), dim3(nodes), dim3(64), coop_lds_bytes(17), st, p->dev, D, out);
+        else hipLaunchKernelGGL((k_hash_ds_coop<9, DS>), dim3(nodes), dim3(64), coop_lds_bytes(9), st, p->dev, D, out);
         break;
     case PoseidonForm::WavePair:
-        if (t == 17) hipLaunchKernelGGL(k_hash_ds2<17>, dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D, out);
-        else hipLaunchKernelGGL(k_hash_ds2<9>, dim3(pairs), dim3(128), pair_lds_bytes(9), st, p->dev, D, out);
+        if (t == 17) hipLaunchKernelGGL((k_hash_ds2<17, DS>), dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D, out);
+        else hipLaunchKernelGGL((k_hash_ds2<9, DS>), dim3(pairs), dim3(128), pair_lds_bytes(9), st, p->dev, D, out);
         break;
     case PoseidonForm::Wide:
-        if (t == 33) hipLaunchKernelGGL(k_hash_ds_wave<33>, dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
-        else if (t == 65) hipLaunchKernelGGL(k_hash_ds_wave<65>, dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
-        else hipLaunchKernelGGL(k_hash_ds_wave<129>, dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
+        if (t == 33) hipLaunchKernelGGL((k_hash_ds_wave<33, DS>), dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
+        else if (t == 65) hipLaunchKernelGGL((k_hash_ds_wave<65, DS>), dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
+        else hipLaunchKernelGGL((k_hash_ds_wave<129, DS>), dim3(nodes), dim3(64), wave_lds_bytes(t), st, p->dev, D, out);
         break;
     case PoseidonForm::Lane: {
         const int block = poseidon_block(t);
-        hipLaunchKernelGGL(k_hash_ds, dim3((unsigned)((D.n_out + block - 1) / block)), dim3(block), poseidon_lds(t, block), st, p->dev, D, out);
+        hipLaunchKernelGGL(k_hash_ds<DS>, dim3((unsigned)((D.n_out + block - 1) / block)), dim3(block), poseidon_lds(t, block), st, p->dev, D, out);
     } }
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
 }
+extern "C" {
+static int32_t launch_hash_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, int mode, size_t arity, uint32_t level, uint64_t pos0, uint64_t label,
+                              const fr_t* in0, const fr_t* in1, size_t n_in, fr_t* out, size_t cp_div = 1, const uint64_t* pos_list = nullptr, size_t chunk = 0) {
+    return launch_ds(ctx, st, p, DsStream::make(mode, arity, level, pos0, label, in0, in1, n_in, cp_div, pos_list, chunk), out);
+}
 }  // extern "C"
+// The batch verifier's gathered DS hashes (capi_verify.hip)
+int32_t stark::hash_ds_gather_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 // DS hashes with scattered positions (the verifier's union-of-paths levels): hash k = H([arity, level, positions[k], label] || chunk children)
 int32_t stark::hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
                                  const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out) {

@@ -3,9 +3,12 @@
 //   stark_deep_fri_verify            deep_fri_verify                    crates/deep_ali/src/fri.rs:643-762
 //   stark_merkle_verify_many_ds      MerkleProver::verify_single        crates/merkle/src/lib.rs:587-722, 800-812
 //   stark_merkle_verify_pairs_ds     MerkleProver::verify_pairs         crates/merkle/src/lib.rs:723-773, 841-855
+//   stark_deep_fri_verify_batch      deep_fri_verify over many proofs: the plan of fri_verify_batch.hpp, one launch per (width, depth)
 #include <cstring>
 #include "ctx.hpp"
 #include "fri_verify.hpp"
+#include "fri_verify_batch.hpp"
+#include "poseidon_streams.hpp"
 
 using namespace stark;
 
@@ -13,6 +16,22 @@ namespace stark {
 int32_t hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
                           const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out);   // capi_core.hip
 }
+
+namespace stark {
+// proof b is accepted iff its host flag is set and every root it computed equals the one it claims (VerifyBatchPlan::chk); one thread per proof
+__global__ void __launch_bounds__(256) k_verify_batch_check(const fr_t* __restrict__ pool, const uint32_t* __restrict__ chk_off, const uint32_t* __restrict__ chk,
+                                                            const int32_t* __restrict__ flag, size_t batch, int32_t* __restrict__ accepted) {
+    const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    int32_t acc = flag[b];
+    for (uint32_t j = chk_off[b]; j < chk_off[b + 1]; ++j) {
+        const fr_t x = ldg(pool + chk[2 * j]), y = ldg(pool + chk[2 * j + 1]);
+        for (int i = 0; i < 8; ++i) acc &= x.v[i] == y.v[i] ? 1 : 0;
+    }
+    accepted[b] = acc;
+}
+
+}  // namespace stark
 
 namespace {
 struct GpuVerifyHasher : VerifyHasher {
@@ -48,6 +67,61 @@ struct GpuVerifyHasher : VerifyHasher {
         return down(out, dout, n);
     }
 };
+
+// Runs one plan: one upload, the leaf step and the DS groups in depth order (groups that share a depth after the first on the side stream),
+// the check kernel, one download of the decisions and one synchronisation.
+int32_t run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, int32_t* accepted) {
+    if (!V.batch) return STARK_OK;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_hdr = 0, o_off = al(o_hdr + V.hdr.size() * 8), o_idx = al(o_off + V.off.size() * 4), o_coff = al(o_idx + V.idx.size() * 4),
+                 o_chk = al(o_coff + V.chk_off.size() * 4), o_flag = al(o_chk + V.chk.size() * 4), o_pool = al(o_flag + V.batch * 4),
+                 o_acc = al(o_pool + V.pool.size() * sizeof(fr_t)), total = al(o_acc + V.batch * 4);
+    std::vector<uint8_t> h(o_pool + V.n_known * sizeof(fr_t));         // everything the device reads, in one upload (the computed digests are not sent)
+    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) memcpy(h.data() + o, src, bytes); };
+    put(o_hdr, V.hdr.data(), V.hdr.size() * 8); put(o_off, V.off.data(), V.off.size() * 4); put(o_idx, V.idx.data(), V.idx.size() * 4);
+    put(o_coff, V.chk_off.data(), V.chk_off.size() * 4); put(o_chk, V.chk.data(), V.chk.size() * 4); put(o_flag, V.flag.data(), V.batch * 4);
+    put(o_pool, V.pool.data(), V.n_known * sizeof(fr_t));
+    DevBuf d; STARK_HIP(ctx, d.alloc(ctx, total));
+    uint8_t* base = (uint8_t*)d.p; fr_t* pool = (fr_t*)(base + o_pool);
+    hipStream_t main_st = ctx->stream, side = nullptr;
+    STARK_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, main_st));
+    bool forked = false;
+    auto bail = [&](int32_t rc) { if (forked) (void)hipStreamSynchronize(side); (void)hipStreamSynchronize(main_st); return rc; };
+    for (size_t g0 = 0, depth = 1; g0 < V.groups.size() || (depth == 1 && V.nl); ++depth) {
+        // the launches of this depth: the leaf step (depth 1), then the DS groups of each width
+        std::vector<int> items; if (depth == 1 && V.nl) items.push_back(-1);
+        size_t g1 = g0; while (g1 < V.groups.size() && V.groups[g1].depth == depth) items.push_back((int)g1++);
+        for (size_t i = 0; i < items.size(); ++i) {
+            hipStream_t st = main_st;
+            if (i == 1) {                                              // fork: the rest of this depth on the side stream
+                { int32_t rc = ctx_side_stream(ctx, &side); if (rc) return bail(rc); }
+                if (hipEventRecord(ctx->ev_fork, main_st) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_fork, 0) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "fork"));
+                forked = true;
+            }
+            if (i >= 1) st = side;
+            int32_t rc = STARK_OK;
+            if (items[i] < 0) rc = leaf_pair_hash_on(ctx, st, pool + V.leaf_f0, pool + V.leaf_f0 + V.nl, V.nl, 1, pool + V.leaf_out0);
+            else {
+                const VerifyBatchPlan::Group& G = V.groups[items[i]];
+                stark_params* mp = nullptr; rc = ctx_merkle_params(ctx, G.t, &mp);
+                const DsGatherStream D{(const uint64_t*)(base + o_hdr) + 4 * G.job0, (const uint32_t*)(base + o_off) + G.job0, (const uint32_t*)(base + o_idx), pool, G.n, G.max_children};
+                if (!rc) rc = hash_ds_gather_on(ctx, st, mp, D, pool + G.out0);
+            }
+            if (rc) return bail(rc);
+        }
+        if (items.size() > 1) {                                        // join before the next depth reads these digests
+            if (hipEventRecord(ctx->ev_fork, side) != hipSuccess || hipStreamWaitEvent(main_st, ctx->ev_fork, 0) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "join"));
+        }
+        g0 = g1;
+    }
+    int32_t* acc_dev = (int32_t*)(base + o_acc);
+    hipLaunchKernelGGL(k_verify_batch_check, dim3((unsigned)((V.batch + 255) / 256)), dim3(256), 0, main_st, pool, (const uint32_t*)(base + o_coff), (const uint32_t*)(base + o_chk),
+                       (const int32_t*)(base + o_flag), V.batch, acc_dev);
+    STARK_HIP(ctx, hipGetLastError());
+    STARK_HIP(ctx, hipMemcpyAsync(accepted, acc_dev, V.batch * 4, hipMemcpyDeviceToHost, main_st));
+    STARK_HIP(ctx, hipStreamSynchronize(main_st));
+    return STARK_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -61,6 +135,30 @@ int32_t stark_deep_fri_verify(stark_ctx_t* ctx, const uint8_t* proof, size_t len
     GpuVerifyHasher H(ctx); bool ok = false;
     STARK_TRY(deep_fri_verify_host(H, P, schedule, L, r, ok));
     *accepted = ok ? 1 : 0; return STARK_OK;
+}
+
+// A plan is run once it holds this many pool slots (1 GiB of field elements), so device memory stays bounded whatever the batch.
+static const size_t kVerifyBatchMaxSlots = (size_t)1 << 25;
+int32_t stark_deep_fri_verify_batch(stark_ctx_t* ctx, size_t batch, const uint8_t* const* proofs, const size_t* lens, const size_t* schedule, size_t L, size_t r, uint64_t seed_z,
+                                    int32_t* accepted) {
+    if (!batch) return STARK_OK;
+    if (!accepted) return STARK_ERR_INVALID_ARG;
+    memset(accepted, 0, batch * sizeof(int32_t));
+    if (!ctx || !proofs || !lens || (!schedule && L)) return STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) if (!proofs[b] && lens[b]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    (void)seed_z;   // carried for signature parity, as in stark_deep_fri_verify
+    size_t b0 = 0;
+    while (b0 < batch) {
+        VerifyBatchPlanner pl; size_t b1 = b0;
+        while (b1 < batch && (b1 == b0 || pl.slots() < kVerifyBatchMaxSlots)) { pl.add(proofs[b1], lens[b1], schedule, L, r); ++b1; }
+        if (!pl.fits_u32()) return ctx->fail(STARK_ERR_INVALID_ARG, "a proof of the batch needs more than 2^31 pool slots");
+        VerifyBatchPlan V; pl.finish(V);
+        int32_t rc = run_verify_batch(ctx, V, accepted + b0);
+        if (rc) { memset(accepted, 0, batch * sizeof(int32_t)); return rc; }
+        b0 = b1;
+    }
+    return STARK_OK;
 }
 
 static int32_t merkle_verify(stark_ctx_t* ctx, int pairs, size_t cfg_arity, uint64_t tree_label, const uint64_t* root4, const size_t* idx, size_t k, const uint64_t* values, const uint64_t* cp,

@@ -85,12 +85,24 @@ inline bool decode_proof(const uint8_t* bytes, size_t len, DeepFriProofHost& P) 
     return R.ok && R.left() == 0;
 }
 
+#define STARK_VERIFY_TRY(expr) do { int32_t rc__ = (expr); if (rc__) return rc__; } while (0)
+
 inline bool ok_width_for(size_t arity) { return arity >= 1 && arity <= 128; }      // the dynamic params ARE poseidon_params_for_arity(arity) (MerkleChannelCfg::new), so the t / arity guard (:605-614) reduces to the arity range
 
-// verify_many_ds (merkle/src/lib.rs:587-722) with cfg = MerkleChannelCfg::new(cfg_arity).with_tree_label(label):
-// the Poseidon parameters belong to the VERIFIER's arity (fri.rs:676-678), the hashing arity comes from the proof (:602).
-inline int32_t verify_many_ds_host(VerifyHasher& H, size_t cfg_arity, const fr_t& root, const std::vector<size_t>& indices, const std::vector<fr_t>& values, const MerkleProofHost& proof, uint64_t label, bool& ok) {
-    ok = false;
+// ---- the index walks, over values of any type -------------------------------------------------------------------------------
+// Every reject decision of verify_many_ds / verify_pairs_ds / deep_fri_verify is written once, here, over values of type V: field
+// elements for the single-proof path below (it hashes each level as the walk reaches it), pool slots for the batch planner
+// (fri_verify_batch.hpp: it records each level's hashes as jobs and compares the roots on the device).
+
+// The level walk of verify_many_ds (merkle/src/lib.rs:587-722) with cfg = MerkleChannelCfg::new(cfg_arity): the Poseidon parameters belong
+// to the VERIFIER's arity (fri.rs:676-678), the hashing arity comes from the proof (:602).
+//   sib(level, j) -> V                                  the j-th sibling of `level`
+//   hash_level(level, arity, parents, kids, out) -> rc  out[g] = hash_with_ds_dynamic([arity, level, parents[g], label], kids[g])
+// shaped = false is a rejection; otherwise `top` is the root the opening computes (the caller compares it with the claimed one).
+template <class V, class Sib, class HashLevel>
+inline int32_t ds_walk(size_t cfg_arity, const std::vector<size_t>& indices, const std::vector<V>& values, const MerkleProofHost& proof, Sib sib, HashLevel hash_level,
+                       bool& shaped, V& top) {
+    shaped = false;
     if (indices.empty() || indices.size() != values.size()) return 0;                                        // :595-597
     std::vector<size_t> req = indices; std::sort(req.begin(), req.end()); req.erase(std::unique(req.begin(), req.end()), req.end());
     if (proof.indices != req) return 0;                                                                      // :601-603
@@ -98,12 +110,12 @@ inline int32_t verify_many_ds_host(VerifyHasher& H, size_t cfg_arity, const fr_t
     const size_t arity = proof.arity;
     if (arity == 0) return 0;                                                                                // (the reference divides by it)
     if (host::width_for_arity(arity) != host::width_for_arity(cfg_arity) || host::width_for_arity(cfg_arity) < 0) return 0;   // ok_width, :610-618
-    std::map<size_t, fr_t> mp; for (size_t k = 0; k < indices.size(); ++k) mp[indices[k]] = values[k];      // later entries win (:622-625)
-    std::vector<size_t> cur_idx = req; std::vector<fr_t> cur_val; for (size_t i : cur_idx) cur_val.push_back(mp[i]);
+    std::map<size_t, V> mp; for (size_t k = 0; k < indices.size(); ++k) mp[indices[k]] = values[k];          // later entries win (:622-625)
+    std::vector<size_t> cur_idx = req; std::vector<V> cur_val; for (size_t i : cur_idx) cur_val.push_back(mp[i]);
     for (size_t level = 0; level < proof.siblings.size(); ++level) {
-        const std::vector<fr_t>& sib = proof.siblings[level]; const std::vector<uint8_t>& gs = proof.group_sizes[level];
+        const size_t n_sib = proof.siblings[level].size(); const std::vector<uint8_t>& gs = proof.group_sizes[level];
         // groups by parent, in parent order (cur_idx is sorted, so consecutive runs)
-        std::vector<size_t> parents; std::vector<std::vector<std::pair<size_t, fr_t>>> opened;
+        std::vector<size_t> parents; std::vector<std::vector<std::pair<size_t, V>>> opened;
         for (size_t k = 0; k < cur_idx.size(); ++k) {
             const size_t par = cur_idx[k] / arity, cpos = cur_idx[k] % arity;
             if (parents.empty() || parents.back() != par) { parents.push_back(par); opened.emplace_back(); }
@@ -111,49 +123,43 @@ inline int32_t verify_many_ds_host(VerifyHasher& H, size_t cfg_arity, const fr_t
         }
         if (parents.size() != gs.size()) return 0;                                                           // :641-643
         // children of every group: opened where the position matches, siblings otherwise (:656-676)
-        size_t off = 0; std::vector<std::vector<fr_t>> kids(parents.size());
+        size_t off = 0; std::vector<std::vector<V>> kids(parents.size());
         for (size_t g = 0; g < parents.size(); ++g) {
             const size_t cc = gs[g]; if (cc == 0 || cc > arity) return 0;                                     // :653-655
             size_t o = 0;                                                                                     // opened[g] is sorted by cpos already
             for (size_t c = 0; c < cc; ++c) {
                 if (o < opened[g].size() && opened[g][o].first == c) { kids[g].push_back(opened[g][o].second); ++o; continue; }
-                if (off >= sib.size()) return 0;
-                kids[g].push_back(sib[off++]);
+                if (off >= n_sib) return 0;
+                kids[g].push_back(sib(level, off++));
             }
         }
-        if (off != sib.size()) return 0;                                                                      // :696-698
-        // hash the groups in batches of equal child count (at most two distinct counts in an honest proof)
-        std::vector<fr_t> nv(parents.size());
-        std::vector<char> done(parents.size(), 0);
-        for (size_t g0 = 0; g0 < parents.size(); ++g0) {
-            if (done[g0]) continue;
-            const size_t cc = kids[g0].size(); std::vector<size_t> members; std::vector<uint64_t> pos; std::vector<fr_t> ch;
-            for (size_t g = g0; g < parents.size(); ++g) if (!done[g] && kids[g].size() == cc) { done[g] = 1; members.push_back(g); pos.push_back((uint64_t)parents[g]); ch.insert(ch.end(), kids[g].begin(), kids[g].end()); }
-            std::vector<fr_t> outv(members.size());
-            int32_t rc = H.ds_nodes(arity, cc, (uint32_t)level, label, pos.data(), ch.data(), members.size(), outv.data()); if (rc) return rc;
-            for (size_t k = 0; k < members.size(); ++k) nv[members[k]] = outv[k];
-        }
+        if (off != n_sib) return 0;                                                                           // :696-698
+        std::vector<V> nv(parents.size());
+        { int32_t rc = hash_level((uint32_t)level, arity, parents, kids, nv); if (rc) return rc; }
         cur_idx = parents; cur_val = nv;
     }
     if (cur_val.size() != 1) return 0;                                                                        // :704-706
-    ok = fr_eq(cur_val[0], root); return 0;
+    top = cur_val[0]; shaped = true; return 0;
 }
-// verify_pairs_ds (merkle/src/lib.rs:723-773)
-inline int32_t verify_pairs_ds_host(VerifyHasher& H, size_t cfg_arity, const fr_t& root, const std::vector<size_t>& indices, const std::vector<fr_t>& f, const std::vector<fr_t>& cp, const MerkleProofHost& proof, uint64_t label, bool& ok) {
-    ok = false;
-    if (indices.size() != f.size() || indices.size() != cp.size() || indices.empty()) return 0;              // :731-733
+// The checks and leaf set of verify_pairs_ds (merkle/src/lib.rs:723-750): the sorted distinct indices `req` with their (f, cp), a later entry
+// winning.  false is a rejection; otherwise the pair leaves hash_with_ds_dynamic([arity, 2^32-1, req[k], label], [ff[k], cc[k]]) go to ds_walk.
+template <class V>
+inline bool pairs_leaf_set(size_t cfg_arity, const std::vector<size_t>& indices, const std::vector<V>& f, const std::vector<V>& cp, const MerkleProofHost& proof,
+                           std::vector<size_t>& req, std::vector<V>& ff, std::vector<V>& cc) {
+    if (indices.size() != f.size() || indices.size() != cp.size() || indices.empty()) return false;          // :731-733
     const size_t arity = proof.arity;
-    if (arity == 0 || host::width_for_arity(cfg_arity) < 0 || host::width_for_arity(arity) != host::width_for_arity(cfg_arity)) return 0;   // :737-745
-    std::vector<size_t> req = indices; std::sort(req.begin(), req.end()); req.erase(std::unique(req.begin(), req.end()), req.end());
-    std::map<size_t, std::pair<fr_t, fr_t>> mp; for (size_t k = 0; k < indices.size(); ++k) mp[indices[k]] = {f[k], cp[k]};
-    std::vector<fr_t> ff, cc; std::vector<uint64_t> pos; for (size_t i : req) { ff.push_back(mp[i].first); cc.push_back(mp[i].second); pos.push_back((uint64_t)i); }
-    std::vector<fr_t> leaves(req.size());
-    { int32_t rc = H.ds_pair_leaves(arity, label, pos.data(), ff.data(), cc.data(), req.size(), leaves.data()); if (rc) return rc; }
-    return verify_many_ds_host(H, cfg_arity, root, req, leaves, proof, label, ok);
+    if (arity == 0 || host::width_for_arity(cfg_arity) < 0 || host::width_for_arity(arity) != host::width_for_arity(cfg_arity)) return false;   // :737-745
+    req = indices; std::sort(req.begin(), req.end()); req.erase(std::unique(req.begin(), req.end()), req.end());
+    std::map<size_t, std::pair<V, V>> mp; for (size_t k = 0; k < indices.size(); ++k) mp[indices[k]] = {f[k], cp[k]};
+    ff.clear(); cc.clear(); for (size_t i : req) { ff.push_back(mp[i].first); cc.push_back(mp[i].second); }
+    return true;
 }
-
-// deep_fri_verify (fri.rs:643-762)
-inline int32_t deep_fri_verify_host(VerifyHasher& H, const DeepFriProofHost& P, const size_t* schedule, size_t L, size_t r, bool& ok) {
+// deep_fri_verify (fri.rs:643-762) with each Merkle opening handed to
+//   open(layer, arity, hashed, idx, f, s, proof, good) -> rc   layer `layer`'s opening of `idx` against roots[layer]: verify_single over
+//                                                               hash_leaf_pair(f, s) when `hashed`, verify_pairs over (f, s) otherwise
+// ok = every check passed and every opening was good.  The first failed check ends the walk.
+template <class Open>
+inline int32_t deep_fri_walk(const DeepFriProofHost& P, const size_t* schedule, size_t L, size_t r, Open open, bool& ok) {
     ok = false;
     if (P.roots.size() != L + 1 || P.layers.size() != L || P.queries.size() != r) return 0;                  // :645-647
     std::vector<size_t> sizes(1, P.n0);
@@ -169,14 +175,10 @@ inline int32_t deep_fri_verify_host(VerifyHasher& H, const DeepFriProofHost& P, 
     }
     auto check_opening = [&](size_t layer, size_t m_req, const std::vector<size_t>& idx, const std::map<size_t, std::pair<fr_t, fr_t>>& mp, const MerkleProofHost& pr, bool& good) -> int32_t {
         good = false;
-        const size_t ar = pick_arity_for_layer(sizes[layer], m_req); const bool hashed = hashed_arity(ar);     // :671-673
+        const size_t ar = pick_arity_for_layer(sizes[layer], m_req);                                          // :671-673
         std::vector<fr_t> ff, ss;
         for (size_t i : idx) { auto it = mp.find(i); if (it == mp.end()) return 0; ff.push_back(it->second.first); ss.push_back(it->second.second); }   // :677-680
-        if (hashed) {
-            std::vector<fr_t> lh(idx.size()); if (!idx.empty()) { int32_t rc = H.leaf_pairs(ff.data(), ss.data(), idx.size(), lh.data()); if (rc) return rc; }
-            return verify_many_ds_host(H, ar, P.roots[layer], idx, lh, pr, (uint64_t)layer, good);           // verify_single, :682
-        }
-        return verify_pairs_ds_host(H, ar, P.roots[layer], idx, ff, ss, pr, (uint64_t)layer, good);           // verify_pairs, :691
+        return open(layer, ar, hashed_arity(ar), idx, ff, ss, pr, good);                                      // verify_single (:682) / verify_pairs (:691)
     };
     for (size_t l = 0; l < L; ++l) {
         const LayerBatchHost& lb = P.layers[l]; bool good = false;
@@ -196,6 +198,49 @@ inline int32_t deep_fri_verify_host(VerifyHasher& H, const DeepFriProofHost& P, 
         bool good = false; int32_t rc = check_opening(L, 1, std::vector<size_t>{0}, one, P.final_proof, good); if (rc) return rc; if (!good) return 0;
     }
     ok = true; return 0;
+}
+
+// ---- the single-proof verifier: the walks with every level hashed through `VerifyHasher` as it is reached ---------------------
+// verify_many_ds (merkle/src/lib.rs:587-722)
+inline int32_t verify_many_ds_host(VerifyHasher& H, size_t cfg_arity, const fr_t& root, const std::vector<size_t>& indices, const std::vector<fr_t>& values, const MerkleProofHost& proof, uint64_t label, bool& ok) {
+    ok = false;
+    auto sib = [&](size_t level, size_t j) { return proof.siblings[level][j]; };
+    // hash the groups in batches of equal child count (at most two distinct counts in an honest proof)
+    auto hash_level = [&](uint32_t level, size_t arity, const std::vector<size_t>& parents, const std::vector<std::vector<fr_t>>& kids, std::vector<fr_t>& nv) -> int32_t {
+        std::vector<char> done(parents.size(), 0);
+        for (size_t g0 = 0; g0 < parents.size(); ++g0) {
+            if (done[g0]) continue;
+            const size_t cc = kids[g0].size(); std::vector<size_t> members; std::vector<uint64_t> pos; std::vector<fr_t> ch;
+            for (size_t g = g0; g < parents.size(); ++g) if (!done[g] && kids[g].size() == cc) { done[g] = 1; members.push_back(g); pos.push_back((uint64_t)parents[g]); ch.insert(ch.end(), kids[g].begin(), kids[g].end()); }
+            std::vector<fr_t> outv(members.size());
+            int32_t rc = H.ds_nodes(arity, cc, level, label, pos.data(), ch.data(), members.size(), outv.data()); if (rc) return rc;
+            for (size_t k = 0; k < members.size(); ++k) nv[members[k]] = outv[k];
+        }
+        return 0;
+    };
+    bool shaped = false; fr_t top = fr_zero<PallasFr>();
+    STARK_VERIFY_TRY(ds_walk(cfg_arity, indices, values, proof, sib, hash_level, shaped, top));
+    ok = shaped && fr_eq(top, root); return 0;
+}
+// verify_pairs_ds (merkle/src/lib.rs:723-773)
+inline int32_t verify_pairs_ds_host(VerifyHasher& H, size_t cfg_arity, const fr_t& root, const std::vector<size_t>& indices, const std::vector<fr_t>& f, const std::vector<fr_t>& cp, const MerkleProofHost& proof, uint64_t label, bool& ok) {
+    ok = false;
+    std::vector<size_t> req; std::vector<fr_t> ff, cc;
+    if (!pairs_leaf_set(cfg_arity, indices, f, cp, proof, req, ff, cc)) return 0;
+    std::vector<uint64_t> pos(req.begin(), req.end()); std::vector<fr_t> leaves(req.size());
+    STARK_VERIFY_TRY(H.ds_pair_leaves(proof.arity, label, pos.data(), ff.data(), cc.data(), req.size(), leaves.data()));
+    return verify_many_ds_host(H, cfg_arity, root, req, leaves, proof, label, ok);
+}
+// deep_fri_verify (fri.rs:643-762)
+inline int32_t deep_fri_verify_host(VerifyHasher& H, const DeepFriProofHost& P, const size_t* schedule, size_t L, size_t r, bool& ok) {
+    auto open = [&](size_t layer, size_t ar, bool hashed, const std::vector<size_t>& idx, const std::vector<fr_t>& ff, const std::vector<fr_t>& ss, const MerkleProofHost& pr, bool& good) -> int32_t {
+        if (hashed) {
+            std::vector<fr_t> lh(idx.size()); if (!idx.empty()) STARK_VERIFY_TRY(H.leaf_pairs(ff.data(), ss.data(), idx.size(), lh.data()));
+            return verify_many_ds_host(H, ar, P.roots[layer], idx, lh, pr, (uint64_t)layer, good);
+        }
+        return verify_pairs_ds_host(H, ar, P.roots[layer], idx, ff, ss, pr, (uint64_t)layer, good);
+    };
+    return deep_fri_walk(P, schedule, L, r, open, ok);
 }
 
 }  // namespace stark

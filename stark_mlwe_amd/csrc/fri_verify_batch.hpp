@@ -1,0 +1,136 @@
+// stark_mlwe_amd/csrc/fri_verify_batch.hpp — deep_fri_verify over a batch of proofs, planned on the host (product code).
+//
+// The hashes a verification makes depend only on the indices and group sizes inside the proof, never on hash values, so the walks
+// of fri_verify.hpp run once per proof over pool SLOTS instead of field elements and record every hash as a job.  The device then runs
+// every opening of every proof that sits at the same dependency depth in one launch per Poseidon width (capi_verify.hip), and one
+// thread per proof compares its computed roots with the claimed ones.  Everything that compares values inside the proof only
+// (s_i == f_parent[b], final_index, the n0 / schedule checks) stays in the walk on the host and ends in the per-proof flag.
+//
+// The plan, after finish():
+//   pool     [ inputs: siblings, pair-leaf children, claimed roots | leaf f (nl) | leaf s (nl) | computed digests ]
+//   leaf     pool[leaf_out0 + j] = hash_leaf_pair(pool[leaf_f0 + j], pool[leaf_f0 + nl + j])                              depth 1
+//   groups   DS jobs of one (width, depth), in depth order: job k of group G writes pool[G.out0 + k - G.job0]; its header is
+//            hdr[4k .. 4k+3] = (arity, level, position, label) and its children pool[idx[off[k]] .. idx[off[k+1] - 1]]   (DsGatherStream)
+//   checks   proof b is accepted iff flag[b] and pool[chk[2j]] == pool[chk[2j+1]] for every j in [chk_off[b], chk_off[b+1])
+// Inputs are depth 0; a computed digest is one deeper than its deepest child.  A proof that fails a check in the walk keeps no job.
+// Host-only C++.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+#include "fri_verify.hpp"
+
+namespace stark {
+
+struct VerifyBatchPlan {
+    struct Group { int t; uint32_t depth; size_t job0, n, max_children, out0; };
+    size_t batch = 0, n_known = 0;                 // n_known: the pool prefix the host fills (inputs and leaf f / s); the rest is computed
+    std::vector<fr_t> pool;
+    size_t nl = 0, leaf_f0 = 0, leaf_out0 = 0;
+    std::vector<uint64_t> hdr; std::vector<uint32_t> off, idx;
+    std::vector<Group> groups;
+    std::vector<uint32_t> chk_off, chk; std::vector<int32_t> flag;
+};
+
+// Builds a VerifyBatchPlan one proof at a time.  Slots while planning: an input is its pool index, a computed digest is kComputed | its number.
+class VerifyBatchPlanner {
+public:
+    static constexpr uint32_t kComputed = 0x80000000u;
+    // plans deep_fri_verify of one proof; a proof that does not decode or fails a check in the walk is planned as a rejection
+    void add(const uint8_t* bytes, size_t len, const size_t* schedule, size_t L, size_t r) {
+        const Mark m = mark();
+        DeepFriProofHost P; bool ok = false;
+        if (decode_proof(bytes, len, P)) deep_fri_walk(P, schedule, L, r, [&](size_t layer, size_t ar, bool hashed, const std::vector<size_t>& ix, const std::vector<fr_t>& ff,
+                                                                              const std::vector<fr_t>& ss, const MerkleProofHost& pr, bool& good) -> int32_t {
+            good = open(P, layer, ar, hashed, ix, ff, ss, pr); return 0;
+        }, ok);
+        if (!ok) rollback(m);
+        flag_.push_back(ok ? 1 : 0); chk_off_.push_back((uint32_t)(chk_.size() / 2));
+    }
+    size_t proofs() const { return flag_.size(); }
+    size_t slots() const { return pool_.size() + 2 * leaf_f_.size() + n_comp_; }      // the pool the plan needs so far
+    bool fits_u32() const { return slots() < kComputed && ch_.size() < kComputed; }
+    void finish(VerifyBatchPlan& out);
+private:
+    struct Job { int t; uint32_t depth; uint64_t hdr[4]; size_t ch0, nch; uint32_t out; };
+    struct Mark { size_t pool, leaf, jobs, ch, comp, chk; };
+    std::vector<fr_t> pool_, leaf_f_, leaf_s_; std::vector<uint32_t> leaf_out_;
+    std::vector<Job> jobs_; std::vector<uint32_t> ch_; std::vector<uint32_t> depth_;     // depth_[c]: depth of computed digest c
+    size_t n_comp_ = 0;
+    std::vector<uint32_t> chk_, chk_off_{0}; std::vector<int32_t> flag_;
+
+    Mark mark() const { return Mark{pool_.size(), leaf_f_.size(), jobs_.size(), ch_.size(), n_comp_, chk_.size()}; }
+    void rollback(const Mark& m) {
+        pool_.resize(m.pool); leaf_f_.resize(m.leaf); leaf_s_.resize(m.leaf); leaf_out_.resize(m.leaf);
+        jobs_.resize(m.jobs); ch_.resize(m.ch); n_comp_ = m.comp; depth_.resize(m.comp); chk_.resize(m.chk);
+    }
+    uint32_t input(const fr_t& x) { pool_.push_back(x); return (uint32_t)(pool_.size() - 1); }
+    uint32_t depth_of(uint32_t s) const { return s & kComputed ? depth_[s & ~kComputed] : 0; }
+    uint32_t computed(uint32_t depth) { depth_.push_back(depth); return kComputed | (uint32_t)(n_comp_++); }
+    uint32_t leaf(const fr_t& f, const fr_t& s) { leaf_f_.push_back(f); leaf_s_.push_back(s); leaf_out_.push_back(computed(1)); return leaf_out_.back(); }
+    uint32_t ds_job(size_t arity, uint32_t level, uint64_t position, uint64_t label, const std::vector<uint32_t>& kids) {
+        Job j; j.t = host::width_for_arity(arity); j.hdr[0] = arity; j.hdr[1] = level; j.hdr[2] = position; j.hdr[3] = label;
+        j.ch0 = ch_.size(); j.nch = kids.size(); uint32_t d = 0;
+        for (uint32_t k : kids) { ch_.push_back(k); d = std::max(d, depth_of(k)); }
+        j.depth = d + 1; j.out = computed(j.depth); jobs_.push_back(j); return j.out;
+    }
+    // verify_many_ds over slots: the level walk records each group as a job; a good walk leaves one root comparison
+    bool many(size_t cfg_arity, const fr_t& root, const std::vector<size_t>& ix, const std::vector<uint32_t>& vals, const MerkleProofHost& pr, uint64_t label) {
+        auto sib = [&](size_t level, size_t j) { return input(pr.siblings[level][j]); };
+        auto hash_level = [&](uint32_t level, size_t arity, const std::vector<size_t>& parents, const std::vector<std::vector<uint32_t>>& kids, std::vector<uint32_t>& nv) -> int32_t {
+            for (size_t g = 0; g < parents.size(); ++g) nv[g] = ds_job(arity, level, (uint64_t)parents[g], label, kids[g]);
+            return 0;
+        };
+        bool shaped = false; uint32_t top = 0;
+        ds_walk(cfg_arity, ix, vals, pr, sib, hash_level, shaped, top);
+        if (!shaped) return false;
+        chk_.push_back(top); chk_.push_back(input(root)); return true;
+    }
+    bool open(const DeepFriProofHost& P, size_t layer, size_t ar, bool hashed, const std::vector<size_t>& ix, const std::vector<fr_t>& ff, const std::vector<fr_t>& ss,
+              const MerkleProofHost& pr) {
+        std::vector<uint32_t> v;
+        if (hashed) {                                                    // verify_single over hash_leaf_pair(f, s)
+            for (size_t k = 0; k < ix.size(); ++k) v.push_back(leaf(ff[k], ss[k]));
+            return many(ar, P.roots[layer], ix, v, pr, (uint64_t)layer);
+        }
+        std::vector<uint32_t> f, s, cf, cs; std::vector<size_t> req;     // verify_pairs: the pair leaves, then verify_many_ds over them
+        for (size_t k = 0; k < ix.size(); ++k) { f.push_back(input(ff[k])); s.push_back(input(ss[k])); }
+        if (!pairs_leaf_set(ar, ix, f, s, pr, req, cf, cs)) return false;
+        for (size_t k = 0; k < req.size(); ++k) v.push_back(ds_job(pr.arity, 0xFFFFFFFFu, (uint64_t)req[k], (uint64_t)layer, {cf[k], cs[k]}));
+        return many(ar, P.roots[layer], req, v, pr, (uint64_t)layer);
+    }
+};
+
+inline void VerifyBatchPlanner::finish(VerifyBatchPlan& out) {
+    VerifyBatchPlan& o = out; o = VerifyBatchPlan();
+    o.batch = flag_.size(); o.flag = flag_; o.chk_off = chk_off_;
+    const size_t ni = pool_.size(), nl = leaf_f_.size();
+    o.nl = nl; o.leaf_f0 = ni; o.leaf_out0 = ni + 2 * nl; o.n_known = ni + 2 * nl;
+    // DS jobs in launch order: by depth, then width; each group's digests contiguous after the leaf digests
+    std::vector<size_t> order(jobs_.size()); for (size_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return jobs_[a].depth != jobs_[b].depth ? jobs_[a].depth < jobs_[b].depth : jobs_[a].t < jobs_[b].t; });
+    std::vector<uint32_t> pos(n_comp_);                                 // computed digest -> pool slot
+    for (size_t j = 0; j < nl; ++j) pos[leaf_out_[j] & ~kComputed] = (uint32_t)(o.leaf_out0 + j);
+    size_t next = o.leaf_out0 + nl;
+    for (size_t k = 0; k < order.size(); ++k) {
+        const Job& J = jobs_[order[k]];
+        if (o.groups.empty() || o.groups.back().depth != J.depth || o.groups.back().t != J.t) o.groups.push_back(VerifyBatchPlan::Group{J.t, J.depth, k, 0, 0, next});
+        VerifyBatchPlan::Group& G = o.groups.back(); ++G.n; G.max_children = std::max(G.max_children, J.nch);
+        pos[J.out & ~kComputed] = (uint32_t)next++;
+    }
+    auto slot = [&](uint32_t s) { return s & kComputed ? pos[s & ~kComputed] : s; };
+    o.pool.assign(next, fr_zero<PallasFr>());
+    std::copy(pool_.begin(), pool_.end(), o.pool.begin());
+    std::copy(leaf_f_.begin(), leaf_f_.end(), o.pool.begin() + ni); std::copy(leaf_s_.begin(), leaf_s_.end(), o.pool.begin() + ni + nl);
+    o.hdr.reserve(4 * order.size()); o.off.reserve(order.size() + 1); o.idx.reserve(ch_.size());
+    o.off.push_back(0);
+    for (size_t k : order) {
+        const Job& J = jobs_[k];
+        o.hdr.insert(o.hdr.end(), J.hdr, J.hdr + 4);
+        for (size_t c = 0; c < J.nch; ++c) o.idx.push_back(slot(ch_[J.ch0 + c]));
+        o.off.push_back((uint32_t)o.idx.size());
+    }
+    o.chk.resize(chk_.size()); for (size_t j = 0; j < chk_.size(); ++j) o.chk[j] = slot(chk_[j]);
+}
+
+}  // namespace stark

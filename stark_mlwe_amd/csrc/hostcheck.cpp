@@ -12,6 +12,7 @@
 #include "poseidon_dev.hpp"
 #include "fri_plan.hpp"
 #include "fri_verify.hpp"
+#include "fri_verify_batch.hpp"
 #include "mfma_digits.hpp"
 #include "poseidon_chain.hpp"
 
@@ -214,12 +215,18 @@ int hc_permute_dense(void* h, uint64_t* states, size_t n) {
     return 0;
 }
 // kernel bodies on the host ---------------------------------------------------------------------------
-int hc_leaf_pair(void* tparams, const uint64_t* f, const uint64_t* f_next, size_t n, size_t m, uint64_t* hout) {
-    HcParams* P = (HcParams*)tparams;
+}  // extern "C"
+// the 17-lane template of hash_leaf_pair (capi_core.hip ctx_leaf_init)
+static void leaf_init(fr_t init[17]) {
     const fr_t AB = host::h_tag("FSv1-ABSORB-BYTES"), CH = host::h_tag("FSv1-CHALLENGE");
-    fr_t init[17]; for (auto& x : init) x = host::h_zero();
+    for (int j = 0; j < 17; ++j) init[j] = host::h_zero();
     init[0] = AB; init[1] = host::h_words("FRI/leaf/poseidon")[0]; init[2] = AB; init[3] = host::h_words("FRI/leaf")[0];
     init[6] = CH; init[7] = AB; init[8] = host::h_words("leaf")[0]; init[16] = host::h_tag("FSv1-TRANSCRIPT-INIT");
+}
+extern "C" {
+int hc_leaf_pair(void* tparams, const uint64_t* f, const uint64_t* f_next, size_t n, size_t m, uint64_t* hout) {
+    HcParams* P = (HcParams*)tparams;
+    fr_t init[17]; leaf_init(init);
     std::vector<fr_t> fv(n), nv(f_next ? (n + m - 1) / m : 0);
     for (size_t i = 0; i < fv.size(); ++i) fv[i] = ld4(f + 4 * i);
     for (size_t i = 0; i < nv.size(); ++i) nv[i] = ld4(f_next + 4 * i);
@@ -322,6 +329,35 @@ int hc_deep_fri_verify(void* tparams, const uint8_t* bytes, size_t len, const si
     HcVerifyHasher H(tparams); bool ok = false;
     int32_t rc = deep_fri_verify_host(H, P, schedule, L, r, ok); if (rc) return rc;
     return ok ? 1 : 0;
+}
+// deep_fri_verify over `batch` proofs through the batch plan (fri_verify_batch.hpp), run step by step as the device runs it: the leaf step,
+// then every (width, depth) group of gathered DS hashes in depth order, then the per-proof root comparisons.  accepted[i] = 1 / 0.
+int hc_deep_fri_verify_batch(void* tparams, size_t batch, const uint8_t* const* proofs, const size_t* lens, const size_t* schedule, size_t L, size_t r, int32_t* accepted) {
+    VerifyBatchPlanner pl; for (size_t b = 0; b < batch; ++b) pl.add(proofs[b], lens[b], schedule, L, r);
+    if (!pl.fits_u32()) return -1;
+    VerifyBatchPlan V; pl.finish(V);
+    HcVerifyHasher H(tparams);
+    fr_t init[17]; leaf_init(init);
+    const LeafStream LS{init, V.pool.data() + V.leaf_f0, V.pool.data() + V.leaf_f0 + V.nl, 1, V.nl};
+    { fr_t st[17]; for (size_t j = 0; j < V.nl; ++j) { ArrayState s{st}; V.pool[V.leaf_out0 + j] = leaf_pair_body(s, ((HcParams*)tparams)->dev, LS, j); } }
+    for (const VerifyBatchPlan::Group& G : V.groups) {
+        HcParams* P = H.params((size_t)G.t - 1); std::vector<fr_t> st(P->dev.t);
+        const DsGatherStream D{V.hdr.data() + 4 * G.job0, V.off.data() + G.job0, V.idx.data(), V.pool.data(), G.n, G.max_children};
+        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; V.pool[G.out0 + k] = hash_ds_body(s, P->dev, D, k); }
+    }
+    for (size_t b = 0; b < batch; ++b) {
+        int32_t acc = V.flag[b];
+        for (uint32_t j = V.chk_off[b]; j < V.chk_off[b + 1]; ++j) acc &= fr_eq(V.pool[V.chk[2 * j]], V.pool[V.chk[2 * j + 1]]) ? 1 : 0;
+        accepted[b] = acc;
+    }
+    return 0;
+}
+// the launch steps of the batch plan: (width, depth, hashes) of each DS group, in launch order; returns the number of groups (at most cap written)
+size_t hc_verify_batch_groups(size_t batch, const uint8_t* const* proofs, const size_t* lens, const size_t* schedule, size_t L, size_t r, int32_t* t, uint32_t* depth, size_t* n, size_t cap) {
+    VerifyBatchPlanner pl; for (size_t b = 0; b < batch; ++b) pl.add(proofs[b], lens[b], schedule, L, r);
+    VerifyBatchPlan V; pl.finish(V);
+    for (size_t g = 0; g < V.groups.size() && g < cap; ++g) { t[g] = V.groups[g].t; depth[g] = V.groups[g].depth; n[g] = V.groups[g].n; }
+    return V.groups.size();
 }
 // MerkleProver::verify_single / verify_pairs (merkle/src/lib.rs:800-855) over the canonical MerkleProof encoding
 int hc_merkle_verify(void* tparams, int pairs, size_t cfg_arity, uint64_t label, const uint64_t* root, const size_t* idx, size_t k, const uint64_t* vals, const uint64_t* cp, const uint8_t* proof, size_t len) {

@@ -427,7 +427,8 @@ __global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))
 
 // SMALL Merkle levels and leaf layers, where the launch is one permutation's latency whatever the kernel: the same five waves per NODE (72 us per
 // permutation against 142 us on one wave and ~0.4 ms in the wave-pair throughput form).
-__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_hash_ds_chain(PoseidonDev P, DsStream D, row::Consts RK, fr_t* __restrict__ out) {
+template <class DS>
+__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_hash_ds_chain(PoseidonDev P, DS D, row::Consts RK, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     const size_t k = blockIdx.x;
     chain_sponge(P, RK, lds, D.total(k), fr_zero<PF>(), [&](size_t q) -> fr_t { return D.elem(k, q); }, out + k);

@@ -251,8 +251,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
 }
 
 // One Merkle node per wave (small levels: latency matters, not throughput).
-template <int T>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_hash_ds_coop(PoseidonDev P, DsStream D, fr_t* __restrict__ out) {
+template <int T, class DS>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_hash_ds_coop(PoseidonDev P, DS D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     CoopLds L = coop_setup<T>(lds, P);
     const int lane = threadIdx.x, rate = T - 1; const size_t k = blockIdx.x, total = D.total(k);

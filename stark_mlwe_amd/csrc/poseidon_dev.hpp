@@ -126,7 +126,7 @@ template <class S> FR_HD fr_t leaf_pair_body(const S& s, const PoseidonDev& P, c
     return permute_core(s, P, true);
 }
 // hash_with_ds_dynamic: eager sponge (permute after every full rate block and after the final one).
-template <class S> FR_HD fr_t hash_ds_body(const S& s, const PoseidonDev& P, const DsStream& D, size_t k) {
+template <class S, class DS> FR_HD fr_t hash_ds_body(const S& s, const PoseidonDev& P, const DS& D, size_t k) {   // DS: DsStream or DsGatherStream
     const int t = P.t, rate = t - 1;
     for (int j = 0; j < t; ++j) s.st(j, fr_zero<PF>());
     const size_t total = D.total(k);
@@ -201,7 +201,8 @@ __global__ void __launch_bounds__(64) k_leaf_pair(PoseidonDev P, LeafStream L, f
     stg(h + i, leaf_pair_body(s, P, L, i));
 }
 // K4: one Merkle level / the pair-leaf level.
-__global__ void __launch_bounds__(64) k_hash_ds(PoseidonDev P, DsStream D, fr_t* __restrict__ out) {
+template <class DS>
+__global__ void __launch_bounds__(64) k_hash_ds(PoseidonDev P, DS D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= D.n_out) return;

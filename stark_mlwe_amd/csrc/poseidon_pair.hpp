@@ -316,8 +316,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
 }
 
 // K4 (pair form): one Merkle level / the pair-leaf level.
-template <int T>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_hash_ds2(PoseidonDev P, DsStream D, fr_t* __restrict__ out) {
+template <int T, class DS>
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_hash_ds2(PoseidonDev P, DS D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     constexpr int rate = T - 1;
     PairState s = pair_setup(lds);

@@ -42,6 +42,22 @@ struct DsStream {
     }
 };
 
+// The batch verifier's DS hashes (fri_verify_batch.hpp): the hashes of one (width, depth) step of every opening of every proof.
+//   hash k = hash_with_ds_dynamic([hdr[4k] .. hdr[4k+3]] || pool[idx[off[k]]] .. pool[idx[off[k+1] - 1]] || 1), eager sponge, cap 0
+// with the header (arity, level, position, label) given per hash and the children gathered from the plan's pool (off: CSR into idx).
+// A pair leaf of an unhashed layer is such a hash with two children and level 2^32 - 1.
+struct DsGatherStream {
+    const uint64_t* hdr; const uint32_t* off; const uint32_t* idx; const fr_t* pool; size_t n_out, max_children;
+    FR_HD uint64_t position(size_t k) const { return hdr[4 * k + 2]; }
+    FR_HD size_t total(size_t k) const { return 4 + (size_t)(off[k + 1] - off[k]) + 1; }
+    FR_HD size_t max_total() const { return 4 + max_children + 1; }
+    FR_HD fr_t elem(size_t k, size_t q) const {
+        if (q < 4) return fr_from_u64<PF>(hdr[4 * k + q]);
+        if (q == total(k) - 1) return fr_one<PF>();
+        return ldg(pool + idx[off[k] + (q - 4)]);
+    }
+};
+
 // tr_hash_fields_tagged (fri.rs:28-35): the stream prefix || fields || suffix under the capacity FSv1-TRANSCRIPT-INIT (lazy duplex,
 // transcript/src/lib.rs:79-101).  Frames (prefix, suffix) per column c < 4; the layout says which sponge reads which frame and fields:
 //   Equal        : n sponges of k[0] fields at fields[0] + b * k[0], all under column 0's frame (one tag)

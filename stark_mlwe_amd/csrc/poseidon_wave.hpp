@@ -118,8 +118,8 @@ __device__ __forceinline__ void wave_permute(const WaveLds& L, const PoseidonDev
 }
 
 // K4 (wave form): one Merkle node per wave — hash_with_ds_dynamic([arity, level, position, label], children), eager sponge of rate T - 1.
-template <int T>
-__global__ void __launch_bounds__(64) k_hash_ds_wave(PoseidonDev P, DsStream D, fr_t* __restrict__ out) {
+template <int T, class DS>
+__global__ void __launch_bounds__(64) k_hash_ds_wave(PoseidonDev P, DS D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     WaveLds L; L.st = reinterpret_cast<uint32_t*>(lds); L.x = L.st + T * 9; L.part = L.x + T * 9;
     const int lane = threadIdx.x, rate = T - 1; const size_t k = blockIdx.x, total = D.total(k);
