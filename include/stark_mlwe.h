@@ -249,6 +249,16 @@ int32_t stark_sumcheck_verify_plain(stark_ctx_t* ctx, size_t k, uint64_t tree_la
 int32_t stark_sumcheck_prove_mf(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, size_t queries_per_round, stark_proof_t** out);
 int32_t stark_sumcheck_prove_mf_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, size_t queries_per_round, stark_proof_t** out);
 int32_t stark_sumcheck_verify_mf(stark_ctx_t* ctx, size_t k, uint64_t tree_label, size_t queries_per_round, const uint8_t* proof, size_t len, int32_t* accepted);
+/* prove_plain (channel/src/lib.rs:1045-1076) of `batch` independent witnesses of 2^k elements each: witnesses[i] is a DEVICE pointer,
+ * tree_labels[i] the instance's VK tree label (host array).  out[i] = what stark_sumcheck_prove_plain_dev returns for instance i alone,
+ * byte for byte.  The batch runs side by side: one Merkle level of all witnesses per launch, the B transcripts in one launch per round,
+ * and no host round trip inside the round loop.  batch == 0 returns STARK_OK.  STARK_ERR_INVALID_ARG (batch > 0): a null ctx, out,
+ * witnesses or tree_labels, a null witnesses[i], k > 40.  On any error every out[i] is NULL.  k = 0: claim = witness[0], no rounds. */
+int32_t stark_sumcheck_prove_plain_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k,
+                                             const uint64_t* tree_labels, stark_proof_t** out);
+/* prove_mf (:1130-1172), same contract, one queries_per_round for the batch; one host synchronisation per round (the query indices). */
+int32_t stark_sumcheck_prove_mf_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k,
+                                          const uint64_t* tree_labels, size_t queries_per_round, stark_proof_t** out);
 
 /* ---- Transcript (transcript/src/lib.rs:48-117) -------------------------------------------------------
  * Transcript::new(label, transcript::default_params()) / absorb_bytes / absorb_field(s) / challenge / challenges as an object:

@@ -416,6 +416,21 @@ pub mod channel {
         ctx.chk(unsafe { stark_sumcheck_prove_mf(ctx.raw(), limbs(witness), k, tree_label, queries_per_round, &mut raw) });
         take(ctx, raw)
     }
+    /// `prove_plain` of many witnesses in one device pass: `witnesses[i]` is a DEVICE pointer to 2^k elements, `tree_labels[i]` its VK tree
+    /// label; element i == `prove_plain(ctx, k, tree_labels[i], <witness i>)`, byte for byte.
+    pub unsafe fn prove_plain_batch_dev(ctx: &Ctx, k: usize, tree_labels: &[u64], witnesses: &[*const u64]) -> Vec<Vec<u8>> {
+        assert!(tree_labels.len() == witnesses.len(), "one tree label per witness");
+        let mut raw: Vec<*mut stark_proof_t> = vec![ptr::null_mut(); witnesses.len()];
+        ctx.chk(stark_sumcheck_prove_plain_batch_dev(ctx.raw(), witnesses.len(), witnesses.as_ptr(), k, tree_labels.as_ptr(), raw.as_mut_ptr()));
+        raw.into_iter().map(|h| take(ctx, h)).collect()
+    }
+    /// `prove_mf` of many witnesses in one device pass, one `queries_per_round` for the batch; same contract as `prove_plain_batch_dev`.
+    pub unsafe fn prove_mf_batch_dev(ctx: &Ctx, k: usize, tree_labels: &[u64], queries_per_round: usize, witnesses: &[*const u64]) -> Vec<Vec<u8>> {
+        assert!(tree_labels.len() == witnesses.len(), "one tree label per witness");
+        let mut raw: Vec<*mut stark_proof_t> = vec![ptr::null_mut(); witnesses.len()];
+        ctx.chk(stark_sumcheck_prove_mf_batch_dev(ctx.raw(), witnesses.len(), witnesses.as_ptr(), k, tree_labels.as_ptr(), queries_per_round, raw.as_mut_ptr()));
+        raw.into_iter().map(|h| take(ctx, h)).collect()
+    }
     /// `verify_mf(vk, proof)` — :1176-1240.
     pub fn verify_mf(ctx: &Ctx, k: usize, tree_label: u64, queries_per_round: usize, proof: &[u8]) -> bool {
         let mut ok = 0i32;

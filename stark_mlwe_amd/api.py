@@ -591,6 +591,33 @@ class Context:
         self._chk(self.lib.stark_sumcheck_verify_mf(self.h, k, tree_label, queries_per_round, buf, len(proof), C.byref(ok)))
         return bool(ok.value)
 
+    def prove_plain_batch_dev(self, k, tree_labels, witness_ptrs) -> list:
+        """prove_plain of each witness (DEVICE pointers, ints, of 2^k elements; tree_labels[i] its VK tree label) in one pass
+        (stark_sumcheck_prove_plain_batch_dev) -> list of proof bytes, each equal to prove_plain of that witness alone."""
+        return self._sumcheck_batch(0, k, tree_labels, 0, witness_ptrs)
+
+    def prove_mf_batch_dev(self, k, tree_labels, queries_per_round, witness_ptrs) -> list:
+        """prove_mf of each witness in one pass (stark_sumcheck_prove_mf_batch_dev) -> list of proof bytes."""
+        return self._sumcheck_batch(1, k, tree_labels, queries_per_round, witness_ptrs)
+
+    def _sumcheck_batch(self, mf, k, tree_labels, q, witness_ptrs):
+        B = len(witness_ptrs)
+        if len(tree_labels) != B:
+            raise StarkError(-1, "one tree label per witness")
+        if B == 0:
+            return []
+        w = (C.c_void_p * B)(*[None if p is None else int(p) for p in witness_ptrs])
+        lab = np.ascontiguousarray(tree_labels, dtype=np.uint64)
+        out = (C.c_void_p * B)()
+        if mf:
+            self._chk(self.lib.stark_sumcheck_prove_mf_batch_dev(self.h, B, w, k, _ptr(lab), q, out))
+        else:
+            self._chk(self.lib.stark_sumcheck_prove_plain_batch_dev(self.h, B, w, k, _ptr(lab), out))
+        res = []
+        for p in range(B):
+            res.append(self._proof_out(C.c_void_p(out[p]))[0])
+        return res
+
     def _proof_out(self, h):
         try:
             ln = self.lib.stark_proof_len(h)

@@ -15,6 +15,7 @@
 #include "fri_verify_batch.hpp"
 #include "mfma_digits.hpp"
 #include "poseidon_chain.hpp"
+#include "sumcheck_impl.hpp"     // the provers' transcript labels and sumcheck_batch.hpp (its HIP part is guarded)
 
 using namespace stark;
 
@@ -370,4 +371,74 @@ int hc_merkle_verify(void* tparams, int pairs, size_t cfg_arity, uint64_t label,
     return ok ? 1 : 0;
 }
 
+}  // extern "C"
+
+// ---- the batched sum-check provers (sumcheck_batch.hpp) through the host instantiation of the kernel bodies -------------------------
+struct ScHostExec {
+    HcParams* cp; HcParams* tp; std::vector<std::vector<uint64_t>> mem;
+    int32_t alloc(size_t bytes, void** out) { mem.emplace_back((bytes + 7) / 8 + 1, 0); *out = mem.back().data(); return 0; }
+    int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
+    int32_t download(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
+    int32_t ds_level(const DsBatchStream& D, fr_t* out) {
+        std::vector<fr_t> st(cp->dev.t);
+        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, cp->dev, D, k); }
+        return 0;
+    }
+    int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim) {
+        for (size_t b = 0; b < B; ++b) {
+            const fr_t* l = ptrs ? ptrs[b] : layers + b * len; fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
+            for (size_t j = 0; j < len / 2; ++j) { c0 = fr_add<PF>(c0, l[2 * j]); c1 = fr_add<PF>(c1, fr_sub<PF>(l[2 * j + 1], l[2 * j])); }
+            c01[2 * b] = c0; c01[2 * b + 1] = c1; if (claim) claim[b] = fr_add<PF>(fr_add<PF>(c0, c0), c1);
+        }
+        return 0;
+    }
+    int32_t fold(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, const fr_t* r, fr_t* next) {
+        for (size_t b = 0; b < B; ++b) {
+            const fr_t* l = ptrs ? ptrs[b] : layers + b * len;
+            for (size_t j = 0; j < len / 2; ++j) next[b * (len / 2) + j] = fr_add<PF>(l[2 * j], fr_mul<PF>(r[b], fr_sub<PF>(l[2 * j + 1], l[2 * j])));
+        }
+        return 0;
+    }
+    int32_t transcript(const TrBatchStream& T) { fr_t st[17]; for (size_t a = 0; a < T.n_active; ++a) { ArrayState s{st}; tr_batch_body(s, tp->dev, T, a); } return 0; }
+    int32_t gather(const fr_t* const* addr, size_t n, fr_t* out) { for (size_t j = 0; j < n; ++j) out[j] = *addr[j]; return 0; }
+};
+extern "C" {
+// One Merkle level of B same-shape trees (DsBatchStream): in = B x n_in contiguous (by_ptrs: read through a pointer per tree), labels[b]
+int hc_hash_ds_batch_level(void* params, size_t arity, uint32_t level, uint64_t pos0, const uint64_t* labels, const uint64_t* in, size_t n_in, size_t trees, int by_ptrs, uint64_t* out) {
+    HcParams* P = (HcParams*)params;
+    std::vector<fr_t> a(n_in * trees), st(P->dev.t); for (size_t i = 0; i < a.size(); ++i) a[i] = ld4(in + 4 * i);
+    std::vector<const fr_t*> ptrs(trees); for (size_t b = 0; b < trees; ++b) ptrs[b] = a.data() + b * n_in;
+    const DsBatchStream D = DsBatchStream::make(arity, level, pos0, labels, by_ptrs ? ptrs.data() : nullptr, by_ptrs ? nullptr : a.data(), n_in, trees);
+    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, D, k)); }
+    return 0;
+}
+// One launch of a TrBatchStream: state (17 per instance) and pos updated in place; out[a * nseg + s] per finished segment.
+int hc_tr_batch(void* tparams, uint64_t* state, uint32_t* pos, size_t n_inst, const uint32_t* inst, size_t inst0, size_t n_active, size_t nseg, const uint32_t* el_off,
+                const uint32_t* idx, const uint64_t* pool0, size_t n0, const uint64_t* pool1, size_t n1, int reset, int finish_last, uint64_t* out) {
+    HcParams* P = (HcParams*)tparams;
+    std::vector<fr_t> st(17 * n_inst), p0(n0), p1(n1), o(n_active * nseg, host::h_zero());
+    for (size_t i = 0; i < st.size(); ++i) st[i] = ld4(state + 4 * i);
+    for (size_t i = 0; i < n0; ++i) p0[i] = ld4(pool0 + 4 * i); for (size_t i = 0; i < n1; ++i) p1[i] = ld4(pool1 + 4 * i);
+    TrBatchStream T; T.state = st.data(); T.pos = pos; T.inst = inst; T.inst0 = inst0; T.n_active = n_active; T.nseg = nseg; T.el_off = el_off; T.idx = idx;
+    T.pool0 = p0.data(); T.pool1 = p1.data(); T.out = o.data(); T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = reset; T.finish_last = finish_last;
+    fr_t s17[17]; for (size_t a = 0; a < n_active; ++a) { ArrayState s{s17}; tr_batch_body(s, P->dev, T, a); }
+    for (size_t i = 0; i < st.size(); ++i) st4(state + 4 * i, st[i]);
+    for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
+    return 0;
+}
+// prove_plain (mf = 0) / prove_mf (mf = 1) of B witnesses (host arrays of 2^k elements) through the batched driver.  Writes the proofs back
+// to back into buf when cap suffices, their lengths into lens; returns the total length (0 on error).
+size_t hc_sumcheck_prove_batch(void* tparams, void* cparams, int mf, size_t B, const uint64_t* const* witnesses, size_t k, const uint64_t* labels, size_t q,
+                               uint8_t* buf, size_t cap, size_t* lens) {
+    const size_t n = (size_t)1 << k;
+    std::vector<std::vector<fr_t>> w(B, std::vector<fr_t>(n)); std::vector<const fr_t*> wp(B);
+    for (size_t b = 0; b < B; ++b) { for (size_t i = 0; i < n; ++i) w[b][i] = ld4(witnesses[b] + 4 * i); wp[b] = w[b].data(); }
+    ScHostExec X{(HcParams*)cparams, (HcParams*)tparams, {}};
+    ScBatch<ScHostExec> S(X, B, wp.data(), k, labels);
+    std::vector<std::vector<uint8_t>> pr;
+    if (mf ? S.prove_mf(q, pr) : S.prove_plain(pr)) return 0;
+    size_t tot = 0; for (size_t b = 0; b < B; ++b) { lens[b] = pr[b].size(); tot += pr[b].size(); }
+    if (buf && cap >= tot) { size_t o = 0; for (auto& p : pr) { memcpy(buf + o, p.data(), p.size()); o += p.size(); } }
+    return tot;
+}
 }  // extern "C"

@@ -152,6 +152,23 @@ template <class S> FR_HD fr_t tr_hash_body(const S& s, const PoseidonDev& P, con
     }
     return permute_core(s, P, true);
 }
+// Active instance a of a TrBatchStream: the stored (or reset) state, the lazy permute before absorbing into a full rate, one permutation
+// and squeeze per finished segment; state and cursor written back.
+template <class S> FR_HD void tr_batch_body(const S& s, const PoseidonDev& P, const TrBatchStream& T, size_t a) {
+    const size_t b = T.instance(a);
+    for (int j = 0; j < 17; ++j) s.st(j, T.reset ? (j == 16 ? T.init_cap : fr_zero<PF>()) : T.state[17 * b + j]);
+    uint32_t pos = T.reset ? 0u : T.pos[b];
+    for (size_t sg = 0; sg < T.nseg; ++sg) {
+        const size_t seg = a * T.nseg + sg;
+        for (uint32_t j = T.el_off[seg]; j < T.el_off[seg + 1]; ++j) {
+            if (pos == 16) { permute_core(s, P, false); pos = 0; }
+            s.st((int)pos, fr_add<PF>(s.ld((int)pos), T.elem(j))); ++pos;
+        }
+        if (T.finishes(sg)) { T.out[seg] = permute_core(s, P, false); pos = 0; }
+    }
+    for (int j = 0; j < 17; ++j) T.state[17 * b + j] = s.ld(j);
+    T.pos[b] = pos;
+}
 // Generic eager sponge over explicit per-hash streams.
 //   mode 0: hash_with_ds_dynamic — stream = a_k || b_k || 1, zero-padded (eager permute on a full rate).
 //   mode 1: hash_with_ds (legacy) — state[t-1] = tag, b_k absorbed in rate-sized chunks, one permutation

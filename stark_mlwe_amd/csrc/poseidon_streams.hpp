@@ -58,6 +58,50 @@ struct DsGatherStream {
     }
 };
 
+// One Merkle level of B same-shape trees in one launch (the batched sum-check commits, sumcheck_batch.hpp): hash k belongs to tree
+// k / nodes_per_tree and is node j = k % nodes_per_tree of that tree's level, position pos0 + j, under the tree's own label.
+//   hash k = hash_with_ds_dynamic([arity, level, pos0 + j, labels[tree]] || children || 1), eager sponge, zero padded, cap 0
+// with children in_tree[j*arity .. min((j+1)*arity, n_in)) (the last node of every tree may be ragged) and in_tree = in_ptrs[tree] (a
+// device array of per-tree pointers: the witnesses) or in + tree * n_in (a contiguous B x n_in buffer: the folded layers and upper levels).
+struct DsBatchStream {
+    fr_t arity_f, level_f; uint64_t pos0; const uint64_t* labels; size_t arity, n_in, nodes_per_tree, n_out;
+    const fr_t* const* in_ptrs; const fr_t* in;
+    static inline DsBatchStream make(size_t arity, uint32_t level, uint64_t pos0, const uint64_t* labels, const fr_t* const* in_ptrs, const fr_t* in, size_t n_in, size_t trees) {
+        DsBatchStream D;
+        D.arity_f = fr_from_u64<PF>(arity); D.level_f = fr_from_u64<PF>(level); D.pos0 = pos0; D.labels = labels; D.arity = arity; D.n_in = n_in;
+        D.nodes_per_tree = (n_in + arity - 1) / arity; D.n_out = D.nodes_per_tree * trees; D.in_ptrs = in_ptrs; D.in = in;
+        return D;
+    }
+    FR_HD size_t tree(size_t k) const { return k / nodes_per_tree; }
+    FR_HD uint64_t position(size_t k) const { return pos0 + k % nodes_per_tree; }
+    FR_HD size_t total(size_t k) const { const size_t j = k % nodes_per_tree; return 4 + ((j + 1) * arity <= n_in ? arity : n_in - j * arity) + 1; }
+    FR_HD size_t max_total() const { return 4 + arity + 1; }
+    FR_HD fr_t elem(size_t k, size_t q) const {
+        if (q < 4) return q == 0 ? arity_f : (q == 1 ? level_f : (q == 2 ? fr_from_u64<PF>(position(k)) : fr_from_u64<PF>(labels[tree(k)])));
+        if (q == total(k) - 1) return fr_one<PF>();
+        const size_t t = tree(k), j = k % nodes_per_tree;
+        const fr_t* src = in_ptrs ? in_ptrs[t] : in + t * n_in;
+        return ldg(src + j * arity + (q - 4));
+    }
+};
+
+// B streaming transcripts (transcript/src/lib.rs:79-101, lazy duplex) advanced in one launch, one workgroup per active instance
+// (the batched sum-check provers, sumcheck_batch.hpp).  Instance b keeps state[17 b .. 17 b + 16] and its rate cursor pos[b] in
+// device memory between launches; active a runs instance inst[a] (inst == nullptr: inst0 + a).  Active a runs nseg segments: segment
+// s = a * nseg + s' absorbs the elements idx[el_off[s] .. el_off[s + 1]) gathered from the pools (an index with bit 31 set reads
+// pool1, else pool0), then — every segment but an unfinished last one — permutes and squeezes state[0] into out[s] (a challenge).
+//   reset       : the instance starts from Transcript::new's state (zeros, capacity `init_cap`, cursor 0) instead of the stored one
+//   finish_last : 0 leaves the last segment absorbed but not permuted (the cursor then records where the next absorb goes)
+struct TrBatchStream {
+    fr_t* state; uint32_t* pos; const uint32_t* inst; size_t inst0, n_active, nseg;
+    const uint32_t* el_off; const uint32_t* idx; const fr_t* pool0; const fr_t* pool1; fr_t* out;
+    fr_t init_cap; int reset, finish_last;
+    static constexpr uint32_t kPool1 = 0x80000000u;
+    FR_HD size_t instance(size_t a) const { return inst ? (size_t)inst[a] : inst0 + a; }
+    FR_HD bool finishes(size_t s) const { return finish_last || s + 1 < nseg; }
+    FR_HD fr_t elem(size_t j) const { const uint32_t x = idx[j]; return x & kPool1 ? ldg(pool1 + (x & ~kPool1)) : ldg(pool0 + x); }
+};
+
 // tr_hash_fields_tagged (fri.rs:28-35): the stream prefix || fields || suffix under the capacity FSv1-TRANSCRIPT-INIT (lazy duplex,
 // transcript/src/lib.rs:79-101).  Frames (prefix, suffix) per column c < 4; the layout says which sponge reads which frame and fields:
 //   Equal        : n sponges of k[0] fields at fields[0] + b * k[0], all under column 0's frame (one tag)

@@ -4,23 +4,41 @@
 //   * MerkleCommitment::commit (commitment/src/lib.rs:85-90: arity 16, parameters "POSEIDON-T17-X5-SEED") of the witness and of every
 //     shrinking folded layer = the level-batched Merkle kernels of the FRI path (merkle_build_on);
 //   * round coefficients c0 = sum a_j, c1 = sum (b_j - a_j) (:406-416) and the fold (1-r) a + r b (:456-462) = streaming kernels;
-//   * the Fiat-Shamir channel (:7-117) = a DEVICE-RESIDENT transcript: absorbs are queued on the host and run as ONE launch of the
-//     one-wave sponge (poseidon_coop.hpp) when a challenge is drawn — the only host round trips are the challenges themselves,
-//     which the protocol serialises anyway (r_i depends on the previous root, transcript/src/lib.rs:92-101).
+//   * the Fiat-Shamir channel (:7-117) = DEVICE-RESIDENT transcripts: the verifiers and the ABI's transcript object queue absorbs on the
+//     host and run them as ONE launch when a challenge is drawn (DevTranscript); the provers lay out what every instance absorbs as pool
+//     indices and advance all transcripts of a batch per launch (TrBatchStream), so prove_plain has no host round trip in its rounds.
+// Every prove — one witness or many — runs the batched round loops of sumcheck_batch.hpp over the device executor below (ScDevExec).
 // Proof bytes = bincode 1.x layout of the reference's serde structs ProofPlain / ProofMF (:925-979), what its bench measures.
 #pragma once
+#include <memory>
 #include <set>
 #include "fri_verify.hpp"
+
+// The provers' transcript labels, the reference's strings verbatim (channel/src/lib.rs).  The round loops of sumcheck_batch.hpp lay out
+// their absorbs with these; the host-check library includes this file for them (everything HIP below is guarded).
+namespace stark { namespace sc_lab {
+constexpr const char *digest = "CHAN/SEND/DIGEST", *open = "CHAN/SEND/OPEN", *arity = "PROOF/ARITY", *group_sizes = "PROOF/GROUP_SIZES",
+                     *siblings = "PROOF/SIBLINGS";                                                                          // :22-56
+constexpr const char *plain = "E2E/PLAIN", *root = "commit/root", *claim = "SUMCHECK/CLAIM", *round = "SUMCHECK/ROUND", *c0 = "COEFF/c0",
+                     *c1 = "COEFF/c1", *r = "sumcheck/r";                                                                   // :175, :442-472, :1064
+constexpr const char *mf = "E2E/MF", *mf_round_chal = "SUMCHECK-MF/ROUND-CHAL", *mf_r = "SUMCHECK/MF/R", *r_i = "r_i", *mf_root0 = "sumcheck-mf/root/0",
+                     *mf_claim = "SUMCHECK/MF/CLAIM", *mf_round = "SUMCHECK/MF/ROUND", *mf_root_next = "sumcheck-mf/root/next", *mf_q = "sumcheck-mf/q";   // :593-735
+// finalize_eval absorbs "SUMCHECK/FINAL/EVAL" / "SUMCHECK/MF/FINAL/EVAL" and the final value last (:474-484, :732-738); nothing is drawn
+// after it, so no launch would ever run that absorb and the provers leave it out.
+} }
+#include "sumcheck_batch.hpp"
 
 using namespace stark;
 
 struct stark_proof { std::vector<uint8_t> bytes; size_t size_estimate = 0; double ms[3] = {0, 0, 0}; };   // same object as capi_fri.hip's
 
+#if defined(__HIPCC__)
+
 namespace {
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------
-// block partials of (c0, c1) over pairs (a, b) = (layer[2j], layer[2j+1]); out[2*block], out[2*block+1]
-__global__ void __launch_bounds__(256) k_sc_coeffs(const fr_t* __restrict__ layer, uint64_t npairs, fr_t* __restrict__ out) {
+// block partials of (c0, c1) over pairs (a, b) = (layer[2j], layer[2j+1]); out[2*block], out[2*block+1] (grid-stride over gridDim.x blocks)
+__device__ __forceinline__ void sc_coeffs_block(const fr_t* __restrict__ layer, uint64_t npairs, fr_t* __restrict__ out) {
     __shared__ uint4 red[2 * 2 * 4];
     fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
     for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < npairs; j += (uint64_t)gridDim.x * blockDim.x) {
@@ -42,13 +60,6 @@ __global__ void __launch_bounds__(256) k_sc_coeffs(const fr_t* __restrict__ laye
         }
         stg(out + 2 * blockIdx.x, t0); stg(out + 2 * blockIdx.x + 1, t1);
     }
-}
-// final reduction of the block partials (one block): out[0] = sum partial c0, out[1] = sum partial c1
-__global__ void __launch_bounds__(64) k_sc_coeffs_final(const fr_t* __restrict__ part, uint64_t nblocks, fr_t* __restrict__ out) {
-    fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
-    for (uint64_t i = threadIdx.x; i < nblocks; i += 64) { c0 = fr_add<PF>(c0, ldg(part + 2 * i)); c1 = fr_add<PF>(c1, ldg(part + 2 * i + 1)); }
-    for (int sft = 1; sft < 64; sft <<= 1) { c0 = fr_add<PF>(c0, shfl_xor_fr(c0, sft)); c1 = fr_add<PF>(c1, shfl_xor_fr(c1, sft)); }
-    if (threadIdx.x == 0) { stg(out, c0); stg(out + 1, c1); }
 }
 // next[j] = (1 - r) * layer[2j] + r * layer[2j+1]  =  a + r * (b - a)
 __global__ void __launch_bounds__(256) k_sc_fold(const fr_t* __restrict__ layer, uint64_t npairs, fr_t r, fr_t* __restrict__ next) {
@@ -89,6 +100,73 @@ __global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))
     if (threadIdx.x == 0) *pos_io = finish ? 0u : (total ? (uint32_t)(total - 16 * ((total - 1) / 16)) : 0u);
 }
 
+// ---- the batched round kernels (sumcheck_batch.hpp): instance b = b0 + blockIdx.y reads layer ptrs[b] or layers + b * len ----------------
+// block partials of (c0, c1) of every layer: part[2 (b gridDim.x + block)], +1
+__global__ void __launch_bounds__(256) k_sc_coeffs_batch(const fr_t* const* __restrict__ ptrs, const fr_t* __restrict__ layers, uint64_t len, uint64_t b0, fr_t* __restrict__ part) {
+    const uint64_t b = b0 + blockIdx.y;
+    sc_coeffs_block(ptrs ? ptrs[b] : layers + b * len, len / 2, part + 2 * (uint64_t)gridDim.x * b);
+}
+// one block per instance: c01[2b] = sum of its partial c0, c01[2b+1] = of c1; claim != nullptr: claim[b] = 2 c0 + c1 (send_claim, :434-446)
+__global__ void __launch_bounds__(64) k_sc_coeffs_final_batch(const fr_t* __restrict__ part, uint64_t nblocks, fr_t* __restrict__ c01, fr_t* __restrict__ claim) {
+    const uint64_t b = blockIdx.x; const fr_t* p = part + 2 * nblocks * b;
+    fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
+    for (uint64_t i = threadIdx.x; i < nblocks; i += 64) { c0 = fr_add<PF>(c0, ldg(p + 2 * i)); c1 = fr_add<PF>(c1, ldg(p + 2 * i + 1)); }
+    for (int sft = 1; sft < 64; sft <<= 1) { c0 = fr_add<PF>(c0, shfl_xor_fr(c0, sft)); c1 = fr_add<PF>(c1, shfl_xor_fr(c1, sft)); }
+    if (threadIdx.x == 0) { stg(c01 + 2 * b, c0); stg(c01 + 2 * b + 1, c1); if (claim) stg(claim + b, fr_add<PF>(fr_add<PF>(c0, c0), c1)); }
+}
+// next[b len/2 + j] = a + r_b (b - a) with r_b = r[b], the instance's challenge as the transcript kernel left it in device memory
+__global__ void __launch_bounds__(256) k_sc_fold_batch(const fr_t* const* __restrict__ ptrs, const fr_t* __restrict__ layers, uint64_t len, uint64_t b0, const fr_t* __restrict__ r,
+                                                       fr_t* __restrict__ next) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = b0 + blockIdx.y, np = len / 2;
+    if (j >= np) return;
+    const fr_t* layer = ptrs ? ptrs[b] : layers + b * len;
+    const fr_t a = ldg(layer + 2 * j), c = ldg(layer + 2 * j + 1), rb = ldg(r + b);
+    stg(next + b * np + j, fr_add<PF>(a, fr_mul<PF>(rb, fr_sub<PF>(c, a))));
+}
+// out[j] = *addr[j]: the roots of one-leaf trees and the openings of prove_mf (addresses built on the host from the known shapes)
+__global__ void __launch_bounds__(256) k_sc_gather(const fr_t* const* __restrict__ addr, uint64_t n, fr_t* __restrict__ out) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) stg(out + j, ldg(addr[j]));
+}
+// B transcripts (TrBatchStream), one wave each: k_tr_stream's absorb loop per segment, the elements gathered from the pools.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_batch(PoseidonDev P, TrBatchStream T) {
+    extern __shared__ uint4 lds[];
+    CoopLds L = coop_setup<17>(lds, P);
+    const int lane = threadIdx.x;
+    const size_t a = blockIdx.x, b = T.instance(a);
+    fr_t s = T.reset ? (lane == 16 ? T.init_cap : fr_zero<PF>()) : (lane < 17 ? ldg(T.state + 17 * b + lane) : fr_zero<PF>());
+    uint32_t pos = T.reset ? 0u : T.pos[b];
+    for (size_t sg = 0; sg < T.nseg; ++sg) {
+        const size_t seg = a * T.nseg + sg;
+        const uint64_t e0 = T.el_off[seg], n = T.el_off[seg + 1] - e0;
+        for (uint64_t i = 0; i < n;) {
+            if (pos == 16) { s = coop_permute<17>(s, P, L, lane); pos = 0; }                 // only before absorbing more (lazy)
+            const uint64_t take = (16 - pos) < (n - i) ? (16 - pos) : (n - i);
+            if ((uint32_t)lane >= pos && (uint64_t)lane < pos + take) s = fr_add<PF>(s, T.elem(e0 + i + (lane - pos)));
+            pos += (uint32_t)take; i += take;
+        }
+        if (T.finishes(sg)) { s = coop_permute<17>(s, P, L, lane); pos = 0; if (lane == 0) stg(T.out + seg, s); }
+    }
+    if (lane < 17) stg(T.state + 17 * b + lane, s);
+    if (lane == 0) T.pos[b] = pos;
+}
+// The same on five waves: segment `sg` of every active instance, as k_tr_stream_chain runs it (the stored cursor becomes leading no-op
+// elements, so the lazy permutations fall where the one-wave form puts them; a finished segment leaves the cursor at 0).  One launch per
+// segment index: a loop over the segments inside this kernel raises it from 159 to 214 VGPRs (k_tr_stream_chain: 157).
+__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_batch_chain(PoseidonDev P, row::Consts RK, TrBatchStream T, uint32_t sg) {
+    extern __shared__ uint4 lds[];
+    const size_t a = blockIdx.x, b = T.instance(a), seg = a * T.nseg + sg;
+    const bool fresh = T.reset && sg == 0;
+    fr_t* st = T.state + 17 * b;
+    const uint32_t lead = fresh ? 0u : T.pos[b];                                            // every thread reads it before thread 0 writes it back (barriers in between)
+    const uint32_t e0 = T.el_off[seg];
+    const size_t total = (size_t)lead + (T.el_off[seg + 1] - e0);
+    const bool fin = T.finishes(sg);
+    chain_sponge_ex(P, RK, lds, total, T.init_cap, [&](size_t q) -> fr_t { return q < lead ? fr_zero<PF>() : T.elem(e0 + (q - lead)); },
+                    fin ? T.out + seg : (fr_t*)nullptr, fresh ? (const fr_t*)nullptr : st, fin, st);
+    if (threadIdx.x == 0) T.pos[b] = fin ? 0u : (total ? (uint32_t)(total - 16 * ((total - 1) / 16)) : 0u);
+}
+
 // ---- device-resident transcript -----------------------------------------------------------------------------------------
 struct DevTranscript {
     stark_ctx* ctx; DevBuf state, posb, out; std::vector<fr_t> pending; stark_params* tp = nullptr;
@@ -127,20 +205,6 @@ struct DevTranscript {
     }
 };
 
-// ---- bincode layout of ProofPlain / ProofMF (channel/src/lib.rs:925-979) ---------------------------------------------------
-struct BinW {
-    std::vector<uint8_t>& b; explicit BinW(std::vector<uint8_t>& v) : b(v) {}
-    void u64(uint64_t x) { enc_u64(b, x); }
-    void fb(const fr_t& x) { u64(32); enc_fr(b, x); }                                      // FBytes: serde_bytes Vec<u8> of the 32-byte compressed element
-    void idxs(const std::vector<size_t>& v) { u64(v.size()); for (size_t x : v) u64(x); }
-    void fvec(const std::vector<fr_t>& v) { u64(v.size()); for (auto& x : v) fb(x); }
-    void mproof(const MerkleProofHost& p) {                                                // MerkleProofBytes { arity, group_sizes, indices, siblings }
-        u64(p.arity);
-        u64(p.group_sizes.size()); for (auto& l : p.group_sizes) { u64(l.size()); for (uint8_t x : l) b.push_back(x); }
-        idxs(p.indices);
-        u64(p.siblings.size()); for (auto& l : p.siblings) fvec(l);
-    }
-};
 struct BinR {
     ByteReader R; explicit BinR(const uint8_t* p, size_t n) : R(p, n) {}
     fr_t fb() { if (R.u64() != 32) R.ok = false; return R.fr(); }
@@ -154,9 +218,7 @@ struct BinR {
         return R.ok;
     }
 };
-struct RoundMFHost { fr_t c0, c1, next_root; std::vector<size_t> cur_indices, next_indices; std::vector<fr_t> cur_values, next_values; MerkleProofHost cur_proof, next_proof; };
 
-static inline std::vector<uint8_t> lab_idx(const char* base, uint64_t i) { std::vector<uint8_t> l((const uint8_t*)base, (const uint8_t*)base + strlen(base)); for (int j = 0; j < 8; ++j) l.push_back((uint8_t)(i >> (8 * j))); return l; }
 static void send_digest(DevTranscript& T, const char* label, const fr_t& d) { T.absorb_str("CHAN/SEND/DIGEST"); T.absorb_str(label); T.absorb_field(d); }   // :22-26
 static void send_opening(DevTranscript& T, const std::vector<size_t>& idx, const std::vector<fr_t>& vals, const MerkleProofHost& pr) {                  // :32-62
     T.absorb_str("CHAN/SEND/OPEN");
@@ -177,137 +239,79 @@ static int32_t commit_params(stark_ctx* ctx, stark_params** out) {
     STARK_TRY(stark_poseidon_params_t17_seed(ctx, (const uint8_t*)seed, strlen(seed), &P));
     ctx->merkle_params[-17] = P; *out = P; return STARK_OK;
 }
-// (c0, c1) of a layer, on the host (the protocol sends them)
-static int32_t round_coeffs(stark_ctx* ctx, const fr_t* layer, size_t len, fr_t* c0, fr_t* c1) {
-    const uint64_t np = len / 2; const unsigned grid = (unsigned)std::min<uint64_t>((np + 255) / 256, 1024);
-    DevBuf part, res; STARK_HIP(ctx, part.alloc(ctx, (size_t)grid * 2 * sizeof(fr_t))); STARK_HIP(ctx, res.alloc(ctx, 2 * sizeof(fr_t)));
-    hipLaunchKernelGGL(k_sc_coeffs, dim3(grid), dim3(256), 0, ctx->stream, layer, np, part.fr());
-    hipLaunchKernelGGL(k_sc_coeffs_final, dim3(1), dim3(64), 0, ctx->stream, (const fr_t*)part.fr(), (uint64_t)grid, res.fr());
-    STARK_HIP(ctx, hipGetLastError());
-    fr_t h[2]; STARK_HIP(ctx, hipMemcpyAsync(h, res.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *c0 = h[0]; *c1 = h[1]; return STARK_OK;
-}
 static int32_t fold(stark_ctx* ctx, const fr_t* layer, size_t len, const fr_t& r, fr_t* next) {
     const uint64_t np = len / 2;
     hipLaunchKernelGGL(k_sc_fold, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, layer, np, r, next);
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
 }
-static int32_t read_elems(stark_ctx* ctx, const fr_t* dev, const std::vector<size_t>& idx, std::vector<fr_t>& out) {
-    out.resize(idx.size()); if (idx.empty()) return STARK_OK;
-    DevBuf di, dout; STARK_HIP(ctx, di.alloc(ctx, idx.size() * 8)); STARK_HIP(ctx, dout.alloc(ctx, idx.size() * sizeof(fr_t)));
-    std::vector<uint64_t> ix(idx.begin(), idx.end());
-    STARK_HIP(ctx, hipMemcpyAsync(di.p, ix.data(), ix.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather, dim3((unsigned)((ix.size() + 255) / 256)), dim3(256), 0, ctx->stream, dev, (const uint64_t*)di.p, (uint64_t)ix.size(), dout.fr());
-    STARK_HIP(ctx, hipGetLastError());
-    STARK_HIP(ctx, hipMemcpyAsync(out.data(), dout.p, ix.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return STARK_OK;
-}
-static int32_t tree_root(stark_ctx* ctx, stark_tree* t, fr_t* r) {
-    STARK_HIP(ctx, hipMemcpyAsync(r, t->levels.back(), sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
-}
-struct TreeHolder { stark_tree* t = nullptr; ~TreeHolder() { if (t) stark_merkle_free(t); } };
-
-// prove_plain (:1045-1076) on a device-resident witness of 2^k elements
-static int32_t prove_plain_impl(stark_ctx* ctx, const fr_t* witness, size_t k, uint64_t tree_label, stark_proof** out) {
-    if (k > 40) return ctx->fail(STARK_ERR_INVALID_ARG, "k too large");
-    const size_t n = (size_t)1 << k;
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
-    DevTranscript T(ctx); STARK_TRY(T.init((const uint8_t*)"E2E/PLAIN", 9));
-    TreeHolder tree; STARK_TRY(merkle_build_on(ctx, ctx->stream, cp, 16, tree_label, witness, n, 0, nullptr, 1, 0, 0, 0, false, &tree.t));   // MerkleProver::commit_vector (:172-179)
-    fr_t root; STARK_TRY(tree_root(ctx, tree.t, &root));
-    send_digest(T, "commit/root", root);
-    DevBuf bufA, bufB; STARK_HIP(ctx, bufA.alloc(ctx, std::max<size_t>(n / 2, 1) * sizeof(fr_t))); STARK_HIP(ctx, bufB.alloc(ctx, std::max<size_t>(n / 4, 1) * sizeof(fr_t)));
-    const fr_t* layer = witness; size_t len = n;
-    stark_proof* P = new stark_proof(); BinW W(P->bytes);
-    auto bail = [&](int32_t rc) { delete P; return rc; };
-    std::vector<std::pair<fr_t, fr_t>> rounds;
-    fr_t c0, c1;
-    if (k == 0) { std::vector<fr_t> v; int32_t rc = read_elems(ctx, witness, {0}, v); if (rc) return bail(rc); T.absorb_str("SUMCHECK/CLAIM"); T.absorb_field(v[0]); }
-    for (size_t i = 0; i < k; ++i) {
-        { int32_t rc = round_coeffs(ctx, layer, len, &c0, &c1); if (rc) return bail(rc); }
-        if (i == 0) { T.absorb_str("SUMCHECK/CLAIM"); T.absorb_field(host::h_add(host::h_add(c0, c0), c1)); }      // send_claim (:434-446): s = sum of the table = 2 c0 + c1
-        T.absorb_str("SUMCHECK/ROUND"); T.absorb_u64((uint64_t)i);                                                // round (:448-472)
-        T.absorb_str("COEFF/c0"); T.absorb_field(c0); T.absorb_str("COEFF/c1"); T.absorb_field(c1);
-        fr_t r; { auto lb = lab_idx("sumcheck/r", i); int32_t rc = T.challenge(lb.data(), lb.size(), &r); if (rc) return bail(rc); }
-        fr_t* nx = (i & 1) ? bufB.fr() : bufA.fr();
-        { int32_t rc = fold(ctx, layer, len, r, nx); if (rc) return bail(rc); }
-        layer = nx; len /= 2; rounds.push_back({c0, c1});
-    }
-    std::vector<fr_t> fin; { int32_t rc = read_elems(ctx, layer, {0}, fin); if (rc) return bail(rc); }
-    T.absorb_str("SUMCHECK/FINAL/EVAL"); T.absorb_field(fin[0]);                                                   // :474-484 (bound; no further challenge is drawn)
-    W.fb(root); W.u64(rounds.size()); for (auto& r : rounds) { W.fb(r.first); W.fb(r.second); }
-    P->bytes.push_back(0);                                                                                         // extra_openings: None
-    W.fb(fin[0]); P->size_estimate = P->bytes.size();
-    *out = P; return STARK_OK;
-}
-
 // mf_round_challenge_from_root (:592-598): a fresh transcript per round
 static int32_t mf_round_challenge(stark_ctx* ctx, size_t round_idx, const fr_t& prev_root, fr_t* r) {
     DevTranscript T(ctx); STARK_TRY(T.init((const uint8_t*)"SUMCHECK-MF/ROUND-CHAL", 22));
     T.absorb_str("SUMCHECK/MF/R"); T.absorb_u64((uint64_t)round_idx); T.absorb_field(prev_root);
     return T.challenge((const uint8_t*)"r_i", 3, r);
 }
-static inline size_t mf_query_index(const fr_t& r, size_t half) {                            // :667-676
-    const fr_t c = fr_to_canonical<PallasFr>(r); uint64_t acc = 0;
-    for (int i = 0; i < 4; ++i) acc ^= (uint64_t)c.v[2 * i] | ((uint64_t)c.v[2 * i + 1] << 32);
-    return (size_t)(acc % (uint64_t)half);
-}
-// prove_mf (:1130-1172)
-static int32_t prove_mf_impl(stark_ctx* ctx, const fr_t* witness, size_t k, uint64_t tree_label, size_t qpr, stark_proof** out) {
-    if (k > 40) return ctx->fail(STARK_ERR_INVALID_ARG, "k too large");
-    const size_t n = (size_t)1 << k;
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
-    DevTranscript T(ctx); STARK_TRY(T.init((const uint8_t*)"E2E/MF", 6));
-    TreeHolder cur_tree; STARK_TRY(merkle_build_on(ctx, ctx->stream, cp, 16, tree_label, witness, n, 0, nullptr, 1, 0, 0, 0, false, &cur_tree.t));     // SumCheckMFProver::new (:601-622)
-    fr_t cur_root; STARK_TRY(tree_root(ctx, cur_tree.t, &cur_root));
-    send_digest(T, "sumcheck-mf/root/0", cur_root);
-    const fr_t initial_root = cur_root;
-    DevBuf bufA, bufB; STARK_HIP(ctx, bufA.alloc(ctx, std::max<size_t>(n / 2, 1) * sizeof(fr_t))); STARK_HIP(ctx, bufB.alloc(ctx, std::max<size_t>(n / 4, 1) * sizeof(fr_t)));
-    const fr_t* layer = witness; size_t len = n;
-    std::vector<RoundMFHost> rounds; fr_t c0, c1;
-    if (k == 0) { std::vector<fr_t> v; STARK_TRY(read_elems(ctx, witness, {0}, v)); T.absorb_str("SUMCHECK/MF/CLAIM"); T.absorb_field(v[0]); }
-    for (size_t i = 0; i < k; ++i) {                                                        // round (:631-737)
-        RoundMFHost R;
-        STARK_TRY(round_coeffs(ctx, layer, len, &c0, &c1));
-        if (i == 0) { T.absorb_str("SUMCHECK/MF/CLAIM"); T.absorb_field(host::h_add(host::h_add(c0, c0), c1)); }     // send_claim (:624-629)
-        T.absorb_str("SUMCHECK/MF/ROUND"); T.absorb_u64((uint64_t)i);
-        T.absorb_str("COEFF/c0"); T.absorb_field(c0); T.absorb_str("COEFF/c1"); T.absorb_field(c1);
-        fr_t r; STARK_TRY(mf_round_challenge(ctx, i, cur_root, &r));
-        const size_t half = len / 2;
-        fr_t* nx = (i & 1) ? bufB.fr() : bufA.fr();
-        STARK_TRY(fold(ctx, layer, len, r, nx));
-        TreeHolder next_tree; STARK_TRY(merkle_build_on(ctx, ctx->stream, cp, 16, tree_label, nx, half, 0, nullptr, 1, 0, 0, 0, false, &next_tree.t));
-        fr_t next_root; STARK_TRY(tree_root(ctx, next_tree.t, &next_root));
-        send_digest(T, "sumcheck-mf/root/next", next_root);
-        const size_t q_target = std::min(std::max(qpr, (size_t)1), half);                   // :656
-        std::set<size_t> qs; size_t attempt = 0, j = 0; const size_t max_attempts = std::max(q_target * 16, (size_t)16);
-        while (qs.size() < q_target && attempt < max_attempts) {
-            std::vector<uint8_t> ql((const uint8_t*)"sumcheck-mf/q", (const uint8_t*)"sumcheck-mf/q" + 13);
-            for (int b = 0; b < 8; ++b) ql.push_back((uint8_t)((uint64_t)i >> (8 * b))); for (int b = 0; b < 8; ++b) ql.push_back((uint8_t)((uint64_t)j >> (8 * b)));
-            fr_t rr; STARK_TRY(T.challenge(ql.data(), ql.size(), &rr));
-            if (half > 0) qs.insert(mf_query_index(rr, half));
-            ++j; ++attempt;
-        }
-        if (qs.size() < q_target) for (size_t idx = 0; idx < half && qs.size() < q_target; ++idx) qs.insert(idx);      // :683-690
-        std::vector<size_t> queries(qs.begin(), qs.end());
-        for (size_t jj : queries) { R.cur_indices.push_back(2 * jj); R.cur_indices.push_back(2 * jj + 1); }
-        STARK_TRY(read_elems(ctx, layer, R.cur_indices, R.cur_values));
-        STARK_TRY(merkle_open_host(cur_tree.t, R.cur_indices, R.cur_proof));
-        R.next_indices = queries; STARK_TRY(read_elems(ctx, nx, queries, R.next_values));
-        STARK_TRY(merkle_open_host(next_tree.t, R.next_indices, R.next_proof));
-        send_opening(T, R.cur_indices, R.cur_values, R.cur_proof);
-        send_opening(T, R.next_indices, R.next_values, R.next_proof);
-        R.c0 = c0; R.c1 = c1; R.next_root = next_root;
-        rounds.push_back(std::move(R));
-        std::swap(cur_tree.t, next_tree.t); cur_root = next_root; layer = nx; len = half;
+// The device executor of the batched drivers (sumcheck_batch.hpp): every operation is one launch (or a few, for more than 65535 layers) on
+// the context's stream; uploads are staged until the next download synchronises.
+struct ScDevExec {
+    stark_ctx* ctx; stark_params* cp; stark_params* tp;
+    std::vector<std::unique_ptr<DevBuf>> mem; std::vector<std::vector<uint8_t>> staged;
+    ScDevExec(stark_ctx* c, stark_params* commit, stark_params* tr) : ctx(c), cp(commit), tp(tr) {}
+    ~ScDevExec() { if (!staged.empty()) (void)hipStreamSynchronize(ctx->stream); }
+    int32_t alloc(size_t bytes, void** out) { mem.emplace_back(new DevBuf()); STARK_HIP(ctx, mem.back()->alloc(ctx, bytes)); *out = mem.back()->p; return STARK_OK; }
+    int32_t upload(void* dst, const void* src, size_t bytes) {
+        staged.emplace_back((const uint8_t*)src, (const uint8_t*)src + bytes);
+        STARK_HIP(ctx, hipMemcpyAsync(dst, staged.back().data(), bytes, hipMemcpyHostToDevice, ctx->stream)); return STARK_OK;
     }
-    std::vector<fr_t> fin; STARK_TRY(read_elems(ctx, layer, {0}, fin));
-    T.absorb_str("SUMCHECK/MF/FINAL/EVAL"); T.absorb_field(fin[0]);          // finalize_eval (:732-738): bound, nothing is drawn after it (queued, never launched)
-    stark_proof* P = new stark_proof(); BinW W(P->bytes);
-    W.fb(initial_root); W.u64(rounds.size());
-    for (auto& R : rounds) { W.fb(R.c0); W.fb(R.c1); W.fb(R.next_root); W.idxs(R.cur_indices); W.fvec(R.cur_values); W.mproof(R.cur_proof); W.idxs(R.next_indices); W.fvec(R.next_values); W.mproof(R.next_proof); }
-    W.fb(fin[0]); P->size_estimate = P->bytes.size();
-    *out = P; return STARK_OK;
+    int32_t download(void* dst, const void* src, size_t bytes) {
+        STARK_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        staged.clear(); return STARK_OK;
+    }
+    int32_t ds_level(const DsBatchStream& D, fr_t* out) { return launch_ds(ctx, ctx->stream, cp, D, out); }
+    int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim) {
+        const uint64_t np = len / 2; const unsigned grid = (unsigned)std::min<uint64_t>((np + 255) / 256, 1024);
+        DevBuf part; STARK_HIP(ctx, part.alloc(ctx, (size_t)grid * 2 * B * sizeof(fr_t)));
+        for (size_t b0 = 0; b0 < B; b0 += 65535)
+            hipLaunchKernelGGL(k_sc_coeffs_batch, dim3(grid, (unsigned)std::min<size_t>(65535, B - b0)), dim3(256), 0, ctx->stream, ptrs, layers, (uint64_t)len, (uint64_t)b0, part.fr());
+        hipLaunchKernelGGL(k_sc_coeffs_final_batch, dim3((unsigned)B), dim3(64), 0, ctx->stream, (const fr_t*)part.fr(), (uint64_t)grid, c01, claim);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t fold(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, const fr_t* r, fr_t* next) {
+        const uint64_t np = len / 2;
+        for (size_t b0 = 0; b0 < B; b0 += 65535)
+            hipLaunchKernelGGL(k_sc_fold_batch, dim3((unsigned)((np + 255) / 256), (unsigned)std::min<size_t>(65535, B - b0)), dim3(256), 0, ctx->stream, ptrs, layers, (uint64_t)len, (uint64_t)b0, r, next);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t transcript(const TrBatchStream& T) {
+        if (!T.n_active) return STARK_OK;
+        if (poseidon_form(ctx, tp, PoseidonOp::DeviceTranscript, 1) == PoseidonForm::FiveWave)
+            for (uint32_t sg = 0; sg < (uint32_t)T.nseg; ++sg)
+                hipLaunchKernelGGL(k_tr_batch_chain, dim3((unsigned)T.n_active), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, row_consts_of(ctx), T, sg);
+        else
+            hipLaunchKernelGGL(k_tr_batch, dim3((unsigned)T.n_active), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t gather(const fr_t* const* addr, size_t n, fr_t* out) {
+        hipLaunchKernelGGL(k_sc_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, addr, (uint64_t)n, out);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+};
+// prove_plain (mf = 0, :1045-1076) / prove_mf (mf = 1, :1130-1172) of `B` device-resident witnesses of 2^k elements: out[b] = the proof of
+// witness b alone.  The single entry points are this with B = 1.
+static int32_t prove_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t B, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, size_t qpr, stark_proof** out) {
+    for (size_t b = 0; b < B; ++b) out[b] = nullptr;
+    if (k > 40) return ctx->fail(STARK_ERR_INVALID_ARG, "k too large");
+    if (!B) return STARK_OK;
+    stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
+    std::vector<const fr_t*> w(B); for (size_t b = 0; b < B; ++b) w[b] = as_fr(witnesses[b]);
+    std::vector<std::vector<uint8_t>> proofs;
+    {
+        ScDevExec X(ctx, cp, tp);
+        ScBatch<ScDevExec> S(X, B, w.data(), k, tree_labels);
+        const int32_t rc = mf ? S.prove_mf(qpr, proofs) : S.prove_plain(proofs);
+        if (rc) return rc;
+    }
+    for (size_t b = 0; b < B; ++b) { out[b] = new stark_proof(); out[b]->bytes.swap(proofs[b]); out[b]->size_estimate = out[b]->bytes.size(); }
+    return STARK_OK;
 }
 
 // verifier hashing with MerkleCommitment's parameters (a t = 17 set that is NOT poseidon_params_for_arity(16))
@@ -482,26 +486,45 @@ int32_t stark_mle_evaluate(stark_ctx_t* ctx, const uint64_t* table, size_t k, co
 int32_t stark_sumcheck_prove_plain_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out) {
     if (!ctx || !witness || !out) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return prove_plain_impl(ctx, as_fr(witness), k, tree_label, out);
+    return prove_sumcheck_batch_impl(ctx, 0, 1, &witness, k, &tree_label, 0, out);
 }
 int32_t stark_sumcheck_prove_mf_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, size_t queries_per_round, stark_proof_t** out) {
     if (!ctx || !witness || !out) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return prove_mf_impl(ctx, as_fr(witness), k, tree_label, queries_per_round, out);
+    return prove_sumcheck_batch_impl(ctx, 1, 1, &witness, k, &tree_label, queries_per_round, out);
 }
 int32_t stark_sumcheck_prove_plain(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out) {
     if (!ctx || !witness || !out || k > 40) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     const size_t n = (size_t)1 << k; DevBuf d; STARK_HIP(ctx, d.alloc(ctx, n * sizeof(fr_t)));
     STARK_HIP(ctx, hipMemcpyAsync(d.p, witness, n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    return prove_plain_impl(ctx, d.fr(), k, tree_label, out);
+    const uint64_t* w = (const uint64_t*)d.p;
+    return prove_sumcheck_batch_impl(ctx, 0, 1, &w, k, &tree_label, 0, out);
 }
 int32_t stark_sumcheck_prove_mf(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, size_t queries_per_round, stark_proof_t** out) {
     if (!ctx || !witness || !out || k > 40) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     const size_t n = (size_t)1 << k; DevBuf d; STARK_HIP(ctx, d.alloc(ctx, n * sizeof(fr_t)));
     STARK_HIP(ctx, hipMemcpyAsync(d.p, witness, n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    return prove_mf_impl(ctx, d.fr(), k, tree_label, queries_per_round, out);
+    const uint64_t* w = (const uint64_t*)d.p;
+    return prove_sumcheck_batch_impl(ctx, 1, 1, &w, k, &tree_label, queries_per_round, out);
+}
+int32_t stark_sumcheck_prove_plain_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, stark_proof_t** out) {
+    if (!batch) return STARK_OK;
+    if (out) for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (!ctx || !out || !witnesses || !tree_labels || k > 40) return STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) if (!witnesses[b]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    return prove_sumcheck_batch_impl(ctx, 0, batch, witnesses, k, tree_labels, 0, out);
+}
+int32_t stark_sumcheck_prove_mf_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, size_t queries_per_round,
+                                          stark_proof_t** out) {
+    if (!batch) return STARK_OK;
+    if (out) for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (!ctx || !out || !witnesses || !tree_labels || k > 40) return STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) if (!witnesses[b]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    return prove_sumcheck_batch_impl(ctx, 1, batch, witnesses, k, tree_labels, queries_per_round, out);
 }
 int32_t stark_sumcheck_verify_plain(stark_ctx_t* ctx, size_t k, uint64_t tree_label, const uint8_t* proof, size_t len, int32_t* accepted) {
     if (!ctx || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
@@ -515,3 +538,4 @@ int32_t stark_sumcheck_verify_mf(stark_ctx_t* ctx, size_t k, uint64_t tree_label
 }
 
 }  // extern "C"
+#endif  // __HIPCC__
