@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <type_traits>
 #include "ctx.hpp"
 #include "poseidon_dev.hpp"
 #include "poseidon_pair.hpp"
@@ -41,11 +42,13 @@ static PoseidonForm poseidon_form(const stark_ctx* ctx, const stark_params* p, P
     const bool chain = !lane_only && !one_wave && d.t == 17 && d.rf == 8 && d.rp == 64 && d.chain_a;
     switch (op) {
     case PoseidonOp::MerkleLevel:
+        if (ctx->side_commit && !lane_only && (d.t == 9 || d.t == 17)) return PoseidonForm::WavePair;
         if (chain && n <= kChainMaxNodes) return PoseidonForm::FiveWave;
         if (!lane_only && (d.t == 9 || d.t == 17)) return n <= kCoopMaxNodes ? PoseidonForm::OneWave : PoseidonForm::WavePair;
         if (!lane_only && (d.t == 33 || d.t == 65 || d.t == 129) && n <= 0x7fffffffu) return PoseidonForm::Wide;     // one block per node
         return PoseidonForm::Lane;
     case PoseidonOp::LeafLayer:
+        if (ctx->side_commit && !lane_only) return PoseidonForm::WavePair;
         if (chain && n <= kChainMaxLeaves) return PoseidonForm::FiveWave;
         if (!lane_only && !one_wave && n <= kCoopMaxLeaves) return PoseidonForm::OneWave;
         return lane_only ? PoseidonForm::Lane : PoseidonForm::WavePair;
@@ -291,6 +294,7 @@ int32_t stark_ctx_create(int32_t device, void* stream, stark_ctx_t** out) {
     (void)hipFuncSetAttribute((const void*)k_hash_stream, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_leaf_pair2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_hash_ds2<17, DsStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_node16_pair, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_hash_ds2<9, DsStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_hash_ds2<17, DsGatherStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_hash_ds2<9, DsGatherStream>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
@@ -362,6 +366,7 @@ int32_t ctx_aux(stark_ctx* ctx, size_t k, stark_ctx** out) {
     stark_ctx* a = ctx->aux[k];
     a->opt_ntt_direct_max_log = ctx->opt_ntt_direct_max_log; a->opt_ntt_merged_coset = ctx->opt_ntt_merged_coset; a->opt_ntt_log_tile = ctx->opt_ntt_log_tile; a->opt_ntt_log_tile_forced = ctx->opt_ntt_log_tile_forced;
     a->opt_ntt_min_waves = ctx->opt_ntt_min_waves; a->opt_poseidon_lane_only = ctx->opt_poseidon_lane_only; a->opt_sponge_one_wave = ctx->opt_sponge_one_wave;
+    a->opt_merkle_node16_pair = ctx->opt_merkle_node16_pair; a->opt_fri_side_pair = ctx->opt_fri_side_pair;
     *out = a; return STARK_OK;
 }
 }
@@ -377,7 +382,9 @@ int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value) {
     else if (k == "poseidon_lane_only") ctx->opt_poseidon_lane_only = value != 0;
     else if (k == "sponge_one_wave") ctx->opt_sponge_one_wave = value != 0;
     else if (k == "sponge_debug") ctx->opt_sponge_debug = (int)value;
-    else return ctx->fail(STARK_ERR_INVALID_ARG, "unknown option '" + k + "' (ntt_direct_max_log, ntt_merged_coset, ntt_log_tile, ntt_min_waves, poseidon_lane_only, sponge_one_wave)");
+    else if (k == "merkle_node16_pair") ctx->opt_merkle_node16_pair = value != 0;
+    else if (k == "fri_side_pair") ctx->opt_fri_side_pair = value != 0;
+    else return ctx->fail(STARK_ERR_INVALID_ARG, "unknown option '" + k + "' (ntt_direct_max_log, ntt_merged_coset, ntt_log_tile, ntt_min_waves, poseidon_lane_only, sponge_one_wave, merkle_node16_pair, fri_side_pair)");
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     stark::ntt_plans_free(ctx);                  // plans (and their direct tables) are rebuilt lazily under the new options
     return STARK_OK;
@@ -514,6 +521,13 @@ static int32_t launch_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, co
         else hipLaunchKernelGGL((k_hash_ds_coop<9, DS>), dim3(nodes), dim3(64), coop_lds_bytes(9), st, p->dev, D, out);
         break;
     case PoseidonForm::WavePair:
+        if constexpr (std::is_same<DS, DsStream>::value) {
+            // a node level whose every node has 16 children (no ragged last node, contiguous positions): the fixed two-permutation kernel
+            if (t == 17 && ctx->opt_merkle_node16_pair && D.mode == 0 && D.arity == 16 && !D.pos_list && D.n_in == 16 * D.n_out) {
+                hipLaunchKernelGGL(k_node16_pair, dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D.arity_f, D.level_f, D.label_f, D.pos0, D.in0, D.n_out, out);
+                break;
+            }
+        }
         if (t == 17) hipLaunchKernelGGL((k_hash_ds2<17, DS>), dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D, out);
         else hipLaunchKernelGGL((k_hash_ds2<9, DS>), dim3(pairs), dim3(128), pair_lds_bytes(9), st, p->dev, D, out);
         break;

@@ -153,8 +153,13 @@ static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, con
     auto commit_layer = [&](size_t l, hipStream_t st) {
         return commit_layer_on(ctx, st, mps[l], S->arity[l], l, S->f[l], l < L ? S->f[l + 1] : nullptr, S->n[l], l < L ? schedule[l] : 1, 0, 0, &S->trees[l]);
     };
+    // Underneath a layer-0 leaf launch of 32 or more chip-fills (k_leaf_pair2: 4 workgroups of 64 leaves per CU) the side stream has time to spare,
+    // but every wave slot it holds is one the leaf launch cannot use: its levels and leaf layers then take the wave-pair form at every size (64
+    // sponges per two waves) instead of the latency forms (one wave, or five waves, per sponge) — option "fri_side_pair", poseidon_form.
+    ctx->side_commit = ctx->opt_fri_side_pair && S->n[0] >= (size_t)ctx->num_cus * 4 * 64 * 32;
     int32_t crc = STARK_OK;
     for (size_t l = L; l >= 1 && crc == STARK_OK; --l) crc = commit_layer(l, side);
+    ctx->side_commit = false;
     if (crc == STARK_OK) crc = commit_layer(0, main_stream);
     // join: the main stream continues only after the side stream's commitments
     if (hipEventRecord(ctx->ev_fork, side) != hipSuccess || hipStreamWaitEvent(main_stream, ctx->ev_fork, 0) != hipSuccess) { (void)hipStreamSynchronize(side); return bail(ctx->fail(STARK_ERR_HIP, "join")); }

@@ -85,6 +85,10 @@ struct stark_ctx {
     int opt_sponge_debug = 0;            // timing experiments on the five-wave sponge (bit 0: A does not wait, 1: B idle, 2: C idle, 3: no full rounds, 4: no partial rounds); digests are WRONG when set
     bool opt_sponge_one_wave = false;    // long serial sponges on ONE wave (poseidon_coop.hpp, round 2) instead of three (poseidon_chain.hpp) (diagnostic / comparison)
     bool opt_poseidon_lane_only = false; // one-lane-per-sponge kernels instead of the wave-pair / one-wave forms (diagnostic)
+    bool opt_merkle_node16_pair = true;  // t = 17 Merkle levels of > 4096 nodes with exactly 16 children each: the fixed two-permutation kernel k_node16_pair; 0 = the generic k_hash_ds2 (comparison)
+    bool opt_fri_side_pair = true;       // fri_build: the small layers' commitments on the side stream in the wave-pair form at every size (see side_commit); 0 = the latency forms (comparison)
+    bool side_commit = false;            // set while fri_build enqueues work that runs underneath the 2^n-leaf launch: Merkle levels and leaf layers of t = 9, 17 take the
+                                         // wave-pair form (64 sponges per two waves) instead of one wave or five waves per sponge, which would hold many wave slots at lone-wave speed
 
     int32_t fail(int32_t code, const std::string& msg) { err = msg; return code; }
 };

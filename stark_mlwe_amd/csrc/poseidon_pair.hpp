@@ -349,5 +349,42 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
     if (live && !s.isY) stg(out + k0, res);
 }
 
+// K4, arity 16 (pair form): one Merkle level of t = 17 whose every node has exactly 16 children, node k = in[16 k .. 16 k + 16) at DS position pos0 + k.
+// The node's stream is [arity, level, pos0 + k, label] || 16 children || 1: exactly two permutations, both fixed at compile time — perm 1 over
+// elements 0..15 = (DS words, children 0..11) with capacity 0, perm 2 after absorbing children 12..15 and the closing 1 into elements 0..4, squeezed.
+// Nothing of k_hash_ds2's generic machinery (element-by-element absorbs through DS::elem, dead permutations for ragged nodes, a runtime squeeze flag)
+// is live across a permutation.  Measured (tools/node_rate.py, 2^19 nodes): 17.4 ms against 17.7 for k_hash_ds2<17>, 60 M perm/s against the leaf
+// kernel's 69: the rest of the gap is work, not spills — both permutations run round 0 in full (one more MFMA product than k_leaf_pair2's
+// closed-form round 0, about 1/8 of a permutation's full-round time).  Two inlined permutations measured faster than one in a loop (17.6 ms).
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_node16_pair(PoseidonDev P, fr_t arity_f, fr_t level_f, fr_t label_f, uint64_t pos0,
+                                                    const fr_t* __restrict__ in, size_t n_out, fr_t* __restrict__ out) {
+    extern __shared__ uint4 lds[];
+    PairState s = pair_setup(lds);
+    const size_t k0 = (size_t)blockIdx.x * 64 + s.lane; const bool live = k0 < n_out; const size_t k = live ? k0 : n_out - 1;   // tail lanes recompute the last node
+    const fr_t* c = in + k * 16;
+    // perm 1: each wave fills the elements it owns in the full rounds (X 0..NX-1, Y NX..16), the children straight from global memory
+    static_assert(PairCfg<17>::NX == 8, "X fills elements 0..7");
+    if (!s.isY) {
+        s.sto(0, arity_f); s.sto(1, level_f); s.sto(2, fr_from_u64<PF>(pos0 + k)); s.sto(3, label_f);
+#pragma unroll
+        for (int j = 4; j < 8; ++j) s.sto(j, ldg(c + (j - 4)));
+    } else {
+#pragma unroll
+        for (int j = 8; j < 16; ++j) s.sto(j, ldg(c + (j - 4)));
+        s.sto(16, fr_zero<PF>());
+    }
+    __syncthreads();
+    pair_permute<17>(s, P, false);                 // ends with a barrier: the state is consistent
+    // perm 2: children 12..15 and the closing 1 into elements 0..4 (X's)
+    if (!s.isY) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s.sto(j, fr_add<PF>(s.ld(j), ldg(c + 12 + j)));
+        s.sto(4, fr_add<PF>(s.ld(4), fr_one<PF>()));
+    }
+    __syncthreads();
+    const fr_t res = pair_permute<17>(s, P, true);
+    if (live && !s.isY) stg(out + k0, res);
+}
+
 }  // namespace stark
 #endif

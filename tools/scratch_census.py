@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/scratch_census.py — where the spilled registers of the two Poseidon throughput kernels are touched.
+"""tools/scratch_census.py — where the spilled registers of the Poseidon throughput kernels are touched.
 Compiles capi_core.hip to gfx950 assembly (same flags as the library) and counts scratch_load / scratch_store instructions per loop
 nesting depth (LLVM's "Loop Header: Depth=" / "in Loop ... Depth=" / "Parent Loop ... Depth=" block comments) next to the kernel's total
 instruction count.  A spill that sits outside the round loops is executed a handful of times per permutation."""
@@ -11,7 +11,7 @@ with tempfile.TemporaryDirectory() as td:
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-w", "-o", out, src])
     text = open(out).read()
 res = []
-for sym, name in [("_ZN5stark12k_leaf_pair2", "k_leaf_pair2"), ("_ZN5stark10k_hash_ds2ILi17EE", "k_hash_ds2<17>")]:
+for sym, name in [("_ZN5stark12k_leaf_pair2", "k_leaf_pair2"), ("_ZN5stark10k_hash_ds2ILi17ENS_8DsStreamE", "k_hash_ds2<17, DsStream>"), ("_ZN5stark13k_node16_pair", "k_node16_pair")]:
     m = re.search(r"^%s\w*:[^\n]*\n(.*?)s_endpgm" % re.escape(sym), text, re.S | re.M)
     if not m:
         continue
