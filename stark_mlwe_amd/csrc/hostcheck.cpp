@@ -34,17 +34,18 @@ static void bind(HcParams* P) {
 
 extern "C" {
 
-// field: 0 Pallas, 1 BLS12-381.  op: 0 add, 1 sub, 2 mul, 3 inv, 4 from_u64(a[0]), 5 to_canonical, 6 root_of_unity(a[0]), 7 pow_u64(a, b[0])
+// field: 0 Pallas, 1 BLS12-381.  op: 0 add, 1 sub, 2 mul, 3 inv, 4 from_u64(a[0]), 5 to_canonical, 6 root_of_unity(a[0]), 7 pow_u64(a, b[0]),
+// 8 the kernels' S-box fr_pow5_r29 (fr29.hpp: x^5 / 2^20)
 int hc_fr_op(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out) {
     fr_t x = ld4(a), y = b ? ld4(b) : x, z;
     if (field == 0) {
         switch (op) { case 0: z = fr_add<PallasFr>(x, y); break; case 1: z = fr_sub<PallasFr>(x, y); break; case 2: z = fr_mul<PallasFr>(x, y); break; case 3: z = fr_inv<PallasFr>(x); break;
             case 4: z = fr_from_u64<PallasFr>(a[0]); break; case 5: z = fr_to_canonical<PallasFr>(x); break; case 6: z = fr_root_of_unity<PallasFr>((unsigned)a[0]); break;
-            case 7: z = fr_pow_u64<PallasFr>(x, b[0]); break; default: return -1; }
+            case 7: z = fr_pow_u64<PallasFr>(x, b[0]); break; case 8: z = fr_pow5_r29<PallasFr>(x); break; default: return -1; }
     } else {
         switch (op) { case 0: z = fr_add<Bls12381Fr>(x, y); break; case 1: z = fr_sub<Bls12381Fr>(x, y); break; case 2: z = fr_mul<Bls12381Fr>(x, y); break; case 3: z = fr_inv<Bls12381Fr>(x); break;
             case 4: z = fr_from_u64<Bls12381Fr>(a[0]); break; case 5: z = fr_to_canonical<Bls12381Fr>(x); break; case 6: z = fr_root_of_unity<Bls12381Fr>((unsigned)a[0]); break;
-            case 7: z = fr_pow_u64<Bls12381Fr>(x, b[0]); break; default: return -1; }
+            case 7: z = fr_pow_u64<Bls12381Fr>(x, b[0]); break; case 8: z = fr_pow5_r29<Bls12381Fr>(x); break; default: return -1; }
     }
     st4(out, z); return 0;
 }

@@ -90,9 +90,11 @@ def test_tr_hash_fields_tagged(gpu_ctx, oracle):
 
 def test_throughput_kernels_on_extreme_field_values(gpu_ctx, oracle):
     """The wave-pair kernels' full rounds multiply on the int8 matrix cores over SIGNED radix-256 digits (poseidon_pair.hpp): inputs whose
-    bytes sit at the recoding's corners — 0, 1, r - 1, r - 2, all-0x7f / all-0x80 / all-0xff byte patterns (reduced below r), single high
+    LOGICAL values are extreme — 0, 1, r - 1, r - 2, all-0x7f / all-0x80 / all-0xff byte patterns (reduced below r), single high
     bits — through the leaf hash (k_leaf_pair2) and through an arity-16 Merkle tree of 2^18 leaves, whose first level (16 384 nodes, above
-    the one-wave threshold) runs k_hash_ds2<17>, against the oracle."""
+    the one-wave threshold) runs the wave-pair node kernels, against the oracle.  These byte patterns do not reach the recoding: from_int
+    multiplies by R and the recoding reads the stored bytes of the S-box OUTPUTS.  test_gpu_corner_values.py crafts inputs whose round-0 S-box
+    outputs are the chosen stored bytes."""
     import pyref
     p = pyref.P_PALLAS
     pats = [0, 1, 2, p - 1, p - 2, p - 3, (p - 1) // 2, (p + 1) // 2]

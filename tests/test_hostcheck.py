@@ -126,8 +126,11 @@ def test_hash_stream_body(oracle, hostcheck):
 @pytest.mark.parametrize("n", [1, 2, 6, 7, 12, 13, 17, 24, 25, 27, 48, 59, 60, 61, 120, 129])
 def test_wide_dot_worst_case_and_random(oracle, hostcheck, n):
     """Sums of products with ONE Montgomery reduction per chunk (radix-2^29 columns, constants in the 2^261 domain:
-    carry pass every 6 terms, chunks of 60 — csrc/fr29.hpp): worst case (all operands r-1) and random, across every
-    chunk boundary; the radix-2^32 accumulator of the cooperative kernels must agree where it applies (<= 24 terms)."""
+    carry pass every 6 terms, chunks of 60 — csrc/fr29.hpp): all operands the logical r - 1 and random, across every
+    chunk boundary; the radix-2^32 accumulator of the cooperative kernels must agree where it applies (<= 24 terms).
+    Logical r - 1 is not the worst case of the column sums: operands are held in Montgomery form, R = -4t (mod r) with t = r - 2^254 ~ 2^125,
+    so it is STORED as 4t ~ 2^127 and the upper four 29-bit limbs of every operand are zero.  The stored extremes (stored r - 1, 2^254 - 1,
+    2^254, alternating maximal limbs) are in test_corner_values_host.py::test_wide_dots_on_stored_extremes."""
     p = pyref.P_PALLAS
     top = oracle.from_int(p - 1)
     a = np.tile(top, (n, 1)); b = np.tile(top, (n, 1))
@@ -144,7 +147,10 @@ def test_wide_dot_worst_case_and_random(oracle, hostcheck, n):
 def test_lazy_nine_limb_ntt_tile_vs_oracle(oracle, hostcheck, field, p):
     """The NTT kernels' arithmetic (csrc/ntt_dev.hpp: nine 29-bit limbs, lazily reduced decimation-in-time butterflies, tables carrying the
     factor 32, carry pass before stages 4/7/10) instantiated on the host: equal to the oracle's radix-2 NTT for every sub-NTT size a pass can
-    take, forward and inverse, on random values and on the worst case (every input r - 1), with the operand bounds the column sums rely on."""
+    take, forward and inverse, on random values, on every input the logical r - 1 ("max") and on logical r - 1 / 0 alternating, with the operand
+    bounds the column sums rely on.  The logical r - 1 is stored as 4t ~ 2^127 (Pallas: upper limbs zero), so "max" is a benign operand for that
+    field; vectors of stored r - 1, stored 2^254 - 1 and alternating maximal limbs are in
+    test_corner_values_host.py::test_lazy_nine_limb_ntt_on_stored_extremes, under the same bounds."""
     rng = random.Random(4242 + field)
     for log_b in list(range(1, 11)) + [12]:
         n = 1 << log_b
@@ -199,8 +205,10 @@ def test_matrix_core_full_round_tables_and_fold(oracle, hostcheck):
     """The t = 17 wave-pair kernels multiply the full rounds' dense matrices on the int8 matrix cores (poseidon_pair.hpp).  Everything of that path
     that is not the MFMA instruction itself is host-checkable: the signed radix-256 recoding, the Toeplitz FRAGMENT TABLES (host_util.hpp mfma_frags,
     emulated as D[row][col] = sum_k A[row][k] B[k][col] over the tables' lane layout), the accumulator-row order the lanes see, the fold into 29-bit
-    columns, the signed carry pass and the Montgomery step.  Equal to the L*U rows of the VALU path on random S-box outputs and on the corners of the
-    recoding (0, r - 1, 0x7f / 0x80 / 0xff byte patterns), for M and for B_1 * M, with the Merkle and the transcript parameter sets."""
+    columns, the signed carry pass and the Montgomery step.  Equal to the L*U rows of the VALU path on random S-box outputs and on logical corner
+    values (0, r - 1, 0x7f / 0x80 / 0xff byte patterns of the LOGICAL value: from_int multiplies by R, so the stored bytes the recoding reads are
+    ordinary words), for M and for B_1 * M, with the Merkle and the transcript parameter sets.  The corners of the recoding itself — stored 0x80 /
+    0x7f carry chains, all-0xff, the band above 2^254 — are in test_corner_values_host.py::test_matrix_core_emulation_on_stored_corners."""
     p = pyref.P_PALLAS
     rng = random.Random(1717)
     corner = [0, 1, p - 1, p - 2, (p - 1) // 2] + [int.from_bytes(bytes([b]) * 32, "little") % p for b in (0x7f, 0x80, 0x81, 0xff)]
