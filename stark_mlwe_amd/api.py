@@ -713,6 +713,8 @@ class Context:
     def lde(self, evals, log_blowup, field=PALLAS_FR, coset=None):
         v = _arr(evals)
         log_n = int(v.shape[0]).bit_length() - 1
+        if log_n < 0 or (1 << log_n) != v.shape[0]:
+            raise StarkError(-1, "radix-2 domain size must be a power of two")
         out = np.zeros((v.shape[0] << log_blowup, 4), np.uint64)
         self._chk(self.lib.stark_lde(self.h, field, _ptr(v), log_n, log_blowup, _ptr(None if coset is None else _arr(coset)), _ptr(out)))
         return out
