@@ -259,6 +259,22 @@ int32_t stark_sumcheck_prove_plain_batch_dev(stark_ctx_t* ctx, size_t batch, con
 /* prove_mf (:1130-1172), same contract, one queries_per_round for the batch; one host synchronisation per round (the query indices). */
 int32_t stark_sumcheck_prove_mf_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k,
                                           const uint64_t* tree_labels, size_t queries_per_round, stark_proof_t** out);
+/* verify_plain (:1080-1128) over `batch` proofs at once; accepted[i] == what stark_sumcheck_verify_plain answers for proofs[i] alone, for
+ * every input (honest, tampered, truncated, extended, empty, a proof of another k).  Like the single verifier this reads neither k nor the
+ * labels: both are carried for signature parity, tree_labels may be NULL, and proofs of different round counts may share a batch.  The
+ * host only parses the structure of each proof; its field elements are decoded on the device (range check, Montgomery form), the
+ * transcripts of all proofs advance side by side and the round relations are checked one lane per (proof, round): one upload, a number of
+ * device steps that does not depend on the batch, one download of the decisions, one synchronisation.  A proof that does not decode or
+ * fails a check is a rejection, never an error.  batch == 0 returns STARK_OK.  STARK_ERR_INVALID_ARG: a null ctx or accepted (batch > 0),
+ * null proofs or lens, a null proofs[i] with lens[i] != 0.  On any error every accepted[i] is 0.  Device memory is bounded: a large batch
+ * runs as several plans (option "sumcheck_verify_batch_max_slots", default 2^25 field elements). */
+int32_t stark_sumcheck_verify_plain_batch(stark_ctx_t* ctx, size_t batch, const uint8_t* const* proofs, const size_t* lens, size_t k, const uint64_t* tree_labels, int32_t* accepted);
+/* verify_mf (:1176-1240), same contract: accepted[i] == stark_sumcheck_verify_mf on proofs[i] alone under tree_labels[i] (a null
+ * tree_labels is STARK_ERR_INVALID_ARG); k and queries_per_round are carried but unread, so proofs of different round and query counts
+ * may share a batch.  Every round challenge is one transcript of the batch, every Merkle opening of every round of every proof runs in
+ * one launch per tree depth (MerkleCommitment's parameters), and the fold relations and root comparisons are checked one lane each. */
+int32_t stark_sumcheck_verify_mf_batch(stark_ctx_t* ctx, size_t batch, const uint8_t* const* proofs, const size_t* lens, size_t k, const uint64_t* tree_labels, size_t queries_per_round,
+                                       int32_t* accepted);
 
 /* ---- Transcript (transcript/src/lib.rs:48-117) -------------------------------------------------------
  * Transcript::new(label, transcript::default_params()) / absorb_bytes / absorb_field(s) / challenge / challenges as an object:

@@ -437,6 +437,24 @@ pub mod channel {
         ctx.chk(unsafe { stark_sumcheck_verify_mf(ctx.raw(), k, tree_label, queries_per_round, proof.as_ptr(), proof.len(), &mut ok) });
         ok == 1
     }
+    /// `verify_plain` of many proofs in one device pass; element i == `verify_plain(ctx, k, _, proofs[i])`.  Like the single verifier it
+    /// reads neither `k` nor a tree label.
+    pub fn verify_plain_batch(ctx: &Ctx, k: usize, proofs: &[&[u8]]) -> Vec<bool> {
+        let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+        let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let mut ok = vec![0i32; proofs.len()];
+        ctx.chk(unsafe { stark_sumcheck_verify_plain_batch(ctx.raw(), proofs.len(), ptrs.as_ptr(), lens.as_ptr(), k, ptr::null(), ok.as_mut_ptr()) });
+        ok.into_iter().map(|a| a == 1).collect()
+    }
+    /// `verify_mf` of many proofs in one device pass; element i == `verify_mf(ctx, k, tree_labels[i], queries_per_round, proofs[i])`.
+    pub fn verify_mf_batch(ctx: &Ctx, k: usize, tree_labels: &[u64], queries_per_round: usize, proofs: &[&[u8]]) -> Vec<bool> {
+        assert!(tree_labels.len() == proofs.len(), "one tree label per proof");
+        let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+        let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let mut ok = vec![0i32; proofs.len()];
+        ctx.chk(unsafe { stark_sumcheck_verify_mf_batch(ctx.raw(), proofs.len(), ptrs.as_ptr(), lens.as_ptr(), k, tree_labels.as_ptr(), queries_per_round, ok.as_mut_ptr()) });
+        ok.into_iter().map(|a| a == 1).collect()
+    }
 }
 
 pub mod comm {

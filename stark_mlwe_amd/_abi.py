@@ -105,6 +105,8 @@ SIGNATURES = {
     "stark_sumcheck_verify_mf": (i32, [vp, sz, u64, sz, vp, sz, C.POINTER(i32)]),
     "stark_sumcheck_prove_plain_batch_dev": (i32, [vp, sz, vp, sz, vp, vp]),
     "stark_sumcheck_prove_mf_batch_dev": (i32, [vp, sz, vp, sz, vp, sz, vp]),
+    "stark_sumcheck_verify_plain_batch": (i32, [vp, sz, vp, vp, sz, vp, vp]),
+    "stark_sumcheck_verify_mf_batch": (i32, [vp, sz, vp, vp, sz, vp, sz, vp]),
     "stark_ali_merge_shard_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, u64, sz, vp, vp]),
     "stark_ali_cstar_from_partials": (i32, [vp, vp, sz, sz, vp]),
     "stark_ali_challenges": (i32, [vp, vp, sz, vp]),

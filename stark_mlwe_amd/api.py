@@ -591,6 +591,32 @@ class Context:
         self._chk(self.lib.stark_sumcheck_verify_mf(self.h, k, tree_label, queries_per_round, buf, len(proof), C.byref(ok)))
         return bool(ok.value)
 
+    def verify_plain_batch(self, k, tree_labels, proofs) -> list:
+        """verify_plain on each of `proofs` in one device pass (stark_sumcheck_verify_plain_batch); one bool per proof, each equal to
+        verify_plain of that proof alone.  Neither k nor the labels are read (tree_labels may be None)."""
+        return self._sumcheck_verify_batch(0, k, tree_labels, 0, proofs)
+
+    def verify_mf_batch(self, k, tree_labels, queries_per_round, proofs) -> list:
+        """verify_mf on each of `proofs` under tree_labels[i] in one device pass (stark_sumcheck_verify_mf_batch); one bool per proof."""
+        return self._sumcheck_verify_batch(1, k, tree_labels, queries_per_round, proofs)
+
+    def _sumcheck_verify_batch(self, mf, k, tree_labels, q, proofs):
+        n = len(proofs)
+        if (mf or tree_labels is not None) and len(tree_labels) != n:
+            raise StarkError(-1, "one tree label per proof")
+        if n == 0:
+            return []
+        bufs = [(C.c_uint8 * max(1, len(p))).from_buffer_copy(bytes(p) or b"\0") for p in proofs]
+        ptrs = (C.c_void_p * n)(*[C.cast(b, C.c_void_p) for b in bufs])
+        lens = (C.c_size_t * n)(*[len(p) for p in proofs])
+        lab = None if tree_labels is None else np.ascontiguousarray(tree_labels, dtype=np.uint64)
+        acc = (C.c_int32 * n)()
+        if mf:
+            self._chk(self.lib.stark_sumcheck_verify_mf_batch(self.h, n, ptrs, lens, k, _ptr(lab), q, acc))
+        else:
+            self._chk(self.lib.stark_sumcheck_verify_plain_batch(self.h, n, ptrs, lens, k, None if lab is None else _ptr(lab), acc))
+        return [bool(acc[i]) for i in range(n)]
+
     def prove_plain_batch_dev(self, k, tree_labels, witness_ptrs) -> list:
         """prove_plain of each witness (DEVICE pointers, ints, of 2^k elements; tree_labels[i] its VK tree label) in one pass
         (stark_sumcheck_prove_plain_batch_dev) -> list of proof bytes, each equal to prove_plain of that witness alone."""

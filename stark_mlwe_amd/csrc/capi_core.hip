@@ -57,8 +57,8 @@ static PoseidonForm poseidon_form(const stark_ctx* ctx, const stark_params* p, P
         return !lane_only && n <= kCoopMaxSponges ? PoseidonForm::OneWave : PoseidonForm::Lane;
     case PoseidonOp::ColumnSponges:
         return d.chain_a && !one_wave ? PoseidonForm::FiveWave : PoseidonForm::OneWave;
-    case PoseidonOp::DeviceTranscript:
-        return chain ? PoseidonForm::FiveWave : PoseidonForm::OneWave;
+    case PoseidonOp::DeviceTranscript:                                  // n instances advanced by one launch; up to two resident five-wave workgroups per CU, as for TrHash
+        return chain && n <= kChainMaxSponges ? PoseidonForm::FiveWave : PoseidonForm::OneWave;
     }
     return PoseidonForm::Lane;
 }
@@ -366,7 +366,7 @@ int32_t ctx_aux(stark_ctx* ctx, size_t k, stark_ctx** out) {
     stark_ctx* a = ctx->aux[k];
     a->opt_ntt_direct_max_log = ctx->opt_ntt_direct_max_log; a->opt_ntt_merged_coset = ctx->opt_ntt_merged_coset; a->opt_ntt_log_tile = ctx->opt_ntt_log_tile; a->opt_ntt_log_tile_forced = ctx->opt_ntt_log_tile_forced;
     a->opt_ntt_min_waves = ctx->opt_ntt_min_waves; a->opt_poseidon_lane_only = ctx->opt_poseidon_lane_only; a->opt_sponge_one_wave = ctx->opt_sponge_one_wave;
-    a->opt_merkle_node16_pair = ctx->opt_merkle_node16_pair; a->opt_fri_side_pair = ctx->opt_fri_side_pair;
+    a->opt_merkle_node16_pair = ctx->opt_merkle_node16_pair; a->opt_fri_side_pair = ctx->opt_fri_side_pair; a->opt_sumcheck_verify_batch_max_slots = ctx->opt_sumcheck_verify_batch_max_slots;
     *out = a; return STARK_OK;
 }
 }
@@ -384,7 +384,8 @@ int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value) {
     else if (k == "sponge_debug") ctx->opt_sponge_debug = (int)value;
     else if (k == "merkle_node16_pair") ctx->opt_merkle_node16_pair = value != 0;
     else if (k == "fri_side_pair") ctx->opt_fri_side_pair = value != 0;
-    else return ctx->fail(STARK_ERR_INVALID_ARG, "unknown option '" + k + "' (ntt_direct_max_log, ntt_merged_coset, ntt_log_tile, ntt_min_waves, poseidon_lane_only, sponge_one_wave, merkle_node16_pair, fri_side_pair)");
+    else if (k == "sumcheck_verify_batch_max_slots") { if (value < 1) return ctx->fail(STARK_ERR_INVALID_ARG, "sumcheck_verify_batch_max_slots: at least 1"); ctx->opt_sumcheck_verify_batch_max_slots = (size_t)value; }
+    else return ctx->fail(STARK_ERR_INVALID_ARG, "unknown option '" + k + "' (ntt_direct_max_log, ntt_merged_coset, ntt_log_tile, ntt_min_waves, poseidon_lane_only, sponge_one_wave, merkle_node16_pair, fri_side_pair, sumcheck_verify_batch_max_slots)");
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     stark::ntt_plans_free(ctx);                  // plans (and their direct tables) are rebuilt lazily under the new options
     return STARK_OK;

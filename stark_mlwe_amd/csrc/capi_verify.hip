@@ -68,23 +68,12 @@ struct GpuVerifyHasher : VerifyHasher {
     }
 };
 
-// Runs one plan: one upload, the leaf step and the DS groups in depth order (groups that share a depth after the first on the side stream),
-// the check kernel, one download of the decisions and one synchronisation.
-int32_t run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, int32_t* accepted) {
-    if (!V.batch) return STARK_OK;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_hdr = 0, o_off = al(o_hdr + V.hdr.size() * 8), o_idx = al(o_off + V.off.size() * 4), o_coff = al(o_idx + V.idx.size() * 4),
-                 o_chk = al(o_coff + V.chk_off.size() * 4), o_flag = al(o_chk + V.chk.size() * 4), o_pool = al(o_flag + V.batch * 4),
-                 o_acc = al(o_pool + V.pool.size() * sizeof(fr_t)), total = al(o_acc + V.batch * 4);
-    std::vector<uint8_t> h(o_pool + V.n_known * sizeof(fr_t));         // everything the device reads, in one upload (the computed digests are not sent)
-    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) memcpy(h.data() + o, src, bytes); };
-    put(o_hdr, V.hdr.data(), V.hdr.size() * 8); put(o_off, V.off.data(), V.off.size() * 4); put(o_idx, V.idx.data(), V.idx.size() * 4);
-    put(o_coff, V.chk_off.data(), V.chk_off.size() * 4); put(o_chk, V.chk.data(), V.chk.size() * 4); put(o_flag, V.flag.data(), V.batch * 4);
-    put(o_pool, V.pool.data(), V.n_known * sizeof(fr_t));
-    DevBuf d; STARK_HIP(ctx, d.alloc(ctx, total));
-    uint8_t* base = (uint8_t*)d.p; fr_t* pool = (fr_t*)(base + o_pool);
+}  // namespace
+// The leaf step and the DS groups of a plan whose arrays are on the device, in depth order on the context's stream (groups that share a
+// depth after the first on the side stream, joined before the next depth).  fixed != nullptr: every group hashes with that parameter set
+// (the sum-check openings: MerkleCommitment's) instead of ctx_merkle_params(G.t).  On an error both streams are drained.
+int32_t stark::verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, const uint64_t* hdr, const uint32_t* off, const uint32_t* idx, fr_t* pool, stark_params* fixed) {
     hipStream_t main_st = ctx->stream, side = nullptr;
-    STARK_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, main_st));
     bool forked = false;
     auto bail = [&](int32_t rc) { if (forked) (void)hipStreamSynchronize(side); (void)hipStreamSynchronize(main_st); return rc; };
     for (size_t g0 = 0, depth = 1; g0 < V.groups.size() || (depth == 1 && V.nl); ++depth) {
@@ -103,8 +92,8 @@ int32_t run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, int32_t* acce
             if (items[i] < 0) rc = leaf_pair_hash_on(ctx, st, pool + V.leaf_f0, pool + V.leaf_f0 + V.nl, V.nl, 1, pool + V.leaf_out0);
             else {
                 const VerifyBatchPlan::Group& G = V.groups[items[i]];
-                stark_params* mp = nullptr; rc = ctx_merkle_params(ctx, G.t, &mp);
-                const DsGatherStream D{(const uint64_t*)(base + o_hdr) + 4 * G.job0, (const uint32_t*)(base + o_off) + G.job0, (const uint32_t*)(base + o_idx), pool, G.n, G.max_children};
+                stark_params* mp = fixed; if (!mp) rc = ctx_merkle_params(ctx, G.t, &mp);
+                const DsGatherStream D{hdr + 4 * G.job0, off + G.job0, idx, pool, G.n, G.max_children};
                 if (!rc) rc = hash_ds_gather_on(ctx, st, mp, D, pool + G.out0);
             }
             if (rc) return bail(rc);
@@ -114,6 +103,27 @@ int32_t run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, int32_t* acce
         }
         g0 = g1;
     }
+    return STARK_OK;
+}
+namespace {
+// Runs one plan: one upload, the leaf step and the DS groups in depth order (verify_batch_groups_on), the check kernel, one download of
+// the decisions and one synchronisation.
+int32_t run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, int32_t* accepted) {
+    if (!V.batch) return STARK_OK;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_hdr = 0, o_off = al(o_hdr + V.hdr.size() * 8), o_idx = al(o_off + V.off.size() * 4), o_coff = al(o_idx + V.idx.size() * 4),
+                 o_chk = al(o_coff + V.chk_off.size() * 4), o_flag = al(o_chk + V.chk.size() * 4), o_pool = al(o_flag + V.batch * 4),
+                 o_acc = al(o_pool + V.pool.size() * sizeof(fr_t)), total = al(o_acc + V.batch * 4);
+    std::vector<uint8_t> h(o_pool + V.n_known * sizeof(fr_t));         // everything the device reads, in one upload (the computed digests are not sent)
+    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) memcpy(h.data() + o, src, bytes); };
+    put(o_hdr, V.hdr.data(), V.hdr.size() * 8); put(o_off, V.off.data(), V.off.size() * 4); put(o_idx, V.idx.data(), V.idx.size() * 4);
+    put(o_coff, V.chk_off.data(), V.chk_off.size() * 4); put(o_chk, V.chk.data(), V.chk.size() * 4); put(o_flag, V.flag.data(), V.batch * 4);
+    put(o_pool, V.pool.data(), V.n_known * sizeof(fr_t));
+    DevBuf d; STARK_HIP(ctx, d.alloc(ctx, total));
+    uint8_t* base = (uint8_t*)d.p; fr_t* pool = (fr_t*)(base + o_pool);
+    hipStream_t main_st = ctx->stream;
+    STARK_HIP(ctx, hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, main_st));
+    STARK_TRY(verify_batch_groups_on(ctx, V, (const uint64_t*)(base + o_hdr), (const uint32_t*)(base + o_off), (const uint32_t*)(base + o_idx), pool, nullptr));
     int32_t* acc_dev = (int32_t*)(base + o_acc);
     hipLaunchKernelGGL(k_verify_batch_check, dim3((unsigned)((V.batch + 255) / 256)), dim3(256), 0, main_st, pool, (const uint32_t*)(base + o_coff), (const uint32_t*)(base + o_chk),
                        (const int32_t*)(base + o_flag), V.batch, acc_dev);

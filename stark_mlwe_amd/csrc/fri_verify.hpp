@@ -99,8 +99,10 @@ inline bool ok_width_for(size_t arity) { return arity >= 1 && arity <= 128; }   
 //   sib(level, j) -> V                                  the j-th sibling of `level`
 //   hash_level(level, arity, parents, kids, out) -> rc  out[g] = hash_with_ds_dynamic([arity, level, parents[g], label], kids[g])
 // shaped = false is a rejection; otherwise `top` is the root the opening computes (the caller compares it with the claimed one).
-template <class V, class Sib, class HashLevel>
-inline int32_t ds_walk(size_t cfg_arity, const std::vector<size_t>& indices, const std::vector<V>& values, const MerkleProofHost& proof, Sib sib, HashLevel hash_level,
+// `proof` is a MerkleProofHost or any type with its members of which only the SIZES of `siblings` are read here (the slot form of the
+// sum-check batch planner, which never holds a sibling's value on the host).
+template <class V, class Proof, class Sib, class HashLevel>
+inline int32_t ds_walk(size_t cfg_arity, const std::vector<size_t>& indices, const std::vector<V>& values, const Proof& proof, Sib sib, HashLevel hash_level,
                        bool& shaped, V& top) {
     shaped = false;
     if (indices.empty() || indices.size() != values.size()) return 0;                                        // :595-597

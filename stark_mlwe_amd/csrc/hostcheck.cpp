@@ -443,3 +443,50 @@ size_t hc_sumcheck_prove_batch(void* tparams, void* cparams, int mf, size_t B, c
     return tot;
 }
 }  // extern "C"
+
+// ---- the batched sum-check verifiers (sumcheck_verify_batch.hpp): the plan run step by step as the device runs it -------------------
+static int sc_verify_plan(int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* labels, ScVerifyPlan& V) {
+    bool fits = false;
+    if (sc_verify_plan_some(mf, 0, batch, proofs, lens, labels, (size_t)-1, V, fits) != batch || !fits) return -1;
+    return 0;
+}
+extern "C" {
+// The decode body on the element at byte `off` of `blob` (len bytes): 1 and out4 = the stored form, 0 when the value is >= r.
+int hc_sc_decode_fr(const uint8_t* blob, size_t len, size_t off, uint64_t* out4) {
+    if (off + 32 > len) return -1;
+    std::vector<uint32_t> w((len + 3) / 4 + 2, 0u); memcpy(w.data(), blob, len);
+    fr_t x; const bool ok = sc_decode_fr(w.data(), (uint32_t)off, 0u, x); st4(out4, x); return ok ? 1 : 0;
+}
+// verify_plain (mf = 0; labels may be null) / verify_mf (mf = 1) of `batch` proofs through the batch plan: decode, the transcript streams,
+// the DS groups in depth order (cparams: MerkleCommitment's parameters), the checks.  accepted[i] = 1 / 0.
+int hc_sumcheck_verify_batch(void* tparams, void* cparams, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* labels, int32_t* accepted) {
+    ScVerifyPlan V; if (sc_verify_plan(mf, batch, proofs, lens, labels, V)) return -1;
+    HcParams *tp = (HcParams*)tparams, *cp = (HcParams*)cparams;
+    std::vector<fr_t> pool(std::max<size_t>(V.pool_slots, 1), host::h_zero());
+    for (size_t j = 0; j < V.n_dec; ++j) if (!sc_decode_fr(V.blob.data(), V.dec_off[j], V.dec_proof[j], pool[j])) V.flag[V.dec_proof[j] & ~kScClaim] = 0;
+    std::vector<fr_t> state(17 * std::max<size_t>(V.n_inst, 1)); std::vector<uint32_t> pos(std::max<size_t>(V.n_inst, 1), 0u);
+    for (const ScVerifyPlan::Stream& S : V.tr) {
+        TrBatchStream T; T.state = state.data(); T.pos = pos.data(); T.inst = nullptr; T.inst0 = S.inst0; T.n_active = S.n; T.nseg = S.nseg; T.el_off = V.tr_off.data() + S.seg0;
+        T.idx = V.tr_idx.data(); T.pool0 = pool.data(); T.pool1 = V.consts.data(); T.out = pool.data() + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = 1; T.finish_last = 1;
+        fr_t st[17]; for (size_t a = 0; a < S.n; ++a) { ArrayState s{st}; tr_batch_body(s, tp->dev, T, a); }
+    }
+    for (const VerifyBatchPlan::Group& G : V.ds.groups) {
+        std::vector<fr_t> st(cp->dev.t);
+        const DsGatherStream D{V.ds.hdr.data() + 4 * G.job0, V.ds.off.data() + G.job0, V.ds.idx.data(), pool.data(), G.n, G.max_children};
+        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; pool[G.out0 + k] = hash_ds_body(s, cp->dev, D, k); }
+    }
+    for (size_t j = 0; j < V.n_rec(); ++j) {
+        const uint32_t* r = V.rec.data() + 8 * j;
+        if (!(mf ? sc_check_mf(pool.data(), r) : sc_check_plain(pool.data(), r))) V.flag[mf ? r[1] : r[0]] = 0;
+    }
+    for (size_t b = 0; b < batch; ++b) accepted[b] = V.flag[b];
+    return 0;
+}
+// the device steps of the plan as (kind, count) rows in launch order (ScVerifyPlan::steps); returns their number (at most cap written)
+size_t hc_sumcheck_verify_batch_steps(int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* labels, int32_t* kind, size_t* count, size_t cap) {
+    ScVerifyPlan V; if (sc_verify_plan(mf, batch, proofs, lens, labels, V)) return 0;
+    const auto st = V.steps();
+    for (size_t i = 0; i < st.size() && i < cap; ++i) { kind[i] = st[i].first; count[i] = st[i].second; }
+    return st.size();
+}
+}  // extern "C"

@@ -27,6 +27,7 @@ constexpr const char *mf = "E2E/MF", *mf_round_chal = "SUMCHECK-MF/ROUND-CHAL", 
 // after it, so no launch would ever run that absorb and the provers leave it out.
 } }
 #include "sumcheck_batch.hpp"
+#include "sumcheck_verify_batch.hpp"
 
 using namespace stark;
 
@@ -165,6 +166,27 @@ __global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))
     chain_sponge_ex(P, RK, lds, total, T.init_cap, [&](size_t q) -> fr_t { return q < lead ? fr_zero<PF>() : T.elem(e0 + (q - lead)); },
                     fin ? T.out + seg : (fr_t*)nullptr, fresh ? (const fr_t*)nullptr : st, fin, st);
     if (threadIdx.x == 0) T.pos[b] = fin ? 0u : (total ? (uint32_t)(total - 16 * ((total - 1) / 16)) : 0u);
+}
+
+// ---- the batched verifiers (sumcheck_verify_batch.hpp) ---------------------------------------------------------------------------
+// Decode entry j of a plan -> pool[j]: one lane per field element, its 32 bytes read at any byte offset of the uploaded proofs as the nine
+// covering dwords; a value >= r clears the owning proof's flag.
+__global__ void __launch_bounds__(256) k_sc_decode_fr(const uint32_t* __restrict__ words, const uint32_t* __restrict__ dec_off, const uint32_t* __restrict__ dec_proof, uint32_t n,
+                                                      fr_t* __restrict__ pool, int32_t* __restrict__ flag) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t owner = dec_proof[j]; fr_t x;
+    if (!sc_decode_fr(words, dec_off[j], owner, x)) flag[owner & ~kScClaim] = 0;
+    stg(pool + j, x);
+}
+// verify_plain's relations, one lane per (proof, round); verify_mf's, one lane per relation.  A failed one clears the proof's flag.
+__global__ void __launch_bounds__(256) k_sc_verify_plain_check(const fr_t* __restrict__ pool, const uint32_t* __restrict__ rec, uint32_t n, int32_t* __restrict__ flag) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n && !sc_check_plain(pool, rec + 8 * (size_t)j)) flag[rec[8 * (size_t)j]] = 0;
+}
+__global__ void __launch_bounds__(256) k_sc_verify_mf_check(const fr_t* __restrict__ pool, const uint32_t* __restrict__ rec, uint32_t n, int32_t* __restrict__ flag) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n && !sc_check_mf(pool, rec + 8 * (size_t)j)) flag[rec[8 * (size_t)j + 1]] = 0;
 }
 
 // ---- device-resident transcript -----------------------------------------------------------------------------------------
@@ -383,6 +405,72 @@ static int32_t verify_mf_impl(stark_ctx* ctx, uint64_t tree_label, const uint8_t
     ok = !have || fr_eq(final_eval, running); return STARK_OK;                               // :1237-1238
 }
 
+// B transcripts of a TrBatchStream in the form the selector picks for that many instances
+static int32_t launch_tr_batch(stark_ctx* ctx, stark_params* tp, const TrBatchStream& T) {
+    if (!T.n_active) return STARK_OK;
+    if (poseidon_form(ctx, tp, PoseidonOp::DeviceTranscript, T.n_active) == PoseidonForm::FiveWave)
+        for (uint32_t sg = 0; sg < (uint32_t)T.nseg; ++sg)
+            hipLaunchKernelGGL(k_tr_batch_chain, dim3((unsigned)T.n_active), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, row_consts_of(ctx), T, sg);
+    else
+        hipLaunchKernelGGL(k_tr_batch, dim3((unsigned)T.n_active), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T);
+    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+}
+// Runs one plan of the batched verifiers: one upload (the proofs' bytes and the plan's index arrays), the decode, the transcript streams,
+// the DS groups in depth order, the checks, one download of the flags and one synchronisation.
+static int32_t run_sc_verify_batch(stark_ctx* ctx, const ScVerifyPlan& V, int32_t* accepted) {
+    if (!V.batch) return STARK_OK;
+    stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const VerifyBatchPlan& D = V.ds;
+    const size_t o_flag = 0, o_blob = al(V.batch * 4), o_doff = al(o_blob + V.blob.size() * 4), o_dpr = al(o_doff + V.n_dec * 4), o_con = al(o_dpr + V.n_dec * 4),
+                 o_toff = al(o_con + V.consts.size() * sizeof(fr_t)), o_tidx = al(o_toff + V.tr_off.size() * 4), o_hdr = al(o_tidx + V.tr_idx.size() * 4),
+                 o_off = al(o_hdr + D.hdr.size() * 8), o_idx = al(o_off + D.off.size() * 4), o_rec = al(o_idx + D.idx.size() * 4), n_up = al(o_rec + V.rec.size() * 4),
+                 o_pool = n_up, o_state = al(o_pool + V.pool_slots * sizeof(fr_t)), o_pos = al(o_state + 17 * V.n_inst * sizeof(fr_t)), total = al(o_pos + 4 * V.n_inst);
+    std::vector<uint8_t> h(n_up);                                       // everything the device reads, in one upload
+    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) memcpy(h.data() + o, src, bytes); };
+    put(o_flag, V.flag.data(), V.batch * 4); put(o_blob, V.blob.data(), V.blob.size() * 4); put(o_doff, V.dec_off.data(), V.n_dec * 4); put(o_dpr, V.dec_proof.data(), V.n_dec * 4);
+    put(o_con, V.consts.data(), V.consts.size() * sizeof(fr_t)); put(o_toff, V.tr_off.data(), V.tr_off.size() * 4); put(o_tidx, V.tr_idx.data(), V.tr_idx.size() * 4);
+    put(o_hdr, D.hdr.data(), D.hdr.size() * 8); put(o_off, D.off.data(), D.off.size() * 4); put(o_idx, D.idx.data(), D.idx.size() * 4); put(o_rec, V.rec.data(), V.rec.size() * 4);
+    DevBuf d; STARK_HIP(ctx, d.alloc(ctx, total));
+    uint8_t* base = (uint8_t*)d.p; fr_t* pool = (fr_t*)(base + o_pool); int32_t* flag = (int32_t*)(base + o_flag);
+    hipStream_t st = ctx->stream;
+    auto bail = [&](int32_t rc) { (void)hipStreamSynchronize(st); return rc; };      // `h` is host memory the upload may still read
+    if (hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "upload"));
+    if (V.n_dec) hipLaunchKernelGGL(k_sc_decode_fr, dim3((unsigned)((V.n_dec + 255) / 256)), dim3(256), 0, st, (const uint32_t*)(base + o_blob), (const uint32_t*)(base + o_doff),
+                                    (const uint32_t*)(base + o_dpr), (uint32_t)V.n_dec, pool, flag);
+    for (const ScVerifyPlan::Stream& S : V.tr) {
+        TrBatchStream T; T.state = (fr_t*)(base + o_state); T.pos = (uint32_t*)(base + o_pos); T.inst = nullptr; T.inst0 = S.inst0; T.n_active = S.n; T.nseg = S.nseg;
+        T.el_off = (const uint32_t*)(base + o_toff) + S.seg0; T.idx = (const uint32_t*)(base + o_tidx); T.pool0 = pool; T.pool1 = (const fr_t*)(base + o_con);
+        T.out = pool + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = 1; T.finish_last = 1;
+        for (size_t a0 = 0; a0 < S.n; a0 += 0x7fffffffu / 2) {                       // (a grid's x dimension)
+            TrBatchStream Ta = T; Ta.inst0 = S.inst0 + a0; Ta.n_active = std::min<size_t>(S.n - a0, 0x7fffffffu / 2); Ta.el_off = T.el_off + a0 * S.nseg; Ta.out = T.out + a0 * S.nseg;
+            int32_t rc = launch_tr_batch(ctx, tp, Ta); if (rc) return bail(rc);
+        }
+    }
+    { int32_t rc = verify_batch_groups_on(ctx, D, (const uint64_t*)(base + o_hdr), (const uint32_t*)(base + o_off), (const uint32_t*)(base + o_idx), pool, cp); if (rc) return bail(rc); }
+    if (const size_t n = V.n_rec()) {
+        const dim3 grid((unsigned)((n + 255) / 256));
+        if (V.mf) hipLaunchKernelGGL(k_sc_verify_mf_check, grid, dim3(256), 0, st, (const fr_t*)pool, (const uint32_t*)(base + o_rec), (uint32_t)n, flag);
+        else hipLaunchKernelGGL(k_sc_verify_plain_check, grid, dim3(256), 0, st, (const fr_t*)pool, (const uint32_t*)(base + o_rec), (uint32_t)n, flag);
+    }
+    if (hipGetLastError() != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "sum-check batch verification launch"));
+    if (hipMemcpyAsync(accepted, flag, V.batch * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "download"));
+    STARK_HIP(ctx, hipStreamSynchronize(st));
+    return STARK_OK;
+}
+// verify_plain (mf = 0) / verify_mf (mf = 1) of a batch, cut into plans of at most the context's "sumcheck_verify_batch_max_slots" pool slots
+static int32_t verify_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* tree_labels, int32_t* accepted) {
+    size_t b0 = 0;
+    while (b0 < batch) {
+        ScVerifyPlan V; bool fits = false;
+        const size_t b1 = sc_verify_plan_some(mf, b0, batch, proofs, lens, tree_labels, ctx->opt_sumcheck_verify_batch_max_slots, V, fits);
+        int32_t rc = fits ? run_sc_verify_batch(ctx, V, accepted + b0) : ctx->fail(STARK_ERR_INVALID_ARG, "a proof of the batch needs more than 2^30 pool slots");
+        if (rc) { memset(accepted, 0, batch * sizeof(int32_t)); return rc; }
+        b0 = b1;
+    }
+    return STARK_OK;
+}
+
 }  // namespace
 
 // ---- the streaming transcript as an object of the ABI (transcript/src/lib.rs:48-117) ------------------------------------------
@@ -535,6 +623,25 @@ int32_t stark_sumcheck_verify_mf(stark_ctx_t* ctx, size_t k, uint64_t tree_label
     if (!ctx || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx)); (void)k; (void)queries_per_round;
     bool ok = false; STARK_TRY(verify_mf_impl(ctx, tree_label, proof, len, ok)); *accepted = ok ? 1 : 0; return STARK_OK;
+}
+int32_t stark_sumcheck_verify_plain_batch(stark_ctx_t* ctx, size_t batch, const uint8_t* const* proofs, const size_t* lens, size_t k, const uint64_t* tree_labels, int32_t* accepted) {
+    if (!batch) return STARK_OK;
+    if (!accepted) return STARK_ERR_INVALID_ARG;
+    memset(accepted, 0, batch * sizeof(int32_t));
+    if (!ctx || !proofs || !lens) return STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) if (!proofs[b] && lens[b]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx)); (void)k; (void)tree_labels;     // read by neither verify_plain nor this (tree_labels may be NULL)
+    return verify_sumcheck_batch_impl(ctx, 0, batch, proofs, lens, nullptr, accepted);
+}
+int32_t stark_sumcheck_verify_mf_batch(stark_ctx_t* ctx, size_t batch, const uint8_t* const* proofs, const size_t* lens, size_t k, const uint64_t* tree_labels, size_t queries_per_round,
+                                       int32_t* accepted) {
+    if (!batch) return STARK_OK;
+    if (!accepted) return STARK_ERR_INVALID_ARG;
+    memset(accepted, 0, batch * sizeof(int32_t));
+    if (!ctx || !proofs || !lens || !tree_labels) return STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) if (!proofs[b] && lens[b]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx)); (void)k; (void)queries_per_round;
+    return verify_sumcheck_batch_impl(ctx, 1, batch, proofs, lens, tree_labels, accepted);
 }
 
 }  // extern "C"
