@@ -6,7 +6,7 @@
 #include <thread>
 #include <cstring>
 #include <map>
-#include "ctx.hpp"
+#include "poseidon_launch.hpp"
 #include "fri_dev.hpp"
 
 using namespace stark;
@@ -21,7 +21,6 @@ struct stark_fri_state {
     std::vector<fr_t> roots;                                // fetched on first use (one download + one sync for all L+1)
     ~stark_fri_state() { for (auto p : f) if (p) ctx_release(ctx, p); for (auto t : trees) if (t) stark_merkle_free(t); }
 };
-struct stark_proof { std::vector<uint8_t> bytes; size_t size_estimate = 0; double ms[3] = {0, 0, 0}; };
 
 static inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 static inline int ilog2(size_t x) { return ilog2_ceil(x); }
@@ -155,8 +154,8 @@ static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, con
     };
     // Underneath a layer-0 leaf launch of 32 or more chip-fills (k_leaf_pair2: 4 workgroups of 64 leaves per CU) the side stream has time to spare,
     // but every wave slot it holds is one the leaf launch cannot use: its levels and leaf layers then take the wave-pair form at every size (64
-    // sponges per two waves) instead of the latency forms (one wave, or five waves, per sponge) — option "fri_side_pair", poseidon_form.
-    ctx->side_commit = ctx->opt_fri_side_pair && S->n[0] >= (size_t)ctx->num_cus * 4 * 64 * 32;
+    // sponges per two waves) instead of the latency forms (one wave, or five waves, per sponge) — option "fri_side_pair", read by the selector of capi_poseidon.hip.
+    ctx->side_commit = ctx->opt.fri_side_pair && S->n[0] >= (size_t)ctx->num_cus * 4 * 64 * 32;
     int32_t crc = STARK_OK;
     for (size_t l = L; l >= 1 && crc == STARK_OK; --l) crc = commit_layer(l, side);
     ctx->side_commit = false;

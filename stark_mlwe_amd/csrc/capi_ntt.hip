@@ -45,7 +45,7 @@ struct NttPlan {
 static const size_t kMaxLds = 160 * 1024;
 // direct (one-product) twiddle / coset tables for transforms up to 2^ntt_direct_max_log points (option, default 24; 0 disables): they cost
 // n*32 B of HBM per strided pass and plan, which the VALU-bound transform does not notice, and save a product per element and pass
-static inline int ntt_direct_max(const stark_ctx* ctx) { return ctx->opt_ntt_direct_max_log; }
+static inline int ntt_direct_max(const stark_ctx* ctx) { return ctx->opt.ntt_direct_max_log; }
 
 // The NTT kernels multiply by table entries with ONE Montgomery step by 2^261 on nine-limb values (ntt_dev.hpp): every table
 // of a plan carries the factor 32 that makes that step a product in the 2^256 domain.
@@ -103,10 +103,10 @@ static inline size_t ntt_lds_bytes(int log_b, int log_c) { return ntt_tile_words
 // one workgroup per CU (tile > 80 KiB of LDS) => 512 threads so that every SIMD still holds 2 waves
 static inline unsigned ntt_threads(size_t lds) { return lds > 80 * 1024 ? 512u : 256u; }
 // tile elements E = B*C: 2^11 by default (64 KiB + twiddles => 2 workgroups per CU); option "ntt_log_tile" overrides for tuning
-static inline int ntt_minw(const stark_ctx* ctx) { return ctx->opt_ntt_min_waves; }
+static inline int ntt_minw(const stark_ctx* ctx) { return ctx->opt.ntt_min_waves; }
 // total_log: log2 of all elements the launch covers; small launches take smaller tiles so that the grid still fills the chip
 static inline int pick_log_c(const stark_ctx* ctx, int log_b, int cap, int total_log = 30) {
-    int le = ctx->opt_ntt_log_tile; if (!ctx->opt_ntt_log_tile_forced && total_log - le < 9) le = std::max(8, std::min(le, total_log - 8));
+    int le = ctx->opt.ntt_log_tile; if (!ctx->opt.ntt_log_tile_forced && total_log - le < 9) le = std::max(8, std::min(le, total_log - 8));
     int lc = std::max(2, le - log_b); lc = std::max(0, std::min(lc, cap));
     while (lc > 0 && ntt_lds_bytes(log_b, lc) > kMaxLds) --lc;      // 2^10-point sub-NTTs: two columns per tile (36 B per element in LDS)
     return lc;
@@ -152,7 +152,7 @@ static int32_t ntt_run(stark_ctx* ctx, fr_t* data, int log_n, uint64_t batch, bo
             if (p->coset_small) { (void)hipFree(p->coset_small); p->coset_small = nullptr; }
             if (p->tw_coset_direct) { (void)hipFree(p->tw_coset_direct); p->tw_coset_direct = nullptr; }
             bool merged = false;
-            if (!inverse && p->P >= 2 && p->tw_direct[0] && ctx->opt_ntt_merged_coset && ntt_direct_max(ctx) >= log_n) {
+            if (!inverse && p->P >= 2 && p->tw_direct[0] && ctx->opt.ntt_merged_coset && ntt_direct_max(ctx) >= log_n) {
                 // merged tables: the pre-scale's g^rest goes into the first pass's twiddle table, what is left is (g^S)^p by point index
                 PowTable gplain; STARK_TRY(plain_table<F>(ctx, p, *coset, log_n, &gplain));
                 const int lb0 = p->log_b[0], ls = log_n - lb0;

@@ -5,17 +5,10 @@
 //   stark_merkle_verify_pairs_ds     MerkleProver::verify_pairs         crates/merkle/src/lib.rs:723-773, 841-855
 //   stark_deep_fri_verify_batch      deep_fri_verify over many proofs: the plan of fri_verify_batch.hpp, one launch per (width, depth)
 #include <cstring>
-#include "ctx.hpp"
-#include "fri_verify.hpp"
+#include "verify_dev.hpp"
 #include "fri_verify_batch.hpp"
-#include "poseidon_streams.hpp"
 
 using namespace stark;
-
-namespace stark {
-int32_t hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
-                          const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out);   // capi_core.hip
-}
 
 namespace stark {
 // proof b is accepted iff its host flag is set and every root it computed equals the one it claims (VerifyBatchPlan::chk); one thread per proof
@@ -33,42 +26,6 @@ __global__ void __launch_bounds__(256) k_verify_batch_check(const fr_t* __restri
 
 }  // namespace stark
 
-namespace {
-struct GpuVerifyHasher : VerifyHasher {
-    stark_ctx* ctx; explicit GpuVerifyHasher(stark_ctx* c) : ctx(c) {}
-    // host vectors -> pooled device buffers -> kernel -> host (a few hundred hashes per call; one synchronisation each)
-    int32_t up(DevBuf& d, const void* src, size_t bytes) {
-        STARK_HIP(ctx, d.alloc(ctx, bytes));
-        if (bytes) STARK_HIP(ctx, hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return STARK_OK;
-    }
-    int32_t down(fr_t* dst, const DevBuf& d, size_t n) {
-        STARK_HIP(ctx, hipMemcpyAsync(dst, d.p, n * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
-    }
-    int32_t leaf_pairs(const fr_t* f, const fr_t* s, size_t n, fr_t* out) override {
-        if (!n) return STARK_OK;
-        DevBuf df, ds, dh; STARK_TRY(up(df, f, n * sizeof(fr_t))); STARK_TRY(up(ds, s, n * sizeof(fr_t))); STARK_HIP(ctx, dh.alloc(ctx, n * sizeof(fr_t)));
-        STARK_TRY(leaf_pair_hash_on(ctx, ctx->stream, df.fr(), ds.fr(), n, 1, dh.fr()));
-        return down(out, dh, n);
-    }
-    int32_t ds_nodes(size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions, const fr_t* children, size_t n, fr_t* out) override {
-        if (!n) return STARK_OK;
-        stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp));
-        DevBuf dp, dc, dout; STARK_TRY(up(dp, positions, n * 8)); STARK_TRY(up(dc, children, n * chunk * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n * sizeof(fr_t)));
-        STARK_TRY(hash_ds_scattered(ctx, mp, 0, arity, chunk, level, label, (const uint64_t*)dp.p, dc.fr(), nullptr, n, dout.fr()));
-        return down(out, dout, n);
-    }
-    int32_t ds_pair_leaves(size_t arity, uint64_t label, const uint64_t* positions, const fr_t* f, const fr_t* cp, size_t n, fr_t* out) override {
-        if (!n) return STARK_OK;
-        stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp));
-        DevBuf dp, df, dc, dout; STARK_TRY(up(dp, positions, n * 8)); STARK_TRY(up(df, f, n * sizeof(fr_t))); STARK_TRY(up(dc, cp, n * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n * sizeof(fr_t)));
-        STARK_TRY(hash_ds_scattered(ctx, mp, 1, arity, arity, 0xFFFFFFFFu, label, (const uint64_t*)dp.p, df.fr(), dc.fr(), n, dout.fr()));
-        return down(out, dout, n);
-    }
-};
-
-}  // namespace
 // The leaf step and the DS groups of a plan whose arrays are on the device, in depth order on the context's stream (groups that share a
 // depth after the first on the side stream, joined before the next depth).  fixed != nullptr: every group hashes with that parameter set
 // (the sum-check openings: MerkleCommitment's) instead of ctx_merkle_params(G.t).  On an error both streams are drained.
@@ -94,7 +51,7 @@ int32_t stark::verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, 
                 const VerifyBatchPlan::Group& G = V.groups[items[i]];
                 stark_params* mp = fixed; if (!mp) rc = ctx_merkle_params(ctx, G.t, &mp);
                 const DsGatherStream D{hdr + 4 * G.job0, off + G.job0, idx, pool, G.n, G.max_children};
-                if (!rc) rc = hash_ds_gather_on(ctx, st, mp, D, pool + G.out0);
+                if (!rc) rc = hash_ds_on(ctx, st, mp, D, pool + G.out0);
             }
             if (rc) return bail(rc);
         }

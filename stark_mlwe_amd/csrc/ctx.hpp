@@ -12,11 +12,7 @@
 #include "ntt_dev.hpp"
 #include "fri_plan.hpp"
 
-namespace stark {
-
-struct NttPlan;
-
-}  // namespace stark
+namespace stark { struct NttPlan; }
 
 // Handles (trees, FRI states, plans, transcripts, caller-made parameter sets) keep their context alive: stark_ctx_destroy with live handles
 // only marks the context; the LAST handle freed tears it down.  `CtxRef` is the FIRST member of every handle type, so it is destroyed last — after
@@ -77,17 +73,19 @@ struct stark_ctx {
     void* pinned = nullptr; size_t pinned_bytes = 0;                   // small pinned staging area for async uploads / downloads
 
     // tuning / diagnostic options (stark_ctx_set_option): explicit API state, never the environment
-    int opt_ntt_direct_max_log = 24;     // direct (one-product) twiddle / coset tables for transforms up to 2^this (0 disables)
-    bool opt_ntt_merged_coset = true;    // coset transforms: the pre-scale folded into the first pass's twiddle table (one table read instead of two); 0 = separate tables (comparison)
-    int opt_ntt_log_tile = 11;           // log2 of the elements of an NTT tile (8..12); -1 would mean "auto" (the default also shrinks for small launches)
-    bool opt_ntt_log_tile_forced = false;
-    int opt_ntt_min_waves = 2;           // occupancy hint of the NTT kernels (2 or 4 waves per SIMD)
-    int opt_sponge_debug = 0;            // timing experiments on the five-wave sponge (bit 0: A does not wait, 1: B idle, 2: C idle, 3: no full rounds, 4: no partial rounds); digests are WRONG when set
-    bool opt_sponge_one_wave = false;    // long serial sponges on ONE wave (poseidon_coop.hpp, round 2) instead of three (poseidon_chain.hpp) (diagnostic / comparison)
-    bool opt_poseidon_lane_only = false; // one-lane-per-sponge kernels instead of the wave-pair / one-wave forms (diagnostic)
-    bool opt_merkle_node16_pair = true;  // t = 17 Merkle levels of > 4096 nodes with exactly 16 children each: the fixed two-permutation kernel k_node16_pair; 0 = the generic k_hash_ds2 (comparison)
-    bool opt_fri_side_pair = true;       // fri_build: the small layers' commitments on the side stream in the wave-pair form at every size (see side_commit); 0 = the latency forms (comparison)
-    size_t opt_sumcheck_verify_batch_max_slots = (size_t)1 << 25;   // a plan of the batched sum-check verifiers is run once it holds this many pool slots (1 GiB of field elements): device memory stays bounded whatever the batch
+    struct Options {
+        int ntt_direct_max_log = 24;     // direct (one-product) twiddle / coset tables for transforms up to 2^this (0 disables)
+        bool ntt_merged_coset = true;    // coset transforms: the pre-scale folded into the first pass's twiddle table (one table read instead of two); 0 = separate tables (comparison)
+        int ntt_log_tile = 11;           // log2 of the elements of an NTT tile (8..12); -1 would mean "auto" (the default also shrinks for small launches)
+        bool ntt_log_tile_forced = false;
+        int ntt_min_waves = 2;           // occupancy hint of the NTT kernels (2 or 4 waves per SIMD)
+        int sponge_debug = 0;            // timing experiments on the five-wave sponge (bit 0: A does not wait, 1: B idle, 2: C idle, 3: no full rounds, 4: no partial rounds); digests are WRONG when set
+        bool sponge_one_wave = false;    // long serial sponges on ONE wave (poseidon_coop.hpp, round 2) instead of three (poseidon_chain.hpp) (diagnostic / comparison)
+        bool poseidon_lane_only = false; // one-lane-per-sponge kernels instead of the wave-pair / one-wave forms (diagnostic)
+        bool merkle_node16_pair = true;  // t = 17 Merkle levels of > 4096 nodes with exactly 16 children each: the fixed two-permutation kernel k_node16_pair; 0 = the generic k_hash_ds2 (comparison)
+        bool fri_side_pair = true;       // fri_build: the small layers' commitments on the side stream in the wave-pair form at every size (see side_commit); 0 = the latency forms (comparison)
+        size_t sumcheck_verify_batch_max_slots = (size_t)1 << 25;   // a plan of the batched sum-check verifiers is run once it holds this many pool slots (1 GiB of field elements): device memory stays bounded whatever the batch
+    } opt;
     bool side_commit = false;            // set while fri_build enqueues work that runs underneath the 2^n-leaf launch: Merkle levels and leaf layers of t = 9, 17 take the
                                          // wave-pair form (64 sponges per two waves) instead of one wave or five waves per sponge, which would hold many wave slots at lone-wave speed
 
@@ -105,7 +103,7 @@ struct stark_tree {
     std::vector<stark::fr_t*> levels; std::vector<size_t> lens; std::vector<char> owned;
     ~stark_tree() { for (size_t i = 0; i < levels.size(); ++i) if (owned[i] && levels[i]) stark::ctx_release(ctx, levels[i]); }
 };
-
+struct stark_proof { std::vector<uint8_t> bytes; size_t size_estimate = 0; double ms[3] = {0, 0, 0}; };   // a finished proof (capi_fri.hip, capi_sumcheck.hip): bytes, size estimate, stage times
 
 #define STARK_HIP(ctx, call)                                                                                     \
     do {                                                                                                         \
@@ -128,6 +126,10 @@ struct DevBuf {
     DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { if (p) ctx_release(ctx, p); }
     hipError_t alloc(stark_ctx* c, size_t bytes) { ctx = c; return ctx_alloc(c, bytes, &p) == STARK_OK ? hipSuccess : hipErrorOutOfMemory; }
+    // alloc, then the upload of `bytes` from host memory enqueued on the context's stream (`src` stays valid until the next synchronisation)
+    hipError_t upload(stark_ctx* c, const void* src, size_t bytes) { const hipError_t e = alloc(c, bytes); return e != hipSuccess || !bytes ? e : hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, c->stream); }
+    // the first `bytes` to host memory, then one synchronisation of the context's stream
+    hipError_t download_sync(void* dst, size_t bytes) const { const hipError_t e = bytes ? hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream); }
     fr_t* fr() const { return reinterpret_cast<fr_t*>(p); }
     void* release() { void* q = p; p = nullptr; return q; }
 };
@@ -135,7 +137,7 @@ struct DevBuf {
 // open_union_of_paths over a device-resident tree (MerkleProofHost and the encoders: fri_plan.hpp)
 int32_t merkle_open_host(stark_tree* t, const std::vector<size_t>& indices, MerkleProofHost& pr);
 
-// shared internal entry points (defined in capi_core.hip / capi_fri.hip / capi_ntt.hip)
+// shared internal entry points (defined in capi_core.hip / capi_ntt.hip / capi_comm.hip; the Poseidon ones: poseidon_launch.hpp)
 int32_t ctx_transcript_params(stark_ctx* ctx, stark_params** out);
 int32_t ctx_merkle_params(stark_ctx* ctx, int t, stark_params** out);
 int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out);
@@ -145,18 +147,5 @@ int32_t ctx_aux(stark_ctx* ctx, size_t k, stark_ctx** out);          // the k-th
 void comm_destroy(stark_ctx* ctx);
 void ntt_set_attrs();                                                // per-device kernel attributes of the NTT kernels (capi_ntt.hip)
 void ntt_plans_free(stark_ctx* ctx);
-int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h);
-int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t arity, uint64_t label, const fr_t* leaves, size_t n, int pairs, const fr_t* cp, size_t cp_div,
-                        uint64_t first_pos, uint32_t level0, size_t stop_at_len, bool adopt, stark_tree** out);
-int32_t hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
-                          const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out);
-struct DsGatherStream;
-int32_t hash_ds_gather_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out);   // one (width, depth) step of the batch verifier
-struct VerifyBatchPlan;
-int32_t verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, const uint64_t* hdr, const uint32_t* off, const uint32_t* idx, fr_t* pool, stark_params* fixed);   // the leaf step and DS groups of a batch plan (capi_verify.hip)
-int32_t tr_hash_dev(stark_ctx* ctx, const char* tag, const fr_t* fields_dev, size_t k, size_t n, fr_t* out_dev);
-int32_t tr_hash_columns4_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const cols[4], size_t n0, fr_t* out4_dev);
-int32_t tr_hash_columns_batch_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const* ptrs_dev, size_t batch, size_t n0, fr_t* out_dev);
-int32_t tr_hash_host1(stark_ctx* ctx, const char* tag, const std::vector<fr_t>& fields, fr_t* out);   // one hash, host in/out
 
 }  // namespace stark

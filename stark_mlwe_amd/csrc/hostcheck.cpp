@@ -15,7 +15,7 @@
 #include "fri_verify_batch.hpp"
 #include "mfma_digits.hpp"
 #include "poseidon_chain.hpp"
-#include "sumcheck_impl.hpp"     // the provers' transcript labels and sumcheck_batch.hpp (its HIP part is guarded)
+#include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
 
 using namespace stark;
 
@@ -218,7 +218,7 @@ int hc_permute_dense(void* h, uint64_t* states, size_t n) {
 }
 // kernel bodies on the host ---------------------------------------------------------------------------
 }  // extern "C"
-// the 17-lane template of hash_leaf_pair (capi_core.hip ctx_leaf_init)
+// the 17-lane template of hash_leaf_pair (capi_poseidon.hip ctx_leaf_init)
 static void leaf_init(fr_t init[17]) {
     const fr_t AB = host::h_tag("FSv1-ABSORB-BYTES"), CH = host::h_tag("FSv1-CHALLENGE");
     for (int j = 0; j < 17; ++j) init[j] = host::h_zero();

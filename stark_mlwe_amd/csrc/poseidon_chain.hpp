@@ -356,7 +356,7 @@ __device__ __forceinline__ void chain_partial_rounds(uint32_t& sr, const Poseido
 // into a state whose capacity element starts as `cap`, the lazy duplex of transcript/src/lib.rs:79-88 (permute only before absorbing more, once at
 // the end) — which is also hash_with_ds_dynamic's eager sponge over ds || children || 1 (crates/poseidon/src/lib.rs:219-312: the same permutations at
 // the same points, cap = 0).  Element 0 of the final state goes to *out_slot.
-// state_in != nullptr: the sponge RESUMES from 17 stored elements (the streaming transcript of sumcheck_impl.hpp; cap is ignored); final_permute = false leaves
+// state_in != nullptr: the sponge RESUMES from 17 stored elements (the streaming transcripts of poseidon_transcript.hpp; cap is ignored); final_permute = false leaves
 // the last block absorbed but not permuted; state_out != nullptr receives the 17 elements of the final state (canonical).
 template <class Elem>
 __device__ __forceinline__ void chain_sponge_ex(const PoseidonDev& P, const row::Consts& RK, uint4* lds, size_t total, const fr_t& cap, Elem elem, fr_t* out_slot,

@@ -1,0 +1,38 @@
+// stark_mlwe_amd/csrc/poseidon_launch.hpp — how the rest of the library launches Poseidon work: declarations only.  The kernels, the
+// kernel-form selector and these launchers are defined once, in capi_poseidon.hip; every consumer (capi_fri.hip, capi_verify.hip,
+// capi_sumcheck.hip) describes its sponges as a stream of poseidon_streams.hpp and calls one of these.
+#pragma once
+#include "ctx.hpp"
+#include "poseidon_streams.hpp"
+
+namespace stark {
+
+void poseidon_set_attrs();                                           // per-device kernel attributes of every Poseidon kernel these can launch (stark_ctx_create)
+
+// One launch of hash_with_ds_dynamic over the hashes of a DS stream on `st`, in the form the selector picks for a Merkle level of D.n_out nodes
+// (DsStream: a Merkle level / pair-leaf level; DsGatherStream: one (width, depth) step of the batch verifiers; DsBatchStream: one level of B trees).
+int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsStream& D, fr_t* out);
+int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out);
+int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out);
+// DS hashes with scattered positions (the verifier's union-of-paths levels): hash k = H([arity, level, positions[k], label] || chunk children)
+int32_t hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
+                          const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out);
+
+int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h);
+int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t arity, uint64_t label, const fr_t* leaves, size_t n, int pairs, const fr_t* cp, size_t cp_div,
+                        uint64_t first_pos, uint32_t level0, size_t stop_at_len, bool adopt, stark_tree** out);
+
+int32_t tr_hash_dev(stark_ctx* ctx, const char* tag, const fr_t* fields_dev, size_t k, size_t n, fr_t* out_dev);
+int32_t tr_hash_columns4_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const cols[4], size_t n0, fr_t* out4_dev);
+int32_t tr_hash_columns_batch_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const* ptrs_dev, size_t batch, size_t n0, fr_t* out_dev);
+int32_t tr_hash_host1(stark_ctx* ctx, const char* tag, const std::vector<fr_t>& fields, fr_t* out);   // one hash, host in/out
+
+// One device-resident streaming transcript (17 elements at `state`, rate cursor *pos) on the context's stream: absorbs the n device fields, then
+// (finish) permutes and squeezes state[0] into `out`.
+int32_t tr_stream_on(stark_ctx* ctx, stark_params* tp, fr_t* state, uint32_t* pos, const fr_t* fields, size_t n, bool finish, fr_t* out);
+// The active transcripts of a TrBatchStream on the context's stream, in the form the selector picks for n_for_form instances.  The batched provers
+// pass 1 (they select as one instance does) and the batched verifiers T.n_active: that difference is inherited from the two launch sites this
+// replaces, not designed.
+int32_t tr_batch_on(stark_ctx* ctx, stark_params* tp, const TrBatchStream& T, size_t n_for_form);
+
+}  // namespace stark

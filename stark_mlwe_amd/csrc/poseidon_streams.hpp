@@ -131,7 +131,7 @@ struct TrStream {
     }
 };
 
-// hash_leaf_pair(f_i, s_i) (fri.rs:38-44): ONE t = 17 permutation of the template `init` (capi_core.hip ctx_leaf_init)
+// hash_leaf_pair(f_i, s_i) (fri.rs:38-44): ONE t = 17 permutation of the template `init` (capi_poseidon.hip ctx_leaf_init)
 // with elements 4, 5 = (f[i], s_i), s_i = f_next[i / m] (zero when f_next == nullptr: fri.rs:266).  Elements 0..8 are the absorbed ones,
 // 9..15 of the template are zero, element 16 is the capacity.
 struct LeafStream {

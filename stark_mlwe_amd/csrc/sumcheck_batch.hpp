@@ -1,6 +1,6 @@
 // stark_mlwe_amd/csrc/sumcheck_batch.hpp — prove_plain / prove_mf (crates/channel/src/lib.rs:1045-1076, :1130-1172) of B independent
 // witnesses of 2^k elements in one pass: the round loops written once, over an executor that runs the batched kernels
-// (sumcheck_impl.hpp: the device; hostcheck.cpp: the same bodies on the host).
+// (capi_sumcheck.hip: the device; hostcheck.cpp: the same bodies on the host).
 //
 // Every per-round step is ONE operation for the whole batch, whatever B:
 //   * the Merkle commits (MerkleCommitment: arity 16, label per witness, commitment/src/lib.rs:85-90) run one DS level of all B trees per

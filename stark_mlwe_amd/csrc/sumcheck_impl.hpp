@@ -1,21 +1,10 @@
-// stark_mlwe_amd/csrc/sumcheck_impl.hpp — (included at the end of capi_core.hip: the Poseidon kernels it launches are defined once, in that translation unit)
-// "next" row N4: the sum-check consumer of the Merkle / Poseidon / transcript kernels
-// (crates/channel/src/lib.rs).  prove_plain / verify_plain (:1045-1128) and the Merkle-folded prove_mf / verify_mf (:1130-1240):
-//   * MerkleCommitment::commit (commitment/src/lib.rs:85-90: arity 16, parameters "POSEIDON-T17-X5-SEED") of the witness and of every
-//     shrinking folded layer = the level-batched Merkle kernels of the FRI path (merkle_build_on);
-//   * round coefficients c0 = sum a_j, c1 = sum (b_j - a_j) (:406-416) and the fold (1-r) a + r b (:456-462) = streaming kernels;
-//   * the Fiat-Shamir channel (:7-117) = DEVICE-RESIDENT transcripts: the verifiers and the ABI's transcript object queue absorbs on the
-//     host and run them as ONE launch when a challenge is drawn (DevTranscript); the provers lay out what every instance absorbs as pool
-//     indices and advance all transcripts of a batch per launch (TrBatchStream), so prove_plain has no host round trip in its rounds.
-// Every prove — one witness or many — runs the batched round loops of sumcheck_batch.hpp over the device executor below (ScDevExec).
-// Proof bytes = bincode 1.x layout of the reference's serde structs ProofPlain / ProofMF (:925-979), what its bench measures.
+// stark_mlwe_amd/csrc/sumcheck_impl.hpp — the host-only part of the sum-check consumer (the device part: capi_sumcheck.hip)
+// the provers' transcript labels and the batched round loops / verification plans that hostcheck.cpp runs on the host as well.
 #pragma once
-#include <memory>
-#include <set>
 #include "fri_verify.hpp"
 
 // The provers' transcript labels, the reference's strings verbatim (channel/src/lib.rs).  The round loops of sumcheck_batch.hpp lay out
-// their absorbs with these; the host-check library includes this file for them (everything HIP below is guarded).
+// their absorbs with these, the single verifiers of capi_sumcheck.hip absorb them, and the host-check library includes this file for them.
 namespace stark { namespace sc_lab {
 constexpr const char *digest = "CHAN/SEND/DIGEST", *open = "CHAN/SEND/OPEN", *arity = "PROOF/ARITY", *group_sizes = "PROOF/GROUP_SIZES",
                      *siblings = "PROOF/SIBLINGS";                                                                          // :22-56
@@ -28,621 +17,3 @@ constexpr const char *mf = "E2E/MF", *mf_round_chal = "SUMCHECK-MF/ROUND-CHAL", 
 } }
 #include "sumcheck_batch.hpp"
 #include "sumcheck_verify_batch.hpp"
-
-using namespace stark;
-
-struct stark_proof { std::vector<uint8_t> bytes; size_t size_estimate = 0; double ms[3] = {0, 0, 0}; };   // same object as capi_fri.hip's
-
-#if defined(__HIPCC__)
-
-namespace {
-
-// ---- kernels ------------------------------------------------------------------------------------------------------------
-// block partials of (c0, c1) over pairs (a, b) = (layer[2j], layer[2j+1]); out[2*block], out[2*block+1] (grid-stride over gridDim.x blocks)
-__device__ __forceinline__ void sc_coeffs_block(const fr_t* __restrict__ layer, uint64_t npairs, fr_t* __restrict__ out) {
-    __shared__ uint4 red[2 * 2 * 4];
-    fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < npairs; j += (uint64_t)gridDim.x * blockDim.x) {
-        const fr_t a = ldg(layer + 2 * j), b = ldg(layer + 2 * j + 1);
-        c0 = fr_add<PF>(c0, a); c1 = fr_add<PF>(c1, fr_sub<PF>(b, a));
-    }
-    for (int sft = 1; sft < 64; sft <<= 1) { c0 = fr_add<PF>(c0, shfl_xor_fr(c0, sft)); c1 = fr_add<PF>(c1, shfl_xor_fr(c1, sft)); }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { red[4 * wave] = make_uint4(c0.v[0], c0.v[1], c0.v[2], c0.v[3]); red[4 * wave + 1] = make_uint4(c0.v[4], c0.v[5], c0.v[6], c0.v[7]);
-                     red[4 * wave + 2] = make_uint4(c1.v[0], c1.v[1], c1.v[2], c1.v[3]); red[4 * wave + 3] = make_uint4(c1.v[4], c1.v[5], c1.v[6], c1.v[7]); }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        fr_t t0 = fr_zero<PF>(), t1 = fr_zero<PF>();
-        for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) {
-            fr_t x, y; const uint4 a = red[4 * wv], b = red[4 * wv + 1], c = red[4 * wv + 2], d = red[4 * wv + 3];
-            x.v[0] = a.x; x.v[1] = a.y; x.v[2] = a.z; x.v[3] = a.w; x.v[4] = b.x; x.v[5] = b.y; x.v[6] = b.z; x.v[7] = b.w;
-            y.v[0] = c.x; y.v[1] = c.y; y.v[2] = c.z; y.v[3] = c.w; y.v[4] = d.x; y.v[5] = d.y; y.v[6] = d.z; y.v[7] = d.w;
-            t0 = fr_add<PF>(t0, x); t1 = fr_add<PF>(t1, y);
-        }
-        stg(out + 2 * blockIdx.x, t0); stg(out + 2 * blockIdx.x + 1, t1);
-    }
-}
-// next[j] = (1 - r) * layer[2j] + r * layer[2j+1]  =  a + r * (b - a)
-__global__ void __launch_bounds__(256) k_sc_fold(const fr_t* __restrict__ layer, uint64_t npairs, fr_t r, fr_t* __restrict__ next) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= npairs) return;
-    const fr_t a = ldg(layer + 2 * j), b = ldg(layer + 2 * j + 1);
-    stg(next + j, fr_add<PF>(a, fr_mul<PF>(r, fr_sub<PF>(b, a))));
-}
-// The streaming transcript (transcript/src/lib.rs:79-101) on one wave: state[17] and the rate cursor live in device memory between
-// launches; absorbs `n` queued fields with the lazy permute-on-full rule, then (finish) permutes and squeezes state[0].
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_stream(PoseidonDev P, fr_t* __restrict__ state, uint32_t* __restrict__ pos_io,
-                                                                                           const fr_t* __restrict__ fields, uint64_t n, int finish, fr_t* __restrict__ out) {
-    extern __shared__ uint4 lds[];
-    CoopLds L = coop_setup<17>(lds, P);
-    const int lane = threadIdx.x;
-    fr_t s = lane < 17 ? ldg(state + lane) : fr_zero<PF>();
-    uint32_t pos = *pos_io;
-    for (uint64_t i = 0; i < n;) {
-        if (pos == 16) { s = coop_permute<17>(s, P, L, lane); pos = 0; }                 // only before absorbing more (lazy)
-        const uint64_t take = (16 - pos) < (n - i) ? (16 - pos) : (n - i);
-        if ((uint32_t)lane >= pos && (uint64_t)lane < pos + take) s = fr_add<PF>(s, ldg(fields + i + (lane - pos)));
-        pos += (uint32_t)take; i += take;
-    }
-    if (finish) { s = coop_permute<17>(s, P, L, lane); pos = 0; }
-    if (lane < 17) stg(state + lane, s);
-    if (lane == 0) { *pos_io = pos; if (out) stg(out, s); }
-}
-
-// The same on the five waves of poseidon_chain.hpp (72 us per permutation instead of 142 us): the stored cursor becomes `pos` leading no-op elements of
-// the stream, so that the block boundaries — and with them the lazy permutations — fall where k_tr_stream puts them.
-__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_stream_chain(PoseidonDev P, row::Consts RK, fr_t* __restrict__ state, uint32_t* __restrict__ pos_io,
-                                                                                                  const fr_t* __restrict__ fields, uint64_t n, int finish, fr_t* __restrict__ out) {
-    extern __shared__ uint4 lds[];
-    const uint32_t pos = *pos_io;                                                           // every thread reads it before thread 0 writes it back (barriers in between)
-    const size_t total = (size_t)pos + n;
-    chain_sponge_ex(P, RK, lds, total, fr_zero<PF>(), [&](size_t q) -> fr_t { return q < pos ? fr_zero<PF>() : ldg(fields + (q - pos)); },
-                    finish ? out : (fr_t*)nullptr, state, finish != 0, state);
-    if (threadIdx.x == 0) *pos_io = finish ? 0u : (total ? (uint32_t)(total - 16 * ((total - 1) / 16)) : 0u);
-}
-
-// ---- the batched round kernels (sumcheck_batch.hpp): instance b = b0 + blockIdx.y reads layer ptrs[b] or layers + b * len ----------------
-// block partials of (c0, c1) of every layer: part[2 (b gridDim.x + block)], +1
-__global__ void __launch_bounds__(256) k_sc_coeffs_batch(const fr_t* const* __restrict__ ptrs, const fr_t* __restrict__ layers, uint64_t len, uint64_t b0, fr_t* __restrict__ part) {
-    const uint64_t b = b0 + blockIdx.y;
-    sc_coeffs_block(ptrs ? ptrs[b] : layers + b * len, len / 2, part + 2 * (uint64_t)gridDim.x * b);
-}
-// one block per instance: c01[2b] = sum of its partial c0, c01[2b+1] = of c1; claim != nullptr: claim[b] = 2 c0 + c1 (send_claim, :434-446)
-__global__ void __launch_bounds__(64) k_sc_coeffs_final_batch(const fr_t* __restrict__ part, uint64_t nblocks, fr_t* __restrict__ c01, fr_t* __restrict__ claim) {
-    const uint64_t b = blockIdx.x; const fr_t* p = part + 2 * nblocks * b;
-    fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
-    for (uint64_t i = threadIdx.x; i < nblocks; i += 64) { c0 = fr_add<PF>(c0, ldg(p + 2 * i)); c1 = fr_add<PF>(c1, ldg(p + 2 * i + 1)); }
-    for (int sft = 1; sft < 64; sft <<= 1) { c0 = fr_add<PF>(c0, shfl_xor_fr(c0, sft)); c1 = fr_add<PF>(c1, shfl_xor_fr(c1, sft)); }
-    if (threadIdx.x == 0) { stg(c01 + 2 * b, c0); stg(c01 + 2 * b + 1, c1); if (claim) stg(claim + b, fr_add<PF>(fr_add<PF>(c0, c0), c1)); }
-}
-// next[b len/2 + j] = a + r_b (b - a) with r_b = r[b], the instance's challenge as the transcript kernel left it in device memory
-__global__ void __launch_bounds__(256) k_sc_fold_batch(const fr_t* const* __restrict__ ptrs, const fr_t* __restrict__ layers, uint64_t len, uint64_t b0, const fr_t* __restrict__ r,
-                                                       fr_t* __restrict__ next) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = b0 + blockIdx.y, np = len / 2;
-    if (j >= np) return;
-    const fr_t* layer = ptrs ? ptrs[b] : layers + b * len;
-    const fr_t a = ldg(layer + 2 * j), c = ldg(layer + 2 * j + 1), rb = ldg(r + b);
-    stg(next + b * np + j, fr_add<PF>(a, fr_mul<PF>(rb, fr_sub<PF>(c, a))));
-}
-// out[j] = *addr[j]: the roots of one-leaf trees and the openings of prove_mf (addresses built on the host from the known shapes)
-__global__ void __launch_bounds__(256) k_sc_gather(const fr_t* const* __restrict__ addr, uint64_t n, fr_t* __restrict__ out) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) stg(out + j, ldg(addr[j]));
-}
-// B transcripts (TrBatchStream), one wave each: k_tr_stream's absorb loop per segment, the elements gathered from the pools.
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_batch(PoseidonDev P, TrBatchStream T) {
-    extern __shared__ uint4 lds[];
-    CoopLds L = coop_setup<17>(lds, P);
-    const int lane = threadIdx.x;
-    const size_t a = blockIdx.x, b = T.instance(a);
-    fr_t s = T.reset ? (lane == 16 ? T.init_cap : fr_zero<PF>()) : (lane < 17 ? ldg(T.state + 17 * b + lane) : fr_zero<PF>());
-    uint32_t pos = T.reset ? 0u : T.pos[b];
-    for (size_t sg = 0; sg < T.nseg; ++sg) {
-        const size_t seg = a * T.nseg + sg;
-        const uint64_t e0 = T.el_off[seg], n = T.el_off[seg + 1] - e0;
-        for (uint64_t i = 0; i < n;) {
-            if (pos == 16) { s = coop_permute<17>(s, P, L, lane); pos = 0; }                 // only before absorbing more (lazy)
-            const uint64_t take = (16 - pos) < (n - i) ? (16 - pos) : (n - i);
-            if ((uint32_t)lane >= pos && (uint64_t)lane < pos + take) s = fr_add<PF>(s, T.elem(e0 + i + (lane - pos)));
-            pos += (uint32_t)take; i += take;
-        }
-        if (T.finishes(sg)) { s = coop_permute<17>(s, P, L, lane); pos = 0; if (lane == 0) stg(T.out + seg, s); }
-    }
-    if (lane < 17) stg(T.state + 17 * b + lane, s);
-    if (lane == 0) T.pos[b] = pos;
-}
-// The same on five waves: segment `sg` of every active instance, as k_tr_stream_chain runs it (the stored cursor becomes leading no-op
-// elements, so the lazy permutations fall where the one-wave form puts them; a finished segment leaves the cursor at 0).  One launch per
-// segment index: a loop over the segments inside this kernel raises it from 159 to 214 VGPRs (k_tr_stream_chain: 157).
-__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_batch_chain(PoseidonDev P, row::Consts RK, TrBatchStream T, uint32_t sg) {
-    extern __shared__ uint4 lds[];
-    const size_t a = blockIdx.x, b = T.instance(a), seg = a * T.nseg + sg;
-    const bool fresh = T.reset && sg == 0;
-    fr_t* st = T.state + 17 * b;
-    const uint32_t lead = fresh ? 0u : T.pos[b];                                            // every thread reads it before thread 0 writes it back (barriers in between)
-    const uint32_t e0 = T.el_off[seg];
-    const size_t total = (size_t)lead + (T.el_off[seg + 1] - e0);
-    const bool fin = T.finishes(sg);
-    chain_sponge_ex(P, RK, lds, total, T.init_cap, [&](size_t q) -> fr_t { return q < lead ? fr_zero<PF>() : T.elem(e0 + (q - lead)); },
-                    fin ? T.out + seg : (fr_t*)nullptr, fresh ? (const fr_t*)nullptr : st, fin, st);
-    if (threadIdx.x == 0) T.pos[b] = fin ? 0u : (total ? (uint32_t)(total - 16 * ((total - 1) / 16)) : 0u);
-}
-
-// ---- the batched verifiers (sumcheck_verify_batch.hpp) ---------------------------------------------------------------------------
-// Decode entry j of a plan -> pool[j]: one lane per field element, its 32 bytes read at any byte offset of the uploaded proofs as the nine
-// covering dwords; a value >= r clears the owning proof's flag.
-__global__ void __launch_bounds__(256) k_sc_decode_fr(const uint32_t* __restrict__ words, const uint32_t* __restrict__ dec_off, const uint32_t* __restrict__ dec_proof, uint32_t n,
-                                                      fr_t* __restrict__ pool, int32_t* __restrict__ flag) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t owner = dec_proof[j]; fr_t x;
-    if (!sc_decode_fr(words, dec_off[j], owner, x)) flag[owner & ~kScClaim] = 0;
-    stg(pool + j, x);
-}
-// verify_plain's relations, one lane per (proof, round); verify_mf's, one lane per relation.  A failed one clears the proof's flag.
-__global__ void __launch_bounds__(256) k_sc_verify_plain_check(const fr_t* __restrict__ pool, const uint32_t* __restrict__ rec, uint32_t n, int32_t* __restrict__ flag) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n && !sc_check_plain(pool, rec + 8 * (size_t)j)) flag[rec[8 * (size_t)j]] = 0;
-}
-__global__ void __launch_bounds__(256) k_sc_verify_mf_check(const fr_t* __restrict__ pool, const uint32_t* __restrict__ rec, uint32_t n, int32_t* __restrict__ flag) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n && !sc_check_mf(pool, rec + 8 * (size_t)j)) flag[rec[8 * (size_t)j + 1]] = 0;
-}
-
-// ---- device-resident transcript -----------------------------------------------------------------------------------------
-struct DevTranscript {
-    stark_ctx* ctx; DevBuf state, posb, out; std::vector<fr_t> pending; stark_params* tp = nullptr;
-    explicit DevTranscript(stark_ctx* c) : ctx(c) {}
-    int32_t init(const uint8_t* label, size_t n) {                                        // Transcript::new (:55-65)
-        STARK_TRY(ctx_transcript_params(ctx, &tp));
-        STARK_HIP(ctx, state.alloc(ctx, 17 * sizeof(fr_t))); STARK_HIP(ctx, posb.alloc(ctx, 4)); STARK_HIP(ctx, out.alloc(ctx, sizeof(fr_t)));
-        fr_t st[17]; for (auto& x : st) x = host::h_zero(); st[16] = host::h_tag("FSv1-TRANSCRIPT-INIT");
-        STARK_HIP(ctx, hipMemcpyAsync(state.p, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
-        STARK_HIP(ctx, hipMemsetAsync(posb.p, 0, 4, ctx->stream));
-        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));                                 // st is a stack temporary
-        absorb_bytes(label, n); return STARK_OK;
-    }
-    void absorb_field(const fr_t& x) { pending.push_back(x); }
-    void absorb_bytes(const uint8_t* b, size_t n) {                                        // :67-73: marker, then 31-byte words
-        pending.push_back(host::h_tag("FSv1-ABSORB-BYTES"));
-        for (size_t o = 0; o < n; o += 31) pending.push_back(host::h_from_le_bytes_mod_order(b + o, std::min<size_t>(31, n - o)));
-    }
-    void absorb_str(const char* s) { absorb_bytes((const uint8_t*)s, strlen(s)); }
-    void absorb_u64(uint64_t x) { uint8_t b[8]; for (int j = 0; j < 8; ++j) b[j] = (uint8_t)(x >> (8 * j)); absorb_bytes(b, 8); }
-    int32_t run(bool finish, fr_t* result) {
-        DevBuf f; const size_t n = pending.size();
-        if (n) { STARK_HIP(ctx, f.alloc(ctx, n * sizeof(fr_t))); STARK_HIP(ctx, hipMemcpyAsync(f.p, pending.data(), n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream)); }
-        if (poseidon_form(ctx, tp, PoseidonOp::DeviceTranscript, 1) == PoseidonForm::FiveWave)
-            hipLaunchKernelGGL(k_tr_stream_chain, dim3(1), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, row_consts_of(ctx), state.fr(), (uint32_t*)posb.p, (const fr_t*)f.fr(), (uint64_t)n, finish ? 1 : 0, finish ? out.fr() : (fr_t*)nullptr);
-        else
-            hipLaunchKernelGGL(k_tr_stream, dim3(1), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, state.fr(), (uint32_t*)posb.p, (const fr_t*)f.fr(), (uint64_t)n, finish ? 1 : 0, finish ? out.fr() : (fr_t*)nullptr);
-        STARK_HIP(ctx, hipGetLastError());
-        if (finish && result) STARK_HIP(ctx, hipMemcpyAsync(result, out.p, sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));                                 // `pending` is host memory; a challenge is needed on the host anyway
-        pending.clear(); return STARK_OK;
-    }
-    int32_t challenge(const uint8_t* label, size_t n, fr_t* r) {                           // :92-101
-        pending.push_back(host::h_tag("FSv1-CHALLENGE")); absorb_bytes(label, n);
-        return run(true, r);
-    }
-};
-
-struct BinR {
-    ByteReader R; explicit BinR(const uint8_t* p, size_t n) : R(p, n) {}
-    fr_t fb() { if (R.u64() != 32) R.ok = false; return R.fr(); }
-    bool idxs(std::vector<size_t>& v) { size_t k = R.len(8); v.resize(k); for (size_t i = 0; i < k; ++i) v[i] = (size_t)R.u64(); return R.ok; }
-    bool fvec(std::vector<fr_t>& v) { size_t k = R.len(40); v.resize(k); for (size_t i = 0; i < k && R.ok; ++i) v[i] = fb(); return R.ok; }
-    bool mproof(MerkleProofHost& p) {
-        p.arity = (size_t)R.u64();
-        size_t g = R.len(8); p.group_sizes.assign(g, {}); for (size_t i = 0; i < g && R.ok; ++i) { size_t k = R.len(1); p.group_sizes[i].resize(k); for (size_t j = 0; j < k; ++j) p.group_sizes[i][j] = R.u8(); }
-        if (!idxs(p.indices)) return false;
-        size_t a = R.len(8); p.siblings.assign(a, {}); for (size_t i = 0; i < a && R.ok; ++i) fvec(p.siblings[i]);
-        return R.ok;
-    }
-};
-
-static void send_digest(DevTranscript& T, const char* label, const fr_t& d) { T.absorb_str("CHAN/SEND/DIGEST"); T.absorb_str(label); T.absorb_field(d); }   // :22-26
-static void send_opening(DevTranscript& T, const std::vector<size_t>& idx, const std::vector<fr_t>& vals, const MerkleProofHost& pr) {                  // :32-62
-    T.absorb_str("CHAN/SEND/OPEN");
-    for (size_t i : idx) T.absorb_u64((uint64_t)i);
-    for (auto& v : vals) T.absorb_field(v);
-    T.absorb_str("PROOF/ARITY"); T.absorb_u64((uint64_t)pr.arity);
-    T.absorb_str("PROOF/GROUP_SIZES");
-    for (auto& l : pr.group_sizes) { T.absorb_u64((uint64_t)l.size()); for (uint8_t sz : l) T.absorb_bytes(&sz, 1); }
-    T.absorb_str("PROOF/SIBLINGS");
-    for (auto& l : pr.siblings) { T.absorb_u64((uint64_t)l.size()); for (auto& s : l) T.absorb_field(s); }
-}
-
-// MerkleCommitment's parameters (commitment/src/lib.rs:48-51), cached per context next to the other parameter sets (key -17)
-static int32_t commit_params(stark_ctx* ctx, stark_params** out) {
-    auto it = ctx->merkle_params.find(-17);
-    if (it != ctx->merkle_params.end()) { *out = it->second; return STARK_OK; }
-    stark_params* P = nullptr; const char* seed = "POSEIDON-T17-X5-SEED";
-    STARK_TRY(stark_poseidon_params_t17_seed(ctx, (const uint8_t*)seed, strlen(seed), &P));
-    ctx->merkle_params[-17] = P; *out = P; return STARK_OK;
-}
-static int32_t fold(stark_ctx* ctx, const fr_t* layer, size_t len, const fr_t& r, fr_t* next) {
-    const uint64_t np = len / 2;
-    hipLaunchKernelGGL(k_sc_fold, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, layer, np, r, next);
-    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-}
-// mf_round_challenge_from_root (:592-598): a fresh transcript per round
-static int32_t mf_round_challenge(stark_ctx* ctx, size_t round_idx, const fr_t& prev_root, fr_t* r) {
-    DevTranscript T(ctx); STARK_TRY(T.init((const uint8_t*)"SUMCHECK-MF/ROUND-CHAL", 22));
-    T.absorb_str("SUMCHECK/MF/R"); T.absorb_u64((uint64_t)round_idx); T.absorb_field(prev_root);
-    return T.challenge((const uint8_t*)"r_i", 3, r);
-}
-// The device executor of the batched drivers (sumcheck_batch.hpp): every operation is one launch (or a few, for more than 65535 layers) on
-// the context's stream; uploads are staged until the next download synchronises.
-struct ScDevExec {
-    stark_ctx* ctx; stark_params* cp; stark_params* tp;
-    std::vector<std::unique_ptr<DevBuf>> mem; std::vector<std::vector<uint8_t>> staged;
-    ScDevExec(stark_ctx* c, stark_params* commit, stark_params* tr) : ctx(c), cp(commit), tp(tr) {}
-    ~ScDevExec() { if (!staged.empty()) (void)hipStreamSynchronize(ctx->stream); }
-    int32_t alloc(size_t bytes, void** out) { mem.emplace_back(new DevBuf()); STARK_HIP(ctx, mem.back()->alloc(ctx, bytes)); *out = mem.back()->p; return STARK_OK; }
-    int32_t upload(void* dst, const void* src, size_t bytes) {
-        staged.emplace_back((const uint8_t*)src, (const uint8_t*)src + bytes);
-        STARK_HIP(ctx, hipMemcpyAsync(dst, staged.back().data(), bytes, hipMemcpyHostToDevice, ctx->stream)); return STARK_OK;
-    }
-    int32_t download(void* dst, const void* src, size_t bytes) {
-        STARK_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        staged.clear(); return STARK_OK;
-    }
-    int32_t ds_level(const DsBatchStream& D, fr_t* out) { return launch_ds(ctx, ctx->stream, cp, D, out); }
-    int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim) {
-        const uint64_t np = len / 2; const unsigned grid = (unsigned)std::min<uint64_t>((np + 255) / 256, 1024);
-        DevBuf part; STARK_HIP(ctx, part.alloc(ctx, (size_t)grid * 2 * B * sizeof(fr_t)));
-        for (size_t b0 = 0; b0 < B; b0 += 65535)
-            hipLaunchKernelGGL(k_sc_coeffs_batch, dim3(grid, (unsigned)std::min<size_t>(65535, B - b0)), dim3(256), 0, ctx->stream, ptrs, layers, (uint64_t)len, (uint64_t)b0, part.fr());
-        hipLaunchKernelGGL(k_sc_coeffs_final_batch, dim3((unsigned)B), dim3(64), 0, ctx->stream, (const fr_t*)part.fr(), (uint64_t)grid, c01, claim);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    int32_t fold(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, const fr_t* r, fr_t* next) {
-        const uint64_t np = len / 2;
-        for (size_t b0 = 0; b0 < B; b0 += 65535)
-            hipLaunchKernelGGL(k_sc_fold_batch, dim3((unsigned)((np + 255) / 256), (unsigned)std::min<size_t>(65535, B - b0)), dim3(256), 0, ctx->stream, ptrs, layers, (uint64_t)len, (uint64_t)b0, r, next);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    int32_t transcript(const TrBatchStream& T) {
-        if (!T.n_active) return STARK_OK;
-        if (poseidon_form(ctx, tp, PoseidonOp::DeviceTranscript, 1) == PoseidonForm::FiveWave)
-            for (uint32_t sg = 0; sg < (uint32_t)T.nseg; ++sg)
-                hipLaunchKernelGGL(k_tr_batch_chain, dim3((unsigned)T.n_active), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, row_consts_of(ctx), T, sg);
-        else
-            hipLaunchKernelGGL(k_tr_batch, dim3((unsigned)T.n_active), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-    int32_t gather(const fr_t* const* addr, size_t n, fr_t* out) {
-        hipLaunchKernelGGL(k_sc_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, addr, (uint64_t)n, out);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-};
-// prove_plain (mf = 0, :1045-1076) / prove_mf (mf = 1, :1130-1172) of `B` device-resident witnesses of 2^k elements: out[b] = the proof of
-// witness b alone.  The single entry points are this with B = 1.
-static int32_t prove_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t B, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, size_t qpr, stark_proof** out) {
-    for (size_t b = 0; b < B; ++b) out[b] = nullptr;
-    if (k > 40) return ctx->fail(STARK_ERR_INVALID_ARG, "k too large");
-    if (!B) return STARK_OK;
-    stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
-    std::vector<const fr_t*> w(B); for (size_t b = 0; b < B; ++b) w[b] = as_fr(witnesses[b]);
-    std::vector<std::vector<uint8_t>> proofs;
-    {
-        ScDevExec X(ctx, cp, tp);
-        ScBatch<ScDevExec> S(X, B, w.data(), k, tree_labels);
-        const int32_t rc = mf ? S.prove_mf(qpr, proofs) : S.prove_plain(proofs);
-        if (rc) return rc;
-    }
-    for (size_t b = 0; b < B; ++b) { out[b] = new stark_proof(); out[b]->bytes.swap(proofs[b]); out[b]->size_estimate = out[b]->bytes.size(); }
-    return STARK_OK;
-}
-
-// verifier hashing with MerkleCommitment's parameters (a t = 17 set that is NOT poseidon_params_for_arity(16))
-struct CommitVerifyHasher : VerifyHasher {
-    stark_ctx* ctx; stark_params* cp; CommitVerifyHasher(stark_ctx* c, stark_params* p) : ctx(c), cp(p) {}
-    int32_t leaf_pairs(const fr_t*, const fr_t*, size_t, fr_t*) override { return STARK_ERR_UNSUPPORTED; }
-    int32_t ds_pair_leaves(size_t, uint64_t, const uint64_t*, const fr_t*, const fr_t*, size_t, fr_t*) override { return STARK_ERR_UNSUPPORTED; }
-    int32_t ds_nodes(size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions, const fr_t* children, size_t n, fr_t* out) override {
-        if (!n) return STARK_OK;
-        DevBuf dp, dc, dout; STARK_HIP(ctx, dp.alloc(ctx, n * 8)); STARK_HIP(ctx, dc.alloc(ctx, n * chunk * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n * sizeof(fr_t)));
-        STARK_HIP(ctx, hipMemcpyAsync(dp.p, positions, n * 8, hipMemcpyHostToDevice, ctx->stream)); STARK_HIP(ctx, hipMemcpyAsync(dc.p, children, n * chunk * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-        STARK_TRY(hash_ds_scattered(ctx, cp, 0, arity, chunk, level, label, (const uint64_t*)dp.p, dc.fr(), nullptr, n, dout.fr()));
-        STARK_HIP(ctx, hipMemcpyAsync(out, dout.p, n * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
-    }
-};
-
-// verify_plain (:1080-1128).  A failed check answers `false` (inside the reference it is a failed assert_eq!, i.e. a panic).
-static int32_t verify_plain_impl(stark_ctx* ctx, const uint8_t* bytes, size_t len, bool& ok) {
-    ok = false;
-    BinR D(bytes, len); const fr_t root = D.fb(); const size_t nr = D.R.len(80);
-    std::vector<std::pair<fr_t, fr_t>> rounds(nr); for (size_t i = 0; i < nr && D.R.ok; ++i) { rounds[i].first = D.fb(); rounds[i].second = D.fb(); }
-    if (D.R.u8() != 0) D.R.ok = false;
-    const fr_t final_eval = D.fb();
-    if (!D.R.ok || D.R.left()) return STARK_OK;
-    if (rounds.empty()) return STARK_OK;                                                     // :1100-1102
-    DevTranscript T(ctx); STARK_TRY(T.init((const uint8_t*)"E2E/PLAIN", 9));
-    send_digest(T, "commit/root", root);
-    fr_t running = host::h_add(host::h_add(rounds[0].first, rounds[0].first), rounds[0].second);
-    T.absorb_str("SUMCHECK/CLAIM"); T.absorb_field(running);
-    for (size_t i = 0; i < rounds.size(); ++i) {
-        const fr_t& c0 = rounds[i].first; const fr_t& c1 = rounds[i].second;
-        T.absorb_str("SUMCHECK/ROUND"); T.absorb_u64((uint64_t)i); T.absorb_str("COEFF/c0"); T.absorb_field(c0); T.absorb_str("COEFF/c1"); T.absorb_field(c1);
-        if (!fr_eq(host::h_add(host::h_add(c0, c0), c1), running)) return STARK_OK;          // :511-512
-        fr_t r; { auto lb = lab_idx("sumcheck/r", i); STARK_TRY(T.challenge(lb.data(), lb.size(), &r)); }
-        running = host::h_add(c0, host::h_mul(c1, r));
-    }
-    ok = fr_eq(final_eval, running); return STARK_OK;                                        // :528
-}
-// verify_mf (:1176-1240)
-static int32_t verify_mf_impl(stark_ctx* ctx, uint64_t tree_label, const uint8_t* bytes, size_t len, bool& ok) {
-    ok = false;
-    BinR D(bytes, len); const fr_t initial_root = D.fb(); const size_t nr = D.R.len(120);
-    std::vector<RoundMFHost> rounds(nr);
-    for (size_t i = 0; i < nr && D.R.ok; ++i) { RoundMFHost& R = rounds[i]; R.c0 = D.fb(); R.c1 = D.fb(); R.next_root = D.fb(); D.idxs(R.cur_indices); D.fvec(R.cur_values); D.mproof(R.cur_proof); D.idxs(R.next_indices); D.fvec(R.next_values); D.mproof(R.next_proof); }
-    const fr_t final_eval = D.fb();
-    if (!D.R.ok || D.R.left()) return STARK_OK;
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
-    CommitVerifyHasher H(ctx, cp);
-    bool have = false; fr_t running = host::h_zero(), prev_root = initial_root;
-    for (size_t i = 0; i < rounds.size(); ++i) {
-        const RoundMFHost& R = rounds[i];
-        const fr_t twoc = host::h_add(host::h_add(R.c0, R.c0), R.c1);
-        if (have && !fr_eq(twoc, running)) return STARK_OK;                                  // start_round (:803-804)
-        fr_t r; STARK_TRY(mf_round_challenge(ctx, i, prev_root, &r));                        // derive_round_challenge (:807-810)
-        bool good = false;                                                                   // verify_fold_openings (:821-869)
-        STARK_TRY(verify_many_ds_host(H, 16, prev_root, R.cur_indices, R.cur_values, R.cur_proof, tree_label, good)); if (!good) return STARK_OK;
-        STARK_TRY(verify_many_ds_host(H, 16, R.next_root, R.next_indices, R.next_values, R.next_proof, tree_label, good)); if (!good) return STARK_OK;
-        if (R.cur_indices.size() != R.cur_values.size() || R.next_indices.size() != R.next_values.size()) return STARK_OK;
-        std::map<size_t, std::pair<std::pair<bool, fr_t>, std::pair<bool, fr_t>>> pairs;
-        for (size_t t = 0; t < R.cur_indices.size(); ++t) { const size_t ix = R.cur_indices[t]; auto& e = pairs[ix / 2]; if (ix % 2 == 0) e.first = {true, R.cur_values[t]}; else e.second = {true, R.cur_values[t]}; }
-        for (size_t t = 0; t < R.next_indices.size(); ++t) {
-            auto it = pairs.find(R.next_indices[t]);
-            if (it == pairs.end() || !it->second.first.first || !it->second.second.first) return STARK_OK;
-            const fr_t a = it->second.first.second, b = it->second.second.second;
-            if (!fr_eq(host::h_add(a, host::h_mul(r, host::h_sub(b, a))), R.next_values[t])) return STARK_OK;
-        }
-        running = host::h_add(R.c0, host::h_mul(R.c1, r)); have = true; prev_root = R.next_root;
-    }
-    ok = !have || fr_eq(final_eval, running); return STARK_OK;                               // :1237-1238
-}
-
-// B transcripts of a TrBatchStream in the form the selector picks for that many instances
-static int32_t launch_tr_batch(stark_ctx* ctx, stark_params* tp, const TrBatchStream& T) {
-    if (!T.n_active) return STARK_OK;
-    if (poseidon_form(ctx, tp, PoseidonOp::DeviceTranscript, T.n_active) == PoseidonForm::FiveWave)
-        for (uint32_t sg = 0; sg < (uint32_t)T.nseg; ++sg)
-            hipLaunchKernelGGL(k_tr_batch_chain, dim3((unsigned)T.n_active), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, row_consts_of(ctx), T, sg);
-    else
-        hipLaunchKernelGGL(k_tr_batch, dim3((unsigned)T.n_active), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T);
-    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-}
-// Runs one plan of the batched verifiers: one upload (the proofs' bytes and the plan's index arrays), the decode, the transcript streams,
-// the DS groups in depth order, the checks, one download of the flags and one synchronisation.
-static int32_t run_sc_verify_batch(stark_ctx* ctx, const ScVerifyPlan& V, int32_t* accepted) {
-    if (!V.batch) return STARK_OK;
-    stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const VerifyBatchPlan& D = V.ds;
-    const size_t o_flag = 0, o_blob = al(V.batch * 4), o_doff = al(o_blob + V.blob.size() * 4), o_dpr = al(o_doff + V.n_dec * 4), o_con = al(o_dpr + V.n_dec * 4),
-                 o_toff = al(o_con + V.consts.size() * sizeof(fr_t)), o_tidx = al(o_toff + V.tr_off.size() * 4), o_hdr = al(o_tidx + V.tr_idx.size() * 4),
-                 o_off = al(o_hdr + D.hdr.size() * 8), o_idx = al(o_off + D.off.size() * 4), o_rec = al(o_idx + D.idx.size() * 4), n_up = al(o_rec + V.rec.size() * 4),
-                 o_pool = n_up, o_state = al(o_pool + V.pool_slots * sizeof(fr_t)), o_pos = al(o_state + 17 * V.n_inst * sizeof(fr_t)), total = al(o_pos + 4 * V.n_inst);
-    std::vector<uint8_t> h(n_up);                                       // everything the device reads, in one upload
-    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) memcpy(h.data() + o, src, bytes); };
-    put(o_flag, V.flag.data(), V.batch * 4); put(o_blob, V.blob.data(), V.blob.size() * 4); put(o_doff, V.dec_off.data(), V.n_dec * 4); put(o_dpr, V.dec_proof.data(), V.n_dec * 4);
-    put(o_con, V.consts.data(), V.consts.size() * sizeof(fr_t)); put(o_toff, V.tr_off.data(), V.tr_off.size() * 4); put(o_tidx, V.tr_idx.data(), V.tr_idx.size() * 4);
-    put(o_hdr, D.hdr.data(), D.hdr.size() * 8); put(o_off, D.off.data(), D.off.size() * 4); put(o_idx, D.idx.data(), D.idx.size() * 4); put(o_rec, V.rec.data(), V.rec.size() * 4);
-    DevBuf d; STARK_HIP(ctx, d.alloc(ctx, total));
-    uint8_t* base = (uint8_t*)d.p; fr_t* pool = (fr_t*)(base + o_pool); int32_t* flag = (int32_t*)(base + o_flag);
-    hipStream_t st = ctx->stream;
-    auto bail = [&](int32_t rc) { (void)hipStreamSynchronize(st); return rc; };      // `h` is host memory the upload may still read
-    if (hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "upload"));
-    if (V.n_dec) hipLaunchKernelGGL(k_sc_decode_fr, dim3((unsigned)((V.n_dec + 255) / 256)), dim3(256), 0, st, (const uint32_t*)(base + o_blob), (const uint32_t*)(base + o_doff),
-                                    (const uint32_t*)(base + o_dpr), (uint32_t)V.n_dec, pool, flag);
-    for (const ScVerifyPlan::Stream& S : V.tr) {
-        TrBatchStream T; T.state = (fr_t*)(base + o_state); T.pos = (uint32_t*)(base + o_pos); T.inst = nullptr; T.inst0 = S.inst0; T.n_active = S.n; T.nseg = S.nseg;
-        T.el_off = (const uint32_t*)(base + o_toff) + S.seg0; T.idx = (const uint32_t*)(base + o_tidx); T.pool0 = pool; T.pool1 = (const fr_t*)(base + o_con);
-        T.out = pool + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = 1; T.finish_last = 1;
-        for (size_t a0 = 0; a0 < S.n; a0 += 0x7fffffffu / 2) {                       // (a grid's x dimension)
-            TrBatchStream Ta = T; Ta.inst0 = S.inst0 + a0; Ta.n_active = std::min<size_t>(S.n - a0, 0x7fffffffu / 2); Ta.el_off = T.el_off + a0 * S.nseg; Ta.out = T.out + a0 * S.nseg;
-            int32_t rc = launch_tr_batch(ctx, tp, Ta); if (rc) return bail(rc);
-        }
-    }
-    { int32_t rc = verify_batch_groups_on(ctx, D, (const uint64_t*)(base + o_hdr), (const uint32_t*)(base + o_off), (const uint32_t*)(base + o_idx), pool, cp); if (rc) return bail(rc); }
-    if (const size_t n = V.n_rec()) {
-        const dim3 grid((unsigned)((n + 255) / 256));
-        if (V.mf) hipLaunchKernelGGL(k_sc_verify_mf_check, grid, dim3(256), 0, st, (const fr_t*)pool, (const uint32_t*)(base + o_rec), (uint32_t)n, flag);
-        else hipLaunchKernelGGL(k_sc_verify_plain_check, grid, dim3(256), 0, st, (const fr_t*)pool, (const uint32_t*)(base + o_rec), (uint32_t)n, flag);
-    }
-    if (hipGetLastError() != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "sum-check batch verification launch"));
-    if (hipMemcpyAsync(accepted, flag, V.batch * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "download"));
-    STARK_HIP(ctx, hipStreamSynchronize(st));
-    return STARK_OK;
-}
-// verify_plain (mf = 0) / verify_mf (mf = 1) of a batch, cut into plans of at most the context's "sumcheck_verify_batch_max_slots" pool slots
-static int32_t verify_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* tree_labels, int32_t* accepted) {
-    size_t b0 = 0;
-    while (b0 < batch) {
-        ScVerifyPlan V; bool fits = false;
-        const size_t b1 = sc_verify_plan_some(mf, b0, batch, proofs, lens, tree_labels, ctx->opt_sumcheck_verify_batch_max_slots, V, fits);
-        int32_t rc = fits ? run_sc_verify_batch(ctx, V, accepted + b0) : ctx->fail(STARK_ERR_INVALID_ARG, "a proof of the batch needs more than 2^30 pool slots");
-        if (rc) { memset(accepted, 0, batch * sizeof(int32_t)); return rc; }
-        b0 = b1;
-    }
-    return STARK_OK;
-}
-
-}  // namespace
-
-// ---- the streaming transcript as an object of the ABI (transcript/src/lib.rs:48-117) ------------------------------------------
-struct stark_transcript { CtxRef ref_; DevTranscript T; explicit stark_transcript(stark_ctx* c) : T(c) { ref_.bind(c); } };
-
-extern "C" {
-
-// Transcript::new(label, default_params()) — the state lives on the device; absorbs are queued and run with the next challenge.
-int32_t stark_transcript_new(stark_ctx_t* ctx, const uint8_t* label, size_t label_len, stark_transcript_t** out) {
-    if (!ctx || !out || (!label && label_len)) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    stark_transcript* t = new stark_transcript(ctx);
-    int32_t rc = t->T.init(label, label_len); if (rc) { delete t; return rc; }
-    *out = t; return STARK_OK;
-}
-int32_t stark_transcript_absorb_bytes(stark_transcript_t* t, const uint8_t* bytes, size_t n) { if (!t || (!bytes && n)) return STARK_ERR_INVALID_ARG; t->T.absorb_bytes(bytes, n); return STARK_OK; }
-int32_t stark_transcript_absorb_fields(stark_transcript_t* t, const uint64_t* fields, size_t n) {
-    if (!t || (!fields && n)) return STARK_ERR_INVALID_ARG;
-    for (size_t i = 0; i < n; ++i) t->T.absorb_field(load_fr(fields + 4 * i));
-    return STARK_OK;
-}
-int32_t stark_transcript_challenge(stark_transcript_t* t, const uint8_t* label, size_t label_len, uint64_t* out4) {
-    if (!t || !out4 || (!label && label_len)) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(t->T.ctx));
-    fr_t r; STARK_TRY(t->T.challenge(label, label_len, &r)); store_fr(out4, r); return STARK_OK;
-}
-// Transcript::challenges(label, n): challenge(label || le64(i)) for i < n (:103-112)
-int32_t stark_transcript_challenges(stark_transcript_t* t, const uint8_t* label, size_t label_len, size_t n, uint64_t* out) {
-    if (!t || (!out && n) || (!label && label_len)) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(t->T.ctx));
-    for (size_t i = 0; i < n; ++i) {
-        std::vector<uint8_t> tag(label, label + label_len); for (int j = 0; j < 8; ++j) tag.push_back((uint8_t)((uint64_t)i >> (8 * j)));
-        fr_t r; STARK_TRY(t->T.challenge(tag.data(), tag.size(), &r)); store_fr(out + 4 * i, r);
-    }
-    return STARK_OK;
-}
-int32_t stark_transcript_free(stark_transcript_t* t) { if (!t) return STARK_ERR_INVALID_ARG; delete t; return STARK_OK; }
-
-// The reference's bench inputs (channel/benches/end_to_end.rs:249-253): `ncols` vectors of n elements drawn one after the other
-// from ONE StdRng::seed_from_u64(seed) with ark-ff's Fp::rand (rand_core 0.6.4 PCG32 seed expansion, ChaCha12, rejection sampling of
-// 255-bit candidates; the accepted limbs ARE the Montgomery representation).  Host-only: no context, no device.
-int32_t stark_ref_bench_inputs(uint64_t seed, size_t n, size_t ncols, uint64_t* out) {
-    if (!out && n * ncols) return STARK_ERR_INVALID_ARG;
-    uint8_t key[32]; uint64_t state = seed;
-    for (int c = 0; c < 8; ++c) {                                                          // SeedableRng::seed_from_u64
-        state = state * 6364136223846793005ull + 11634580027462260723ull;
-        const uint32_t xs = (uint32_t)(((state >> 18) ^ state) >> 27), rot = (uint32_t)(state >> 59);
-        const uint32_t x = (xs >> rot) | (xs << ((32 - rot) & 31));
-        key[4 * c] = (uint8_t)x; key[4 * c + 1] = (uint8_t)(x >> 8); key[4 * c + 2] = (uint8_t)(x >> 16); key[4 * c + 3] = (uint8_t)(x >> 24);
-    }
-    host::ChaCha12Rng rng(key);
-    for (size_t i = 0; i < n * ncols; ++i) {
-        for (;;) {                                                                         // Fp::rand: 4 limbs, top bit cleared, accept below the modulus
-            uint64_t l[4]; for (int j = 0; j < 4; ++j) l[j] = rng.next_u64();
-            l[3] &= 0x7FFFFFFFFFFFFFFFull;
-            uint32_t t[9]; for (int j = 0; j < 4; ++j) { t[2 * j] = (uint32_t)l[j]; t[2 * j + 1] = (uint32_t)(l[j] >> 32); } t[8] = 0;
-            if (fr_geq_p<PallasFr>(t)) continue;
-            for (int j = 0; j < 4; ++j) out[4 * i + j] = l[j];
-            break;
-        }
-    }
-    return STARK_OK;
-}
-
-// CommitmentScheme for MerkleCommitment (commitment/src/lib.rs:80-114): arity 16, tree_label = cfg.ds_tag, parameters "POSEIDON-T17-X5-SEED".
-int32_t stark_commitment_commit(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* leaves, size_t n, stark_tree_t** out) {
-    if (!ctx || !leaves || !out) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
-    DevBuf d; STARK_HIP(ctx, d.alloc(ctx, std::max<size_t>(n, 1) * sizeof(fr_t)));
-    if (n) STARK_HIP(ctx, hipMemcpyAsync(d.p, leaves, n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    STARK_TRY(merkle_build_on(ctx, ctx->stream, cp, 16, ds_tag, d.fr(), n, 0, nullptr, 1, 0, 0, 0, false, out));     // commit (:85-90); open = stark_merkle_open (:92-94)
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
-}
-// verify (:96-113): verify_many_ds with the static t = 17 parameters lifted to the dynamic form
-int32_t stark_commitment_verify(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* root4, const size_t* indices, size_t k, const uint64_t* values, const uint8_t* proof, size_t len, int32_t* accepted) {
-    if (!ctx || !root4 || (!indices && k) || (!values && k) || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    *accepted = 0;
-    ByteReader R(proof, len); MerkleProofHost pr; if (!dec_mproof(R, pr) || R.left()) return STARK_OK;
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
-    std::vector<size_t> ix(indices, indices + k); std::vector<fr_t> v(k); for (size_t i = 0; i < k; ++i) v[i] = load_fr(values + 4 * i);
-    CommitVerifyHasher H(ctx, cp); bool ok = false;
-    STARK_TRY(verify_many_ds_host(H, 16, load_fr(root4), ix, v, pr, ds_tag, ok));
-    *accepted = ok ? 1 : 0; return STARK_OK;
-}
-
-// Mle::evaluate(r) (channel/src/lib.rs:279-295): k folds layer[i] = (1 - r_j) layer[2i] + r_j layer[2i+1]; table of 2^k elements (host).
-int32_t stark_mle_evaluate(stark_ctx_t* ctx, const uint64_t* table, size_t k, const uint64_t* r, uint64_t* out4) {
-    if (!ctx || !table || (!r && k) || !out4 || k > 40) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    const size_t n = (size_t)1 << k;
-    DevBuf a, b; STARK_HIP(ctx, a.alloc(ctx, n * sizeof(fr_t))); STARK_HIP(ctx, b.alloc(ctx, std::max<size_t>(n / 2, 1) * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(a.p, table, n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    fr_t* cur = a.fr(); fr_t* nxt = b.fr(); size_t len = n;
-    for (size_t j = 0; j < k; ++j) { STARK_TRY(fold(ctx, cur, len, load_fr(r + 4 * j), nxt)); std::swap(cur, nxt); len /= 2; }
-    fr_t v; STARK_HIP(ctx, hipMemcpyAsync(&v, cur, sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    store_fr(out4, v); return STARK_OK;
-}
-
-int32_t stark_sumcheck_prove_plain_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out) {
-    if (!ctx || !witness || !out) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    return prove_sumcheck_batch_impl(ctx, 0, 1, &witness, k, &tree_label, 0, out);
-}
-int32_t stark_sumcheck_prove_mf_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, size_t queries_per_round, stark_proof_t** out) {
-    if (!ctx || !witness || !out) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    return prove_sumcheck_batch_impl(ctx, 1, 1, &witness, k, &tree_label, queries_per_round, out);
-}
-int32_t stark_sumcheck_prove_plain(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out) {
-    if (!ctx || !witness || !out || k > 40) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    const size_t n = (size_t)1 << k; DevBuf d; STARK_HIP(ctx, d.alloc(ctx, n * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(d.p, witness, n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    const uint64_t* w = (const uint64_t*)d.p;
-    return prove_sumcheck_batch_impl(ctx, 0, 1, &w, k, &tree_label, 0, out);
-}
-int32_t stark_sumcheck_prove_mf(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, size_t queries_per_round, stark_proof_t** out) {
-    if (!ctx || !witness || !out || k > 40) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    const size_t n = (size_t)1 << k; DevBuf d; STARK_HIP(ctx, d.alloc(ctx, n * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(d.p, witness, n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    const uint64_t* w = (const uint64_t*)d.p;
-    return prove_sumcheck_batch_impl(ctx, 1, 1, &w, k, &tree_label, queries_per_round, out);
-}
-int32_t stark_sumcheck_prove_plain_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, stark_proof_t** out) {
-    if (!batch) return STARK_OK;
-    if (out) for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
-    if (!ctx || !out || !witnesses || !tree_labels || k > 40) return STARK_ERR_INVALID_ARG;
-    for (size_t b = 0; b < batch; ++b) if (!witnesses[b]) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    return prove_sumcheck_batch_impl(ctx, 0, batch, witnesses, k, tree_labels, 0, out);
-}
-int32_t stark_sumcheck_prove_mf_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, size_t queries_per_round,
-                                          stark_proof_t** out) {
-    if (!batch) return STARK_OK;
-    if (out) for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
-    if (!ctx || !out || !witnesses || !tree_labels || k > 40) return STARK_ERR_INVALID_ARG;
-    for (size_t b = 0; b < batch; ++b) if (!witnesses[b]) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    return prove_sumcheck_batch_impl(ctx, 1, batch, witnesses, k, tree_labels, queries_per_round, out);
-}
-int32_t stark_sumcheck_verify_plain(stark_ctx_t* ctx, size_t k, uint64_t tree_label, const uint8_t* proof, size_t len, int32_t* accepted) {
-    if (!ctx || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx)); (void)k; (void)tree_label;     // verify_plain reads neither vk.k (it walks proof.rounds) nor the tree label
-    bool ok = false; STARK_TRY(verify_plain_impl(ctx, proof, len, ok)); *accepted = ok ? 1 : 0; return STARK_OK;
-}
-int32_t stark_sumcheck_verify_mf(stark_ctx_t* ctx, size_t k, uint64_t tree_label, size_t queries_per_round, const uint8_t* proof, size_t len, int32_t* accepted) {
-    if (!ctx || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx)); (void)k; (void)queries_per_round;
-    bool ok = false; STARK_TRY(verify_mf_impl(ctx, tree_label, proof, len, ok)); *accepted = ok ? 1 : 0; return STARK_OK;
-}
-int32_t stark_sumcheck_verify_plain_batch(stark_ctx_t* ctx, size_t batch, const uint8_t* const* proofs, const size_t* lens, size_t k, const uint64_t* tree_labels, int32_t* accepted) {
-    if (!batch) return STARK_OK;
-    if (!accepted) return STARK_ERR_INVALID_ARG;
-    memset(accepted, 0, batch * sizeof(int32_t));
-    if (!ctx || !proofs || !lens) return STARK_ERR_INVALID_ARG;
-    for (size_t b = 0; b < batch; ++b) if (!proofs[b] && lens[b]) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx)); (void)k; (void)tree_labels;     // read by neither verify_plain nor this (tree_labels may be NULL)
-    return verify_sumcheck_batch_impl(ctx, 0, batch, proofs, lens, nullptr, accepted);
-}
-int32_t stark_sumcheck_verify_mf_batch(stark_ctx_t* ctx, size_t batch, const uint8_t* const* proofs, const size_t* lens, size_t k, const uint64_t* tree_labels, size_t queries_per_round,
-                                       int32_t* accepted) {
-    if (!batch) return STARK_OK;
-    if (!accepted) return STARK_ERR_INVALID_ARG;
-    memset(accepted, 0, batch * sizeof(int32_t));
-    if (!ctx || !proofs || !lens || !tree_labels) return STARK_ERR_INVALID_ARG;
-    for (size_t b = 0; b < batch; ++b) if (!proofs[b] && lens[b]) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx)); (void)k; (void)queries_per_round;
-    return verify_sumcheck_batch_impl(ctx, 1, batch, proofs, lens, tree_labels, accepted);
-}
-
-}  // extern "C"
-#endif  // __HIPCC__

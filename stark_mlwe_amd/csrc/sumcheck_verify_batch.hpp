@@ -1,9 +1,9 @@
 // stark_mlwe_amd/csrc/sumcheck_verify_batch.hpp — verify_plain / verify_mf (crates/channel/src/lib.rs:1080-1128, :1176-1240) over a batch of
-// proofs, planned on the host and decided on the device (sumcheck_impl.hpp: the device; hostcheck.cpp: the same bodies on the host).
+// proofs, planned on the host and decided on the device (capi_sumcheck.hip: the device; hostcheck.cpp: the same bodies on the host).
 //
 // Everything a sum-check verifier hashes or absorbs is data inside the proof: verify_mf draws r_i from prev_root, which it reads and never
 // computes, and checks each opening against a root the proof claims; verify_plain's transcript absorbs only the proof's coefficients.  So
-// the planner parses the bincode layout exactly as BinR does (sumcheck_impl.hpp: same length guards, the == 32 FBytes prefix, the Option
+// the planner parses the bincode layout exactly as BinR does (capi_sumcheck.hip: same length guards, the == 32 FBytes prefix, the Option
 // tag byte of ProofPlain, no trailing bytes) but converts NO field element: it records where each one sits in the uploaded bytes and
 // which pool slot it lands in, and the device decodes them (sc_decode_fr: range check and Montgomery conversion, one lane each).
 //
@@ -22,7 +22,7 @@
 //            mf, one per relation:             { kind, proof, a, b, c, d, e, 0 }
 //                   kChain 2 a + b == c + d e | kFinal a == c + d e | kFold a + e (b - a) == c | kEq a == b (a computed root, the claimed one)
 // accepted[b] = flag[b] after the checks.  A proof that does not parse or fails a host check keeps nothing in the plan and has flag 0.
-// Host-only C++ but for the FR_HD bodies, which the kernels of sumcheck_impl.hpp run.  Included by sumcheck_impl.hpp after sumcheck_batch.hpp.
+// Host-only C++ but for the FR_HD bodies, which the kernels of capi_sumcheck.hip run.  Included by sumcheck_impl.hpp after sumcheck_batch.hpp.
 #pragma once
 #include <map>
 #include "fri_verify_batch.hpp"

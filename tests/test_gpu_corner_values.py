@@ -40,7 +40,7 @@ def first_diff(got, want):
 
 
 # ---- Poseidon: every kernel form on crafted levels ----------------------------------------------------------------------------------
-# kernel forms of a Merkle level (capi_core.hip poseidon_form): the default choice by size — five-wave up to 256 nodes, one-wave up to 4096,
+# kernel forms of a Merkle level (capi_poseidon.hip poseidon_form): the default choice by size — five-wave up to 256 nodes, one-wave up to 4096,
 # k_node16_pair above — and what the options force
 FORMS = {"default": {}, "k_hash_ds2 (merkle_node16_pair = 0)": {"merkle_node16_pair": (0, 1)}, "lane (poseidon_lane_only = 1)": {"poseidon_lane_only": (1, 0)},
          "one-wave / wave-pair (sponge_one_wave = 1)": {"sponge_one_wave": (1, 0)}}

@@ -1,5 +1,5 @@
 """Batched sum-check proving on the GPU: stark_sumcheck_prove_plain_batch_dev / stark_sumcheck_prove_mf_batch_dev (stark_mlwe_amd/csrc/
-sumcheck_batch.hpp over the device executor of sumcheck_impl.hpp).  Every proof of a batch must be byte-identical to the single-proof entry
+sumcheck_batch.hpp over the device executor of capi_sumcheck.hip).  Every proof of a batch must be byte-identical to the single-proof entry
 point on that witness alone, hence to the oracle's restatement of crates/channel/src/lib.rs, and accepted by the verifiers.  Tree labels are
 mixed within each batch; one batch has more instances than the chip has CUs; a second context runs the one-wave transcript form.
 Needs an MI355X: `pytest -m gpu`."""

@@ -1,4 +1,4 @@
-"""stark_sumcheck_verify_plain_batch / _mf_batch on the GPU (sumcheck_impl.hpp: the plan of sumcheck_verify_batch.hpp — device decode,
+"""stark_sumcheck_verify_plain_batch / _mf_batch on the GPU (capi_sumcheck.hip: the plan of sumcheck_verify_batch.hpp — device decode,
 transcript streams, one DS launch per tree depth, the check kernels, one download): every decision equals the single entry point's and
 the oracle's verify_plain / verify_mf (channel/src/lib.rs:1080-1128, :1176-1240) on that proof alone.  Needs an MI355X: `pytest -m gpu`."""
 import ctypes as C

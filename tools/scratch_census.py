@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """tools/scratch_census.py — where the spilled registers of the Poseidon throughput kernels are touched.
-Compiles capi_core.hip to gfx950 assembly (same flags as the library) and counts scratch_load / scratch_store instructions per loop
+Compiles capi_poseidon.hip to gfx950 assembly (same flags as the library) and counts scratch_load / scratch_store instructions per loop
 nesting depth (LLVM's "Loop Header: Depth=" / "in Loop ... Depth=" / "Parent Loop ... Depth=" block comments) next to the kernel's total
 instruction count.  A spill that sits outside the round loops is executed a handful of times per permutation."""
 import os, re, subprocess, sys, tempfile, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "stark_mlwe_amd", "csrc", "capi_core.hip")
+src = os.path.join(ROOT, "stark_mlwe_amd", "csrc", "capi_poseidon.hip")
 with tempfile.TemporaryDirectory() as td:
-    out = os.path.join(td, "core.s")
+    out = os.path.join(td, "poseidon.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-w", "-o", out, src])
     text = open(out).read()
 res = []
