@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstring>
 #include "poseidon_launch.hpp"
+#include "pow_table.hpp"   // stark_ctx::omega_tabs is destroyed with the context
 
 using namespace stark;
 
@@ -10,10 +11,10 @@ namespace stark {
 
 int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out) {
     if (bytes > ctx->scratch_bytes) {
-        if (ctx->scratch) { STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
-        STARK_HIP(ctx, hipMalloc(&ctx->scratch, bytes)); ctx->scratch_bytes = bytes;
+        if (ctx->scratch) STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->scratch_bytes = 0; STARK_HIP(ctx, ctx->scratch.alloc(bytes)); ctx->scratch_bytes = bytes;      // alloc frees the smaller block first
     }
-    *out = ctx->scratch; return STARK_OK;
+    *out = ctx->scratch.p; return STARK_OK;
 }
 
 // ---- caching device allocator (stark_ctx::pool_free) ----------------------------------------------------------
@@ -74,25 +75,26 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
     // int8 MFMA fragments of the dense matrices (t = 17), raw bytes in the same blob
     const size_t o_frag = blob.size(), frag_elems = (k.mds_frag.size() + sizeof(fr_t) - 1) / sizeof(fr_t);
     if (!k.mds_frag.empty()) { blob.resize(o_frag + 2 * frag_elems); memcpy((void*)(blob.data() + o_frag), k.mds_frag.data(), k.mds_frag.size()); memcpy((void*)(blob.data() + o_frag + frag_elems), k.mds_pre_frag.data(), k.mds_pre_frag.size()); }
-    STARK_HIP(ctx, hipMalloc((void**)&P->blob, blob.size() * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(P->blob, blob.data(), blob.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
+    STARK_HIP(ctx, P->blob.alloc(blob.size() * sizeof(fr_t)));
+    fr_t* const dev = P->blob.fr();
+    STARK_HIP(ctx, hipMemcpyAsync(dev, blob.data(), blob.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     P->dev.t = k.t; P->dev.rf = k.rf; P->dev.rp = k.rp;
-    P->dev.rc_full = P->blob + o_rcf; P->dev.rc_partial = P->blob + o_rcp; P->dev.lu = P->blob + o_lu; P->dev.lu_pre = P->blob + o_pre;
-    P->dev.row0 = P->blob + o_row0; P->dev.sparse = P->blob + o_sp; P->dev.mds = P->blob + o_mds; P->dev.mds_pre = P->blob + o_mpre; P->dev.gamma = P->blob + o_gam;
-    { const uint32_t* b29 = reinterpret_cast<const uint32_t*>(P->blob + o_29);
+    P->dev.rc_full = dev + o_rcf; P->dev.rc_partial = dev + o_rcp; P->dev.lu = dev + o_lu; P->dev.lu_pre = dev + o_pre;
+    P->dev.row0 = dev + o_row0; P->dev.sparse = dev + o_sp; P->dev.mds = dev + o_mds; P->dev.mds_pre = dev + o_mpre; P->dev.gamma = dev + o_gam;
+    { const uint32_t* b29 = reinterpret_cast<const uint32_t*>(dev + o_29);
       P->dev.lu29 = b29; P->dev.lu_pre29 = b29 + k.lu29.size(); P->dev.row0_29 = P->dev.lu_pre29 + k.lu_pre29.size();
       P->dev.sparse29 = P->dev.row0_29 + k.row0_29.size(); P->dev.gamma29 = P->dev.sparse29 + k.sparse29.size();
       P->dev.mds29 = P->dev.gamma29 + k.gamma29.size(); P->dev.mds_pre29 = P->dev.mds29 + k.mds29.size();
       const uint32_t* ch = P->dev.mds_pre29 + k.mds_pre29.size();
       P->dev.chain_a = k.chain_a.empty() ? nullptr : ch; P->dev.chain_g = k.chain_a.empty() ? nullptr : ch + k.chain_a.size(); P->dev.chain_w = k.chain_a.empty() ? nullptr : ch + k.chain_a.size() + k.chain_g.size(); }
-    P->dev.mds_frag = k.mds_frag.empty() ? nullptr : (const void*)(P->blob + o_frag); P->dev.mds_pre_frag = k.mds_frag.empty() ? nullptr : (const void*)(P->blob + o_frag + frag_elems);
+    P->dev.mds_frag = k.mds_frag.empty() ? nullptr : (const void*)(dev + o_frag); P->dev.mds_pre_frag = k.mds_frag.empty() ? nullptr : (const void*)(dev + o_frag + frag_elems);
     return STARK_OK;
 }
 static int32_t params_from_consts(stark_ctx* ctx, const host::PoseidonConsts& c, stark_params** out) {
     stark_params* P = new stark_params(); P->ctx = ctx; P->ref = c;
     int32_t rc = params_finish(ctx, P);
-    if (rc != STARK_OK) { if (P->blob) (void)hipFree(P->blob); delete P; return rc; }
+    if (rc != STARK_OK) { delete P; return rc; }
     *out = P; return STARK_OK;
 }
 int32_t ctx_transcript_params(stark_ctx* ctx, stark_params** out) {
@@ -140,10 +142,6 @@ static void ctx_teardown(stark_ctx* ctx) {
     stark::ntt_plans_free(ctx);
     if (ctx->tparams) stark_poseidon_params_free(ctx->tparams);
     for (auto& kv : ctx->merkle_params) stark_poseidon_params_free(kv.second);
-    for (auto& kv : ctx->tr_frames) (void)hipFree(kv.second);
-    if (ctx->leaf_init) (void)hipFree(ctx->leaf_init);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    for (auto& o : ctx->omega_tabs) { (void)hipFree(o.lo); (void)hipFree(o.hi); }
     for (auto& kv : ctx->pool_free) for (void* q : kv.second) (void)hipFree(q);
     for (auto& kv : ctx->pool_live) (void)hipFree(kv.first);                 // stark_alloc blocks the caller never freed (handles are gone by now)
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
@@ -151,7 +149,7 @@ static void ctx_teardown(stark_ctx* ctx) {
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;                                                               // the DevMem members and the power-table cache free themselves here, the device still current
 }
 namespace stark {
 void ctx_ref(stark_ctx* c) { ++c->live_handles; }
@@ -176,7 +174,7 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx) {
     ctx->pool_cached_bytes = 0;
     for (stark_ctx* a : ctx->aux) if (a) (void)stark_ctx_trim(a);
     stark::ntt_plans_free(ctx);                  // NTT plans with their direct twiddle / coset tables (up to 3*n*32 B per plan) are rebuilt on demand
-    if (ctx->scratch) { (void)hipFree(ctx->scratch); ctx->scratch = nullptr; ctx->scratch_bytes = 0; }
+    ctx->scratch.reset(); ctx->scratch_bytes = 0;
     return STARK_OK;
 }
 size_t stark_ctx_cached_bytes(stark_ctx_t* ctx) { return ctx ? ctx->pool_cached_bytes : 0; }
@@ -297,6 +295,6 @@ int32_t stark_poseidon_params_export(stark_params_t* p, int32_t* t, int32_t* rf,
     if (rc_partial) for (size_t i = 0; i < p->ref.rc_partial.size(); ++i) store_fr(rc_partial + 4 * i, p->ref.rc_partial[i]);
     return STARK_OK;
 }
-int32_t stark_poseidon_params_free(stark_params_t* p) { if (!p) return STARK_ERR_INVALID_ARG; if (p->blob) (void)hipFree(p->blob); delete p; return STARK_OK; }
+int32_t stark_poseidon_params_free(stark_params_t* p) { if (!p) return STARK_ERR_INVALID_ARG; delete p; return STARK_OK; }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <map>
 #include "poseidon_launch.hpp"
+#include "pow_table.hpp"
 #include "fri_dev.hpp"
 
 using namespace stark;
@@ -169,17 +170,9 @@ static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, con
 // Two-level power table of a domain generator, cached per (generator, size) — the reference's DomainH (deep_ali/src/lib.rs:109-125).
 static int32_t omega_table(stark_ctx* ctx, const fr_t& omega, size_t n_global, PowTable* out) {
     int bits = ilog2(n_global); if (bits < 1) bits = 1;
-    for (auto& o : ctx->omega_tabs) if (o.bits == bits && fr_eq(o.omega, omega)) { *out = PowTable{o.lo, o.hi, o.lo_bits}; return STARK_OK; }
     const int lo_bits = (bits + 1) / 2, hi_bits = bits - lo_bits + 1;
-    fr_t *lo = nullptr, *hi = nullptr;
-    STARK_HIP(ctx, hipMalloc((void**)&lo, ((size_t)1 << lo_bits) * sizeof(fr_t)));
-    if (hipMalloc((void**)&hi, ((size_t)1 << hi_bits) * sizeof(fr_t)) != hipSuccess) { (void)hipFree(lo); return ctx->fail(STARK_ERR_OOM, "omega table"); }
-    const uint64_t tot = (1ull << lo_bits) + (1ull << hi_bits);
-    hipLaunchKernelGGL(k_fill_pow_table<PallasFr>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, lo, hi, lo_bits, hi_bits, omega, host::h_one());
-    STARK_HIP(ctx, hipGetLastError());
-    if (ctx->omega_tabs.size() >= 16) { STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->omega_tabs[0].lo); (void)hipFree(ctx->omega_tabs[0].hi); ctx->omega_tabs.erase(ctx->omega_tabs.begin()); }
-    ctx->omega_tabs.push_back({bits, omega, lo, hi, lo_bits});
-    *out = PowTable{lo, hi, lo_bits}; return STARK_OK;
+    if (!ctx->omega_tabs) ctx->omega_tabs.reset(new PowCache(16));
+    return ctx->omega_tabs->get<PallasFr>(ctx, omega, bits, host::h_one(), lo_bits, hi_bits, out);
 }
 
 // deep_ali_merge_evals_blinded on device pointers (deep_ali/src/lib.rs:60-105).
@@ -243,28 +236,7 @@ static int32_t build_f0_dev_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, c
     return ali_merge_dev_impl(ctx, a, s, e, t, nullptr, host::h_zero(), omega, z, n0, f0, nullptr);
 }
 
-// fri_prove_queries + payload assembly + canonical encoding (fri.rs:355-466, 613-640).
-// Sources of the query phase (fri_plan.hpp): the device-resident state of one GPU, and the device transcript hasher.
-struct LocalSource : FriSource {
-    stark_ctx* ctx; stark_fri_state* S;
-    LocalSource(stark_ctx* c, stark_fri_state* s) : ctx(c), S(s) {}
-    int32_t layer(size_t l, const std::vector<size_t>& idx, std::vector<fr_t>& outv) override {
-        outv.resize(idx.size()); if (idx.empty()) return STARK_OK;
-        if (l >= S->f.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range");
-        for (size_t i : idx) if (i >= S->n[l]) return ctx->fail(STARK_ERR_INVALID_ARG, "layer index out of range");
-        DevBuf di, dout; STARK_HIP(ctx, di.alloc(ctx, idx.size() * 8)); STARK_HIP(ctx, dout.alloc(ctx, idx.size() * sizeof(fr_t)));
-        std::vector<uint64_t> ix(idx.begin(), idx.end());
-        STARK_HIP(ctx, hipMemcpyAsync(di.p, ix.data(), ix.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_gather, dim3((unsigned)((ix.size() + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t*)S->f[l], (const uint64_t*)di.p, (uint64_t)ix.size(), dout.fr());
-        STARK_HIP(ctx, hipGetLastError());
-        STARK_HIP(ctx, hipMemcpyAsync(outv.data(), dout.p, ix.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return STARK_OK;
-    }
-    int32_t digests(size_t tree, size_t level, const std::vector<size_t>& idx, std::vector<fr_t>& out) override {
-        if (tree >= S->trees.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "tree out of range");
-        out.resize(idx.size()); return stark_merkle_gather(S->trees[tree], (int32_t)level, idx.data(), idx.size(), (uint64_t*)out.data());
-    }
-};
+// The transcript hasher of the query phase (fri_plan.hpp) on the device.
 struct DeviceHasher : TrHasher {
     stark_ctx* ctx; explicit DeviceHasher(stark_ctx* c) : ctx(c) {}
     int32_t hash(const char* tag, const fr_t* fields, size_t k, size_t n, fr_t* out) override {
@@ -461,11 +433,9 @@ int32_t stark_fri_fold(stark_ctx_t* ctx, const uint64_t* f, size_t n, const uint
     if (!ctx || !z4 || (!f && n) || (!out && n)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     if (m < 2) return ctx->fail(STARK_ERR_INVALID_ARG, "m >= 2"); if (n % m) return ctx->fail(STARK_ERR_INVALID_ARG, "layer size must be divisible by m");
-    DevBuf df, dout; STARK_HIP(ctx, df.alloc(ctx, n * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n / m * sizeof(fr_t)));
-    if (n) STARK_HIP(ctx, hipMemcpyAsync(df.p, f, n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
+    DevBuf df, dout; STARK_HIP(ctx, df.upload(ctx, f, n * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n / m * sizeof(fr_t)));
     STARK_TRY(fold_dev(ctx, df.fr(), n, load_fr(z4), m, dout.fr()));
-    if (n) STARK_HIP(ctx, hipMemcpyAsync(out, dout.p, n / m * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
+    STARK_HIP(ctx, dout.download_sync(out, n / m * sizeof(fr_t))); return STARK_OK;
 }
 int32_t stark_fri_build_dev(stark_ctx_t* ctx, const uint64_t* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state_t** out) {
     if (!ctx || !f0 || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
@@ -475,7 +445,7 @@ int32_t stark_fri_build_dev(stark_ctx_t* ctx, const uint64_t* f0, size_t n0, con
 int32_t stark_fri_build(stark_ctx_t* ctx, const uint64_t* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state_t** out) {
     if (!ctx || !f0 || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    DevBuf d; STARK_HIP(ctx, d.alloc(ctx, n0 * sizeof(fr_t))); STARK_HIP(ctx, hipMemcpyAsync(d.p, f0, n0 * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
+    DevBuf d; STARK_HIP(ctx, d.upload(ctx, f0, n0 * sizeof(fr_t)));
     STARK_TRY(fri_build_impl(ctx, d.fr(), n0, schedule, L, seed_z, out)); return STARK_OK;
 }
 int32_t stark_fri_num_layers(stark_fri_state_t* s) { return s ? (int32_t)s->f.size() : STARK_ERR_INVALID_ARG; }
@@ -504,10 +474,10 @@ int32_t stark_ali_merge(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, 
     if (!ctx || !a || !s || !e || !t || !omega4 || !z4 || !f0 || (r_opt && !beta4)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     DevBuf d[6]; const uint64_t* src[5] = {a, s, e, t, r_opt};
-    for (int i = 0; i < 5; ++i) if (src[i]) { STARK_HIP(ctx, d[i].alloc(ctx, n * sizeof(fr_t))); STARK_HIP(ctx, hipMemcpyAsync(d[i].p, src[i], n * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream)); }
+    for (int i = 0; i < 5; ++i) if (src[i]) STARK_HIP(ctx, d[i].upload(ctx, src[i], n * sizeof(fr_t)));
     STARK_HIP(ctx, d[5].alloc(ctx, n * sizeof(fr_t)));
     STARK_TRY(stark_ali_merge_dev(ctx, (const uint64_t*)d[0].p, (const uint64_t*)d[1].p, (const uint64_t*)d[2].p, (const uint64_t*)d[3].p, r_opt ? (const uint64_t*)d[4].p : nullptr, beta4, omega4, z4, n, (uint64_t*)d[5].p, c_star4));
-    STARK_HIP(ctx, hipMemcpyAsync(f0, d[5].p, n * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
+    STARK_HIP(ctx, d[5].download_sync(f0, n * sizeof(fr_t))); return STARK_OK;
 }
 int32_t stark_build_f0_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, size_t n0, uint64_t* f0, uint64_t* aux7) {
     if (!ctx || !a || !s || !e || !t || !f0) return STARK_ERR_INVALID_ARG;
@@ -519,10 +489,10 @@ int32_t stark_build_f0(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, c
     if (!ctx || !a || !s || !e || !t || !f0) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     DevBuf d[5]; const uint64_t* src[4] = {a, s, e, t};
-    for (int i = 0; i < 4; ++i) { STARK_HIP(ctx, d[i].alloc(ctx, n0 * sizeof(fr_t))); STARK_HIP(ctx, hipMemcpyAsync(d[i].p, src[i], n0 * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream)); }
+    for (int i = 0; i < 4; ++i) STARK_HIP(ctx, d[i].upload(ctx, src[i], n0 * sizeof(fr_t)));
     STARK_HIP(ctx, d[4].alloc(ctx, n0 * sizeof(fr_t)));
     STARK_TRY(stark_build_f0_dev(ctx, (const uint64_t*)d[0].p, (const uint64_t*)d[1].p, (const uint64_t*)d[2].p, (const uint64_t*)d[3].p, n0, (uint64_t*)d[4].p, aux7));
-    STARK_HIP(ctx, hipMemcpyAsync(f0, d[4].p, n0 * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
+    STARK_HIP(ctx, d[4].download_sync(f0, n0 * sizeof(fr_t))); return STARK_OK;
 }
 
 int32_t stark_deep_fri_prove_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, const uint64_t* f0, size_t n0,
@@ -536,7 +506,7 @@ int32_t stark_deep_fri_prove(stark_ctx_t* ctx, const uint64_t* a, const uint64_t
     if (!ctx || !out || (!schedule && L) || (!f0 && (!a || !s || !e || !t))) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     DevBuf d[5]; const uint64_t* src[5] = {a, s, e, t, f0};
-    for (int i = 0; i < 5; ++i) if ((i < 4 && !f0) || (i == 4 && f0)) { STARK_HIP(ctx, d[i].alloc(ctx, n0 * sizeof(fr_t))); STARK_HIP(ctx, hipMemcpyAsync(d[i].p, src[i], n0 * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream)); }
+    for (int i = 0; i < 5; ++i) if ((i < 4 && !f0) || (i == 4 && f0)) STARK_HIP(ctx, d[i].upload(ctx, src[i], n0 * sizeof(fr_t)));
     return stark_deep_fri_prove_dev(ctx, (const uint64_t*)d[0].p, (const uint64_t*)d[1].p, (const uint64_t*)d[2].p, (const uint64_t*)d[3].p, f0 ? (const uint64_t*)d[4].p : nullptr, n0, schedule, L, r, seed_z, out);
 }
 int32_t stark_deep_fri_prove_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, size_t n0,

@@ -88,11 +88,12 @@ static int32_t ctx_leaf_init(stark_ctx* ctx, fr_t** out) {
             const fr_t k20 = fr_from_u64<PallasFr>(1ull << FR29_SBOX_SHIFT);     // the S-box outputs x4, x5 arrive divided by 2^20 (fr_pow5_r29)
             fr29_const_from<PallasFr>(host::h_mul(c.mds[(size_t)i * 17 + 4], k20), m45 + 9 * i); fr29_const_from<PallasFr>(host::h_mul(c.mds[(size_t)i * 17 + 5], k20), m45 + 9 * (17 + i));
         }
-        STARK_HIP(ctx, hipMalloc((void**)&ctx->leaf_init, sizeof(blob)));
-        STARK_HIP(ctx, hipMemcpyAsync(ctx->leaf_init, blob, sizeof(blob), hipMemcpyHostToDevice, ctx->stream));
+        DevMem d; STARK_HIP(ctx, d.alloc(sizeof(blob)));
+        STARK_HIP(ctx, hipMemcpyAsync(d.p, blob, sizeof(blob), hipMemcpyHostToDevice, ctx->stream));
         STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->leaf_init = std::move(d);
     }
-    *out = ctx->leaf_init; return STARK_OK;
+    *out = ctx->leaf_init.fr(); return STARK_OK;
 }
 
 namespace stark {
@@ -103,13 +104,12 @@ static int32_t tr_frame(stark_ctx* ctx, const char* tag, fr_t** dev, int* np, in
     auto it = ctx->tr_frames.find(key);
     if (it == ctx->tr_frames.end()) {
         std::vector<fr_t> fr; const int p = host::tr_hash_frame(tag, fr);
-        fr_t* d = nullptr; STARK_HIP(ctx, hipMalloc((void**)&d, fr.size() * sizeof(fr_t)));
-        STARK_HIP(ctx, hipMemcpyAsync(d, fr.data(), fr.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
+        DevMem d; STARK_HIP(ctx, d.alloc(fr.size() * sizeof(fr_t)));
+        STARK_HIP(ctx, hipMemcpyAsync(d.p, fr.data(), fr.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
         STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->tr_frames[key] = d; ctx->tr_frame_dims[key] = {p, (int)fr.size() - p};
-        it = ctx->tr_frames.find(key);
+        it = ctx->tr_frames.emplace(key, std::move(d)).first; ctx->tr_frame_dims[key] = {p, (int)fr.size() - p};
     }
-    *dev = it->second; *np = ctx->tr_frame_dims[key].first; *ns = ctx->tr_frame_dims[key].second; return STARK_OK;
+    *dev = it->second.fr(); *np = ctx->tr_frame_dims[key].first; *ns = ctx->tr_frame_dims[key].second; return STARK_OK;
 }
 static int32_t launch_tr_hash(stark_ctx* ctx, stark_params* tp, PoseidonForm form, const TrStream& T, fr_t* out_dev) {
     switch (form) {

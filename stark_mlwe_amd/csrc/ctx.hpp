@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/stark_mlwe.h"
@@ -12,7 +13,7 @@
 #include "ntt_dev.hpp"
 #include "fri_plan.hpp"
 
-namespace stark { struct NttPlan; }
+namespace stark { struct NttPlan; struct PowCache; }
 
 // Handles (trees, FRI states, plans, transcripts, caller-made parameter sets) keep their context alive: stark_ctx_destroy with live handles
 // only marks the context; the LAST handle freed tears it down.  `CtxRef` is the FIRST member of every handle type, so it is destroyed last — after
@@ -26,12 +27,30 @@ struct CtxRef {
     ~CtxRef() { if (c) stark::ctx_unref(c); }
 };
 
+namespace stark {
+// Owner of ONE unpooled device allocation (hipMalloc on alloc, hipFree on reset / destruction; move-only): the long-lived tables and constants.
+// They stay outside the context's pool, so stark_ctx_trim and the out-of-memory retry of ctx_alloc never touch them.  An owner is destroyed
+// with its context's device current (see ctx_teardown); DevBuf below is the pooled, per-call counterpart.
+struct DevMem {
+    void* p = nullptr;
+    DevMem() = default; DevMem(const DevMem&) = delete; DevMem& operator=(const DevMem&) = delete;
+    DevMem(DevMem&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    ~DevMem() { reset(); }
+    hipError_t alloc(size_t bytes) { reset(); const hipError_t e = hipMalloc(&p, bytes); if (e != hipSuccess) p = nullptr; return e; }
+    void reset() { if (p) { (void)hipFree(p); p = nullptr; } }
+    explicit operator bool() const { return p != nullptr; }
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+    fr_t* fr() const { return as<fr_t>(); }
+};
+}  // namespace stark
+
 struct stark_params {
     CtxRef ref_;                         // bound only for parameter sets handed to the caller (the context's own cached sets do not pin it)
     stark_ctx* ctx = nullptr;
     stark::host::PoseidonConsts ref;     // reference-form constants (as uploaded / derived)
     stark::host::KernelConsts kc;        // kernel-form constants
-    stark::fr_t* blob = nullptr;         // one device allocation holding all tables
+    stark::DevMem blob;                  // one device allocation holding all tables
     stark::PoseidonDev dev{};            // device pointers into `blob`
 };
 
@@ -51,11 +70,11 @@ struct stark_ctx {
     // lazily created constants
     stark_params* tparams = nullptr;                 // transcript params (t=17, "POSEIDON-T17-X5-TRANSCRIPT")
     std::map<int, stark_params*> merkle_params;      // poseidon_params_for_width(t)
-    stark::fr_t* leaf_init = nullptr;                // 17-lane template of hash_leaf_pair (device)
-    std::map<std::string, stark::fr_t*> tr_frames;   // per-tag transcript prefix/suffix frames (device): [prefix.., suffix..]
+    stark::DevMem leaf_init;                         // 17-lane template of hash_leaf_pair (device)
+    std::map<std::string, stark::DevMem> tr_frames;  // per-tag transcript prefix/suffix frames (device): [prefix.., suffix..]
     std::map<std::string, std::pair<int, int>> tr_frame_dims;
     // scratch
-    void* scratch = nullptr; size_t scratch_bytes = 0;
+    stark::DevMem scratch; size_t scratch_bytes = 0;
     // NTT plans
     std::map<uint64_t, stark::NttPlan*> plans;
     // Caching device allocator for the library's own temporaries, layers and tree levels: a block released here is reused by a
@@ -68,8 +87,7 @@ struct stark_ctx {
     // host-side caches of values that depend only on their key
     struct ZKey { uint64_t seed; size_t level, size; bool operator<(const ZKey& o) const { return seed != o.seed ? seed < o.seed : (level != o.level ? level < o.level : size < o.size); } };
     std::map<ZKey, stark::fr_t> z_cache;                                // fri_sample_z_ell(seed_z, level, size)  (fri.rs:59-82)
-    struct OmegaTab { int bits; stark::fr_t omega; stark::fr_t* lo; stark::fr_t* hi; int lo_bits; };
-    std::vector<OmegaTab> omega_tabs;                                  // two-level power tables of a domain generator (DomainH, deep_ali/src/lib.rs:109-125)
+    std::unique_ptr<stark::PowCache> omega_tabs;                       // two-level power tables of a domain generator (DomainH, deep_ali/src/lib.rs:109-125); pow_table.hpp, made on first use
     void* pinned = nullptr; size_t pinned_bytes = 0;                   // small pinned staging area for async uploads / downloads
 
     // tuning / diagnostic options (stark_ctx_set_option): explicit API state, never the environment
