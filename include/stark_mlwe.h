@@ -196,10 +196,29 @@ int32_t stark_deep_fri_prove_dev(stark_ctx_t* ctx, const uint64_t* a, const uint
  * channel/benches/end_to_end.rs:229-309).  a, s, e, t: HOST arrays of `batch` DEVICE pointers; out: host array of `batch` proof handles
  * (all NULL on failure).  The serial column sponges of build_f0 (fri.rs:548-557) bound a single prove and keep four waves of the chip
  * busy; the 4 * batch chains of a batch are independent and run in ONE launch, so the stage costs what it costs for one trace.
- * Every proof is byte-identical to stark_deep_fri_prove_dev on that trace alone.  stage_ms(0) of each proof = the shared sponge stage
- * of the whole batch + that trace's merge. */
+ * The tails (merge, commit phase, query phase) of the traces then run side by side: the batch is cut into passes of at most
+ * "prove_batch_max_rows" rows (option, default 2^22; a pass of one trace is the single tail), and every step of a pass is one launch
+ * for all its traces.  Option "prove_batch_workers" = 1 restores the earlier tail (trace after trace on four worker contexts).
+ * Every proof is byte-identical to stark_deep_fri_prove_dev on that trace alone.  stage_ms 0 / 1 / 2 of a proof are its pass's shared
+ * stage times: the sponge stage of the whole batch + the pass's merge, the pass's commit phase, the pass's query phase.  They are HOST times
+ * between the steps: in a pass of two or more traces merge and commit phase only enqueue their launches, so stages 0 and 1 count enqueueing
+ * and stage 2, which holds the pass's first synchronisation, absorbs the device time of all three. */
 int32_t stark_deep_fri_prove_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t,
                                        size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out);
+/* The batch forms of "prove given f0", of the commit phase and of the merge.  Tables (f0, a, s, e, t, r_opt) are HOST arrays of `batch`
+ * DEVICE pointers.  Element i of every result equals what the single call returns for trace i alone, byte for byte:
+ * stark_deep_fri_prove_dev with f0; the L + 1 roots of stark_fri_build_dev (roots[(i (L + 1) + l) * 4 ..]); stark_ali_merge_dev (one omega4
+ * for the batch, z and beta per trace on the host, r_opt NULL or per trace with NULL entries allowed, c_star NULL or batch x 4 on the host).
+ * The traces of a pass (see stark_deep_fri_prove_batch_dev) run every step in one launch.  batch == 0 returns STARK_OK.
+ * STARK_ERR_INVALID_ARG, before any launch: a null ctx, table or entry; a z[i] inside H; n0 not a power of two or <= 1 (the prove); a null
+ * schedule with L > 0 or a schedule that does not divide n0.  On any error every out[i] is NULL. */
+int32_t stark_deep_fri_prove_f0_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z,
+                                          stark_proof_t** out);
+int32_t stark_fri_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z,
+                                   uint64_t* roots /* host, batch x (L+1) x 4 */);
+int32_t stark_ali_merge_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t,
+                                  const uint64_t* const* r_opt, const uint64_t* beta /* batch x 4, host */, const uint64_t* omega4, const uint64_t* z /* batch x 4, host */,
+                                  size_t n, uint64_t* const* f0, uint64_t* c_star /* batch x 4, host, may be NULL */);
 size_t  stark_proof_len(stark_proof_t* p);
 int32_t stark_proof_bytes(stark_proof_t* p, uint8_t* out);
 size_t  stark_proof_size_estimate(stark_proof_t* p);                /* deep_fri_proof_size_bytes, fri.rs:764-805 */

@@ -304,6 +304,26 @@ pub mod fri {
             (bytes, est)
         }).collect()
     }
+    /// "Prove given f0" for many vectors in one call: `f0s[p]` = DEVICE pointer of an n0-element f0; every proof is byte-identical to
+    /// `deep_fri_prove` with that f0 alone.  The commit and query phases of the traces run side by side (one launch per step and pass).
+    pub unsafe fn deep_fri_prove_f0_batch_dev(ctx: &Ctx, f0s: &[*const u64], n0: usize, schedule: &[usize], r: usize, seed_z: u64) -> Vec<(Vec<u8>, usize)> {
+        let mut raw: Vec<*mut stark_proof_t> = vec![ptr::null_mut(); f0s.len()];
+        ctx.chk(stark_deep_fri_prove_f0_batch_dev(ctx.raw, f0s.len(), f0s.as_ptr(), n0, schedule.as_ptr(), schedule.len(), r, seed_z, raw.as_mut_ptr()));
+        raw.into_iter().map(|h| {
+            let mut bytes = vec![0u8; stark_proof_len(h)];
+            ctx.chk(stark_proof_bytes(h, bytes.as_mut_ptr()));
+            let est = stark_proof_size_estimate(h);
+            stark_proof_free(h);
+            (bytes, est)
+        }).collect()
+    }
+    /// The L + 1 layer roots of `fri_build_transcript` for each DEVICE vector of `f0s`: `roots[p][l]` = four limbs.
+    pub unsafe fn fri_commit_batch_dev(ctx: &Ctx, f0s: &[*const u64], n0: usize, schedule: &[usize], seed_z: u64) -> Vec<Vec<[u64; 4]>> {
+        let per = schedule.len() + 1;
+        let mut flat = vec![0u64; 4 * per * f0s.len()];
+        ctx.chk(stark_fri_commit_batch_dev(ctx.raw, f0s.len(), f0s.as_ptr(), n0, schedule.as_ptr(), schedule.len(), seed_z, flat.as_mut_ptr()));
+        flat.chunks(4 * per).map(|t| t.chunks(4).map(|c| [c[0], c[1], c[2], c[3]]).collect()).collect()
+    }
     /// `pub fn deep_fri_verify(params: &DeepFriParams, proof: &DeepFriProof) -> bool` — fri.rs:643-762, over the canonical bytes.
     pub fn deep_fri_verify(ctx: &Ctx, schedule: &[usize], r: usize, seed_z: u64, proof_bytes: &[u8]) -> bool {
         let mut ok = 0i32;

@@ -323,7 +323,7 @@ class Context:
         self._chk(self.lib.stark_ctx_sync(self.h))
 
     def set_option(self, key: str, value: int):
-        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "fri_side_pair"."""
+        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "fri_side_pair", "prove_batch_max_rows", "prove_batch_workers"."""
         self._chk(self.lib.stark_ctx_set_option(self.h, key.encode(), value))
 
     def trim(self):
@@ -496,6 +496,9 @@ class Context:
         cols = [(C.c_void_p * B)(*[int(tr[c]) for tr in traces]) for c in range(4)]
         out = (C.c_void_p * B)()
         self._chk(self.lib.stark_deep_fri_prove_batch_dev(self.h, B, cols[0], cols[1], cols[2], cols[3], n0, _ptr(sch), len(sch), params.r, params.seed_z, out))
+        return self._proofs_out(out, B)
+
+    def _proofs_out(self, out, B):
         res = []
         for p in range(B):
             h = C.c_void_p(out[p])
@@ -506,6 +509,40 @@ class Context:
             finally:
                 self.lib.stark_proof_free(h)
         return res
+
+    def deep_fri_prove_f0_batch_dev(self, f0s, n0, params: DeepFriParams):
+        """`f0s`: DEVICE pointers (ints) of independent n0-element f0 vectors -> list of (proof bytes, size estimate, stage ms), each equal to
+        deep_fri_prove(f0=...) of that vector alone; merge-free tails side by side (stark_deep_fri_prove_f0_batch_dev)."""
+        B = len(f0s)
+        sch = np.ascontiguousarray(params.schedule, dtype=np.uint64)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in f0s])
+        out = (C.c_void_p * max(B, 1))()
+        self._chk(self.lib.stark_deep_fri_prove_f0_batch_dev(self.h, B, tab, n0, _ptr(sch), len(sch), params.r, params.seed_z, out))
+        return self._proofs_out(out, B)
+
+    def fri_commit_batch_dev(self, f0s, n0, schedule, seed_z):
+        """The L + 1 layer roots of fri_build_transcript for each of the DEVICE vectors `f0s` (ints), as a (B, L + 1, 4) array
+        (stark_fri_commit_batch_dev)."""
+        B = len(f0s)
+        sch = np.ascontiguousarray(schedule, dtype=np.uint64)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in f0s])
+        roots = np.zeros((B, len(sch) + 1, 4), np.uint64)
+        self._chk(self.lib.stark_fri_commit_batch_dev(self.h, B, tab, n0, _ptr(sch), len(sch), seed_z, _ptr(roots)))
+        return roots
+
+    def ali_merge_batch_dev(self, traces, omega, zs, n, f0s, r_opts=None, betas=None, want_c_star=True):
+        """deep_ali_merge_evals(_blinded) of B traces in one launch: `traces` = list of (a, s, e, t) DEVICE pointers, `f0s` the B DEVICE outputs,
+        `zs` (B, 4) host, `r_opts` None or a list of DEVICE pointers / None per trace with `betas` (B, 4) host.  Returns c* as (B, 4) or None
+        (stark_ali_merge_batch_dev)."""
+        B = len(traces)
+        cols = [(C.c_void_p * max(B, 1))(*[int(tr[c]) for tr in traces]) for c in range(4)]
+        outs = (C.c_void_p * max(B, 1))(*[int(x) for x in f0s])
+        rt = None if r_opts is None else (C.c_void_p * max(B, 1))(*[None if x is None else int(x) for x in r_opts])
+        bt = None if betas is None else _arr(betas)
+        z = _arr(zs)
+        cs = np.zeros((B, 4), np.uint64) if want_c_star else None
+        self._chk(self.lib.stark_ali_merge_batch_dev(self.h, B, cols[0], cols[1], cols[2], cols[3], rt, _ptr(bt), _ptr(_arr(omega)), _ptr(z), n, outs, _ptr(cs)))
+        return cs
 
     def deep_fri_verify(self, params: DeepFriParams, proof: bytes) -> bool:
         """deep_fri_verify (fri.rs:643-762) on canonical proof bytes."""

@@ -205,6 +205,8 @@ static const OptionDef kOptions[] = {
     {"merkle_node16_pair", [](stark_ctx::Options& o, int64_t v) -> const char* { o.merkle_node16_pair = v != 0; return nullptr; }},
     {"fri_side_pair", [](stark_ctx::Options& o, int64_t v) -> const char* { o.fri_side_pair = v != 0; return nullptr; }},
     {"sumcheck_verify_batch_max_slots", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1) return "at least 1"; o.sumcheck_verify_batch_max_slots = (size_t)v; return nullptr; }},
+    {"prove_batch_max_rows", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.prove_batch_max_rows = (size_t)v; return nullptr; }},
+    {"prove_batch_workers", [](stark_ctx::Options& o, int64_t v) -> const char* { o.prove_batch_workers = v != 0; return nullptr; }},
 };
 extern "C" {
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value) {

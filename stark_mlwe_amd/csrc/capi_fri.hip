@@ -6,9 +6,11 @@
 #include <thread>
 #include <cstring>
 #include <map>
+#include <memory>
 #include "poseidon_launch.hpp"
 #include "pow_table.hpp"
 #include "fri_dev.hpp"
+#include "fri_batch.hpp"
 
 using namespace stark;
 
@@ -62,17 +64,7 @@ static int32_t sample_z(stark_ctx* ctx, uint64_t seed_z, size_t level, size_t do
     auto it = ctx->z_cache.find(key);
     if (it != ctx->z_cache.end()) { *z = it->second; return STARK_OK; }
     fr_t fused; STARK_TRY(tr_hash_host1(ctx, "FRI/z/l", {host::h_u64(seed_z), host::h_u64(level), host::h_u64(domain_size)}, &fused));
-    uint8_t seed[32]; host::h_to_bytes_le(fused, seed);
-    host::ChaCha12Rng rng(seed);
-    const fr_t one = host::h_one();
-    for (size_t tries = 0;;) {
-        fr_t cand = host::h_u64(rng.next_u64());
-        if (!fr_is_zero(cand) && !fr_eq(fr_pow_u64<PallasFr>(cand, domain_size), one)) { *z = cand; break; }
-        if (++tries >= 1000) {
-            fr_t fb = host::h_u64(seed_z + (uint64_t)level + 7);
-            *z = !fr_eq(fr_pow_u64<PallasFr>(fb, domain_size), one) ? fb : host::h_u64(11); break;
-        }
-    }
+    *z = fri_z_from_fused(fused, seed_z, level, domain_size);
     ctx->z_cache[key] = *z; return STARK_OK;
 }
 
@@ -254,8 +246,13 @@ static int32_t shape_of_state(stark_ctx* ctx, stark_fri_state* S, size_t n0, Fri
 struct MemoHasher : TrHasher {
     TrHasher& inner; std::map<std::string, std::vector<fr_t>> memo;
     explicit MemoHasher(TrHasher& h) : inner(h) {}
+    static std::string key_of(const char* tag, const fr_t* fields, size_t k, size_t n) {
+        std::string key(tag); key.push_back('\0'); key.append((const char*)&k, sizeof(k)); key.append((const char*)fields, k * n * sizeof(fr_t)); return key;
+    }
+    // a result computed elsewhere (the batched query phase hashes the seeds of all its proofs in one launch)
+    void preload(const char* tag, const fr_t* fields, size_t k, size_t n, const fr_t* out) { memo[key_of(tag, fields, k, n)] = std::vector<fr_t>(out, out + n); }
     int32_t hash(const char* tag, const fr_t* fields, size_t k, size_t n, fr_t* out) override {
-        std::string key(tag); key.push_back('\0'); key.append((const char*)&k, sizeof(k)); key.append((const char*)fields, k * n * sizeof(fr_t));
+        std::string key = key_of(tag, fields, k, n);
         auto it = memo.find(key);
         if (it == memo.end()) { std::vector<fr_t> v(n); int32_t rc = inner.hash(tag, fields, k, n, v.data()); if (rc) return rc; it = memo.emplace(std::move(key), std::move(v)).first; }
         memcpy((void*)out, it->second.data(), n * sizeof(fr_t)); return 0;
@@ -343,10 +340,270 @@ static int32_t prove_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr
     *out = P; return STARK_OK;
 }
 
+// The tail of ONE trace of a batch prove on context c, its challenge z known: merge into f0buf (n0 elements, c's memory), commit phase, query phase.
+// stage_ms: shared_ms (the batch's sponge stage) + the merge, the commit phase, the query phase.  Used by the worker contexts and by a pass of one trace.
+static int32_t prove_tail_single(stark_ctx* c, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t& omega, const fr_t& z, fr_t* f0buf, size_t n0,
+                                 const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, stark_proof** out) {
+    auto u0 = Clock::now();
+    STARK_TRY(ali_merge_dev_impl(c, a, s, e, t, nullptr, host::h_zero(), omega, z, n0, f0buf, nullptr));
+    auto u1 = Clock::now();
+    stark_fri_state* S = nullptr; STARK_TRY(fri_build_impl(c, f0buf, n0, schedule, L, seed_z, &S));
+    auto u2 = Clock::now();
+    stark_proof* P = new stark_proof();
+    { int32_t rc = prove_queries_encode(c, S, n0, r, P); delete S; if (rc) { delete P; return rc; } }
+    auto u3 = Clock::now();
+    P->ms[0] = shared_ms + ms_between(u0, u1); P->ms[1] = ms_between(u1, u2); P->ms[2] = ms_between(u2, u3);
+    *out = P; return STARK_OK;
+}
+
+// ---- the side-by-side tail of the batched provers: merge, commit phase and query phase of a pass of traces (fri_batch.hpp) ----------------
+// The executor of FriBatchCommit on the device.  Everything it allocates is pooled and returns to the pool with it; the folds run on the
+// context's stream, the commitments on the current one (the side stream between fork() and side(false)).
+struct FriDevExec {
+    stark_ctx* ctx; hipStream_t main_st, side_st = nullptr, cur; std::vector<void*> blocks; bool forked = false;
+    // Host sources of the uploads: every upload goes out of a copy the executor owns, so a caller's table may die as soon as upload() returns.  The
+    // copies live until the executor does; if it is destroyed with uploads enqueued since the caller's last synchronisation (an early error return),
+    // it synchronises the stream first.
+    std::vector<std::unique_ptr<uint8_t[]>> staged; bool pending = false;
+    explicit FriDevExec(stark_ctx* c) : ctx(c), main_st(c->stream), cur(c->stream) {}
+    FriDevExec(const FriDevExec&) = delete; FriDevExec& operator=(const FriDevExec&) = delete;
+    ~FriDevExec() { if (forked) (void)hipStreamSynchronize(side_st); if (pending) (void)hipStreamSynchronize(main_st); for (void* p : blocks) ctx_release(ctx, p); }
+    void synced() { pending = false; }                  // the caller has synchronised the context's stream
+    int32_t alloc(size_t bytes, void** out) { STARK_TRY(ctx_alloc(ctx, bytes, out)); blocks.push_back(*out); return STARK_OK; }
+    int32_t upload(void* dst, const void* src, size_t bytes) {
+        if (!bytes) return STARK_OK;
+        staged.emplace_back(new uint8_t[bytes]); memcpy(staged.back().get(), src, bytes);
+        pending = true;
+        STARK_HIP(ctx, hipMemcpyAsync(dst, staged.back().get(), bytes, hipMemcpyHostToDevice, main_st)); return STARK_OK;
+    }
+    template <class T> int32_t put(const std::vector<T>& h, T** out) {
+        void* p = nullptr; STARK_TRY(alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p));
+        if (!h.empty()) STARK_TRY(upload(p, h.data(), h.size() * sizeof(T)));
+        *out = (T*)p; return STARK_OK;
+    }
+    int32_t zpows(const fr_t& z, size_t m, fr_t* zp) { return zpows_launch(ctx, main_st, z, m, zp); }
+    int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out) { return fold_launch(ctx, main_st, f, n, zp, m, out); }
+    int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h) { return leaf_pair_hash_on(ctx, cur, f, f_next, n, m, h); }
+    int32_t pair_level(size_t arity, const DsBatchPairStream& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
+    int32_t ds_level(size_t arity, const DsBatchStream& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
+    int32_t fork() {
+        STARK_TRY(ctx_side_stream(ctx, &side_st));
+        STARK_HIP(ctx, hipEventRecord(ctx->ev_fork, main_st)); STARK_HIP(ctx, hipStreamWaitEvent(side_st, ctx->ev_fork, 0));
+        forked = true; return STARK_OK;
+    }
+    void side(bool on) { cur = on && side_st ? side_st : main_st; }
+    int32_t join() {
+        if (!forked) return STARK_OK;
+        STARK_HIP(ctx, hipEventRecord(ctx->ev_fork, side_st)); STARK_HIP(ctx, hipStreamWaitEvent(main_st, ctx->ev_fork, 0));
+        forked = false; return STARK_OK;
+    }
+};
+typedef FriBatchCommit<FriDevExec> FriDevBatch;
+constexpr size_t kMaxPassTraces = 32768;             // blockIdx.y of the merge and copy kernels is the trace
+// How many traces of n0 rows go into one pass (option "prove_batch_max_rows").
+static size_t pass_traces(const stark_ctx* ctx, size_t n0) { return std::min(std::max<size_t>(ctx->opt.prove_batch_max_rows / std::max<size_t>(n0, 1), 1), kMaxPassTraces); }
+// What the entry points check before any launch: the schedule divides n0 layer by layer (fri.rs:150).
+static bool schedule_divides(size_t n0, const size_t* schedule, size_t L) {
+    size_t n = n0; for (size_t l = 0; l < L; ++l) { if (schedule[l] < 2 || n % schedule[l]) return false; n /= schedule[l]; } return n0 != 0;
+}
+// Shapes, challenges and buffers of a pass; everything that may upload constants (and synchronise doing so) runs here, before the first launch.
+static int32_t batch_commit_begin(stark_ctx* ctx, FriDevBatch& C, size_t Bp, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z) {
+    if (!schedule_divides(n0, schedule, L)) return ctx->fail(STARK_ERR_INVALID_ARG, "schedule not dividing domain size");
+    std::vector<fr_t> z(L); { size_t n = n0; for (size_t l = 0; l < L; ++l) { STARK_TRY(sample_z(ctx, seed_z, l, n, &z[l])); n /= schedule[l]; } }
+    std::string err; const int32_t rc = C.init(Bp, n0, schedule, L, z.data(), err);
+    if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, err); if (rc == -2) return ctx->fail(STARK_ERR_UNSUPPORTED, err); if (rc) return rc;
+    stark_params* p = nullptr; STARK_TRY(ctx_transcript_params(ctx, &p));
+    for (size_t a : C.arity) STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(a), &p));
+    return STARK_OK;
+}
+// Layer 0 of a pass from a host table of per-trace device pointers: one copy kernel.
+static int32_t batch_fill_layer0(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, const uint64_t* const* f0) {
+    std::vector<const fr_t*> h(C.Bp); for (size_t b = 0; b < C.Bp; ++b) h[b] = as_fr(f0[b]);
+    const fr_t** d = nullptr; STARK_TRY(X.put(h, &d));
+    hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)((C.n[0] + 255) / 256), (unsigned)C.Bp), dim3(256), 0, ctx->stream, (const fr_t* const*)d, (uint64_t)C.n[0], C.f[0]);
+    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+}
+// deep_ali_merge_evals_blinded of Bp <= kMaxPassTraces traces over one domain of n points in one launch (k_ali_merge_batch).  Tables, z and beta are
+// device arrays; the result goes to out_base + b n or to out_ptrs[b]; c_star_dev (optional) receives c*[b] through one batched reduction.
+static int32_t ali_merge_batch_launch(stark_ctx* ctx, FriDevExec& X, size_t Bp, const fr_t* const* a, const fr_t* const* s, const fr_t* const* e, const fr_t* const* t,
+                                      const fr_t* const* r_opt, const fr_t* beta, const fr_t& omega, const fr_t* z, size_t n, fr_t* out_base, fr_t* const* out_ptrs, fr_t* c_star_dev) {
+    PowTable wp; STARK_TRY(omega_table(ctx, omega, n, &wp));
+    const unsigned block = 256; const uint64_t lanes = (n + ALI_K - 1) / ALI_K; const unsigned grid = (unsigned)((lanes + block - 1) / block);
+    const fr_t w_step = fr_pow_u64<PallasFr>(omega, (uint64_t)grid * block);
+    fr_t* sums = nullptr; if (c_star_dev) { void* q = nullptr; STARK_TRY(X.alloc(Bp * grid * sizeof(fr_t), &q)); sums = (fr_t*)q; }
+    hipLaunchKernelGGL(k_ali_merge_batch<PallasFr>, dim3(grid, (unsigned)Bp), dim3(block), 0, ctx->stream, a, s, e, t, r_opt, beta, wp, w_step, fr_inv<PallasFr>(w_step), z, (uint64_t)n, out_base, out_ptrs, sums);
+    STARK_HIP(ctx, hipGetLastError());
+    if (c_star_dev) {                                   // c*[b] = (1/n) * sum of trace b's block partials (lib.rs:44, :94)
+        hipLaunchKernelGGL(k_sum_single_block<PallasFr>, dim3((unsigned)Bp), dim3(256), 0, ctx->stream, (const fr_t*)sums, (uint64_t)grid, fr_inv<PallasFr>(host::h_u64(n)), c_star_dev);
+        STARK_HIP(ctx, hipGetLastError());
+    }
+    return STARK_OK;
+}
+// The query phase of every proof of a pass (prove_queries_encode, side by side).  FOUR host synchronisations, whatever Bp: the roots; the Bp
+// "FRI/seed" hashes (one launch); the Bp * r * L "FRI/index" hashes (one launch); the opened values of all proofs (one gather launch).  The seeds
+// are pre-loaded into each proof's MemoHasher, so fri_plan_make and assemble_proof run per proof without touching the device (the reseed of
+// fri.rs:379-381 cannot occur with power-of-two layers; it alone would go through the single hasher: ReseedOnlyHasher).
+// What a proof's MemoHasher of the batched query phase may still ask the device for: the reseed alone.  Anything else was to be pre-loaded; a request
+// for it means the pre-loaded keys no longer match what fri_plan.hpp asks for, and is an error rather than a silent launch and synchronisation per proof
+// (the constant of four synchronisations per pass rests on this).
+struct ReseedOnlyHasher : TrHasher {
+    DeviceHasher dev; explicit ReseedOnlyHasher(stark_ctx* c) : dev(c) {}
+    int32_t hash(const char* tag, const fr_t* fields, size_t k, size_t n, fr_t* out) override {
+        if (strcmp(tag, "FRI/index") || k != 2 || n != 1) return dev.ctx->fail(STARK_ERR_HIP, std::string("batched query phase: hash '") + tag + "' was not pre-loaded");
+        return dev.hash(tag, fields, k, n, out);
+    }
+};
+static int32_t batch_queries(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, size_t n0, size_t r, stark_proof** out) {
+    const size_t Bp = C.Bp, L = C.L, R = L + 1, q = r * L;
+    std::vector<fr_t> rl(R * Bp), rt(R * Bp), seed(Bp), in(3 * q * Bp), idx(q * Bp);
+    STARK_HIP(ctx, hipMemcpyAsync(rl.data(), C.roots, rl.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t b = 0; b < Bp; ++b) for (size_t l = 0; l < R; ++l) rt[b * R + l] = rl[l * Bp + b];
+    fr_t *d_rt = nullptr, *d_seed = nullptr; STARK_TRY(X.put(rt, &d_rt)); { void* p = nullptr; STARK_TRY(X.alloc(Bp * sizeof(fr_t), &p)); d_seed = (fr_t*)p; }
+    STARK_TRY(tr_hash_dev(ctx, "FRI/seed", d_rt, R, Bp, d_seed));                                                        // fs_seed_from_roots, fri.rs:178
+    STARK_HIP(ctx, hipMemcpyAsync(seed.data(), d_seed, Bp * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (q) {                                                                                                             // the index seeds of all (proof, query, layer): fri.rs:374, :189-191
+        for (size_t b = 0; b < Bp; ++b) for (size_t j = 0; j < r; ++j) for (size_t l = 0; l < L; ++l) { fr_t* p = &in[3 * (b * q + j * L + l)]; p[0] = seed[b]; p[1] = host::h_u64(l); p[2] = host::h_u64(j); }
+        fr_t *d_in = nullptr, *d_idx = nullptr; STARK_TRY(X.put(in, &d_in)); { void* p = nullptr; STARK_TRY(X.alloc(q * Bp * sizeof(fr_t), &p)); d_idx = (fr_t*)p; }
+        STARK_TRY(tr_hash_dev(ctx, "FRI/index", d_in, 3, q * Bp, d_idx));
+        STARK_HIP(ctx, hipMemcpyAsync(idx.data(), d_idx, q * Bp * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ReseedOnlyHasher H0(ctx); std::vector<std::unique_ptr<MemoHasher>> H(Bp); std::vector<FriPlan> plan(Bp);
+    std::vector<size_t> row0(Bp + 1, 0);
+    std::vector<const fr_t*> base; std::map<const fr_t*, uint32_t> slot; std::vector<uint32_t> src; std::vector<uint64_t> ix, row;
+    for (size_t b = 0; b < Bp; ++b) {
+        H[b].reset(new MemoHasher(H0));
+        H[b]->preload("FRI/seed", &rt[b * R], R, 1, &seed[b]);
+        if (q) H[b]->preload("FRI/index", &in[3 * q * b], 3, q, &idx[q * b]);
+        plan[b].r = r;
+        { std::string err; if (!plan[b].shape.make(n0, C.sched.data(), L, &rt[b * R], err)) return ctx->fail(STARK_ERR_INVALID_ARG, err); }
+        { int32_t rc = fri_plan_make(plan[b], *H[b]); if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: bad index"); if (rc) return rc; }
+        for (const FriRequest& rq : plan[b].req) {
+            const fr_t* p = nullptr; size_t len = 0;
+            if (rq.kind == 0) { if (rq.which > L) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range"); p = C.layer_at(b, rq.which); len = C.n[rq.which]; }
+            else {
+                if (rq.which > L || rq.level >= C.trees[rq.which].levels.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
+                p = C.level_at(b, rq.which, rq.level); len = C.trees[rq.which].lens[rq.level];
+            }
+            if (rq.index >= len) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: opening index out of range");
+            auto it = slot.emplace(p, (uint32_t)base.size()).first;
+            if (it->second == base.size()) base.push_back(p);
+            src.push_back(it->second); ix.push_back(rq.index); row.push_back(row.size());
+        }
+        row0[b + 1] = row.size();
+    }
+    const size_t k = row.size();
+    std::vector<fr_t> vals(k);
+    if (k) {                                                                                                             // ONE gather over all proofs' requests, one download
+        const fr_t** d_base = nullptr; uint32_t* d_src = nullptr; uint64_t *d_ix = nullptr, *d_row = nullptr; void* d_out = nullptr;
+        STARK_TRY(X.put(base, &d_base)); STARK_TRY(X.put(src, &d_src)); STARK_TRY(X.put(ix, &d_ix)); STARK_TRY(X.put(row, &d_row)); STARK_TRY(X.alloc(k * sizeof(fr_t), &d_out));
+        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)d_base, (const uint32_t*)d_src, (const uint64_t*)d_ix, (const uint64_t*)d_row, (uint64_t)k, (fr_t*)d_out);
+        STARK_HIP(ctx, hipGetLastError());
+        STARK_HIP(ctx, hipMemcpyAsync(vals.data(), d_out, k * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); X.synced();
+    for (size_t b = 0; b < Bp; ++b) {
+        ReplaySource rep(vals.data() + row0[b], row0[b + 1] - row0[b]);
+        stark_proof* P = new stark_proof();
+        const int32_t rc = assemble_proof(plan[b].shape, r, *H[b], rep, P->bytes, P->size_estimate);
+        if (rc || rep.pos != rep.n) {
+            delete P; for (size_t j = 0; j < b; ++j) { delete out[j]; out[j] = nullptr; }
+            return rc > 0 ? rc : ctx->fail(STARK_ERR_INVALID_ARG, "query phase: value list does not match the plan");
+        }
+        out[b] = P;
+    }
+    return STARK_OK;
+}
+// The tail of one pass of Bp >= 2 traces: layer 0 of every trace from the batched merge (cols: host tables of device pointers a, s, e, t with
+// the traces' z on the host) or from given f0 (a host table of device pointers), then the commit phase and the query phase side by side.
+// Host synchronisations per pass: the FOUR of batch_queries, independent of Bp (merge and commit phase only enqueue).  stage_ms of every proof
+// of the pass: shared_ms + the pass's merge, the pass's commit, the pass's queries.
+static int32_t prove_pass_batch(stark_ctx* ctx, size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, size_t n0,
+                                const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, stark_proof** out) {
+    auto u0 = Clock::now();
+    FriDevExec X(ctx); FriDevBatch C(X);
+    STARK_TRY(batch_commit_begin(ctx, C, Bp, n0, schedule, L, seed_z));
+    std::vector<const fr_t*> tab; std::vector<fr_t> zv;
+    if (f0) STARK_TRY(batch_fill_layer0(ctx, X, C, f0));
+    else {
+        for (size_t b = 0; b < Bp; ++b) if (fr_eq(fr_pow_u64<PallasFr>(zs[b], n0), host::h_one())) return ctx->fail(STARK_ERR_INVALID_ARG, "z must be outside H");   // lib.rs:78
+        tab.resize(4 * Bp); for (int c = 0; c < 4; ++c) for (size_t b = 0; b < Bp; ++b) tab[c * Bp + b] = as_fr(cols[c][b]);
+        zv.assign(zs, zs + Bp);
+        const fr_t** d_tab = nullptr; fr_t* d_z = nullptr; STARK_TRY(X.put(tab, &d_tab)); STARK_TRY(X.put(zv, &d_z));
+        const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));
+        STARK_TRY(ali_merge_batch_launch(ctx, X, Bp, d_tab, d_tab + Bp, d_tab + 2 * Bp, d_tab + 3 * Bp, nullptr, nullptr, omega, d_z, n0, C.f[0], nullptr, nullptr));
+    }
+    auto u1 = Clock::now();
+    STARK_TRY(C.run());
+    auto u2 = Clock::now();
+    STARK_TRY(batch_queries(ctx, X, C, n0, r, out));
+    auto u3 = Clock::now();
+    for (size_t b = 0; b < Bp; ++b) { out[b]->ms[0] = shared_ms + ms_between(u0, u1); out[b]->ms[1] = ms_between(u1, u2); out[b]->ms[2] = ms_between(u2, u3); }
+    return STARK_OK;
+}
+static void free_proofs(stark_proof** out, size_t B) { for (size_t p = 0; p < B; ++p) if (out[p]) { delete out[p]; out[p] = nullptr; } }
+// stark_deep_fri_prove_f0_batch_dev: the batch cut into passes of at most "prove_batch_max_rows" rows; a pass of one trace is the single prove.
+static int32_t prove_f0_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
+    const size_t per = pass_traces(ctx, n0);
+    for (size_t p0 = 0; p0 < B; p0 += per) {
+        const size_t Bp = std::min(per, B - p0);
+        const int32_t rc = Bp == 1 ? prove_impl(ctx, nullptr, nullptr, nullptr, nullptr, as_fr(f0[p0]), n0, schedule, L, r, seed_z, &out[p0])
+                                   : prove_pass_batch(ctx, Bp, nullptr, nullptr, f0 + p0, n0, schedule, L, r, seed_z, 0.0, out + p0);
+        if (rc) { free_proofs(out, B); return rc; }
+    }
+    return STARK_OK;
+}
+// stark_fri_commit_batch_dev: the roots of fri_build of every trace, roots[(b (L + 1) + l) * 4 ..]; one synchronisation per pass.
+static int32_t commit_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, uint64_t* roots) {
+    const size_t per = pass_traces(ctx, n0), R = L + 1;
+    for (size_t p0 = 0; p0 < B; p0 += per) {
+        const size_t Bp = std::min(per, B - p0);
+        if (Bp == 1) {
+            stark_fri_state* S = nullptr; STARK_TRY(fri_build_impl(ctx, as_fr(f0[p0]), n0, schedule, L, seed_z, &S));
+            const int32_t rc = state_roots(S);
+            if (!rc) for (size_t l = 0; l < R; ++l) store_fr(roots + 4 * (p0 * R + l), S->roots[l]);
+            delete S; if (rc) return rc;
+            continue;
+        }
+        FriDevExec X(ctx); FriDevBatch C(X);
+        STARK_TRY(batch_commit_begin(ctx, C, Bp, n0, schedule, L, seed_z));
+        STARK_TRY(batch_fill_layer0(ctx, X, C, f0 + p0));
+        STARK_TRY(C.run());
+        std::vector<fr_t> rl(R * Bp);
+        STARK_HIP(ctx, hipMemcpyAsync(rl.data(), C.roots, rl.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); X.synced();
+        for (size_t b = 0; b < Bp; ++b) for (size_t l = 0; l < R; ++l) store_fr(roots + 4 * ((p0 + b) * R + l), rl[l * Bp + b]);
+    }
+    return STARK_OK;
+}
+// stark_ali_merge_batch_dev: tables of `batch` device pointers (host), z / beta on the host; kMaxPassTraces traces per launch.
+static int32_t ali_merge_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, const uint64_t* const* r_opt,
+                                    const uint64_t* beta, const fr_t& omega, const uint64_t* z, size_t n, uint64_t* const* f0, uint64_t* c_star) {
+    FriDevExec X(ctx);
+    std::vector<const fr_t*> tab(5 * B, nullptr); std::vector<fr_t*> outp(B); std::vector<fr_t> zb(2 * B, host::h_zero()), cs(B);
+    bool blinded = false;
+    for (size_t b = 0; b < B; ++b) {
+        tab[b] = as_fr(a[b]); tab[B + b] = as_fr(s[b]); tab[2 * B + b] = as_fr(e[b]); tab[3 * B + b] = as_fr(t[b]);
+        if (r_opt && r_opt[b]) { tab[4 * B + b] = as_fr(r_opt[b]); zb[B + b] = load_fr(beta + 4 * b); blinded = true; }
+        outp[b] = as_fr(f0[b]); zb[b] = load_fr(z + 4 * b);
+    }
+    const fr_t** d_tab = nullptr; fr_t** d_out = nullptr; fr_t *d_zb = nullptr, *d_cs = nullptr;
+    STARK_TRY(X.put(tab, &d_tab)); STARK_TRY(X.put(outp, &d_out)); STARK_TRY(X.put(zb, &d_zb));
+    if (c_star) { void* q = nullptr; STARK_TRY(X.alloc(B * sizeof(fr_t), &q)); d_cs = (fr_t*)q; }
+    for (size_t b0 = 0; b0 < B; b0 += kMaxPassTraces) {
+        const size_t Bp = std::min(kMaxPassTraces, B - b0);
+        STARK_TRY(ali_merge_batch_launch(ctx, X, Bp, d_tab + b0, d_tab + B + b0, d_tab + 2 * B + b0, d_tab + 3 * B + b0, blinded ? d_tab + 4 * B + b0 : nullptr, d_zb + B + b0, omega, d_zb + b0, n,
+                                         nullptr, d_out + b0, d_cs ? d_cs + b0 : nullptr));
+    }
+    if (c_star) STARK_HIP(ctx, hipMemcpyAsync(cs.data(), d_cs, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
+    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); X.synced();       // the caller reads f0 and c_star on return
+    if (c_star) for (size_t b = 0; b < B; ++b) store_fr(c_star + 4 * b, cs[b]);
+    return STARK_OK;
+}
+
 // B independent proofs of equal shape (stark_deep_fri_prove_batch_dev).  What bounds one prove is the serial column sponge of build_f0
 // (fri.rs:548-557: n0/16 dependent permutations per column, one wave each): four waves of the chip are busy for 99 % of the time.  The chains of
 // different traces are independent, so all 4 * B of them run in ONE launch; the two Fiat-Shamir hashes per trace (ALI/seed, ALI/DEEP) are
-// one launch each for the whole batch; merge, fri_build and the query phase then run trace after trace on the context's stream.
+// one launch each for the whole batch; merge, fri_build and the query phase of the traces then run side by side, pass by pass (prove_pass_batch;
+// a pass of one trace is the single tail on this context).  Option "prove_batch_workers" = 1 keeps the earlier tail: trace after trace on four worker contexts.
 // Every proof is byte-for-byte what stark_deep_fri_prove_dev returns for that trace alone.
 static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, size_t n0,
                                 const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
@@ -379,11 +636,29 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
     std::vector<fr_t> fu(B);
     STARK_HIP(ctx, hipMemcpyAsync(fu.data(), fused.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     auto t1 = Clock::now();
-    // (3) per trace: merge, commit phase, query phase.  These tails are latency-bound (a few ms of small dependent launches each), so up to four of them run
-    // side by side: worker contexts of this context (same device, private streams, own pools), one host thread each, traces dealt round-robin.  The inputs
-    // are resident and this context's stream is idle (synchronised above), so the workers' streams may read them.
+    // (3) merge, commit phase, query phase: side by side per pass (prove_pass_batch), or — option "prove_batch_workers" — trace after trace.  A single tail is
+    // latency-bound (a few ms of small dependent launches), so the worker form runs up to four of them at a time: worker contexts of this context (same
+    // device, private streams, own pools), one host thread each, traces dealt round-robin.  The inputs are resident and this context's stream is idle
+    // (synchronised above), so the workers' streams may read them.
     const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));
     const double shared_ms = ms_between(t0, t1);
+    if (!ctx->opt.prove_batch_workers) {
+        std::vector<fr_t> zs(B); for (size_t p = 0; p < B; ++p) { fr_t beta; ali_z_beta_from_fused(fu[p], n0, seed_f[p], &zs[p], &beta); }
+        const size_t per = pass_traces(ctx, n0);
+        for (size_t p0 = 0; p0 < B; p0 += per) {
+            const size_t Bp = std::min(per, B - p0);
+            int32_t rc = STARK_OK;
+            if (Bp == 1) {                                                                      // the single tail, unchanged
+                DevBuf f0buf; if (f0buf.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) rc = ctx->fail(STARK_ERR_OOM, "f0");
+                if (!rc) rc = prove_tail_single(ctx, as_fr(a[p0]), as_fr(s[p0]), as_fr(e[p0]), as_fr(t[p0]), omega, zs[p0], f0buf.fr(), n0, schedule, L, r, seed_z, shared_ms, &out[p0]);
+            } else {
+                const uint64_t* const* const cols[4] = {a + p0, s + p0, e + p0, t + p0};
+                rc = prove_pass_batch(ctx, Bp, cols, zs.data() + p0, nullptr, n0, schedule, L, r, seed_z, shared_ms, out + p0);
+            }
+            if (rc) { free_proofs(out, B); return rc; }
+        }
+        return STARK_OK;
+    }
     const size_t NT = std::min<size_t>(B, 4);
     std::vector<stark_ctx*> cx(NT); for (size_t w = 0; w < NT; ++w) STARK_TRY(ctx_aux(ctx, w, &cx[w]));
     std::vector<int32_t> rcs(NT, STARK_OK);
@@ -392,18 +667,8 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
         int32_t rc = ctx_enter(c); if (rc) { rcs[w] = rc; return; }
         DevBuf f0buf; if (f0buf.alloc(c, n0 * sizeof(fr_t)) != hipSuccess) { rcs[w] = c->fail(STARK_ERR_OOM, "f0"); return; }
         for (size_t p = w; p < B; p += NT) {
-            auto u0 = Clock::now();
             fr_t z, beta; ali_z_beta_from_fused(fu[p], n0, seed_f[p], &z, &beta);
-            rc = ali_merge_dev_impl(c, as_fr(a[p]), as_fr(s[p]), as_fr(e[p]), as_fr(t[p]), nullptr, host::h_zero(), omega, z, n0, f0buf.fr(), nullptr); if (rc) { rcs[w] = rc; return; }
-            auto u1 = Clock::now();
-            stark_fri_state* S = nullptr; rc = fri_build_impl(c, f0buf.fr(), n0, schedule, L, seed_z, &S); if (rc) { rcs[w] = rc; return; }
-            auto u2 = Clock::now();
-            stark_proof* P = new stark_proof();
-            rc = prove_queries_encode(c, S, n0, r, P); delete S; if (rc) { delete P; rcs[w] = rc; return; }
-            auto u3 = Clock::now();
-            P->ms[0] = shared_ms + ms_between(u0, u1);          // the shared sponge stage (whole batch) + this trace's merge
-            P->ms[1] = ms_between(u1, u2); P->ms[2] = ms_between(u2, u3);
-            out[p] = P;
+            rc = prove_tail_single(c, as_fr(a[p]), as_fr(s[p]), as_fr(e[p]), as_fr(t[p]), omega, z, f0buf.fr(), n0, schedule, L, r, seed_z, shared_ms, &out[p]); if (rc) { rcs[w] = rc; return; }
         }
         (void)hipStreamSynchronize(c->stream);
     };
@@ -515,6 +780,37 @@ int32_t stark_deep_fri_prove_batch_dev(stark_ctx_t* ctx, size_t batch, const uin
     for (size_t p = 0; p < batch; ++p) if (!a[p] || !s[p] || !e[p] || !t[p]) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     return prove_batch_impl(ctx, batch, a, s, e, t, n0, schedule, L, r, seed_z, out);
+}
+int32_t stark_deep_fri_prove_f0_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out) {
+    if (out) for (size_t p = 0; p < batch; ++p) out[p] = nullptr;
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!batch) return STARK_OK;
+    if (!out || !f0 || (!schedule && L)) return STARK_ERR_INVALID_ARG;
+    for (size_t p = 0; p < batch; ++p) if (!f0[p]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    if (!is_pow2(n0) || n0 <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two above 1 (radix-2 domain)");
+    if (!schedule_divides(n0, schedule, L)) return ctx->fail(STARK_ERR_INVALID_ARG, "schedule not dividing domain size");
+    return prove_f0_batch_impl(ctx, batch, f0, n0, schedule, L, r, seed_z, out);
+}
+int32_t stark_fri_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, uint64_t* roots) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!batch) return STARK_OK;
+    if (!roots || !f0 || (!schedule && L)) return STARK_ERR_INVALID_ARG;
+    for (size_t p = 0; p < batch; ++p) if (!f0[p]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    if (!schedule_divides(n0, schedule, L)) return ctx->fail(STARK_ERR_INVALID_ARG, n0 ? "schedule not dividing domain size" : "empty layer");
+    return commit_batch_impl(ctx, batch, f0, n0, schedule, L, seed_z, roots);
+}
+int32_t stark_ali_merge_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t,
+                                  const uint64_t* const* r_opt, const uint64_t* beta, const uint64_t* omega4, const uint64_t* z, size_t n, uint64_t* const* f0, uint64_t* c_star) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!batch) return STARK_OK;
+    if (!a || !s || !e || !t || !omega4 || !z || !f0 || (r_opt && !beta)) return STARK_ERR_INVALID_ARG;
+    for (size_t p = 0; p < batch; ++p) if (!a[p] || !s[p] || !e[p] || !t[p] || !f0[p]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    if (n <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n > 1");                                                                                       // lib.rs:71
+    for (size_t p = 0; p < batch; ++p) if (fr_eq(fr_pow_u64<PallasFr>(load_fr(z + 4 * p), n), host::h_one())) return ctx->fail(STARK_ERR_INVALID_ARG, "z must be outside H");   // lib.rs:78
+    return ali_merge_batch_impl(ctx, batch, a, s, e, t, r_opt, beta, load_fr(omega4), z, n, f0, c_star);
 }
 size_t stark_proof_len(stark_proof_t* p) { return p ? p->bytes.size() : 0; }
 int32_t stark_proof_bytes(stark_proof_t* p, uint8_t* out) { if (!p || !out) return STARK_ERR_INVALID_ARG; memcpy(out, p->bytes.data(), p->bytes.size()); return STARK_OK; }

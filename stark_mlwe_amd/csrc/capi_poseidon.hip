@@ -252,6 +252,7 @@ static int32_t launch_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, co
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
+int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
                                  const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out) {
     return hash_ds_on(ctx, ctx->stream, p, DsStream::make(mode, arity, level, 0, label, in0, in1, mode == 1 ? n_hashes : n_hashes * chunk, 1, positions_dev, mode == 1 ? 0 : chunk), out);
@@ -265,7 +266,7 @@ static void ds_attrs() {
     lds_attr((const void*)k_hash_ds<DS>); lds_attr((const void*)k_hash_ds2<17, DS>); lds_attr((const void*)k_hash_ds2<9, DS>); lds_attr((const void*)k_hash_ds_chain<DS>);
 }
 void stark::poseidon_set_attrs() {
-    ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>();
+    ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>();
     for (const void* k : {(const void*)k_leaf_pair, (const void*)k_permute_batch, (const void*)k_tr_hash, (const void*)k_hash_stream, (const void*)k_leaf_pair2, (const void*)k_node16_pair,
                           (const void*)k_tr_hash_chain, (const void*)k_leaf_pair_chain, (const void*)k_tr_stream_chain, (const void*)k_tr_batch_chain})
         lds_attr(k);

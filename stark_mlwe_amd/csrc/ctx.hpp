@@ -103,6 +103,8 @@ struct stark_ctx {
         bool merkle_node16_pair = true;  // t = 17 Merkle levels of > 4096 nodes with exactly 16 children each: the fixed two-permutation kernel k_node16_pair; 0 = the generic k_hash_ds2 (comparison)
         bool fri_side_pair = true;       // fri_build: the small layers' commitments on the side stream in the wave-pair form at every size (see side_commit); 0 = the latency forms (comparison)
         size_t sumcheck_verify_batch_max_slots = (size_t)1 << 25;   // a plan of the batched sum-check verifiers is run once it holds this many pool slots (1 GiB of field elements): device memory stays bounded whatever the batch
+        size_t prove_batch_max_rows = (size_t)1 << 22;   // the batched DEEP-FRI provers cut a batch into passes of at most this many rows (traces x n0) whose tails run side by side (fri_batch.hpp); device memory per pass stays near 70 B per row
+        bool prove_batch_workers = false;                // stark_deep_fri_prove_batch_dev: 1 = the tails trace after trace on four worker contexts, as before the side-by-side tail (comparison)
     } opt;
     bool side_commit = false;            // set while fri_build enqueues work that runs underneath the 2^n-leaf launch: Merkle levels and leaf layers of t = 9, 17 take the
                                          // wave-pair form (64 sponges per two waves) instead of one wave or five waves per sponge, which would hold many wave slots at lone-wave speed

@@ -59,10 +59,12 @@ __global__ void __launch_bounds__(256) k_fri_fold_any(const fr_t* __restrict__ f
 // on how they are obtained.
 // Also accumulates the barycentric partial sum  sum_j phi_j w^j / (z - w^j)  per block (for c*).
 #define ALI_K 8
+// The work of one workgroup (blockIdx.x of gridDim.x) on one trace: k_ali_merge runs it for its only trace, k_ali_merge_batch for trace blockIdx.y.
+// block_sum: where this workgroup's barycentric partial goes (nullptr: c* is not asked for).
 template <class F>
-__global__ void __launch_bounds__(256) k_ali_merge(const fr_t* __restrict__ a, const fr_t* __restrict__ s, const fr_t* __restrict__ e, const fr_t* __restrict__ t,
-                                                   const fr_t* __restrict__ r_opt, fr_t beta, PowTable wpow, fr_t w_step /* w^T */, fr_t w_step_inv, fr_t z, uint64_t n, uint64_t j0 /* global position of element 0 */,
-                                                   fr_t* __restrict__ f0, fr_t* __restrict__ block_sums) {
+__device__ __forceinline__ void ali_merge_block(const fr_t* __restrict__ a, const fr_t* __restrict__ s, const fr_t* __restrict__ e, const fr_t* __restrict__ t,
+                                                const fr_t* __restrict__ r_opt, const fr_t& beta, const PowTable& wpow, const fr_t& w_step /* w^T */, const fr_t& w_step_inv, const fr_t& z, uint64_t n,
+                                                uint64_t j0 /* global position of element 0 */, fr_t* __restrict__ f0, fr_t* __restrict__ block_sum) {
     __shared__ uint4 red[2 * 4];
     const uint64_t T = (uint64_t)gridDim.x * blockDim.x, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     fr_t phi[ALI_K], pre[ALI_K];
@@ -117,10 +119,10 @@ __global__ void __launch_bounds__(256) k_ali_merge(const fr_t* __restrict__ a, c
             inv = fr_mul<F>(inv, fr_sub<F>(w, z));
             fr_t q = fr_mul<F>(phi[u], dinv);
             stg(f0 + j, q);
-            if (block_sums) bary = fr_sub<F>(bary, fr_mul<F>(q, w));   // phi w^j / (z - w^j) = -(phi / (w^j - z)) w^j  (only when c* is asked for)
+            if (block_sum) bary = fr_sub<F>(bary, fr_mul<F>(q, w));   // phi w^j / (z - w^j) = -(phi / (w^j - z)) w^j  (only when c* is asked for)
         }
     }
-    if (block_sums) {
+    if (block_sum) {
         for (int sft = 1; sft < 64; sft <<= 1) bary = fr_add<F>(bary, shfl_xor_fr(bary, sft));
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
         if (lane == 0) { red[2 * wave] = make_uint4(bary.v[0], bary.v[1], bary.v[2], bary.v[3]); red[2 * wave + 1] = make_uint4(bary.v[4], bary.v[5], bary.v[6], bary.v[7]); }
@@ -132,14 +134,40 @@ __global__ void __launch_bounds__(256) k_ali_merge(const fr_t* __restrict__ a, c
                 x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w; x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w;
                 acc = fr_add<F>(acc, x);
             }
-            stg(block_sums + blockIdx.x, acc);
+            stg(block_sum, acc);
         }
     }
 }
-// out[0] = scale * sum_{i<n} v[i]   (single 256-thread block; n is a few thousand block partials).
+template <class F>
+__global__ void __launch_bounds__(256) k_ali_merge(const fr_t* __restrict__ a, const fr_t* __restrict__ s, const fr_t* __restrict__ e, const fr_t* __restrict__ t,
+                                                   const fr_t* __restrict__ r_opt, fr_t beta, PowTable wpow, fr_t w_step /* w^T */, fr_t w_step_inv, fr_t z, uint64_t n, uint64_t j0 /* global position of element 0 */,
+                                                   fr_t* __restrict__ f0, fr_t* __restrict__ block_sums) {
+    ali_merge_block<F>(a, s, e, t, r_opt, beta, wpow, w_step, w_step_inv, z, n, j0, f0, block_sums ? block_sums + blockIdx.x : (fr_t*)nullptr);
+}
+// The merges of gridDim.y traces of n elements over one domain in ONE launch: trace b = blockIdx.y reads its columns through the pointer tables
+// (r_opt == nullptr, or r_opt[b] == nullptr: no blinding term for that trace), its own z[b] and beta[b] from device arrays, and writes
+// out_base + b * n (a trace-major layer-0 buffer) or, with out_base == nullptr, out_ptrs[b].  block_sums: gridDim.x partials per trace.
+template <class F>
+__global__ void __launch_bounds__(256) k_ali_merge_batch(const fr_t* const* __restrict__ a, const fr_t* const* __restrict__ s, const fr_t* const* __restrict__ e, const fr_t* const* __restrict__ t,
+                                                         const fr_t* const* __restrict__ r_opt, const fr_t* __restrict__ beta, PowTable wpow, fr_t w_step, fr_t w_step_inv, const fr_t* __restrict__ z,
+                                                         uint64_t n, fr_t* __restrict__ out_base, fr_t* const* __restrict__ out_ptrs, fr_t* __restrict__ block_sums) {
+    const uint64_t b = blockIdx.y;
+    const fr_t* r = r_opt ? r_opt[b] : (const fr_t*)nullptr;
+    const fr_t bt = r ? ldg(beta + b) : fr_zero<F>();
+    ali_merge_block<F>(a[b], s[b], e[b], t[b], r, bt, wpow, w_step, w_step_inv, ldg(z + b), n, 0, out_base ? out_base + b * n : out_ptrs[b],
+                       block_sums ? block_sums + b * gridDim.x + blockIdx.x : (fr_t*)nullptr);
+}
+// dst[b * n + i] = src[b][i] for b = blockIdx.y: layer 0 of a batch from a table of per-trace pointers (one launch instead of one copy per trace).
+static __global__ void __launch_bounds__(256) k_copy_rows(const fr_t* const* __restrict__ src, uint64_t n, fr_t* __restrict__ dst) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i < n) stg(dst + b * n + i, ldg(src[b] + i));
+}
+// out[b] = scale * sum_{i<n} v[b * n + i] for b = blockIdx.x   (one 256-thread block per sum; n is a few thousand block partials; a grid of one
+// block is the single sum).
 template <class F>
 __global__ void __launch_bounds__(256) k_sum_single_block(const fr_t* __restrict__ v, uint64_t n, fr_t scale, fr_t* __restrict__ out) {
     __shared__ uint4 red[2 * 4];
+    v += (uint64_t)blockIdx.x * n; out += blockIdx.x;
     fr_t acc = fr_zero<F>();
     for (uint64_t i = threadIdx.x; i < n; i += blockDim.x) acc = fr_add<F>(acc, ldg(v + i));
     for (int sft = 1; sft < 64; sft <<= 1) acc = fr_add<F>(acc, shfl_xor_fr(acc, sft));

@@ -15,6 +15,7 @@
 #include "fri_verify_batch.hpp"
 #include "mfma_digits.hpp"
 #include "poseidon_chain.hpp"
+#include "fri_batch.hpp"
 #include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
 
 using namespace stark;
@@ -488,5 +489,64 @@ size_t hc_sumcheck_verify_batch_steps(int mf, size_t batch, const uint8_t* const
     const auto st = V.steps();
     for (size_t i = 0; i < st.size() && i < cap; ++i) { kind[i] = st[i].first; count[i] = st[i].second; }
     return st.size();
+}
+}  // extern "C"
+
+// ---- the batched commit phase (fri_batch.hpp) through the host instantiation of the stream bodies ----------------------------------
+struct FriHostExec {
+    HcParams* tp; std::vector<std::vector<uint64_t>> mem;
+    struct ParamCache { HcVerifyHasher h{nullptr}; HcParams* params(size_t arity) { return h.params(arity); } };
+    ParamCache& mp;                                                   // the Merkle parameters per width, derived once per process (t = 129 takes a while on the host)
+    static ParamCache& cache() { static ParamCache c; return c; }
+    explicit FriHostExec(HcParams* t) : tp(t), mp(cache()) {}
+    int32_t alloc(size_t bytes, void** out) { mem.emplace_back((bytes + 7) / 8 + 1, 0); *out = mem.back().data(); return 0; }
+    int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
+    int32_t zpows(const fr_t& z, size_t m, fr_t* zp) { fr_t acc = fr_one<PF>(); for (size_t t = 0; t < m; ++t) { zp[t] = acc; acc = fr_mul<PF>(acc, z); } return 0; }
+    int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out) {                                   // fri_fold_layer (fri.rs:85-102)
+        for (size_t b = 0; b < n / m; ++b) { fr_t acc = fr_zero<PF>(); for (size_t t = 0; t < m; ++t) acc = fr_add<PF>(acc, fr_mul<PF>(f[b * m + t], zp[t])); out[b] = acc; }
+        return 0;
+    }
+    int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h) {
+        fr_t init[17]; leaf_init(init); const LeafStream LS{init, f, f_next, m, n};
+        fr_t st[17]; for (size_t i = 0; i < n; ++i) { ArrayState s{st}; h[i] = leaf_pair_body(s, tp->dev, LS, i); }
+        return 0;
+    }
+    template <class DS> int32_t ds(size_t arity, const DS& D, fr_t* out) {
+        HcParams* P = mp.params(arity); std::vector<fr_t> st(P->dev.t);
+        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, P->dev, D, k); }
+        return 0;
+    }
+    int32_t pair_level(size_t arity, const DsBatchPairStream& D, fr_t* out) { return ds(arity, D, out); }
+    int32_t ds_level(size_t arity, const DsBatchStream& D, fr_t* out) { return ds(arity, D, out); }
+    int32_t fork() { return 0; }
+    void side(bool) {}
+    int32_t join() { return 0; }
+};
+extern "C" {
+// The pair leaves of `trees` same-shape unhashed layers (DsBatchPairStream): f = trees x n, cp = trees x (n / cp_div) or null, labels[b]
+int hc_hash_ds_batch_pairs_level(void* params, size_t arity, const uint64_t* labels, const uint64_t* f, const uint64_t* cp, size_t n, size_t cp_div, size_t trees, uint64_t* out) {
+    HcParams* P = (HcParams*)params;
+    if (!cp_div || n % cp_div) return -1;
+    std::vector<fr_t> a(n * trees), b(cp ? n / cp_div * trees : 0), st(P->dev.t);
+    for (size_t i = 0; i < a.size(); ++i) a[i] = ld4(f + 4 * i);
+    for (size_t i = 0; i < b.size(); ++i) b[i] = ld4(cp + 4 * i);
+    const DsBatchPairStream D = DsBatchPairStream::make(arity, labels, a.data(), cp ? b.data() : nullptr, n, cp_div, trees);
+    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, D, k)); }
+    return 0;
+}
+// The commit phase of B traces side by side (FriBatchCommit): roots[(b (L + 1) + l) * 4 ..] = root of layer l of trace b.  0 on success.
+int hc_fri_commit_batch(void* tparams, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, uint64_t* roots) {
+    FriHostExec X((HcParams*)tparams); FriBatchCommit<FriHostExec> C(X);
+    HcHasher H(tparams); std::vector<fr_t> z(L);
+    { size_t n = n0; for (size_t l = 0; l < L; ++l) {
+          if (schedule[l] < 2 || n % schedule[l]) return -1;
+          const fr_t in[3] = {host::h_u64(seed_z), host::h_u64(l), host::h_u64(n)}; fr_t fused; if (H.hash("FRI/z/l", in, 3, 1, &fused)) return -3;
+          z[l] = fri_z_from_fused(fused, seed_z, l, n); n /= schedule[l];
+      } }
+    std::string err; if (int rc = C.init(B, n0, schedule, L, z.data(), err)) return rc;
+    for (size_t b = 0; b < B; ++b) for (size_t i = 0; i < n0; ++i) C.f[0][b * n0 + i] = ld4(f0[b] + 4 * i);
+    if (int rc = C.run()) return rc;
+    for (size_t b = 0; b < B; ++b) for (size_t l = 0; l <= L; ++l) st4(roots + 4 * (b * (L + 1) + l), C.roots[l * B + b]);
+    return 0;
 }
 }  // extern "C"

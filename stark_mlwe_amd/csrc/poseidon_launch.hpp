@@ -10,10 +10,12 @@ namespace stark {
 void poseidon_set_attrs();                                           // per-device kernel attributes of every Poseidon kernel these can launch (stark_ctx_create)
 
 // One launch of hash_with_ds_dynamic over the hashes of a DS stream on `st`, in the form the selector picks for a Merkle level of D.n_out nodes
-// (DsStream: a Merkle level / pair-leaf level; DsGatherStream: one (width, depth) step of the batch verifiers; DsBatchStream: one level of B trees).
+// (DsStream: a Merkle level / pair-leaf level; DsGatherStream: one (width, depth) step of the batch verifiers; DsBatchStream: one level of B trees;
+// DsBatchPairStream: the pair leaves of B unhashed FRI layers).
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out);
+int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out);
 // DS hashes with scattered positions (the verifier's union-of-paths levels): hash k = H([arity, level, positions[k], label] || chunk children)
 int32_t hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
                           const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out);

@@ -85,6 +85,28 @@ struct DsBatchStream {
     }
 };
 
+// The pair leaves of B same-shape unhashed FRI layers in one launch (the batched commit phase, fri_batch.hpp): DsStream mode 1 with per-tree
+// positions.  Hash k belongs to tree k / n and is leaf j = k % n of it, position j, under the tree's own label:
+//   hash k = hash_with_ds_dynamic([arity, 2^32 - 1, k % n, labels[k / n]] || f[k], cp ? cp[k / cp_div] : 0 || 1), eager sponge, cap 0
+// with f the B x n trace-major layer and cp the B x (n / cp_div) next one (cp_div divides n, so k / cp_div stays inside tree k / n's slice).
+struct DsBatchPairStream {
+    fr_t arity_f, level_f; const uint64_t* labels; size_t n, n_out, cp_div; const fr_t* f; const fr_t* cp;
+    static inline DsBatchPairStream make(size_t arity, const uint64_t* labels, const fr_t* f, const fr_t* cp, size_t n, size_t cp_div, size_t trees) {
+        DsBatchPairStream D;
+        D.arity_f = fr_from_u64<PF>(arity); D.level_f = fr_from_u64<PF>(0xFFFFFFFFu); D.labels = labels; D.n = n; D.n_out = n * trees;
+        D.cp_div = cp_div ? cp_div : 1; D.f = f; D.cp = cp;
+        return D;
+    }
+    FR_HD uint64_t position(size_t k) const { return k % n; }
+    FR_HD size_t total(size_t) const { return 7; }
+    FR_HD size_t max_total() const { return 7; }
+    FR_HD fr_t elem(size_t k, size_t q) const {
+        if (q < 4) return q == 0 ? arity_f : (q == 1 ? level_f : (q == 2 ? fr_from_u64<PF>(position(k)) : fr_from_u64<PF>(labels[k / n])));
+        if (q == 6) return fr_one<PF>();
+        return q == 4 ? ldg(f + k) : (cp ? ldg(cp + k / cp_div) : fr_zero<PF>());
+    }
+};
+
 // B streaming transcripts (transcript/src/lib.rs:79-101, lazy duplex) advanced in one launch, one workgroup per active instance
 // (the batched sum-check provers, sumcheck_batch.hpp).  Instance b keeps state[17 b .. 17 b + 16] and its rate cursor pos[b] in
 // device memory between launches; active a runs instance inst[a] (inst == nullptr: inst0 + a).  Active a runs nseg segments: segment
