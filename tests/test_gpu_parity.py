@@ -191,9 +191,13 @@ def test_merkle_errors_and_open(gpu_ctx, oracle):
 
 
 # ---- FRI -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("m", [2, 4, 8, 16, 32, 64, 128, 3, 6])
-def test_fri_fold_layer(gpu_ctx, oracle, m):
-    n = m * 37 if m in (3, 6) else max(m * 5, 1 << 11)
+# every arity at a lane count that is a multiple of the 256-thread block (ids as before), then output counts that leave the last block partial
+FOLD_SHAPES = ([pytest.param(m, m * 37 if m in (3, 6) else max(m * 5, 1 << 11), id=str(m)) for m in (2, 4, 8, 16, 32, 64, 128, 3, 6)] +
+               [(m, m * c) for m in (2, 16, 128) for c in (37, 300)] + [(3, 3 * 257), (6, 6 * 257)])
+
+
+@pytest.mark.parametrize("m,n", FOLD_SHAPES)
+def test_fri_fold_layer(gpu_ctx, oracle, m, n):
     f = oracle.synth_column(2, 0, 0, n); z = oracle.fri_sample_z_ell(0xDEEFBAAD, 0, 1 << 11)
     got = gpu_ctx.fri_fold_layer(f, z, m)
     assert (got == oracle.fri_fold_layer(f, z, m)).all()
