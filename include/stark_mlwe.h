@@ -81,6 +81,8 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  *   "ntt_log_tile" (8..12, default 11; -1 restores the default), "ntt_min_waves" (2 | 4), "poseidon_lane_only" (0 | 1).
  *   "sponge_one_wave" (0 | 1: long serial sponges, small Merkle levels / leaf layers and short transcript hashes on the one-wave / wave-pair kernels
  *   instead of the five-wave latency kernel; comparison), "sponge_debug" (timing experiments on the five-wave kernel; digests are WRONG when set).
+ *   "prove_batch_max_rows" (1..2^28, default 2^22: the rows of one pass of the batched DEEP-FRI provers).
+ * An unknown key is STARK_ERR_INVALID_ARG; stark_last_error then lists the known keys.
  * Changing an option synchronises the stream and drops the cached NTT plans. */
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value);
 size_t  stark_ctx_cached_bytes(stark_ctx_t* ctx);
@@ -198,7 +200,8 @@ int32_t stark_deep_fri_prove_dev(stark_ctx_t* ctx, const uint64_t* a, const uint
  * busy; the 4 * batch chains of a batch are independent and run in ONE launch, so the stage costs what it costs for one trace.
  * The tails (merge, commit phase, query phase) of the traces then run side by side: the batch is cut into passes of at most
  * "prove_batch_max_rows" rows (option, default 2^22; a pass of one trace is the single tail), and every step of a pass is one launch
- * for all its traces.  Option "prove_batch_workers" = 1 restores the earlier tail (trace after trace on four worker contexts).
+ * for all its traces.  (The earlier tail, trace after trace on four worker contexts, has been removed together with the option that selected
+ * it: stark_ctx_set_option now refuses that key as it refuses any unknown one, with STARK_ERR_INVALID_ARG.)
  * Every proof is byte-identical to stark_deep_fri_prove_dev on that trace alone.  stage_ms 0 / 1 / 2 of a proof are its pass's shared
  * stage times: the sponge stage of the whole batch + the pass's merge, the pass's commit phase, the pass's query phase.  They are HOST times
  * between the steps: in a pass of two or more traces merge and commit phase only enqueue their launches, so stages 0 and 1 count enqueueing

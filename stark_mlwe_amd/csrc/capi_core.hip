@@ -59,6 +59,15 @@ int32_t ctx_side_stream(stark_ctx* ctx, hipStream_t* out) {
     if (!ctx->side_stream) { STARK_HIP(ctx, hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking)); STARK_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming)); }
     *out = ctx->side_stream; return STARK_OK;
 }
+int32_t ctx_fork(stark_ctx* ctx, hipStream_t* side) {
+    STARK_TRY(ctx_side_stream(ctx, side));
+    if (hipEventRecord(ctx->ev_fork, ctx->stream) != hipSuccess || hipStreamWaitEvent(*side, ctx->ev_fork, 0) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "fork");
+    return STARK_OK;
+}
+int32_t ctx_join(stark_ctx* ctx) {
+    if (hipEventRecord(ctx->ev_fork, ctx->side_stream) != hipSuccess || hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "join");
+    return STARK_OK;
+}
 
 static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
     if (host::rp_for_width(P->ref.t) < 0) return ctx->fail(STARK_ERR_UNSUPPORTED, "Poseidon width must be one of 9,17,33,65,129");
@@ -135,8 +144,6 @@ int32_t stark_ctx_create(int32_t device, void* stream, stark_ctx_t** out) {
 }  // extern "C"
 // everything the context owns; runs when the context has been destroyed AND its last handle is gone
 static void ctx_teardown(stark_ctx* ctx) {
-    for (stark_ctx* a : ctx->aux) if (a) ctx_teardown(a);            // worker contexts hand out no handles of their own
-    ctx->aux.clear();
     (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream);
     stark::comm_destroy(ctx);
     stark::ntt_plans_free(ctx);
@@ -172,26 +179,12 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx) {
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (auto& kv : ctx->pool_free) { for (void* q : kv.second) (void)hipFree(q); kv.second.clear(); }
     ctx->pool_cached_bytes = 0;
-    for (stark_ctx* a : ctx->aux) if (a) (void)stark_ctx_trim(a);
     stark::ntt_plans_free(ctx);                  // NTT plans with their direct twiddle / coset tables (up to 3*n*32 B per plan) are rebuilt on demand
     ctx->scratch.reset(); ctx->scratch_bytes = 0;
     return STARK_OK;
 }
 size_t stark_ctx_cached_bytes(stark_ctx_t* ctx) { return ctx ? ctx->pool_cached_bytes : 0; }
 }  // extern "C"
-namespace stark {
-int32_t ctx_aux(stark_ctx* ctx, size_t k, stark_ctx** out) {
-    while (ctx->aux.size() <= k) {
-        stark_ctx* a = nullptr; int32_t rc = stark_ctx_create(ctx->device, STARK_STREAM_PRIVATE, &a);
-        if (rc) return ctx->fail(rc, "worker context");
-        ctx->aux.push_back(a);
-    }
-    stark_ctx* a = ctx->aux[k];
-    const int own_debug = a->opt.sponge_debug;
-    a->opt = ctx->opt; a->opt.sponge_debug = own_debug;      // the parent's options, except "sponge_debug": the workers have never received it (whether by intent is not recorded), and that is kept
-    *out = a; return STARK_OK;
-}
-}
 // The options of stark_ctx_set_option: the key, and what a value does to the context's options (the accepted range when it is refused).
 struct OptionDef { const char* key; const char* (*set)(stark_ctx::Options&, int64_t); };
 static const OptionDef kOptions[] = {
@@ -206,7 +199,6 @@ static const OptionDef kOptions[] = {
     {"fri_side_pair", [](stark_ctx::Options& o, int64_t v) -> const char* { o.fri_side_pair = v != 0; return nullptr; }},
     {"sumcheck_verify_batch_max_slots", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1) return "at least 1"; o.sumcheck_verify_batch_max_slots = (size_t)v; return nullptr; }},
     {"prove_batch_max_rows", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.prove_batch_max_rows = (size_t)v; return nullptr; }},
-    {"prove_batch_workers", [](stark_ctx::Options& o, int64_t v) -> const char* { o.prove_batch_workers = v != 0; return nullptr; }},
 };
 extern "C" {
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value) {

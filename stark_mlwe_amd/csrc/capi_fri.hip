@@ -3,7 +3,6 @@
 // crates/deep_ali/src/fri.rs and crates/deep_ali/src/lib.rs).  C-ABI in include/stark_mlwe.h.
 #include <algorithm>
 #include <chrono>
-#include <thread>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -82,13 +81,11 @@ static int32_t state_roots(stark_fri_state* S) {
     S->roots = r; return STARK_OK;
 }
 
-// The layers of a commit phase: their sizes under the schedule (fri.rs:150) and their Merkle arities (fri.rs:220-229).
-static bool fri_layer_shape(size_t n0, const size_t* sched, size_t L, std::vector<size_t>& n, std::vector<size_t>& arity, std::string& err) {
-    if (!n0) { err = "empty layer"; return false; }
-    n.assign(1, n0);
-    for (size_t l = 0; l < L; ++l) { if (sched[l] < 2 || n[l] % sched[l]) { err = "schedule not dividing domain size"; return false; } n.push_back(n[l] / sched[l]); }
-    arity.clear(); for (size_t l = 0; l <= L; ++l) arity.push_back(pick_arity_for_layer(n[l], l < L ? sched[l] : 1));
-    return true;
+// What a refused layer shape (fri_plan.hpp: fri_layers) is to the entry points of this file: INVALID_ARG for an empty layer or a schedule that does not
+// divide.  A layer with arity 1 passes here: the single commit leaves it to merkle_build_on (STARK_ERR_UNSUPPORTED), the batched one to FriBatchCommit::shape.
+static int32_t layers_or_fail(stark_ctx* ctx, size_t n0, const size_t* schedule, size_t L, std::vector<size_t>& n, std::vector<size_t>& arity) {
+    const LayerShape sh = fri_layers(n0, schedule, L, n, arity);
+    return sh == LayerShape::empty_layer || sh == LayerShape::not_dividing ? ctx->fail(STARK_ERR_INVALID_ARG, layer_shape_text(sh)) : STARK_OK;
 }
 // Everything of a commit phase that may upload constants (and synchronise doing so), to run before its first launch: the transcript parameters,
 // the Merkle parameters of every layer (MerkleChannelCfg::new(arity), fri.rs:277) and the fold challenges (fri.rs:250).  After the first call
@@ -119,14 +116,13 @@ static int32_t commit_layer_on(stark_ctx* ctx, hipStream_t st, stark_params* mp,
 static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state** out) {
     stark_fri_state* S = new stark_fri_state(); S->ref_.bind(ctx); S->ctx = ctx; S->schedule.assign(schedule, schedule + L);
     auto bail = [&](int32_t rc) { delete S; return rc; };
-    { std::string err; if (!fri_layer_shape(n0, schedule, L, S->n, S->arity, err)) return bail(ctx->fail(STARK_ERR_INVALID_ARG, err)); }
+    { int32_t rc = layers_or_fail(ctx, n0, schedule, L, S->n, S->arity); if (rc) return bail(rc); }
     S->trees.assign(L + 1, nullptr);
     // The prelude runs BEFORE any stream is forked.
     std::vector<stark_params*> mps;
     { int32_t rc = fri_prelude(ctx, S->n, S->arity, seed_z, mps, S->z); if (rc) return bail(rc); }
     size_t zp_total = 0; for (size_t l = 0; l < L; ++l) zp_total += schedule[l];
     hipStream_t main_stream = ctx->stream, side = nullptr;
-    { int32_t rc = ctx_side_stream(ctx, &side); if (rc) return bail(rc); }
     // layer 0 copy + folds back to back (the challenges do not depend on any commitment: fri.rs:250)
     for (size_t l = 0; l <= L; ++l) { void* q = nullptr; int32_t rc = ctx_alloc(ctx, S->n[l] * sizeof(fr_t), &q); S->f.push_back((fr_t*)q); if (rc) return bail(rc); }
     if (hipMemcpyAsync(S->f[0], f0_dev, n0 * sizeof(fr_t), hipMemcpyDeviceToDevice, main_stream) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "copy f0"));
@@ -141,7 +137,7 @@ static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, con
     // are small and mostly LATENCY-bound (tree tops: one dependent permutation per level), so they go to a side stream and run
     // underneath layer 0 instead of after it.  The streams are passed explicitly; the side stream is forked from and joined back
     // into the main one with events, so nothing here synchronises the host.
-    if (hipEventRecord(ctx->ev_fork, main_stream) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_fork, 0) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "fork"));
+    { int32_t rc = ctx_fork(ctx, &side); if (rc) return bail(rc); }
     auto commit_layer = [&](size_t l, hipStream_t st) {
         return commit_layer_on(ctx, st, mps[l], S->arity[l], l, S->f[l], l < L ? S->f[l + 1] : nullptr, S->n[l], l < L ? schedule[l] : 1, 0, 0, &S->trees[l]);
     };
@@ -154,7 +150,7 @@ static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, con
     ctx->side_commit = false;
     if (crc == STARK_OK) crc = commit_layer(0, main_stream);
     // join: the main stream continues only after the side stream's commitments
-    if (hipEventRecord(ctx->ev_fork, side) != hipSuccess || hipStreamWaitEvent(main_stream, ctx->ev_fork, 0) != hipSuccess) { (void)hipStreamSynchronize(side); return bail(ctx->fail(STARK_ERR_HIP, "join")); }
+    { int32_t rc = ctx_join(ctx); if (rc) { (void)hipStreamSynchronize(side); return bail(rc); } }
     if (crc != STARK_OK) { (void)hipStreamSynchronize(side); (void)hipStreamSynchronize(main_stream); return bail(crc); }
     *out = S; return STARK_OK;
 }
@@ -236,12 +232,6 @@ struct DeviceHasher : TrHasher {
         return stark_tr_hash_fields_tagged(ctx, nullptr, tag, (const uint64_t*)fields, k, n, (uint64_t*)out);
     }
 };
-static int32_t shape_of_state(stark_ctx* ctx, stark_fri_state* S, size_t n0, FriShape& sh) {
-    STARK_TRY(state_roots(S));
-    std::string err;
-    if (!sh.make(n0, S->schedule.data(), S->schedule.size(), S->roots.data(), err)) return ctx->fail(STARK_ERR_INVALID_ARG, err);
-    return STARK_OK;
-}
 // Transcript hashes of the query phase are pure functions of their inputs: the plan pass and the assembling pass ask for the same ones.
 struct MemoHasher : TrHasher {
     TrHasher& inner; std::map<std::string, std::vector<fr_t>> memo;
@@ -258,102 +248,126 @@ struct MemoHasher : TrHasher {
         memcpy((void*)out, it->second.data(), n * sizeof(fr_t)); return 0;
     }
 };
-// Where a request of the query plan reads: a device array (a layer or a tree level), its length, the rank that holds the value, the index there.
-struct FriOpening { const fr_t* src; size_t len; uint64_t owner, index; };
-// The values of the plan's requests that `rank` owns, into their rows of the nreq-row device table `out`, with ONE gather launch over a table of
-// source arrays; resolve(request, opening) locates each request.  host (optional) receives a download of the whole table.  Returns synchronised:
-// the host index arrays end here.
-template <class Resolve>
-static int32_t gather_openings(stark_ctx* ctx, const FriPlan& plan, uint64_t rank, Resolve resolve, fr_t* out, fr_t* host) {
-    std::vector<const fr_t*> base; std::map<const fr_t*, uint32_t> slot; std::vector<uint32_t> src; std::vector<uint64_t> idx, row;
-    for (size_t i = 0; i < plan.req.size(); ++i) {
-        FriOpening o; STARK_TRY(resolve(plan.req[i], o));
-        if (o.owner != rank) continue;
-        if (o.index >= o.len) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: opening index out of range");
-        auto it = slot.emplace(o.src, (uint32_t)base.size()).first;
-        if (it->second == base.size()) base.push_back(o.src);
-        src.push_back(it->second); idx.push_back(o.index); row.push_back(i);
-    }
-    const size_t k = src.size();
-    if (!k) return STARK_OK;
-    DevBuf db, ds, di, dr;
-    STARK_HIP(ctx, db.alloc(ctx, base.size() * sizeof(void*))); STARK_HIP(ctx, ds.alloc(ctx, k * 4)); STARK_HIP(ctx, di.alloc(ctx, k * 8)); STARK_HIP(ctx, dr.alloc(ctx, k * 8));
-    STARK_HIP(ctx, hipMemcpyAsync(db.p, base.data(), base.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
-    STARK_HIP(ctx, hipMemcpyAsync(ds.p, src.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
-    STARK_HIP(ctx, hipMemcpyAsync(di.p, idx.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
-    STARK_HIP(ctx, hipMemcpyAsync(dr.p, row.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)db.p, (const uint32_t*)ds.p, (const uint64_t*)di.p,
-                       (const uint64_t*)dr.p, (uint64_t)k, out);
-    STARK_HIP(ctx, hipGetLastError());
-    if (host) STARK_HIP(ctx, hipMemcpyAsync(host, out, plan.req.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return STARK_OK;
+// ---- the query phase: plan, ONE gather of the opened values, assembly -----------------------------------------------------------------------
+// The query plan of a commit phase with the given roots.  The failures are INVALID_ARG: a refused shape under FriShape::make's message, an index
+// outside its layer (fri_plan_make's -1) under the caller's wording.
+static int32_t make_query_plan(stark_ctx* ctx, FriPlan& plan, size_t n0, const size_t* schedule, size_t L, const fr_t* roots, size_t r, TrHasher& H,
+                               const char* bad_index = "query phase: bad index") {
+    plan.r = r;
+    { std::string err; if (!plan.shape.make(n0, schedule, L, roots, err)) return ctx->fail(STARK_ERR_INVALID_ARG, err); }
+    const int32_t rc = fri_plan_make(plan, H);
+    return rc == -1 ? ctx->fail(STARK_ERR_INVALID_ARG, bad_index) : rc;
 }
+// The proof from the n values of the plan's requests, in request order.  A list that runs short (assemble_proof's -1) or is not used up is
+// INVALID_ARG under the caller's wording; any other failure is the hasher's and is returned as it is.
+static int32_t assemble_from_values(stark_ctx* ctx, const FriShape& shape, size_t r, TrHasher& H, const fr_t* vals, size_t n, stark_proof* P,
+                                    const char* mismatch = "query phase: value list does not match the plan") {
+    ReplaySource rep(vals, n);
+    const int32_t rc = assemble_proof(shape, r, H, rep, P->bytes, P->size_estimate);
+    return rc == -1 || (rc == 0 && rep.pos != n) ? ctx->fail(STARK_ERR_INVALID_ARG, mismatch) : rc;
+}
+// The opened values of a query phase, fetched with ONE launch of k_gather_rows over a table of source arrays: add() records that `row` of the output
+// table is src[index], launch() uploads the four tables and gathers.  The object owns the host sources of those uploads, so it lives until the
+// caller's next synchronisation of the context's stream (synced()); destroyed with uploads pending — an early error return — it synchronises first
+// (the rule of FriDevExec).
+struct OpeningGather {
+    stark_ctx* ctx; std::vector<const fr_t*> base; std::map<const fr_t*, uint32_t> slot; std::vector<uint32_t> src; std::vector<uint64_t> idx, row;
+    DevBuf db, ds, di, dr; bool pending = false;
+    explicit OpeningGather(stark_ctx* c) : ctx(c) {}
+    OpeningGather(const OpeningGather&) = delete; OpeningGather& operator=(const OpeningGather&) = delete;
+    ~OpeningGather() { if (pending) (void)hipStreamSynchronize(ctx->stream); }
+    void synced() { pending = false; }                  // the caller has synchronised the context's stream
+    size_t size() const { return src.size(); }
+    int32_t add(const fr_t* from, size_t len, uint64_t index, uint64_t to_row) {
+        if (index >= len) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: opening index out of range");
+        auto it = slot.emplace(from, (uint32_t)base.size()).first;
+        if (it->second == base.size()) base.push_back(from);
+        src.push_back(it->second); idx.push_back(index); row.push_back(to_row); return STARK_OK;
+    }
+    int32_t launch(fr_t* out) {
+        const size_t k = src.size();
+        if (!k) return STARK_OK;
+        pending = true;
+        STARK_HIP(ctx, db.upload(ctx, base.data(), base.size() * sizeof(void*))); STARK_HIP(ctx, ds.upload(ctx, src.data(), k * 4));
+        STARK_HIP(ctx, di.upload(ctx, idx.data(), k * 8)); STARK_HIP(ctx, dr.upload(ctx, row.data(), k * 8));
+        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)db.p, (const uint32_t*)ds.p, (const uint64_t*)di.p,
+                           (const uint64_t*)dr.p, (uint64_t)k, out);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+};
+// Where a request reads when the whole commit phase of its proof is on this GPU: `c` names the layers and tree levels
+// (layers(); layer(l, &len); levels(l); level(l, v, &len)), and the range checks are written here.
+template <class Commit> static int32_t resolve_opening(stark_ctx* ctx, const Commit& c, const FriRequest& q, const fr_t** from, size_t* len) {
+    if (q.kind == 0) {
+        if (q.which >= c.layers()) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range");
+        *from = c.layer(q.which, len); return STARK_OK;
+    }
+    if (q.which >= c.layers() || q.level >= c.levels(q.which)) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
+    *from = c.level(q.which, q.level, len); return STARK_OK;
+}
+struct StateArrays {                                    // a stark_fri_state
+    const stark_fri_state* S;
+    size_t layers() const { return S->f.size(); }
+    const fr_t* layer(size_t l, size_t* len) const { *len = S->n[l]; return S->f[l]; }
+    size_t levels(size_t l) const { return S->trees[l]->levels.size(); }
+    const fr_t* level(size_t l, size_t v, size_t* len) const { *len = S->trees[l]->lens[v]; return S->trees[l]->levels[v]; }
+};
 // fri_prove_queries + payload assembly + canonical encoding (fri.rs:355-466, 613-640).  The indices of every opened value depend
 // only on the roots, so the query phase first RECORDS what it will read (fri_plan.hpp: the same code against a recording source),
 // fetches all of it — a few thousand layer elements and tree nodes spread over every layer and level — with ONE gather launch and
 // one download, and then assembles the proof from that list.  (One synchronisation instead of one per opened level.)
 static int32_t prove_queries_encode(stark_ctx* ctx, stark_fri_state* S, size_t n0, size_t r, stark_proof* P) {
-    FriPlan plan; plan.r = r; STARK_TRY(shape_of_state(ctx, S, n0, plan.shape));
+    STARK_TRY(state_roots(S));
     DeviceHasher H0(ctx); MemoHasher H(H0);
-    { int32_t rc = fri_plan_make(plan, H); if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: bad index"); if (rc) return rc; }
+    FriPlan plan; STARK_TRY(make_query_plan(ctx, plan, n0, S->schedule.data(), S->schedule.size(), S->roots.data(), r, H));
     const size_t nreq = plan.req.size();
     std::vector<fr_t> vals(nreq);
     if (nreq) {
-        auto resolve = [&](const FriRequest& q, FriOpening& o) -> int32_t {              // every value is on this GPU
-            if (q.kind == 0) {
-                if (q.which >= S->f.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range");
-                o = {S->f[q.which], S->n[q.which], 0, q.index}; return STARK_OK;
-            }
-            if (q.which >= S->trees.size() || q.level >= S->trees[q.which]->levels.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
-            const stark_tree* T = S->trees[q.which];
-            o = {T->levels[q.level], T->lens[q.level], 0, q.index}; return STARK_OK;
-        };
+        OpeningGather G(ctx); const StateArrays A{S};
+        for (size_t i = 0; i < nreq; ++i) { const fr_t* from; size_t len; STARK_TRY(resolve_opening(ctx, A, plan.req[i], &from, &len)); STARK_TRY(G.add(from, len, plan.req[i].index, i)); }
         DevBuf dout; STARK_HIP(ctx, dout.alloc(ctx, nreq * sizeof(fr_t)));
-        STARK_TRY(gather_openings(ctx, plan, 0, resolve, dout.fr(), vals.data()));
+        STARK_TRY(G.launch(dout.fr()));
+        STARK_HIP(ctx, dout.download_sync(vals.data(), nreq * sizeof(fr_t))); G.synced();
     }
-    ReplaySource rep(vals.data(), vals.size());
-    int32_t rc = assemble_proof(plan.shape, r, H, rep, P->bytes, P->size_estimate);
-    if (rc == -1 || (rc == 0 && rep.pos != vals.size())) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: value list does not match the plan");
-    return rc;
+    return assemble_from_values(ctx, plan.shape, r, H, vals.data(), nreq, P);
 }
 
 // Query plan of a commit phase whose layers live elsewhere (sharded over ranks): see fri_plan.hpp.
 struct stark_fri_plan { CtxRef ref_; stark_ctx* ctx = nullptr; FriPlan plan; };
 
+// The prove once f0 is known: commit phase, query phase, stage times.  The first stage is stage0_ms plus what has passed since t_start (the
+// caller's own work on f0: build_f0, a merge, or nothing).
+static int32_t prove_from_f0(stark_ctx* ctx, const fr_t* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double stage0_ms,
+                             Clock::time_point t_start, stark_proof** out) {
+    const auto t1 = Clock::now();
+    std::unique_ptr<stark_fri_state> S; { stark_fri_state* s = nullptr; STARK_TRY(fri_build_impl(ctx, f0, n0, schedule, L, seed_z, &s)); S.reset(s); }
+    const auto t2 = Clock::now();
+    std::unique_ptr<stark_proof> P(new stark_proof());
+    { const int32_t rc = prove_queries_encode(ctx, S.get(), n0, r, P.get()); S.reset(); if (rc) return rc; }
+    const auto t3 = Clock::now();
+    P->ms[0] = stage0_ms + ms_between(t_start, t1); P->ms[1] = ms_between(t1, t2); P->ms[2] = ms_between(t2, t3);
+    *out = P.release(); return STARK_OK;
+}
 static int32_t prove_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t* f0_in, size_t n0,
                           const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
     if (!is_pow2(n0)) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two (radix-2 domain)");
-    stark_proof* P = new stark_proof(); auto t0 = Clock::now();
+    const auto t0 = Clock::now();
     DevBuf f0buf; const fr_t* f0 = f0_in;
     if (!f0) {
-        if (f0buf.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) { delete P; return ctx->fail(STARK_ERR_OOM, "f0"); }
-        int32_t rc = build_f0_dev_impl(ctx, a, s, e, t, n0, f0buf.fr(), nullptr); if (rc) { delete P; return rc; }
+        if (f0buf.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "f0");
+        STARK_TRY(build_f0_dev_impl(ctx, a, s, e, t, n0, f0buf.fr(), nullptr));
         f0 = f0buf.fr();
     }
-    auto t1 = Clock::now();
-    stark_fri_state* S = nullptr; { int32_t rc = fri_build_impl(ctx, f0, n0, schedule, L, seed_z, &S); if (rc) { delete P; return rc; } }
-    auto t2 = Clock::now();
-    { int32_t rc = prove_queries_encode(ctx, S, n0, r, P); delete S; if (rc) { delete P; return rc; } }
-    auto t3 = Clock::now();
-    P->ms[0] = ms_between(t0, t1); P->ms[1] = ms_between(t1, t2); P->ms[2] = ms_between(t2, t3);
-    *out = P; return STARK_OK;
+    return prove_from_f0(ctx, f0, n0, schedule, L, r, seed_z, 0.0, t0, out);
 }
-
-// The tail of ONE trace of a batch prove on context c, its challenge z known: merge into f0buf (n0 elements, c's memory), commit phase, query phase.
-// stage_ms: shared_ms (the batch's sponge stage) + the merge, the commit phase, the query phase.  Used by the worker contexts and by a pass of one trace.
-static int32_t prove_tail_single(stark_ctx* c, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t& omega, const fr_t& z, fr_t* f0buf, size_t n0,
+// The tail of ONE trace of a batch prove (a pass of one trace), its challenge z known: the merge into f0, then the prove from f0.
+// stage_ms: shared_ms (the batch's sponge stage) + the merge, the commit phase, the query phase.
+static int32_t prove_tail_single(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t& omega, const fr_t& z, size_t n0,
                                  const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, stark_proof** out) {
-    auto u0 = Clock::now();
-    STARK_TRY(ali_merge_dev_impl(c, a, s, e, t, nullptr, host::h_zero(), omega, z, n0, f0buf, nullptr));
-    auto u1 = Clock::now();
-    stark_fri_state* S = nullptr; STARK_TRY(fri_build_impl(c, f0buf, n0, schedule, L, seed_z, &S));
-    auto u2 = Clock::now();
-    stark_proof* P = new stark_proof();
-    { int32_t rc = prove_queries_encode(c, S, n0, r, P); delete S; if (rc) { delete P; return rc; } }
-    auto u3 = Clock::now();
-    P->ms[0] = shared_ms + ms_between(u0, u1); P->ms[1] = ms_between(u1, u2); P->ms[2] = ms_between(u2, u3);
-    *out = P; return STARK_OK;
+    DevBuf f0buf; if (f0buf.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "f0");
+    const auto u0 = Clock::now();
+    STARK_TRY(ali_merge_dev_impl(ctx, a, s, e, t, nullptr, host::h_zero(), omega, z, n0, f0buf.fr(), nullptr));
+    return prove_from_f0(ctx, f0buf.fr(), n0, schedule, L, r, seed_z, shared_ms, u0, out);
 }
 
 // ---- the side-by-side tail of the batched provers: merge, commit phase and query phase of a pass of traces (fri_batch.hpp) ----------------
@@ -386,35 +400,20 @@ struct FriDevExec {
     int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h) { return leaf_pair_hash_on(ctx, cur, f, f_next, n, m, h); }
     int32_t pair_level(size_t arity, const DsBatchPairStream& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
     int32_t ds_level(size_t arity, const DsBatchStream& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
-    int32_t fork() {
-        STARK_TRY(ctx_side_stream(ctx, &side_st));
-        STARK_HIP(ctx, hipEventRecord(ctx->ev_fork, main_st)); STARK_HIP(ctx, hipStreamWaitEvent(side_st, ctx->ev_fork, 0));
-        forked = true; return STARK_OK;
-    }
+    int32_t fork() { STARK_TRY(ctx_fork(ctx, &side_st)); forked = true; return STARK_OK; }
     void side(bool on) { cur = on && side_st ? side_st : main_st; }
-    int32_t join() {
-        if (!forked) return STARK_OK;
-        STARK_HIP(ctx, hipEventRecord(ctx->ev_fork, side_st)); STARK_HIP(ctx, hipStreamWaitEvent(main_st, ctx->ev_fork, 0));
-        forked = false; return STARK_OK;
-    }
+    int32_t join() { if (forked) { STARK_TRY(ctx_join(ctx)); forked = false; } return STARK_OK; }
 };
 typedef FriBatchCommit<FriDevExec> FriDevBatch;
 constexpr size_t kMaxPassTraces = 32768;             // blockIdx.y of the merge and copy kernels is the trace
 // How many traces of n0 rows go into one pass (option "prove_batch_max_rows").
 static size_t pass_traces(const stark_ctx* ctx, size_t n0) { return std::min(std::max<size_t>(ctx->opt.prove_batch_max_rows / std::max<size_t>(n0, 1), 1), kMaxPassTraces); }
-// What the entry points check before any launch: the schedule divides n0 layer by layer (fri.rs:150).
-static bool schedule_divides(size_t n0, const size_t* schedule, size_t L) {
-    size_t n = n0; for (size_t l = 0; l < L; ++l) { if (schedule[l] < 2 || n % schedule[l]) return false; n /= schedule[l]; } return n0 != 0;
-}
 // Shapes, challenges and buffers of a pass; everything that may upload constants (and synchronise doing so) runs here, before the first launch.
 static int32_t batch_commit_begin(stark_ctx* ctx, FriDevBatch& C, size_t Bp, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z) {
-    if (!schedule_divides(n0, schedule, L)) return ctx->fail(STARK_ERR_INVALID_ARG, "schedule not dividing domain size");
-    std::vector<fr_t> z(L); { size_t n = n0; for (size_t l = 0; l < L; ++l) { STARK_TRY(sample_z(ctx, seed_z, l, n, &z[l])); n /= schedule[l]; } }
-    std::string err; const int32_t rc = C.init(Bp, n0, schedule, L, z.data(), err);
-    if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, err); if (rc == -2) return ctx->fail(STARK_ERR_UNSUPPORTED, err); if (rc) return rc;
-    stark_params* p = nullptr; STARK_TRY(ctx_transcript_params(ctx, &p));
-    for (size_t a : C.arity) STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(a), &p));
-    return STARK_OK;
+    std::string err; int32_t rc = C.shape(Bp, n0, schedule, L, err);
+    if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, err); if (rc == -2) return ctx->fail(STARK_ERR_UNSUPPORTED, err);
+    std::vector<stark_params*> mps; std::vector<fr_t> z; STARK_TRY(fri_prelude(ctx, C.n, C.arity, seed_z, mps, z));
+    return C.init(z.data());
 }
 // Layer 0 of a pass from a host table of per-trace device pointers: one copy kernel.
 static int32_t batch_fill_layer0(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, const uint64_t* const* f0) {
@@ -453,6 +452,13 @@ struct ReseedOnlyHasher : TrHasher {
         return dev.hash(tag, fields, k, n, out);
     }
 };
+struct BatchArrays {                                    // trace b of a pass (resolve_opening)
+    const FriDevBatch& C; size_t b;
+    size_t layers() const { return C.L + 1; }
+    const fr_t* layer(size_t l, size_t* len) const { *len = C.n[l]; return C.layer_at(b, l); }
+    size_t levels(size_t l) const { return C.trees[l].levels.size(); }
+    const fr_t* level(size_t l, size_t v, size_t* len) const { *len = C.trees[l].lens[v]; return C.level_at(b, l, v); }
+};
 static int32_t batch_queries(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, size_t n0, size_t r, stark_proof** out) {
     const size_t Bp = C.Bp, L = C.L, R = L + 1, q = r * L;
     std::vector<fr_t> rl(R * Bp), rt(R * Bp), seed(Bp), in(3 * q * Bp), idx(q * Bp);
@@ -469,47 +475,29 @@ static int32_t batch_queries(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, size
     }
     ReseedOnlyHasher H0(ctx); std::vector<std::unique_ptr<MemoHasher>> H(Bp); std::vector<FriPlan> plan(Bp);
     std::vector<size_t> row0(Bp + 1, 0);
-    std::vector<const fr_t*> base; std::map<const fr_t*, uint32_t> slot; std::vector<uint32_t> src; std::vector<uint64_t> ix, row;
+    OpeningGather G(ctx);                                                                                                // row: the running count over all proofs
     for (size_t b = 0; b < Bp; ++b) {
         H[b].reset(new MemoHasher(H0));
         H[b]->preload("FRI/seed", &rt[b * R], R, 1, &seed[b]);
         if (q) H[b]->preload("FRI/index", &in[3 * q * b], 3, q, &idx[q * b]);
-        plan[b].r = r;
-        { std::string err; if (!plan[b].shape.make(n0, C.sched.data(), L, &rt[b * R], err)) return ctx->fail(STARK_ERR_INVALID_ARG, err); }
-        { int32_t rc = fri_plan_make(plan[b], *H[b]); if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: bad index"); if (rc) return rc; }
-        for (const FriRequest& rq : plan[b].req) {
-            const fr_t* p = nullptr; size_t len = 0;
-            if (rq.kind == 0) { if (rq.which > L) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range"); p = C.layer_at(b, rq.which); len = C.n[rq.which]; }
-            else {
-                if (rq.which > L || rq.level >= C.trees[rq.which].levels.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
-                p = C.level_at(b, rq.which, rq.level); len = C.trees[rq.which].lens[rq.level];
-            }
-            if (rq.index >= len) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: opening index out of range");
-            auto it = slot.emplace(p, (uint32_t)base.size()).first;
-            if (it->second == base.size()) base.push_back(p);
-            src.push_back(it->second); ix.push_back(rq.index); row.push_back(row.size());
-        }
-        row0[b + 1] = row.size();
+        STARK_TRY(make_query_plan(ctx, plan[b], n0, C.sched.data(), L, &rt[b * R], r, *H[b]));
+        const BatchArrays A{C, b};
+        for (const FriRequest& rq : plan[b].req) { const fr_t* from; size_t len; STARK_TRY(resolve_opening(ctx, A, rq, &from, &len)); STARK_TRY(G.add(from, len, rq.index, G.size())); }
+        row0[b + 1] = G.size();
     }
-    const size_t k = row.size();
+    const size_t k = G.size();
     std::vector<fr_t> vals(k);
     if (k) {                                                                                                             // ONE gather over all proofs' requests, one download
-        const fr_t** d_base = nullptr; uint32_t* d_src = nullptr; uint64_t *d_ix = nullptr, *d_row = nullptr; void* d_out = nullptr;
-        STARK_TRY(X.put(base, &d_base)); STARK_TRY(X.put(src, &d_src)); STARK_TRY(X.put(ix, &d_ix)); STARK_TRY(X.put(row, &d_row)); STARK_TRY(X.alloc(k * sizeof(fr_t), &d_out));
-        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)d_base, (const uint32_t*)d_src, (const uint64_t*)d_ix, (const uint64_t*)d_row, (uint64_t)k, (fr_t*)d_out);
-        STARK_HIP(ctx, hipGetLastError());
+        void* d_out = nullptr; STARK_TRY(X.alloc(k * sizeof(fr_t), &d_out));
+        STARK_TRY(G.launch((fr_t*)d_out));
         STARK_HIP(ctx, hipMemcpyAsync(vals.data(), d_out, k * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); X.synced();
+    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); X.synced(); G.synced();
     for (size_t b = 0; b < Bp; ++b) {
-        ReplaySource rep(vals.data() + row0[b], row0[b + 1] - row0[b]);
-        stark_proof* P = new stark_proof();
-        const int32_t rc = assemble_proof(plan[b].shape, r, *H[b], rep, P->bytes, P->size_estimate);
-        if (rc || rep.pos != rep.n) {
-            delete P; for (size_t j = 0; j < b; ++j) { delete out[j]; out[j] = nullptr; }
-            return rc > 0 ? rc : ctx->fail(STARK_ERR_INVALID_ARG, "query phase: value list does not match the plan");
-        }
-        out[b] = P;
+        std::unique_ptr<stark_proof> P(new stark_proof());
+        const int32_t rc = assemble_from_values(ctx, plan[b].shape, r, *H[b], vals.data() + row0[b], row0[b + 1] - row0[b], P.get());
+        if (rc) { for (size_t j = 0; j < b; ++j) { delete out[j]; out[j] = nullptr; } return rc; }
+        out[b] = P.release();
     }
     return STARK_OK;
 }
@@ -546,7 +534,7 @@ static int32_t prove_f0_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* con
     const size_t per = pass_traces(ctx, n0);
     for (size_t p0 = 0; p0 < B; p0 += per) {
         const size_t Bp = std::min(per, B - p0);
-        const int32_t rc = Bp == 1 ? prove_impl(ctx, nullptr, nullptr, nullptr, nullptr, as_fr(f0[p0]), n0, schedule, L, r, seed_z, &out[p0])
+        const int32_t rc = Bp == 1 ? prove_from_f0(ctx, as_fr(f0[p0]), n0, schedule, L, r, seed_z, 0.0, Clock::now(), &out[p0])
                                    : prove_pass_batch(ctx, Bp, nullptr, nullptr, f0 + p0, n0, schedule, L, r, seed_z, 0.0, out + p0);
         if (rc) { free_proofs(out, B); return rc; }
     }
@@ -557,11 +545,10 @@ static int32_t commit_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const
     const size_t per = pass_traces(ctx, n0), R = L + 1;
     for (size_t p0 = 0; p0 < B; p0 += per) {
         const size_t Bp = std::min(per, B - p0);
-        if (Bp == 1) {
-            stark_fri_state* S = nullptr; STARK_TRY(fri_build_impl(ctx, as_fr(f0[p0]), n0, schedule, L, seed_z, &S));
-            const int32_t rc = state_roots(S);
-            if (!rc) for (size_t l = 0; l < R; ++l) store_fr(roots + 4 * (p0 * R + l), S->roots[l]);
-            delete S; if (rc) return rc;
+        if (Bp == 1) {                                                                          // a pass of one trace: the single commit phase
+            std::unique_ptr<stark_fri_state> S; { stark_fri_state* s = nullptr; STARK_TRY(fri_build_impl(ctx, as_fr(f0[p0]), n0, schedule, L, seed_z, &s)); S.reset(s); }
+            STARK_TRY(state_roots(S.get()));
+            for (size_t l = 0; l < R; ++l) store_fr(roots + 4 * (p0 * R + l), S->roots[l]);
             continue;
         }
         FriDevExec X(ctx); FriDevBatch C(X);
@@ -603,7 +590,7 @@ static int32_t ali_merge_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* co
 // (fri.rs:548-557: n0/16 dependent permutations per column, one wave each): four waves of the chip are busy for 99 % of the time.  The chains of
 // different traces are independent, so all 4 * B of them run in ONE launch; the two Fiat-Shamir hashes per trace (ALI/seed, ALI/DEEP) are
 // one launch each for the whole batch; merge, fri_build and the query phase of the traces then run side by side, pass by pass (prove_pass_batch;
-// a pass of one trace is the single tail on this context).  Option "prove_batch_workers" = 1 keeps the earlier tail: trace after trace on four worker contexts.
+// a pass of one trace is the single tail, prove_tail_single).
 // Every proof is byte-for-byte what stark_deep_fri_prove_dev returns for that trace alone.
 static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, size_t n0,
                                 const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
@@ -636,49 +623,17 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
     std::vector<fr_t> fu(B);
     STARK_HIP(ctx, hipMemcpyAsync(fu.data(), fused.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     auto t1 = Clock::now();
-    // (3) merge, commit phase, query phase: side by side per pass (prove_pass_batch), or — option "prove_batch_workers" — trace after trace.  A single tail is
-    // latency-bound (a few ms of small dependent launches), so the worker form runs up to four of them at a time: worker contexts of this context (same
-    // device, private streams, own pools), one host thread each, traces dealt round-robin.  The inputs are resident and this context's stream is idle
-    // (synchronised above), so the workers' streams may read them.
+    // (3) merge, commit phase, query phase: side by side per pass (prove_pass_batch); a pass of one trace takes the single tail
     const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));
     const double shared_ms = ms_between(t0, t1);
-    if (!ctx->opt.prove_batch_workers) {
-        std::vector<fr_t> zs(B); for (size_t p = 0; p < B; ++p) { fr_t beta; ali_z_beta_from_fused(fu[p], n0, seed_f[p], &zs[p], &beta); }
-        const size_t per = pass_traces(ctx, n0);
-        for (size_t p0 = 0; p0 < B; p0 += per) {
-            const size_t Bp = std::min(per, B - p0);
-            int32_t rc = STARK_OK;
-            if (Bp == 1) {                                                                      // the single tail, unchanged
-                DevBuf f0buf; if (f0buf.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) rc = ctx->fail(STARK_ERR_OOM, "f0");
-                if (!rc) rc = prove_tail_single(ctx, as_fr(a[p0]), as_fr(s[p0]), as_fr(e[p0]), as_fr(t[p0]), omega, zs[p0], f0buf.fr(), n0, schedule, L, r, seed_z, shared_ms, &out[p0]);
-            } else {
-                const uint64_t* const* const cols[4] = {a + p0, s + p0, e + p0, t + p0};
-                rc = prove_pass_batch(ctx, Bp, cols, zs.data() + p0, nullptr, n0, schedule, L, r, seed_z, shared_ms, out + p0);
-            }
-            if (rc) { free_proofs(out, B); return rc; }
-        }
-        return STARK_OK;
-    }
-    const size_t NT = std::min<size_t>(B, 4);
-    std::vector<stark_ctx*> cx(NT); for (size_t w = 0; w < NT; ++w) STARK_TRY(ctx_aux(ctx, w, &cx[w]));
-    std::vector<int32_t> rcs(NT, STARK_OK);
-    auto worker = [&](size_t w) {
-        stark_ctx* c = cx[w];
-        int32_t rc = ctx_enter(c); if (rc) { rcs[w] = rc; return; }
-        DevBuf f0buf; if (f0buf.alloc(c, n0 * sizeof(fr_t)) != hipSuccess) { rcs[w] = c->fail(STARK_ERR_OOM, "f0"); return; }
-        for (size_t p = w; p < B; p += NT) {
-            fr_t z, beta; ali_z_beta_from_fused(fu[p], n0, seed_f[p], &z, &beta);
-            rc = prove_tail_single(c, as_fr(a[p]), as_fr(s[p]), as_fr(e[p]), as_fr(t[p]), omega, z, f0buf.fr(), n0, schedule, L, r, seed_z, shared_ms, &out[p]); if (rc) { rcs[w] = rc; return; }
-        }
-        (void)hipStreamSynchronize(c->stream);
-    };
-    if (NT == 1) worker(0);
-    else { std::vector<std::thread> th; for (size_t w = 0; w < NT; ++w) th.emplace_back(worker, w); for (auto& x : th) x.join(); }
-    STARK_TRY(ctx_enter(ctx));
-    for (size_t w = 0; w < NT; ++w) if (rcs[w]) {
-        ctx->err = cx[w]->err;
-        for (size_t p = 0; p < B; ++p) if (out[p]) { delete out[p]; out[p] = nullptr; }
-        return rcs[w];
+    std::vector<fr_t> zs(B); for (size_t p = 0; p < B; ++p) { fr_t beta; ali_z_beta_from_fused(fu[p], n0, seed_f[p], &zs[p], &beta); }
+    const size_t per = pass_traces(ctx, n0);
+    for (size_t p0 = 0; p0 < B; p0 += per) {
+        const size_t Bp = std::min(per, B - p0);
+        const uint64_t* const* const cols[4] = {a + p0, s + p0, e + p0, t + p0};
+        const int32_t rc = Bp == 1 ? prove_tail_single(ctx, as_fr(a[p0]), as_fr(s[p0]), as_fr(e[p0]), as_fr(t[p0]), omega, zs[p0], n0, schedule, L, r, seed_z, shared_ms, &out[p0])
+                                   : prove_pass_batch(ctx, Bp, cols, zs.data() + p0, nullptr, n0, schedule, L, r, seed_z, shared_ms, out + p0);
+        if (rc) { free_proofs(out, B); return rc; }
     }
     return STARK_OK;
 }
@@ -789,7 +744,7 @@ int32_t stark_deep_fri_prove_f0_batch_dev(stark_ctx_t* ctx, size_t batch, const 
     for (size_t p = 0; p < batch; ++p) if (!f0[p]) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     if (!is_pow2(n0) || n0 <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two above 1 (radix-2 domain)");
-    if (!schedule_divides(n0, schedule, L)) return ctx->fail(STARK_ERR_INVALID_ARG, "schedule not dividing domain size");
+    { std::vector<size_t> n, arity; STARK_TRY(layers_or_fail(ctx, n0, schedule, L, n, arity)); }
     return prove_f0_batch_impl(ctx, batch, f0, n0, schedule, L, r, seed_z, out);
 }
 int32_t stark_fri_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, uint64_t* roots) {
@@ -798,7 +753,7 @@ int32_t stark_fri_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_
     if (!roots || !f0 || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     for (size_t p = 0; p < batch; ++p) if (!f0[p]) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    if (!schedule_divides(n0, schedule, L)) return ctx->fail(STARK_ERR_INVALID_ARG, n0 ? "schedule not dividing domain size" : "empty layer");
+    { std::vector<size_t> n, arity; STARK_TRY(layers_or_fail(ctx, n0, schedule, L, n, arity)); }
     return commit_batch_impl(ctx, batch, f0, n0, schedule, L, seed_z, roots);
 }
 int32_t stark_ali_merge_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t,
@@ -845,11 +800,9 @@ int32_t stark_fri_plan_create(stark_ctx_t* ctx, const uint64_t* roots, size_t n0
     if (!ctx || !roots || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     std::vector<fr_t> rt(L + 1); for (size_t l = 0; l <= L; ++l) rt[l] = load_fr(roots + 4 * l);
-    stark_fri_plan* P = new stark_fri_plan(); P->ref_.bind(ctx); P->ctx = ctx; P->plan.r = r;
-    std::string err; if (!P->plan.shape.make(n0, schedule, L, rt.data(), err)) { delete P; return ctx->fail(STARK_ERR_INVALID_ARG, err); }
-    DeviceHasher H(ctx); int32_t rc = fri_plan_make(P->plan, H);
-    if (rc) { delete P; return rc == -1 ? ctx->fail(STARK_ERR_INVALID_ARG, "query plan") : rc; }
-    *out = P; return STARK_OK;
+    std::unique_ptr<stark_fri_plan> P(new stark_fri_plan()); P->ref_.bind(ctx); P->ctx = ctx;
+    DeviceHasher H(ctx); STARK_TRY(make_query_plan(ctx, P->plan, n0, schedule, L, rt.data(), r, H, "query plan"));
+    *out = P.release(); return STARK_OK;
 }
 size_t stark_fri_plan_num_requests(stark_fri_plan_t* p) { return p ? p->plan.req.size() : 0; }
 int32_t stark_fri_plan_requests(stark_fri_plan_t* p, uint32_t* kind, uint32_t* which, uint32_t* level, uint64_t* index) {
@@ -862,11 +815,9 @@ int32_t stark_fri_plan_assemble(stark_fri_plan_t* p, const uint64_t* values, siz
     stark_ctx* ctx = p->ctx;
     if (n_values != p->plan.req.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "value count differs from the plan's request count");
     std::vector<fr_t> v(n_values); for (size_t i = 0; i < n_values; ++i) v[i] = load_fr(values + 4 * i);
-    ReplaySource src(v.data(), v.size()); DeviceHasher H(ctx);
-    stark_proof* P = new stark_proof();
-    int32_t rc = assemble_proof(p->plan.shape, p->plan.r, H, src, P->bytes, P->size_estimate);
-    if (rc || src.pos != v.size()) { delete P; return ctx->fail(STARK_ERR_INVALID_ARG, "assemble: values do not match the plan"); }
-    *out = P; return STARK_OK;
+    DeviceHasher H(ctx); std::unique_ptr<stark_proof> P(new stark_proof());
+    STARK_TRY(assemble_from_values(ctx, p->plan.shape, p->plan.r, H, v.data(), v.size(), P.get(), "assemble: values do not match the plan"));
+    *out = P.release(); return STARK_OK;
 }
 int32_t stark_fri_plan_free(stark_fri_plan_t* p) { if (!p) return STARK_ERR_INVALID_ARG; delete p; return STARK_OK; }
 

@@ -40,8 +40,7 @@ int32_t stark::verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, 
         for (size_t i = 0; i < items.size(); ++i) {
             hipStream_t st = main_st;
             if (i == 1) {                                              // fork: the rest of this depth on the side stream
-                { int32_t rc = ctx_side_stream(ctx, &side); if (rc) return bail(rc); }
-                if (hipEventRecord(ctx->ev_fork, main_st) != hipSuccess || hipStreamWaitEvent(side, ctx->ev_fork, 0) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "fork"));
+                { int32_t rc = ctx_fork(ctx, &side); if (rc) return bail(rc); }
                 forked = true;
             }
             if (i >= 1) st = side;
@@ -56,7 +55,7 @@ int32_t stark::verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, 
             if (rc) return bail(rc);
         }
         if (items.size() > 1) {                                        // join before the next depth reads these digests
-            if (hipEventRecord(ctx->ev_fork, side) != hipSuccess || hipStreamWaitEvent(main_st, ctx->ev_fork, 0) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "join"));
+            int32_t rc = ctx_join(ctx); if (rc) return bail(rc);
         }
         g0 = g1;
     }

@@ -64,9 +64,8 @@ struct stark_ctx {
     hipStream_t side_stream = nullptr;               // lazily created: small independent jobs that run underneath a big one (fri_build)
     std::string err;
     int live_handles = 0; bool destroy_pending = false;   // see CtxRef
-    std::vector<stark_ctx*> aux;                     // worker contexts on the same device (private streams) for the tails of a batch prove; created lazily, torn down with this context
     hipEvent_t ev0 = nullptr, ev1 = nullptr;         // stark_timer_start / stop
-    hipEvent_t ev_fork = nullptr;                    // orders the side stream after the main one
+    hipEvent_t ev_fork = nullptr;                    // orders the side stream after the main one and back (ctx_fork / ctx_join)
     // lazily created constants
     stark_params* tparams = nullptr;                 // transcript params (t=17, "POSEIDON-T17-X5-TRANSCRIPT")
     std::map<int, stark_params*> merkle_params;      // poseidon_params_for_width(t)
@@ -104,7 +103,6 @@ struct stark_ctx {
         bool fri_side_pair = true;       // fri_build: the small layers' commitments on the side stream in the wave-pair form at every size (see side_commit); 0 = the latency forms (comparison)
         size_t sumcheck_verify_batch_max_slots = (size_t)1 << 25;   // a plan of the batched sum-check verifiers is run once it holds this many pool slots (1 GiB of field elements): device memory stays bounded whatever the batch
         size_t prove_batch_max_rows = (size_t)1 << 22;   // the batched DEEP-FRI provers cut a batch into passes of at most this many rows (traces x n0) whose tails run side by side (fri_batch.hpp); device memory per pass stays near 70 B per row
-        bool prove_batch_workers = false;                // stark_deep_fri_prove_batch_dev: 1 = the tails trace after trace on four worker contexts, as before the side-by-side tail (comparison)
     } opt;
     bool side_commit = false;            // set while fri_build enqueues work that runs underneath the 2^n-leaf launch: Merkle levels and leaf layers of t = 9, 17 take the
                                          // wave-pair form (64 sponges per two waves) instead of one wave or five waves per sponge, which would hold many wave slots at lone-wave speed
@@ -162,8 +160,12 @@ int32_t ctx_transcript_params(stark_ctx* ctx, stark_params** out);
 int32_t ctx_merkle_params(stark_ctx* ctx, int t, stark_params** out);
 int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out);
 int32_t ctx_side_stream(stark_ctx* ctx, hipStream_t* out);
+// Fork: what is enqueued on *side from here on runs after everything enqueued on the context's stream so far, and concurrently with what that stream
+// receives next.  Join: the context's stream continues after everything enqueued on the side stream.  Events only; the host is not synchronised.
+// After a failure the caller drains whichever streams it has enqueued on before it releases what they use.
+int32_t ctx_fork(stark_ctx* ctx, hipStream_t* side);
+int32_t ctx_join(stark_ctx* ctx);
 int32_t ctx_enter(stark_ctx* ctx);                                   // makes the context's device current (every entry point)
-int32_t ctx_aux(stark_ctx* ctx, size_t k, stark_ctx** out);          // the k-th worker context of `ctx` (same device, private stream, the parent's options)
 void comm_destroy(stark_ctx* ctx);
 void ntt_set_attrs();                                                // per-device kernel attributes of the NTT kernels (capi_ntt.hip)
 void ntt_plans_free(stark_ctx* ctx);

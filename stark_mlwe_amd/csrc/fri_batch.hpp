@@ -62,17 +62,17 @@ template <class X> struct FriBatchCommit {
     explicit FriBatchCommit(X& x_) : x(x_) {}
 
     int32_t alloc_fr(size_t k, fr_t** out) { void* p = nullptr; FB_TRY(x.alloc((k ? k : 1) * sizeof(fr_t), &p)); *out = (fr_t*)p; return 0; }
-    // shapes, the layers, the root and label buffers; z_[l] = fri_sample_z_ell(seed_z, l, n[l]).  The caller then fills f[0] and calls run().
-    int32_t init(size_t Bp_, size_t n0, const size_t* schedule, size_t L_, const fr_t* z_, std::string& err) {
-        Bp = Bp_; L = L_; sched.assign(schedule, schedule + L); z.assign(z_, z_ + L);
-        if (!n0 || !Bp) { err = "empty layer"; return -1; }
-        n.assign(1, n0);
-        for (size_t l = 0; l < L; ++l) { if (sched[l] < 2 || n[l] % sched[l]) { err = "schedule not dividing domain size"; return -1; } n.push_back(n[l] / sched[l]); }   // fri.rs:150
-        arity.clear();
-        for (size_t l = 0; l <= L; ++l) {
-            arity.push_back(pick_arity_for_layer(n[l], l < L ? sched[l] : 1));                                                  // fri.rs:220-229
-            if (arity[l] < 2 && n[l] > 1) { err = "arity 1 with more than one leaf never terminates in the reference"; return -2; }
-        }
+    // The shapes of a pass (fri_layers).  -1: an empty layer or a schedule that does not divide; -2: a layer with arity 1.
+    int32_t shape(size_t Bp_, size_t n0, const size_t* schedule, size_t L_, std::string& err) {
+        Bp = Bp_; L = L_; sched.assign(schedule, schedule + L);
+        const LayerShape sh = Bp ? fri_layers(n0, schedule, L, n, arity) : LayerShape::empty_layer;
+        if (sh == LayerShape::arity_one) { err = "arity 1 with more than one leaf never terminates in the reference"; return -2; }
+        if (sh != LayerShape::ok) { err = layer_shape_text(sh); return -1; }
+        return 0;
+    }
+    // After shape(): the layers, the root and label buffers; z_[l] = fri_sample_z_ell(seed_z, l, n[l]).  The caller then fills f[0] and calls run().
+    int32_t init(const fr_t* z_) {
+        z.assign(z_, z_ + L);
         f.assign(L + 1, nullptr); trees.assign(L + 1, Tree());
         for (size_t l = 0; l <= L; ++l) FB_TRY(alloc_fr(Bp * n[l], &f[l]));
         FB_TRY(alloc_fr((L + 1) * Bp, &roots));

@@ -42,20 +42,35 @@ inline size_t pick_arity_for_layer(size_t n, size_t m) {    // fri.rs:220-229
 inline bool hashed_arity(size_t a) { return a == 128 || a == 64 || a == 32 || a == 16 || a == 8; }   // fri.rs:275
 inline int ilog2_ceil(size_t x) { int k = 0; while (((size_t)1 << k) < x) ++k; return k; }
 
+// The layers of a commit phase: their sizes under the schedule (fri.rs:150) and their Merkle arities (fri.rs:220-229), written once.  Every user maps
+// the result to its own return code and message (layer_shape_text has the wording they share).  arity_one: some layer of more than one leaf gets
+// arity 1, a tree that never terminates in the reference; n and arity are complete all the same, and the first two results leave them unspecified.
+enum class LayerShape { ok, empty_layer, not_dividing, arity_one };
+inline LayerShape fri_layers(size_t n0, const size_t* sched, size_t L, std::vector<size_t>& n, std::vector<size_t>& arity) {
+    if (!n0) return LayerShape::empty_layer;
+    n.assign(1, n0); arity.clear();
+    for (size_t l = 0; l < L; ++l) { if (sched[l] < 2 || n[l] % sched[l]) return LayerShape::not_dividing; n.push_back(n[l] / sched[l]); }
+    LayerShape rc = LayerShape::ok;
+    for (size_t l = 0; l <= L; ++l) { arity.push_back(pick_arity_for_layer(n[l], l < L ? sched[l] : 1)); if (arity[l] < 2 && n[l] > 1) rc = LayerShape::arity_one; }
+    return rc;
+}
+inline const char* layer_shape_text(LayerShape s) {
+    return s == LayerShape::empty_layer ? "empty layer" : s == LayerShape::not_dividing ? "schedule not dividing domain size" : s == LayerShape::arity_one ? "layer with arity 1" : "";
+}
+
 // Shapes of the L+1 committed layers: sizes, Merkle arities, leaf kinds, level lengths; plus the roots.
 struct FriShape {
     size_t n0 = 0; std::vector<size_t> schedule, n, arity; std::vector<char> hashed;
     std::vector<std::vector<size_t>> lens;           // lens[l][v] = number of nodes of tree l at level v (level 0 = leaf digests)
     std::vector<fr_t> roots;
     bool make(size_t n0_, const size_t* sched, size_t L, const fr_t* roots_, std::string& err) {
-        if (!n0_) { err = "empty layer"; return false; }
-        n0 = n0_; schedule.assign(sched, sched + L); n.assign(1, n0);
-        for (size_t l = 0; l < L; ++l) { if (sched[l] < 2 || n.back() % sched[l]) { err = "schedule not dividing domain size"; return false; } n.push_back(n.back() / sched[l]); }   // fri.rs:150
-        arity.clear(); hashed.clear(); lens.clear();
+        const LayerShape sh = fri_layers(n0_, sched, L, n, arity);                        // arity 1 is refused here: its level lengths never reach 1
+        if (sh != LayerShape::ok) { err = layer_shape_text(sh); return false; }
+        n0 = n0_; schedule.assign(sched, sched + L);
+        hashed.clear(); lens.clear();
         for (size_t l = 0; l <= L; ++l) {
-            size_t a = pick_arity_for_layer(n[l], l < L ? sched[l] : 1); arity.push_back(a); hashed.push_back(hashed_arity(a) ? 1 : 0);
+            const size_t a = arity[l]; hashed.push_back(hashed_arity(a) ? 1 : 0);
             std::vector<size_t> lv(1, n[l]); while (lv.back() > 1) lv.push_back((lv.back() + a - 1) / a);                       // merkle/src/lib.rs:166-190
-            if (a < 2 && n[l] > 1) { err = "layer with arity 1"; return false; }
             lens.push_back(lv);
         }
         roots.assign(roots_, roots_ + L + 1);

@@ -33,7 +33,8 @@ static bool fri_shard_plan(size_t n0, const size_t* sched, size_t L, int W, FriS
     if (n0 % (size_t)W) { err = "n0 must divide over the ranks"; return false; }
     if (L && !sched) { err = "schedule"; return false; }
     P = FriShardPlan(); P.W = W; P.n0 = n0; P.L = L; P.sched.assign(sched, sched + L);
-    if (!fri_layer_shape(n0, sched, L, P.n, P.arity, err)) return false;
+    { const LayerShape sh = fri_layers(n0, sched, L, P.n, P.arity);                      // arity 1 passes: merkle_build_on refuses it (STARK_ERR_UNSUPPORTED)
+      if (sh == LayerShape::empty_layer || sh == LayerShape::not_dividing) { err = layer_shape_text(sh); return false; } }
     bool prev = true; P.T = L + 1;
     for (size_t l = 0; l <= L; ++l) {
         const size_t m = P.m(l), a = P.arity[l];
@@ -226,6 +227,7 @@ static int32_t shard_query_fill(stark_ctx* ctx, const FriShardPlan& P, FriShardR
     STARK_TRY(coll_alloc(ctx, K, std::max<size_t>(nreq, 1) * sizeof(fr_t)));
     STARK_HIP(ctx, hipMemsetAsync(K.coll.p, 0, nreq * sizeof(fr_t), ctx->stream));
     // a value of a sharded layer or of a lower tree is owned by the rank whose block holds it, any other (replicated layer, tree top) by rank 0
+    struct FriOpening { const fr_t* src; size_t len; uint64_t owner, index; };
     auto resolve = [&](const FriRequest& r, FriOpening& o) -> int32_t {
         if (r.which > P.L) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: layer out of range");
         const size_t l = r.which;
@@ -246,14 +248,19 @@ static int32_t shard_query_fill(stark_ctx* ctx, const FriShardPlan& P, FriShardR
         }
         return STARK_OK;
     };
-    return gather_openings(ctx, plan, (uint64_t)K.rank, resolve, K.coll.fr(), nullptr);
+    OpeningGather G(ctx);                                                                  // the rows of the other ranks stay zero for the all-reduce
+    for (size_t i = 0; i < nreq; ++i) {
+        FriOpening o; STARK_TRY(resolve(plan.req[i], o));
+        if (o.owner == (uint64_t)K.rank) STARK_TRY(G.add(o.src, o.len, o.index, i));
+    }
+    STARK_TRY(G.launch(K.coll.fr()));
+    if (G.size()) { STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); G.synced(); }       // the host index arrays end here
+    return STARK_OK;
 }
 static int32_t shard_queries(const ShardColl& C, const FriShardPlan& P, std::vector<FriShardRank>& K, size_t r, std::vector<stark_proof*>& out) {
     stark_ctx* ctx = C.ctx;
-    FriPlan plan; plan.r = r;
-    { std::string err; if (!plan.shape.make(P.n0, P.sched.data(), P.L, K[0].roots.data(), err)) return ctx->fail(STARK_ERR_INVALID_ARG, err); }
     DeviceHasher H0(ctx); MemoHasher H(H0);
-    { int32_t rc = fri_plan_make(plan, H); if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: bad index"); if (rc) return rc; }
+    FriPlan plan; STARK_TRY(make_query_plan(ctx, plan, P.n0, P.sched.data(), P.L, K[0].roots.data(), r, H));
     const size_t nreq = plan.req.size();
     std::vector<void*> buf;
     for (auto& k : K) {
@@ -268,12 +275,10 @@ static int32_t shard_queries(const ShardColl& C, const FriShardPlan& P, std::vec
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (auto& k : K) {
         ctx_release(ctx, k.coll.release());
-        ReplaySource rep(k.table.data(), nreq);
-        stark_proof* Pf = new stark_proof();
-        int32_t rc = assemble_proof(plan.shape, r, H, rep, Pf->bytes, Pf->size_estimate);
-        if (rc == -1 || (rc == 0 && rep.pos != nreq)) rc = ctx->fail(STARK_ERR_INVALID_ARG, "query phase: value list does not match the plan");
-        if (rc) { delete Pf; for (auto* x : out) delete x; out.clear(); return rc; }
-        out.push_back(Pf);
+        std::unique_ptr<stark_proof> Pf(new stark_proof());
+        const int32_t rc = assemble_from_values(ctx, plan.shape, r, H, k.table.data(), nreq, Pf.get());
+        if (rc) { for (auto* x : out) delete x; out.clear(); return rc; }
+        out.push_back(Pf.release());
     }
     return STARK_OK;
 }

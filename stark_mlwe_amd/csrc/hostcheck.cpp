@@ -537,13 +537,13 @@ int hc_hash_ds_batch_pairs_level(void* params, size_t arity, const uint64_t* lab
 // The commit phase of B traces side by side (FriBatchCommit): roots[(b (L + 1) + l) * 4 ..] = root of layer l of trace b.  0 on success.
 int hc_fri_commit_batch(void* tparams, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, uint64_t* roots) {
     FriHostExec X((HcParams*)tparams); FriBatchCommit<FriHostExec> C(X);
+    std::string err; if (int rc = C.shape(B, n0, schedule, L, err)) return rc;
     HcHasher H(tparams); std::vector<fr_t> z(L);
-    { size_t n = n0; for (size_t l = 0; l < L; ++l) {
-          if (schedule[l] < 2 || n % schedule[l]) return -1;
-          const fr_t in[3] = {host::h_u64(seed_z), host::h_u64(l), host::h_u64(n)}; fr_t fused; if (H.hash("FRI/z/l", in, 3, 1, &fused)) return -3;
-          z[l] = fri_z_from_fused(fused, seed_z, l, n); n /= schedule[l];
-      } }
-    std::string err; if (int rc = C.init(B, n0, schedule, L, z.data(), err)) return rc;
+    for (size_t l = 0; l < L; ++l) {
+        const fr_t in[3] = {host::h_u64(seed_z), host::h_u64(l), host::h_u64(C.n[l])}; fr_t fused; if (H.hash("FRI/z/l", in, 3, 1, &fused)) return -3;
+        z[l] = fri_z_from_fused(fused, seed_z, l, C.n[l]);
+    }
+    if (int rc = C.init(z.data())) return rc;
     for (size_t b = 0; b < B; ++b) for (size_t i = 0; i < n0; ++i) C.f[0][b * n0 + i] = ld4(f0[b] + 4 * i);
     if (int rc = C.run()) return rc;
     for (size_t b = 0; b < B; ++b) for (size_t l = 0; l <= L; ++l) st4(roots + 4 * (b * (L + 1) + l), C.roots[l * B + b]);

@@ -152,18 +152,12 @@ def prove_single(ctx, tr, n0, sched, r):
 
 
 @pytest.mark.parametrize("k,B", [(10, 5), (12, 4)])
-def test_prove_batch_tail_equals_workers_and_singles(gpu_ctx, k, B):
+def test_prove_batch_tail_equals_singles(gpu_ctx, k, B):
     from stark_mlwe_amd.api import DeepFriParams
     sched, r = SHAPES[k]; n0 = 1 << k
     keep, tr = synth_traces(gpu_ctx, k, B)
     prm = DeepFriParams(sched, r, SEED_Z)
     side = [g[0] for g in gpu_ctx.deep_fri_prove_batch_dev(tr, n0, prm)]
-    gpu_ctx.set_option("prove_batch_workers", 1)
-    try:
-        workers = [g[0] for g in gpu_ctx.deep_fri_prove_batch_dev(tr, n0, prm)]
-    finally:
-        gpu_ctx.set_option("prove_batch_workers", 0)
-    assert side == workers
     assert side == [prove_single(gpu_ctx, tr[p], n0, sched, r) for p in range(B)]
     if k == 10:                                                   # passes of 2, 2 and 1 traces: the last one takes the single tail
         gpu_ctx.set_option("prove_batch_max_rows", 2 * n0)
@@ -171,6 +165,18 @@ def test_prove_batch_tail_equals_workers_and_singles(gpu_ctx, k, B):
             assert [g[0] for g in gpu_ctx.deep_fri_prove_batch_dev(tr, n0, prm)] == side
         finally:
             gpu_ctx.set_option("prove_batch_max_rows", 1 << 22)
+
+
+def test_worker_tail_option_is_gone(gpu_ctx, traces):
+    """The worker-context tail was removed: its option is an unknown key like any other, and the context stays usable."""
+    from stark_mlwe_amd.api import DeepFriParams
+    k = 10; sched, r = SHAPES[k]; n0 = 1 << k
+    _, d = traces[k]
+    assert gpu_ctx.lib.stark_ctx_set_option(gpu_ctx.h, b"prove_batch_workers", 1) == INVALID_ARG
+    err = gpu_ctx.lib.stark_last_error(gpu_ctx.h).decode()
+    assert err.startswith("unknown option 'prove_batch_workers' (") and "prove_batch_max_rows" in err, err
+    got = gpu_ctx.deep_fri_prove_f0_batch_dev([f.data_ptr() for f in d[:3]], n0, DeepFriParams(sched, r, SEED_Z))
+    assert [g[0] for g in got] == [prove_f0_single(gpu_ctx, d[b], n0, sched, r) for b in range(3)]
 
 
 def test_passes_f0(gpu_ctx, traces):
@@ -227,6 +233,91 @@ def test_argument_errors(gpu_ctx, oracle, traces):
     # the context stays usable
     got = ctx.deep_fri_prove_f0_batch_dev([f.data_ptr() for f in d[:B]], n0, DeepFriParams(sched, r, SEED_Z))
     assert got[1][0] == prove_f0_single(ctx, d[1], n0, sched, r)
+
+
+UNSUPPORTED = -5
+SHAPE_INPUTS = [(0, []), (64, [16, 8]), (64, [1]), (3, []), (6, [2])]
+SHAPE_ENTRIES = ["fri_build_dev", "commit_batch_dev B=1", "commit_batch_dev B=2", "prove_dev f0", "prove_f0_batch_dev B=2", "build_sharded_emulated W=2", "plan_create"]
+UNSET = "unknown option 'no_such_option'"                    # what stark_last_error holds when the refused call did not set it
+# (n0, schedule) -> per entry of SHAPE_ENTRIES (return code, stable substring of stark_last_error or None where the entry point leaves it unset).
+# Every row is what the commit BEFORE the one layer-shape function (fri_plan.hpp: fri_layers) answers, entry point by entry point; the rows are
+# literals, not derived from the code under test.  The two plan_create entries marked LOOPED never returned there: FriShape::make built the level lengths of an
+# arity-1 tree (a loop that does not terminate) before it checked the arity.  They were not run on the device; with the shape checked first the
+# call is refused with make's own message, which is what these two entries now pin.
+LOOPED = (INVALID_ARG, "layer with arity 1")
+SHAPE_TABLE = {
+    (0, ()): [(INVALID_ARG, "empty layer")] * 3 + [(INVALID_ARG, "power of two")] * 2 + [(INVALID_ARG, "sharded FRI: empty layer"), (INVALID_ARG, "empty layer")],
+    (64, (16, 8)): [(INVALID_ARG, "schedule not dividing")] * 5 + [(INVALID_ARG, "sharded FRI: schedule not dividing"), (INVALID_ARG, "schedule not dividing")],
+    (64, (1,)): [(INVALID_ARG, "schedule not dividing")] * 5 + [(INVALID_ARG, "sharded FRI: schedule not dividing"), (INVALID_ARG, "schedule not dividing")],
+    (3, ()): [(UNSUPPORTED, "arity 1 with more than one leaf")] * 3 + [(INVALID_ARG, "power of two")] * 2 + [(INVALID_ARG, "n0 must divide over the ranks"), LOOPED],
+    (6, (2,)): [(UNSUPPORTED, "arity 1 with more than one leaf")] * 3 + [(INVALID_ARG, "power of two")] * 2 + [(UNSUPPORTED, "arity 1 with more than one leaf"), LOOPED],
+}
+
+
+def shape_error_results(ctx, f_ptrs, n0, sched, entries=SHAPE_ENTRIES):
+    """(return code, stark_last_error or None when the call left it unset) of every entry point of `entries` for one (n0, schedule);
+    f_ptrs: two device vectors of at least max(n0, 1) elements."""
+    lib = ctx.lib
+    sch = np.ascontiguousarray(sched if sched else [0], dtype=np.uint64); sp = sch.ctypes.data_as(vp); L = len(sched)
+    f = vp(f_ptrs[0]); tab = (vp * 2)(*f_ptrs[:2]); r = 4
+    roots = np.zeros((2, L + 1, 4), np.uint64); rp = roots.ctypes.data_as(vp)
+
+    def build():
+        st = vp(); rc = lib.stark_fri_build_dev(ctx.h, f, n0, sp, L, SEED_Z, C.byref(st))
+        if rc == 0: lib.stark_fri_state_free(st)
+        return rc
+
+    def prove():
+        h = vp(); rc = lib.stark_deep_fri_prove_dev(ctx.h, None, None, None, None, f, n0, sp, L, r, SEED_Z, C.byref(h))
+        if rc == 0: lib.stark_proof_free(h)
+        return rc
+
+    def prove_batch():
+        out = (vp * 2)(); rc = lib.stark_deep_fri_prove_f0_batch_dev(ctx.h, 2, tab, n0, sp, L, r, SEED_Z, out)
+        if rc == 0: [lib.stark_proof_free(out[i]) for i in range(2)]
+        return rc
+
+    def plan():
+        h = vp(); rc = lib.stark_fri_plan_create(ctx.h, rp, n0, sp, L, r, C.byref(h))
+        if rc == 0: lib.stark_fri_plan_free(h)
+        return rc
+    calls = {"fri_build_dev": build,
+             "commit_batch_dev B=1": lambda: lib.stark_fri_commit_batch_dev(ctx.h, 1, tab, n0, sp, L, SEED_Z, rp),
+             "commit_batch_dev B=2": lambda: lib.stark_fri_commit_batch_dev(ctx.h, 2, tab, n0, sp, L, SEED_Z, rp),
+             "prove_dev f0": prove, "prove_f0_batch_dev B=2": prove_batch,
+             "build_sharded_emulated W=2": lambda: lib.stark_diag_fri_build_sharded_emulated_dev(ctx.h, 2, f, n0, sp, L, SEED_Z, rp),
+             "plan_create": plan}
+    for name in entries:
+        assert lib.stark_ctx_set_option(ctx.h, b"no_such_option", 0) == INVALID_ARG       # a known last error: a call that sets none leaves it
+        rc = calls[name]()
+        err = lib.stark_last_error(ctx.h).decode()
+        yield name, rc, None if err.startswith(UNSET) else err
+
+
+def test_shape_errors_by_entry_point(gpu_ctx, traces, single_roots):
+    """Empty layers, non-dividing schedules and arity-1 layers through every entry point that derives the layer shape: each keeps its own return code
+    and message (SHAPE_TABLE), nothing is launched that could fault, and after every refusal a good stark_fri_build_dev returns the roots it did before."""
+    _, d = traces[6]
+    ptrs = [d[0].data_ptr(), d[1].data_ptr()]
+    sch = np.ascontiguousarray(SHAPES[6][0], dtype=np.uint64)
+
+    def good_roots():
+        st = vp(); rs = np.zeros((len(sch) + 1, 4), np.uint64)
+        gpu_ctx._chk(gpu_ctx.lib.stark_fri_build_dev(gpu_ctx.h, vp(ptrs[0]), 64, sch.ctypes.data_as(vp), len(sch), SEED_Z, C.byref(st)))
+        try:
+            for l in range(len(sch) + 1):
+                gpu_ctx._chk(gpu_ctx.lib.stark_fri_layer_root(st, l, rs[l].ctypes.data_as(vp)))
+        finally:
+            gpu_ctx.lib.stark_fri_state_free(st)
+        return rs
+    assert (good_roots() == single_roots[6][0]).all()
+    for n0, sched in SHAPE_INPUTS:
+        want = SHAPE_TABLE[(n0, tuple(sched))]
+        for (name, rc, err), (want_rc, want_err) in zip(shape_error_results(gpu_ctx, ptrs, n0, sched), want):
+            print(n0, sched, name, rc, repr(err))
+            assert rc == want_rc, (n0, sched, name, rc, err)
+            assert (err is None) if want_err is None else (err is not None and want_err in err), (n0, sched, name, rc, err)
+            assert (good_roots() == single_roots[6][0]).all(), (n0, sched, name)
 
 
 def test_f0_batch_is_not_slower_than_single_calls(gpu_ctx, oracle):

@@ -69,8 +69,8 @@ def test_batch_prove_equals_single_proves(gpu_ctx, oracle, k, B):
     """stark_deep_fri_prove_batch_dev: B independent traces in one call (the reference's bench proves one after another,
     channel/benches/end_to_end.rs:229-309).  Each proof is byte-equal to the single prove of its trace (and, at 2^10, to the
     oracle's).  The 4 * B serial column sponges of crates/deep_ali/src/fri.rs:548-557 run concurrently, so the sponge stage of the batch costs what it
-    costs for one trace; the B tails (merge, commit, queries: a few ms each, latency-bound) run up to four at a time on worker contexts.  16 proves of
-    2^16 rows: 0.39 s against 0.31 s for one."""
+    costs for one trace; the B tails (merge, commit, queries: a few ms each, latency-bound) run side by side, pass by pass.  16 proves of
+    2^16 rows: 0.39 s against 0.31 s for one (measured with the earlier tails, four at a time on worker contexts)."""
     import time
     import torch
     from stark_mlwe_amd.api import DeepFriParams

@@ -13,7 +13,7 @@ for p in range(128):
     for c in range(4): ctx._chk(lib.stark_synth_column_dev(ctx.h, 0xBA7C0000 + p, c, 0, n0, C.c_void_p(cols[c].data_ptr())))
     keep.append(cols); traces.append([c.data_ptr() for c in cols])
 torch.cuda.synchronize()
-ctx.deep_fri_prove_batch_dev(traces[:8], n0, prm)      # warm-up: creates all four worker contexts (a one-time cost of ~85 ms)
+ctx.deep_fri_prove_batch_dev(traces[:8], n0, prm)      # warm-up: pool and parameter caches
 for B in (1, 2, 4, 8, 16, 32, 64, 128):
     t0 = time.perf_counter(); got = ctx.deep_fri_prove_batch_dev(traces[:B], n0, prm); dt = time.perf_counter() - t0
     sponge_ms = got[0][2][0] - 0  # stage 0 of proof 0 = the shared sponge stage + its own merge

@@ -1,9 +1,9 @@
 """tools/prove_batch_timing.py — the side-by-side tail of the batched DEEP-FRI provers against what it replaces, wall time per call, medians over
-ten alternating pairs in one process (pool, parameter caches and the four worker contexts warmed first), every compared output checked byte-equal:
+ten alternating pairs in one process (pool and parameter caches warmed first), every compared output checked byte-equal:
   (a) stark_deep_fri_prove_f0_batch_dev against B single stark_deep_fri_prove_dev(f0) calls, k = 11, 12, 14, 16 and B = 1, 4, 16, 64, 256 within memory;
-  (b) stark_deep_fri_prove_batch_dev with option prove_batch_workers 0 against 1 (the earlier worker-context tails) on the same grid;
   (c) option prove_batch_max_rows from 2^18 to 2^24 at k = 12 and k = 16, f0 batch at the largest B of the grid (so that the small settings cut it into several passes).
-Writes profiles/prove_batch_timing.jsonl (or the path given as the first argument).  `--quick` as a further argument keeps the grid to what fits in a
+(Part (b) compared the side-by-side tail of stark_deep_fri_prove_batch_dev with the worker-context tail it replaced; that tail is gone, and its rows
+stay in profiles/prove_batch_timing.jsonl as the record.)  Writes profiles/prove_batch_timing_ac.jsonl (or the path given as the first argument).  `--quick` as a further argument keeps the grid to what fits in a
 couple of minutes (fewer pairs, B <= 64).  Not product code."""
 import ctypes as C
 import json
@@ -20,7 +20,7 @@ from stark_mlwe_amd.api import Context, DeepFriParams
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 QUICK = "--quick" in sys.argv
-OUT = args[0] if args else os.path.join(ROOT, "profiles", "prove_batch_timing.jsonl")
+OUT = args[0] if args else os.path.join(ROOT, "profiles", "prove_batch_timing_ac.jsonl")
 PAIRS = 3 if QUICK else 10
 MAX_ROWS_TOTAL = 1 << 22 if QUICK else 1 << 24          # B * n0 kept within this (memory and time)
 SEED_Z = 0xDEEFBAAD
@@ -33,14 +33,14 @@ def shape(k):
 
 
 def synth(k, B, seed):
-    n0 = 1 << k; keep, tr = [], []
+    n0 = 1 << k; keep = []
     for p in range(B):
         cols = [torch.empty((n0, 4), dtype=torch.int64, device="cuda") for _ in range(4)]
         for c in range(4):
             ctx._chk(ctx.lib.stark_synth_column_dev(ctx.h, seed + p, c, 0, n0, vp(cols[c].data_ptr())))
-        keep.append(cols); tr.append([c.data_ptr() for c in cols])
+        keep.append(cols)
     torch.cuda.synchronize()
-    return keep, tr
+    return keep
 
 
 def single_f0(ptr, n0, sched, r):
@@ -63,22 +63,13 @@ rows = []
 for k in (11, 12, 14, 16):
     sched, r = shape(k); n0 = 1 << k; prm = DeepFriParams(sched, r, SEED_Z)
     Bs = [B for B in (1, 4, 16, 64, 256) if B * n0 <= MAX_ROWS_TOTAL and (not QUICK or B <= 64)]
-    keep, tr = synth(k, max(Bs), 0x7B000000 + (k << 12))
+    keep = synth(k, max(Bs), 0x7B000000 + (k << 12))
     f0s = [cols[0].data_ptr() for cols in keep]          # any resident vector serves as an f0
     for B in Bs:
         b_ms, s_ms = alternate(lambda: [g[0] for g in ctx.deep_fri_prove_f0_batch_dev(f0s[:B], n0, prm)], lambda: [single_f0(p, n0, sched, r) for p in f0s[:B]])
         rows.append({"what": "f0_batch_vs_singles", "log_n0": k, "batch": B, "batch_ms": b_ms, "singles_ms": s_ms, "speedup": s_ms / b_ms})
         print(rows[-1], flush=True)
 
-        def with_workers(v):
-            ctx.set_option("prove_batch_workers", v)
-            try:
-                return [g[0] for g in ctx.deep_fri_prove_batch_dev(tr[:B], n0, prm)]
-            finally:
-                ctx.set_option("prove_batch_workers", 0)
-        side_ms, work_ms = alternate(lambda: with_workers(0), lambda: with_workers(1))
-        rows.append({"what": "prove_batch_side_by_side_vs_workers", "log_n0": k, "batch": B, "side_by_side_ms": side_ms, "workers_ms": work_ms, "speedup": work_ms / side_ms})
-        print(rows[-1], flush=True)
     if k in (12, 16):
         B = max(Bs)
         want = [g[0] for g in ctx.deep_fri_prove_f0_batch_dev(f0s[:B], n0, prm)]
