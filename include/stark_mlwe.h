@@ -82,6 +82,7 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  *   "sponge_one_wave" (0 | 1: long serial sponges, small Merkle levels / leaf layers and short transcript hashes on the one-wave / wave-pair kernels
  *   instead of the five-wave latency kernel; comparison), "sponge_debug" (timing experiments on the five-wave kernel; digests are WRONG when set).
  *   "prove_batch_max_rows" (1..2^28, default 2^22: the rows of one pass of the batched DEEP-FRI provers).
+ *   "ntt_batch_max_elems" (1..2^28, default 2^24: the output elements of one pass of stark_ntt_batch_dev / stark_lde_batch_dev).
  * An unknown key is STARK_ERR_INVALID_ARG; stark_last_error then lists the known keys.
  * Changing an option synchronises the stream and drops the cached NTT plans. */
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value);
@@ -390,6 +391,19 @@ int32_t stark_ntt_dev(stark_ctx_t* ctx, int32_t field_id, uint64_t* data, size_t
 /* LDE: 2^log_n evaluations on <w_n> -> 2^(log_n+log_blowup) evaluations on coset4 * <w_N> (coset4 NULL => 1). */
 int32_t stark_lde(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* out);
 int32_t stark_lde_dev(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* out);
+/* `batch` transforms / extensions of one shape and one coset; tables are HOST arrays of `batch` DEVICE pointers.
+ * Element i equals what stark_ntt_dev / stark_lde_dev returns for column i alone, byte for byte.
+ * Stream-ordered with no host synchronisation, like the single calls (the tables are copied before the call returns).  batch == 0 is STARK_OK.
+ * STARK_ERR_INVALID_ARG, checked on the host before anything is launched: a null ctx, table or entry; log_n (or log_n + log_blowup) outside
+ * the single call's range (0..30); an unknown field; two `out` ranges (two `data` ranges) that overlap.
+ * Inputs may repeat, and evals[i] may be out[i]: a column is read completely before its output is written.  Inputs are otherwise left intact; an
+ * input that overlaps ANOTHER column's output is not supported (columns of different passes are not ordered against each other).
+ * The batch is cut into passes of at most "ntt_batch_max_elems" output elements (option, default 2^24: 512 MiB of outputs and as much scratch);
+ * inside a pass every step of the single call is ONE launch for all columns and the columns are read and written in place through pointer
+ * tables (no gather copy).  A pass of one column — every column larger than the limit — is the single call itself. */
+int32_t stark_ntt_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, uint64_t* const* data, size_t log_n, int32_t inverse, const uint64_t* coset4);
+int32_t stark_lde_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, const uint64_t* const* evals, size_t log_n, size_t log_blowup,
+                            const uint64_t* coset4, uint64_t* const* out);
 /* Building blocks of the multi-GPU six-step NTT (one process per GPU; the exchange between the two
  * is an all-to-all done by the caller, see stark_mlwe_amd/dist.py):
  *   phase A: `ncols` column NTTs of size 2^log_rows on a row-major [2^log_rows][ncols] slab, then the

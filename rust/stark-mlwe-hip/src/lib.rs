@@ -372,6 +372,19 @@ pub mod fft {
         ctx.chk(unsafe { stark_lde(ctx.raw, STARK_FIELD_PALLAS_FR, limbs(evals), evals.len().trailing_zeros() as usize, log_blowup, c, limbs_mut(&mut out)) });
         out
     }
+    /// `lde` of many DEVICE columns (Pallas Fr, 2^log_n elements each) with one coset into the DEVICE vectors `outs`, every step one launch for all
+    /// columns; element i is what `stark_lde_dev` gives for column i alone.  Stream-ordered: the caller synchronises before reading `outs`.
+    /// Safety: every pointer is device memory of the stated length, and the `outs` ranges do not overlap.
+    pub unsafe fn lde_batch_dev(ctx: &Ctx, evals: &[*const u64], log_n: usize, log_blowup: usize, coset: Option<F>, outs: &[*mut u64]) {
+        assert_eq!(evals.len(), outs.len());
+        let c = coset.as_ref().map(limb1).unwrap_or(ptr::null());
+        ctx.chk(stark_lde_batch_dev(ctx.raw, STARK_FIELD_PALLAS_FR, evals.len(), evals.as_ptr(), log_n, log_blowup, c, outs.as_ptr()));
+    }
+    /// `fft_in_place` / `ifft_in_place` of many DEVICE vectors (BLS12-381 Fr, 2^log_n elements each) in place, every pass one launch for all of them.
+    /// Safety: as `lde_batch_dev`; the `datas` ranges do not overlap.
+    pub unsafe fn ntt_batch_dev(ctx: &Ctx, datas: &[*mut u64], log_n: usize, inverse: bool) {
+        ctx.chk(stark_ntt_batch_dev(ctx.raw, STARK_FIELD_BLS12_381_FR, datas.len(), datas.as_ptr(), log_n, inverse as i32, ptr::null()));
+    }
 }
 
 pub mod transcript {

@@ -323,7 +323,7 @@ class Context:
         self._chk(self.lib.stark_ctx_sync(self.h))
 
     def set_option(self, key: str, value: int):
-        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "fri_side_pair", "prove_batch_max_rows".  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
+        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems".  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
         self._chk(self.lib.stark_ctx_set_option(self.h, key.encode(), value))
 
     def trim(self):
@@ -543,6 +543,21 @@ class Context:
         cs = np.zeros((B, 4), np.uint64) if want_c_star else None
         self._chk(self.lib.stark_ali_merge_batch_dev(self.h, B, cols[0], cols[1], cols[2], cols[3], rt, _ptr(bt), _ptr(_arr(omega)), _ptr(z), n, outs, _ptr(cs)))
         return cs
+
+    def ntt_batch_dev(self, field, datas, log_n, inverse=False, coset=None):
+        """stark_ntt_dev of each of the DEVICE vectors `datas` (ints, 2^log_n elements each, transformed in place) with one coset, every pass of the
+        transform one launch for all of them; stream-ordered, no synchronisation (stark_ntt_batch_dev)."""
+        B = len(datas)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in datas])
+        self._chk(self.lib.stark_ntt_batch_dev(self.h, field, B, tab, log_n, 1 if inverse else 0, _ptr(None if coset is None else _arr(coset))))
+
+    def lde_batch_dev(self, field, evals, log_n, log_blowup, outs, coset=None):
+        """stark_lde_dev of each of the DEVICE columns `evals` (ints, 2^log_n elements) into the DEVICE vectors `outs` (2^(log_n + log_blowup) elements)
+        with one coset, every step one launch for all columns; stream-ordered, no synchronisation (stark_lde_batch_dev)."""
+        B = len(evals)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in evals])
+        otab = (C.c_void_p * max(B, 1))(*[int(x) for x in outs])
+        self._chk(self.lib.stark_lde_batch_dev(self.h, field, B, tab, log_n, log_blowup, _ptr(None if coset is None else _arr(coset)), otab))
 
     def deep_fri_verify(self, params: DeepFriParams, proof: bytes) -> bool:
         """deep_fri_verify (fri.rs:643-762) on canonical proof bytes."""

@@ -17,6 +17,22 @@ int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out) {
     *out = ctx->scratch.p; return STARK_OK;
 }
 
+int32_t ctx_upload_staged(stark_ctx* ctx, void* dst, const void* src, size_t bytes) {
+    if (!bytes) return STARK_OK;
+    auto& q = ctx->staged;
+    for (size_t i = 0; i < q.size();) {                                     // uploads the stream has passed: their host copies go
+        if (hipEventQuery(q[i].done) == hipSuccess) { (void)hipEventDestroy(q[i].done); q[i] = std::move(q.back()); q.pop_back(); } else ++i;
+    }
+    (void)hipGetLastError();                                                // hipErrorNotReady of the queries is not an error
+    stark_ctx::StagedUpload u; u.host.reset(new uint8_t[bytes]); memcpy(u.host.get(), src, bytes);
+    STARK_HIP(ctx, hipEventCreateWithFlags(&u.done, hipEventDisableTiming));
+    const uint8_t* from = u.host.get();
+    q.push_back(std::move(u));                                              // owned from here on, whatever fails below (teardown synchronises first)
+    STARK_HIP(ctx, hipMemcpyAsync(dst, from, bytes, hipMemcpyHostToDevice, ctx->stream));
+    STARK_HIP(ctx, hipEventRecord(q.back().done, ctx->stream));
+    return STARK_OK;
+}
+
 // ---- caching device allocator (stark_ctx::pool_free) ----------------------------------------------------------
 static inline size_t pool_round(size_t bytes) {
     if (bytes < 256) return 256;
@@ -152,6 +168,7 @@ static void ctx_teardown(stark_ctx* ctx) {
     for (auto& kv : ctx->pool_free) for (void* q : kv.second) (void)hipFree(q);
     for (auto& kv : ctx->pool_live) (void)hipFree(kv.first);                 // stark_alloc blocks the caller never freed (handles are gone by now)
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    for (auto& u : ctx->staged) (void)hipEventDestroy(u.done);               // the stream was synchronised above: every staged upload is done
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0); if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
@@ -198,6 +215,7 @@ static const OptionDef kOptions[] = {
     {"merkle_node16_pair", [](stark_ctx::Options& o, int64_t v) -> const char* { o.merkle_node16_pair = v != 0; return nullptr; }},
     {"fri_side_pair", [](stark_ctx::Options& o, int64_t v) -> const char* { o.fri_side_pair = v != 0; return nullptr; }},
     {"sumcheck_verify_batch_max_slots", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1) return "at least 1"; o.sumcheck_verify_batch_max_slots = (size_t)v; return nullptr; }},
+    {"ntt_batch_max_elems", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.ntt_batch_max_elems = (size_t)v; return nullptr; }},
     {"prove_batch_max_rows", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.prove_batch_max_rows = (size_t)v; return nullptr; }},
 };
 extern "C" {

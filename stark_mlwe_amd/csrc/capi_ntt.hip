@@ -5,6 +5,7 @@
 #include <cstring>
 #include <memory>
 #include "pow_table.hpp"
+#include "ntt_batch_plan.hpp"
 #include "fri_dev.hpp"
 #include "shard_coll.hpp"
 
@@ -106,23 +107,29 @@ static inline int pick_log_c(const stark_ctx* ctx, int log_b, int cap, int total
     return lc;
 }
 
+// Bt: the vectors' addresses of a batched pass (the NttBatchAddr instantiations of the pass kernels); nullptr: the plain kernels
 template <class F, int MINW, bool STRIDED>
-static void launch_pass(bool pre, unsigned th, size_t lds, hipStream_t st, const NttPassArgs& A, const fr_t* src, fr_t* dst) {
+static void launch_pass(bool pre, unsigned th, size_t lds, hipStream_t st, const NttPassArgs& A, const fr_t* src, fr_t* dst, const NttBatchAddr* Bt) {
     const dim3 grid(A.ntiles), block(th);
+    if (Bt) {
+        if (STRIDED) { if (pre) hipLaunchKernelGGL((k_ntt_strided<F, MINW, true, NttBatchAddr>), grid, block, lds, st, A, src, dst, *Bt); else hipLaunchKernelGGL((k_ntt_strided<F, MINW, false, NttBatchAddr>), grid, block, lds, st, A, src, dst, *Bt); }
+        else { if (pre) hipLaunchKernelGGL((k_ntt_last<F, MINW, true, NttBatchAddr>), grid, block, lds, st, A, src, dst, *Bt); else hipLaunchKernelGGL((k_ntt_last<F, MINW, false, NttBatchAddr>), grid, block, lds, st, A, src, dst, *Bt); }
+        return;
+    }
     if (STRIDED) { if (pre) hipLaunchKernelGGL((k_ntt_strided<F, MINW, true>), grid, block, lds, st, A, src, dst); else hipLaunchKernelGGL((k_ntt_strided<F, MINW, false>), grid, block, lds, st, A, src, dst); }
     else { if (pre) hipLaunchKernelGGL((k_ntt_last<F, MINW, true>), grid, block, lds, st, A, src, dst); else hipLaunchKernelGGL((k_ntt_last<F, MINW, false>), grid, block, lds, st, A, src, dst); }
 }
 template <class F, bool STRIDED>
-static int32_t launch_any(stark_ctx* ctx, NttPassArgs A, uint64_t total_elems, bool pre, const fr_t* src, fr_t* dst) {
+static int32_t launch_any(stark_ctx* ctx, NttPassArgs A, uint64_t total_elems, bool pre, const fr_t* src, fr_t* dst, const NttBatchAddr* Bt) {
     size_t lds = ntt_lds_bytes(A.log_b, A.log_c);
     if (lds > kMaxLds) return ctx->fail(STARK_ERR_UNSUPPORTED, "NTT tile exceeds LDS");
     A.ntiles = (uint32_t)(total_elems >> (A.log_b + A.log_c));
-    if (ntt_minw(ctx) > 2 && lds <= 40 * 1024) launch_pass<F, 4, STRIDED>(pre, 256u, lds, ctx->stream, A, src, dst);
-    else launch_pass<F, 2, STRIDED>(pre, ntt_threads(lds), lds, ctx->stream, A, src, dst);
+    if (ntt_minw(ctx) > 2 && lds <= 40 * 1024) launch_pass<F, 4, STRIDED>(pre, 256u, lds, ctx->stream, A, src, dst, Bt);
+    else launch_pass<F, 2, STRIDED>(pre, ntt_threads(lds), lds, ctx->stream, A, src, dst, Bt);
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
 }
-template <class F> static int32_t launch_strided(stark_ctx* ctx, const NttPassArgs& A, uint64_t total_elems, const fr_t* src, fr_t* dst) { return launch_any<F, true>(ctx, A, total_elems, A.pre_direct || A.pre.lo, src, dst); }
-template <class F> static int32_t launch_last(stark_ctx* ctx, const NttPassArgs& A, uint64_t total_elems, const fr_t* src, fr_t* dst) { return launch_any<F, false>(ctx, A, total_elems, A.pre.lo != nullptr, src, dst); }
+template <class F> static int32_t launch_strided(stark_ctx* ctx, const NttPassArgs& A, uint64_t total_elems, const fr_t* src, fr_t* dst, const NttBatchAddr* Bt = nullptr) { return launch_any<F, true>(ctx, A, total_elems, A.pre_direct || A.pre.lo, src, dst, Bt); }
+template <class F> static int32_t launch_last(stark_ctx* ctx, const NttPassArgs& A, uint64_t total_elems, const fr_t* src, fr_t* dst, const NttBatchAddr* Bt = nullptr) { return launch_any<F, false>(ctx, A, total_elems, A.pre.lo != nullptr, src, dst, Bt); }
 
 // plain (c0 = 1) power table of `base` over the plan's 2^log_n points, from the plan's cache (`pin`: PowCache::get)
 template <class F> static int32_t plain_table(stark_ctx* ctx, NttPlan* big, const fr_t& base, PowTable* out, const PowTable* pin = nullptr) {
@@ -159,14 +166,20 @@ static int32_t build_coset(stark_ctx* ctx, NttPlan* p, const fr_t& g, NttCoset& 
     }
     return STARK_OK;
 }
-// `batch` vectors of 2^log_n elements each, contiguous.  data is transformed in place (scratch from the context).
+// Where the vectors of a transform start and end.  Plain (ntt_run): contiguous at `src` == `dst`, 2^log_n apart, transformed in place through the
+// context's scratch by the plain kernels.  Batched (`batch` set; the NttBatchAddr instantiations): vector v is read at src_tab[v] or src + v * src_pitch
+// and leaves at dst_tab[v] or dst + v * dst_pitch (tables of DEVICE pointers in device memory, pitches in elements); `work` holds the [B][2^log_n]
+// intermediate of a transform of more than one pass and may be the source (a strided pass works in place), never the destination.
+struct NttEnds {
+    bool batch = false;
+    const fr_t* const* src_tab = nullptr; const fr_t* src = nullptr; uint64_t src_pitch = 0;
+    fr_t* const* dst_tab = nullptr; fr_t* dst = nullptr; uint64_t dst_pitch = 0;
+    fr_t* work = nullptr;
+};
+static inline int floor_log2(uint64_t x) { int k = 0; while (x >> (k + 1)) ++k; return k; }
+// The passes of `batch` transforms of 2^log_n points (1 <= log_n <= 30, batch >= 1) between the ends E.
 template <class F>
-static int32_t ntt_run(stark_ctx* ctx, fr_t* data, int log_n, uint64_t batch, bool inverse, const fr_t* coset, const fr_t* scale_override_dev, int log_nonzero = -1) {
-    if (log_n < 0 || log_n > 30) return ctx->fail(STARK_ERR_INVALID_ARG, "log_n out of range");
-    if (batch == 0) return STARK_OK;
-    if (log_n == 0) {   // size-1 transform: identity (n^-1 = 1, g^0 = 1)
-        return STARK_OK;
-    }
+static int32_t ntt_passes(stark_ctx* ctx, const NttEnds& E, int log_n, uint64_t batch, bool inverse, const fr_t* coset, const fr_t* scale_override_dev, int log_nonzero) {
     NttPlan* p = nullptr; STARK_TRY(get_plan<F>(ctx, log_n, inverse, &p));
     PowTable none{nullptr, nullptr, 0};
     PowTable pre = none, post = none;
@@ -177,31 +190,45 @@ static int32_t ntt_run(stark_ctx* ctx, fr_t* data, int log_n, uint64_t batch, bo
     const NttCoset& C = p->coset;
     const fr_t* pre_direct = (coset && !inverse) ? C.direct.fr() : nullptr;
     const bool merged = coset && !inverse && C.small && C.tw_direct;
-    const uint64_t total = batch << log_n;
-    fr_t* scratch = nullptr;
-    if (p->P > 1) { void* s = nullptr; STARK_TRY(ctx_scratch(ctx, total * sizeof(fr_t), &s)); scratch = (fr_t*)s; }
+    const uint64_t total = batch << log_n, n = 1ull << log_n;
+    // tile width: a plain call sizes its tiles by one vector (what it has always done), a batched pass by all the elements its launches cover
+    const int total_log = E.batch ? floor_log2(total) : log_n;
+    fr_t* scratch = E.work;
+    if (p->P > 1 && !E.batch) { void* s = nullptr; STARK_TRY(ctx_scratch(ctx, total * sizeof(fr_t), &s)); scratch = (fr_t*)s; }
+    const NttBatchAddr first{E.src_tab, nullptr, E.src_pitch, n}, middle{nullptr, nullptr, n, n}, last{p->P == 1 ? E.src_tab : nullptr, E.dst_tab, p->P == 1 ? E.src_pitch : n, E.dst_pitch};
     NttPassArgs A; memset(&A, 0, sizeof(A)); ntt29_offset<F>(A.dlimb);
     A.log_n = log_n; A.root = p->root.view(); A.pre = none; A.post = none; A.scale = nullptr; A.rest0 = 0; A.log_vec = log_n;
-    const fr_t* src = data;
+    const fr_t* src = E.src;
     int rem = log_n;                       // log2 of the current sub-problem size
     for (int i = 0; i + 1 < p->P; ++i) {   // strided passes
         A.log_b = p->log_b[i]; A.log_m = rem; A.stride = 1ull << (rem - A.log_b);
-        A.log_c = pick_log_c(ctx, A.log_b, rem - A.log_b, log_n);
+        A.log_c = pick_log_c(ctx, A.log_b, rem - A.log_b, total_log);
         A.stage_tw = p->stage_tw[i].fr(); A.pre = (i == 0) ? pre : none; A.pre_direct = (i == 0) ? pre_direct : nullptr; A.tw_direct = p->tw_direct[i].fr();
         A.pre_small = nullptr;
         if (i == 0 && merged) { A.pre_small = C.small.fr(); A.tw_direct = C.tw_direct.fr(); }
         // zero-padded input (LDE): element j is non-zero only for j < 2^log_nonzero; in the first strided pass that is the points p < 2^log_nonzero / stride
         A.nz_points = (i == 0 && log_nonzero >= 0 && log_nonzero < log_n && (1ull << log_nonzero) >= A.stride) ? (uint32_t)((1ull << log_nonzero) / A.stride) : 0u;
-        STARK_TRY(launch_strided<F>(ctx, A, total, src, scratch));
+        STARK_TRY(launch_strided<F>(ctx, A, total, src, scratch, E.batch ? (i == 0 ? &first : &middle) : nullptr));
         src = scratch; rem -= A.log_b;
     }
     A.pre = (p->P == 1) ? pre : none; A.pre_direct = nullptr; A.pre_small = nullptr; A.tw_direct = nullptr; A.nz_points = 0;
     A.log_b = p->log_b[p->P - 1]; A.stage_tw = p->stage_tw[p->P - 1].fr();
     A.log_b1 = p->P >= 2 ? p->log_b[0] : 0; A.log_b2 = p->P == 3 ? p->log_b[1] : 0;
-    A.log_c = p->P == 1 ? 0 : pick_log_c(ctx, A.log_b, A.log_b1, log_n);
+    A.log_c = p->P == 1 ? 0 : pick_log_c(ctx, A.log_b, A.log_b1, total_log);
     A.post = post; A.scale = post.lo ? nullptr : (scale_override_dev ? scale_override_dev : (inverse ? p->scale.fr() : nullptr));
-    STARK_TRY(launch_last<F>(ctx, A, total, src, data));
+    STARK_TRY(launch_last<F>(ctx, A, total, src, E.dst, E.batch ? &last : nullptr));
     return STARK_OK;
+}
+// `batch` vectors of 2^log_n elements each, contiguous.  data is transformed in place (scratch from the context).
+template <class F>
+static int32_t ntt_run(stark_ctx* ctx, fr_t* data, int log_n, uint64_t batch, bool inverse, const fr_t* coset, const fr_t* scale_override_dev, int log_nonzero = -1) {
+    if (log_n < 0 || log_n > 30) return ctx->fail(STARK_ERR_INVALID_ARG, "log_n out of range");
+    if (batch == 0) return STARK_OK;
+    if (log_n == 0) {   // size-1 transform: identity (n^-1 = 1, g^0 = 1)
+        return STARK_OK;
+    }
+    NttEnds E; E.src = data; E.dst = data;
+    return ntt_passes<F>(ctx, E, log_n, batch, inverse, coset, scale_override_dev, log_nonzero);
 }
 
 template <class F>
@@ -220,6 +247,80 @@ static int32_t lde_run(stark_ctx* ctx, const fr_t* evals, int log_n, int log_blo
     return ntt_run<F>(ctx, out, big, 1, false, unit ? nullptr : coset, nullptr, skip ? log_n : -1);   // coefficients -> coset evaluations on the larger domain
 }
 
+// ---- stark_ntt_batch_dev / stark_lde_batch_dev: many columns of one shape and one coset per device pass ---------------------------------------
+// A pass's pointer tables ([sources | destinations], one upload) in pooled device memory; the host copy of the upload belongs to the context.
+static int32_t upload_tables(stark_ctx* ctx, DevBuf& d, const std::vector<const void*>& tab) {
+    STARK_HIP(ctx, d.alloc(ctx, tab.size() * sizeof(void*)));
+    return ctx_upload_staged(ctx, d.p, tab.data(), tab.size() * sizeof(void*));
+}
+template <class F>
+static int32_t pad_fill(stark_ctx* ctx, const fr_t* const* src_tab, const fr_t* src, uint64_t src_pitch, fr_t* const* dst_tab, fr_t* dst, uint64_t dst_pitch, uint64_t first, uint64_t head, uint64_t len, uint64_t B) {
+    const uint64_t tot = (len - first) * B; if (!tot) return STARK_OK;
+    hipLaunchKernelGGL(k_pad_fill_batch<F>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, src_tab, src, src_pitch, dst_tab, dst, dst_pitch, first, head, len, B);
+    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+}
+// One pass of B >= 2 in-place transforms: the first launch reads the caller's vectors through the table, the last one writes them through it.
+template <class F>
+static int32_t ntt_batch_pass(stark_ctx* ctx, uint64_t* const* data, size_t B, int log_n, bool inverse, const fr_t* coset) {
+    if (log_n == 0) return STARK_OK;                                         // size-1 transforms: identity
+    NttPlan* p = nullptr; STARK_TRY(get_plan<F>(ctx, log_n, inverse, &p));
+    NttEnds E; E.batch = true;
+    if (p->P > 1) { void* w = nullptr; STARK_TRY(ctx_scratch(ctx, (B << log_n) * sizeof(fr_t), &w)); E.work = (fr_t*)w; }
+    DevBuf dtab; STARK_TRY(upload_tables(ctx, dtab, std::vector<const void*>(data, data + B)));
+    E.src_tab = (const fr_t* const*)dtab.p; E.dst_tab = (fr_t* const*)dtab.p;
+    return ntt_passes<F>(ctx, E, log_n, B, inverse, coset, nullptr, -1);
+}
+template <class F>
+static int32_t ntt_batch_run(stark_ctx* ctx, size_t batch, uint64_t* const* data, int log_n, bool inverse, const fr_t* coset) {
+    size_t b0 = 0;
+    for (size_t Bp : ntt_batch_passes(batch, log_n, ctx->opt.ntt_batch_max_elems)) {
+        if (Bp == 1) STARK_TRY(ntt_run<F>(ctx, as_fr(data[b0]), log_n, 1, inverse, coset, nullptr));
+        else STARK_TRY(ntt_batch_pass<F>(ctx, data + b0, Bp, log_n, inverse, coset));
+        b0 += Bp;
+    }
+    return STARK_OK;
+}
+// One pass of B >= 2 extensions, lde_run's steps once each for all columns.  Scratch: X = [B][N] and Cs = [B][n].  The inverse transform reads
+// the caller's columns through the table (no copy) and leaves the coefficients where the forward transform's first pass wants them: in Cs at
+// pitch n when that pass takes the padding as zero without reading it (lde_run's `skip`), else in X at pitch N with the tails zeroed by one
+// launch.  Its own intermediate is the other region.  The forward transform works in X and its last pass stores into the caller's outputs.
+// Every input is read by the first launch and every output written by the last, so inside a pass an input may alias any output.
+template <class F>
+static int32_t lde_batch_pass(stark_ctx* ctx, const uint64_t* const* evals, uint64_t* const* out, size_t B, int log_n, int log_blowup, const fr_t* coset) {
+    const int big = log_n + log_blowup;
+    const uint64_t n = 1ull << log_n, N = 1ull << big;
+    const fr_t one = fr_one<F>(); const bool unit = !coset || fr_eq(*coset, one);
+    bool skip = false;
+    if (big > 0) { NttPlan* bp = nullptr; STARK_TRY(get_plan<F>(ctx, big, false, &bp)); skip = N > n && bp->P > 1 && (big - bp->log_b[0]) <= log_n; }
+    void* w = nullptr; STARK_TRY(ctx_scratch(ctx, B * (N + n) * sizeof(fr_t), &w));
+    fr_t* const X = (fr_t*)w; fr_t* const Cs = X + B * N;
+    std::vector<const void*> tab(2 * B);
+    for (size_t b = 0; b < B; ++b) { tab[b] = evals[b]; tab[B + b] = out[b]; }
+    DevBuf dtab; STARK_TRY(upload_tables(ctx, dtab, tab));
+    const fr_t* const* src_tab = (const fr_t* const*)dtab.p; fr_t* const* dst_tab = (fr_t* const*)dtab.p + B;
+    fr_t* const coef = skip ? Cs : X; const uint64_t pitch = skip ? n : N;
+    if (log_n == 0) {          // one point: the interpolation is the point itself, written with its padding in one launch
+        STARK_TRY(pad_fill<F>(ctx, src_tab, nullptr, 0, nullptr, X, N, 0, 1, N, B));
+        if (big == 0) return pad_fill<F>(ctx, nullptr, X, 1, dst_tab, nullptr, 0, 0, 1, 1, B);
+    } else {
+        NttEnds I; I.batch = true; I.src_tab = src_tab; I.dst = coef; I.dst_pitch = pitch; I.work = skip ? X : Cs;
+        STARK_TRY(ntt_passes<F>(ctx, I, log_n, B, true, nullptr, nullptr, -1));                // evaluations on H -> coefficients
+        if (N > n && !skip) STARK_TRY(pad_fill<F>(ctx, nullptr, nullptr, 0, nullptr, X, N, n, 0, N, B));
+    }
+    NttEnds O; O.batch = true; O.src = coef; O.src_pitch = pitch; O.dst_tab = dst_tab; O.work = X;
+    return ntt_passes<F>(ctx, O, big, B, false, unit ? nullptr : coset, nullptr, skip ? log_n : -1);   // coefficients -> coset evaluations on the larger domain
+}
+template <class F>
+static int32_t lde_batch_run(stark_ctx* ctx, size_t batch, const uint64_t* const* evals, uint64_t* const* out, int log_n, int log_blowup, const fr_t* coset) {
+    size_t b0 = 0;
+    for (size_t Bp : ntt_batch_passes(batch, log_n + log_blowup, ctx->opt.ntt_batch_max_elems)) {
+        if (Bp == 1) STARK_TRY(lde_run<F>(ctx, as_fr(evals[b0]), log_n, log_blowup, coset, as_fr(out[b0])));
+        else STARK_TRY(lde_batch_pass<F>(ctx, evals + b0, out + b0, Bp, log_n, log_blowup, coset));
+        b0 += Bp;
+    }
+    return STARK_OK;
+}
+
 void stark::ntt_plans_free(stark_ctx* ctx) { for (auto& kv : ctx->plans) delete kv.second; ctx->plans.clear(); }
 
 // Per-DEVICE kernel attributes (the default tile is 64 KiB + twiddles, above the 64 KiB a kernel may use without opting in):
@@ -229,6 +330,10 @@ template <class F> static void set_attrs_for() {
     (void)hipFuncSetAttribute((const void*)k_ntt_strided<F, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_ntt_last<F, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_ntt_last<F, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_ntt_strided<F, 2, false, NttBatchAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_ntt_strided<F, 2, true, NttBatchAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_ntt_last<F, 2, false, NttBatchAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_ntt_last<F, 2, true, NttBatchAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
 }
 void stark::ntt_set_attrs() { set_attrs_for<PallasFr>(); set_attrs_for<Bls12381Fr>(); }
 
@@ -391,6 +496,22 @@ int32_t stark_lde_dev(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals,
     STARK_TRY(ctx_enter(ctx));
     fr_t cs; if (coset4) cs = load_fr(coset4);
     return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return lde_run<F>(ctx, as_fr(evals), (int)log_n, (int)log_blowup, coset4 ? &cs : nullptr, as_fr(out)); });
+}
+int32_t stark_ntt_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, uint64_t* const* data, size_t log_n, int32_t inverse, const uint64_t* coset4) {
+    if (!ctx || (batch && !data) || log_n > 30) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    for (size_t b = 0; b < batch; ++b) if (!data[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_batch: null column");
+    if (ntt_batch_ranges_overlap((const void* const*)data, batch, sizeof(fr_t) << log_n)) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_batch: columns overlap");
+    fr_t cs; if (coset4) cs = load_fr(coset4);
+    return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return ntt_batch_run<F>(ctx, batch, data, (int)log_n, inverse != 0, coset4 ? &cs : nullptr); });
+}
+int32_t stark_lde_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, const uint64_t* const* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* const* out) {
+    if (!ctx || (batch && (!evals || !out)) || log_n > 30 || log_blowup > 30 || log_n + log_blowup > 30) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    for (size_t b = 0; b < batch; ++b) if (!evals[b] || !out[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_batch: null column");
+    if (ntt_batch_ranges_overlap((const void* const*)out, batch, sizeof(fr_t) << (log_n + log_blowup))) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_batch: outputs overlap");
+    fr_t cs; if (coset4) cs = load_fr(coset4);
+    return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return lde_batch_run<F>(ctx, batch, evals, out, (int)log_n, (int)log_blowup, coset4 ? &cs : nullptr); });
 }
 int32_t stark_lde(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* out) {
     if (!ctx || !evals || !out || log_n + log_blowup > 30) return STARK_ERR_INVALID_ARG;

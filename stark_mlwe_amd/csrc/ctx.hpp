@@ -88,6 +88,10 @@ struct stark_ctx {
     std::map<ZKey, stark::fr_t> z_cache;                                // fri_sample_z_ell(seed_z, level, size)  (fri.rs:59-82)
     std::unique_ptr<stark::PowCache> omega_tabs;                       // two-level power tables of a domain generator (DomainH, deep_ali/src/lib.rs:109-125); pow_table.hpp, made on first use
     void* pinned = nullptr; size_t pinned_bytes = 0;                   // small pinned staging area for async uploads / downloads
+    // Host sources of uploads enqueued by calls that return WITHOUT synchronising (ctx_upload_staged: the pointer tables of the batched transforms).
+    // Each copy lives until the event recorded behind its upload has passed; later calls reap the finished ones, teardown the rest.
+    struct StagedUpload { hipEvent_t done; std::unique_ptr<uint8_t[]> host; };
+    std::vector<StagedUpload> staged;
 
     // tuning / diagnostic options (stark_ctx_set_option): explicit API state, never the environment
     struct Options {
@@ -102,6 +106,7 @@ struct stark_ctx {
         bool merkle_node16_pair = true;  // t = 17 Merkle levels of > 4096 nodes with exactly 16 children each: the fixed two-permutation kernel k_node16_pair; 0 = the generic k_hash_ds2 (comparison)
         bool fri_side_pair = true;       // fri_build: the small layers' commitments on the side stream in the wave-pair form at every size (see side_commit); 0 = the latency forms (comparison)
         size_t sumcheck_verify_batch_max_slots = (size_t)1 << 25;   // a plan of the batched sum-check verifiers is run once it holds this many pool slots (1 GiB of field elements): device memory stays bounded whatever the batch
+        size_t ntt_batch_max_elems = (size_t)1 << 24;    // stark_ntt_batch_dev / stark_lde_batch_dev cut a batch into passes of at most this many output elements (ntt_batch_plan.hpp): 512 MiB of outputs and as much scratch per pass
         size_t prove_batch_max_rows = (size_t)1 << 22;   // the batched DEEP-FRI provers cut a batch into passes of at most this many rows (traces x n0) whose tails run side by side (fri_batch.hpp); device memory per pass stays near 70 B per row
     } opt;
     bool side_commit = false;            // set while fri_build enqueues work that runs underneath the 2^n-leaf launch: Merkle levels and leaf layers of t = 9, 17 take the
@@ -159,6 +164,9 @@ int32_t merkle_open_host(stark_tree* t, const std::vector<size_t>& indices, Merk
 int32_t ctx_transcript_params(stark_ctx* ctx, stark_params** out);
 int32_t ctx_merkle_params(stark_ctx* ctx, int t, stark_params** out);
 int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out);
+// `bytes` of host memory to device memory on the context's stream, out of a copy the context owns (stark_ctx::staged): the caller's source may die
+// on return and the host is not synchronised
+int32_t ctx_upload_staged(stark_ctx* ctx, void* dst, const void* src, size_t bytes);
 int32_t ctx_side_stream(stark_ctx* ctx, hipStream_t* out);
 // Fork: what is enqueued on *side from here on runs after everything enqueued on the context's stream so far, and concurrently with what that stream
 // receives next.  Join: the context's stream continues after everything enqueued on the side stream.  Events only; the host is not synchronised.

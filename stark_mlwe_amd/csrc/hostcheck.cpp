@@ -16,6 +16,7 @@
 #include "mfma_digits.hpp"
 #include "poseidon_chain.hpp"
 #include "fri_batch.hpp"
+#include "ntt_batch_plan.hpp"
 #include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
 
 using namespace stark;
@@ -548,5 +549,19 @@ int hc_fri_commit_batch(void* tparams, size_t B, const uint64_t* const* f0, size
     if (int rc = C.run()) return rc;
     for (size_t b = 0; b < B; ++b) for (size_t l = 0; l <= L; ++l) st4(roots + 4 * (b * (L + 1) + l), C.roots[l * B + b]);
     return 0;
+}
+}  // extern "C"
+
+// ---- the pass cutting of stark_ntt_batch_dev / stark_lde_batch_dev (ntt_batch_plan.hpp) --------------------------------------------------------
+extern "C" {
+// columns per pass into out[0 .. cap); returns the number of passes
+size_t hc_ntt_batch_passes(size_t batch, int log_out, size_t max_elems, size_t* out, size_t cap) {
+    const std::vector<size_t> p = ntt_batch_passes(batch, log_out, max_elems);
+    for (size_t i = 0; i < p.size() && i < cap; ++i) out[i] = p[i];
+    return p.size();
+}
+int hc_ntt_batch_ranges_overlap(const uint64_t* starts, size_t batch, size_t bytes) {
+    std::vector<const void*> p(batch); for (size_t i = 0; i < batch; ++i) p[i] = (const void*)(uintptr_t)starts[i];
+    return ntt_batch_ranges_overlap(p.data(), batch, bytes) ? 1 : 0;
 }
 }  // extern "C"

@@ -181,8 +181,24 @@ __device__ __forceinline__ fr_t finish29_plain(fr29_t y) { fr29_partial_reduce<F
 // PRE: the pass applies a coset pre-scale on load (first pass of a coset transform): the scaled points go to LDS first and the head
 // works from there — eight inlined table products would not unroll.
 struct TileJob { uint64_t base, tile; };     // strided: element offset of the tile, tile index inside its outer block
-template <class F, int MINW, bool PRE>
-__global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_strided(NttPassArgs A, const fr_t* src, fr_t* dst) {
+// Where the vectors of a BATCHED pass live (the NttBatchAddr instantiations of the pass kernels; stark_ntt_batch_dev / stark_lde_batch_dev): vector v is read at src_tab[v] (the
+// caller's columns, first pass of a transform) or src + v * src_pitch, and written at dst_tab[v] (the caller's outputs, last pass) or
+// dst + v * dst_pitch; pitches in elements.  Inside a vector every index — tile offsets, table exponents — is the single transform's.
+struct NttBatchAddr { const fr_t* const* src_tab; fr_t* const* dst_tab; uint64_t src_pitch, dst_pitch; };
+// Where a tile's vector starts.  The pass kernels take the batch addressing as an optional trailing kernel argument (BT... is empty or NttBatchAddr): the
+// plain instantiations pick the first overload of each pair at compile time and keep the signature and the one spacing, v << log_n, they always had.
+struct TileEnds { const fr_t* src; fr_t* dst; };
+__device__ __forceinline__ TileEnds strided_ends(const NttPassArgs&, TileJob&, const fr_t* src, fr_t* dst) { return TileEnds{src, dst}; }
+__device__ __forceinline__ TileEnds strided_ends(const NttPassArgs& A, TileJob& J, const fr_t* src, fr_t* dst, const NttBatchAddr& Bt) {
+    const uint64_t v = J.base >> A.log_n; J.base &= (1ull << A.log_n) - 1;          // the vector this tile belongs to, and the tile's offset inside it
+    return TileEnds{Bt.src_tab ? Bt.src_tab[v] : src + v * Bt.src_pitch, Bt.dst_tab ? Bt.dst_tab[v] : dst + v * Bt.dst_pitch};
+}
+__device__ __forceinline__ TileEnds last_ends(const NttPassArgs& A, uint64_t vec, const fr_t* src, fr_t* dst) { return TileEnds{src + (vec << A.log_vec), dst + (vec << A.log_vec)}; }
+__device__ __forceinline__ TileEnds last_ends(const NttPassArgs&, uint64_t vec, const fr_t* src, fr_t* dst, const NttBatchAddr& Bt) {
+    return TileEnds{Bt.src_tab ? Bt.src_tab[vec] : src + vec * Bt.src_pitch, Bt.dst_tab ? Bt.dst_tab[vec] : dst + vec * Bt.dst_pitch};
+}
+template <class F, int MINW, bool PRE, class... BT>
+__global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_strided(NttPassArgs A, const fr_t* src0, fr_t* dst0, BT... bt) {
     extern __shared__ uint4 lds[];
     const int B = 1 << A.log_b, C = 1 << A.log_c, E = B << A.log_c, NT = B > 1 ? B >> 1 : 1;
     const TileLds L = tile_lds(lds, E, NT);
@@ -190,7 +206,9 @@ __global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_strided(NttP
     auto job = [&](uint64_t t) { const uint64_t outer = t / tiles_per_outer, tile = t % tiles_per_outer; return TileJob{(outer << A.log_m) + (tile << A.log_c), tile}; };
     load_stage_tw<F>(L.tw, A.stage_tw, NT);
     for (uint64_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {
-        const TileJob J = job(t);
+        TileJob J = job(t);
+        const TileEnds V = strided_ends(A, J, src0, dst0, bt...);
+        const fr_t* const src = V.src; fr_t* const dst = V.dst;
         int head;
         if (PRE && A.nz_points && A.log_b >= 3 && A.nz_points <= (uint32_t)(B >> 3)) {
             // Zero-padded input (LDE) whose non-zero points p < B/8 are the FIRST point of every head group: the three head stages pair a value with zeros,
@@ -257,8 +275,8 @@ __global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_strided(NttP
 }
 
 // Last (contiguous) pass with the digit-reversing store.  Tiles = n / (B*C).  PRE as above (single-pass coset transforms).
-template <class F, int MINW, bool PRE>
-__global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_last(NttPassArgs A, const fr_t* src0, fr_t* dst0) {
+template <class F, int MINW, bool PRE, class... BT>
+__global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_last(NttPassArgs A, const fr_t* src0, fr_t* dst0, BT... bt) {
     extern __shared__ uint4 lds[];
     const int B = 1 << A.log_b, E = B << A.log_c, NT = B > 1 ? B >> 1 : 1;
     const TileLds L = tile_lds(lds, E, NT);
@@ -268,7 +286,8 @@ __global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_last(NttPass
     load_stage_tw<F>(L.tw, A.stage_tw, NT);
     for (uint64_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {
         const uint64_t vec = t / tiles_per_vec, vt = t % tiles_per_vec, k2 = vt / k1_blocks, k1_0 = (vt % k1_blocks) << A.log_c;
-        const fr_t* src = src0 + (vec << A.log_vec); fr_t* dst = dst0 + (vec << A.log_vec);
+        const TileEnds V = last_ends(A, vec, src0, dst0, bt...);
+        const fr_t* const src = V.src; fr_t* const dst = V.dst;
         int head;
         if (PRE) {
             for (int idx = threadIdx.x; idx < E; idx += blockDim.x) {
@@ -360,6 +379,17 @@ template <class F>
 __global__ void k_zero_fill(fr_t* p, uint64_t n) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) stg(p + i, fr_zero<F>());
+}
+// The padding of a batched pass in one launch: for every vector v < B, dst_v[i] = i < head ? src_v[i] : 0 over first <= i < len, with
+// src_v = src_tab[v] or src + v * src_pitch and dst_v = dst_tab[v] or dst + v * dst_pitch.  head = 0: the zero tails [n, N) of the coefficient
+// vectors (k_zero_fill for all columns of the pass); head = 1: one-point columns, whose interpolation is the point itself.
+template <class F>
+__global__ void k_pad_fill_batch(const fr_t* const* src_tab, const fr_t* src, uint64_t src_pitch, fr_t* const* dst_tab, fr_t* dst, uint64_t dst_pitch,
+                                 uint64_t first, uint64_t head, uint64_t len, uint64_t B) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, span = len - first, v = t / span, i = first + t % span;
+    if (v >= B) return;
+    fr_t* d = dst_tab ? dst_tab[v] : dst + v * dst_pitch;
+    if (i < head) stg(d + i, ldg((src_tab ? src_tab[v] : src + v * src_pitch) + i)); else stg(d + i, fr_zero<F>());
 }
 
 }  // namespace stark
