@@ -214,7 +214,7 @@ struct KernelConsts {
     // the multiplier tables of every dot product again, as nine 29-bit limbs of c*2^261 mod r per entry (fr29.hpp)
     std::vector<uint32_t> lu29, lu_pre29, row0_29, sparse29, gamma29;
     std::vector<uint32_t> mds29, mds_pre29;   // dense forms for the one-wave kernel (every entry meets an S-box output: all scaled)
-    // t = 17 only: the dense matrices as int8 MFMA operand fragments (signed radix-256 digits, Toeplitz windows), see mfma_frags
+    // t = 17 only: the dense matrices as int8 MFMA operand fragments (signed radix-256 digits of the residue tables), see mfma_frags
     std::vector<int8_t> mds_frag, mds_pre_frag;
     // t = 17 only: the partial rounds UNROLLED over all rp rounds for the five-wave latency kernel (poseidon_chain.hpp):
     //     X_{q+1} = c_{q+1} + sum_j u_{q,j} s_j^(0) + a_q y_q + sum_{p<q} Gamma_{q,p} y_p,   y_q = X_q^5,   Gamma_{q,p} = sum_j u_{q,j} w_{p,j}
@@ -233,23 +233,27 @@ template <class Pred> inline std::vector<uint32_t> to_radix29(const std::vector<
     for (size_t i = 0; i < v.size(); ++i) fr29_const_from<PF>(scaled(i) ? fr_mul<PF>(v[i], k) : v[i], &o[9 * i]);
     return o;
 }
-// A-operand fragments of v_mfma_i32_32x32x32_i8 for y = M * x with x an S-box output (poseidon_pair.hpp pair_apply_mds_mfma).
-// Entry (i, e) is c = M[i][e] * 2^20 * 32 in Montgomery form (2^20: fr_pow5_r29's scale; 32: the Montgomery step by 2^261 instead of 2^256),
-// written in SIGNED radix-256 digits d[0..31] in [-128, 127] (add 0x80 to every byte with carries, subtract 0x80 from every digit; c < r
-// keeps the top byte below 0x80, so no 33rd digit).  The product's digit-column sums are S[c] = sum_{e,b} d_ie[c - b] * xd_e[b]: row c of
-// a Toeplitz matrix.  Fragment ((i*2 + rt)*t + e) holds, for lane l (tile row r = l & 31, k half kh = l >> 5), the 16 bytes
-// j -> d_ie[(32 rt + r) - (16 kh + j)] (zero outside 0..31): the left operand of the K-step of element e for the output digits 32 rt .. 32 rt + 31.
+// A-operand fragments of v_mfma_i32_32x32x32_i8 for y = M * x with x an S-box output (poseidon_pair.hpp pair_apply_mds_mfma): RESIDUE TABLES.
+// The left factor is constant, so the reduction mod r is done here, once per parameter set.  For entry (i, e) and input digit position b,
+//     C[i][e][b] = ( M[i][e] * 2^20 * 256^b ) mod r        a plain integer in [0, r)   (2^20: fr_pow5_r29's scale)
+// written in SIGNED radix-256 digits d[0..31] in [-128, 127] (add 0x80 to every byte with carries, subtract 0x80 from every digit; C < r
+// keeps the top byte below 0x80, so no 33rd digit).  With xd_e the signed digits of the STORED x_e (x * 2^256 mod r),
+//     sum_{e,b} xd_e[b] * C[i][e][b]  ==  2^20 * sum_e M[i][e] * stored(x_e)  ==  stored((M x)_i)      (mod r),
+// so the digit sums S[c] = sum_{e,b} d_{i,e,b}[c] * xd_e[b], c = 0..31, are ONE 32-row tile of a dense int8 product (no structural zeros), and
+// sum_c S[c] 256^c needs no Montgomery step, only a reduction of its top bits.  Fragment (i*t + e) holds, for lane l (tile row = output digit
+// c = l & 31, K half kh = l >> 5), the 16 bytes j -> d_{i,e,16 kh + j}[c]: the left operand of the K-step of element e.  t*t*64*16 bytes.
 inline std::vector<int8_t> mfma_frags(const std::vector<fr_t>& mat, int t) {
-    std::vector<int8_t> out((size_t)t * 2 * t * 64 * 16, 0);
-    const fr_t scale = h_mul(fr_from_u64<PF>(1ull << FR29_SBOX_SHIFT), fr_from_u64<PF>(32));
+    std::vector<int8_t> out((size_t)t * t * 64 * 16, 0);
+    const fr_t scale = fr_from_u64<PF>(1ull << FR29_SBOX_SHIFT), k256 = fr_from_u64<PF>(256);
     for (int i = 0; i < t; ++i) for (int e = 0; e < t; ++e) {
-        const fr_t c = h_mul(mat[(size_t)i * t + e], scale);
-        int8_t d[32]; int cy = 0;
-        for (int b = 0; b < 32; ++b) { const int v = (int)((c.v[b >> 2] >> (8 * (b & 3))) & 0xff) + 0x80 + cy; cy = v >> 8; d[b] = (int8_t)((v & 0xff) - 0x80); }
-        for (int rt = 0; rt < 2; ++rt) for (int l = 0; l < 64; ++l) for (int j = 0; j < 16; ++j) {
-            const int idx = (32 * rt + (l & 31)) - (16 * (l >> 5) + j);
-            out[(((size_t)(i * 2 + rt) * t + e) * 64 + l) * 16 + j] = (idx >= 0 && idx < 32) ? d[idx] : (int8_t)0;
+        fr_t g = h_mul(mat[(size_t)i * t + e], scale);                        // Montgomery form of M[i][e] * 2^20 * 256^b, b = 0, 1, ...
+        int8_t d[32][32];                                                     // d[b][c]
+        for (int b = 0; b < 32; ++b, g = h_mul(g, k256)) {
+            const fr_t c = fr_to_canonical<PF>(g); int cy = 0;
+            for (int k = 0; k < 32; ++k) { const int v = (int)((c.v[k >> 2] >> (8 * (k & 3))) & 0xff) + 0x80 + cy; cy = v >> 8; d[b][k] = (int8_t)((v & 0xff) - 0x80); }
         }
+        for (int l = 0; l < 64; ++l) for (int j = 0; j < 16; ++j)
+            out[(((size_t)i * t + e) * 64 + l) * 16 + j] = d[16 * (l >> 5) + j][l & 31];
     }
     return out;
 }

@@ -5,6 +5,7 @@
 // state) so that `pytest -m "not gpu"` can check the product's host logic and kernel bodies against
 // the oracle without a GPU.  No product entry point loads or calls this library; it is not a
 // fallback: libstark_mlwe_hip.so fails with STARK_ERR_HIP when no device is present.
+#include <algorithm>
 #include <cstring>
 #include <vector>
 #include "fr.hpp"
@@ -151,9 +152,10 @@ int hc_params_export(void* h, uint64_t* mds, uint64_t* rc_full, uint64_t* rc_par
     return 0;
 }
 // One full round's linear layer  y = M * x  (x = S-box outputs) of t = 17 states, two ways on the host: through the in-place L*U rows the VALU
-// kernels use (which = 0), and through an emulation of the matrix-core path (which = 1): signed recoding, the int8 FRAGMENT TABLES the kernels
-// read (host_util.hpp mfma_frags: lane l of fragment (i, rt, e) holds A[row l & 31][k = 16 (l >> 5) + j]), D[row][col] = sum_k A[row][k] B[k][col]
-// per tile, the accumulator rows as the two lanes of a sponge receive them, the fold and the Montgomery step of mfma_digits.hpp.  pre: the B_1 * M matrix.
+// kernels use (which = 0), and through an emulation of the matrix-core path (which = 1): signed recoding, the int8 RESIDUE FRAGMENT TABLES the
+// kernels read (host_util.hpp mfma_frags: lane l of fragment (i, e) holds A[row l & 31][k = 16 (l >> 5) + j]), D[row][col] = sum_k A[row][k] B[k][col]
+// for the one 32-row tile, the accumulator rows as the two lanes of a sponge receive them, the fold and the finishing step of mfma_digits.hpp.
+// pre: the B_1 * M matrix.
 int hc_full_round_linear(void* h, int which, int pre, uint64_t* states, size_t n) {
     HcParams* P = (HcParams*)h; const int t = P->dev.t;
     if (t != 17 || P->kc.mds_frag.empty()) return -1;
@@ -165,21 +167,40 @@ int hc_full_round_linear(void* h, int which, int pre, uint64_t* states, size_t n
         else {
             std::vector<fr_t> xd(t); for (int e = 0; e < t; ++e) xd[e] = recode_signed(st[e]);
             for (int i = 0; i < t; ++i) {
-                int64_t col[18]; for (int k = 0; k < 18; ++k) col[k] = 0;
-                for (int rt = 0; rt < 2; ++rt) {
-                    int32_t S[32];
-                    for (int r = 0; r < 32; ++r) { int64_t acc = 0;
-                        for (int e = 0; e < t; ++e) for (int kh = 0; kh < 2; ++kh) { const int8_t* a = &F[((((size_t)(i * 2 + rt) * t + e) * 64) + (r + 32 * kh)) * 16];
-                            const int8_t* b = reinterpret_cast<const int8_t*>(xd[e].v) + 16 * kh; for (int j = 0; j < 16; ++j) acc += (int64_t)a[j] * b[j]; }
-                        if (acc > 0x7fffffffll || acc < -0x80000000ll) return -2; S[r] = (int32_t)acc; }
-                    int32_t lo[16], hi[16];
-                    for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
-                    mfma_fold_rows(col, lo, hi, rt);
-                }
+                int32_t S[32];
+                for (int r = 0; r < 32; ++r) { int64_t acc = 0;
+                    for (int e = 0; e < t; ++e) for (int kh = 0; kh < 2; ++kh) { const int8_t* a = &F[((((size_t)i * t + e) * 64) + (r + 32 * kh)) * 16];
+                        const int8_t* b = reinterpret_cast<const int8_t*>(xd[e].v) + 16 * kh; for (int j = 0; j < 16; ++j) acc += (int64_t)a[j] * b[j]; }
+                    if (acc > 0x7fffffffll || acc < -0x80000000ll) return -2; S[r] = (int32_t)acc; }
+                int32_t lo[16], hi[16];
+                for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
+                int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
+                mfma_fold_rows(col, lo, hi);
                 out[i] = mfma_finish_cols(col);
             }
         }
         for (int j = 0; j < t; ++j) st4(states + 4 * (s * t + j), out[j]);
+    }
+    return 0;
+}
+// the int8 residue fragment table of a t = 17 parameter set (pre = 0: M, 1: B_1 * M), t*t*64*16 bytes in the layout of host_util.hpp mfma_frags;
+// copies at most cap bytes out, returns the table's length
+size_t hc_mfma_frag_table(void* h, int pre, int8_t* out, size_t cap) {
+    HcParams* P = (HcParams*)h; const std::vector<int8_t>& F = pre ? P->kc.mds_pre_frag : P->kc.mds_frag;
+    if (out) memcpy(out, F.data(), std::min(cap, F.size()));
+    return F.size();
+}
+// the finishing step of the matrix-core product alone (mfma_digits.hpp: fold, signed carry pass, product-free reduction): n cases of 32 digit sums
+// S_c (any |S_c| < 2^24, row c = digit position) -> the canonical representative of sum_c S_c 256^c mod r; -1 when a sum is outside the domain
+int hc_mfma_finish(const int32_t* sums, size_t n, uint64_t* out) {
+    for (size_t s = 0; s < n; ++s) {
+        const int32_t* S = sums + 32 * s;
+        for (int c = 0; c < 32; ++c) if (S[c] >= (1 << 24) || S[c] <= -(1 << 24)) return -1;
+        int32_t lo[16], hi[16];
+        for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
+        int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
+        mfma_fold_rows(col, lo, hi);
+        st4(out + 4 * s, mfma_finish_cols(col));
     }
     return 0;
 }

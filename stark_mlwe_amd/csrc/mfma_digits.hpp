@@ -1,8 +1,10 @@
 // stark_mlwe_amd/csrc/mfma_digits.hpp — HOST MIRROR of the scalar pieces of the int8-MFMA field products (poseidon_pair.hpp: recode_signed,
-// mfma_fold_rows, the carry pass + Montgomery step of pair_apply_mds_mfma), statement by statement, for the host-check library: the fragment
-// tables (host_util.hpp mfma_frags) and the fold arithmetic are exercised on the CPU against the L*U rows (tests/test_hostcheck.py).  The device
-// keeps its own copies: routing the kernels through these templates compiled to a 2 % slower leaf kernel (same box, A/B), and the kernels'
-// own results are pinned by the GPU parity tests.  Not included by any device translation unit.
+// mfma_fold_rows, mfma_finish_cols: the fold of the 32 digit sums, the signed carry pass and the product-free reduction of pair_apply_mds_mfma),
+// statement by statement, for the host-check library: the residue fragment tables (host_util.hpp mfma_frags), the fold and the finishing step are
+// exercised on the CPU against the L*U rows and against big integers (tests/test_hostcheck.py, tests/test_full_round_residue_tables_host.py).  The
+// bounds of every intermediate are written next to the device code.  The device keeps its own copies: routing the kernels through these templates
+// compiled to a 2 % slower leaf kernel (same box, A/B), and the kernels' own results are pinned by the GPU parity tests.  Not included by any
+// device translation unit.
 #pragma once
 #include "fr.hpp"
 #include "fr29.hpp"
@@ -17,10 +19,10 @@ FR_HD fr_t recode_signed(const fr_t& x) {
     for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)x.v[i] + 0x80808080u + c; y.v[i] = (uint32_t)t ^ 0x80808080u; c = t >> 32; }
     return y;
 }
-// Digit sums of one 32-row tile pair -> 64-bit columns of weight 2^(29k).  lo[reg] = row (reg & 3) + 8 (reg >> 2) of tile rt (the rows the lower lane of a
-// sponge's lane pair receives), hi[reg] = the same + 4 (the upper lane's rows); row = digit position c - 32 rt.  Pairs of adjacent digit sums
-// (S0 + 256 S1 < 2^33) go into the column that holds the lower digit (shift < 29: no overflow, the columns are not normalised).
-template <class V> FR_HD void mfma_fold_rows(int64_t* col, const V& lo, const V& hi, int rt) {
+// The 32 digit sums of one output -> nine 64-bit columns of weight 2^(29k).  lo[reg] = row (reg & 3) + 8 (reg >> 2) of the tile (the rows the lower lane
+// of a sponge's lane pair receives), hi[reg] = the same + 4 (the upper lane's rows); row = digit position c.  Pairs of adjacent digit sums
+// (|S0 + 256 S1| < 2^32.01) go into the column that holds the lower digit (shift < 29, at most two pairs per column: below 2^61.01).
+template <class V> FR_HD void mfma_fold_rows(int64_t* col, const V& lo, const V& hi) {
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -29,17 +31,30 @@ template <class V> FR_HD void mfma_fold_rows(int64_t* col, const V& lo, const V&
             for (int p = 0; p < 2; ++p) {
                 const V& a = hh ? hi : lo;
                 const int64_t pair = (int64_t)a[4 * q + 2 * p] + (int64_t)a[4 * q + 2 * p + 1] * 256;
-                const int c = 32 * rt + 8 * q + 4 * hh + 2 * p, k = (8 * c) / 29, sh = 8 * c - 29 * k;
+                const int c = 8 * q + 4 * hh + 2 * p, k = (8 * c) / 29, sh = 8 * c - 29 * k;
                 col[k] += pair * ((int64_t)1 << sh);      // pair may be negative: a product, not a shift of a signed value (undefined before C++20)
             }
 }
-// columns (signed, the total a non-negative integer) -> canonical field element: signed carry pass, Montgomery step by 2^261
+// nine signed columns (weight 2^(29k), the total any integer V with |V| < 2^272.01) -> the canonical representative of V mod r: signed carry pass,
+// q1 = floor(V / 2^254) - 1, W = V - q1 r = (V mod 2^254) + 2^254 - q1 t in (0, 3r), two conditional subtractions
 FR_HD fr_t mfma_finish_cols(int64_t* col) {
-    fr_wide29 w;
+    typedef PallasFr PF;
+    static_assert(fr_p29<PF>(4) < (1u << 10) && fr_p29<PF>(5) == 0 && fr_p29<PF>(6) == 0 && fr_p29<PF>(7) == 0 && fr_p29<PF>(8) == (1u << 22), "r = 2^254 + t with t below 2^126");
+    uint32_t l[9];
 #pragma unroll
-    for (int k = 0; k < 17; ++k) { col[k + 1] += col[k] >> 29; w.c[k] = (uint64_t)col[k] & FR_M29; }
-    w.c[17] = (uint64_t)col[17];
-    return fr_wide29_reduce<PallasFr>(w);
+    for (int k = 0; k < 8; ++k) { col[k + 1] += col[k] >> 29; l[k] = (uint32_t)col[k] & FR_M29; }
+    const int64_t top = col[8];
+    const int32_t q1 = (int32_t)(top >> 22) - 1;
+    l[8] = ((uint32_t)top & ((1u << 22) - 1)) + (1u << 22);
+    int64_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { const int64_t d = (int64_t)l[i] - (int64_t)q1 * (int64_t)fr_p29<PF>(i) + carry; l[i] = (uint32_t)d & FR_M29; carry = d >> 29; }
+    int32_t c32 = (int32_t)carry;                            // |carry| < 2^19 from here on
+#pragma unroll
+    for (int i = 5; i < 9; ++i) { const int32_t d = (int32_t)l[i] + c32; if (i < 8) { l[i] = (uint32_t)d & FR_M29; c32 = d >> 29; } else l[8] = (uint32_t)d; }
+    fr_t z = fr29_pack_reduce<PF>(l);
+    fr_cond_sub<PF>(z.v, 0u);
+    return z;
 }
 
 }  // namespace stark

@@ -7,7 +7,7 @@
 // the batch: lane l of both waves works on state l, each wave on its own part of the linear algebra.
 // Same LDS per state, twice the waves per SIMD (4 workgroups of 40 KiB per CU for t = 17).
 //   * full rounds : S-box on the wave's own elements; the dense MDS product
-//                   - t = 17: on the MATRIX CORES (pair_apply_mds_mfma below): int8 MFMA over signed radix-256 digits, X the even
+//                   - t = 17: on the MATRIX CORES (pair_apply_mds_mfma below): int8 MFMA of the matrix's residue table with the state's signed radix-256 digits, X the even
 //                     output rows, Y the odd ones, each wave holding the whole state as operand registers;
 //                   - t = 9: as in-place L*(U*x) on the VALU, X taking the even rows and Y the odd rows of each step (rows
 //                     2k/2k+1 read only slots >= 2k, so a single barrier between the step's reads and its two writes keeps it race-free);
@@ -105,22 +105,33 @@ __device__ __forceinline__ void pair_sbox_full(const PairState& s, const fr_t* r
 }
 
 // ---- the dense full-round product on the matrix cores (T = 17) ---------------------------------------------------------------------
-// y = M * x for the 64 sponges of the pair, x = the S-box outputs, stored RECODED (signed digits) in the state slots.  With both factors in
-// signed radix-256 digits the digit-column sums S[(i,c)][n] = sum_{e,b} d_ie[c-b] * xd_e[n][b] are one int8 matrix product with a Toeplitz
-// left factor (host_util.hpp mfma_frags), |S| < 2^24: exact in the i32 accumulators of v_mfma_i32_32x32x32_i8.
+// y = M * x for the 64 sponges of the pair, x = the S-box outputs, stored RECODED (signed digits) in the state slots.  The left factor is the
+// RESIDUE TABLE of the matrix (host_util.hpp mfma_frags): for every entry (i, e) and input digit position b the 32 signed radix-256 digits of
+// C[i][e][b] = (M[i][e] * 2^20 * 256^b) mod r.  The digit sums S[(i,c)][n] = sum_{e,b} d_{i,e,b}[c] * xd_e[n][b], c = 0..31, are one dense int8
+// matrix product (K = 17 * 32, no structural zeros), and V = sum_c S[c] 256^c is congruent to the stored form of (M x)_i: no Montgomery step,
+// no 512-bit intermediate — only the bits of V above 2^254 are reduced, without a product (r = 2^254 + t, t < 2^126).
 //   * B operand: lane l holds, for element e and column tile ct, the 16 bytes of half (l >> 5) of element e of sponge 32 ct + (l & 31) — exactly one
-//     16-byte state slot.  A wave keeps the whole state in registers (17 x 2 x 4 VGPRs): every A fragment then feeds 4 MFMAs (1 KB of L2 traffic per
-//     128 cycles of matrix pipe; less reuse is L1-bound, tools/mfma_dense.hip).
-//   * X takes the even outputs, Y the odd ones.  Per output: 68 MFMAs into 2 x 2 tiles (digits 0..31 / 32..63 x sponges 0..31 / 32..63).
-//   * D layout: lane l, register r = row (r & 3) + 8 (r >> 2) + 4 (l >> 5) of column l & 31: a sponge's 64 digit sums sit in lanes l and l + 32.
+//     16-byte state slot.  A wave keeps the whole state in registers (17 x 2 x 4 VGPRs): every A fragment then feeds 2 MFMAs (1 KB of L2 traffic per
+//     64 cycles of matrix pipe, the same bytes per MFMA as the former two-row-tile form; less reuse is L1-bound, tools/mfma_dense.hip).
+//   * X takes the even outputs, Y the odd ones.  Per output: 34 MFMAs into 1 x 2 tiles (digits 0..31 x sponges 0..31 / 32..63).
+//   * D layout: lane l, register r = row (r & 3) + 8 (r >> 2) + 4 (l >> 5) of column l & 31: a sponge's 32 digit sums sit in lanes l and l + 32.
 //     v_permlane32_swap(tile of sponges 0..31, tile of sponges 32..63) hands the lower lane the upper lane's rows of ITS sponge and vice versa, so
 //     that afterwards lane l owns sponge l (the kernels' lane <-> sponge map) with the rows in a lane-uniform order.
-//   * fold: pairs of adjacent digit sums (S0 + 256 S1 < 2^33) are shifted into the 64-bit column of weight 2^(29k) that holds the lower digit; a
-//     signed carry pass (the total is a non-negative integer) leaves 29-bit limbs, and the usual Montgomery step by 2^261 returns y canonical.
-// 95 k SIMD-cycles per product against ~180 k for the in-place L*U form (tools/mfma_mds.hip, profiles/r02_mfma_mds_end_to_end_prototype.jsonl).
+//   * fold and finish, with the bound of every intermediate (mfma_digits.hpp mirrors both statement by statement for the host checks):
+//       digit sum   |S_c| <= 17 * 32 * 128 * 128 = 8 912 896 < 2^24: exact in the i32 accumulators.  Everything below holds for ANY |S_c| < 2^24.
+//       pair        P = S_c + 256 S_{c+1} (c even), |P| < 257 * 2^24 < 2^32.01, goes into the 64-bit column k = floor(8c / 29) of weight 2^(29k)
+//                   that holds the lower digit, shifted by 8c - 29k <= 28: |P << sh| < 2^60.01.
+//       column      nine columns (8 * 30 = 240 = 29 * 8 + 8); bit positions 16 apart: at most two pairs per column, |col| < 2^61.01; with the carry
+//                   from below (< 2^32.1) still < 2^62.  The signed carry pass leaves limbs 0..7 in [0, 2^29) and top = floor(V / 2^232) in column 8:
+//                   |V| < 2^24 * (256^32 - 1) / 255 < 2^272.01, |top| < 2^40.01.
+//       q           q1 = floor(V / 2^254) - 1 = (top >> 22) - 1, |q1| < 2^18.02; q1 * (a 29-bit limb of t) < 2^47.02.
+//       W           W = V - q1 r = (V mod 2^254) + 2^254 - q1 t  (a five-limb multiply and one signed carry pass): V mod 2^254 is in [0, 2^254) and
+//                   |q1 t| < 2^144.02, so W is in (2^254 - 2^144.02, 2^255 + 2^144.02), inside (0, 3r) and below 2^256: every limb ends non-negative,
+//                   the top limb below 2^24, and TWO conditional subtractions of r return the canonical value (the second fires only for
+//                   V mod 2^254 within 2^144 of 2^254; taking q1 one lower than the floor is what keeps W non-negative at the other end).
 typedef int mfma_v4i __attribute__((ext_vector_type(4)));
 typedef int mfma_v16i __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ void mfma_fold_rows(int64_t* col, const mfma_v16i& lo, const mfma_v16i& hi, int rt) {
+__device__ __forceinline__ void mfma_fold_rows(int64_t* col, const mfma_v16i& lo, const mfma_v16i& hi) {
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -129,13 +140,32 @@ __device__ __forceinline__ void mfma_fold_rows(int64_t* col, const mfma_v16i& lo
             for (int p = 0; p < 2; ++p) {
                 const mfma_v16i& a = hh ? hi : lo;
                 const int64_t pair = (int64_t)a[4 * q + 2 * p] + (int64_t)a[4 * q + 2 * p + 1] * 256;
-                const int c = 32 * rt + 8 * q + 4 * hh + 2 * p, k = (8 * c) / 29, sh = 8 * c - 29 * k;
+                const int c = 8 * q + 4 * hh + 2 * p, k = (8 * c) / 29, sh = 8 * c - 29 * k;
                 col[k] += pair * ((int64_t)1 << sh);      // pair may be negative: a product, not a shift of a signed value (undefined before C++20)
             }
+}
+// nine signed columns (weight 2^(29k), the total any integer V with |V| < 2^272.01) -> the canonical representative of V mod r
+__device__ __forceinline__ fr_t mfma_finish_cols(int64_t* col) {
+    uint32_t l[9];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { col[k + 1] += col[k] >> 29; l[k] = (uint32_t)col[k] & FR_M29; }
+    const int64_t top = col[8];
+    const int32_t q1 = (int32_t)(top >> 22) - 1;
+    l[8] = ((uint32_t)top & ((1u << 22) - 1)) + (1u << 22);
+    int64_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { const int64_t d = (int64_t)l[i] - (int64_t)q1 * (int64_t)fr_p29<PF>(i) + carry; l[i] = (uint32_t)d & FR_M29; carry = d >> 29; }
+    int32_t c32 = (int32_t)carry;                            // |carry| < 2^19 from here on
+#pragma unroll
+    for (int i = 5; i < 9; ++i) { const int32_t d = (int32_t)l[i] + c32; if (i < 8) { l[i] = (uint32_t)d & FR_M29; c32 = d >> 29; } else l[8] = (uint32_t)d; }
+    fr_t z = fr29_pack_reduce<PF>(l);
+    fr_cond_sub<PF>(z.v, 0u);
+    return z;
 }
 // Precondition: every state slot holds a recoded S-box output and a barrier has passed.  Ends with the state canonical and consistent.
 __device__ __forceinline__ void pair_apply_mds_mfma(const PairState& s, const void* frag) {
     constexpr int T = 17;
+    static_assert(fr_p29<PF>(4) < (1u << 10) && fr_p29<PF>(5) == 0 && fr_p29<PF>(6) == 0 && fr_p29<PF>(7) == 0 && fr_p29<PF>(8) == (1u << 22), "r = 2^254 + t with t below 2^126");
     const int lane = s.lane, h = lane >> 5;
     mfma_v4i b[T][2];
 #pragma unroll
@@ -146,40 +176,29 @@ __device__ __forceinline__ void pair_apply_mds_mfma(const PairState& s, const vo
     const mfma_v4i* A = reinterpret_cast<const mfma_v4i*>(frag) + lane;
 #pragma unroll 1
     for (int i = s.isY ? 1 : 0; i < T; i += 2) {
-        mfma_v16i acc[2][2];
+        mfma_v16i acc[2];
 #pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
+        for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[rt][ct][r] = 0;
-        const mfma_v4i* Ai = A + (size_t)(i * 2) * T * 64;
+            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+        const mfma_v4i* Ai = A + (size_t)i * T * 64;
 #pragma unroll
         for (int e = 0; e < T; ++e) {
-            const mfma_v4i a0 = Ai[(size_t)e * 64], a1 = Ai[(size_t)(T + e) * 64];
+            const mfma_v4i a = Ai[(size_t)e * 64];
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                acc[0][ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b[e][ct], acc[0][ct], 0, 0, 0);
-                acc[1][ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b[e][ct], acc[1][ct], 0, 0, 0);
-            }
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
         }
-        mfma_v16i lo[2], hi[2];
+        mfma_v16i lo, hi;
 #pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
+        for (int r = 0; r < 16; ++r) {
+            const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
+            lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
+        }
+        int64_t col[9];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[rt][0][r], (unsigned)acc[rt][1][r], false, false);
-                lo[rt][r] = (int)sw[0]; hi[rt][r] = (int)sw[1];
-            }
-        int64_t col[18];
-#pragma unroll
-        for (int k = 0; k < 18; ++k) col[k] = 0;
-        mfma_fold_rows(col, lo[0], hi[0], 0); mfma_fold_rows(col, lo[1], hi[1], 1);
-        fr_wide29 w;
-#pragma unroll
-        for (int k = 0; k < 17; ++k) { col[k + 1] += col[k] >> 29; w.c[k] = (uint64_t)col[k] & FR_M29; }
-        w.c[17] = (uint64_t)col[17];
-        s.sto(i, fr_wide29_reduce<PF>(w));
+        for (int k = 0; k < 9; ++k) col[k] = 0;
+        mfma_fold_rows(col, lo, hi);
+        s.sto(i, mfma_finish_cols(col));
     }
     __syncthreads();
 }

@@ -1,0 +1,89 @@
+// tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds:
+// the fragment tables (host_util.hpp mfma_frags) and the fold + finishing step (mfma_digits.hpp), against the portable field code.  Meant for a
+// sanitizer build; tools/mfma_finish_sanitize.sh builds it with AddressSanitizer + UBSan and runs it:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I stark_mlwe_amd/csrc tools/mfma_finish_check.cpp -o tools/bin/mfma_finish_check
+#include <cstdio>
+#include <cstdint>
+#include <vector>
+#include "fr.hpp"
+#include "host_util.hpp"
+#include "mfma_digits.hpp"
+using namespace stark;
+typedef PallasFr PF;
+
+static fr_t finish(const int32_t* S) {
+    int32_t lo[16], hi[16];
+    for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
+    int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
+    mfma_fold_rows(col, lo, hi);
+    return mfma_finish_cols(col);
+}
+// sum_c S_c 256^c mod r as a plain integer, through the field code
+static fr_t reference(const int32_t* S) {
+    fr_t acc = host::h_zero(), w = host::h_one(); const fr_t k256 = fr_from_u64<PF>(256);
+    for (int c = 0; c < 32; ++c, w = host::h_mul(w, k256)) {
+        const fr_t term = host::h_mul(fr_from_u64<PF>((uint64_t)(S[c] < 0 ? -(int64_t)S[c] : (int64_t)S[c])), w);
+        acc = S[c] < 0 ? host::h_sub(acc, term) : host::h_add(acc, term);
+    }
+    return fr_to_canonical<PF>(acc);
+}
+// V = k r + d (k any sign, d in {-1, 0, 1}) -> 32 digit sums with V = sum S_c 256^c: signed radix-256 digits at c < 31, S_31 carries the surplus
+static std::vector<int32_t> split_kr(int64_t k, int d) {
+    const bool neg = k < 0 || (k == 0 && d < 0);
+    const uint64_t ak = (uint64_t)(k < 0 ? -k : k); const int dd = neg ? -d : d;          // |V| = ak r + dd >= 0
+    uint32_t w[10]; uint64_t c = 0;
+    for (int i = 0; i < 8; ++i) { const uint64_t t = ak * PF::P(i) + c; w[i] = (uint32_t)t; c = t >> 32; }
+    w[8] = (uint32_t)c; w[9] = (uint32_t)(c >> 32);
+    int64_t cy = dd;
+    for (int i = 0; i < 10 && cy; ++i) { const int64_t t = (int64_t)w[i] + cy; w[i] = (uint32_t)t; cy = t >> 32; }
+    std::vector<int32_t> S(32); int carry = 0;
+    for (int b = 0; b < 31; ++b) { const int v = (int)((w[b >> 2] >> (8 * (b & 3))) & 0xff) + carry; carry = v >= 128; S[b] = carry ? v - 256 : v; }
+    int64_t rest = carry;
+    for (int b = 31; b < 38; ++b) rest += (int64_t)((w[b >> 2] >> (8 * (b & 3))) & 0xff) << (8 * (b - 31));
+    S[31] = (int32_t)rest;
+    if (neg) for (auto& v : S) v = -v;
+    return S;
+}
+int main() {
+    const int32_t LIM = (1 << 24) - 1; long bad = 0, n = 0;
+    std::vector<std::vector<int32_t>> cases;
+    cases.push_back(std::vector<int32_t>(32, LIM)); cases.push_back(std::vector<int32_t>(32, -LIM)); cases.push_back(std::vector<int32_t>(32, 0));
+    { std::vector<int32_t> a(32), b(32); for (int c = 0; c < 32; ++c) { a[c] = c & 1 ? -LIM : LIM; b[c] = -a[c]; } cases.push_back(a); cases.push_back(b); }
+    for (int c : {0, 31}) for (int32_t v : {1, -1, LIM, -LIM}) { std::vector<int32_t> s(32, 0); s[c] = v; cases.push_back(s); }
+    // V = k 2^254 - 1, k 2^254, k 2^254 + 1: S_31 = k 2^6 (+-), the rest from the signed digits of -1 / 0 / +1
+    for (int32_t k : {-(1 << 17), -1, 0, 1, 1 << 17}) for (int d : {-1, 0, 1}) { std::vector<int32_t> s(32, 0); s[31] = k * 64; s[0] = d; cases.push_back(s); }
+    // V = k r - 1, k r, k r + 1: the two ends of the range the conditional subtractions see
+    for (int64_t k : {-(int64_t)(1 << 17), (int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)(1 << 17)}) for (int d : {-1, 0, 1}) {
+        const std::vector<int32_t> s = split_kr(k, d);
+        for (int c = 0; c < 32; ++c) if (s[c] > LIM || s[c] < -LIM || (c < 31 && (s[c] > 128 || s[c] < -128))) { fprintf(stderr, "crafted case outside the domain\n"); return 1; }
+        cases.push_back(s);
+    }
+    uint64_t x = 0x9e3779b97f4a7c15ull; auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
+    for (int i = 0; i < 20000; ++i) { std::vector<int32_t> s(32); for (auto& v : s) v = (int32_t)(rnd() % (2 * (uint64_t)LIM + 1)) - LIM; cases.push_back(s); }
+    { int idx = 0;                                      // k r + d is d mod r whatever k: checked without the reference as well
+      for (int64_t k : {-(int64_t)(1 << 17), (int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)(1 << 17)}) for (int d : {-1, 0, 1}) {
+        const fr_t got = finish(split_kr(k, d).data()); fr_t want = host::h_zero(); if (d > 0) want.v[0] = 1; if (d < 0) { for (int i = 0; i < 8; ++i) want.v[i] = PF::P(i); want.v[0] -= 1; }
+        ++n; ++idx; if (!fr_eq(got, want)) { if (bad < 5) fprintf(stderr, "k r + d: mismatch in crafted case %d\n", idx - 1); ++bad; }
+      } }
+    for (const auto& s : cases) { ++n; if (!fr_eq(finish(s.data()), reference(s.data()))) { if (bad < 5) fprintf(stderr, "finishing step: mismatch in case %ld\n", n - 1); ++bad; } }
+    // the tables: one emulated product per matrix against the dense field product (states of S-box outputs: the tables carry 2^20)
+    const host::KernelConsts kc = host::make_kernel_consts(host::consts_transcript());
+    if (!kc.ok || kc.mds_frag.size() != (size_t)17 * 17 * 64 * 16) { fprintf(stderr, "tables missing\n"); return 1; }
+    const fr_t k20 = fr_from_u64<PF>(1ull << FR29_SBOX_SHIFT);
+    for (int pre = 0; pre < 2; ++pre) for (int rep = 0; rep < 8; ++rep) {
+        const std::vector<int8_t>& F = pre ? kc.mds_pre_frag : kc.mds_frag; const std::vector<fr_t>& M = pre ? kc.mds_pre : kc.mds;
+        fr_t st[17], xd[17];
+        for (int e = 0; e < 17; ++e) { for (int i = 0; i < 8; ++i) st[e].v[i] = (uint32_t)rnd(); st[e].v[7] &= 0x3fffffffu; if (rep == 0) st[e] = e & 1 ? host::h_zero() : host::h_sub(host::h_zero(), host::h_one()); xd[e] = recode_signed(st[e]); }
+        for (int i = 0; i < 17; ++i) {
+            int32_t S[32];
+            for (int r = 0; r < 32; ++r) { int64_t acc = 0;
+                for (int e = 0; e < 17; ++e) for (int kh = 0; kh < 2; ++kh) { const int8_t* a = &F[((((size_t)i * 17 + e) * 64) + (r + 32 * kh)) * 16];
+                    const int8_t* b = reinterpret_cast<const int8_t*>(xd[e].v) + 16 * kh; for (int j = 0; j < 16; ++j) acc += (int64_t)a[j] * b[j]; }
+                S[r] = (int32_t)acc; }
+            fr_t want = host::h_zero(); for (int e = 0; e < 17; ++e) want = host::h_add(want, host::h_mul(host::h_mul(M[(size_t)i * 17 + e], k20), st[e]));
+            ++n; if (!fr_eq(finish(S), want)) { if (bad < 5) fprintf(stderr, "product: mismatch pre %d rep %d row %d\n", pre, rep, i); ++bad; }
+        }
+    }
+    printf("{\"check\": \"residue tables and finishing step against the portable field code\", \"cases\": %ld, \"mismatches\": %ld}\n", n, bad);
+    return bad ? 1 : 0;
+}
