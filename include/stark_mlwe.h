@@ -83,6 +83,8 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  *   instead of the five-wave latency kernel; comparison), "sponge_debug" (timing experiments on the five-wave kernel; digests are WRONG when set).
  *   "prove_batch_max_rows" (1..2^28, default 2^22: the rows of one pass of the batched DEEP-FRI provers).
  *   "ntt_batch_max_elems" (1..2^28, default 2^24: the output elements of one pass of stark_ntt_batch_dev / stark_lde_batch_dev).
+ *   "mle_log_tile" (3..12, default 12; -1 restores the default: the rounds one launch of stark_mle_evaluate_dev / _batch_dev folds),
+ *   "mle_lane_contiguous" (0 | 1, default 0; -1 restores the default: a lane of those launches owns consecutive elements instead of interleaved ones; comparison).
  * An unknown key is STARK_ERR_INVALID_ARG; stark_last_error then lists the known keys.
  * Changing an option synchronises the stream and drops the cached NTT plans. */
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value);
@@ -266,6 +268,17 @@ int32_t stark_commitment_verify(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_
                                 const uint8_t* proof, size_t len, int32_t* accepted);
 /* Mle::evaluate (channel/src/lib.rs:279-295): the multilinear extension of a 2^k table at r (k elements); host pointers. */
 int32_t stark_mle_evaluate(stark_ctx_t* ctx, const uint64_t* table, size_t k, const uint64_t* r, uint64_t* out4);
+/* Mle::evaluate (channel/src/lib.rs:279-295) of a DEVICE-resident table of 2^k elements at the point r (HOST, k elements) into out4 (DEVICE, one
+ * element): the batch form below with batch = 1. */
+int32_t stark_mle_evaluate_dev(stark_ctx_t* ctx, const uint64_t* table, size_t k, const uint64_t* r, uint64_t* out4);
+/* Mle::evaluate (channel/src/lib.rs:279-295) of `batch` tables of 2^k elements each: tables is a HOST array of DEVICE pointers, r the HOST array of
+ * the batch x k challenges (point i at r + 4 * k * i), out the batch results in DEVICE memory.  out[i] == stark_mle_evaluate on table i and point i,
+ * byte for byte.  Every challenge is known up front, so one launch folds "mle_log_tile" rounds of all tables and an evaluation is
+ * ceil(k / mle_log_tile) launches that read each table once.  Stream-ordered, no host synchronisation: r and the pointer table are copied before
+ * the call returns.  Tables may repeat (one table at many points) and are left intact.  batch == 0 returns STARK_OK; k = 0 gives out[i] = table i's
+ * only element.  STARK_ERR_INVALID_ARG, checked on the host before anything is launched: a null ctx, tables, tables[i] or out; a null r with
+ * k > 0; k > 40; an out range that overlaps a table. */
+int32_t stark_mle_evaluate_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* tables, size_t k, const uint64_t* r, uint64_t* out);
 int32_t stark_sumcheck_prove_plain(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out);
 int32_t stark_sumcheck_prove_plain_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out);
 int32_t stark_sumcheck_verify_plain(stark_ctx_t* ctx, size_t k, uint64_t tree_label, const uint8_t* proof, size_t len, int32_t* accepted);

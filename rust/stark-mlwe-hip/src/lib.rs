@@ -488,6 +488,13 @@ pub mod channel {
         ctx.chk(unsafe { stark_sumcheck_verify_mf_batch(ctx.raw(), proofs.len(), ptrs.as_ptr(), lens.as_ptr(), k, tree_labels.as_ptr(), queries_per_round, ok.as_mut_ptr()) });
         ok.into_iter().map(|a| a == 1).collect()
     }
+    /// `Mle::new(table_i).evaluate(&r_i)` (:279-295) of many DEVICE tables of 2^k elements into the DEVICE vector `out` (`tables.len()` elements), a
+    /// few launches for the whole batch; `points[i]` holds the k challenges of table i.  A table may repeat.  Stream-ordered: the caller
+    /// synchronises before reading `out`.  Safety: every pointer is device memory of the stated length, and `out` overlaps no table.
+    pub unsafe fn mle_evaluate_batch_dev(ctx: &Ctx, k: usize, tables: &[*const u64], points: &[F], out: *mut u64) {
+        assert!(points.len() == tables.len() * k, "k challenges per table");
+        ctx.chk(stark_mle_evaluate_batch_dev(ctx.raw(), tables.len(), tables.as_ptr(), k, limbs(points), out));
+    }
 }
 
 pub mod comm {

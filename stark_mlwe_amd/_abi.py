@@ -100,6 +100,8 @@ SIGNATURES = {
     "stark_commitment_commit": (i32, [vp, u64, vp, sz, vpp]),
     "stark_commitment_verify": (i32, [vp, u64, vp, vp, sz, vp, vp, sz, C.POINTER(i32)]),
     "stark_mle_evaluate": (i32, [vp, vp, sz, vp, vp]),
+    "stark_mle_evaluate_dev": (i32, [vp, vp, sz, vp, vp]),
+    "stark_mle_evaluate_batch_dev": (i32, [vp, sz, vp, sz, vp, vp]),
     "stark_sumcheck_prove_plain": (i32, [vp, vp, sz, u64, vpp]),
     "stark_sumcheck_prove_plain_dev": (i32, [vp, vp, sz, u64, vpp]),
     "stark_sumcheck_verify_plain": (i32, [vp, sz, u64, vp, sz, C.POINTER(i32)]),

@@ -323,7 +323,7 @@ class Context:
         self._chk(self.lib.stark_ctx_sync(self.h))
 
     def set_option(self, key: str, value: int):
-        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems".  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
+        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous".  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
         self._chk(self.lib.stark_ctx_set_option(self.h, key.encode(), value))
 
     def trim(self):
@@ -616,6 +616,24 @@ class Context:
             raise StarkError(-1, "dimension mismatch")
         self._chk(self.lib.stark_mle_evaluate(self.h, _ptr(t), rr.shape[0], _ptr(rr), _ptr(out)))
         return out
+
+    def mle_evaluate_dev(self, table, k, r, out):
+        """Mle::evaluate of the DEVICE table `table` (int, 2^k elements) at the host point r (k, 4) into the DEVICE element `out` (int);
+        stream-ordered, no synchronisation (stark_mle_evaluate_dev)."""
+        rr = _arr(r).reshape(-1, 4)
+        if rr.shape[0] != k:
+            raise StarkError(-1, "dimension mismatch")
+        self._chk(self.lib.stark_mle_evaluate_dev(self.h, C.c_void_p(int(table)), k, _ptr(rr) if k else None, C.c_void_p(int(out))))
+
+    def mle_evaluate_batch_dev(self, tables, k, r, out):
+        """Mle::evaluate of each of the DEVICE tables `tables` (ints, 2^k elements each; a table may repeat) at its own host point r[i] ((B, k, 4)) into
+        the DEVICE vector `out` (int, B elements), a few launches for the whole batch; stream-ordered, no synchronisation (stark_mle_evaluate_batch_dev)."""
+        B = len(tables)
+        rr = _arr(r).reshape(-1, 4)
+        if rr.shape[0] != B * k:
+            raise StarkError(-1, "dimension mismatch")
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in tables])
+        self._chk(self.lib.stark_mle_evaluate_batch_dev(self.h, B, tab, k, _ptr(rr) if B * k else None, C.c_void_p(int(out))))
 
     def prove_plain(self, k, tree_label, witness):
         """prove_plain(&build_vk_plain(k, F::from(tree_label)), witness) -> bincode-layout ProofPlain bytes."""

@@ -217,6 +217,8 @@ static const OptionDef kOptions[] = {
     {"sumcheck_verify_batch_max_slots", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1) return "at least 1"; o.sumcheck_verify_batch_max_slots = (size_t)v; return nullptr; }},
     {"ntt_batch_max_elems", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.ntt_batch_max_elems = (size_t)v; return nullptr; }},
     {"prove_batch_max_rows", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.prove_batch_max_rows = (size_t)v; return nullptr; }},
+    {"mle_log_tile", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v != -1 && (v < 3 || v > 12)) return "3..12, or -1 for the default"; o.mle_log_tile = (int)v; return nullptr; }},
+    {"mle_lane_contiguous", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 1) return "0 or 1, or -1 for the default"; o.mle_lane_contiguous = (int)v; return nullptr; }},
 };
 extern "C" {
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value) {

@@ -12,6 +12,7 @@
 #include <memory>
 #include "verify_dev.hpp"
 #include "sumcheck_impl.hpp"
+#include "mle_dev.hpp"
 
 using namespace stark;
 
@@ -344,6 +345,65 @@ static int32_t verify_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t batch, 
     return STARK_OK;
 }
 
+// ---- Mle::evaluate of device-resident tables (mle_dev.hpp) ----------------------------------------------------------------------------
+template <int C, bool CONTIG>
+static void mle_launch(stark_ctx* ctx, size_t B, const fr_t* const* ptrs, const fr_t* layers, uint64_t len, int t, const fr_t* r, size_t k, size_t j0, fr_t* next) {
+    const unsigned gx = (unsigned)(((len >> C) + 255) / 256);
+    for (size_t b0 = 0; b0 < B; b0 += 65535)                                                // (a grid's y dimension)
+        hipLaunchKernelGGL((k_mle_fold_pass<C, CONTIG>), dim3(gx, (unsigned)std::min<size_t>(65535, B - b0)), dim3(256), 0, ctx->stream, ptrs, layers, len, t, (uint64_t)b0, r,
+                           (uint64_t)k, (uint64_t)j0, next);
+}
+static int32_t mle_pass(stark_ctx* ctx, bool contig, size_t B, const fr_t* const* ptrs, const fr_t* layers, uint64_t len, int t, const fr_t* r, size_t k, size_t j0, fr_t* next) {
+#define STARK_MLE_CASE(C) case C: if (contig) mle_launch<C, true>(ctx, B, ptrs, layers, len, t, r, k, j0, next); else mle_launch<C, false>(ctx, B, ptrs, layers, len, t, r, k, j0, next); break;
+    switch (mle_local_rounds(t)) { STARK_MLE_CASE(0) STARK_MLE_CASE(1) STARK_MLE_CASE(2) STARK_MLE_CASE(3) STARK_MLE_CASE(4) default: return ctx->fail(STARK_ERR_UNSUPPORTED, "mle: tile out of range"); }
+#undef STARK_MLE_CASE
+    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+}
+// out[b] = the multilinear extension of tables[b] (2^k elements, device) at r[b * k .. (b + 1) * k) (host).  One upload (the points and the pointer
+// table, out of a copy the context owns), ceil(k / T) passes, no synchronisation; the intermediate layers are pooled blocks of B * 2^(k - T) elements
+// and less, released in stream order.
+static int32_t mle_evaluate_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* tables, size_t k, const uint64_t* r, uint64_t* out) {
+    const size_t rbytes = B * k * sizeof(fr_t), bytes = rbytes + B * sizeof(void*);
+    std::vector<uint8_t> h(bytes);
+    if (rbytes) memcpy(h.data(), r, rbytes);
+    memcpy(h.data() + rbytes, tables, B * sizeof(void*));
+    DevBuf up; STARK_HIP(ctx, up.alloc(ctx, bytes)); STARK_TRY(ctx_upload_staged(ctx, up.p, h.data(), bytes));
+    const fr_t* dr = up.fr(); const fr_t* const* ptrs = (const fr_t* const*)((const uint8_t*)up.p + rbytes);
+    if (k == 0) {                                                                           // no round: out[b] = tables[b][0]
+        hipLaunchKernelGGL(k_sc_gather, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, ctx->stream, ptrs, (uint64_t)B, as_fr(out));
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    const int T = ctx->opt.mle_log_tile < 0 ? kMleDefaultLogTile : ctx->opt.mle_log_tile;
+    const bool contig = (ctx->opt.mle_lane_contiguous < 0 ? kMleDefaultContig : ctx->opt.mle_lane_contiguous) != 0;
+    const std::vector<int> rounds = mle_pass_rounds(k, T);
+    DevBuf tmp[2];                                                                          // layers after pass 0, 2, .. / 1, 3, ..
+    for (size_t i = 0; i + 1 < rounds.size() && i < 2; ++i) {
+        size_t left = k; for (size_t q = 0; q <= i; ++q) left -= (size_t)rounds[q];
+        STARK_HIP(ctx, tmp[i].alloc(ctx, (B << left) * sizeof(fr_t)));
+    }
+    size_t j0 = 0; const fr_t* cur = nullptr;
+    for (size_t i = 0; i < rounds.size(); ++i) {
+        fr_t* nxt = i + 1 == rounds.size() ? as_fr(out) : tmp[i & 1].fr();
+        STARK_TRY(mle_pass(ctx, contig, B, i ? nullptr : ptrs, cur, (uint64_t)1 << (k - j0), rounds[i], dr, k, j0, nxt));
+        j0 += (size_t)rounds[i]; cur = nxt;
+    }
+    return STARK_OK;
+}
+// the argument checks of stark_mle_evaluate_batch_dev, all before anything is enqueued
+static int32_t mle_check_args(stark_ctx* ctx, size_t B, const uint64_t* const* tables, size_t k, const uint64_t* r, const uint64_t* out) {
+    if (!tables) return ctx->fail(STARK_ERR_INVALID_ARG, "mle_evaluate: null table array");
+    if (!out) return ctx->fail(STARK_ERR_INVALID_ARG, "mle_evaluate: null out");
+    if (!r && k) return ctx->fail(STARK_ERR_INVALID_ARG, "mle_evaluate: null r with k > 0");
+    if (k > 40) return ctx->fail(STARK_ERR_INVALID_ARG, "mle_evaluate: k too large (at most 40)");
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + B * sizeof(fr_t), tbytes = sizeof(fr_t) << k;
+    for (size_t b = 0; b < B; ++b) {
+        if (!tables[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "mle_evaluate: null table entry " + std::to_string(b));
+        const uintptr_t t0 = (uintptr_t)tables[b];
+        if (t0 < o1 && o0 < t0 + tbytes) return ctx->fail(STARK_ERR_INVALID_ARG, "mle_evaluate: out overlaps table " + std::to_string(b));
+    }
+    return STARK_OK;
+}
+
 }  // namespace
 
 // ---- the streaming transcript as an object of the ABI (transcript/src/lib.rs:48-117) ------------------------------------------
@@ -440,6 +500,18 @@ int32_t stark_mle_evaluate(stark_ctx_t* ctx, const uint64_t* table, size_t k, co
     for (size_t j = 0; j < k; ++j) { STARK_TRY(fold(ctx, cur, len, load_fr(r + 4 * j), nxt)); std::swap(cur, nxt); len /= 2; }
     fr_t v; STARK_HIP(ctx, hipMemcpyAsync(&v, cur, sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     store_fr(out4, v); return STARK_OK;
+}
+// Mle::evaluate (:279-295) of `batch` device-resident tables, table i at the point r[i * k ..] (host): a few launches for the whole batch
+// (mle_dev.hpp), stream-ordered, no synchronisation.  The host form above keeps its own path.
+int32_t stark_mle_evaluate_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* tables, size_t k, const uint64_t* r, uint64_t* out) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!batch) return STARK_OK;
+    STARK_TRY(mle_check_args(ctx, batch, tables, k, r, out));
+    STARK_TRY(ctx_enter(ctx));
+    return mle_evaluate_batch_impl(ctx, batch, tables, k, r, out);
+}
+int32_t stark_mle_evaluate_dev(stark_ctx_t* ctx, const uint64_t* table, size_t k, const uint64_t* r, uint64_t* out4) {
+    return stark_mle_evaluate_batch_dev(ctx, 1, &table, k, r, out4);
 }
 
 int32_t stark_sumcheck_prove_plain_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out) {

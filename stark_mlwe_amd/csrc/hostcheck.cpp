@@ -19,6 +19,7 @@
 #include "fri_batch.hpp"
 #include "ntt_batch_plan.hpp"
 #include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
+#include "mle_dev.hpp"
 
 using namespace stark;
 
@@ -586,3 +587,62 @@ int hc_ntt_batch_ranges_overlap(const uint64_t* starts, size_t batch, size_t byt
     return ntt_batch_ranges_overlap(p.data(), batch, bytes) ? 1 : 0;
 }
 }  // extern "C"
+
+// ---- stark_mle_evaluate_batch_dev (mle_dev.hpp): the passes of the driver, every workgroup of k_mle_fold_pass run in lockstep on the host ----------
+// One pass: the lane geometry, the lane-local fold and the wave stage are the kernel's own inline pieces; a shuffle is a read of the partner's slot.
+template <int C>
+static void mle_pass_host(bool contig, size_t B, const fr_t* const* ptrs, const fr_t* layers, uint64_t len, int t, const fr_t* r, size_t k, size_t j0, fr_t* next) {
+    const int x = t - C; const uint64_t blocks = ((len >> C) + 255) / 256;
+    for (size_t b = 0; b < B; ++b) {
+        const fr_t* layer = ptrs ? ptrs[b] : layers + b * len; const fr_t* rr = r + b * k + j0; fr_t* dst = next + b * (len >> t);
+        for (uint64_t blk = 0; blk < blocks; ++blk) {
+            fr_t v[256], u[256]; MleLane L[256]; bool live[256];
+            for (int tid = 0; tid < 256; ++tid) {
+                L[tid] = mle_lane(blk * 256 + tid, t, C, contig); live[tid] = L[tid].first < len;
+                v[tid] = live[tid] ? mle_fold_local<C>(layer + L[tid].first, L[tid].stride, rr + L[tid].local0) : fr_zero<PF>();
+            }
+            for (int s = 0; s < 6 && s < x; ++s) {
+                for (int tid = 0; tid < 256; ++tid) u[tid] = mle_fold1(v[tid], v[tid ^ (1 << s)], rr[L[tid].cross0 + s]);
+                std::copy(u, u + 256, v);
+            }
+            if (x <= 6) { for (int tid = 0; tid < 256; ++tid) if (live[tid] && (tid & ((1 << x) - 1)) == 0) dst[L[tid].tile] = v[tid]; continue; }
+            const fr_t w[4] = {v[0], v[64], v[128], v[192]};
+            for (int tid = 0; tid < (4 >> (x - 6)); ++tid) {
+                const uint64_t tile = (blk << (kMleLogThreads - x)) + tid;
+                if ((tile << t) < len) dst[tile] = mle_fold_waves(w, x, tid, rr[L[tid].cross0 + 6], x == 8 ? rr[L[tid].cross0 + 7] : fr_zero<PF>());
+            }
+        }
+    }
+}
+extern "C" {
+// out[b] = Mle::evaluate of tables[b] (2^k elements) at r[b * k ..], through the driver's passes with tile 2^log_tile (-1: the default) and the lane
+// ownership `contig` (-1: the default).  passes (may be null) = the number of launches one evaluation takes.  -1: log_tile out of range.
+int hc_mle_evaluate_batch(size_t B, const uint64_t* const* tables, size_t k, const uint64_t* r, int log_tile, int contig, uint64_t* out, size_t* passes) {
+    const int T = log_tile < 0 ? kMleDefaultLogTile : log_tile;
+    if (T < kMleMinLogTile || T > kMleMaxLogTile || k > 40) return -1;
+    const bool cg = (contig < 0 ? kMleDefaultContig : contig) != 0;
+    const std::vector<int> rounds = mle_pass_rounds(k, T);
+    if (passes) *passes = rounds.size();
+    std::vector<std::vector<fr_t>> tab(B, std::vector<fr_t>((size_t)1 << k)); std::vector<const fr_t*> ptrs(B); std::vector<fr_t> rv(B * k);
+    for (size_t b = 0; b < B; ++b) { for (size_t i = 0; i < tab[b].size(); ++i) tab[b][i] = ld4(tables[b] + 4 * i); ptrs[b] = tab[b].data(); }
+    for (size_t i = 0; i < rv.size(); ++i) rv[i] = ld4(r + 4 * i);
+    if (k == 0) { for (size_t b = 0; b < B; ++b) st4(out + 4 * b, tab[b][0]); return 0; }
+    std::vector<fr_t> cur, nxt; size_t j0 = 0;
+    for (size_t i = 0; i < rounds.size(); ++i) {
+        const int t = rounds[i]; const uint64_t len = (uint64_t)1 << (k - j0);
+        nxt.assign(B * (len >> t), fr_zero<PF>());
+        switch (mle_local_rounds(t)) {
+            case 0: mle_pass_host<0>(cg, B, i ? nullptr : ptrs.data(), cur.data(), len, t, rv.data(), k, j0, nxt.data()); break;
+            case 1: mle_pass_host<1>(cg, B, i ? nullptr : ptrs.data(), cur.data(), len, t, rv.data(), k, j0, nxt.data()); break;
+            case 2: mle_pass_host<2>(cg, B, i ? nullptr : ptrs.data(), cur.data(), len, t, rv.data(), k, j0, nxt.data()); break;
+            case 3: mle_pass_host<3>(cg, B, i ? nullptr : ptrs.data(), cur.data(), len, t, rv.data(), k, j0, nxt.data()); break;
+            case 4: mle_pass_host<4>(cg, B, i ? nullptr : ptrs.data(), cur.data(), len, t, rv.data(), k, j0, nxt.data()); break;
+            default: return -1;
+        }
+        cur.swap(nxt); j0 += (size_t)t;
+    }
+    for (size_t b = 0; b < B; ++b) st4(out + 4 * b, cur[b]);
+    return 0;
+}
+}  // extern "C"
+extern "C" int hc_mle_default_log_tile() { return kMleDefaultLogTile; }
