@@ -160,6 +160,41 @@ int32_t stark_merkle_gather(stark_tree_t* t, int32_t lvl, const size_t* idx, siz
 int32_t stark_merkle_open(stark_tree_t* t, const size_t* idx, size_t k, uint8_t* buf, size_t cap, size_t* len);
 int32_t stark_merkle_free(stark_tree_t* t);
 
+/* Many trees in one device pass.  Element i of every result equals what the single call returns for item i alone, byte for byte, and the handles
+ * are ordinary stark_tree_t: every accessor above (and stark_merkle_open, stark_merkle_free) takes them, they may be freed in any order, and like
+ * every handle they keep their context alive.
+ *  - build: MerkleTree::new / new_pairs (merkle/src/lib.rs:147-193, 392-445) of `batch` trees of one shape (arity, n, pairs, params) — every arity
+ *    and width of the single build, ragged last nodes, n = 1 (no hash: root = leaf).  Stream-ordered with no host synchronisation (the labels and
+ *    pointer tables are copied before the call returns).  Level v of all trees is ONE pooled block of batch x len_v elements (tree i's level the
+ *    slice at i * len_v) that goes back to the pool when the last tree of the batch is freed; level 0 is one launch (a copy, or the pair leaves read
+ *    through the pointer tables) and every level above one launch whose kernel form is chosen for batch x nodes hashes.  The same pointer may appear
+ *    twice; inputs are left intact.  Shard builds (first_pos / level0 / stop_at_len) have no batch form.
+ *  - roots: the batch's roots with ONE download and one synchronisation (any complete trees of one context).
+ *  - open: open_union_of_paths (:246-315) of every tree: tree i opens idx[idx_off[i] .. idx_off[i+1]); out[i] is a stark_proof_t whose bytes are
+ *    exactly stark_merkle_open's (stark_proof_len / stark_proof_bytes).  The trees need not share a shape or come from a batch build; they share a
+ *    context.  Every tree is planned on the host and all siblings come back with one gather launch, one download and one synchronisation.
+ *  - verify: verify_many_ds (:587-722) over `batch` openings under one cfg_arity: item i has tree_labels[i], roots[4 i ..], the indices and values
+ *    (stored form, as the single call takes them) at [idx_off[i], idx_off[i+1]) and proofs[i] / lens[i]; accepted[i] == stark_merkle_verify_many_ds on
+ *    item i alone.  The host parses and plans every opening, the device runs one launch per (width, tree depth) and compares the roots: one upload,
+ *    one download, one synchronisation (a plan is cut at 2^25 pool slots, so a huge batch runs as several).  An item that does not decode, fails a
+ *    structural check or has no index is a rejection, never an error.  verify_pairs_ds has no batch form.
+ * batch == 0 returns STARK_OK.  STARK_ERR_INVALID_ARG, before any launch: a null ctx, params, table or out / accepted; a null leaves[i] or trees[i];
+ * pairs without a cp table; n == 0; an arity incompatible with the parameter width; a non-monotone idx_off; (open) an empty index list for a tree, as
+ * open_many, or a leaf index out of range; trees of different contexts or a partial tree; batch x n above 2^31 - 1.  Arity 1 with n > 1 and (verify) a
+ * cfg_arity above 128 are STARK_ERR_UNSUPPORTED, as in the single calls.  On any error every out[i] is NULL and every accepted[i] is 0. */
+/* MerkleTree::new / new_pairs (merkle/src/lib.rs:147-193, 392-445) of `batch` trees of one shape (arity, n, pairs, params). */
+int32_t stark_merkle_build_batch_dev(stark_ctx_t* ctx, stark_params_t* p, size_t arity, size_t batch, const uint64_t* tree_labels /* host, batch */,
+                                     const uint64_t* const* leaves /* host array of batch DEVICE pointers */, size_t n, int32_t pairs,
+                                     const uint64_t* const* cp /* as leaves; NULL iff !pairs; a NULL entry = zeros */, stark_tree_t** out /* host, batch handles */);
+/* the batch roots with ONE download (MerkleTree::root, merkle/src/lib.rs:195-197) */
+int32_t stark_merkle_roots_batch(stark_tree_t* const* trees, size_t batch, uint64_t* roots /* host, batch x 4 */);
+/* open_union_of_paths (merkle/src/lib.rs:246-315) of every tree: tree i opens idx[idx_off[i] .. idx_off[i+1]) */
+int32_t stark_merkle_open_batch(stark_tree_t* const* trees, size_t batch, const size_t* idx, const size_t* idx_off /* batch + 1 */, stark_proof_t** out);
+/* verify_many_ds (merkle/src/lib.rs:587-722) over `batch` openings; accepted[i] == stark_merkle_verify_many_ds on item i alone. */
+int32_t stark_merkle_verify_many_ds_batch(stark_ctx_t* ctx, size_t cfg_arity, size_t batch, const uint64_t* tree_labels, const uint64_t* roots /* batch x 4 */,
+                                          const size_t* indices, const size_t* idx_off, const uint64_t* values /* concatenated, idx_off-indexed */,
+                                          const uint8_t* const* proofs, const size_t* lens, int32_t* accepted);
+
 /* ---- FRI ------------------------------------------------------------------------------------------ */
 /* fri_sample_z_ell (fri.rs:59-82). */
 int32_t stark_fri_sample_z(stark_ctx_t* ctx, stark_params_t* tparams, uint64_t seed_z, size_t level, size_t domain_size, uint64_t* z4);
@@ -264,6 +299,9 @@ int32_t stark_merkle_verify_pairs_ds(stark_ctx_t* ctx, size_t cfg_arity, uint64_
 /* trait CommitmentScheme for MerkleCommitment (commitment/src/lib.rs:13-27, 80-114): commit (arity 16, tree_label = ds_tag, parameters
  * "POSEIDON-T17-X5-SEED") -> a tree handle (root: stark_merkle_root; open: stark_merkle_open); verify over the bytes of stark_merkle_open. */
 int32_t stark_commitment_commit(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* leaves, size_t n, stark_tree_t** out);
+/* MerkleCommitment::commit (commitment/src/lib.rs:80-90) of `batch` DEVICE vectors of n leaves: arity 16, "POSEIDON-T17-X5-SEED", tree_label = ds_tags[i];
+ * stark_merkle_build_batch_dev with those parameters (same contract; out[i] equals stark_commitment_commit's tree on vector i). */
+int32_t stark_commitment_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* ds_tags, const uint64_t* const* leaves, size_t n, stark_tree_t** out);
 int32_t stark_commitment_verify(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* root4, const size_t* indices, size_t k, const uint64_t* values,
                                 const uint8_t* proof, size_t len, int32_t* accepted);
 /* Mle::evaluate (channel/src/lib.rs:279-295): the multilinear extension of a 2^k table at r (k elements); host pointers. */

@@ -175,6 +175,56 @@ pub mod merkle {
     }
     impl Drop for Tree { fn drop(&mut self) { unsafe { stark_merkle_free(self.raw); } } }
 
+    /// `MerkleTree::new` / `new_pairs` (merkle/src/lib.rs:147-193, 392-445) of many DEVICE columns of `n` leaves in one pass: one launch per level for
+    /// the whole batch, stream-ordered.  `cp`: `None` for plain trees; a null entry is a zero column.  Element i == the single build of column i.
+    /// Safety: every pointer is device memory of `n` elements that stays valid until the work has run.
+    pub unsafe fn build_batch_dev(ctx: &Ctx, leaves: &[*const u64], cp: Option<&[*const u64]>, n: usize, arity: usize, tree_labels: &[u64], params: &Params) -> Vec<Tree> {
+        assert!(tree_labels.len() == leaves.len() && cp.map_or(true, |c| c.len() == leaves.len()), "one label (and one cp entry) per tree");
+        let mut raw: Vec<*mut stark_tree_t> = vec![ptr::null_mut(); leaves.len()];
+        ctx.chk(stark_merkle_build_batch_dev(ctx.raw, params.raw, arity, leaves.len(), tree_labels.as_ptr(), leaves.as_ptr(), n, cp.is_some() as i32,
+                                             cp.map_or(ptr::null(), |c| c.as_ptr()), raw.as_mut_ptr()));
+        raw.into_iter().zip(tree_labels).map(|(raw, &tree_label)| Tree { raw, arity, tree_label }).collect()
+    }
+    /// `MerkleCommitment::commit` (commitment/src/lib.rs:80-90) of many DEVICE vectors in one pass; same contract as `build_batch_dev`.
+    pub unsafe fn commit_batch_dev(ctx: &Ctx, leaves: &[*const u64], n: usize, ds_tags: &[u64]) -> Vec<Tree> {
+        assert!(ds_tags.len() == leaves.len(), "one ds_tag per vector");
+        let mut raw: Vec<*mut stark_tree_t> = vec![ptr::null_mut(); leaves.len()];
+        ctx.chk(stark_commitment_commit_batch_dev(ctx.raw, leaves.len(), ds_tags.as_ptr(), leaves.as_ptr(), n, raw.as_mut_ptr()));
+        raw.into_iter().zip(ds_tags).map(|(raw, &tree_label)| Tree { raw, arity: 16, tree_label }).collect()
+    }
+    /// The roots of many trees with one download.
+    pub fn roots_batch(ctx: &Ctx, trees: &[&Tree]) -> Vec<F> {
+        let raw: Vec<*mut stark_tree_t> = trees.iter().map(|t| t.raw).collect();
+        let mut out = vec![F::from(0u64); trees.len()];
+        ctx.chk(unsafe { stark_merkle_roots_batch(raw.as_ptr(), raw.len(), limbs_mut(&mut out)) });
+        out
+    }
+    /// `open_many` of many trees (any shapes, one context) with one gather: element i == `trees[i].open_many(ctx, indices[i])`.
+    pub fn open_many_batch(ctx: &Ctx, trees: &[&Tree], indices: &[&[usize]]) -> Vec<Vec<u8>> {
+        assert!(trees.len() == indices.len(), "one index list per tree");
+        let raw: Vec<*mut stark_tree_t> = trees.iter().map(|t| t.raw).collect();
+        let mut off = vec![0usize]; let mut idx = Vec::new();
+        for ix in indices { idx.extend_from_slice(ix); off.push(idx.len()); }
+        let mut out: Vec<*mut stark_proof_t> = vec![ptr::null_mut(); trees.len()];
+        ctx.chk(unsafe { stark_merkle_open_batch(raw.as_ptr(), raw.len(), idx.as_ptr(), off.as_ptr(), out.as_mut_ptr()) });
+        out.into_iter().map(|h| unsafe {
+            let mut b = vec![0u8; stark_proof_len(h)];
+            ctx.chk(stark_proof_bytes(h, b.as_mut_ptr())); stark_proof_free(h); b
+        }).collect()
+    }
+    /// `verify_single` of many openings in one device pass: element i == `verify_single(ctx, cfg_arity, tree_labels[i], &roots[i], indices[i], leaves[i], proofs[i])`.
+    pub fn verify_single_batch(ctx: &Ctx, cfg_arity: usize, tree_labels: &[u64], roots: &[F], indices: &[&[usize]], leaves: &[&[F]], proofs: &[&[u8]]) -> Vec<bool> {
+        let b = proofs.len();
+        assert!(tree_labels.len() == b && roots.len() == b && indices.len() == b && leaves.len() == b, "one label, root, index list and value list per proof");
+        let mut off = vec![0usize]; let mut idx = Vec::new(); let mut vals: Vec<F> = Vec::new();
+        for (ix, lv) in indices.iter().zip(leaves) { assert!(ix.len() == lv.len(), "one value per index"); idx.extend_from_slice(ix); vals.extend_from_slice(lv); off.push(idx.len()); }
+        let ptrs: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+        let lens: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let mut ok = vec![0i32; b];
+        ctx.chk(unsafe { stark_merkle_verify_many_ds_batch(ctx.raw, cfg_arity, b, tree_labels.as_ptr(), limbs(roots), idx.as_ptr(), off.as_ptr(), limbs(&vals), ptrs.as_ptr(), lens.as_ptr(), ok.as_mut_ptr()) });
+        ok.into_iter().map(|a| a == 1).collect()
+    }
+
     /// `MerkleProver::verify_single` → `verify_many_ds` (merkle/src/lib.rs:587-722, 800-812).
     pub fn verify_single(ctx: &Ctx, cfg_arity: usize, tree_label: u64, root: &F, indices: &[usize], leaves: &[F], proof_bytes: &[u8]) -> bool {
         let mut ok = 0i32;

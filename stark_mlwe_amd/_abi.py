@@ -66,6 +66,10 @@ SIGNATURES = {
     "stark_merkle_gather": (i32, [vp, i32, vp, sz, vp]),
     "stark_merkle_open": (i32, [vp, vp, sz, vp, sz, szp]),
     "stark_merkle_free": (i32, [vp]),
+    "stark_merkle_build_batch_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, i32, vp, vp]),
+    "stark_merkle_roots_batch": (i32, [vp, sz, vp]),
+    "stark_merkle_open_batch": (i32, [vp, sz, vp, vp, vp]),
+    "stark_merkle_verify_many_ds_batch": (i32, [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
     "stark_fri_sample_z": (i32, [vp, vp, u64, sz, sz, vp]),
     "stark_fri_fold": (i32, [vp, vp, sz, vp, sz, vp]),
     "stark_fri_fold_dev": (i32, [vp, vp, sz, vp, sz, vp]),
@@ -98,6 +102,7 @@ SIGNATURES = {
     "stark_merkle_verify_many_ds": (i32, [vp, sz, u64, vp, vp, sz, vp, vp, sz, C.POINTER(i32)]),
     "stark_merkle_verify_pairs_ds": (i32, [vp, sz, u64, vp, vp, sz, vp, vp, vp, sz, C.POINTER(i32)]),
     "stark_commitment_commit": (i32, [vp, u64, vp, sz, vpp]),
+    "stark_commitment_commit_batch_dev": (i32, [vp, sz, vp, vp, sz, vp]),
     "stark_commitment_verify": (i32, [vp, u64, vp, vp, sz, vp, vp, sz, C.POINTER(i32)]),
     "stark_mle_evaluate": (i32, [vp, vp, sz, vp, vp]),
     "stark_mle_evaluate_dev": (i32, [vp, vp, sz, vp, vp]),

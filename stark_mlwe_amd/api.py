@@ -425,6 +425,74 @@ class Context:
         self._chk(self.lib.stark_merkle_build(self.h, cfg.params.h, cfg.arity, cfg.tree_label, _ptr(f), f.shape[0] if f.size else 0, 1, _ptr(cp), C.byref(h)))
         return MerkleTree(self, h, cfg)
 
+    def merkle_build_batch_dev(self, leaves, n, cfg_arity, tree_labels, params, cp=None):
+        """MerkleTree::new / new_pairs of each of the DEVICE columns `leaves` (ints, n elements each) in one pass, one launch per level for the whole
+        batch; `cp`: None, or a list of DEVICE pointers / None per tree (None = a zero column).  Stream-ordered, no synchronisation.  -> list of
+        MerkleTree, each equal to the single build of that column (stark_merkle_build_batch_dev)."""
+        B = len(leaves)
+        if len(tree_labels) != B or (cp is not None and len(cp) != B):
+            raise StarkError(-1, "one tree label (and one cp entry) per tree")
+        tab = (C.c_void_p * max(B, 1))(*[None if x is None else int(x) for x in leaves])
+        ctab = None if cp is None else (C.c_void_p * max(B, 1))(*[None if x is None else int(x) for x in cp])
+        lab = np.ascontiguousarray(tree_labels, dtype=np.uint64)
+        out = (C.c_void_p * max(B, 1))()
+        self._chk(self.lib.stark_merkle_build_batch_dev(self.h, params.h, cfg_arity, B, _ptr(lab), tab, n, 0 if cp is None else 1, ctab, out))
+        return [MerkleTree(self, C.c_void_p(out[b]), MerkleChannelCfg(cfg_arity, params, int(lab[b]))) for b in range(B)]
+
+    def commitment_commit_batch_dev(self, ds_tags, leaves, n):
+        """MerkleCommitment::commit of each of the DEVICE vectors `leaves` (ints, n elements) in one pass -> list of MerkleTree
+        (stark_commitment_commit_batch_dev)."""
+        B = len(leaves)
+        if len(ds_tags) != B:
+            raise StarkError(-1, "one ds_tag per vector")
+        tab = (C.c_void_p * max(B, 1))(*[None if x is None else int(x) for x in leaves])
+        lab = np.ascontiguousarray(ds_tags, dtype=np.uint64)
+        out = (C.c_void_p * max(B, 1))()
+        self._chk(self.lib.stark_commitment_commit_batch_dev(self.h, B, _ptr(lab), tab, n, out))
+        return [MerkleTree(self, C.c_void_p(out[b]), MerkleChannelCfg(16, None, int(lab[b]))) for b in range(B)]
+
+    def merkle_roots_batch(self, trees):
+        """The roots of `trees` (MerkleTree, one context) as a (B, 4) array with one download (stark_merkle_roots_batch)."""
+        B = len(trees)
+        tab = (C.c_void_p * max(B, 1))(*[t.h for t in trees])
+        out = np.zeros((B, 4), np.uint64)
+        self._chk(self.lib.stark_merkle_roots_batch(tab, B, _ptr(out)))
+        return out
+
+    def merkle_open_batch(self, trees, indices):
+        """open_union_of_paths of every tree of `trees` (any shapes, one context) at indices[i], all siblings in one gather -> list of canonical
+        MerkleProof bytes, each equal to trees[i].open_many(indices[i]) (stark_merkle_open_batch)."""
+        B = len(trees)
+        if len(indices) != B:
+            raise StarkError(-1, "one index list per tree")
+        off = np.zeros(B + 1, np.uint64); off[1:] = np.cumsum([len(ix) for ix in indices])
+        ix = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64).reshape(-1) for x in indices]) if B else np.zeros(0), dtype=np.uint64)
+        tab = (C.c_void_p * max(B, 1))(*[t.h for t in trees])
+        out = (C.c_void_p * max(B, 1))()
+        self._chk(self.lib.stark_merkle_open_batch(tab, B, _ptr(ix), _ptr(off), out))
+        return [self._proof_out(C.c_void_p(out[b]))[0] for b in range(B)]
+
+    def merkle_verify_single_batch(self, cfg_arity, tree_labels, roots, indices, leaves, proofs) -> list:
+        """MerkleProver::verify_single on each of the openings (tree_labels[i], roots[i], indices[i], leaves[i], proofs[i]) in one device pass;
+        one bool per opening, each equal to merkle_verify_single of it alone (stark_merkle_verify_many_ds_batch)."""
+        B = len(proofs)
+        if not (len(tree_labels) == len(roots) == len(indices) == len(leaves) == B):
+            raise StarkError(-1, "one label, root, index list and value list per proof")
+        if B == 0:
+            return []
+        off = np.zeros(B + 1, np.uint64); off[1:] = np.cumsum([len(ix) for ix in indices])
+        ix = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint64).reshape(-1) for x in indices]), dtype=np.uint64)
+        vals = np.ascontiguousarray(np.concatenate([_arr(v).reshape(-1, 4) for v in leaves]), dtype=np.uint64)
+        if vals.shape[0] != ix.shape[0]:
+            raise StarkError(-1, "one value per index")
+        bufs = [(C.c_uint8 * max(1, len(p))).from_buffer_copy(bytes(p) or b"\0") for p in proofs]
+        ptrs = (C.c_void_p * B)(*[C.cast(b, C.c_void_p) for b in bufs])
+        lens = (C.c_size_t * B)(*[len(p) for p in proofs])
+        lab = np.ascontiguousarray(tree_labels, dtype=np.uint64); rt = np.ascontiguousarray(np.stack([_arr(r).reshape(4) for r in roots]), dtype=np.uint64)
+        acc = (C.c_int32 * B)()
+        self._chk(self.lib.stark_merkle_verify_many_ds_batch(self.h, cfg_arity, B, _ptr(lab), _ptr(rt), _ptr(ix), _ptr(off), _ptr(vals), ptrs, lens, acc))
+        return [bool(acc[i]) for i in range(B)]
+
     # ---- fri ---------------------------------------------------------------------------------------
     def fri_sample_z_ell(self, seed_z, level, domain_size):
         out = np.zeros(4, np.uint64)

@@ -13,6 +13,7 @@
 #include "poseidon_wave.hpp"
 #include "poseidon_transcript.hpp"
 #include "fri_dev.hpp"
+#include "merkle_batch.hpp"
 
 using namespace stark;
 
@@ -253,6 +254,7 @@ int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
+int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
                                  const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out) {
     return hash_ds_on(ctx, ctx->stream, p, DsStream::make(mode, arity, level, 0, label, in0, in1, mode == 1 ? n_hashes : n_hashes * chunk, 1, positions_dev, mode == 1 ? 0 : chunk), out);
@@ -266,7 +268,7 @@ static void ds_attrs() {
     lds_attr((const void*)k_hash_ds<DS>); lds_attr((const void*)k_hash_ds2<17, DS>); lds_attr((const void*)k_hash_ds2<9, DS>); lds_attr((const void*)k_hash_ds_chain<DS>);
 }
 void stark::poseidon_set_attrs() {
-    ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>();
+    ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>(); ds_attrs<DsBatchPairPtrStream>();
     for (const void* k : {(const void*)k_leaf_pair, (const void*)k_permute_batch, (const void*)k_tr_hash, (const void*)k_hash_stream, (const void*)k_leaf_pair2, (const void*)k_node16_pair,
                           (const void*)k_tr_hash_chain, (const void*)k_leaf_pair_chain, (const void*)k_tr_stream_chain, (const void*)k_tr_batch_chain})
         lds_attr(k);
@@ -447,3 +449,111 @@ extern "C" int32_t stark_merkle_open(stark_tree_t* t, const size_t* idx, size_t 
     if (buf) { if (cap < b.size()) return t->ctx->fail(STARK_ERR_INVALID_ARG, "buffer too small"); memcpy(buf, b.data(), b.size()); }
     return STARK_OK;
 }
+
+// ---- many trees in one pass (merkle_batch.hpp) ----------------------------------------------------------------------------------------------------
+namespace stark {
+// The device executor of merkle_build_batch: every step is one launch on the context's stream (a few, for more than 65535 trees in the copy), the
+// level blocks are pooled and owned by the holder the batch's trees share, and the labels and pointer tables go up as ONE staged upload.
+struct MerkleBatchDevExec {
+    stark_ctx* ctx; stark_params* p; std::shared_ptr<TreeBlocks> blocks; DevBuf tab;
+    MerkleBatchDevExec(stark_ctx* c, stark_params* p_) : ctx(c), p(p_), blocks(std::make_shared<TreeBlocks>(c)) {}
+    int32_t level_block(size_t n_fr, fr_t** out) {
+        void* q = nullptr; STARK_TRY(ctx_alloc(ctx, n_fr * sizeof(fr_t), &q)); blocks->blocks.push_back(q); *out = (fr_t*)q; return STARK_OK;
+    }
+    int32_t tables(const uint64_t* labels, const fr_t* const* leaves, const fr_t* const* cp, size_t B, const uint64_t** labels_x, const fr_t* const** leaves_x, const fr_t* const** cp_x) {
+        std::vector<uint64_t> h((cp ? 3 : 2) * B);                       // [labels | leaves | cp], eight bytes each
+        for (size_t b = 0; b < B; ++b) { h[b] = labels[b]; h[B + b] = (uint64_t)(uintptr_t)leaves[b]; if (cp) h[2 * B + b] = (uint64_t)(uintptr_t)cp[b]; }
+        STARK_HIP(ctx, tab.alloc(ctx, h.size() * 8)); STARK_TRY(ctx_upload_staged(ctx, tab.p, h.data(), h.size() * 8));
+        const uint64_t* d = (const uint64_t*)tab.p;
+        *labels_x = d; *leaves_x = (const fr_t* const*)(d + B); *cp_x = cp ? (const fr_t* const*)(d + 2 * B) : nullptr; return STARK_OK;
+    }
+    int32_t copy_rows(const fr_t* const* src_x, size_t n, size_t B, fr_t* dst) {
+        for (size_t b0 = 0; b0 < B; b0 += 65535)
+            hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<size_t>(65535, B - b0)), dim3(256), 0, ctx->stream, src_x + b0, (uint64_t)n, dst + b0 * n);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t pair_level(const DsBatchPairPtrStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, p, D, out); }
+    int32_t ds_level(const DsBatchStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, p, D, out); }
+};
+int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, size_t batch, const uint64_t* labels, const uint64_t* const* leaves, size_t n, int pairs,
+                              const uint64_t* const* cp, stark_tree** out) {
+    for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (n == 0) return ctx->fail(STARK_ERR_INVALID_ARG, "no leaves");                                                 // merkle/src/lib.rs:148
+    if (arity == 0 || host::width_for_arity(arity) != p->dev.t) return ctx->fail(STARK_ERR_INVALID_ARG, "arity incompatible with Poseidon width");   // :155-161
+    if (arity == 1 && n > 1) return ctx->fail(STARK_ERR_UNSUPPORTED, "arity 1 with more than one leaf never terminates in the reference");
+    for (size_t b = 0; b < batch; ++b) if (!leaves[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "null leaves entry");
+    if (n > 0x7fffffffu / batch) return ctx->fail(STARK_ERR_INVALID_ARG, "batch x n exceeds 2^31 - 1 leaves: one level of the batch is one launch");
+    MerkleBatchDevExec X(ctx, p);
+    std::vector<size_t> lens; std::vector<fr_t*> base;
+    STARK_TRY(merkle_build_batch(X, arity, batch, labels, reinterpret_cast<const fr_t* const*>(leaves), n, pairs, reinterpret_cast<const fr_t* const*>(cp), lens, base));
+    for (size_t b = 0; b < batch; ++b) {
+        stark_tree* T = new stark_tree(); T->ref_.bind(ctx); T->ctx = ctx; T->p = p; T->arity = arity; T->label = labels[b]; T->shared = X.blocks;
+        for (size_t v = 0; v < lens.size(); ++v) { T->levels.push_back(base[v] + b * lens[v]); T->lens.push_back(lens[v]); T->owned.push_back(0); }
+        out[b] = T;
+    }
+    return STARK_OK;
+}
+// Request i = element index[i] of base[src[i]] into the i-th 32 bytes of out_host (host memory of any alignment: it is only the target of a copy): one upload of the four tables, one k_gather_rows launch, one download, one synchronisation.
+static int32_t gather_rows_sync(stark_ctx* ctx, const MerkleGatherList& G, void* out_host) {
+    const size_t k = G.size(), nb = G.base.size();
+    if (!k) return STARK_OK;
+    std::vector<uint64_t> h(nb + 2 * k + (k + 1) / 2);                   // [base | index | row | src (u32)]
+    for (size_t i = 0; i < nb; ++i) h[i] = (uint64_t)(uintptr_t)G.base[i];
+    for (size_t i = 0; i < k; ++i) { h[nb + i] = G.index[i]; h[nb + k + i] = (uint64_t)i; }
+    memcpy(h.data() + nb + 2 * k, G.src.data(), k * 4);
+    DevBuf d, o; STARK_HIP(ctx, o.alloc(ctx, k * sizeof(fr_t))); STARK_HIP(ctx, d.upload(ctx, h.data(), h.size() * 8));     // nothing can fail between the enqueued upload of h and a drain
+    const uint64_t* t = (const uint64_t*)d.p;
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)t, (const uint32_t*)(t + nb + 2 * k), t + nb, t + nb + k, (uint64_t)k, o.fr());
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return ctx->fail(STARK_ERR_HIP, std::string("k_gather_rows: ") + hipGetErrorString(e)); }   // h is the source of an enqueued upload
+    STARK_HIP(ctx, o.download_sync(out_host, k * sizeof(fr_t))); return STARK_OK;
+}
+struct MerkleOpenDevExec { stark_ctx* ctx; int32_t gather(const MerkleGatherList& G, fr_t* out_host) { return gather_rows_sync(ctx, G, out_host); } };
+// the trees of one call: all non-null, complete and of one context
+static int32_t same_ctx_trees(stark_tree* const* trees, size_t batch, stark_ctx** ctx) {
+    for (size_t b = 0; b < batch; ++b) if (!trees[b]) return STARK_ERR_INVALID_ARG;
+    stark_ctx* c = trees[0]->ctx;
+    for (size_t b = 1; b < batch; ++b) if (trees[b]->ctx != c) return c->fail(STARK_ERR_INVALID_ARG, "the trees of a batch must share one context");
+    for (size_t b = 0; b < batch; ++b) if (trees[b]->lens.back() != 1) return c->fail(STARK_ERR_INVALID_ARG, "partial (sharded) tree in a batch");
+    *ctx = c; return STARK_OK;
+}
+}  // namespace stark
+
+extern "C" {
+int32_t stark_merkle_build_batch_dev(stark_ctx_t* ctx, stark_params_t* p, size_t arity, size_t batch, const uint64_t* tree_labels, const uint64_t* const* leaves, size_t n, int32_t pairs,
+                                     const uint64_t* const* cp, stark_tree_t** out) {
+    if (!batch) return STARK_OK;
+    if (!out) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad merkle batch args") : STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (!ctx || !p || !tree_labels || !leaves || (pairs && !cp)) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad merkle batch args") : STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    const int32_t rc = merkle_build_batch_on(ctx, p, arity, batch, tree_labels, leaves, n, pairs, pairs ? cp : nullptr, out);
+    if (rc) for (size_t b = 0; b < batch; ++b) { delete out[b]; out[b] = nullptr; }
+    return rc;
+}
+int32_t stark_merkle_roots_batch(stark_tree_t* const* trees, size_t batch, uint64_t* roots) {
+    if (!batch) return STARK_OK;
+    if (!trees || !roots) return STARK_ERR_INVALID_ARG;
+    stark_ctx* ctx = nullptr; STARK_TRY(same_ctx_trees(trees, batch, &ctx));
+    STARK_TRY(ctx_enter(ctx));
+    MerkleGatherList G;
+    for (size_t b = 0; b < batch; ++b) G.level(trees[b]->levels.back(), std::vector<size_t>(1, 0));
+    return gather_rows_sync(ctx, G, roots);
+}
+int32_t stark_merkle_open_batch(stark_tree_t* const* trees, size_t batch, const size_t* idx, const size_t* idx_off, stark_proof_t** out) {
+    if (!batch) return STARK_OK;
+    if (!out) return STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (!trees || !idx || !idx_off) return STARK_ERR_INVALID_ARG;
+    stark_ctx* ctx = nullptr; STARK_TRY(same_ctx_trees(trees, batch, &ctx));
+    STARK_TRY(ctx_enter(ctx));
+    std::vector<MerkleTreeView> views(batch);
+    for (size_t b = 0; b < batch; ++b) views[b] = MerkleTreeView{trees[b]->arity, &trees[b]->lens, trees[b]->levels.data()};
+    MerkleOpenDevExec X{ctx}; std::vector<std::vector<uint8_t>> proofs;
+    const int32_t rc = merkle_open_batch(X, views.data(), batch, idx, idx_off, proofs);
+    if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, "open batch: idx_off not increasing, an empty index list or a leaf index out of range");
+    if (rc) return rc;
+    for (size_t b = 0; b < batch; ++b) { out[b] = new stark_proof(); out[b]->bytes = std::move(proofs[b]); }
+    return STARK_OK;
+}
+}  // extern "C"

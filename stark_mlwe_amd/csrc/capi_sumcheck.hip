@@ -477,6 +477,18 @@ int32_t stark_commitment_commit(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_
     STARK_TRY(merkle_build_on(ctx, ctx->stream, cp, 16, ds_tag, d.fr(), n, 0, nullptr, 1, 0, 0, 0, false, out));     // commit (:85-90); open = stark_merkle_open (:92-94)
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
 }
+// commit of `batch` DEVICE vectors of n leaves side by side (merkle_build_batch_on): stream-ordered, no host synchronisation
+int32_t stark_commitment_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* ds_tags, const uint64_t* const* leaves, size_t n, stark_tree_t** out) {
+    if (!batch) return STARK_OK;
+    if (!out) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad commitment batch args") : STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (!ctx || !ds_tags || !leaves) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad commitment batch args") : STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
+    const int32_t rc = merkle_build_batch_on(ctx, cp, 16, batch, ds_tags, leaves, n, 0, nullptr, out);
+    if (rc) for (size_t b = 0; b < batch; ++b) { delete out[b]; out[b] = nullptr; }
+    return rc;
+}
 // verify (:96-113): verify_many_ds with the static t = 17 parameters lifted to the dynamic form
 int32_t stark_commitment_verify(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* root4, const size_t* indices, size_t k, const uint64_t* values, const uint8_t* proof, size_t len, int32_t* accepted) {
     if (!ctx || !root4 || (!indices && k) || (!values && k) || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;

@@ -4,9 +4,11 @@
 //   stark_merkle_verify_many_ds      MerkleProver::verify_single        crates/merkle/src/lib.rs:587-722, 800-812
 //   stark_merkle_verify_pairs_ds     MerkleProver::verify_pairs         crates/merkle/src/lib.rs:723-773, 841-855
 //   stark_deep_fri_verify_batch      deep_fri_verify over many proofs: the plan of fri_verify_batch.hpp, one launch per (width, depth)
+//   stark_merkle_verify_many_ds_batch  verify_many_ds over many openings: the planner of merkle_batch.hpp, the same launches
 #include <cstring>
 #include "verify_dev.hpp"
 #include "fri_verify_batch.hpp"
+#include "merkle_batch.hpp"
 
 using namespace stark;
 
@@ -21,6 +23,18 @@ __global__ void __launch_bounds__(256) k_verify_batch_check(const fr_t* __restri
         const fr_t x = ldg(pool + chk[2 * j]), y = ldg(pool + chk[2 * j + 1]);
         for (int i = 0; i < 8; ++i) acc &= x.v[i] == y.v[i] ? 1 : 0;
     }
+    accepted[b] = acc;
+}
+
+// item b of a batch of Merkle openings is accepted iff its host flag is set and the root its walk computed, pool[pair[2b]], equals the root it
+// claims, pool[pair[2b + 1]] (MerkleVerifyPlanner; a rejected item carries the pair (0, 0) and flag 0); one thread per item
+__global__ void __launch_bounds__(256) k_merkle_root_check(const fr_t* __restrict__ pool, const uint32_t* __restrict__ pair, const int32_t* __restrict__ flag, size_t batch,
+                                                           int32_t* __restrict__ accepted) {
+    const size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    const fr_t x = ldg(pool + pair[2 * b]), y = ldg(pool + pair[2 * b + 1]);
+    int32_t acc = flag[b];
+    for (int i = 0; i < 8; ++i) acc &= x.v[i] == y.v[i] ? 1 : 0;
     accepted[b] = acc;
 }
 
@@ -88,6 +102,31 @@ int32_t run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, int32_t* acce
     STARK_HIP(ctx, hipStreamSynchronize(main_st));
     return STARK_OK;
 }
+// The device executor of merkle_verify_batch (merkle_batch.hpp): one upload of everything the device reads, the DS groups in depth order, the root
+// check, one download of the decisions and one synchronisation.
+struct MerkleVerifyDevExec {
+    stark_ctx* ctx;
+    int32_t run(const VerifyBatchPlan& V, const std::vector<uint32_t>& pair, int32_t* accepted) {
+        if (!V.batch) return STARK_OK;
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t o_hdr = 0, o_off = al(o_hdr + V.hdr.size() * 8), o_idx = al(o_off + V.off.size() * 4), o_pair = al(o_idx + V.idx.size() * 4),
+                     o_flag = al(o_pair + pair.size() * 4), o_pool = al(o_flag + V.batch * 4), o_acc = al(o_pool + V.pool.size() * sizeof(fr_t)), total = al(o_acc + V.batch * 4);
+        std::vector<uint8_t> h(o_pool + V.n_known * sizeof(fr_t));
+        auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) memcpy(h.data() + o, src, bytes); };
+        put(o_hdr, V.hdr.data(), V.hdr.size() * 8); put(o_off, V.off.data(), V.off.size() * 4); put(o_idx, V.idx.data(), V.idx.size() * 4);
+        put(o_pair, pair.data(), pair.size() * 4); put(o_flag, V.flag.data(), V.batch * 4); put(o_pool, V.pool.data(), V.n_known * sizeof(fr_t));
+        DevBuf d; STARK_HIP(ctx, d.alloc(ctx, total));
+        uint8_t* base = (uint8_t*)d.p; fr_t* pool = (fr_t*)(base + o_pool); int32_t* acc_dev = (int32_t*)(base + o_acc);
+        hipStream_t st = ctx->stream;
+        auto bail = [&](int32_t rc) { (void)hipStreamSynchronize(st); return rc; };      // h is the source of an enqueued upload
+        if (hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "merkle verify batch: upload"));
+        { const int32_t rc = verify_batch_groups_on(ctx, V, (const uint64_t*)(base + o_hdr), (const uint32_t*)(base + o_off), (const uint32_t*)(base + o_idx), pool, nullptr); if (rc) return bail(rc); }
+        hipLaunchKernelGGL(k_merkle_root_check, dim3((unsigned)((V.batch + 255) / 256)), dim3(256), 0, st, (const fr_t*)pool, (const uint32_t*)(base + o_pair), (const int32_t*)(base + o_flag), V.batch, acc_dev);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(accepted, acc_dev, V.batch * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "merkle verify batch: check"));
+        STARK_HIP(ctx, hipStreamSynchronize(st));
+        return STARK_OK;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -147,6 +186,22 @@ int32_t stark_merkle_verify_many_ds(stark_ctx_t* ctx, size_t cfg_arity, uint64_t
 int32_t stark_merkle_verify_pairs_ds(stark_ctx_t* ctx, size_t cfg_arity, uint64_t tree_label, const uint64_t* root4, const size_t* indices, size_t k, const uint64_t* f_vals, const uint64_t* cp_vals,
                                      const uint8_t* proof, size_t len, int32_t* accepted) {
     return merkle_verify(ctx, 1, cfg_arity, tree_label, root4, indices, k, f_vals, cp_vals, proof, len, accepted);
+}
+int32_t stark_merkle_verify_many_ds_batch(stark_ctx_t* ctx, size_t cfg_arity, size_t batch, const uint64_t* tree_labels, const uint64_t* roots, const size_t* indices, const size_t* idx_off,
+                                          const uint64_t* values, const uint8_t* const* proofs, const size_t* lens, int32_t* accepted) {
+    if (!batch) return STARK_OK;
+    if (!accepted) return STARK_ERR_INVALID_ARG;
+    memset(accepted, 0, batch * sizeof(int32_t));
+    if (!ctx || !tree_labels || !roots || !idx_off || !proofs || !lens) return STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) if ((!proofs[b] && lens[b]) || idx_off[b + 1] < idx_off[b]) return STARK_ERR_INVALID_ARG;
+    if ((!indices || !values) && idx_off[batch] != idx_off[0]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    if (host::width_for_arity(cfg_arity) < 0 || cfg_arity == 0) return ctx->fail(STARK_ERR_UNSUPPORTED, "unsupported Merkle arity; max supported = 128");   // MerkleChannelCfg::new (poseidon/src/lib.rs:164)
+    MerkleVerifyDevExec X{ctx};
+    int32_t rc = merkle_verify_batch(X, cfg_arity, batch, tree_labels, roots, indices, idx_off, values, proofs, lens, kVerifyBatchMaxSlots, accepted);
+    if (rc == -1) rc = ctx->fail(STARK_ERR_INVALID_ARG, "an opening of the batch needs more than 2^31 pool slots");
+    if (rc) memset(accepted, 0, batch * sizeof(int32_t));
+    return rc;
 }
 
 }  // extern "C"

@@ -121,11 +121,23 @@ namespace stark {
 int32_t ctx_alloc(stark_ctx* ctx, size_t bytes, void** out);   // pooled device memory (see stark_ctx::pool_free)
 void ctx_release(stark_ctx* ctx, void* p);
 }
+namespace stark {
+// The pooled blocks the trees of one batched build share (merkle_batch.hpp: level v of all trees is one block): every tree of the batch holds a
+// reference, and the blocks go back to the context's pool when the last of them is freed.  Each holding tree pins the context (its CtxRef outlives
+// this member), so the context is alive whenever the blocks are released.
+struct TreeBlocks {
+    stark_ctx* ctx; std::vector<void*> blocks;
+    explicit TreeBlocks(stark_ctx* c) : ctx(c) {}
+    TreeBlocks(const TreeBlocks&) = delete; TreeBlocks& operator=(const TreeBlocks&) = delete;
+    ~TreeBlocks() { for (void* p : blocks) ctx_release(ctx, p); }
+};
+}
 struct stark_tree {
     CtxRef ref_;
     stark_ctx* ctx = nullptr; stark_params* p = nullptr;
     size_t arity = 0; uint64_t label = 0;
     std::vector<stark::fr_t*> levels; std::vector<size_t> lens; std::vector<char> owned;
+    std::shared_ptr<stark::TreeBlocks> shared;          // a tree of a batched build: its levels are slices of these blocks (owned[i] = 0)
     ~stark_tree() { for (size_t i = 0; i < levels.size(); ++i) if (owned[i] && levels[i]) stark::ctx_release(ctx, levels[i]); }
 };
 struct stark_proof { std::vector<uint8_t> bytes; size_t size_estimate = 0; double ms[3] = {0, 0, 0}; };   // a finished proof (capi_fri.hip, capi_sumcheck.hip): bytes, size estimate, stage times

@@ -71,6 +71,13 @@ protected:
         if (!shaped) return false;
         chk_.push_back(top); chk_.push_back(root); return true;
     }
+    // many() against a claimed root that is an input of the plan: root_slot() hands out its slot after the walk's siblings, and only for a walk that is shaped
+    template <class Proof, class Sib, class Root>
+    bool many_rooted(size_t cfg_arity, const std::vector<size_t>& ix, const std::vector<uint32_t>& vals, const Proof& pr, uint64_t label, Sib sib, Root root_slot) {
+        const size_t before = chk_.size();
+        if (!many(cfg_arity, 0u, ix, vals, pr, label, sib)) return false;
+        chk_[before + 1] = root_slot(); return true;
+    }
     // Lays the jobs out in launch order — by depth, then width; each group's digests contiguous from pool slot `next` on — and fills the
     // plan's groups, hdr, off, idx and chk.  pos: computed digest -> pool slot, preset by the caller for what it computes itself (leaf
     // digests).  Returns the pool size.
@@ -125,11 +132,8 @@ private:
     uint32_t input(const fr_t& x) { pool_.push_back(x); return new_input(); }
     uint32_t leaf(const fr_t& f, const fr_t& s) { leaf_f_.push_back(f); leaf_s_.push_back(s); leaf_out_.push_back(computed(1)); return leaf_out_.back(); }
     bool many(size_t cfg_arity, const fr_t& root, const std::vector<size_t>& ix, const std::vector<uint32_t>& vals, const MerkleProofHost& pr, uint64_t label) {
-        // the root's slot is taken after the walk's siblings, and only by a walk that is shaped
         auto sib = [&](size_t level, size_t j) { return input(pr.siblings[level][j]); };
-        const size_t before = chk_.size();
-        if (!DsJobPlanner::many(cfg_arity, 0u, ix, vals, pr, label, sib)) return false;
-        chk_[before + 1] = input(root); return true;
+        return many_rooted(cfg_arity, ix, vals, pr, label, sib, [&]() { return input(root); });
     }
     bool open(const DeepFriProofHost& P, size_t layer, size_t ar, bool hashed, const std::vector<size_t>& ix, const std::vector<fr_t>& ff, const std::vector<fr_t>& ss,
               const MerkleProofHost& pr) {

@@ -20,6 +20,7 @@
 #include "ntt_batch_plan.hpp"
 #include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
 #include "mle_dev.hpp"
+#include "merkle_batch.hpp"
 
 using namespace stark;
 
@@ -646,3 +647,86 @@ int hc_mle_evaluate_batch(size_t B, const uint64_t* const* tables, size_t k, con
 }
 }  // extern "C"
 extern "C" int hc_mle_default_log_tile() { return kMleDefaultLogTile; }
+
+// ---- many Merkle trees in one pass (merkle_batch.hpp) through the host instantiation of the stream bodies -----------------------------------------
+struct MerkleHostExec {
+    HcParams* p; std::vector<std::vector<uint64_t>> mem; std::vector<uint64_t> labels; std::vector<const fr_t*> lv, cpv;
+    int32_t level_block(size_t n_fr, fr_t** out) { mem.emplace_back(4 * n_fr + 1, 0xA5A5A5A5A5A5A5A5ull); *out = (fr_t*)mem.back().data(); return 0; }   // a block that held something before
+    int32_t tables(const uint64_t* l, const fr_t* const* leaves, const fr_t* const* cp, size_t B, const uint64_t** lx, const fr_t* const** vx, const fr_t* const** cx) {
+        labels.assign(l, l + B); lv.assign(leaves, leaves + B); if (cp) cpv.assign(cp, cp + B);
+        *lx = labels.data(); *vx = lv.data(); *cx = cp ? cpv.data() : nullptr; return 0;
+    }
+    int32_t copy_rows(const fr_t* const* src, size_t n, size_t B, fr_t* dst) { for (size_t b = 0; b < B; ++b) for (size_t i = 0; i < n; ++i) dst[b * n + i] = src[b][i]; return 0; }
+    template <class DS> int32_t ds(const DS& D, fr_t* out) {
+        std::vector<fr_t> st(p->dev.t);
+        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, p->dev, D, k); }
+        return 0;
+    }
+    int32_t pair_level(const DsBatchPairPtrStream& D, fr_t* out) { return ds(D, out); }
+    int32_t ds_level(const DsBatchStream& D, fr_t* out) { return ds(D, out); }
+};
+struct MerkleOpenHostExec { int32_t gather(const MerkleGatherList& G, fr_t* out) { for (size_t i = 0; i < G.size(); ++i) out[i] = G.base[G.src[i]][G.index[i]]; return 0; } };
+struct MerkleVerifyHostExec {
+    FriHostExec::ParamCache& mp;
+    int32_t run(const VerifyBatchPlan& V0, const std::vector<uint32_t>& pair, int32_t* accepted) {
+        VerifyBatchPlan V = V0;
+        for (const VerifyBatchPlan::Group& G : V.groups) {
+            HcParams* P = mp.params((size_t)G.t - 1); std::vector<fr_t> st(P->dev.t);
+            const DsGatherStream D{V.hdr.data() + 4 * G.job0, V.off.data() + G.job0, V.idx.data(), V.pool.data(), G.n, G.max_children};
+            for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; V.pool[G.out0 + k] = hash_ds_body(s, P->dev, D, k); }
+        }
+        for (size_t b = 0; b < V.batch; ++b) accepted[b] = V.flag[b] & (fr_eq(V.pool[pair[2 * b]], V.pool[pair[2 * b + 1]]) ? 1 : 0);
+        return 0;
+    }
+};
+static std::vector<size_t> total_lens(const std::vector<size_t>& lens, size_t B) { std::vector<size_t> o(lens.size() + 1, 0); for (size_t v = 0; v < lens.size(); ++v) o[v + 1] = o[v] + B * lens[v]; return o; }
+extern "C" {
+// MerkleTree::new / new_pairs of B trees of n leaves through the batch driver.  leaves / cp: B host columns (cp null iff !pairs; a null entry = zeros).
+// out (cap_fr elements) receives the level blocks back to back: level v at element offset sum_{u<v} B lens[u], tree b's slice at b lens[v] inside it.
+// Returns the number of levels (lens_out: their lengths, at most 64), or -1 on a refused shape.
+int hc_merkle_build_batch(void* params, size_t arity, size_t B, const uint64_t* labels, const uint64_t* const* leaves, size_t n, int pairs, const uint64_t* const* cp,
+                          uint64_t* out, size_t cap_fr, size_t* lens_out) {
+    HcParams* P = (HcParams*)params;
+    if (!B || !n || !arity || host::width_for_arity(arity) != P->dev.t || (arity == 1 && n > 1) || (pairs && !cp)) return -1;
+    std::vector<std::vector<fr_t>> col(B, std::vector<fr_t>(n)), cc(B); std::vector<const fr_t*> lp(B), cpp(B, nullptr);
+    for (size_t b = 0; b < B; ++b) {
+        for (size_t i = 0; i < n; ++i) col[b][i] = ld4(leaves[b] + 4 * i);
+        lp[b] = col[b].data();
+        if (pairs && cp[b]) { cc[b].resize(n); for (size_t i = 0; i < n; ++i) cc[b][i] = ld4(cp[b] + 4 * i); cpp[b] = cc[b].data(); }
+    }
+    MerkleHostExec X{P, {}, {}, {}, {}}; std::vector<size_t> lens; std::vector<fr_t*> base;
+    if (merkle_build_batch(X, arity, B, labels, lp.data(), n, pairs, pairs ? cpp.data() : nullptr, lens, base)) return -1;
+    const std::vector<size_t> at = total_lens(lens, B);
+    if (lens.size() > 64 || at.back() > cap_fr) return -1;
+    for (size_t v = 0; v < lens.size(); ++v) { lens_out[v] = lens[v]; for (size_t i = 0; i < B * lens[v]; ++i) st4(out + 4 * (at[v] + i), base[v][i]); }
+    return (int)lens.size();
+}
+// open_union_of_paths of B trees through the batch driver.  Tree b: arity[b], nlev[b] levels; the levels of all trees are listed tree by tree in
+// levels / lens.  Tree b opens idx[idx_off[b] .. idx_off[b + 1]).  The proofs are written back to back into buf when cap suffices, their lengths
+// into out_lens; returns the total length, or -1 on refused arguments.
+long hc_merkle_open_batch(size_t B, const size_t* arity, const size_t* nlev, const uint64_t* const* levels, const size_t* lens, const size_t* idx, const size_t* idx_off,
+                          uint8_t* buf, size_t cap, size_t* out_lens) {
+    std::vector<std::vector<std::vector<fr_t>>> lv(B); std::vector<std::vector<const fr_t*>> lp(B); std::vector<std::vector<size_t>> ll(B); std::vector<MerkleTreeView> views(B);
+    for (size_t b = 0, q = 0; b < B; ++b) {
+        for (size_t v = 0; v < nlev[b]; ++v, ++q) {
+            lv[b].emplace_back(lens[q]); for (size_t i = 0; i < lens[q]; ++i) lv[b][v][i] = ld4(levels[q] + 4 * i);
+            ll[b].push_back(lens[q]);
+        }
+        for (auto& l : lv[b]) lp[b].push_back(l.data());
+        views[b] = MerkleTreeView{arity[b], &ll[b], lp[b].data()};
+    }
+    MerkleOpenHostExec X; std::vector<std::vector<uint8_t>> pr;
+    if (merkle_open_batch(X, views.data(), B, idx, idx_off, pr)) return -1;
+    size_t tot = 0; for (size_t b = 0; b < B; ++b) { out_lens[b] = pr[b].size(); tot += pr[b].size(); }
+    if (buf && cap >= tot) { size_t o = 0; for (auto& p : pr) { memcpy(buf + o, p.data(), p.size()); o += p.size(); } }
+    return (long)tot;
+}
+// verify_many_ds of `batch` openings through the batch planner, run step by step as the device runs it (max_slots: the pool slots of one plan;
+// 0 = the library's 2^25); roots and values go to the driver as they come, at any 8-byte alignment.  accepted[i] = 1 / 0.  Returns 0, or -1 on an unsupported cfg_arity.
+int hc_merkle_verify_batch(size_t cfg_arity, size_t batch, const uint64_t* labels, const uint64_t* roots, const size_t* indices, const size_t* idx_off, const uint64_t* values,
+                           const uint8_t* const* proofs, const size_t* lens, size_t max_slots, int32_t* accepted) {
+    if (host::width_for_arity(cfg_arity) < 0 || cfg_arity == 0) return -1;
+    MerkleVerifyHostExec X{FriHostExec::cache()};
+    return merkle_verify_batch(X, cfg_arity, batch, labels, roots, indices, idx_off, values, proofs, lens, max_slots ? max_slots : (size_t)1 << 25, accepted);
+}
+}  // extern "C"

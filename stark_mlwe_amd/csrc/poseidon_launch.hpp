@@ -11,11 +11,12 @@ void poseidon_set_attrs();                                           // per-devi
 
 // One launch of hash_with_ds_dynamic over the hashes of a DS stream on `st`, in the form the selector picks for a Merkle level of D.n_out nodes
 // (DsStream: a Merkle level / pair-leaf level; DsGatherStream: one (width, depth) step of the batch verifiers; DsBatchStream: one level of B trees;
-// DsBatchPairStream: the pair leaves of B unhashed FRI layers).
+// DsBatchPairStream: the pair leaves of B unhashed FRI layers; DsBatchPairPtrStream: the pair leaves of B trees read through pointer tables).
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out);
+int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out);
 // DS hashes with scattered positions (the verifier's union-of-paths levels): hash k = H([arity, level, positions[k], label] || chunk children)
 int32_t hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
                           const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out);
@@ -23,6 +24,10 @@ int32_t hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arit
 int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h);
 int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t arity, uint64_t label, const fr_t* leaves, size_t n, int pairs, const fr_t* cp, size_t cp_div,
                         uint64_t first_pos, uint32_t level0, size_t stop_at_len, bool adopt, stark_tree** out);
+// MerkleTree::new / new_pairs of `batch` trees of one shape on the context's stream (merkle_batch.hpp): leaves / cp are HOST arrays of DEVICE pointers
+// (cp: nullptr iff !pairs; a null entry = zeros).  Stream-ordered, no host synchronisation.  out: `batch` handles, all null on any error.
+int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, size_t batch, const uint64_t* labels, const uint64_t* const* leaves, size_t n, int pairs,
+                              const uint64_t* const* cp, stark_tree** out);
 
 int32_t tr_hash_dev(stark_ctx* ctx, const char* tag, const fr_t* fields_dev, size_t k, size_t n, fr_t* out_dev);
 int32_t tr_hash_columns4_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const cols[4], size_t n0, fr_t* out4_dev);

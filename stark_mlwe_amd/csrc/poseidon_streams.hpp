@@ -107,6 +107,30 @@ struct DsBatchPairStream {
     }
 };
 
+// The pair leaves of B same-shape trees whose columns live wherever the caller put them (the batched Merkle build, merkle_batch.hpp):
+// DsBatchPairStream read through two device arrays of per-tree pointers.  Hash k belongs to tree k / n and is leaf j = k % n of it:
+//   hash k = hash_with_ds_dynamic([arity, 2^32 - 1, j, labels[k / n]] || f[k / n][j], cp[k / n] ? cp[k / n][j] : 0 || 1), eager sponge, cap 0
+// A null cp[b] makes every second child of tree b zero (MerkleTree::new_pairs over a zero column, fri.rs:266).
+struct DsBatchPairPtrStream {
+    fr_t arity_f, level_f; const uint64_t* labels; size_t n, n_out; const fr_t* const* f; const fr_t* const* cp;
+    static inline DsBatchPairPtrStream make(size_t arity, const uint64_t* labels, const fr_t* const* f, const fr_t* const* cp, size_t n, size_t trees) {
+        DsBatchPairPtrStream D;
+        D.arity_f = fr_from_u64<PF>(arity); D.level_f = fr_from_u64<PF>(0xFFFFFFFFu); D.labels = labels; D.n = n; D.n_out = n * trees; D.f = f; D.cp = cp;
+        return D;
+    }
+    FR_HD uint64_t position(size_t k) const { return k % n; }
+    FR_HD size_t total(size_t) const { return 7; }
+    FR_HD size_t max_total() const { return 7; }
+    FR_HD fr_t elem(size_t k, size_t q) const {
+        if (q < 4) return q == 0 ? arity_f : (q == 1 ? level_f : (q == 2 ? fr_from_u64<PF>(position(k)) : fr_from_u64<PF>(labels[k / n])));
+        if (q == 6) return fr_one<PF>();
+        const size_t b = k / n, j = k % n;
+        if (q == 4) return ldg(f[b] + j);
+        const fr_t* c = cp[b];
+        return c ? ldg(c + j) : fr_zero<PF>();
+    }
+};
+
 // B streaming transcripts (transcript/src/lib.rs:79-101, lazy duplex) advanced in one launch, one workgroup per active instance
 // (the batched sum-check provers, sumcheck_batch.hpp).  Instance b keeps state[17 b .. 17 b + 16] and its rate cursor pos[b] in
 // device memory between launches; active a runs instance inst[a] (inst == nullptr: inst0 + a).  Active a runs nseg segments: segment
