@@ -270,7 +270,8 @@ int32_t stark_proof_free(stark_proof_t* p);
  * deep_fri_verify (fri.rs:643-762) over the canonical proof bytes stark_proof_bytes returns; *accepted = 1 / 0 (the reference
  * returns bool; bytes that do not decode are rejected, inputs on which the reference would panic are rejected).  seed_z is
  * DeepFriParams.seed_z, carried for signature parity (the reference's verifier does not read it).  Host index logic in the
- * library, every hash (leaf pairs, DS nodes) batched onto the GPU kernels of the prover. */
+ * library, every hash (leaf pairs, DS nodes) batched onto the GPU kernels of the prover: a single call is the batch call with one proof
+ * (one upload, one synchronisation).  Every single verifier of this header leaves *accepted 0 on a reject and on an error. */
 int32_t stark_deep_fri_verify(stark_ctx_t* ctx, const uint8_t* proof, size_t len, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, int32_t* accepted);
 /* deep_fri_verify (fri.rs:643-762) over `batch` canonical proofs at once; accepted[i] == what stark_deep_fri_verify answers for proofs[i]
  * alone, for every input (honest, tampered, truncated, empty, other n0).  The proofs share one schedule and r; each proof's n0 is read from

@@ -230,8 +230,8 @@ static int32_t launch_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, co
         break;
     case PoseidonForm::WavePair:
         if constexpr (std::is_same<DS, DsStream>::value) {
-            // a node level whose every node has 16 children (no ragged last node, contiguous positions): the fixed two-permutation kernel
-            if (t == 17 && ctx->opt.merkle_node16_pair && D.mode == 0 && D.arity == 16 && !D.pos_list && D.n_in == 16 * D.n_out) {
+            // a node level whose every node has 16 children (no ragged last node): the fixed two-permutation kernel
+            if (t == 17 && ctx->opt.merkle_node16_pair && D.mode == 0 && D.arity == 16 && D.n_in == 16 * D.n_out) {
                 hipLaunchKernelGGL(k_node16_pair, dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D.arity_f, D.level_f, D.label_f, D.pos0, D.in0, D.n_out, out);
                 break;
             }
@@ -255,10 +255,6 @@ int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
-int32_t stark::hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
-                                 const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out) {
-    return hash_ds_on(ctx, ctx->stream, p, DsStream::make(mode, arity, level, 0, label, in0, in1, mode == 1 ? n_hashes : n_hashes * chunk, 1, positions_dev, mode == 1 ? 0 : chunk), out);
-}
 // The full 160 KiB of LDS per workgroup for the kernels that stage through it: every instantiation the launchers of this file can reach (a DS
 // kernel: once per stream type hash_ds_on takes).  Not listed: the one-wave and wide kernels (k_*_coop, k_hash_ds_wave, k_tr_stream, k_tr_batch), whose
 // coop_lds_bytes / wave_lds_bytes stay below the 64 KiB a kernel may use without the attribute.

@@ -4,10 +4,13 @@
 //   * MerkleCommitment::commit (commitment/src/lib.rs:85-90: arity 16, parameters "POSEIDON-T17-X5-SEED") of the witness and of every
 //     shrinking folded layer = the level-batched Merkle kernels of the FRI path (merkle_build_on);
 //   * round coefficients c0 = sum a_j, c1 = sum (b_j - a_j) (:406-416) and the fold (1-r) a + r b (:456-462) = streaming kernels;
-//   * the Fiat-Shamir channel (:7-117) = DEVICE-RESIDENT transcripts: the verifiers and the ABI's transcript object queue absorbs on the
-//     host and run them as ONE launch when a challenge is drawn (DevTranscript); the provers lay out what every instance absorbs as pool
-//     indices and advance all transcripts of a batch per launch (TrBatchStream), so prove_plain has no host round trip in its rounds.
-// Every prove — one witness or many — runs the batched round loops of sumcheck_batch.hpp over the device executor below (ScDevExec).
+//   * the Fiat-Shamir channel (:7-117) = DEVICE-RESIDENT transcripts:
+//     the ABI's transcript object queues absorbs on the host and runs them as ONE launch when a challenge is drawn (DevTranscript); the
+//     provers and verifiers lay out what every instance absorbs as pool indices and advance all transcripts of a batch per launch
+//     (TrBatchStream), so neither has a host round trip in its rounds.
+// Every prove — one witness or many — runs the batched round loops of sumcheck_batch.hpp over the device executor below (ScDevExec); every
+// verify — one proof or many — is a plan of sumcheck_verify_batch.hpp run by run_sc_verify_batch, and stark_commitment_verify a Merkle plan
+// of one item through capi_verify.hip's runner (verify_dev.hpp).
 // Proof bytes = bincode 1.x layout of the reference's serde structs ProofPlain / ProofMF (:925-979), what its bench measures.
 #include <memory>
 #include "verify_dev.hpp"
@@ -117,8 +120,6 @@ struct DevTranscript {
         pending.push_back(host::h_tag("FSv1-ABSORB-BYTES"));
         for (size_t o = 0; o < n; o += 31) pending.push_back(host::h_from_le_bytes_mod_order(b + o, std::min<size_t>(31, n - o)));
     }
-    void absorb_str(const char* s) { absorb_bytes((const uint8_t*)s, strlen(s)); }
-    void absorb_u64(uint64_t x) { uint8_t b[8]; for (int j = 0; j < 8; ++j) b[j] = (uint8_t)(x >> (8 * j)); absorb_bytes(b, 8); }
     int32_t run(bool finish, fr_t* result) {
         DevBuf f; const size_t n = pending.size();
         if (n) STARK_HIP(ctx, f.upload(ctx, pending.data(), n * sizeof(fr_t)));
@@ -133,32 +134,6 @@ struct DevTranscript {
     }
 };
 
-struct BinR {
-    ByteReader R; explicit BinR(const uint8_t* p, size_t n) : R(p, n) {}
-    fr_t fb() { if (R.u64() != 32) R.ok = false; return R.fr(); }
-    bool idxs(std::vector<size_t>& v) { size_t k = R.len(8); v.resize(k); for (size_t i = 0; i < k; ++i) v[i] = (size_t)R.u64(); return R.ok; }
-    bool fvec(std::vector<fr_t>& v) { size_t k = R.len(40); v.resize(k); for (size_t i = 0; i < k && R.ok; ++i) v[i] = fb(); return R.ok; }
-    bool mproof(MerkleProofHost& p) {
-        p.arity = (size_t)R.u64();
-        size_t g = R.len(8); p.group_sizes.assign(g, {}); for (size_t i = 0; i < g && R.ok; ++i) { size_t k = R.len(1); p.group_sizes[i].resize(k); for (size_t j = 0; j < k; ++j) p.group_sizes[i][j] = R.u8(); }
-        if (!idxs(p.indices)) return false;
-        size_t a = R.len(8); p.siblings.assign(a, {}); for (size_t i = 0; i < a && R.ok; ++i) fvec(p.siblings[i]);
-        return R.ok;
-    }
-};
-
-static void send_digest(DevTranscript& T, const char* label, const fr_t& d) { T.absorb_str(sc_lab::digest); T.absorb_str(label); T.absorb_field(d); }   // :22-26
-static void send_opening(DevTranscript& T, const std::vector<size_t>& idx, const std::vector<fr_t>& vals, const MerkleProofHost& pr) {                  // :32-62
-    T.absorb_str(sc_lab::open);
-    for (size_t i : idx) T.absorb_u64((uint64_t)i);
-    for (auto& v : vals) T.absorb_field(v);
-    T.absorb_str(sc_lab::arity); T.absorb_u64((uint64_t)pr.arity);
-    T.absorb_str(sc_lab::group_sizes);
-    for (auto& l : pr.group_sizes) { T.absorb_u64((uint64_t)l.size()); for (uint8_t sz : l) T.absorb_bytes(&sz, 1); }
-    T.absorb_str(sc_lab::siblings);
-    for (auto& l : pr.siblings) { T.absorb_u64((uint64_t)l.size()); for (auto& s : l) T.absorb_field(s); }
-}
-
 // MerkleCommitment's parameters (commitment/src/lib.rs:48-51), cached per context next to the other parameter sets (key -17)
 static int32_t commit_params(stark_ctx* ctx, stark_params** out) {
     auto it = ctx->merkle_params.find(-17);
@@ -171,12 +146,6 @@ static int32_t fold(stark_ctx* ctx, const fr_t* layer, size_t len, const fr_t& r
     const uint64_t np = len / 2;
     hipLaunchKernelGGL(k_sc_fold, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, layer, np, r, next);
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-}
-// mf_round_challenge_from_root (:592-598): a fresh transcript per round
-static int32_t mf_round_challenge(stark_ctx* ctx, size_t round_idx, const fr_t& prev_root, fr_t* r) {
-    DevTranscript T(ctx); STARK_TRY(T.init((const uint8_t*)sc_lab::mf_round_chal, strlen(sc_lab::mf_round_chal)));
-    T.absorb_str(sc_lab::mf_r); T.absorb_u64((uint64_t)round_idx); T.absorb_field(prev_root);
-    return T.challenge((const uint8_t*)sc_lab::r_i, strlen(sc_lab::r_i), r);
 }
 // The device executor of the batched drivers (sumcheck_batch.hpp): every operation is one launch (or a few, for more than 65535 layers) on
 // the context's stream; uploads are staged until the next download synchronises.
@@ -234,61 +203,6 @@ static int32_t prove_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t B, const
     return STARK_OK;
 }
 
-// verify_plain (:1080-1128).  A failed check answers `false` (inside the reference it is a failed assert_eq!, i.e. a panic).
-static int32_t verify_plain_impl(stark_ctx* ctx, const uint8_t* bytes, size_t len, bool& ok) {
-    ok = false;
-    BinR D(bytes, len); const fr_t root = D.fb(); const size_t nr = D.R.len(80);
-    std::vector<std::pair<fr_t, fr_t>> rounds(nr); for (size_t i = 0; i < nr && D.R.ok; ++i) { rounds[i].first = D.fb(); rounds[i].second = D.fb(); }
-    if (D.R.u8() != 0) D.R.ok = false;
-    const fr_t final_eval = D.fb();
-    if (!D.R.ok || D.R.left()) return STARK_OK;
-    if (rounds.empty()) return STARK_OK;                                                     // :1100-1102
-    DevTranscript T(ctx); STARK_TRY(T.init((const uint8_t*)sc_lab::plain, strlen(sc_lab::plain)));
-    send_digest(T, sc_lab::root, root);
-    fr_t running = host::h_add(host::h_add(rounds[0].first, rounds[0].first), rounds[0].second);
-    T.absorb_str(sc_lab::claim); T.absorb_field(running);
-    for (size_t i = 0; i < rounds.size(); ++i) {
-        const fr_t& c0 = rounds[i].first; const fr_t& c1 = rounds[i].second;
-        T.absorb_str(sc_lab::round); T.absorb_u64((uint64_t)i); T.absorb_str(sc_lab::c0); T.absorb_field(c0); T.absorb_str(sc_lab::c1); T.absorb_field(c1);
-        if (!fr_eq(host::h_add(host::h_add(c0, c0), c1), running)) return STARK_OK;          // :511-512
-        fr_t r; { auto lb = lab_idx(sc_lab::r, i); STARK_TRY(T.challenge(lb.data(), lb.size(), &r)); }
-        running = host::h_add(c0, host::h_mul(c1, r));
-    }
-    ok = fr_eq(final_eval, running); return STARK_OK;                                        // :528
-}
-// verify_mf (:1176-1240)
-static int32_t verify_mf_impl(stark_ctx* ctx, uint64_t tree_label, const uint8_t* bytes, size_t len, bool& ok) {
-    ok = false;
-    BinR D(bytes, len); const fr_t initial_root = D.fb(); const size_t nr = D.R.len(120);
-    std::vector<RoundMFHost> rounds(nr);
-    for (size_t i = 0; i < nr && D.R.ok; ++i) { RoundMFHost& R = rounds[i]; R.c0 = D.fb(); R.c1 = D.fb(); R.next_root = D.fb(); D.idxs(R.cur_indices); D.fvec(R.cur_values); D.mproof(R.cur_proof); D.idxs(R.next_indices); D.fvec(R.next_values); D.mproof(R.next_proof); }
-    const fr_t final_eval = D.fb();
-    if (!D.R.ok || D.R.left()) return STARK_OK;
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
-    GpuVerifyHasher H(ctx, cp);      // MerkleCommitment's parameters
-    bool have = false; fr_t running = host::h_zero(), prev_root = initial_root;
-    for (size_t i = 0; i < rounds.size(); ++i) {
-        const RoundMFHost& R = rounds[i];
-        const fr_t twoc = host::h_add(host::h_add(R.c0, R.c0), R.c1);
-        if (have && !fr_eq(twoc, running)) return STARK_OK;                                  // start_round (:803-804)
-        fr_t r; STARK_TRY(mf_round_challenge(ctx, i, prev_root, &r));                        // derive_round_challenge (:807-810)
-        bool good = false;                                                                   // verify_fold_openings (:821-869)
-        STARK_TRY(verify_many_ds_host(H, 16, prev_root, R.cur_indices, R.cur_values, R.cur_proof, tree_label, good)); if (!good) return STARK_OK;
-        STARK_TRY(verify_many_ds_host(H, 16, R.next_root, R.next_indices, R.next_values, R.next_proof, tree_label, good)); if (!good) return STARK_OK;
-        if (R.cur_indices.size() != R.cur_values.size() || R.next_indices.size() != R.next_values.size()) return STARK_OK;
-        std::map<size_t, std::pair<std::pair<bool, fr_t>, std::pair<bool, fr_t>>> pairs;
-        for (size_t t = 0; t < R.cur_indices.size(); ++t) { const size_t ix = R.cur_indices[t]; auto& e = pairs[ix / 2]; if (ix % 2 == 0) e.first = {true, R.cur_values[t]}; else e.second = {true, R.cur_values[t]}; }
-        for (size_t t = 0; t < R.next_indices.size(); ++t) {
-            auto it = pairs.find(R.next_indices[t]);
-            if (it == pairs.end() || !it->second.first.first || !it->second.second.first) return STARK_OK;
-            const fr_t a = it->second.first.second, b = it->second.second.second;
-            if (!fr_eq(host::h_add(a, host::h_mul(r, host::h_sub(b, a))), R.next_values[t])) return STARK_OK;
-        }
-        running = host::h_add(R.c0, host::h_mul(R.c1, r)); have = true; prev_root = R.next_root;
-    }
-    ok = !have || fr_eq(final_eval, running); return STARK_OK;                               // :1237-1238
-}
-
 // Runs one plan of the batched verifiers: one upload (the proofs' bytes and the plan's index arrays), the decode, the transcript streams,
 // the DS groups in depth order, the checks, one download of the flags and one synchronisation.
 static int32_t run_sc_verify_batch(stark_ctx* ctx, const ScVerifyPlan& V, int32_t* accepted) {
@@ -332,7 +246,7 @@ static int32_t run_sc_verify_batch(stark_ctx* ctx, const ScVerifyPlan& V, int32_
     STARK_HIP(ctx, hipStreamSynchronize(st));
     return STARK_OK;
 }
-// verify_plain (mf = 0) / verify_mf (mf = 1) of a batch, cut into plans of at most the context's "sumcheck_verify_batch_max_slots" pool slots
+// verify_plain (mf = 0) / verify_mf (mf = 1) of a batch (the single entry points: B = 1), cut into plans of at most the context's "sumcheck_verify_batch_max_slots" pool slots
 static int32_t verify_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* tree_labels, int32_t* accepted) {
     size_t b0 = 0;
     while (b0 < batch) {
@@ -492,14 +406,10 @@ int32_t stark_commitment_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const 
 // verify (:96-113): verify_many_ds with the static t = 17 parameters lifted to the dynamic form
 int32_t stark_commitment_verify(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* root4, const size_t* indices, size_t k, const uint64_t* values, const uint8_t* proof, size_t len, int32_t* accepted) {
     if (!ctx || !root4 || (!indices && k) || (!values && k) || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
     *accepted = 0;
-    ByteReader R(proof, len); MerkleProofHost pr; if (!dec_mproof(R, pr) || R.left()) return STARK_OK;
+    STARK_TRY(ctx_enter(ctx));
     stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
-    std::vector<size_t> ix(indices, indices + k); std::vector<fr_t> v(k); for (size_t i = 0; i < k; ++i) v[i] = load_fr(values + 4 * i);
-    GpuVerifyHasher H(ctx, cp); bool ok = false;      // MerkleCommitment's parameters
-    STARK_TRY(verify_many_ds_host(H, 16, load_fr(root4), ix, v, pr, ds_tag, ok));
-    *accepted = ok ? 1 : 0; return STARK_OK;
+    return merkle_verify_one(ctx, cp, 16, ds_tag, root4, indices, k, values, nullptr, proof, len, accepted);      // MerkleCommitment's parameters
 }
 
 // Mle::evaluate(r) (channel/src/lib.rs:279-295): k folds layer[i] = (1 - r_j) layer[2i] + r_j layer[2i+1]; table of 2^k elements (host).
@@ -565,13 +475,15 @@ int32_t stark_sumcheck_prove_mf_batch_dev(stark_ctx_t* ctx, size_t batch, const 
 }
 int32_t stark_sumcheck_verify_plain(stark_ctx_t* ctx, size_t k, uint64_t tree_label, const uint8_t* proof, size_t len, int32_t* accepted) {
     if (!ctx || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
+    *accepted = 0;
     STARK_TRY(ctx_enter(ctx)); (void)k; (void)tree_label;     // verify_plain reads neither vk.k (it walks proof.rounds) nor the tree label
-    bool ok = false; STARK_TRY(verify_plain_impl(ctx, proof, len, ok)); *accepted = ok ? 1 : 0; return STARK_OK;
+    return verify_sumcheck_batch_impl(ctx, 0, 1, &proof, &len, nullptr, accepted);
 }
 int32_t stark_sumcheck_verify_mf(stark_ctx_t* ctx, size_t k, uint64_t tree_label, size_t queries_per_round, const uint8_t* proof, size_t len, int32_t* accepted) {
     if (!ctx || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
+    *accepted = 0;
     STARK_TRY(ctx_enter(ctx)); (void)k; (void)queries_per_round;
-    bool ok = false; STARK_TRY(verify_mf_impl(ctx, tree_label, proof, len, ok)); *accepted = ok ? 1 : 0; return STARK_OK;
+    return verify_sumcheck_batch_impl(ctx, 1, 1, &proof, &len, &tree_label, accepted);
 }
 // tree_labels: required by verify_mf; read by neither verify_plain nor its batch (may be NULL there).  k and queries_per_round are read by no verifier.
 static int32_t verify_batch(stark_ctx_t* ctx, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* tree_labels, int32_t* accepted) {

@@ -1,4 +1,4 @@
-// stark_mlwe_amd/csrc/fri_verify.hpp — the verifier side of the path as host logic over abstract batch hashers (product code):
+// stark_mlwe_amd/csrc/fri_verify.hpp — the verifier side of the path as host logic (product code): the proof decoding and the index walks of
 //   deep_fri_verify                 crates/deep_ali/src/fri.rs:643-762
 //   verify_many_ds / verify_pairs_ds crates/merkle/src/lib.rs:587-722, 723-773  (MerkleProver::verify_single / verify_pairs, :800-855)
 // over the canonical proof encoding of DESIGN.md §7 (the reference's DeepFriProof has no serialisation of its own).
@@ -9,8 +9,9 @@
 // s_i == f_parent[b], fri.rs:168-176) — so accept/reject agrees with `deep_fri_verify` on every input the reference answers.
 // Where the reference would PANIC on malformed input (index out of bounds on an empty query list, division by a zero arity,
 // a schedule that does not divide n0) this code answers `false`.
-// All hashing goes through `VerifyHasher`, which the library implements with its batched GPU kernels (capi_verify.hip) and the
-// CPU diagnostic build with the host instantiation of the same kernel bodies (hostcheck.cpp).  Host-only C++.
+// Nothing here hashes: the walks run over values of any type, and the planners of fri_verify_batch.hpp and merkle_batch.hpp run them over
+// pool slots, recording every hash as a job of a plan.  A single proof is a plan of one item; the library runs a plan with its batched GPU
+// kernels (capi_verify.hip) and the CPU diagnostic build with the host instantiation of the same kernel bodies (hostcheck.cpp).  Host-only C++.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -22,16 +23,6 @@
 #include "fri_plan.hpp"
 
 namespace stark {
-
-struct VerifyHasher {
-    virtual ~VerifyHasher() {}
-    // out[i] = hash_leaf_pair(f[i], s[i])                                                        fri.rs:38-44
-    virtual int32_t leaf_pairs(const fr_t* f, const fr_t* s, size_t n, fr_t* out) = 0;
-    // out[k] = hash_with_ds_dynamic([arity, level, positions[k], label], children[k*chunk .. (k+1)*chunk), params(arity))   merkle/src/lib.rs:683-689
-    virtual int32_t ds_nodes(size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions, const fr_t* children, size_t n, fr_t* out) = 0;
-    // out[k] = hash_with_ds_dynamic([arity, 2^32-1, positions[k], label], [f[k], cp[k]], params(arity))                      merkle/src/lib.rs:757-766
-    virtual int32_t ds_pair_leaves(size_t arity, uint64_t label, const uint64_t* positions, const fr_t* f, const fr_t* cp, size_t n, fr_t* out) = 0;
-};
 
 // ---- decoding (bounds-checked: the bytes are untrusted) ---------------------------------------------------------------
 struct ByteReader {
@@ -85,14 +76,11 @@ inline bool decode_proof(const uint8_t* bytes, size_t len, DeepFriProofHost& P) 
     return R.ok && R.left() == 0;
 }
 
-#define STARK_VERIFY_TRY(expr) do { int32_t rc__ = (expr); if (rc__) return rc__; } while (0)
-
 inline bool ok_width_for(size_t arity) { return arity >= 1 && arity <= 128; }      // the dynamic params ARE poseidon_params_for_arity(arity) (MerkleChannelCfg::new), so the t / arity guard (:605-614) reduces to the arity range
 
 // ---- the index walks, over values of any type -------------------------------------------------------------------------------
-// Every reject decision of verify_many_ds / verify_pairs_ds / deep_fri_verify is written once, here, over values of type V: field
-// elements for the single-proof path below (it hashes each level as the walk reaches it), pool slots for the batch planner
-// (fri_verify_batch.hpp: it records each level's hashes as jobs and compares the roots on the device).
+// Every reject decision of verify_many_ds / verify_pairs_ds / deep_fri_verify is written once, here, over values of type V: the planners
+// instantiate them with pool slots (fri_verify_batch.hpp: each level's hashes become jobs, the roots are compared where the plan runs).
 
 // The level walk of verify_many_ds (merkle/src/lib.rs:587-722) with cfg = MerkleChannelCfg::new(cfg_arity): the Poseidon parameters belong
 // to the VERIFIER's arity (fri.rs:676-678), the hashing arity comes from the proof (:602).
@@ -200,49 +188,6 @@ inline int32_t deep_fri_walk(const DeepFriProofHost& P, const size_t* schedule, 
         bool good = false; int32_t rc = check_opening(L, 1, std::vector<size_t>{0}, one, P.final_proof, good); if (rc) return rc; if (!good) return 0;
     }
     ok = true; return 0;
-}
-
-// ---- the single-proof verifier: the walks with every level hashed through `VerifyHasher` as it is reached ---------------------
-// verify_many_ds (merkle/src/lib.rs:587-722)
-inline int32_t verify_many_ds_host(VerifyHasher& H, size_t cfg_arity, const fr_t& root, const std::vector<size_t>& indices, const std::vector<fr_t>& values, const MerkleProofHost& proof, uint64_t label, bool& ok) {
-    ok = false;
-    auto sib = [&](size_t level, size_t j) { return proof.siblings[level][j]; };
-    // hash the groups in batches of equal child count (at most two distinct counts in an honest proof)
-    auto hash_level = [&](uint32_t level, size_t arity, const std::vector<size_t>& parents, const std::vector<std::vector<fr_t>>& kids, std::vector<fr_t>& nv) -> int32_t {
-        std::vector<char> done(parents.size(), 0);
-        for (size_t g0 = 0; g0 < parents.size(); ++g0) {
-            if (done[g0]) continue;
-            const size_t cc = kids[g0].size(); std::vector<size_t> members; std::vector<uint64_t> pos; std::vector<fr_t> ch;
-            for (size_t g = g0; g < parents.size(); ++g) if (!done[g] && kids[g].size() == cc) { done[g] = 1; members.push_back(g); pos.push_back((uint64_t)parents[g]); ch.insert(ch.end(), kids[g].begin(), kids[g].end()); }
-            std::vector<fr_t> outv(members.size());
-            int32_t rc = H.ds_nodes(arity, cc, level, label, pos.data(), ch.data(), members.size(), outv.data()); if (rc) return rc;
-            for (size_t k = 0; k < members.size(); ++k) nv[members[k]] = outv[k];
-        }
-        return 0;
-    };
-    bool shaped = false; fr_t top = fr_zero<PallasFr>();
-    STARK_VERIFY_TRY(ds_walk(cfg_arity, indices, values, proof, sib, hash_level, shaped, top));
-    ok = shaped && fr_eq(top, root); return 0;
-}
-// verify_pairs_ds (merkle/src/lib.rs:723-773)
-inline int32_t verify_pairs_ds_host(VerifyHasher& H, size_t cfg_arity, const fr_t& root, const std::vector<size_t>& indices, const std::vector<fr_t>& f, const std::vector<fr_t>& cp, const MerkleProofHost& proof, uint64_t label, bool& ok) {
-    ok = false;
-    std::vector<size_t> req; std::vector<fr_t> ff, cc;
-    if (!pairs_leaf_set(cfg_arity, indices, f, cp, proof, req, ff, cc)) return 0;
-    std::vector<uint64_t> pos(req.begin(), req.end()); std::vector<fr_t> leaves(req.size());
-    STARK_VERIFY_TRY(H.ds_pair_leaves(proof.arity, label, pos.data(), ff.data(), cc.data(), req.size(), leaves.data()));
-    return verify_many_ds_host(H, cfg_arity, root, req, leaves, proof, label, ok);
-}
-// deep_fri_verify (fri.rs:643-762)
-inline int32_t deep_fri_verify_host(VerifyHasher& H, const DeepFriProofHost& P, const size_t* schedule, size_t L, size_t r, bool& ok) {
-    auto open = [&](size_t layer, size_t ar, bool hashed, const std::vector<size_t>& idx, const std::vector<fr_t>& ff, const std::vector<fr_t>& ss, const MerkleProofHost& pr, bool& good) -> int32_t {
-        if (hashed) {
-            std::vector<fr_t> lh(idx.size()); if (!idx.empty()) STARK_VERIFY_TRY(H.leaf_pairs(ff.data(), ss.data(), idx.size(), lh.data()));
-            return verify_many_ds_host(H, ar, P.roots[layer], idx, lh, pr, (uint64_t)layer, good);
-        }
-        return verify_pairs_ds_host(H, ar, P.roots[layer], idx, ff, ss, pr, (uint64_t)layer, good);
-    };
-    return deep_fri_walk(P, schedule, L, r, open, ok);
 }
 
 }  // namespace stark

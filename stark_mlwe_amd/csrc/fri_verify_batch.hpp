@@ -1,4 +1,5 @@
-// stark_mlwe_amd/csrc/fri_verify_batch.hpp — deep_fri_verify over a batch of proofs, planned on the host (product code).
+// stark_mlwe_amd/csrc/fri_verify_batch.hpp — deep_fri_verify over one proof or many, planned on the host (product code).  This is the
+// only verifier there is: the single entry point plans a batch of one.
 //
 // The hashes a verification makes depend only on the indices and group sizes inside the proof, never on hash values, so the walks
 // of fri_verify.hpp run once per proof over pool SLOTS instead of field elements and record every hash as a job.  The device then runs
@@ -35,7 +36,7 @@ struct VerifyBatchPlan {
 // The job, depth and group machinery of a batch plan, shared by the planners that walk openings over pool slots (the DEEP-FRI one below,
 // the sum-check one of sumcheck_verify_batch.hpp).  Slots while planning: an input is its pool index, a computed digest is kComputed | its
 // number.  A planner hands out input slots with new_input() (what the pool holds there is its own business), records DS hashes with
-// ds_job() and root comparisons with many(), and lays the jobs out with finish_jobs().
+// ds_job() and root comparisons with many() / pairs_rooted(), closes each item with end_item() and lays the jobs out with finish_jobs().
 class DsJobPlanner {
 public:
     static constexpr uint32_t kComputed = 0x80000000u;
@@ -45,10 +46,11 @@ protected:
     size_t n_in_ = 0;                                                                    // input slots handed out so far
     std::vector<Job> jobs_; std::vector<uint32_t> ch_; std::vector<uint32_t> depth_;     // depth_[c]: depth of computed digest c
     size_t n_comp_ = 0;
-    std::vector<uint32_t> chk_;
+    std::vector<uint32_t> chk_, chk_off_{0}; std::vector<int32_t> flag_;                 // item b: its host flag, its checks chk_[2 chk_off_[b] .. 2 chk_off_[b + 1])
 
     JobMark job_mark() const { return JobMark{n_in_, jobs_.size(), ch_.size(), n_comp_, chk_.size()}; }
     void job_rollback(const JobMark& m) { n_in_ = m.in; jobs_.resize(m.jobs); ch_.resize(m.ch); n_comp_ = m.comp; depth_.resize(m.comp); chk_.resize(m.chk); }
+    void end_item(bool ok) { flag_.push_back(ok ? 1 : 0); chk_off_.push_back((uint32_t)(chk_.size() / 2)); }      // after the rollback of a rejected item: an empty range
     uint32_t new_input() { return (uint32_t)(n_in_++); }
     uint32_t depth_of(uint32_t s) const { return s & kComputed ? depth_[s & ~kComputed] : 0; }
     uint32_t computed(uint32_t depth) { depth_.push_back(depth); return kComputed | (uint32_t)(n_comp_++); }
@@ -78,6 +80,18 @@ protected:
         if (!many(cfg_arity, 0u, ix, vals, pr, label, sib)) return false;
         chk_[before + 1] = root_slot(); return true;
     }
+    // verify_pairs_ds over slots (merkle/src/lib.rs:723-773): one two-child job at level 2^32 - 1 per distinct index over (f, cp), then many_rooted over those leaves
+    template <class Sib, class Root>
+    bool pairs_rooted(size_t cfg_arity, const std::vector<size_t>& ix, const std::vector<uint32_t>& f, const std::vector<uint32_t>& cp, const MerkleProofHost& pr, uint64_t label, Sib sib,
+                      Root root_slot) {
+        std::vector<size_t> req; std::vector<uint32_t> cf, cc, v;
+        if (!pairs_leaf_set(cfg_arity, ix, f, cp, pr, req, cf, cc)) return false;
+        for (size_t k = 0; k < req.size(); ++k) v.push_back(ds_job(pr.arity, 0xFFFFFFFFu, (uint64_t)req[k], label, {cf[k], cc[k]}));
+        return many_rooted(cfg_arity, req, v, pr, label, sib, root_slot);
+    }
+    // the items of a plan whose checks are all root comparisons (the DEEP-FRI and Merkle planners; the sum-check plan keeps its own flags and turns
+    // its comparisons into records)
+    void finish_items(VerifyBatchPlan& o) const { o.batch = flag_.size(); o.flag = flag_; o.chk_off = chk_off_; }
     // Lays the jobs out in launch order — by depth, then width; each group's digests contiguous from pool slot `next` on — and fills the
     // plan's groups, hdr, off, idx and chk.  pos: computed digest -> pool slot, preset by the caller for what it computes itself (leaf
     // digests).  Returns the pool size.
@@ -116,7 +130,7 @@ public:
             good = open(P, layer, ar, hashed, ix, ff, ss, pr); return 0;
         }, ok);
         if (!ok) rollback(m);
-        flag_.push_back(ok ? 1 : 0); chk_off_.push_back((uint32_t)(chk_.size() / 2));
+        end_item(ok);
     }
     size_t proofs() const { return flag_.size(); }
     size_t slots() const { return pool_.size() + 2 * leaf_f_.size() + n_comp_; }      // the pool the plan needs so far
@@ -125,34 +139,28 @@ public:
 private:
     struct Mark { JobMark j; size_t leaf; };
     std::vector<fr_t> pool_, leaf_f_, leaf_s_; std::vector<uint32_t> leaf_out_;
-    std::vector<uint32_t> chk_off_{0}; std::vector<int32_t> flag_;
 
     Mark mark() const { return Mark{job_mark(), leaf_f_.size()}; }
     void rollback(const Mark& m) { job_rollback(m.j); pool_.resize(m.j.in); leaf_f_.resize(m.leaf); leaf_s_.resize(m.leaf); leaf_out_.resize(m.leaf); }
     uint32_t input(const fr_t& x) { pool_.push_back(x); return new_input(); }
     uint32_t leaf(const fr_t& f, const fr_t& s) { leaf_f_.push_back(f); leaf_s_.push_back(s); leaf_out_.push_back(computed(1)); return leaf_out_.back(); }
-    bool many(size_t cfg_arity, const fr_t& root, const std::vector<size_t>& ix, const std::vector<uint32_t>& vals, const MerkleProofHost& pr, uint64_t label) {
-        auto sib = [&](size_t level, size_t j) { return input(pr.siblings[level][j]); };
-        return many_rooted(cfg_arity, ix, vals, pr, label, sib, [&]() { return input(root); });
-    }
     bool open(const DeepFriProofHost& P, size_t layer, size_t ar, bool hashed, const std::vector<size_t>& ix, const std::vector<fr_t>& ff, const std::vector<fr_t>& ss,
               const MerkleProofHost& pr) {
-        std::vector<uint32_t> v;
+        auto sib = [&](size_t level, size_t j) { return input(pr.siblings[level][j]); };
+        auto root = [&]() { return input(P.roots[layer]); };
         if (hashed) {                                                    // verify_single over hash_leaf_pair(f, s)
-            for (size_t k = 0; k < ix.size(); ++k) v.push_back(leaf(ff[k], ss[k]));
-            return many(ar, P.roots[layer], ix, v, pr, (uint64_t)layer);
+            std::vector<uint32_t> v; for (size_t k = 0; k < ix.size(); ++k) v.push_back(leaf(ff[k], ss[k]));
+            return many_rooted(ar, ix, v, pr, (uint64_t)layer, sib, root);
         }
-        std::vector<uint32_t> f, s, cf, cs; std::vector<size_t> req;     // verify_pairs: the pair leaves, then verify_many_ds over them
+        std::vector<uint32_t> f, s;                                      // verify_pairs over (f, s)
         for (size_t k = 0; k < ix.size(); ++k) { f.push_back(input(ff[k])); s.push_back(input(ss[k])); }
-        if (!pairs_leaf_set(ar, ix, f, s, pr, req, cf, cs)) return false;
-        for (size_t k = 0; k < req.size(); ++k) v.push_back(ds_job(pr.arity, 0xFFFFFFFFu, (uint64_t)req[k], (uint64_t)layer, {cf[k], cs[k]}));
-        return many(ar, P.roots[layer], req, v, pr, (uint64_t)layer);
+        return pairs_rooted(ar, ix, f, s, pr, (uint64_t)layer, sib, root);
     }
 };
 
 inline void VerifyBatchPlanner::finish(VerifyBatchPlan& out) {
     VerifyBatchPlan& o = out; o = VerifyBatchPlan();
-    o.batch = flag_.size(); o.flag = flag_; o.chk_off = chk_off_;
+    finish_items(o);
     const size_t ni = pool_.size(), nl = leaf_f_.size();
     o.nl = nl; o.leaf_f0 = ni; o.leaf_out0 = ni + 2 * nl; o.n_known = ni + 2 * nl;
     std::vector<uint32_t> pos(n_comp_);                                 // computed digest -> pool slot: the leaf digests, then each group's

@@ -324,60 +324,46 @@ size_t hc_fri_plan_assemble(void* p, const uint64_t* values, size_t n_values, ui
 }
 void hc_fri_plan_free(void* p) { delete (HcPlan*)p; }
 
-// ---- verifier (fri_verify.hpp) with every hash computed by the host instantiation of the kernel bodies -------------
-struct HcVerifyHasher : VerifyHasher {
-    void* tp; explicit HcVerifyHasher(void* t) : tp(t) {}
+// ---- verifiers: the batch plans (fri_verify_batch.hpp, merkle_batch.hpp) run step by step as the device runs them, every hash by the host
+// instantiation of the kernel bodies.  A single proof is a plan of one item. -------------
+// The Merkle parameters per width, derived once per process (t = 129 takes a while on the host)
+struct HcParamCache {
     std::map<int, HcParams*> mp;
-    ~HcVerifyHasher() { for (auto& kv : mp) delete kv.second; }
+    ~HcParamCache() { for (auto& kv : mp) delete kv.second; }
     HcParams* params(size_t arity) { int t = host::width_for_arity(arity); auto it = mp.find(t); if (it != mp.end()) return it->second; HcParams* P = new HcParams(); P->ref = host::consts_for_width(t); bind(P); mp[t] = P; return P; }
-    int32_t leaf_pairs(const fr_t* f, const fr_t* s, size_t n, fr_t* out) override {
-        std::vector<uint64_t> a(4 * n), b(4 * n), o(4 * n);
-        for (size_t i = 0; i < n; ++i) { st4(a.data() + 4 * i, f[i]); st4(b.data() + 4 * i, s[i]); }
-        hc_leaf_pair(tp, a.data(), b.data(), n, 1, o.data());
-        for (size_t i = 0; i < n; ++i) out[i] = ld4(o.data() + 4 * i);
-        return 0;
-    }
-    int32_t ds_nodes(size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions, const fr_t* children, size_t n, fr_t* out) override {
-        HcParams* P = params(arity); std::vector<fr_t> st(P->dev.t);
-        const DsStream D = DsStream::make(0, arity, level, 0, label, children, nullptr, n * chunk, 1, positions, chunk);
-        for (size_t k = 0; k < n; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, P->dev, D, k); }
-        return 0;
-    }
-    int32_t ds_pair_leaves(size_t arity, uint64_t label, const uint64_t* positions, const fr_t* f, const fr_t* cp, size_t n, fr_t* out) override {
-        HcParams* P = params(arity); std::vector<fr_t> st(P->dev.t);
-        const DsStream D = DsStream::make(1, arity, 0xFFFFFFFFu, 0, label, f, cp, n, 1, positions);
-        for (size_t k = 0; k < n; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, P->dev, D, k); }
-        return 0;
-    }
 };
-// 1 accept, 0 reject, negative: internal error
-int hc_deep_fri_verify(void* tparams, const uint8_t* bytes, size_t len, const size_t* schedule, size_t L, size_t r) {
-    DeepFriProofHost P; if (!decode_proof(bytes, len, P)) return 0;
-    HcVerifyHasher H(tparams); bool ok = false;
-    int32_t rc = deep_fri_verify_host(H, P, schedule, L, r, ok); if (rc) return rc;
-    return ok ? 1 : 0;
-}
-// deep_fri_verify over `batch` proofs through the batch plan (fri_verify_batch.hpp), run step by step as the device runs it: the leaf step,
-// then every (width, depth) group of gathered DS hashes in depth order, then the per-proof root comparisons.  accepted[i] = 1 / 0.
-int hc_deep_fri_verify_batch(void* tparams, size_t batch, const uint8_t* const* proofs, const size_t* lens, const size_t* schedule, size_t L, size_t r, int32_t* accepted) {
-    VerifyBatchPlanner pl; for (size_t b = 0; b < batch; ++b) pl.add(proofs[b], lens[b], schedule, L, r);
-    if (!pl.fits_u32()) return -1;
-    VerifyBatchPlan V; pl.finish(V);
-    HcVerifyHasher H(tparams);
-    fr_t init[17]; leaf_init(init);
-    const LeafStream LS{init, V.pool.data() + V.leaf_f0, V.pool.data() + V.leaf_f0 + V.nl, 1, V.nl};
-    { fr_t st[17]; for (size_t j = 0; j < V.nl; ++j) { ArrayState s{st}; V.pool[V.leaf_out0 + j] = leaf_pair_body(s, ((HcParams*)tparams)->dev, LS, j); } }
+static HcParamCache& hc_param_cache() { static HcParamCache c; return c; }
+// One plan: the leaf step (tparams: the transcript parameters; read only when the plan has leaves), then every (width, depth) group of gathered DS
+// hashes in depth order, then the per-item root comparisons.
+static void run_plan_host(VerifyBatchPlan V, const HcParams* tparams, int32_t* accepted) {
+    if (V.nl) {
+        fr_t init[17]; leaf_init(init);
+        const LeafStream LS{init, V.pool.data() + V.leaf_f0, V.pool.data() + V.leaf_f0 + V.nl, 1, V.nl};
+        fr_t st[17]; for (size_t j = 0; j < V.nl; ++j) { ArrayState s{st}; V.pool[V.leaf_out0 + j] = leaf_pair_body(s, tparams->dev, LS, j); }
+    }
     for (const VerifyBatchPlan::Group& G : V.groups) {
-        HcParams* P = H.params((size_t)G.t - 1); std::vector<fr_t> st(P->dev.t);
+        HcParams* P = hc_param_cache().params((size_t)G.t - 1); std::vector<fr_t> st(P->dev.t);
         const DsGatherStream D{V.hdr.data() + 4 * G.job0, V.off.data() + G.job0, V.idx.data(), V.pool.data(), G.n, G.max_children};
         for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; V.pool[G.out0 + k] = hash_ds_body(s, P->dev, D, k); }
     }
-    for (size_t b = 0; b < batch; ++b) {
+    for (size_t b = 0; b < V.batch; ++b) {
         int32_t acc = V.flag[b];
         for (uint32_t j = V.chk_off[b]; j < V.chk_off[b + 1]; ++j) acc &= fr_eq(V.pool[V.chk[2 * j]], V.pool[V.chk[2 * j + 1]]) ? 1 : 0;
         accepted[b] = acc;
     }
+}
+// deep_fri_verify over `batch` proofs through the batch plan.  accepted[i] = 1 / 0.
+int hc_deep_fri_verify_batch(void* tparams, size_t batch, const uint8_t* const* proofs, const size_t* lens, const size_t* schedule, size_t L, size_t r, int32_t* accepted) {
+    VerifyBatchPlanner pl; for (size_t b = 0; b < batch; ++b) pl.add(proofs[b], lens[b], schedule, L, r);
+    if (!pl.fits_u32()) return -1;
+    VerifyBatchPlan V; pl.finish(V);
+    run_plan_host(std::move(V), (const HcParams*)tparams, accepted);
     return 0;
+}
+// 1 accept, 0 reject, negative: internal error
+int hc_deep_fri_verify(void* tparams, const uint8_t* bytes, size_t len, const size_t* schedule, size_t L, size_t r) {
+    int32_t acc = 0; const int rc = hc_deep_fri_verify_batch(tparams, 1, &bytes, &len, schedule, L, r, &acc);
+    return rc ? rc : acc;
 }
 // the launch steps of the batch plan: (width, depth, hashes) of each DS group, in launch order; returns the number of groups (at most cap written)
 size_t hc_verify_batch_groups(size_t batch, const uint8_t* const* proofs, const size_t* lens, const size_t* schedule, size_t L, size_t r, int32_t* t, uint32_t* depth, size_t* n, size_t cap) {
@@ -388,13 +374,13 @@ size_t hc_verify_batch_groups(size_t batch, const uint8_t* const* proofs, const 
 }
 // MerkleProver::verify_single / verify_pairs (merkle/src/lib.rs:800-855) over the canonical MerkleProof encoding
 int hc_merkle_verify(void* tparams, int pairs, size_t cfg_arity, uint64_t label, const uint64_t* root, const size_t* idx, size_t k, const uint64_t* vals, const uint64_t* cp, const uint8_t* proof, size_t len) {
-    ByteReader R(proof, len); MerkleProofHost pr; if (!dec_mproof(R, pr) || R.left()) return 0;
-    HcVerifyHasher H(tparams); bool ok = false;
-    std::vector<size_t> ix(idx, idx + k); std::vector<fr_t> v(k), c(k);
-    for (size_t i = 0; i < k; ++i) { v[i] = ld4(vals + 4 * i); if (pairs) c[i] = ld4(cp + 4 * i); }
-    int32_t rc = pairs ? verify_pairs_ds_host(H, cfg_arity, ld4(root), ix, v, c, pr, label, ok) : verify_many_ds_host(H, cfg_arity, ld4(root), ix, v, pr, label, ok);
-    if (rc) return rc;
-    return ok ? 1 : 0;
+    (void)tparams;                                                     // a Merkle plan has no leaf step
+    const uint64_t none[4] = {0, 0, 0, 0};                             // pairs mode is chosen by a non-null cp: an empty pairs request still goes the pairs way
+    MerkleVerifyPlanner pl; pl.add(cfg_arity, label, root, idx, k, vals, pairs ? (cp ? cp : none) : nullptr, proof, len);
+    if (!pl.fits_u32()) return -1;
+    VerifyBatchPlan V; pl.finish(V);
+    int32_t acc = 0; run_plan_host(std::move(V), nullptr, &acc);
+    return acc;
 }
 
 }  // extern "C"
@@ -519,10 +505,8 @@ size_t hc_sumcheck_verify_batch_steps(int mf, size_t batch, const uint8_t* const
 // ---- the batched commit phase (fri_batch.hpp) through the host instantiation of the stream bodies ----------------------------------
 struct FriHostExec {
     HcParams* tp; std::vector<std::vector<uint64_t>> mem;
-    struct ParamCache { HcVerifyHasher h{nullptr}; HcParams* params(size_t arity) { return h.params(arity); } };
-    ParamCache& mp;                                                   // the Merkle parameters per width, derived once per process (t = 129 takes a while on the host)
-    static ParamCache& cache() { static ParamCache c; return c; }
-    explicit FriHostExec(HcParams* t) : tp(t), mp(cache()) {}
+    HcParamCache& mp;
+    explicit FriHostExec(HcParams* t) : tp(t), mp(hc_param_cache()) {}
     int32_t alloc(size_t bytes, void** out) { mem.emplace_back((bytes + 7) / 8 + 1, 0); *out = mem.back().data(); return 0; }
     int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
     int32_t zpows(const fr_t& z, size_t m, fr_t* zp) { fr_t acc = fr_one<PF>(); for (size_t t = 0; t < m; ++t) { zp[t] = acc; acc = fr_mul<PF>(acc, z); } return 0; }
@@ -666,19 +650,6 @@ struct MerkleHostExec {
     int32_t ds_level(const DsBatchStream& D, fr_t* out) { return ds(D, out); }
 };
 struct MerkleOpenHostExec { int32_t gather(const MerkleGatherList& G, fr_t* out) { for (size_t i = 0; i < G.size(); ++i) out[i] = G.base[G.src[i]][G.index[i]]; return 0; } };
-struct MerkleVerifyHostExec {
-    FriHostExec::ParamCache& mp;
-    int32_t run(const VerifyBatchPlan& V0, const std::vector<uint32_t>& pair, int32_t* accepted) {
-        VerifyBatchPlan V = V0;
-        for (const VerifyBatchPlan::Group& G : V.groups) {
-            HcParams* P = mp.params((size_t)G.t - 1); std::vector<fr_t> st(P->dev.t);
-            const DsGatherStream D{V.hdr.data() + 4 * G.job0, V.off.data() + G.job0, V.idx.data(), V.pool.data(), G.n, G.max_children};
-            for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; V.pool[G.out0 + k] = hash_ds_body(s, P->dev, D, k); }
-        }
-        for (size_t b = 0; b < V.batch; ++b) accepted[b] = V.flag[b] & (fr_eq(V.pool[pair[2 * b]], V.pool[pair[2 * b + 1]]) ? 1 : 0);
-        return 0;
-    }
-};
 static std::vector<size_t> total_lens(const std::vector<size_t>& lens, size_t B) { std::vector<size_t> o(lens.size() + 1, 0); for (size_t v = 0; v < lens.size(); ++v) o[v + 1] = o[v] + B * lens[v]; return o; }
 extern "C" {
 // MerkleTree::new / new_pairs of B trees of n leaves through the batch driver.  leaves / cp: B host columns (cp null iff !pairs; a null entry = zeros).
@@ -726,7 +697,7 @@ long hc_merkle_open_batch(size_t B, const size_t* arity, const size_t* nlev, con
 int hc_merkle_verify_batch(size_t cfg_arity, size_t batch, const uint64_t* labels, const uint64_t* roots, const size_t* indices, const size_t* idx_off, const uint64_t* values,
                            const uint8_t* const* proofs, const size_t* lens, size_t max_slots, int32_t* accepted) {
     if (host::width_for_arity(cfg_arity) < 0 || cfg_arity == 0) return -1;
-    MerkleVerifyHostExec X{FriHostExec::cache()};
-    return merkle_verify_batch(X, cfg_arity, batch, labels, roots, indices, idx_off, values, proofs, lens, max_slots ? max_slots : (size_t)1 << 25, accepted);
+    auto run = [](const VerifyBatchPlan& V, int32_t* acc) { run_plan_host(V, nullptr, acc); return 0; };
+    return merkle_verify_batch(run, cfg_arity, batch, labels, roots, indices, idx_off, values, proofs, lens, max_slots ? max_slots : (size_t)1 << 25, accepted);
 }
 }  // extern "C"

@@ -6,8 +6,8 @@
 //           b * lens[v]: level 0 is one copy (or one pair-leaf launch) through the pointer tables, every level above one DsBatchStream launch.
 //   open    any trees of one context: every tree is planned on the host (merkle_open_from over a recording source), all siblings of all trees and
 //           levels come back with ONE gather, and each proof is encoded with enc_mproof.
-//   verify  every opening is parsed with the single verifier's guards and walked over pool slots (DsJobPlanner); the device runs one launch per
-//           (width, depth) and compares each item's computed root with the claimed one.
+//   verify  every opening is parsed (dec_mproof) and walked over pool slots (DsJobPlanner) into the plan shape of fri_verify_batch.hpp; what runs the
+//           plan makes one launch per (width, depth) and compares each item's computed root with the claimed one.  The single verify calls are a batch of one.
 // Element i of every result equals what the single call returns for item i alone, byte for byte.  Host-only C++ (no HIP).
 #pragma once
 #include <cstdint>
@@ -97,57 +97,55 @@ inline int32_t merkle_open_batch(X& x, const MerkleTreeView* trees, size_t B, co
 }
 
 // ---- verify -----------------------------------------------------------------------------------------------------------------------------------
-// Plans verify_many_ds of one opening at a time.  Every input slot holds a field element the caller handed over (values in the stored form, as
-// the single call takes them; siblings decoded from the proof bytes; the claimed root).  After finish(): item b is accepted iff flag[b] and
-// pool[pair[2b]] == pool[pair[2b + 1]] (the root the walk computed, the root it claims); a rejected item keeps no job and the pair (0, 0).
+// Plans verify_many_ds (cp_values == nullptr) or verify_pairs_ds of one opening at a time.  Every input slot holds a field element the caller handed
+// over (values in the stored form; siblings decoded from the proof bytes; the claimed root).  After finish(): an accepted item has flag 1 and one
+// check (the root its walk computed, the root it claims); a rejected item keeps no job, an empty check range and flag 0.
 class MerkleVerifyPlanner : public DsJobPlanner {
 public:
-    // root4 / values: the caller's host words, four per element, at whatever alignment a uint64_t has (an fr_t is 16-byte aligned: never cast)
-    void add(size_t cfg_arity, uint64_t label, const uint64_t* root4, const size_t* idx, size_t k, const uint64_t* values, const uint8_t* proof, size_t len) {
+    // root4 / values / cp_values: the caller's host words, four per element, at whatever alignment a uint64_t has (an fr_t is 16-byte aligned: never cast)
+    void add(size_t cfg_arity, uint64_t label, const uint64_t* root4, const size_t* idx, size_t k, const uint64_t* values, const uint64_t* cp_values, const uint8_t* proof, size_t len) {
         const JobMark m = job_mark(); bool ok = false;
         ByteReader R(proof, len); MerkleProofHost pr;
         if (dec_mproof(R, pr) && !R.left()) {                          // bytes that do not decode: a rejection
-            const std::vector<size_t> ix(idx, idx + k); std::vector<uint32_t> v;
-            for (size_t i = 0; i < k; ++i) v.push_back(input(words(values + 4 * i)));
+            const std::vector<size_t> ix(idx, idx + k); std::vector<uint32_t> v, c;
+            for (size_t i = 0; i < k; ++i) { v.push_back(input(words(values + 4 * i))); if (cp_values) c.push_back(input(words(cp_values + 4 * i))); }
             auto sib = [&](size_t level, size_t j) { return input(pr.siblings[level][j]); };
-            ok = many_rooted(cfg_arity, ix, v, pr, label, sib, [&]() { return input(words(root4)); });
+            auto root = [&]() { return input(words(root4)); };
+            ok = cp_values ? pairs_rooted(cfg_arity, ix, v, c, pr, label, sib, root) : many_rooted(cfg_arity, ix, v, pr, label, sib, root);
         }
         if (!ok) { job_rollback(m); pool_.resize(m.in); }
-        flag_.push_back(ok ? 1 : 0);
+        end_item(ok);
     }
     size_t items() const { return flag_.size(); }
     size_t slots() const { return pool_.size() + n_comp_; }
     bool fits_u32() const { return slots() < kComputed && ch_.size() < kComputed; }
-    void finish(VerifyBatchPlan& o, std::vector<uint32_t>& pair) const {
-        o = VerifyBatchPlan(); o.batch = flag_.size(); o.flag = flag_; o.n_known = pool_.size();
+    void finish(VerifyBatchPlan& o) const {
+        o = VerifyBatchPlan(); finish_items(o); o.n_known = pool_.size();
         std::vector<uint32_t> pos(n_comp_);
         const size_t total = finish_jobs(o, pos, pool_.size());
-        o.pool.assign(std::max<size_t>(total, 1), fr_zero<PallasFr>()); std::copy(pool_.begin(), pool_.end(), o.pool.begin());   // slot 0 exists: the pair of a rejected item reads it
-        pair.assign(2 * o.batch, 0u);
-        for (size_t b = 0, j = 0; b < o.batch; ++b) if (flag_[b]) { pair[2 * b] = o.chk[2 * j]; pair[2 * b + 1] = o.chk[2 * j + 1]; ++j; }
+        o.pool.assign(total, fr_zero<PallasFr>()); std::copy(pool_.begin(), pool_.end(), o.pool.begin());
     }
 private:
-    std::vector<fr_t> pool_; std::vector<int32_t> flag_;
+    std::vector<fr_t> pool_;
     uint32_t input(const fr_t& x) { pool_.push_back(x); return new_input(); }
     static fr_t words(const uint64_t* p) { fr_t x; for (int i = 0; i < 4; ++i) { x.v[2 * i] = (uint32_t)p[i]; x.v[2 * i + 1] = (uint32_t)(p[i] >> 32); } return x; }
 };
 // verify_many_ds of `batch` openings: item i opens indices[idx_off[i] .. idx_off[i + 1]) with values[4 x the same range] against roots[4 i ..] under
-// labels[i] (roots and values as uint64_t words, read at their own alignment).  A plan is run once it holds max_slots pool slots, so the executor's memory stays bounded whatever the batch.
-// An executor X provides   int32_t run(const VerifyBatchPlan& V, const std::vector<uint32_t>& pair, int32_t* accepted)
-//   (the DS groups of V in depth order, then accepted[b] = V.flag[b] & (pool[pair[2b]] == pool[pair[2b + 1]])).
+// labels[i] (roots and values as uint64_t words, read at their own alignment).  A plan is run once it holds max_slots pool slots, so the memory of
+// whatever runs it stays bounded whatever the batch.  run(V, accepted) runs one plan: the DS groups of V in depth order, then its checks.
 // -1: an item that needs more than 2^31 pool slots.
-template <class X>
-inline int32_t merkle_verify_batch(X& x, size_t cfg_arity, size_t batch, const uint64_t* labels, const uint64_t* roots, const size_t* indices, const size_t* idx_off,
+template <class Run>
+inline int32_t merkle_verify_batch(Run run, size_t cfg_arity, size_t batch, const uint64_t* labels, const uint64_t* roots, const size_t* indices, const size_t* idx_off,
                                    const uint64_t* values, const uint8_t* const* proofs, const size_t* lens, size_t max_slots, int32_t* accepted) {
     size_t b0 = 0;
     while (b0 < batch) {
         MerkleVerifyPlanner pl; size_t b1 = b0;
         while (b1 < batch && (b1 == b0 || pl.slots() < max_slots)) {
-            pl.add(cfg_arity, labels[b1], roots + 4 * b1, indices + idx_off[b1], idx_off[b1 + 1] - idx_off[b1], values + 4 * idx_off[b1], proofs[b1], lens[b1]); ++b1;
+            pl.add(cfg_arity, labels[b1], roots + 4 * b1, indices + idx_off[b1], idx_off[b1 + 1] - idx_off[b1], values + 4 * idx_off[b1], nullptr, proofs[b1], lens[b1]); ++b1;
         }
         if (!pl.fits_u32()) return -1;
-        VerifyBatchPlan V; std::vector<uint32_t> pair; pl.finish(V, pair);
-        MB_TRY(x.run(V, pair, accepted + b0));
+        VerifyBatchPlan V; pl.finish(V);
+        MB_TRY(run(V, accepted + b0));
         b0 = b1;
     }
     return 0;

@@ -17,10 +17,6 @@ int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGath
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out);
-// DS hashes with scattered positions (the verifier's union-of-paths levels): hash k = H([arity, level, positions[k], label] || chunk children)
-int32_t hash_ds_scattered(stark_ctx* ctx, stark_params* p, int mode, size_t arity, size_t chunk, uint32_t level, uint64_t label, const uint64_t* positions_dev,
-                          const fr_t* in0, const fr_t* in1, size_t n_hashes, fr_t* out);
-
 int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h);
 int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t arity, uint64_t label, const fr_t* leaves, size_t n, int pairs, const fr_t* cp, size_t cp_div,
                         uint64_t first_pos, uint32_t level0, size_t stop_at_len, bool adopt, stark_tree** out);

@@ -16,21 +16,19 @@ typedef PallasFr PF;   // the prover field
 //   mode 0 (node level): children_k = in0[k*arity .. min((k+1)*arity, n_in))  (the last node of a level may be ragged)
 //   mode 1 (pair leaf) : children_k = {in0[k], in1[k / cp_div]}  (merkle/src/lib.rs:380-388); in1 == nullptr: the second child is zero
 //                        (fri.rs:266).  cp_div = m serves commit_pairs(f_l, s_l) with s_l the view f_{l+1}[i/m].
-//   pos_list != nullptr: hash k carries DS position pos_list[k] instead of pos0 + k (the verifier's union-of-paths levels, whose parents are
-//                        scattered; merkle/src/lib.rs:683-689).
-//   chunk != 0         : `chunk` children per hash while the DS field stays `arity` (the verifier's groups: a short last chunk of the proof's level).
+// (The verifiers' union-of-paths levels, whose parents are scattered, are DsGatherStream's.)
 struct DsStream {
-    fr_t arity_f, level_f, label_f; uint64_t pos0; size_t arity, n_in, n_out; int mode; size_t cp_div; const uint64_t* pos_list;
+    fr_t arity_f, level_f, label_f; uint64_t pos0; size_t arity, n_in, n_out; int mode; size_t cp_div;
     const fr_t* in0; const fr_t* in1;
     static inline DsStream make(int mode, size_t arity, uint32_t level, uint64_t pos0, uint64_t label, const fr_t* in0, const fr_t* in1, size_t n_in,
-                                size_t cp_div = 1, const uint64_t* pos_list = nullptr, size_t chunk = 0) {
+                                size_t cp_div = 1) {
         DsStream D;
         D.arity_f = fr_from_u64<PF>(arity); D.level_f = fr_from_u64<PF>(level); D.label_f = fr_from_u64<PF>(label); D.pos0 = pos0;
-        D.arity = chunk ? chunk : arity; D.n_in = n_in; D.mode = mode; D.cp_div = cp_div ? cp_div : 1; D.pos_list = pos_list; D.in0 = in0; D.in1 = in1;
+        D.arity = arity; D.n_in = n_in; D.mode = mode; D.cp_div = cp_div ? cp_div : 1; D.in0 = in0; D.in1 = in1;
         D.n_out = mode == 1 ? n_in : (n_in + D.arity - 1) / D.arity;
         return D;
     }
-    FR_HD uint64_t position(size_t k) const { return pos_list ? pos_list[k] : pos0 + k; }
+    FR_HD uint64_t position(size_t k) const { return pos0 + k; }
     FR_HD size_t total(size_t k) const { return 4 + (mode == 1 ? 2 : ((k + 1) * arity <= n_in ? arity : n_in - k * arity)) + 1; }
     FR_HD size_t max_total() const { return 4 + (mode == 1 ? 2 : arity) + 1; }      // the widest sponge of the batch
     FR_HD fr_t elem(size_t k, size_t q) const {

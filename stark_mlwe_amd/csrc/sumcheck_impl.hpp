@@ -4,7 +4,7 @@
 #include "fri_verify.hpp"
 
 // The provers' transcript labels, the reference's strings verbatim (channel/src/lib.rs).  The round loops of sumcheck_batch.hpp lay out
-// their absorbs with these, the single verifiers of capi_sumcheck.hip absorb them, and the host-check library includes this file for them.
+// their absorbs with these, as the verification plans of sumcheck_verify_batch.hpp do, and the host-check library includes this file for them.
 namespace stark { namespace sc_lab {
 constexpr const char *digest = "CHAN/SEND/DIGEST", *open = "CHAN/SEND/OPEN", *arity = "PROOF/ARITY", *group_sizes = "PROOF/GROUP_SIZES",
                      *siblings = "PROOF/SIBLINGS";                                                                          // :22-56

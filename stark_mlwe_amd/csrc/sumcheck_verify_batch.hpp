@@ -3,8 +3,8 @@
 //
 // Everything a sum-check verifier hashes or absorbs is data inside the proof: verify_mf draws r_i from prev_root, which it reads and never
 // computes, and checks each opening against a root the proof claims; verify_plain's transcript absorbs only the proof's coefficients.  So
-// the planner parses the bincode layout exactly as BinR does (capi_sumcheck.hip: same length guards, the == 32 FBytes prefix, the Option
-// tag byte of ProofPlain, no trailing bytes) but converts NO field element: it records where each one sits in the uploaded bytes and
+// the planner parses the bincode layout of ProofPlain / ProofMF (length guards that a forged prefix cannot pass, the == 32 FBytes prefix, the
+// Option tag byte of ProofPlain, no trailing bytes) but converts NO field element: it records where each one sits in the uploaded bytes and
 // which pool slot it lands in, and the device decodes them (sc_decode_fr: range check and Montgomery conversion, one lane each).
 //
 // The plan, after finish():
@@ -112,7 +112,7 @@ public:
         const bool ok = mf_ ? add_mf(bytes, len, label) : add_plain(bytes, len);
         if (ok) { blob_.resize((base_ + len + 15) / 16 * 4, 0u); if (len) memcpy((uint8_t*)blob_.data() + base_, bytes, len); }
         else rollback(m);
-        flag_.push_back(ok ? 1 : 0); chk_off_.push_back((uint32_t)(chk_.size() / 2));
+        end_item(ok);
     }
     size_t proofs() const { return flag_.size(); }
     size_t slots() const { return n_in_ + seg_end_.size() + n_comp_; }               // the pool the plan needs so far
@@ -129,7 +129,7 @@ private:
     ScConsts C_;
     std::vector<uint32_t> blob_, dec_off_, dec_proof_;
     std::vector<Inst> inst_; std::vector<uint32_t> seg_end_, tidx_;      // seg_end_[s]: end of segment s in tidx_
-    std::vector<uint32_t> rec_, chk_off_{0}; std::vector<int32_t> flag_;
+    std::vector<uint32_t> rec_;
 
     Mark mark() const { return Mark{job_mark(), dec_off_.size(), inst_.size(), seg_end_.size(), tidx_.size(), rec_.size()}; }
     void rollback(const Mark& m) { job_rollback(m.j); dec_off_.resize(m.dec); dec_proof_.resize(m.dec); inst_.resize(m.inst); seg_end_.resize(m.seg); tidx_.resize(m.tidx); rec_.resize(m.rec); }
@@ -137,7 +137,7 @@ private:
     void record(std::initializer_list<uint32_t> w) { rec_.insert(rec_.end(), w.begin(), w.end()); }
     uint32_t end_segment() { seg_end_.push_back((uint32_t)tidx_.size()); return kRSlot | (uint32_t)(seg_end_.size() - 1); }
 
-    // BinR over slots: an FBytes is its length prefix (== 32) and 32 bytes that stay where they are
+    // the bincode reader over slots: an FBytes is its length prefix (== 32) and 32 bytes that stay where they are
     struct Rd {
         ScVerifyPlanner& P; ByteReader R; Rd(ScVerifyPlanner& p, const uint8_t* b, size_t n) : P(p), R(b, n) {}
         uint32_t fb() { if (R.u64() != 32) R.ok = false; if (!R.ok || R.left() < 32) { R.ok = false; return 0; } const uint32_t s = P.decode_at(R.pos, 0u); R.pos += 32; return s; }
@@ -153,7 +153,7 @@ private:
         }
     };
 
-    bool add_plain(const uint8_t* bytes, size_t len) {                                          // verify_plain_impl
+    bool add_plain(const uint8_t* bytes, size_t len) {                                          // verify_plain (:1080-1128): a failed check answers `false` (in the reference a failed assert_eq!, a panic)
         Rd D(*this, bytes, len); const uint32_t root = D.fb(); const size_t nr = D.R.len(80);
         std::vector<std::pair<uint32_t, uint32_t>> rounds(nr); size_t c0_pos = 0;
         for (size_t i = 0; i < nr && D.R.ok; ++i) { if (i == 0) c0_pos = D.R.pos + 8; rounds[i].first = D.fb(); rounds[i].second = D.fb(); }
@@ -174,7 +174,7 @@ private:
         }
         return true;
     }
-    bool add_mf(const uint8_t* bytes, size_t len, uint64_t label) {                              // verify_mf_impl
+    bool add_mf(const uint8_t* bytes, size_t len, uint64_t label) {                              // verify_mf (:1176-1240)
         Rd D(*this, bytes, len); const uint32_t initial_root = D.fb(); const size_t nr = D.R.len(120);
         std::vector<RoundMF> rounds(nr);
         for (size_t i = 0; i < nr && D.R.ok; ++i) { RoundMF& R = rounds[i]; R.c0 = D.fb(); R.c1 = D.fb(); R.next_root = D.fb(); D.idxs(R.cur_indices); D.fvec(R.cur_values); D.mproof(R.cur_proof); D.idxs(R.next_indices); D.fvec(R.next_values); D.mproof(R.next_proof); }

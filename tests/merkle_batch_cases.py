@@ -1,5 +1,5 @@
 """What the batched-Merkle tests share (tests/test_merkle_batch_host.py on the CPU, tests/test_gpu_merkle_batch.py on the GPU): the shapes, the
-inputs, the oracle's trees and its verify_many_ds over proof bytes (tests/oracle_merkle_verify.cpp, built here), and the tamperings."""
+inputs, the oracle's trees and its verify_many_ds / verify_pairs_ds over proof bytes (tests/oracle_merkle_verify.cpp, built here), and the tamperings."""
 import ctypes as C
 import functools
 import os
@@ -50,6 +50,15 @@ def oracle_verify(cfg_arity, label, root, idx, values, proof: bytes):
     buf = (C.c_uint8 * max(1, len(proof))).from_buffer_copy(proof or b"\0")
     return oracle_verify_lib().om_verify_many_ds(C.c_size_t(cfg_arity), C.c_uint64(label), r.ctypes.data_as(C.c_void_p), ix.ctypes.data_as(C.c_void_p), C.c_size_t(len(ix)),
                                                  v.ctypes.data_as(C.c_void_p), buf, C.c_size_t(len(proof)))
+
+
+def oracle_verify_pairs(cfg_arity, label, root, idx, f, cp, proof: bytes):
+    """the oracle's verify_pairs_ds over proof bytes: 1 accept, 0 reject, -1 where the reference would panic"""
+    ix = np.ascontiguousarray(idx, dtype=np.uint64); r = np.ascontiguousarray(root, dtype=np.uint64)
+    fv = np.ascontiguousarray(f, dtype=np.uint64).reshape(-1, 4); cv = np.ascontiguousarray(cp, dtype=np.uint64).reshape(-1, 4)
+    buf = (C.c_uint8 * max(1, len(proof))).from_buffer_copy(proof or b"\0")
+    return oracle_verify_lib().om_verify_pairs_ds(C.c_size_t(cfg_arity), C.c_uint64(label), r.ctypes.data_as(C.c_void_p), ix.ctypes.data_as(C.c_void_p), C.c_size_t(len(ix)),
+                                                  fv.ctypes.data_as(C.c_void_p), cv.ctypes.data_as(C.c_void_p), buf, C.c_size_t(len(proof)))
 
 
 def off8(a):

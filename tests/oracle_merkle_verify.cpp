@@ -1,5 +1,5 @@
-// tests/oracle_merkle_verify.cpp — TEST INFRASTRUCTURE ONLY: the oracle's verify_many_ds (oracle/merkle.hpp, merkle/src/lib.rs:587-701) over the
-// canonical MerkleProof bytes, so that tampered, truncated and empty proofs can be put to the oracle as they are put to the product.
+// tests/oracle_merkle_verify.cpp — TEST INFRASTRUCTURE ONLY: the oracle's verify_many_ds and verify_pairs_ds (oracle/merkle.hpp,
+// merkle/src/lib.rs:587-701, :723-773) over the canonical MerkleProof bytes, so that tampered, truncated and empty proofs can be put to the oracle as they are put to the product.
 // Built by tests/merkle_batch_cases.py into tests/_build/; the product never links or loads it.
 #include <cstring>
 #include "../oracle/merkle.hpp"
@@ -34,4 +34,12 @@ extern "C" int om_verify_many_ds(size_t cfg_arity, uint64_t label, const uint64_
     std::vector<size_t> ix(idx, idx + k); std::vector<Fr> v(k);
     for (size_t i = 0; i < k; ++i) v[i] = Fr::from_raw(values + 4 * i);
     try { return verify_many_ds(Fr::from_raw(root), ix, v, pr, label, poseidon_params_for_arity(cfg_arity)) ? 1 : 0; } catch (...) { return -1; }
+}
+// the same for verify_pairs_ds over (f[i], cp[i])
+extern "C" int om_verify_pairs_ds(size_t cfg_arity, uint64_t label, const uint64_t* root, const size_t* idx, size_t k, const uint64_t* f, const uint64_t* cp, const uint8_t* proof, size_t len) {
+    Dec d{proof, len}; MerkleProof pr;
+    if (!d.mproof(pr)) return 0;
+    std::vector<size_t> ix(idx, idx + k); std::vector<std::pair<Fr, Fr>> ps(k);
+    for (size_t i = 0; i < k; ++i) ps[i] = {Fr::from_raw(f + 4 * i), Fr::from_raw(cp + 4 * i)};
+    try { return verify_pairs_ds(Fr::from_raw(root), ix, ps, pr, label, poseidon_params_for_arity(cfg_arity)) ? 1 : 0; } catch (...) { return -1; }
 }

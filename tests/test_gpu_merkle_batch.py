@@ -182,16 +182,17 @@ def test_verify_batch_matches_the_single_verifier_item_by_item(gpu_ctx, oracle):
             items.append((lab, s.root, [], s.levels[0][:0], s.open(ix))); names.append((n, b, "no index"))
     assert len(items) == 16 and {nm[2] for nm in names} >= {"honest", "value bit", "sibling bit", "wrong root", "truncated", "empty", "index out of range"}
     cfg = gpu_ctx.merkle_cfg(16)
-    want = [gpu_ctx.merkle_verify_single(cfg.with_tree_label(lab), root, ix, v, pr) for lab, root, ix, v, pr in items]
+    want = [mc.oracle_verify(16, *it) == 1 for it in items]                 # every item's decision is the oracle's; the single call plans a batch of one
+    assert want == [nm[2].startswith("honest") for nm in names]
+    alone = [gpu_ctx.merkle_verify_single(cfg.with_tree_label(lab), root, ix, v, pr) for lab, root, ix, v, pr in items]
+    assert alone == want, list(zip(names, alone, want))
     got = gpu_ctx.merkle_verify_single_batch(16, [it[0] for it in items], [it[1] for it in items], [it[2] for it in items], [it[3] for it in items], [it[4] for it in items])
     assert got == want, list(zip(names, got, want))
-    assert want == [nm[2].startswith("honest") for nm in names]
-    assert want == [mc.oracle_verify(16, *it) == 1 for it in items]
 
 
 def test_verify_batch_reads_roots_and_values_at_eight_byte_alignment(gpu_ctx, oracle):
     """`roots` and `values` are uint64_t pointers: buffers whose address is 8 mod 16 (a root behind a u64 in a struct, a Rust `&[F]`) give the
-    decisions of the single call, which takes the same pointers"""
+    decisions of the single call, which takes the same pointers, and of the oracle"""
     lib, h = gpu_ctx.lib, gpu_ctx.h
     s = single(gpu_ctx, oracle, 16, 257, False, 3, 1); ix = mc.index_lists(257, 1); lab = mc.labels_of(3)[1]; pr = s.open(ix)
     vals = s.levels[0][ix]; bad = mc.flip_bit(vals, 1, 3)
@@ -206,6 +207,7 @@ def test_verify_batch_reads_roots_and_values_at_eight_byte_alignment(gpu_ctx, or
         gpu_ctx._chk(lib.stark_merkle_verify_many_ds(h, 16, lab, hp(rt[b]), hp(ixa), len(ix), hp(va[b * len(ix):(b + 1) * len(ix)]), buf, len(pr), C.byref(ok)))
         want.append(ok.value)
     assert [int(a) for a in acc] == want == [1, 0]
+    assert want == [int(mc.oracle_verify(16, lab, s.root, ix, v, pr) == 1) for v in (vals, bad)]
     roots = mc.off8(np.zeros((2, 4), np.uint64))                             # and the roots come back into such a buffer
     gpu_ctx._chk(lib.stark_merkle_roots_batch(tab([s.tree.h.value, s.tree.h.value]), 2, hp(roots)))
     assert (roots == s.root).all()

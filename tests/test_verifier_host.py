@@ -1,13 +1,15 @@
 """The PRODUCT's verifier logic (stark_mlwe_amd/csrc/fri_verify.hpp: decoder, deep_fri_verify, verify_many_ds / verify_pairs_ds —
-written from crates/deep_ali/src/fri.rs:643-762 and crates/merkle/src/lib.rs:587-773) on the CPU, with the hashes computed by the
-host instantiation of the kernel bodies (libstark_mlwe_hostcheck.so).  Checked against the oracle's independent restatement of
+written from crates/deep_ali/src/fri.rs:643-762 and crates/merkle/src/lib.rs:587-773) on the CPU: each proof planned as a batch of one
+(fri_verify_batch.hpp, merkle_batch.hpp) and the plan run by the host instantiation of the kernel bodies (libstark_mlwe_hostcheck.so).  Checked against the oracle's independent restatement of
 the same functions: accept on honest proofs, and the SAME accept/reject decision on hundreds of tampered byte strings.
-The GPU build of the same logic (capi_verify.hip: hashes on the device) is tested in tests/test_gpu_r2_verify.py."""
+The GPU build of the same logic (capi_verify.hip: the plan run on the device) is tested in tests/test_gpu_r2_verify.py."""
 import random
 import struct
 
 import numpy as np
 import pytest
+
+import merkle_batch_cases as mc
 
 
 @pytest.fixture(scope="module")
@@ -111,3 +113,22 @@ def test_merkle_verify_pairs_roundtrip_and_tamper(oracle, hostcheck, tparams, ar
     assert hostcheck.merkle_verify(tparams, True, arity, 7, root, idx, f[idx], bad, pr) == 0
     assert hostcheck.merkle_verify(tparams, True, arity, 8, root, idx, f[idx], cp[idx], pr) == 0
     assert hostcheck.merkle_verify(tparams, False, arity, 7, root, idx, f[idx], None, pr) == 0                # single-column verification of a pair tree
+
+
+@pytest.mark.parametrize("arity,n", [(2, 5), (16, 17)])
+def test_merkle_verify_pairs_repeated_index_later_payload_wins_and_empty_list(oracle, hostcheck, tparams, arity, n):
+    """verify_pairs_ds (merkle/src/lib.rs:723-773) as the shared planner walks it, on a ragged last node (2, 5) and a two-level tree (16, 17): for an
+    index given twice with different payloads the LATER entry is the leaf (:746-750), and an empty index list is a rejection (:731-733).  Every
+    decision is the oracle's verify_pairs_ds on the same bytes."""
+    f = oracle.synth_column(43, 0, 0, n); cp = oracle.synth_column(43, 1, 0, n); label = 11
+    t = oracle.merkle_build(arity, label, f, cp=cp)
+    idx = [n - 1, 1, n - 1]
+    pr = t.open_bytes(idx); root = t.root(); t.free()
+    fv, cv = f[idx].copy(), cp[idx].copy()
+    wrong_f = fv.copy(); wrong_f[0, 0] ^= np.uint64(1)                    # the earlier entry of the repeated index is wrong: it is overwritten
+    wrong_c = cv.copy(); wrong_c[2, 1] ^= np.uint64(2)                    # the later entry is wrong: it is the one that is hashed
+    cases = [(idx, fv, cv, 1), (idx, wrong_f, cv, 1), (idx, fv, wrong_c, 0), (idx[::-1], fv[::-1], wrong_c[::-1], 1), ([], fv[:0], cv[:0], 0)]
+    for ix, a, b, expect in cases:
+        want = mc.oracle_verify_pairs(arity, label, root, ix, a, b, pr)
+        assert want == expect, (ix, want)
+        assert hostcheck.merkle_verify(tparams, True, arity, label, root, ix, a, b, pr) == want, ix

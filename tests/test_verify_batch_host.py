@@ -1,7 +1,7 @@
 """The batch verifier's plan (stark_mlwe_amd/csrc/fri_verify_batch.hpp: every hash of every opening of every proof recorded as a job over one
 pool, grouped by Poseidon width and dependency depth) on the CPU: hc_deep_fri_verify_batch runs that plan through the host instantiation of
-the kernel bodies the device runs (hash_ds_body over DsGatherStream, leaf_pair_body).  Each decision must equal the single-proof verifier
-(hc_deep_fri_verify) and the oracle's restatement of deep_fri_verify (fri.rs:643-762) on that proof alone.
+the kernel bodies the device runs (hash_ds_body over DsGatherStream, leaf_pair_body).  Each decision must equal the single call
+(hc_deep_fri_verify: the same plan with one item) and, independently, the oracle's restatement of deep_fri_verify (fri.rs:643-762) on that proof alone.
 The GPU build of the same plan (stark_deep_fri_verify_batch) is tested in tests/test_gpu_verify_batch.py."""
 import ctypes as C
 import random
@@ -66,7 +66,8 @@ def test_batch_decisions_equal_single_and_oracle(oracle, hostcheck, tparams, n0,
 
 def test_batch_first_payload_wins_and_local_check(oracle, hostcheck, tparams):
     """Repeated query indices (fri.rs:663-664: the FIRST payload is hashed) and the local check s_i == f_parent_b (:168-176), in one batch:
-    every byte of the query section flipped once, decisions equal to the single verifier's."""
+    every fifth byte of the first three queries flipped once, decisions equal to the oracle's (the single call is this planner with one item: it is
+    compared too, but it is no independent witness)."""
     n0, sched, r = 64, [8, 8], 24
     proof = make_proof(oracle, n0, sched, r, 5)
     per_q = 8 + 2 * 32 + 8 + len(sched) * 32 + 8 + len(sched) * 128
@@ -74,9 +75,10 @@ def test_batch_first_payload_wins_and_local_check(oracle, hostcheck, tparams):
     batch = [proof]
     for pos in range(qbase, qbase + 3 * per_q, 5):
         bad = bytearray(proof); bad[pos] ^= 4; batch.append(bytes(bad))
-    want = [hostcheck.deep_fri_verify(tparams, p, sched, r) for p in batch]
+    want = [1 if oracle.deep_fri_verify(p, sched, r, SEED_Z) == 1 else 0 for p in batch]
     assert 1 < sum(want) < len(batch)
     assert verify_batch(hostcheck, tparams, batch, sched, r) == want
+    assert [hostcheck.deep_fri_verify(tparams, p, sched, r) for p in batch] == want
 
 
 def test_batch_empty(hostcheck, tparams):
