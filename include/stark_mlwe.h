@@ -85,6 +85,9 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  *   "ntt_batch_max_elems" (1..2^28, default 2^24: the output elements of one pass of stark_ntt_batch_dev / stark_lde_batch_dev).
  *   "mle_log_tile" (3..12, default 12; -1 restores the default: the rounds one launch of stark_mle_evaluate_dev / _batch_dev folds),
  *   "mle_lane_contiguous" (0 | 1, default 0; -1 restores the default: a lane of those launches owns consecutive elements instead of interleaved ones; comparison).
+ *   "pool_poison" (0..255, default -1 = off; FOR TESTS ONLY: every pooled block the library hands to itself, recycled or fresh, and the NTT scratch vector are
+ *   filled with this byte first, so a result that depends on a temporary nobody wrote changes with the byte.  Each fill synchronises the stream: the
+ *   calls that promise "no synchronisation" do synchronise while it is set.  The long-lived tables are not filled).
  * An unknown key is STARK_ERR_INVALID_ARG; stark_last_error then lists the known keys.
  * Changing an option synchronises the stream and drops the cached NTT plans. */
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value);

@@ -9,11 +9,21 @@ using namespace stark;
 
 namespace stark {
 
+// Option "pool_poison" (tests only): `bytes` at p become the fill byte before the allocator hands p out.  The fill is enqueued on the context's stream
+// and the host waits for it: a block allocated between ctx_fork and ctx_join is first touched on the SIDE stream, which is not ordered after a memset
+// enqueued later on the main one — because the allocator returns only once the fill has landed, every later launch on either stream sees it.
+static int32_t pool_poison_fill(stark_ctx* ctx, void* p, size_t bytes) {
+    STARK_HIP(ctx, hipMemsetAsync(p, ctx->opt.pool_poison, bytes, ctx->stream));
+    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return STARK_OK;
+}
+
 int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out) {
     if (bytes > ctx->scratch_bytes) {
         if (ctx->scratch) STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ctx->scratch_bytes = 0; STARK_HIP(ctx, ctx->scratch.alloc(bytes)); ctx->scratch_bytes = bytes;      // alloc frees the smaller block first
     }
+    if (ctx->opt.pool_poison >= 0 && ctx->scratch_bytes) STARK_TRY(pool_poison_fill(ctx, ctx->scratch.p, ctx->scratch_bytes));
     *out = ctx->scratch.p; return STARK_OK;
 }
 
@@ -44,7 +54,8 @@ int32_t ctx_alloc(stark_ctx* ctx, size_t bytes, void** out) {
     auto it = ctx->pool_free.find(sz);
     if (it != ctx->pool_free.end() && !it->second.empty()) {
         void* p = it->second.back(); it->second.pop_back(); ctx->pool_cached_bytes -= sz;
-        ctx->pool_live[p] = sz; *out = p; return STARK_OK;
+        ctx->pool_live[p] = sz; *out = p;
+        return ctx->opt.pool_poison >= 0 ? pool_poison_fill(ctx, p, sz) : STARK_OK;       // the whole rounded block, not only `bytes`
     }
     void* p = nullptr; hipError_t e = hipMalloc(&p, sz);
     if (e != hipSuccess) {                                       // out of memory: give the cached blocks back and retry once
@@ -55,7 +66,8 @@ int32_t ctx_alloc(stark_ctx* ctx, size_t bytes, void** out) {
         e = hipMalloc(&p, sz);
         if (e != hipSuccess) { (void)hipGetLastError(); return ctx->fail(STARK_ERR_OOM, "device allocation of " + std::to_string(sz) + " bytes failed"); }
     }
-    ctx->pool_live[p] = sz; *out = p; return STARK_OK;
+    ctx->pool_live[p] = sz; *out = p;
+    return ctx->opt.pool_poison >= 0 ? pool_poison_fill(ctx, p, sz) : STARK_OK;
 }
 void ctx_release(stark_ctx* ctx, void* p) {
     if (!p || !ctx) return;
@@ -219,6 +231,7 @@ static const OptionDef kOptions[] = {
     {"prove_batch_max_rows", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.prove_batch_max_rows = (size_t)v; return nullptr; }},
     {"mle_log_tile", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v != -1 && (v < 3 || v > 12)) return "3..12, or -1 for the default"; o.mle_log_tile = (int)v; return nullptr; }},
     {"mle_lane_contiguous", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 1) return "0 or 1, or -1 for the default"; o.mle_lane_contiguous = (int)v; return nullptr; }},
+    {"pool_poison", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 255) return "0..255, or -1 for off"; o.pool_poison = (int)v; return nullptr; }},
 };
 extern "C" {
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value) {

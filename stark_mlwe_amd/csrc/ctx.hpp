@@ -110,6 +110,8 @@ struct stark_ctx {
         size_t prove_batch_max_rows = (size_t)1 << 22;   // the batched DEEP-FRI provers cut a batch into passes of at most this many rows (traces x n0) whose tails run side by side (fri_batch.hpp); device memory per pass stays near 70 B per row
         int mle_log_tile = -1;           // log2 of the elements one workgroup of k_mle_fold_pass folds to one (3..12); -1 = the default of mle_dev.hpp
         int mle_lane_contiguous = -1;    // a lane of k_mle_fold_pass owns consecutive (1) or interleaved (0) elements; -1 = the default of mle_dev.hpp (comparison)
+        int pool_poison = -1;            // TESTS ONLY: 0..255 = ctx_alloc fills every block it hands out (the whole rounded block, recycled or fresh) and ctx_scratch the scratch vector
+                                         // with this byte, so a read of a temporary nobody wrote shows; each fill synchronises the stream.  -1 = off (one branch per allocation, no HIP call)
     } opt;
     bool side_commit = false;            // set while fri_build enqueues work that runs underneath the 2^n-leaf launch: Merkle levels and leaf layers of t = 9, 17 take the
                                          // wave-pair form (64 sponges per two waves) instead of one wave or five waves per sponge, which would hold many wave slots at lone-wave speed

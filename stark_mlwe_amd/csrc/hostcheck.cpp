@@ -27,6 +27,12 @@ using namespace stark;
 static fr_t ld4(const uint64_t* p) { fr_t x; for (int i = 0; i < 4; ++i) { x.v[2 * i] = (uint32_t)p[i]; x.v[2 * i + 1] = (uint32_t)(p[i] >> 32); } return x; }
 static void st4(uint64_t* p, const fr_t& x) { for (int i = 0; i < 4; ++i) p[i] = (uint64_t)x.v[2 * i] | ((uint64_t)x.v[2 * i + 1] << 32); }
 
+// What the host executors hand out as "device" memory holds this byte (hc_set_alloc_fill; 0 unless a test sets it), as the device allocator's blocks
+// do under the context option "pool_poison": a shared driver that reads a slot nothing filled reads this, not zero.
+static int g_alloc_fill = 0;
+static std::vector<uint64_t> hc_block(size_t bytes) { std::vector<uint64_t> v((bytes + 7) / 8 + 1); memset(v.data(), g_alloc_fill, v.size() * sizeof(uint64_t)); return v; }
+static std::vector<fr_t> hc_fr_block(size_t n) { std::vector<fr_t> v(n); if (n) memset((void*)v.data(), g_alloc_fill, n * sizeof(fr_t)); return v; }
+
 struct HcParams { host::PoseidonConsts ref; host::KernelConsts kc; PoseidonDev dev; };
 static void bind(HcParams* P) {
     P->kc = host::make_kernel_consts(P->ref);
@@ -38,6 +44,11 @@ static void bind(HcParams* P) {
 }
 
 extern "C" {
+
+// The byte of every block the host executors allocate from here on (process-wide; 0 = the default).  Returns the previous one; -1: not a byte.
+int hc_set_alloc_fill(int byte) { if (byte < 0 || byte > 255) return -1; const int old = g_alloc_fill; g_alloc_fill = byte; return old; }
+// A block of `bytes` through the executors' allocation path, copied out: what a driver would read from a slot nothing wrote.
+int hc_alloc_probe(size_t bytes, uint8_t* out) { const std::vector<uint64_t> v = hc_block(bytes); memcpy(out, v.data(), bytes); return 0; }
 
 // field: 0 Pallas, 1 BLS12-381.  op: 0 add, 1 sub, 2 mul, 3 inv, 4 from_u64(a[0]), 5 to_canonical, 6 root_of_unity(a[0]), 7 pow_u64(a, b[0]),
 // 8 the kernels' S-box fr_pow5_r29 (fr29.hpp: x^5 / 2^20)
@@ -336,6 +347,7 @@ static HcParamCache& hc_param_cache() { static HcParamCache c; return c; }
 // One plan: the leaf step (tparams: the transcript parameters; read only when the plan has leaves), then every (width, depth) group of gathered DS
 // hashes in depth order, then the per-item root comparisons.
 static void run_plan_host(VerifyBatchPlan V, const HcParams* tparams, int32_t* accepted) {
+    { std::vector<fr_t> dev = hc_fr_block(V.pool.size()); std::copy(V.pool.begin(), V.pool.begin() + V.n_known, dev.begin()); V.pool.swap(dev); }   // run_verify_batch uploads the known prefix only
     if (V.nl) {
         fr_t init[17]; leaf_init(init);
         const LeafStream LS{init, V.pool.data() + V.leaf_f0, V.pool.data() + V.leaf_f0 + V.nl, 1, V.nl};
@@ -388,7 +400,7 @@ int hc_merkle_verify(void* tparams, int pairs, size_t cfg_arity, uint64_t label,
 // ---- the batched sum-check provers (sumcheck_batch.hpp) through the host instantiation of the kernel bodies -------------------------
 struct ScHostExec {
     HcParams* cp; HcParams* tp; std::vector<std::vector<uint64_t>> mem;
-    int32_t alloc(size_t bytes, void** out) { mem.emplace_back((bytes + 7) / 8 + 1, 0); *out = mem.back().data(); return 0; }
+    int32_t alloc(size_t bytes, void** out) { mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
     int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
     int32_t download(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
     int32_t ds_level(const DsBatchStream& D, fr_t* out) {
@@ -473,9 +485,9 @@ int hc_sc_decode_fr(const uint8_t* blob, size_t len, size_t off, uint64_t* out4)
 int hc_sumcheck_verify_batch(void* tparams, void* cparams, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* labels, int32_t* accepted) {
     ScVerifyPlan V; if (sc_verify_plan(mf, batch, proofs, lens, labels, V)) return -1;
     HcParams *tp = (HcParams*)tparams, *cp = (HcParams*)cparams;
-    std::vector<fr_t> pool(std::max<size_t>(V.pool_slots, 1), host::h_zero());
+    std::vector<fr_t> pool = hc_fr_block(std::max<size_t>(V.pool_slots, 1));       // run_sc_verify_batch: the pool, the states and the cursors are not uploaded
     for (size_t j = 0; j < V.n_dec; ++j) if (!sc_decode_fr(V.blob.data(), V.dec_off[j], V.dec_proof[j], pool[j])) V.flag[V.dec_proof[j] & ~kScClaim] = 0;
-    std::vector<fr_t> state(17 * std::max<size_t>(V.n_inst, 1)); std::vector<uint32_t> pos(std::max<size_t>(V.n_inst, 1), 0u);
+    std::vector<fr_t> state = hc_fr_block(17 * std::max<size_t>(V.n_inst, 1)); std::vector<uint32_t> pos(std::max<size_t>(V.n_inst, 1), 0x01010101u * (uint32_t)g_alloc_fill);
     for (const ScVerifyPlan::Stream& S : V.tr) {
         TrBatchStream T; T.state = state.data(); T.pos = pos.data(); T.inst = nullptr; T.inst0 = S.inst0; T.n_active = S.n; T.nseg = S.nseg; T.el_off = V.tr_off.data() + S.seg0;
         T.idx = V.tr_idx.data(); T.pool0 = pool.data(); T.pool1 = V.consts.data(); T.out = pool.data() + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = 1; T.finish_last = 1;
@@ -507,7 +519,7 @@ struct FriHostExec {
     HcParams* tp; std::vector<std::vector<uint64_t>> mem;
     HcParamCache& mp;
     explicit FriHostExec(HcParams* t) : tp(t), mp(hc_param_cache()) {}
-    int32_t alloc(size_t bytes, void** out) { mem.emplace_back((bytes + 7) / 8 + 1, 0); *out = mem.back().data(); return 0; }
+    int32_t alloc(size_t bytes, void** out) { mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
     int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
     int32_t zpows(const fr_t& z, size_t m, fr_t* zp) { fr_t acc = fr_one<PF>(); for (size_t t = 0; t < m; ++t) { zp[t] = acc; acc = fr_mul<PF>(acc, z); } return 0; }
     int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out) {                                   // fri_fold_layer (fri.rs:85-102)
@@ -615,7 +627,7 @@ int hc_mle_evaluate_batch(size_t B, const uint64_t* const* tables, size_t k, con
     std::vector<fr_t> cur, nxt; size_t j0 = 0;
     for (size_t i = 0; i < rounds.size(); ++i) {
         const int t = rounds[i]; const uint64_t len = (uint64_t)1 << (k - j0);
-        nxt.assign(B * (len >> t), fr_zero<PF>());
+        nxt = hc_fr_block(B * (len >> t));                                                 // a pooled intermediate layer of the device driver
         switch (mle_local_rounds(t)) {
             case 0: mle_pass_host<0>(cg, B, i ? nullptr : ptrs.data(), cur.data(), len, t, rv.data(), k, j0, nxt.data()); break;
             case 1: mle_pass_host<1>(cg, B, i ? nullptr : ptrs.data(), cur.data(), len, t, rv.data(), k, j0, nxt.data()); break;
@@ -635,7 +647,9 @@ extern "C" int hc_mle_default_log_tile() { return kMleDefaultLogTile; }
 // ---- many Merkle trees in one pass (merkle_batch.hpp) through the host instantiation of the stream bodies -----------------------------------------
 struct MerkleHostExec {
     HcParams* p; std::vector<std::vector<uint64_t>> mem; std::vector<uint64_t> labels; std::vector<const fr_t*> lv, cpv;
-    int32_t level_block(size_t n_fr, fr_t** out) { mem.emplace_back(4 * n_fr + 1, 0xA5A5A5A5A5A5A5A5ull); *out = (fr_t*)mem.back().data(); return 0; }   // a block that held something before
+    int32_t level_block(size_t n_fr, fr_t** out) {                                   // a block that held something before: the fill of hc_set_alloc_fill, and never zeros
+        mem.emplace_back(4 * n_fr + 1, g_alloc_fill ? 0x0101010101010101ull * (uint64_t)g_alloc_fill : 0xA5A5A5A5A5A5A5A5ull); *out = (fr_t*)mem.back().data(); return 0;
+    }
     int32_t tables(const uint64_t* l, const fr_t* const* leaves, const fr_t* const* cp, size_t B, const uint64_t** lx, const fr_t* const** vx, const fr_t* const** cx) {
         labels.assign(l, l + B); lv.assign(leaves, leaves + B); if (cp) cpv.assign(cp, cp + B);
         *lx = labels.data(); *vx = lv.data(); *cx = cp ? cpv.data() : nullptr; return 0;

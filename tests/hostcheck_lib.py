@@ -22,6 +22,14 @@ class HostCheck:
         self.l = C.CDLL(PATH)
         self.l.hc_params_new.restype = vp
 
+    def set_alloc_fill(self, byte):
+        """the byte every block of the host executors holds from here on (process-wide; 0 is the default) -> the previous one"""
+        old = self.l.hc_set_alloc_fill(C.c_int(byte)); assert old >= 0, byte; return old
+
+    def alloc_probe(self, nbytes):
+        """a block of the host executors' allocation path as a driver would first see it"""
+        out = (C.c_uint8 * nbytes)(); assert self.l.hc_alloc_probe(C.c_size_t(nbytes), out) == 0; return bytes(out)
+
     def fr_op(self, field, op, a, b=None):
         out = np.zeros(4, np.uint64); assert self.l.hc_fr_op(field, op, P(A(a)), P(None if b is None else A(b)), P(out)) == 0; return out
 

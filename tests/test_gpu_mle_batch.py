@@ -203,7 +203,7 @@ def test_bad_arguments_are_refused_before_any_launch(gpu_ctx, oracle):
 
 def test_option_range_and_known_keys(gpu_ctx):
     from stark_mlwe_amd.api import StarkError
-    for key, bad in (("mle_log_tile", (2, 13, -2, 0)), ("mle_lane_contiguous", (2, -2))):
+    for key, bad in (("mle_log_tile", (2, 13, -2, 0)), ("mle_lane_contiguous", (2, -2)), ("pool_poison", (-2, 256))):
         for v in bad:
             with pytest.raises(StarkError) as e:
                 gpu_ctx.set_option(key, v)
@@ -212,4 +212,4 @@ def test_option_range_and_known_keys(gpu_ctx):
         gpu_ctx.set_option("mle_log_tile", v)
     with pytest.raises(StarkError) as e:
         gpu_ctx.set_option("no_such_option", 1)
-    assert "mle_log_tile" in str(e.value) and "mle_lane_contiguous" in str(e.value)
+    assert "mle_log_tile" in str(e.value) and "mle_lane_contiguous" in str(e.value) and "pool_poison" in str(e.value)
