@@ -1,6 +1,13 @@
 // stark_mlwe_amd/csrc/capi_fri.hip — FRI folding, fri_build_transcript, DEEP-ALI merge, build_f0 and
 // the end-to-end deep_fri_prove orchestration (host logic in C++ above the kernels, mirroring
 // crates/deep_ali/src/fri.rs and crates/deep_ali/src/lib.rs).  C-ABI in include/stark_mlwe.h.
+//
+// One trace is a batch of one.  Every prove — stark_deep_fri_prove_dev from columns or from f0, and the two batch entry points — is
+//   challenge_stage (columns only: all column sponges and Fiat-Shamir hashes of the batch, three synchronisations)
+//   -> prove_pass per pass of traces: PassCommit::run (layer 0 + commit phase, no synchronisation) -> batch_queries (four synchronisations).
+// Each of these is written once.  Only the commit phase has two forms — fri_build_impl for a pass of one trace, FriDevBatch (fri_batch.hpp) side
+// by side — and PassCommit::run is the one place that chooses; what follows reads either through a view (StateArrays / BatchArrays).  The
+// sharded prover (fri_shard_impl.hpp) shares the plan, the assembly and the row gather (merkle_batch.hpp: MerkleGatherList; gather_rows).
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -10,6 +17,7 @@
 #include "pow_table.hpp"
 #include "fri_dev.hpp"
 #include "fri_batch.hpp"
+#include "merkle_batch.hpp"
 
 using namespace stark;
 
@@ -210,18 +218,43 @@ static int32_t ali_challenges(stark_ctx* ctx, const fr_t h[4], size_t n0, fr_t* 
     fr_t fused; STARK_TRY(tr_hash_host1(ctx, "ALI/DEEP", {*seed_f, host::h_u64(n0)}, &fused));
     ali_z_beta_from_fused(fused, n0, *seed_f, z, beta); return STARK_OK;
 }
-// DeepAliRealBuilder::build_f0 (fri.rs:535-569), default builder: no blinding, ds_tag "ALI/DEEP".
+// The challenge stage of build_f0 (fri.rs:548-560, 511-533) for B traces of n0 rows; cols[4 p + c] = column c of trace p (device).  What bounds one
+// prove is the serial column sponge (n0 / 16 dependent permutations per column, one block each), and the chains of different traces are independent:
+// all 4 B of them run in ONE launch, and the two Fiat-Shamir hashes per trace ("ALI/seed", "ALI/DEEP") are one launch each for the batch.
+// THREE host synchronisations whatever B: the digests, the seeds, the fused hashes.  Per trace p: h[4 p ..], seed_f[p], z[p], beta[p].
+struct AliChallenges { std::vector<fr_t> h, seed_f, z, beta; };
+static int32_t challenge_stage(stark_ctx* ctx, size_t B, const fr_t* const* cols, size_t n0, AliChallenges& out) {
+    DevBuf dptr, dig, seeds_in, seeds, deep_in, fused;
+    STARK_HIP(ctx, dptr.alloc(ctx, 4 * B * sizeof(void*))); STARK_HIP(ctx, dig.alloc(ctx, 4 * B * sizeof(fr_t)));
+    STARK_HIP(ctx, hipMemcpyAsync(dptr.p, cols, 4 * B * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    const char* tags[4] = {"ALI/A", "ALI/S", "ALI/E", "ALI/T"};
+    STARK_TRY(tr_hash_columns_batch_dev(ctx, tags, (const fr_t* const*)dptr.p, B, n0, dig.fr()));
+    out.h.resize(4 * B);
+    STARK_HIP(ctx, hipMemcpyAsync(out.h.data(), dig.p, 4 * B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // seed_f = H("ALI/seed", [h_a, h_s, h_e, h_t, n0]) and the fused hash of ali_sample_z_beta_fs (fri.rs:556-557, 511-515)
+    const fr_t n0f = host::h_u64(n0);
+    std::vector<fr_t> in5(5 * B); for (size_t p = 0; p < B; ++p) { for (int c = 0; c < 4; ++c) in5[5 * p + c] = out.h[4 * p + c]; in5[5 * p + 4] = n0f; }
+    STARK_HIP(ctx, seeds_in.alloc(ctx, in5.size() * sizeof(fr_t))); STARK_HIP(ctx, seeds.alloc(ctx, B * sizeof(fr_t)));
+    STARK_HIP(ctx, hipMemcpyAsync(seeds_in.p, in5.data(), in5.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
+    STARK_TRY(tr_hash_dev(ctx, "ALI/seed", seeds_in.fr(), 5, B, seeds.fr()));
+    out.seed_f.resize(B);
+    STARK_HIP(ctx, hipMemcpyAsync(out.seed_f.data(), seeds.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<fr_t> in2(2 * B), fu(B); for (size_t p = 0; p < B; ++p) { in2[2 * p] = out.seed_f[p]; in2[2 * p + 1] = n0f; }
+    STARK_HIP(ctx, deep_in.alloc(ctx, in2.size() * sizeof(fr_t))); STARK_HIP(ctx, fused.alloc(ctx, B * sizeof(fr_t)));
+    STARK_HIP(ctx, hipMemcpyAsync(deep_in.p, in2.data(), in2.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
+    STARK_TRY(tr_hash_dev(ctx, "ALI/DEEP", deep_in.fr(), 2, B, fused.fr()));
+    STARK_HIP(ctx, hipMemcpyAsync(fu.data(), fused.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    out.z.resize(B); out.beta.resize(B);
+    for (size_t p = 0; p < B; ++p) ali_z_beta_from_fused(fu[p], n0, out.seed_f[p], &out.z[p], &out.beta[p]);
+    return STARK_OK;
+}
+// DeepAliRealBuilder::build_f0 (fri.rs:535-569), default builder: no blinding, ds_tag "ALI/DEEP": the challenge stage of one trace, then the merge.
 static int32_t build_f0_dev_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, size_t n0, fr_t* f0, fr_t* aux7) {
     if (n0 <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 > 1");
-    // four serial column sponges (fri.rs:551-554): one lane per column, inherently sequential in n0
-    DevBuf dig; STARK_HIP(ctx, dig.alloc(ctx, 4 * sizeof(fr_t)));
-    const fr_t* cols[4] = {a, s, e, t}; const char* tags[4] = {"ALI/A", "ALI/S", "ALI/E", "ALI/T"};
-    STARK_TRY(tr_hash_columns4_dev(ctx, tags, cols, n0, dig.fr()));           // the chains are independent: one launch, four concurrent blocks
-    fr_t h[4]; STARK_HIP(ctx, hipMemcpyAsync(h, dig.p, 4 * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    fr_t seed_f, z, beta; STARK_TRY(ali_challenges(ctx, h, n0, &seed_f, &z, &beta));
-    if (aux7) { for (int c = 0; c < 4; ++c) aux7[c] = h[c]; aux7[4] = seed_f; aux7[5] = z; aux7[6] = beta; }
+    const fr_t* cols[4] = {a, s, e, t}; AliChallenges ch; STARK_TRY(challenge_stage(ctx, 1, cols, n0, ch));
+    if (aux7) { for (int c = 0; c < 4; ++c) aux7[c] = ch.h[c]; aux7[4] = ch.seed_f[0]; aux7[5] = ch.z[0]; aux7[6] = ch.beta[0]; }
     fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));         // FriDomain::new_radix2(n0).omega (fri.rs:53-56); Radix2EvaluationDomain::new rounds n0 up to a power of two, as ilog2 does
-    return ali_merge_dev_impl(ctx, a, s, e, t, nullptr, host::h_zero(), omega, z, n0, f0, nullptr);
+    return ali_merge_dev_impl(ctx, a, s, e, t, nullptr, host::h_zero(), omega, ch.z[0], n0, f0, nullptr);
 }
 
 // The transcript hasher of the query phase (fri_plan.hpp) on the device.
@@ -266,130 +299,46 @@ static int32_t assemble_from_values(stark_ctx* ctx, const FriShape& shape, size_
     const int32_t rc = assemble_proof(shape, r, H, rep, P->bytes, P->size_estimate);
     return rc == -1 || (rc == 0 && rep.pos != n) ? ctx->fail(STARK_ERR_INVALID_ARG, mismatch) : rc;
 }
-// The opened values of a query phase, fetched with ONE launch of k_gather_rows over a table of source arrays: add() records that `row` of the output
-// table is src[index], launch() uploads the four tables and gathers.  The object owns the host sources of those uploads, so it lives until the
-// caller's next synchronisation of the context's stream (synced()); destroyed with uploads pending — an early error return — it synchronises first
-// (the rule of FriDevExec).
-struct OpeningGather {
-    stark_ctx* ctx; std::vector<const fr_t*> base; std::map<const fr_t*, uint32_t> slot; std::vector<uint32_t> src; std::vector<uint64_t> idx, row;
-    DevBuf db, ds, di, dr; bool pending = false;
-    explicit OpeningGather(stark_ctx* c) : ctx(c) {}
-    OpeningGather(const OpeningGather&) = delete; OpeningGather& operator=(const OpeningGather&) = delete;
-    ~OpeningGather() { if (pending) (void)hipStreamSynchronize(ctx->stream); }
-    void synced() { pending = false; }                  // the caller has synchronised the context's stream
-    size_t size() const { return src.size(); }
-    int32_t add(const fr_t* from, size_t len, uint64_t index, uint64_t to_row) {
-        if (index >= len) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: opening index out of range");
-        auto it = slot.emplace(from, (uint32_t)base.size()).first;
-        if (it->second == base.size()) base.push_back(from);
-        src.push_back(it->second); idx.push_back(index); row.push_back(to_row); return STARK_OK;
-    }
-    int32_t launch(fr_t* out) {
-        const size_t k = src.size();
-        if (!k) return STARK_OK;
-        pending = true;
-        STARK_HIP(ctx, db.upload(ctx, base.data(), base.size() * sizeof(void*))); STARK_HIP(ctx, ds.upload(ctx, src.data(), k * 4));
-        STARK_HIP(ctx, di.upload(ctx, idx.data(), k * 8)); STARK_HIP(ctx, dr.upload(ctx, row.data(), k * 8));
-        hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)db.p, (const uint32_t*)ds.p, (const uint64_t*)di.p,
-                           (const uint64_t*)dr.p, (uint64_t)k, out);
-        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
-    }
-};
-// Where a request reads when the whole commit phase of its proof is on this GPU: `c` names the layers and tree levels
-// (layers(); layer(l, &len); levels(l); level(l, v, &len)), and the range checks are written here.
-template <class Commit> static int32_t resolve_opening(stark_ctx* ctx, const Commit& c, const FriRequest& q, const fr_t** from, size_t* len) {
+// One opened value of a query phase: row `to_row` of the gathered table is from[index] (the one row gather: MerkleGatherList, gather_rows).
+static int32_t add_opening(stark_ctx* ctx, MerkleGatherList& G, const fr_t* from, size_t len, uint64_t index, uint64_t to_row) {
+    if (index >= len) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: opening index out of range");
+    G.add(from, index, to_row); return STARK_OK;
+}
+// Where a request of trace b reads when the whole commit phase of its pass is on this GPU: `c` names the layers and tree levels
+// (layers(); layer(b, l, &len); levels(l); level(b, l, v, &len)), and the range checks are written here.
+template <class Commit> static int32_t resolve_opening(stark_ctx* ctx, const Commit& c, size_t b, const FriRequest& q, const fr_t** from, size_t* len) {
     if (q.kind == 0) {
         if (q.which >= c.layers()) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range");
-        *from = c.layer(q.which, len); return STARK_OK;
+        *from = c.layer(b, q.which, len); return STARK_OK;
     }
     if (q.which >= c.layers() || q.level >= c.levels(q.which)) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
-    *from = c.level(q.which, q.level, len); return STARK_OK;
+    *from = c.level(b, q.which, q.level, len); return STARK_OK;
 }
-struct StateArrays {                                    // a stark_fri_state
-    const stark_fri_state* S;
+// The two views the query phase reads a commit phase through.  Besides the arrays each says how its (L + 1) x traces() roots reach the host
+// (roots_host: rt[b (L + 1) + l], one download and one synchronisation).
+struct StateArrays {                                    // a stark_fri_state: one trace
+    stark_fri_state* S;
+    size_t traces() const { return 1; }
     size_t layers() const { return S->f.size(); }
-    const fr_t* layer(size_t l, size_t* len) const { *len = S->n[l]; return S->f[l]; }
+    const fr_t* layer(size_t, size_t l, size_t* len) const { *len = S->n[l]; return S->f[l]; }
     size_t levels(size_t l) const { return S->trees[l]->levels.size(); }
-    const fr_t* level(size_t l, size_t v, size_t* len) const { *len = S->trees[l]->lens[v]; return S->trees[l]->levels[v]; }
+    const fr_t* level(size_t, size_t l, size_t v, size_t* len) const { *len = S->trees[l]->lens[v]; return S->trees[l]->levels[v]; }
+    int32_t roots_host(stark_ctx*, std::vector<fr_t>& rt) const { STARK_TRY(state_roots(S)); rt = S->roots; return STARK_OK; }
 };
-// fri_prove_queries + payload assembly + canonical encoding (fri.rs:355-466, 613-640).  The indices of every opened value depend
-// only on the roots, so the query phase first RECORDS what it will read (fri_plan.hpp: the same code against a recording source),
-// fetches all of it — a few thousand layer elements and tree nodes spread over every layer and level — with ONE gather launch and
-// one download, and then assembles the proof from that list.  (One synchronisation instead of one per opened level.)
-static int32_t prove_queries_encode(stark_ctx* ctx, stark_fri_state* S, size_t n0, size_t r, stark_proof* P) {
-    STARK_TRY(state_roots(S));
-    DeviceHasher H0(ctx); MemoHasher H(H0);
-    FriPlan plan; STARK_TRY(make_query_plan(ctx, plan, n0, S->schedule.data(), S->schedule.size(), S->roots.data(), r, H));
-    const size_t nreq = plan.req.size();
-    std::vector<fr_t> vals(nreq);
-    if (nreq) {
-        OpeningGather G(ctx); const StateArrays A{S};
-        for (size_t i = 0; i < nreq; ++i) { const fr_t* from; size_t len; STARK_TRY(resolve_opening(ctx, A, plan.req[i], &from, &len)); STARK_TRY(G.add(from, len, plan.req[i].index, i)); }
-        DevBuf dout; STARK_HIP(ctx, dout.alloc(ctx, nreq * sizeof(fr_t)));
-        STARK_TRY(G.launch(dout.fr()));
-        STARK_HIP(ctx, dout.download_sync(vals.data(), nreq * sizeof(fr_t))); G.synced();
-    }
-    return assemble_from_values(ctx, plan.shape, r, H, vals.data(), nreq, P);
-}
 
 // Query plan of a commit phase whose layers live elsewhere (sharded over ranks): see fri_plan.hpp.
 struct stark_fri_plan { CtxRef ref_; stark_ctx* ctx = nullptr; FriPlan plan; };
 
-// The prove once f0 is known: commit phase, query phase, stage times.  The first stage is stage0_ms plus what has passed since t_start (the
-// caller's own work on f0: build_f0, a merge, or nothing).
-static int32_t prove_from_f0(stark_ctx* ctx, const fr_t* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double stage0_ms,
-                             Clock::time_point t_start, stark_proof** out) {
-    const auto t1 = Clock::now();
-    std::unique_ptr<stark_fri_state> S; { stark_fri_state* s = nullptr; STARK_TRY(fri_build_impl(ctx, f0, n0, schedule, L, seed_z, &s)); S.reset(s); }
-    const auto t2 = Clock::now();
-    std::unique_ptr<stark_proof> P(new stark_proof());
-    { const int32_t rc = prove_queries_encode(ctx, S.get(), n0, r, P.get()); S.reset(); if (rc) return rc; }
-    const auto t3 = Clock::now();
-    P->ms[0] = stage0_ms + ms_between(t_start, t1); P->ms[1] = ms_between(t1, t2); P->ms[2] = ms_between(t2, t3);
-    *out = P.release(); return STARK_OK;
-}
-static int32_t prove_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t* f0_in, size_t n0,
-                          const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
-    if (!is_pow2(n0)) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two (radix-2 domain)");
-    const auto t0 = Clock::now();
-    DevBuf f0buf; const fr_t* f0 = f0_in;
-    if (!f0) {
-        if (f0buf.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "f0");
-        STARK_TRY(build_f0_dev_impl(ctx, a, s, e, t, n0, f0buf.fr(), nullptr));
-        f0 = f0buf.fr();
-    }
-    return prove_from_f0(ctx, f0, n0, schedule, L, r, seed_z, 0.0, t0, out);
-}
-// The tail of ONE trace of a batch prove (a pass of one trace), its challenge z known: the merge into f0, then the prove from f0.
-// stage_ms: shared_ms (the batch's sponge stage) + the merge, the commit phase, the query phase.
-static int32_t prove_tail_single(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, const fr_t& omega, const fr_t& z, size_t n0,
-                                 const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, stark_proof** out) {
-    DevBuf f0buf; if (f0buf.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "f0");
-    const auto u0 = Clock::now();
-    STARK_TRY(ali_merge_dev_impl(ctx, a, s, e, t, nullptr, host::h_zero(), omega, z, n0, f0buf.fr(), nullptr));
-    return prove_from_f0(ctx, f0buf.fr(), n0, schedule, L, r, seed_z, shared_ms, u0, out);
-}
-
-// ---- the side-by-side tail of the batched provers: merge, commit phase and query phase of a pass of traces (fri_batch.hpp) ----------------
+// ---- a pass of traces: the side-by-side commit (fri_batch.hpp), the query phase, the pass function and the batch drivers over them ----------
 // The executor of FriBatchCommit on the device.  Everything it allocates is pooled and returns to the pool with it; the folds run on the
 // context's stream, the commitments on the current one (the side stream between fork() and side(false)).
 struct FriDevExec {
     stark_ctx* ctx; hipStream_t main_st, side_st = nullptr, cur; std::vector<void*> blocks; bool forked = false;
-    // Host sources of the uploads: every upload goes out of a copy the executor owns, so a caller's table may die as soon as upload() returns.  The
-    // copies live until the executor does; if it is destroyed with uploads enqueued since the caller's last synchronisation (an early error return),
-    // it synchronises the stream first.
-    std::vector<std::unique_ptr<uint8_t[]>> staged; bool pending = false;
     explicit FriDevExec(stark_ctx* c) : ctx(c), main_st(c->stream), cur(c->stream) {}
     FriDevExec(const FriDevExec&) = delete; FriDevExec& operator=(const FriDevExec&) = delete;
-    ~FriDevExec() { if (forked) (void)hipStreamSynchronize(side_st); if (pending) (void)hipStreamSynchronize(main_st); for (void* p : blocks) ctx_release(ctx, p); }
-    void synced() { pending = false; }                  // the caller has synchronised the context's stream
+    ~FriDevExec() { if (forked) (void)hipStreamSynchronize(side_st); for (void* p : blocks) ctx_release(ctx, p); }
     int32_t alloc(size_t bytes, void** out) { STARK_TRY(ctx_alloc(ctx, bytes, out)); blocks.push_back(*out); return STARK_OK; }
-    int32_t upload(void* dst, const void* src, size_t bytes) {
-        if (!bytes) return STARK_OK;
-        staged.emplace_back(new uint8_t[bytes]); memcpy(staged.back().get(), src, bytes);
-        pending = true;
-        STARK_HIP(ctx, hipMemcpyAsync(dst, staged.back().get(), bytes, hipMemcpyHostToDevice, main_st)); return STARK_OK;
-    }
+    int32_t upload(void* dst, const void* src, size_t bytes) { return ctx_upload_staged(ctx, dst, src, bytes); }     // the context owns the host copy: src may die on return
     template <class T> int32_t put(const std::vector<T>& h, T** out) {
         void* p = nullptr; STARK_TRY(alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p));
         if (!h.empty()) STARK_TRY(upload(p, h.data(), h.size() * sizeof(T)));
@@ -438,13 +387,9 @@ static int32_t ali_merge_batch_launch(stark_ctx* ctx, FriDevExec& X, size_t Bp, 
     }
     return STARK_OK;
 }
-// The query phase of every proof of a pass (prove_queries_encode, side by side).  FOUR host synchronisations, whatever Bp: the roots; the Bp
-// "FRI/seed" hashes (one launch); the Bp * r * L "FRI/index" hashes (one launch); the opened values of all proofs (one gather launch).  The seeds
-// are pre-loaded into each proof's MemoHasher, so fri_plan_make and assemble_proof run per proof without touching the device (the reseed of
-// fri.rs:379-381 cannot occur with power-of-two layers; it alone would go through the single hasher: ReseedOnlyHasher).
-// What a proof's MemoHasher of the batched query phase may still ask the device for: the reseed alone.  Anything else was to be pre-loaded; a request
-// for it means the pre-loaded keys no longer match what fri_plan.hpp asks for, and is an error rather than a silent launch and synchronisation per proof
-// (the constant of four synchronisations per pass rests on this).
+// What a proof's MemoHasher of the query phase may still ask the device for: the reseed of fri.rs:379-381 alone (it cannot occur with power-of-two
+// layers).  Anything else was to be pre-loaded; a request for it means the pre-loaded keys no longer match what fri_plan.hpp asks for, and is an error
+// rather than a silent launch and synchronisation per proof (the constant of four synchronisations per pass rests on this).
 struct ReseedOnlyHasher : TrHasher {
     DeviceHasher dev; explicit ReseedOnlyHasher(stark_ctx* c) : dev(c) {}
     int32_t hash(const char* tag, const fr_t* fields, size_t k, size_t n, fr_t* out) override {
@@ -452,47 +397,56 @@ struct ReseedOnlyHasher : TrHasher {
         return dev.hash(tag, fields, k, n, out);
     }
 };
-struct BatchArrays {                                    // trace b of a pass (resolve_opening)
-    const FriDevBatch& C; size_t b;
+struct BatchArrays {                                    // the traces of a side-by-side pass
+    const FriDevBatch& C;
+    size_t traces() const { return C.Bp; }
     size_t layers() const { return C.L + 1; }
-    const fr_t* layer(size_t l, size_t* len) const { *len = C.n[l]; return C.layer_at(b, l); }
+    const fr_t* layer(size_t b, size_t l, size_t* len) const { *len = C.n[l]; return C.layer_at(b, l); }
     size_t levels(size_t l) const { return C.trees[l].levels.size(); }
-    const fr_t* level(size_t l, size_t v, size_t* len) const { *len = C.trees[l].lens[v]; return C.level_at(b, l, v); }
+    const fr_t* level(size_t b, size_t l, size_t v, size_t* len) const { *len = C.trees[l].lens[v]; return C.level_at(b, l, v); }
+    int32_t roots_host(stark_ctx* ctx, std::vector<fr_t>& rt) const {
+        const size_t Bp = C.Bp, R = C.L + 1; std::vector<fr_t> rl(R * Bp);                                               // C.roots is layer-major
+        STARK_HIP(ctx, hipMemcpyAsync(rl.data(), C.roots, rl.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        rt.resize(R * Bp); for (size_t b = 0; b < Bp; ++b) for (size_t l = 0; l < R; ++l) rt[b * R + l] = rl[l * Bp + b];
+        return STARK_OK;
+    }
 };
-static int32_t batch_queries(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, size_t n0, size_t r, stark_proof** out) {
-    const size_t Bp = C.Bp, L = C.L, R = L + 1, q = r * L;
-    std::vector<fr_t> rl(R * Bp), rt(R * Bp), seed(Bp), in(3 * q * Bp), idx(q * Bp);
-    STARK_HIP(ctx, hipMemcpyAsync(rl.data(), C.roots, rl.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (size_t b = 0; b < Bp; ++b) for (size_t l = 0; l < R; ++l) rt[b * R + l] = rl[l * Bp + b];
-    fr_t *d_rt = nullptr, *d_seed = nullptr; STARK_TRY(X.put(rt, &d_rt)); { void* p = nullptr; STARK_TRY(X.alloc(Bp * sizeof(fr_t), &p)); d_seed = (fr_t*)p; }
-    STARK_TRY(tr_hash_dev(ctx, "FRI/seed", d_rt, R, Bp, d_seed));                                                        // fs_seed_from_roots, fri.rs:178
-    STARK_HIP(ctx, hipMemcpyAsync(seed.data(), d_seed, Bp * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+// THE query phase: fri_prove_queries + payload assembly + canonical encoding (fri.rs:355-466, 613-640) of every proof of a pass, read through the
+// view V of its commit phase (one trace: StateArrays; side by side: BatchArrays).  The indices of every opened value depend only on the roots, so
+// the phase first RECORDS what it will read (fri_plan.hpp: the same code against a recording source), fetches all of it — layer elements and tree
+// nodes spread over every layer and level of every proof — with ONE gather, and then assembles the proofs from that list.  FOUR host
+// synchronisations, whatever the number of traces: the roots; the "FRI/seed" hashes (one launch); the r * L "FRI/index" hashes per proof (one
+// launch; none when r * L = 0); the opened values (one gather launch; none when nothing is opened).  Seeds and index seeds are pre-loaded into each
+// proof's MemoHasher, so fri_plan_make and assemble_proof run per proof without touching the device (ReseedOnlyHasher).
+template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V, size_t n0, const size_t* schedule, size_t L, size_t r, stark_proof** out) {
+    const size_t Bp = V.traces(), R = L + 1, q = r * L;
+    std::vector<fr_t> rt, seed(Bp), in(3 * q * Bp), idx(q * Bp);
+    STARK_TRY(V.roots_host(ctx, rt));
+    DevBuf d_rt, d_seed, d_in, d_idx;
+    STARK_HIP(ctx, d_rt.alloc(ctx, rt.size() * sizeof(fr_t))); STARK_HIP(ctx, d_seed.alloc(ctx, Bp * sizeof(fr_t)));
+    STARK_TRY(ctx_upload_staged(ctx, d_rt.p, rt.data(), rt.size() * sizeof(fr_t)));
+    STARK_TRY(tr_hash_dev(ctx, "FRI/seed", d_rt.fr(), R, Bp, d_seed.fr()));                                               // fs_seed_from_roots, fri.rs:178
+    STARK_HIP(ctx, d_seed.download_sync(seed.data(), Bp * sizeof(fr_t)));
     if (q) {                                                                                                             // the index seeds of all (proof, query, layer): fri.rs:374, :189-191
         for (size_t b = 0; b < Bp; ++b) for (size_t j = 0; j < r; ++j) for (size_t l = 0; l < L; ++l) { fr_t* p = &in[3 * (b * q + j * L + l)]; p[0] = seed[b]; p[1] = host::h_u64(l); p[2] = host::h_u64(j); }
-        fr_t *d_in = nullptr, *d_idx = nullptr; STARK_TRY(X.put(in, &d_in)); { void* p = nullptr; STARK_TRY(X.alloc(q * Bp * sizeof(fr_t), &p)); d_idx = (fr_t*)p; }
-        STARK_TRY(tr_hash_dev(ctx, "FRI/index", d_in, 3, q * Bp, d_idx));
-        STARK_HIP(ctx, hipMemcpyAsync(idx.data(), d_idx, q * Bp * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        STARK_HIP(ctx, d_in.alloc(ctx, in.size() * sizeof(fr_t))); STARK_HIP(ctx, d_idx.alloc(ctx, q * Bp * sizeof(fr_t)));
+        STARK_TRY(ctx_upload_staged(ctx, d_in.p, in.data(), in.size() * sizeof(fr_t)));
+        STARK_TRY(tr_hash_dev(ctx, "FRI/index", d_in.fr(), 3, q * Bp, d_idx.fr()));
+        STARK_HIP(ctx, d_idx.download_sync(idx.data(), q * Bp * sizeof(fr_t)));
     }
     ReseedOnlyHasher H0(ctx); std::vector<std::unique_ptr<MemoHasher>> H(Bp); std::vector<FriPlan> plan(Bp);
     std::vector<size_t> row0(Bp + 1, 0);
-    OpeningGather G(ctx);                                                                                                // row: the running count over all proofs
+    MerkleGatherList G;                                                                                                  // row: the running count over all proofs
     for (size_t b = 0; b < Bp; ++b) {
         H[b].reset(new MemoHasher(H0));
         H[b]->preload("FRI/seed", &rt[b * R], R, 1, &seed[b]);
         if (q) H[b]->preload("FRI/index", &in[3 * q * b], 3, q, &idx[q * b]);
-        STARK_TRY(make_query_plan(ctx, plan[b], n0, C.sched.data(), L, &rt[b * R], r, *H[b]));
-        const BatchArrays A{C, b};
-        for (const FriRequest& rq : plan[b].req) { const fr_t* from; size_t len; STARK_TRY(resolve_opening(ctx, A, rq, &from, &len)); STARK_TRY(G.add(from, len, rq.index, G.size())); }
+        STARK_TRY(make_query_plan(ctx, plan[b], n0, schedule, L, &rt[b * R], r, *H[b]));
+        for (const FriRequest& rq : plan[b].req) { const fr_t* from; size_t len; STARK_TRY(resolve_opening(ctx, V, b, rq, &from, &len)); STARK_TRY(add_opening(ctx, G, from, len, rq.index, G.size())); }
         row0[b + 1] = G.size();
     }
-    const size_t k = G.size();
-    std::vector<fr_t> vals(k);
-    if (k) {                                                                                                             // ONE gather over all proofs' requests, one download
-        void* d_out = nullptr; STARK_TRY(X.alloc(k * sizeof(fr_t), &d_out));
-        STARK_TRY(G.launch((fr_t*)d_out));
-        STARK_HIP(ctx, hipMemcpyAsync(vals.data(), d_out, k * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); X.synced(); G.synced();
+    std::vector<fr_t> vals(G.size());
+    STARK_TRY(gather_rows(ctx, G, nullptr, vals.data()));                                                                // ONE gather over all proofs' requests, one download
     for (size_t b = 0; b < Bp; ++b) {
         std::unique_ptr<stark_proof> P(new stark_proof());
         const int32_t rc = assemble_from_values(ctx, plan[b].shape, r, *H[b], vals.data() + row0[b], row0[b + 1] - row0[b], P.get());
@@ -501,41 +455,63 @@ static int32_t batch_queries(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, size
     }
     return STARK_OK;
 }
-// The tail of one pass of Bp >= 2 traces: layer 0 of every trace from the batched merge (cols: host tables of device pointers a, s, e, t with
-// the traces' z on the host) or from given f0 (a host table of device pointers), then the commit phase and the query phase side by side.
-// Host synchronisations per pass: the FOUR of batch_queries, independent of Bp (merge and commit phase only enqueue).  stage_ms of every proof
-// of the pass: shared_ms + the pass's merge, the pass's commit, the pass's queries.
-static int32_t prove_pass_batch(stark_ctx* ctx, size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, size_t n0,
-                                const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, stark_proof** out) {
-    auto u0 = Clock::now();
-    FriDevExec X(ctx); FriDevBatch C(X);
-    STARK_TRY(batch_commit_begin(ctx, C, Bp, n0, schedule, L, seed_z));
-    std::vector<const fr_t*> tab; std::vector<fr_t> zv;
-    if (f0) STARK_TRY(batch_fill_layer0(ctx, X, C, f0));
-    else {
-        for (size_t b = 0; b < Bp; ++b) if (fr_eq(fr_pow_u64<PallasFr>(zs[b], n0), host::h_one())) return ctx->fail(STARK_ERR_INVALID_ARG, "z must be outside H");   // lib.rs:78
-        tab.resize(4 * Bp); for (int c = 0; c < 4; ++c) for (size_t b = 0; b < Bp; ++b) tab[c * Bp + b] = as_fr(cols[c][b]);
-        zv.assign(zs, zs + Bp);
-        const fr_t** d_tab = nullptr; fr_t* d_z = nullptr; STARK_TRY(X.put(tab, &d_tab)); STARK_TRY(X.put(zv, &d_z));
+// Layer 0 and the commit phase of one pass of Bp >= 1 traces, in the two forms of the commit, chosen HERE and nowhere else:
+//   one trace      fri_build_impl — the stark_fri_state that stark_fri_build_dev hands out and the benchmark step runs through, and the only
+//                  commit whose levels are DsStreams (k_node16_pair, the "fri_side_pair" form); layer 0 is the caller's f0 or ali_merge_dev_impl's;
+//   side by side   FriDevBatch (fri_batch.hpp) — layer 0 of every trace from one copy kernel or the batched merge.
+// Neither form synchronises the host.  Whatever reads the result goes through with_view and does not know which form ran.
+struct PassCommit {
+    stark_ctx* ctx; FriDevExec X; FriDevBatch C; std::unique_ptr<stark_fri_state> S;
+    explicit PassCommit(stark_ctx* c) : ctx(c), X(c), C(X) {}
+    // cols: host tables of device pointers a, s, e, t with the traces' z on the host (zs), or f0: a host table of device pointers.  *t_layer0 (optional): when layer 0 was enqueued.
+    int32_t run(size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z,
+                Clock::time_point* t_layer0) {
         const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));
-        STARK_TRY(ali_merge_batch_launch(ctx, X, Bp, d_tab, d_tab + Bp, d_tab + 2 * Bp, d_tab + 3 * Bp, nullptr, nullptr, omega, d_z, n0, C.f[0], nullptr, nullptr));
+        if (Bp == 1) {
+            DevBuf merged; const fr_t* f = f0 ? as_fr(f0[0]) : nullptr;
+            if (!f) {
+                if (merged.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "f0");
+                STARK_TRY(ali_merge_dev_impl(ctx, as_fr(cols[0][0]), as_fr(cols[1][0]), as_fr(cols[2][0]), as_fr(cols[3][0]), nullptr, host::h_zero(), omega, zs[0], n0, merged.fr(), nullptr));
+                f = merged.fr();
+            }
+            if (t_layer0) *t_layer0 = Clock::now();
+            stark_fri_state* s = nullptr; STARK_TRY(fri_build_impl(ctx, f, n0, schedule, L, seed_z, &s)); S.reset(s);       // copies f: `merged` returns to the pool behind that copy
+            return STARK_OK;
+        }
+        STARK_TRY(batch_commit_begin(ctx, C, Bp, n0, schedule, L, seed_z));
+        if (f0) STARK_TRY(batch_fill_layer0(ctx, X, C, f0));
+        else {
+            for (size_t b = 0; b < Bp; ++b) if (fr_eq(fr_pow_u64<PallasFr>(zs[b], n0), host::h_one())) return ctx->fail(STARK_ERR_INVALID_ARG, "z must be outside H");   // lib.rs:78
+            std::vector<const fr_t*> tab(4 * Bp); for (int c = 0; c < 4; ++c) for (size_t b = 0; b < Bp; ++b) tab[c * Bp + b] = as_fr(cols[c][b]);
+            const fr_t** d_tab = nullptr; fr_t* d_z = nullptr; STARK_TRY(X.put(tab, &d_tab)); STARK_TRY(X.put(std::vector<fr_t>(zs, zs + Bp), &d_z));
+            STARK_TRY(ali_merge_batch_launch(ctx, X, Bp, d_tab, d_tab + Bp, d_tab + 2 * Bp, d_tab + 3 * Bp, nullptr, nullptr, omega, d_z, n0, C.f[0], nullptr, nullptr));
+        }
+        if (t_layer0) *t_layer0 = Clock::now();
+        return C.run();
     }
-    auto u1 = Clock::now();
-    STARK_TRY(C.run());
-    auto u2 = Clock::now();
-    STARK_TRY(batch_queries(ctx, X, C, n0, r, out));
-    auto u3 = Clock::now();
+    template <class F> int32_t with_view(F f) const { return S ? f(StateArrays{S.get()}) : f(BatchArrays{C}); }
+};
+// One pass of a batch prove: layer 0 -> commit phase -> query phase -> stage times.  Host synchronisations per pass: the FOUR of batch_queries, whatever
+// Bp (layer 0 and the commit phase only enqueue).  stage_ms of every proof of the pass: shared_ms + the pass's layer 0, its commit, its queries.
+static int32_t prove_pass(stark_ctx* ctx, size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, size_t n0,
+                          const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, stark_proof** out) {
+    const auto u0 = Clock::now(); auto u1 = u0;
+    PassCommit P(ctx);
+    STARK_TRY(P.run(Bp, cols, zs, f0, n0, schedule, L, seed_z, &u1));
+    const auto u2 = Clock::now();
+    const int32_t rc = P.with_view([&](const auto& V) { return batch_queries(ctx, V, n0, schedule, L, r, out); });
+    P.S.reset();                                                                            // a single state's layers and trees go back to the pool here, before the proofs are handed out
+    if (rc) return rc;
+    const auto u3 = Clock::now();
     for (size_t b = 0; b < Bp; ++b) { out[b]->ms[0] = shared_ms + ms_between(u0, u1); out[b]->ms[1] = ms_between(u1, u2); out[b]->ms[2] = ms_between(u2, u3); }
     return STARK_OK;
 }
 static void free_proofs(stark_proof** out, size_t B) { for (size_t p = 0; p < B; ++p) if (out[p]) { delete out[p]; out[p] = nullptr; } }
-// stark_deep_fri_prove_f0_batch_dev: the batch cut into passes of at most "prove_batch_max_rows" rows; a pass of one trace is the single prove.
+// stark_deep_fri_prove_f0_batch_dev, and stark_deep_fri_prove_dev given f0 with B = 1: the batch cut into passes of at most "prove_batch_max_rows" rows.
 static int32_t prove_f0_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
     const size_t per = pass_traces(ctx, n0);
     for (size_t p0 = 0; p0 < B; p0 += per) {
-        const size_t Bp = std::min(per, B - p0);
-        const int32_t rc = Bp == 1 ? prove_from_f0(ctx, as_fr(f0[p0]), n0, schedule, L, r, seed_z, 0.0, Clock::now(), &out[p0])
-                                   : prove_pass_batch(ctx, Bp, nullptr, nullptr, f0 + p0, n0, schedule, L, r, seed_z, 0.0, out + p0);
+        const int32_t rc = prove_pass(ctx, std::min(per, B - p0), nullptr, nullptr, f0 + p0, n0, schedule, L, r, seed_z, 0.0, out + p0);
         if (rc) { free_proofs(out, B); return rc; }
     }
     return STARK_OK;
@@ -545,19 +521,10 @@ static int32_t commit_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const
     const size_t per = pass_traces(ctx, n0), R = L + 1;
     for (size_t p0 = 0; p0 < B; p0 += per) {
         const size_t Bp = std::min(per, B - p0);
-        if (Bp == 1) {                                                                          // a pass of one trace: the single commit phase
-            std::unique_ptr<stark_fri_state> S; { stark_fri_state* s = nullptr; STARK_TRY(fri_build_impl(ctx, as_fr(f0[p0]), n0, schedule, L, seed_z, &s)); S.reset(s); }
-            STARK_TRY(state_roots(S.get()));
-            for (size_t l = 0; l < R; ++l) store_fr(roots + 4 * (p0 * R + l), S->roots[l]);
-            continue;
-        }
-        FriDevExec X(ctx); FriDevBatch C(X);
-        STARK_TRY(batch_commit_begin(ctx, C, Bp, n0, schedule, L, seed_z));
-        STARK_TRY(batch_fill_layer0(ctx, X, C, f0 + p0));
-        STARK_TRY(C.run());
-        std::vector<fr_t> rl(R * Bp);
-        STARK_HIP(ctx, hipMemcpyAsync(rl.data(), C.roots, rl.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); X.synced();
-        for (size_t b = 0; b < Bp; ++b) for (size_t l = 0; l < R; ++l) store_fr(roots + 4 * ((p0 + b) * R + l), rl[l * Bp + b]);
+        PassCommit P(ctx); std::vector<fr_t> rt;
+        STARK_TRY(P.run(Bp, nullptr, nullptr, f0 + p0, n0, schedule, L, seed_z, nullptr));
+        STARK_TRY(P.with_view([&](const auto& V) { return V.roots_host(ctx, rt); }));
+        for (size_t i = 0; i < Bp * R; ++i) store_fr(roots + 4 * (p0 * R + i), rt[i]);
     }
     return STARK_OK;
 }
@@ -581,58 +548,28 @@ static int32_t ali_merge_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* co
                                          nullptr, d_out + b0, d_cs ? d_cs + b0 : nullptr));
     }
     if (c_star) STARK_HIP(ctx, hipMemcpyAsync(cs.data(), d_cs, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); X.synced();       // the caller reads f0 and c_star on return
+    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));       // the caller reads f0 and c_star on return
     if (c_star) for (size_t b = 0; b < B; ++b) store_fr(c_star + 4 * b, cs[b]);
     return STARK_OK;
 }
 
-// B independent proofs of equal shape (stark_deep_fri_prove_batch_dev).  What bounds one prove is the serial column sponge of build_f0
-// (fri.rs:548-557: n0/16 dependent permutations per column, one wave each): four waves of the chip are busy for 99 % of the time.  The chains of
-// different traces are independent, so all 4 * B of them run in ONE launch; the two Fiat-Shamir hashes per trace (ALI/seed, ALI/DEEP) are
-// one launch each for the whole batch; merge, fri_build and the query phase of the traces then run side by side, pass by pass (prove_pass_batch;
-// a pass of one trace is the single tail, prove_tail_single).
+// B independent proofs of equal shape (stark_deep_fri_prove_batch_dev; stark_deep_fri_prove_dev from columns is B = 1): the challenge stage of all
+// traces at once, then merge, commit phase and query phase pass by pass (prove_pass).
 // Every proof is byte-for-byte what stark_deep_fri_prove_dev returns for that trace alone.
 static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, size_t n0,
                                 const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
     if (!is_pow2(n0)) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two (radix-2 domain)");
     if (n0 <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 > 1");
     for (size_t p = 0; p < B; ++p) out[p] = nullptr;
-    auto t0 = Clock::now();
-    // (1) all column digests: 4 * B serial sponges, concurrently
+    const auto t0 = Clock::now();
     std::vector<const fr_t*> ptrs(4 * B);
     for (size_t p = 0; p < B; ++p) { ptrs[4 * p] = as_fr(a[p]); ptrs[4 * p + 1] = as_fr(s[p]); ptrs[4 * p + 2] = as_fr(e[p]); ptrs[4 * p + 3] = as_fr(t[p]); }
-    DevBuf dptr, dig, seeds_in, seeds, deep_in, fused;
-    STARK_HIP(ctx, dptr.alloc(ctx, ptrs.size() * sizeof(void*))); STARK_HIP(ctx, dig.alloc(ctx, 4 * B * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(dptr.p, ptrs.data(), ptrs.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
-    const char* tags[4] = {"ALI/A", "ALI/S", "ALI/E", "ALI/T"};
-    STARK_TRY(tr_hash_columns_batch_dev(ctx, tags, (const fr_t* const*)dptr.p, B, n0, dig.fr()));
-    std::vector<fr_t> h(4 * B);
-    STARK_HIP(ctx, hipMemcpyAsync(h.data(), dig.p, 4 * B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // (2) seed_f = H("ALI/seed", [h_a, h_s, h_e, h_t, n0]) and the fused hash of ali_sample_z_beta_fs, one launch each for the batch (fri.rs:556-557, 511-515)
-    const fr_t n0f = host::h_u64(n0);
-    std::vector<fr_t> in5(5 * B); for (size_t p = 0; p < B; ++p) { for (int c = 0; c < 4; ++c) in5[5 * p + c] = h[4 * p + c]; in5[5 * p + 4] = n0f; }
-    STARK_HIP(ctx, seeds_in.alloc(ctx, in5.size() * sizeof(fr_t))); STARK_HIP(ctx, seeds.alloc(ctx, B * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(seeds_in.p, in5.data(), in5.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    STARK_TRY(tr_hash_dev(ctx, "ALI/seed", seeds_in.fr(), 5, B, seeds.fr()));
-    std::vector<fr_t> seed_f(B);
-    STARK_HIP(ctx, hipMemcpyAsync(seed_f.data(), seeds.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<fr_t> in2(2 * B); for (size_t p = 0; p < B; ++p) { in2[2 * p] = seed_f[p]; in2[2 * p + 1] = n0f; }
-    STARK_HIP(ctx, deep_in.alloc(ctx, in2.size() * sizeof(fr_t))); STARK_HIP(ctx, fused.alloc(ctx, B * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(deep_in.p, in2.data(), in2.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    STARK_TRY(tr_hash_dev(ctx, "ALI/DEEP", deep_in.fr(), 2, B, fused.fr()));
-    std::vector<fr_t> fu(B);
-    STARK_HIP(ctx, hipMemcpyAsync(fu.data(), fused.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    auto t1 = Clock::now();
-    // (3) merge, commit phase, query phase: side by side per pass (prove_pass_batch); a pass of one trace takes the single tail
-    const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));
-    const double shared_ms = ms_between(t0, t1);
-    std::vector<fr_t> zs(B); for (size_t p = 0; p < B; ++p) { fr_t beta; ali_z_beta_from_fused(fu[p], n0, seed_f[p], &zs[p], &beta); }
+    AliChallenges ch; STARK_TRY(challenge_stage(ctx, B, ptrs.data(), n0, ch));
+    const double shared_ms = ms_between(t0, Clock::now());
     const size_t per = pass_traces(ctx, n0);
     for (size_t p0 = 0; p0 < B; p0 += per) {
-        const size_t Bp = std::min(per, B - p0);
         const uint64_t* const* const cols[4] = {a + p0, s + p0, e + p0, t + p0};
-        const int32_t rc = Bp == 1 ? prove_tail_single(ctx, as_fr(a[p0]), as_fr(s[p0]), as_fr(e[p0]), as_fr(t[p0]), omega, zs[p0], n0, schedule, L, r, seed_z, shared_ms, &out[p0])
-                                   : prove_pass_batch(ctx, Bp, cols, zs.data() + p0, nullptr, n0, schedule, L, r, seed_z, shared_ms, out + p0);
+        const int32_t rc = prove_pass(ctx, std::min(per, B - p0), cols, ch.z.data() + p0, nullptr, n0, schedule, L, r, seed_z, shared_ms, out + p0);
         if (rc) { free_proofs(out, B); return rc; }
     }
     return STARK_OK;
@@ -719,7 +656,13 @@ int32_t stark_deep_fri_prove_dev(stark_ctx_t* ctx, const uint64_t* a, const uint
                                  const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out) {
     if (!ctx || !out || (!schedule && L) || (!f0 && (!a || !s || !e || !t))) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return prove_impl(ctx, as_fr(a), as_fr(s), as_fr(e), as_fr(t), as_fr(f0), n0, schedule, L, r, seed_z, out);
+    stark_proof* P = nullptr; int32_t rc;                                     // a batch of one; *out is written on success only
+    if (f0) {
+        if (!is_pow2(n0)) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two (radix-2 domain)");
+        rc = prove_f0_batch_impl(ctx, 1, &f0, n0, schedule, L, r, seed_z, &P);
+    } else rc = prove_batch_impl(ctx, 1, &a, &s, &e, &t, n0, schedule, L, r, seed_z, &P);
+    if (rc == STARK_OK) *out = P;
+    return rc;
 }
 int32_t stark_deep_fri_prove(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, const uint64_t* f0, size_t n0,
                              const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out) {

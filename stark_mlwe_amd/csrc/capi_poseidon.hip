@@ -408,43 +408,12 @@ int32_t stark_merkle_gather(stark_tree_t* t, int32_t lvl, const size_t* idx, siz
     stark_ctx* ctx = t->ctx; if (!k) return STARK_OK;
     STARK_TRY(ctx_enter(ctx));
     for (size_t i = 0; i < k; ++i) if (idx[i] >= t->lens[lvl]) return ctx->fail(STARK_ERR_INVALID_ARG, "gather index out of range");
-    std::vector<uint64_t> ix(idx, idx + k);
-    DevBuf di, dout; STARK_HIP(ctx, di.upload(ctx, ix.data(), k * 8)); STARK_HIP(ctx, dout.alloc(ctx, k * sizeof(fr_t)));
-    hipLaunchKernelGGL(k_gather, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, t->levels[lvl], (const uint64_t*)di.p, (uint64_t)k, dout.fr());
-    STARK_HIP(ctx, hipGetLastError());
-    STARK_HIP(ctx, dout.download_sync(out, k * sizeof(fr_t))); return STARK_OK;
+    MerkleGatherList G; G.level(t->levels[lvl], std::vector<size_t>(idx, idx + k));
+    return gather_rows(ctx, G, nullptr, out);
 }
 int32_t stark_merkle_free(stark_tree_t* t) { if (!t) return STARK_ERR_INVALID_ARG; delete t; return STARK_OK; }   // levels go back to the context's pool (stream-ordered reuse: no device sync)
 
 }  // extern "C"
-
-// open_union_of_paths (merkle/src/lib.rs:246-315): host index logic (fri_plan.hpp) + device gathers of the siblings.
-namespace stark {
-struct TreeSource : FriSource {
-    stark_tree* t; explicit TreeSource(stark_tree* t_) : t(t_) {}
-    int32_t layer(size_t, const std::vector<size_t>&, std::vector<fr_t>&) override { return STARK_ERR_INVALID_ARG; }
-    int32_t digests(size_t, size_t level, const std::vector<size_t>& idx, std::vector<fr_t>& out) override {
-        out.resize(idx.size()); return stark_merkle_gather(t, (int32_t)level, idx.data(), idx.size(), (uint64_t*)out.data());
-    }
-};
-int32_t merkle_open_host(stark_tree* t, const std::vector<size_t>& indices, MerkleProofHost& pr) {
-    stark_ctx* ctx = t->ctx;
-    if (indices.empty()) return ctx->fail(STARK_ERR_INVALID_ARG, "open_many: empty indices");                           // :247
-    if (t->lens.back() != 1) return ctx->fail(STARK_ERR_INVALID_ARG, "cannot open a partial tree");
-    for (size_t i : indices) if (i >= t->lens[0]) return ctx->fail(STARK_ERR_INVALID_ARG, "leaf index out of range");
-    TreeSource src(t);
-    return merkle_open_from(src, 0, t->lens, t->arity, indices, pr);
-}
-}  // namespace stark
-
-extern "C" int32_t stark_merkle_open(stark_tree_t* t, const size_t* idx, size_t k, uint8_t* buf, size_t cap, size_t* len) {
-    if (!t || !len || (!idx && k)) return STARK_ERR_INVALID_ARG;
-    MerkleProofHost pr; STARK_TRY(merkle_open_host(t, std::vector<size_t>(idx, idx + k), pr));
-    std::vector<uint8_t> b; enc_mproof(b, pr);
-    *len = b.size();
-    if (buf) { if (cap < b.size()) return t->ctx->fail(STARK_ERR_INVALID_ARG, "buffer too small"); memcpy(buf, b.data(), b.size()); }
-    return STARK_OK;
-}
 
 // ---- many trees in one pass (merkle_batch.hpp) ----------------------------------------------------------------------------------------------------
 namespace stark {
@@ -489,22 +458,26 @@ int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, siz
     }
     return STARK_OK;
 }
-// Request i = element index[i] of base[src[i]] into the i-th 32 bytes of out_host (host memory of any alignment: it is only the target of a copy): one upload of the four tables, one k_gather_rows launch, one download, one synchronisation.
-static int32_t gather_rows_sync(stark_ctx* ctx, const MerkleGatherList& G, void* out_host) {
+// THE row gather (declared in ctx.hpp): stark_merkle_gather, stark_merkle_roots_batch, every Merkle open and every DEEP-FRI query phase end here.
+int32_t gather_rows(stark_ctx* ctx, const MerkleGatherList& G, fr_t* out_dev, void* out_host) {
     const size_t k = G.size(), nb = G.base.size();
     if (!k) return STARK_OK;
     std::vector<uint64_t> h(nb + 2 * k + (k + 1) / 2);                   // [base | index | row | src (u32)]
     for (size_t i = 0; i < nb; ++i) h[i] = (uint64_t)(uintptr_t)G.base[i];
-    for (size_t i = 0; i < k; ++i) { h[nb + i] = G.index[i]; h[nb + k + i] = (uint64_t)i; }
+    for (size_t i = 0; i < k; ++i) { h[nb + i] = G.index[i]; h[nb + k + i] = G.row_of(i); }
     memcpy(h.data() + nb + 2 * k, G.src.data(), k * 4);
-    DevBuf d, o; STARK_HIP(ctx, o.alloc(ctx, k * sizeof(fr_t))); STARK_HIP(ctx, d.upload(ctx, h.data(), h.size() * 8));     // nothing can fail between the enqueued upload of h and a drain
+    DevBuf d, o; STARK_HIP(ctx, d.alloc(ctx, h.size() * 8));
+    if (!out_dev) { STARK_HIP(ctx, o.alloc(ctx, k * sizeof(fr_t))); out_dev = o.fr(); }
+    STARK_TRY(ctx_upload_staged(ctx, d.p, h.data(), h.size() * 8));
     const uint64_t* t = (const uint64_t*)d.p;
-    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)t, (const uint32_t*)(t + nb + 2 * k), t + nb, t + nb + k, (uint64_t)k, o.fr());
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return ctx->fail(STARK_ERR_HIP, std::string("k_gather_rows: ") + hipGetErrorString(e)); }   // h is the source of an enqueued upload
-    STARK_HIP(ctx, o.download_sync(out_host, k * sizeof(fr_t))); return STARK_OK;
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, ctx->stream, (const fr_t* const*)t, (const uint32_t*)(t + nb + 2 * k), t + nb, t + nb + k, (uint64_t)k, out_dev);
+    STARK_HIP(ctx, hipGetLastError());
+    if (!out_host) return STARK_OK;
+    STARK_HIP(ctx, hipMemcpyAsync(out_host, out_dev, k * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return STARK_OK;
 }
-struct MerkleOpenDevExec { stark_ctx* ctx; int32_t gather(const MerkleGatherList& G, fr_t* out_host) { return gather_rows_sync(ctx, G, out_host); } };
+// merkle_open_batch's executor: every sibling of every tree and level of a call through that one gather
+struct MerkleOpenDevExec { stark_ctx* ctx; int32_t gather(const MerkleGatherList& G, fr_t* out_host) { return gather_rows(ctx, G, nullptr, out_host); } };
 // the trees of one call: all non-null, complete and of one context
 static int32_t same_ctx_trees(stark_tree* const* trees, size_t batch, stark_ctx** ctx) {
     for (size_t b = 0; b < batch; ++b) if (!trees[b]) return STARK_ERR_INVALID_ARG;
@@ -534,7 +507,7 @@ int32_t stark_merkle_roots_batch(stark_tree_t* const* trees, size_t batch, uint6
     STARK_TRY(ctx_enter(ctx));
     MerkleGatherList G;
     for (size_t b = 0; b < batch; ++b) G.level(trees[b]->levels.back(), std::vector<size_t>(1, 0));
-    return gather_rows_sync(ctx, G, roots);
+    return gather_rows(ctx, G, nullptr, roots);
 }
 int32_t stark_merkle_open_batch(stark_tree_t* const* trees, size_t batch, const size_t* idx, const size_t* idx_off, stark_proof_t** out) {
     if (!batch) return STARK_OK;
@@ -550,6 +523,23 @@ int32_t stark_merkle_open_batch(stark_tree_t* const* trees, size_t batch, const 
     if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, "open batch: idx_off not increasing, an empty index list or a leaf index out of range");
     if (rc) return rc;
     for (size_t b = 0; b < batch; ++b) { out[b] = new stark_proof(); out[b]->bytes = std::move(proofs[b]); }
+    return STARK_OK;
+}
+// open_union_of_paths (merkle/src/lib.rs:246-315) of one tree: merkle_open_batch over one view.  The three refusals keep their own wording (they run
+// first, so the batch driver's one message for all of them never surfaces here).
+int32_t stark_merkle_open(stark_tree_t* t, const size_t* idx, size_t k, uint8_t* buf, size_t cap, size_t* len) {
+    if (!t || !len || (!idx && k)) return STARK_ERR_INVALID_ARG;
+    stark_ctx* ctx = t->ctx;
+    if (!k) return ctx->fail(STARK_ERR_INVALID_ARG, "open_many: empty indices");                                        // :247
+    if (t->lens.back() != 1) return ctx->fail(STARK_ERR_INVALID_ARG, "cannot open a partial tree");
+    for (size_t i = 0; i < k; ++i) if (idx[i] >= t->lens[0]) return ctx->fail(STARK_ERR_INVALID_ARG, "leaf index out of range");
+    STARK_TRY(ctx_enter(ctx));
+    const MerkleTreeView view{t->arity, &t->lens, t->levels.data()}; const size_t off[2] = {0, k};
+    MerkleOpenDevExec X{ctx}; std::vector<std::vector<uint8_t>> proofs;
+    STARK_TRY(merkle_open_batch(X, &view, 1, idx, off, proofs));
+    const std::vector<uint8_t>& b = proofs[0];
+    *len = b.size();
+    if (buf) { if (cap < b.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "buffer too small"); memcpy(buf, b.data(), b.size()); }
     return STARK_OK;
 }
 }  // extern "C"

@@ -173,8 +173,11 @@ struct DevBuf {
     void* release() { void* q = p; p = nullptr; return q; }
 };
 
-// open_union_of_paths over a device-resident tree (MerkleProofHost and the encoders: fri_plan.hpp)
-int32_t merkle_open_host(stark_tree* t, const std::vector<size_t>& indices, MerkleProofHost& pr);
+// THE row gather on the device (capi_poseidon.hip; the list: merkle_batch.hpp): the four tables go up as ONE packed ctx_upload_staged block (the list
+// may die on return), then ONE k_gather_rows launch into out_dev (nullptr: a pooled table of G.size() rows).  out_host (optional, host memory of any
+// alignment): the first G.size() rows of the table are downloaded and the context's stream synchronised.  Index bounds are the caller's to check.
+struct MerkleGatherList;
+int32_t gather_rows(stark_ctx* ctx, const MerkleGatherList& G, fr_t* out_dev, void* out_host);
 
 // shared internal entry points (defined in capi_core.hip / capi_ntt.hip / capi_comm.hip; the Poseidon ones: poseidon_launch.hpp)
 int32_t ctx_transcript_params(stark_ctx* ctx, stark_params** out);

@@ -12,6 +12,8 @@
 //     one DsBatchPairStream launch, and every Merkle level of the Bp same-shape trees is one DsBatchStream launch under a per-tree label
 //     array holding l; the top level writes the Bp roots of layer l into roots[l * Bp ..];
 //   * layers 1..L are committed between fork() and side(false) — the device runs them on its side stream underneath layer 0, as fri_build does.
+// A pass of ONE trace does not come here: its commit is fri_build_impl (capi_fri.hip: PassCommit::run chooses), whose levels are DsStreams and
+// reach k_node16_pair and the "fri_side_pair" form; everything before and after the commit phase is shared by both forms.
 // Nothing here synchronises the host.  Memory of a pass: the layers (Bp n0 (1 + 1/m_0 + ...)), the leaf digests of every layer (the same
 // again) and the upper tree levels (at most 1/(arity - 1) of that): about Bp * n0 * 32 B * (2 + small), all released with the executor.
 // Host-only C++ (no HIP).
@@ -44,7 +46,7 @@ inline fr_t fri_z_from_fused(const fr_t& fused, uint64_t seed_z, size_t level, s
 
 // An executor X provides (pointers are its own memory: device pointers on the GPU, host pointers in the host check):
 //   int32_t alloc(size_t bytes, void** out)                     memory that lives as long as X
-//   int32_t upload(void* dst, const void* src, size_t bytes)    src stays valid until the caller's next synchronisation
+//   int32_t upload(void* dst, const void* src, size_t bytes)    src may die on return (the device executor: ctx_upload_staged)
 //   int32_t zpows(const fr_t& z, size_t m, fr_t* zp)            zp[t] = z^t, t < m
 //   int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out)              fri_fold_layer over n elements
 //   int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h)      hash_leaf_pair(f[i], f_next[i / m]) (f_next == nullptr: zero)

@@ -3,7 +3,7 @@
 //   k_fri_fold   fri_fold_layer            crates/deep_ali/src/fri.rs:85-102   out[b] = sum_t f[b*m+t] z^t
 //                (compute_s_layer, fri.rs:123-143, is the view s[i] = out[i/m]; never materialised)
 //   k_ali_*      deep_ali_merge_evals(_blinded)   crates/deep_ali/src/lib.rs:60-105
-//   k_gather     levels[l][idx] reads for openings (merkle/src/lib.rs:261-291)
+//   k_gather_rows  every read of a Merkle opening or a query phase (merkle/src/lib.rs:261-291; fri.rs:355-466) in one launch
 //   k_synth      synthetic trace columns for benchmarks (definition in DESIGN.md "Synthetic inputs")
 // All HBM-streaming: every lane moves whole 32-byte elements as 2 x dwordx4, consecutive lanes touch
 // consecutive elements.
@@ -185,13 +185,8 @@ __global__ void __launch_bounds__(256) k_sum_single_block(const fr_t* __restrict
     }
 }
 
-static __global__ void k_gather(const fr_t* __restrict__ src, const uint64_t* __restrict__ idx, uint64_t k, fr_t* __restrict__ out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < k) stg(out + i, ldg(src + idx[i]));
-}
-
-// Batched opening reads of the query phase: request i reads element index[i] of the array base[src[i]] (a layer or a tree level) into
-// row[i] of the table (layers and tree levels of a whole proof in ONE launch instead of one synchronised gather per level).  A sharded
+// THE gather of the library (host side: MerkleGatherList, gather_rows): request i reads element index[i] of the array base[src[i]] (a layer or a
+// tree level) into row[i] of the table (layers and tree levels of whole proofs and openings in ONE launch instead of one synchronised gather per level).  A sharded
 // prove writes only the rows its rank owns into a zeroed table, so that one all-reduce SUM completes it.  Bounds are checked on the host.
 static __global__ void k_gather_rows(const fr_t* const* __restrict__ base, const uint32_t* __restrict__ src, const uint64_t* __restrict__ index,
                                      const uint64_t* __restrict__ row, uint64_t k, fr_t* __restrict__ out) {

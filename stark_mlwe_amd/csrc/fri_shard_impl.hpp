@@ -248,14 +248,12 @@ static int32_t shard_query_fill(stark_ctx* ctx, const FriShardPlan& P, FriShardR
         }
         return STARK_OK;
     };
-    OpeningGather G(ctx);                                                                  // the rows of the other ranks stay zero for the all-reduce
+    MerkleGatherList G;                                                                    // the rows of the other ranks stay zero for the all-reduce
     for (size_t i = 0; i < nreq; ++i) {
         FriOpening o; STARK_TRY(resolve(plan.req[i], o));
-        if (o.owner == (uint64_t)K.rank) STARK_TRY(G.add(o.src, o.len, o.index, i));
+        if (o.owner == (uint64_t)K.rank) STARK_TRY(add_opening(ctx, G, o.src, o.len, o.index, i));
     }
-    STARK_TRY(G.launch(K.coll.fr()));
-    if (G.size()) { STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); G.synced(); }       // the host index arrays end here
-    return STARK_OK;
+    return gather_rows(ctx, G, K.coll.fr(), nullptr);
 }
 static int32_t shard_queries(const ShardColl& C, const FriShardPlan& P, std::vector<FriShardRank>& K, size_t r, std::vector<stark_proof*>& out) {
     stark_ctx* ctx = C.ctx;

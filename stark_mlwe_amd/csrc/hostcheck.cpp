@@ -663,7 +663,7 @@ struct MerkleHostExec {
     int32_t pair_level(const DsBatchPairPtrStream& D, fr_t* out) { return ds(D, out); }
     int32_t ds_level(const DsBatchStream& D, fr_t* out) { return ds(D, out); }
 };
-struct MerkleOpenHostExec { int32_t gather(const MerkleGatherList& G, fr_t* out) { for (size_t i = 0; i < G.size(); ++i) out[i] = G.base[G.src[i]][G.index[i]]; return 0; } };
+struct MerkleOpenHostExec { int32_t gather(const MerkleGatherList& G, fr_t* out) { for (size_t i = 0; i < G.size(); ++i) out[G.row_of(i)] = G.base[G.src[i]][G.index[i]]; return 0; } };
 static std::vector<size_t> total_lens(const std::vector<size_t>& lens, size_t B) { std::vector<size_t> o(lens.size() + 1, 0); for (size_t v = 0; v < lens.size(); ++v) o[v + 1] = o[v] + B * lens[v]; return o; }
 extern "C" {
 // MerkleTree::new / new_pairs of B trees of n leaves through the batch driver.  leaves / cp: B host columns (cp null iff !pairs; a null entry = zeros).

@@ -5,12 +5,13 @@
 //   build   `batch` trees of one shape (arity, n, pairs).  Level v of all trees is ONE block of batch x lens[v] elements, tree b's level the slice at
 //           b * lens[v]: level 0 is one copy (or one pair-leaf launch) through the pointer tables, every level above one DsBatchStream launch.
 //   open    any trees of one context: every tree is planned on the host (merkle_open_from over a recording source), all siblings of all trees and
-//           levels come back with ONE gather, and each proof is encoded with enc_mproof.
+//           levels come back with ONE gather, and each proof is encoded with enc_mproof.  stark_merkle_open is this with one tree.
 //   verify  every opening is parsed (dec_mproof) and walked over pool slots (DsJobPlanner) into the plan shape of fri_verify_batch.hpp; what runs the
 //           plan makes one launch per (width, depth) and compares each item's computed root with the claimed one.  The single verify calls are a batch of one.
 // Element i of every result equals what the single call returns for item i alone, byte for byte.  Host-only C++ (no HIP).
 #pragma once
 #include <cstdint>
+#include <map>
 #include <vector>
 #include "fr.hpp"
 #include "poseidon_streams.hpp"
@@ -57,14 +58,21 @@ inline int32_t merkle_build_batch(X& x, size_t arity, size_t B, const uint64_t* 
 // ---- open -------------------------------------------------------------------------------------------------------------------------------------
 // A tree as the open driver sees it: its arity, level lengths and level arrays (in the executor's memory).
 struct MerkleTreeView { size_t arity; const std::vector<size_t>* lens; const fr_t* const* levels; };
-// The reads of a batch of openings: request i is element index[i] of the array base[src[i]].
+// The reads of ONE row gather — the openings of a batch of trees, the opened values of a query phase: request i is element index[i] of the array
+// base[src[i]] (each source array once in `base`, however often it is read) and lands in row i of the result, or in row[i] when the list carries
+// explicit rows (add(); all requests of a list or none: a sharded query phase fills only its own rank's rows of a zeroed table).
 struct MerkleGatherList {
-    std::vector<const fr_t*> base; std::vector<uint32_t> src; std::vector<uint64_t> index;
-    void level(const fr_t* from, const std::vector<size_t>& idx) {
-        if (base.empty() || base.back() != from) base.push_back(from);
-        for (size_t i : idx) { src.push_back((uint32_t)(base.size() - 1)); index.push_back((uint64_t)i); }
+    std::vector<const fr_t*> base; std::vector<uint32_t> src; std::vector<uint64_t> index, row;
+    std::map<const fr_t*, uint32_t> slot;
+    uint32_t slot_of(const fr_t* from) {
+        auto it = slot.emplace(from, (uint32_t)base.size()).first;
+        if (it->second == base.size()) base.push_back(from);
+        return it->second;
     }
+    void level(const fr_t* from, const std::vector<size_t>& idx) { const uint32_t s = slot_of(from); for (size_t i : idx) { src.push_back(s); index.push_back((uint64_t)i); } }
+    void add(const fr_t* from, uint64_t i, uint64_t to_row) { src.push_back(slot_of(from)); index.push_back(i); row.push_back(to_row); }
     size_t size() const { return src.size(); }
+    uint64_t row_of(size_t i) const { return row.empty() ? (uint64_t)i : row[i]; }
 };
 // -1: a non-monotone idx_off, an empty index list (open_many, :247) or a leaf index out of range — found before anything is read.
 // An executor X provides   int32_t gather(const MerkleGatherList& G, fr_t* out_host)   (one launch, one download, one synchronisation).
