@@ -155,6 +155,17 @@ void* hc_params_new(int kind, int t, const char* seed) {
     P->ref = kind == 0 ? host::consts_for_width(t) : kind == 1 ? host::consts_transcript() : host::derive_consts(seed, 17, 8, 64);
     bind(P); return P;
 }
+// a caller's own constants (t*t, rf*t and rp elements, four u64 limbs each as stored), as stark_poseidon_params_upload takes them; check hc_params_ok
+void* hc_params_upload(int t, int rf, int rp, const uint64_t* mds, const uint64_t* rc_full, const uint64_t* rc_partial) {
+    if (!mds || !rc_full || !rc_partial || t < 2 || rf <= 0 || (rf & 1) || rp <= 0) return nullptr;
+    HcParams* P = new HcParams();
+    P->ref.t = t; P->ref.rf = rf; P->ref.rp = rp;
+    P->ref.mds.resize((size_t)t * t); P->ref.rc_full.resize((size_t)rf * t); P->ref.rc_partial.resize(rp);
+    for (size_t i = 0; i < P->ref.mds.size(); ++i) P->ref.mds[i] = ld4(mds + 4 * i);
+    for (size_t i = 0; i < P->ref.rc_full.size(); ++i) P->ref.rc_full[i] = ld4(rc_full + 4 * i);
+    for (size_t i = 0; i < P->ref.rc_partial.size(); ++i) P->ref.rc_partial[i] = ld4(rc_partial + 4 * i);
+    bind(P); return P;
+}
 int hc_params_ok(void* h) { return ((HcParams*)h)->kc.ok ? 1 : 0; }
 void hc_params_free(void* h) { delete (HcParams*)h; }
 int hc_params_export(void* h, uint64_t* mds, uint64_t* rc_full, uint64_t* rc_partial) {

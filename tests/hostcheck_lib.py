@@ -66,6 +66,14 @@ class HostCheck:
     def params(self, kind, t=17, seed=b""):
         return vp(self.l.hc_params_new(kind, t, seed))
 
+    def params_upload(self, t, rf, rp, mds, rc_full, rc_partial):
+        """a caller's own constants (stored limbs, as Context.params_upload takes them) with the kernel-form tables derived from them"""
+        mds, rcf, rcp = A(mds), A(rc_full), A(rc_partial)
+        assert mds.size == 4 * t * t and rcf.size == 4 * rf * t and rcp.size == 4 * rp
+        self.l.hc_params_upload.restype = vp
+        h = vp(self.l.hc_params_upload(t, rf, rp, P(mds), P(rcf), P(rcp)))
+        assert h.value and self.params_ok(h); return h
+
     def params_ok(self, h): return self.l.hc_params_ok(h)
     def params_free(self, h): self.l.hc_params_free(h)
 

@@ -2,8 +2,12 @@
 and the oracle.  The inputs are corners of the four u64 limbs AS STORED (Montgomery form) — tests/corner_values.py — not corners of the
 logical value: logical r - 1 is stored as 4t ~ 2^127 for Pallas, a benign operand.  CPU only.
 
-Still open: the non-canonical-lane bound of pair_lane_update (2.7 r after 16 blocks of partial rounds) would need control of the partial-round
-S-box outputs 64 rounds deep; nothing here forces it."""
+The steered tests put chosen stored words behind EVERY S-box of a permutation, not only round 0: the round constants are free (the S-box input
+of every round is state + rc), so for one state they are chosen such that all 8 t full-round outputs and all rp partial-round outputs are stored
+corners (corner_values.steered_params).
+
+Still open: the partial-round S-box outputs are controlled now, but nothing here drives one lane of pair_lane_update to its 2.7 r bound (after 16
+blocks of partial rounds), or the wave form's lanes to theirs: that would need a search over the x_q against the kernel-form w tables."""
 import numpy as np
 import pytest
 
@@ -272,4 +276,95 @@ def test_sponge_bodies_on_corner_inputs(oracle, hostcheck):
     for cnt in (1, 16, 17, 37):
         assert (hostcheck.hash_stream(hseed, 1, None, 0, c[:cnt], cnt, c[50]) == oracle.hash_with_ds(2, c[:cnt], c[50])).all(), cnt
     for h in (ht, h17, h9, hseed):
+        hostcheck.params_free(h)
+
+
+# ---- steered round constants: chosen stored words behind every S-box of all 72 rounds ----------------------------------------------------
+_SCHEDULES = {}
+
+
+def schedules(t):
+    if t not in _SCHEDULES:
+        _SCHEDULES[t] = cv.target_schedules(pyref.params_for_width(t))
+    return _SCHEDULES[t]
+
+
+def test_target_schedules_cover_every_round_half_and_block_position():
+    """By computation, for every width: each uniform corner has a schedule of its own, and over the rotations every other stored corner is the S-box
+    output of every full round in every element half (X and Y of the wave pair for t = 17) and x_q at every position q mod 4."""
+    corners = cv.stored_corners(P)
+    for t in (9, 17, 33, 65):
+        sc = schedules(t)
+        full, part, uni = cv.schedule_coverage(t, [(tf, tp) for _, tf, tp in sc])
+        assert full.shape == (len(corners), 8, 2 if t == 17 else 1) and full.all() and part.all(), t
+        assert uni == set(cv.uniform_corners(P)) and len(uni) == 9
+        for c in (P - 1, (1 << 254) - 1, 1 << 254, cv.alt29(0), cv.alt29(1)):
+            assert c in uni
+        rot = [s for s in sc if s[0].startswith("rotation")]
+        rest = len(corners) - 9
+        assert len(rot) == max(-(-rest // (8 if t == 17 else t)), -(-rest // (pyref.RP_FOR_T[t] // 4))), (t, len(rot))      # no set more than the windows need
+
+
+# (t, index into schedules(t)): every schedule for t = 9 and 17; for t = 33 (a pyref permutation takes 4 times as long, the table
+# derivation 6 times) the uniform p - 1, the first carry chain and the first and last rotation
+STEERED_HOST = [(t, i) for t in (9, 17) for i in range(14)] + [(33, i) for i in (0, 5, 9, 11)]
+
+
+@pytest.mark.parametrize("t,i", STEERED_HOST)
+def test_steered_constants_through_the_host_kernel_bodies(hostcheck, t, i):
+    """One steered set per case.  The construction: pyref.permute under the steered set ends where the walk said, and every S-box output on the
+    trajectory, re-stored as fr_pow5_r29 delivers it, is its target.  The code: the kernel-form permutation (L*U rows, sparse partial rounds in
+    blocks of four with their carry-free radix-2^29 accumulations), the chain model of the five-wave form (t = 17) and the sponge body of a Merkle
+    level agree with pyref on the steered state / node — chosen limbs in all 72 rounds — and on 16 others under the same set; for t = 17 the
+    matrix-core emulation agrees with the L*U rows and with pyref's M x on the steered S-box outputs of each of the eight full rounds."""
+    base = pyref.params_for_width(t); arity = t - 1
+    name, tf, tp = schedules(t)[i]
+    assert len(schedules(17)) == 14 and len(schedules(9)) == 14 and len(schedules(33)) == 12
+    rng = np.random.default_rng(100 * t + i)
+    # ONE set per case (deriving its kernel-form tables is the larger cost at t = 33): steered for a Merkle node — permutation 1 of a full
+    # node, both permutations (which = 2), or the ragged last node — whose first state is the steered state of the permutation checks
+    which, kstar, last = ((1, 5, None), (2, 5, None), (1, 16, 3))[i % 3]
+    nd = cv.steered_set(base, (name, tf, tp), which, 1000 + i, 2, 9, count=last)
+    sp, state = nd["params"], nd["state"]
+    assert sp["mds"] == base["mds"]
+    of, op, end = cv.sbox_outputs(sp, state)
+    assert pyref.permute(state, sp) == end, (t, name)
+    assert sum(a != b for a, b in zip(sum(nd["tf"], []), sum(tf, []))) == (1 if which == 2 else 0) and (which == 1 or nd["tf"][7][:t - 1] == tf[7][:t - 1])
+    for r in range(8):
+        assert of[r] == nd["tf"][r], "t = %d, %s: full round %d delivers %s" % (t, name, r, ["%x" % v for v in of[r]])
+    assert op == tp, (t, name)
+    plain, end2 = cv.steered_params(base, state, nd["tf"], tp)
+    assert plain == sp and end2 == end                                      # the node variant is steered_params on the node's first state
+    h = hostcheck.params_upload(*cv.params_arrays(sp))
+    try:
+        mds, rcf, rcp = hostcheck.params_export(h, t, 8, sp["rp"])
+        assert (rcp == cv.to_stored(sp["rc_partial"])).all() and (rcf == cv.to_stored([x for r in sp["rc_full"] for x in r])).all()
+        others = [[int.from_bytes(rng.bytes(40), "little") % P for _ in range(t)] for _ in range(14)] + [[0] * t, [P - 1] * t]
+        sts = [state] + others
+        want = np.stack([cv.to_stored(end)] + [cv.to_stored(pyref.permute(s, sp)) for s in others])
+        arr = np.stack([cv.to_stored(s) for s in sts])
+        forms = [("kernel form", hostcheck.permute_kernel_form), ("dense", hostcheck.permute_dense)] + ([("chain model", hostcheck.permute_chain_model)] if t == 17 else [])
+        for fname, fn in forms:
+            got = fn(h, arr, t)
+            bad = np.nonzero((got != want).any(axis=(1, 2)))[0]
+            assert bad.size == 0, "%s, t = %d, set '%s': state %d (0 is the steered one) differs from pyref: got %s want %s" % (
+                fname, t, name, bad[0], cv.hex_limbs(got[bad[0]])[:2], cv.hex_limbs(want[bad[0]])[:2])
+        ch, pos0 = cv.steered_level(base, nd, 17, kstar, last_children=last)
+        assert pos0 == 1000 + i - kstar
+        got = hostcheck.hash_ds_level(h, 0, arity, 2, pos0, 9, ch)
+        assert got.shape[0] == 17
+        assert (cv.node_digest(sp, 2, nd["pos"], 9, nd["children"]) == nd["digest"]).all()
+        for k in range(17):
+            w = nd["digest"] if k == kstar else cv.node_digest(sp, 2, pos0 + k, 9, ch[k * arity:(k + 1) * arity])
+            assert (got[k] == w).all(), "hash_ds_level, t = %d, set '%s', permutation %d steered in node %d: node %d differs from pyref" % (t, name, which, kstar, k)
+        if t == 17:
+            Mpre = cv.mds_pre_canonical(base)
+            x = np.stack([cv.raw_array(row) for row in nd["tf"]])             # the eight steered S-box output vectors, stored as delivered
+            for pre, M in ((False, base["mds"]), (True, Mpre)):
+                w = np.stack([cv.raw_array([(sum(M[a][j] * row[j] for j in range(17)) << cv.SBOX_SHIFT) % P for a in range(17)]) for row in nd["tf"]])
+                a, b = hostcheck.full_round_linear(h, 0, pre, x), hostcheck.full_round_linear(h, 1, pre, x)
+                for r in range(8):
+                    assert (b[r] == w[r]).all(), "matrix-core path, pre = %s, set '%s', S-box outputs of full round %d: %s" % (pre, name, r, cv.hex_limbs(x[r]))
+                    assert (a[r] == w[r]).all(), "L*U path, pre = %s, set '%s', S-box outputs of full round %d: %s" % (pre, name, r, cv.hex_limbs(x[r]))
+    finally:
         hostcheck.params_free(h)

@@ -6,8 +6,21 @@ S-box outputs of round 0 — the words the signed radix-256 recoding in front of
 fold and the carry pass, so only device runs on chosen digits can see a mistake in them.  tests/test_corner_values_host.py checks the
 construction itself on the CPU.  Needs an MI355X: `pytest -m gpu`.
 
-Still open: the non-canonical-lane bound of pair_lane_update (2.7 r after 16 blocks of partial rounds) would need control of the partial-round
-S-box outputs 64 rounds deep; nothing here forces it."""
+Chosen words in EVERY round: stark_poseidon_params_upload takes arbitrary round constants and the S-box input of every round is state + rc, so
+for one chosen node the constants are picked (corner_values.steered_params / steered_node) such that all 8 t full-round S-box outputs and all rp
+partial-round outputs x_q on its trajectory are chosen stored values: the recoding sees chosen digits in all eight full rounds, the carry-free
+radix-2^29 accumulations of pair_permute's four-round blocks and the five-wave form's chain tables see chosen x_q at every block position, and the
+uniform schedules make every term of every accumulation the same extreme at once.  Expected values under such a set come from pyref; the oracle
+library knows only the fixed sets.  The wide widths t = 33 / 65 / 129 (k_hash_ds_wave and the lane form with 32-lane blocks) get the crafted
+round-0 levels, and t = 33 / 65 steered sets as well; there is no steered set for t = 129, whose table derivation takes minutes.
+
+Not steerable: tr_hash, the leaf hash and the transcripts run the context's fixed transcript set (ctx_transcript_params; stark_leaf_pair_hash_dev
+rejects other constants).  They share pair_permute / coop_permute / chain_sponge_ex with the DS kernels, which is how they are covered; their own
+inputs stay at round-0 corners.  A full node's second permutation cannot be steered for GIVEN children (its input depends on every constant); it is
+steered by choosing the children so that it repeats the first one's trajectory, at the price of one forced target (steered_node).
+
+Still open: the partial-round S-box outputs are controlled now, but nothing here drives one lane of pair_lane_update to its 2.7 r bound, or the wave
+form's lanes (about r per round, reduced every 32 rounds) to theirs: that would need a search over the x_q against the kernel-form w tables."""
 import numpy as np
 import pytest
 
@@ -46,9 +59,9 @@ FORMS = {"default": {}, "k_hash_ds2 (merkle_node16_pair = 0)": {"merkle_node16_p
          "one-wave / wave-pair (sponge_one_wave = 1)": {"sponge_one_wave": (1, 0)}}
 
 
-def check_level(ctx, oracle, dev_params, okind, params, nodes, level, pos0, label, last_children=None, forms=FORMS):
+def check_level(ctx, oracle, dev_params, okind, params, nodes, level, pos0, label, last_children=None, forms=FORMS, uniform=False):
     t = params["t"]; arity = t - 1
-    ch, slot_idx = cv.crafted_level(params, nodes, last_children=last_children)
+    ch, slot_idx = cv.crafted_level(params, nodes, last_children=last_children, uniform=uniform)
     full = nodes if last_children is None else nodes - 1
     want = np.zeros((nodes, 4), np.uint64)
     want[:full] = oracle.hash_with_ds_dynamic(okind, t, cv.ds_words(oracle, arity, level, pos0, label, full), ch[:full * arity], arity, n=full).reshape(full, 4)
@@ -95,10 +108,10 @@ def test_crafted_levels_other_parameter_sets_and_t9(gpu_ctx, oracle):
         check_level(gpu_ctx, oracle, p9, 0, pyref.params_for_width(9), nodes, 1, 7, 5, last_children=last, forms=forms)
 
 
-@pytest.mark.parametrize("t", [9, 17, 33])
+@pytest.mark.parametrize("t", [9, 17, 33, 65])
 def test_permute_on_corner_and_crafted_states(gpu_ctx, oracle, t):
     corners = cv.stored_corners(P); L = len(corners)
-    params = pyref.params_for_width(t)
+    params = base_params(t)
     rows = [[corners[(i + j) % L] for j in range(t)] for i in range(L)] + [[v] * t for v in corners]
     rows += [cv.crafted_state(params, [corners[(i + 2 * j) % L] for j in range(t)]) for i in range(L)]
     st = np.stack([cv.raw_array(r) for r in rows])
@@ -107,6 +120,217 @@ def test_permute_on_corner_and_crafted_states(gpu_ctx, oracle, t):
     want = oracle.permute(0, t, st)
     bad = np.nonzero((got != want).any(axis=(1, 2)))[0]
     assert bad.size == 0, "t = %d, state %d: %s" % (t, bad[0], cv.hex_limbs(st[bad[0]]))
+
+
+# ---- Poseidon: the wide widths on crafted levels ---------------------------------------------------------------------------------------
+_BASE = {}
+
+
+def base_params(t):
+    """pyref's Merkle set of width t, derived once per module (t = 129 takes seconds in Python)"""
+    if t not in _BASE:
+        _BASE[t] = pyref.params_for_width(t)
+    return _BASE[t]
+
+
+WIDE_FORMS = {"default (Wide, k_hash_ds_wave)": {}, "lane (poseidon_lane_only = 1)": {"poseidon_lane_only": (1, 0)}}
+
+
+@pytest.mark.parametrize("t", [33, 65])
+def test_crafted_levels_wide_widths(gpu_ctx, oracle, t):
+    """k_hash_ds_wave<33 / 65> — nine lazy limbs, row eighths with a carry pass every fr29_max_terms terms — has no host twin and met only
+    synth_column values so far: crafted levels (every stored corner as the round-0 S-box output of every one of the t - 5 controllable elements),
+    L + 2 nodes and L + 3 with a ragged last node, rotated and uniform (one corner in every slot of a node), through the wave form and the lane form."""
+    L = len(cv.stored_corners(P))
+    dev = gpu_ctx.poseidon_params_for_width(t)
+    for nodes, last in ((L + 2, None), (L + 3, 5)):
+        for uniform in (False, True):
+            slot_idx = check_level(gpu_ctx, oracle, dev, 0, base_params(t), nodes, 2, 77, 42, last_children=last, forms=WIDE_FORMS, uniform=uniform)
+            full = slot_idx[:L]
+            if uniform:
+                assert (full == np.arange(L)[:, None]).all()
+            else:
+                assert all(sorted(set(full[:, j].tolist())) == list(range(L)) for j in range(t - 5))        # every corner in every slot
+
+
+def test_crafted_level_t129(gpu_ctx, oracle):
+    """t = 129 on the crafted level, 3 full nodes and a ragged one, under the session context's cached set (its derivation takes minutes: never a
+    second one): the wave form, and the lane form, which at this width runs 32-lane blocks (poseidon_block)."""
+    dev = gpu_ctx.poseidon_params_for_width(129)
+    for uniform in (False, True):
+        check_level(gpu_ctx, oracle, dev, 0, base_params(129), 4, 2, 77, 42, last_children=7, forms=WIDE_FORMS, uniform=uniform)
+
+
+# ---- Poseidon: chosen words behind every S-box of all 72 rounds (steered round constants) ------------------------------------------------
+LEVEL, LABEL = 3, 42
+# lanes 0, 31, 32, 63 of the first four 64-sponge blocks: where the main sets put their steered node (all below 256, the smallest level)
+INTERIOR = [0, 31, 32, 63, 64, 95, 96, 127, 128, 159, 160, 191, 192, 223, 224, 255]
+# the nodes every main set is compared on besides its steered one — first, block edges, the 32-sponge tile edges, a fixed random draw.  They lie below
+# 256 and a set keeps its pos0 at every level size, so their pyref digests (20 ms each at t = 17) are computed once per set, not once per call
+SHARED = sorted(set([0, 1, 31, 32, 33, 62, 63, 64, 65, 127, 128, 129, 191, 192, 254, 255] + np.random.default_rng(7).choice(256, 24, replace=False).tolist()))[:32]
+
+
+class SteeredSets:
+    """The steered sets of one width, derived and uploaded once per module.  role "main": one per schedule (corner_values.target_schedules), first
+    permutation steered, the sets the coverage is computed over; "both": both permutations of a full node steered; "edge": placed in the last
+    partial block (permutation 1, and both); "ragged": the ragged last node, which has one permutation."""
+
+    def __init__(self, ctx):
+        self.ctx, self.by_t, self.memo = ctx, {}, {}
+
+    def sets(self, t, roles=None):
+        if t not in self.by_t:
+            base = base_params(t); sc = cv.target_schedules(base); ragged = 5 if t == 17 else 3
+            rot0 = next(i for i, s in enumerate(sc) if s[0].startswith("rotation"))
+            if t <= 17:
+                plan = [("main", i, 1, None) for i in range(len(sc))] + [("both", rot0, 2, None), ("both", 0, 2, None), ("edge", rot0 + 1, 1, None), ("edge", 1, 2, None), ("ragged", rot0 + 2, 1, ragged)]
+            elif t == 33:
+                plan = [("first", rot0, 1, None), ("last", 0, 2, None)]
+            else:
+                plan = [("first", rot0, 2, None)]                       # ONE set: the table derivation grows like t^4
+            out = []
+            for n, (role, i, which, count) in enumerate(plan):
+                nd = cv.steered_set(base, sc[i], which, 5000 + 977 * n, LEVEL, LABEL, count=count)
+                nd["role"] = role; nd["id"] = "t = %d, set %d (%s, %s, permutation %s steered, %d children)" % (t, n, role, nd["name"], "1" if which == 1 else "1 and 2", nd["count"])
+                nd["kstar"] = INTERIOR[n % len(INTERIOR)]
+                nd["dev"] = self.ctx.params_upload(*cv.params_arrays(nd["params"]))
+                out.append(nd)
+            self.by_t[t] = out
+        return [nd for nd in self.by_t[t] if roles is None or nd["role"] in roles]
+
+    def digest(self, nd, pos0, k, children):
+        """pyref's digest of node k (not the steered one) of a level starting at pos0 under the set nd, memoised: the children of a crafted level
+        depend on the index alone"""
+        key = (nd["id"], pos0, k, children.shape[0])
+        if key not in self.memo:
+            self.memo[key] = cv.node_digest(nd["params"], LEVEL, pos0 + k, LABEL, children)
+        return self.memo[key]
+
+    def free(self):
+        for sets in self.by_t.values():
+            for nd in sets:
+                nd["dev"].free()
+        self.by_t = {}
+
+
+@pytest.fixture(scope="module")
+def steered(gpu_ctx):
+    s = SteeredSets(gpu_ctx)
+    yield s
+    s.free()
+
+
+def check_steered_level(ctx, steered, nd, nodes, kstar, last, forms, sample):
+    """hash_ds_level under the steered set nd over a crafted level with the steered node at index kstar: the steered node against the digest the
+    construction predicts, the nodes of `sample` against pyref under the same set, in every form."""
+    t = nd["t"]; arity = t - 1
+    ch, pos0 = cv.steered_level(base_params(t), nd, nodes, kstar, last_children=last)
+    sample = set(k for k in sample if 0 <= k < nodes and k != kstar)
+    for k in range(2, nodes, 7):                                              # top up to 32 others (the same ones at every level size)
+        if len(sample) >= 32:
+            break
+        if k != kstar:
+            sample.add(k)
+    sample = sorted(sample)
+    assert len(sample) >= 32
+    want = {k: steered.digest(nd, pos0, k, ch[k * arity:(k + 1) * arity]) for k in sample}
+    want[kstar] = nd["digest"]
+    for name, opts in forms.items():
+        got = with_options(ctx, opts, lambda: ctx.hash_ds_level(nd["dev"], arity, LEVEL, pos0, LABEL, ch))
+        assert got.shape == (nodes, 4)
+        for k in [kstar] + sample:
+            assert (got[k] == want[k]).all(), "form %s, %d nodes, %s, steered node %d (lane %d, DS position %d): node %d (lane %d)%s differs from pyref under the same set: got %s want %s; " \
+                "full-round targets %s; partial-round targets %s" % (name, nodes, nd["id"], kstar, kstar % 64, nd["pos"], k, k % 64, " — the steered one" if k == kstar else "",
+                                                                       cv.hex_limbs(got[k]), cv.hex_limbs(want[k]), [cv.hex_limbs(cv.raw_array(r)) for r in nd["tf"]] if k == kstar else "-",
+                                                                       cv.hex_limbs(cv.raw_array(nd["tp"])) if k == kstar else "-")
+
+
+def test_steered_sets_cover_every_round_half_and_block_position(steered):
+    """Coverage by computation, over the values the S-boxes of the main sets really deliver (recomputed from the uploaded constants' trajectory, not
+    read off the schedule): every stored corner in every one of the 8 full rounds — for t = 17 in both element halves X and Y of the wave pair
+    (PairCfg::NX) — and as x_q at every block position q mod 4; each uniform schedule present.  The number of sets is what the windows need:
+    9 uniform schedules and ceil(37 / 8) = 5 rotations for t = 17 (the X half has 8 elements), ceil(37 / 9) = 5 for t = 9.
+    Deriving the tables of an uploaded set is host work that grows like t^4: measured on a slow development CPU 0.08 s at t = 9, 0.37 s at
+    t = 17, 2.3 s at t = 33 and 18 s at t = 65; on the MI355X host this whole test, 38 uploads, takes 1.1 s.  Hence no set more than needed."""
+    corners = cv.stored_corners(P)
+    for t in (17, 9):
+        main = steered.sets(t, ("main",))
+        assert len(main) == 14
+        got = []
+        for nd in main:
+            of, op, _ = cv.sbox_outputs(nd["params"], nd["state"])
+            assert of == nd["tf"] and op == nd["tp"], nd["id"]
+            got.append((of, op))
+        full, part, uni = cv.schedule_coverage(t, got)
+        assert full.shape == (len(corners), 8, 2 if t == 17 else 1)
+        assert full.all(), "t = %d: corner / full round / half never met: %s" % (t, np.argwhere(~full)[:5].tolist())
+        assert part.all(), "t = %d: corner / q mod 4 never met: %s" % (t, np.argwhere(~part)[:5].tolist())
+        assert uni >= {P - 1, (1 << 254) - 1, 1 << 254, cv.alt29(0), cv.alt29(1)} | set(cv.carry_chains())
+        for nd in steered.sets(t, ("both",)):                                 # the second permutation starts from the first one's input state
+            of, op, end = cv.sbox_outputs(nd["params"], nd["state"])
+            assert of == nd["tf"] and op == nd["tp"], nd["id"]
+            kids = [cv.raw_to_int(x) * pow(R, -1, P) % P for x in nd["children"]]
+            absorb = kids[t - 5:] + [1] + [0] * (t - 5)
+            assert [(end[i] + absorb[i]) % P for i in range(t)] == nd["state"] and end[0] * R % P == cv.raw_to_int(nd["digest"]), nd["id"]
+
+
+# (t, nodes, children of a ragged last node): the node counts that select each form — five-wave up to 256, one-wave up to 4096, k_node16_pair above
+# (k_hash_ds2 with merkle_node16_pair = 0, and for a ragged level) — and for t = 9, which has no node16 form, both sides of 4096 and a ragged level
+STEERED_LEVELS = [(17, 256, None), (17, 257, None), (17, 4097, None), (17, 4100, 5), (9, 300, None), (9, 4097, None), (9, 4098, 3)]
+
+
+@pytest.mark.parametrize("t,nodes,last", STEERED_LEVELS)
+def test_steered_nodes_every_merkle_level_form(gpu_ctx, steered, t, nodes, last):
+    """A node whose S-box outputs are chosen stored corners in ALL rounds — 8 t full-round outputs and rp partial-round outputs x_q — through every
+    form of a Merkle level, at the node counts that select the forms and under every option that changes the kernel.  Main sets and the sets with
+    both permutations steered sit at lanes 0 / 31 / 32 / 63 of a 64-sponge block; the edge sets in the last partial block; one set is the ragged
+    last node (one permutation).  The steered node must equal the digest the construction predicts, and >= 32 other nodes (crafted_level children)
+    per call pyref's hash_with_ds_dynamic under the same uploaded set.
+    Measured on the MI355X host: 3.7 s for the first t = 17 case (it computes the pyref digests the later ones share), 0.5 to 1.8 s for the others;
+    pyref, not the device, is the time of this test."""
+    forms = FORMS if t == 17 else {k: v for k, v in FORMS.items() if "node16" not in k}
+    rng = np.random.default_rng(nodes)
+    tail = [nodes - 1, nodes - 2, (nodes - 1) // 64 * 64, (nodes - 1) // 64 * 64 - 1, (nodes - 1) // 32 * 32 - 1] + rng.integers(0, nodes, 4).tolist()
+    for nd in steered.sets(t, ("main", "both")):
+        check_steered_level(gpu_ctx, steered, nd, nodes, nd["kstar"], last, forms, SHARED + tail)
+    n_full = nodes if last is None else nodes - 1
+    if n_full % 64:                                                           # a last partial block: its full nodes, first permutation and both
+        for j, nd in enumerate(steered.sets(t, ("edge",))):
+            kstar = n_full - 1 - j if n_full % 64 > j else n_full - 1
+            check_steered_level(gpu_ctx, steered, nd, nodes, kstar, last, forms, SHARED[:24] + tail + rng.integers(0, nodes, 6).tolist())
+    if last is not None:
+        for nd in steered.sets(t, ("ragged",)):
+            check_steered_level(gpu_ctx, steered, nd, nodes, nodes - 1, last, forms, SHARED[:24] + tail + rng.integers(0, nodes, 6).tolist())
+
+
+@pytest.mark.parametrize("t", [33, 65])
+def test_steered_nodes_wide_widths(gpu_ctx, steered, t):
+    """Steered nodes through k_hash_ds_wave and the lane form at t = 33 and t = 65, at index 0 and at the last index of a level of 34 nodes, 33
+    others per call against pyref.  t = 33: one set with the first permutation steered, one with both.  t = 65: ONE set, both permutations
+    steered: the derivation of an uploaded set's tables grows like t^4 and a pyref permutation takes 0.13 s at this width.  Measured on the
+    MI355X host: 1.9 s (t = 33) and 7.0 s (t = 65), nearly all of it on the CPU.  No t = 129 set: its derivation takes far longer."""
+    nodes = 34
+    sets = steered.sets(t)
+    for nd, kstar in ((sets[0], 0), (sets[-1], nodes - 1)):
+        check_steered_level(gpu_ctx, steered, nd, nodes, kstar, None, WIDE_FORMS, range(nodes))
+
+
+@pytest.mark.parametrize("t", [9, 17, 33, 65])
+def test_permute_on_steered_states(gpu_ctx, steered, t):
+    """k_permute_batch under every steered set of the width: 65 copies of the steered state (more than one 64-lane block) and 5 other states,
+    against the end state the construction predicts and pyref under the same set."""
+    rng = np.random.default_rng(t)
+    others = [[int.from_bytes(rng.bytes(40), "little") % P for _ in range(t)] for _ in range(3)] + [[0] * t, [P - 1] * t]
+    for nd in steered.sets(t):
+        if nd["role"] not in ("main", "first", "last", "both"):
+            continue
+        sp = nd["params"]
+        end = cv.sbox_outputs(sp, nd["state"])[2]
+        st = np.stack([cv.to_stored(nd["state"])] * 65 + [cv.to_stored(s) for s in others])
+        want = np.stack([cv.to_stored(end)] * 65 + [cv.to_stored(pyref.permute(s, sp)) for s in others])
+        got = gpu_ctx.permute(st, nd["dev"])
+        bad = np.nonzero((got != want).any(axis=(1, 2)))[0]
+        assert bad.size == 0, "k_permute_batch, %s: state %d (0..64 are the steered one) differs from pyref: got %s want %s" % (nd["id"], bad[0], cv.hex_limbs(got[bad[0]])[:2], cv.hex_limbs(want[bad[0]])[:2])
 
 
 @pytest.mark.parametrize("n", [2048, 2049, 4096, 4097, 1 << 13])
