@@ -217,11 +217,19 @@ int32_t stark_poseidon_hash_with_ds(stark_ctx_t* ctx, stark_params_t* p, const u
     return hash_stream(ctx, p, 1, nullptr, 0, in, cnt, load_fr(ds_tag), 1, out);
 }
 }  // extern "C"
+// The 8-round partial blocks of the t = 17 wave-pair kernels: option poseidon_block8 (default 1) and a parameter set with rp % 8 == 0.  Such a set
+// without its tables on the device is an error, never a quiet return to blocks of 4.
+static int32_t pair_block8_form(stark_ctx* ctx, const stark_params* p, bool* on) {
+    *on = ctx->opt.poseidon_block8 && p->dev.t == 17 && p->dev.rp % 8 == 0;
+    if (*on && (!p->dev.blk8_efrag || !p->dev.blk8_lfrag || !p->dev.blk8_unit_frag || !p->dev.gamma8_29)) return ctx->fail(STARK_ERR_UNSUPPORTED, "poseidon_block8: the parameter set has no block-8 tables");
+    return STARK_OK;
+}
 // One launch of hash_with_ds_dynamic over the hashes of a DS stream (hash_ds_on), in the form poseidon_form picks for a Merkle level of that many nodes.
 template <class DS>
 static int32_t launch_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, const DS& D, fr_t* out) {
     if (!D.n_out) return STARK_OK;
     const int t = p->dev.t; const unsigned nodes = (unsigned)D.n_out, pairs = (unsigned)((D.n_out + 63) / 64);
+    bool b8 = false; STARK_TRY(pair_block8_form(ctx, p, &b8));
     switch (poseidon_form(ctx, p, PoseidonOp::MerkleLevel, D.n_out)) {
     case PoseidonForm::FiveWave: hipLaunchKernelGGL(k_hash_ds_chain<DS>, dim3(nodes), dim3(320), chain_lds_bytes(), st, p->dev, D, row_consts_of(ctx), out); break;
     case PoseidonForm::OneWave:
@@ -232,11 +240,13 @@ static int32_t launch_ds(stark_ctx_t* ctx, hipStream_t st, stark_params_t* p, co
         if constexpr (std::is_same<DS, DsStream>::value) {
             // a node level whose every node has 16 children (no ragged last node): the fixed two-permutation kernel
             if (t == 17 && ctx->opt.merkle_node16_pair && D.mode == 0 && D.arity == 16 && D.n_in == 16 * D.n_out) {
-                hipLaunchKernelGGL(k_node16_pair, dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D.arity_f, D.level_f, D.label_f, D.pos0, D.in0, D.n_out, out);
+                if (b8) hipLaunchKernelGGL(k_node16_pair<true>, dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D.arity_f, D.level_f, D.label_f, D.pos0, D.in0, D.n_out, out);
+                else hipLaunchKernelGGL(k_node16_pair<false>, dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D.arity_f, D.level_f, D.label_f, D.pos0, D.in0, D.n_out, out);
                 break;
             }
         }
-        if (t == 17) hipLaunchKernelGGL((k_hash_ds2<17, DS>), dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D, out);
+        if (t == 17 && b8) hipLaunchKernelGGL((k_hash_ds2<17, DS, true>), dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D, out);
+        else if (t == 17) hipLaunchKernelGGL((k_hash_ds2<17, DS>), dim3(pairs), dim3(128), pair_lds_bytes(17), st, p->dev, D, out);
         else hipLaunchKernelGGL((k_hash_ds2<9, DS>), dim3(pairs), dim3(128), pair_lds_bytes(9), st, p->dev, D, out);
         break;
     case PoseidonForm::Wide:
@@ -261,11 +271,11 @@ int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const
 static void lds_attr(const void* kernel) { (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds); }
 template <class DS>
 static void ds_attrs() {
-    lds_attr((const void*)k_hash_ds<DS>); lds_attr((const void*)k_hash_ds2<17, DS>); lds_attr((const void*)k_hash_ds2<9, DS>); lds_attr((const void*)k_hash_ds_chain<DS>);
+    lds_attr((const void*)k_hash_ds<DS>); lds_attr((const void*)k_hash_ds2<17, DS>); lds_attr((const void*)k_hash_ds2<17, DS, true>); lds_attr((const void*)k_hash_ds2<9, DS>); lds_attr((const void*)k_hash_ds_chain<DS>);
 }
 void stark::poseidon_set_attrs() {
     ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>(); ds_attrs<DsBatchPairPtrStream>();
-    for (const void* k : {(const void*)k_leaf_pair, (const void*)k_permute_batch, (const void*)k_tr_hash, (const void*)k_hash_stream, (const void*)k_leaf_pair2, (const void*)k_node16_pair,
+    for (const void* k : {(const void*)k_leaf_pair, (const void*)k_permute_batch, (const void*)k_tr_hash, (const void*)k_hash_stream, (const void*)k_leaf_pair2<false>, (const void*)k_leaf_pair2<true>, (const void*)k_node16_pair<false>, (const void*)k_node16_pair<true>,
                           (const void*)k_tr_hash_chain, (const void*)k_leaf_pair_chain, (const void*)k_tr_stream_chain, (const void*)k_tr_batch_chain})
         lds_attr(k);
 }
@@ -301,10 +311,14 @@ int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const f
     stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
     fr_t* init = nullptr; STARK_TRY(ctx_leaf_init(ctx, &init));
     const LeafStream L{init, f, f_next, m, n};
+    bool b8 = false; STARK_TRY(pair_block8_form(ctx, tp, &b8));
     switch (poseidon_form(ctx, tp, PoseidonOp::LeafLayer, n)) {
     case PoseidonForm::FiveWave: hipLaunchKernelGGL(k_leaf_pair_chain, dim3((unsigned)n), dim3(320), chain_lds_bytes(), st, tp->dev, row_consts_of(ctx), L, h); break;
     case PoseidonForm::OneWave: hipLaunchKernelGGL(k_leaf_pair_coop, dim3((unsigned)n), dim3(64), coop_lds_bytes(17), st, tp->dev, L, h); break;
-    case PoseidonForm::WavePair: hipLaunchKernelGGL(k_leaf_pair2, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, init + 17, f, f_next, n, m, h); break;
+    case PoseidonForm::WavePair:
+        if (b8) hipLaunchKernelGGL(k_leaf_pair2<true>, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, init + 17, f, f_next, n, m, h);
+        else hipLaunchKernelGGL(k_leaf_pair2<false>, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, init + 17, f, f_next, n, m, h);
+        break;
     default: hipLaunchKernelGGL(k_leaf_pair, dim3((unsigned)((n + 63) / 64)), dim3(64), poseidon_lds(17, 64), st, tp->dev, L, h);
     }
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;

@@ -224,6 +224,15 @@ struct KernelConsts {
     //   chain_g [rp][9][64]   limb i of Gamma_{q,p} for lane q >= p + 2, else 0   (p = first index)
     //   chain_w [rp][t-1][9]  w_{p,j}
     std::vector<uint32_t> chain_a, chain_g, chain_w;
+    // t = 17 and rp a multiple of 8: the partial rounds in BLOCKS OF 8 whose two long products run on the matrix cores (poseidon_pair.hpp pair_block8).
+    // Inside block b (rounds 8b .. 8b+7), with the lanes s_j at their block-start values and y_q = (X_q + c_q)^5:
+    //     X_{q+1} = E_q + a_q y_q + sum_{p<q} Gamma_{q,p} y_p,   E_q = sum_j u_{q,j} s_j,   Gamma_{q,p} = sum_j u_{q,j} w_{p,j};   s_j <- s_j + sum_p w_{p,j} y_p.
+    //   blk8_efrag [rp/8][8][16]  fragment (mfma_frag_of) of u_{q,j}, UNSCALED: its inputs are lanes in stored form
+    //   blk8_lfrag [rp/8][16][8]  fragment of w_{p,j} * 2^20 (its inputs are fr_pow5_r29 outputs, as in the full rounds), lane-major: row j = 1..16, then p;
+    //                             after the last block ONE fragment of the constant 1: the K-step that adds the lane's own stored value
+    //   gamma8_29  [rp/8][28][9]  Gamma_{q,p} at q (q - 1) / 2 + p, scaled like gamma29
+    std::vector<int8_t> blk8_efrag, blk8_lfrag;
+    std::vector<uint32_t> gamma8_29;
     bool ok = false;
 };
 // scaled(i) == true: the entry multiplies an S-box output, which fr_pow5_r29 delivers as x^5 / 2^20 (fr29.hpp)
@@ -242,21 +251,23 @@ template <class Pred> inline std::vector<uint32_t> to_radix29(const std::vector<
 // so the digit sums S[c] = sum_{e,b} d_{i,e,b}[c] * xd_e[b], c = 0..31, are ONE 32-row tile of a dense int8 product (no structural zeros), and
 // sum_c S[c] 256^c needs no Montgomery step, only a reduction of its top bits.  Fragment (i*t + e) holds, for lane l (tile row = output digit
 // c = l & 31, K half kh = l >> 5), the 16 bytes j -> d_{i,e,16 kh + j}[c]: the left operand of the K-step of element e.  t*t*64*16 bytes.
-inline std::vector<int8_t> mfma_frags(const std::vector<fr_t>& mat, int t) {
-    std::vector<int8_t> out((size_t)t * t * 64 * 16, 0);
-    const fr_t scale = fr_from_u64<PF>(1ull << FR29_SBOX_SHIFT), k256 = fr_from_u64<PF>(256);
-    for (int i = 0; i < t; ++i) for (int e = 0; e < t; ++e) {
-        fr_t g = h_mul(mat[(size_t)i * t + e], scale);                        // Montgomery form of M[i][e] * 2^20 * 256^b, b = 0, 1, ...
-        int8_t d[32][32];                                                     // d[b][c]
-        for (int b = 0; b < 32; ++b, g = h_mul(g, k256)) {
-            const fr_t c = fr_to_canonical<PF>(g); int cy = 0;
-            for (int k = 0; k < 32; ++k) { const int v = (int)((c.v[k >> 2] >> (8 * (k & 3))) & 0xff) + 0x80 + cy; cy = v >> 8; d[b][k] = (int8_t)((v & 0xff) - 0x80); }
-        }
-        for (int l = 0; l < 64; ++l) for (int j = 0; j < 16; ++j)
-            out[(((size_t)i * t + e) * 64 + l) * 16 + j] = d[16 * (l >> 5) + j][l & 31];
+// One fragment (1 KiB): g is the Montgomery form of the coefficient, its scale included.
+inline void mfma_frag_of(fr_t g, int8_t* out) {
+    const fr_t k256 = fr_from_u64<PF>(256);
+    int8_t d[32][32];                                                         // d[b][c]
+    for (int b = 0; b < 32; ++b, g = h_mul(g, k256)) {                        // Montgomery form of coefficient * 256^b, b = 0, 1, ...
+        const fr_t c = fr_to_canonical<PF>(g); int cy = 0;
+        for (int k = 0; k < 32; ++k) { const int v = (int)((c.v[k >> 2] >> (8 * (k & 3))) & 0xff) + 0x80 + cy; cy = v >> 8; d[b][k] = (int8_t)((v & 0xff) - 0x80); }
     }
+    for (int l = 0; l < 64; ++l) for (int j = 0; j < 16; ++j) out[(size_t)l * 16 + j] = d[16 * (l >> 5) + j][l & 31];
+}
+// rows x cols fragments of a row-major matrix, every entry times `scale` (Montgomery form; fr_one for none)
+inline std::vector<int8_t> mfma_frags(const fr_t* mat, int rows, int cols, const fr_t& scale) {
+    std::vector<int8_t> out((size_t)rows * cols * 64 * 16, 0);
+    for (int i = 0; i < rows; ++i) for (int e = 0; e < cols; ++e) mfma_frag_of(h_mul(mat[(size_t)i * cols + e], scale), &out[((size_t)i * cols + e) * 64 * 16]);
     return out;
 }
+inline std::vector<int8_t> mfma_frags(const std::vector<fr_t>& mat, int t) { return mfma_frags(mat.data(), t, t, fr_from_u64<PF>(1ull << FR29_SBOX_SHIFT)); }
 // Gauss-Jordan inverse of an n x n matrix (row-major); returns false when singular.
 inline bool mat_inverse(std::vector<fr_t> a, int n, std::vector<fr_t>& inv) {
     inv.assign((size_t)n * n, h_zero()); for (int i = 0; i < n; ++i) inv[(size_t)i * n + i] = h_one();
@@ -332,6 +343,26 @@ inline KernelConsts make_kernel_consts(const PoseidonConsts& c) {
     k.sparse29 = to_radix29(k.sparse, a_and_w); k.gamma29 = to_radix29(k.gamma, all);
     k.mds29 = to_radix29(k.mds, all); k.mds_pre29 = to_radix29(k.mds_pre, all);
     if (t == 17) { k.mds_frag = mfma_frags(k.mds, t); k.mds_pre_frag = mfma_frags(k.mds_pre, t); }      // the wave-pair kernels' full rounds (poseidon_pair.hpp)
+    if (t == 17 && c.rp % 8 == 0) {                                                                      // blocks of 8 partial rounds on the matrix cores (poseidon_pair.hpp)
+        const int nb = c.rp / 8, w = 2 * t - 1;
+        const fr_t s20 = fr_from_u64<PF>(1ull << FR29_SBOX_SHIFT);
+        std::vector<fr_t> g8((size_t)nb * 28, h_zero()), um((size_t)8 * n), wm((size_t)n * 8);
+        for (int b = 0; b < nb; ++b) {
+            for (int q = 0; q < 8; ++q) for (int j = 1; j < t; ++j) {
+                um[(size_t)q * n + (j - 1)] = k.sparse[(size_t)(8 * b + q) * w + j];
+                wm[(size_t)(j - 1) * 8 + q] = k.sparse[(size_t)(8 * b + q) * w + t - 1 + j];
+            }
+            const std::vector<int8_t> ef = mfma_frags(um.data(), 8, n, h_one()), lf = mfma_frags(wm.data(), n, 8, s20);
+            k.blk8_efrag.insert(k.blk8_efrag.end(), ef.begin(), ef.end()); k.blk8_lfrag.insert(k.blk8_lfrag.end(), lf.begin(), lf.end());
+            for (int q = 1; q < 8; ++q) for (int p2 = 0; p2 < q; ++p2) {
+                fr_t acc = h_zero();
+                for (int j = 0; j < n; ++j) acc = h_add(acc, h_mul(um[(size_t)q * n + j], wm[(size_t)j * 8 + p2]));
+                g8[(size_t)b * 28 + q * (q - 1) / 2 + p2] = acc;
+            }
+        }
+        k.blk8_lfrag.resize(k.blk8_lfrag.size() + 1024); mfma_frag_of(h_one(), &k.blk8_lfrag[k.blk8_lfrag.size() - 1024]);
+        k.gamma8_29 = to_radix29(g8, all);
+    }
     if (t == 17 && c.rp == 64) {                                                                         // the five-wave latency kernel (poseidon_chain.hpp)
         const int rp = c.rp, w = 2 * t - 1;
         const fr_t scale = fr_from_u64<PF>(1ull << 25);

@@ -39,7 +39,7 @@ static void bind(HcParams* P) {
     P->dev.t = P->kc.t; P->dev.rf = P->kc.rf; P->dev.rp = P->kc.rp; P->dev.rc_full = P->kc.rc_full.data(); P->dev.rc_partial = P->kc.rc_partial.data();
     P->dev.lu = P->kc.lu.data(); P->dev.lu_pre = P->kc.lu_pre.data(); P->dev.row0 = P->kc.row0.data(); P->dev.sparse = P->kc.sparse.data(); P->dev.mds = P->kc.mds.data(); P->dev.mds_pre = P->kc.mds_pre.data(); P->dev.gamma = P->kc.gamma.data();
     P->dev.lu29 = P->kc.lu29.data(); P->dev.lu_pre29 = P->kc.lu_pre29.data(); P->dev.row0_29 = P->kc.row0_29.data(); P->dev.sparse29 = P->kc.sparse29.data(); P->dev.gamma29 = P->kc.gamma29.data(); P->dev.mds29 = P->kc.mds29.data(); P->dev.mds_pre29 = P->kc.mds_pre29.data();
-    P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr;
+    P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr; P->dev.blk8_efrag = nullptr; P->dev.blk8_lfrag = nullptr; P->dev.blk8_unit_frag = nullptr; P->dev.gamma8_29 = nullptr;
     P->dev.chain_a = P->kc.chain_a.empty() ? nullptr : P->kc.chain_a.data(); P->dev.chain_g = P->kc.chain_g.empty() ? nullptr : P->kc.chain_g.data(); P->dev.chain_w = P->kc.chain_w.empty() ? nullptr : P->kc.chain_w.data();
 }
 
@@ -225,6 +225,90 @@ int hc_mfma_finish(const int32_t* sums, size_t n, uint64_t* out) {
         int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
         mfma_fold_rows(col, lo, hi);
         st4(out + 4 * s, mfma_finish_cols(col));
+    }
+    return 0;
+}
+// ---- the 8-round partial blocks of the t = 17 wave-pair kernels (poseidon_pair.hpp pair_block8), mirrored on the host with the tables the device gets ----
+// One emulated 32-row tile: K K-steps, fragment k (1 KiB, host_util.hpp mfma_frag_of: lane l holds A[row l & 31][16 (l >> 5) + j]) against the recoded
+// operand xd[k]; S[row] = sum_k sum_b A_k[row][b] xd_k[b].  -2 when a digit sum leaves the finishing step's domain |S| < 2^24.
+static int blk8_tile_sums(const int8_t* const* frag, const fr_t* xd, int K, int32_t* S) {
+    for (int r = 0; r < 32; ++r) { int64_t acc = 0;
+        for (int k = 0; k < K; ++k) for (int kh = 0; kh < 2; ++kh) { const int8_t* a = frag[k] + (size_t)(r + 32 * kh) * 16;
+            const int8_t* b = reinterpret_cast<const int8_t*>(xd[k].v) + 16 * kh; for (int j = 0; j < 16; ++j) acc += (int64_t)a[j] * b[j]; }
+        if (acc >= (1 << 24) || acc <= -(1 << 24)) return -2; S[r] = (int32_t)acc; }
+    return 0;
+}
+static fr_t blk8_finish_sums(const int32_t* S) {      // the accumulator rows as the two lanes of a sponge receive them, fold, finish (mfma_digits.hpp)
+    int32_t lo[16], hi[16];
+    for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
+    int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
+    mfma_fold_rows(col, lo, hi);
+    return mfma_finish_cols(col);
+}
+static int blk8_tile(const int8_t* const* frag, const fr_t* xd, int K, fr_t& out) { int32_t S[32]; const int rc = blk8_tile_sums(frag, xd, K, S); if (rc) return rc; out = blk8_finish_sums(S); return 0; }
+// A whole t = 17 permutation in the wave-pair kernels' block-8 form: full rounds through the residue tables of M and B_1 M, the partial rounds in
+// blocks of 8 — lanes recoded, E rows (8 x 16 tile rows), y_q = fr_pow5_r29, a_q y_q + sum Gamma y_p from sparse29 / gamma8_29, lane rows with the
+// unit fragment as the ninth K-step — with blk8_efrag / blk8_lfrag / gamma8_29 as uploaded.  -1: the set has no block-8 tables; -2: a digit sum out of range.
+int hc_permute_block8(void* h, uint64_t* states, size_t n) {
+    HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc; const int t = k.t, half = k.rf / 2, W = 2 * t - 1;
+    if (t != 17 || k.blk8_efrag.empty() || k.mds_frag.empty()) return -1;
+    const int8_t* unit = k.blk8_lfrag.data() + k.blk8_lfrag.size() - 1024;
+    std::vector<fr_t> st(t), xd(t), o(t);
+    auto full = [&](int r, const std::vector<int8_t>& F) -> int {
+        for (int j = 0; j < t; ++j) xd[j] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(st[j], k.rc_full[(size_t)r * t + j])));
+        for (int i = 0; i < t; ++i) { const int8_t* fr[17]; for (int e = 0; e < t; ++e) fr[e] = &F[((size_t)i * t + e) * 1024]; const int rc = blk8_tile(fr, xd.data(), t, o[i]); if (rc) return rc; }
+        st = o; return 0; };
+    for (size_t s = 0; s < n; ++s) {
+        for (int j = 0; j < t; ++j) st[j] = ld4(states + 4 * (s * t + j));
+        for (int r = 0; r < half; ++r) { const int rc = full(r, r == half - 1 ? k.mds_pre_frag : k.mds_frag); if (rc) return rc; }
+        fr_t s0 = st[0], rec[17], y[8], yd[9];
+        for (int j = 1; j < t; ++j) rec[j] = recode_signed(st[j]);
+        const int nb = k.rp / 8;
+        for (int b = 0; b < nb; ++b) {
+            const int8_t* ef = k.blk8_efrag.data() + (size_t)b * 8 * 16 * 1024; const int8_t* lf = k.blk8_lfrag.data() + (size_t)b * 16 * 8 * 1024;
+            for (int q = 0; q < 8; ++q) {
+                const int8_t* fr[16]; for (int j = 0; j < 16; ++j) fr[j] = ef + ((size_t)q * 16 + j) * 1024;
+                fr_t E; { const int rc = blk8_tile(fr, rec + 1, 16, E); if (rc) return rc; }
+                y[q] = fr_pow5_r29<PF>(fr_add<PF>(s0, k.rc_partial[8 * b + q]));
+                DotAcc acc; acc.init();
+                acc.mac(c29(k.sparse29.data(), (size_t)(8 * b + q) * W), y[q]);
+                for (int p2 = 0; p2 < q; ++p2) acc.mac(c29(k.gamma8_29.data(), (size_t)b * 28 + q * (q - 1) / 2 + p2), y[p2]);
+                s0 = fr_add<PF>(E, acc.finish());
+            }
+            for (int p2 = 0; p2 < 8; ++p2) yd[p2] = recode_signed(y[p2]);
+            for (int j = 1; j < t; ++j) {
+                const int8_t* fr[9]; for (int p2 = 0; p2 < 8; ++p2) fr[p2] = lf + ((size_t)(j - 1) * 8 + p2) * 1024; fr[8] = unit;
+                yd[8] = rec[j];
+                fr_t z; { const int rc = blk8_tile(fr, yd, 9, z); if (rc) return rc; }
+                if (b == nb - 1) st[j] = z; else rec[j] = recode_signed(z);
+            }
+        }
+        st[0] = s0;
+        for (int r = half; r < k.rf; ++r) { const int rc = full(r, k.mds_frag); if (rc) return rc; }
+        for (int j = 0; j < t; ++j) st4(states + 4 * (s * t + j), st[j]);
+    }
+    return 0;
+}
+// the block-8 tables of a set: which = 0 blk8_efrag, 1 blk8_lfrag (its last 1 KiB: the unit fragment), 2 gamma8_29 (bytes of the uint32 words);
+// copies at most cap bytes out, returns the table's length in bytes (0: the set has none)
+size_t hc_blk8_table(void* h, int which, void* out, size_t cap) {
+    HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc;
+    const void* src = which == 0 ? (const void*)k.blk8_efrag.data() : which == 1 ? (const void*)k.blk8_lfrag.data() : (const void*)k.gamma8_29.data();
+    const size_t len = which == 0 ? k.blk8_efrag.size() : which == 1 ? k.blk8_lfrag.size() : k.gamma8_29.size() * 4;
+    if (out && len) memcpy(out, src, std::min(cap, len));
+    return len;
+}
+// The lane product's finish with the base lane in the tile: n cases of 32 digit sums S_c (the eight y K-steps) and a canonical base; the unit
+// fragment's K-step against the recoded base is added to the sums (as the ninth K-step of pair_block8 does), then fold and finish:
+// -> canonical (sum_c S_c 256^c + base) mod r.  -1: a total digit sum outside |S| < 2^24.
+int hc_blk8_finish_with_base(void* h, const int32_t* sums, const uint64_t* bases, size_t n, uint64_t* out) {
+    HcParams* P = (HcParams*)h; if (P->kc.blk8_lfrag.empty()) return -3;
+    const int8_t* unit = P->kc.blk8_lfrag.data() + P->kc.blk8_lfrag.size() - 1024;
+    for (size_t s = 0; s < n; ++s) {
+        const fr_t bd = recode_signed(ld4(bases + 4 * s)); int32_t U[32], S[32];
+        if (blk8_tile_sums(&unit, &bd, 1, U)) return -1;
+        for (int c = 0; c < 32; ++c) { const int64_t v = (int64_t)sums[32 * s + c] + U[c]; if (v >= (1 << 24) || v <= -(1 << 24)) return -1; S[c] = (int32_t)v; }
+        st4(out + 4 * s, blk8_finish_sums(S));
     }
     return 0;
 }

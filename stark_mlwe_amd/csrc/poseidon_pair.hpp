@@ -11,7 +11,9 @@
 //                     output rows, Y the odd ones, each wave holding the whole state as operand registers;
 //                   - t = 9: as in-place L*(U*x) on the VALU, X taking the even rows and Y the odd rows of each step (rows
 //                     2k/2k+1 read only slots >= 2k, so a single barrier between the step's reads and its two writes keeps it race-free);
-//   * partial rounds, in blocks of 4 (see permute_core in poseidon_dev.hpp for the algebra):
+//   * partial rounds, t = 17 with the context option poseidon_block8 (the default): in blocks of 8 whose u-rows and lane updates are two matrix-core
+//     products (pair_block8 below);
+//   * partial rounds otherwise, in blocks of 4 (see permute_core in poseidon_dev.hpp for the algebra):
 //       phase 1  X runs the S-box chain: x_q, then a_q x_q + sum_{p<q} gamma x_p + its share (lanes 1..NXD) of the
 //                lane dot product from registers; Y computes the other lanes' part of every round's
 //                dot product from the block-start state and posts it in an LDS mailbox (one barrier per round);
@@ -203,6 +205,167 @@ __device__ __forceinline__ void pair_apply_mds_mfma(const PairState& s, const vo
     __syncthreads();
 }
 
+// ---- partial rounds in BLOCKS OF 8, both long products on the matrix cores (T = 17, rp % 8 == 0) ------------------------------------------------------
+// Algebra (host_util.hpp blk8_*): with the lanes s_1..s_16 at their block-start values and y_q = (X_q + c_q)^5,
+//     X_{q+1} = E_q + a_q y_q + sum_{p<q} Gamma_{q,p} y_p,   E_q = sum_j u_{q,j} s_j,   and at the end of the block   s_j <- s_j + sum_p w_{p,j} y_p.
+// The 8 x 16 E-product and the 16 x 8 lane product are residue-table products like the full rounds' (same tile, exchange, fold and finish):
+//   * the lanes live in LDS RECODED (signed digits) between the blocks, so a lane's slot is a B operand as it stands;
+//   * E-product: fragments of u_{q,j}, unscaled (the lanes are in stored form); |digit sum| <= 16 * 32 * 128 * 128 = 2^23;
+//   * lane product: fragments of w_{p,j} * 2^20 (the y are fr_pow5_r29 outputs) and, as a ninth K-step, the fragment of the constant 1 against the lane's
+//     own slot, which adds the base lane inside the tile: |digit sum| <= 9 * 32 * 128 * 128 = 4 718 592 < 2^24.  mfma_finish_cols holds for any
+//     |S_c| < 2^24, so both products end canonical and the lazy-lane bound of pair_lane_update does not apply to this form.
+// Schedule of a block (two barriers fewer than two blocks of 4, nothing on the chain waits for a lone row):
+//   X  runs nothing but the chain: y_q, a_q y_q (plus the gamma terms older than Y's YG per round) and X_{q+1} = that + H_q;
+//   Y  computes E_q INSIDE round q — B operands read from the lanes' slots as the MFMAs consume them (one row per round: 32 KB of LDS reads per about
+//      10 k cycles), the fragments of row q + 1 fetched while it sums the gamma terms — and posts H_q = E_q + sum Gamma_{q,p} y_p; one barrier per round;
+//   both then form their share of the lane product (X lanes 1..NLX, Y the rest), the next row's fragments in flight under the current row's fold.
+// The y reach the B layout without LDS: recode, then v_permlane32_swap(low half, high half).  Four slots are free during a block (slot 0: X holds
+// the chain value; the three extra ones): two rings of two, H (written by Y, read by X after the round's barrier) and y (the other way round).
+// Both waves keep y_0..y_7 in registers.  Measured stand-alone (tools/partial_block8.hip, profiles/partial_block8_prototype.jsonl): 119.7 k SIMD-cycles
+// per 8 rounds against 204.6 k for two blocks of 4.
+struct Blk8Tabs {
+    const mfma_v4i* efrag;     // [8][16][64]   row q, lane j = 1..16
+    const mfma_v4i* lfrag;     // [16][8][64]   lane j = 1..16, S-box output p
+    const mfma_v4i* unit;      // [64]          the constant 1
+    const uint32_t* a29;       // a_q at c29(a29, q * (2 T - 1)): the block's first row of sparse29
+    const uint32_t* g29;       // [28][9]       Gamma_{q,p} at q (q - 1) / 2 + p
+    const fr_t* rc;            // [8]
+};
+struct Blk8Cfg {
+    // Y's share of a round's gamma terms (the YG youngest) and X's share of the lane rows: 5 / 8 measured best, the neighbours within 1.5 %
+    // (YG 6 with NLX 8: +1.5 %, YG 6 with NLX 7: +0.2 %, YG 7 with NLX 9: +1.1 %; run-to-run spread 1.5 %)
+    static constexpr int YG = 5, NLX = 8;
+    __host__ __device__ static constexpr int ymail(int q) { return 17 + (q & 1); }
+    __host__ __device__ static constexpr int hmail(int q) { return (q & 1) ? 19 : 0; }
+};
+// exchange, fold, finish: the two accumulator tiles of a row -> the canonical field element of the lane's sponge
+__device__ __forceinline__ fr_t mfma_post(const mfma_v16i (&acc)[2]) {
+    mfma_v16i lo, hi;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
+        lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
+    }
+    int64_t col[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) col[k] = 0;
+    mfma_fold_rows(col, lo, hi);
+    return mfma_finish_cols(col);
+}
+// A is wave-uniform and the lane is added at the load: a scalar base plus one 32-bit lane offset
+__device__ __forceinline__ void blk8_load_frags16(mfma_v4i (&a)[16], const mfma_v4i* A, int lane) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) a[e] = (A + (size_t)e * 64)[lane];
+}
+template <int Q, int P, int LO, int HI>
+__device__ __forceinline__ void blk8_gterm(fr_wide29& acc, const Blk8Tabs& Tb, const fr_t (&yk)[8]) {          // gamma term p of round Q, if p is in [LO, HI)
+    if constexpr (P < Q && P >= LO && P < HI) fr_wide29_mac(acc, c29(Tb.g29, Q * (Q - 1) / 2 + P), fr29_unpack(yk[P]));
+}
+template <int Q, int LO, int HI>
+__device__ __forceinline__ void blk8_gterms(fr_wide29& acc, const Blk8Tabs& Tb, const fr_t (&yk)[8]) {
+    blk8_gterm<Q, 0, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 1, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 2, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 3, LO, HI>(acc, Tb, yk);
+    blk8_gterm<Q, 4, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 5, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 6, LO, HI>(acc, Tb, yk);
+}
+// round Q in wave X: at most 1 + 7 - YG terms, within fr29_max_terms
+template <int Q, int YG>
+__device__ __forceinline__ void blk8_round_x(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, fr_t (&yk)[8]) {
+    __builtin_amdgcn_sched_barrier(0);                     // keep the rounds apart: less register pressure
+    yk[Q] = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));
+    s.sto(Blk8Cfg::ymail(Q), yk[Q]);
+    fr_wide29 acc; fr_wide29_zero(acc);
+    fr_wide29_mac(acc, c29(Tb.a29, (size_t)Q * (2 * 17 - 1)), fr29_unpack(yk[Q]));
+    blk8_gterms<Q, 0, (Q - YG > 0 ? Q - YG : 0)>(acc, Tb, yk);
+    const fr_t part = fr_wide29_reduce<PF>(acc);
+    __syncthreads();                                       // barrier_Q: H_Q is posted
+    s0 = fr_add<PF>(part, s.ld(Blk8Cfg::hmail(Q)));
+}
+// round Q in wave Y.  a: the fragments of E row Q on entry, of row Q + 1 on exit
+template <int Q, int YG>
+__device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs& Tb, fr_t (&yk)[8], mfma_v4i (&a)[16]) {
+    __builtin_amdgcn_sched_barrier(0);
+    const int lane = s.lane, h = lane >> 5;
+    mfma_v16i acc[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            const uint4 u = s.st[(2 * (e + 1) + h) * 64 + 32 * ct + (lane & 31)];
+            acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[e], mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w}, acc[ct], 0, 0, 0);
+        }
+    if constexpr (Q < 7) blk8_load_frags16(a, Tb.efrag + (size_t)(Q + 1) * 16 * 64, lane);
+    fr_t hq = mfma_post(acc);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (Q > 0) {
+        fr_wide29 w; fr_wide29_zero(w);
+        blk8_gterms<Q, (Q - YG > 0 ? Q - YG : 0), Q>(w, Tb, yk);
+        hq = fr_add<PF>(hq, fr_wide29_reduce<PF>(w));
+    }
+    s.sto(Blk8Cfg::hmail(Q), hq);
+    __syncthreads();                                       // barrier_Q: y_Q is posted
+    yk[Q] = s.ld(Blk8Cfg::ymail(Q));
+}
+// One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; s0 = X_0 in wave X.  Ends with a barrier, the lanes recoded again,
+// or canonical after the permutation's last block.
+template <int YG, int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last) {
+    static_assert(YG >= 1 && YG <= 7 && NLX >= 1 && NLX <= 15, "shares");
+    static_assert(YG <= fr29_max_terms<PF>() && 1 + 7 - YG <= fr29_max_terms<PF>(), "Y sums YG terms, X up to 1 + 7 - YG, without a carry pass in between");
+    const int lane = s.lane, h = lane >> 5;
+    fr_t yk[8];
+    if (!s.isY) {
+        blk8_round_x<0, YG>(s, Tb, s0, yk); blk8_round_x<1, YG>(s, Tb, s0, yk); blk8_round_x<2, YG>(s, Tb, s0, yk); blk8_round_x<3, YG>(s, Tb, s0, yk);
+        blk8_round_x<4, YG>(s, Tb, s0, yk); blk8_round_x<5, YG>(s, Tb, s0, yk); blk8_round_x<6, YG>(s, Tb, s0, yk); blk8_round_x<7, YG>(s, Tb, s0, yk);
+    } else {
+        mfma_v4i a[16];
+        blk8_load_frags16(a, Tb.efrag, lane);
+        blk8_round_y<0, YG>(s, Tb, yk, a); blk8_round_y<1, YG>(s, Tb, yk, a); blk8_round_y<2, YG>(s, Tb, yk, a); blk8_round_y<3, YG>(s, Tb, yk, a);
+        blk8_round_y<4, YG>(s, Tb, yk, a); blk8_round_y<5, YG>(s, Tb, yk, a); blk8_round_y<6, YG>(s, Tb, yk, a); blk8_round_y<7, YG>(s, Tb, yk, a);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    mfma_v4i b[8][2];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const fr_t yr = recode_signed(yk[p]);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {      // afterwards b[p][ct] = half (lane >> 5) of y_p of sponge 32 ct + (lane & 31)
+            const auto sw = __builtin_amdgcn_permlane32_swap(yr.v[w], yr.v[4 + w], false, false);
+            b[p][0][w] = (int)sw[0]; b[p][1][w] = (int)sw[1];
+        }
+    }
+    const int j0 = s.isY ? NLX + 1 : 1, j1 = s.isY ? 16 : NLX;
+    const mfma_v4i aunit = Tb.unit[lane];
+    mfma_v4i a[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(j0 - 1) * 8 + p) * 64)[lane];
+#pragma unroll 1
+    for (int j = j0; j <= j1; ++j) {
+        mfma_v16i acc[2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], b[p][ct], acc[ct], 0, 0, 0);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            const uint4 u = s.st[(2 * j + h) * 64 + 32 * ct + (lane & 31)];
+            acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aunit, mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w}, acc[ct], 0, 0, 0);
+        }
+        const int jn = j < j1 ? j + 1 : j1;                // the last row fetches its own fragments again: in bounds, unused
+#pragma unroll
+        for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
+        const fr_t z = mfma_post(acc);
+        s.sto(j, last ? z : recode_signed(z));             // slot j is read by this wave alone, before this write
+    }
+    __syncthreads();
+}
+
 // s_j += w_{0,j} x0 + w_{1,j} x1 + w_{2,j} x2 + w_{3,j} x3   (one reduction)
 template <int T>
 __device__ __forceinline__ fr_t pair_lane_update(const uint32_t* sp, int j, const fr_t& base, const fr29_t& x0, const fr29_t& x1, const fr29_t& x2, const fr29_t& x3) {
@@ -218,8 +381,13 @@ __device__ __forceinline__ fr_t pair_lane_update(const uint32_t* sp, int j, cons
 
 // One permutation by the wave pair.  Precondition: state consistent (a barrier since the last write).
 // Returns lane 0 of the result in BOTH waves; with only0 the rest of the state is dead afterwards.
-template <int T>
+// BLK8 (T = 17, a parameter set with blk8 tables): the partial rounds in blocks of 8 (pair_block8) instead of blocks of 4.
+// Precondition of BLK8: when the partial rounds are entered, lanes 1..16 are CANONICAL (recode_signed needs x < r).  The full round before them leaves
+// them so (mfma_finish_cols); with r_begin >= rf / 2 no full round runs first and the caller's stores must be canonical (today's callers store fr_add
+// results and field elements from memory).
+template <int T, bool BLK8 = false>
 __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonDev& P, bool only0, int r_begin = 0) {
+    static_assert(!BLK8 || T == 17, "8-round blocks exist for t = 17");
     typedef PairCfg<T> Cfg;
     constexpr int NXD = Cfg::NXD, NXU = Cfg::NXU, W = 2 * T - 1;
     const int half = P.rf / 2;
@@ -229,6 +397,17 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
     }
     fr_t s0 = fr_zero<PF>();
     if (!s.isY) s0 = s.ld(0);
+    if constexpr (BLK8) {
+        for (int j = s.isY ? 9 : 1; j <= (s.isY ? 16 : 8); ++j) s.sto(j, recode_signed(s.ld(j)));        // canonical since the full round's finish
+        __syncthreads();
+        const int nb = P.rp / 8;
+#pragma unroll 1
+        for (int b = 0; b < nb; ++b) {
+            const Blk8Tabs Tb{reinterpret_cast<const mfma_v4i*>(P.blk8_efrag) + (size_t)b * 8 * 16 * 64, reinterpret_cast<const mfma_v4i*>(P.blk8_lfrag) + (size_t)b * 16 * 8 * 64,
+                              reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), c29(P.sparse29, (size_t)(8 * b) * W), c29(P.gamma8_29, (size_t)b * 28), P.rc_partial + 8 * b};
+            pair_block8<Blk8Cfg::YG, Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1);
+        }
+    } else
     for (int b = 0; b < P.rp / 4; ++b) {
         const uint32_t* sp = c29(P.sparse29, (size_t)(4 * b) * W);
         const uint32_t* g = c29(P.gamma29, (size_t)b * 6);
@@ -311,6 +490,7 @@ __device__ __forceinline__ PairState pair_setup(uint4* lds) {
 }
 
 // K3 (pair form): h[i] = hash_leaf_pair(f[i], f_next[i/m] or 0).  Block = 128 threads = 64 states.
+template <bool BLK8>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_leaf_pair2(PoseidonDev P, const fr_t* __restrict__ leafc, const fr_t* __restrict__ f,
                                                     const fr_t* __restrict__ f_next, size_t n, size_t m, fr_t* __restrict__ h) {
     extern __shared__ uint4 lds[];
@@ -330,12 +510,12 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
         s.sto(j, fr_add<PF>(leafc[j], fr_wide29_reduce<PF>(w)));
     }
     __syncthreads();
-    fr_t out = pair_permute<17>(s, P, true, 1);
+    fr_t out = pair_permute<17, BLK8>(s, P, true, 1);
     if (live && !s.isY) stg(h + i, out);
 }
 
 // K4 (pair form): one Merkle level / the pair-leaf level.
-template <int T, class DS>
+template <int T, class DS, bool BLK8 = false>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_hash_ds2(PoseidonDev P, DS D, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     constexpr int rate = T - 1;
@@ -362,7 +542,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
             }
         }
         __syncthreads();
-        res = pair_permute<T>(s, P, pidx + 1 == max_perm);
+        res = pair_permute<T, BLK8>(s, P, pidx + 1 == max_perm);
         __syncthreads();
     }
     if (live && !s.isY) stg(out + k0, res);
@@ -375,6 +555,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
 // is live across a permutation.  Measured (tools/node_rate.py, 2^19 nodes): 17.4 ms against 17.7 for k_hash_ds2<17>, 60 M perm/s against the leaf
 // kernel's 69: the rest of the gap is work, not spills — both permutations run round 0 in full (one more MFMA product than k_leaf_pair2's
 // closed-form round 0, about 1/8 of a permutation's full-round time).  Two inlined permutations measured faster than one in a loop (17.6 ms).
+template <bool BLK8>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_node16_pair(PoseidonDev P, fr_t arity_f, fr_t level_f, fr_t label_f, uint64_t pos0,
                                                     const fr_t* __restrict__ in, size_t n_out, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
@@ -393,7 +574,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
         s.sto(16, fr_zero<PF>());
     }
     __syncthreads();
-    pair_permute<17>(s, P, false);                 // ends with a barrier: the state is consistent
+    pair_permute<17, BLK8>(s, P, false);           // ends with a barrier: the state is consistent
     // perm 2: children 12..15 and the closing 1 into elements 0..4 (X's)
     if (!s.isY) {
 #pragma unroll
@@ -401,7 +582,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
         s.sto(4, fr_add<PF>(s.ld(4), fr_one<PF>()));
     }
     __syncthreads();
-    const fr_t res = pair_permute<17>(s, P, true);
+    const fr_t res = pair_permute<17, BLK8>(s, P, true);
     if (live && !s.isY) stg(out + k0, res);
 }
 

@@ -1,4 +1,5 @@
-// tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds:
+// tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds, and of
+// the lane product of the 8-round partial blocks with the base lane in the tile (finish with base):
 // the fragment tables (host_util.hpp mfma_frags) and the fold + finishing step (mfma_digits.hpp), against the portable field code.  Meant for a
 // sanitizer build; tools/mfma_finish_sanitize.sh builds it with AddressSanitizer + UBSan and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I stark_mlwe_amd/csrc tools/mfma_finish_check.cpp -o tools/bin/mfma_finish_check
@@ -82,6 +83,42 @@ int main() {
                 S[r] = (int32_t)acc; }
             fr_t want = host::h_zero(); for (int e = 0; e < 17; ++e) want = host::h_add(want, host::h_mul(host::h_mul(M[(size_t)i * 17 + e], k20), st[e]));
             ++n; if (!fr_eq(finish(S), want)) { if (bad < 5) fprintf(stderr, "product: mismatch pre %d rep %d row %d\n", pre, rep, i); ++bad; }
+        }
+    }
+    // ---- the lane product of the 8-round partial blocks (poseidon_pair.hpp pair_block8): the base lane enters the tile as a NINTH K-step against the
+    // fragment of the constant 1 (the last KiB of blk8_lfrag).  (i) finish with base: for every crafted total above (the extremes +-(2^24 - 1), the
+    // multiples of r and of 2^254) and 2000 of the random ones, and base in {0, 1, r - 1, random}: the y part S = total - unit K-step(base), the
+    // kernel's sum S + unit K-step(base) finished, against (sum_c S_c 256^c + base) mod r.  (ii) whole lane rows of block 0 and of the last block
+    // through the tables: eight y and a base at 0 / r - 1 / random, against base + sum_p w_{p,j} 2^20 y_p in the field code.
+    if (kc.blk8_lfrag.size() != (size_t)(8 * 16 * 8 + 1) * 1024 || kc.blk8_efrag.size() != (size_t)8 * 8 * 16 * 1024) { fprintf(stderr, "block-8 tables missing\n"); return 1; }
+    const int8_t* unit = kc.blk8_lfrag.data() + kc.blk8_lfrag.size() - 1024;
+    auto kstep = [](const int8_t* frag, const fr_t& xd, int64_t* S) {
+        for (int r = 0; r < 32; ++r) for (int kh = 0; kh < 2; ++kh) { const int8_t* a = frag + (size_t)(r + 32 * kh) * 16; const int8_t* b = reinterpret_cast<const int8_t*>(xd.v) + 16 * kh; for (int j = 0; j < 16; ++j) S[r] += (int64_t)a[j] * b[j]; } };
+    auto rand_fr = [&]() { fr_t v; for (int i = 0; i < 8; ++i) v.v[i] = (uint32_t)rnd(); v.v[7] &= 0x3fffffffu; return v; };
+    fr_t rm1; for (int i = 0; i < 8; ++i) rm1.v[i] = PF::P(i); rm1.v[0] -= 1;
+    fr_t one = host::h_zero(); one.v[0] = 1;
+    const size_t ncraft = cases.size() - 20000;
+    for (size_t ci = 0; ci < ncraft + 2000; ++ci) for (int bi = 0; bi < 4; ++bi) {
+        const fr_t base = bi == 0 ? host::h_zero() : bi == 1 ? one : bi == 2 ? rm1 : rand_fr();
+        int64_t U[32] = {0}; kstep(unit, recode_signed(base), U);
+        int32_t Sy[32], St[32]; bool in_domain = true;
+        for (int c = 0; c < 32; ++c) { if (U[c] > 32 * 128 * 128 || U[c] < -32 * 128 * 128) { fprintf(stderr, "unit K-step beyond its bound\n"); return 1; }
+            const int64_t y = (int64_t)cases[ci][c] - U[c]; Sy[c] = (int32_t)y; St[c] = (int32_t)(y + U[c]); if (St[c] > LIM || St[c] < -LIM) in_domain = false; }
+        if (!in_domain) { fprintf(stderr, "with base: total outside the domain\n"); return 1; }
+        ++n; if (!fr_eq(finish(St), fr_add<PF>(reference(Sy), base))) { if (bad < 5) fprintf(stderr, "finish with base: mismatch in case %zu base %d\n", ci, bi); ++bad; }
+    }
+    for (int blk : {0, 7}) for (int rep = 0; rep < 6; ++rep) {
+        fr_t y[8], yd[8];
+        for (int p = 0; p < 8; ++p) { y[p] = rep == 0 ? rm1 : rep == 1 ? host::h_zero() : rep == 2 ? ((p & 1) ? rm1 : host::h_zero()) : rand_fr(); yd[p] = recode_signed(y[p]); }
+        for (int j = 1; j < 17; ++j) {
+            const fr_t base = rep == 0 ? rm1 : rep == 1 ? host::h_zero() : rep == 2 ? rm1 : rand_fr();
+            int64_t S64[32] = {0};
+            for (int p = 0; p < 8; ++p) kstep(kc.blk8_lfrag.data() + (((size_t)blk * 16 + (j - 1)) * 8 + p) * 1024, yd[p], S64);
+            kstep(unit, recode_signed(base), S64);
+            int32_t S[32]; for (int c = 0; c < 32; ++c) { if (S64[c] > 9 * 32 * 128 * 128 || S64[c] < -9 * 32 * 128 * 128) { fprintf(stderr, "lane row beyond its bound\n"); return 1; } S[c] = (int32_t)S64[c]; }
+            fr_t want = base;
+            for (int p = 0; p < 8; ++p) want = host::h_add(want, host::h_mul(host::h_mul(kc.sparse[(size_t)(8 * blk + p) * 33 + 16 + j], k20), y[p]));
+            ++n; if (!fr_eq(finish(S), want)) { if (bad < 5) fprintf(stderr, "lane row: mismatch block %d rep %d lane %d\n", blk, rep, j); ++bad; }
         }
     }
     printf("{\"check\": \"residue tables and finishing step against the portable field code\", \"cases\": %ld, \"mismatches\": %ld}\n", n, bad);
