@@ -85,6 +85,9 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  *   "ntt_batch_max_elems" (1..2^28, default 2^24: the output elements of one pass of stark_ntt_batch_dev / stark_lde_batch_dev).
  *   "mle_log_tile" (3..12, default 12; -1 restores the default: the rounds one launch of stark_mle_evaluate_dev / _batch_dev folds),
  *   "mle_lane_contiguous" (0 | 1, default 0; -1 restores the default: a lane of those launches owns consecutive elements instead of interleaved ones; comparison).
+ *   "lagrange_max_partials" (1..2^28, default 2^21 elements = 64 MiB; -1 restores the default: the block partials one pass of
+ *   stark_lagrange_eval_on_h_batch_dev may hold; a pass of one point is always allowed),
+ *   "lagrange_wide_acc" (0 | 1, default 1; -1 restores the default: a lane's products of a column go through the lazy accumulator; comparison).
  *   "pool_poison" (0..255, default -1 = off; FOR TESTS ONLY: every pooled block the library hands to itself, recycled or fresh, and the NTT scratch vector are
  *   filled with this byte first, so a result that depends on a temporary nobody wrote changes with the byte.  Each fill synchronises the stream: the
  *   calls that promise "no synchronisation" do synchronise while it is set.  The long-lived tables are not filled).
@@ -222,6 +225,27 @@ int32_t stark_ali_merge(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, 
                         const uint64_t* beta4, const uint64_t* omega4, const uint64_t* z4, size_t n, uint64_t* f0, uint64_t* c_star4);
 int32_t stark_ali_merge_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, const uint64_t* r_opt,
                             const uint64_t* beta4, const uint64_t* omega4, const uint64_t* z4, size_t n, uint64_t* f0, uint64_t* c_star4);
+/* lagrange_eval_on_h(values, z, omega) (deep_ali/src/lib.rs:17-45): the value at z of the polynomial of degree < n whose evaluations on
+ * H = <omega> are `values`; host pointers, the reference's signature (uploads the column, synchronises, out4 on the host). */
+int32_t stark_lagrange_eval_on_h(stark_ctx_t* ctx, const uint64_t* values, size_t n, const uint64_t* z4, const uint64_t* omega4, uint64_t* out4);
+/* lagrange_eval_on_h (deep_ali/src/lib.rs:17-45) of a DEVICE-resident column of n elements at the point z4 (HOST) into out4 (DEVICE, one element);
+ * omega4: HOST.  The batch form below with one column and one point. */
+int32_t stark_lagrange_eval_on_h_dev(stark_ctx_t* ctx, const uint64_t* values, size_t n, const uint64_t* z4, const uint64_t* omega4, uint64_t* out4);
+/* lagrange_eval_on_h (deep_ali/src/lib.rs:17-45) of ncols columns at npoints points over one domain: cols is a HOST array of ncols DEVICE pointers
+ * (n elements each), z the HOST array of the npoints x 4 points, out npoints x ncols elements in DEVICE memory:
+ * out[p * ncols + c] = lagrange_eval_on_h(cols[c], z[p], omega), the reference's field element in stored (Montgomery, fully reduced) form and
+ * byte-equal to the single call on that column and point alone.  Outside H (z^n != 1) it is (z^n - 1)/n * sum_j v[j] omega^j / (z - omega^j);
+ * inside H (z = omega^j) it is v[j] itself, copied; points inside and outside H may share a call.  The weights omega^j / (z - omega^j) depend on
+ * the point only: the columns of a call share one batch inversion per point.  Stream-ordered, no host synchronisation: z and the pointer table are
+ * copied before the call returns.  The scratch (block partials) is bounded by cutting the points into passes ("lagrange_max_partials").
+ * n is a power of two, 1 <= n <= 2^30; n = 1 gives v[0] for every z.  omega4 == NULL means the radix-2 generator of size n, as in
+ * stark_ali_merge_shard_dev; a caller's omega must be a primitive n-th root of unity: the host checks omega^n = 1 and, for n >= 2,
+ * omega^(n/2) = -1, so the reference's "z in domain but not matching a power of omega" panic cannot arise.  Columns may repeat and are left
+ * intact.  ncols == 0 or npoints == 0 returns STARK_OK and writes nothing.  STARK_ERR_INVALID_ARG, checked on the host before anything is
+ * launched: a null ctx, cols, cols[c] or out; a null z with npoints > 0; n zero, not a power of two or above 2^30; an omega that fails the
+ * check above; an out range that overlaps a column.  (More than 2^24 columns in one call: STARK_ERR_UNSUPPORTED.) */
+int32_t stark_lagrange_eval_on_h_batch_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega4, size_t npoints,
+                                           const uint64_t* z, uint64_t* out);
 /* DeepAliRealBuilder::build_f0 (fri.rs:535-569): 4 column sponges, (z, beta) sampling, merge.
  * aux7 (optional, host): col digests A,S,E,T, seed_f, z, beta. */
 int32_t stark_build_f0(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, size_t n0, uint64_t* f0, uint64_t* aux7);

@@ -388,6 +388,13 @@ pub mod fri {
         ctx.chk(unsafe { stark_deep_fri_verify_batch(ctx.raw, proofs.len(), ptrs.as_ptr(), lens.as_ptr(), schedule.as_ptr(), schedule.len(), r, seed_z, ok.as_mut_ptr()) });
         ok.into_iter().map(|a| a == 1).collect()
     }
+    /// `lagrange_eval_on_h(values, z, omega) -> F` — deep_ali/src/lib.rs:17-45.  `omega` must be a primitive `values.len()`-th root of unity
+    /// (the library checks it, so the reference's "z in domain but not matching a power of omega" panic cannot arise); z inside H gives the value itself.
+    pub fn lagrange_eval_on_h(ctx: &Ctx, values: &[F], z: F, omega: F) -> F {
+        let mut out = F::from(0u64);
+        ctx.chk(unsafe { stark_lagrange_eval_on_h(ctx.raw, limbs(values), values.len(), limb1(&z), limb1(&omega), &mut out as *mut F as *mut u64) });
+        out
+    }
     /// `deep_ali_merge_evals(a, s, e, t, omega, z) -> (f0, z, c*)` — deep_ali/src/lib.rs:48-105.
     pub fn deep_ali_merge_evals(ctx: &Ctx, a: &[F], s: &[F], e: &[F], t: &[F], omega: F, z: F) -> (Vec<F>, F, F) {
         let n = a.len();

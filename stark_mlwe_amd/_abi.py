@@ -84,6 +84,9 @@ SIGNATURES = {
     "stark_fri_state_free": (i32, [vp]),
     "stark_ali_merge": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
     "stark_ali_merge_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+    "stark_lagrange_eval_on_h": (i32, [vp, vp, sz, vp, vp, vp]),
+    "stark_lagrange_eval_on_h_dev": (i32, [vp, vp, sz, vp, vp, vp]),
+    "stark_lagrange_eval_on_h_batch_dev": (i32, [vp, sz, vp, sz, vp, sz, vp, vp]),
     "stark_build_f0": (i32, [vp, vp, vp, vp, vp, sz, vp, vp]),
     "stark_build_f0_dev": (i32, [vp, vp, vp, vp, vp, sz, vp, vp]),
     "stark_deep_fri_prove": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, sz, sz, u64, vpp]),

@@ -323,7 +323,7 @@ class Context:
         self._chk(self.lib.stark_ctx_sync(self.h))
 
     def set_option(self, key: str, value: int):
-        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "poseidon_block8", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous", "pool_poison" (tests only: fills the library's pooled temporaries, synchronises).  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
+        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "poseidon_block8", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous", "lagrange_max_partials", "lagrange_wide_acc", "pool_poison" (tests only: fills the library's pooled temporaries, synchronises).  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
         self._chk(self.lib.stark_ctx_set_option(self.h, key.encode(), value))
 
     def trim(self):
@@ -702,6 +702,26 @@ class Context:
             raise StarkError(-1, "dimension mismatch")
         tab = (C.c_void_p * max(B, 1))(*[int(x) for x in tables])
         self._chk(self.lib.stark_mle_evaluate_batch_dev(self.h, B, tab, k, _ptr(rr) if B * k else None, C.c_void_p(int(out))))
+
+    def lagrange_eval_on_h(self, values, z, omega=None):
+        """lagrange_eval_on_h(values, z, omega) (deep_ali/src/lib.rs:17-45): host column of n = 2^k elements, host point -> the value as 4 limbs;
+        omega None = the radix-2 generator of size n."""
+        v = _arr(values); out = np.zeros(4, np.uint64)
+        self._chk(self.lib.stark_lagrange_eval_on_h(self.h, _ptr(v), v.shape[0], _ptr(_arr(z)), _ptr(None if omega is None else _arr(omega)), _ptr(out)))
+        return out
+
+    def lagrange_eval_on_h_dev(self, values, n, z, out, omega=None):
+        """lagrange_eval_on_h of the DEVICE column `values` (int, n elements) at the host point z into the DEVICE element `out` (int);
+        stream-ordered, no synchronisation (stark_lagrange_eval_on_h_dev)."""
+        self._chk(self.lib.stark_lagrange_eval_on_h_dev(self.h, C.c_void_p(int(values)), n, _ptr(_arr(z)), _ptr(None if omega is None else _arr(omega)), C.c_void_p(int(out))))
+
+    def lagrange_eval_on_h_batch_dev(self, cols, n, zs, out, omega=None):
+        """lagrange_eval_on_h of each of the DEVICE columns `cols` (ints, n elements each; a column may repeat) at each of the host points zs ((P, 4)) into
+        the DEVICE array `out` (int, P x len(cols) elements, point-major), one batch inversion per point for all columns; stream-ordered, no
+        synchronisation (stark_lagrange_eval_on_h_batch_dev)."""
+        B = len(cols); z = _arr(zs).reshape(-1, 4)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in cols])
+        self._chk(self.lib.stark_lagrange_eval_on_h_batch_dev(self.h, B, tab, n, _ptr(None if omega is None else _arr(omega)), z.shape[0], _ptr(z) if z.shape[0] else None, C.c_void_p(int(out))))
 
     def prove_plain(self, k, tree_label, witness):
         """prove_plain(&build_vk_plain(k, F::from(tree_label)), witness) -> bincode-layout ProofPlain bytes."""

@@ -238,6 +238,8 @@ static const OptionDef kOptions[] = {
     {"prove_batch_max_rows", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.prove_batch_max_rows = (size_t)v; return nullptr; }},
     {"mle_log_tile", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v != -1 && (v < 3 || v > 12)) return "3..12, or -1 for the default"; o.mle_log_tile = (int)v; return nullptr; }},
     {"mle_lane_contiguous", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 1) return "0 or 1, or -1 for the default"; o.mle_lane_contiguous = (int)v; return nullptr; }},
+    {"lagrange_max_partials", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v != -1 && (v < 1 || v > ((int64_t)1 << 28))) return "1..2^28, or -1 for the default"; o.lagrange_max_partials = v == -1 ? (size_t)1 << 21 : (size_t)v; return nullptr; }},
+    {"lagrange_wide_acc", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 1) return "0 or 1, or -1 for the default"; o.lagrange_wide_acc = (int)v; return nullptr; }},
     {"pool_poison", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 255) return "0..255, or -1 for off"; o.pool_poison = (int)v; return nullptr; }},
 };
 extern "C" {

@@ -18,6 +18,7 @@
 #include "fri_dev.hpp"
 #include "fri_batch.hpp"
 #include "merkle_batch.hpp"
+#include "lagrange_dev.hpp"
 
 using namespace stark;
 
@@ -553,6 +554,53 @@ static int32_t ali_merge_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* co
     return STARK_OK;
 }
 
+// ---- lagrange_eval_on_h of device-resident columns (deep_ali/src/lib.rs:17-45; lagrange_dev.hpp) -----------------------------------------------
+// The executor of lagrange_eval_batch on the device: pooled blocks that return to the pool with it, staged uploads, every launch on the context's stream.
+struct LagDevExec : FriDevExec {
+    explicit LagDevExec(stark_ctx* c) : FriDevExec(c) {}
+    int32_t pow_table(const fr_t& omega, size_t n, LagPow* out) {                        // the merge's table of this domain (PowCache): a prove that merged over it has filled it
+        PowTable t; STARK_TRY(omega_table(ctx, omega, n, &t)); *out = LagPow{t.lo, t.hi, t.lo_bits}; return STARK_OK;
+    }
+    int32_t gather(const fr_t* const* cols, size_t ncols, const uint64_t* j, const uint64_t* slot, size_t cnt, fr_t* out) {
+        hipLaunchKernelGGL(k_lagrange_gather, dim3((unsigned)((cnt * ncols + 255) / 256)), dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, j, slot, (uint64_t)cnt, out);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, unsigned groups, unsigned grid, fr_t* part) {
+        const bool wide = ctx->opt.lagrange_wide_acc < 0 ? kLagWideAcc : ctx->opt.lagrange_wide_acc != 0;
+        if (wide) hipLaunchKernelGGL(k_lagrange_partials<true>, dim3(grid, groups), dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n, wp, w_step, w_step_inv, zs, (uint64_t)npts, part);
+        else hipLaunchKernelGGL(k_lagrange_partials<false>, dim3(grid, groups), dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n, wp, w_step, w_step_inv, zs, (uint64_t)npts, part);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t finish(const fr_t* part, unsigned grid, const fr_t* scale, const uint64_t* slot, size_t npts, size_t ncols, fr_t* out) {
+        hipLaunchKernelGGL(k_lagrange_finish, dim3((unsigned)(npts * ncols)), dim3(256), 0, ctx->stream, part, (uint64_t)grid, scale, slot, (uint64_t)ncols, out);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+};
+// the argument checks of stark_lagrange_eval_on_h_batch_dev, all before anything is enqueued; *omega = the caller's generator or the radix-2 one of size n
+static int32_t lagrange_check_args(stark_ctx* ctx, size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega4, size_t npoints, const uint64_t* z, const uint64_t* out, fr_t* omega) {
+    if (!cols) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null column table");
+    if (!out) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null out");
+    if (!z) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null z with npoints > 0");
+    if (!is_pow2(n) || n > ((size_t)1 << kLagMaxLogN)) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: n must be a power of two, 1 <= n <= 2^30");
+    *omega = omega4 ? load_fr(omega4) : fr_root_of_unity<PallasFr>((unsigned)ilog2(n));       // FriDomain::new_radix2(n).omega, fri.rs:53-56
+    if (const char* why = lag_check_domain(n, *omega)) return ctx->fail(STARK_ERR_INVALID_ARG, std::string("lagrange_eval: ") + why);
+    if (ncols > kLagMaxCols) return ctx->fail(STARK_ERR_UNSUPPORTED, "lagrange_eval: more than 2^24 columns in one call");
+    if (npoints > ((size_t)1 << 36) / ncols) return ctx->fail(STARK_ERR_UNSUPPORTED, "lagrange_eval: more than 2^36 results in one call");
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + npoints * ncols * sizeof(fr_t), cbytes = n * sizeof(fr_t);
+    for (size_t c = 0; c < ncols; ++c) {
+        if (!cols[c]) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null column entry " + std::to_string(c));
+        const uintptr_t c0 = (uintptr_t)cols[c];
+        if (c0 < o1 && o0 < c0 + cbytes) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: out overlaps column " + std::to_string(c));
+    }
+    return STARK_OK;
+}
+static int32_t lagrange_eval_batch_impl(stark_ctx* ctx, size_t ncols, const uint64_t* const* cols, size_t n, const fr_t& omega, size_t npoints, const uint64_t* z, uint64_t* out) {
+    std::vector<const fr_t*> cp(ncols); for (size_t c = 0; c < ncols; ++c) cp[c] = as_fr(cols[c]);
+    std::vector<fr_t> zs(npoints); for (size_t p = 0; p < npoints; ++p) zs[p] = load_fr(z + 4 * p);
+    LagDevExec X(ctx);
+    return lagrange_eval_batch(X, ncols, cp.data(), n, omega, npoints, zs.data(), ctx->opt.lagrange_max_partials, as_fr(out), nullptr);
+}
+
 // B independent proofs of equal shape (stark_deep_fri_prove_batch_dev; stark_deep_fri_prove_dev from columns is B = 1): the challenge stage of all
 // traces at once, then merge, commit phase and query phase pass by pass (prove_pass).
 // Every proof is byte-for-byte what stark_deep_fri_prove_dev returns for that trace alone.
@@ -709,6 +757,28 @@ int32_t stark_ali_merge_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t
     if (n <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n > 1");                                                                                       // lib.rs:71
     for (size_t p = 0; p < batch; ++p) if (fr_eq(fr_pow_u64<PallasFr>(load_fr(z + 4 * p), n), host::h_one())) return ctx->fail(STARK_ERR_INVALID_ARG, "z must be outside H");   // lib.rs:78
     return ali_merge_batch_impl(ctx, batch, a, s, e, t, r_opt, beta, load_fr(omega4), z, n, f0, c_star);
+}
+// lagrange_eval_on_h (deep_ali/src/lib.rs:17-45) of ncols DEVICE columns at npoints HOST points: ONE driver (lagrange_dev.hpp) for the batch, the
+// single device form (1 x 1) and the host-pointer form (upload, 1 x 1, download); stream-ordered, z and the pointer table are copied before return.
+int32_t stark_lagrange_eval_on_h_batch_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega4, size_t npoints, const uint64_t* z, uint64_t* out) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!ncols || !npoints) return STARK_OK;
+    fr_t omega; STARK_TRY(lagrange_check_args(ctx, ncols, cols, n, omega4, npoints, z, out, &omega));
+    STARK_TRY(ctx_enter(ctx));
+    return lagrange_eval_batch_impl(ctx, ncols, cols, n, omega, npoints, z, out);
+}
+int32_t stark_lagrange_eval_on_h_dev(stark_ctx_t* ctx, const uint64_t* values, size_t n, const uint64_t* z4, const uint64_t* omega4, uint64_t* out4) {
+    return stark_lagrange_eval_on_h_batch_dev(ctx, 1, &values, n, omega4, 1, z4, out4);
+}
+int32_t stark_lagrange_eval_on_h(stark_ctx_t* ctx, const uint64_t* values, size_t n, const uint64_t* z4, const uint64_t* omega4, uint64_t* out4) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!values || !z4 || !out4) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null values, z or out");
+    if (!is_pow2(n) || n > ((size_t)1 << kLagMaxLogN)) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: n must be a power of two, 1 <= n <= 2^30");
+    STARK_TRY(ctx_enter(ctx));
+    DevBuf d, o; STARK_HIP(ctx, d.upload(ctx, values, n * sizeof(fr_t))); STARK_HIP(ctx, o.alloc(ctx, sizeof(fr_t)));
+    const int32_t rc = stark_lagrange_eval_on_h_dev(ctx, (const uint64_t*)d.p, n, z4, omega4, (uint64_t*)o.p);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }                          // the upload reads the caller's `values`
+    STARK_HIP(ctx, o.download_sync(out4, sizeof(fr_t))); return STARK_OK;
 }
 size_t stark_proof_len(stark_proof_t* p) { return p ? p->bytes.size() : 0; }
 int32_t stark_proof_bytes(stark_proof_t* p, uint8_t* out) { if (!p || !out) return STARK_ERR_INVALID_ARG; memcpy(out, p->bytes.data(), p->bytes.size()); return STARK_OK; }

@@ -111,6 +111,8 @@ struct stark_ctx {
         size_t prove_batch_max_rows = (size_t)1 << 22;   // the batched DEEP-FRI provers cut a batch into passes of at most this many rows (traces x n0) whose tails run side by side (fri_batch.hpp); device memory per pass stays near 70 B per row
         int mle_log_tile = -1;           // log2 of the elements one workgroup of k_mle_fold_pass folds to one (3..12); -1 = the default of mle_dev.hpp
         int mle_lane_contiguous = -1;    // a lane of k_mle_fold_pass owns consecutive (1) or interleaved (0) elements; -1 = the default of mle_dev.hpp (comparison)
+        size_t lagrange_max_partials = (size_t)1 << 21;  // stark_lagrange_eval_on_h_batch_dev cuts the points of a call into passes of at most this many block partials (points x columns x workgroups per column; lagrange_dev.hpp): 64 MiB of scratch per pass; a pass of one point is always allowed
+        int lagrange_wide_acc = -1;      // k_lagrange_partials: a lane's K products of a column in the lazy accumulator (1) or as K products and additions (0); -1 = the default of lagrange_dev.hpp (comparison)
         int pool_poison = -1;            // TESTS ONLY: 0..255 = ctx_alloc fills every block it hands out (the whole rounded block, recycled or fresh) and ctx_scratch the scratch vector
                                          // with this byte, so a read of a temporary nobody wrote shows; each fill synchronises the stream.  -1 = off (one branch per allocation, no HIP call)
     } opt;

@@ -21,6 +21,7 @@
 #include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
 #include "mle_dev.hpp"
 #include "merkle_batch.hpp"
+#include "lagrange_dev.hpp"
 
 using namespace stark;
 
@@ -738,6 +739,94 @@ int hc_mle_evaluate_batch(size_t B, const uint64_t* const* tables, size_t k, con
 }
 }  // extern "C"
 extern "C" int hc_mle_default_log_tile() { return kMleDefaultLogTile; }
+
+// ---- stark_lagrange_eval_on_h_batch_dev (lagrange_dev.hpp): the driver itself, every workgroup of k_lagrange_partials run in lockstep on the host ------
+// The lane geometry, the weights, the lane dot product and the sums are the kernels' own inline pieces; a shuffle scan is a product over the wave's
+// other lanes, LDS a plain array.  Blocks come from the executors' allocation path (hc_set_alloc_fill), as the device driver's come from the pool.
+struct LagHostExec {
+    std::vector<std::vector<uint64_t>> mem; std::vector<fr_t> lo, hi;
+    int32_t alloc(size_t bytes, void** out) { mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
+    template <class T> int32_t put(const std::vector<T>& h, T** out) {
+        void* p = nullptr; alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p);
+        if (!h.empty()) memcpy(p, h.data(), h.size() * sizeof(T));
+        *out = (T*)p; return 0;
+    }
+    int32_t pow_table(const fr_t& omega, size_t n, LagPow* out) {
+        int bits, lo_bits, hi_bits; lag_pow_split(n, &bits, &lo_bits, &hi_bits);
+        lo.assign((size_t)1 << lo_bits, fr_one<PF>()); hi.assign((size_t)1 << hi_bits, fr_one<PF>());
+        for (size_t i = 1; i < lo.size(); ++i) lo[i] = fr_mul<PF>(lo[i - 1], omega);
+        const fr_t step = fr_pow_u64<PF>(omega, (uint64_t)1 << lo_bits);
+        for (size_t i = 1; i < hi.size(); ++i) hi[i] = fr_mul<PF>(hi[i - 1], step);
+        *out = LagPow{lo.data(), hi.data(), lo_bits}; return 0;
+    }
+    int32_t gather(const fr_t* const* cols, size_t ncols, const uint64_t* j, const uint64_t* slot, size_t cnt, fr_t* out) {
+        for (size_t q = 0; q < cnt; ++q) for (size_t c = 0; c < ncols; ++c) out[slot[q] * ncols + c] = cols[c][j[q]];
+        return 0;
+    }
+    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, unsigned groups, unsigned grid, fr_t* part) {
+        const uint32_t T = grid * 256, n32 = (uint32_t)n;
+        std::vector<fr_t> Wv(256 * kLagK), w(256), run(256), lane(256);
+        auto W = [&](int t) -> fr_t (&)[kLagK] { return *reinterpret_cast<fr_t (*)[kLagK]>(&Wv[(size_t)t * kLagK]); };
+        for (unsigned g = 0; g < groups; ++g) for (unsigned blk = 0; blk < grid; ++blk) {
+            for (int t = 0; t < 256; ++t) { const uint32_t tid = blk * 256 + t; w[t] = tid < n32 ? lag_pow(wp, tid) : fr_one<PF>(); }
+            for (size_t p = g; p < npts; p += groups) {
+                const fr_t z = zs[p];
+                for (int t = 0; t < 256; ++t) run[t] = lag_prefix(z, w[t], w_step, blk * 256 + (uint32_t)t, T, n32, W(t));
+                fr_t tot[4], P = fr_one<PF>();
+                for (int v = 0; v < 4; ++v) { tot[v] = fr_one<PF>(); for (int l = 0; l < 64; ++l) tot[v] = fr_mul<PF>(tot[v], run[64 * v + l]); P = fr_mul<PF>(P, tot[v]); }
+                const fr_t Pinv = fr_inv<PF>(P);
+                for (int t = 0; t < 256; ++t) {
+                    const int v = t >> 6, l = t & 63; fr_t before = fr_one<PF>(), after = fr_one<PF>();
+                    for (int q = 0; q < l; ++q) before = fr_mul<PF>(before, run[64 * v + q]);
+                    for (int q = l + 1; q < 64; ++q) after = fr_mul<PF>(after, run[64 * v + q]);
+                    lag_peel(z, w[t], w_step_inv, blk * 256 + (uint32_t)t, T, n32, lag_lane_inverse(Pinv, tot, v, fr_mul<PF>(before, after)), W(t));
+                }
+                for (size_t c = 0; c < ncols; ++c) {
+                    for (int t = 0; t < 256; ++t) lane[t] = lag_lane_dot<kLagWideAcc>(cols[c], blk * 256 + (uint32_t)t, T, n32, W(t));
+                    fr_t w4[4];
+                    for (int v = 0; v < 4; ++v) { w4[v] = fr_zero<PF>(); for (int l = 0; l < 64; ++l) w4[v] = fr_add<PF>(w4[v], lane[64 * v + l]); }
+                    part[(p * ncols + c) * grid + blk] = lag_sum4(w4);
+                }
+            }
+        }
+        return 0;
+    }
+    int32_t finish(const fr_t* part, unsigned grid, const fr_t* scale, const uint64_t* slot, size_t npts, size_t ncols, fr_t* out) {
+        for (size_t b = 0; b < npts * ncols; ++b) {
+            const size_t p = b / ncols, c = b % ncols; fr_t lane[256];
+            for (int t = 0; t < 256; ++t) { lane[t] = fr_zero<PF>(); for (size_t i = (size_t)t; i < grid; i += 256) lane[t] = fr_add<PF>(lane[t], part[b * grid + i]); }
+            fr_t w4[4];
+            for (int w = 0; w < 4; ++w) { w4[w] = fr_zero<PF>(); for (int l = 0; l < 64; ++l) w4[w] = fr_add<PF>(w4[w], lane[64 * w + l]); }
+            out[slot[p] * ncols + c] = fr_mul<PF>(lag_sum4(w4), scale[p]);
+        }
+        return 0;
+    }
+};
+extern "C" {
+// out[p * ncols + c] = lagrange_eval_on_h(cols[c] (n elements), z[p], omega) through the driver of stark_lagrange_eval_on_h_batch_dev with passes of at
+// most max_partials block partials (0: the default).  omega null: the radix-2 generator of size n.  passes (may be null) = the partial passes taken.
+// -1: a refused (n, omega), as the entry point refuses it.
+int hc_lagrange_eval_batch(size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega, size_t npoints, const uint64_t* z, size_t max_partials, uint64_t* out, size_t* passes) {
+    if (passes) *passes = 0;
+    if (!ncols || !npoints) return 0;
+    if (!n || (n & (n - 1)) || n > ((size_t)1 << kLagMaxLogN)) return -1;
+    int lg = 0; while (((size_t)1 << lg) < n) ++lg;
+    const fr_t w = omega ? ld4(omega) : fr_root_of_unity<PF>((unsigned)lg);
+    if (lag_check_domain(n, w)) return -1;
+    std::vector<std::vector<fr_t>> col(ncols, std::vector<fr_t>(n)); std::vector<const fr_t*> ptrs(ncols); std::vector<fr_t> zs(npoints);
+    for (size_t c = 0; c < ncols; ++c) {
+        size_t first = c; for (size_t q = 0; q < c; ++q) if (cols[q] == cols[c]) { first = q; break; }      // a repeated pointer stays one column
+        if (first == c) for (size_t i = 0; i < n; ++i) col[c][i] = ld4(cols[c] + 4 * i);
+        ptrs[c] = col[first].data();
+    }
+    for (size_t p = 0; p < npoints; ++p) zs[p] = ld4(z + 4 * p);
+    std::vector<fr_t> o = hc_fr_block(npoints * ncols);
+    LagHostExec X;
+    if (lagrange_eval_batch(X, ncols, ptrs.data(), n, w, npoints, zs.data(), max_partials ? max_partials : kLagDefaultMaxPartials, o.data(), passes)) return -1;
+    for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
+    return 0;
+}
+}  // extern "C"
 
 // ---- many Merkle trees in one pass (merkle_batch.hpp) through the host instantiation of the stream bodies -----------------------------------------
 struct MerkleHostExec {

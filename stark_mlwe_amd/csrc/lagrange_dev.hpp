@@ -1,0 +1,265 @@
+// stark_mlwe_amd/csrc/lagrange_dev.hpp — lagrange_eval_on_h (deep_ali/src/lib.rs:17-45) of many columns at many points on CDNA4 (gfx950).
+//
+//   outside H (z^n != 1):  f(z) = (z^n - 1)/n * sum_j v[j] w^j / (z - w^j)          inside H (z = w^j):  f(z) = v[j], copied
+//
+// The weights W_j(z) = w^j / (z - w^j) depend on the point only, so C columns at one point cost one batch inversion and C dot products.
+// The host classifies the points (z is a host array): z^n, the scale (z^n - 1)/n, and for a point inside H its index by the 2-adic discrete
+// logarithm (one bit of j per step, no device search).  Points inside H are one k_lagrange_gather launch; the others go, as a compacted list
+// cut into passes that bound the scratch, through
+//   k_lagrange_partials   grid (tiles of the domain, point groups): a 256-thread workgroup owns the 256 K positions j = tid + u T (tid counted
+//                         over the grid's x dimension, T its lanes: every column load of a wave is 64 consecutive elements) and walks the
+//                         points of its group: the K weights of a lane from ONE Fermat inversion per
+//                         workgroup (the two-level scheme of ali_merge_block, fri_dev.hpp), then per column K products, a wave reduction by
+//                         shuffles and the four waves through LDS: one partial per (point, column, workgroup);
+//   k_lagrange_finish     one block per (point, column): the sum of its partials times the point's scale -> out[p * ncols + c].
+// The driver (lagrange_eval_batch) and the per-lane pieces are host code / FR_HD: hostcheck.cpp runs the same driver with every workgroup in
+// lockstep on the CPU (hc_lagrange_eval_batch).  Every stored value is fully reduced, so neither the order of a sum nor how an inverse is
+// obtained changes a bit.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <vector>
+#include "fr.hpp"
+#include "dev_common.hpp"
+
+namespace stark {
+
+constexpr int kLagK = 8;                                        // positions per lane (the merge's ALI_K)
+constexpr int kLagMaxLogN = 30;
+constexpr size_t kLagDefaultMaxPartials = (size_t)1 << 21;      // context option "lagrange_max_partials": 64 MiB of block partials per pass
+constexpr size_t kLagMaxCols = (size_t)1 << 24;                 // blockIdx.x of k_lagrange_finish is the (point, column) pair
+constexpr size_t kLagTargetWorkgroups = 1024;                   // point groups are added until a launch has about this many workgroups
+constexpr bool kLagWideAcc = true;                              // a lane's K products of a column in the lazy accumulator (fr_wide): K multiplications, one reduction
+
+// c0 = 1 view of a two-level power table (PowTable of ntt_dev.hpp, which is device-only): g^e = lo[e mod 2^lo_bits] * hi[e >> lo_bits]
+struct LagPow { const fr_t* lo; const fr_t* hi; int lo_bits; };
+FR_HD fr_t lag_pow(const LagPow& t, uint64_t e) {
+    const fr_t a = ldg(t.lo + (e & ((1ull << t.lo_bits) - 1)));
+    const uint64_t h = e >> t.lo_bits;
+    return h ? fr_mul<PallasFr>(a, ldg(t.hi + h)) : a;
+}
+inline void lag_pow_split(size_t n, int* bits, int* lo_bits, int* hi_bits) {     // the split of the merge's omega_table (capi_fri.hip)
+    int b = 0; while (((size_t)1 << b) < n) ++b;
+    if (b < 1) b = 1;
+    *bits = b; *lo_bits = (b + 1) / 2; *hi_bits = b - *lo_bits + 1;
+}
+
+// A launch over n positions: `grid` workgroups of 256 lanes, T = 256 grid lanes, lane tid owns j = tid + u T, u < K, where j < n.
+struct LagGeom { unsigned grid; uint64_t T; };
+inline LagGeom lag_geom(size_t n) {
+    const uint64_t lanes = ((uint64_t)n + kLagK - 1) / kLagK; LagGeom g;
+    g.grid = (unsigned)((lanes + 255) / 256); g.T = (uint64_t)g.grid * 256; return g;
+}
+// the points of one pass (a pass of one point is always allowed) and the point groups of its launch (group g walks the points g, g + groups, ...)
+inline size_t lag_pass_points(size_t max_partials, size_t ncols, unsigned grid) { return std::max<size_t>(max_partials / (ncols * (size_t)grid), 1); }
+inline unsigned lag_point_groups(size_t pass_points, unsigned grid) {
+    return (unsigned)std::min<size_t>(std::min<size_t>(pass_points, 65535), std::max<size_t>((kLagTargetWorkgroups + grid - 1) / grid, 1));
+}
+
+// nullptr, or why (n, omega) is refused: n a power of two in 1 .. 2^30; omega a primitive n-th root of unity (omega^n = 1 and, for n >= 2,
+// omega^(n/2) = -1), which is what makes every z with z^n = 1 a power of omega.
+inline const char* lag_check_domain(size_t n, const fr_t& omega) {
+    if (!n || (n & (n - 1))) return "n must be a power of two";
+    if (n > ((size_t)1 << kLagMaxLogN)) return "n too large (at most 2^30)";
+    if (!fr_eq(fr_pow_u64<PallasFr>(omega, n), fr_one<PallasFr>())) return "omega^n != 1";
+    if (n >= 2 && !fr_eq(fr_pow_u64<PallasFr>(omega, n / 2), fr_neg<PallasFr>(fr_one<PallasFr>()))) return "omega is not a primitive n-th root of unity";
+    return nullptr;
+}
+// j < 2^k with w^j = z, for z^(2^k) = 1 and w of order 2^k; winv2[i] = w^-(2^i).  Bit i of j is set iff (z w^-(j mod 2^i))^(2^(k-1-i)) = -1:
+// one power compared against 1 per bit, about k^2 / 2 squarings in all.
+inline uint64_t lag_dlog(const fr_t& z, const std::vector<fr_t>& winv2, int k) {
+    const fr_t one = fr_one<PallasFr>(); fr_t cur = z; uint64_t j = 0;
+    for (int i = 0; i < k; ++i) {
+        fr_t t = cur; for (int s = 0; s < k - 1 - i; ++s) t = fr_sqr<PallasFr>(t);
+        if (!fr_eq(t, one)) { j |= 1ull << i; cur = fr_mul<PallasFr>(cur, winv2[i]); }
+    }
+    return j;
+}
+
+// ---- the work of one lane (tid counted over the whole launch; tid + (K - 1) T < max(n, 2048) <= 2^30, so positions are 32-bit) ------------------
+// The lane walks w^j over its K positions with w_step = w^T and back with its inverse, as ali_merge_block does, instead of holding K powers: the 64
+// registers they would take are what lets three workgroups share a CU, and several resident workgroups are what covers a wave that inverts.
+// forward: pre[u] = product of d_v = z - w^(j_v) over v < u (d = 1 past n); w: w^tid in, w^(tid + K T) out; returns the product over all K
+FR_HD fr_t lag_prefix(const fr_t& z, fr_t& w, const fr_t& w_step, uint32_t tid, uint32_t T, uint32_t n, fr_t (&pre)[kLagK]) {
+    fr_t run = fr_one<PallasFr>();
+#pragma unroll
+    for (int u = 0; u < kLagK; ++u) {
+        const fr_t d = tid + (uint32_t)u * T < n ? fr_sub<PallasFr>(z, w) : fr_one<PallasFr>();
+        pre[u] = run; run = u ? fr_mul<PallasFr>(run, d) : d;
+        w = fr_mul<PallasFr>(w, w_step);
+    }
+    return run;
+}
+// 1 / (this lane's product) from Pinv = 1 / (the product over the workgroup), the four wave totals, and `others` = the product of the other lanes
+// of its wave (formed before the inversion, so that one value and not two stays live across it)
+FR_HD fr_t lag_lane_inverse(const fr_t& Pinv, const fr_t (&tot)[4], int wave, const fr_t& others) {
+    fr_t inv = Pinv;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) if (i != wave) inv = fr_mul<PallasFr>(inv, tot[i]);
+    return fr_mul<PallasFr>(inv, others);
+}
+// backward: peels the inverses off, pre[u] becomes the weight W_u = w^(j_u) / (z - w^(j_u))  (0 past n); w: w^(tid + K T) in, w^tid out
+FR_HD void lag_peel(const fr_t& z, fr_t& w, const fr_t& w_step_inv, uint32_t tid, uint32_t T, uint32_t n, fr_t inv, fr_t (&pre)[kLagK]) {
+#pragma unroll
+    for (int u = kLagK - 1; u >= 0; --u) {
+        const bool live = tid + (uint32_t)u * T < n;
+        w = fr_mul<PallasFr>(w, w_step_inv);                                                          // back to w^(j_u)
+        const fr_t dinv = u ? fr_mul<PallasFr>(inv, pre[u]) : inv;                                    // 1 / d_u
+        if (u) inv = fr_mul<PallasFr>(inv, live ? fr_sub<PallasFr>(z, w) : fr_one<PallasFr>());
+        pre[u] = live ? fr_mul<PallasFr>(w, dinv) : fr_zero<PallasFr>();
+    }
+}
+// sum_u col[j_u] W_u.  WIDE: K multiplications into the lazy accumulator and one reduction (inputs below r, K <= 27 terms: fr.hpp); else K
+// products and K additions.  Both are fully reduced, hence the same bits.
+template <bool WIDE>
+FR_HD fr_t lag_lane_dot(const fr_t* __restrict__ col, uint32_t tid, uint32_t T, uint32_t n, const fr_t (&W)[kLagK]) {
+    if constexpr (WIDE) {
+        fr_wide acc; fr_wide_zero(acc);
+#pragma unroll
+        for (int u = 0; u < kLagK; ++u) { const uint32_t j = tid + (uint32_t)u * T; fr_wide_mac_f<PallasFr>(acc, j < n ? ldg(col + j) : fr_zero<PallasFr>(), W[u]); }
+        return fr_wide_reduce<PallasFr>(acc);
+    } else {
+        fr_t acc = fr_zero<PallasFr>();
+#pragma unroll
+        for (int u = 0; u < kLagK; ++u) { const uint32_t j = tid + (uint32_t)u * T; if (j < n) acc = fr_add<PallasFr>(acc, fr_mul<PallasFr>(ldg(col + j), W[u])); }
+        return acc;
+    }
+}
+FR_HD fr_t lag_sum4(const fr_t (&w)[4]) { return fr_add<PallasFr>(fr_add<PallasFr>(w[0], w[1]), fr_add<PallasFr>(w[2], w[3])); }
+
+// ---- the driver ------------------------------------------------------------------------------------------------------------------------
+// out[p * ncols + c] = lagrange_eval_on_h(cols[c], z[p], omega) for the executor's memory (device: capi_fri.hip; host: hostcheck.cpp).  The
+// arguments have passed lag_check_domain and the null / overlap checks; ncols, npoints >= 1.  passes (may be null) = the partial passes taken.
+// An executor provides  alloc(bytes, void**)  put(vector<T>, T**)  pow_table(omega, n, LagPow*)  gather(...)  partials(...)  finish(...).
+template <class Exec>
+int32_t lagrange_eval_batch(Exec& X, size_t ncols, const fr_t* const* cols, size_t n, const fr_t& omega, size_t npoints, const fr_t* z, size_t max_partials,
+                            fr_t* out, size_t* passes) {
+    const fr_t one = fr_one<PallasFr>(), n_inv = fr_inv<PallasFr>(fr_from_u64<PallasFr>((uint64_t)n));
+    int k = 0; while (((size_t)1 << k) < n) ++k;
+    std::vector<fr_t> winv2((size_t)k);
+    if (k) { winv2[0] = fr_inv<PallasFr>(omega); for (int i = 1; i < k; ++i) winv2[(size_t)i] = fr_sqr<PallasFr>(winv2[(size_t)i - 1]); }
+    std::vector<fr_t> zo, scale; std::vector<uint64_t> slot_o, jin, slot_i;          // outside H: point, scale, index of the point in the call; inside: j*, index
+    for (size_t p = 0; p < npoints; ++p) {
+        const fr_t zn = fr_pow_u64<PallasFr>(z[p], (uint64_t)n);
+        if (fr_eq(zn, one)) { jin.push_back(lag_dlog(z[p], winv2, k)); slot_i.push_back((uint64_t)p); }
+        else { zo.push_back(z[p]); scale.push_back(fr_mul<PallasFr>(fr_sub<PallasFr>(zn, one), n_inv)); slot_o.push_back((uint64_t)p); }
+    }
+    if (passes) *passes = 0;
+    const fr_t** d_cols = nullptr;
+    { std::vector<const fr_t*> h(cols, cols + ncols); int32_t rc = X.put(h, &d_cols); if (rc) return rc; }
+    if (!jin.empty()) {
+        uint64_t *d_j = nullptr, *d_slot = nullptr;
+        int32_t rc = X.put(jin, &d_j); if (rc) return rc;
+        rc = X.put(slot_i, &d_slot); if (rc) return rc;
+        rc = X.gather((const fr_t* const*)d_cols, ncols, d_j, d_slot, jin.size(), out); if (rc) return rc;
+    }
+    if (zo.empty()) return 0;
+    const LagGeom G = lag_geom(n);
+    const size_t per_pass = std::min(lag_pass_points(max_partials, ncols, G.grid), zo.size());
+    if (passes) *passes = (zo.size() + per_pass - 1) / per_pass;
+    fr_t *d_z = nullptr, *d_scale = nullptr; uint64_t* d_slot = nullptr; void* d_part = nullptr; LagPow wp;
+    int32_t rc = X.put(zo, &d_z); if (rc) return rc;
+    rc = X.put(scale, &d_scale); if (rc) return rc;
+    rc = X.put(slot_o, &d_slot); if (rc) return rc;
+    rc = X.alloc(per_pass * ncols * G.grid * sizeof(fr_t), &d_part); if (rc) return rc;       // reused by every pass: they are ordered on one stream
+    rc = X.pow_table(omega, n, &wp); if (rc) return rc;
+    const fr_t w_step = fr_pow_u64<PallasFr>(omega, G.T), w_step_inv = fr_inv<PallasFr>(w_step);
+    for (size_t p0 = 0; p0 < zo.size(); p0 += per_pass) {
+        const size_t pp = std::min(per_pass, zo.size() - p0);
+        rc = X.partials((const fr_t* const*)d_cols, ncols, n, wp, w_step, w_step_inv, d_z + p0, pp, lag_point_groups(pp, G.grid), G.grid, (fr_t*)d_part); if (rc) return rc;
+        rc = X.finish((const fr_t*)d_part, G.grid, d_scale + p0, d_slot + p0, pp, ncols, out); if (rc) return rc;
+    }
+    return 0;
+}
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ void lag_st_lds(uint4* p, int i, const fr_t& x) { p[2 * i] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]); p[2 * i + 1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]); }
+__device__ __forceinline__ fr_t lag_ld_lds(const uint4* p, int i) {
+    const uint4 lo = p[2 * i], hi = p[2 * i + 1]; fr_t x;
+    x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w; x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w; return x;
+}
+// Workgroup blockIdx.x of gridDim.x tiles, point group blockIdx.y: the points blockIdx.y, blockIdx.y + gridDim.y, ... < npts of zs;
+// partials[(p * ncols + c) * gridDim.x + blockIdx.x] = this workgroup's share of sum_j cols[c][j] W_j(zs[p]).  The scan-and-invert step is the
+// one of ali_merge_block (fri_dev.hpp), whose comment says why one inversion per lane would dwarf the useful work; it is a copy, not a shared
+// helper, so that the merge kernels' code does not move (open unification).
+template <bool WIDE>
+__global__ void __launch_bounds__(256, 3) k_lagrange_partials(const fr_t* const* __restrict__ cols, uint64_t ncols, uint64_t n64, LagPow wp, fr_t w_step, fr_t w_step_inv,
+                                                           const fr_t* __restrict__ zs, uint64_t npts, fr_t* __restrict__ partials) {
+    __shared__ uint4 tot[2 * 4], pinv[2], red[2][2 * 4];
+    const uint32_t T = gridDim.x * 256, tid = blockIdx.x * 256 + threadIdx.x, n = (uint32_t)n64;
+    const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+    fr_t w = tid < n ? lag_pow(wp, tid) : fr_one<PallasFr>();      // w^tid; every point leaves it there again
+    for (uint64_t p = blockIdx.y; p < npts; p += gridDim.y) {
+        const fr_t z = ldg(zs + p);
+        fr_t W[kLagK];
+        const fr_t run = lag_prefix(z, w, w_step, tid, T, n, W);
+        fr_t pre_i = run, suf_i = run;                              // inclusive prefix / suffix products of the lanes' `run` over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const fr_t a = shfl_up_fr(pre_i, d), b = shfl_dn_fr(suf_i, d);
+            if (ln >= d) pre_i = fr_mul<PallasFr>(pre_i, a);
+            if (ln + d < 64) suf_i = fr_mul<PallasFr>(suf_i, b);
+        }
+        fr_t before = shfl_up_fr(pre_i, 1), after = shfl_dn_fr(suf_i, 1);
+        if (ln == 0) before = fr_one<PallasFr>();
+        if (ln == 63) after = fr_one<PallasFr>();
+        if (ln == 63) lag_st_lds(tot, wv, pre_i);
+        const fr_t others = fr_mul<PallasFr>(before, after);
+        __syncthreads();
+        // ONE Fermat inversion per workgroup and point, by one wave while the other three wait.  Which wave rotates with the workgroup, so that the
+        // workgroups resident on a CU (three fit: launch bound) tend to invert on different SIMDs instead of all on wave 0's.
+        if (wv == (int)((blockIdx.x + (blockIdx.x >> 8) + p) & 3)) {
+            fr_t P = lag_ld_lds(tot, 0);
+            for (int i = 1; i < 4; ++i) P = fr_mul<PallasFr>(P, lag_ld_lds(tot, i));
+            const fr_t Pi = fr_inv<PallasFr>(P);
+            if (ln == 0) lag_st_lds(pinv, 0, Pi);
+        }
+        __syncthreads();
+        {
+            const fr_t t4[4] = {lag_ld_lds(tot, 0), lag_ld_lds(tot, 1), lag_ld_lds(tot, 2), lag_ld_lds(tot, 3)};
+            lag_peel(z, w, w_step_inv, tid, T, n, lag_lane_inverse(lag_ld_lds(pinv, 0), t4, wv, others), W);
+        }
+        // The columns: the pointer table is indexed, never a register array.  red[] alternates between two halves, so one barrier per column
+        // orders thread 0's reads of a half before its next writers; tot and pinv of the next point are written behind at least that barrier.
+        for (uint64_t c = 0; c < ncols; ++c) {
+            fr_t acc = lag_lane_dot<WIDE>(cols[c], tid, T, n, W);
+#pragma unroll
+            for (int sft = 1; sft < 64; sft <<= 1) acc = fr_add<PallasFr>(acc, shfl_xor_fr(acc, sft));
+            uint4* r = red[c & 1];
+            if (ln == 0) lag_st_lds(r, wv, acc);
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const fr_t w4[4] = {lag_ld_lds(r, 0), lag_ld_lds(r, 1), lag_ld_lds(r, 2), lag_ld_lds(r, 3)};
+                stg(partials + ((p * ncols + c) * gridDim.x + blockIdx.x), lag_sum4(w4));
+            }
+        }
+    }
+}
+// One block per (point, column) of a pass, in the shape of k_sum_single_block: out[slot[p] * ncols + c] = scale[p] * the sum of the pair's `grid` partials.
+static __global__ void __launch_bounds__(256) k_lagrange_finish(const fr_t* __restrict__ partials, uint64_t grid, const fr_t* __restrict__ scale, const uint64_t* __restrict__ slot,
+                                                                uint64_t ncols, fr_t* __restrict__ out) {
+    __shared__ uint4 red[2 * 4];
+    const uint64_t p = blockIdx.x / ncols, c = blockIdx.x % ncols;
+    const fr_t* v = partials + (uint64_t)blockIdx.x * grid;
+    fr_t acc = fr_zero<PallasFr>();
+    for (uint64_t i = threadIdx.x; i < grid; i += 256) acc = fr_add<PallasFr>(acc, ldg(v + i));
+#pragma unroll
+    for (int sft = 1; sft < 64; sft <<= 1) acc = fr_add<PallasFr>(acc, shfl_xor_fr(acc, sft));
+    if ((threadIdx.x & 63) == 0) lag_st_lds(red, threadIdx.x >> 6, acc);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const fr_t w4[4] = {lag_ld_lds(red, 0), lag_ld_lds(red, 1), lag_ld_lds(red, 2), lag_ld_lds(red, 3)};
+        stg(out + slot[p] * ncols + c, fr_mul<PallasFr>(lag_sum4(w4), ldg(scale + p)));
+    }
+}
+// The points inside H: out[slot[q] * ncols + c] = cols[c][j[q]] for the `cnt` such points and all columns, copied.
+static __global__ void __launch_bounds__(256) k_lagrange_gather(const fr_t* const* __restrict__ cols, uint64_t ncols, const uint64_t* __restrict__ j, const uint64_t* __restrict__ slot,
+                                                                uint64_t cnt, fr_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt * ncols) return;
+    const uint64_t q = i / ncols, c = i % ncols;
+    stg(out + slot[q] * ncols + c, ldg(cols[c] + j[q]));
+}
+#endif  // __HIPCC__
+
+}  // namespace stark
