@@ -72,7 +72,7 @@ int32_t ctx_alloc(stark_ctx* ctx, size_t bytes, void** out) {
 void ctx_release(stark_ctx* ctx, void* p) {
     if (!p || !ctx) return;
     auto it = ctx->pool_live.find(p);
-    if (it == ctx->pool_live.end()) { (void)hipFree(p); return; }            // not ours (defensive)
+    if (it == ctx->pool_live.end()) { ctx->err = "ctx_release: the pointer is not a live block of this context's pool (left alone)"; return; }   // never hipFree: the pool may still list it
     const size_t sz = it->second; ctx->pool_live.erase(it);
     ctx->pool_free[sz].push_back(p); ctx->pool_cached_bytes += sz;
 }
@@ -134,25 +134,36 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
     P->dev.mds_frag = k.mds_frag.empty() ? nullptr : (const void*)(dev + o_frag); P->dev.mds_pre_frag = k.mds_frag.empty() ? nullptr : (const void*)(dev + o_frag + frag_elems);
     return STARK_OK;
 }
-static int32_t params_from_consts(stark_ctx* ctx, const host::PoseidonConsts& c, stark_params** out) {
-    stark_params* P = new stark_params(); P->ctx = ctx; P->ref = c;
-    int32_t rc = params_finish(ctx, P);
-    if (rc != STARK_OK) { delete P; return rc; }
-    *out = P; return STARK_OK;
+static int32_t params_from_consts(stark_ctx* ctx, const host::PoseidonConsts& c, std::unique_ptr<stark_params>& out) {
+    std::unique_ptr<stark_params> P(new stark_params()); P->ctx = ctx; P->ref = c;
+    STARK_TRY(params_finish(ctx, P.get()));
+    out = std::move(P); return STARK_OK;
+}
+// a set handed to the caller keeps the context alive
+static int32_t params_for_caller(stark_ctx* ctx, const host::PoseidonConsts& c, stark_params** out) {
+    std::unique_ptr<stark_params> P; STARK_TRY(params_from_consts(ctx, c, P));
+    P->ref_.bind(ctx); *out = P.release(); return STARK_OK;
 }
 int32_t ctx_transcript_params(stark_ctx* ctx, stark_params** out) {
-    if (!ctx->tparams) STARK_TRY(params_from_consts(ctx, host::consts_transcript(), &ctx->tparams));
-    if (out) *out = ctx->tparams;
+    if (!ctx->tparams) STARK_TRY(params_from_consts(ctx, host::consts_transcript(), ctx->tparams));
+    if (out) *out = ctx->tparams.get();
     return STARK_OK;
 }
 int32_t ctx_merkle_params(stark_ctx* ctx, int t, stark_params** out) {
     auto it = ctx->merkle_params.find(t);
     if (it == ctx->merkle_params.end()) {
         if (host::rp_for_width(t) < 0) return ctx->fail(STARK_ERR_UNSUPPORTED, "unsupported Poseidon width");
-        stark_params* P = nullptr; STARK_TRY(params_from_consts(ctx, host::consts_for_width(t), &P));
-        ctx->merkle_params[t] = P; *out = P; return STARK_OK;
+        std::unique_ptr<stark_params> P; STARK_TRY(params_from_consts(ctx, host::consts_for_width(t), P));
+        *out = P.get(); ctx->merkle_params[t] = std::move(P); return STARK_OK;
     }
-    *out = it->second; return STARK_OK;
+    *out = it->second.get(); return STARK_OK;
+}
+// MerkleCommitment's parameters (commitment/src/lib.rs:48-51: generate_params_t17_x5 of "POSEIDON-T17-X5-SEED"), cached next to the other sets
+// under key -17; like them it does not pin the context
+int32_t ctx_commit_params(stark_ctx* ctx, stark_params** out) {
+    std::unique_ptr<stark_params>& slot = ctx->merkle_params[-17];
+    if (!slot) STARK_TRY(params_from_consts(ctx, host::derive_consts("POSEIDON-T17-X5-SEED", 17, 8, 64), slot));
+    *out = slot.get(); return STARK_OK;
 }
 
 }  // namespace stark
@@ -166,14 +177,14 @@ int32_t stark_ctx_create(int32_t device, void* stream, stark_ctx_t** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return STARK_ERR_HIP;   // no device => no product path
     if (hipSetDevice(device) != hipSuccess) return STARK_ERR_HIP;
-    stark_ctx* c = new stark_ctx(); c->device = device;
-    if (stream == STARK_STREAM_PRIVATE) { if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return STARK_ERR_HIP; } c->own_stream = true; }
+    std::unique_ptr<stark_ctx> c(new stark_ctx()); c->device = device;
+    if (stream == STARK_STREAM_PRIVATE) { if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return STARK_ERR_HIP; c->own_stream = true; }
     else { c->stream = (hipStream_t)stream; c->own_stream = false; }         // NULL = the device's legacy default stream (ordered against torch's default stream and every blocking stream)
-    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) { delete c; return STARK_ERR_HIP; }
+    if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) return STARK_ERR_HIP;
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->num_cus = cus; }
     stark::ntt_set_attrs();
     stark::poseidon_set_attrs();
-    *out = c; return STARK_OK;
+    *out = c.release(); return STARK_OK;
 }
 }  // extern "C"
 // everything the context owns; runs when the context has been destroyed AND its last handle is gone
@@ -181,17 +192,15 @@ static void ctx_teardown(stark_ctx* ctx) {
     (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream);
     stark::comm_destroy(ctx);
     stark::ntt_plans_free(ctx);
-    if (ctx->tparams) stark_poseidon_params_free(ctx->tparams);
-    for (auto& kv : ctx->merkle_params) stark_poseidon_params_free(kv.second);
     for (auto& kv : ctx->pool_free) for (void* q : kv.second) (void)hipFree(q);
-    for (auto& kv : ctx->pool_live) (void)hipFree(kv.first);                 // stark_alloc blocks the caller never freed (handles are gone by now)
+    for (auto& kv : ctx->pool_live) (void)hipFree(kv.first);                 // blocks whose owner leaked (every handle is gone by now)
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     for (auto& u : ctx->staged) (void)hipEventDestroy(u.done);               // the stream was synchronised above: every staged upload is done
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0); if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;                                                               // the DevMem members and the power-table cache free themselves here, the device still current
+    delete ctx;                                                               // the DevMem members, the cached parameter sets and the power-table cache free themselves here, the device still current
 }
 namespace stark {
 void ctx_ref(stark_ctx* c) { ++c->live_handles; }
@@ -310,18 +319,18 @@ int32_t stark_poseidon_params_upload(stark_ctx_t* ctx, int32_t t, int32_t rf, in
     for (size_t i = 0; i < c.mds.size(); ++i) c.mds[i] = load_fr(mds + 4 * i);
     for (size_t i = 0; i < c.rc_full.size(); ++i) c.rc_full[i] = load_fr(rc_full + 4 * i);
     for (size_t i = 0; i < c.rc_partial.size(); ++i) c.rc_partial[i] = load_fr(rc_partial + 4 * i);
-    { int32_t rc = params_from_consts(ctx, c, out); if (rc == STARK_OK) (*out)->ref_.bind(ctx); return rc; }   // a set handed to the caller keeps the context alive
+    return params_for_caller(ctx, c, out);
 }
 int32_t stark_poseidon_params_for_width(stark_ctx_t* ctx, int32_t t, stark_params_t** out) {
     if (!ctx || !out) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     if (host::rp_for_width(t) < 0) return ctx->fail(STARK_ERR_UNSUPPORTED, "unsupported Poseidon width t; supported t in {9,17,33,65,129}");   // poseidon/src/lib.rs:127
-    { int32_t rc = params_from_consts(ctx, host::consts_for_width(t), out); if (rc == STARK_OK) (*out)->ref_.bind(ctx); return rc; }   // a set handed to the caller keeps the context alive
+    return params_for_caller(ctx, host::consts_for_width(t), out);
 }
 int32_t stark_poseidon_params_t17_seed(stark_ctx_t* ctx, const uint8_t* seed, size_t n, stark_params_t** out) {
     if (!ctx || !out || (!seed && n)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    { int32_t rc = params_from_consts(ctx, host::derive_consts(std::string((const char*)seed, n), 17, 8, 64), out); if (rc == STARK_OK) (*out)->ref_.bind(ctx); return rc; }   // a set handed to the caller keeps the context alive
+    return params_for_caller(ctx, host::derive_consts(std::string((const char*)seed, n), 17, 8, 64), out);
 }
 int32_t stark_poseidon_params_export(stark_params_t* p, int32_t* t, int32_t* rf, int32_t* rp, uint64_t* mds, uint64_t* rc_full, uint64_t* rc_partial) {
     if (!p) return STARK_ERR_INVALID_ARG;

@@ -26,11 +26,10 @@ struct stark_fri_state {
     CtxRef ref_;
     stark_ctx* ctx = nullptr;
     std::vector<size_t> schedule;
-    std::vector<fr_t*> f; std::vector<size_t> n;           // L+1 layers (device, pooled)
+    std::vector<DevBuf> f; std::vector<size_t> n;          // L+1 layers (device, pooled)
     std::vector<fr_t> z;                                    // L fold challenges
-    std::vector<stark_tree*> trees; std::vector<size_t> arity;
+    std::vector<std::unique_ptr<stark_tree>> trees; std::vector<size_t> arity;
     std::vector<fr_t> roots;                                // fetched on first use (one download + one sync for all L+1)
-    ~stark_fri_state() { for (auto p : f) if (p) ctx_release(ctx, p); for (auto t : trees) if (t) stark_merkle_free(t); }
 };
 
 static inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
@@ -82,7 +81,7 @@ static int32_t state_roots(stark_fri_state* S) {
     if (!S->roots.empty()) return STARK_OK;
     stark_ctx* ctx = S->ctx; std::vector<fr_t> r(S->trees.size());
     for (size_t l = 0; l < S->trees.size(); ++l) {
-        stark_tree* T = S->trees[l];
+        const stark_tree* T = S->trees[l].get();
         if (T->lens.back() != 1) return ctx->fail(STARK_ERR_INVALID_ARG, "partial (sharded) tree has no root");
         STARK_HIP(ctx, hipMemcpyAsync(&r[l], T->levels.back(), sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
     }
@@ -109,59 +108,56 @@ static int32_t fri_prelude(stark_ctx* ctx, const std::vector<size_t>& n, const s
     return STARK_OK;
 }
 // The commitment of layer l on `st`.  A hashed arity hashes the leaf pairs (f[i], s[i] = f_next[i / m]; zeros on the last layer, fri.rs:266, 283)
-// and adopts the digests as level 0; any other arity is commit_pairs(f, s) (fri.rs:289).  The n leaves sit at DS positions pos0 onwards, and the
+// and moves the digests into the tree as level 0; any other arity is commit_pairs(f, s) (fri.rs:289).  The n leaves sit at DS positions pos0 onwards, and the
 // tree climbs until a level of `stop` nodes (0: to the root).
 static int32_t commit_layer_on(stark_ctx* ctx, hipStream_t st, stark_params* mp, size_t arity, size_t l, const fr_t* f, const fr_t* f_next, size_t n, size_t m,
-                               uint64_t pos0, size_t stop, stark_tree** out) {
-    if (!hashed_arity(arity)) return merkle_build_on(ctx, st, mp, arity, (uint64_t)l, f, n, 1, f_next, m, pos0, 0, stop, false, out);
-    void* h = nullptr; STARK_TRY(ctx_alloc(ctx, n * sizeof(fr_t), &h));
-    stark_tree* T = nullptr;
-    int32_t rc = leaf_pair_hash_on(ctx, st, f, f_next, n, m, (fr_t*)h);
-    if (rc == STARK_OK) rc = merkle_build_on(ctx, st, mp, arity, (uint64_t)l, (const fr_t*)h, n, 0, nullptr, 1, pos0, 0, stop, /*adopt=*/true, &T);
-    if (rc) { if (!T) ctx_release(ctx, h); return rc; }
-    *out = T; return STARK_OK;
+                               uint64_t pos0, size_t stop, std::unique_ptr<stark_tree>& out) {
+    if (!hashed_arity(arity)) return merkle_build_on(ctx, st, mp, arity, (uint64_t)l, f, n, 1, f_next, m, pos0, 0, stop, DevBuf(), out);
+    DevBuf h; STARK_TRY(h.take(ctx, n * sizeof(fr_t)));
+    STARK_TRY(leaf_pair_hash_on(ctx, st, f, f_next, n, m, h.fr()));
+    return merkle_build_on(ctx, st, mp, arity, (uint64_t)l, nullptr, n, 0, nullptr, 1, pos0, 0, stop, std::move(h), out);
 }
 
-static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state** out) {
-    stark_fri_state* S = new stark_fri_state(); S->ref_.bind(ctx); S->ctx = ctx; S->schedule.assign(schedule, schedule + L);
-    auto bail = [&](int32_t rc) { delete S; return rc; };
-    { int32_t rc = layers_or_fail(ctx, n0, schedule, L, S->n, S->arity); if (rc) return bail(rc); }
-    S->trees.assign(L + 1, nullptr);
+static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, std::unique_ptr<stark_fri_state>& out) {
+    std::unique_ptr<stark_fri_state> S(new stark_fri_state()); S->ref_.bind(ctx); S->ctx = ctx; S->schedule.assign(schedule, schedule + L);
+    STARK_TRY(layers_or_fail(ctx, n0, schedule, L, S->n, S->arity));
+    S->trees.resize(L + 1);
     // The prelude runs BEFORE any stream is forked.
     std::vector<stark_params*> mps;
-    { int32_t rc = fri_prelude(ctx, S->n, S->arity, seed_z, mps, S->z); if (rc) return bail(rc); }
+    STARK_TRY(fri_prelude(ctx, S->n, S->arity, seed_z, mps, S->z));
     size_t zp_total = 0; for (size_t l = 0; l < L; ++l) zp_total += schedule[l];
-    hipStream_t main_stream = ctx->stream, side = nullptr;
+    hipStream_t main_stream = ctx->stream;
     // layer 0 copy + folds back to back (the challenges do not depend on any commitment: fri.rs:250)
-    for (size_t l = 0; l <= L; ++l) { void* q = nullptr; int32_t rc = ctx_alloc(ctx, S->n[l] * sizeof(fr_t), &q); S->f.push_back((fr_t*)q); if (rc) return bail(rc); }
-    if (hipMemcpyAsync(S->f[0], f0_dev, n0 * sizeof(fr_t), hipMemcpyDeviceToDevice, main_stream) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "copy f0"));
-    DevBuf zp; if (L && zp.alloc(ctx, zp_total * sizeof(fr_t)) != hipSuccess) return bail(ctx->fail(STARK_ERR_OOM, "z powers"));
+    S->f.resize(L + 1);
+    for (size_t l = 0; l <= L; ++l) STARK_TRY(S->f[l].take(ctx, S->n[l] * sizeof(fr_t)));
+    if (hipMemcpyAsync(S->f[0].p, f0_dev, n0 * sizeof(fr_t), hipMemcpyDeviceToDevice, main_stream) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "copy f0");
+    DevBuf zp; if (L && zp.alloc(ctx, zp_total * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "z powers");
     { size_t off = 0;
       for (size_t l = 0; l < L; ++l) {
-          int32_t rc = zpows_launch(ctx, main_stream, S->z[l], schedule[l], zp.fr() + off); if (rc) return bail(rc);
-          rc = fold_launch(ctx, main_stream, S->f[l], S->n[l], zp.fr() + off, schedule[l], S->f[l + 1]); if (rc) return bail(rc);
+          STARK_TRY(zpows_launch(ctx, main_stream, S->z[l], schedule[l], zp.fr() + off));
+          STARK_TRY(fold_launch(ctx, main_stream, S->f[l].fr(), S->n[l], zp.fr() + off, schedule[l], S->f[l + 1].fr()));
           off += schedule[l];
       } }
     // Commitments of all L+1 layers (independent jobs).  Layer 0 is ~94 % of the hashing and fills the GPU; the later layers
     // are small and mostly LATENCY-bound (tree tops: one dependent permutation per level), so they go to a side stream and run
     // underneath layer 0 instead of after it.  The streams are passed explicitly; the side stream is forked from and joined back
-    // into the main one with events, so nothing here synchronises the host.
-    { int32_t rc = ctx_fork(ctx, &side); if (rc) return bail(rc); }
+    // into the main one with events, so nothing here synchronises the host.  A failure from here on leaves through the guard, which
+    // drains both streams before S and zp return their blocks.
+    StreamFork fk(ctx); STARK_TRY(fk.fork());
     auto commit_layer = [&](size_t l, hipStream_t st) {
-        return commit_layer_on(ctx, st, mps[l], S->arity[l], l, S->f[l], l < L ? S->f[l + 1] : nullptr, S->n[l], l < L ? schedule[l] : 1, 0, 0, &S->trees[l]);
+        return commit_layer_on(ctx, st, mps[l], S->arity[l], l, S->f[l].fr(), l < L ? S->f[l + 1].fr() : nullptr, S->n[l], l < L ? schedule[l] : 1, 0, 0, S->trees[l]);
     };
     // Underneath a layer-0 leaf launch of 32 or more chip-fills (k_leaf_pair2: 4 workgroups of 64 leaves per CU) the side stream has time to spare,
     // but every wave slot it holds is one the leaf launch cannot use: its levels and leaf layers then take the wave-pair form at every size (64
     // sponges per two waves) instead of the latency forms (one wave, or five waves, per sponge) — option "fri_side_pair", read by the selector of capi_poseidon.hip.
     ctx->side_commit = ctx->opt.fri_side_pair && S->n[0] >= (size_t)ctx->num_cus * 4 * 64 * 32;
     int32_t crc = STARK_OK;
-    for (size_t l = L; l >= 1 && crc == STARK_OK; --l) crc = commit_layer(l, side);
+    for (size_t l = L; l >= 1 && crc == STARK_OK; --l) crc = commit_layer(l, fk.side);
     ctx->side_commit = false;
     if (crc == STARK_OK) crc = commit_layer(0, main_stream);
-    // join: the main stream continues only after the side stream's commitments
-    { int32_t rc = ctx_join(ctx); if (rc) { (void)hipStreamSynchronize(side); return bail(rc); } }
-    if (crc != STARK_OK) { (void)hipStreamSynchronize(side); (void)hipStreamSynchronize(main_stream); return bail(crc); }
-    *out = S; return STARK_OK;
+    STARK_TRY(crc);
+    STARK_TRY(fk.join());                                           // the main stream continues only after the side stream's commitments
+    out = std::move(S); return STARK_OK;
 }
 
 // Two-level power table of a domain generator, cached per (generator, size) — the reference's DomainH (deep_ali/src/lib.rs:109-125).
@@ -321,7 +317,7 @@ struct StateArrays {                                    // a stark_fri_state: on
     stark_fri_state* S;
     size_t traces() const { return 1; }
     size_t layers() const { return S->f.size(); }
-    const fr_t* layer(size_t, size_t l, size_t* len) const { *len = S->n[l]; return S->f[l]; }
+    const fr_t* layer(size_t, size_t l, size_t* len) const { *len = S->n[l]; return S->f[l].fr(); }
     size_t levels(size_t l) const { return S->trees[l]->levels.size(); }
     const fr_t* level(size_t, size_t l, size_t v, size_t* len) const { *len = S->trees[l]->lens[v]; return S->trees[l]->levels[v]; }
     int32_t roots_host(stark_ctx*, std::vector<fr_t>& rt) const { STARK_TRY(state_roots(S)); rt = S->roots; return STARK_OK; }
@@ -334,11 +330,9 @@ struct stark_fri_plan { CtxRef ref_; stark_ctx* ctx = nullptr; FriPlan plan; };
 // The executor of FriBatchCommit on the device.  Everything it allocates is pooled and returns to the pool with it; the folds run on the
 // context's stream, the commitments on the current one (the side stream between fork() and side(false)).
 struct FriDevExec {
-    stark_ctx* ctx; hipStream_t main_st, side_st = nullptr, cur; std::vector<void*> blocks; bool forked = false;
-    explicit FriDevExec(stark_ctx* c) : ctx(c), main_st(c->stream), cur(c->stream) {}
-    FriDevExec(const FriDevExec&) = delete; FriDevExec& operator=(const FriDevExec&) = delete;
-    ~FriDevExec() { if (forked) (void)hipStreamSynchronize(side_st); for (void* p : blocks) ctx_release(ctx, p); }
-    int32_t alloc(size_t bytes, void** out) { STARK_TRY(ctx_alloc(ctx, bytes, out)); blocks.push_back(*out); return STARK_OK; }
+    stark_ctx* ctx; hipStream_t main_st, cur; std::vector<DevBuf> blocks; StreamFork fk;      // fk after blocks: a scope left forked drains before they are released
+    explicit FriDevExec(stark_ctx* c) : ctx(c), main_st(c->stream), cur(c->stream), fk(c) {}
+    int32_t alloc(size_t bytes, void** out) { DevBuf b; STARK_TRY(b.take(ctx, bytes)); *out = b.p; blocks.push_back(std::move(b)); return STARK_OK; }
     int32_t upload(void* dst, const void* src, size_t bytes) { return ctx_upload_staged(ctx, dst, src, bytes); }     // the context owns the host copy: src may die on return
     template <class T> int32_t put(const std::vector<T>& h, T** out) {
         void* p = nullptr; STARK_TRY(alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p));
@@ -350,9 +344,9 @@ struct FriDevExec {
     int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h) { return leaf_pair_hash_on(ctx, cur, f, f_next, n, m, h); }
     int32_t pair_level(size_t arity, const DsBatchPairStream& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
     int32_t ds_level(size_t arity, const DsBatchStream& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
-    int32_t fork() { STARK_TRY(ctx_fork(ctx, &side_st)); forked = true; return STARK_OK; }
-    void side(bool on) { cur = on && side_st ? side_st : main_st; }
-    int32_t join() { if (forked) { STARK_TRY(ctx_join(ctx)); forked = false; } return STARK_OK; }
+    int32_t fork() { return fk.fork(); }
+    void side(bool on) { cur = on && fk.side ? fk.side : main_st; }
+    int32_t join() { return fk.join(); }
 };
 typedef FriBatchCommit<FriDevExec> FriDevBatch;
 constexpr size_t kMaxPassTraces = 32768;             // blockIdx.y of the merge and copy kernels is the trace
@@ -419,7 +413,7 @@ struct BatchArrays {                                    // the traces of a side-
 // synchronisations, whatever the number of traces: the roots; the "FRI/seed" hashes (one launch); the r * L "FRI/index" hashes per proof (one
 // launch; none when r * L = 0); the opened values (one gather launch; none when nothing is opened).  Seeds and index seeds are pre-loaded into each
 // proof's MemoHasher, so fri_plan_make and assemble_proof run per proof without touching the device (ReseedOnlyHasher).
-template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V, size_t n0, const size_t* schedule, size_t L, size_t r, stark_proof** out) {
+template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V, size_t n0, const size_t* schedule, size_t L, size_t r, std::unique_ptr<stark_proof>* out) {
     const size_t Bp = V.traces(), R = L + 1, q = r * L;
     std::vector<fr_t> rt, seed(Bp), in(3 * q * Bp), idx(q * Bp);
     STARK_TRY(V.roots_host(ctx, rt));
@@ -449,10 +443,8 @@ template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V
     std::vector<fr_t> vals(G.size());
     STARK_TRY(gather_rows(ctx, G, nullptr, vals.data()));                                                                // ONE gather over all proofs' requests, one download
     for (size_t b = 0; b < Bp; ++b) {
-        std::unique_ptr<stark_proof> P(new stark_proof());
-        const int32_t rc = assemble_from_values(ctx, plan[b].shape, r, *H[b], vals.data() + row0[b], row0[b + 1] - row0[b], P.get());
-        if (rc) { for (size_t j = 0; j < b; ++j) { delete out[j]; out[j] = nullptr; } return rc; }
-        out[b] = P.release();
+        out[b].reset(new stark_proof());
+        STARK_TRY(assemble_from_values(ctx, plan[b].shape, r, *H[b], vals.data() + row0[b], row0[b + 1] - row0[b], out[b].get()));
     }
     return STARK_OK;
 }
@@ -476,8 +468,7 @@ struct PassCommit {
                 f = merged.fr();
             }
             if (t_layer0) *t_layer0 = Clock::now();
-            stark_fri_state* s = nullptr; STARK_TRY(fri_build_impl(ctx, f, n0, schedule, L, seed_z, &s)); S.reset(s);       // copies f: `merged` returns to the pool behind that copy
-            return STARK_OK;
+            return fri_build_impl(ctx, f, n0, schedule, L, seed_z, S);       // copies f: `merged` returns to the pool behind that copy
         }
         STARK_TRY(batch_commit_begin(ctx, C, Bp, n0, schedule, L, seed_z));
         if (f0) STARK_TRY(batch_fill_layer0(ctx, X, C, f0));
@@ -495,7 +486,7 @@ struct PassCommit {
 // One pass of a batch prove: layer 0 -> commit phase -> query phase -> stage times.  Host synchronisations per pass: the FOUR of batch_queries, whatever
 // Bp (layer 0 and the commit phase only enqueue).  stage_ms of every proof of the pass: shared_ms + the pass's layer 0, its commit, its queries.
 static int32_t prove_pass(stark_ctx* ctx, size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, size_t n0,
-                          const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, stark_proof** out) {
+                          const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, std::unique_ptr<stark_proof>* out) {
     const auto u0 = Clock::now(); auto u1 = u0;
     PassCommit P(ctx);
     STARK_TRY(P.run(Bp, cols, zs, f0, n0, schedule, L, seed_z, &u1));
@@ -507,15 +498,12 @@ static int32_t prove_pass(stark_ctx* ctx, size_t Bp, const uint64_t* const* cons
     for (size_t b = 0; b < Bp; ++b) { out[b]->ms[0] = shared_ms + ms_between(u0, u1); out[b]->ms[1] = ms_between(u1, u2); out[b]->ms[2] = ms_between(u2, u3); }
     return STARK_OK;
 }
-static void free_proofs(stark_proof** out, size_t B) { for (size_t p = 0; p < B; ++p) if (out[p]) { delete out[p]; out[p] = nullptr; } }
 // stark_deep_fri_prove_f0_batch_dev, and stark_deep_fri_prove_dev given f0 with B = 1: the batch cut into passes of at most "prove_batch_max_rows" rows.
 static int32_t prove_f0_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
     const size_t per = pass_traces(ctx, n0);
-    for (size_t p0 = 0; p0 < B; p0 += per) {
-        const int32_t rc = prove_pass(ctx, std::min(per, B - p0), nullptr, nullptr, f0 + p0, n0, schedule, L, r, seed_z, 0.0, out + p0);
-        if (rc) { free_proofs(out, B); return rc; }
-    }
-    return STARK_OK;
+    std::vector<std::unique_ptr<stark_proof>> pf(B);
+    for (size_t p0 = 0; p0 < B; p0 += per) STARK_TRY(prove_pass(ctx, std::min(per, B - p0), nullptr, nullptr, f0 + p0, n0, schedule, L, r, seed_z, 0.0, pf.data() + p0));
+    hand_out(pf, out); return STARK_OK;
 }
 // stark_fri_commit_batch_dev: the roots of fri_build of every trace, roots[(b (L + 1) + l) * 4 ..]; one synchronisation per pass.
 static int32_t commit_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, uint64_t* roots) {
@@ -615,12 +603,12 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
     AliChallenges ch; STARK_TRY(challenge_stage(ctx, B, ptrs.data(), n0, ch));
     const double shared_ms = ms_between(t0, Clock::now());
     const size_t per = pass_traces(ctx, n0);
+    std::vector<std::unique_ptr<stark_proof>> pf(B);
     for (size_t p0 = 0; p0 < B; p0 += per) {
         const uint64_t* const* const cols[4] = {a + p0, s + p0, e + p0, t + p0};
-        const int32_t rc = prove_pass(ctx, std::min(per, B - p0), cols, ch.z.data() + p0, nullptr, n0, schedule, L, r, seed_z, shared_ms, out + p0);
-        if (rc) { free_proofs(out, B); return rc; }
+        STARK_TRY(prove_pass(ctx, std::min(per, B - p0), cols, ch.z.data() + p0, nullptr, n0, schedule, L, r, seed_z, shared_ms, pf.data() + p0));
     }
-    return STARK_OK;
+    hand_out(pf, out); return STARK_OK;
 }
 
 extern "C" {
@@ -645,26 +633,28 @@ int32_t stark_fri_fold(stark_ctx_t* ctx, const uint64_t* f, size_t n, const uint
 int32_t stark_fri_build_dev(stark_ctx_t* ctx, const uint64_t* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state_t** out) {
     if (!ctx || !f0 || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return fri_build_impl(ctx, as_fr(f0), n0, schedule, L, seed_z, out);
+    std::unique_ptr<stark_fri_state> S; STARK_TRY(fri_build_impl(ctx, as_fr(f0), n0, schedule, L, seed_z, S));
+    *out = S.release(); return STARK_OK;
 }
 int32_t stark_fri_build(stark_ctx_t* ctx, const uint64_t* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state_t** out) {
     if (!ctx || !f0 || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     DevBuf d; STARK_HIP(ctx, d.upload(ctx, f0, n0 * sizeof(fr_t)));
-    STARK_TRY(fri_build_impl(ctx, d.fr(), n0, schedule, L, seed_z, out)); return STARK_OK;
+    std::unique_ptr<stark_fri_state> S; STARK_TRY(fri_build_impl(ctx, d.fr(), n0, schedule, L, seed_z, S));
+    *out = S.release(); return STARK_OK;
 }
 int32_t stark_fri_num_layers(stark_fri_state_t* s) { return s ? (int32_t)s->f.size() : STARK_ERR_INVALID_ARG; }
 size_t stark_fri_layer_len(stark_fri_state_t* s, int32_t l) { return (s && l >= 0 && (size_t)l < s->n.size()) ? s->n[l] : 0; }
 int32_t stark_fri_layer_f(stark_fri_state_t* s, int32_t l, uint64_t* out) {
     if (!s || !out || l < 0 || (size_t)l >= s->f.size()) return STARK_ERR_INVALID_ARG; stark_ctx* ctx = s->ctx;
-    STARK_HIP(ctx, hipMemcpyAsync(out, s->f[l], s->n[l] * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
+    STARK_HIP(ctx, hipMemcpyAsync(out, s->f[l].p, s->n[l] * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
 }
 int32_t stark_fri_layer_root(stark_fri_state_t* s, int32_t l, uint64_t* out4) {
     if (!s || !out4 || l < 0 || (size_t)l >= s->trees.size()) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(s->ctx)); STARK_TRY(state_roots(s)); store_fr(out4, s->roots[l]); return STARK_OK;
 }
 int32_t stark_fri_layer_z(stark_fri_state_t* s, int32_t l, uint64_t* out4) { if (!s || !out4 || l < 0 || (size_t)l >= s->z.size()) return STARK_ERR_INVALID_ARG; store_fr(out4, s->z[l]); return STARK_OK; }
-stark_tree_t* stark_fri_layer_tree(stark_fri_state_t* s, int32_t l) { return (s && l >= 0 && (size_t)l < s->trees.size()) ? s->trees[l] : nullptr; }
+stark_tree_t* stark_fri_layer_tree(stark_fri_state_t* s, int32_t l) { return (s && l >= 0 && (size_t)l < s->trees.size()) ? s->trees[l].get() : nullptr; }
 int32_t stark_fri_state_free(stark_fri_state_t* s) { if (!s) return STARK_ERR_INVALID_ARG; delete s; return STARK_OK; }   // layers and levels return to the pool (stream-ordered reuse)
 
 int32_t stark_ali_merge_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, const uint64_t* r_opt, const uint64_t* beta4,

@@ -360,32 +360,30 @@ int32_t stark_tr_hash_fields_tagged(stark_ctx_t* ctx, stark_params_t* tp, const 
 // ---- Merkle ------------------------------------------------------------------------------------------
 }  // extern "C"
 namespace stark {
-// MerkleTree::new / new_pairs on `st`.  pairs: leaves are (f_i, cp[i / cp_div]) pairs (cp == nullptr: zeros).  adopt: `leaves` is a
-// pooled block (ctx_alloc) whose ownership moves into the tree as level 0 (no copy); otherwise level 0 is a copy.
+// MerkleTree::new / new_pairs on `st`.  pairs: leaves are (f_i, cp[i / cp_div]) pairs (cp == nullptr: zeros).  level0: a pooled block that already
+// holds the n leaves is MOVED into the tree as level 0 (no copy; `leaves` is not read); an empty one: level 0 is a copy of `leaves`.  On a failure
+// the block is released once, by whoever holds it then: the caller's owner before the move, the tree that dies here after it.
 int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t arity, uint64_t label, const fr_t* leaves, size_t n, int pairs, const fr_t* cp, size_t cp_div,
-                        uint64_t first_pos, uint32_t level0, size_t stop_at_len, bool adopt, stark_tree** out) {
+                        uint64_t first_pos, uint32_t level0, size_t stop_at_len, DevBuf&& level0_block, std::unique_ptr<stark_tree>& out) {
     if (n == 0) return ctx->fail(STARK_ERR_INVALID_ARG, "no leaves");                                                 // merkle/src/lib.rs:148
     if (host::width_for_arity(arity) != p->dev.t) return ctx->fail(STARK_ERR_INVALID_ARG, "arity incompatible with Poseidon width");   // :155-161
     if (arity == 1 && n > 1) return ctx->fail(STARK_ERR_UNSUPPORTED, "arity 1 with more than one leaf never terminates in the reference");
-    stark_tree* T = new stark_tree(); T->ref_.bind(ctx); T->ctx = ctx; T->p = p; T->arity = arity; T->label = label;
-    auto bail = [&](int32_t rc) { delete T; return rc; };
-    fr_t* l0 = nullptr;
-    if (adopt && !pairs) l0 = const_cast<fr_t*>(leaves);
-    else { void* q = nullptr; int32_t rc = ctx_alloc(ctx, n * sizeof(fr_t), &q); if (rc) return bail(rc); l0 = (fr_t*)q; }
-    T->levels.push_back(l0); T->lens.push_back(n); T->owned.push_back(1);
-    if (pairs) { int32_t rc = hash_ds_on(ctx, st, p, DsStream::make(1, arity, 0xFFFFFFFFu, first_pos, label, leaves, cp, n, cp_div), l0); if (rc) return bail(rc); }
-    else if (!adopt && hipMemcpyAsync(l0, leaves, n * sizeof(fr_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "copy leaves"));
+    std::unique_ptr<stark_tree> T(new stark_tree(ctx, p, arity, label));
+    auto add_level = [&](DevBuf&& b, size_t len) { T->levels.push_back(b.fr()); T->lens.push_back(len); T->blocks.push_back(std::move(b)); };
+    const bool moved_in = level0_block.p && !pairs;
+    { DevBuf l0; if (moved_in) l0 = std::move(level0_block); else STARK_TRY(l0.take(ctx, n * sizeof(fr_t))); add_level(std::move(l0), n); }
+    if (pairs) STARK_TRY(hash_ds_on(ctx, st, p, DsStream::make(1, arity, 0xFFFFFFFFu, first_pos, label, leaves, cp, n, cp_div), T->levels[0]));
+    else if (!moved_in && hipMemcpyAsync(T->levels[0], leaves, n * sizeof(fr_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "copy leaves");
     uint32_t level = level0; uint64_t pos = first_pos; size_t stop = stop_at_len > 0 ? stop_at_len : 1;
     while (T->lens.back() > stop) {
         size_t len = T->lens.back(), nn = (len + arity - 1) / arity;
-        if (pos % arity) return bail(ctx->fail(STARK_ERR_INVALID_ARG, "shard offset not aligned to the arity"));
+        if (pos % arity) return ctx->fail(STARK_ERR_INVALID_ARG, "shard offset not aligned to the arity");
         pos /= arity;
-        void* nx = nullptr; { int32_t rc = ctx_alloc(ctx, nn * sizeof(fr_t), &nx); if (rc) return bail(rc); }
-        T->levels.push_back((fr_t*)nx); T->lens.push_back(nn); T->owned.push_back(1);
-        int32_t rc = hash_ds_on(ctx, st, p, DsStream::make(0, arity, level, pos, label, T->levels[T->levels.size() - 2], nullptr, len), (fr_t*)nx); if (rc) return bail(rc);
+        { DevBuf nx; STARK_TRY(nx.take(ctx, nn * sizeof(fr_t))); add_level(std::move(nx), nn); }
+        STARK_TRY(hash_ds_on(ctx, st, p, DsStream::make(0, arity, level, pos, label, T->levels[T->levels.size() - 2], nullptr, len), T->levels.back()));
         level += 1;
     }
-    *out = T; return STARK_OK;
+    out = std::move(T); return STARK_OK;
 }
 }  // namespace stark
 extern "C" {
@@ -393,7 +391,9 @@ int32_t stark_merkle_build_dev(stark_ctx_t* ctx, stark_params_t* p, size_t arity
                                uint64_t first_pos, uint32_t level0, int32_t stop_at_len, stark_tree_t** out) {
     if (!ctx || !p || !leaves || !out || arity == 0 || (pairs && !cp)) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad merkle args") : STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return merkle_build_on(ctx, ctx->stream, p, arity, label, as_fr(leaves), n, pairs, as_fr(cp), 1, first_pos, level0, stop_at_len > 0 ? (size_t)stop_at_len : 0, false, out);
+    std::unique_ptr<stark_tree> T;
+    STARK_TRY(merkle_build_on(ctx, ctx->stream, p, arity, label, as_fr(leaves), n, pairs, as_fr(cp), 1, first_pos, level0, stop_at_len > 0 ? (size_t)stop_at_len : 0, DevBuf(), T));
+    *out = T.release(); return STARK_OK;
 }
 int32_t stark_merkle_build(stark_ctx_t* ctx, stark_params_t* p, size_t arity, uint64_t label, const uint64_t* leaves, size_t n, int32_t pairs, const uint64_t* cp, stark_tree_t** out) {
     if (!ctx || !p || !leaves || !out || (pairs && !cp)) return STARK_ERR_INVALID_ARG;
@@ -435,9 +435,9 @@ namespace stark {
 // level blocks are pooled and owned by the holder the batch's trees share, and the labels and pointer tables go up as ONE staged upload.
 struct MerkleBatchDevExec {
     stark_ctx* ctx; stark_params* p; std::shared_ptr<TreeBlocks> blocks; DevBuf tab;
-    MerkleBatchDevExec(stark_ctx* c, stark_params* p_) : ctx(c), p(p_), blocks(std::make_shared<TreeBlocks>(c)) {}
+    MerkleBatchDevExec(stark_ctx* c, stark_params* p_) : ctx(c), p(p_), blocks(std::make_shared<TreeBlocks>()) {}
     int32_t level_block(size_t n_fr, fr_t** out) {
-        void* q = nullptr; STARK_TRY(ctx_alloc(ctx, n_fr * sizeof(fr_t), &q)); blocks->blocks.push_back(q); *out = (fr_t*)q; return STARK_OK;
+        DevBuf b; STARK_TRY(b.take(ctx, n_fr * sizeof(fr_t))); *out = b.fr(); blocks->blocks.push_back(std::move(b)); return STARK_OK;
     }
     int32_t tables(const uint64_t* labels, const fr_t* const* leaves, const fr_t* const* cp, size_t B, const uint64_t** labels_x, const fr_t* const** leaves_x, const fr_t* const** cp_x) {
         std::vector<uint64_t> h((cp ? 3 : 2) * B);                       // [labels | leaves | cp], eight bytes each
@@ -465,11 +465,12 @@ int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, siz
     MerkleBatchDevExec X(ctx, p);
     std::vector<size_t> lens; std::vector<fr_t*> base;
     STARK_TRY(merkle_build_batch(X, arity, batch, labels, reinterpret_cast<const fr_t* const*>(leaves), n, pairs, reinterpret_cast<const fr_t* const*>(cp), lens, base));
+    std::vector<std::unique_ptr<stark_tree>> trees(batch);
     for (size_t b = 0; b < batch; ++b) {
-        stark_tree* T = new stark_tree(); T->ref_.bind(ctx); T->ctx = ctx; T->p = p; T->arity = arity; T->label = labels[b]; T->shared = X.blocks;
-        for (size_t v = 0; v < lens.size(); ++v) { T->levels.push_back(base[v] + b * lens[v]); T->lens.push_back(lens[v]); T->owned.push_back(0); }
-        out[b] = T;
+        trees[b].reset(new stark_tree(ctx, p, arity, labels[b])); trees[b]->shared = X.blocks;
+        for (size_t v = 0; v < lens.size(); ++v) { trees[b]->levels.push_back(base[v] + b * lens[v]); trees[b]->lens.push_back(lens[v]); }
     }
+    for (size_t b = 0; b < batch; ++b) out[b] = trees[b].release();                      // the single success point
     return STARK_OK;
 }
 // THE row gather (declared in ctx.hpp): stark_merkle_gather, stark_merkle_roots_batch, every Merkle open and every DEEP-FRI query phase end here.
@@ -510,9 +511,7 @@ int32_t stark_merkle_build_batch_dev(stark_ctx_t* ctx, stark_params_t* p, size_t
     for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
     if (!ctx || !p || !tree_labels || !leaves || (pairs && !cp)) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad merkle batch args") : STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    const int32_t rc = merkle_build_batch_on(ctx, p, arity, batch, tree_labels, leaves, n, pairs, pairs ? cp : nullptr, out);
-    if (rc) for (size_t b = 0; b < batch; ++b) { delete out[b]; out[b] = nullptr; }
-    return rc;
+    return merkle_build_batch_on(ctx, p, arity, batch, tree_labels, leaves, n, pairs, pairs ? cp : nullptr, out);
 }
 int32_t stark_merkle_roots_batch(stark_tree_t* const* trees, size_t batch, uint64_t* roots) {
     if (!batch) return STARK_OK;
@@ -536,8 +535,9 @@ int32_t stark_merkle_open_batch(stark_tree_t* const* trees, size_t batch, const 
     const int32_t rc = merkle_open_batch(X, views.data(), batch, idx, idx_off, proofs);
     if (rc == -1) return ctx->fail(STARK_ERR_INVALID_ARG, "open batch: idx_off not increasing, an empty index list or a leaf index out of range");
     if (rc) return rc;
-    for (size_t b = 0; b < batch; ++b) { out[b] = new stark_proof(); out[b]->bytes = std::move(proofs[b]); }
-    return STARK_OK;
+    std::vector<std::unique_ptr<stark_proof>> pf(batch);
+    for (size_t b = 0; b < batch; ++b) { pf[b].reset(new stark_proof()); pf[b]->bytes = std::move(proofs[b]); }
+    hand_out(pf, out); return STARK_OK;
 }
 // open_union_of_paths (merkle/src/lib.rs:246-315) of one tree: merkle_open_batch over one view.  The three refusals keep their own wording (they run
 // first, so the batch driver's one message for all of them never surfaces here).

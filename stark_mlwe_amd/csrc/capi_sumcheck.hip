@@ -134,14 +134,6 @@ struct DevTranscript {
     }
 };
 
-// MerkleCommitment's parameters (commitment/src/lib.rs:48-51), cached per context next to the other parameter sets (key -17)
-static int32_t commit_params(stark_ctx* ctx, stark_params** out) {
-    auto it = ctx->merkle_params.find(-17);
-    if (it != ctx->merkle_params.end()) { *out = it->second; return STARK_OK; }
-    stark_params* P = nullptr; const char* seed = "POSEIDON-T17-X5-SEED";
-    STARK_TRY(stark_poseidon_params_t17_seed(ctx, (const uint8_t*)seed, strlen(seed), &P));
-    ctx->merkle_params[-17] = P; *out = P; return STARK_OK;
-}
 static int32_t fold(stark_ctx* ctx, const fr_t* layer, size_t len, const fr_t& r, fr_t* next) {
     const uint64_t np = len / 2;
     hipLaunchKernelGGL(k_sc_fold, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, ctx->stream, layer, np, r, next);
@@ -151,10 +143,10 @@ static int32_t fold(stark_ctx* ctx, const fr_t* layer, size_t len, const fr_t& r
 // the context's stream; uploads are staged until the next download synchronises.
 struct ScDevExec {
     stark_ctx* ctx; stark_params* cp; stark_params* tp;
-    std::vector<std::unique_ptr<DevBuf>> mem; std::vector<std::vector<uint8_t>> staged;
+    std::vector<DevBuf> mem; std::vector<std::vector<uint8_t>> staged;
     ScDevExec(stark_ctx* c, stark_params* commit, stark_params* tr) : ctx(c), cp(commit), tp(tr) {}
     ~ScDevExec() { if (!staged.empty()) (void)hipStreamSynchronize(ctx->stream); }
-    int32_t alloc(size_t bytes, void** out) { mem.emplace_back(new DevBuf()); STARK_HIP(ctx, mem.back()->alloc(ctx, bytes)); *out = mem.back()->p; return STARK_OK; }
+    int32_t alloc(size_t bytes, void** out) { mem.emplace_back(); STARK_HIP(ctx, mem.back().alloc(ctx, bytes)); *out = mem.back().p; return STARK_OK; }
     int32_t upload(void* dst, const void* src, size_t bytes) {
         staged.emplace_back((const uint8_t*)src, (const uint8_t*)src + bytes);
         STARK_HIP(ctx, hipMemcpyAsync(dst, staged.back().data(), bytes, hipMemcpyHostToDevice, ctx->stream)); return STARK_OK;
@@ -190,7 +182,7 @@ static int32_t prove_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t B, const
     for (size_t b = 0; b < B; ++b) out[b] = nullptr;
     if (k > 40) return ctx->fail(STARK_ERR_INVALID_ARG, "k too large");
     if (!B) return STARK_OK;
-    stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
+    stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
     std::vector<const fr_t*> w(B); for (size_t b = 0; b < B; ++b) w[b] = as_fr(witnesses[b]);
     std::vector<std::vector<uint8_t>> proofs;
     {
@@ -199,15 +191,16 @@ static int32_t prove_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t B, const
         const int32_t rc = mf ? S.prove_mf(qpr, proofs) : S.prove_plain(proofs);
         if (rc) return rc;
     }
-    for (size_t b = 0; b < B; ++b) { out[b] = new stark_proof(); out[b]->bytes.swap(proofs[b]); out[b]->size_estimate = out[b]->bytes.size(); }
-    return STARK_OK;
+    std::vector<std::unique_ptr<stark_proof>> pf(B);
+    for (size_t b = 0; b < B; ++b) { pf[b].reset(new stark_proof()); pf[b]->bytes.swap(proofs[b]); pf[b]->size_estimate = pf[b]->bytes.size(); }
+    hand_out(pf, out); return STARK_OK;
 }
 
 // Runs one plan of the batched verifiers: one upload (the proofs' bytes and the plan's index arrays), the decode, the transcript streams,
 // the DS groups in depth order, the checks, one download of the flags and one synchronisation.
 static int32_t run_sc_verify_batch(stark_ctx* ctx, const ScVerifyPlan& V, int32_t* accepted) {
     if (!V.batch) return STARK_OK;
-    stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
+    stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const VerifyBatchPlan& D = V.ds;
     const size_t o_flag = 0, o_blob = al(V.batch * 4), o_doff = al(o_blob + V.blob.size() * 4), o_dpr = al(o_doff + V.n_dec * 4), o_con = al(o_dpr + V.n_dec * 4),
@@ -329,9 +322,9 @@ extern "C" {
 int32_t stark_transcript_new(stark_ctx_t* ctx, const uint8_t* label, size_t label_len, stark_transcript_t** out) {
     if (!ctx || !out || (!label && label_len)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    stark_transcript* t = new stark_transcript(ctx);
-    int32_t rc = t->T.init(label, label_len); if (rc) { delete t; return rc; }
-    *out = t; return STARK_OK;
+    std::unique_ptr<stark_transcript> t(new stark_transcript(ctx));
+    STARK_TRY(t->T.init(label, label_len));
+    *out = t.release(); return STARK_OK;
 }
 int32_t stark_transcript_absorb_bytes(stark_transcript_t* t, const uint8_t* bytes, size_t n) { if (!t || (!bytes && n)) return STARK_ERR_INVALID_ARG; t->T.absorb_bytes(bytes, n); return STARK_OK; }
 int32_t stark_transcript_absorb_fields(stark_transcript_t* t, const uint64_t* fields, size_t n) {
@@ -386,10 +379,11 @@ int32_t stark_ref_bench_inputs(uint64_t seed, size_t n, size_t ncols, uint64_t* 
 int32_t stark_commitment_commit(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* leaves, size_t n, stark_tree_t** out) {
     if (!ctx || !leaves || !out) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
+    stark_params* cp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp));
     DevBuf d; STARK_HIP(ctx, d.upload(ctx, leaves, n * sizeof(fr_t)));
-    STARK_TRY(merkle_build_on(ctx, ctx->stream, cp, 16, ds_tag, d.fr(), n, 0, nullptr, 1, 0, 0, 0, false, out));     // commit (:85-90); open = stark_merkle_open (:92-94)
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
+    std::unique_ptr<stark_tree> T;
+    STARK_TRY(merkle_build_on(ctx, ctx->stream, cp, 16, ds_tag, d.fr(), n, 0, nullptr, 1, 0, 0, 0, DevBuf(), T));     // commit (:85-90); open = stark_merkle_open (:92-94)
+    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); *out = T.release(); return STARK_OK;
 }
 // commit of `batch` DEVICE vectors of n leaves side by side (merkle_build_batch_on): stream-ordered, no host synchronisation
 int32_t stark_commitment_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* ds_tags, const uint64_t* const* leaves, size_t n, stark_tree_t** out) {
@@ -398,17 +392,15 @@ int32_t stark_commitment_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const 
     for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
     if (!ctx || !ds_tags || !leaves) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad commitment batch args") : STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
-    const int32_t rc = merkle_build_batch_on(ctx, cp, 16, batch, ds_tags, leaves, n, 0, nullptr, out);
-    if (rc) for (size_t b = 0; b < batch; ++b) { delete out[b]; out[b] = nullptr; }
-    return rc;
+    stark_params* cp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp));
+    return merkle_build_batch_on(ctx, cp, 16, batch, ds_tags, leaves, n, 0, nullptr, out);
 }
 // verify (:96-113): verify_many_ds with the static t = 17 parameters lifted to the dynamic form
 int32_t stark_commitment_verify(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* root4, const size_t* indices, size_t k, const uint64_t* values, const uint8_t* proof, size_t len, int32_t* accepted) {
     if (!ctx || !root4 || (!indices && k) || (!values && k) || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
     *accepted = 0;
     STARK_TRY(ctx_enter(ctx));
-    stark_params* cp = nullptr; STARK_TRY(commit_params(ctx, &cp));
+    stark_params* cp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp));
     return merkle_verify_one(ctx, cp, 16, ds_tag, root4, indices, k, values, nullptr, proof, len, accepted);      // MerkleCommitment's parameters
 }
 

@@ -31,22 +31,17 @@ __global__ void __launch_bounds__(256) k_verify_batch_check(const fr_t* __restri
 
 // The leaf step and the DS groups of a plan whose arrays are on the device, in depth order on the context's stream (groups that share a
 // depth after the first on the side stream, joined before the next depth).  fixed != nullptr: every group hashes with that parameter set
-// (the sum-check openings: MerkleCommitment's) instead of ctx_merkle_params(G.t).  On an error both streams are drained.
+// (the sum-check openings: MerkleCommitment's) instead of ctx_merkle_params(G.t).  An error while forked drains both streams (StreamFork);
+// any other leaves the context's stream to the caller, who drains it for its staging vector anyway.
 int32_t stark::verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, const uint64_t* hdr, const uint32_t* off, const uint32_t* idx, fr_t* pool, stark_params* fixed) {
-    hipStream_t main_st = ctx->stream, side = nullptr;
-    bool forked = false;
-    auto bail = [&](int32_t rc) { if (forked) (void)hipStreamSynchronize(side); (void)hipStreamSynchronize(main_st); return rc; };
+    hipStream_t main_st = ctx->stream; StreamFork fk(ctx);
     for (size_t g0 = 0, depth = 1; g0 < V.groups.size() || (depth == 1 && V.nl); ++depth) {
         // the launches of this depth: the leaf step (depth 1), then the DS groups of each width
         std::vector<int> items; if (depth == 1 && V.nl) items.push_back(-1);
         size_t g1 = g0; while (g1 < V.groups.size() && V.groups[g1].depth == depth) items.push_back((int)g1++);
         for (size_t i = 0; i < items.size(); ++i) {
-            hipStream_t st = main_st;
-            if (i == 1) {                                              // fork: the rest of this depth on the side stream
-                { int32_t rc = ctx_fork(ctx, &side); if (rc) return bail(rc); }
-                forked = true;
-            }
-            if (i >= 1) st = side;
+            if (i == 1) STARK_TRY(fk.fork());                          // the rest of this depth on the side stream
+            const hipStream_t st = i >= 1 ? fk.side : main_st;
             int32_t rc = STARK_OK;
             if (items[i] < 0) rc = leaf_pair_hash_on(ctx, st, pool + V.leaf_f0, pool + V.leaf_f0 + V.nl, V.nl, 1, pool + V.leaf_out0);
             else {
@@ -55,11 +50,9 @@ int32_t stark::verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, 
                 const DsGatherStream D{hdr + 4 * G.job0, off + G.job0, idx, pool, G.n, G.max_children};
                 if (!rc) rc = hash_ds_on(ctx, st, mp, D, pool + G.out0);
             }
-            if (rc) return bail(rc);
+            STARK_TRY(rc);
         }
-        if (items.size() > 1) {                                        // join before the next depth reads these digests
-            int32_t rc = ctx_join(ctx); if (rc) return bail(rc);
-        }
+        STARK_TRY(fk.join());                                          // before the next depth reads these digests (nothing when this depth did not fork)
         g0 = g1;
     }
     return STARK_OK;

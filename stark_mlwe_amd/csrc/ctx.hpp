@@ -16,9 +16,10 @@
 namespace stark { struct NttPlan; struct PowCache; }
 
 // Handles (trees, FRI states, plans, transcripts, caller-made parameter sets) keep their context alive: stark_ctx_destroy with live handles
-// only marks the context; the LAST handle freed tears it down.  `CtxRef` is the FIRST member of every handle type, so it is destroyed last — after
-// the handle's own destructor has returned its blocks to the context's pool.  (A Rust host drops its thread-local context at thread exit while
-// Tree / ProverState values owned by the caller may outlive it — ADVICE r2.)
+// only marks the context; the LAST handle freed tears it down.  `CtxRef` is the FIRST member of every handle type and members are destroyed in
+// reverse order, so it is destroyed last — after the handle's owners (DevBuf, unique_ptr<stark_tree>, the shared TreeBlocks) have returned
+// their blocks to the context's pool.  No handle has a destructor of its own.  (A Rust host drops its thread-local context at thread exit
+// while Tree / ProverState values owned by the caller may outlive it — ADVICE r2.)
 namespace stark { void ctx_ref(stark_ctx* c); void ctx_unref(stark_ctx* c); }
 struct CtxRef {
     stark_ctx* c = nullptr;
@@ -67,8 +68,8 @@ struct stark_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;         // stark_timer_start / stop
     hipEvent_t ev_fork = nullptr;                    // orders the side stream after the main one and back (ctx_fork / ctx_join)
     // lazily created constants
-    stark_params* tparams = nullptr;                 // transcript params (t=17, "POSEIDON-T17-X5-TRANSCRIPT")
-    std::map<int, stark_params*> merkle_params;      // poseidon_params_for_width(t)
+    std::unique_ptr<stark_params> tparams;           // transcript params (t=17, "POSEIDON-T17-X5-TRANSCRIPT")
+    std::map<int, std::unique_ptr<stark_params>> merkle_params;   // poseidon_params_for_width(t)
     stark::DevMem leaf_init;                         // 17-lane template of hash_leaf_pair (device)
     std::map<std::string, stark::DevMem> tr_frames;  // per-tag transcript prefix/suffix frames (device): [prefix.., suffix..]
     std::map<std::string, std::pair<int, int>> tr_frame_dims;
@@ -123,29 +124,44 @@ struct stark_ctx {
 };
 
 namespace stark {
-int32_t ctx_alloc(stark_ctx* ctx, size_t bytes, void** out);   // pooled device memory (see stark_ctx::pool_free)
+// The pooled allocator's two functions (capi_core.hip; see stark_ctx::pool_free).  Only DevBuf calls them.
+int32_t ctx_alloc(stark_ctx* ctx, size_t bytes, void** out);
 void ctx_release(stark_ctx* ctx, void* p);
-}
-namespace stark {
+
+// THE owner of one pooled block (move-only): the block returns to its context's pool on reset() or destruction, exactly once, by whoever holds
+// the owner at that point.  Temporaries of an entry point, the layers and tree levels of the handles and adopted blocks (merkle_build_on) are all this.
+struct DevBuf {
+    stark_ctx* ctx = nullptr; void* p = nullptr;
+    DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : ctx(o.ctx), p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); ctx = o.ctx; p = o.p; o.p = nullptr; } return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) { ctx_release(ctx, p); p = nullptr; } }      // releases now; idempotent
+    int32_t take(stark_ctx* c, size_t bytes) { reset(); ctx = c; return ctx_alloc(c, bytes, &p); }     // the allocator's own code and message
+    hipError_t alloc(stark_ctx* c, size_t bytes) { return take(c, bytes) == STARK_OK ? hipSuccess : hipErrorOutOfMemory; }
+    // alloc, then the upload of `bytes` from host memory enqueued on the context's stream (`src` stays valid until the next synchronisation)
+    hipError_t upload(stark_ctx* c, const void* src, size_t bytes) { const hipError_t e = alloc(c, bytes); return e != hipSuccess || !bytes ? e : hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, c->stream); }
+    // the first `bytes` to host memory, then one synchronisation of the context's stream
+    hipError_t download_sync(void* dst, size_t bytes) const { const hipError_t e = bytes ? hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream); }
+    fr_t* fr() const { return reinterpret_cast<fr_t*>(p); }
+};
 // The pooled blocks the trees of one batched build share (merkle_batch.hpp: level v of all trees is one block): every tree of the batch holds a
 // reference, and the blocks go back to the context's pool when the last of them is freed.  Each holding tree pins the context (its CtxRef outlives
 // this member), so the context is alive whenever the blocks are released.
-struct TreeBlocks {
-    stark_ctx* ctx; std::vector<void*> blocks;
-    explicit TreeBlocks(stark_ctx* c) : ctx(c) {}
-    TreeBlocks(const TreeBlocks&) = delete; TreeBlocks& operator=(const TreeBlocks&) = delete;
-    ~TreeBlocks() { for (void* p : blocks) ctx_release(ctx, p); }
-};
+struct TreeBlocks { std::vector<DevBuf> blocks; };
 }
 struct stark_tree {
     CtxRef ref_;
     stark_ctx* ctx = nullptr; stark_params* p = nullptr;
     size_t arity = 0; uint64_t label = 0;
-    std::vector<stark::fr_t*> levels; std::vector<size_t> lens; std::vector<char> owned;
-    std::shared_ptr<stark::TreeBlocks> shared;          // a tree of a batched build: its levels are slices of these blocks (owned[i] = 0)
-    ~stark_tree() { for (size_t i = 0; i < levels.size(); ++i) if (owned[i] && levels[i]) stark::ctx_release(ctx, levels[i]); }
+    std::vector<stark::fr_t*> levels; std::vector<size_t> lens;   // the raw views MerkleTreeView and the kernels read
+    std::vector<stark::DevBuf> blocks;                             // the blocks this tree owns (a tree of its own: one per level)
+    std::shared_ptr<stark::TreeBlocks> shared;                     // a tree of a batched build: its levels are slices of these blocks
+    stark_tree(stark_ctx* c, stark_params* p_, size_t arity_, uint64_t label_) : ctx(c), p(p_), arity(arity_), label(label_) { ref_.bind(c); }
 };
 struct stark_proof { std::vector<uint8_t> bytes; size_t size_estimate = 0; double ms[3] = {0, 0, 0}; };   // a finished proof (capi_fri.hip, capi_sumcheck.hip): bytes, size estimate, stage times
+// the single success point of a call that returns proofs: the caller owns out[0 .. v.size()) from here on
+inline void hand_out(std::vector<std::unique_ptr<stark_proof>>& v, stark_proof** out) { for (size_t i = 0; i < v.size(); ++i) out[i] = v[i].release(); }
 
 #define STARK_HIP(ctx, call)                                                                                     \
     do {                                                                                                         \
@@ -162,20 +178,6 @@ inline fr_t* as_fr(uint64_t* p) { return reinterpret_cast<fr_t*>(p); }
 inline fr_t load_fr(const uint64_t* p) { fr_t x; for (int i = 0; i < 4; ++i) { x.v[2 * i] = (uint32_t)p[i]; x.v[2 * i + 1] = (uint32_t)(p[i] >> 32); } return x; }
 inline void store_fr(uint64_t* p, const fr_t& x) { for (int i = 0; i < 4; ++i) p[i] = (uint64_t)x.v[2 * i] | ((uint64_t)x.v[2 * i + 1] << 32); }
 
-// RAII device buffer used inside entry points (returned to the context's pool on every return path).
-struct DevBuf {
-    stark_ctx* ctx = nullptr; void* p = nullptr;
-    DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) ctx_release(ctx, p); }
-    hipError_t alloc(stark_ctx* c, size_t bytes) { ctx = c; return ctx_alloc(c, bytes, &p) == STARK_OK ? hipSuccess : hipErrorOutOfMemory; }
-    // alloc, then the upload of `bytes` from host memory enqueued on the context's stream (`src` stays valid until the next synchronisation)
-    hipError_t upload(stark_ctx* c, const void* src, size_t bytes) { const hipError_t e = alloc(c, bytes); return e != hipSuccess || !bytes ? e : hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, c->stream); }
-    // the first `bytes` to host memory, then one synchronisation of the context's stream
-    hipError_t download_sync(void* dst, size_t bytes) const { const hipError_t e = bytes ? hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream); }
-    fr_t* fr() const { return reinterpret_cast<fr_t*>(p); }
-    void* release() { void* q = p; p = nullptr; return q; }
-};
-
 // THE row gather on the device (capi_poseidon.hip; the list: merkle_batch.hpp): the four tables go up as ONE packed ctx_upload_staged block (the list
 // may die on return), then ONE k_gather_rows launch into out_dev (nullptr: a pooled table of G.size() rows).  out_host (optional, host memory of any
 // alignment): the first G.size() rows of the table are downloaded and the context's stream synchronised.  Index bounds are the caller's to check.
@@ -185,6 +187,7 @@ int32_t gather_rows(stark_ctx* ctx, const MerkleGatherList& G, fr_t* out_dev, vo
 // shared internal entry points (defined in capi_core.hip / capi_ntt.hip / capi_comm.hip; the Poseidon ones: poseidon_launch.hpp)
 int32_t ctx_transcript_params(stark_ctx* ctx, stark_params** out);
 int32_t ctx_merkle_params(stark_ctx* ctx, int t, stark_params** out);
+int32_t ctx_commit_params(stark_ctx* ctx, stark_params** out);      // MerkleCommitment's set (the sum-check openings)
 int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out);
 // `bytes` of host memory to device memory on the context's stream, out of a copy the context owns (stark_ctx::staged): the caller's source may die
 // on return and the host is not synchronised
@@ -192,9 +195,19 @@ int32_t ctx_upload_staged(stark_ctx* ctx, void* dst, const void* src, size_t byt
 int32_t ctx_side_stream(stark_ctx* ctx, hipStream_t* out);
 // Fork: what is enqueued on *side from here on runs after everything enqueued on the context's stream so far, and concurrently with what that stream
 // receives next.  Join: the context's stream continues after everything enqueued on the side stream.  Events only; the host is not synchronised.
-// After a failure the caller drains whichever streams it has enqueued on before it releases what they use.
 int32_t ctx_fork(stark_ctx* ctx, hipStream_t* side);
 int32_t ctx_join(stark_ctx* ctx);
+// THE fork guard: whoever forks holds one, declared AFTER the owners of what the two streams use.  A scope left while still forked (an error
+// between fork() and join(), or a failed join) drains the side stream and then the context's stream before those owners release anything;
+// a joined guard does nothing, so no success path synchronises.
+struct StreamFork {
+    stark_ctx* ctx; hipStream_t side = nullptr; bool forked = false;
+    explicit StreamFork(stark_ctx* c) : ctx(c) {}
+    StreamFork(const StreamFork&) = delete; StreamFork& operator=(const StreamFork&) = delete;
+    ~StreamFork() { if (forked) { (void)hipStreamSynchronize(side); (void)hipStreamSynchronize(ctx->stream); } }
+    int32_t fork() { STARK_TRY(ctx_fork(ctx, &side)); forked = true; return STARK_OK; }
+    int32_t join() { if (forked) { STARK_TRY(ctx_join(ctx)); forked = false; } return STARK_OK; }
+};
 int32_t ctx_enter(stark_ctx* ctx);                                   // makes the context's device current (every entry point)
 void comm_destroy(stark_ctx* ctx);
 void ntt_set_attrs();                                                // per-device kernel attributes of the NTT kernels (capi_ntt.hip)

@@ -52,18 +52,13 @@ static bool fri_shard_plan(size_t n0, const size_t* sched, size_t L, int W, FriS
 // ---- per-rank state -----------------------------------------------------------------------------------------------------------------------
 struct FriShardRank {
     stark_ctx* ctx = nullptr; int rank = 0;
-    std::vector<fr_t*> f;                     // layer l: this rank's block (sharded) or the whole layer (replicated); pooled
-    std::vector<stark_tree*> tree, top;       // sharded: the levels below the crossing level / the top built from the all-gathered level; replicated: the tree / null
+    std::vector<DevBuf> f;                    // layer l: this rank's block (sharded) or the whole layer (replicated); pooled
+    std::vector<std::unique_ptr<stark_tree>> tree, top;   // sharded: the levels below the crossing level / the top built from the all-gathered level; replicated: the tree / null
     DevBuf zp, coll;                          // fold z-powers; the buffer of the collective in flight (in place: this rank's chunk sits at rank * chunk)
     std::vector<fr_t> roots;                  // L+1 roots, identical on every rank
     std::vector<fr_t> table;                  // query phase: the all-reduced value table, downloaded
-    FriShardRank() = default; FriShardRank(const FriShardRank&) = delete; FriShardRank& operator=(const FriShardRank&) = delete;
-    ~FriShardRank() { for (auto p : f) if (p) ctx_release(ctx, p); for (auto t : tree) if (t) stark_merkle_free(t); for (auto t : top) if (t) stark_merkle_free(t); }
 };
-static int32_t coll_alloc(stark_ctx* ctx, FriShardRank& K, size_t bytes) {
-    if (K.coll.p) ctx_release(ctx, K.coll.release());
-    STARK_HIP(ctx, K.coll.alloc(ctx, bytes)); return STARK_OK;
-}
+static int32_t coll_alloc(stark_ctx* ctx, FriShardRank& K, size_t bytes) { STARK_HIP(ctx, K.coll.alloc(ctx, bytes)); return STARK_OK; }   // alloc releases the previous buffer first
 
 // ---- collective 0 of every entry point: all ranks hold the same arguments ------------------------------------------------------------------
 static constexpr size_t SHARD_HDR_WORDS = 72;         // magic, n0, L, r, seed_z, f0 given, schedule[0..64) (a dividing schedule has L <= 63), pad
@@ -86,7 +81,7 @@ static int32_t shard_header_agree(const ShardColl& C, std::vector<FriShardRank>&
         STARK_HIP(ctx, hipMemcpyAsync(all.data(), k.coll.p, (size_t)C.W * bytes, hipMemcpyDeviceToHost, ctx->stream));
         STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (size_t q = 0; q < (size_t)C.W; ++q) if (memcmp(all.data() + q * SHARD_HDR_WORDS, h.data(), bytes) != 0) same = false;
-        ctx_release(ctx, k.coll.release());
+        k.coll.reset();
     }
     if (!same) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: the ranks disagree on (n0, L, schedule, r, seed_z, f0)");
     return STARK_OK;
@@ -125,7 +120,7 @@ static int32_t shard_build_f0(const ShardColl& C, std::vector<FriShardRank>& K, 
     }
     // collective 5: every row is non-zero on exactly one rank, so the SUM is the selection
     STARK_TRY(C.all_reduce(buf, 16));
-    for (auto& w : whole) if (w.p) ctx_release(ctx, w.release());
+    for (auto& w : whole) w.reset();
     // phase: (seed, z, beta) from the four digests, then the block-local merge at global positions
     const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));                                             // FriDomain::new_radix2(n0).omega, fri.rs:53-56
     for (size_t i = 0; i < K.size(); ++i) {
@@ -146,32 +141,32 @@ static int32_t shard_commit_phase(stark_ctx* ctx, const FriShardPlan& P, FriShar
                                   const std::vector<stark_params*>& mps, size_t& top_words) {
     const size_t L = P.L, W = P.W, q = K.rank; hipStream_t st = ctx->stream;
     if (phase == 0) {
-        K.ctx = ctx; K.f.assign(L + 1, nullptr); K.tree.assign(L + 1, nullptr); K.top.assign(L + 1, nullptr);
-        for (size_t l = 0; l <= L; ++l) { void* p = nullptr; STARK_TRY(ctx_alloc(ctx, P.here(l) * sizeof(fr_t), &p)); K.f[l] = (fr_t*)p; }
+        K.ctx = ctx; K.f.clear(); K.f.resize(L + 1); K.tree.clear(); K.tree.resize(L + 1); K.top.clear(); K.top.resize(L + 1);
+        for (size_t l = 0; l <= L; ++l) STARK_TRY(K.f[l].take(ctx, P.here(l) * sizeof(fr_t)));
         if (L) STARK_HIP(ctx, K.zp.alloc(ctx, P.zoff(L) * sizeof(fr_t)));
         const size_t nl0 = P.n0 / W;
-        STARK_HIP(ctx, hipMemcpyAsync(P.T == 0 ? K.f[0] + q * nl0 : K.f[0], f0_local, nl0 * sizeof(fr_t), hipMemcpyDeviceToDevice, st));
+        STARK_HIP(ctx, hipMemcpyAsync(P.T == 0 ? K.f[0].fr() + q * nl0 : K.f[0].fr(), f0_local, nl0 * sizeof(fr_t), hipMemcpyDeviceToDevice, st));
         for (size_t l = 0; l < std::min(P.T, L); ++l) {          // sharded -> sharded, or the last sharded layer into its chunk of the whole layer T
             STARK_TRY(zpows_launch(ctx, st, z[l], P.sched[l], K.zp.fr() + P.zoff(l)));
-            fr_t* dst = P.sharded[l + 1] ? K.f[l + 1] : K.f[l + 1] + q * (P.n[l + 1] / W);
-            STARK_TRY(fold_launch(ctx, st, K.f[l], P.here(l), K.zp.fr() + P.zoff(l), P.sched[l], dst));
+            fr_t* dst = P.sharded[l + 1] ? K.f[l + 1].fr() : K.f[l + 1].fr() + q * (P.n[l + 1] / W);
+            STARK_TRY(fold_launch(ctx, st, K.f[l].fr(), P.here(l), K.zp.fr() + P.zoff(l), P.sched[l], dst));
         }
         return STARK_OK;
     }
     if (phase == 1) {
         for (size_t l = P.T; l < L; ++l) {                        // replicated folds (whole layers, the same on every rank)
             STARK_TRY(zpows_launch(ctx, st, z[l], P.sched[l], K.zp.fr() + P.zoff(l)));
-            STARK_TRY(fold_launch(ctx, st, K.f[l], P.n[l], K.zp.fr() + P.zoff(l), P.sched[l], K.f[l + 1]));
+            STARK_TRY(fold_launch(ctx, st, K.f[l].fr(), P.n[l], K.zp.fr() + P.zoff(l), P.sched[l], K.f[l + 1].fr()));
         }
         top_words = 0; for (size_t l = 0; l <= L; ++l) if (P.sharded[l]) top_words += P.stop[l];
         if (top_words) STARK_TRY(coll_alloc(ctx, K, W * top_words * sizeof(fr_t)));
         size_t toff = 0;
         for (size_t l = 0; l <= L; ++l) {                         // a sharded layer: its lower tree at global DS positions; a replicated one: the whole tree
             const bool sh = P.sharded[l]; const size_t nl = P.here(l), m = P.m(l);
-            const fr_t* f_next = l == L ? nullptr : !sh || P.sharded[l + 1] ? K.f[l + 1] : K.f[l + 1] + q * (nl / m);    // this block's parents, fri.rs:283
-            STARK_TRY(commit_layer_on(ctx, st, mps[l], P.arity[l], l, K.f[l], f_next, nl, m, sh ? q * nl : 0, sh ? P.stop[l] : 0, &K.tree[l]));
+            const fr_t* f_next = l == L ? nullptr : !sh || P.sharded[l + 1] ? K.f[l + 1].fr() : K.f[l + 1].fr() + q * (nl / m);    // this block's parents, fri.rs:283
+            STARK_TRY(commit_layer_on(ctx, st, mps[l], P.arity[l], l, K.f[l].fr(), f_next, nl, m, sh ? q * nl : 0, sh ? P.stop[l] : 0, K.tree[l]));
             if (!sh) continue;
-            const stark_tree* T = K.tree[l];
+            const stark_tree* T = K.tree[l].get();
             if (T->lens.back() != P.stop[l]) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: lower tree stopped at an unplanned level");
             STARK_HIP(ctx, hipMemcpyAsync(K.coll.fr() + q * top_words + toff, T->levels.back(), P.stop[l] * sizeof(fr_t), hipMemcpyDeviceToDevice, st));
             toff += P.stop[l];
@@ -184,20 +179,18 @@ static int32_t shard_commit_phase(stark_ctx* ctx, const FriShardPlan& P, FriShar
     for (size_t l = 0; l <= L; ++l) {
         if (P.sharded[l]) {
             const size_t s = P.stop[l], nin = W * s;
-            void* in = nullptr; STARK_TRY(ctx_alloc(ctx, nin * sizeof(fr_t), &in));
-            if (hipMemcpy2DAsync(in, s * sizeof(fr_t), K.coll.fr() + toff, top_words * sizeof(fr_t), s * sizeof(fr_t), W, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                ctx_release(ctx, in); return ctx->fail(STARK_ERR_HIP, "sharded FRI: unpack the crossing level"); }
-            stark_tree* T = nullptr;
+            DevBuf in; STARK_TRY(in.take(ctx, nin * sizeof(fr_t)));
+            if (hipMemcpy2DAsync(in.p, s * sizeof(fr_t), K.coll.fr() + toff, top_words * sizeof(fr_t), s * sizeof(fr_t), W, hipMemcpyDeviceToDevice, st) != hipSuccess)
+                return ctx->fail(STARK_ERR_HIP, "sharded FRI: unpack the crossing level");
             const uint32_t lv0 = (uint32_t)(K.tree[l]->levels.size() - 1);
-            int32_t rc = merkle_build_on(ctx, st, mps[l], P.arity[l], (uint64_t)l, (const fr_t*)in, nin, 0, nullptr, 1, 0, lv0, 1, true, &T);
-            if (rc) { if (!T) ctx_release(ctx, in); return rc; }
-            K.top[l] = T; toff += s;
+            STARK_TRY(merkle_build_on(ctx, st, mps[l], P.arity[l], (uint64_t)l, nullptr, nin, 0, nullptr, 1, 0, lv0, 1, std::move(in), K.top[l]));
+            toff += s;
         }
-        stark_tree* T = P.sharded[l] ? K.top[l] : K.tree[l];
+        const stark_tree* T = (P.sharded[l] ? K.top[l] : K.tree[l]).get();
         if (T->lens.back() != 1) return ctx->fail(STARK_ERR_INVALID_ARG, "sharded FRI: a tree without a root");
         STARK_HIP(ctx, hipMemcpyAsync(&K.roots[l], T->levels.back(), sizeof(fr_t), hipMemcpyDeviceToHost, st));
     }
-    if (K.coll.p) ctx_release(ctx, K.coll.release());
+    K.coll.reset();
     return STARK_OK;
 }
 static int32_t shard_commit(const ShardColl& C, const FriShardPlan& P, std::vector<FriShardRank>& K, const std::vector<const fr_t*>& f0_local, uint64_t seed_z) {
@@ -206,7 +199,7 @@ static int32_t shard_commit(const ShardColl& C, const FriShardPlan& P, std::vect
     size_t top_words = 0;
     for (size_t i = 0; i < K.size(); ++i) STARK_TRY(shard_commit_phase(ctx, P, K[i], 0, f0_local[i], z, mps, top_words));
     if (P.T <= L) {                                                                        // collective 6: the first replicated layer
-        std::vector<void*> buf; for (auto& k : K) buf.push_back(k.f[P.T]);
+        std::vector<void*> buf; for (auto& k : K) buf.push_back(k.f[P.T].p);
         STARK_TRY(C.all_gather(buf, P.n[P.T] / P.W * sizeof(fr_t)));
     }
     for (size_t i = 0; i < K.size(); ++i) STARK_TRY(shard_commit_phase(ctx, P, K[i], 1, f0_local[i], z, mps, top_words));
@@ -232,14 +225,14 @@ static int32_t shard_query_fill(stark_ctx* ctx, const FriShardPlan& P, FriShardR
         if (r.which > P.L) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: layer out of range");
         const size_t l = r.which;
         if (r.kind == 0) {
-            o = {K.f[l], P.here(l), 0, r.index};
+            o = {K.f[l].fr(), P.here(l), 0, r.index};
             if (P.sharded[l]) { const uint64_t nl = P.n[l] / P.W; o.owner = r.index / nl; o.index = r.index % nl; }
             return STARK_OK;
         }
-        const stark_tree* T = K.tree[l]; const uint32_t nlev = (uint32_t)T->levels.size();
+        const stark_tree* T = K.tree[l].get(); const uint32_t nlev = (uint32_t)T->levels.size();
         if (P.sharded[l] && r.level + 1 < nlev) { const uint64_t ln = T->lens[r.level]; o = {T->levels[r.level], T->lens[r.level], r.index / ln, r.index % ln}; }
         else if (P.sharded[l]) {
-            const stark_tree* U = K.top[l]; const uint32_t v = r.level - (nlev - 1);
+            const stark_tree* U = K.top[l].get(); const uint32_t v = r.level - (nlev - 1);
             if (v >= U->levels.size()) return ctx->fail(STARK_ERR_INVALID_ARG, "query phase: tree level out of range");
             o = {U->levels[v], U->lens[v], 0, r.index};
         } else {
@@ -255,7 +248,7 @@ static int32_t shard_query_fill(stark_ctx* ctx, const FriShardPlan& P, FriShardR
     }
     return gather_rows(ctx, G, K.coll.fr(), nullptr);
 }
-static int32_t shard_queries(const ShardColl& C, const FriShardPlan& P, std::vector<FriShardRank>& K, size_t r, std::vector<stark_proof*>& out) {
+static int32_t shard_queries(const ShardColl& C, const FriShardPlan& P, std::vector<FriShardRank>& K, size_t r, std::vector<std::unique_ptr<stark_proof>>& out) {
     stark_ctx* ctx = C.ctx;
     DeviceHasher H0(ctx); MemoHasher H(H0);
     FriPlan plan; STARK_TRY(make_query_plan(ctx, plan, P.n0, P.sched.data(), P.L, K[0].roots.data(), r, H));
@@ -272,11 +265,9 @@ static int32_t shard_queries(const ShardColl& C, const FriShardPlan& P, std::vec
     }
     STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (auto& k : K) {
-        ctx_release(ctx, k.coll.release());
-        std::unique_ptr<stark_proof> Pf(new stark_proof());
-        const int32_t rc = assemble_from_values(ctx, plan.shape, r, H, k.table.data(), nreq, Pf.get());
-        if (rc) { for (auto* x : out) delete x; out.clear(); return rc; }
-        out.push_back(Pf.release());
+        k.coll.reset();
+        out.emplace_back(new stark_proof());
+        STARK_TRY(assemble_from_values(ctx, plan.shape, r, H, k.table.data(), nreq, out.back().get()));
     }
     return STARK_OK;
 }
@@ -330,10 +321,10 @@ static int32_t shard_prove(const ShardColl& C, const fr_t* a, const fr_t* s, con
     const auto t1 = Clock::now();
     STARK_TRY(shard_commit(C, P, K, f0, seed_z));
     const auto t2 = Clock::now();
-    std::vector<stark_proof*> pf; STARK_TRY(shard_queries(C, P, K, r, pf));
+    std::vector<std::unique_ptr<stark_proof>> pf; STARK_TRY(shard_queries(C, P, K, r, pf));
     const auto t3 = Clock::now();
-    for (size_t i = 0; i < pf.size(); ++i) { pf[i]->ms[0] = ms_between(t0, t1); pf[i]->ms[1] = ms_between(t1, t2); pf[i]->ms[2] = ms_between(t2, t3); out[i] = pf[i]; }
-    return STARK_OK;
+    for (auto& p : pf) { p->ms[0] = ms_between(t0, t1); p->ms[1] = ms_between(t1, t2); p->ms[2] = ms_between(t2, t3); }
+    hand_out(pf, out); return STARK_OK;
 }
 
 struct stark_fri_shard {
@@ -355,10 +346,9 @@ int32_t stark_fri_shard_layout(size_t n0, const size_t* schedule, size_t L, int3
 int32_t stark_fri_build_sharded_dev(stark_ctx_t* ctx, const uint64_t* f0_block, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_shard_t** out) {
     if (!ctx || !f0_block || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    stark_fri_shard* S = new stark_fri_shard(ctx, seed_z);
-    int32_t rc = shard_build(S->C, as_fr(f0_block), n0, schedule, L, seed_z, S->P, S->K);
-    if (rc) { delete S; return rc; }
-    *out = S; return STARK_OK;
+    std::unique_ptr<stark_fri_shard> S(new stark_fri_shard(ctx, seed_z));
+    STARK_TRY(shard_build(S->C, as_fr(f0_block), n0, schedule, L, seed_z, S->P, S->K));
+    *out = S.release(); return STARK_OK;
 }
 int32_t stark_fri_shard_num_layers(stark_fri_shard_t* h) { return h ? (int32_t)(h->P.L + 1) : STARK_ERR_INVALID_ARG; }
 int32_t stark_fri_shard_root(stark_fri_shard_t* h, int32_t l, uint64_t* out4) {
@@ -372,8 +362,8 @@ int32_t stark_fri_shard_prove_queries(stark_fri_shard_t* h, size_t r, stark_proo
     stark_ctx* ctx = h->C.ctx; STARK_TRY(ctx_enter(ctx));
     if (!r) return ctx->fail(STARK_ERR_INVALID_ARG, "r >= 1");
     STARK_TRY(shard_header_agree(h->C, h->K, h->P, r, h->seed_z, 1));
-    std::vector<stark_proof*> pf; STARK_TRY(shard_queries(h->C, h->P, h->K, r, pf));
-    *out = pf[0]; return STARK_OK;
+    std::vector<std::unique_ptr<stark_proof>> pf; STARK_TRY(shard_queries(h->C, h->P, h->K, r, pf));
+    *out = pf[0].release(); return STARK_OK;
 }
 int32_t stark_deep_fri_prove_sharded_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, const uint64_t* f0_opt, size_t n0,
                                          const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out) {

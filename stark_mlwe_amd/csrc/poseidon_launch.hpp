@@ -18,8 +18,9 @@ int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatc
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out);
 int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h);
+// level0_block: a pooled block holding the leaves, moved into the tree as level 0; an empty one: level 0 is a copy of `leaves` (capi_poseidon.hip)
 int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t arity, uint64_t label, const fr_t* leaves, size_t n, int pairs, const fr_t* cp, size_t cp_div,
-                        uint64_t first_pos, uint32_t level0, size_t stop_at_len, bool adopt, stark_tree** out);
+                        uint64_t first_pos, uint32_t level0, size_t stop_at_len, DevBuf&& level0_block, std::unique_ptr<stark_tree>& out);
 // MerkleTree::new / new_pairs of `batch` trees of one shape on the context's stream (merkle_batch.hpp): leaves / cp are HOST arrays of DEVICE pointers
 // (cp: nullptr iff !pairs; a null entry = zeros).  Stream-ordered, no host synchronisation.  out: `batch` handles, all null on any error.
 int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, size_t batch, const uint64_t* labels, const uint64_t* const* leaves, size_t n, int pairs,

@@ -9,6 +9,7 @@ namespace stark {
 struct VerifyBatchPlan;
 // The leaf step and the DS groups of a batch plan whose arrays are on the device; fixed != nullptr: every group hashes with that parameter set (the
 // sum-check openings: MerkleCommitment's, a t = 17 set that is NOT poseidon_params_for_arity(16)) instead of ctx_merkle_params(width of the group).
+// On an error the side stream is drained if a depth was forked (StreamFork); the context's stream is the CALLER's to drain before it frees what the launches read.
 int32_t verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, const uint64_t* hdr, const uint32_t* off, const uint32_t* idx, fr_t* pool, stark_params* fixed);
 // Runs one plan whole: one upload, verify_batch_groups_on, the check kernel, one download of accepted[0 .. V.batch) and one synchronisation.
 int32_t run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, stark_params* fixed, int32_t* accepted);
