@@ -230,8 +230,9 @@ struct KernelConsts {
     //   blk8_efrag [rp/8][8][16]  fragment (mfma_frag_of) of u_{q,j}, UNSCALED: its inputs are lanes in stored form
     //   blk8_lfrag [rp/8][16][8]  fragment of w_{p,j} * 2^20 (its inputs are fr_pow5_r29 outputs, as in the full rounds), lane-major: row j = 1..16, then p;
     //                             after the last block ONE fragment of the constant 1: the K-step that adds the lane's own stored value
-    //   gamma8_29  [rp/8][28][9]  Gamma_{q,p} at q (q - 1) / 2 + p, scaled like gamma29
-    std::vector<int8_t> blk8_efrag, blk8_lfrag;
+    //   blk8_gfrag [rp/8][28]     fragment of Gamma_{q,p} * 2^20 at q (q - 1) / 2 + p: the y_p enter row q's tile as q further K-steps (H_q = E_q + sum Gamma y_p)
+    //   gamma8_29  [rp/8][28][9]  the same Gamma_{q,p} scaled like gamma29: host checks and tools only, not uploaded
+    std::vector<int8_t> blk8_efrag, blk8_lfrag, blk8_gfrag;
     std::vector<uint32_t> gamma8_29;
     bool ok = false;
 };
@@ -358,6 +359,7 @@ inline KernelConsts make_kernel_consts(const PoseidonConsts& c) {
                 fr_t acc = h_zero();
                 for (int j = 0; j < n; ++j) acc = h_add(acc, h_mul(um[(size_t)q * n + j], wm[(size_t)j * 8 + p2]));
                 g8[(size_t)b * 28 + q * (q - 1) / 2 + p2] = acc;
+                k.blk8_gfrag.resize(k.blk8_gfrag.size() + 1024); mfma_frag_of(h_mul(acc, s20), &k.blk8_gfrag[k.blk8_gfrag.size() - 1024]);
             }
         }
         k.blk8_lfrag.resize(k.blk8_lfrag.size() + 1024); mfma_frag_of(h_one(), &k.blk8_lfrag[k.blk8_lfrag.size() - 1024]);

@@ -6,6 +6,7 @@
 // the oracle without a GPU.  No product entry point loads or calls this library; it is not a
 // fallback: libstark_mlwe_hip.so fails with STARK_ERR_HIP when no device is present.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <vector>
 #include "fr.hpp"
@@ -40,7 +41,7 @@ static void bind(HcParams* P) {
     P->dev.t = P->kc.t; P->dev.rf = P->kc.rf; P->dev.rp = P->kc.rp; P->dev.rc_full = P->kc.rc_full.data(); P->dev.rc_partial = P->kc.rc_partial.data();
     P->dev.lu = P->kc.lu.data(); P->dev.lu_pre = P->kc.lu_pre.data(); P->dev.row0 = P->kc.row0.data(); P->dev.sparse = P->kc.sparse.data(); P->dev.mds = P->kc.mds.data(); P->dev.mds_pre = P->kc.mds_pre.data(); P->dev.gamma = P->kc.gamma.data();
     P->dev.lu29 = P->kc.lu29.data(); P->dev.lu_pre29 = P->kc.lu_pre29.data(); P->dev.row0_29 = P->kc.row0_29.data(); P->dev.sparse29 = P->kc.sparse29.data(); P->dev.gamma29 = P->kc.gamma29.data(); P->dev.mds29 = P->kc.mds29.data(); P->dev.mds_pre29 = P->kc.mds_pre29.data();
-    P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr; P->dev.blk8_efrag = nullptr; P->dev.blk8_lfrag = nullptr; P->dev.blk8_unit_frag = nullptr; P->dev.gamma8_29 = nullptr;
+    P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr; P->dev.blk8_efrag = nullptr; P->dev.blk8_lfrag = nullptr; P->dev.blk8_unit_frag = nullptr; P->dev.blk8_gfrag = nullptr;
     P->dev.chain_a = P->kc.chain_a.empty() ? nullptr : P->kc.chain_a.data(); P->dev.chain_g = P->kc.chain_g.empty() ? nullptr : P->kc.chain_g.data(); P->dev.chain_w = P->kc.chain_w.empty() ? nullptr : P->kc.chain_w.data();
 }
 
@@ -247,12 +248,16 @@ static fr_t blk8_finish_sums(const int32_t* S) {      // the accumulator rows as
     return mfma_finish_cols(col);
 }
 static int blk8_tile(const int8_t* const* frag, const fr_t* xd, int K, fr_t& out) { int32_t S[32]; const int rc = blk8_tile_sums(frag, xd, K, S); if (rc) return rc; out = blk8_finish_sums(S); return 0; }
+// the largest |digit sum| hc_permute_block8 has seen in a row of 16 + 7 K-steps (the longest tile of the block form) since the last reset
+static std::atomic<int32_t> g_blk8_row23_max{0};
+int32_t hc_blk8_row23_max(int reset) { return reset ? g_blk8_row23_max.exchange(0) : g_blk8_row23_max.load(); }
 // A whole t = 17 permutation in the wave-pair kernels' block-8 form: full rounds through the residue tables of M and B_1 M, the partial rounds in
-// blocks of 8 — lanes recoded, E rows (8 x 16 tile rows), y_q = fr_pow5_r29, a_q y_q + sum Gamma y_p from sparse29 / gamma8_29, lane rows with the
-// unit fragment as the ninth K-step — with blk8_efrag / blk8_lfrag / gamma8_29 as uploaded.  -1: the set has no block-8 tables; -2: a digit sum out of range.
+// blocks of 8 — lanes recoded, row q = H_q = E_q + sum Gamma y_p as ONE tile of 16 + q K-steps (E fragments against the lanes, blk8_gfrag against the
+// recoded y_0..y_{q-1}), y_q = fr_pow5_r29, a_q y_q from sparse29, lane rows with the unit fragment as the ninth K-step — with blk8_efrag / blk8_gfrag /
+// blk8_lfrag as uploaded.  -1: the set has no block-8 tables; -2: a digit sum out of range.
 int hc_permute_block8(void* h, uint64_t* states, size_t n) {
     HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc; const int t = k.t, half = k.rf / 2, W = 2 * t - 1;
-    if (t != 17 || k.blk8_efrag.empty() || k.mds_frag.empty()) return -1;
+    if (t != 17 || k.blk8_efrag.empty() || k.blk8_gfrag.empty() || k.mds_frag.empty()) return -1;
     const int8_t* unit = k.blk8_lfrag.data() + k.blk8_lfrag.size() - 1024;
     std::vector<fr_t> st(t), xd(t), o(t);
     auto full = [&](int r, const std::vector<int8_t>& F) -> int {
@@ -262,21 +267,26 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
     for (size_t s = 0; s < n; ++s) {
         for (int j = 0; j < t; ++j) st[j] = ld4(states + 4 * (s * t + j));
         for (int r = 0; r < half; ++r) { const int rc = full(r, r == half - 1 ? k.mds_pre_frag : k.mds_frag); if (rc) return rc; }
-        fr_t s0 = st[0], rec[17], y[8], yd[9];
+        fr_t s0 = st[0], rec[17], y[8], yd[9], kx[23];
         for (int j = 1; j < t; ++j) rec[j] = recode_signed(st[j]);
         const int nb = k.rp / 8;
         for (int b = 0; b < nb; ++b) {
             const int8_t* ef = k.blk8_efrag.data() + (size_t)b * 8 * 16 * 1024; const int8_t* lf = k.blk8_lfrag.data() + (size_t)b * 16 * 8 * 1024;
+            const int8_t* gf = k.blk8_gfrag.data() + (size_t)b * 28 * 1024;
+            for (int j = 0; j < 16; ++j) kx[j] = rec[1 + j];
             for (int q = 0; q < 8; ++q) {
-                const int8_t* fr[16]; for (int j = 0; j < 16; ++j) fr[j] = ef + ((size_t)q * 16 + j) * 1024;
-                fr_t E; { const int rc = blk8_tile(fr, rec + 1, 16, E); if (rc) return rc; }
+                const int8_t* fr[23]; for (int j = 0; j < 16; ++j) fr[j] = ef + ((size_t)q * 16 + j) * 1024;
+                for (int p2 = 0; p2 < q; ++p2) { fr[16 + p2] = gf + ((size_t)q * (q - 1) / 2 + p2) * 1024; kx[16 + p2] = yd[p2]; }
+                int32_t S[32]; { const int rc = blk8_tile_sums(fr, kx, 16 + q, S); if (rc) return rc; }
+                if (q == 7) { int32_t m = 0; for (int c = 0; c < 32; ++c) m = std::max(m, S[c] < 0 ? -S[c] : S[c]);
+                              int32_t seen = g_blk8_row23_max.load(); while (m > seen && !g_blk8_row23_max.compare_exchange_weak(seen, m)) {} }
+                const fr_t H = blk8_finish_sums(S);
                 y[q] = fr_pow5_r29<PF>(fr_add<PF>(s0, k.rc_partial[8 * b + q]));
+                yd[q] = recode_signed(y[q]);
                 DotAcc acc; acc.init();
                 acc.mac(c29(k.sparse29.data(), (size_t)(8 * b + q) * W), y[q]);
-                for (int p2 = 0; p2 < q; ++p2) acc.mac(c29(k.gamma8_29.data(), (size_t)b * 28 + q * (q - 1) / 2 + p2), y[p2]);
-                s0 = fr_add<PF>(E, acc.finish());
+                s0 = fr_add<PF>(H, acc.finish());
             }
-            for (int p2 = 0; p2 < 8; ++p2) yd[p2] = recode_signed(y[p2]);
             for (int j = 1; j < t; ++j) {
                 const int8_t* fr[9]; for (int p2 = 0; p2 < 8; ++p2) fr[p2] = lf + ((size_t)(j - 1) * 8 + p2) * 1024; fr[8] = unit;
                 yd[8] = rec[j];
@@ -290,12 +300,12 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
     }
     return 0;
 }
-// the block-8 tables of a set: which = 0 blk8_efrag, 1 blk8_lfrag (its last 1 KiB: the unit fragment), 2 gamma8_29 (bytes of the uint32 words);
+// the block-8 tables of a set: which = 0 blk8_efrag, 1 blk8_lfrag (its last 1 KiB: the unit fragment), 2 gamma8_29 (bytes of the uint32 words), 3 blk8_gfrag;
 // copies at most cap bytes out, returns the table's length in bytes (0: the set has none)
 size_t hc_blk8_table(void* h, int which, void* out, size_t cap) {
     HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc;
-    const void* src = which == 0 ? (const void*)k.blk8_efrag.data() : which == 1 ? (const void*)k.blk8_lfrag.data() : (const void*)k.gamma8_29.data();
-    const size_t len = which == 0 ? k.blk8_efrag.size() : which == 1 ? k.blk8_lfrag.size() : k.gamma8_29.size() * 4;
+    const void* src = which == 0 ? (const void*)k.blk8_efrag.data() : which == 1 ? (const void*)k.blk8_lfrag.data() : which == 3 ? (const void*)k.blk8_gfrag.data() : (const void*)k.gamma8_29.data();
+    const size_t len = which == 0 ? k.blk8_efrag.size() : which == 1 ? k.blk8_lfrag.size() : which == 3 ? k.blk8_gfrag.size() : k.gamma8_29.size() * 4;
     if (out && len) memcpy(out, src, std::min(cap, len));
     return len;
 }

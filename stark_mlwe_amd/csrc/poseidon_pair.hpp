@@ -214,27 +214,32 @@ __device__ __forceinline__ void pair_apply_mds_mfma(const PairState& s, const vo
 //   * lane product: fragments of w_{p,j} * 2^20 (the y are fr_pow5_r29 outputs) and, as a ninth K-step, the fragment of the constant 1 against the lane's
 //     own slot, which adds the base lane inside the tile: |digit sum| <= 9 * 32 * 128 * 128 = 4 718 592 < 2^24.  mfma_finish_cols holds for any
 //     |S_c| < 2^24, so both products end canonical and the lazy-lane bound of pair_lane_update does not apply to this form.
+// The third product of the block algebra rides in the E rows' tiles: H_q = E_q + sum_{p<q} Gamma_{q,p} y_p is row q of a product with constant left
+// factors, and y_0..y_{q-1} are known when round q starts, so row q takes them as q further K-steps (fragments of Gamma_{q,p} * 2^20, blk8_gfrag) before the
+// exchange, fold and finish it pays anyway: |digit sum| <= (16 + 7) * 32 * 128 * 128 = 12 058 624 < 2^24.  No Gamma term is left on the vector ALU.
 // Schedule of a block (two barriers fewer than two blocks of 4, nothing on the chain waits for a lone row):
-//   X  runs nothing but the chain: y_q, a_q y_q (plus the gamma terms older than Y's YG per round) and X_{q+1} = that + H_q;
-//   Y  computes E_q INSIDE round q — B operands read from the lanes' slots as the MFMAs consume them (one row per round: 32 KB of LDS reads per about
-//      10 k cycles), the fragments of row q + 1 fetched while it sums the gamma terms — and posts H_q = E_q + sum Gamma_{q,p} y_p; one barrier per round;
+//   X  runs nothing but the chain, the same in every round: y_q, a_q y_q, one reduction and X_{q+1} = that + H_q;
+//   Y  computes H_q INSIDE round q — B operands read from the lanes' slots as the MFMAs consume them (one row per round: 32 KB of LDS reads per about
+//      10 k cycles), then the q steps of the y; the fragments of row q + 1 (16 of E, q + 1 of Gamma) are fetched under the fold — and posts it; one barrier per round;
 //   both then form their share of the lane product (X lanes 1..NLX, Y the rest), the next row's fragments in flight under the current row's fold.
-// The y reach the B layout without LDS: recode, then v_permlane32_swap(low half, high half).  Four slots are free during a block (slot 0: X holds
-// the chain value; the three extra ones): two rings of two, H (written by Y, read by X after the round's barrier) and y (the other way round).
-// Both waves keep y_0..y_7 in registers.  Measured stand-alone (tools/partial_block8.hip, profiles/partial_block8_prototype.jsonl): 119.7 k SIMD-cycles
-// per 8 rounds against 204.6 k for two blocks of 4.
+// X posts y_q RECODED: a recoded slot is a B operand as it stands, and both waves read it as one after the round's barrier (X its own write back), so
+// no wave converts a y and none holds one as a field element across rounds.  Four slots are free during a block (slot 0: X holds the chain value; the
+// three extra ones): two rings of two, H (written by Y, read by X after the round's barrier) and y (the other way round).
+// Measured stand-alone (tools/partial_block8.hip, profiles/partial_block8_gamma_rows_prototype.jsonl): 105.1 / 104.2 k SIMD-cycles per 8 rounds against
+// 118.4 / 116.1 k with the Gamma terms on the vector ALU and 209.3 / 206.6 k for two blocks of 4; pipelining wave Y across the round barrier (the lane
+// steps and the older Gamma steps of row q + 1 before barrier_q) measured 106.7 / 105.4 k: not adopted.
 struct Blk8Tabs {
     const mfma_v4i* efrag;     // [8][16][64]   row q, lane j = 1..16
     const mfma_v4i* lfrag;     // [16][8][64]   lane j = 1..16, S-box output p
     const mfma_v4i* unit;      // [64]          the constant 1
+    const mfma_v4i* gfrag;     // [28][64]      Gamma_{q,p} at q (q - 1) / 2 + p
     const uint32_t* a29;       // a_q at c29(a29, q * (2 T - 1)): the block's first row of sparse29
-    const uint32_t* g29;       // [28][9]       Gamma_{q,p} at q (q - 1) / 2 + p
     const fr_t* rc;            // [8]
 };
 struct Blk8Cfg {
-    // Y's share of a round's gamma terms (the YG youngest) and X's share of the lane rows: 5 / 8 measured best, the neighbours within 1.5 %
-    // (YG 6 with NLX 8: +1.5 %, YG 6 with NLX 7: +0.2 %, YG 7 with NLX 9: +1.1 %; run-to-run spread 1.5 %)
-    static constexpr int YG = 5, NLX = 8;
+    // X's share of the lane rows.  Measured, k SIMD-cycles per 8 rounds in two processes: 6 -> 107.7 / 107.0, 7 -> 105.8 / 106.1, 8 -> 105.1 / 104.2, 9 -> 106.4 / 107.0,
+    // 10 -> 111.6 / 111.8 (run-to-run spread 2-5 k)
+    static constexpr int NLX = 8;
     __host__ __device__ static constexpr int ymail(int q) { return 17 + (q & 1); }
     __host__ __device__ static constexpr int hmail(int q) { return (q & 1) ? 19 : 0; }
 };
@@ -257,33 +262,29 @@ __device__ __forceinline__ void blk8_load_frags16(mfma_v4i (&a)[16], const mfma_
 #pragma unroll
     for (int e = 0; e < 16; ++e) a[e] = (A + (size_t)e * 64)[lane];
 }
-template <int Q, int P, int LO, int HI>
-__device__ __forceinline__ void blk8_gterm(fr_wide29& acc, const Blk8Tabs& Tb, const fr_t (&yk)[8]) {          // gamma term p of round Q, if p is in [LO, HI)
-    if constexpr (P < Q && P >= LO && P < HI) fr_wide29_mac(acc, c29(Tb.g29, Q * (Q - 1) / 2 + P), fr29_unpack(yk[P]));
+// slot j (recoded) as the B operand of column tile ct: half (lane >> 5) of the element of sponge 32 ct + (lane & 31)
+__device__ __forceinline__ mfma_v4i blk8_b_of_slot(const PairState& s, int j, int ct) {
+    const uint4 u = s.st[(2 * j + (s.lane >> 5)) * 64 + 32 * ct + (s.lane & 31)];
+    return mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
 }
-template <int Q, int LO, int HI>
-__device__ __forceinline__ void blk8_gterms(fr_wide29& acc, const Blk8Tabs& Tb, const fr_t (&yk)[8]) {
-    blk8_gterm<Q, 0, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 1, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 2, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 3, LO, HI>(acc, Tb, yk);
-    blk8_gterm<Q, 4, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 5, LO, HI>(acc, Tb, yk); blk8_gterm<Q, 6, LO, HI>(acc, Tb, yk);
-}
-// round Q in wave X: at most 1 + 7 - YG terms, within fr29_max_terms
-template <int Q, int YG>
-__device__ __forceinline__ void blk8_round_x(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, fr_t (&yk)[8]) {
+// round Q in wave X.  b[Q]: y_Q as B operands on exit
+template <int Q>
+__device__ __forceinline__ void blk8_round_x(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, mfma_v4i (&b)[8][2]) {
     __builtin_amdgcn_sched_barrier(0);                     // keep the rounds apart: less register pressure
-    yk[Q] = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));
-    s.sto(Blk8Cfg::ymail(Q), yk[Q]);
+    const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));
     fr_wide29 acc; fr_wide29_zero(acc);
-    fr_wide29_mac(acc, c29(Tb.a29, (size_t)Q * (2 * 17 - 1)), fr29_unpack(yk[Q]));
-    blk8_gterms<Q, 0, (Q - YG > 0 ? Q - YG : 0)>(acc, Tb, yk);
+    fr_wide29_mac(acc, c29(Tb.a29, (size_t)Q * (2 * 17 - 1)), fr29_unpack(y));
     const fr_t part = fr_wide29_reduce<PF>(acc);
+    s.sto(Blk8Cfg::ymail(Q), recode_signed(y));            // off the chain: nothing of X_{Q+1} reads it
     __syncthreads();                                       // barrier_Q: H_Q is posted
     s0 = fr_add<PF>(part, s.ld(Blk8Cfg::hmail(Q)));
+    b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
-// round Q in wave Y.  a: the fragments of E row Q on entry, of row Q + 1 on exit
-template <int Q, int YG>
-__device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs& Tb, fr_t (&yk)[8], mfma_v4i (&a)[16]) {
+// round Q in wave Y.  a, g: the fragments of E row Q and of Gamma row Q on entry, of row Q + 1 on exit; b[Q]: y_Q as B operands on exit
+template <int Q>
+__device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs& Tb, mfma_v4i (&b)[8][2], mfma_v4i (&a)[16], mfma_v4i (&g)[7]) {
     __builtin_amdgcn_sched_barrier(0);
-    const int lane = s.lane, h = lane >> 5;
+    const int lane = s.lane;
     mfma_v16i acc[2];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
@@ -292,50 +293,27 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
 #pragma unroll
     for (int e = 0; e < 16; ++e)
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            const uint4 u = s.st[(2 * (e + 1) + h) * 64 + 32 * ct + (lane & 31)];
-            acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[e], mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w}, acc[ct], 0, 0, 0);
-        }
-    if constexpr (Q < 7) blk8_load_frags16(a, Tb.efrag + (size_t)(Q + 1) * 16 * 64, lane);
-    fr_t hq = mfma_post(acc);
-    __builtin_amdgcn_sched_barrier(0);
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[e], blk8_b_of_slot(s, e + 1, ct), acc[ct], 0, 0, 0);
     if constexpr (Q > 0) {
-        fr_wide29 w; fr_wide29_zero(w);
-        blk8_gterms<Q, (Q - YG > 0 ? Q - YG : 0), Q>(w, Tb, yk);
-        hq = fr_add<PF>(hq, fr_wide29_reduce<PF>(w));
+#pragma unroll
+        for (int p = 0; p < Q; ++p)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(g[p], b[p][ct], acc[ct], 0, 0, 0);
     }
-    s.sto(Blk8Cfg::hmail(Q), hq);
+    if constexpr (Q < 7) {
+        blk8_load_frags16(a, Tb.efrag + (size_t)(Q + 1) * 16 * 64, lane);
+#pragma unroll
+        for (int p = 0; p <= Q; ++p) g[p] = (Tb.gfrag + (size_t)((Q + 1) * Q / 2 + p) * 64)[lane];
+    }
+    s.sto(Blk8Cfg::hmail(Q), mfma_post(acc));
     __syncthreads();                                       // barrier_Q: y_Q is posted
-    yk[Q] = s.ld(Blk8Cfg::ymail(Q));
+    b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
-// One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; s0 = X_0 in wave X.  Ends with a barrier, the lanes recoded again,
-// or canonical after the permutation's last block.
-template <int YG, int NLX>
-__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last) {
-    static_assert(YG >= 1 && YG <= 7 && NLX >= 1 && NLX <= 15, "shares");
-    static_assert(YG <= fr29_max_terms<PF>() && 1 + 7 - YG <= fr29_max_terms<PF>(), "Y sums YG terms, X up to 1 + 7 - YG, without a carry pass in between");
-    const int lane = s.lane, h = lane >> 5;
-    fr_t yk[8];
-    if (!s.isY) {
-        blk8_round_x<0, YG>(s, Tb, s0, yk); blk8_round_x<1, YG>(s, Tb, s0, yk); blk8_round_x<2, YG>(s, Tb, s0, yk); blk8_round_x<3, YG>(s, Tb, s0, yk);
-        blk8_round_x<4, YG>(s, Tb, s0, yk); blk8_round_x<5, YG>(s, Tb, s0, yk); blk8_round_x<6, YG>(s, Tb, s0, yk); blk8_round_x<7, YG>(s, Tb, s0, yk);
-    } else {
-        mfma_v4i a[16];
-        blk8_load_frags16(a, Tb.efrag, lane);
-        blk8_round_y<0, YG>(s, Tb, yk, a); blk8_round_y<1, YG>(s, Tb, yk, a); blk8_round_y<2, YG>(s, Tb, yk, a); blk8_round_y<3, YG>(s, Tb, yk, a);
-        blk8_round_y<4, YG>(s, Tb, yk, a); blk8_round_y<5, YG>(s, Tb, yk, a); blk8_round_y<6, YG>(s, Tb, yk, a); blk8_round_y<7, YG>(s, Tb, yk, a);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    mfma_v4i b[8][2];
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        const fr_t yr = recode_signed(yk[p]);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {      // afterwards b[p][ct] = half (lane >> 5) of y_p of sponge 32 ct + (lane & 31)
-            const auto sw = __builtin_amdgcn_permlane32_swap(yr.v[w], yr.v[4 + w], false, false);
-            b[p][0][w] = (int)sw[0]; b[p][1][w] = (int)sw[1];
-        }
-    }
+// the lane product: s_j <- s_j + sum_p w_{p,j} y_p for this wave's share of the lanes (X lanes 1..NLX, Y the rest), b: y_0..y_7 as B operands.  Ends with a barrier.
+template <int NLX>
+__device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], bool last) {
+    static_assert(NLX >= 1 && NLX <= 15, "shares");
+    const int lane = s.lane;
     const int j0 = s.isY ? NLX + 1 : 1, j1 = s.isY ? 16 : NLX;
     const mfma_v4i aunit = Tb.unit[lane];
     mfma_v4i a[8];
@@ -353,10 +331,7 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], b[p][ct], acc[ct], 0, 0, 0);
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            const uint4 u = s.st[(2 * j + h) * 64 + 32 * ct + (lane & 31)];
-            acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aunit, mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w}, acc[ct], 0, 0, 0);
-        }
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aunit, blk8_b_of_slot(s, j, ct), acc[ct], 0, 0, 0);
         const int jn = j < j1 ? j + 1 : j1;                // the last row fetches its own fragments again: in bounds, unused
 #pragma unroll
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
@@ -364,6 +339,23 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
         s.sto(j, last ? z : recode_signed(z));             // slot j is read by this wave alone, before this write
     }
     __syncthreads();
+}
+// One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; s0 = X_0 in wave X.  Ends with a barrier, the lanes recoded again,
+// or canonical after the permutation's last block.
+template <int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last) {
+    mfma_v4i b[8][2];
+    if (!s.isY) {
+        blk8_round_x<0>(s, Tb, s0, b); blk8_round_x<1>(s, Tb, s0, b); blk8_round_x<2>(s, Tb, s0, b); blk8_round_x<3>(s, Tb, s0, b);
+        blk8_round_x<4>(s, Tb, s0, b); blk8_round_x<5>(s, Tb, s0, b); blk8_round_x<6>(s, Tb, s0, b); blk8_round_x<7>(s, Tb, s0, b);
+    } else {
+        mfma_v4i a[16], g[7];
+        blk8_load_frags16(a, Tb.efrag, s.lane);
+        blk8_round_y<0>(s, Tb, b, a, g); blk8_round_y<1>(s, Tb, b, a, g); blk8_round_y<2>(s, Tb, b, a, g); blk8_round_y<3>(s, Tb, b, a, g);
+        blk8_round_y<4>(s, Tb, b, a, g); blk8_round_y<5>(s, Tb, b, a, g); blk8_round_y<6>(s, Tb, b, a, g); blk8_round_y<7>(s, Tb, b, a, g);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    blk8_lane_rows<NLX>(s, Tb, b, last);
 }
 
 // s_j += w_{0,j} x0 + w_{1,j} x1 + w_{2,j} x2 + w_{3,j} x3   (one reduction)
@@ -404,8 +396,9 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
 #pragma unroll 1
         for (int b = 0; b < nb; ++b) {
             const Blk8Tabs Tb{reinterpret_cast<const mfma_v4i*>(P.blk8_efrag) + (size_t)b * 8 * 16 * 64, reinterpret_cast<const mfma_v4i*>(P.blk8_lfrag) + (size_t)b * 16 * 8 * 64,
-                              reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), c29(P.sparse29, (size_t)(8 * b) * W), c29(P.gamma8_29, (size_t)b * 28), P.rc_partial + 8 * b};
-            pair_block8<Blk8Cfg::YG, Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1);
+                              reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), reinterpret_cast<const mfma_v4i*>(P.blk8_gfrag) + (size_t)b * 28 * 64,
+                              c29(P.sparse29, (size_t)(8 * b) * W), P.rc_partial + 8 * b};
+            pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1);
         }
     } else
     for (int b = 0; b < P.rp / 4; ++b) {

@@ -20,7 +20,7 @@ struct PoseidonDev {           // device pointers to kernel-form constants (see 
     // t = 17: the partial rounds unrolled over all rp rounds for the five-wave latency kernel (host_util.hpp chain_*, poseidon_chain.hpp); nullptr otherwise
     const uint32_t* chain_a; const uint32_t* chain_g; const uint32_t* chain_w;
     // t = 17, rp % 8 == 0: the 8-round partial blocks of the wave-pair kernels (host_util.hpp blk8_*, poseidon_pair.hpp pair_block8); nullptr otherwise
-    const void* blk8_efrag; const void* blk8_lfrag; const void* blk8_unit_frag; const uint32_t* gamma8_29;
+    const void* blk8_efrag; const void* blk8_lfrag; const void* blk8_unit_frag; const void* blk8_gfrag;
 };
 
 }  // namespace stark

@@ -1,5 +1,5 @@
-// tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds, and of
-// the lane product of the 8-round partial blocks with the base lane in the tile (finish with base):
+// tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds, of
+// the lane product of the 8-round partial blocks with the base lane in the tile (finish with base), and of the blocks' H rows of up to 16 + 7 K-steps:
 // the fragment tables (host_util.hpp mfma_frags) and the fold + finishing step (mfma_digits.hpp), against the portable field code.  Meant for a
 // sanitizer build; tools/mfma_finish_sanitize.sh builds it with AddressSanitizer + UBSan and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I stark_mlwe_amd/csrc tools/mfma_finish_check.cpp -o tools/bin/mfma_finish_check
@@ -120,6 +120,25 @@ int main() {
             for (int p = 0; p < 8; ++p) want = host::h_add(want, host::h_mul(host::h_mul(kc.sparse[(size_t)(8 * blk + p) * 33 + 16 + j], k20), y[p]));
             ++n; if (!fr_eq(finish(S), want)) { if (bad < 5) fprintf(stderr, "lane row: mismatch block %d rep %d lane %d\n", blk, rep, j); ++bad; }
         }
+    }
+    // ---- the H rows of the 8-round partial blocks: H_q = E_q + sum_{p<q} Gamma_{q,p} y_p as ONE tile of 16 + q K-steps, E fragments (unscaled) against the
+    // lanes and blk8_gfrag (Gamma * 2^20) against the y.  Rows 1, 4 and 7 (17, 20 and 23 K-steps) of block 0 and of the last block, lanes and y at
+    // r - 1 / 0 / alternating / random, against sum_j u_{q,j} s_j + sum_p (sum_j u_{q,j} w_{p,j}) 2^20 y_p in the field code; the bound of the longest row checked.
+    if (kc.blk8_gfrag.size() != (size_t)8 * 28 * 1024) { fprintf(stderr, "block-8 Gamma fragments missing\n"); return 1; }
+    for (int blk : {0, 7}) for (int q : {1, 4, 7}) for (int rep = 0; rep < 6; ++rep) {
+        fr_t sl[16], y[7]; int64_t S64[32] = {0};
+        for (int j = 0; j < 16; ++j) sl[j] = rep == 0 ? rm1 : rep == 1 ? host::h_zero() : rep == 2 ? ((j & 1) ? rm1 : host::h_zero()) : rand_fr();
+        for (int p = 0; p < q; ++p) y[p] = rep == 0 ? rm1 : rep == 1 ? host::h_zero() : rep == 2 ? ((p & 1) ? host::h_zero() : rm1) : rand_fr();
+        const fr_t* uq = &kc.sparse[(size_t)(8 * blk + q) * 33];
+        fr_t want = host::h_zero();
+        for (int j = 0; j < 16; ++j) { kstep(kc.blk8_efrag.data() + (((size_t)blk * 8 + q) * 16 + j) * 1024, recode_signed(sl[j]), S64); want = host::h_add(want, host::h_mul(uq[1 + j], sl[j])); }
+        for (int p = 0; p < q; ++p) {
+            kstep(kc.blk8_gfrag.data() + ((size_t)blk * 28 + q * (q - 1) / 2 + p) * 1024, recode_signed(y[p]), S64);
+            fr_t g = host::h_zero(); for (int j = 0; j < 16; ++j) g = host::h_add(g, host::h_mul(uq[1 + j], kc.sparse[(size_t)(8 * blk + p) * 33 + 17 + j]));
+            want = host::h_add(want, host::h_mul(host::h_mul(g, k20), y[p]));
+        }
+        int32_t S[32]; for (int c = 0; c < 32; ++c) { if (S64[c] > (16 + q) * 32 * 128 * 128 || S64[c] < -(16 + q) * 32 * 128 * 128 || S64[c] > LIM || S64[c] < -LIM) { fprintf(stderr, "H row beyond its bound\n"); return 1; } S[c] = (int32_t)S64[c]; }
+        ++n; if (!fr_eq(finish(S), want)) { if (bad < 5) fprintf(stderr, "H row: mismatch block %d row %d rep %d\n", blk, q, rep); ++bad; }
     }
     printf("{\"check\": \"residue tables and finishing step against the portable field code\", \"cases\": %ld, \"mismatches\": %ld}\n", n, bad);
     return bad ? 1 : 0;

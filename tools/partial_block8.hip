@@ -1,12 +1,13 @@
-// tools/partial_block8.hip — PROTOTYPE, not product code: 8 partial rounds of the t = 17 Poseidon permutation for 64 sponges per wave pair, in two forms.
-//   form 4: the shipped block-of-4 code, twice — pair_permute<17> of poseidon_pair.hpp itself, run with rf = 0 and rp = 8 (no full rounds);
-//   form 8: the product's pair_block8 (poseidon_pair.hpp, where the schedule is described): one block of 8 rounds whose E-product (8 rows x 16 lanes) and
-//           lane product (16 rows x 8 S-box outputs, plus the base lane as a ninth K-step) run on the matrix cores through residue tables; Y computes
-//           E_q inside round q, X runs nothing but the chain.  Instantiated for several shares (YG: Y's gamma terms per round, NLX: X's lane rows).
-//           A first form — both waves computing their E rows before the chain from B operands held in registers, no fragment prefetch — measured
-//           126.8 k SIMD-cycles per 8 rounds where this one measured 114.7 k; it is not kept here.
-//   LDS stays at PairCfg<17>::lds_bytes() = 40 KiB.  The host checks both forms against the sparse rounds in the portable field code (0 and r - 1 among
-//   the inputs) and requires zero mismatches; then the two forms are timed alternately in one process, the state reloaded from memory for every repetition.
+// tools/partial_block8.hip — PROTOTYPE, not product code: 8 partial rounds of the t = 17 Poseidon permutation for 64 sponges per wave pair, in four forms.
+//   form 4      : the shipped block-of-4 code, twice — pair_permute<17> of poseidon_pair.hpp itself, run with rf = 0 and rp = 8 (no full rounds);
+//   former 8    : one block of 8 rounds whose E-product (8 rows x 16 lanes) and lane product (16 rows x 8 S-box outputs, plus the base lane as a ninth
+//                 K-step) run on the matrix cores through residue tables, the 28 Gamma terms of the block on the vector ALU (namespace former below: the
+//                 product's form until the Gamma terms moved; kept here as the comparison);
+//   form 8      : the product's pair_block8 (poseidon_pair.hpp, where the schedule is described): the Gamma terms as q further K-steps of row q's tile,
+//                 X posting y_q recoded.  Instantiated for several shares of the lane rows (NLX);
+//   form 8 piped: the same with wave Y software-pipelined across the round barrier (namespace piped below), measured and not adopted.
+//   LDS stays at PairCfg<17>::lds_bytes() = 40 KiB.  The host checks every form against the sparse rounds in the portable field code (0 and r - 1 among
+//   the inputs) and requires zero mismatches; then the forms are timed alternately in one process, the state reloaded from memory for every repetition.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I stark_mlwe_amd/csrc tools/partial_block8.hip -o tools/bin/partial_block8
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -19,11 +20,203 @@
 using namespace stark;
 constexpr int T = 17, W = 2 * T - 1, B8 = 8;
 
+// ---- the FORMER form of the block, kept here as the comparison: the Gamma terms on the vector ALU (Y the YG youngest per round, X the older ones, each
+// term a nine-limb unpack and 81 MACs, a wide reduction and an add per round in Y), the y held as field elements by both waves and brought to the B layout
+// at the end of the block.  The product no longer contains it.
+namespace former {
+struct Tabs {
+    const mfma_v4i* efrag;     // [8][16][64]   row q, lane j = 1..16
+    const mfma_v4i* lfrag;     // [16][8][64]   lane j = 1..16, S-box output p
+    const mfma_v4i* unit;      // [64]          the constant 1
+    const uint32_t* a29;       // a_q at c29(a29, q * (2 T - 1)): the block's first row of sparse29
+    const uint32_t* g29;       // [28][9]       Gamma_{q,p} at q (q - 1) / 2 + p
+    const fr_t* rc;            // [8]
+};
+struct Cfg {
+    // Y's share of a round's gamma terms (the YG youngest) and X's share of the lane rows: 5 / 8 measured best, the neighbours within 1.5 %
+    // (YG 6 with NLX 8: +1.5 %, YG 6 with NLX 7: +0.2 %, YG 7 with NLX 9: +1.1 %; run-to-run spread 1.5 %)
+    static constexpr int YG = 5, NLX = 8;
+    __host__ __device__ static constexpr int ymail(int q) { return 17 + (q & 1); }
+    __host__ __device__ static constexpr int hmail(int q) { return (q & 1) ? 19 : 0; }
+};
+template <int Q, int P, int LO, int HI>
+__device__ __forceinline__ void gterm(fr_wide29& acc, const Tabs& Tb, const fr_t (&yk)[8]) {          // gamma term p of round Q, if p is in [LO, HI)
+    if constexpr (P < Q && P >= LO && P < HI) fr_wide29_mac(acc, c29(Tb.g29, Q * (Q - 1) / 2 + P), fr29_unpack(yk[P]));
+}
+template <int Q, int LO, int HI>
+__device__ __forceinline__ void gterms(fr_wide29& acc, const Tabs& Tb, const fr_t (&yk)[8]) {
+    gterm<Q, 0, LO, HI>(acc, Tb, yk); gterm<Q, 1, LO, HI>(acc, Tb, yk); gterm<Q, 2, LO, HI>(acc, Tb, yk); gterm<Q, 3, LO, HI>(acc, Tb, yk);
+    gterm<Q, 4, LO, HI>(acc, Tb, yk); gterm<Q, 5, LO, HI>(acc, Tb, yk); gterm<Q, 6, LO, HI>(acc, Tb, yk);
+}
+// round Q in wave X: at most 1 + 7 - YG terms, within fr29_max_terms
+template <int Q, int YG>
+__device__ __forceinline__ void round_x(const PairState& s, const Tabs& Tb, fr_t& s0, fr_t (&yk)[8]) {
+    __builtin_amdgcn_sched_barrier(0);                     // keep the rounds apart: less register pressure
+    yk[Q] = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));
+    s.sto(Cfg::ymail(Q), yk[Q]);
+    fr_wide29 acc; fr_wide29_zero(acc);
+    fr_wide29_mac(acc, c29(Tb.a29, (size_t)Q * (2 * 17 - 1)), fr29_unpack(yk[Q]));
+    gterms<Q, 0, (Q - YG > 0 ? Q - YG : 0)>(acc, Tb, yk);
+    const fr_t part = fr_wide29_reduce<PF>(acc);
+    __syncthreads();                                       // barrier_Q: H_Q is posted
+    s0 = fr_add<PF>(part, s.ld(Cfg::hmail(Q)));
+}
+// round Q in wave Y.  a: the fragments of E row Q on entry, of row Q + 1 on exit
+template <int Q, int YG>
+__device__ __forceinline__ void round_y(const PairState& s, const Tabs& Tb, fr_t (&yk)[8], mfma_v4i (&a)[16]) {
+    __builtin_amdgcn_sched_barrier(0);
+    const int lane = s.lane, h = lane >> 5;
+    mfma_v16i acc[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            const uint4 u = s.st[(2 * (e + 1) + h) * 64 + 32 * ct + (lane & 31)];
+            acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[e], mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w}, acc[ct], 0, 0, 0);
+        }
+    if constexpr (Q < 7) blk8_load_frags16(a, Tb.efrag + (size_t)(Q + 1) * 16 * 64, lane);
+    fr_t hq = mfma_post(acc);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (Q > 0) {
+        fr_wide29 w; fr_wide29_zero(w);
+        gterms<Q, (Q - YG > 0 ? Q - YG : 0), Q>(w, Tb, yk);
+        hq = fr_add<PF>(hq, fr_wide29_reduce<PF>(w));
+    }
+    s.sto(Cfg::hmail(Q), hq);
+    __syncthreads();                                       // barrier_Q: y_Q is posted
+    yk[Q] = s.ld(Cfg::ymail(Q));
+}
+// One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; s0 = X_0 in wave X.  Ends with a barrier, the lanes recoded again,
+// or canonical after the permutation's last block.
+template <int YG, int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Tabs& Tb, fr_t& s0, bool last) {
+    static_assert(YG >= 1 && YG <= 7 && NLX >= 1 && NLX <= 15, "shares");
+    static_assert(YG <= fr29_max_terms<PF>() && 1 + 7 - YG <= fr29_max_terms<PF>(), "Y sums YG terms, X up to 1 + 7 - YG, without a carry pass in between");
+    const int lane = s.lane, h = lane >> 5;
+    fr_t yk[8];
+    if (!s.isY) {
+        round_x<0, YG>(s, Tb, s0, yk); round_x<1, YG>(s, Tb, s0, yk); round_x<2, YG>(s, Tb, s0, yk); round_x<3, YG>(s, Tb, s0, yk);
+        round_x<4, YG>(s, Tb, s0, yk); round_x<5, YG>(s, Tb, s0, yk); round_x<6, YG>(s, Tb, s0, yk); round_x<7, YG>(s, Tb, s0, yk);
+    } else {
+        mfma_v4i a[16];
+        blk8_load_frags16(a, Tb.efrag, lane);
+        round_y<0, YG>(s, Tb, yk, a); round_y<1, YG>(s, Tb, yk, a); round_y<2, YG>(s, Tb, yk, a); round_y<3, YG>(s, Tb, yk, a);
+        round_y<4, YG>(s, Tb, yk, a); round_y<5, YG>(s, Tb, yk, a); round_y<6, YG>(s, Tb, yk, a); round_y<7, YG>(s, Tb, yk, a);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    mfma_v4i b[8][2];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+        const fr_t yr = recode_signed(yk[p]);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {      // afterwards b[p][ct] = half (lane >> 5) of y_p of sponge 32 ct + (lane & 31)
+            const auto sw = __builtin_amdgcn_permlane32_swap(yr.v[w], yr.v[4 + w], false, false);
+            b[p][0][w] = (int)sw[0]; b[p][1][w] = (int)sw[1];
+        }
+    }
+    const int j0 = s.isY ? NLX + 1 : 1, j1 = s.isY ? 16 : NLX;
+    const mfma_v4i aunit = Tb.unit[lane];
+    mfma_v4i a[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(j0 - 1) * 8 + p) * 64)[lane];
+#pragma unroll 1
+    for (int j = j0; j <= j1; ++j) {
+        mfma_v16i acc[2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], b[p][ct], acc[ct], 0, 0, 0);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            const uint4 u = s.st[(2 * j + h) * 64 + 32 * ct + (lane & 31)];
+            acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aunit, mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w}, acc[ct], 0, 0, 0);
+        }
+        const int jn = j < j1 ? j + 1 : j1;                // the last row fetches its own fragments again: in bounds, unused
+#pragma unroll
+        for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
+        const fr_t z = mfma_post(acc);
+        s.sto(j, last ? z : recode_signed(z));             // slot j is read by this wave alone, before this write
+    }
+    __syncthreads();
+}
+}  // namespace former
+
+// ---- the product's form with wave Y SOFTWARE-PIPELINED across the round barrier, measured here and not in the product unless it wins: of row Q only the
+// K-step of y_{Q-1} depends on barrier_{Q-1}, so the 16 lane steps and the steps of y_p, p <= Q - 2, are issued before that barrier, after H_{Q-1} is
+// posted (the accumulator pair is free again by then: no second pair).  Wave X and the lane product are the product's.
+namespace piped {
+template <int Q>
+__device__ __forceinline__ void round_y(const PairState& s, const Blk8Tabs& Tb, mfma_v4i (&b)[8][2], mfma_v4i (&a)[16], mfma_v4i (&g)[7], mfma_v16i (&acc)[2]) {
+    __builtin_amdgcn_sched_barrier(0);
+    const int lane = s.lane;
+    if constexpr (Q > 0) {
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(g[Q - 1], b[Q - 1][ct], acc[ct], 0, 0, 0);
+    }
+    if constexpr (Q < 7) {
+        blk8_load_frags16(a, Tb.efrag + (size_t)(Q + 1) * 16 * 64, lane);
+#pragma unroll
+        for (int p = 0; p <= Q; ++p) g[p] = (Tb.gfrag + (size_t)((Q + 1) * Q / 2 + p) * 64)[lane];
+    }
+    s.sto(Blk8Cfg::hmail(Q), mfma_post(acc));
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (Q < 7) {                                 // row Q + 1 up to the step of y_{Q-1}
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[e], blk8_b_of_slot(s, e + 1, ct), acc[ct], 0, 0, 0);
+        if constexpr (Q > 0) {
+#pragma unroll
+            for (int p = 0; p < Q; ++p)
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(g[p], b[p][ct], acc[ct], 0, 0, 0);
+        }
+    }
+    __syncthreads();                                       // barrier_Q: y_Q is posted
+    b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
+}
+template <int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last) {
+    mfma_v4i b[8][2];
+    if (!s.isY) {
+        blk8_round_x<0>(s, Tb, s0, b); blk8_round_x<1>(s, Tb, s0, b); blk8_round_x<2>(s, Tb, s0, b); blk8_round_x<3>(s, Tb, s0, b);
+        blk8_round_x<4>(s, Tb, s0, b); blk8_round_x<5>(s, Tb, s0, b); blk8_round_x<6>(s, Tb, s0, b); blk8_round_x<7>(s, Tb, s0, b);
+    } else {
+        mfma_v4i a[16], g[7]; mfma_v16i acc[2];
+        blk8_load_frags16(a, Tb.efrag, s.lane);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[e], blk8_b_of_slot(s, e + 1, ct), acc[ct], 0, 0, 0);
+        round_y<0>(s, Tb, b, a, g, acc); round_y<1>(s, Tb, b, a, g, acc); round_y<2>(s, Tb, b, a, g, acc); round_y<3>(s, Tb, b, a, g, acc);
+        round_y<4>(s, Tb, b, a, g, acc); round_y<5>(s, Tb, b, a, g, acc); round_y<6>(s, Tb, b, a, g, acc); round_y<7>(s, Tb, b, a, g, acc);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    blk8_lane_rows<NLX>(s, Tb, b, last);
+}
+}  // namespace piped
+
 // The tables of "block rep & blkmask" (always block 0): as in a permutation's loop over its blocks the fragment addresses change from one pass to the
 // next, so the compiler cannot hoist all of them out of the repetition loop (it did, and spilled 200 registers for them).
-struct ProtoTabs { const mfma_v4i* efrag; const mfma_v4i* lfrag; const mfma_v4i* unit; const uint32_t* sparse29; const uint32_t* gamma8_29; const fr_t* rc; int blkmask; };
+struct ProtoTabs { const mfma_v4i* efrag; const mfma_v4i* lfrag; const mfma_v4i* unit; const mfma_v4i* gfrag; const uint32_t* sparse29; const uint32_t* gamma8_29; const fr_t* rc; int blkmask; };
 
-template <int YG, int NLX>
+template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_block8(ProtoTabs Tp, const fr_t* __restrict__ X, fr_t* __restrict__ Y, int reps) {
     extern __shared__ uint4 lds[];
     PairState s = pair_setup(lds);
@@ -34,8 +227,13 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
         for (int j = s.isY ? 9 : 1; j <= (s.isY ? 16 : 8); ++j) s.sto(j, recode_signed(ldg(X + b0 + (size_t)j * 64 + s.lane)));
         __syncthreads();
         const int blk = rep & Tp.blkmask;
-        const Blk8Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sparse29, Tp.gamma8_29, Tp.rc};
-        pair_block8<YG, NLX>(s, Tb, s0, true);          // last: the lanes end canonical in their slots
+        if constexpr (YG > 0) {
+            const former::Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sparse29, Tp.gamma8_29, Tp.rc};
+            former::pair_block8<YG, NLX>(s, Tb, s0, true);  // last: the lanes end canonical in their slots
+        } else {
+            const Blk8Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.gfrag + (size_t)blk * 28 * 64, Tp.sparse29, Tp.rc};
+            if constexpr (YG == 0) pair_block8<NLX>(s, Tb, s0, true); else piped::pair_block8<NLX>(s, Tb, s0, true);
+        }
         if (rep == 0) {
             if (!s.isY) stg(Y + b0 + s.lane, s0);
             for (int j = s.isY ? 9 : 1; j <= (s.isY ? 16 : 8); ++j) stg(Y + b0 + (size_t)j * 64 + s.lane, s.ld(j));
@@ -73,7 +271,7 @@ int main() {
     // the product's tables (host_util.hpp blk8_*); block 0 = rounds 0..7
     if (K.blk8_efrag.empty()) { fprintf(stderr, "no block-8 tables\n"); return 1; }
     g_tb.efrag = to_dev<mfma_v4i>(K.blk8_efrag.data(), K.blk8_efrag.size()); g_tb.lfrag = to_dev<mfma_v4i>(K.blk8_lfrag.data(), K.blk8_lfrag.size());
-    g_tb.unit = g_tb.lfrag + (K.blk8_lfrag.size() - 1024) / 16;
+    g_tb.unit = g_tb.lfrag + (K.blk8_lfrag.size() - 1024) / 16; g_tb.gfrag = to_dev<mfma_v4i>(K.blk8_gfrag.data(), K.blk8_gfrag.size());
     g_tb.sparse29 = to_dev<uint32_t>(K.sparse29.data(), K.sparse29.size() * 4); g_tb.gamma8_29 = to_dev<uint32_t>(K.gamma8_29.data(), K.gamma8_29.size() * 4);
     g_tb.blkmask = 0;
     g_tb.rc = to_dev<fr_t>(K.rc_partial.data(), K.rc_partial.size() * sizeof(fr_t));
@@ -93,10 +291,14 @@ int main() {
 
     const Form forms[] = {
         {"block4 x 2 (shipped pair_permute<17>, rf = 0, rp = 8)", launch4},
-        {"block8 YG=5 NLX=8 (the product's shares)", launch8<Blk8Cfg::YG, Blk8Cfg::NLX>},
-        {"block8 YG=6 NLX=8", launch8<6, 8>},
-        {"block8 YG=6 NLX=7", launch8<6, 7>},
-        {"block8 YG=7 NLX=9", launch8<7, 9>},
+        {"block8, Gamma terms on the vector ALU, YG=5 NLX=8 (the former product form)", launch8<5, 8>},
+        {"block8, Gamma terms as K-steps of the E rows, NLX=8 (the product's pair_block8)", launch8<0, Blk8Cfg::NLX>},
+        {"block8, Gamma K-steps, NLX=8, wave Y pipelined across the round barrier", launch8<-1, 8>},
+        {"block8, Gamma K-steps, NLX=7, wave Y pipelined across the round barrier", launch8<-1, 7>},
+        {"block8, Gamma K-steps, NLX=6", launch8<0, 6>},
+        {"block8, Gamma K-steps, NLX=7", launch8<0, 7>},
+        {"block8, Gamma K-steps, NLX=9", launch8<0, 9>},
+        {"block8, Gamma K-steps, NLX=10", launch8<0, 10>},
     };
     const int nforms = (int)(sizeof forms / sizeof forms[0]);
     // reference: the sparse rounds in the portable field code, sampled batches
