@@ -145,6 +145,15 @@ int32_t stark_leaf_pair_hash_dev(stark_ctx_t* ctx, stark_params_t* tparams, cons
 /* tr_hash_fields_tagged (fri.rs:28-35): n_hashes independent transcript hashes of k fields each. */
 int32_t stark_tr_hash_fields_tagged(stark_ctx_t* ctx, stark_params_t* tparams, const char* tag, const uint64_t* fields, size_t k, size_t n_hashes, uint64_t* out);
 int32_t stark_tr_hash_fields_tagged_dev(stark_ctx_t* ctx, stark_params_t* tparams, const char* tag, const uint64_t* fields, size_t k, size_t n_hashes, uint64_t* out);
+/* n transcript hashes of ANY tags and lengths in one launch: out[i] = tr_hash_fields_tagged(tags[i], fields[i][0 .. k[i])) (fri.rs:28-35), byte-equal
+ * to stark_tr_hash_fields_tagged_dev on item i alone.  tags: HOST array of n C strings; fields: HOST array of n DEVICE pointers (a NULL entry is
+ * allowed iff k[i] == 0: such an item hashes its tag's frame alone; the table itself may be NULL when every k[i] is 0); k: HOST, n; out: DEVICE,
+ * n x 4.  The sponges are independent chains and run side by side, the longest first, each digest written to its caller's slot: the call costs what
+ * its longest item costs.  Stream-ordered, no host synchronisation (the first use of a tag uploads its frame and synchronises, as in every
+ * transcript hash).  Pointers may repeat; inputs are left intact.  n == 0 returns STARK_OK.
+ * STARK_ERR_INVALID_ARG, before any launch: a null ctx, tags, k or out; a null tags[i]; a null fields table or entry with k[i] > 0; an out range
+ * that overlaps an input. */
+int32_t stark_tr_hash_many_dev(stark_ctx_t* ctx, size_t n, const char* const* tags, const uint64_t* const* fields, const size_t* k, uint64_t* out);
 
 /* ---- Merkle ---------------------------------------------------------------------------------------
  * MerkleTree::new / new_pairs (merkle/src/lib.rs:147-193, 392-445): level-by-level build, all levels
@@ -273,6 +282,20 @@ int32_t stark_deep_fri_prove_dev(stark_ctx_t* ctx, const uint64_t* a, const uint
  * and stage 2, which holds the pass's first synchronisation, absorbs the device time of all three. */
 int32_t stark_deep_fri_prove_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t,
                                        size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out);
+/* `batch` independent traces of ANY shapes in one call: trace i has n0[i] rows, folds by schedule[sched_off[i] .. sched_off[i + 1]) and answers r[i]
+ * queries (the reference's bench proves k = 11, 12, .. 18 one after another, channel/benches/end_to_end.rs:229-309).  a, s, e, t: HOST arrays of
+ * `batch` DEVICE pointers; n0, r: HOST, batch; sched_off: HOST, batch + 1, non-decreasing; out: host array of `batch` proof handles.
+ * The 4 * batch column sponges of build_f0 run in ONE launch whatever their lengths (longest first), so the stage that bounds a prove costs what
+ * the largest trace's costs instead of the sum over the traces.  Traces of equal (n0, schedule, r) then form a group — groups in order of first
+ * appearance, traces in the caller's order — and each group takes the tail of stark_deep_fri_prove_batch_dev: passes of at most
+ * "prove_batch_max_rows" rows, a pass of one trace the single tail.
+ * Proof i is byte-identical to stark_deep_fri_prove_dev on trace i alone under (n0[i], its schedule, r[i]).  stage_ms 0 of a proof is the sponge
+ * stage of the whole batch + its pass's merge; 1 and 2 are its pass's, as in stark_deep_fri_prove_batch_dev.  batch == 0 returns STARK_OK.
+ * STARK_ERR_INVALID_ARG, before any launch: a null ctx, table, entry, n0, r, sched_off or out; a decreasing sched_off; a null schedule with a
+ * fold; an n0[i] that is not a power of two or is <= 1; a schedule that does not divide its n0.  Shapes the single call refuses with
+ * STARK_ERR_UNSUPPORTED are refused with it here.  On any error every out[i] is NULL. */
+int32_t stark_deep_fri_prove_mixed_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t,
+                                             const size_t* n0, const size_t* schedule, const size_t* sched_off, const size_t* r, uint64_t seed_z, stark_proof_t** out);
 /* The batch forms of "prove given f0", of the commit phase and of the merge.  Tables (f0, a, s, e, t, r_opt) are HOST arrays of `batch`
  * DEVICE pointers.  Element i of every result equals what the single call returns for trace i alone, byte for byte:
  * stark_deep_fri_prove_dev with f0; the L + 1 roots of stark_fri_build_dev (roots[(i (L + 1) + l) * 4 ..]); stark_ali_merge_dev (one omega4

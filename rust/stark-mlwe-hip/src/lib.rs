@@ -354,6 +354,28 @@ pub mod fri {
             (bytes, est)
         }).collect()
     }
+    /// Traces of ANY shapes in one call (the sweep k = 11, 12, .. of `channel/benches/end_to_end.rs:229-309` is one): `traces[p] = (a, s, e, t)`
+    /// as DEVICE pointers, `shapes[p] = (n0, schedule, r)` of trace p.  All 4 * B column sponges run in one launch whatever their lengths; traces
+    /// of equal shape share the batched tail.  Every proof is byte-identical to `deep_fri_prove` of that trace alone under its own shape.
+    pub unsafe fn deep_fri_prove_mixed_batch_dev(ctx: &Ctx, traces: &[[*const u64; 4]], shapes: &[(usize, &[usize], usize)], seed_z: u64) -> Vec<(Vec<u8>, usize)> {
+        assert_eq!(traces.len(), shapes.len());
+        let col = |c: usize| traces.iter().map(|t| t[c]).collect::<Vec<_>>();
+        let (a, s, e, t) = (col(0), col(1), col(2), col(3));
+        let n0: Vec<usize> = shapes.iter().map(|sh| sh.0).collect();
+        let r: Vec<usize> = shapes.iter().map(|sh| sh.2).collect();
+        let mut schedule: Vec<usize> = Vec::new();
+        let mut sched_off: Vec<usize> = vec![0];
+        for sh in shapes { schedule.extend_from_slice(sh.1); sched_off.push(schedule.len()); }
+        let mut raw: Vec<*mut stark_proof_t> = vec![ptr::null_mut(); traces.len()];
+        ctx.chk(stark_deep_fri_prove_mixed_batch_dev(ctx.raw, traces.len(), a.as_ptr(), s.as_ptr(), e.as_ptr(), t.as_ptr(), n0.as_ptr(), schedule.as_ptr(), sched_off.as_ptr(), r.as_ptr(), seed_z, raw.as_mut_ptr()));
+        raw.into_iter().map(|h| {
+            let mut bytes = vec![0u8; stark_proof_len(h)];
+            ctx.chk(stark_proof_bytes(h, bytes.as_mut_ptr()));
+            let est = stark_proof_size_estimate(h);
+            stark_proof_free(h);
+            (bytes, est)
+        }).collect()
+    }
     /// "Prove given f0" for many vectors in one call: `f0s[p]` = DEVICE pointer of an n0-element f0; every proof is byte-identical to
     /// `deep_fri_prove` with that f0 alone.  The commit and query phases of the traces run side by side (one launch per step and pass).
     pub unsafe fn deep_fri_prove_f0_batch_dev(ctx: &Ctx, f0s: &[*const u64], n0: usize, schedule: &[usize], r: usize, seed_z: u64) -> Vec<(Vec<u8>, usize)> {

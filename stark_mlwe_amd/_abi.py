@@ -56,6 +56,7 @@ SIGNATURES = {
     "stark_leaf_pair_hash_dev": (i32, [vp, vp, vp, vp, sz, sz, vp]),
     "stark_tr_hash_fields_tagged": (i32, [vp, vp, C.c_char_p, vp, sz, sz, vp]),
     "stark_tr_hash_fields_tagged_dev": (i32, [vp, vp, C.c_char_p, vp, sz, sz, vp]),
+    "stark_tr_hash_many_dev": (i32, [vp, sz, vp, vp, vp, vp]),
     "stark_merkle_build": (i32, [vp, vp, sz, u64, vp, sz, i32, vp, vpp]),
     "stark_merkle_build_dev": (i32, [vp, vp, sz, u64, vp, sz, i32, vp, u64, u32, i32, vpp]),
     "stark_merkle_num_levels": (i32, [vp]),
@@ -92,6 +93,7 @@ SIGNATURES = {
     "stark_deep_fri_prove": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, sz, sz, u64, vpp]),
     "stark_deep_fri_prove_dev": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, sz, sz, u64, vpp]),
     "stark_deep_fri_prove_batch_dev": (i32, [vp, sz, vp, vp, vp, vp, sz, vp, sz, sz, u64, vp]),
+    "stark_deep_fri_prove_mixed_batch_dev": (i32, [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]),
     "stark_deep_fri_prove_f0_batch_dev": (i32, [vp, sz, vp, sz, vp, sz, sz, u64, vp]),
     "stark_fri_commit_batch_dev": (i32, [vp, sz, vp, sz, vp, sz, u64, vp]),
     "stark_ali_merge_batch_dev": (i32, [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),

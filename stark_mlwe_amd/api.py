@@ -406,6 +406,16 @@ class Context:
         self._chk(self.lib.stark_tr_hash_fields_tagged(self.h, None, tag, _ptr(fl), k, n, _ptr(out)))
         return out[0] if n == 1 else out
 
+    def tr_hash_many_dev(self, items, out):
+        """`items`: list of (tag bytes, DEVICE pointer of the fields (int; None or 0 allowed when k == 0), k); `out`: DEVICE pointer (int) of
+        len(items) x 4 words.  out[i] = tr_hash_fields_tagged(tag_i, fields_i[0 .. k_i)), all items in one launch whatever their tags and lengths,
+        stream-ordered (stark_tr_hash_many_dev)."""
+        n = len(items)
+        tags = (C.c_char_p * max(n, 1))(*[it[0] for it in items])
+        flds = (C.c_void_p * max(n, 1))(*[int(it[1]) if it[1] else None for it in items])
+        ks = (C.c_size_t * max(n, 1))(*[int(it[2]) for it in items])
+        self._chk(self.lib.stark_tr_hash_many_dev(self.h, n, tags, flds, ks, C.c_void_p(int(out) if out else None)))
+
     # ---- merkle -------------------------------------------------------------------------------------
     def merkle_cfg(self, arity, tree_label=0):
         """MerkleChannelCfg::new(arity).with_tree_label(label)."""
@@ -564,6 +574,23 @@ class Context:
         cols = [(C.c_void_p * B)(*[int(tr[c]) for tr in traces]) for c in range(4)]
         out = (C.c_void_p * B)()
         self._chk(self.lib.stark_deep_fri_prove_batch_dev(self.h, B, cols[0], cols[1], cols[2], cols[3], n0, _ptr(sch), len(sch), params.r, params.seed_z, out))
+        return self._proofs_out(out, B)
+
+    def deep_fri_prove_mixed_batch_dev(self, traces, shapes, seed_z):
+        """`traces`: list of (a, s, e, t) DEVICE pointers (ints) of independent traces of ANY sizes; `shapes`: per trace (n0, schedule, r) ->
+        list of (proof bytes, size estimate, stage ms), each equal to deep_fri_prove of that trace alone under its own shape.  All column sponges
+        run in one launch; traces of equal shape share the batched tail (stark_deep_fri_prove_mixed_batch_dev)."""
+        B = len(traces)
+        cols = [(C.c_void_p * max(B, 1))(*[int(tr[c]) if tr[c] else None for tr in traces]) for c in range(4)]
+        n0 = (C.c_size_t * max(B, 1))(*[int(sh[0]) for sh in shapes])
+        r = (C.c_size_t * max(B, 1))(*[int(sh[2]) for sh in shapes])
+        flat, off = [], [0]
+        for sh in shapes:
+            flat += [int(m) for m in sh[1]]; off.append(len(flat))
+        sch = (C.c_size_t * max(len(flat), 1))(*flat)
+        offs = (C.c_size_t * len(off))(*off)
+        out = (C.c_void_p * max(B, 1))()
+        self._chk(self.lib.stark_deep_fri_prove_mixed_batch_dev(self.h, B, cols[0], cols[1], cols[2], cols[3], n0, sch, offs, r, seed_z, out))
         return self._proofs_out(out, B)
 
     def _proofs_out(self, out, B):

@@ -215,35 +215,47 @@ static int32_t ali_challenges(stark_ctx* ctx, const fr_t h[4], size_t n0, fr_t* 
     fr_t fused; STARK_TRY(tr_hash_host1(ctx, "ALI/DEEP", {*seed_f, host::h_u64(n0)}, &fused));
     ali_z_beta_from_fused(fused, n0, *seed_f, z, beta); return STARK_OK;
 }
-// The challenge stage of build_f0 (fri.rs:548-560, 511-533) for B traces of n0 rows; cols[4 p + c] = column c of trace p (device).  What bounds one
-// prove is the serial column sponge (n0 / 16 dependent permutations per column, one block each), and the chains of different traces are independent:
-// all 4 B of them run in ONE launch, and the two Fiat-Shamir hashes per trace ("ALI/seed", "ALI/DEEP") are one launch each for the batch.
+// The challenge stage of build_f0 (fri.rs:548-560, 511-533) for B traces, trace p of n0[p] rows; cols[4 p + c] = column c of trace p (device).  What bounds one
+// prove is the serial column sponge (n0 / 16 dependent permutations per column, one block each), and the chains of different traces are independent
+// whatever their lengths: all 4 B of them run in ONE launch — traces of one size through the BatchColumns layout, traces of several sizes through the
+// Ragged one (longest chains first, poseidon_streams.hpp), so the stage costs what its longest chain costs — and the two Fiat-Shamir hashes per trace
+// ("ALI/seed", "ALI/DEEP", each with its trace's n0) are one launch each for the batch.
 // THREE host synchronisations whatever B: the digests, the seeds, the fused hashes.  Per trace p: h[4 p ..], seed_f[p], z[p], beta[p].
 struct AliChallenges { std::vector<fr_t> h, seed_f, z, beta; };
-static int32_t challenge_stage(stark_ctx* ctx, size_t B, const fr_t* const* cols, size_t n0, AliChallenges& out) {
+static int32_t challenge_stage(stark_ctx* ctx, size_t B, const fr_t* const* cols, const size_t* n0, AliChallenges& out) {
     DevBuf dptr, dig, seeds_in, seeds, deep_in, fused;
-    STARK_HIP(ctx, dptr.alloc(ctx, 4 * B * sizeof(void*))); STARK_HIP(ctx, dig.alloc(ctx, 4 * B * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(dptr.p, cols, 4 * B * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+    STARK_HIP(ctx, dig.alloc(ctx, 4 * B * sizeof(fr_t)));
     const char* tags[4] = {"ALI/A", "ALI/S", "ALI/E", "ALI/T"};
-    STARK_TRY(tr_hash_columns_batch_dev(ctx, tags, (const fr_t* const*)dptr.p, B, n0, dig.fr()));
+    if (std::all_of(n0, n0 + B, [&](size_t n) { return n == n0[0]; })) {
+        STARK_HIP(ctx, dptr.alloc(ctx, 4 * B * sizeof(void*)));
+        STARK_HIP(ctx, hipMemcpyAsync(dptr.p, cols, 4 * B * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+        STARK_TRY(tr_hash_columns_batch_dev(ctx, tags, (const fr_t* const*)dptr.p, B, n0[0], dig.fr()));
+    } else {
+        std::vector<const char*> tg(4 * B); std::vector<size_t> kk(4 * B);
+        for (size_t p = 0; p < B; ++p) for (int c = 0; c < 4; ++c) { tg[4 * p + c] = tags[c]; kk[4 * p + c] = n0[p]; }
+        STARK_TRY(tr_hash_many_dev(ctx, 4 * B, tg.data(), cols, kk.data(), dig.fr(), true));
+    }
     out.h.resize(4 * B);
     STARK_HIP(ctx, hipMemcpyAsync(out.h.data(), dig.p, 4 * B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // seed_f = H("ALI/seed", [h_a, h_s, h_e, h_t, n0]) and the fused hash of ali_sample_z_beta_fs (fri.rs:556-557, 511-515)
-    const fr_t n0f = host::h_u64(n0);
-    std::vector<fr_t> in5(5 * B); for (size_t p = 0; p < B; ++p) { for (int c = 0; c < 4; ++c) in5[5 * p + c] = out.h[4 * p + c]; in5[5 * p + 4] = n0f; }
+    std::vector<fr_t> in5(5 * B); for (size_t p = 0; p < B; ++p) { for (int c = 0; c < 4; ++c) in5[5 * p + c] = out.h[4 * p + c]; in5[5 * p + 4] = host::h_u64(n0[p]); }
     STARK_HIP(ctx, seeds_in.alloc(ctx, in5.size() * sizeof(fr_t))); STARK_HIP(ctx, seeds.alloc(ctx, B * sizeof(fr_t)));
     STARK_HIP(ctx, hipMemcpyAsync(seeds_in.p, in5.data(), in5.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
     STARK_TRY(tr_hash_dev(ctx, "ALI/seed", seeds_in.fr(), 5, B, seeds.fr()));
     out.seed_f.resize(B);
     STARK_HIP(ctx, hipMemcpyAsync(out.seed_f.data(), seeds.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<fr_t> in2(2 * B), fu(B); for (size_t p = 0; p < B; ++p) { in2[2 * p] = out.seed_f[p]; in2[2 * p + 1] = n0f; }
+    std::vector<fr_t> in2(2 * B), fu(B); for (size_t p = 0; p < B; ++p) { in2[2 * p] = out.seed_f[p]; in2[2 * p + 1] = host::h_u64(n0[p]); }
     STARK_HIP(ctx, deep_in.alloc(ctx, in2.size() * sizeof(fr_t))); STARK_HIP(ctx, fused.alloc(ctx, B * sizeof(fr_t)));
     STARK_HIP(ctx, hipMemcpyAsync(deep_in.p, in2.data(), in2.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
     STARK_TRY(tr_hash_dev(ctx, "ALI/DEEP", deep_in.fr(), 2, B, fused.fr()));
     STARK_HIP(ctx, hipMemcpyAsync(fu.data(), fused.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     out.z.resize(B); out.beta.resize(B);
-    for (size_t p = 0; p < B; ++p) ali_z_beta_from_fused(fu[p], n0, out.seed_f[p], &out.z[p], &out.beta[p]);
+    for (size_t p = 0; p < B; ++p) ali_z_beta_from_fused(fu[p], n0[p], out.seed_f[p], &out.z[p], &out.beta[p]);
     return STARK_OK;
+}
+// B traces of one size: the same stage with a constant vector
+static int32_t challenge_stage(stark_ctx* ctx, size_t B, const fr_t* const* cols, size_t n0, AliChallenges& out) {
+    const std::vector<size_t> n(B, n0); return challenge_stage(ctx, B, cols, n.data(), out);
 }
 // DeepAliRealBuilder::build_f0 (fri.rs:535-569), default builder: no blinding, ds_tag "ALI/DEEP": the challenge stage of one trace, then the merge.
 static int32_t build_f0_dev_impl(stark_ctx* ctx, const fr_t* a, const fr_t* s, const fr_t* e, const fr_t* t, size_t n0, fr_t* f0, fr_t* aux7) {
@@ -611,6 +623,34 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
     hand_out(pf, out); return STARK_OK;
 }
 
+// B independent proofs of ANY shapes (stark_deep_fri_prove_mixed_batch_dev): trace i has n0[i] rows, folds by schedule[sched_off[i] .. sched_off[i + 1])
+// and answers r[i] queries.  The challenge stage of all traces at once — the 4 B column sponges side by side in one Ragged launch, which is where
+// the time of a prove is — then the traces of equal (n0, schedule, r) together (mixed_prove_groups, fri_plan.hpp), each group through the passes of
+// the equal-shape batch: prove_pass, cut by "prove_batch_max_rows"; a group (or pass) of one trace takes the single commit.  No merge, commit or query
+// code of its own.  stage_ms[0] of a proof: the challenge stage of the whole batch + its pass's layer 0; [1], [2]: its pass's commit and queries.
+// The arguments were checked by the entry point.  Every proof is byte-for-byte what stark_deep_fri_prove_dev returns for that trace alone.
+static int32_t prove_mixed_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, const size_t* n0,
+                                      const size_t* schedule, const size_t* sched_off, const size_t* r, uint64_t seed_z, stark_proof** out) {
+    const auto t0 = Clock::now();
+    std::vector<const fr_t*> ptrs(4 * B);
+    for (size_t p = 0; p < B; ++p) { ptrs[4 * p] = as_fr(a[p]); ptrs[4 * p + 1] = as_fr(s[p]); ptrs[4 * p + 2] = as_fr(e[p]); ptrs[4 * p + 3] = as_fr(t[p]); }
+    AliChallenges ch; STARK_TRY(challenge_stage(ctx, B, ptrs.data(), n0, ch));
+    const double shared_ms = ms_between(t0, Clock::now());
+    std::vector<std::unique_ptr<stark_proof>> pf(B);
+    for (const std::vector<size_t>& G : mixed_prove_groups(B, n0, schedule, sched_off, r)) {
+        const size_t g0 = G[0], Bg = G.size(), L = sched_off[g0 + 1] - sched_off[g0], per = pass_traces(ctx, n0[g0]);
+        const size_t* sched = L ? schedule + sched_off[g0] : nullptr;
+        std::vector<const uint64_t*> tab[4]; std::vector<fr_t> zs(Bg); std::vector<std::unique_ptr<stark_proof>> gp(Bg);
+        for (size_t j = 0; j < Bg; ++j) { tab[0].push_back(a[G[j]]); tab[1].push_back(s[G[j]]); tab[2].push_back(e[G[j]]); tab[3].push_back(t[G[j]]); zs[j] = ch.z[G[j]]; }
+        for (size_t p0 = 0; p0 < Bg; p0 += per) {
+            const uint64_t* const* const cols[4] = {tab[0].data() + p0, tab[1].data() + p0, tab[2].data() + p0, tab[3].data() + p0};
+            STARK_TRY(prove_pass(ctx, std::min(per, Bg - p0), cols, zs.data() + p0, nullptr, n0[g0], sched, L, r[g0], seed_z, shared_ms, gp.data() + p0));
+        }
+        for (size_t j = 0; j < Bg; ++j) pf[G[j]] = std::move(gp[j]);
+    }
+    hand_out(pf, out); return STARK_OK;
+}
+
 extern "C" {
 
 int32_t stark_fri_sample_z(stark_ctx_t* ctx, stark_params_t* tp, uint64_t seed_z, size_t level, size_t domain_size, uint64_t* z4) {
@@ -716,6 +756,23 @@ int32_t stark_deep_fri_prove_batch_dev(stark_ctx_t* ctx, size_t batch, const uin
     for (size_t p = 0; p < batch; ++p) if (!a[p] || !s[p] || !e[p] || !t[p]) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     return prove_batch_impl(ctx, batch, a, s, e, t, n0, schedule, L, r, seed_z, out);
+}
+int32_t stark_deep_fri_prove_mixed_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, const size_t* n0,
+                                             const size_t* schedule, const size_t* sched_off, const size_t* r, uint64_t seed_z, stark_proof_t** out) {
+    if (out) for (size_t p = 0; p < batch; ++p) out[p] = nullptr;
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!batch) return STARK_OK;
+    if (!out || !a || !s || !e || !t || !n0 || !r || !sched_off) return STARK_ERR_INVALID_ARG;
+    for (size_t p = 0; p < batch; ++p) if (!a[p] || !s[p] || !e[p] || !t[p]) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    for (size_t p = 0; p < batch; ++p) if (sched_off[p + 1] < sched_off[p]) return ctx->fail(STARK_ERR_INVALID_ARG, "sched_off must not decrease");
+    if (!schedule && sched_off[batch] != sched_off[0]) return ctx->fail(STARK_ERR_INVALID_ARG, "null schedule with a fold");
+    for (size_t p = 0; p < batch; ++p) {
+        if (!is_pow2(n0[p]) || n0[p] <= 1) return ctx->fail(STARK_ERR_INVALID_ARG, "n0 must be a power of two above 1 (radix-2 domain), trace " + std::to_string(p));
+        const size_t L = sched_off[p + 1] - sched_off[p]; std::vector<size_t> n, arity;
+        STARK_TRY(layers_or_fail(ctx, n0[p], L ? schedule + sched_off[p] : nullptr, L, n, arity));
+    }
+    return prove_mixed_batch_impl(ctx, batch, a, s, e, t, n0, schedule, sched_off, r, seed_z, out);
 }
 int32_t stark_deep_fri_prove_f0_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out) {
     if (out) for (size_t p = 0; p < batch; ++p) out[p] = nullptr;

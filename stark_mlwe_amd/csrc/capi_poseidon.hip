@@ -34,8 +34,10 @@ static inline size_t poseidon_lds(int t, int block) { return (size_t)t * 32 * bl
 // batches on the one-wave / wave-pair kernels (comparison).
 // The mapping is kept exactly as measured, including where operations differ: under "sponge_one_wave" a Merkle level of <= 4096 nodes runs one wave per
 // node but a leaf layer of <= 4096 leaves the wave pair, and the column sponges ignore "poseidon_lane_only".
+// RaggedSponges (stark_tr_hash_many_dev: items of any tag and length in one launch) selects as the column sponges do, whatever the count — a
+// ragged launch is for chains — except that it honours "poseidon_lane_only", so that the lane form of the layout can be run.
 enum class PoseidonForm { Lane, WavePair, OneWave, FiveWave, Wide };
-enum class PoseidonOp { MerkleLevel, LeafLayer, TrHash, ColumnSponges, DeviceTranscript };
+enum class PoseidonOp { MerkleLevel, LeafLayer, TrHash, ColumnSponges, RaggedSponges, DeviceTranscript };
 constexpr size_t kChainMaxNodes = 256, kChainMaxLeaves = 2048, kChainMaxSponges = 512, kCoopMaxNodes = 4096, kCoopMaxLeaves = 4096, kCoopMaxSponges = 4096;
 static PoseidonForm poseidon_form(const stark_ctx* ctx, const stark_params* p, PoseidonOp op, size_t n) {
     const PoseidonDev& d = p->dev;
@@ -56,6 +58,9 @@ static PoseidonForm poseidon_form(const stark_ctx* ctx, const stark_params* p, P
     case PoseidonOp::TrHash:
         if (chain && n <= kChainMaxSponges) return PoseidonForm::FiveWave;
         return !lane_only && n <= kCoopMaxSponges ? PoseidonForm::OneWave : PoseidonForm::Lane;
+    case PoseidonOp::RaggedSponges:
+        if (lane_only) return PoseidonForm::Lane;
+        [[fallthrough]];
     case PoseidonOp::ColumnSponges:
         return d.chain_a && !one_wave ? PoseidonForm::FiveWave : PoseidonForm::OneWave;
     case PoseidonOp::DeviceTranscript:                                  // n instances advanced by one launch; up to two resident five-wave workgroups per CU, as for TrHash
@@ -113,16 +118,21 @@ static int32_t tr_frame(stark_ctx* ctx, const char* tag, fr_t** dev, int* np, in
     *dev = it->second.fr(); *np = ctx->tr_frame_dims[key].first; *ns = ctx->tr_frame_dims[key].second; return STARK_OK;
 }
 static int32_t launch_tr_hash(stark_ctx* ctx, stark_params* tp, PoseidonForm form, const TrStream& T, fr_t* out_dev) {
+    const bool ragged = T.layout == TrStream::Ragged;
     switch (form) {
     case PoseidonForm::FiveWave:
-        hipLaunchKernelGGL(k_tr_hash_chain, dim3((unsigned)T.n), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, T, row_consts_of(ctx), out_dev); break;
+        if (ragged) hipLaunchKernelGGL(k_tr_hash_chain_ragged, dim3((unsigned)T.n), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, T, row_consts_of(ctx), out_dev);
+        else hipLaunchKernelGGL(k_tr_hash_chain, dim3((unsigned)T.n), dim3(320), chain_lds_bytes(), ctx->stream, tp->dev, T, row_consts_of(ctx), out_dev);
+        break;
     case PoseidonForm::OneWave:
-        if (T.layout == TrStream::Equal) hipLaunchKernelGGL(k_tr_hash_coop<false>, dim3((unsigned)T.n), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T, out_dev);
+        if (ragged) hipLaunchKernelGGL((k_tr_hash_coop<true, true>), dim3((unsigned)T.n), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T, out_dev);
+        else if (T.layout == TrStream::Equal) hipLaunchKernelGGL(k_tr_hash_coop<false>, dim3((unsigned)T.n), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T, out_dev);
         else hipLaunchKernelGGL(k_tr_hash_coop<true>, dim3((unsigned)T.n), dim3(64), coop_lds_bytes(17), ctx->stream, tp->dev, T, out_dev);
         break;
     default: {
         const int block = 64;
-        hipLaunchKernelGGL(k_tr_hash, dim3((unsigned)((T.n + block - 1) / block)), dim3(block), poseidon_lds(17, block), ctx->stream, tp->dev, T, out_dev);
+        if (ragged) hipLaunchKernelGGL(k_tr_hash_ragged, dim3((unsigned)((T.n + block - 1) / block)), dim3(block), poseidon_lds(17, block), ctx->stream, tp->dev, T, out_dev);
+        else hipLaunchKernelGGL(k_tr_hash, dim3((unsigned)((T.n + block - 1) / block)), dim3(block), poseidon_lds(17, block), ctx->stream, tp->dev, T, out_dev);
     } }
     STARK_HIP(ctx, hipGetLastError());
     return STARK_OK;
@@ -150,6 +160,21 @@ int32_t tr_hash_columns4_dev(stark_ctx* ctx, const char* const tags[4], const fr
 }
 int32_t tr_hash_columns_batch_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const* ptrs_dev, size_t batch, size_t n0, fr_t* out_dev) {
     return tr_hash_columns(ctx, tags, nullptr, ptrs_dev, 4 * batch, n0, out_dev);
+}
+// n sponges of any tags and lengths in ONE launch (the Ragged layout of TrStream): out_dev[i] = tr_hash_fields_tagged(tags[i], fields[i][0 .. k[i])),
+// fields a host table of device pointers (an entry with k[i] == 0 is not read and may be null).  The frames come from the per-tag cache (the first
+// use of a tag uploads its frame and synchronises, as everywhere); the items go up staged, so nothing else synchronises.  column_sponges: select the
+// kernel form as the column sponges of build_f0 do (the mixed-size prover); otherwise as PoseidonOp::RaggedSponges.
+int32_t tr_hash_many_dev(stark_ctx* ctx, size_t n, const char* const* tags, const fr_t* const* fields, const size_t* k, fr_t* out_dev, bool column_sponges) {
+    stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
+    std::vector<TrFrameRef> fr(n);
+    for (size_t i = 0; i < n; ++i) { fr_t* frame = nullptr; STARK_TRY(tr_frame(ctx, tags[i], &frame, &fr[i].np, &fr[i].ns)); fr[i].frame = frame; }
+    if (n == 0) return STARK_OK;
+    if (n > 0x7fffffffu) return ctx->fail(STARK_ERR_UNSUPPORTED, "tr_hash_many: more than 2^31 - 1 items in one call");
+    const std::vector<TrStream::Item> items = tr_ragged_items(fr.data(), fields, k, n);
+    DevBuf d; STARK_HIP(ctx, d.alloc(ctx, n * sizeof(TrStream::Item))); STARK_TRY(ctx_upload_staged(ctx, d.p, items.data(), n * sizeof(TrStream::Item)));
+    const TrStream T = tr_ragged_stream((const TrStream::Item*)d.p, n, host::h_tag("FSv1-TRANSCRIPT-INIT"));
+    return launch_tr_hash(ctx, tp, poseidon_form(ctx, tp, column_sponges ? PoseidonOp::ColumnSponges : PoseidonOp::RaggedSponges, n), T, out_dev);
 }
 int32_t tr_hash_host1(stark_ctx* ctx, const char* tag, const std::vector<fr_t>& fields, fr_t* out) {
     DevBuf in, o; STARK_HIP(ctx, in.upload(ctx, fields.data(), fields.size() * sizeof(fr_t))); STARK_HIP(ctx, o.alloc(ctx, sizeof(fr_t)));
@@ -276,7 +301,7 @@ static void ds_attrs() {
 void stark::poseidon_set_attrs() {
     ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>(); ds_attrs<DsBatchPairPtrStream>();
     for (const void* k : {(const void*)k_leaf_pair, (const void*)k_permute_batch, (const void*)k_tr_hash, (const void*)k_hash_stream, (const void*)k_leaf_pair2<false>, (const void*)k_leaf_pair2<true>, (const void*)k_node16_pair<false>, (const void*)k_node16_pair<true>,
-                          (const void*)k_tr_hash_chain, (const void*)k_leaf_pair_chain, (const void*)k_tr_stream_chain, (const void*)k_tr_batch_chain})
+                          (const void*)k_tr_hash_chain, (const void*)k_tr_hash_chain_ragged, (const void*)k_tr_hash_ragged, (const void*)k_leaf_pair_chain, (const void*)k_tr_stream_chain, (const void*)k_tr_batch_chain})
         lds_attr(k);
 }
 extern "C" {
@@ -355,6 +380,21 @@ int32_t stark_tr_hash_fields_tagged(stark_ctx_t* ctx, stark_params_t* tp, const 
     DevBuf di, dout; STARK_HIP(ctx, di.upload(ctx, fields, n * k * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n * sizeof(fr_t)));
     STARK_TRY(stark_tr_hash_fields_tagged_dev(ctx, tp, tag, (const uint64_t*)di.p, k, n, (uint64_t*)dout.p));
     STARK_HIP(ctx, dout.download_sync(out, n * sizeof(fr_t))); return STARK_OK;
+}
+int32_t stark_tr_hash_many_dev(stark_ctx_t* ctx, size_t n, const char* const* tags, const uint64_t* const* fields, const size_t* k, uint64_t* out) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!n) return STARK_OK;
+    if (!tags || !k || !out) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + n * sizeof(fr_t);
+    for (size_t i = 0; i < n; ++i) {
+        if (!tags[i]) return ctx->fail(STARK_ERR_INVALID_ARG, "tr_hash_many: null tag " + std::to_string(i));
+        if (!k[i]) continue;
+        if (!fields || !fields[i]) return ctx->fail(STARK_ERR_INVALID_ARG, "tr_hash_many: null fields with k > 0, item " + std::to_string(i));
+        const uintptr_t f0 = (uintptr_t)fields[i];
+        if (f0 < o1 && o0 < f0 + k[i] * sizeof(fr_t)) return ctx->fail(STARK_ERR_INVALID_ARG, "tr_hash_many: out overlaps the fields of item " + std::to_string(i));
+    }
+    return tr_hash_many_dev(ctx, n, tags, reinterpret_cast<const fr_t* const*>(fields), k, as_fr(out), false);
 }
 
 // ---- Merkle ------------------------------------------------------------------------------------------

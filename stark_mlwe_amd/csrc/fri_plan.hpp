@@ -58,6 +58,24 @@ inline const char* layer_shape_text(LayerShape s) {
     return s == LayerShape::empty_layer ? "empty layer" : s == LayerShape::not_dividing ? "schedule not dividing domain size" : s == LayerShape::arity_one ? "layer with arity 1" : "";
 }
 
+// The groups of a mixed-size batch prove (stark_deep_fri_prove_mixed_batch_dev): traces of equal (n0, schedule, r) form a group and share the tail of
+// the equal-shape batch.  Groups in order of first appearance, the traces of a group in the caller's order; trace i folds by
+// schedule[sched_off[i] .. sched_off[i + 1]).  Equal n0 under another schedule or another r is another group.
+inline std::vector<std::vector<size_t>> mixed_prove_groups(size_t B, const size_t* n0, const size_t* schedule, const size_t* sched_off, const size_t* r) {
+    std::vector<std::vector<size_t>> groups;
+    for (size_t i = 0; i < B; ++i) {
+        const size_t Li = sched_off[i + 1] - sched_off[i];
+        size_t g = 0;
+        for (; g < groups.size(); ++g) {
+            const size_t j = groups[g][0];
+            if (n0[j] == n0[i] && r[j] == r[i] && sched_off[j + 1] - sched_off[j] == Li && std::equal(schedule + sched_off[i], schedule + sched_off[i] + Li, schedule + sched_off[j])) break;
+        }
+        if (g == groups.size()) groups.emplace_back();
+        groups[g].push_back(i);
+    }
+    return groups;
+}
+
 // Shapes of the L+1 committed layers: sizes, Merkle arities, leaf kinds, level lengths; plus the roots.
 struct FriShape {
     size_t n0 = 0; std::vector<size_t> schedule, n, arity; std::vector<char> hashed;

@@ -396,6 +396,37 @@ int hc_tr_hash(void* tparams, const char* tag, const uint64_t* fields, size_t k,
     for (size_t i = 0; i < n; ++i) { ArrayState s{st}; st4(out + 4 * i, tr_hash_body(s, P->dev, T, i)); }
     return 0;
 }
+// the frame of a tag (host::tr_hash_frame): np elements in front of the fields, ns behind them
+int hc_tr_frame_dims(const char* tag, int* np, int* ns) { std::vector<fr_t> fr; *np = host::tr_hash_frame(tag, fr); *ns = (int)fr.size() - *np; return 0; }
+// stark_tr_hash_many_dev on the host: tr_hash_body over the Ragged stream that tr_ragged_items builds for the device driver, in its launch order,
+// each digest to its item's out slot.  fields: n host pointers (null allowed iff k[i] == 0).  launch_order (optional, n): the caller's index of launch slot j.
+int hc_tr_hash_many(void* tparams, size_t n, const char* const* tags, const uint64_t* const* fields, const size_t* k, uint64_t* out, size_t* launch_order) {
+    HcParams* P = (HcParams*)tparams;
+    std::vector<std::vector<fr_t>> frames(n), fl(n); std::vector<TrFrameRef> fr(n); std::vector<const fr_t*> fp(n, nullptr);
+    for (size_t i = 0; i < n; ++i) {
+        const int np = host::tr_hash_frame(tags[i], frames[i]); fr[i] = TrFrameRef{frames[i].data(), np, (int)frames[i].size() - np};
+        if (!k[i]) continue;
+        if (!fields || !fields[i]) return -1;
+        fl[i].resize(k[i]); for (size_t q = 0; q < k[i]; ++q) fl[i][q] = ld4(fields[i] + 4 * q);
+        fp[i] = fl[i].data();
+    }
+    const std::vector<TrStream::Item> items = tr_ragged_items(fr.data(), fp.data(), k, n);
+    const TrStream T = tr_ragged_stream(items.data(), n, host::h_tag("FSv1-TRANSCRIPT-INIT"));
+    fr_t st[17];
+    for (size_t j = 0; j < n; ++j) {
+        ArrayState s{st}; size_t slot = n; const fr_t d = tr_hash_body<true>(s, P->dev, T, j, &slot);
+        if (slot >= n) return -2;
+        st4(out + 4 * slot, d); if (launch_order) launch_order[j] = slot;
+    }
+    return 0;
+}
+// mixed_prove_groups (fri_plan.hpp): group_of[i] = the group of trace i, order = the traces group by group; returns the number of groups
+size_t hc_mixed_prove_groups(size_t B, const size_t* n0, const size_t* schedule, const size_t* sched_off, const size_t* r, size_t* group_of, size_t* order) {
+    const std::vector<std::vector<size_t>> G = mixed_prove_groups(B, n0, schedule, sched_off, r);
+    size_t pos = 0;
+    for (size_t g = 0; g < G.size(); ++g) for (size_t i : G[g]) { group_of[i] = g; order[pos++] = i; }
+    return G.size();
+}
 int hc_hash_stream(void* params, int mode, const uint64_t* a, size_t na, const uint64_t* b, size_t nb, const uint64_t* tag, size_t n, uint64_t* out) {
     HcParams* P = (HcParams*)params;
     std::vector<fr_t> av(n * na), bv(n * nb), st(P->dev.t);

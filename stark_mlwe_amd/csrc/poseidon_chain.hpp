@@ -424,6 +424,12 @@ __global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))
     const TrStream::Sponge sp = T.sponge(blockIdx.x);
     chain_sponge(P, RK, lds, sp.total(), T.cap, [&](size_t q) -> fr_t { return sp.elem(q); }, out + blockIdx.x);
 }
+// The Ragged layout: workgroup b runs items[b], whatever its tag and length, and writes out[items[b].out].
+__global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_hash_chain_ragged(PoseidonDev P, TrStream T, row::Consts RK, fr_t* __restrict__ out) {
+    extern __shared__ uint4 lds[];
+    size_t slot; const TrStream::Sponge sp = T.sponge_as<true>(blockIdx.x, &slot);
+    chain_sponge(P, RK, lds, sp.total(), T.cap, [&](size_t q) -> fr_t { return sp.elem(q); }, out + slot);
+}
 
 // SMALL Merkle levels and leaf layers, where the launch is one permutation's latency whatever the kernel: the same five waves per NODE (72 us per
 // permutation against 142 us on one wave and ~0.4 ms in the wave-pair throughput form).

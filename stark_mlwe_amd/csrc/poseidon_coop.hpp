@@ -216,12 +216,14 @@ __device__ __forceinline__ fr_t coop_permute(fr_t s, const PoseidonDev& P, const
 // PREFETCH: the next rate block is loaded BEFORE the permutation, so that its HBM latency hides under it — the long column sponges (the
 // Columns / BatchColumns layouts).  It costs registers (189 VGPRs against 162): the Equal layout (many short sponges) launches the
 // instantiation without it, which keeps 3 waves per SIMD up to 4096 sponges.
-template <bool PREFETCH>
+// RAGGED: the stream's Ragged layout (sponge b is items[b], its digest goes to out[items[b].out]) — instantiations of their own, so the
+// kernels of the older layouts are the code they were.
+template <bool PREFETCH, bool RAGGED = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_hash_coop(PoseidonDev P, TrStream T, fr_t* __restrict__ out) {
     extern __shared__ uint4 lds[];
     CoopLds L = coop_setup<17>(lds, P);
-    const int lane = threadIdx.x; const size_t b = blockIdx.x;
-    const TrStream::Sponge sp = T.sponge(b); const size_t total = sp.total();
+    const int lane = threadIdx.x; size_t b = blockIdx.x;
+    const TrStream::Sponge sp = T.sponge_as<RAGGED>(blockIdx.x, &b); const size_t total = sp.total();
     fr_t s = lane == 16 ? T.cap : fr_zero<PF>();
     auto fetch = [&](size_t base) -> fr_t {                                                // this lane's element of the rate block starting at `base`
         const size_t e = base + lane;

@@ -140,10 +140,11 @@ template <class S, class DS> FR_HD fr_t hash_ds_body(const S& s, const PoseidonD
     return res;
 }
 // Transcript-style duplex (t=17, rate 16, lazy permute: only before absorbing more, once at the end), state[16] = cap.
-template <class S> FR_HD fr_t tr_hash_body(const S& s, const PoseidonDev& P, const TrStream& T, size_t i) {
+// RAGGED: the stream's Ragged layout (sponge i is items[i], digest to *slot = items[i].out; otherwise *slot = i).
+template <bool RAGGED, class S> FR_HD fr_t tr_hash_body(const S& s, const PoseidonDev& P, const TrStream& T, size_t i, size_t* slot) {
     for (int j = 0; j < 16; ++j) s.st(j, fr_zero<PF>());
     s.st(16, T.cap);
-    const TrStream::Sponge sp = T.sponge(i);
+    const TrStream::Sponge sp = T.sponge_as<RAGGED>(i, slot);
     int pos = 0;
     for (size_t q = 0; q < sp.total(); ++q) {
         const fr_t x = sp.elem(q);
@@ -152,6 +153,7 @@ template <class S> FR_HD fr_t tr_hash_body(const S& s, const PoseidonDev& P, con
     }
     return permute_core(s, P, true);
 }
+template <class S> FR_HD fr_t tr_hash_body(const S& s, const PoseidonDev& P, const TrStream& T, size_t i) { size_t slot; return tr_hash_body<false>(s, P, T, i, &slot); }
 // Active instance a of a TrBatchStream: the stored (or reset) state, the lazy permute before absorbing into a full rate, one permutation
 // and squeeze per finished segment; state and cursor written back.
 template <class S> FR_HD void tr_batch_body(const S& s, const PoseidonDev& P, const TrBatchStream& T, size_t a) {
@@ -244,6 +246,17 @@ __global__ void __launch_bounds__(64) k_tr_hash(PoseidonDev P, TrStream T, fr_t*
     if (i >= T.n) return;
     LdsState s{lds, (int)blockDim.x, (int)threadIdx.x};
     stg(out + i, tr_hash_body(s, P, T, i));
+}
+// The Ragged layout, one lane per item.  The lanes of a wave have different lengths and simply leave the absorb loop at different times:
+// permute_core over LdsState is lane-local (no shuffle, DPP move or barrier; each lane reads and writes its own LDS column), so a lane that
+// is done waits masked off while its neighbours go on.  The driver's longest-first order keeps the lengths within a wave close.
+__global__ void __launch_bounds__(64) k_tr_hash_ragged(PoseidonDev P, TrStream T, fr_t* __restrict__ out) {
+    extern __shared__ uint4 lds[];
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T.n) return;
+    LdsState s{lds, (int)blockDim.x, (int)threadIdx.x};
+    size_t slot; const fr_t d = tr_hash_body<true>(s, P, T, i, &slot);
+    stg(out + slot, d);
 }
 __global__ void __launch_bounds__(64) k_hash_stream(PoseidonDev P, int mode, const fr_t* __restrict__ a, size_t na, const fr_t* __restrict__ b, size_t nb,
                                                     fr_t tag, size_t n, fr_t* __restrict__ out) {

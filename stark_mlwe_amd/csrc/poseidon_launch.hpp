@@ -29,6 +29,8 @@ int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, siz
 int32_t tr_hash_dev(stark_ctx* ctx, const char* tag, const fr_t* fields_dev, size_t k, size_t n, fr_t* out_dev);
 int32_t tr_hash_columns4_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const cols[4], size_t n0, fr_t* out4_dev);
 int32_t tr_hash_columns_batch_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const* ptrs_dev, size_t batch, size_t n0, fr_t* out_dev);
+// n sponges of any tags and lengths in one launch (TrStream's Ragged layout); tags, fields (device pointers; null allowed iff k[i] == 0) and k on the host
+int32_t tr_hash_many_dev(stark_ctx* ctx, size_t n, const char* const* tags, const fr_t* const* fields, const size_t* k, fr_t* out_dev, bool column_sponges);
 int32_t tr_hash_host1(stark_ctx* ctx, const char* tag, const std::vector<fr_t>& fields, fr_t* out);   // one hash, host in/out
 
 // One device-resident streaming transcript (17 elements at `state`, rate cursor *pos) on the context's stream: absorbs the n device fields, then

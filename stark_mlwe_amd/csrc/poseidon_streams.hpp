@@ -5,6 +5,9 @@
 // one-wave (poseidon_coop.hpp), wave-pair (poseidon_pair.hpp), five-wave (poseidon_chain.hpp) and wide (poseidon_wave.hpp) kernels all read
 // their inputs through these types; only the absorb schedule (eager or lazy permute) and the arithmetic differ between them.
 #pragma once
+#include <algorithm>
+#include <numeric>
+#include <vector>
 #include "fr.hpp"
 #include "dev_common.hpp"
 
@@ -151,11 +154,16 @@ struct TrBatchStream {
 //   Equal        : n sponges of k[0] fields at fields[0] + b * k[0], all under column 0's frame (one tag)
 //   Columns      : sponge b < 4 is column b, fields[b] (k[b] of them)
 //   BatchColumns : sponge b is column b & 3 of trace b >> 2, its k[b & 3] fields at batch[b] (a device array of device pointers)
+//   Ragged       : sponge b is items[b] (a device array): its own frame, fields, length and output slot, so every sponge of a launch may have
+//                  another tag and another length.  The kernels of this layout are instantiations of their own (sponge_as<true>(b, &slot), not sponge(b)) and write
+//                  digest b to out[items[b].out]; the other layouts keep out[b].  k == 0 is an item like any other: it hashes the frame alone and
+//                  its fields pointer (which may be null) is never read.
 struct TrStream {
-    enum Layout { Equal, Columns, BatchColumns };
+    enum Layout { Equal, Columns, BatchColumns, Ragged };
+    struct Item { const fr_t* prefix; const fr_t* suffix; const fr_t* fields; uint32_t np, ns; uint64_t k, out; };
     Layout layout; size_t n;
     const fr_t* prefix[4]; int np[4]; const fr_t* suffix[4]; int ns[4]; const fr_t* fields[4]; size_t k[4];
-    const fr_t* const* batch; fr_t cap;
+    const fr_t* const* batch; fr_t cap; const Item* items;
     // n sponges of k fields each under one frame (frame = prefix || suffix, np + ns elements)
     static inline TrStream equal(const fr_t* frame, int np, int ns, const fr_t* fields, size_t k, size_t n, const fr_t& cap) {
         TrStream T{}; T.layout = Equal; T.n = n; T.cap = cap; T.batch = nullptr;
@@ -173,7 +181,36 @@ struct TrStream {
         const fr_t* f = layout == Equal ? fields[0] + b * k[0] : (layout == Columns ? fields[b] : batch[b]);
         return Sponge{prefix[c], f, suffix[c], (size_t)np[c], k[c], (size_t)np[c] + k[c] + (size_t)ns[c]};
     }
+    // the Ragged layout: ONE load of the item per workgroup or lane, then the same view
+    FR_HD static Sponge sponge_of(const Item& it) { return Sponge{it.prefix, it.fields, it.suffix, (size_t)it.np, (size_t)it.k, (size_t)it.np + (size_t)it.k + (size_t)it.ns}; }
+    template <bool RAGGED> FR_HD Sponge sponge_as(size_t b, size_t* slot) const {
+        if (RAGGED) { const Item it = items[b]; *slot = (size_t)it.out; return sponge_of(it); }
+        *slot = b; return sponge(b);
+    }
 };
+
+// The items of a Ragged launch, built once for the device driver (capi_poseidon.hip) and its host twin (hostcheck.cpp): sponge i of the caller
+// absorbs frames[i] around fields[i][0 .. k[i]) and writes slot i.  Workgroups are dispatched in index order, so the items go LONGEST FIRST (by
+// absorbed length, ties by the caller's index): a long chain never starts behind short ones once a launch exceeds what is resident, and the 64
+// lanes of a wave of the lane form get neighbouring lengths.  `out` restores the caller's order.
+struct TrFrameRef { const fr_t* frame; int np, ns; };
+inline std::vector<size_t> tr_ragged_order(const TrFrameRef* frames, const size_t* k, size_t n) {
+    std::vector<size_t> ord(n); std::iota(ord.begin(), ord.end(), (size_t)0);
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return (size_t)frames[x].np + k[x] + (size_t)frames[x].ns > (size_t)frames[y].np + k[y] + (size_t)frames[y].ns; });
+    return ord;
+}
+inline std::vector<TrStream::Item> tr_ragged_items(const TrFrameRef* frames, const fr_t* const* fields, const size_t* k, size_t n) {
+    const std::vector<size_t> ord = tr_ragged_order(frames, k, n);
+    std::vector<TrStream::Item> items(n);
+    for (size_t j = 0; j < n; ++j) {
+        const size_t i = ord[j]; const TrFrameRef& f = frames[i];
+        items[j] = TrStream::Item{f.frame, f.frame + f.np, k[i] ? fields[i] : nullptr, (uint32_t)f.np, (uint32_t)f.ns, (uint64_t)k[i], (uint64_t)i};
+    }
+    return items;
+}
+inline TrStream tr_ragged_stream(const TrStream::Item* items, size_t n, const fr_t& cap) {
+    TrStream T{}; T.layout = TrStream::Ragged; T.n = n; T.cap = cap; T.batch = nullptr; T.items = items; return T;
+}
 
 // hash_leaf_pair(f_i, s_i) (fri.rs:38-44): ONE t = 17 permutation of the template `init` (capi_poseidon.hip ctx_leaf_init)
 // with elements 4, 5 = (f[i], s_i), s_i = f_next[i / m] (zero when f_next == nullptr: fri.rs:266).  Elements 0..8 are the absorbed ones,
