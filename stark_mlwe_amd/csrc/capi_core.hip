@@ -106,7 +106,7 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
     size_t o_rcf = put(k.rc_full), o_rcp = put(k.rc_partial), o_lu = put(k.lu), o_pre = put(k.lu_pre), o_row0 = put(k.row0), o_sp = put(k.sparse), o_mds = put(k.mds), o_mpre = put(k.mds_pre), o_gam = put(k.gamma);
     // radix-2^29 multiplier tables (fr29.hpp), appended to the same device blob as raw words
     const size_t o_29 = blob.size();
-    { std::vector<uint32_t> w29; for (auto* v : {&k.lu29, &k.lu_pre29, &k.row0_29, &k.sparse29, &k.gamma29, &k.mds29, &k.mds_pre29, &k.chain_a, &k.chain_g, &k.chain_w}) w29.insert(w29.end(), v->begin(), v->end());
+    { std::vector<uint32_t> w29; for (auto* v : {&k.lu29, &k.lu_pre29, &k.row0_29, &k.sparse29, &k.gamma29, &k.mds29, &k.mds_pre29, &k.chain_a, &k.chain_g, &k.chain_w, &k.rc_full29}) w29.insert(w29.end(), v->begin(), v->end());
       while (w29.size() % 8) w29.push_back(0);
       blob.resize(o_29 + w29.size() / 8); memcpy((void*)(blob.data() + o_29), w29.data(), w29.size() * 4); }
     // int8 MFMA fragments of the dense matrices (t = 17), raw bytes in the same blob
@@ -128,7 +128,8 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
       P->dev.sparse29 = P->dev.row0_29 + k.row0_29.size(); P->dev.gamma29 = P->dev.sparse29 + k.sparse29.size();
       P->dev.mds29 = P->dev.gamma29 + k.gamma29.size(); P->dev.mds_pre29 = P->dev.mds29 + k.mds29.size();
       const uint32_t* ch = P->dev.mds_pre29 + k.mds_pre29.size();
-      P->dev.chain_a = k.chain_a.empty() ? nullptr : ch; P->dev.chain_g = k.chain_a.empty() ? nullptr : ch + k.chain_a.size(); P->dev.chain_w = k.chain_a.empty() ? nullptr : ch + k.chain_a.size() + k.chain_g.size(); }
+      P->dev.chain_a = k.chain_a.empty() ? nullptr : ch; P->dev.chain_g = k.chain_a.empty() ? nullptr : ch + k.chain_a.size(); P->dev.chain_w = k.chain_a.empty() ? nullptr : ch + k.chain_a.size() + k.chain_g.size();
+      P->dev.rc_full29 = ch + k.chain_a.size() + k.chain_g.size() + k.chain_w.size(); }
     P->dev.blk8_efrag = k.blk8_efrag.empty() ? nullptr : (const void*)(dev + o_b8); P->dev.blk8_lfrag = k.blk8_efrag.empty() ? nullptr : (const void*)(dev + o_b8 + ef_elems);
     P->dev.blk8_gfrag = k.blk8_gfrag.empty() ? nullptr : (const void*)(dev + o_b8 + ef_elems + lf_elems);
     P->dev.blk8_unit_frag = k.blk8_efrag.empty() ? nullptr : (const void*)((const int8_t*)P->dev.blk8_lfrag + k.blk8_lfrag.size() - 1024);

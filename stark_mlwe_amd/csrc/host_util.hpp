@@ -214,6 +214,7 @@ struct KernelConsts {
     // the multiplier tables of every dot product again, as nine 29-bit limbs of c*2^261 mod r per entry (fr29.hpp)
     std::vector<uint32_t> lu29, lu_pre29, row0_29, sparse29, gamma29;
     std::vector<uint32_t> mds29, mds_pre29;   // dense forms for the one-wave kernel (every entry meets an S-box output: all scaled)
+    std::vector<uint32_t> rc_full29;          // rf*t*9: fr29_unpack of every full-round constant as stored (an addend, not a multiplier: no R' factor, no scale)
     // t = 17 only: the dense matrices as int8 MFMA operand fragments (signed radix-256 digits of the residue tables), see mfma_frags
     std::vector<int8_t> mds_frag, mds_pre_frag;
     // t = 17 only: the partial rounds UNROLLED over all rp rounds for the five-wave latency kernel (poseidon_chain.hpp):
@@ -343,6 +344,8 @@ inline KernelConsts make_kernel_consts(const PoseidonConsts& c) {
     k.lu29 = to_radix29(k.lu, upper); k.lu_pre29 = to_radix29(k.lu_pre, upper); k.row0_29 = to_radix29(k.row0, all);
     k.sparse29 = to_radix29(k.sparse, a_and_w); k.gamma29 = to_radix29(k.gamma, all);
     k.mds29 = to_radix29(k.mds, all); k.mds_pre29 = to_radix29(k.mds_pre, all);
+    k.rc_full29.resize(k.rc_full.size() * 9);
+    for (size_t i = 0; i < k.rc_full.size(); ++i) { const fr29_t u = fr29_unpack(k.rc_full[i]); for (int j = 0; j < 9; ++j) k.rc_full29[9 * i + j] = u.l[j]; }
     if (t == 17) { k.mds_frag = mfma_frags(k.mds, t); k.mds_pre_frag = mfma_frags(k.mds_pre, t); }      // the wave-pair kernels' full rounds (poseidon_pair.hpp)
     if (t == 17 && c.rp % 8 == 0) {                                                                      // blocks of 8 partial rounds on the matrix cores (poseidon_pair.hpp)
         const int nb = c.rp / 8, w = 2 * t - 1;

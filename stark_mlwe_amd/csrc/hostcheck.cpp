@@ -40,7 +40,7 @@ static void bind(HcParams* P) {
     P->kc = host::make_kernel_consts(P->ref);
     P->dev.t = P->kc.t; P->dev.rf = P->kc.rf; P->dev.rp = P->kc.rp; P->dev.rc_full = P->kc.rc_full.data(); P->dev.rc_partial = P->kc.rc_partial.data();
     P->dev.lu = P->kc.lu.data(); P->dev.lu_pre = P->kc.lu_pre.data(); P->dev.row0 = P->kc.row0.data(); P->dev.sparse = P->kc.sparse.data(); P->dev.mds = P->kc.mds.data(); P->dev.mds_pre = P->kc.mds_pre.data(); P->dev.gamma = P->kc.gamma.data();
-    P->dev.lu29 = P->kc.lu29.data(); P->dev.lu_pre29 = P->kc.lu_pre29.data(); P->dev.row0_29 = P->kc.row0_29.data(); P->dev.sparse29 = P->kc.sparse29.data(); P->dev.gamma29 = P->kc.gamma29.data(); P->dev.mds29 = P->kc.mds29.data(); P->dev.mds_pre29 = P->kc.mds_pre29.data();
+    P->dev.lu29 = P->kc.lu29.data(); P->dev.lu_pre29 = P->kc.lu_pre29.data(); P->dev.row0_29 = P->kc.row0_29.data(); P->dev.sparse29 = P->kc.sparse29.data(); P->dev.gamma29 = P->kc.gamma29.data(); P->dev.mds29 = P->kc.mds29.data(); P->dev.mds_pre29 = P->kc.mds_pre29.data(); P->dev.rc_full29 = P->kc.rc_full29.data();
     P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr; P->dev.blk8_efrag = nullptr; P->dev.blk8_lfrag = nullptr; P->dev.blk8_unit_frag = nullptr; P->dev.blk8_gfrag = nullptr;
     P->dev.chain_a = P->kc.chain_a.empty() ? nullptr : P->kc.chain_a.data(); P->dev.chain_g = P->kc.chain_g.empty() ? nullptr : P->kc.chain_g.data(); P->dev.chain_w = P->kc.chain_w.empty() ? nullptr : P->kc.chain_w.data();
 }
@@ -230,6 +230,36 @@ int hc_mfma_finish(const int32_t* sums, size_t n, uint64_t* out) {
     }
     return 0;
 }
+// The finishing step stopped at its nine limbs (mfma_finish_limbs: what a fused row hands to the next S-box): n cases of 32 digit sums -> 9 x u32 each,
+// W == sum_c S_c 256^c (mod r), 0 < W < 3r, limbs 0..7 below 2^29 and the top limb below 2^24; -1 when a sum is outside the domain
+int hc_mfma_finish_limbs(const int32_t* sums, size_t n, uint32_t* out) {
+    for (size_t s = 0; s < n; ++s) {
+        const int32_t* S = sums + 32 * s;
+        for (int c = 0; c < 32; ++c) if (S[c] >= (1 << 24) || S[c] <= -(1 << 24)) return -1;
+        int32_t lo[16], hi[16];
+        for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
+        int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
+        mfma_fold_rows(col, lo, hi);
+        mfma_finish_limbs(col, out + 9 * s);
+    }
+    return 0;
+}
+// The S-box on lazy limbs (mfma_digits.hpp sbox_lazy29, the kernels' 64-bit columns): n cases of limbs l (9 x u32, below 2^29, top below 2^24) and an
+// addend c (9 x u32, below 2^29, top below 2^23) -> the canonical fr_pow5_r29 of (l + c) mod r.  colmax (optional, two u64 per case: low, high): the
+// largest column value of the same steps in 128-bit arithmetic.  -1: a limb outside the domain; -2: the 64-bit and the 128-bit columns disagree.
+int hc_sbox_lazy29(const uint32_t* l, const uint32_t* c, size_t n, uint64_t* out, uint64_t* colmax) {
+    for (size_t s = 0; s < n; ++s) {
+        const uint32_t* ls = l + 9 * s; const uint32_t* cs = c + 9 * s;
+        for (int i = 0; i < 9; ++i) if (ls[i] >= (i < 8 ? 1u << 29 : 1u << 24) || cs[i] >= (i < 8 ? 1u << 29 : 1u << 23)) return -1;
+        const fr_t z = sbox_lazy29(ls, cs);
+        Lazy29Wide wide; const fr29_t x5 = wide.pow5(ls, cs);
+        const fr_t zw = fr29_pack_reduce<PF>(x5.l);
+        if (colmax) { colmax[2 * s] = (uint64_t)wide.max_col; colmax[2 * s + 1] = (uint64_t)(wide.max_col >> 64); }
+        if ((wide.max_col >> 64) == 0 && memcmp(&z, &zw, sizeof(fr_t)) != 0) return -2;
+        st4(out + 4 * s, z);
+    }
+    return 0;
+}
 // ---- the 8-round partial blocks of the t = 17 wave-pair kernels (poseidon_pair.hpp pair_block8), mirrored on the host with the tables the device gets ----
 // One emulated 32-row tile: K K-steps, fragment k (1 KiB, host_util.hpp mfma_frag_of: lane l holds A[row l & 31][16 (l >> 5) + j]) against the recoded
 // operand xd[k]; S[row] = sum_k sum_b A_k[row][b] xd_k[b].  -2 when a digit sum leaves the finishing step's domain |S| < 2^24.
@@ -247,11 +277,21 @@ static fr_t blk8_finish_sums(const int32_t* S) {      // the accumulator rows as
     mfma_fold_rows(col, lo, hi);
     return mfma_finish_cols(col);
 }
+static void blk8_finish_sums_limbs(const int32_t* S, uint32_t* l) {      // the same, stopped at the nine limbs (mfma_finish_limbs)
+    int32_t lo[16], hi[16];
+    for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
+    int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
+    mfma_fold_rows(col, lo, hi);
+    mfma_finish_limbs(col, l);
+}
 static int blk8_tile(const int8_t* const* frag, const fr_t* xd, int K, fr_t& out) { int32_t S[32]; const int rc = blk8_tile_sums(frag, xd, K, S); if (rc) return rc; out = blk8_finish_sums(S); return 0; }
 // the largest |digit sum| hc_permute_block8 has seen in a row of 16 + 7 K-steps (the longest tile of the block form) since the last reset
 static std::atomic<int32_t> g_blk8_row23_max{0};
 int32_t hc_blk8_row23_max(int reset) { return reset ? g_blk8_row23_max.exchange(0) : g_blk8_row23_max.load(); }
-// A whole t = 17 permutation in the wave-pair kernels' block-8 form: full rounds through the residue tables of M and B_1 M, the partial rounds in
+// A whole t = 17 permutation in the wave-pair kernels' block-8 form: full rounds through the residue tables of M and B_1 M — every product that is followed
+// by a full round hands its rows over in limb form (finish to limbs, the next round's constant from rc_full29, sbox_lazy29), the products in front of the
+// partial rounds and at the end finish canonical, the first round's S-box stands alone, the last block's lane rows feed the S-box of the round after the partial rounds the same way (element 0 from
+// the chain value) —, the partial rounds in
 // blocks of 8 — lanes recoded, row q = H_q = E_q + sum Gamma y_p as ONE tile of 16 + q K-steps (E fragments against the lanes, blk8_gfrag against the
 // recoded y_0..y_{q-1}), y_q = fr_pow5_r29, a_q y_q from sparse29, lane rows with the unit fragment as the ninth K-step — with blk8_efrag / blk8_gfrag /
 // blk8_lfrag as uploaded.  -1: the set has no block-8 tables; -2: a digit sum out of range.
@@ -260,13 +300,22 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
     if (t != 17 || k.blk8_efrag.empty() || k.blk8_gfrag.empty() || k.mds_frag.empty()) return -1;
     const int8_t* unit = k.blk8_lfrag.data() + k.blk8_lfrag.size() - 1024;
     std::vector<fr_t> st(t), xd(t), o(t);
-    auto full = [&](int r, const std::vector<int8_t>& F) -> int {
-        for (int j = 0; j < t; ++j) xd[j] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(st[j], k.rc_full[(size_t)r * t + j])));
-        for (int i = 0; i < t; ++i) { const int8_t* fr[17]; for (int e = 0; e < t; ++e) fr[e] = &F[((size_t)i * t + e) * 1024]; const int rc = blk8_tile(fr, xd.data(), t, o[i]); if (rc) return rc; }
-        st = o; return 0; };
+    // pair_sbox_full<17, true>: st (canonical) -> xd
+    auto sbox = [&](int r) { for (int j = 0; j < t; ++j) xd[j] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(st[j], k.rc_full[(size_t)r * t + j]))); };
+    // pair_mds_sbox_mfma: xd -> st (canonical) when next < 0, else xd -> xd = the recoded S-box outputs of round `next`
+    auto product = [&](const std::vector<int8_t>& F, int next) -> int {
+        for (int i = 0; i < t; ++i) {
+            const int8_t* fr[17]; for (int e = 0; e < t; ++e) fr[e] = &F[((size_t)i * t + e) * 1024];
+            int32_t S[32]; const int rc = blk8_tile_sums(fr, xd.data(), t, S); if (rc) return rc;
+            if (next < 0) o[i] = blk8_finish_sums(S);
+            else { uint32_t l[9]; blk8_finish_sums_limbs(S, l); o[i] = recode_signed(sbox_lazy29(l, &k.rc_full29[((size_t)next * t + i) * 9])); }
+        }
+        if (next < 0) st = o; else xd = o;
+        return 0; };
     for (size_t s = 0; s < n; ++s) {
         for (int j = 0; j < t; ++j) st[j] = ld4(states + 4 * (s * t + j));
-        for (int r = 0; r < half; ++r) { const int rc = full(r, r == half - 1 ? k.mds_pre_frag : k.mds_frag); if (rc) return rc; }
+        sbox(0);
+        for (int r = 0; r < half; ++r) { const int rc = product(r == half - 1 ? k.mds_pre_frag : k.mds_frag, r == half - 1 ? -1 : r + 1); if (rc) return rc; }
         fr_t s0 = st[0], rec[17], y[8], yd[9], kx[23];
         for (int j = 1; j < t; ++j) rec[j] = recode_signed(st[j]);
         const int nb = k.rp / 8;
@@ -290,12 +339,14 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
             for (int j = 1; j < t; ++j) {
                 const int8_t* fr[9]; for (int p2 = 0; p2 < 8; ++p2) fr[p2] = lf + ((size_t)(j - 1) * 8 + p2) * 1024; fr[8] = unit;
                 yd[8] = rec[j];
-                fr_t z; { const int rc = blk8_tile(fr, yd, 9, z); if (rc) return rc; }
-                if (b == nb - 1) st[j] = z; else rec[j] = recode_signed(z);
+                if (b == nb - 1) {          // the last block: the lane goes from its finish limbs through the next full round's S-box, like a fused product row
+                    int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; }
+                    uint32_t l[9]; blk8_finish_sums_limbs(S, l); xd[j] = recode_signed(sbox_lazy29(l, &k.rc_full29[((size_t)half * t + j) * 9]));
+                } else { fr_t z; { const int rc = blk8_tile(fr, yd, 9, z); if (rc) return rc; } rec[j] = recode_signed(z); }
             }
         }
-        st[0] = s0;
-        for (int r = half; r < k.rf; ++r) { const int rc = full(r, k.mds_frag); if (rc) return rc; }
+        xd[0] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(s0, k.rc_full[(size_t)half * t])));      // element 0 of that S-box from the chain's final value
+        for (int r = half; r < k.rf; ++r) { const int rc = product(k.mds_frag, r == k.rf - 1 ? -1 : r + 1); if (rc) return rc; }
         for (int j = 0; j < t; ++j) st4(states + 4 * (s * t + j), st[j]);
     }
     return 0;
@@ -308,6 +359,13 @@ size_t hc_blk8_table(void* h, int which, void* out, size_t cap) {
     const size_t len = which == 0 ? k.blk8_efrag.size() : which == 1 ? k.blk8_lfrag.size() : which == 3 ? k.blk8_gfrag.size() : k.gamma8_29.size() * 4;
     if (out && len) memcpy(out, src, std::min(cap, len));
     return len;
+}
+// the full rounds' constants as the fused rows add them (KernelConsts::rc_full29: rf * t entries of nine 29-bit limbs of the STORED constant); copies at
+// most cap words out, returns the table's length in words
+size_t hc_rc_full29_table(void* h, uint32_t* out, size_t cap) {
+    const std::vector<uint32_t>& v = ((HcParams*)h)->kc.rc_full29;
+    if (out && !v.empty()) memcpy(out, v.data(), std::min(cap, v.size()) * 4);
+    return v.size();
 }
 // The lane product's finish with the base lane in the tile: n cases of 32 digit sums S_c (the eight y K-steps) and a canonical base; the unit
 // fragment's K-step against the recoded base is added to the sums (as the ninth K-step of pair_block8 does), then fold and finish:

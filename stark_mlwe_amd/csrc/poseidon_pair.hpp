@@ -146,7 +146,25 @@ __device__ __forceinline__ void mfma_fold_rows(int64_t* col, const mfma_v16i& lo
                 col[k] += pair * ((int64_t)1 << sh);      // pair may be negative: a product, not a shift of a signed value (undefined before C++20)
             }
 }
-// nine signed columns (weight 2^(29k), the total any integer V with |V| < 2^272.01) -> the canonical representative of V mod r
+// nine signed columns (weight 2^(29k), the total any integer V with |V| < 2^272.01) -> W = V - q1 r as nine limbs: W == V (mod r), W in
+// (2^254 - 2^144.02, 2^255 + 2^144.02), inside (0, 3r); limbs 0..7 below 2^29, the top limb below 2^24 (bounds above: q, W)
+__device__ __forceinline__ void mfma_finish_limbs(int64_t* col, uint32_t* l) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { col[k + 1] += col[k] >> 29; l[k] = (uint32_t)col[k] & FR_M29; }
+    const int64_t top = col[8];
+    const int32_t q1 = (int32_t)(top >> 22) - 1;
+    l[8] = ((uint32_t)top & ((1u << 22) - 1)) + (1u << 22);
+    int64_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { const int64_t d = (int64_t)l[i] - (int64_t)q1 * (int64_t)fr_p29<PF>(i) + carry; l[i] = (uint32_t)d & FR_M29; carry = d >> 29; }
+    int32_t c32 = (int32_t)carry;                            // |carry| < 2^19 from here on
+#pragma unroll
+    for (int i = 5; i < 9; ++i) { const int32_t d = (int32_t)l[i] + c32; if (i < 8) { l[i] = (uint32_t)d & FR_M29; c32 = d >> 29; } else l[8] = (uint32_t)d; }
+}
+// the same -> the canonical representative of V mod r: W is below 3r, so the pack's conditional subtraction is followed by a second one.  The limb part is
+// written out again, statement for statement, instead of calling mfma_finish_limbs: through the call the register allocator laid out every kernel that
+// finishes canonical differently (the blocks-of-4 kernels 237 instead of 243 VGPRs, k_hash_ds2<17, DsBatchStream, true> 11 spilled instead of 10); like
+// this their code is the former one.
 __device__ __forceinline__ fr_t mfma_finish_cols(int64_t* col) {
     uint32_t l[9];
 #pragma unroll
@@ -163,6 +181,25 @@ __device__ __forceinline__ fr_t mfma_finish_cols(int64_t* col) {
     fr_t z = fr29_pack_reduce<PF>(l);
     fr_cond_sub<PF>(z.v, 0u);
     return z;
+}
+// The S-box on the finish's nine limbs, with no canonical value in between: u = W + c limb by limb (c = the next round's constant as nine 29-bit limbs
+// of its stored value, PoseidonDev::rc_full29), then x^5 as in fr_pow5_r29.  Bounds, for ANY u of value below 4r whose limbs are below 2^30 (here W < 3r
+// with limbs below 2^29 and c < r with limbs below 2^29):
+//   u^2     a doubled limb is below 2^31 (fits the 32-bit operand), a doubled cross product below 2^61, a square below 2^60; the fullest column (8) holds
+//           four doubled cross products and one square: 4 * 2^61 + 2^60 = 2^63 + 2^60, and the reduction adds at most 6 * 2^58 (five non-zero limbs of r
+//           above limb 0, the carry): below 2^63 + 2^60 + 2^60.6 < 2^64.  The Montgomery step leaves x2 < u^2 / 2^261 + r < (16 / 128 + 1) r < 1.13 r.
+//   x2^2    limbs below 2^29: the bounds of fr29.hpp; x4 < 1.01 r.
+//   u * x4  nine products below 2^30 * 2^29 per column: 9 * 2^59 + 6 * 2^58 < 2^63; x5 < (4 * 1.01 / 128 + 1) r < 1.04 r: fr29_pack_reduce's ONE conditional
+//           subtraction returns the canonical x^5 / 2^20 of fr_pow5_r29.
+// (mfma_digits.hpp sbox_lazy29 mirrors it for the host checks, with the column maximum reported.)
+__device__ __forceinline__ fr_t sbox_lazy29(const uint32_t* l, const uint32_t* __restrict__ c_) {
+    typedef const __attribute__((address_space(4))) uint32_t* cptr_t;      // wave-uniform constants on the scalar data path, as in fr_wide29_mac
+    cptr_t c = (cptr_t)c_;
+    fr29_t u;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) u.l[i] = l[i] + c[i];
+    const fr29_t x2 = fr29_sqr_mont<PF>(u), x4 = fr29_sqr_mont<PF>(x2), x5 = fr29_mul_mont<PF>(u, x4);
+    return fr29_pack_reduce<PF>(x5.l);
 }
 // Precondition: every state slot holds a recoded S-box output and a barrier has passed.  Ends with the state canonical and consistent.
 __device__ __forceinline__ void pair_apply_mds_mfma(const PairState& s, const void* frag) {
@@ -205,6 +242,55 @@ __device__ __forceinline__ void pair_apply_mds_mfma(const PairState& s, const vo
     __syncthreads();
 }
 
+// The same product with the row's hand-over fused (BLK8 form of pair_permute).  rc29 == nullptr: as pair_apply_mds_mfma.  Otherwise rc29 = the NEXT full
+// round's constants (17 x 9 limbs) and every row goes from its nine finish limbs straight through that round's S-box (sbox_lazy29) in the wave that
+// formed it — X the even elements, Y the odd ones, nothing crosses waves — and is stored as the next product's operand (recoded; canonical, not
+// recoded, in front of the squeeze round): no canonical value, no LDS round trip, no standalone S-box pass and one barrier less per round.
+__device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const void* frag, const uint32_t* rc29, bool recode) {
+    constexpr int T = 17;
+    static_assert(fr_p29<PF>(4) < (1u << 10) && fr_p29<PF>(5) == 0 && fr_p29<PF>(6) == 0 && fr_p29<PF>(7) == 0 && fr_p29<PF>(8) == (1u << 22), "r = 2^254 + t with t below 2^126");
+    const int lane = s.lane, h = lane >> 5;
+    mfma_v4i b[T][2];
+#pragma unroll
+    for (int e = 0; e < T; ++e)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) { const uint4 u = s.st[(2 * e + h) * 64 + 32 * ct + (lane & 31)]; b[e][ct] = mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w}; }
+    __syncthreads();                                   // both waves hold the state: the slots may be overwritten
+    const mfma_v4i* A = reinterpret_cast<const mfma_v4i*>(frag) + lane;
+#pragma unroll 1
+    for (int i = s.isY ? 1 : 0; i < T; i += 2) {
+        mfma_v16i acc[2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+        const mfma_v4i* Ai = A + (size_t)i * T * 64;
+#pragma unroll
+        for (int e = 0; e < T; ++e) {
+            const mfma_v4i a = Ai[(size_t)e * 64];
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
+        }
+        mfma_v16i lo, hi;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
+            lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
+        }
+        int64_t col[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) col[k] = 0;
+        mfma_fold_rows(col, lo, hi);
+        if (rc29) {
+            uint32_t l[9];
+            mfma_finish_limbs(col, l);
+            const fr_t y = sbox_lazy29(l, c29(rc29, i));
+            s.sto(i, recode ? recode_signed(y) : y);
+        } else s.sto(i, mfma_finish_cols(col));
+    }
+    __syncthreads();
+}
+
 // ---- partial rounds in BLOCKS OF 8, both long products on the matrix cores (T = 17, rp % 8 == 0) ------------------------------------------------------
 // Algebra (host_util.hpp blk8_*): with the lanes s_1..s_16 at their block-start values and y_q = (X_q + c_q)^5,
 //     X_{q+1} = E_q + a_q y_q + sum_{p<q} Gamma_{q,p} y_p,   E_q = sum_j u_{q,j} s_j,   and at the end of the block   s_j <- s_j + sum_p w_{p,j} y_p.
@@ -243,6 +329,18 @@ struct Blk8Cfg {
     __host__ __device__ static constexpr int ymail(int q) { return 17 + (q & 1); }
     __host__ __device__ static constexpr int hmail(int q) { return (q & 1) ? 19 : 0; }
 };
+// exchange and fold alone: the nine columns
+__device__ __forceinline__ void mfma_post_cols(const mfma_v16i (&acc)[2], int64_t* col) {
+    mfma_v16i lo, hi;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
+        lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) col[k] = 0;
+    mfma_fold_rows(col, lo, hi);
+}
 // exchange, fold, finish: the two accumulator tiles of a row -> the canonical field element of the lane's sponge
 __device__ __forceinline__ fr_t mfma_post(const mfma_v16i (&acc)[2]) {
     mfma_v16i lo, hi;
@@ -310,8 +408,10 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
 // the lane product: s_j <- s_j + sum_p w_{p,j} y_p for this wave's share of the lanes (X lanes 1..NLX, Y the rest), b: y_0..y_7 as B operands.  Ends with a barrier.
+// rc29_next != nullptr (FUSE, the permutation's last block): the constants of the full round that follows, 17 x 9 limbs; lane j then goes from its nine finish
+// limbs through that round's S-box (sbox_lazy29) and is stored as the round's operand (recoded unless that round is the squeeze round), like a fused product row.
 template <int NLX>
-__device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], bool last) {
+__device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], bool last, const uint32_t* rc29_next = nullptr, bool recode_next = true) {
     static_assert(NLX >= 1 && NLX <= 15, "shares");
     const int lane = s.lane;
     const int j0 = s.isY ? NLX + 1 : 1, j1 = s.isY ? 16 : NLX;
@@ -335,15 +435,22 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
         const int jn = j < j1 ? j + 1 : j1;                // the last row fetches its own fragments again: in bounds, unused
 #pragma unroll
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
-        const fr_t z = mfma_post(acc);
-        s.sto(j, last ? z : recode_signed(z));             // slot j is read by this wave alone, before this write
+        // slot j is read by this wave alone, before this write
+        if (rc29_next) {
+            int64_t col[9]; uint32_t l[9];
+            mfma_post_cols(acc, col); mfma_finish_limbs(col, l);
+            const fr_t y = sbox_lazy29(l, c29(rc29_next, j));
+            s.sto(j, recode_next ? recode_signed(y) : y);
+        } else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }
     }
     __syncthreads();
 }
 // One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; s0 = X_0 in wave X.  Ends with a barrier, the lanes recoded again,
 // or canonical after the permutation's last block.
+// With rc29_next (FUSE, last block): every slot ends as the next full round's S-box output instead — the lanes through blk8_lane_rows, element 0 from the chain's
+// final value (rc_next: the same round's constants as field elements).
 template <int NLX>
-__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last) {
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last, const uint32_t* rc29_next = nullptr, const fr_t* rc_next = nullptr, bool recode_next = true) {
     mfma_v4i b[8][2];
     if (!s.isY) {
         blk8_round_x<0>(s, Tb, s0, b); blk8_round_x<1>(s, Tb, s0, b); blk8_round_x<2>(s, Tb, s0, b); blk8_round_x<3>(s, Tb, s0, b);
@@ -355,7 +462,9 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
         blk8_round_y<4>(s, Tb, b, a, g); blk8_round_y<5>(s, Tb, b, a, g); blk8_round_y<6>(s, Tb, b, a, g); blk8_round_y<7>(s, Tb, b, a, g);
     }
     __builtin_amdgcn_sched_barrier(0);
-    blk8_lane_rows<NLX>(s, Tb, b, last);
+    // slot 0 was H's mailbox in the even rounds, last read by X after barrier_6; the lane rows' closing barrier publishes the store
+    if (rc29_next && !s.isY) { const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, rc_next[0])); s.sto(0, recode_next ? recode_signed(y) : y); }
+    blk8_lane_rows<NLX>(s, Tb, b, last, rc29_next, recode_next);
 }
 
 // s_j += w_{0,j} x0 + w_{1,j} x1 + w_{2,j} x2 + w_{3,j} x3   (one reduction)
@@ -377,12 +486,22 @@ __device__ __forceinline__ fr_t pair_lane_update(const uint32_t* sp, int j, cons
 // Precondition of BLK8: when the partial rounds are entered, lanes 1..16 are CANONICAL (recode_signed needs x < r).  The full round before them leaves
 // them so (mfma_finish_cols); with r_begin >= rf / 2 no full round runs first and the caller's stores must be canonical (today's callers store fr_add
 // results and field elements from memory).
-template <int T, bool BLK8 = false>
+// FUSE (BLK8 only, its default): every full-round product that is followed by a full round hands its rows to that round's S-box in limb form
+// (pair_mds_sbox_mfma), and the last block's lane rows hand theirs to the S-box after the partial rounds (blk8_lane_rows).  k_hash_ds2 turns it off: its generic stream state is live across the permutation, and with the S-box's columns beside the product's
+// operand registers three of its instantiations took 88 / 36 / 52 B of scratch against 44 / 12 / 28 B without (the two fixed-shape kernels hold 244 VGPRs, none spilled).
+template <int T, bool BLK8 = false, bool FUSE = BLK8>
 __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonDev& P, bool only0, int r_begin = 0) {
     static_assert(!BLK8 || T == 17, "8-round blocks exist for t = 17");
+    static_assert(!FUSE || BLK8, "the fused hand-over belongs to the 8-round form");
     typedef PairCfg<T> Cfg;
     constexpr int NXD = Cfg::NXD, NXU = Cfg::NXU, W = 2 * T - 1;
     const int half = P.rf / 2;
+    if constexpr (FUSE) {
+        // one standalone S-box, then every product hands its rows to the next round's S-box in limb form; the product in front of the partial rounds ends canonical
+        if (r_begin < half) pair_sbox_full<T, true>(s, P.rc_full + r_begin * T);
+        for (int r = r_begin; r < half; ++r)
+            pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, (r == half - 1) ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T), true);
+    } else
     for (int r = r_begin; r < half; ++r) {
         if constexpr (T == 17) { pair_sbox_full<T, true>(s, P.rc_full + r * T); pair_apply_mds_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag); }
         else { pair_sbox_full<T>(s, P.rc_full + r * T); pair_apply_lu<T>(s, (r == half - 1) ? P.lu_pre29 : P.lu29); }
@@ -398,7 +517,8 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
             const Blk8Tabs Tb{reinterpret_cast<const mfma_v4i*>(P.blk8_efrag) + (size_t)b * 8 * 16 * 64, reinterpret_cast<const mfma_v4i*>(P.blk8_lfrag) + (size_t)b * 16 * 8 * 64,
                               reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), reinterpret_cast<const mfma_v4i*>(P.blk8_gfrag) + (size_t)b * 28 * 64,
                               c29(P.sparse29, (size_t)(8 * b) * W), P.rc_partial + 8 * b};
-            pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1);
+            if constexpr (FUSE) pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1, b == nb - 1 ? c29(P.rc_full29, (size_t)half * T) : nullptr, P.rc_full + half * T, !(only0 && half == P.rf - 1));
+            else pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1);
         }
     } else
     for (int b = 0; b < P.rp / 4; ++b) {
@@ -454,11 +574,14 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
         }
         __syncthreads();                                               // E: lanes 1..T-1 consistent, mailboxes free
     }
-    if (!s.isY) s.sto(0, s0);
-    __syncthreads();
+    if constexpr (!FUSE) {
+        if (!s.isY) s.sto(0, s0);
+        __syncthreads();
+    }   // FUSE: the last block left round half's S-box outputs in every slot (recoded unless it is the squeeze round), behind its closing barrier
     for (int r = half; r < P.rf; ++r) {
         const bool squeeze = only0 && r == P.rf - 1;
-        if constexpr (T == 17) { if (squeeze) pair_sbox_full<T>(s, P.rc_full + r * T); else pair_sbox_full<T, true>(s, P.rc_full + r * T); }
+        if constexpr (FUSE) { /* this round's S-box ran with the row that fed it */ }
+        else if constexpr (T == 17) { if (squeeze) pair_sbox_full<T>(s, P.rc_full + r * T); else pair_sbox_full<T, true>(s, P.rc_full + r * T); }
         else pair_sbox_full<T>(s, P.rc_full + r * T);
         if (squeeze) {                                      // squeeze: row 0 only, split over the two waves
             const int j0 = s.isY ? Cfg::NX : 0, j1 = s.isY ? T : Cfg::NX;
@@ -471,7 +594,8 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
             __syncthreads();                                 // the slots are reused by the next permutation
             return out;
         }
-        if constexpr (T == 17) pair_apply_mds_mfma(s, P.mds_frag); else pair_apply_lu<T>(s, P.lu29);
+        if constexpr (FUSE) pair_mds_sbox_mfma(s, P.mds_frag, r == P.rf - 1 ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T), !(only0 && r + 1 == P.rf - 1));
+        else if constexpr (T == 17) pair_apply_mds_mfma(s, P.mds_frag); else pair_apply_lu<T>(s, P.lu29);
     }
     return s.ld(0);
 }
@@ -535,7 +659,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
             }
         }
         __syncthreads();
-        res = pair_permute<T, BLK8>(s, P, pidx + 1 == max_perm);
+        res = pair_permute<T, BLK8, false>(s, P, pidx + 1 == max_perm);
         __syncthreads();
     }
     if (live && !s.isY) stg(out + k0, res);

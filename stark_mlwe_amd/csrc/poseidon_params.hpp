@@ -21,6 +21,9 @@ struct PoseidonDev {           // device pointers to kernel-form constants (see 
     const uint32_t* chain_a; const uint32_t* chain_g; const uint32_t* chain_w;
     // t = 17, rp % 8 == 0: the 8-round partial blocks of the wave-pair kernels (host_util.hpp blk8_*, poseidon_pair.hpp pair_block8); nullptr otherwise
     const void* blk8_efrag; const void* blk8_lfrag; const void* blk8_unit_frag; const void* blk8_gfrag;
+    // the full rounds' constants again as nine 29-bit limbs of their STORED value (fr29_unpack; not the R' domain of the multiplier tables), 9 words per entry:
+    // added limb by limb to a product row that stays in limbs up to its S-box (poseidon_pair.hpp sbox_lazy29)
+    const uint32_t* rc_full29;
 };
 
 }  // namespace stark

@@ -1,6 +1,7 @@
 // tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds, of
 // the lane product of the 8-round partial blocks with the base lane in the tile (finish with base), and of the blocks' H rows of up to 16 + 7 K-steps:
-// the fragment tables (host_util.hpp mfma_frags) and the fold + finishing step (mfma_digits.hpp), against the portable field code.  Meant for a
+// the fragment tables (host_util.hpp mfma_frags), the fold + finishing step and the limb-form hand-over to the next S-box (mfma_digits.hpp: finish to
+// limbs, S-box on lazy limbs), against the portable field code.  Meant for a
 // sanitizer build; tools/mfma_finish_sanitize.sh builds it with AddressSanitizer + UBSan and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I stark_mlwe_amd/csrc tools/mfma_finish_check.cpp -o tools/bin/mfma_finish_check
 #include <cstdio>
@@ -139,6 +140,36 @@ int main() {
         }
         int32_t S[32]; for (int c = 0; c < 32; ++c) { if (S64[c] > (16 + q) * 32 * 128 * 128 || S64[c] < -(16 + q) * 32 * 128 * 128 || S64[c] > LIM || S64[c] < -LIM) { fprintf(stderr, "H row beyond its bound\n"); return 1; } S[c] = (int32_t)S64[c]; }
         ++n; if (!fr_eq(finish(S), want)) { if (bad < 5) fprintf(stderr, "H row: mismatch block %d row %d rep %d\n", blk, q, rep); ++bad; }
+    }
+    // ---- the limb-form hand-over of the fused full-round rows (poseidon_pair.hpp pair_mds_sbox_mfma).  (i) finish to limbs (mfma_finish_limbs) on every case
+    // above: limbs 0..7 below 2^29, the top limb below 2^24, the value inside (2^254 - 2^145, 2^255 + 2^145) — top limb in [2^22 - 1, 2^23] —, and its
+    // canonical form equal to the finishing step's.  (ii) the S-box on those limbs plus a round constant from rc_full29 (sbox_lazy29) against fr_pow5_r29 of the
+    // canonical sum, for every crafted case against eight constants and every random case against one.  (iii) every limb at its maximum, the top limbs at the
+    // ends of their ranges: the same steps with 128-bit columns (Lazy29Wide) agree and no column reaches 2^64.
+    if (kc.rc_full29.size() != (size_t)8 * 17 * 9) { fprintf(stderr, "rc_full29 missing\n"); return 1; }
+    auto finish_limbs = [](const int32_t* S, uint32_t* l) {
+        int32_t lo[16], hi[16];
+        for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
+        int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
+        mfma_fold_rows(col, lo, hi);
+        mfma_finish_limbs(col, l); };
+    for (size_t ci = 0; ci < cases.size(); ++ci) {
+        uint32_t l[9]; finish_limbs(cases[ci].data(), l);
+        bool ok = l[8] < (1u << 24) && l[8] >= (1u << 22) - 1 && l[8] <= (1u << 23);
+        for (int i = 0; i < 8; ++i) ok = ok && l[i] <= FR_M29;
+        fr_t z = fr29_pack_reduce<PF>(l); fr_cond_sub<PF>(z.v, 0u);
+        const fr_t canon = finish(cases[ci].data());
+        ++n; if (!ok || !fr_eq(z, canon)) { if (bad < 5) fprintf(stderr, "finish to limbs: case %zu\n", ci); ++bad; }
+        for (int e = 0; e < (ci < ncraft ? 8 : 1); ++e) {
+            const size_t idx = (ci * 7 + (size_t)e * 17) % (8 * 17);
+            const fr_t want = fr_pow5_r29<PF>(fr_add<PF>(canon, kc.rc_full[idx]));
+            ++n; if (!fr_eq(sbox_lazy29(l, &kc.rc_full29[9 * idx]), want)) { if (bad < 5) fprintf(stderr, "S-box on lazy limbs: case %zu constant %zu\n", ci, idx); ++bad; }
+        }
+    }
+    for (uint32_t l8 : {0u, 1u << 22, 3u * (1u << 22) - 1}) for (uint32_t c8 : {0u, (1u << 22) - 1}) {
+        uint32_t l[9], c[9]; for (int i = 0; i < 8; ++i) l[i] = c[i] = FR_M29; l[8] = l8; c[8] = c8;
+        Lazy29Wide wide; const fr29_t x5 = wide.pow5(l, c);
+        ++n; if ((wide.max_col >> 64) != 0 || !fr_eq(sbox_lazy29(l, c), fr29_pack_reduce<PF>(x5.l))) { if (bad < 5) fprintf(stderr, "S-box on lazy limbs: column overflow at l8 %u c8 %u\n", l8, c8); ++bad; }
     }
     printf("{\"check\": \"residue tables and finishing step against the portable field code\", \"cases\": %ld, \"mismatches\": %ld}\n", n, bad);
     return bad ? 1 : 0;
