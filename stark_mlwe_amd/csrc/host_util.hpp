@@ -244,7 +244,7 @@ template <class Pred> inline std::vector<uint32_t> to_radix29(const std::vector<
     for (size_t i = 0; i < v.size(); ++i) fr29_const_from<PF>(scaled(i) ? fr_mul<PF>(v[i], k) : v[i], &o[9 * i]);
     return o;
 }
-// A-operand fragments of v_mfma_i32_32x32x32_i8 for y = M * x with x an S-box output (poseidon_pair.hpp pair_apply_mds_mfma): RESIDUE TABLES.
+// A-operand fragments of v_mfma_i32_32x32x32_i8 for y = M * x with x an S-box output (poseidon_pair.hpp pair_mds_sbox_mfma): RESIDUE TABLES.
 // The left factor is constant, so the reduction mod r is done here, once per parameter set.  For entry (i, e) and input digit position b,
 //     C[i][e][b] = ( M[i][e] * 2^20 * 256^b ) mod r        a plain integer in [0, r)   (2^20: fr_pow5_r29's scale)
 // written in SIGNED radix-256 digits d[0..31] in [-128, 127] (add 0x80 to every byte with carries, subtract 0x80 from every digit; C < r

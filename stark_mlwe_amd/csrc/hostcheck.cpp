@@ -180,7 +180,7 @@ int hc_params_export(void* h, uint64_t* mds, uint64_t* rc_full, uint64_t* rc_par
 // One full round's linear layer  y = M * x  (x = S-box outputs) of t = 17 states, two ways on the host: through the in-place L*U rows the VALU
 // kernels use (which = 0), and through an emulation of the matrix-core path (which = 1): signed recoding, the int8 RESIDUE FRAGMENT TABLES the
 // kernels read (host_util.hpp mfma_frags: lane l of fragment (i, e) holds A[row l & 31][k = 16 (l >> 5) + j]), D[row][col] = sum_k A[row][k] B[k][col]
-// for the one 32-row tile, the accumulator rows as the two lanes of a sponge receive them, the fold and the finishing step of mfma_digits.hpp.
+// for the one 32-row tile, then the kernels' own fold and finishing step (mfma_digits.hpp mfma_cols_of_sums, mfma_finish_cols).
 // pre: the B_1 * M matrix.
 int hc_full_round_linear(void* h, int which, int pre, uint64_t* states, size_t n) {
     HcParams* P = (HcParams*)h; const int t = P->dev.t;
@@ -198,10 +198,7 @@ int hc_full_round_linear(void* h, int which, int pre, uint64_t* states, size_t n
                     for (int e = 0; e < t; ++e) for (int kh = 0; kh < 2; ++kh) { const int8_t* a = &F[((((size_t)i * t + e) * 64) + (r + 32 * kh)) * 16];
                         const int8_t* b = reinterpret_cast<const int8_t*>(xd[e].v) + 16 * kh; for (int j = 0; j < 16; ++j) acc += (int64_t)a[j] * b[j]; }
                     if (acc > 0x7fffffffll || acc < -0x80000000ll) return -2; S[r] = (int32_t)acc; }
-                int32_t lo[16], hi[16];
-                for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
-                int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
-                mfma_fold_rows(col, lo, hi);
+                int64_t col[9]; mfma_cols_of_sums(S, col);
                 out[i] = mfma_finish_cols(col);
             }
         }
@@ -222,10 +219,7 @@ int hc_mfma_finish(const int32_t* sums, size_t n, uint64_t* out) {
     for (size_t s = 0; s < n; ++s) {
         const int32_t* S = sums + 32 * s;
         for (int c = 0; c < 32; ++c) if (S[c] >= (1 << 24) || S[c] <= -(1 << 24)) return -1;
-        int32_t lo[16], hi[16];
-        for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
-        int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
-        mfma_fold_rows(col, lo, hi);
+        int64_t col[9]; mfma_cols_of_sums(S, col);
         st4(out + 4 * s, mfma_finish_cols(col));
     }
     return 0;
@@ -236,10 +230,7 @@ int hc_mfma_finish_limbs(const int32_t* sums, size_t n, uint32_t* out) {
     for (size_t s = 0; s < n; ++s) {
         const int32_t* S = sums + 32 * s;
         for (int c = 0; c < 32; ++c) if (S[c] >= (1 << 24) || S[c] <= -(1 << 24)) return -1;
-        int32_t lo[16], hi[16];
-        for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
-        int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
-        mfma_fold_rows(col, lo, hi);
+        int64_t col[9]; mfma_cols_of_sums(S, col);
         mfma_finish_limbs(col, out + 9 * s);
     }
     return 0;
@@ -260,7 +251,7 @@ int hc_sbox_lazy29(const uint32_t* l, const uint32_t* c, size_t n, uint64_t* out
     }
     return 0;
 }
-// ---- the 8-round partial blocks of the t = 17 wave-pair kernels (poseidon_pair.hpp pair_block8), mirrored on the host with the tables the device gets ----
+// ---- the 8-round partial blocks of the t = 17 wave-pair kernels (poseidon_pair.hpp pair_block8) on the host: the kernels' schedule re-enacted with the tables the device gets, the rows' fold and finish their own ----
 // One emulated 32-row tile: K K-steps, fragment k (1 KiB, host_util.hpp mfma_frag_of: lane l holds A[row l & 31][16 (l >> 5) + j]) against the recoded
 // operand xd[k]; S[row] = sum_k sum_b A_k[row][b] xd_k[b].  -2 when a digit sum leaves the finishing step's domain |S| < 2^24.
 static int blk8_tile_sums(const int8_t* const* frag, const fr_t* xd, int K, int32_t* S) {
@@ -270,20 +261,9 @@ static int blk8_tile_sums(const int8_t* const* frag, const fr_t* xd, int K, int3
         if (acc >= (1 << 24) || acc <= -(1 << 24)) return -2; S[r] = (int32_t)acc; }
     return 0;
 }
-static fr_t blk8_finish_sums(const int32_t* S) {      // the accumulator rows as the two lanes of a sponge receive them, fold, finish (mfma_digits.hpp)
-    int32_t lo[16], hi[16];
-    for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
-    int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
-    mfma_fold_rows(col, lo, hi);
-    return mfma_finish_cols(col);
-}
-static void blk8_finish_sums_limbs(const int32_t* S, uint32_t* l) {      // the same, stopped at the nine limbs (mfma_finish_limbs)
-    int32_t lo[16], hi[16];
-    for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
-    int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
-    mfma_fold_rows(col, lo, hi);
-    mfma_finish_limbs(col, l);
-}
+// a tile's 32 digit sums -> the row's value: the kernels' fold and finish (mfma_digits.hpp), canonical or stopped at the nine limbs
+static fr_t blk8_finish_sums(const int32_t* S) { int64_t col[9]; mfma_cols_of_sums(S, col); return mfma_finish_cols(col); }
+static void blk8_finish_sums_limbs(const int32_t* S, uint32_t* l) { int64_t col[9]; mfma_cols_of_sums(S, col); mfma_finish_limbs(col, l); }
 static int blk8_tile(const int8_t* const* frag, const fr_t* xd, int K, fr_t& out) { int32_t S[32]; const int rc = blk8_tile_sums(frag, xd, K, S); if (rc) return rc; out = blk8_finish_sums(S); return 0; }
 // the largest |digit sum| hc_permute_block8 has seen in a row of 16 + 7 K-steps (the longest tile of the block form) since the last reset
 static std::atomic<int32_t> g_blk8_row23_max{0};

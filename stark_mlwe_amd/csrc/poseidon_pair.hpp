@@ -7,7 +7,7 @@
 // the batch: lane l of both waves works on state l, each wave on its own part of the linear algebra.
 // Same LDS per state, twice the waves per SIMD (4 workgroups of 40 KiB per CU for t = 17).
 //   * full rounds : S-box on the wave's own elements; the dense MDS product
-//                   - t = 17: on the MATRIX CORES (pair_apply_mds_mfma below): int8 MFMA of the matrix's residue table with the state's signed radix-256 digits, X the even
+//                   - t = 17: on the MATRIX CORES (pair_mds_sbox_mfma below): int8 MFMA of the matrix's residue table with the state's signed radix-256 digits, X the even
 //                     output rows, Y the odd ones, each wave holding the whole state as operand registers;
 //                   - t = 9: as in-place L*(U*x) on the VALU, X taking the even rows and Y the odd rows of each step (rows
 //                     2k/2k+1 read only slots >= 2k, so a single barrier between the step's reads and its two writes keeps it race-free);
@@ -28,6 +28,7 @@
 #include "poseidon_params.hpp"
 #include "poseidon_dev.hpp"
 #include "poseidon_streams.hpp"
+#include "mfma_digits.hpp"
 
 #if defined(__HIPCC__)
 namespace stark {
@@ -91,14 +92,6 @@ __device__ __forceinline__ void pair_apply_lu(const PairState& s, const uint32_t
     }
     __syncthreads();
 }
-// x (canonical) -> signed radix-256 digits in place of its bytes: add 0x80 to every byte with carries, flip every byte's top bit
-// (digit b = byte b - 0x80 in [-128, 127]; x < r keeps the top byte below 0x80, so 32 digits hold it).  The int8 operand form of the MFMA product.
-__device__ __forceinline__ fr_t recode_signed(const fr_t& x) {
-    fr_t y; uint64_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { const uint64_t t = (uint64_t)x.v[i] + 0x80808080u + c; y.v[i] = (uint32_t)t ^ 0x80808080u; c = t >> 32; }
-    return y;
-}
 template <int T, bool RECODE = false>
 __device__ __forceinline__ void pair_sbox_full(const PairState& s, const fr_t* rc) {
     const int j0 = s.isY ? PairCfg<T>::NX : 0, j1 = s.isY ? T : PairCfg<T>::NX;
@@ -119,136 +112,48 @@ __device__ __forceinline__ void pair_sbox_full(const PairState& s, const fr_t* r
 //   * D layout: lane l, register r = row (r & 3) + 8 (r >> 2) + 4 (l >> 5) of column l & 31: a sponge's 32 digit sums sit in lanes l and l + 32.
 //     v_permlane32_swap(tile of sponges 0..31, tile of sponges 32..63) hands the lower lane the upper lane's rows of ITS sponge and vice versa, so
 //     that afterwards lane l owns sponge l (the kernels' lane <-> sponge map) with the rows in a lane-uniform order.
-//   * fold and finish, with the bound of every intermediate (mfma_digits.hpp mirrors both statement by statement for the host checks):
-//       digit sum   |S_c| <= 17 * 32 * 128 * 128 = 8 912 896 < 2^24: exact in the i32 accumulators.  Everything below holds for ANY |S_c| < 2^24.
-//       pair        P = S_c + 256 S_{c+1} (c even), |P| < 257 * 2^24 < 2^32.01, goes into the 64-bit column k = floor(8c / 29) of weight 2^(29k)
-//                   that holds the lower digit, shifted by 8c - 29k <= 28: |P << sh| < 2^60.01.
-//       column      nine columns (8 * 30 = 240 = 29 * 8 + 8); bit positions 16 apart: at most two pairs per column, |col| < 2^61.01; with the carry
-//                   from below (< 2^32.1) still < 2^62.  The signed carry pass leaves limbs 0..7 in [0, 2^29) and top = floor(V / 2^232) in column 8:
-//                   |V| < 2^24 * (256^32 - 1) / 255 < 2^272.01, |top| < 2^40.01.
-//       q           q1 = floor(V / 2^254) - 1 = (top >> 22) - 1, |q1| < 2^18.02; q1 * (a 29-bit limb of t) < 2^47.02.
-//       W           W = V - q1 r = (V mod 2^254) + 2^254 - q1 t  (a five-limb multiply and one signed carry pass): V mod 2^254 is in [0, 2^254) and
-//                   |q1 t| < 2^144.02, so W is in (2^254 - 2^144.02, 2^255 + 2^144.02), inside (0, 3r) and below 2^256: every limb ends non-negative,
-//                   the top limb below 2^24, and TWO conditional subtractions of r return the canonical value (the second fires only for
-//                   V mod 2^254 within 2^144 of 2^254; taking q1 one lower than the floor is what keeps W non-negative at the other end).
+//   * fold and finish: mfma_digits.hpp (mfma_fold_rows, mfma_finish_limbs / mfma_finish_cols, sbox_lazy29), the statements the host checks run, with the
+//     bound of every intermediate; they hold for any |digit sum| < 2^24, here |S_c| <= 17 * 32 * 128 * 128 = 8 912 896.
+// One row pipeline serves this product and the two of the 8-round blocks: zeroed tile -> MFMAs -> mfma_post_cols -> a canonical finish (mfma_post) or the
+// limb-form hand-over to the next S-box (pair_sto_sbox29).
 typedef int mfma_v4i __attribute__((ext_vector_type(4)));
 typedef int mfma_v16i __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ void mfma_fold_rows(int64_t* col, const mfma_v16i& lo, const mfma_v16i& hi) {
+__device__ __forceinline__ void mfma_zero_tile(mfma_v16i (&acc)[2]) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
+    for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const mfma_v16i& a = hh ? hi : lo;
-                const int64_t pair = (int64_t)a[4 * q + 2 * p] + (int64_t)a[4 * q + 2 * p + 1] * 256;
-                const int c = 8 * q + 4 * hh + 2 * p, k = (8 * c) / 29, sh = 8 * c - 29 * k;
-                col[k] += pair * ((int64_t)1 << sh);      // pair may be negative: a product, not a shift of a signed value (undefined before C++20)
-            }
+        for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
 }
-// nine signed columns (weight 2^(29k), the total any integer V with |V| < 2^272.01) -> W = V - q1 r as nine limbs: W == V (mod r), W in
-// (2^254 - 2^144.02, 2^255 + 2^144.02), inside (0, 3r); limbs 0..7 below 2^29, the top limb below 2^24 (bounds above: q, W)
-__device__ __forceinline__ void mfma_finish_limbs(int64_t* col, uint32_t* l) {
+// exchange and fold: the two accumulator tiles of a row -> the nine columns of the lane's sponge
+__device__ __forceinline__ void mfma_post_cols(const mfma_v16i (&acc)[2], int64_t* col) {
+    mfma_v16i lo, hi;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { col[k + 1] += col[k] >> 29; l[k] = (uint32_t)col[k] & FR_M29; }
-    const int64_t top = col[8];
-    const int32_t q1 = (int32_t)(top >> 22) - 1;
-    l[8] = ((uint32_t)top & ((1u << 22) - 1)) + (1u << 22);
-    int64_t carry = 0;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) { const int64_t d = (int64_t)l[i] - (int64_t)q1 * (int64_t)fr_p29<PF>(i) + carry; l[i] = (uint32_t)d & FR_M29; carry = d >> 29; }
-    int32_t c32 = (int32_t)carry;                            // |carry| < 2^19 from here on
-#pragma unroll
-    for (int i = 5; i < 9; ++i) { const int32_t d = (int32_t)l[i] + c32; if (i < 8) { l[i] = (uint32_t)d & FR_M29; c32 = d >> 29; } else l[8] = (uint32_t)d; }
-}
-// the same -> the canonical representative of V mod r: W is below 3r, so the pack's conditional subtraction is followed by a second one.  The limb part is
-// written out again, statement for statement, instead of calling mfma_finish_limbs: through the call the register allocator laid out every kernel that
-// finishes canonical differently (the blocks-of-4 kernels 237 instead of 243 VGPRs, k_hash_ds2<17, DsBatchStream, true> 11 spilled instead of 10); like
-// this their code is the former one.
-__device__ __forceinline__ fr_t mfma_finish_cols(int64_t* col) {
-    uint32_t l[9];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { col[k + 1] += col[k] >> 29; l[k] = (uint32_t)col[k] & FR_M29; }
-    const int64_t top = col[8];
-    const int32_t q1 = (int32_t)(top >> 22) - 1;
-    l[8] = ((uint32_t)top & ((1u << 22) - 1)) + (1u << 22);
-    int64_t carry = 0;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) { const int64_t d = (int64_t)l[i] - (int64_t)q1 * (int64_t)fr_p29<PF>(i) + carry; l[i] = (uint32_t)d & FR_M29; carry = d >> 29; }
-    int32_t c32 = (int32_t)carry;                            // |carry| < 2^19 from here on
-#pragma unroll
-    for (int i = 5; i < 9; ++i) { const int32_t d = (int32_t)l[i] + c32; if (i < 8) { l[i] = (uint32_t)d & FR_M29; c32 = d >> 29; } else l[8] = (uint32_t)d; }
-    fr_t z = fr29_pack_reduce<PF>(l);
-    fr_cond_sub<PF>(z.v, 0u);
-    return z;
-}
-// The S-box on the finish's nine limbs, with no canonical value in between: u = W + c limb by limb (c = the next round's constant as nine 29-bit limbs
-// of its stored value, PoseidonDev::rc_full29), then x^5 as in fr_pow5_r29.  Bounds, for ANY u of value below 4r whose limbs are below 2^30 (here W < 3r
-// with limbs below 2^29 and c < r with limbs below 2^29):
-//   u^2     a doubled limb is below 2^31 (fits the 32-bit operand), a doubled cross product below 2^61, a square below 2^60; the fullest column (8) holds
-//           four doubled cross products and one square: 4 * 2^61 + 2^60 = 2^63 + 2^60, and the reduction adds at most 6 * 2^58 (five non-zero limbs of r
-//           above limb 0, the carry): below 2^63 + 2^60 + 2^60.6 < 2^64.  The Montgomery step leaves x2 < u^2 / 2^261 + r < (16 / 128 + 1) r < 1.13 r.
-//   x2^2    limbs below 2^29: the bounds of fr29.hpp; x4 < 1.01 r.
-//   u * x4  nine products below 2^30 * 2^29 per column: 9 * 2^59 + 6 * 2^58 < 2^63; x5 < (4 * 1.01 / 128 + 1) r < 1.04 r: fr29_pack_reduce's ONE conditional
-//           subtraction returns the canonical x^5 / 2^20 of fr_pow5_r29.
-// (mfma_digits.hpp sbox_lazy29 mirrors it for the host checks, with the column maximum reported.)
-__device__ __forceinline__ fr_t sbox_lazy29(const uint32_t* l, const uint32_t* __restrict__ c_) {
-    typedef const __attribute__((address_space(4))) uint32_t* cptr_t;      // wave-uniform constants on the scalar data path, as in fr_wide29_mac
-    cptr_t c = (cptr_t)c_;
-    fr29_t u;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) u.l[i] = l[i] + c[i];
-    const fr29_t x2 = fr29_sqr_mont<PF>(u), x4 = fr29_sqr_mont<PF>(x2), x5 = fr29_mul_mont<PF>(u, x4);
-    return fr29_pack_reduce<PF>(x5.l);
-}
-// Precondition: every state slot holds a recoded S-box output and a barrier has passed.  Ends with the state canonical and consistent.
-__device__ __forceinline__ void pair_apply_mds_mfma(const PairState& s, const void* frag) {
-    constexpr int T = 17;
-    static_assert(fr_p29<PF>(4) < (1u << 10) && fr_p29<PF>(5) == 0 && fr_p29<PF>(6) == 0 && fr_p29<PF>(7) == 0 && fr_p29<PF>(8) == (1u << 22), "r = 2^254 + t with t below 2^126");
-    const int lane = s.lane, h = lane >> 5;
-    mfma_v4i b[T][2];
-#pragma unroll
-    for (int e = 0; e < T; ++e)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) { const uint4 u = s.st[(2 * e + h) * 64 + 32 * ct + (lane & 31)]; b[e][ct] = mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w}; }
-    __syncthreads();                                   // both waves hold the state: the slots may be overwritten
-    const mfma_v4i* A = reinterpret_cast<const mfma_v4i*>(frag) + lane;
-#pragma unroll 1
-    for (int i = s.isY ? 1 : 0; i < T; i += 2) {
-        mfma_v16i acc[2];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
-        const mfma_v4i* Ai = A + (size_t)i * T * 64;
-#pragma unroll
-        for (int e = 0; e < T; ++e) {
-            const mfma_v4i a = Ai[(size_t)e * 64];
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
-        }
-        mfma_v16i lo, hi;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
-            lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
-        }
-        int64_t col[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) col[k] = 0;
-        mfma_fold_rows(col, lo, hi);
-        s.sto(i, mfma_finish_cols(col));
+    for (int r = 0; r < 16; ++r) {
+        const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
+        lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
     }
-    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 9; ++k) col[k] = 0;
+    mfma_fold_rows(col, lo, hi);
 }
-
-// The same product with the row's hand-over fused (BLK8 form of pair_permute).  rc29 == nullptr: as pair_apply_mds_mfma.  Otherwise rc29 = the NEXT full
-// round's constants (17 x 9 limbs) and every row goes from its nine finish limbs straight through that round's S-box (sbox_lazy29) in the wave that
-// formed it — X the even elements, Y the odd ones, nothing crosses waves — and is stored as the next product's operand (recoded; canonical, not
-// recoded, in front of the squeeze round): no canonical value, no LDS round trip, no standalone S-box pass and one barrier less per round.
+// exchange, fold, finish: -> the canonical field element of the lane's sponge
+__device__ __forceinline__ fr_t mfma_post(const mfma_v16i (&acc)[2]) {
+    int64_t col[9];
+    mfma_post_cols(acc, col);
+    return mfma_finish_cols(col);
+}
+// The limb-form hand-over of a row: its nine finish limbs l (mfma_finish_limbs) go straight through the next full round's S-box (rc29: that round's constant
+// for element j, nine limbs) and into slot j as the next product's operand (recoded; canonical, not recoded, in front of the squeeze round).  No canonical value
+// in between.  The finish itself stays at the two call sites: taken in here as well, k_node16_pair<true> holds one VGPR more than before the merge (245).
+__device__ __forceinline__ void pair_sto_sbox29(const PairState& s, int j, const uint32_t* l, const uint32_t* rc29, bool recode) {
+    const fr_t y = sbox_lazy29(l, rc29);
+    s.sto(j, recode ? recode_signed(y) : y);
+}
+// The product.  Precondition: every state slot holds a recoded S-box output and a barrier has passed.  rc29 == nullptr: ends with the state canonical and
+// consistent.  Otherwise rc29 = the NEXT full round's constants (17 x 9 limbs) and every row is handed to that round's S-box in the wave that formed it
+// (pair_sto_sbox29) — X the even elements, Y the odd ones, nothing crosses waves: no LDS round trip, no standalone S-box pass and one barrier less per round.
 __device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const void* frag, const uint32_t* rc29, bool recode) {
     constexpr int T = 17;
-    static_assert(fr_p29<PF>(4) < (1u << 10) && fr_p29<PF>(5) == 0 && fr_p29<PF>(6) == 0 && fr_p29<PF>(7) == 0 && fr_p29<PF>(8) == (1u << 22), "r = 2^254 + t with t below 2^126");
     const int lane = s.lane, h = lane >> 5;
     mfma_v4i b[T][2];
 #pragma unroll
@@ -260,10 +165,7 @@ __device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const voi
 #pragma unroll 1
     for (int i = s.isY ? 1 : 0; i < T; i += 2) {
         mfma_v16i acc[2];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+        mfma_zero_tile(acc);
         const mfma_v4i* Ai = A + (size_t)i * T * 64;
 #pragma unroll
         for (int e = 0; e < T; ++e) {
@@ -271,22 +173,10 @@ __device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const voi
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
         }
-        mfma_v16i lo, hi;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
-            lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
-        }
         int64_t col[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) col[k] = 0;
-        mfma_fold_rows(col, lo, hi);
-        if (rc29) {
-            uint32_t l[9];
-            mfma_finish_limbs(col, l);
-            const fr_t y = sbox_lazy29(l, c29(rc29, i));
-            s.sto(i, recode ? recode_signed(y) : y);
-        } else s.sto(i, mfma_finish_cols(col));
+        mfma_post_cols(acc, col);
+        if (rc29) { uint32_t l[9]; mfma_finish_limbs(col, l); pair_sto_sbox29(s, i, l, c29(rc29, i), recode); }
+        else s.sto(i, mfma_finish_cols(col));
     }
     __syncthreads();
 }
@@ -329,32 +219,6 @@ struct Blk8Cfg {
     __host__ __device__ static constexpr int ymail(int q) { return 17 + (q & 1); }
     __host__ __device__ static constexpr int hmail(int q) { return (q & 1) ? 19 : 0; }
 };
-// exchange and fold alone: the nine columns
-__device__ __forceinline__ void mfma_post_cols(const mfma_v16i (&acc)[2], int64_t* col) {
-    mfma_v16i lo, hi;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
-        lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) col[k] = 0;
-    mfma_fold_rows(col, lo, hi);
-}
-// exchange, fold, finish: the two accumulator tiles of a row -> the canonical field element of the lane's sponge
-__device__ __forceinline__ fr_t mfma_post(const mfma_v16i (&acc)[2]) {
-    mfma_v16i lo, hi;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
-        lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
-    }
-    int64_t col[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) col[k] = 0;
-    mfma_fold_rows(col, lo, hi);
-    return mfma_finish_cols(col);
-}
 // A is wave-uniform and the lane is added at the load: a scalar base plus one 32-bit lane offset
 __device__ __forceinline__ void blk8_load_frags16(mfma_v4i (&a)[16], const mfma_v4i* A, int lane) {
 #pragma unroll
@@ -384,10 +248,7 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
     __builtin_amdgcn_sched_barrier(0);
     const int lane = s.lane;
     mfma_v16i acc[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+    mfma_zero_tile(acc);
 #pragma unroll
     for (int e = 0; e < 16; ++e)
 #pragma unroll
@@ -422,10 +283,7 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
 #pragma unroll 1
     for (int j = j0; j <= j1; ++j) {
         mfma_v16i acc[2];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
+        mfma_zero_tile(acc);
 #pragma unroll
         for (int p = 0; p < 8; ++p)
 #pragma unroll
@@ -436,12 +294,8 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
 #pragma unroll
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
         // slot j is read by this wave alone, before this write
-        if (rc29_next) {
-            int64_t col[9]; uint32_t l[9];
-            mfma_post_cols(acc, col); mfma_finish_limbs(col, l);
-            const fr_t y = sbox_lazy29(l, c29(rc29_next, j));
-            s.sto(j, recode_next ? recode_signed(y) : y);
-        } else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }
+        if (rc29_next) { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); mfma_finish_limbs(col, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
+        else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }
     }
     __syncthreads();
 }
@@ -503,7 +357,7 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
             pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, (r == half - 1) ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T), true);
     } else
     for (int r = r_begin; r < half; ++r) {
-        if constexpr (T == 17) { pair_sbox_full<T, true>(s, P.rc_full + r * T); pair_apply_mds_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag); }
+        if constexpr (T == 17) { pair_sbox_full<T, true>(s, P.rc_full + r * T); pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, nullptr, true); }
         else { pair_sbox_full<T>(s, P.rc_full + r * T); pair_apply_lu<T>(s, (r == half - 1) ? P.lu_pre29 : P.lu29); }
     }
     fr_t s0 = fr_zero<PF>();
@@ -595,7 +449,7 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
             return out;
         }
         if constexpr (FUSE) pair_mds_sbox_mfma(s, P.mds_frag, r == P.rf - 1 ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T), !(only0 && r + 1 == P.rf - 1));
-        else if constexpr (T == 17) pair_apply_mds_mfma(s, P.mds_frag); else pair_apply_lu<T>(s, P.lu29);
+        else if constexpr (T == 17) pair_mds_sbox_mfma(s, P.mds_frag, nullptr, true); else pair_apply_lu<T>(s, P.lu29);
     }
     return s.ld(0);
 }

@@ -1,4 +1,4 @@
-"""The residue-table form of the t = 17 full rounds' matrix-core product (poseidon_pair.hpp pair_apply_mds_mfma), host side: the int8 fragment
+"""The residue-table form of the t = 17 full rounds' matrix-core product (poseidon_pair.hpp pair_mds_sbox_mfma), host side: the int8 fragment
 tables host_util.hpp mfma_frags builds, read back through their documented lane layout, and the finishing step (fold of the 32 digit sums, signed
 carry pass, product-free reduction: mfma_digits.hpp) over its whole stated input domain |S_c| < 2^24 — both against Python big integers.  CPU only."""
 import ctypes as C

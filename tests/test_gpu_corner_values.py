@@ -2,9 +2,9 @@
 
 The inputs are corners of the four u64 limbs AS STORED (tests/corner_values.py), and for the Poseidon kernels inputs crafted so that the
 S-box outputs of round 0 — the words the signed radix-256 recoding in front of the int8 matrix cores reads — are chosen byte patterns
-(0x80 / 0x7f carry chains across every 32-bit word, all-0xff, the band [2^254, r) ...).  The device keeps its own copies of the recoding, the
-fold and the carry pass, so only device runs on chosen digits can see a mistake in them.  tests/test_corner_values_host.py checks the
-construction itself on the CPU.  Needs an MI355X: `pytest -m gpu`.
+(0x80 / 0x7f carry chains across every 32-bit word, all-0xff, the band [2^254, r) ...).  The recoding, the fold and the carry pass are the host checks'
+statements (mfma_digits.hpp), but the tile layout, the lane exchange and the device compilation of those statements are seen only by device runs on
+chosen digits.  tests/test_corner_values_host.py checks the construction itself on the CPU.  Needs an MI355X: `pytest -m gpu`.
 
 Chosen words in EVERY round: stark_poseidon_params_upload takes arbitrary round constants and the S-box input of every round is state + rc, so
 for one chosen node the constants are picked (corner_values.steered_params / steered_node) such that all 8 t full-round S-box outputs and all rp

@@ -1,7 +1,7 @@
 // tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds, of
 // the lane product of the 8-round partial blocks with the base lane in the tile (finish with base), and of the blocks' H rows of up to 16 + 7 K-steps:
-// the fragment tables (host_util.hpp mfma_frags), the fold + finishing step and the limb-form hand-over to the next S-box (mfma_digits.hpp: finish to
-// limbs, S-box on lazy limbs), against the portable field code.  Meant for a
+// the fragment tables (host_util.hpp mfma_frags), the fold + finishing step and the limb-form hand-over to the next S-box (mfma_digits.hpp, the
+// statements the kernels compile: finish to limbs, S-box on lazy limbs), against the portable field code.  Meant for a
 // sanitizer build; tools/mfma_finish_sanitize.sh builds it with AddressSanitizer + UBSan and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I stark_mlwe_amd/csrc tools/mfma_finish_check.cpp -o tools/bin/mfma_finish_check
 #include <cstdio>
@@ -11,15 +11,8 @@
 #include "host_util.hpp"
 #include "mfma_digits.hpp"
 using namespace stark;
-typedef PallasFr PF;
 
-static fr_t finish(const int32_t* S) {
-    int32_t lo[16], hi[16];
-    for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
-    int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
-    mfma_fold_rows(col, lo, hi);
-    return mfma_finish_cols(col);
-}
+static fr_t finish(const int32_t* S) { int64_t col[9]; mfma_cols_of_sums(S, col); return mfma_finish_cols(col); }
 // sum_c S_c 256^c mod r as a plain integer, through the field code
 static fr_t reference(const int32_t* S) {
     fr_t acc = host::h_zero(), w = host::h_one(); const fr_t k256 = fr_from_u64<PF>(256);
@@ -147,12 +140,7 @@ int main() {
     // canonical sum, for every crafted case against eight constants and every random case against one.  (iii) every limb at its maximum, the top limbs at the
     // ends of their ranges: the same steps with 128-bit columns (Lazy29Wide) agree and no column reaches 2^64.
     if (kc.rc_full29.size() != (size_t)8 * 17 * 9) { fprintf(stderr, "rc_full29 missing\n"); return 1; }
-    auto finish_limbs = [](const int32_t* S, uint32_t* l) {
-        int32_t lo[16], hi[16];
-        for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
-        int64_t col[9]; for (int k = 0; k < 9; ++k) col[k] = 0;
-        mfma_fold_rows(col, lo, hi);
-        mfma_finish_limbs(col, l); };
+    auto finish_limbs = [](const int32_t* S, uint32_t* l) { int64_t col[9]; mfma_cols_of_sums(S, col); mfma_finish_limbs(col, l); };
     for (size_t ci = 0; ci < cases.size(); ++ci) {
         uint32_t l[9]; finish_limbs(cases[ci].data(), l);
         bool ok = l[8] < (1u << 24) && l[8] >= (1u << 22) - 1 && l[8] <= (1u << 23);
