@@ -655,11 +655,10 @@ int hc_sc_decode_fr(const uint8_t* blob, size_t len, size_t off, uint64_t* out4)
     std::vector<uint32_t> w((len + 3) / 4 + 2, 0u); memcpy(w.data(), blob, len);
     fr_t x; const bool ok = sc_decode_fr(w.data(), (uint32_t)off, 0u, x); st4(out4, x); return ok ? 1 : 0;
 }
-// verify_plain (mf = 0; labels may be null) / verify_mf (mf = 1) of `batch` proofs through the batch plan: decode, the transcript streams,
-// the DS groups in depth order (cparams: MerkleCommitment's parameters), the checks.  accepted[i] = 1 / 0.
-int hc_sumcheck_verify_batch(void* tparams, void* cparams, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* labels, int32_t* accepted) {
-    ScVerifyPlan V; if (sc_verify_plan(mf, batch, proofs, lens, labels, V)) return -1;
-    HcParams *tp = (HcParams*)tparams, *cp = (HcParams*)cparams;
+// One plan run step by step: decode, the transcript streams, the DS groups in depth order (cp: MerkleCommitment's parameters), the checks.
+// accepted[i] = 1 / 0 for the V.batch proofs of the plan.
+static void run_sc_plan_host(ScVerifyPlan& V, HcParams* tp, HcParams* cp, int32_t* accepted) {
+    const int mf = V.mf;
     std::vector<fr_t> pool = hc_fr_block(std::max<size_t>(V.pool_slots, 1));       // run_sc_verify_batch: the pool, the states and the cursors are not uploaded
     for (size_t j = 0; j < V.n_dec; ++j) if (!sc_decode_fr(V.blob.data(), V.dec_off[j], V.dec_proof[j], pool[j])) V.flag[V.dec_proof[j] & ~kScClaim] = 0;
     std::vector<fr_t> state = hc_fr_block(17 * std::max<size_t>(V.n_inst, 1)); std::vector<uint32_t> pos(std::max<size_t>(V.n_inst, 1), 0x01010101u * (uint32_t)g_alloc_fill);
@@ -677,7 +676,25 @@ int hc_sumcheck_verify_batch(void* tparams, void* cparams, int mf, size_t batch,
         const uint32_t* r = V.rec.data() + 8 * j;
         if (!(mf ? sc_check_mf(pool.data(), r) : sc_check_plain(pool.data(), r))) V.flag[mf ? r[1] : r[0]] = 0;
     }
-    for (size_t b = 0; b < batch; ++b) accepted[b] = V.flag[b];
+    for (size_t b = 0; b < V.batch; ++b) accepted[b] = V.flag[b];
+}
+// verify_plain (mf = 0; labels may be null) / verify_mf (mf = 1) of `batch` proofs through one batch plan.  accepted[i] = 1 / 0.
+int hc_sumcheck_verify_batch(void* tparams, void* cparams, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* labels, int32_t* accepted) {
+    ScVerifyPlan V; if (sc_verify_plan(mf, batch, proofs, lens, labels, V)) return -1;
+    run_sc_plan_host(V, (HcParams*)tparams, (HcParams*)cparams, accepted);
+    return 0;
+}
+// the same cut into plans of at most max_slots pool slots each (at least one proof a plan), as the device driver cuts a batch under the
+// context's "sumcheck_verify_batch_max_slots"
+int hc_sumcheck_verify_batch_slots(void* tparams, void* cparams, int mf, size_t batch, const uint8_t* const* proofs, const size_t* lens, const uint64_t* labels, size_t max_slots, int32_t* accepted) {
+    size_t b0 = 0;
+    while (b0 < batch) {
+        ScVerifyPlan V; bool fits = false;
+        const size_t b1 = sc_verify_plan_some(mf, b0, batch, proofs, lens, labels, max_slots, V, fits);
+        if (!fits) return -1;
+        run_sc_plan_host(V, (HcParams*)tparams, (HcParams*)cparams, accepted + b0);
+        b0 = b1;
+    }
     return 0;
 }
 // the device steps of the plan as (kind, count) rows in launch order (ScVerifyPlan::steps); returns their number (at most cap written)

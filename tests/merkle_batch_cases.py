@@ -45,9 +45,15 @@ def oracle_verify_lib():
     return C.CDLL(out)
 
 
-def oracle_verify(cfg_arity, label, root, idx, values, proof: bytes):
+def oracle_verify(cfg_arity, label, root, idx, values, proof: bytes, commitment=False):
+    """the oracle's verify_many_ds over proof bytes: 1 accept, 0 reject, -1 where the reference would panic; commitment: under MerkleCommitment's
+    parameters (arity 16, "POSEIDON-T17-X5-SEED": the trees of the sum-check proofs) instead of poseidon_params_for_arity(cfg_arity)"""
     ix = np.ascontiguousarray(idx, dtype=np.uint64); v = np.ascontiguousarray(values, dtype=np.uint64); r = np.ascontiguousarray(root, dtype=np.uint64)
     buf = (C.c_uint8 * max(1, len(proof))).from_buffer_copy(proof or b"\0")
+    if commitment:
+        assert cfg_arity == 16
+        return oracle_verify_lib().om_verify_many_ds_commitment(C.c_uint64(label), r.ctypes.data_as(C.c_void_p), ix.ctypes.data_as(C.c_void_p), C.c_size_t(len(ix)),
+                                                                v.ctypes.data_as(C.c_void_p), buf, C.c_size_t(len(proof)))
     return oracle_verify_lib().om_verify_many_ds(C.c_size_t(cfg_arity), C.c_uint64(label), r.ctypes.data_as(C.c_void_p), ix.ctypes.data_as(C.c_void_p), C.c_size_t(len(ix)),
                                                  v.ctypes.data_as(C.c_void_p), buf, C.c_size_t(len(proof)))
 

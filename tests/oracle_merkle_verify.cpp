@@ -35,6 +35,15 @@ extern "C" int om_verify_many_ds(size_t cfg_arity, uint64_t label, const uint64_
     for (size_t i = 0; i < k; ++i) v[i] = Fr::from_raw(values + 4 * i);
     try { return verify_many_ds(Fr::from_raw(root), ix, v, pr, label, poseidon_params_for_arity(cfg_arity)) ? 1 : 0; } catch (...) { return -1; }
 }
+// the same under MerkleCommitment's parameters (commitment/src/lib.rs:48-51: arity 16, "POSEIDON-T17-X5-SEED"): the openings inside a ProofMF
+extern "C" int om_verify_many_ds_commitment(uint64_t label, const uint64_t* root, const size_t* idx, size_t k, const uint64_t* values, const uint8_t* proof, size_t len) {
+    static const PoseidonParams params = generate_params_t17_x5(bytes_of("POSEIDON-T17-X5-SEED"));
+    Dec d{proof, len}; MerkleProof pr;
+    if (!d.mproof(pr)) return 0;
+    std::vector<size_t> ix(idx, idx + k); std::vector<Fr> v(k);
+    for (size_t i = 0; i < k; ++i) v[i] = Fr::from_raw(values + 4 * i);
+    try { return verify_many_ds(Fr::from_raw(root), ix, v, pr, label, params) ? 1 : 0; } catch (...) { return -1; }
+}
 // the same for verify_pairs_ds over (f[i], cp[i])
 extern "C" int om_verify_pairs_ds(size_t cfg_arity, uint64_t label, const uint64_t* root, const size_t* idx, size_t k, const uint64_t* f, const uint64_t* cp, const uint8_t* proof, size_t len) {
     Dec d{proof, len}; MerkleProof pr;

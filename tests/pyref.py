@@ -195,3 +195,184 @@ def from_limbs(l, p=P_PALLAS):
 def dft(a, w, p):
     n = len(a)
     return [sum(a[j] * pow(w, i * j, p) for j in range(n)) % p for i in range(n)]
+
+
+# ---- the sum-check channel and its proofs (crates/channel/src/lib.rs, as restated in oracle/channel.hpp) ----------------------------------
+def le64(x):
+    return struct.pack("<Q", x)
+
+
+class Channel:
+    """ProverChannel / VerifierChannel: one transcript flow (channel/src/lib.rs:7-117)"""
+
+    def __init__(self, label: bytes):
+        self.tr = Transcript(label)
+
+    def bytes(self, b: bytes):
+        self.tr.absorb_bytes(b)
+
+    def send_digest(self, label: bytes, d):
+        self.bytes(b"CHAN/SEND/DIGEST"); self.bytes(label); self.tr.absorb_field(d)
+
+    def challenge_scalar(self, label: bytes):
+        return self.tr.challenge(label)
+
+    def send_opening(self, indices, values, proof):
+        """proof: the dict of mproof_* below (elements as integers)"""
+        self.bytes(b"CHAN/SEND/OPEN")
+        for i in indices:
+            self.tr.absorb_bytes(le64(i))
+        for v in values:
+            self.tr.absorb_field(v)
+        self.bytes(b"PROOF/ARITY"); self.tr.absorb_bytes(le64(proof["arity"]))
+        self.bytes(b"PROOF/GROUP_SIZES")
+        for lvl in proof["group_sizes"]:
+            self.tr.absorb_bytes(le64(len(lvl)))
+            for sz in lvl:
+                self.tr.absorb_bytes(bytes([sz]))
+        self.bytes(b"PROOF/SIBLINGS")
+        for lvl in proof["siblings"]:
+            self.tr.absorb_bytes(le64(len(lvl)))
+            for s in lvl:
+                self.tr.absorb_field(s)
+
+
+def mf_round_challenge_from_root(round_idx, prev_root):
+    """channel/src/lib.rs:592-598: r_i is a function of the previous root alone"""
+    tmp = Transcript(b"SUMCHECK-MF/ROUND-CHAL")
+    tmp.absorb_bytes(b"SUMCHECK/MF/R"); tmp.absorb_bytes(le64(round_idx)); tmp.absorb_field(prev_root % P_PALLAS)
+    return tmp.challenge(b"r_i")
+
+
+def mf_query_index(r, half):
+    """channel/src/lib.rs:667-676: XOR of the four 64-bit limbs of the canonical value, mod half"""
+    m = (1 << 64) - 1
+    return ((r & m) ^ ((r >> 64) & m) ^ ((r >> 128) & m) ^ (r >> 192)) % half
+
+
+class ByteRd:
+    """a strict little-endian reader: any read past the end raises ValueError"""
+
+    def __init__(self, b, pos=0):
+        self.b, self.pos = bytes(b), pos
+
+    def take(self, n):
+        if self.pos + n > len(self.b):
+            raise ValueError("short read")
+        out = self.b[self.pos:self.pos + n]; self.pos += n; return out
+
+    def u64(self): return struct.unpack("<Q", self.take(8))[0]
+    def u8(self): return self.take(1)[0]
+    def el(self): return int.from_bytes(self.take(32), "little")          # the 256-bit value as it stands: it may be >= r
+
+    def fbytes(self):
+        if self.u64() != 32:
+            raise ValueError("FBytes length")
+        return self.el()
+
+    def idxs(self): return [self.u64() for _ in range(self.u64())]
+    def fvec(self): return [self.fbytes() for _ in range(self.u64())]
+    def done(self): return self.pos == len(self.b)
+
+
+def _el(x): return int(x).to_bytes(32, "little")
+def _fb(x): return le64(32) + _el(x)
+def _idxs(v): return le64(len(v)) + b"".join(le64(i) for i in v)
+def _fvec(v): return le64(len(v)) + b"".join(_fb(x) for x in v)
+
+
+# A Merkle proof is a dict {arity, group_sizes: [bytes], indices: [int], siblings: [[int]]}.  Two encodings:
+#   bincode MerkleProofBytes (channel/src/lib.rs:974-979): arity | group_sizes | indices | siblings of FBytes        (inside ProofMF)
+#   canonical (DESIGN.md §7):                              indices | siblings of 32-byte elements | group_sizes | arity (the C-ABI, DEEP-FRI)
+def mproof_read_bincode(rd):
+    arity = rd.u64(); gs = [rd.take(rd.u64()) for _ in range(rd.u64())]; ix = rd.idxs(); sib = [rd.fvec() for _ in range(rd.u64())]
+    return dict(arity=arity, group_sizes=gs, indices=ix, siblings=sib)
+
+
+def mproof_bincode(p):
+    return (le64(p["arity"]) + le64(len(p["group_sizes"])) + b"".join(le64(len(g)) + bytes(g) for g in p["group_sizes"]) + _idxs(p["indices"])
+            + le64(len(p["siblings"])) + b"".join(_fvec(l) for l in p["siblings"]))
+
+
+def mproof_read_canonical(rd):
+    """also records sib_off[level][j], the byte offset of each sibling in the buffer read"""
+    ix = rd.idxs(); sib, off = [], []
+    for _ in range(rd.u64()):
+        k = rd.u64(); off.append([rd.pos + 32 * j for j in range(k)]); sib.append([rd.el() for _ in range(k)])
+    gs = [rd.take(rd.u64()) for _ in range(rd.u64())]; arity = rd.u64()
+    return dict(arity=arity, group_sizes=gs, indices=ix, siblings=sib, sib_off=off)
+
+
+def mproof_canonical(p):
+    return (_idxs(p["indices"]) + le64(len(p["siblings"])) + b"".join(le64(len(l)) + b"".join(_el(x) for x in l) for l in p["siblings"])
+            + le64(len(p["group_sizes"])) + b"".join(le64(len(g)) + bytes(g) for g in p["group_sizes"]) + le64(p["arity"]))
+
+
+def mproof_parse_canonical(b):
+    rd = ByteRd(b); p = mproof_read_canonical(rd)
+    if not rd.done():
+        raise ValueError("trailing bytes")
+    return p
+
+
+# ProofPlain {root, rounds: [[c0, c1]], final_eval} and ProofMF {initial_root, rounds: [round], final_eval} with
+# round = {c0, c1, next_root, cur_indices, cur_values, cur_proof, next_indices, next_values, next_proof} (channel/src/lib.rs:925-979), bincode 1.x
+def parse_proof_plain(b):
+    rd = ByteRd(b); root = rd.fbytes(); rounds = [[rd.fbytes(), rd.fbytes()] for _ in range(rd.u64())]
+    if rd.u8() != 0:
+        raise ValueError("extra_openings")
+    fin = rd.fbytes()
+    if not rd.done():
+        raise ValueError("trailing bytes")
+    return dict(root=root, rounds=rounds, final_eval=fin)
+
+
+def encode_proof_plain(P):
+    return _fb(P["root"]) + le64(len(P["rounds"])) + b"".join(_fb(c0) + _fb(c1) for c0, c1 in P["rounds"]) + b"\0" + _fb(P["final_eval"])
+
+
+def parse_proof_mf(b):
+    rd = ByteRd(b); root = rd.fbytes(); rounds = []
+    for _ in range(rd.u64()):
+        R = dict(c0=rd.fbytes(), c1=rd.fbytes(), next_root=rd.fbytes())
+        R["cur_indices"] = rd.idxs(); R["cur_values"] = rd.fvec(); R["cur_proof"] = mproof_read_bincode(rd)
+        R["next_indices"] = rd.idxs(); R["next_values"] = rd.fvec(); R["next_proof"] = mproof_read_bincode(rd)
+        rounds.append(R)
+    fin = rd.fbytes()
+    if not rd.done():
+        raise ValueError("trailing bytes")
+    return dict(initial_root=root, rounds=rounds, final_eval=fin)
+
+
+def encode_proof_mf(P):
+    out = _fb(P["initial_root"]) + le64(len(P["rounds"]))
+    for R in P["rounds"]:
+        out += _fb(R["c0"]) + _fb(R["c1"]) + _fb(R["next_root"])
+        out += _idxs(R["cur_indices"]) + _fvec(R["cur_values"]) + mproof_bincode(R["cur_proof"])
+        out += _idxs(R["next_indices"]) + _fvec(R["next_values"]) + mproof_bincode(R["next_proof"])
+    return out + _fb(P["final_eval"])
+
+
+def parse_deep_fri_proof(b):
+    """The DEEP-FRI proof encoding (decode_proof of csrc/fri_verify.hpp), with the byte offset of every root (root_off[l]) and,
+    through mproof_read_canonical, of every sibling; each Merkle proof also keeps its own byte range (span)."""
+    rd = ByteRd(b); nr = rd.u64(); root_off = [rd.pos + 32 * i for i in range(nr)]; roots = [rd.el() for _ in range(nr)]
+    layers = []
+
+    def mp():
+        a = rd.pos; p = mproof_read_canonical(rd); p["span"] = (a, rd.pos); return p
+    for _ in range(rd.u64()):
+        h = rd.u8()
+        if h > 1:
+            raise ValueError("bool")
+        ci = rd.idxs(); cp = mp(); pi = rd.idxs(); pp = mp()
+        layers.append(dict(hashed=h, child_indices=ci, child_proof=cp, parent_indices=pi, parent_proof=pp))
+    final_proof = mp(); queries = []
+    for _ in range(rd.u64()):
+        refs = [dict(i=rd.u64(), child_pos=rd.u64(), parent_index=rd.u64(), parent_pos=rd.u64()) for _ in range(rd.u64())]
+        pays = [dict(f_i=rd.el(), s_i=rd.el(), f_parent_b=rd.el(), s_parent_b=rd.el()) for _ in range(rd.u64())]
+        queries.append(dict(refs=refs, pays=pays, final_index=rd.u64(), final_f=rd.el(), final_s=rd.el()))
+    n0 = rd.u64(); omega0 = rd.el()
+    if not rd.done():
+        raise ValueError("trailing bytes")
+    return dict(roots=roots, root_off=root_off, layers=layers, final_proof=final_proof, queries=queries, n0=n0, omega0=omega0)
