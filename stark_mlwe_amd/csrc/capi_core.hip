@@ -112,10 +112,19 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
     // int8 MFMA fragments of the dense matrices (t = 17), raw bytes in the same blob
     const size_t o_frag = blob.size(), frag_elems = (k.mds_frag.size() + sizeof(fr_t) - 1) / sizeof(fr_t);
     if (!k.mds_frag.empty()) { blob.resize(o_frag + 2 * frag_elems); memcpy((void*)(blob.data() + o_frag), k.mds_frag.data(), k.mds_frag.size()); memcpy((void*)(blob.data() + o_frag + frag_elems), k.mds_pre_frag.data(), k.mds_pre_frag.size()); }
-    // int8 MFMA fragments of the 8-round partial blocks (t = 17, rp % 8 == 0): E-product, lane product with the unit fragment, Gamma terms; owned and freed with the set
-    const size_t o_b8 = blob.size(), ef_elems = (k.blk8_efrag.size() + sizeof(fr_t) - 1) / sizeof(fr_t), lf_elems = (k.blk8_lfrag.size() + sizeof(fr_t) - 1) / sizeof(fr_t), gf_elems = (k.blk8_gfrag.size() + sizeof(fr_t) - 1) / sizeof(fr_t);
-    if (!k.blk8_efrag.empty()) { blob.resize(o_b8 + ef_elems + lf_elems + gf_elems); memcpy((void*)(blob.data() + o_b8), k.blk8_efrag.data(), k.blk8_efrag.size()); memcpy((void*)(blob.data() + o_b8 + ef_elems), k.blk8_lfrag.data(), k.blk8_lfrag.size());
-                                 memcpy((void*)(blob.data() + o_b8 + ef_elems + lf_elems), k.blk8_gfrag.data(), k.blk8_gfrag.size()); }
+    // The 8-round partial blocks (t = 17, rp % 8 == 0, M[0][0] != 0), the SCALED family (host_util.hpp blk8s_*): int8 MFMA fragments of the E-product, of the lane
+    // product followed by the shared unit fragment, of the Gamma terms; then the scaled round constants with the unscale multiplier right behind them (PoseidonDev::blk8_unscale29).  The unscaled family stays on the
+    // host.  Owned and freed with the set.
+    const size_t o_b8 = blob.size(), ef_elems = (k.blk8s_efrag.size() + sizeof(fr_t) - 1) / sizeof(fr_t), lf_bytes = k.blk8s_lfrag.size() + 1024, lf_elems = (lf_bytes + sizeof(fr_t) - 1) / sizeof(fr_t),
+                 gf_elems = (k.blk8s_gfrag.size() + sizeof(fr_t) - 1) / sizeof(fr_t), rcs_elems = k.rc_partial_scaled.size(), un_elems = (k.blk8_unscale29.size() * 4 + sizeof(fr_t) - 1) / sizeof(fr_t);
+    const bool have_b8 = !k.blk8s_efrag.empty();
+    if (have_b8) { blob.resize(o_b8 + ef_elems + lf_elems + gf_elems + rcs_elems + un_elems);
+                   int8_t* const b8 = (int8_t*)(blob.data() + o_b8);
+                   memcpy(b8, k.blk8s_efrag.data(), k.blk8s_efrag.size());
+                   memcpy(b8 + ef_elems * sizeof(fr_t), k.blk8s_lfrag.data(), k.blk8s_lfrag.size()); memcpy(b8 + ef_elems * sizeof(fr_t) + k.blk8s_lfrag.size(), k.blk8_lfrag.data() + k.blk8_lfrag.size() - 1024, 1024);
+                   memcpy(b8 + (ef_elems + lf_elems) * sizeof(fr_t), k.blk8s_gfrag.data(), k.blk8s_gfrag.size());
+                   memcpy(b8 + (ef_elems + lf_elems + gf_elems) * sizeof(fr_t), k.rc_partial_scaled.data(), rcs_elems * sizeof(fr_t));
+                   memcpy(b8 + (ef_elems + lf_elems + gf_elems + rcs_elems) * sizeof(fr_t), k.blk8_unscale29.data(), k.blk8_unscale29.size() * 4); }
     STARK_HIP(ctx, P->blob.alloc(blob.size() * sizeof(fr_t)));
     fr_t* const dev = P->blob.fr();
     STARK_HIP(ctx, hipMemcpyAsync(dev, blob.data(), blob.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
@@ -130,9 +139,10 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
       const uint32_t* ch = P->dev.mds_pre29 + k.mds_pre29.size();
       P->dev.chain_a = k.chain_a.empty() ? nullptr : ch; P->dev.chain_g = k.chain_a.empty() ? nullptr : ch + k.chain_a.size(); P->dev.chain_w = k.chain_a.empty() ? nullptr : ch + k.chain_a.size() + k.chain_g.size();
       P->dev.rc_full29 = ch + k.chain_a.size() + k.chain_g.size() + k.chain_w.size(); }
-    P->dev.blk8_efrag = k.blk8_efrag.empty() ? nullptr : (const void*)(dev + o_b8); P->dev.blk8_lfrag = k.blk8_efrag.empty() ? nullptr : (const void*)(dev + o_b8 + ef_elems);
-    P->dev.blk8_gfrag = k.blk8_gfrag.empty() ? nullptr : (const void*)(dev + o_b8 + ef_elems + lf_elems);
-    P->dev.blk8_unit_frag = k.blk8_efrag.empty() ? nullptr : (const void*)((const int8_t*)P->dev.blk8_lfrag + k.blk8_lfrag.size() - 1024);
+    P->dev.blk8_efrag = have_b8 ? (const void*)(dev + o_b8) : nullptr; P->dev.blk8_lfrag = have_b8 ? (const void*)(dev + o_b8 + ef_elems) : nullptr;
+    P->dev.blk8_gfrag = have_b8 ? (const void*)(dev + o_b8 + ef_elems + lf_elems) : nullptr;
+    P->dev.blk8_unit_frag = have_b8 ? (const void*)((const int8_t*)P->dev.blk8_lfrag + k.blk8s_lfrag.size()) : nullptr;
+    P->dev.rc_partial_scaled = have_b8 ? dev + o_b8 + ef_elems + lf_elems + gf_elems : nullptr;
     P->dev.mds_frag = k.mds_frag.empty() ? nullptr : (const void*)(dev + o_frag); P->dev.mds_pre_frag = k.mds_frag.empty() ? nullptr : (const void*)(dev + o_frag + frag_elems);
     return STARK_OK;
 }
@@ -243,6 +253,7 @@ static const OptionDef kOptions[] = {
     {"sponge_debug", [](stark_ctx::Options& o, int64_t v) -> const char* { o.sponge_debug = (int)v; return nullptr; }},
     {"merkle_node16_pair", [](stark_ctx::Options& o, int64_t v) -> const char* { o.merkle_node16_pair = v != 0; return nullptr; }},
     {"poseidon_block8", [](stark_ctx::Options& o, int64_t v) -> const char* { o.poseidon_block8 = v != 0; return nullptr; }},
+    {"merkle_wave_pair", [](stark_ctx::Options& o, int64_t v) -> const char* { o.merkle_wave_pair = v != 0; return nullptr; }},
     {"fri_side_pair", [](stark_ctx::Options& o, int64_t v) -> const char* { o.fri_side_pair = v != 0; return nullptr; }},
     {"sumcheck_verify_batch_max_slots", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1) return "at least 1"; o.sumcheck_verify_batch_max_slots = (size_t)v; return nullptr; }},
     {"ntt_batch_max_elems", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < 1 || v > ((int64_t)1 << 28)) return "1..2^28"; o.ntt_batch_max_elems = (size_t)v; return nullptr; }},

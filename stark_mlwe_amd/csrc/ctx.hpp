@@ -106,6 +106,7 @@ struct stark_ctx {
         bool poseidon_lane_only = false; // one-lane-per-sponge kernels instead of the wave-pair / one-wave forms (diagnostic)
         bool merkle_node16_pair = true;  // t = 17 Merkle levels of > 4096 nodes with exactly 16 children each: the fixed two-permutation kernel k_node16_pair; 0 = the generic k_hash_ds2 (comparison)
         bool poseidon_block8 = true;     // t = 17 wave-pair kernels (k_leaf_pair2, k_hash_ds2<17>, k_node16_pair), parameter sets with rp % 8 == 0: partial rounds in blocks of 8 with the E-product and the lane product on the matrix cores; 0 = blocks of 4 on the vector ALU (comparison)
+        bool merkle_wave_pair = false;   // Merkle levels of t = 9, 17 in the wave-pair form at EVERY size, as under side_commit (diagnostic: the wave-pair kernels at their smallest shapes)
         bool fri_side_pair = true;       // fri_build: the small layers' commitments on the side stream in the wave-pair form at every size (see side_commit); 0 = the latency forms (comparison)
         size_t sumcheck_verify_batch_max_slots = (size_t)1 << 25;   // a plan of the batched sum-check verifiers is run once it holds this many pool slots (1 GiB of field elements): device memory stays bounded whatever the batch
         size_t ntt_batch_max_elems = (size_t)1 << 24;    // stark_ntt_batch_dev / stark_lde_batch_dev cut a batch into passes of at most this many output elements (ntt_batch_plan.hpp): 512 MiB of outputs and as much scratch per pass

@@ -5,7 +5,10 @@
 //   * ChaCha12 block function        -> `StdRng::from_seed` + `gen::<u64>()` (fri.rs:66-71,185-186)
 //   * from_le_bytes_mod_order, tags  -> transcript framing constants (transcript/src/lib.rs:13-41)
 //   * constant tables for the kernels: LU factors of the MDS matrix and the sparse factorisation of
-//     the partial rounds (algebraically identical to the dense rounds of poseidon/src/lib.rs:31-68).
+//     the partial rounds (algebraically identical to the dense rounds of poseidon/src/lib.rs:31-68);
+//     for t = 17 the int8 residue tables of the matrix-core products, those of the 8-round partial
+//     blocks in two families: unscaled (host checks) and with the S-box chain scaled by lambda_q,
+//     which is what the device gets (KernelConsts blk8_* / blk8s_*).
 // Written independently of oracle/ (which is test infrastructure and is never linked here).
 #pragma once
 #include <cstdint>
@@ -235,6 +238,24 @@ struct KernelConsts {
     //   gamma8_29  [rp/8][28][9]  the same Gamma_{q,p} scaled like gamma29: host checks and tools only, not uploaded
     std::vector<int8_t> blk8_efrag, blk8_lfrag, blk8_gfrag;
     std::vector<uint32_t> gamma8_29;
+    // The same blocks with the chain SCALED, the family the device gets: wave X carries lambda_q X_q instead of X_q, with lambda_0 = 1 and
+    //     lambda_{q+1} = lambda_q^5 kappa / a      (kappa = 2^-20, fr_pow5_r29's scale; a = M[0][0], every round's a_q; q runs over all rp rounds),
+    // so that yt_q = fr_pow5_r29(lambda_q X_q + lambda_q c_q) = kappa lambda_q^5 y_q enters the next chain value with coefficient exactly 1:
+    //     lambda_{q+1} X_{q+1} = yt_q + lambda_{q+1} ( E_q + sum_{p<q} Gamma_{q,p} y_p ).
+    // No a_q y_q product is left in a round; every lambda sits on a constant left factor (exact field arithmetic: identical bits):
+    //   blk8_lambda        [rp + 1]      lambda_q, host side only (tests, tools)
+    //   blk8s_efrag        [rp/8][8][16] fragment of u_{q,j} lambda_{q+1}
+    //   blk8s_lfrag        [rp/8][16][8] fragment of w_{p,j} / (kappa lambda_p^5): its inputs are the yt_p.  No unit fragment of its own: blk8_lfrag's serves both
+    //   blk8s_gfrag        [rp/8][28]    fragment of Gamma_{q,p} lambda_{q+1} / (kappa lambda_p^5)
+    //   rc_partial_scaled  [rp]          lambda_q c_q, stored form
+    //   blk8_unscale29     [9]           1 / lambda_rp as a multiplier-table entry (fr29_const_from, no 2^20: it meets the chain value, not an S-box output):
+    //                                    one product per permutation brings X_rp back
+    // The fragments are still signed radix-256 digits of residues in [0, r): the digit-sum bounds of the unscaled family hold unchanged.
+    // lambda needs M[0][0] != 0.  Every set that gets this far has it: the in-place LU of M (lu_pack, no pivoting) refuses a zero M[0][0] first, and such a
+    // set is not ok at all.
+    std::vector<fr_t> blk8_lambda, rc_partial_scaled;
+    std::vector<int8_t> blk8s_efrag, blk8s_lfrag, blk8s_gfrag;
+    std::vector<uint32_t> blk8_unscale29;
     bool ok = false;
 };
 // scaled(i) == true: the entry multiplies an S-box output, which fr_pow5_r29 delivers as x^5 / 2^20 (fr29.hpp)
@@ -347,10 +368,20 @@ inline KernelConsts make_kernel_consts(const PoseidonConsts& c) {
     k.rc_full29.resize(k.rc_full.size() * 9);
     for (size_t i = 0; i < k.rc_full.size(); ++i) { const fr29_t u = fr29_unpack(k.rc_full[i]); for (int j = 0; j < 9; ++j) k.rc_full29[9 * i + j] = u.l[j]; }
     if (t == 17) { k.mds_frag = mfma_frags(k.mds, t); k.mds_pre_frag = mfma_frags(k.mds_pre, t); }      // the wave-pair kernels' full rounds (poseidon_pair.hpp)
-    if (t == 17 && c.rp % 8 == 0) {                                                                      // blocks of 8 partial rounds on the matrix cores (poseidon_pair.hpp)
+    if (t == 17 && c.rp % 8 == 0) {                                             // blocks of 8 partial rounds on the matrix cores (poseidon_pair.hpp)
         const int nb = c.rp / 8, w = 2 * t - 1;
         const fr_t s20 = fr_from_u64<PF>(1ull << FR29_SBOX_SHIFT);
         std::vector<fr_t> g8((size_t)nb * 28, h_zero()), um((size_t)8 * n), wm((size_t)n * 8);
+        // the scaled chain: lambda_q and yinv_q = 1 / (kappa lambda_q^5), the factor that turns yt_q back into y_q
+        const fr_t kappa = fr_inv<PF>(s20), a_inv = fr_inv<PF>(c.mds[0]);
+        std::vector<fr_t> yinv(c.rp), ums((size_t)8 * n), wms((size_t)n * 8);
+        k.blk8_lambda.assign((size_t)c.rp + 1, h_one()); k.rc_partial_scaled.resize(c.rp);
+        for (int q = 0; q < c.rp; ++q) {
+            const fr_t l5k = h_mul(fr_pow5<PF>(k.blk8_lambda[q]), kappa);
+            k.blk8_lambda[q + 1] = h_mul(l5k, a_inv); yinv[q] = fr_inv<PF>(l5k);
+            k.rc_partial_scaled[q] = h_mul(k.blk8_lambda[q], c.rc_partial[q]);
+        }
+        k.blk8_unscale29.resize(9); fr29_const_from<PF>(fr_inv<PF>(k.blk8_lambda[c.rp]), k.blk8_unscale29.data());
         for (int b = 0; b < nb; ++b) {
             for (int q = 0; q < 8; ++q) for (int j = 1; j < t; ++j) {
                 um[(size_t)q * n + (j - 1)] = k.sparse[(size_t)(8 * b + q) * w + j];
@@ -363,7 +394,14 @@ inline KernelConsts make_kernel_consts(const PoseidonConsts& c) {
                 for (int j = 0; j < n; ++j) acc = h_add(acc, h_mul(um[(size_t)q * n + j], wm[(size_t)j * 8 + p2]));
                 g8[(size_t)b * 28 + q * (q - 1) / 2 + p2] = acc;
                 k.blk8_gfrag.resize(k.blk8_gfrag.size() + 1024); mfma_frag_of(h_mul(acc, s20), &k.blk8_gfrag[k.blk8_gfrag.size() - 1024]);
+                k.blk8s_gfrag.resize(k.blk8s_gfrag.size() + 1024); mfma_frag_of(h_mul(h_mul(acc, k.blk8_lambda[8 * b + q + 1]), yinv[8 * b + p2]), &k.blk8s_gfrag[k.blk8s_gfrag.size() - 1024]);
             }
+            for (int q = 0; q < 8; ++q) for (int j = 0; j < n; ++j) {
+                ums[(size_t)q * n + j] = h_mul(um[(size_t)q * n + j], k.blk8_lambda[8 * b + q + 1]);
+                wms[(size_t)j * 8 + q] = h_mul(wm[(size_t)j * 8 + q], yinv[8 * b + q]);
+            }
+            const std::vector<int8_t> efs = mfma_frags(ums.data(), 8, n, h_one()), lfs = mfma_frags(wms.data(), n, 8, h_one());
+            k.blk8s_efrag.insert(k.blk8s_efrag.end(), efs.begin(), efs.end()); k.blk8s_lfrag.insert(k.blk8s_lfrag.end(), lfs.begin(), lfs.end());
         }
         k.blk8_lfrag.resize(k.blk8_lfrag.size() + 1024); mfma_frag_of(h_one(), &k.blk8_lfrag[k.blk8_lfrag.size() - 1024]);
         k.gamma8_29 = to_radix29(g8, all);

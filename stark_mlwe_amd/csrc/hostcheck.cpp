@@ -41,7 +41,7 @@ static void bind(HcParams* P) {
     P->dev.t = P->kc.t; P->dev.rf = P->kc.rf; P->dev.rp = P->kc.rp; P->dev.rc_full = P->kc.rc_full.data(); P->dev.rc_partial = P->kc.rc_partial.data();
     P->dev.lu = P->kc.lu.data(); P->dev.lu_pre = P->kc.lu_pre.data(); P->dev.row0 = P->kc.row0.data(); P->dev.sparse = P->kc.sparse.data(); P->dev.mds = P->kc.mds.data(); P->dev.mds_pre = P->kc.mds_pre.data(); P->dev.gamma = P->kc.gamma.data();
     P->dev.lu29 = P->kc.lu29.data(); P->dev.lu_pre29 = P->kc.lu_pre29.data(); P->dev.row0_29 = P->kc.row0_29.data(); P->dev.sparse29 = P->kc.sparse29.data(); P->dev.gamma29 = P->kc.gamma29.data(); P->dev.mds29 = P->kc.mds29.data(); P->dev.mds_pre29 = P->kc.mds_pre29.data(); P->dev.rc_full29 = P->kc.rc_full29.data();
-    P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr; P->dev.blk8_efrag = nullptr; P->dev.blk8_lfrag = nullptr; P->dev.blk8_unit_frag = nullptr; P->dev.blk8_gfrag = nullptr;
+    P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr; P->dev.blk8_efrag = nullptr; P->dev.blk8_lfrag = nullptr; P->dev.blk8_unit_frag = nullptr; P->dev.blk8_gfrag = nullptr; P->dev.rc_partial_scaled = nullptr;
     P->dev.chain_a = P->kc.chain_a.empty() ? nullptr : P->kc.chain_a.data(); P->dev.chain_g = P->kc.chain_g.empty() ? nullptr : P->kc.chain_g.data(); P->dev.chain_w = P->kc.chain_w.empty() ? nullptr : P->kc.chain_w.data();
 }
 
@@ -273,11 +273,12 @@ int32_t hc_blk8_row23_max(int reset) { return reset ? g_blk8_row23_max.exchange(
 // partial rounds and at the end finish canonical, the first round's S-box stands alone, the last block's lane rows feed the S-box of the round after the partial rounds the same way (element 0 from
 // the chain value) —, the partial rounds in
 // blocks of 8 — lanes recoded, row q = H_q = E_q + sum Gamma y_p as ONE tile of 16 + q K-steps (E fragments against the lanes, blk8_gfrag against the
-// recoded y_0..y_{q-1}), y_q = fr_pow5_r29, a_q y_q from sparse29, lane rows with the unit fragment as the ninth K-step — with blk8_efrag / blk8_gfrag /
-// blk8_lfrag as uploaded.  -1: the set has no block-8 tables; -2: a digit sum out of range.
+// recoded yt_0..yt_{q-1}), the SCALED chain (s0 = lambda_q X_q; yt_q = fr_pow5_r29(s0 + lambda_q c_q); s0 <- yt_q + H_q, no a_q y_q product; one product by
+// 1 / lambda_rp after the last block), lane rows with the unit fragment as the ninth K-step — with blk8s_efrag / blk8s_gfrag / blk8s_lfrag, rc_partial_scaled and
+// blk8_unscale29 as uploaded.  -1: the set has no block-8 tables; -2: a digit sum out of range.
 int hc_permute_block8(void* h, uint64_t* states, size_t n) {
-    HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc; const int t = k.t, half = k.rf / 2, W = 2 * t - 1;
-    if (t != 17 || k.blk8_efrag.empty() || k.blk8_gfrag.empty() || k.mds_frag.empty()) return -1;
+    HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc; const int t = k.t, half = k.rf / 2;
+    if (t != 17 || k.blk8s_efrag.empty() || k.blk8s_gfrag.empty() || k.blk8_unscale29.empty() || k.mds_frag.empty()) return -1;
     const int8_t* unit = k.blk8_lfrag.data() + k.blk8_lfrag.size() - 1024;
     std::vector<fr_t> st(t), xd(t), o(t);
     // pair_sbox_full<17, true>: st (canonical) -> xd
@@ -300,8 +301,8 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
         for (int j = 1; j < t; ++j) rec[j] = recode_signed(st[j]);
         const int nb = k.rp / 8;
         for (int b = 0; b < nb; ++b) {
-            const int8_t* ef = k.blk8_efrag.data() + (size_t)b * 8 * 16 * 1024; const int8_t* lf = k.blk8_lfrag.data() + (size_t)b * 16 * 8 * 1024;
-            const int8_t* gf = k.blk8_gfrag.data() + (size_t)b * 28 * 1024;
+            const int8_t* ef = k.blk8s_efrag.data() + (size_t)b * 8 * 16 * 1024; const int8_t* lf = k.blk8s_lfrag.data() + (size_t)b * 16 * 8 * 1024;
+            const int8_t* gf = k.blk8s_gfrag.data() + (size_t)b * 28 * 1024;
             for (int j = 0; j < 16; ++j) kx[j] = rec[1 + j];
             for (int q = 0; q < 8; ++q) {
                 const int8_t* fr[23]; for (int j = 0; j < 16; ++j) fr[j] = ef + ((size_t)q * 16 + j) * 1024;
@@ -310,11 +311,9 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
                 if (q == 7) { int32_t m = 0; for (int c = 0; c < 32; ++c) m = std::max(m, S[c] < 0 ? -S[c] : S[c]);
                               int32_t seen = g_blk8_row23_max.load(); while (m > seen && !g_blk8_row23_max.compare_exchange_weak(seen, m)) {} }
                 const fr_t H = blk8_finish_sums(S);
-                y[q] = fr_pow5_r29<PF>(fr_add<PF>(s0, k.rc_partial[8 * b + q]));
+                y[q] = fr_pow5_r29<PF>(fr_add<PF>(s0, k.rc_partial_scaled[8 * b + q]));     // s0 = lambda_q X_q: yt_q
                 yd[q] = recode_signed(y[q]);
-                DotAcc acc; acc.init();
-                acc.mac(c29(k.sparse29.data(), (size_t)(8 * b + q) * W), y[q]);
-                s0 = fr_add<PF>(H, acc.finish());
+                s0 = fr_add<PF>(y[q], H);
             }
             for (int j = 1; j < t; ++j) {
                 const int8_t* fr[9]; for (int p2 = 0; p2 < 8; ++p2) fr[p2] = lf + ((size_t)(j - 1) * 8 + p2) * 1024; fr[8] = unit;
@@ -325,6 +324,7 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
                 } else { fr_t z; { const int rc = blk8_tile(fr, yd, 9, z); if (rc) return rc; } rec[j] = recode_signed(z); }
             }
         }
+        s0 = fr_mul_c29(k.blk8_unscale29.data(), s0);                                              // lambda_rp X_rp -> X_rp, once per permutation
         xd[0] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(s0, k.rc_full[(size_t)half * t])));      // element 0 of that S-box from the chain's final value
         for (int r = half; r < k.rf; ++r) { const int rc = product(k.mds_frag, r == k.rf - 1 ? -1 : r + 1); if (rc) return rc; }
         for (int j = 0; j < t; ++j) st4(states + 4 * (s * t + j), st[j]);
@@ -332,9 +332,20 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
     return 0;
 }
 // the block-8 tables of a set: which = 0 blk8_efrag, 1 blk8_lfrag (its last 1 KiB: the unit fragment), 2 gamma8_29 (bytes of the uint32 words), 3 blk8_gfrag;
+// the scaled family: 4 blk8s_efrag, 5 blk8s_lfrag (no unit fragment), 6 blk8s_gfrag, 7 rc_partial_scaled (rp stored field elements), 8 blk8_lambda (rp + 1 stored
+// field elements) followed by the nine uint32 limbs of blk8_unscale29;
 // copies at most cap bytes out, returns the table's length in bytes (0: the set has none)
 size_t hc_blk8_table(void* h, int which, void* out, size_t cap) {
     HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc;
+    if (which >= 4) {
+        std::vector<uint8_t> lam;
+        if (which == 8 && !k.blk8_lambda.empty()) { lam.resize(k.blk8_lambda.size() * sizeof(fr_t) + k.blk8_unscale29.size() * 4);
+            memcpy(lam.data(), k.blk8_lambda.data(), k.blk8_lambda.size() * sizeof(fr_t)); memcpy(lam.data() + k.blk8_lambda.size() * sizeof(fr_t), k.blk8_unscale29.data(), k.blk8_unscale29.size() * 4); }
+        const void* src = which == 4 ? (const void*)k.blk8s_efrag.data() : which == 5 ? (const void*)k.blk8s_lfrag.data() : which == 6 ? (const void*)k.blk8s_gfrag.data() : which == 7 ? (const void*)k.rc_partial_scaled.data() : (const void*)lam.data();
+        const size_t len = which == 4 ? k.blk8s_efrag.size() : which == 5 ? k.blk8s_lfrag.size() : which == 6 ? k.blk8s_gfrag.size() : which == 7 ? k.rc_partial_scaled.size() * sizeof(fr_t) : which == 8 ? lam.size() : 0;
+        if (out && len) memcpy(out, src, std::min(cap, len));
+        return len;
+    }
     const void* src = which == 0 ? (const void*)k.blk8_efrag.data() : which == 1 ? (const void*)k.blk8_lfrag.data() : which == 3 ? (const void*)k.blk8_gfrag.data() : (const void*)k.gamma8_29.data();
     const size_t len = which == 0 ? k.blk8_efrag.size() : which == 1 ? k.blk8_lfrag.size() : which == 3 ? k.blk8_gfrag.size() : k.gamma8_29.size() * 4;
     if (out && len) memcpy(out, src, std::min(cap, len));

@@ -50,6 +50,9 @@ struct DotAcc {
     }
 };
 FR_HD const uint32_t* c29(const uint32_t* base, size_t idx) { return base + 9 * idx; }
+// One product by an entry of a multiplier table (nine limbs, fr29_const_from): canonical c * x.  The unscale of the 8-round blocks' chain value
+// (poseidon_pair.hpp pair_permute), the same statement in the host checks.
+FR_HD fr_t fr_mul_c29(const uint32_t* __restrict__ c, const fr_t& x) { fr_wide29 w; fr_wide29_zero(w); fr_wide29_mac(w, c, fr29_unpack(x)); return fr_wide29_reduce<PF>(w); }
 
 // y = L*(U*x) in place.  U: row i needs x[j>=i] (top-down); unit-lower L: row i needs y[j<i] (bottom-up).
 // Every row is a dot product with wave-uniform constants: the 64-MAC partial products of all its terms

@@ -12,7 +12,7 @@
 //                   - t = 9: as in-place L*(U*x) on the VALU, X taking the even rows and Y the odd rows of each step (rows
 //                     2k/2k+1 read only slots >= 2k, so a single barrier between the step's reads and its two writes keeps it race-free);
 //   * partial rounds, t = 17 with the context option poseidon_block8 (the default): in blocks of 8 whose u-rows and lane updates are two matrix-core
-//     products (pair_block8 below);
+//     products (pair_block8 below), wave X's S-box chain scaled so that no round multiplies by a_q (one product per permutation undoes the scale);
 //   * partial rounds otherwise, in blocks of 4 (see permute_core in poseidon_dev.hpp for the algebra):
 //       phase 1  X runs the S-box chain: x_q, then a_q x_q + sum_{p<q} gamma x_p + its share (lanes 1..NXD) of the
 //                lane dot product from registers; Y computes the other lanes' part of every round's
@@ -193,8 +193,16 @@ __device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const voi
 // The third product of the block algebra rides in the E rows' tiles: H_q = E_q + sum_{p<q} Gamma_{q,p} y_p is row q of a product with constant left
 // factors, and y_0..y_{q-1} are known when round q starts, so row q takes them as q further K-steps (fragments of Gamma_{q,p} * 2^20, blk8_gfrag) before the
 // exchange, fold and finish it pays anyway: |digit sum| <= (16 + 7) * 32 * 128 * 128 = 12 058 624 < 2^24.  No Gamma term is left on the vector ALU.
+// The chain is SCALED (host_util.hpp blk8s_*): X carries s0 = lambda_q X_q, lambda_0 = 1, lambda_{q+1} = lambda_q^5 kappa / a over all rp rounds (kappa = 2^-20,
+// fr_pow5_r29's scale; a = M[0][0] = every a_q).  Then yt_q = fr_pow5_r29(s0 + lambda_q c_q) = kappa lambda_q^5 y_q and
+//     lambda_{q+1} X_{q+1} = yt_q + lambda_{q+1} ( E_q + sum_{p<q} Gamma_{q,p} y_p ):
+// the S-box output enters with coefficient 1 — no a_q y_q product (unpack, 81 MACs, Montgomery step, carry pass, pack, conditional subtraction) on the chain.
+// Every lambda sits on a constant left factor: E fragments u_{q,j} lambda_{q+1}, Gamma fragments Gamma_{q,p} lambda_{q+1} / (kappa lambda_p^5), lane fragments
+// w_{p,j} / (kappa lambda_p^5) (the posted yt_p stand for the y_p), constants lambda_q c_q; the unit fragment and the lanes are unscaled.  After the last block ONE
+// product by 1 / lambda_rp brings X_rp back (fr_mul_c29).  Exact field arithmetic: the same bits.  The fragments are still digits of residues in [0, r): the digit-sum
+// bounds above stand.  Both addends of the chain's fr_add are canonical (fr_pow5_r29 and mfma_post end canonical).
 // Schedule of a block (two barriers fewer than two blocks of 4, nothing on the chain waits for a lone row):
-//   X  runs nothing but the chain, the same in every round: y_q, a_q y_q, one reduction and X_{q+1} = that + H_q;
+//   X  runs nothing but the chain, the same in every round: the scaled constant, the S-box, recode and post, and after the barrier one fr_add with H_q;
 //   Y  computes H_q INSIDE round q — B operands read from the lanes' slots as the MFMAs consume them (one row per round: 32 KB of LDS reads per about
 //      10 k cycles), then the q steps of the y; the fragments of row q + 1 (16 of E, q + 1 of Gamma) are fetched under the fold — and posts it; one barrier per round;
 //   both then form their share of the lane product (X lanes 1..NLX, Y the rest), the next row's fragments in flight under the current row's fold.
@@ -209,8 +217,7 @@ struct Blk8Tabs {
     const mfma_v4i* lfrag;     // [16][8][64]   lane j = 1..16, S-box output p
     const mfma_v4i* unit;      // [64]          the constant 1
     const mfma_v4i* gfrag;     // [28][64]      Gamma_{q,p} at q (q - 1) / 2 + p
-    const uint32_t* a29;       // a_q at c29(a29, q * (2 T - 1)): the block's first row of sparse29
-    const fr_t* rc;            // [8]
+    const fr_t* rc;            // [8]           lambda_q c_q (rc_partial_scaled)
 };
 struct Blk8Cfg {
     // X's share of the lane rows.  Measured, k SIMD-cycles per 8 rounds in two processes: 6 -> 107.7 / 107.0, 7 -> 105.8 / 106.1, 8 -> 105.1 / 104.2, 9 -> 106.4 / 107.0,
@@ -229,17 +236,14 @@ __device__ __forceinline__ mfma_v4i blk8_b_of_slot(const PairState& s, int j, in
     const uint4 u = s.st[(2 * j + (s.lane >> 5)) * 64 + 32 * ct + (s.lane & 31)];
     return mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
 }
-// round Q in wave X.  b[Q]: y_Q as B operands on exit
+// round Q in wave X: s0 = lambda_Q X_Q on entry, lambda_{Q+1} X_{Q+1} on exit.  b[Q]: yt_Q as B operands on exit
 template <int Q>
 __device__ __forceinline__ void blk8_round_x(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, mfma_v4i (&b)[8][2]) {
     __builtin_amdgcn_sched_barrier(0);                     // keep the rounds apart: less register pressure
-    const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));
-    fr_wide29 acc; fr_wide29_zero(acc);
-    fr_wide29_mac(acc, c29(Tb.a29, (size_t)Q * (2 * 17 - 1)), fr29_unpack(y));
-    const fr_t part = fr_wide29_reduce<PF>(acc);
+    const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));   // yt_Q: canonical
     s.sto(Blk8Cfg::ymail(Q), recode_signed(y));            // off the chain: nothing of X_{Q+1} reads it
-    __syncthreads();                                       // barrier_Q: H_Q is posted
-    s0 = fr_add<PF>(part, s.ld(Blk8Cfg::hmail(Q)));
+    __syncthreads();                                       // barrier_Q: H_Q is posted (canonical: mfma_post)
+    s0 = fr_add<PF>(y, s.ld(Blk8Cfg::hmail(Q)));
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
 // round Q in wave Y.  a, g: the fragments of E row Q and of Gamma row Q on entry, of row Q + 1 on exit; b[Q]: y_Q as B operands on exit
@@ -302,9 +306,10 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
 // One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; s0 = X_0 in wave X.  Ends with a barrier, the lanes recoded again,
 // or canonical after the permutation's last block.
 // With rc29_next (FUSE, last block): every slot ends as the next full round's S-box output instead — the lanes through blk8_lane_rows, element 0 from the chain's
-// final value (rc_next: the same round's constants as field elements).
+// final value, brought back from lambda_rp X_rp by one product with unscale29 = 1 / lambda_rp first (rc_next: the same round's constants as field elements).
 template <int NLX>
-__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last, const uint32_t* rc29_next = nullptr, const fr_t* rc_next = nullptr, bool recode_next = true) {
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last, const uint32_t* rc29_next = nullptr, const fr_t* rc_next = nullptr, bool recode_next = true,
+                                            const uint32_t* unscale29 = nullptr) {
     mfma_v4i b[8][2];
     if (!s.isY) {
         blk8_round_x<0>(s, Tb, s0, b); blk8_round_x<1>(s, Tb, s0, b); blk8_round_x<2>(s, Tb, s0, b); blk8_round_x<3>(s, Tb, s0, b);
@@ -317,7 +322,7 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
     }
     __builtin_amdgcn_sched_barrier(0);
     // slot 0 was H's mailbox in the even rounds, last read by X after barrier_6; the lane rows' closing barrier publishes the store
-    if (rc29_next && !s.isY) { const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, rc_next[0])); s.sto(0, recode_next ? recode_signed(y) : y); }
+    if (rc29_next && !s.isY) { s0 = fr_mul_c29(unscale29, s0); const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, rc_next[0])); s.sto(0, recode_next ? recode_signed(y) : y); }
     blk8_lane_rows<NLX>(s, Tb, b, last, rc29_next, recode_next);
 }
 
@@ -370,10 +375,12 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
         for (int b = 0; b < nb; ++b) {
             const Blk8Tabs Tb{reinterpret_cast<const mfma_v4i*>(P.blk8_efrag) + (size_t)b * 8 * 16 * 64, reinterpret_cast<const mfma_v4i*>(P.blk8_lfrag) + (size_t)b * 16 * 8 * 64,
                               reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), reinterpret_cast<const mfma_v4i*>(P.blk8_gfrag) + (size_t)b * 28 * 64,
-                              c29(P.sparse29, (size_t)(8 * b) * W), P.rc_partial + 8 * b};
-            if constexpr (FUSE) pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1, b == nb - 1 ? c29(P.rc_full29, (size_t)half * T) : nullptr, P.rc_full + half * T, !(only0 && half == P.rf - 1));
+                              P.rc_partial_scaled + 8 * b};
+            if constexpr (FUSE) pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1, b == nb - 1 ? c29(P.rc_full29, (size_t)half * T) : nullptr, P.rc_full + half * T, !(only0 && half == P.rf - 1), P.blk8_unscale29());
             else pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1);
         }
+        // FUSE: the chain value was unscaled inside the last block, in front of element 0's S-box
+        if constexpr (!FUSE) { if (!s.isY) s0 = fr_mul_c29(P.blk8_unscale29(), s0); }
     } else
     for (int b = 0; b < P.rp / 4; ++b) {
         const uint32_t* sp = c29(P.sparse29, (size_t)(4 * b) * W);

@@ -1,11 +1,15 @@
-// tools/partial_block8.hip — PROTOTYPE, not product code: 8 partial rounds of the t = 17 Poseidon permutation for 64 sponges per wave pair, in four forms.
+// tools/partial_block8.hip — PROTOTYPE, not product code: 8 partial rounds of the t = 17 Poseidon permutation for 64 sponges per wave pair, in five forms.
 //   form 4      : the shipped block-of-4 code, twice — pair_permute<17> of poseidon_pair.hpp itself, run with rf = 0 and rp = 8 (no full rounds);
 //   former 8    : one block of 8 rounds whose E-product (8 rows x 16 lanes) and lane product (16 rows x 8 S-box outputs, plus the base lane as a ninth
 //                 K-step) run on the matrix cores through residue tables, the 28 Gamma terms of the block on the vector ALU (namespace former below: the
 //                 product's form until the Gamma terms moved; kept here as the comparison);
 //   form 8      : the product's pair_block8 (poseidon_pair.hpp, where the schedule is described): the Gamma terms as q further K-steps of row q's tile,
-//                 X posting y_q recoded.  Instantiated for several shares of the lane rows (NLX);
-//   form 8 piped: the same with wave Y software-pipelined across the round barrier (namespace piped below), measured and not adopted.
+//                 X posting y_q recoded, the chain SCALED (s0 = lambda_q X_q, no a_q y_q product; tables blk8s_*).  Instantiated for several shares of
+//                 the lane rows (NLX).  The one product by 1 / lambda_8 that brings X_8 back runs in the checked repetition only: a permutation pays it
+//                 once per eight blocks;
+//   unscaled 8  : the same schedule with the chain unscaled, a_q y_q as a nine-limb product in every round of X (namespace unscaled below: the product's
+//                 form until the chain was scaled; kept here as the comparison; tables blk8_*);
+//   form 8 piped: the scaled form with wave Y software-pipelined across the round barrier (namespace piped below), measured and not adopted.
 //   LDS stays at PairCfg<17>::lds_bytes() = 40 KiB.  The host checks every form against the sparse rounds in the portable field code (0 and r - 1 among
 //   the inputs) and requires zero mismatches; then the forms are timed alternately in one process, the state reloaded from memory for every repetition.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I stark_mlwe_amd/csrc tools/partial_block8.hip -o tools/bin/partial_block8
@@ -149,6 +153,38 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Tabs& Tb, 
 }
 }  // namespace former
 
+// ---- the product's schedule with the chain UNSCALED, kept here as the comparison: X_{q+1} = H_q + a_q y_q, the product a nine-limb unpack, 81 MACs and a wide
+// reduction in every round of wave X.  Wave Y and the lane rows are the product's, fed the unscaled tables.  The product no longer contains it.
+namespace unscaled {
+template <int Q>
+__device__ __forceinline__ void round_x(const PairState& s, const Blk8Tabs& Tb, const uint32_t* a29, fr_t& s0, mfma_v4i (&b)[8][2]) {
+    __builtin_amdgcn_sched_barrier(0);
+    const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));
+    fr_wide29 acc; fr_wide29_zero(acc);
+    fr_wide29_mac(acc, c29(a29, (size_t)Q * (2 * 17 - 1)), fr29_unpack(y));
+    const fr_t part = fr_wide29_reduce<PF>(acc);
+    s.sto(Blk8Cfg::ymail(Q), recode_signed(y));
+    __syncthreads();                                       // barrier_Q: H_Q is posted
+    s0 = fr_add<PF>(part, s.ld(Blk8Cfg::hmail(Q)));
+    b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
+}
+template <int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, const uint32_t* a29, fr_t& s0, bool last) {
+    mfma_v4i b[8][2];
+    if (!s.isY) {
+        round_x<0>(s, Tb, a29, s0, b); round_x<1>(s, Tb, a29, s0, b); round_x<2>(s, Tb, a29, s0, b); round_x<3>(s, Tb, a29, s0, b);
+        round_x<4>(s, Tb, a29, s0, b); round_x<5>(s, Tb, a29, s0, b); round_x<6>(s, Tb, a29, s0, b); round_x<7>(s, Tb, a29, s0, b);
+    } else {
+        mfma_v4i a[16], g[7];
+        blk8_load_frags16(a, Tb.efrag, s.lane);
+        blk8_round_y<0>(s, Tb, b, a, g); blk8_round_y<1>(s, Tb, b, a, g); blk8_round_y<2>(s, Tb, b, a, g); blk8_round_y<3>(s, Tb, b, a, g);
+        blk8_round_y<4>(s, Tb, b, a, g); blk8_round_y<5>(s, Tb, b, a, g); blk8_round_y<6>(s, Tb, b, a, g); blk8_round_y<7>(s, Tb, b, a, g);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    blk8_lane_rows<NLX>(s, Tb, b, last);
+}
+}  // namespace unscaled
+
 // ---- the product's form with wave Y SOFTWARE-PIPELINED across the round barrier, measured here and not in the product unless it wins: of row Q only the
 // K-step of y_{Q-1} depends on barrier_{Q-1}, so the 16 lane steps and the steps of y_p, p <= Q - 2, are issued before that barrier, after H_{Q-1} is
 // posted (the accumulator pair is free again by then: no second pair).  Wave X and the lane product are the product's.
@@ -214,9 +250,12 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
 
 // The tables of "block rep & blkmask" (always block 0): as in a permutation's loop over its blocks the fragment addresses change from one pass to the
 // next, so the compiler cannot hoist all of them out of the repetition loop (it did, and spilled 200 registers for them).
-struct ProtoTabs { const mfma_v4i* efrag; const mfma_v4i* lfrag; const mfma_v4i* unit; const mfma_v4i* gfrag; const uint32_t* sparse29; const uint32_t* gamma8_29; const fr_t* rc; int blkmask; };
+// efrag / lfrag / gfrag / rc: the unscaled family (blk8_*, rc_partial); sefrag / slfrag / sgfrag / src: the scaled one (blk8s_*, rc_partial_scaled);
+// unscale8: 1 / lambda_8 as a multiplier-table entry (block 0 ends at round 8; the product's table holds 1 / lambda_rp)
+struct ProtoTabs { const mfma_v4i* efrag; const mfma_v4i* lfrag; const mfma_v4i* unit; const mfma_v4i* gfrag; const uint32_t* sparse29; const uint32_t* gamma8_29; const fr_t* rc;
+                   const mfma_v4i* sefrag; const mfma_v4i* slfrag; const mfma_v4i* sgfrag; const fr_t* src; const uint32_t* unscale8; int blkmask; };
 
-template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>
+template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>; YG = -2: unscaled::pair_block8<NLX>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_block8(ProtoTabs Tp, const fr_t* __restrict__ X, fr_t* __restrict__ Y, int reps) {
     extern __shared__ uint4 lds[];
     PairState s = pair_setup(lds);
@@ -230,9 +269,13 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
         if constexpr (YG > 0) {
             const former::Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sparse29, Tp.gamma8_29, Tp.rc};
             former::pair_block8<YG, NLX>(s, Tb, s0, true);  // last: the lanes end canonical in their slots
+        } else if constexpr (YG == -2) {
+            const Blk8Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.gfrag + (size_t)blk * 28 * 64, Tp.rc};
+            unscaled::pair_block8<NLX>(s, Tb, Tp.sparse29, s0, true);
         } else {
-            const Blk8Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.gfrag + (size_t)blk * 28 * 64, Tp.sparse29, Tp.rc};
+            const Blk8Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, Tp.src};
             if constexpr (YG == 0) pair_block8<NLX>(s, Tb, s0, true); else piped::pair_block8<NLX>(s, Tb, s0, true);
+            if (rep == 0 && !s.isY) s0 = fr_mul_c29(Tp.unscale8, s0);      // lambda_8 X_8 -> X_8
         }
         if (rep == 0) {
             if (!s.isY) stg(Y + b0 + s.lane, s0);
@@ -273,6 +316,9 @@ int main() {
     g_tb.efrag = to_dev<mfma_v4i>(K.blk8_efrag.data(), K.blk8_efrag.size()); g_tb.lfrag = to_dev<mfma_v4i>(K.blk8_lfrag.data(), K.blk8_lfrag.size());
     g_tb.unit = g_tb.lfrag + (K.blk8_lfrag.size() - 1024) / 16; g_tb.gfrag = to_dev<mfma_v4i>(K.blk8_gfrag.data(), K.blk8_gfrag.size());
     g_tb.sparse29 = to_dev<uint32_t>(K.sparse29.data(), K.sparse29.size() * 4); g_tb.gamma8_29 = to_dev<uint32_t>(K.gamma8_29.data(), K.gamma8_29.size() * 4);
+    g_tb.sefrag = to_dev<mfma_v4i>(K.blk8s_efrag.data(), K.blk8s_efrag.size()); g_tb.slfrag = to_dev<mfma_v4i>(K.blk8s_lfrag.data(), K.blk8s_lfrag.size());
+    g_tb.sgfrag = to_dev<mfma_v4i>(K.blk8s_gfrag.data(), K.blk8s_gfrag.size()); g_tb.src = to_dev<fr_t>(K.rc_partial_scaled.data(), K.rc_partial_scaled.size() * sizeof(fr_t));
+    { uint32_t u8[9]; fr29_const_from<host::PF>(fr_inv<host::PF>(K.blk8_lambda[8]), u8); g_tb.unscale8 = to_dev<uint32_t>(u8, sizeof u8); }
     g_tb.blkmask = 0;
     g_tb.rc = to_dev<fr_t>(K.rc_partial.data(), K.rc_partial.size() * sizeof(fr_t));
     memset(&g_p, 0, sizeof g_p);
@@ -292,13 +338,15 @@ int main() {
     const Form forms[] = {
         {"block4 x 2 (shipped pair_permute<17>, rf = 0, rp = 8)", launch4},
         {"block8, Gamma terms on the vector ALU, YG=5 NLX=8 (the former product form)", launch8<5, 8>},
-        {"block8, Gamma terms as K-steps of the E rows, NLX=8 (the product's pair_block8)", launch8<0, Blk8Cfg::NLX>},
-        {"block8, Gamma K-steps, NLX=8, wave Y pipelined across the round barrier", launch8<-1, 8>},
-        {"block8, Gamma K-steps, NLX=7, wave Y pipelined across the round barrier", launch8<-1, 7>},
-        {"block8, Gamma K-steps, NLX=6", launch8<0, 6>},
-        {"block8, Gamma K-steps, NLX=7", launch8<0, 7>},
-        {"block8, Gamma K-steps, NLX=9", launch8<0, 9>},
-        {"block8, Gamma K-steps, NLX=10", launch8<0, 10>},
+        {"block8, Gamma K-steps, chain unscaled (a_q y_q product per round), NLX=8 (the former product form)", launch8<-2, 8>},
+        {"block8, Gamma K-steps, chain scaled, NLX=8", launch8<0, 8>},
+        {"block8, Gamma K-steps, chain scaled, NLX=8, wave Y pipelined across the round barrier", launch8<-1, 8>},
+        {"block8, Gamma K-steps, chain scaled, NLX=6", launch8<0, 6>},
+        {"block8, Gamma K-steps, chain scaled, NLX=7", launch8<0, 7>},
+        {"block8, Gamma K-steps, chain scaled, NLX=9", launch8<0, 9>},
+        {"block8, Gamma K-steps, chain scaled, NLX=10", launch8<0, 10>},
+        {"block8, Gamma K-steps, chain unscaled, NLX=7", launch8<-2, 7>},
+        {"block8, Gamma K-steps, chain unscaled, NLX=9", launch8<-2, 9>},
     };
     const int nforms = (int)(sizeof forms / sizeof forms[0]);
     // reference: the sparse rounds in the portable field code, sampled batches
