@@ -87,7 +87,9 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  *   "mle_lane_contiguous" (0 | 1, default 0; -1 restores the default: a lane of those launches owns consecutive elements instead of interleaved ones; comparison).
  *   "lagrange_max_partials" (1..2^28, default 2^21 elements = 64 MiB; -1 restores the default: the block partials one pass of
  *   stark_lagrange_eval_on_h_batch_dev may hold; a pass of one point is always allowed),
- *   "lagrange_wide_acc" (0 | 1, default 1; -1 restores the default: a lane's products of a column go through the lazy accumulator; comparison).
+ *   "lagrange_wide_acc" (0 | 1, default 1; -1 restores the default: a lane's products of a column go through the lazy accumulator; comparison),
+ *   "lagrange_col_groups" (1..65535, default -1 = automatic; -1 restores the default: the column groups of a launch of the lagrange_eval kernel;
+ *   1 = one group, g > 1 = min(g, ncols) groups; every value gives the same bytes).
  *   "pool_poison" (0..255, default -1 = off; FOR TESTS ONLY: every pooled block the library hands to itself, recycled or fresh, and the NTT scratch vector are
  *   filled with this byte first, so a result that depends on a temporary nobody wrote changes with the byte.  Each fill synchronises the stream: the
  *   calls that promise "no synchronisation" do synchronise while it is set.  The long-lived tables are not filled).
@@ -255,6 +257,41 @@ int32_t stark_lagrange_eval_on_h_dev(stark_ctx_t* ctx, const uint64_t* values, s
  * check above; an out range that overlaps a column.  (More than 2^24 columns in one call: STARK_ERR_UNSUPPORTED.) */
 int32_t stark_lagrange_eval_on_h_batch_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega4, size_t npoints,
                                            const uint64_t* z, uint64_t* out);
+/* lagrange_eval_on_h (deep_ali/src/lib.rs:17-45) of columns that live as blocks: the share of the rows [j0, j0 + n_local) of an n_global-point
+ * domain.  cols is a HOST array of ncols DEVICE pointers to this block's n_local rows, z the HOST array of the npoints x 4 points, partials_out
+ * npoints x ncols elements in DEVICE memory, point-major.  Outside H: partials_out[p * ncols + c] = sum over the block's rows j of
+ * cols[c][j] omega^(j0 + j) / (z[p] - omega^(j0 + j)), unscaled, omega the generator of the GLOBAL domain.  Inside H (z[p] = omega^(j*), classified
+ * against the global domain): the row cols[c][j* - j0] when j0 <= j* < j0 + n_local, zero otherwise.  The shares of the blocks of any partition of
+ * [0, n_global) go through stark_lagrange_eval_from_partials_dev.  Any block with 1 <= n_local and j0 + n_local <= n_global is accepted; n_local
+ * need not be a power of two.  n_global and omega4 follow the batch call's rules (omega4 == NULL: the radix-2 generator of size n_global).
+ * Stream-ordered, no host synchronisation: z and the pointer table are copied before the call returns; passes are bounded by
+ * "lagrange_max_partials".  ncols == 0 or npoints == 0 returns STARK_OK and writes nothing.  STARK_ERR_INVALID_ARG, before anything is launched:
+ * the batch call's causes, n_local == 0, j0 + n_local > n_global, a partials_out range that overlaps a column block. */
+int32_t stark_lagrange_eval_shard_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols, size_t n_local, uint64_t j0, size_t n_global, const uint64_t* omega4,
+                                      size_t npoints, const uint64_t* z, uint64_t* partials_out);
+/* The combine of the block shares of lagrange_eval_on_h (deep_ali/src/lib.rs:17-45): partials is DEVICE, nparts x npoints x ncols (the
+ * partials_out of nparts calls of stark_lagrange_eval_shard_dev, one after the other), out DEVICE, npoints x ncols:
+ * out[p * ncols + c] = scale[p] * sum_q partials[(q * npoints + p) * ncols + c], scale = (z^n - 1)/n outside H and one inside H, computed on the
+ * host from z (HOST).  When the parts tile [0, n_global), out equals stark_lagrange_eval_on_h_batch_dev on the whole columns byte for byte.
+ * Stream-ordered, no host synchronisation.  STARK_ERR_INVALID_ARG: nparts == 0 with results requested, a null partials, z or out, a refused
+ * (n_global, omega4), out overlapping partials. */
+int32_t stark_lagrange_eval_from_partials_dev(stark_ctx_t* ctx, size_t nparts, const uint64_t* partials, size_t ncols, size_t n_global, const uint64_t* omega4, size_t npoints,
+                                              const uint64_t* z, uint64_t* out);
+/* lagrange_eval_on_h (deep_ali/src/lib.rs:17-45) of columns block-sharded over the context's communicator as ONE collective call (W = 1 without a
+ * communicator): rank q passes its rows [q*n/W, (q+1)*n/W) of every column (cols_block: a HOST array of ncols DEVICE pointers) and EVERY rank
+ * receives the full out (DEVICE, npoints x ncols), the bytes of stark_lagrange_eval_on_h_batch_dev on the whole columns.  Steps: the block
+ * partials, one all-gather of the W tables of npoints x ncols elements, the combine.  All argument checks come before the first collective; the
+ * first collective all-gathers a small header (n_global, ncols, npoints, a 64-bit digest of the omega and z bytes) and, when any two headers
+ * differ, EVERY rank returns STARK_ERR_INVALID_ARG (the rule of stark_fri_build_sharded_dev).  W must be a power of two that divides n_global.
+ *  - stark_diag_lagrange_eval_sharded_emulated_dev: the diagnostic twin (deep_ali/src/lib.rs:17-45): the same phase code for `nranks` VIRTUAL
+ *    ranks on this one GPU, every collective as device copies.  cols_whole: the WHOLE columns; out: nranks x npoints x ncols, the result as every
+ *    virtual rank sees it.  nranks must be a power of two that divides n_global, else STARK_ERR_INVALID_ARG.
+ * STATUS: W > 1 over a real communicator has run only as the emulation, like the sharded LDE, commit and prove (no multi-GPU node was available
+ * to the build). */
+int32_t stark_lagrange_eval_on_h_sharded_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols_block, size_t n_global, const uint64_t* omega4, size_t npoints,
+                                             const uint64_t* z, uint64_t* out);
+int32_t stark_diag_lagrange_eval_sharded_emulated_dev(stark_ctx_t* ctx, int32_t nranks, size_t ncols, const uint64_t* const* cols_whole, size_t n_global, const uint64_t* omega4,
+                                                      size_t npoints, const uint64_t* z, uint64_t* out);
 /* DeepAliRealBuilder::build_f0 (fri.rs:535-569): 4 column sponges, (z, beta) sampling, merge.
  * aux7 (optional, host): col digests A,S,E,T, seed_f, z, beta. */
 int32_t stark_build_f0(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, size_t n0, uint64_t* f0, uint64_t* aux7);

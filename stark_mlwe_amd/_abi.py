@@ -88,6 +88,10 @@ SIGNATURES = {
     "stark_lagrange_eval_on_h": (i32, [vp, vp, sz, vp, vp, vp]),
     "stark_lagrange_eval_on_h_dev": (i32, [vp, vp, sz, vp, vp, vp]),
     "stark_lagrange_eval_on_h_batch_dev": (i32, [vp, sz, vp, sz, vp, sz, vp, vp]),
+    "stark_lagrange_eval_shard_dev": (i32, [vp, sz, vp, sz, u64, sz, vp, sz, vp, vp]),
+    "stark_lagrange_eval_from_partials_dev": (i32, [vp, sz, vp, sz, sz, vp, sz, vp, vp]),
+    "stark_lagrange_eval_on_h_sharded_dev": (i32, [vp, sz, vp, sz, vp, sz, vp, vp]),
+    "stark_diag_lagrange_eval_sharded_emulated_dev": (i32, [vp, i32, sz, vp, sz, vp, sz, vp, vp]),
     "stark_build_f0": (i32, [vp, vp, vp, vp, vp, sz, vp, vp]),
     "stark_build_f0_dev": (i32, [vp, vp, vp, vp, vp, sz, vp, vp]),
     "stark_deep_fri_prove": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, sz, sz, u64, vpp]),

@@ -323,7 +323,7 @@ class Context:
         self._chk(self.lib.stark_ctx_sync(self.h))
 
     def set_option(self, key: str, value: int):
-        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "poseidon_block8", "merkle_wave_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous", "lagrange_max_partials", "lagrange_wide_acc", "pool_poison" (tests only: fills the library's pooled temporaries, synchronises).  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
+        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "poseidon_block8", "merkle_wave_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous", "lagrange_max_partials", "lagrange_wide_acc", "lagrange_col_groups", "pool_poison" (tests only: fills the library's pooled temporaries, synchronises).  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
         self._chk(self.lib.stark_ctx_set_option(self.h, key.encode(), value))
 
     def trim(self):
@@ -749,6 +749,41 @@ class Context:
         B = len(cols); z = _arr(zs).reshape(-1, 4)
         tab = (C.c_void_p * max(B, 1))(*[int(x) for x in cols])
         self._chk(self.lib.stark_lagrange_eval_on_h_batch_dev(self.h, B, tab, n, _ptr(None if omega is None else _arr(omega)), z.shape[0], _ptr(z) if z.shape[0] else None, C.c_void_p(int(out))))
+
+    def lagrange_eval_shard_dev(self, cols, n_local, j0, n_global, zs, partials_out, omega=None):
+        """The block form of lagrange_eval_on_h: `cols` (ints) are the DEVICE rows [j0, j0 + n_local) of each column of an n_global-point domain; the
+        block's unscaled shares at the host points zs ((P, 4)) go into the DEVICE array `partials_out` (int, P x len(cols) elements, point-major);
+        stream-ordered, no synchronisation (stark_lagrange_eval_shard_dev)."""
+        B = len(cols); z = _arr(zs).reshape(-1, 4)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in cols])
+        self._chk(self.lib.stark_lagrange_eval_shard_dev(self.h, B, tab, n_local, j0, n_global, _ptr(None if omega is None else _arr(omega)), z.shape[0], _ptr(z) if z.shape[0] else None,
+                                                         C.c_void_p(int(partials_out))))
+
+    def lagrange_eval_from_partials_dev(self, nparts, partials, ncols, n_global, zs, out, omega=None):
+        """The combine of `nparts` block shares (DEVICE `partials`, int, nparts x P x ncols elements) into the DEVICE array `out` (int, P x ncols): the
+        bytes of lagrange_eval_on_h_batch_dev on the whole columns when the blocks tile the domain; stream-ordered, no synchronisation
+        (stark_lagrange_eval_from_partials_dev)."""
+        z = _arr(zs).reshape(-1, 4)
+        self._chk(self.lib.stark_lagrange_eval_from_partials_dev(self.h, nparts, C.c_void_p(int(partials)), ncols, n_global, _ptr(None if omega is None else _arr(omega)), z.shape[0],
+                                                                 _ptr(z) if z.shape[0] else None, C.c_void_p(int(out))))
+
+    def lagrange_eval_on_h_sharded(self, cols_block, n_global, zs, out, omega=None):
+        """Collective: lagrange_eval_on_h of columns block-sharded over the context's communicator (one rank without it); cols_block (ints) = this
+        rank's DEVICE rows of each column, `out` (int, DEVICE, P x len(cols_block)) = the full result on every rank
+        (stark_lagrange_eval_on_h_sharded_dev)."""
+        B = len(cols_block); z = _arr(zs).reshape(-1, 4)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in cols_block])
+        self._chk(self.lib.stark_lagrange_eval_on_h_sharded_dev(self.h, B, tab, n_global, _ptr(None if omega is None else _arr(omega)), z.shape[0], _ptr(z) if z.shape[0] else None,
+                                                                C.c_void_p(int(out))))
+
+    def diag_lagrange_eval_sharded_emulated(self, nranks, cols_whole, n_global, zs, out, omega=None):
+        """Diagnostic: the sharded lagrange_eval_on_h for `nranks` virtual ranks on this GPU (collectives as device copies) over the WHOLE DEVICE columns
+        (ints); `out` (int, DEVICE, nranks x P x len(cols_whole)) = the result as every virtual rank sees it
+        (stark_diag_lagrange_eval_sharded_emulated_dev)."""
+        B = len(cols_whole); z = _arr(zs).reshape(-1, 4)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in cols_whole])
+        self._chk(self.lib.stark_diag_lagrange_eval_sharded_emulated_dev(self.h, nranks, B, tab, n_global, _ptr(None if omega is None else _arr(omega)), z.shape[0],
+                                                                         _ptr(z) if z.shape[0] else None, C.c_void_p(int(out))))
 
     def prove_plain(self, k, tree_label, witness):
         """prove_plain(&build_vk_plain(k, F::from(tree_label)), witness) -> bincode-layout ProofPlain bytes."""

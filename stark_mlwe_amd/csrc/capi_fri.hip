@@ -19,6 +19,7 @@
 #include "fri_batch.hpp"
 #include "merkle_batch.hpp"
 #include "lagrange_dev.hpp"
+#include "shard_coll.hpp"
 
 using namespace stark;
 
@@ -556,6 +557,13 @@ static int32_t ali_merge_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* co
 
 // ---- lagrange_eval_on_h of device-resident columns (deep_ali/src/lib.rs:17-45; lagrange_dev.hpp) -----------------------------------------------
 // The executor of lagrange_eval_batch on the device: pooled blocks that return to the pool with it, staged uploads, every launch on the context's stream.
+// (n, omega4) of a lagrange_eval entry point: *omega = the caller's generator or the radix-2 one of size n
+static int32_t lagrange_check_domain(stark_ctx* ctx, size_t n, const uint64_t* omega4, fr_t* omega) {
+    if (!is_pow2(n) || n > ((size_t)1 << kLagMaxLogN)) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: n must be a power of two, 1 <= n <= 2^30");
+    *omega = omega4 ? load_fr(omega4) : fr_root_of_unity<PallasFr>((unsigned)ilog2(n));       // FriDomain::new_radix2(n).omega, fri.rs:53-56
+    if (const char* why = lag_check_domain(n, *omega)) return ctx->fail(STARK_ERR_INVALID_ARG, std::string("lagrange_eval: ") + why);
+    return STARK_OK;
+}
 struct LagDevExec : FriDevExec {
     explicit LagDevExec(stark_ctx* c) : FriDevExec(c) {}
     int32_t pow_table(const fr_t& omega, size_t n, LagPow* out) {                        // the merge's table of this domain (PowCache): a prove that merged over it has filled it
@@ -565,28 +573,35 @@ struct LagDevExec : FriDevExec {
         hipLaunchKernelGGL(k_lagrange_gather, dim3((unsigned)((cnt * ncols + 255) / 256)), dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, j, slot, (uint64_t)cnt, out);
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
-    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, unsigned groups, unsigned grid, fr_t* part) {
+    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n_local, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, unsigned groups,
+                     unsigned col_groups, size_t group_cols, unsigned grid, fr_t* part) {
         const bool wide = ctx->opt.lagrange_wide_acc < 0 ? kLagWideAcc : ctx->opt.lagrange_wide_acc != 0;
-        if (wide) hipLaunchKernelGGL(k_lagrange_partials<true>, dim3(grid, groups), dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n, wp, w_step, w_step_inv, zs, (uint64_t)npts, part);
-        else hipLaunchKernelGGL(k_lagrange_partials<false>, dim3(grid, groups), dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n, wp, w_step, w_step_inv, zs, (uint64_t)npts, part);
+        const dim3 g(grid, groups, col_groups);
+        if (wide) hipLaunchKernelGGL(k_lagrange_partials<true>, g, dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n_local, j0, wp, w_step, w_step_inv, zs, (uint64_t)npts, (uint64_t)group_cols, part);
+        else hipLaunchKernelGGL(k_lagrange_partials<false>, g, dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n_local, j0, wp, w_step, w_step_inv, zs, (uint64_t)npts, (uint64_t)group_cols, part);
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
     int32_t finish(const fr_t* part, unsigned grid, const fr_t* scale, const uint64_t* slot, size_t npts, size_t ncols, fr_t* out) {
         hipLaunchKernelGGL(k_lagrange_finish, dim3((unsigned)(npts * ncols)), dim3(256), 0, ctx->stream, part, (uint64_t)grid, scale, slot, (uint64_t)ncols, out);
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
+    int32_t combine(const fr_t* partials, size_t nparts, const fr_t* scale, size_t npoints, size_t ncols, fr_t* out) {
+        const uint64_t total = (uint64_t)npoints * ncols;
+        hipLaunchKernelGGL(k_lagrange_combine, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, partials, (uint64_t)nparts, scale, total, (uint64_t)ncols, out);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
 };
-// the argument checks of stark_lagrange_eval_on_h_batch_dev, all before anything is enqueued; *omega = the caller's generator or the radix-2 one of size n
-static int32_t lagrange_check_args(stark_ctx* ctx, size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega4, size_t npoints, const uint64_t* z, const uint64_t* out, fr_t* omega) {
+// The argument checks of the lagrange_eval entry points, all before anything is enqueued: ncols columns of col_len rows each (the whole column, or a
+// block of it) over a domain of n points, results into `out_elems` elements at out.  *omega = the caller's generator or the radix-2 one of size n.
+static int32_t lagrange_check_args(stark_ctx* ctx, size_t ncols, const uint64_t* const* cols, size_t col_len, size_t n, const uint64_t* omega4, size_t npoints, const uint64_t* z, const uint64_t* out,
+                                   size_t out_elems, fr_t* omega) {
     if (!cols) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null column table");
     if (!out) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null out");
     if (!z) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null z with npoints > 0");
-    if (!is_pow2(n) || n > ((size_t)1 << kLagMaxLogN)) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: n must be a power of two, 1 <= n <= 2^30");
-    *omega = omega4 ? load_fr(omega4) : fr_root_of_unity<PallasFr>((unsigned)ilog2(n));       // FriDomain::new_radix2(n).omega, fri.rs:53-56
-    if (const char* why = lag_check_domain(n, *omega)) return ctx->fail(STARK_ERR_INVALID_ARG, std::string("lagrange_eval: ") + why);
+    STARK_TRY(lagrange_check_domain(ctx, n, omega4, omega));
     if (ncols > kLagMaxCols) return ctx->fail(STARK_ERR_UNSUPPORTED, "lagrange_eval: more than 2^24 columns in one call");
     if (npoints > ((size_t)1 << 36) / ncols) return ctx->fail(STARK_ERR_UNSUPPORTED, "lagrange_eval: more than 2^36 results in one call");
-    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + npoints * ncols * sizeof(fr_t), cbytes = n * sizeof(fr_t);
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + out_elems * sizeof(fr_t), cbytes = col_len * sizeof(fr_t);
     for (size_t c = 0; c < ncols; ++c) {
         if (!cols[c]) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null column entry " + std::to_string(c));
         const uintptr_t c0 = (uintptr_t)cols[c];
@@ -594,11 +609,43 @@ static int32_t lagrange_check_args(stark_ctx* ctx, size_t ncols, const uint64_t*
     }
     return STARK_OK;
 }
-static int32_t lagrange_eval_batch_impl(stark_ctx* ctx, size_t ncols, const uint64_t* const* cols, size_t n, const fr_t& omega, size_t npoints, const uint64_t* z, uint64_t* out) {
+static std::vector<fr_t> lagrange_points(size_t npoints, const uint64_t* z) { std::vector<fr_t> zs(npoints); for (size_t p = 0; p < npoints; ++p) zs[p] = load_fr(z + 4 * p); return zs; }
+// the block B of the columns `cols` (a host table of device pointers to the block's rows) through THE driver; B = lag_whole(n): the batch call
+static int32_t lagrange_eval_block_impl(stark_ctx* ctx, size_t ncols, const uint64_t* const* cols, const LagBlock& B, const fr_t& omega, const std::vector<fr_t>& zs, fr_t* out) {
     std::vector<const fr_t*> cp(ncols); for (size_t c = 0; c < ncols; ++c) cp[c] = as_fr(cols[c]);
-    std::vector<fr_t> zs(npoints); for (size_t p = 0; p < npoints; ++p) zs[p] = load_fr(z + 4 * p);
     LagDevExec X(ctx);
-    return lagrange_eval_batch(X, ncols, cp.data(), n, omega, npoints, zs.data(), ctx->opt.lagrange_max_partials, as_fr(out), nullptr);
+    return lagrange_eval_batch(X, ncols, cp.data(), B, omega, zs.size(), zs.data(), ctx->opt.lagrange_max_partials, ctx->opt.lagrange_col_groups, out, nullptr);
+}
+
+// ---- lagrange_eval_on_h of columns block-sharded over the ranks of a ShardColl: block partials, ONE all-gather of the W tables, the combine --------
+// One driver for the communicator's rank (stark_lagrange_eval_on_h_sharded_dev) and for W ranks emulated on one GPU
+// (stark_diag_lagrange_eval_sharded_emulated_dev).  cols[c]: this rank's rows [q n/W, (q+1) n/W) of column c, or the whole column when C is emulated;
+// out: npoints x ncols per local rank.  The arguments have passed lagrange_check_args.  Collective 0 is the header: ranks that were given a different
+// (n, ncols, npoints, omega, z) all return STARK_ERR_INVALID_ARG (the rule of shard_header_agree, fri_shard_impl.hpp).
+static int32_t lagrange_sharded(const ShardColl& C, size_t ncols, const uint64_t* const* cols, size_t n, const fr_t& omega, const std::vector<fr_t>& zs, fr_t* out) {
+    stark_ctx* ctx = C.ctx; const size_t W = (size_t)C.W, nl = n / W, total = zs.size() * ncols, chunk = total * sizeof(fr_t), hbytes = kLagHdrWords * 8;
+    uint64_t h[kLagHdrWords]; lag_shard_header(n, ncols, zs.size(), omega, zs.data(), h);
+    {
+        std::vector<DevBuf> hb(C.local()); std::vector<void*> buf;
+        for (size_t i = 0; i < hb.size(); ++i) {
+            STARK_TRY(hb[i].take(ctx, W * hbytes));
+            STARK_HIP(ctx, hipMemcpyAsync((char*)hb[i].p + (size_t)C.rank(i) * hbytes, h, hbytes, hipMemcpyHostToDevice, ctx->stream));
+            buf.push_back(hb[i].p);
+        }
+        STARK_TRY(C.all_gather(buf, hbytes));
+        std::vector<uint64_t> all(W * kLagHdrWords); bool same = true;
+        for (auto& b : hb) { STARK_HIP(ctx, b.download_sync(all.data(), W * hbytes)); same = same && lag_headers_agree(all.data(), W, h); }
+        if (!same) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval sharded: the ranks disagree on (n_global, ncols, npoints, omega, z)");
+    }
+    std::vector<DevBuf> tab(C.local()); std::vector<void*> buf; std::vector<const uint64_t*> blk(ncols);
+    for (size_t i = 0; i < tab.size(); ++i) {                  // in place: this rank's table sits at rank * chunk of its W tables
+        STARK_TRY(tab[i].take(ctx, W * chunk)); buf.push_back(tab[i].p);
+        for (size_t c = 0; c < ncols; ++c) blk[c] = cols[c] + 4 * C.block(i) * nl;
+        STARK_TRY(lagrange_eval_block_impl(ctx, ncols, blk.data(), LagBlock{nl, (uint64_t)C.rank(i) * nl, n, false}, omega, zs, tab[i].fr() + (size_t)C.rank(i) * total));
+    }
+    STARK_TRY(C.all_gather(buf, chunk));
+    for (size_t i = 0; i < tab.size(); ++i) { LagDevExec X(ctx); STARK_TRY(lagrange_combine(X, W, (const fr_t*)tab[i].fr(), ncols, n, zs.size(), zs.data(), out + C.block(i) * total)); }
+    return STARK_OK;
 }
 
 // B independent proofs of equal shape (stark_deep_fri_prove_batch_dev; stark_deep_fri_prove_dev from columns is B = 1): the challenge stage of all
@@ -810,9 +857,9 @@ int32_t stark_ali_merge_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t
 int32_t stark_lagrange_eval_on_h_batch_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega4, size_t npoints, const uint64_t* z, uint64_t* out) {
     if (!ctx) return STARK_ERR_INVALID_ARG;
     if (!ncols || !npoints) return STARK_OK;
-    fr_t omega; STARK_TRY(lagrange_check_args(ctx, ncols, cols, n, omega4, npoints, z, out, &omega));
+    fr_t omega; STARK_TRY(lagrange_check_args(ctx, ncols, cols, n, n, omega4, npoints, z, out, npoints * ncols, &omega));
     STARK_TRY(ctx_enter(ctx));
-    return lagrange_eval_batch_impl(ctx, ncols, cols, n, omega, npoints, z, out);
+    return lagrange_eval_block_impl(ctx, ncols, cols, lag_whole(n), omega, lagrange_points(npoints, z), as_fr(out));
 }
 int32_t stark_lagrange_eval_on_h_dev(stark_ctx_t* ctx, const uint64_t* values, size_t n, const uint64_t* z4, const uint64_t* omega4, uint64_t* out4) {
     return stark_lagrange_eval_on_h_batch_dev(ctx, 1, &values, n, omega4, 1, z4, out4);
@@ -826,6 +873,56 @@ int32_t stark_lagrange_eval_on_h(stark_ctx_t* ctx, const uint64_t* values, size_
     const int32_t rc = stark_lagrange_eval_on_h_dev(ctx, (const uint64_t*)d.p, n, z4, omega4, (uint64_t*)o.p);
     if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }                          // the upload reads the caller's `values`
     STARK_HIP(ctx, o.download_sync(out4, sizeof(fr_t))); return STARK_OK;
+}
+// The block form (lagrange_dev.hpp): the unscaled share of the rows [j0, j0 + n_local) of an n_global-point domain, and the combine of such shares.
+int32_t stark_lagrange_eval_shard_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols, size_t n_local, uint64_t j0, size_t n_global, const uint64_t* omega4, size_t npoints,
+                                      const uint64_t* z, uint64_t* partials_out) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!ncols || !npoints) return STARK_OK;
+    if (!n_local) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: n_local must be at least 1");
+    if (j0 > n_global || n_local > n_global - j0) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: j0 + n_local exceeds n_global");
+    fr_t omega; STARK_TRY(lagrange_check_args(ctx, ncols, cols, n_local, n_global, omega4, npoints, z, partials_out, npoints * ncols, &omega));
+    STARK_TRY(ctx_enter(ctx));
+    return lagrange_eval_block_impl(ctx, ncols, cols, LagBlock{n_local, j0, n_global, false}, omega, lagrange_points(npoints, z), as_fr(partials_out));
+}
+int32_t stark_lagrange_eval_from_partials_dev(stark_ctx_t* ctx, size_t nparts, const uint64_t* partials, size_t ncols, size_t n_global, const uint64_t* omega4, size_t npoints, const uint64_t* z,
+                                              uint64_t* out) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!ncols || !npoints) return STARK_OK;
+    if (!nparts) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: nparts must be at least 1");
+    if (!partials) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null partials");
+    if (!out) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null out");
+    if (!z) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null z with npoints > 0");
+    fr_t omega; STARK_TRY(lagrange_check_domain(ctx, n_global, omega4, &omega));
+    if (ncols > kLagMaxCols || npoints > ((size_t)1 << 36) / ncols || nparts > ((size_t)1 << 20)) return ctx->fail(STARK_ERR_UNSUPPORTED, "lagrange_eval: more than 2^24 columns, 2^36 results or 2^20 parts in one call");
+    const uintptr_t o0 = (uintptr_t)out, obytes = npoints * ncols * sizeof(fr_t), p0 = (uintptr_t)partials;
+    if (p0 < o0 + obytes && o0 < p0 + nparts * obytes) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: out overlaps partials");
+    STARK_TRY(ctx_enter(ctx));
+    const std::vector<fr_t> zs = lagrange_points(npoints, z);
+    LagDevExec X(ctx);
+    return lagrange_combine(X, nparts, as_fr(partials), ncols, n_global, npoints, zs.data(), as_fr(out));
+}
+// Collective: the sharded call.  Every check of this rank's arguments comes before the first collective (lagrange_sharded).
+int32_t stark_lagrange_eval_on_h_sharded_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols_block, size_t n_global, const uint64_t* omega4, size_t npoints, const uint64_t* z,
+                                             uint64_t* out) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!ncols || !npoints) return STARK_OK;
+    const ShardColl C = ShardColl::real(ctx); const size_t W = (size_t)std::max(C.W, 1);
+    if (C.W < 1 || (W & (W - 1)) || !n_global || n_global % W) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval sharded: the communicator's size must be a power of two that divides n_global");
+    fr_t omega; STARK_TRY(lagrange_check_args(ctx, ncols, cols_block, n_global / W, n_global, omega4, npoints, z, out, npoints * ncols, &omega));
+    STARK_TRY(ctx_enter(ctx));
+    return lagrange_sharded(C, ncols, cols_block, n_global, omega, lagrange_points(npoints, z), as_fr(out));
+}
+int32_t stark_diag_lagrange_eval_sharded_emulated_dev(stark_ctx_t* ctx, int32_t nranks, size_t ncols, const uint64_t* const* cols_whole, size_t n_global, const uint64_t* omega4, size_t npoints,
+                                                      const uint64_t* z, uint64_t* out) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (!ncols || !npoints) return STARK_OK;
+    if (nranks < 1 || (nranks & (nranks - 1)) || !n_global || (size_t)nranks > n_global || n_global % (size_t)nranks)
+        return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval sharded: nranks must be a power of two that divides n_global");
+    if (npoints > ((size_t)1 << 36) / ncols / (size_t)nranks) return ctx->fail(STARK_ERR_UNSUPPORTED, "lagrange_eval: more than 2^36 results in one call");
+    fr_t omega; STARK_TRY(lagrange_check_args(ctx, ncols, cols_whole, n_global, n_global, omega4, npoints, z, out, (size_t)nranks * npoints * ncols, &omega));
+    STARK_TRY(ctx_enter(ctx));
+    return lagrange_sharded(ShardColl::emulate(ctx, nranks), ncols, cols_whole, n_global, omega, lagrange_points(npoints, z), as_fr(out));
 }
 size_t stark_proof_len(stark_proof_t* p) { return p ? p->bytes.size() : 0; }
 int32_t stark_proof_bytes(stark_proof_t* p, uint8_t* out) { if (!p || !out) return STARK_ERR_INVALID_ARG; memcpy(out, p->bytes.data(), p->bytes.size()); return STARK_OK; }

@@ -867,15 +867,17 @@ struct LagHostExec {
         *out = LagPow{lo.data(), hi.data(), lo_bits}; return 0;
     }
     int32_t gather(const fr_t* const* cols, size_t ncols, const uint64_t* j, const uint64_t* slot, size_t cnt, fr_t* out) {
-        for (size_t q = 0; q < cnt; ++q) for (size_t c = 0; c < ncols; ++c) out[slot[q] * ncols + c] = cols[c][j[q]];
+        for (size_t q = 0; q < cnt; ++q) for (size_t c = 0; c < ncols; ++c) out[slot[q] * ncols + c] = j[q] == kLagNoRow ? fr_zero<PF>() : cols[c][j[q]];
         return 0;
     }
-    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, unsigned groups, unsigned grid, fr_t* part) {
+    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, unsigned groups,
+                     unsigned col_groups, size_t group_cols, unsigned grid, fr_t* part) {
         const uint32_t T = grid * 256, n32 = (uint32_t)n;
         std::vector<fr_t> Wv(256 * kLagK), w(256), run(256), lane(256);
         auto W = [&](int t) -> fr_t (&)[kLagK] { return *reinterpret_cast<fr_t (*)[kLagK]>(&Wv[(size_t)t * kLagK]); };
-        for (unsigned g = 0; g < groups; ++g) for (unsigned blk = 0; blk < grid; ++blk) {
-            for (int t = 0; t < 256; ++t) { const uint32_t tid = blk * 256 + t; w[t] = tid < n32 ? lag_pow(wp, tid) : fr_one<PF>(); }
+        for (unsigned cg = 0; cg < col_groups; ++cg) for (unsigned g = 0; g < groups; ++g) for (unsigned blk = 0; blk < grid; ++blk) {      // a workgroup per (tile, point group, column group), as on the device
+            const size_t c_lo = (size_t)cg * group_cols, c_hi = std::min(c_lo + group_cols, ncols);
+            for (int t = 0; t < 256; ++t) { const uint32_t tid = blk * 256 + t; w[t] = tid < n32 ? lag_pow(wp, j0 + tid) : fr_one<PF>(); }
             for (size_t p = g; p < npts; p += groups) {
                 const fr_t z = zs[p];
                 for (int t = 0; t < 256; ++t) run[t] = lag_prefix(z, w[t], w_step, blk * 256 + (uint32_t)t, T, n32, W(t));
@@ -888,7 +890,7 @@ struct LagHostExec {
                     for (int q = l + 1; q < 64; ++q) after = fr_mul<PF>(after, run[64 * v + q]);
                     lag_peel(z, w[t], w_step_inv, blk * 256 + (uint32_t)t, T, n32, lag_lane_inverse(Pinv, tot, v, fr_mul<PF>(before, after)), W(t));
                 }
-                for (size_t c = 0; c < ncols; ++c) {
+                for (size_t c = c_lo; c < c_hi; ++c) {
                     for (int t = 0; t < 256; ++t) lane[t] = lag_lane_dot<kLagWideAcc>(cols[c], blk * 256 + (uint32_t)t, T, n32, W(t));
                     fr_t w4[4];
                     for (int v = 0; v < 4; ++v) { w4[v] = fr_zero<PF>(); for (int l = 0; l < 64; ++l) w4[v] = fr_add<PF>(w4[v], lane[64 * v + l]); }
@@ -904,22 +906,34 @@ struct LagHostExec {
             for (int t = 0; t < 256; ++t) { lane[t] = fr_zero<PF>(); for (size_t i = (size_t)t; i < grid; i += 256) lane[t] = fr_add<PF>(lane[t], part[b * grid + i]); }
             fr_t w4[4];
             for (int w = 0; w < 4; ++w) { w4[w] = fr_zero<PF>(); for (int l = 0; l < 64; ++l) w4[w] = fr_add<PF>(w4[w], lane[64 * w + l]); }
-            out[slot[p] * ncols + c] = fr_mul<PF>(lag_sum4(w4), scale[p]);
+            out[slot[p] * ncols + c] = scale ? fr_mul<PF>(lag_sum4(w4), scale[p]) : lag_sum4(w4);
+        }
+        return 0;
+    }
+    int32_t combine(const fr_t* partials, size_t nparts, const fr_t* scale, size_t npoints, size_t ncols, fr_t* out) {
+        const size_t total = npoints * ncols;
+        for (size_t i = 0; i < total; ++i) {
+            fr_t acc = partials[i];
+            for (size_t q = 1; q < nparts; ++q) acc = fr_add<PF>(acc, partials[q * total + i]);
+            out[i] = fr_mul<PF>(acc, scale[i / ncols]);
         }
         return 0;
     }
 };
-extern "C" {
-// out[p * ncols + c] = lagrange_eval_on_h(cols[c] (n elements), z[p], omega) through the driver of stark_lagrange_eval_on_h_batch_dev with passes of at
-// most max_partials block partials (0: the default).  omega null: the radix-2 generator of size n.  passes (may be null) = the partial passes taken.
-// -1: a refused (n, omega), as the entry point refuses it.
-int hc_lagrange_eval_batch(size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega, size_t npoints, const uint64_t* z, size_t max_partials, uint64_t* out, size_t* passes) {
+// the domain of an entry point: false when (n, omega) is refused; *w = the caller's generator or the radix-2 one of size n
+static bool hc_lag_domain(size_t n, const uint64_t* omega, fr_t* w) {
+    if (!n || (n & (n - 1)) || n > ((size_t)1 << kLagMaxLogN)) return false;
+    int lg = 0; while (((size_t)1 << lg) < n) ++lg;
+    *w = omega ? ld4(omega) : fr_root_of_unity<PF>((unsigned)lg);
+    return !lag_check_domain(n, *w);
+}
+// THE driver on the block B of the columns (cols[c]: B.n_local rows) with the host executor
+static int hc_lag_block(size_t ncols, const uint64_t* const* cols, const LagBlock& B, const uint64_t* omega, size_t npoints, const uint64_t* z, size_t max_partials, int col_groups, uint64_t* out,
+                        size_t* passes) {
     if (passes) *passes = 0;
     if (!ncols || !npoints) return 0;
-    if (!n || (n & (n - 1)) || n > ((size_t)1 << kLagMaxLogN)) return -1;
-    int lg = 0; while (((size_t)1 << lg) < n) ++lg;
-    const fr_t w = omega ? ld4(omega) : fr_root_of_unity<PF>((unsigned)lg);
-    if (lag_check_domain(n, w)) return -1;
+    fr_t w; if (!hc_lag_domain(B.n_global, omega, &w)) return -1;
+    const size_t n = B.n_local;
     std::vector<std::vector<fr_t>> col(ncols, std::vector<fr_t>(n)); std::vector<const fr_t*> ptrs(ncols); std::vector<fr_t> zs(npoints);
     for (size_t c = 0; c < ncols; ++c) {
         size_t first = c; for (size_t q = 0; q < c; ++q) if (cols[q] == cols[c]) { first = q; break; }      // a repeated pointer stays one column
@@ -929,9 +943,51 @@ int hc_lagrange_eval_batch(size_t ncols, const uint64_t* const* cols, size_t n, 
     for (size_t p = 0; p < npoints; ++p) zs[p] = ld4(z + 4 * p);
     std::vector<fr_t> o = hc_fr_block(npoints * ncols);
     LagHostExec X;
-    if (lagrange_eval_batch(X, ncols, ptrs.data(), n, w, npoints, zs.data(), max_partials ? max_partials : kLagDefaultMaxPartials, o.data(), passes)) return -1;
+    if (lagrange_eval_batch(X, ncols, ptrs.data(), B, w, npoints, zs.data(), max_partials ? max_partials : kLagDefaultMaxPartials, col_groups, o.data(), passes)) return -1;
     for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
     return 0;
+}
+extern "C" {
+// out[p * ncols + c] = lagrange_eval_on_h(cols[c] (n elements), z[p], omega) through the driver of stark_lagrange_eval_on_h_batch_dev with passes of at
+// most max_partials block partials (0: the default).  omega null: the radix-2 generator of size n.  passes (may be null) = the partial passes taken.
+// -1: a refused (n, omega), as the entry point refuses it.
+int hc_lagrange_eval_batch(size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega, size_t npoints, const uint64_t* z, size_t max_partials, uint64_t* out, size_t* passes) {
+    return hc_lag_block(ncols, cols, lag_whole(n), omega, npoints, z, max_partials, -1, out, passes);
+}
+// The block form, stark_lagrange_eval_shard_dev: cols[c] = the n_local rows [j0, j0 + n_local) of column c; partials_out[p * ncols + c] = the block's unscaled
+// share.  col_groups: the option "lagrange_col_groups" (-1: automatic).  -1: refused as the entry point refuses it.
+int hc_lagrange_eval_shard(size_t ncols, const uint64_t* const* cols, size_t n_local, uint64_t j0, size_t n_global, const uint64_t* omega, size_t npoints, const uint64_t* z, size_t max_partials,
+                           int col_groups, uint64_t* partials_out, size_t* passes) {
+    if (passes) *passes = 0;
+    if (!ncols || !npoints) return 0;
+    if (!n_local || j0 > n_global || n_local > n_global - j0) return -1;
+    return hc_lag_block(ncols, cols, LagBlock{n_local, j0, n_global, false}, omega, npoints, z, max_partials, col_groups, partials_out, passes);
+}
+// stark_lagrange_eval_from_partials_dev: out[p * ncols + c] = scale[p] * the sum of the nparts shares (lagrange_combine)
+int hc_lagrange_eval_from_partials(size_t nparts, const uint64_t* partials, size_t ncols, size_t n_global, const uint64_t* omega, size_t npoints, const uint64_t* z, uint64_t* out) {
+    if (!ncols || !npoints) return 0;
+    fr_t w; if (!nparts || !hc_lag_domain(n_global, omega, &w)) return -1;
+    const size_t total = npoints * ncols;
+    std::vector<fr_t> part = hc_fr_block(nparts * total), o = hc_fr_block(total), zs(npoints);
+    for (size_t i = 0; i < part.size(); ++i) part[i] = ld4(partials + 4 * i);
+    for (size_t p = 0; p < npoints; ++p) zs[p] = ld4(z + 4 * p);
+    LagHostExec X;
+    if (lagrange_combine(X, nparts, part.data(), ncols, n_global, npoints, zs.data(), o.data())) return -1;
+    for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
+    return 0;
+}
+// The header of the sharded call's first collective (kLagHdrWords words) and the comparison every rank makes of the W gathered headers with its own
+int hc_lagrange_shard_header(size_t n_global, size_t ncols, size_t npoints, const uint64_t* omega, const uint64_t* z, uint64_t* out8) {
+    std::vector<fr_t> zs(npoints); for (size_t p = 0; p < npoints; ++p) zs[p] = ld4(z + 4 * p);
+    lag_shard_header(n_global, ncols, npoints, ld4(omega), zs.data(), out8); return (int)kLagHdrWords;
+}
+int hc_lagrange_headers_agree(const uint64_t* all, size_t W, const uint64_t* mine) { return lag_headers_agree(all, W, mine) ? 1 : 0; }
+// the column groups the driver launches for a pass of pass_points points of a block of n_local rows (lag_col_groups); *group_cols = the columns of a group
+unsigned hc_lagrange_col_groups(int opt, size_t ncols, size_t n_local, size_t pass_points, size_t* group_cols) {
+    const LagGeom G = lag_geom(n_local); unsigned cg = 1;
+    const size_t per = lag_col_groups(opt, ncols, G.grid, lag_point_groups(pass_points, G.grid), &cg);
+    if (group_cols) *group_cols = per;
+    return cg;
 }
 }  // extern "C"
 

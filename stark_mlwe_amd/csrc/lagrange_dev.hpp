@@ -15,6 +15,17 @@
 // The driver (lagrange_eval_batch) and the per-lane pieces are host code / FR_HD: hostcheck.cpp runs the same driver with every workgroup in
 // lockstep on the CPU (hc_lagrange_eval_batch).  Every stored value is fully reduced, so neither the order of a sum nor how an inverse is
 // obtained changes a bit.
+//
+// BLOCK FORM (LagBlock): the driver works on the rows [j0, j0 + n_local) of a domain of n_global points.  The workgroup geometry, the liveness of a
+// position and the column loads are LOCAL (tid + u T < n_local); the weight is GLOBAL, W = w^(j0 + j) / (z - w^(j0 + j)) with w the generator of
+// the global domain, so a lane starts from lag_pow(j0 + tid) of the global table.  The sum over j splits over blocks and every stored value is
+// fully reduced: the unscaled shares of any partition of [0, n_global), added and scaled by k_lagrange_combine (lagrange_combine), are the bytes of
+// the single call.  A point inside H is the row v[j* - j0] on the block that holds j* and zero elsewhere, and its scale in the combine is one, so
+// one combine rule serves both kinds of point.  The batch call is the block form with j0 = 0, n_local = n_global and the scaled finish.
+//
+// COLUMN GROUPS: blockIdx.z of k_lagrange_partials splits the columns of a launch into contiguous groups (the last may be short); a workgroup
+// recomputes the weights of its points and walks only its group's columns.  The layout of the partials does not depend on it, hence neither do
+// the scratch, the passes or one byte of the result (lag_col_groups: the rule).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -29,6 +40,12 @@ constexpr int kLagMaxLogN = 30;
 constexpr size_t kLagDefaultMaxPartials = (size_t)1 << 21;      // context option "lagrange_max_partials": 64 MiB of block partials per pass
 constexpr size_t kLagMaxCols = (size_t)1 << 24;                 // blockIdx.x of k_lagrange_finish is the (point, column) pair
 constexpr size_t kLagTargetWorkgroups = 1024;                   // point groups are added until a launch has about this many workgroups
+constexpr size_t kLagGroupTargetWorkgroups = 512;               // column groups are added while a launch is below this, two workgroups per CU.  Measured at n = 2^17, 64 columns,
+                                                                // 2 points (128 workgroups in one group; profiles/lagrange_shard_timing.jsonl): 2 / 4 / 8 groups run 0.73 / 0.71 / 1.07 x
+                                                                // the time of one.  Three workgroups fit a CU, so 1024 leave a second round of a third while every group pays its weights
+constexpr size_t kLagMinGroupCols = 8;                          // automatic column groups keep at least this many columns: a weight costs 7.75 products, a column term 1
+constexpr size_t kLagMaxWorkgroups = (size_t)1 << 22;           // a launch stays below 2^30 lanes whatever "lagrange_col_groups" asks for
+constexpr uint64_t kLagNoRow = ~0ull;                           // k_lagrange_gather: a point inside H whose row another block holds -> zero
 constexpr bool kLagWideAcc = true;                              // a lane's K products of a column in the lazy accumulator (fr_wide): K multiplications, one reduction
 
 // c0 = 1 view of a two-level power table (PowTable of ntt_dev.hpp, which is device-only): g^e = lo[e mod 2^lo_bits] * hi[e >> lo_bits]
@@ -56,6 +73,39 @@ inline unsigned lag_point_groups(size_t pass_points, unsigned grid) {
     return (unsigned)std::min<size_t>(std::min<size_t>(pass_points, 65535), std::max<size_t>((kLagTargetWorkgroups + grid - 1) / grid, 1));
 }
 
+// The column groups of a launch of `grid` tiles and `point_groups` point groups over ncols columns -> the columns per group; *groups = how many.
+// opt = the context option "lagrange_col_groups": 1 = one group; g > 1 = min(g, ncols) groups; -1 = automatic: a group is added while every
+// group keeps kLagMinGroupCols columns (a group pays the 7.75 products of a weight again for each of its points and positions, a column term is
+// 1 product: at 8 columns the repeated work is below half) and the launch is below kLagGroupTargetWorkgroups.  No group is empty.
+inline size_t lag_col_groups(int opt, size_t ncols, unsigned grid, unsigned point_groups, unsigned* groups) {
+    const size_t wg = (size_t)grid * point_groups; size_t G = 1;
+    if (opt < 0) while (ncols / (G + 1) >= kLagMinGroupCols && wg * G < kLagGroupTargetWorkgroups) ++G;
+    else G = std::min<size_t>(std::min<size_t>(std::max(opt, 1), ncols), std::min<size_t>(std::max<size_t>(kLagMaxWorkgroups / wg, 1), 65535));
+    const size_t per = (ncols + G - 1) / G;
+    *groups = (unsigned)((ncols + per - 1) / per); return per;
+}
+
+// The rows [j0, j0 + n_local) of a domain of n_global points; scaled: the finish multiplies by (z^n - 1)/n (the batch call: the whole domain)
+struct LagBlock { size_t n_local; uint64_t j0; size_t n_global; bool scaled; };
+inline LagBlock lag_whole(size_t n) { return LagBlock{n, 0, n, true}; }
+
+// The first collective of the sharded call all-gathers this header; ranks whose headers differ were given different arguments.
+constexpr size_t kLagHdrWords = 8;                              // magic, n_global, ncols, npoints, digest of the omega and z bytes, pad
+inline uint64_t lag_digest(uint64_t h, const void* bytes, size_t len) {     // FNV-1a, 64 bit
+    const unsigned char* b = (const unsigned char*)bytes;
+    for (size_t i = 0; i < len; ++i) { h ^= b[i]; h *= 0x100000001B3ull; }
+    return h;
+}
+inline void lag_shard_header(size_t n_global, size_t ncols, size_t npoints, const fr_t& omega, const fr_t* z, uint64_t* h) {
+    for (size_t i = 0; i < kLagHdrWords; ++i) h[i] = 0;
+    h[0] = 0x4C41475348415244ull; h[1] = n_global; h[2] = ncols; h[3] = npoints;
+    h[4] = lag_digest(lag_digest(0xCBF29CE484222325ull, &omega, sizeof(fr_t)), z, npoints * sizeof(fr_t));
+}
+inline bool lag_headers_agree(const uint64_t* all, size_t W, const uint64_t* mine) {
+    for (size_t q = 0; q < W; ++q) for (size_t i = 0; i < kLagHdrWords; ++i) if (all[q * kLagHdrWords + i] != mine[i]) return false;
+    return true;
+}
+
 // nullptr, or why (n, omega) is refused: n a power of two in 1 .. 2^30; omega a primitive n-th root of unity (omega^n = 1 and, for n >= 2,
 // omega^(n/2) = -1), which is what makes every z with z^n = 1 a power of omega.
 inline const char* lag_check_domain(size_t n, const fr_t& omega) {
@@ -77,6 +127,7 @@ inline uint64_t lag_dlog(const fr_t& z, const std::vector<fr_t>& winv2, int k) {
 }
 
 // ---- the work of one lane (tid counted over the whole launch; tid + (K - 1) T < max(n, 2048) <= 2^30, so positions are 32-bit) ------------------
+// tid, T and n are LOCAL to the block (n = n_local); w carries the global power w^(j0 + tid), so nothing below knows j0.
 // The lane walks w^j over its K positions with w_step = w^T and back with its inverse, as ali_merge_block does, instead of holding K powers: the 64
 // registers they would take are what lets three workgroups share a CU, and several resident workgroups are what covers a wave that inverts.
 // forward: pre[u] = product of d_v = z - w^(j_v) over v < u (d = 1 past n); w: w^tid in, w^(tid + K T) out; returns the product over all K
@@ -128,21 +179,27 @@ FR_HD fr_t lag_lane_dot(const fr_t* __restrict__ col, uint32_t tid, uint32_t T, 
 FR_HD fr_t lag_sum4(const fr_t (&w)[4]) { return fr_add<PallasFr>(fr_add<PallasFr>(w[0], w[1]), fr_add<PallasFr>(w[2], w[3])); }
 
 // ---- the driver ------------------------------------------------------------------------------------------------------------------------
-// out[p * ncols + c] = lagrange_eval_on_h(cols[c], z[p], omega) for the executor's memory (device: capi_fri.hip; host: hostcheck.cpp).  The
-// arguments have passed lag_check_domain and the null / overlap checks; ncols, npoints >= 1.  passes (may be null) = the partial passes taken.
-// An executor provides  alloc(bytes, void**)  put(vector<T>, T**)  pow_table(omega, n, LagPow*)  gather(...)  partials(...)  finish(...).
+// The whole domain (B = lag_whole(n)): out[p * ncols + c] = lagrange_eval_on_h(cols[c], z[p], omega).  A block: out[p * ncols + c] = the block's
+// unscaled share, sum over its rows of cols[c][j] w^(j0 + j) / (z[p] - w^(j0 + j)), or for z[p] = w^(j*) inside H the row j* - j0 if the block holds
+// it and zero if not.  For the executor's memory (device: capi_fri.hip; host: hostcheck.cpp); cols[c] = the block's n_local rows.  The arguments
+// have passed lag_check_domain and the null / overlap checks; ncols, npoints >= 1.  passes (may be null) = the partial passes taken.
+// col_groups: the option "lagrange_col_groups" (lag_col_groups).
+// An executor provides  alloc(bytes, void**)  put(vector<T>, T**)  pow_table(omega, n, LagPow*)  gather(...)  partials(...)  finish(...)  combine(...).
 template <class Exec>
-int32_t lagrange_eval_batch(Exec& X, size_t ncols, const fr_t* const* cols, size_t n, const fr_t& omega, size_t npoints, const fr_t* z, size_t max_partials,
-                            fr_t* out, size_t* passes) {
+int32_t lagrange_eval_batch(Exec& X, size_t ncols, const fr_t* const* cols, const LagBlock& B, const fr_t& omega, size_t npoints, const fr_t* z, size_t max_partials,
+                            int col_groups, fr_t* out, size_t* passes) {
+    const size_t n = B.n_global;
     const fr_t one = fr_one<PallasFr>(), n_inv = fr_inv<PallasFr>(fr_from_u64<PallasFr>((uint64_t)n));
     int k = 0; while (((size_t)1 << k) < n) ++k;
     std::vector<fr_t> winv2((size_t)k);
     if (k) { winv2[0] = fr_inv<PallasFr>(omega); for (int i = 1; i < k; ++i) winv2[(size_t)i] = fr_sqr<PallasFr>(winv2[(size_t)i - 1]); }
-    std::vector<fr_t> zo, scale; std::vector<uint64_t> slot_o, jin, slot_i;          // outside H: point, scale, index of the point in the call; inside: j*, index
+    std::vector<fr_t> zo, scale; std::vector<uint64_t> slot_o, jin, slot_i;          // outside H: point, scale, index of the point in the call; inside: local row (or kLagNoRow), index
     for (size_t p = 0; p < npoints; ++p) {
         const fr_t zn = fr_pow_u64<PallasFr>(z[p], (uint64_t)n);
-        if (fr_eq(zn, one)) { jin.push_back(lag_dlog(z[p], winv2, k)); slot_i.push_back((uint64_t)p); }
-        else { zo.push_back(z[p]); scale.push_back(fr_mul<PallasFr>(fr_sub<PallasFr>(zn, one), n_inv)); slot_o.push_back((uint64_t)p); }
+        if (fr_eq(zn, one)) {
+            const uint64_t j = lag_dlog(z[p], winv2, k);
+            jin.push_back(j >= B.j0 && j - B.j0 < B.n_local ? j - B.j0 : kLagNoRow); slot_i.push_back((uint64_t)p);
+        } else { zo.push_back(z[p]); if (B.scaled) scale.push_back(fr_mul<PallasFr>(fr_sub<PallasFr>(zn, one), n_inv)); slot_o.push_back((uint64_t)p); }
     }
     if (passes) *passes = 0;
     const fr_t** d_cols = nullptr;
@@ -154,22 +211,38 @@ int32_t lagrange_eval_batch(Exec& X, size_t ncols, const fr_t* const* cols, size
         rc = X.gather((const fr_t* const*)d_cols, ncols, d_j, d_slot, jin.size(), out); if (rc) return rc;
     }
     if (zo.empty()) return 0;
-    const LagGeom G = lag_geom(n);
+    const LagGeom G = lag_geom(B.n_local);
     const size_t per_pass = std::min(lag_pass_points(max_partials, ncols, G.grid), zo.size());
     if (passes) *passes = (zo.size() + per_pass - 1) / per_pass;
     fr_t *d_z = nullptr, *d_scale = nullptr; uint64_t* d_slot = nullptr; void* d_part = nullptr; LagPow wp;
     int32_t rc = X.put(zo, &d_z); if (rc) return rc;
-    rc = X.put(scale, &d_scale); if (rc) return rc;
+    if (B.scaled) { rc = X.put(scale, &d_scale); if (rc) return rc; }
     rc = X.put(slot_o, &d_slot); if (rc) return rc;
     rc = X.alloc(per_pass * ncols * G.grid * sizeof(fr_t), &d_part); if (rc) return rc;       // reused by every pass: they are ordered on one stream
     rc = X.pow_table(omega, n, &wp); if (rc) return rc;
     const fr_t w_step = fr_pow_u64<PallasFr>(omega, G.T), w_step_inv = fr_inv<PallasFr>(w_step);
     for (size_t p0 = 0; p0 < zo.size(); p0 += per_pass) {
         const size_t pp = std::min(per_pass, zo.size() - p0);
-        rc = X.partials((const fr_t* const*)d_cols, ncols, n, wp, w_step, w_step_inv, d_z + p0, pp, lag_point_groups(pp, G.grid), G.grid, (fr_t*)d_part); if (rc) return rc;
-        rc = X.finish((const fr_t*)d_part, G.grid, d_scale + p0, d_slot + p0, pp, ncols, out); if (rc) return rc;
+        const unsigned pg = lag_point_groups(pp, G.grid); unsigned cg = 1;
+        const size_t group_cols = lag_col_groups(col_groups, ncols, G.grid, pg, &cg);
+        rc = X.partials((const fr_t* const*)d_cols, ncols, B.n_local, B.j0, wp, w_step, w_step_inv, d_z + p0, pp, pg, cg, group_cols, G.grid, (fr_t*)d_part); if (rc) return rc;
+        rc = X.finish((const fr_t*)d_part, G.grid, B.scaled ? d_scale + p0 : nullptr, d_slot + p0, pp, ncols, out); if (rc) return rc;     // no scale: the unscaled finish
     }
     return 0;
+}
+// out[p * ncols + c] = scale[p] * sum over q < nparts of partials[(q * npoints + p) * ncols + c], scale = (z^n - 1)/n outside H and one inside:
+// lagrange_eval_on_h of the whole columns when the parts are the blocks' shares of a partition of [0, n).
+template <class Exec>
+int32_t lagrange_combine(Exec& X, size_t nparts, const fr_t* partials, size_t ncols, size_t n, size_t npoints, const fr_t* z, fr_t* out) {
+    const fr_t one = fr_one<PallasFr>(), n_inv = fr_inv<PallasFr>(fr_from_u64<PallasFr>((uint64_t)n));
+    std::vector<fr_t> scale(npoints);
+    for (size_t p = 0; p < npoints; ++p) {
+        const fr_t zn = fr_pow_u64<PallasFr>(z[p], (uint64_t)n);
+        scale[p] = fr_eq(zn, one) ? one : fr_mul<PallasFr>(fr_sub<PallasFr>(zn, one), n_inv);
+    }
+    fr_t* d_scale = nullptr;
+    int32_t rc = X.put(scale, &d_scale); if (rc) return rc;
+    return X.combine(partials, nparts, (const fr_t*)d_scale, npoints, ncols, out);
 }
 
 #if defined(__HIPCC__)
@@ -178,17 +251,20 @@ __device__ __forceinline__ fr_t lag_ld_lds(const uint4* p, int i) {
     const uint4 lo = p[2 * i], hi = p[2 * i + 1]; fr_t x;
     x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w; x.v[4] = hi.x; x.v[5] = hi.y; x.v[6] = hi.z; x.v[7] = hi.w; return x;
 }
-// Workgroup blockIdx.x of gridDim.x tiles, point group blockIdx.y: the points blockIdx.y, blockIdx.y + gridDim.y, ... < npts of zs;
-// partials[(p * ncols + c) * gridDim.x + blockIdx.x] = this workgroup's share of sum_j cols[c][j] W_j(zs[p]).  The scan-and-invert step is the
+// Workgroup blockIdx.x of gridDim.x tiles, point group blockIdx.y: the points blockIdx.y, blockIdx.y + gridDim.y, ... < npts of zs; column group
+// blockIdx.z: the columns [blockIdx.z * group_cols, + group_cols) below ncols;
+// partials[(p * ncols + c) * gridDim.x + blockIdx.x] = this workgroup's share of sum_j cols[c][j] W_(j0 + j)(zs[p]) over the n64 local rows.
+// A lane past the block (tid >= n) reads no power: j0 + tid may lie past the table of the global domain.  The scan-and-invert step is the
 // one of ali_merge_block (fri_dev.hpp), whose comment says why one inversion per lane would dwarf the useful work; it is a copy, not a shared
 // helper, so that the merge kernels' code does not move (open unification).
 template <bool WIDE>
-__global__ void __launch_bounds__(256, 3) k_lagrange_partials(const fr_t* const* __restrict__ cols, uint64_t ncols, uint64_t n64, LagPow wp, fr_t w_step, fr_t w_step_inv,
-                                                           const fr_t* __restrict__ zs, uint64_t npts, fr_t* __restrict__ partials) {
+__global__ void __launch_bounds__(256, 3) k_lagrange_partials(const fr_t* const* __restrict__ cols, uint64_t ncols, uint64_t n64, uint64_t j0, LagPow wp, fr_t w_step, fr_t w_step_inv,
+                                                           const fr_t* __restrict__ zs, uint64_t npts, uint64_t group_cols, fr_t* __restrict__ partials) {
     __shared__ uint4 tot[2 * 4], pinv[2], red[2][2 * 4];
     const uint32_t T = gridDim.x * 256, tid = blockIdx.x * 256 + threadIdx.x, n = (uint32_t)n64;
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    fr_t w = tid < n ? lag_pow(wp, tid) : fr_one<PallasFr>();      // w^tid; every point leaves it there again
+    const uint64_t c_lo = (uint64_t)blockIdx.z * group_cols, c_hi = c_lo + group_cols < ncols ? c_lo + group_cols : ncols;
+    fr_t w = tid < n ? lag_pow(wp, j0 + tid) : fr_one<PallasFr>(); // w^(j0 + tid); every point leaves it there again
     for (uint64_t p = blockIdx.y; p < npts; p += gridDim.y) {
         const fr_t z = ldg(zs + p);
         fr_t W[kLagK];
@@ -221,7 +297,7 @@ __global__ void __launch_bounds__(256, 3) k_lagrange_partials(const fr_t* const*
         }
         // The columns: the pointer table is indexed, never a register array.  red[] alternates between two halves, so one barrier per column
         // orders thread 0's reads of a half before its next writers; tot and pinv of the next point are written behind at least that barrier.
-        for (uint64_t c = 0; c < ncols; ++c) {
+        for (uint64_t c = c_lo; c < c_hi; ++c) {
             fr_t acc = lag_lane_dot<WIDE>(cols[c], tid, T, n, W);
 #pragma unroll
             for (int sft = 1; sft < 64; sft <<= 1) acc = fr_add<PallasFr>(acc, shfl_xor_fr(acc, sft));
@@ -235,7 +311,8 @@ __global__ void __launch_bounds__(256, 3) k_lagrange_partials(const fr_t* const*
         }
     }
 }
-// One block per (point, column) of a pass, in the shape of k_sum_single_block: out[slot[p] * ncols + c] = scale[p] * the sum of the pair's `grid` partials.
+// One block per (point, column) of a pass, in the shape of k_sum_single_block: out[slot[p] * ncols + c] = scale[p] * the sum of the pair's `grid` partials
+// (scale null: the sum itself, a block's unscaled share).
 static __global__ void __launch_bounds__(256) k_lagrange_finish(const fr_t* __restrict__ partials, uint64_t grid, const fr_t* __restrict__ scale, const uint64_t* __restrict__ slot,
                                                                 uint64_t ncols, fr_t* __restrict__ out) {
     __shared__ uint4 red[2 * 4];
@@ -249,16 +326,27 @@ static __global__ void __launch_bounds__(256) k_lagrange_finish(const fr_t* __re
     __syncthreads();
     if (threadIdx.x == 0) {
         const fr_t w4[4] = {lag_ld_lds(red, 0), lag_ld_lds(red, 1), lag_ld_lds(red, 2), lag_ld_lds(red, 3)};
-        stg(out + slot[p] * ncols + c, fr_mul<PallasFr>(lag_sum4(w4), ldg(scale + p)));
+        const fr_t sum = lag_sum4(w4);
+        stg(out + slot[p] * ncols + c, scale ? fr_mul<PallasFr>(sum, ldg(scale + p)) : sum);
     }
 }
-// The points inside H: out[slot[q] * ncols + c] = cols[c][j[q]] for the `cnt` such points and all columns, copied.
+// The points inside H: out[slot[q] * ncols + c] = cols[c][j[q]] for the `cnt` such points and all columns, copied; j[q] = kLagNoRow (the row belongs to
+// another block): zero.
 static __global__ void __launch_bounds__(256) k_lagrange_gather(const fr_t* const* __restrict__ cols, uint64_t ncols, const uint64_t* __restrict__ j, const uint64_t* __restrict__ slot,
                                                                 uint64_t cnt, fr_t* __restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cnt * ncols) return;
     const uint64_t q = i / ncols, c = i % ncols;
-    stg(out + slot[q] * ncols + c, ldg(cols[c] + j[q]));
+    stg(out + slot[q] * ncols + c, j[q] == kLagNoRow ? fr_zero<PallasFr>() : ldg(cols[c] + j[q]));
+}
+// The combine of the blocks' shares, one lane per result (nparts is a rank count): out[i] = scale[i / ncols] * sum_q partials[q * total + i].
+static __global__ void __launch_bounds__(256) k_lagrange_combine(const fr_t* __restrict__ partials, uint64_t nparts, const fr_t* __restrict__ scale, uint64_t total, uint64_t ncols,
+                                                                 fr_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    fr_t acc = ldg(partials + i);
+    for (uint64_t q = 1; q < nparts; ++q) acc = fr_add<PallasFr>(acc, ldg(partials + q * total + i));
+    stg(out + i, fr_mul<PallasFr>(acc, ldg(scale + i / ncols)));
 }
 #endif  // __HIPCC__
 
