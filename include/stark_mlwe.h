@@ -10,7 +10,8 @@
  *   - A field element is 4 little-endian uint64_t limbs in Montgomery form (R = 2^256): exactly the
  *     in-memory layout of ark-ff `Fp<MontBackend<_,4>,4>`, so `&[F]` <-> `const uint64_t*` is zero-copy.
  *   - Plain-named functions take HOST pointers (what a Rust slice hands over) and return when the
- *     result is in the caller's buffer.  `*_dev` variants take DEVICE pointers obtained from
+ *     result is in the caller's buffer.  A plain-named function returns, with any status, only after the
+ *     device has finished reading the caller's arrays.  `*_dev` variants take DEVICE pointers obtained from
  *     stark_malloc (or any hipMalloc'd / torch CUDA memory) and are stream-ordered on the context's
  *     stream; call stark_ctx_sync before reading results on the host.
  *   - Every function returns a status: 0 = OK, negative = error class.  stark_last_error() gives text.

@@ -125,10 +125,8 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
                    memcpy(b8 + (ef_elems + lf_elems) * sizeof(fr_t), k.blk8s_gfrag.data(), k.blk8s_gfrag.size());
                    memcpy(b8 + (ef_elems + lf_elems + gf_elems) * sizeof(fr_t), k.rc_partial_scaled.data(), rcs_elems * sizeof(fr_t));
                    memcpy(b8 + (ef_elems + lf_elems + gf_elems + rcs_elems) * sizeof(fr_t), k.blk8_unscale29.data(), k.blk8_unscale29.size() * 4); }
-    STARK_HIP(ctx, P->blob.alloc(blob.size() * sizeof(fr_t)));
+    STARK_TRY(P->blob.fill_sync(ctx, blob.data(), blob.size() * sizeof(fr_t)));
     fr_t* const dev = P->blob.fr();
-    STARK_HIP(ctx, hipMemcpyAsync(dev, blob.data(), blob.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     P->dev.t = k.t; P->dev.rf = k.rf; P->dev.rp = k.rp;
     P->dev.rc_full = dev + o_rcf; P->dev.rc_partial = dev + o_rcp; P->dev.lu = dev + o_lu; P->dev.lu_pre = dev + o_pre;
     P->dev.row0 = dev + o_row0; P->dev.sparse = dev + o_sp; P->dev.mds = dev + o_mds; P->dev.mds_pre = dev + o_mpre; P->dev.gamma = dev + o_gam;
@@ -284,7 +282,7 @@ int32_t stark_free(stark_ctx_t* ctx, void* dptr) { if (!ctx) return STARK_ERR_IN
 int32_t stark_memcpy_h2d(stark_ctx_t* ctx, void* d, const void* s, size_t bytes) {
     if (!ctx) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    STARK_HIP(ctx, hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK; }
+    return DevMem::fill_sync(ctx, d, s, bytes); }
 int32_t stark_memcpy_d2h(stark_ctx_t* ctx, void* d, const void* s, size_t bytes) {
     if (!ctx) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));

@@ -229,7 +229,7 @@ static int32_t challenge_stage(stark_ctx* ctx, size_t B, const fr_t* const* cols
     const char* tags[4] = {"ALI/A", "ALI/S", "ALI/E", "ALI/T"};
     if (std::all_of(n0, n0 + B, [&](size_t n) { return n == n0[0]; })) {
         STARK_HIP(ctx, dptr.alloc(ctx, 4 * B * sizeof(void*)));
-        STARK_HIP(ctx, hipMemcpyAsync(dptr.p, cols, 4 * B * sizeof(void*), hipMemcpyHostToDevice, ctx->stream));
+        STARK_TRY(ctx_upload_staged(ctx, dptr.p, cols, 4 * B * sizeof(void*)));
         STARK_TRY(tr_hash_columns_batch_dev(ctx, tags, (const fr_t* const*)dptr.p, B, n0[0], dig.fr()));
     } else {
         std::vector<const char*> tg(4 * B); std::vector<size_t> kk(4 * B);
@@ -241,13 +241,13 @@ static int32_t challenge_stage(stark_ctx* ctx, size_t B, const fr_t* const* cols
     // seed_f = H("ALI/seed", [h_a, h_s, h_e, h_t, n0]) and the fused hash of ali_sample_z_beta_fs (fri.rs:556-557, 511-515)
     std::vector<fr_t> in5(5 * B); for (size_t p = 0; p < B; ++p) { for (int c = 0; c < 4; ++c) in5[5 * p + c] = out.h[4 * p + c]; in5[5 * p + 4] = host::h_u64(n0[p]); }
     STARK_HIP(ctx, seeds_in.alloc(ctx, in5.size() * sizeof(fr_t))); STARK_HIP(ctx, seeds.alloc(ctx, B * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(seeds_in.p, in5.data(), in5.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
+    STARK_TRY(ctx_upload_staged(ctx, seeds_in.p, in5.data(), in5.size() * sizeof(fr_t)));
     STARK_TRY(tr_hash_dev(ctx, "ALI/seed", seeds_in.fr(), 5, B, seeds.fr()));
     out.seed_f.resize(B);
     STARK_HIP(ctx, hipMemcpyAsync(out.seed_f.data(), seeds.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<fr_t> in2(2 * B), fu(B); for (size_t p = 0; p < B; ++p) { in2[2 * p] = out.seed_f[p]; in2[2 * p + 1] = host::h_u64(n0[p]); }
     STARK_HIP(ctx, deep_in.alloc(ctx, in2.size() * sizeof(fr_t))); STARK_HIP(ctx, fused.alloc(ctx, B * sizeof(fr_t)));
-    STARK_HIP(ctx, hipMemcpyAsync(deep_in.p, in2.data(), in2.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
+    STARK_TRY(ctx_upload_staged(ctx, deep_in.p, in2.data(), in2.size() * sizeof(fr_t)));
     STARK_TRY(tr_hash_dev(ctx, "ALI/DEEP", deep_in.fr(), 2, B, fused.fr()));
     STARK_HIP(ctx, hipMemcpyAsync(fu.data(), fused.p, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     out.z.resize(B); out.beta.resize(B);
@@ -340,18 +340,11 @@ struct StateArrays {                                    // a stark_fri_state: on
 struct stark_fri_plan { CtxRef ref_; stark_ctx* ctx = nullptr; FriPlan plan; };
 
 // ---- a pass of traces: the side-by-side commit (fri_batch.hpp), the query phase, the pass function and the batch drivers over them ----------
-// The executor of FriBatchCommit on the device.  Everything it allocates is pooled and returns to the pool with it; the folds run on the
-// context's stream, the commitments on the current one (the side stream between fork() and side(false)).
-struct FriDevExec {
-    stark_ctx* ctx; hipStream_t main_st, cur; std::vector<DevBuf> blocks; StreamFork fk;      // fk after blocks: a scope left forked drains before they are released
-    explicit FriDevExec(stark_ctx* c) : ctx(c), main_st(c->stream), cur(c->stream), fk(c) {}
-    int32_t alloc(size_t bytes, void** out) { DevBuf b; STARK_TRY(b.take(ctx, bytes)); *out = b.p; blocks.push_back(std::move(b)); return STARK_OK; }
-    int32_t upload(void* dst, const void* src, size_t bytes) { return ctx_upload_staged(ctx, dst, src, bytes); }     // the context owns the host copy: src may die on return
-    template <class T> int32_t put(const std::vector<T>& h, T** out) {
-        void* p = nullptr; STARK_TRY(alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p));
-        if (!h.empty()) STARK_TRY(upload(p, h.data(), h.size() * sizeof(T)));
-        *out = (T*)p; return STARK_OK;
-    }
+// The executor of FriBatchCommit on the device.  Its memory is the arena's; the folds run on the context's stream, the commitments on the
+// current one (the side stream between fork() and side(false)).
+struct FriDevExec : DevArena {
+    hipStream_t main_st, cur; StreamFork fk;      // fk is destroyed before the arena's blocks: a scope left forked drains before they are released
+    explicit FriDevExec(stark_ctx* c) : DevArena(c), main_st(c->stream), cur(c->stream), fk(c) {}
     int32_t zpows(const fr_t& z, size_t m, fr_t* zp) { return zpows_launch(ctx, main_st, z, m, zp); }
     int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out) { return fold_launch(ctx, main_st, f, n, zp, m, out); }
     int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h) { return leaf_pair_hash_on(ctx, cur, f, f_next, n, m, h); }
@@ -373,7 +366,7 @@ static int32_t batch_commit_begin(stark_ctx* ctx, FriDevBatch& C, size_t Bp, siz
     return C.init(z.data());
 }
 // Layer 0 of a pass from a host table of per-trace device pointers: one copy kernel.
-static int32_t batch_fill_layer0(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, const uint64_t* const* f0) {
+static int32_t batch_fill_layer0(stark_ctx* ctx, DevArena& X, FriDevBatch& C, const uint64_t* const* f0) {
     std::vector<const fr_t*> h(C.Bp); for (size_t b = 0; b < C.Bp; ++b) h[b] = as_fr(f0[b]);
     const fr_t** d = nullptr; STARK_TRY(X.put(h, &d));
     hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)((C.n[0] + 255) / 256), (unsigned)C.Bp), dim3(256), 0, ctx->stream, (const fr_t* const*)d, (uint64_t)C.n[0], C.f[0]);
@@ -381,7 +374,7 @@ static int32_t batch_fill_layer0(stark_ctx* ctx, FriDevExec& X, FriDevBatch& C, 
 }
 // deep_ali_merge_evals_blinded of Bp <= kMaxPassTraces traces over one domain of n points in one launch (k_ali_merge_batch).  Tables, z and beta are
 // device arrays; the result goes to out_base + b n or to out_ptrs[b]; c_star_dev (optional) receives c*[b] through one batched reduction.
-static int32_t ali_merge_batch_launch(stark_ctx* ctx, FriDevExec& X, size_t Bp, const fr_t* const* a, const fr_t* const* s, const fr_t* const* e, const fr_t* const* t,
+static int32_t ali_merge_batch_launch(stark_ctx* ctx, DevArena& X, size_t Bp, const fr_t* const* a, const fr_t* const* s, const fr_t* const* e, const fr_t* const* t,
                                       const fr_t* const* r_opt, const fr_t* beta, const fr_t& omega, const fr_t* z, size_t n, fr_t* out_base, fr_t* const* out_ptrs, fr_t* c_star_dev) {
     PowTable wp; STARK_TRY(omega_table(ctx, omega, n, &wp));
     const unsigned block = 256; const uint64_t lanes = (n + ALI_K - 1) / ALI_K; const unsigned grid = (unsigned)((lanes + block - 1) / block);
@@ -533,7 +526,7 @@ static int32_t commit_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const
 // stark_ali_merge_batch_dev: tables of `batch` device pointers (host), z / beta on the host; kMaxPassTraces traces per launch.
 static int32_t ali_merge_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, const uint64_t* const* r_opt,
                                     const uint64_t* beta, const fr_t& omega, const uint64_t* z, size_t n, uint64_t* const* f0, uint64_t* c_star) {
-    FriDevExec X(ctx);
+    DevArena X(ctx);
     std::vector<const fr_t*> tab(5 * B, nullptr); std::vector<fr_t*> outp(B); std::vector<fr_t> zb(2 * B, host::h_zero()), cs(B);
     bool blinded = false;
     for (size_t b = 0; b < B; ++b) {
@@ -549,14 +542,12 @@ static int32_t ali_merge_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* co
         STARK_TRY(ali_merge_batch_launch(ctx, X, Bp, d_tab + b0, d_tab + B + b0, d_tab + 2 * B + b0, d_tab + 3 * B + b0, blinded ? d_tab + 4 * B + b0 : nullptr, d_zb + B + b0, omega, d_zb + b0, n,
                                          nullptr, d_out + b0, d_cs ? d_cs + b0 : nullptr));
     }
-    if (c_star) STARK_HIP(ctx, hipMemcpyAsync(cs.data(), d_cs, B * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));       // the caller reads f0 and c_star on return
+    STARK_TRY(X.download(cs.data(), d_cs, c_star ? B * sizeof(fr_t) : 0));       // the caller reads f0 and c_star on return
     if (c_star) for (size_t b = 0; b < B; ++b) store_fr(c_star + 4 * b, cs[b]);
     return STARK_OK;
 }
 
 // ---- lagrange_eval_on_h of device-resident columns (deep_ali/src/lib.rs:17-45; lagrange_dev.hpp) -----------------------------------------------
-// The executor of lagrange_eval_batch on the device: pooled blocks that return to the pool with it, staged uploads, every launch on the context's stream.
 // (n, omega4) of a lagrange_eval entry point: *omega = the caller's generator or the radix-2 one of size n
 static int32_t lagrange_check_domain(stark_ctx* ctx, size_t n, const uint64_t* omega4, fr_t* omega) {
     if (!is_pow2(n) || n > ((size_t)1 << kLagMaxLogN)) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: n must be a power of two, 1 <= n <= 2^30");
@@ -564,8 +555,9 @@ static int32_t lagrange_check_domain(stark_ctx* ctx, size_t n, const uint64_t* o
     if (const char* why = lag_check_domain(n, *omega)) return ctx->fail(STARK_ERR_INVALID_ARG, std::string("lagrange_eval: ") + why);
     return STARK_OK;
 }
-struct LagDevExec : FriDevExec {
-    explicit LagDevExec(stark_ctx* c) : FriDevExec(c) {}
+// The executor of lagrange_eval_batch on the device: the arena's memory, every launch on the context's stream.
+struct LagDevExec : DevArena {
+    explicit LagDevExec(stark_ctx* c) : DevArena(c) {}
     int32_t pow_table(const fr_t& omega, size_t n, LagPow* out) {                        // the merge's table of this domain (PowCache): a prove that merged over it has filled it
         PowTable t; STARK_TRY(omega_table(ctx, omega, n, &t)); *out = LagPow{t.lo, t.hi, t.lo_bits}; return STARK_OK;
     }
@@ -629,7 +621,7 @@ static int32_t lagrange_sharded(const ShardColl& C, size_t ncols, const uint64_t
         std::vector<DevBuf> hb(C.local()); std::vector<void*> buf;
         for (size_t i = 0; i < hb.size(); ++i) {
             STARK_TRY(hb[i].take(ctx, W * hbytes));
-            STARK_HIP(ctx, hipMemcpyAsync((char*)hb[i].p + (size_t)C.rank(i) * hbytes, h, hbytes, hipMemcpyHostToDevice, ctx->stream));
+            STARK_TRY(ctx_upload_staged(ctx, (char*)hb[i].p + (size_t)C.rank(i) * hbytes, h, hbytes));
             buf.push_back(hb[i].p);
         }
         STARK_TRY(C.all_gather(buf, hbytes));
@@ -713,9 +705,9 @@ int32_t stark_fri_fold(stark_ctx_t* ctx, const uint64_t* f, size_t n, const uint
     if (!ctx || !z4 || (!f && n) || (!out && n)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     if (m < 2) return ctx->fail(STARK_ERR_INVALID_ARG, "m >= 2"); if (n % m) return ctx->fail(STARK_ERR_INVALID_ARG, "layer size must be divisible by m");
-    DevBuf df, dout; STARK_HIP(ctx, df.upload(ctx, f, n * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n / m * sizeof(fr_t)));
+    DevBuf df, dout; CallerUploads up(ctx); STARK_HIP(ctx, up.up(df, f, n * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n / m * sizeof(fr_t)));
     STARK_TRY(fold_dev(ctx, df.fr(), n, load_fr(z4), m, dout.fr()));
-    STARK_HIP(ctx, dout.download_sync(out, n / m * sizeof(fr_t))); return STARK_OK;
+    STARK_HIP(ctx, up.download_sync(out, dout.p, n / m * sizeof(fr_t))); return STARK_OK;
 }
 int32_t stark_fri_build_dev(stark_ctx_t* ctx, const uint64_t* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state_t** out) {
     if (!ctx || !f0 || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
@@ -726,8 +718,9 @@ int32_t stark_fri_build_dev(stark_ctx_t* ctx, const uint64_t* f0, size_t n0, con
 int32_t stark_fri_build(stark_ctx_t* ctx, const uint64_t* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, stark_fri_state_t** out) {
     if (!ctx || !f0 || !out || (!schedule && L)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    DevBuf d; STARK_HIP(ctx, d.upload(ctx, f0, n0 * sizeof(fr_t)));
+    DevBuf d; CallerUploads up(ctx); STARK_HIP(ctx, up.up(d, f0, n0 * sizeof(fr_t)));
     std::unique_ptr<stark_fri_state> S; STARK_TRY(fri_build_impl(ctx, d.fr(), n0, schedule, L, seed_z, S));
+    STARK_HIP(ctx, up.sync());                                      // fri_build_impl only enqueues: the device has read f0 from here on
     *out = S.release(); return STARK_OK;
 }
 int32_t stark_fri_num_layers(stark_fri_state_t* s) { return s ? (int32_t)s->f.size() : STARK_ERR_INVALID_ARG; }
@@ -755,11 +748,11 @@ int32_t stark_ali_merge(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, 
                         const uint64_t* omega4, const uint64_t* z4, size_t n, uint64_t* f0, uint64_t* c_star4) {
     if (!ctx || !a || !s || !e || !t || !omega4 || !z4 || !f0 || (r_opt && !beta4)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    DevBuf d[6]; const uint64_t* src[5] = {a, s, e, t, r_opt};
-    for (int i = 0; i < 5; ++i) if (src[i]) STARK_HIP(ctx, d[i].upload(ctx, src[i], n * sizeof(fr_t)));
+    DevBuf d[6]; CallerUploads up(ctx); const uint64_t* src[5] = {a, s, e, t, r_opt};
+    for (int i = 0; i < 5; ++i) if (src[i]) STARK_HIP(ctx, up.up(d[i], src[i], n * sizeof(fr_t)));
     STARK_HIP(ctx, d[5].alloc(ctx, n * sizeof(fr_t)));
     STARK_TRY(stark_ali_merge_dev(ctx, (const uint64_t*)d[0].p, (const uint64_t*)d[1].p, (const uint64_t*)d[2].p, (const uint64_t*)d[3].p, r_opt ? (const uint64_t*)d[4].p : nullptr, beta4, omega4, z4, n, (uint64_t*)d[5].p, c_star4));
-    STARK_HIP(ctx, d[5].download_sync(f0, n * sizeof(fr_t))); return STARK_OK;
+    STARK_HIP(ctx, up.download_sync(f0, d[5].p, n * sizeof(fr_t))); return STARK_OK;
 }
 int32_t stark_build_f0_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, size_t n0, uint64_t* f0, uint64_t* aux7) {
     if (!ctx || !a || !s || !e || !t || !f0) return STARK_ERR_INVALID_ARG;
@@ -770,11 +763,11 @@ int32_t stark_build_f0_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* 
 int32_t stark_build_f0(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, size_t n0, uint64_t* f0, uint64_t* aux7) {
     if (!ctx || !a || !s || !e || !t || !f0) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    DevBuf d[5]; const uint64_t* src[4] = {a, s, e, t};
-    for (int i = 0; i < 4; ++i) STARK_HIP(ctx, d[i].upload(ctx, src[i], n0 * sizeof(fr_t)));
+    DevBuf d[5]; CallerUploads up(ctx); const uint64_t* src[4] = {a, s, e, t};
+    for (int i = 0; i < 4; ++i) STARK_HIP(ctx, up.up(d[i], src[i], n0 * sizeof(fr_t)));
     STARK_HIP(ctx, d[4].alloc(ctx, n0 * sizeof(fr_t)));
     STARK_TRY(stark_build_f0_dev(ctx, (const uint64_t*)d[0].p, (const uint64_t*)d[1].p, (const uint64_t*)d[2].p, (const uint64_t*)d[3].p, n0, (uint64_t*)d[4].p, aux7));
-    STARK_HIP(ctx, d[4].download_sync(f0, n0 * sizeof(fr_t))); return STARK_OK;
+    STARK_HIP(ctx, up.download_sync(f0, d[4].p, n0 * sizeof(fr_t))); return STARK_OK;
 }
 
 int32_t stark_deep_fri_prove_dev(stark_ctx_t* ctx, const uint64_t* a, const uint64_t* s, const uint64_t* e, const uint64_t* t, const uint64_t* f0, size_t n0,
@@ -793,8 +786,8 @@ int32_t stark_deep_fri_prove(stark_ctx_t* ctx, const uint64_t* a, const uint64_t
                              const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof_t** out) {
     if (!ctx || !out || (!schedule && L) || (!f0 && (!a || !s || !e || !t))) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    DevBuf d[5]; const uint64_t* src[5] = {a, s, e, t, f0};
-    for (int i = 0; i < 5; ++i) if ((i < 4 && !f0) || (i == 4 && f0)) STARK_HIP(ctx, d[i].upload(ctx, src[i], n0 * sizeof(fr_t)));
+    DevBuf d[5]; CallerUploads up(ctx); const uint64_t* src[5] = {a, s, e, t, f0};
+    for (int i = 0; i < 5; ++i) if ((i < 4 && !f0) || (i == 4 && f0)) STARK_HIP(ctx, up.up(d[i], src[i], n0 * sizeof(fr_t)));
     return stark_deep_fri_prove_dev(ctx, (const uint64_t*)d[0].p, (const uint64_t*)d[1].p, (const uint64_t*)d[2].p, (const uint64_t*)d[3].p, f0 ? (const uint64_t*)d[4].p : nullptr, n0, schedule, L, r, seed_z, out);
 }
 int32_t stark_deep_fri_prove_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, size_t n0,
@@ -869,10 +862,9 @@ int32_t stark_lagrange_eval_on_h(stark_ctx_t* ctx, const uint64_t* values, size_
     if (!values || !z4 || !out4) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: null values, z or out");
     if (!is_pow2(n) || n > ((size_t)1 << kLagMaxLogN)) return ctx->fail(STARK_ERR_INVALID_ARG, "lagrange_eval: n must be a power of two, 1 <= n <= 2^30");
     STARK_TRY(ctx_enter(ctx));
-    DevBuf d, o; STARK_HIP(ctx, d.upload(ctx, values, n * sizeof(fr_t))); STARK_HIP(ctx, o.alloc(ctx, sizeof(fr_t)));
-    const int32_t rc = stark_lagrange_eval_on_h_dev(ctx, (const uint64_t*)d.p, n, z4, omega4, (uint64_t*)o.p);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }                          // the upload reads the caller's `values`
-    STARK_HIP(ctx, o.download_sync(out4, sizeof(fr_t))); return STARK_OK;
+    DevBuf d, o; CallerUploads up(ctx); STARK_HIP(ctx, up.up(d, values, n * sizeof(fr_t))); STARK_HIP(ctx, o.alloc(ctx, sizeof(fr_t)));
+    STARK_TRY(stark_lagrange_eval_on_h_dev(ctx, (const uint64_t*)d.p, n, z4, omega4, (uint64_t*)o.p));
+    STARK_HIP(ctx, up.download_sync(out4, o.p, sizeof(fr_t))); return STARK_OK;
 }
 // The block form (lagrange_dev.hpp): the unscaled share of the rows [j0, j0 + n_local) of an n_global-point domain, and the combine of such shares.
 int32_t stark_lagrange_eval_shard_dev(stark_ctx_t* ctx, size_t ncols, const uint64_t* const* cols, size_t n_local, uint64_t j0, size_t n_global, const uint64_t* omega4, size_t npoints,

@@ -54,11 +54,11 @@ template <class Fn> static int32_t with_field(stark_ctx* ctx, int32_t field_id, 
     if (field_id == STARK_FIELD_BLS12_381_FR) return fn(Bls12381Fr{});
     return ctx->fail(STARK_ERR_INVALID_ARG, "unknown field id");
 }
-// One field element as a device constant (a scale word of ntt_run).  The upload reads `host` when the stream reaches it and the word goes
-// back to the pool with this object: the caller synchronises the context's stream before it lets go of it.
+// One field element as a device constant (a scale word of ntt_run): a staged upload into a pooled word that goes back to the pool, in stream
+// order, with this object.
 struct DevWord {
-    fr_t host; DevBuf dev;
-    int32_t set(stark_ctx* ctx, const fr_t& v) { host = v; STARK_HIP(ctx, dev.upload(ctx, &host, sizeof(fr_t))); return STARK_OK; }
+    DevBuf dev;
+    int32_t set(stark_ctx* ctx, const fr_t& v) { STARK_HIP(ctx, dev.alloc(ctx, sizeof(fr_t))); return ctx_upload_staged(ctx, dev.p, &v, sizeof(fr_t)); }
 };
 
 template <class F>
@@ -87,9 +87,7 @@ static int32_t get_plan(stark_ctx* ctx, int log_n, bool inverse, NttPlan** out) 
     }
     if (inverse) {
         fr_t ninv = x32<F>(fr_inv<F>(fr_from_u64<F>(1ull << log_n)));
-        if (p->scale.alloc(sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "ntt scale");
-        if (hipMemcpyAsync(p->scale.p, &ninv, sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "ntt scale copy");
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "sync");
+        STARK_TRY(p->scale.fill_sync(ctx, &ninv, sizeof(fr_t)));
     }
     *out = ctx->plans[key] = p.release(); return STARK_OK;
 }
@@ -425,8 +423,7 @@ static int32_t shard_phase(stark_ctx* ctx, const ShardPlan& P, ShardRank& K, int
     case 2: { // [W][nrl][ncl] -> [nrl][C] (rows k1 of c[k1 + R k']); row phase with n^-1; first phase of every coset transform on that slab; pack for exchange 2
         STARK_TRY(pack3(ctx, K.t0.fr(), K.t1.fr(), W, nrl, ncl, 1, 0, 2));
         { DevWord sc; STARK_TRY(sc.set(ctx, x32<F>(fr_inv<F>(fr_from_u64<F>(1ull << P.log_n)))));
-          STARK_TRY((ntt_run<F>(ctx, K.t1.fr(), P.log_cols, nrl, true, nullptr, sc.dev.fr())));
-          STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); }                                       // the scale word is freed on leaving this scope
+          STARK_TRY((ntt_run<F>(ctx, K.t1.fr(), P.log_cols, nrl, true, nullptr, sc.dev.fr()))); }
         const fr_t wN = fr_root_of_unity<F>((unsigned)(P.log_n + P.lb)); fr_t sh = shift;
         for (uint64_t s_ = 0; s_ < b; ++s_) { STARK_TRY((rows_coset_run<F>(ctx, K.t1.fr(), K.big0.fr() + s_ * nl, nrl, P.log_cols, (uint64_t)K.rank * nrl, P.log_n, sh))); sh = fr_mul<F>(sh, wN); }
         return pack3(ctx, K.big0.fr(), K.big1.fr(), b * nrl, W, ncl, 1, 0, 2); }                     // [b nrl][W][ncl] -> [W][b nrl][ncl]
@@ -487,9 +484,9 @@ int32_t stark_ntt_dev(stark_ctx_t* ctx, int32_t field_id, uint64_t* data, size_t
 int32_t stark_ntt(stark_ctx_t* ctx, int32_t field_id, uint64_t* data, size_t log_n, int32_t inverse, const uint64_t* coset4) {
     if (!ctx || !data || log_n > 30) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    size_t bytes = ((size_t)1 << log_n) * sizeof(fr_t); DevBuf d; STARK_HIP(ctx, d.upload(ctx, data, bytes));
+    size_t bytes = ((size_t)1 << log_n) * sizeof(fr_t); DevBuf d; CallerUploads up(ctx); STARK_HIP(ctx, up.up(d, data, bytes));
     STARK_TRY(stark_ntt_dev(ctx, field_id, (uint64_t*)d.p, log_n, inverse, coset4));
-    STARK_HIP(ctx, d.download_sync(data, bytes)); return STARK_OK;
+    STARK_HIP(ctx, up.download_sync(data, d.p, bytes)); return STARK_OK;
 }
 int32_t stark_lde_dev(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* out) {
     if (!ctx || !evals || !out || log_n + log_blowup > 30) return STARK_ERR_INVALID_ARG;
@@ -516,9 +513,9 @@ int32_t stark_lde_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, co
 int32_t stark_lde(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* out) {
     if (!ctx || !evals || !out || log_n + log_blowup > 30) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    size_t n = (size_t)1 << log_n, N = n << log_blowup; DevBuf di, dout; STARK_HIP(ctx, di.upload(ctx, evals, n * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, N * sizeof(fr_t)));
+    size_t n = (size_t)1 << log_n, N = n << log_blowup; DevBuf di, dout; CallerUploads up(ctx); STARK_HIP(ctx, up.up(di, evals, n * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, N * sizeof(fr_t)));
     STARK_TRY(stark_lde_dev(ctx, field_id, (const uint64_t*)di.p, log_n, log_blowup, coset4, (uint64_t*)dout.p));
-    STARK_HIP(ctx, dout.download_sync(out, N * sizeof(fr_t))); return STARK_OK;
+    STARK_HIP(ctx, up.download_sync(out, dout.p, N * sizeof(fr_t))); return STARK_OK;
 }
 
 int32_t stark_ntt_columns_dev(stark_ctx_t* ctx, int32_t field_id, uint64_t* slab, size_t log_rows, size_t ncols, size_t col0, size_t log_n, int32_t inverse) {
@@ -553,12 +550,9 @@ int32_t stark_ntt_rows_dev(stark_ctx_t* ctx, int32_t field_id, uint64_t* slab, s
     STARK_TRY(ctx_enter(ctx));
     return with_field(ctx, field_id, [&](auto f) -> int32_t {
         using F = decltype(f); DevWord sc;
-        if (scale4 || inverse) {   // into the kernels' table domain; an inverse without scale4 multiplies by one, which suppresses the plan's per-row n^-1
-            STARK_TRY(sc.set(ctx, x32<F>(scale4 ? load_fr(scale4) : fr_one<F>()))); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        STARK_TRY(ntt_run<F>(ctx, as_fr(slab), (int)log_cols, nrows, inverse != 0, nullptr, sc.dev.fr()));
-        if (sc.dev.p) STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // sc is freed on return
-        return STARK_OK;
+        // into the kernels' table domain; an inverse without scale4 multiplies by one, which suppresses the plan's per-row n^-1
+        if (scale4 || inverse) STARK_TRY(sc.set(ctx, x32<F>(scale4 ? load_fr(scale4) : fr_one<F>())));
+        return ntt_run<F>(ctx, as_fr(slab), (int)log_cols, nrows, inverse != 0, nullptr, sc.dev.fr());
     });
 }
 

@@ -94,9 +94,7 @@ static int32_t ctx_leaf_init(stark_ctx* ctx, fr_t** out) {
             const fr_t k20 = fr_from_u64<PallasFr>(1ull << FR29_SBOX_SHIFT);     // the S-box outputs x4, x5 arrive divided by 2^20 (fr_pow5_r29)
             fr29_const_from<PallasFr>(host::h_mul(c.mds[(size_t)i * 17 + 4], k20), m45 + 9 * i); fr29_const_from<PallasFr>(host::h_mul(c.mds[(size_t)i * 17 + 5], k20), m45 + 9 * (17 + i));
         }
-        DevMem d; STARK_HIP(ctx, d.alloc(sizeof(blob)));
-        STARK_HIP(ctx, hipMemcpyAsync(d.p, blob, sizeof(blob), hipMemcpyHostToDevice, ctx->stream));
-        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        DevMem d; STARK_TRY(d.fill_sync(ctx, blob, sizeof(blob)));
         ctx->leaf_init = std::move(d);
     }
     *out = ctx->leaf_init.fr(); return STARK_OK;
@@ -110,9 +108,7 @@ static int32_t tr_frame(stark_ctx* ctx, const char* tag, fr_t** dev, int* np, in
     auto it = ctx->tr_frames.find(key);
     if (it == ctx->tr_frames.end()) {
         std::vector<fr_t> fr; const int p = host::tr_hash_frame(tag, fr);
-        DevMem d; STARK_HIP(ctx, d.alloc(fr.size() * sizeof(fr_t)));
-        STARK_HIP(ctx, hipMemcpyAsync(d.p, fr.data(), fr.size() * sizeof(fr_t), hipMemcpyHostToDevice, ctx->stream));
-        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        DevMem d; STARK_TRY(d.fill_sync(ctx, fr.data(), fr.size() * sizeof(fr_t)));
         it = ctx->tr_frames.emplace(key, std::move(d)).first; ctx->tr_frame_dims[key] = {p, (int)fr.size() - p};
     }
     *dev = it->second.fr(); *np = ctx->tr_frame_dims[key].first; *ns = ctx->tr_frame_dims[key].second; return STARK_OK;
@@ -177,7 +173,8 @@ int32_t tr_hash_many_dev(stark_ctx* ctx, size_t n, const char* const* tags, cons
     return launch_tr_hash(ctx, tp, poseidon_form(ctx, tp, column_sponges ? PoseidonOp::ColumnSponges : PoseidonOp::RaggedSponges, n), T, out_dev);
 }
 int32_t tr_hash_host1(stark_ctx* ctx, const char* tag, const std::vector<fr_t>& fields, fr_t* out) {
-    DevBuf in, o; STARK_HIP(ctx, in.upload(ctx, fields.data(), fields.size() * sizeof(fr_t))); STARK_HIP(ctx, o.alloc(ctx, sizeof(fr_t)));
+    DevBuf in, o; STARK_HIP(ctx, in.alloc(ctx, fields.size() * sizeof(fr_t))); STARK_HIP(ctx, o.alloc(ctx, sizeof(fr_t)));
+    STARK_TRY(ctx_upload_staged(ctx, in.p, fields.data(), fields.size() * sizeof(fr_t)));
     STARK_TRY(tr_hash_dev(ctx, tag, in.fr(), fields.size(), 1, o.fr()));
     STARK_HIP(ctx, o.download_sync(out, sizeof(fr_t)));
     return STARK_OK;
@@ -216,17 +213,18 @@ int32_t stark_poseidon_permute_batch_dev(stark_ctx_t* ctx, stark_params_t* p, ui
 int32_t stark_poseidon_permute_batch(stark_ctx_t* ctx, stark_params_t* p, uint64_t* states, size_t n) {
     if (!ctx || !p || (!states && n)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    size_t bytes = n * p->dev.t * sizeof(fr_t); DevBuf d; STARK_HIP(ctx, d.upload(ctx, states, bytes));
+    size_t bytes = n * p->dev.t * sizeof(fr_t); DevBuf d; CallerUploads up(ctx); STARK_HIP(ctx, up.up(d, states, bytes));
     STARK_TRY(stark_poseidon_permute_batch_dev(ctx, p, (uint64_t*)d.p, n));
-    STARK_HIP(ctx, d.download_sync(states, bytes));
+    STARK_HIP(ctx, up.download_sync(states, d.p, bytes));
     return STARK_OK;
 }
 static int32_t hash_stream(stark_ctx_t* ctx, stark_params_t* p, int mode, const uint64_t* a, size_t na, const uint64_t* b, size_t nb, const fr_t& tag, size_t n, uint64_t* out) {
-    DevBuf da, db, dout; STARK_HIP(ctx, da.upload(ctx, a, n * na * sizeof(fr_t))); STARK_HIP(ctx, db.upload(ctx, b, n * nb * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n * sizeof(fr_t)));
+    DevBuf da, db, dout; CallerUploads up(ctx);
+    STARK_HIP(ctx, up.up(da, a, n * na * sizeof(fr_t))); STARK_HIP(ctx, up.up(db, b, n * nb * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n * sizeof(fr_t)));
     const int block = poseidon_block(p->dev.t);
     hipLaunchKernelGGL(k_hash_stream, dim3((unsigned)((n + block - 1) / block)), dim3(block), poseidon_lds(p->dev.t, block), ctx->stream, p->dev, mode, da.fr(), na, db.fr(), nb, tag, n, dout.fr());
     STARK_HIP(ctx, hipGetLastError());
-    STARK_HIP(ctx, dout.download_sync(out, n * sizeof(fr_t)));
+    STARK_HIP(ctx, up.download_sync(out, dout.p, n * sizeof(fr_t)));
     return STARK_OK;
 }
 int32_t stark_poseidon_hash_with_ds_dynamic(stark_ctx_t* ctx, stark_params_t* p, const uint64_t* ds, size_t nds, const uint64_t* in, size_t cnt, size_t n, uint64_t* out) {
@@ -315,9 +313,9 @@ int32_t stark_poseidon_hash_ds_batch_dev(stark_ctx_t* ctx, stark_params_t* p, si
 int32_t stark_poseidon_hash_ds_batch(stark_ctx_t* ctx, stark_params_t* p, size_t arity, uint32_t level, uint64_t pos0, uint64_t label, const uint64_t* in, size_t n_in, uint64_t* out) {
     if (!ctx || !p || !in || !out || arity == 0) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    size_t n_out = (n_in + arity - 1) / arity; DevBuf di, dout; STARK_HIP(ctx, di.upload(ctx, in, n_in * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n_out * sizeof(fr_t)));
+    size_t n_out = (n_in + arity - 1) / arity; DevBuf di, dout; CallerUploads up(ctx); STARK_HIP(ctx, up.up(di, in, n_in * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n_out * sizeof(fr_t)));
     STARK_TRY(stark_poseidon_hash_ds_batch_dev(ctx, p, arity, level, pos0, label, (const uint64_t*)di.p, n_in, (uint64_t*)dout.p));
-    STARK_HIP(ctx, dout.download_sync(out, n_out * sizeof(fr_t)));
+    STARK_HIP(ctx, up.download_sync(out, dout.p, n_out * sizeof(fr_t)));
     return STARK_OK;
 }
 }  // extern "C"
@@ -363,10 +361,10 @@ int32_t stark_leaf_pair_hash_dev(stark_ctx_t* ctx, stark_params_t* tp, const uin
 int32_t stark_leaf_pair_hash(stark_ctx_t* ctx, stark_params_t* tp, const uint64_t* f, const uint64_t* f_next, size_t n, size_t m, uint64_t* h) {
     if (!ctx || (!f && n) || (!h && n) || m == 0) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    size_t nn = f_next ? (n + m - 1) / m : 0; DevBuf df, dn, dh;
-    STARK_HIP(ctx, df.upload(ctx, f, n * sizeof(fr_t))); STARK_HIP(ctx, dn.upload(ctx, f_next, nn * sizeof(fr_t))); STARK_HIP(ctx, dh.alloc(ctx, n * sizeof(fr_t)));
+    size_t nn = f_next ? (n + m - 1) / m : 0; DevBuf df, dn, dh; CallerUploads up(ctx);
+    STARK_HIP(ctx, up.up(df, f, n * sizeof(fr_t))); STARK_HIP(ctx, up.up(dn, f_next, nn * sizeof(fr_t))); STARK_HIP(ctx, dh.alloc(ctx, n * sizeof(fr_t)));
     STARK_TRY(stark_leaf_pair_hash_dev(ctx, tp, (const uint64_t*)df.p, f_next ? (const uint64_t*)dn.p : nullptr, n, m, (uint64_t*)dh.p));
-    STARK_HIP(ctx, dh.download_sync(h, n * sizeof(fr_t))); return STARK_OK;
+    STARK_HIP(ctx, up.download_sync(h, dh.p, n * sizeof(fr_t))); return STARK_OK;
 }
 int32_t stark_tr_hash_fields_tagged_dev(stark_ctx_t* ctx, stark_params_t* tp, const char* tag, const uint64_t* fields, size_t k, size_t n, uint64_t* out) {
     if (!ctx || !tag || (!fields && k && n) || (!out && n)) return STARK_ERR_INVALID_ARG;
@@ -377,9 +375,9 @@ int32_t stark_tr_hash_fields_tagged_dev(stark_ctx_t* ctx, stark_params_t* tp, co
 int32_t stark_tr_hash_fields_tagged(stark_ctx_t* ctx, stark_params_t* tp, const char* tag, const uint64_t* fields, size_t k, size_t n, uint64_t* out) {
     if (!ctx || !tag || (!fields && k && n) || (!out && n)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    DevBuf di, dout; STARK_HIP(ctx, di.upload(ctx, fields, n * k * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n * sizeof(fr_t)));
+    DevBuf di, dout; CallerUploads up(ctx); STARK_HIP(ctx, up.up(di, fields, n * k * sizeof(fr_t))); STARK_HIP(ctx, dout.alloc(ctx, n * sizeof(fr_t)));
     STARK_TRY(stark_tr_hash_fields_tagged_dev(ctx, tp, tag, (const uint64_t*)di.p, k, n, (uint64_t*)dout.p));
-    STARK_HIP(ctx, dout.download_sync(out, n * sizeof(fr_t))); return STARK_OK;
+    STARK_HIP(ctx, up.download_sync(out, dout.p, n * sizeof(fr_t))); return STARK_OK;
 }
 int32_t stark_tr_hash_many_dev(stark_ctx_t* ctx, size_t n, const char* const* tags, const uint64_t* const* fields, const size_t* k, uint64_t* out) {
     if (!ctx) return STARK_ERR_INVALID_ARG;
@@ -439,10 +437,10 @@ int32_t stark_merkle_build(stark_ctx_t* ctx, stark_params_t* p, size_t arity, ui
     if (!ctx || !p || !leaves || !out || (pairs && !cp)) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     if (n == 0) return ctx->fail(STARK_ERR_INVALID_ARG, "no leaves");
-    DevBuf dl, dc; STARK_HIP(ctx, dl.upload(ctx, leaves, n * sizeof(fr_t)));
-    if (pairs) STARK_HIP(ctx, dc.upload(ctx, cp, n * sizeof(fr_t)));
+    DevBuf dl, dc; CallerUploads up(ctx); STARK_HIP(ctx, up.up(dl, leaves, n * sizeof(fr_t)));
+    if (pairs) STARK_HIP(ctx, up.up(dc, cp, n * sizeof(fr_t)));
     STARK_TRY(stark_merkle_build_dev(ctx, p, arity, label, (const uint64_t*)dl.p, n, pairs, pairs ? (const uint64_t*)dc.p : nullptr, 0, 0, 0, out));
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
+    STARK_HIP(ctx, up.sync()); return STARK_OK;
 }
 int32_t stark_merkle_num_levels(stark_tree_t* t) { return t ? (int32_t)t->levels.size() : STARK_ERR_INVALID_ARG; }
 size_t stark_merkle_level_len(stark_tree_t* t, int32_t lvl) { return (t && lvl >= 0 && (size_t)lvl < t->lens.size()) ? t->lens[lvl] : 0; }
@@ -474,16 +472,15 @@ namespace stark {
 // The device executor of merkle_build_batch: every step is one launch on the context's stream (a few, for more than 65535 trees in the copy), the
 // level blocks are pooled and owned by the holder the batch's trees share, and the labels and pointer tables go up as ONE staged upload.
 struct MerkleBatchDevExec {
-    stark_ctx* ctx; stark_params* p; std::shared_ptr<TreeBlocks> blocks; DevBuf tab;
-    MerkleBatchDevExec(stark_ctx* c, stark_params* p_) : ctx(c), p(p_), blocks(std::make_shared<TreeBlocks>()) {}
+    stark_ctx* ctx; stark_params* p; std::shared_ptr<TreeBlocks> blocks; DevArena mem;
+    MerkleBatchDevExec(stark_ctx* c, stark_params* p_) : ctx(c), p(p_), blocks(std::make_shared<TreeBlocks>()), mem(c) {}
     int32_t level_block(size_t n_fr, fr_t** out) {
         DevBuf b; STARK_TRY(b.take(ctx, n_fr * sizeof(fr_t))); *out = b.fr(); blocks->blocks.push_back(std::move(b)); return STARK_OK;
     }
     int32_t tables(const uint64_t* labels, const fr_t* const* leaves, const fr_t* const* cp, size_t B, const uint64_t** labels_x, const fr_t* const** leaves_x, const fr_t* const** cp_x) {
         std::vector<uint64_t> h((cp ? 3 : 2) * B);                       // [labels | leaves | cp], eight bytes each
         for (size_t b = 0; b < B; ++b) { h[b] = labels[b]; h[B + b] = (uint64_t)(uintptr_t)leaves[b]; if (cp) h[2 * B + b] = (uint64_t)(uintptr_t)cp[b]; }
-        STARK_HIP(ctx, tab.alloc(ctx, h.size() * 8)); STARK_TRY(ctx_upload_staged(ctx, tab.p, h.data(), h.size() * 8));
-        const uint64_t* d = (const uint64_t*)tab.p;
+        uint64_t* d = nullptr; STARK_TRY(mem.put(h, &d));
         *labels_x = d; *leaves_x = (const fr_t* const*)(d + B); *cp_x = cp ? (const fr_t* const*)(d + 2 * B) : nullptr; return STARK_OK;
     }
     int32_t copy_rows(const fr_t* const* src_x, size_t n, size_t B, fr_t* dst) {

@@ -110,9 +110,8 @@ struct DevTranscript {
         STARK_TRY(ctx_transcript_params(ctx, &tp));
         STARK_HIP(ctx, state.alloc(ctx, 17 * sizeof(fr_t))); STARK_HIP(ctx, posb.alloc(ctx, 4)); STARK_HIP(ctx, out.alloc(ctx, sizeof(fr_t)));
         fr_t st[17]; for (auto& x : st) x = host::h_zero(); st[16] = host::h_tag("FSv1-TRANSCRIPT-INIT");
-        STARK_HIP(ctx, hipMemcpyAsync(state.p, st, sizeof(st), hipMemcpyHostToDevice, ctx->stream));
+        STARK_TRY(ctx_upload_staged(ctx, state.p, st, sizeof(st)));
         STARK_HIP(ctx, hipMemsetAsync(posb.p, 0, 4, ctx->stream));
-        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));                                 // st is a stack temporary
         absorb_bytes(label, n); return STARK_OK;
     }
     void absorb_field(const fr_t& x) { pending.push_back(x); }
@@ -122,10 +121,10 @@ struct DevTranscript {
     }
     int32_t run(bool finish, fr_t* result) {
         DevBuf f; const size_t n = pending.size();
-        if (n) STARK_HIP(ctx, f.upload(ctx, pending.data(), n * sizeof(fr_t)));
+        if (n) { STARK_HIP(ctx, f.alloc(ctx, n * sizeof(fr_t))); STARK_TRY(ctx_upload_staged(ctx, f.p, pending.data(), n * sizeof(fr_t))); }
         STARK_TRY(tr_stream_on(ctx, tp, state.fr(), (uint32_t*)posb.p, f.fr(), n, finish, out.fr()));
         if (finish && result) STARK_HIP(ctx, hipMemcpyAsync(result, out.p, sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream));
-        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));                                 // `pending` is host memory; a challenge is needed on the host anyway
+        STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));                                 // the challenge is needed on the host
         pending.clear(); return STARK_OK;
     }
     int32_t challenge(const uint8_t* label, size_t n, fr_t* r) {                           // :92-101
@@ -140,21 +139,10 @@ static int32_t fold(stark_ctx* ctx, const fr_t* layer, size_t len, const fr_t& r
     STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
 }
 // The device executor of the batched drivers (sumcheck_batch.hpp): every operation is one launch (or a few, for more than 65535 layers) on
-// the context's stream; uploads are staged until the next download synchronises.
-struct ScDevExec {
-    stark_ctx* ctx; stark_params* cp; stark_params* tp;
-    std::vector<DevBuf> mem; std::vector<std::vector<uint8_t>> staged;
-    ScDevExec(stark_ctx* c, stark_params* commit, stark_params* tr) : ctx(c), cp(commit), tp(tr) {}
-    ~ScDevExec() { if (!staged.empty()) (void)hipStreamSynchronize(ctx->stream); }
-    int32_t alloc(size_t bytes, void** out) { mem.emplace_back(); STARK_HIP(ctx, mem.back().alloc(ctx, bytes)); *out = mem.back().p; return STARK_OK; }
-    int32_t upload(void* dst, const void* src, size_t bytes) {
-        staged.emplace_back((const uint8_t*)src, (const uint8_t*)src + bytes);
-        STARK_HIP(ctx, hipMemcpyAsync(dst, staged.back().data(), bytes, hipMemcpyHostToDevice, ctx->stream)); return STARK_OK;
-    }
-    int32_t download(void* dst, const void* src, size_t bytes) {
-        STARK_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        staged.clear(); return STARK_OK;
-    }
+// the context's stream; its memory is the arena's, the host copies of its uploads held until the round's download.
+struct ScDevExec : DevArena {
+    stark_params* cp; stark_params* tp;
+    ScDevExec(stark_ctx* c, stark_params* commit, stark_params* tr) : DevArena(c, true), cp(commit), tp(tr) {}
     int32_t ds_level(const DsBatchStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, cp, D, out); }
     int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim) {
         const uint64_t np = len / 2; const unsigned grid = (unsigned)std::min<uint64_t>((np + 255) / 256, 1024);
@@ -215,8 +203,8 @@ static int32_t run_sc_verify_batch(stark_ctx* ctx, const ScVerifyPlan& V, int32_
     DevBuf d; STARK_HIP(ctx, d.alloc(ctx, total));
     uint8_t* base = (uint8_t*)d.p; fr_t* pool = (fr_t*)(base + o_pool); int32_t* flag = (int32_t*)(base + o_flag);
     hipStream_t st = ctx->stream;
-    auto bail = [&](int32_t rc) { (void)hipStreamSynchronize(st); return rc; };      // `h` is host memory the upload may still read
-    if (hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "upload"));
+    CallerUploads up(ctx);                                                           // `h` is not copied again: every return below is fenced
+    if (up.copy(base, h.data(), h.size()) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "upload");
     if (V.n_dec) hipLaunchKernelGGL(k_sc_decode_fr, dim3((unsigned)((V.n_dec + 255) / 256)), dim3(256), 0, st, (const uint32_t*)(base + o_blob), (const uint32_t*)(base + o_doff),
                                     (const uint32_t*)(base + o_dpr), (uint32_t)V.n_dec, pool, flag);
     for (const ScVerifyPlan::Stream& S : V.tr) {
@@ -225,18 +213,17 @@ static int32_t run_sc_verify_batch(stark_ctx* ctx, const ScVerifyPlan& V, int32_
         T.out = pool + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = 1; T.finish_last = 1;
         for (size_t a0 = 0; a0 < S.n; a0 += 0x7fffffffu / 2) {                       // (a grid's x dimension)
             TrBatchStream Ta = T; Ta.inst0 = S.inst0 + a0; Ta.n_active = std::min<size_t>(S.n - a0, 0x7fffffffu / 2); Ta.el_off = T.el_off + a0 * S.nseg; Ta.out = T.out + a0 * S.nseg;
-            int32_t rc = tr_batch_on(ctx, tp, Ta, Ta.n_active); if (rc) return bail(rc);     // the form that many instances take
+            STARK_TRY(tr_batch_on(ctx, tp, Ta, Ta.n_active));                            // the form that many instances take
         }
     }
-    { int32_t rc = verify_batch_groups_on(ctx, D, (const uint64_t*)(base + o_hdr), (const uint32_t*)(base + o_off), (const uint32_t*)(base + o_idx), pool, cp); if (rc) return bail(rc); }
+    STARK_TRY(verify_batch_groups_on(ctx, D, (const uint64_t*)(base + o_hdr), (const uint32_t*)(base + o_off), (const uint32_t*)(base + o_idx), pool, cp));
     if (const size_t n = V.n_rec()) {
         const dim3 grid((unsigned)((n + 255) / 256));
         if (V.mf) hipLaunchKernelGGL(k_sc_verify_mf_check, grid, dim3(256), 0, st, (const fr_t*)pool, (const uint32_t*)(base + o_rec), (uint32_t)n, flag);
         else hipLaunchKernelGGL(k_sc_verify_plain_check, grid, dim3(256), 0, st, (const fr_t*)pool, (const uint32_t*)(base + o_rec), (uint32_t)n, flag);
     }
-    if (hipGetLastError() != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "sum-check batch verification launch"));
-    if (hipMemcpyAsync(accepted, flag, V.batch * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "download"));
-    STARK_HIP(ctx, hipStreamSynchronize(st));
+    if (hipGetLastError() != hipSuccess) return ctx->fail(STARK_ERR_HIP, "sum-check batch verification launch");
+    STARK_HIP(ctx, up.download_sync(accepted, flag, V.batch * 4));
     return STARK_OK;
 }
 // verify_plain (mf = 0) / verify_mf (mf = 1) of a batch (the single entry points: B = 1), cut into plans of at most the context's "sumcheck_verify_batch_max_slots" pool slots
@@ -380,10 +367,10 @@ int32_t stark_commitment_commit(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_
     if (!ctx || !leaves || !out) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     stark_params* cp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp));
-    DevBuf d; STARK_HIP(ctx, d.upload(ctx, leaves, n * sizeof(fr_t)));
+    DevBuf d; CallerUploads up(ctx); STARK_HIP(ctx, up.up(d, leaves, n * sizeof(fr_t)));
     std::unique_ptr<stark_tree> T;
     STARK_TRY(merkle_build_on(ctx, ctx->stream, cp, 16, ds_tag, d.fr(), n, 0, nullptr, 1, 0, 0, 0, DevBuf(), T));     // commit (:85-90); open = stark_merkle_open (:92-94)
-    STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); *out = T.release(); return STARK_OK;
+    STARK_HIP(ctx, up.sync()); *out = T.release(); return STARK_OK;
 }
 // commit of `batch` DEVICE vectors of n leaves side by side (merkle_build_batch_on): stream-ordered, no host synchronisation
 int32_t stark_commitment_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* ds_tags, const uint64_t* const* leaves, size_t n, stark_tree_t** out) {
@@ -409,10 +396,10 @@ int32_t stark_mle_evaluate(stark_ctx_t* ctx, const uint64_t* table, size_t k, co
     if (!ctx || !table || (!r && k) || !out4 || k > 40) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     const size_t n = (size_t)1 << k;
-    DevBuf a, b; STARK_HIP(ctx, a.upload(ctx, table, n * sizeof(fr_t))); STARK_HIP(ctx, b.alloc(ctx, std::max<size_t>(n / 2, 1) * sizeof(fr_t)));
+    DevBuf a, b; CallerUploads up(ctx); STARK_HIP(ctx, up.up(a, table, n * sizeof(fr_t))); STARK_HIP(ctx, b.alloc(ctx, std::max<size_t>(n / 2, 1) * sizeof(fr_t)));
     fr_t* cur = a.fr(); fr_t* nxt = b.fr(); size_t len = n;
     for (size_t j = 0; j < k; ++j) { STARK_TRY(fold(ctx, cur, len, load_fr(r + 4 * j), nxt)); std::swap(cur, nxt); len /= 2; }
-    fr_t v; STARK_HIP(ctx, hipMemcpyAsync(&v, cur, sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    fr_t v; STARK_HIP(ctx, up.download_sync(&v, cur, sizeof(fr_t)));
     store_fr(out4, v); return STARK_OK;
 }
 // Mle::evaluate (:279-295) of `batch` device-resident tables, table i at the point r[i * k ..] (host): a few launches for the whole batch
@@ -441,13 +428,13 @@ int32_t stark_sumcheck_prove_mf_dev(stark_ctx_t* ctx, const uint64_t* witness, s
 int32_t stark_sumcheck_prove_plain(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out) {
     if (!ctx || !witness || !out || k > 40) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    DevBuf d; STARK_HIP(ctx, d.upload(ctx, witness, ((size_t)1 << k) * sizeof(fr_t)));
+    DevBuf d; CallerUploads up(ctx); STARK_HIP(ctx, up.up(d, witness, ((size_t)1 << k) * sizeof(fr_t)));
     return stark_sumcheck_prove_plain_dev(ctx, (const uint64_t*)d.p, k, tree_label, out);
 }
 int32_t stark_sumcheck_prove_mf(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, size_t queries_per_round, stark_proof_t** out) {
     if (!ctx || !witness || !out || k > 40) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    DevBuf d; STARK_HIP(ctx, d.upload(ctx, witness, ((size_t)1 << k) * sizeof(fr_t)));
+    DevBuf d; CallerUploads up(ctx); STARK_HIP(ctx, up.up(d, witness, ((size_t)1 << k) * sizeof(fr_t)));
     return stark_sumcheck_prove_mf_dev(ctx, (const uint64_t*)d.p, k, tree_label, queries_per_round, out);
 }
 static int32_t prove_batch_dev(stark_ctx_t* ctx, int mf, size_t batch, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, size_t qpr, stark_proof_t** out) {

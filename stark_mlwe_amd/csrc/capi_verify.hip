@@ -59,7 +59,7 @@ int32_t stark::verify_batch_groups_on(stark_ctx* ctx, const VerifyBatchPlan& V, 
 }
 // Runs one plan (a DEEP-FRI one or a Merkle one): one upload of everything the device reads (the computed digests are not sent), the leaf step and
 // the DS groups in depth order (verify_batch_groups_on), the check kernel, one download of the decisions and one synchronisation.  Once the upload
-// is enqueued every error drains the streams before the staging vector dies.
+// is enqueued every error drains the streams before the staging vector dies (the CallerUploads guard).
 int32_t stark::run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, stark_params* fixed, int32_t* accepted) {
     if (!V.batch) return STARK_OK;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -74,13 +74,13 @@ int32_t stark::run_verify_batch(stark_ctx* ctx, const VerifyBatchPlan& V, stark_
     DevBuf d; STARK_HIP(ctx, d.alloc(ctx, total));
     uint8_t* base = (uint8_t*)d.p; fr_t* pool = (fr_t*)(base + o_pool); int32_t* acc_dev = (int32_t*)(base + o_acc);
     hipStream_t st = ctx->stream;
-    auto bail = [&](int32_t rc) { (void)hipStreamSynchronize(st); return rc; };      // h is the source of an enqueued upload (verify_batch_groups_on drains its side stream itself)
-    if (hipMemcpyAsync(base, h.data(), h.size(), hipMemcpyHostToDevice, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "verify batch: upload"));
-    { const int32_t rc = verify_batch_groups_on(ctx, V, (const uint64_t*)(base + o_hdr), (const uint32_t*)(base + o_off), (const uint32_t*)(base + o_idx), pool, fixed); if (rc) return bail(rc); }
+    CallerUploads up(ctx);                                                           // h is not copied again: every return below is fenced (verify_batch_groups_on drains its side stream itself)
+    if (up.copy(base, h.data(), h.size()) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "verify batch: upload");
+    STARK_TRY(verify_batch_groups_on(ctx, V, (const uint64_t*)(base + o_hdr), (const uint32_t*)(base + o_off), (const uint32_t*)(base + o_idx), pool, fixed));
     hipLaunchKernelGGL(k_verify_batch_check, dim3((unsigned)((V.batch + 255) / 256)), dim3(256), 0, st, (const fr_t*)pool, (const uint32_t*)(base + o_coff), (const uint32_t*)(base + o_chk),
                        (const int32_t*)(base + o_flag), V.batch, acc_dev);
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(accepted, acc_dev, V.batch * 4, hipMemcpyDeviceToHost, st) != hipSuccess) return bail(ctx->fail(STARK_ERR_HIP, "verify batch: check"));
-    STARK_HIP(ctx, hipStreamSynchronize(st));
+    if (hipGetLastError() != hipSuccess) return ctx->fail(STARK_ERR_HIP, "verify batch: check");
+    STARK_HIP(ctx, up.download_sync(accepted, acc_dev, V.batch * 4));
     return STARK_OK;
 }
 // A plan is run once it holds this many pool slots (1 GiB of field elements), so device memory stays bounded whatever the batch.

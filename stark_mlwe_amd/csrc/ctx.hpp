@@ -1,7 +1,9 @@
 // stark_mlwe_amd/csrc/ctx.hpp — internal objects behind the opaque C-ABI handles (product code).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <string>
@@ -14,6 +16,7 @@
 #include "fri_plan.hpp"
 
 namespace stark { struct NttPlan; struct PowCache; }
+struct stark_ctx;
 
 // Handles (trees, FRI states, plans, transcripts, caller-made parameter sets) keep their context alive: stark_ctx_destroy with live handles
 // only marks the context; the LAST handle freed tears it down.  `CtxRef` is the FIRST member of every handle type and members are destroyed in
@@ -39,6 +42,10 @@ struct DevMem {
     DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
     ~DevMem() { reset(); }
     hipError_t alloc(size_t bytes) { reset(); const hipError_t e = hipMalloc(&p, bytes); if (e != hipSuccess) p = nullptr; return e; }
+    // THE one-off fill of a long-lived table: alloc(bytes), the copy from host memory on the context's stream, and the synchronisation right behind it
+    // (src may die on return).  The static form copies into device memory somebody else owns.  Defined below stark_ctx.
+    int32_t fill_sync(stark_ctx* ctx, const void* src, size_t bytes);
+    static int32_t fill_sync(stark_ctx* ctx, void* dst, const void* src, size_t bytes);
     void reset() { if (p) { (void)hipFree(p); p = nullptr; } }
     explicit operator bool() const { return p != nullptr; }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -89,7 +96,7 @@ struct stark_ctx {
     std::map<ZKey, stark::fr_t> z_cache;                                // fri_sample_z_ell(seed_z, level, size)  (fri.rs:59-82)
     std::unique_ptr<stark::PowCache> omega_tabs;                       // two-level power tables of a domain generator (DomainH, deep_ali/src/lib.rs:109-125); pow_table.hpp, made on first use
     void* pinned = nullptr; size_t pinned_bytes = 0;                   // small pinned staging area for async uploads / downloads
-    // Host sources of uploads enqueued by calls that return WITHOUT synchronising (ctx_upload_staged: the pointer tables of the batched transforms).
+    // Host sources of the uploads of everything the library built on the host (ctx_upload_staged: pointer tables, transcript inputs, headers).
     // Each copy lives until the event recorded behind its upload has passed; later calls reap the finished ones, teardown the rest.
     struct StagedUpload { hipEvent_t done; std::unique_ptr<uint8_t[]> host; };
     std::vector<StagedUpload> staged;
@@ -141,8 +148,7 @@ struct DevBuf {
     void reset() { if (p) { ctx_release(ctx, p); p = nullptr; } }      // releases now; idempotent
     int32_t take(stark_ctx* c, size_t bytes) { reset(); ctx = c; return ctx_alloc(c, bytes, &p); }     // the allocator's own code and message
     hipError_t alloc(stark_ctx* c, size_t bytes) { return take(c, bytes) == STARK_OK ? hipSuccess : hipErrorOutOfMemory; }
-    // alloc, then the upload of `bytes` from host memory enqueued on the context's stream (`src` stays valid until the next synchronisation)
-    hipError_t upload(stark_ctx* c, const void* src, size_t bytes) { const hipError_t e = alloc(c, bytes); return e != hipSuccess || !bytes ? e : hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, c->stream); }
+    // (no upload member: host memory reaches a block through ctx_upload_staged or a CallerUploads guard, below)
     // the first `bytes` to host memory, then one synchronisation of the context's stream
     hipError_t download_sync(void* dst, size_t bytes) const { const hipError_t e = bytes ? hipMemcpyAsync(dst, p, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream); }
     fr_t* fr() const { return reinterpret_cast<fr_t*>(p); }
@@ -175,6 +181,11 @@ inline void hand_out(std::vector<std::unique_ptr<stark_proof>>& v, stark_proof**
 
 namespace stark {
 
+inline int32_t DevMem::fill_sync(stark_ctx* ctx, void* dst, const void* src, size_t bytes) {
+    STARK_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
+}
+inline int32_t DevMem::fill_sync(stark_ctx* ctx, const void* src, size_t bytes) { STARK_HIP(ctx, alloc(bytes)); return fill_sync(ctx, p, src, bytes); }
+
 inline const fr_t* as_fr(const uint64_t* p) { return reinterpret_cast<const fr_t*>(p); }
 inline fr_t* as_fr(uint64_t* p) { return reinterpret_cast<fr_t*>(p); }
 inline fr_t load_fr(const uint64_t* p) { fr_t x; for (int i = 0; i < 4; ++i) { x.v[2 * i] = (uint32_t)p[i]; x.v[2 * i + 1] = (uint32_t)(p[i] >> 32); } return x; }
@@ -191,9 +202,53 @@ int32_t ctx_transcript_params(stark_ctx* ctx, stark_params** out);
 int32_t ctx_merkle_params(stark_ctx* ctx, int t, stark_params** out);
 int32_t ctx_commit_params(stark_ctx* ctx, stark_params** out);      // MerkleCommitment's set (the sum-check openings)
 int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out);
-// `bytes` of host memory to device memory on the context's stream, out of a copy the context owns (stark_ctx::staged): the caller's source may die
-// on return and the host is not synchronised
+// Host memory reaches the device in three functions and nowhere else ("Uploads"): DevMem::fill_sync above and the two below.
+// THE upload of what the library itself built on the host: `bytes` of host memory to device memory on the context's stream, out of a copy the
+// context owns (stark_ctx::staged).  The source may die on return, on every path, and the host is not synchronised.
 int32_t ctx_upload_staged(stark_ctx* ctx, void* dst, const void* src, size_t bytes);
+// THE upload of memory the library does not own and will not copy a second time: the caller's arrays of the host-pointer entry points (and a large
+// staging vector of the same scope).  copy() / up() enqueue the direct copy; a scope left before the stream was synchronised behind them (an error,
+// or a success path that only enqueues) synchronises it here, so a plain-named entry point returns, with any status, only after the device has
+// finished reading the caller's arrays.  Declared AFTER the DevBufs it fills and after the host memory it reads (as StreamFork below: destroyed
+// first, the fence runs before the blocks return to the pool).  A success path ends in download_sync() or sync(): one synchronisation, none here;
+// a path whose callee synchronised on its way (a prove) just returns and pays one more on an idle stream.
+struct CallerUploads {
+    stark_ctx* ctx; bool pending = false;
+    explicit CallerUploads(stark_ctx* c) : ctx(c) {}
+    CallerUploads(const CallerUploads&) = delete; CallerUploads& operator=(const CallerUploads&) = delete;
+    ~CallerUploads() { if (pending) (void)hipStreamSynchronize(ctx->stream); }
+    hipError_t copy(void* dst, const void* src, size_t bytes) { if (!bytes) return hipSuccess; pending = true; return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream); }
+    // a pooled block of `bytes` into d, then its copy() from src
+    hipError_t up(DevBuf& d, const void* src, size_t bytes) { const hipError_t e = d.alloc(ctx, bytes); return e != hipSuccess ? e : copy(d.p, src, bytes); }
+    hipError_t sync() { const hipError_t e = hipStreamSynchronize(ctx->stream); if (e == hipSuccess) pending = false; return e; }
+    // the finish of a call: `bytes` of device memory to host memory, then the one synchronisation
+    hipError_t download_sync(void* dst, const void* src, size_t bytes) { const hipError_t e = bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream) : hipSuccess; return e != hipSuccess ? e : sync(); }
+};
+// THE memory of an executor of the templated drivers (fri_batch.hpp, sumcheck_batch.hpp, lagrange_dev.hpp, merkle_batch.hpp): pooled blocks that
+// return to the pool with it, host tables through upload / put (the source may die on return), download = copy + synchronisation.  The device
+// executors derive from it and add their launches; hostcheck.cpp's HostArena is its twin.
+// Where the host copy of an upload lives: in the context (ctx_upload_staged, an event per upload: the executors whose calls return without a
+// synchronisation), or — hold_until_download, for a driver that downloads after every few uploads (the sum-check rounds, where the event per upload
+// measured 2 - 4 %: profiles/sumcheck_batch_parent_vs_upload_discipline.jsonl) — in the arena until its next download() has synchronised; an
+// arena left with such copies outstanding synchronises first (`fence` is the last member: it runs before `held` and `blocks` go).
+struct DevArena {
+    stark_ctx* ctx; std::vector<DevBuf> blocks; const bool hold; std::vector<std::unique_ptr<uint8_t[]>> held; CallerUploads fence;
+    explicit DevArena(stark_ctx* c, bool hold_until_download = false) : ctx(c), hold(hold_until_download), fence(c) {}
+    int32_t alloc(size_t bytes, void** out) { DevBuf b; STARK_TRY(b.take(ctx, bytes)); *out = b.p; blocks.push_back(std::move(b)); return STARK_OK; }
+    int32_t upload(void* dst, const void* src, size_t bytes) {
+        if (!hold || !bytes) return ctx_upload_staged(ctx, dst, src, bytes);
+        held.emplace_back(new uint8_t[bytes]); memcpy(held.back().get(), src, bytes);
+        STARK_HIP(ctx, fence.copy(dst, held.back().get(), bytes)); return STARK_OK;
+    }
+    template <class T> int32_t put(const std::vector<T>& h, T** out) {
+        void* p = nullptr; STARK_TRY(alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p));
+        if (!h.empty()) STARK_TRY(upload(p, h.data(), h.size() * sizeof(T)));
+        *out = (T*)p; return STARK_OK;
+    }
+    int32_t download(void* dst, const void* src, size_t bytes) {
+        STARK_HIP(ctx, fence.download_sync(dst, src, bytes)); held.clear(); return STARK_OK;
+    }
+};
 int32_t ctx_side_stream(stark_ctx* ctx, hipStream_t* out);
 // Fork: what is enqueued on *side from here on runs after everything enqueued on the context's stream so far, and concurrently with what that stream
 // receives next.  Join: the context's stream continues after everything enqueued on the side stream.  Events only; the host is not synchronised.

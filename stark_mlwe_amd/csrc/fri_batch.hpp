@@ -44,9 +44,7 @@ inline fr_t fri_z_from_fused(const fr_t& fused, uint64_t seed_z, size_t level, s
 
 #define FB_TRY(e) do { int32_t rc__ = (e); if (rc__) return rc__; } while (0)
 
-// An executor X provides (pointers are its own memory: device pointers on the GPU, host pointers in the host check):
-//   int32_t alloc(size_t bytes, void** out)                     memory that lives as long as X
-//   int32_t upload(void* dst, const void* src, size_t bytes)    src may die on return (the device executor: ctx_upload_staged)
+// An executor X is an arena (alloc / upload / put: DevArena in ctx.hpp on the GPU, HostArena in hostcheck.cpp; pointers are its own memory) plus:
 //   int32_t zpows(const fr_t& z, size_t m, fr_t* zp)            zp[t] = z^t, t < m
 //   int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out)              fri_fold_layer over n elements
 //   int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h)      hash_leaf_pair(f[i], f_next[i / m]) (f_next == nullptr: zero)

@@ -71,7 +71,7 @@ static int32_t shard_header_agree(const ShardColl& C, std::vector<FriShardRank>&
     std::vector<void*> buf;
     for (auto& k : K) {
         STARK_TRY(coll_alloc(ctx, k, (size_t)C.W * bytes));
-        STARK_HIP(ctx, hipMemcpyAsync((char*)k.coll.p + (size_t)k.rank * bytes, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        STARK_TRY(ctx_upload_staged(ctx, (char*)k.coll.p + (size_t)k.rank * bytes, h.data(), bytes));
         buf.push_back(k.coll.p);
     }
     STARK_TRY(C.all_gather(buf, bytes));

@@ -34,6 +34,18 @@ static void st4(uint64_t* p, const fr_t& x) { for (int i = 0; i < 4; ++i) p[i] =
 static int g_alloc_fill = 0;
 static std::vector<uint64_t> hc_block(size_t bytes) { std::vector<uint64_t> v((bytes + 7) / 8 + 1); memset(v.data(), g_alloc_fill, v.size() * sizeof(uint64_t)); return v; }
 static std::vector<fr_t> hc_fr_block(size_t n) { std::vector<fr_t> v(n); if (n) memset((void*)v.data(), g_alloc_fill, n * sizeof(fr_t)); return v; }
+// THE memory of the host executors, the twin of DevArena (ctx.hpp): blocks of hc_block that live as long as it, upload and download = memcpy.
+struct HostArena {
+    std::vector<std::vector<uint64_t>> mem;
+    int32_t alloc(size_t bytes, void** out) { mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
+    int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
+    template <class T> int32_t put(const std::vector<T>& h, T** out) {
+        void* p = nullptr; alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p);
+        if (!h.empty()) upload(p, h.data(), h.size() * sizeof(T));
+        *out = (T*)p; return 0;
+    }
+    int32_t download(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
+};
 
 struct HcParams { host::PoseidonConsts ref; host::KernelConsts kc; PoseidonDev dev; };
 static void bind(HcParams* P) {
@@ -584,11 +596,9 @@ int hc_merkle_verify(void* tparams, int pairs, size_t cfg_arity, uint64_t label,
 }  // extern "C"
 
 // ---- the batched sum-check provers (sumcheck_batch.hpp) through the host instantiation of the kernel bodies -------------------------
-struct ScHostExec {
-    HcParams* cp; HcParams* tp; std::vector<std::vector<uint64_t>> mem;
-    int32_t alloc(size_t bytes, void** out) { mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
-    int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
-    int32_t download(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
+struct ScHostExec : HostArena {
+    HcParams* cp; HcParams* tp;
+    ScHostExec(HcParams* c, HcParams* t) : cp(c), tp(t) {}
     int32_t ds_level(const DsBatchStream& D, fr_t* out) {
         std::vector<fr_t> st(cp->dev.t);
         for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, cp->dev, D, k); }
@@ -643,7 +653,7 @@ size_t hc_sumcheck_prove_batch(void* tparams, void* cparams, int mf, size_t B, c
     const size_t n = (size_t)1 << k;
     std::vector<std::vector<fr_t>> w(B, std::vector<fr_t>(n)); std::vector<const fr_t*> wp(B);
     for (size_t b = 0; b < B; ++b) { for (size_t i = 0; i < n; ++i) w[b][i] = ld4(witnesses[b] + 4 * i); wp[b] = w[b].data(); }
-    ScHostExec X{(HcParams*)cparams, (HcParams*)tparams, {}};
+    ScHostExec X((HcParams*)cparams, (HcParams*)tparams);
     ScBatch<ScHostExec> S(X, B, wp.data(), k, labels);
     std::vector<std::vector<uint8_t>> pr;
     if (mf ? S.prove_mf(q, pr) : S.prove_plain(pr)) return 0;
@@ -718,12 +728,10 @@ size_t hc_sumcheck_verify_batch_steps(int mf, size_t batch, const uint8_t* const
 }  // extern "C"
 
 // ---- the batched commit phase (fri_batch.hpp) through the host instantiation of the stream bodies ----------------------------------
-struct FriHostExec {
-    HcParams* tp; std::vector<std::vector<uint64_t>> mem;
+struct FriHostExec : HostArena {
+    HcParams* tp;
     HcParamCache& mp;
     explicit FriHostExec(HcParams* t) : tp(t), mp(hc_param_cache()) {}
-    int32_t alloc(size_t bytes, void** out) { mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
-    int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
     int32_t zpows(const fr_t& z, size_t m, fr_t* zp) { fr_t acc = fr_one<PF>(); for (size_t t = 0; t < m; ++t) { zp[t] = acc; acc = fr_mul<PF>(acc, z); } return 0; }
     int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out) {                                   // fri_fold_layer (fri.rs:85-102)
         for (size_t b = 0; b < n / m; ++b) { fr_t acc = fr_zero<PF>(); for (size_t t = 0; t < m; ++t) acc = fr_add<PF>(acc, fr_mul<PF>(f[b * m + t], zp[t])); out[b] = acc; }
@@ -850,14 +858,8 @@ extern "C" int hc_mle_default_log_tile() { return kMleDefaultLogTile; }
 // ---- stark_lagrange_eval_on_h_batch_dev (lagrange_dev.hpp): the driver itself, every workgroup of k_lagrange_partials run in lockstep on the host ------
 // The lane geometry, the weights, the lane dot product and the sums are the kernels' own inline pieces; a shuffle scan is a product over the wave's
 // other lanes, LDS a plain array.  Blocks come from the executors' allocation path (hc_set_alloc_fill), as the device driver's come from the pool.
-struct LagHostExec {
-    std::vector<std::vector<uint64_t>> mem; std::vector<fr_t> lo, hi;
-    int32_t alloc(size_t bytes, void** out) { mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
-    template <class T> int32_t put(const std::vector<T>& h, T** out) {
-        void* p = nullptr; alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p);
-        if (!h.empty()) memcpy(p, h.data(), h.size() * sizeof(T));
-        *out = (T*)p; return 0;
-    }
+struct LagHostExec : HostArena {
+    std::vector<fr_t> lo, hi;
     int32_t pow_table(const fr_t& omega, size_t n, LagPow* out) {
         int bits, lo_bits, hi_bits; lag_pow_split(n, &bits, &lo_bits, &hi_bits);
         lo.assign((size_t)1 << lo_bits, fr_one<PF>()); hi.assign((size_t)1 << hi_bits, fr_one<PF>());
@@ -992,14 +994,16 @@ unsigned hc_lagrange_col_groups(int opt, size_t ncols, size_t n_local, size_t pa
 }  // extern "C"
 
 // ---- many Merkle trees in one pass (merkle_batch.hpp) through the host instantiation of the stream bodies -----------------------------------------
-struct MerkleHostExec {
-    HcParams* p; std::vector<std::vector<uint64_t>> mem; std::vector<uint64_t> labels; std::vector<const fr_t*> lv, cpv;
+struct MerkleHostExec : HostArena {
+    HcParams* p;
+    explicit MerkleHostExec(HcParams* p_) : p(p_) {}
     int32_t level_block(size_t n_fr, fr_t** out) {                                   // a block that held something before: the fill of hc_set_alloc_fill, and never zeros
         mem.emplace_back(4 * n_fr + 1, g_alloc_fill ? 0x0101010101010101ull * (uint64_t)g_alloc_fill : 0xA5A5A5A5A5A5A5A5ull); *out = (fr_t*)mem.back().data(); return 0;
     }
     int32_t tables(const uint64_t* l, const fr_t* const* leaves, const fr_t* const* cp, size_t B, const uint64_t** lx, const fr_t* const** vx, const fr_t* const** cx) {
-        labels.assign(l, l + B); lv.assign(leaves, leaves + B); if (cp) cpv.assign(cp, cp + B);
-        *lx = labels.data(); *vx = lv.data(); *cx = cp ? cpv.data() : nullptr; return 0;
+        uint64_t* dl = nullptr; const fr_t** dv = nullptr; const fr_t** dc = nullptr;
+        put(std::vector<uint64_t>(l, l + B), &dl); put(std::vector<const fr_t*>(leaves, leaves + B), &dv); if (cp) put(std::vector<const fr_t*>(cp, cp + B), &dc);
+        *lx = dl; *vx = dv; *cx = dc; return 0;
     }
     int32_t copy_rows(const fr_t* const* src, size_t n, size_t B, fr_t* dst) { for (size_t b = 0; b < B; ++b) for (size_t i = 0; i < n; ++i) dst[b * n + i] = src[b][i]; return 0; }
     template <class DS> int32_t ds(const DS& D, fr_t* out) {
@@ -1026,7 +1030,7 @@ int hc_merkle_build_batch(void* params, size_t arity, size_t B, const uint64_t* 
         lp[b] = col[b].data();
         if (pairs && cp[b]) { cc[b].resize(n); for (size_t i = 0; i < n; ++i) cc[b][i] = ld4(cp[b] + 4 * i); cpp[b] = cc[b].data(); }
     }
-    MerkleHostExec X{P, {}, {}, {}, {}}; std::vector<size_t> lens; std::vector<fr_t*> base;
+    MerkleHostExec X(P); std::vector<size_t> lens; std::vector<fr_t*> base;
     if (merkle_build_batch(X, arity, B, labels, lp.data(), n, pairs, pairs ? cpp.data() : nullptr, lens, base)) return -1;
     const std::vector<size_t> at = total_lens(lens, B);
     if (lens.size() > 64 || at.back() > cap_fr) return -1;

@@ -184,7 +184,7 @@ FR_HD fr_t lag_sum4(const fr_t (&w)[4]) { return fr_add<PallasFr>(fr_add<PallasF
 // it and zero if not.  For the executor's memory (device: capi_fri.hip; host: hostcheck.cpp); cols[c] = the block's n_local rows.  The arguments
 // have passed lag_check_domain and the null / overlap checks; ncols, npoints >= 1.  passes (may be null) = the partial passes taken.
 // col_groups: the option "lagrange_col_groups" (lag_col_groups).
-// An executor provides  alloc(bytes, void**)  put(vector<T>, T**)  pow_table(omega, n, LagPow*)  gather(...)  partials(...)  finish(...)  combine(...).
+// An executor is an arena (alloc, put: DevArena in ctx.hpp, HostArena in hostcheck.cpp) plus  pow_table(omega, n, LagPow*)  gather(...)  partials(...)  finish(...)  combine(...).
 template <class Exec>
 int32_t lagrange_eval_batch(Exec& X, size_t ncols, const fr_t* const* cols, const LagBlock& B, const fr_t& omega, size_t npoints, const fr_t* z, size_t max_partials,
                             int col_groups, fr_t* out, size_t* passes) {

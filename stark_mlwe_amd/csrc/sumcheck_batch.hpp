@@ -87,9 +87,8 @@ struct ScSeg {                                                          // the a
 
 #define SC_TRY(e) do { int32_t rc__ = (e); if (rc__) return rc__; } while (0)
 
-// An executor X provides (pointers are its own memory: device pointers on the GPU, host pointers in the host check):
-//   int32_t alloc(size_t bytes, void** out)            memory that lives as long as X
-//   int32_t upload(void* dst, const void* src, size_t bytes)   / download(void* dst, const void* src, size_t bytes) (synchronous)
+// An executor X is an arena (alloc / upload / put / download: DevArena in ctx.hpp on the GPU, HostArena in hostcheck.cpp; pointers are its own
+// memory) plus:
 //   int32_t ds_level(const DsBatchStream& D, fr_t* out)        one Merkle level of all trees (MerkleCommitment's parameters)
 //   int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim)
 //           c01[2b], c01[2b+1] = (c0, c1) of layer b (ptrs[b] or layers + b len); claim != nullptr: claim[b] = 2 c0 + c1
@@ -103,11 +102,7 @@ template <class X> struct ScBatch {
     ScBatch(X& x_, size_t B_, const fr_t* const* w, size_t k_, const uint64_t* l) : x(x_), B(B_), k(k_), n((size_t)1 << k_), wit(w), labels(l) {
         init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT");
     }
-    template <class T> int32_t put(const std::vector<T>& h, T** out) {
-        void* p = nullptr; SC_TRY(x.alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p));
-        if (!h.empty()) SC_TRY(x.upload(p, h.data(), h.size() * sizeof(T)));
-        *out = (T*)p; return 0;
-    }
+    template <class T> int32_t put(const std::vector<T>& h, T** out) { return x.put(h, out); }
     int32_t alloc_fr(size_t n_fr, fr_t** out) { void* p = nullptr; SC_TRY(x.alloc(std::max<size_t>(n_fr, 1) * sizeof(fr_t), &p)); *out = (fr_t*)p; return 0; }
     int32_t setup() {
         std::vector<const fr_t*> w(wit, wit + B); std::vector<uint64_t> l(labels, labels + B);
