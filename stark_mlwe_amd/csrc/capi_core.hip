@@ -113,18 +113,18 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
     const size_t o_frag = blob.size(), frag_elems = (k.mds_frag.size() + sizeof(fr_t) - 1) / sizeof(fr_t);
     if (!k.mds_frag.empty()) { blob.resize(o_frag + 2 * frag_elems); memcpy((void*)(blob.data() + o_frag), k.mds_frag.data(), k.mds_frag.size()); memcpy((void*)(blob.data() + o_frag + frag_elems), k.mds_pre_frag.data(), k.mds_pre_frag.size()); }
     // The 8-round partial blocks (t = 17, rp % 8 == 0, M[0][0] != 0), the SCALED family (host_util.hpp blk8s_*): int8 MFMA fragments of the E-product, of the lane
-    // product followed by the shared unit fragment, of the Gamma terms; then the scaled round constants with the unscale multiplier right behind them (PoseidonDev::blk8_unscale29).  The unscaled family stays on the
+    // product followed by the shared unit fragment, of the Gamma terms; then the scaled round constants as nine limbs each (rc_partial_scaled29) with the unscale multiplier right behind them (PoseidonDev::blk8_unscale29).  The unscaled family stays on the
     // host.  Owned and freed with the set.
     const size_t o_b8 = blob.size(), ef_elems = (k.blk8s_efrag.size() + sizeof(fr_t) - 1) / sizeof(fr_t), lf_bytes = k.blk8s_lfrag.size() + 1024, lf_elems = (lf_bytes + sizeof(fr_t) - 1) / sizeof(fr_t),
-                 gf_elems = (k.blk8s_gfrag.size() + sizeof(fr_t) - 1) / sizeof(fr_t), rcs_elems = k.rc_partial_scaled.size(), un_elems = (k.blk8_unscale29.size() * 4 + sizeof(fr_t) - 1) / sizeof(fr_t);
+                 gf_elems = (k.blk8s_gfrag.size() + sizeof(fr_t) - 1) / sizeof(fr_t), rcs_words = k.rc_partial_scaled29.size(), un_elems = ((rcs_words + k.blk8_unscale29.size()) * 4 + sizeof(fr_t) - 1) / sizeof(fr_t);      // the constants' limbs and the unscale multiplier, contiguous words
     const bool have_b8 = !k.blk8s_efrag.empty();
-    if (have_b8) { blob.resize(o_b8 + ef_elems + lf_elems + gf_elems + rcs_elems + un_elems);
+    if (have_b8) { blob.resize(o_b8 + ef_elems + lf_elems + gf_elems + un_elems);
                    int8_t* const b8 = (int8_t*)(blob.data() + o_b8);
                    memcpy(b8, k.blk8s_efrag.data(), k.blk8s_efrag.size());
                    memcpy(b8 + ef_elems * sizeof(fr_t), k.blk8s_lfrag.data(), k.blk8s_lfrag.size()); memcpy(b8 + ef_elems * sizeof(fr_t) + k.blk8s_lfrag.size(), k.blk8_lfrag.data() + k.blk8_lfrag.size() - 1024, 1024);
                    memcpy(b8 + (ef_elems + lf_elems) * sizeof(fr_t), k.blk8s_gfrag.data(), k.blk8s_gfrag.size());
-                   memcpy(b8 + (ef_elems + lf_elems + gf_elems) * sizeof(fr_t), k.rc_partial_scaled.data(), rcs_elems * sizeof(fr_t));
-                   memcpy(b8 + (ef_elems + lf_elems + gf_elems + rcs_elems) * sizeof(fr_t), k.blk8_unscale29.data(), k.blk8_unscale29.size() * 4); }
+                   memcpy(b8 + (ef_elems + lf_elems + gf_elems) * sizeof(fr_t), k.rc_partial_scaled29.data(), rcs_words * 4);
+                   memcpy(b8 + (ef_elems + lf_elems + gf_elems) * sizeof(fr_t) + rcs_words * 4, k.blk8_unscale29.data(), k.blk8_unscale29.size() * 4); }
     STARK_TRY(P->blob.fill_sync(ctx, blob.data(), blob.size() * sizeof(fr_t)));
     fr_t* const dev = P->blob.fr();
     P->dev.t = k.t; P->dev.rf = k.rf; P->dev.rp = k.rp;
@@ -140,7 +140,7 @@ static int32_t params_finish(stark_ctx* ctx, stark_params* P) {
     P->dev.blk8_efrag = have_b8 ? (const void*)(dev + o_b8) : nullptr; P->dev.blk8_lfrag = have_b8 ? (const void*)(dev + o_b8 + ef_elems) : nullptr;
     P->dev.blk8_gfrag = have_b8 ? (const void*)(dev + o_b8 + ef_elems + lf_elems) : nullptr;
     P->dev.blk8_unit_frag = have_b8 ? (const void*)((const int8_t*)P->dev.blk8_lfrag + k.blk8s_lfrag.size()) : nullptr;
-    P->dev.rc_partial_scaled = have_b8 ? dev + o_b8 + ef_elems + lf_elems + gf_elems : nullptr;
+    P->dev.rc_partial_scaled29 = have_b8 ? reinterpret_cast<const uint32_t*>(dev + o_b8 + ef_elems + lf_elems + gf_elems) : nullptr;
     P->dev.mds_frag = k.mds_frag.empty() ? nullptr : (const void*)(dev + o_frag); P->dev.mds_pre_frag = k.mds_frag.empty() ? nullptr : (const void*)(dev + o_frag + frag_elems);
     return STARK_OK;
 }

@@ -244,7 +244,7 @@ int32_t stark_poseidon_hash_with_ds(stark_ctx_t* ctx, stark_params_t* p, const u
 // without its tables on the device is an error, never a quiet return to blocks of 4.
 static int32_t pair_block8_form(stark_ctx* ctx, const stark_params* p, bool* on) {
     *on = ctx->opt.poseidon_block8 && p->dev.t == 17 && p->dev.rp % 8 == 0;
-    if (*on && (!p->dev.blk8_efrag || !p->dev.blk8_lfrag || !p->dev.blk8_unit_frag || !p->dev.blk8_gfrag || !p->dev.rc_partial_scaled)) return ctx->fail(STARK_ERR_UNSUPPORTED, "poseidon_block8: the parameter set has no block-8 tables");
+    if (*on && (!p->dev.blk8_efrag || !p->dev.blk8_lfrag || !p->dev.blk8_unit_frag || !p->dev.blk8_gfrag || !p->dev.rc_partial_scaled29)) return ctx->fail(STARK_ERR_UNSUPPORTED, "poseidon_block8: the parameter set has no block-8 tables");
     return STARK_OK;
 }
 // One launch of hash_with_ds_dynamic over the hashes of a DS stream (hash_ds_on), in the form poseidon_form picks for a Merkle level of that many nodes.

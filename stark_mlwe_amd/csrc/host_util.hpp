@@ -248,6 +248,8 @@ struct KernelConsts {
     //   blk8s_lfrag        [rp/8][16][8] fragment of w_{p,j} / (kappa lambda_p^5): its inputs are the yt_p.  No unit fragment of its own: blk8_lfrag's serves both
     //   blk8s_gfrag        [rp/8][28]    fragment of Gamma_{q,p} lambda_{q+1} / (kappa lambda_p^5)
     //   rc_partial_scaled  [rp]          lambda_q c_q, stored form
+    //   rc_partial_scaled29 [rp + 1][9]  the same as nine 29-bit limbs of the stored value (fr29_unpack, like rc_full29: an addend), entry rp zero: the initial
+    //                                    columns of the finish of the row that round q consumes (mfma_digits.hpp); after the last round no constant follows
     //   blk8_unscale29     [9]           1 / lambda_rp as a multiplier-table entry (fr29_const_from, no 2^20: it meets the chain value, not an S-box output):
     //                                    one product per permutation brings X_rp back
     // The fragments are still signed radix-256 digits of residues in [0, r): the digit-sum bounds of the unscaled family hold unchanged.
@@ -255,7 +257,7 @@ struct KernelConsts {
     // set is not ok at all.
     std::vector<fr_t> blk8_lambda, rc_partial_scaled;
     std::vector<int8_t> blk8s_efrag, blk8s_lfrag, blk8s_gfrag;
-    std::vector<uint32_t> blk8_unscale29;
+    std::vector<uint32_t> blk8_unscale29, rc_partial_scaled29;
     bool ok = false;
 };
 // scaled(i) == true: the entry multiplies an S-box output, which fr_pow5_r29 delivers as x^5 / 2^20 (fr29.hpp)
@@ -381,6 +383,8 @@ inline KernelConsts make_kernel_consts(const PoseidonConsts& c) {
             k.blk8_lambda[q + 1] = h_mul(l5k, a_inv); yinv[q] = fr_inv<PF>(l5k);
             k.rc_partial_scaled[q] = h_mul(k.blk8_lambda[q], c.rc_partial[q]);
         }
+        k.rc_partial_scaled29.assign((size_t)(c.rp + 1) * 9, 0u);
+        for (int q = 0; q < c.rp; ++q) { const fr29_t u = fr29_unpack(k.rc_partial_scaled[q]); for (int j = 0; j < 9; ++j) k.rc_partial_scaled29[(size_t)9 * q + j] = u.l[j]; }
         k.blk8_unscale29.resize(9); fr29_const_from<PF>(fr_inv<PF>(k.blk8_lambda[c.rp]), k.blk8_unscale29.data());
         for (int b = 0; b < nb; ++b) {
             for (int q = 0; q < 8; ++q) for (int j = 1; j < t; ++j) {

@@ -53,7 +53,7 @@ static void bind(HcParams* P) {
     P->dev.t = P->kc.t; P->dev.rf = P->kc.rf; P->dev.rp = P->kc.rp; P->dev.rc_full = P->kc.rc_full.data(); P->dev.rc_partial = P->kc.rc_partial.data();
     P->dev.lu = P->kc.lu.data(); P->dev.lu_pre = P->kc.lu_pre.data(); P->dev.row0 = P->kc.row0.data(); P->dev.sparse = P->kc.sparse.data(); P->dev.mds = P->kc.mds.data(); P->dev.mds_pre = P->kc.mds_pre.data(); P->dev.gamma = P->kc.gamma.data();
     P->dev.lu29 = P->kc.lu29.data(); P->dev.lu_pre29 = P->kc.lu_pre29.data(); P->dev.row0_29 = P->kc.row0_29.data(); P->dev.sparse29 = P->kc.sparse29.data(); P->dev.gamma29 = P->kc.gamma29.data(); P->dev.mds29 = P->kc.mds29.data(); P->dev.mds_pre29 = P->kc.mds_pre29.data(); P->dev.rc_full29 = P->kc.rc_full29.data();
-    P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr; P->dev.blk8_efrag = nullptr; P->dev.blk8_lfrag = nullptr; P->dev.blk8_unit_frag = nullptr; P->dev.blk8_gfrag = nullptr; P->dev.rc_partial_scaled = nullptr;
+    P->dev.mds_frag = nullptr; P->dev.mds_pre_frag = nullptr; P->dev.blk8_efrag = nullptr; P->dev.blk8_lfrag = nullptr; P->dev.blk8_unit_frag = nullptr; P->dev.blk8_gfrag = nullptr; P->dev.rc_partial_scaled29 = nullptr;
     P->dev.chain_a = P->kc.chain_a.empty() ? nullptr : P->kc.chain_a.data(); P->dev.chain_g = P->kc.chain_g.empty() ? nullptr : P->kc.chain_g.data(); P->dev.chain_w = P->kc.chain_w.empty() ? nullptr : P->kc.chain_w.data();
 }
 
@@ -285,9 +285,11 @@ int32_t hc_blk8_row23_max(int reset) { return reset ? g_blk8_row23_max.exchange(
 // partial rounds and at the end finish canonical, the first round's S-box stands alone, the last block's lane rows feed the S-box of the round after the partial rounds the same way (element 0 from
 // the chain value) —, the partial rounds in
 // blocks of 8 — lanes recoded, row q = H_q = E_q + sum Gamma y_p as ONE tile of 16 + q K-steps (E fragments against the lanes, blk8_gfrag against the
-// recoded yt_0..yt_{q-1}), the SCALED chain (s0 = lambda_q X_q; yt_q = fr_pow5_r29(s0 + lambda_q c_q); s0 <- yt_q + H_q, no a_q y_q product; one product by
+// recoded yt_0..yt_{q-1}), the SCALED chain as a LAZY residue (u = lambda_q X_q + lambda_q c_q as nine limbs; x5 = pow5_lazy29(u), yt_q recoded unreduced; u <- x5 + the finish limbs of
+// H_q + lambda_{q+1} c_{q+1} through the mailbox slot's layout; no field element inside a block, no a_q y_q product; one product by
 // 1 / lambda_rp after the last block), lane rows with the unit fragment as the ninth K-step — with blk8s_efrag / blk8s_gfrag / blk8s_lfrag, rc_partial_scaled and
-// blk8_unscale29 as uploaded.  -1: the set has no block-8 tables; -2: a digit sum out of range.
+// blk8_unscale29 as uploaded; between two blocks the lanes are the digits of their signed residue (mfma_finish_recoded), the fused rows' S-box outputs are recoded
+// unreduced.  -1: the set has no block-8 tables; -2: a digit sum out of range; -4: a chain limb outside pow5_lazy29's contract.
 int hc_permute_block8(void* h, uint64_t* states, size_t n) {
     HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc; const int t = k.t, half = k.rf / 2;
     if (t != 17 || k.blk8s_efrag.empty() || k.blk8s_gfrag.empty() || k.blk8_unscale29.empty() || k.mds_frag.empty()) return -1;
@@ -301,7 +303,7 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
             const int8_t* fr[17]; for (int e = 0; e < t; ++e) fr[e] = &F[((size_t)i * t + e) * 1024];
             int32_t S[32]; const int rc = blk8_tile_sums(fr, xd.data(), t, S); if (rc) return rc;
             if (next < 0) o[i] = blk8_finish_sums(S);
-            else { uint32_t l[9]; blk8_finish_sums_limbs(S, l); o[i] = recode_signed(sbox_lazy29(l, &k.rc_full29[((size_t)next * t + i) * 9])); }
+            else { uint32_t l[9]; blk8_finish_sums_limbs(S, l); o[i] = sbox_lazy29_recoded(l, &k.rc_full29[((size_t)next * t + i) * 9]); }
         }
         if (next < 0) st = o; else xd = o;
         return 0; };
@@ -309,7 +311,8 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
         for (int j = 0; j < t; ++j) st[j] = ld4(states + 4 * (s * t + j));
         sbox(0);
         for (int r = 0; r < half; ++r) { const int rc = product(r == half - 1 ? k.mds_pre_frag : k.mds_frag, r == half - 1 ? -1 : r + 1); if (rc) return rc; }
-        fr_t s0 = st[0], rec[17], y[8], yd[9], kx[23];
+        fr_t rec[17], yd[9], kx[23];
+        fr29_t u = lazy29_add_c29(fr29_unpack(st[0]).l, &k.rc_partial_scaled29[0]);              // the chain as a lazy residue: lambda_0 X_0 + lambda_0 c_0
         for (int j = 1; j < t; ++j) rec[j] = recode_signed(st[j]);
         const int nb = k.rp / 8;
         for (int b = 0; b < nb; ++b) {
@@ -322,26 +325,86 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
                 int32_t S[32]; { const int rc = blk8_tile_sums(fr, kx, 16 + q, S); if (rc) return rc; }
                 if (q == 7) { int32_t m = 0; for (int c = 0; c < 32; ++c) m = std::max(m, S[c] < 0 ? -S[c] : S[c]);
                               int32_t seen = g_blk8_row23_max.load(); while (m > seen && !g_blk8_row23_max.compare_exchange_weak(seen, m)) {} }
-                const fr_t H = blk8_finish_sums(S);
-                y[q] = fr_pow5_r29<PF>(fr_add<PF>(s0, k.rc_partial_scaled[8 * b + q]));     // s0 = lambda_q X_q: yt_q
-                yd[q] = recode_signed(y[q]);
-                s0 = fr_add<PF>(y[q], H);
+                // Y: the row's finish with the next round's scaled constant in its columns (zero after the last round), posted as the slot's words
+                int64_t col[9]; uint32_t l[9]; mfma_cols_of_sums(S, col, &k.rc_partial_scaled29[(size_t)9 * (8 * b + q + 1)]); mfma_finish_limbs(col, l);
+                const fr_t slot = lazy29_to_slot(l);
+                // X: the S-box on the lazy value, yt_q recoded unreduced, the slot's limbs added to x5's
+                const fr29_t x5 = pow5_lazy29(u);
+                yd[q] = recode_lazy29(x5);
+                u = lazy29_add_slot(x5, slot);
+                for (int i = 0; i < 9; ++i) if (u.l[i] >= (1u << 30)) return -4;             // pow5_lazy29's contract
             }
             for (int j = 1; j < t; ++j) {
                 const int8_t* fr[9]; for (int p2 = 0; p2 < 8; ++p2) fr[p2] = lf + ((size_t)(j - 1) * 8 + p2) * 1024; fr[8] = unit;
                 yd[8] = rec[j];
                 if (b == nb - 1) {          // the last block: the lane goes from its finish limbs through the next full round's S-box, like a fused product row
                     int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; }
-                    uint32_t l[9]; blk8_finish_sums_limbs(S, l); xd[j] = recode_signed(sbox_lazy29(l, &k.rc_full29[((size_t)half * t + j) * 9]));
-                } else { fr_t z; { const int rc = blk8_tile(fr, yd, 9, z); if (rc) return rc; } rec[j] = recode_signed(z); }
+                    uint32_t l[9]; blk8_finish_sums_limbs(S, l); xd[j] = sbox_lazy29_recoded(l, &k.rc_full29[((size_t)half * t + j) * 9]);
+                } else { int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; } int64_t col[9]; mfma_cols_of_sums(S, col); rec[j] = mfma_finish_recoded(col); }      // the signed residue's digits
             }
         }
-        s0 = fr_mul_c29(k.blk8_unscale29.data(), s0);                                              // lambda_rp X_rp -> X_rp, once per permutation
-        xd[0] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(s0, k.rc_full[(size_t)half * t])));      // element 0 of that S-box from the chain's final value
+        const fr29_t x0 = fr29_mul_c29(k.blk8_unscale29.data(), u);                                // lambda_rp X_rp (lazy) -> X_rp (below 1.04 r), once per permutation
+        xd[0] = sbox_lazy29_recoded(x0.l, &k.rc_full29[((size_t)half * t) * 9]);            // element 0 of that S-box from the chain's final value
         for (int r = half; r < k.rf; ++r) { const int rc = product(k.mds_frag, r == k.rf - 1 ? -1 : r + 1); if (rc) return rc; }
         for (int j = 0; j < t; ++j) st4(states + 4 * (s * t + j), st[j]);
     }
     return 0;
+}
+// ---- the lazy chain of the 8-round blocks, piece by piece (mfma_digits.hpp) ----
+// The finish with a constant in its columns: n cases of 32 digit sums and nine limbs c (below 2^29, top below 2^23) -> the nine limbs of
+// W' == sum_c S_c 256^c + c (mod r) and the eight words of its mailbox slot.  -1: a sum or a limb outside the domain.
+int hc_mfma_finish_limbs_c(const int32_t* sums, const uint32_t* c, size_t n, uint32_t* limbs, uint32_t* slots) {
+    for (size_t s = 0; s < n; ++s) {
+        const int32_t* S = sums + 32 * s; const uint32_t* cs = c + 9 * s;
+        for (int i = 0; i < 32; ++i) if (S[i] >= (1 << 24) || S[i] <= -(1 << 24)) return -1;
+        for (int i = 0; i < 9; ++i) if (cs[i] >= (i < 8 ? 1u << 29 : 1u << 23)) return -1;
+        int64_t col[9]; mfma_cols_of_sums(S, col, cs);
+        mfma_finish_limbs(col, limbs + 9 * s);
+        const fr_t z = lazy29_to_slot(limbs + 9 * s);
+        memcpy(slots + 8 * s, z.v, 32);
+    }
+    return 0;
+}
+// X's side: n cases of x5 (nine limbs) and a slot (eight words) -> u = lazy29_add_slot(x5, slot), nine limbs
+void hc_lazy29_add_slot(const uint32_t* x5, const uint32_t* slots, size_t n, uint32_t* u) {
+    for (size_t s = 0; s < n; ++s) { fr29_t a; fr_t z; memcpy(a.l, x5 + 9 * s, 36); memcpy(z.v, slots + 8 * s, 32); const fr29_t r = lazy29_add_slot(a, z); memcpy(u + 9 * s, r.l, 36); }
+}
+// recode_lazy29: n cases of nine limbs (value below 2^255 - 2^248, so that the top byte stays below 0x7f) -> 32 signed digits each
+void hc_recode_lazy29(const uint32_t* x5, size_t n, int8_t* digits) {
+    for (size_t s = 0; s < n; ++s) { fr29_t a; memcpy(a.l, x5 + 9 * s, 36); const fr_t d = recode_lazy29(a); memcpy(digits + 32 * s, d.v, 32); }
+}
+// The census of the chain's S-box: n cases of u (nine limbs below 2^30) -> x2, x4, x5 of pow5_lazy29 (27 limbs per case), the largest 128-bit column of the
+// same steps (two u64 per case: low, high) and the top byte of the packed x5.  -1: a limb outside the contract; -2: the 64-bit and the 128-bit columns disagree.
+int hc_chain_census(const uint32_t* u, size_t n, uint32_t* x245, uint64_t* colmax, uint8_t* topbyte) {
+    static const uint32_t zero9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t s = 0; s < n; ++s) {
+        fr29_t a; memcpy(a.l, u + 9 * s, 36);
+        for (int i = 0; i < 9; ++i) if (a.l[i] >= (1u << 30)) return -1;
+        Lazy29Wide wide; const fr29_t x5w = wide.pow5(a.l, zero9);
+        const fr29_t x5 = pow5_lazy29(a);
+        colmax[2 * s] = (uint64_t)wide.max_col; colmax[2 * s + 1] = (uint64_t)(wide.max_col >> 64);
+        if ((wide.max_col >> 64) == 0 && memcmp(x5.l, x5w.l, 36) != 0) return -2;
+        memcpy(x245 + 27 * s, wide.x2.l, 36); memcpy(x245 + 27 * s + 9, wide.x4.l, 36); memcpy(x245 + 27 * s + 18, x5w.l, 36);
+        topbyte[s] = (uint8_t)(fr29_pack(x5w.l).v[7] >> 24);
+    }
+    return 0;
+}
+// The floor-quotient finish of the lanes between two blocks: n cases of 32 digit sums -> the nine limbs of W = V - floor(V / 2^254) r (the top limb a signed
+// word) and the 32 signed digits recode_signed returns on its sign-extended pack.  -1: a sum outside the domain.
+int hc_mfma_finish_recoded(const int32_t* sums, size_t n, uint32_t* limbs, int8_t* digits) {
+    for (size_t s = 0; s < n; ++s) {
+        const int32_t* S = sums + 32 * s;
+        for (int i = 0; i < 32; ++i) if (S[i] >= (1 << 24) || S[i] <= -(1 << 24)) return -1;
+        int64_t col[9]; mfma_cols_of_sums(S, col); mfma_finish_limbs_floor(col, limbs + 9 * s);
+        mfma_cols_of_sums(S, col); const fr_t d = mfma_finish_recoded(col); memcpy(digits + 32 * s, d.v, 32);
+    }
+    return 0;
+}
+// the scaled constants as the finishes take them (KernelConsts::rc_partial_scaled29: rp + 1 entries of nine limbs, the last zero); returns the length in words
+size_t hc_rc_partial_scaled29_table(void* h, uint32_t* out, size_t cap) {
+    const std::vector<uint32_t>& v = ((HcParams*)h)->kc.rc_partial_scaled29;
+    if (out && !v.empty()) memcpy(out, v.data(), std::min(cap, v.size()) * 4);
+    return v.size();
 }
 // the block-8 tables of a set: which = 0 blk8_efrag, 1 blk8_lfrag (its last 1 KiB: the unit fragment), 2 gamma8_29 (bytes of the uint32 words), 3 blk8_gfrag;
 // the scaled family: 4 blk8s_efrag, 5 blk8s_lfrag (no unit fragment), 6 blk8s_gfrag, 7 rc_partial_scaled (rp stored field elements), 8 blk8_lambda (rp + 1 stored

@@ -1,8 +1,9 @@
 // stark_mlwe_amd/csrc/mfma_digits.hpp — the scalar pieces of the int8-MFMA field products, ONE definition for device and host: the signed recoding of an
-// operand, the fold of a row's 32 digit sums, the product-free finish (to nine limbs, or canonical) and the S-box that takes a row over in limb form.
+// operand, the fold of a row's 32 digit sums, the product-free finish (to nine limbs, canonical, or the signed residue's digits), the S-box that takes a row over
+// in limb form and the lazy chain of the 8-round blocks (slot layout, limb adds, unreduced recode).
 // poseidon_pair.hpp includes it for the t = 17 wave-pair kernels (exchange and tile handling stay there); hostcheck.cpp and tools/mfma_finish_check.cpp
 // run the same statements on the CPU against the L*U rows and against big integers (tests/test_hostcheck.py,
-// tests/test_full_round_residue_tables_host.py, tests/test_limb_handover_host.py).  The host-only part at the end: the row-order entry of the fold
+// tests/test_full_round_residue_tables_host.py, tests/test_limb_handover_host.py, tests/test_lazy_residue_host.py).  The host-only part at the end: the row-order entry of the fold
 // (mfma_cols_of_sums) and the 128-bit column census of the S-box (Lazy29Wide).
 #pragma once
 #include "fr.hpp"
@@ -81,7 +82,11 @@ FR_HD fr_t mfma_finish_cols(int64_t* col) {
 //   x2^2    limbs below 2^29: the bounds of fr29.hpp; x4 < 1.01 r.
 //   u * x4  nine products below 2^30 * 2^29 per column: 9 * 2^59 + 6 * 2^58 < 2^63; x5 < (4 * 1.01 / 128 + 1) r < 1.04 r: fr29_pack_reduce's ONE conditional
 //           subtraction returns the canonical x^5 / 2^20 of fr_pow5_r29.
-FR_HD fr_t sbox_lazy29(const uint32_t* l, const uint32_t* __restrict__ c_) {
+FR_HD fr29_t pow5_lazy29(const fr29_t& u) {                  // the three products alone: x5 as nine limbs, below 1.04 r, limbs below 2^29, the top limb below 2^23
+    const fr29_t x2 = fr29_sqr_mont<PF>(u), x4 = fr29_sqr_mont<PF>(x2);
+    return fr29_mul_mont<PF>(u, x4);
+}
+FR_HD fr29_t lazy29_add_c29(const uint32_t* l, const uint32_t* __restrict__ c_) {      // l + c limb by limb
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef const __attribute__((address_space(4))) uint32_t* cptr_t;      // wave-uniform constants on the scalar data path, as in fr_wide29_mac
     cptr_t c = (cptr_t)c_;
@@ -91,17 +96,88 @@ FR_HD fr_t sbox_lazy29(const uint32_t* l, const uint32_t* __restrict__ c_) {
     fr29_t u;
 #pragma unroll
     for (int i = 0; i < 9; ++i) u.l[i] = l[i] + c[i];
-    const fr29_t x2 = fr29_sqr_mont<PF>(u), x4 = fr29_sqr_mont<PF>(x2), x5 = fr29_mul_mont<PF>(u, x4);
-    return fr29_pack_reduce<PF>(x5.l);
+    return u;
 }
+FR_HD fr_t sbox_lazy29(const uint32_t* l, const uint32_t* __restrict__ c) { return fr29_pack_reduce<PF>(pow5_lazy29(lazy29_add_c29(l, c)).l); }
+// ---- the chain of the 8-round blocks as LAZY RESIDUES (poseidon_pair.hpp blk8_round_x / blk8_round_y): no canonical value between two S-boxes ----
+// Row q's finish takes the scaled constant of the round that consumes the row INTO the nine columns (c = nine 29-bit limbs of the stored
+// lambda_{q+1} c_{q+1}, KernelConsts::rc_partial_scaled29; limbs below 2^29, c < r), so the constant is off the chain.  It is added to the folded columns in
+// front of the carry pass (from a temporary filled by mfma_cols_set), which is the same sum as columns that start from c.  The register allocator decides the
+// form: with c as the columns' initial value, and also with the nine adds written straight from the scalars, k_hash_ds2<17, DsBatchStream, true> held 256 VGPRs
+// with 2 spilled (12 B of scratch); in this form — mfma_post_cols keeping its start-from-a-constant branch, unused — it holds 252 and spills none.
+//   column      |col| < 2^61.01 + 2^29, with the carry still < 2^62; top = floor((V + c) / 2^232), |top| < 2^40.01 + 1;
+//   q1          floor((V + c) / 2^254) - 1, |q1| < 2^18.02 + 1;
+//   W'          V + c - q1 r = ((V + c) mod 2^254) + 2^254 - q1 t: the range of W above, (2^254 - 2^144.02, 2^255 + 2^144.02), below 2.0001 r and below 2^256,
+//               limbs 0..7 below 2^29, the top limb below 2^24.
+// mfma_finish_limbs is the finish as it stands: only the columns it starts from differ.
+// The mailbox slot (32 bytes) holds W' as its nine limbs: limb k in bits 0..28 of word k, bits 3k..3k+2 of the top limb (24 bits = 8 x 3) in bits 29..31 of
+// word k.  Two instructions per word on either side (bit-field extract + shift-or; and + shift-or), against a pack (8 words of two or three shift-ors) and an
+// unpack (nine limbs of two shifts, an or and a mask) for the packed 256-bit form: the cheaper of the two layouts.
+FR_HD void mfma_cols_set(int64_t* col, const uint32_t* __restrict__ c_) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) uint32_t* cptr_t;
+    cptr_t c = (cptr_t)c_;
+#else
+    const uint32_t* c = c_;
+#endif
+#pragma unroll
+    for (int k = 0; k < 9; ++k) col[k] = (int64_t)c[k];
+}
+FR_HD fr_t lazy29_to_slot(const uint32_t* l) {               // limbs 0..7 below 2^29, the top limb below 2^24
+    fr_t z;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) z.v[k] = l[k] | (((l[8] >> (3 * k)) & 7u) << 29);
+    return z;
+}
+// X's side of the hand-over: u = x5 + W' limb by limb.  x5 < 1.04 r (limbs below 2^29, top below 2^23) and W' < 2.0001 r: u < 3.05 r with limbs below 2^30,
+// inside pow5_lazy29's contract (below 4 r, limbs below 2^30); then x2 < (3.05^2 / 128 + 1) r < 1.08 r, x4 < 1.01 r, x5 < (3.05 * 1.01 / 128 + 1) r < 1.03 r.
+FR_HD fr29_t lazy29_add_slot(const fr29_t& x5, const fr_t& slot) {
+    fr29_t u; uint32_t top = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { u.l[k] = x5.l[k] + (slot.v[k] & FR_M29); top |= (slot.v[k] >> 29) << (3 * k); }
+    u.l[8] = x5.l[8] + top;
+    return u;
+}
+// An S-box output as a B operand WITHOUT the conditional subtraction: x5 < 1.04 r < 1.04 (2^254 + 2^126), so byte 31 of the packed integer is at most
+// floor(1.04 * 64) = 66 = 0x42; recode_signed adds 0x80 and a carry to it: at most 0xc3, no carry out of the top byte, so the 32 digits in [-128, 127] sum
+// (weighted) to the integer x5 itself, which is congruent to the canonical value.  The digit-sum bounds of the products depend on the digit range alone.
+FR_HD fr_t recode_lazy29(const fr29_t& x5) { return recode_signed(fr29_pack(x5.l)); }
+// the fused rows' S-box with the output recoded unreduced: what a slot holds when the next product reads it as a B operand
+FR_HD fr_t sbox_lazy29_recoded(const uint32_t* l, const uint32_t* __restrict__ c) { return recode_lazy29(pow5_lazy29(lazy29_add_c29(l, c))); }
+// ---- the lanes between two 8-round blocks from the SIGNED residue (poseidon_pair.hpp blk8_lane_rows): a B operand needs signed bytes of SOME integer
+// congruent to the lane, not the canonical one.  The finish with the FLOOR quotient:
+//   q           floor(V / 2^254) = top >> 22, |q| < 2^18.02 + 1;
+//   W           V - q r = (V mod 2^254) - q t in (-2^144.02, 2^254 + 2^144.02): limbs 0..7 in [0, 2^29), the top limb in [-1, 2^22] as a signed word.
+// fr29_pack takes bits 232..255 from the low 24 bits of the top limb, so the eight words are W's two's complement (sign-extended), and recode_signed on it
+// returns W's digits: with K = 0x8080...80 it forms t = (W + K) mod 2^256 and digits t_b - 128, whose weighted sum is t - K; W + K lies in [0, 2^256) for
+// -K <= W < 2^256 - K (K > 2^255, and W's top byte is at most 0x40), so t = W + K without wrap-around for either sign and the digits sum to W exactly.
+FR_HD void mfma_finish_limbs_floor(int64_t* col, uint32_t* l) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { col[k + 1] += col[k] >> 29; l[k] = (uint32_t)col[k] & FR_M29; }
+    const int64_t top = col[8];
+    const int32_t q = (int32_t)(top >> 22);
+    l[8] = (uint32_t)top & ((1u << 22) - 1);
+    int64_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { const int64_t d = (int64_t)l[i] - (int64_t)q * (int64_t)fr_p29<PF>(i) + carry; l[i] = (uint32_t)d & FR_M29; carry = d >> 29; }
+    int32_t c32 = (int32_t)carry;                            // |carry| < 2^19 from here on
+#pragma unroll
+    for (int i = 5; i < 9; ++i) { const int32_t d = (int32_t)l[i] + c32; if (i < 8) { l[i] = (uint32_t)d & FR_M29; c32 = d >> 29; } else l[8] = (uint32_t)d; }
+}
+FR_HD fr_t mfma_finish_recoded(int64_t* col) { uint32_t l[9]; mfma_finish_limbs_floor(col, l); return recode_signed(fr29_pack(l)); }
+// c * u for a multiplier-table entry c (nine limbs of c R' mod r, fr29_const_from) and a lazy u (limbs below 2^30, below 4 r): a column holds nine products
+// below 2^59 and the reduction's 6 * 2^58: below 2^63; the result is below (4 / 128 + 1) r < 1.04 r with limbs below 2^29.
+FR_HD fr29_t fr29_mul_c29(const uint32_t* __restrict__ c, const fr29_t& u) { fr_wide29 w; fr_wide29_zero(w); fr_wide29_mac(w, c, u); fr29_t r; fr_wide29_mont<PF>(w, r.l); return r; }
 #if !defined(__HIP_DEVICE_COMPILE__)
 // 32 digit sums in ROW order (S[c] = digit position c) -> the nine columns, as a lane of the kernels forms them: the D layout's register order of the
 // rows a sponge's two lanes hold after the exchange (lo / hi above), zeroed columns, fold.
-inline void mfma_cols_of_sums(const int32_t* S, int64_t* col) {
+// c29 != nullptr: a constant's nine limbs are added to the folded columns, as blk8_round_y does.
+inline void mfma_cols_of_sums(const int32_t* S, int64_t* col, const uint32_t* c29 = nullptr) {
     int32_t lo[16], hi[16];
     for (int reg = 0; reg < 16; ++reg) { const int row = (reg & 3) + 8 * (reg >> 2); lo[reg] = S[row]; hi[reg] = S[row + 4]; }
     for (int k = 0; k < 9; ++k) col[k] = 0;
     mfma_fold_rows(col, lo, hi);
+    if (c29) { int64_t cc[9]; mfma_cols_set(cc, c29); for (int k = 0; k < 9; ++k) col[k] += cc[k]; }
 }
 // sbox_lazy29's three steps with 128-bit columns, statement by statement after fr29_sqr_mont / fr29_mul_mont / fr_wide29_mont, recording the largest value any
 // column holds when it is consumed (a column only grows until then): what the 64-bit columns of the kernels have to hold.  Returns x5's limbs.
@@ -130,8 +206,9 @@ struct Lazy29Wide {
     }
     fr29_t pow5(const uint32_t* l, const uint32_t* c) {
         fr29_t u; for (int i = 0; i < 9; ++i) u.l[i] = l[i] + c[i];
-        const fr29_t x2 = sqr(u), x4 = sqr(x2); return mul(u, x4);
+        x2 = sqr(u); x4 = sqr(x2); return mul(u, x4);
     }
+    fr29_t x2, x4;                                            // the intermediates of the last pow5, for the census of their sizes
 };
 #endif
 

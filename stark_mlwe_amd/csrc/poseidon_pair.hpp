@@ -125,15 +125,20 @@ __device__ __forceinline__ void mfma_zero_tile(mfma_v16i (&acc)[2]) {
         for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
 }
 // exchange and fold: the two accumulator tiles of a row -> the nine columns of the lane's sponge
-__device__ __forceinline__ void mfma_post_cols(const mfma_v16i (&acc)[2], int64_t* col) {
+// c29 != nullptr: the columns start from that constant's nine limbs.  No caller passes one (blk8_round_y adds its constant after the fold); the branch stays
+// because without it k_hash_ds2<17, DsBatchStream, true> spills 2 VGPRs (mfma_digits.hpp).
+__device__ __forceinline__ void mfma_post_cols(const mfma_v16i (&acc)[2], int64_t* col, const uint32_t* c29 = nullptr) {
     mfma_v16i lo, hi;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
         lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
     }
+    if (c29) mfma_cols_set(col, c29);
+    else {
 #pragma unroll
-    for (int k = 0; k < 9; ++k) col[k] = 0;
+        for (int k = 0; k < 9; ++k) col[k] = 0;
+    }
     mfma_fold_rows(col, lo, hi);
 }
 // exchange, fold, finish: -> the canonical field element of the lane's sponge
@@ -146,8 +151,8 @@ __device__ __forceinline__ fr_t mfma_post(const mfma_v16i (&acc)[2]) {
 // for element j, nine limbs) and into slot j as the next product's operand (recoded; canonical, not recoded, in front of the squeeze round).  No canonical value
 // in between.  The finish itself stays at the two call sites: taken in here as well, k_node16_pair<true> holds one VGPR more than before the merge (245).
 __device__ __forceinline__ void pair_sto_sbox29(const PairState& s, int j, const uint32_t* l, const uint32_t* rc29, bool recode) {
-    const fr_t y = sbox_lazy29(l, rc29);
-    s.sto(j, recode ? recode_signed(y) : y);
+    const fr29_t x5 = pow5_lazy29(lazy29_add_c29(l, rc29));
+    s.sto(j, recode ? recode_lazy29(x5) : fr29_pack_reduce<PF>(x5.l));      // recoded from the unreduced x5 (below 1.04 r); canonical for the squeeze round's dot product
 }
 // The product.  Precondition: every state slot holds a recoded S-box output and a barrier has passed.  rc29 == nullptr: ends with the state canonical and
 // consistent.  Otherwise rc29 = the NEXT full round's constants (17 x 9 limbs) and every row is handed to that round's S-box in the wave that formed it
@@ -200,9 +205,12 @@ __device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const voi
 // Every lambda sits on a constant left factor: E fragments u_{q,j} lambda_{q+1}, Gamma fragments Gamma_{q,p} lambda_{q+1} / (kappa lambda_p^5), lane fragments
 // w_{p,j} / (kappa lambda_p^5) (the posted yt_p stand for the y_p), constants lambda_q c_q; the unit fragment and the lanes are unscaled.  After the last block ONE
 // product by 1 / lambda_rp brings X_rp back (fr_mul_c29).  Exact field arithmetic: the same bits.  The fragments are still digits of residues in [0, r): the digit-sum
-// bounds above stand.  Both addends of the chain's fr_add are canonical (fr_pow5_r29 and mfma_post end canonical).
+// bounds above stand.
+// The chain is a LAZY RESIDUE inside a block (mfma_digits.hpp, with the bounds): Y finishes row q to its nine limbs with lambda_{q+1} c_{q+1} as the columns'
+// addend and posts the limbs in the 32-byte slot; X adds them limb-wise to x5's limbs and squares the sum as it stands; y_q is posted recoded from the
+// packed, unreduced x5.  No conditional subtraction, pack-and-unpack or constant add is left on the chain; canonical values exist only outside the blocks.
 // Schedule of a block (two barriers fewer than two blocks of 4, nothing on the chain waits for a lone row):
-//   X  runs nothing but the chain, the same in every round: the scaled constant, the S-box, recode and post, and after the barrier one fr_add with H_q;
+//   X  runs nothing but the chain, the same in every round: the S-box's three products, recode and post, and after the barrier nine limb adds with H_q's slot;
 //   Y  computes H_q INSIDE round q — B operands read from the lanes' slots as the MFMAs consume them (one row per round: 32 KB of LDS reads per about
 //      10 k cycles), then the q steps of the y; the fragments of row q + 1 (16 of E, q + 1 of Gamma) are fetched under the fold — and posts it; one barrier per round;
 //   both then form their share of the lane product (X lanes 1..NLX, Y the rest), the next row's fragments in flight under the current row's fold.
@@ -217,7 +225,7 @@ struct Blk8Tabs {
     const mfma_v4i* lfrag;     // [16][8][64]   lane j = 1..16, S-box output p
     const mfma_v4i* unit;      // [64]          the constant 1
     const mfma_v4i* gfrag;     // [28][64]      Gamma_{q,p} at q (q - 1) / 2 + p
-    const fr_t* rc;            // [8]           lambda_q c_q (rc_partial_scaled)
+    const uint32_t* rc29;      // [9][9]        lambda_q c_q of rounds 1..8 (the next block's round 0; zero after the last block) as nine limbs (rc_partial_scaled29)
 };
 struct Blk8Cfg {
     // X's share of the lane rows.  Measured, k SIMD-cycles per 8 rounds in two processes: 6 -> 107.7 / 107.0, 7 -> 105.8 / 106.1, 8 -> 105.1 / 104.2, 9 -> 106.4 / 107.0,
@@ -236,14 +244,15 @@ __device__ __forceinline__ mfma_v4i blk8_b_of_slot(const PairState& s, int j, in
     const uint4 u = s.st[(2 * j + (s.lane >> 5)) * 64 + 32 * ct + (s.lane & 31)];
     return mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
 }
-// round Q in wave X: s0 = lambda_Q X_Q on entry, lambda_{Q+1} X_{Q+1} on exit.  b[Q]: yt_Q as B operands on exit
+// round Q in wave X: u = lambda_Q X_Q + lambda_Q c_Q on entry, the same of round Q + 1 on exit, as a LAZY residue (nine limbs below 2^30, below 3.05 r:
+// mfma_digits.hpp); no field element is formed.  b[Q]: yt_Q as B operands on exit
 template <int Q>
-__device__ __forceinline__ void blk8_round_x(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, mfma_v4i (&b)[8][2]) {
+__device__ __forceinline__ void blk8_round_x(const PairState& s, const Blk8Tabs& Tb, fr29_t& u, mfma_v4i (&b)[8][2]) {
     __builtin_amdgcn_sched_barrier(0);                     // keep the rounds apart: less register pressure
-    const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));   // yt_Q: canonical
-    s.sto(Blk8Cfg::ymail(Q), recode_signed(y));            // off the chain: nothing of X_{Q+1} reads it
-    __syncthreads();                                       // barrier_Q: H_Q is posted (canonical: mfma_post)
-    s0 = fr_add<PF>(y, s.ld(Blk8Cfg::hmail(Q)));
+    const fr29_t x5 = pow5_lazy29(u);                      // yt_Q below 1.04 r
+    s.sto(Blk8Cfg::ymail(Q), recode_lazy29(x5));           // off the chain: nothing of X_{Q+1} reads it
+    __syncthreads();                                       // barrier_Q: H_Q + lambda_{Q+1} c_{Q+1} is posted as its nine finish limbs
+    u = lazy29_add_slot(x5, s.ld(Blk8Cfg::hmail(Q)));
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
 // round Q in wave Y.  a, g: the fragments of E row Q and of Gamma row Q on entry, of row Q + 1 on exit; b[Q]: y_Q as B operands on exit
@@ -268,14 +277,16 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
 #pragma unroll
         for (int p = 0; p <= Q; ++p) g[p] = (Tb.gfrag + (size_t)((Q + 1) * Q / 2 + p) * 64)[lane];
     }
-    s.sto(Blk8Cfg::hmail(Q), mfma_post(acc));
+    { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); { int64_t cc[9]; mfma_cols_set(cc, c29(Tb.rc29, Q)); _Pragma("unroll") for (int k = 0; k < 9; ++k) col[k] += cc[k]; } mfma_finish_limbs(col, l); s.sto(Blk8Cfg::hmail(Q), lazy29_to_slot(l)); }
     __syncthreads();                                       // barrier_Q: y_Q is posted
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
 // the lane product: s_j <- s_j + sum_p w_{p,j} y_p for this wave's share of the lanes (X lanes 1..NLX, Y the rest), b: y_0..y_7 as B operands.  Ends with a barrier.
 // rc29_next != nullptr (FUSE, the permutation's last block): the constants of the full round that follows, 17 x 9 limbs; lane j then goes from its nine finish
 // limbs through that round's S-box (sbox_lazy29) and is stored as the round's operand (recoded unless that round is the squeeze round), like a fused product row.
-template <int NLX>
+// LAZY (the FUSE kernels): between two blocks a lane is stored as the digits of its SIGNED residue (mfma_finish_recoded: floor quotient, sign-extended pack, no
+// conditional subtraction).  k_hash_ds2 keeps canonical lanes: with the signed form k_hash_ds2<17, DsBatchStream, true> spilled 6 VGPRs (28 B of scratch).
+template <int NLX, bool LAZY = false>
 __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], bool last, const uint32_t* rc29_next = nullptr, bool recode_next = true) {
     static_assert(NLX >= 1 && NLX <= 15, "shares");
     const int lane = s.lane;
@@ -299,21 +310,22 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
         // slot j is read by this wave alone, before this write
         if (rc29_next) { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); mfma_finish_limbs(col, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
-        else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }
+        else if (LAZY && !last) { int64_t col[9]; mfma_post_cols(acc, col); s.sto(j, mfma_finish_recoded(col)); }
+        else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }      // between two blocks: the signed residue's digits, no canonical value
     }
     __syncthreads();
 }
-// One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; s0 = X_0 in wave X.  Ends with a barrier, the lanes recoded again,
+// One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; u = lambda_0 X_0 + lambda_0 c_0 of the block's first round as nine limbs in wave X.  Ends with a barrier, the lanes recoded again (LAZY: as digits of their signed residue),
 // or canonical after the permutation's last block.
 // With rc29_next (FUSE, last block): every slot ends as the next full round's S-box output instead — the lanes through blk8_lane_rows, element 0 from the chain's
-// final value, brought back from lambda_rp X_rp by one product with unscale29 = 1 / lambda_rp first (rc_next: the same round's constants as field elements).
-template <int NLX>
-__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last, const uint32_t* rc29_next = nullptr, const fr_t* rc_next = nullptr, bool recode_next = true,
+// final value (lazy, no constant in it), brought back from lambda_rp X_rp by one product with unscale29 = 1 / lambda_rp first and handed to the S-box as limbs.
+template <int NLX, bool LAZY = false>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr29_t& u, bool last, const uint32_t* rc29_next = nullptr, bool recode_next = true,
                                             const uint32_t* unscale29 = nullptr) {
     mfma_v4i b[8][2];
     if (!s.isY) {
-        blk8_round_x<0>(s, Tb, s0, b); blk8_round_x<1>(s, Tb, s0, b); blk8_round_x<2>(s, Tb, s0, b); blk8_round_x<3>(s, Tb, s0, b);
-        blk8_round_x<4>(s, Tb, s0, b); blk8_round_x<5>(s, Tb, s0, b); blk8_round_x<6>(s, Tb, s0, b); blk8_round_x<7>(s, Tb, s0, b);
+        blk8_round_x<0>(s, Tb, u, b); blk8_round_x<1>(s, Tb, u, b); blk8_round_x<2>(s, Tb, u, b); blk8_round_x<3>(s, Tb, u, b);
+        blk8_round_x<4>(s, Tb, u, b); blk8_round_x<5>(s, Tb, u, b); blk8_round_x<6>(s, Tb, u, b); blk8_round_x<7>(s, Tb, u, b);
     } else {
         mfma_v4i a[16], g[7];
         blk8_load_frags16(a, Tb.efrag, s.lane);
@@ -322,8 +334,8 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
     }
     __builtin_amdgcn_sched_barrier(0);
     // slot 0 was H's mailbox in the even rounds, last read by X after barrier_6; the lane rows' closing barrier publishes the store
-    if (rc29_next && !s.isY) { s0 = fr_mul_c29(unscale29, s0); const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, rc_next[0])); s.sto(0, recode_next ? recode_signed(y) : y); }
-    blk8_lane_rows<NLX>(s, Tb, b, last, rc29_next, recode_next);
+    if (rc29_next && !s.isY) { const fr29_t x = fr29_mul_c29(unscale29, u); pair_sto_sbox29(s, 0, x.l, c29(rc29_next, 0), recode_next); }
+    blk8_lane_rows<NLX, LAZY>(s, Tb, b, last, rc29_next, recode_next);
 }
 
 // s_j += w_{0,j} x0 + w_{1,j} x1 + w_{2,j} x2 + w_{3,j} x3   (one reduction)
@@ -368,6 +380,9 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
     fr_t s0 = fr_zero<PF>();
     if (!s.isY) s0 = s.ld(0);
     if constexpr (BLK8) {
+        // the chain as nine limbs from here to the unscale product; the first constant (lambda_0 = 1) enters here, every later one in Y's finish
+        fr29_t u = fr29_unpack(s0);
+        if (!s.isY) u = lazy29_add_c29(u.l, c29(P.rc_partial_scaled29, 0));      // canonical + canonical: below 2 r, limbs below 2^30
         for (int j = s.isY ? 9 : 1; j <= (s.isY ? 16 : 8); ++j) s.sto(j, recode_signed(s.ld(j)));        // canonical since the full round's finish
         __syncthreads();
         const int nb = P.rp / 8;
@@ -375,12 +390,12 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
         for (int b = 0; b < nb; ++b) {
             const Blk8Tabs Tb{reinterpret_cast<const mfma_v4i*>(P.blk8_efrag) + (size_t)b * 8 * 16 * 64, reinterpret_cast<const mfma_v4i*>(P.blk8_lfrag) + (size_t)b * 16 * 8 * 64,
                               reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), reinterpret_cast<const mfma_v4i*>(P.blk8_gfrag) + (size_t)b * 28 * 64,
-                              P.rc_partial_scaled + 8 * b};
-            if constexpr (FUSE) pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1, b == nb - 1 ? c29(P.rc_full29, (size_t)half * T) : nullptr, P.rc_full + half * T, !(only0 && half == P.rf - 1), P.blk8_unscale29());
-            else pair_block8<Blk8Cfg::NLX>(s, Tb, s0, b == nb - 1);
+                              c29(P.rc_partial_scaled29, (size_t)8 * b + 1)};
+            if constexpr (FUSE) pair_block8<Blk8Cfg::NLX, true>(s, Tb, u, b == nb - 1, b == nb - 1 ? c29(P.rc_full29, (size_t)half * T) : nullptr, !(only0 && half == P.rf - 1), P.blk8_unscale29());
+            else pair_block8<Blk8Cfg::NLX>(s, Tb, u, b == nb - 1);
         }
-        // FUSE: the chain value was unscaled inside the last block, in front of element 0's S-box
-        if constexpr (!FUSE) { if (!s.isY) s0 = fr_mul_c29(P.blk8_unscale29(), s0); }
+        // FUSE: the chain value was unscaled inside the last block, in front of element 0's S-box; otherwise the state's element 0 ends canonical here
+        if constexpr (!FUSE) { if (!s.isY) s0 = fr29_pack_reduce<PF>(fr29_mul_c29(P.blk8_unscale29(), u).l); }
     } else
     for (int b = 0; b < P.rp / 4; ++b) {
         const uint32_t* sp = c29(P.sparse29, (size_t)(4 * b) * W);

@@ -20,12 +20,13 @@ struct PoseidonDev {           // device pointers to kernel-form constants (see 
     // t = 17: the partial rounds unrolled over all rp rounds for the five-wave latency kernel (host_util.hpp chain_*, poseidon_chain.hpp); nullptr otherwise
     const uint32_t* chain_a; const uint32_t* chain_g; const uint32_t* chain_w;
     // t = 17, rp % 8 == 0: the 8-round partial blocks of the wave-pair kernels (host_util.hpp blk8_*, poseidon_pair.hpp pair_block8); nullptr otherwise
-    // The device holds the SCALED family (KernelConsts blk8s_*: the chain carries lambda_q X_q), the unit fragment and rc_partial_scaled: the rp scaled round
-    // constants lambda_q c_q, and right behind them the nine limbs of the multiplier 1 / lambda_rp that brings the chain value back after the last block
+    // The device holds the SCALED family (KernelConsts blk8s_*: the chain carries lambda_q X_q), the unit fragment and rc_partial_scaled29: the rp scaled round
+    // constants lambda_q c_q as nine 29-bit limbs of their stored value and a zero entry for "no round follows" (they enter the finish of the row their round
+    // consumes), and right behind them the nine limbs of the multiplier 1 / lambda_rp that brings the chain value back after the last block
     // (blk8_unscale29 below: one pointer for both, the wave-pair kernels have no scalar register to spare).  The unscaled family stays on the host.
     const void* blk8_efrag; const void* blk8_lfrag; const void* blk8_unit_frag; const void* blk8_gfrag;
-    const fr_t* rc_partial_scaled;
-    FR_HD const uint32_t* blk8_unscale29() const { return reinterpret_cast<const uint32_t*>(rc_partial_scaled + rp); }
+    const uint32_t* rc_partial_scaled29;       // (rp + 1) * 9, then blk8_unscale29
+    FR_HD const uint32_t* blk8_unscale29() const { return rc_partial_scaled29 + (size_t)(rp + 1) * 9; }
     // the full rounds' constants again as nine 29-bit limbs of their STORED value (fr29_unpack; not the R' domain of the multiplier tables), 9 words per entry:
     // added limb by limb to a product row that stays in limbs up to its S-box (poseidon_pair.hpp sbox_lazy29)
     const uint32_t* rc_full29;

@@ -1,7 +1,8 @@
 // tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds, of
 // the lane product of the 8-round partial blocks with the base lane in the tile (finish with base), and of the blocks' H rows of up to 16 + 7 K-steps:
 // the fragment tables (host_util.hpp mfma_frags), the fold + finishing step and the limb-form hand-over to the next S-box (mfma_digits.hpp, the
-// statements the kernels compile: finish to limbs, S-box on lazy limbs), against the portable field code.  Meant for a
+// statements the kernels compile: finish to limbs, S-box on lazy limbs, the lazy chain's finish with a constant, slot and chain step, the signed-residue lanes),
+// against the portable field code.  Meant for a
 // sanitizer build; tools/mfma_finish_sanitize.sh builds it with AddressSanitizer + UBSan and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I stark_mlwe_amd/csrc tools/mfma_finish_check.cpp -o tools/bin/mfma_finish_check
 #include <cstdio>
@@ -158,6 +159,51 @@ int main() {
         uint32_t l[9], c[9]; for (int i = 0; i < 8; ++i) l[i] = c[i] = FR_M29; l[8] = l8; c[8] = c8;
         Lazy29Wide wide; const fr29_t x5 = wide.pow5(l, c);
         ++n; if ((wide.max_col >> 64) != 0 || !fr_eq(sbox_lazy29(l, c), fr29_pack_reduce<PF>(x5.l))) { if (bad < 5) fprintf(stderr, "S-box on lazy limbs: column overflow at l8 %u c8 %u\n", l8, c8); ++bad; }
+    }
+    // ---- the lazy chain of the 8-round blocks (poseidon_pair.hpp blk8_round_x / blk8_round_y).  (i) the finish with a constant in the columns (0, 1, r - 1
+    // and a scaled round constant from rc_partial_scaled29) on every case above: limbs in range, the value inside (2^254 - 2^145, 2^255 + 2^145), canonical form
+    // = finish + constant; the mailbox slot returns the same limbs.  (ii) one chain step on it: x5 = pow5_lazy29 of a lazy u, recoded unreduced (digits sum to
+    // the canonical x5 under the unit fragment's finish), u' = x5 + slot within pow5_lazy29's contract, and pow5 of u' equal to fr_pow5_r29 of the canonical sum.
+    if (kc.rc_partial_scaled29.size() != (size_t)65 * 9) { fprintf(stderr, "rc_partial_scaled29 missing\n"); return 1; }
+    for (int i = 0; i < 9; ++i) if (kc.rc_partial_scaled29[64 * 9 + i] != 0) { fprintf(stderr, "rc_partial_scaled29: the closing entry is not zero\n"); return 1; }
+    for (size_t ci = 0; ci < cases.size(); ++ci) for (int k = 0; k < (ci < ncraft ? 4 : 1); ++k) {
+        const int kk = ci < ncraft ? k : (int)(ci & 3);
+        const fr_t cst = kk == 0 ? host::h_zero() : kk == 1 ? one : kk == 2 ? rm1 : kc.rc_partial_scaled[ci % 64];
+        const fr29_t c29l = fr29_unpack(cst);
+        int64_t col[9]; uint32_t l[9]; mfma_cols_of_sums(cases[ci].data(), col, c29l.l); mfma_finish_limbs(col, l);
+        bool ok = l[8] < (1u << 24) && l[8] >= (1u << 22) - 1 && l[8] <= (1u << 23);
+        for (int i = 0; i < 8; ++i) ok = ok && l[i] <= FR_M29;
+        fr_t z = fr29_pack_reduce<PF>(l); fr_cond_sub<PF>(z.v, 0u);
+        const fr_t hq = fr_add<PF>(finish(cases[ci].data()), cst);
+        const fr_t slot = lazy29_to_slot(l);
+        fr29_t zero9; for (int i = 0; i < 9; ++i) zero9.l[i] = 0;
+        const fr29_t back = lazy29_add_slot(zero9, slot);
+        for (int i = 0; i < 9; ++i) ok = ok && back.l[i] == l[i];
+        ++n; if (!ok || !fr_eq(z, hq)) { if (bad < 5) fprintf(stderr, "finish with constant: case %zu constant %d\n", ci, kk); ++bad; }
+        // a chain step: u = a canonical value plus a constant (as the chain enters a block), or every limb at its maximum
+        fr29_t u = lazy29_add_c29(fr29_unpack(ci & 1 ? rm1 : rand_fr()).l, c29l.l);
+        if (ci == 0) { for (int i = 0; i < 8; ++i) u.l[i] = 2 * FR_M29; u.l[8] = (3u << 22) + (1u << 20); }
+        fr_t ucan = fr29_canon_lazy<PF>([&] { fr29_t t = u; fr29_norm(t); return t; }());
+        const fr29_t x5 = pow5_lazy29(u);
+        const fr_t x5can = fr29_pack_reduce<PF>(x5.l);
+        const fr_t yd = recode_lazy29(x5);
+        int64_t U[32] = {0}; kstep(unit, yd, U); int32_t S[32]; for (int c = 0; c < 32; ++c) S[c] = (int32_t)U[c];
+        bool step_ok = fr_eq(x5can, fr_pow5_r29<PF>(ucan)) && fr_eq(finish(S), x5can) && (fr29_pack(x5.l).v[7] >> 24) <= 0x42;
+        const fr29_t un = lazy29_add_slot(x5, slot);
+        for (int i = 0; i < 9; ++i) step_ok = step_ok && un.l[i] < (1u << 30);
+        step_ok = step_ok && fr_eq(fr29_pack_reduce<PF>(pow5_lazy29(un).l), fr_pow5_r29<PF>(fr_add<PF>(x5can, hq)));
+        ++n; if (!step_ok) { if (bad < 5) fprintf(stderr, "chain step: case %zu constant %d\n", ci, kk); ++bad; }
+    }
+    // ---- the lanes between two blocks from the signed residue (mfma_finish_recoded: floor quotient, sign-extended pack, recode) on every case above: the top
+    // limb in [-1, 2^22], and the digits, taken through the unit fragment's K-step and the canonical finish as the next block's products take them, give the
+    // canonical value of the row
+    for (size_t ci = 0; ci < cases.size(); ++ci) {
+        int64_t col[9]; uint32_t l[9]; mfma_cols_of_sums(cases[ci].data(), col); mfma_finish_limbs_floor(col, l);
+        bool ok = (int32_t)l[8] >= -1 && (int32_t)l[8] <= (1 << 22);
+        for (int i = 0; i < 8; ++i) ok = ok && l[i] <= FR_M29;
+        mfma_cols_of_sums(cases[ci].data(), col); const fr_t d = mfma_finish_recoded(col);
+        int64_t U[32] = {0}; kstep(unit, d, U); int32_t S[32]; for (int c = 0; c < 32; ++c) S[c] = (int32_t)U[c];
+        ++n; if (!ok || !fr_eq(finish(S), finish(cases[ci].data()))) { if (bad < 5) fprintf(stderr, "signed-residue lane: case %zu\n", ci); ++bad; }
     }
     printf("{\"check\": \"residue tables and finishing step against the portable field code\", \"cases\": %ld, \"mismatches\": %ld}\n", n, bad);
     return bad ? 1 : 0;

@@ -1,12 +1,15 @@
-// tools/partial_block8.hip — PROTOTYPE, not product code: 8 partial rounds of the t = 17 Poseidon permutation for 64 sponges per wave pair, in five forms.
+// tools/partial_block8.hip — PROTOTYPE, not product code: 8 partial rounds of the t = 17 Poseidon permutation for 64 sponges per wave pair, in six forms.
 //   form 4      : the shipped block-of-4 code, twice — pair_permute<17> of poseidon_pair.hpp itself, run with rf = 0 and rp = 8 (no full rounds);
 //   former 8    : one block of 8 rounds whose E-product (8 rows x 16 lanes) and lane product (16 rows x 8 S-box outputs, plus the base lane as a ninth
 //                 K-step) run on the matrix cores through residue tables, the 28 Gamma terms of the block on the vector ALU (namespace former below: the
 //                 product's form until the Gamma terms moved; kept here as the comparison);
 //   form 8      : the product's pair_block8 (poseidon_pair.hpp, where the schedule is described): the Gamma terms as q further K-steps of row q's tile,
-//                 X posting y_q recoded, the chain SCALED (s0 = lambda_q X_q, no a_q y_q product; tables blk8s_*).  Instantiated for several shares of
-//                 the lane rows (NLX).  The one product by 1 / lambda_8 that brings X_8 back runs in the checked repetition only: a permutation pays it
-//                 once per eight blocks;
+//                 X posting y_q recoded, the chain SCALED (s0 = lambda_q X_q, no a_q y_q product; tables blk8s_*) and carried as a LAZY RESIDUE: H_q handed
+//                 over as its nine finish limbs with the next round's constant in them, no field element formed inside the block.  Instantiated for several
+//                 shares of the lane rows (NLX).  The one product by 1 / lambda_8 that brings X_8 back runs in the checked repetition only: a permutation
+//                 pays it once per eight blocks;
+//   canonical 8 : the same schedule with a canonical chain value in every round (namespace canonical below: the product's form until the chain became a lazy
+//                 residue; kept here as the comparison) — fr_add with the constant, fr_pow5_r29, recode, and after the barrier fr_add with a canonical H_q;
 //   unscaled 8  : the same schedule with the chain unscaled, a_q y_q as a nine-limb product in every round of X (namespace unscaled below: the product's
 //                 form until the chain was scaled; kept here as the comparison; tables blk8_*);
 //   form 8 piped: the scaled form with wave Y software-pipelined across the round barrier (namespace piped below), measured and not adopted.
@@ -153,11 +156,72 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Tabs& Tb, 
 }
 }  // namespace former
 
+// ---- the product's schedule with a CANONICAL chain value in every round, kept here as the comparison: wave X adds the scaled constant (fr_add), runs
+// fr_pow5_r29 (unpack, three products, pack, conditional subtraction), posts the recoded y and adds the canonical H_q (mfma_post: pack and two conditional
+// subtractions in wave Y) after the barrier.  The lane rows are the product's.  The product no longer contains it.
+namespace canonical {
+struct Tabs { const mfma_v4i* efrag; const mfma_v4i* lfrag; const mfma_v4i* unit; const mfma_v4i* gfrag; const fr_t* rc; };      // rc [8]: lambda_q c_q, or c_q for the unscaled chain
+template <int Q>
+__device__ __forceinline__ void round_x(const PairState& s, const Tabs& Tb, fr_t& s0, mfma_v4i (&b)[8][2]) {
+    __builtin_amdgcn_sched_barrier(0);
+    const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));   // yt_Q: canonical
+    s.sto(Blk8Cfg::ymail(Q), recode_signed(y));
+    __syncthreads();                                       // barrier_Q: H_Q is posted (canonical: mfma_post)
+    s0 = fr_add<PF>(y, s.ld(Blk8Cfg::hmail(Q)));
+    b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
+}
+template <int Q>
+__device__ __forceinline__ void round_y(const PairState& s, const Tabs& Tb, mfma_v4i (&b)[8][2], mfma_v4i (&a)[16], mfma_v4i (&g)[7]) {
+    __builtin_amdgcn_sched_barrier(0);
+    const int lane = s.lane;
+    mfma_v16i acc[2];
+    mfma_zero_tile(acc);
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[e], blk8_b_of_slot(s, e + 1, ct), acc[ct], 0, 0, 0);
+    if constexpr (Q > 0) {
+#pragma unroll
+        for (int p = 0; p < Q; ++p)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(g[p], b[p][ct], acc[ct], 0, 0, 0);
+    }
+    if constexpr (Q < 7) {
+        blk8_load_frags16(a, Tb.efrag + (size_t)(Q + 1) * 16 * 64, lane);
+#pragma unroll
+        for (int p = 0; p <= Q; ++p) g[p] = (Tb.gfrag + (size_t)((Q + 1) * Q / 2 + p) * 64)[lane];
+    }
+    s.sto(Blk8Cfg::hmail(Q), mfma_post(acc));
+    __syncthreads();                                       // barrier_Q: y_Q is posted
+    b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
+}
+template <int NLX>
+__device__ __forceinline__ void lane_rows(const PairState& s, const Tabs& Tb, const mfma_v4i (&b)[8][2], bool last) {
+    const Blk8Tabs T8{Tb.efrag, Tb.lfrag, Tb.unit, Tb.gfrag, nullptr};
+    blk8_lane_rows<NLX>(s, T8, b, last);
+}
+template <int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Tabs& Tb, fr_t& s0, bool last) {
+    mfma_v4i b[8][2];
+    if (!s.isY) {
+        round_x<0>(s, Tb, s0, b); round_x<1>(s, Tb, s0, b); round_x<2>(s, Tb, s0, b); round_x<3>(s, Tb, s0, b);
+        round_x<4>(s, Tb, s0, b); round_x<5>(s, Tb, s0, b); round_x<6>(s, Tb, s0, b); round_x<7>(s, Tb, s0, b);
+    } else {
+        mfma_v4i a[16], g[7];
+        blk8_load_frags16(a, Tb.efrag, s.lane);
+        round_y<0>(s, Tb, b, a, g); round_y<1>(s, Tb, b, a, g); round_y<2>(s, Tb, b, a, g); round_y<3>(s, Tb, b, a, g);
+        round_y<4>(s, Tb, b, a, g); round_y<5>(s, Tb, b, a, g); round_y<6>(s, Tb, b, a, g); round_y<7>(s, Tb, b, a, g);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    lane_rows<NLX>(s, Tb, b, last);
+}
+}  // namespace canonical
+
 // ---- the product's schedule with the chain UNSCALED, kept here as the comparison: X_{q+1} = H_q + a_q y_q, the product a nine-limb unpack, 81 MACs and a wide
-// reduction in every round of wave X.  Wave Y and the lane rows are the product's, fed the unscaled tables.  The product no longer contains it.
+// reduction in every round of wave X.  Wave Y is the canonical form's, the lane rows are the product's, fed the unscaled tables.  The product no longer contains it.
 namespace unscaled {
 template <int Q>
-__device__ __forceinline__ void round_x(const PairState& s, const Blk8Tabs& Tb, const uint32_t* a29, fr_t& s0, mfma_v4i (&b)[8][2]) {
+__device__ __forceinline__ void round_x(const PairState& s, const canonical::Tabs& Tb, const uint32_t* a29, fr_t& s0, mfma_v4i (&b)[8][2]) {
     __builtin_amdgcn_sched_barrier(0);
     const fr_t y = fr_pow5_r29<PF>(fr_add<PF>(s0, Tb.rc[Q]));
     fr_wide29 acc; fr_wide29_zero(acc);
@@ -169,7 +233,7 @@ __device__ __forceinline__ void round_x(const PairState& s, const Blk8Tabs& Tb, 
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
 template <int NLX>
-__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, const uint32_t* a29, fr_t& s0, bool last) {
+__device__ __forceinline__ void pair_block8(const PairState& s, const canonical::Tabs& Tb, const uint32_t* a29, fr_t& s0, bool last) {
     mfma_v4i b[8][2];
     if (!s.isY) {
         round_x<0>(s, Tb, a29, s0, b); round_x<1>(s, Tb, a29, s0, b); round_x<2>(s, Tb, a29, s0, b); round_x<3>(s, Tb, a29, s0, b);
@@ -177,20 +241,20 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
     } else {
         mfma_v4i a[16], g[7];
         blk8_load_frags16(a, Tb.efrag, s.lane);
-        blk8_round_y<0>(s, Tb, b, a, g); blk8_round_y<1>(s, Tb, b, a, g); blk8_round_y<2>(s, Tb, b, a, g); blk8_round_y<3>(s, Tb, b, a, g);
-        blk8_round_y<4>(s, Tb, b, a, g); blk8_round_y<5>(s, Tb, b, a, g); blk8_round_y<6>(s, Tb, b, a, g); blk8_round_y<7>(s, Tb, b, a, g);
+        canonical::round_y<0>(s, Tb, b, a, g); canonical::round_y<1>(s, Tb, b, a, g); canonical::round_y<2>(s, Tb, b, a, g); canonical::round_y<3>(s, Tb, b, a, g);
+        canonical::round_y<4>(s, Tb, b, a, g); canonical::round_y<5>(s, Tb, b, a, g); canonical::round_y<6>(s, Tb, b, a, g); canonical::round_y<7>(s, Tb, b, a, g);
     }
     __builtin_amdgcn_sched_barrier(0);
-    blk8_lane_rows<NLX>(s, Tb, b, last);
+    canonical::lane_rows<NLX>(s, Tb, b, last);
 }
 }  // namespace unscaled
 
-// ---- the product's form with wave Y SOFTWARE-PIPELINED across the round barrier, measured here and not in the product unless it wins: of row Q only the
+// ---- the canonical form with wave Y SOFTWARE-PIPELINED across the round barrier, measured here and not in the product unless it wins: of row Q only the
 // K-step of y_{Q-1} depends on barrier_{Q-1}, so the 16 lane steps and the steps of y_p, p <= Q - 2, are issued before that barrier, after H_{Q-1} is
 // posted (the accumulator pair is free again by then: no second pair).  Wave X and the lane product are the product's.
 namespace piped {
 template <int Q>
-__device__ __forceinline__ void round_y(const PairState& s, const Blk8Tabs& Tb, mfma_v4i (&b)[8][2], mfma_v4i (&a)[16], mfma_v4i (&g)[7], mfma_v16i (&acc)[2]) {
+__device__ __forceinline__ void round_y(const PairState& s, const canonical::Tabs& Tb, mfma_v4i (&b)[8][2], mfma_v4i (&a)[16], mfma_v4i (&g)[7], mfma_v16i (&acc)[2]) {
     __builtin_amdgcn_sched_barrier(0);
     const int lane = s.lane;
     if constexpr (Q > 0) {
@@ -224,11 +288,11 @@ __device__ __forceinline__ void round_y(const PairState& s, const Blk8Tabs& Tb, 
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
 template <int NLX>
-__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr_t& s0, bool last) {
+__device__ __forceinline__ void pair_block8(const PairState& s, const canonical::Tabs& Tb, fr_t& s0, bool last) {
     mfma_v4i b[8][2];
     if (!s.isY) {
-        blk8_round_x<0>(s, Tb, s0, b); blk8_round_x<1>(s, Tb, s0, b); blk8_round_x<2>(s, Tb, s0, b); blk8_round_x<3>(s, Tb, s0, b);
-        blk8_round_x<4>(s, Tb, s0, b); blk8_round_x<5>(s, Tb, s0, b); blk8_round_x<6>(s, Tb, s0, b); blk8_round_x<7>(s, Tb, s0, b);
+        canonical::round_x<0>(s, Tb, s0, b); canonical::round_x<1>(s, Tb, s0, b); canonical::round_x<2>(s, Tb, s0, b); canonical::round_x<3>(s, Tb, s0, b);
+        canonical::round_x<4>(s, Tb, s0, b); canonical::round_x<5>(s, Tb, s0, b); canonical::round_x<6>(s, Tb, s0, b); canonical::round_x<7>(s, Tb, s0, b);
     } else {
         mfma_v4i a[16], g[7]; mfma_v16i acc[2];
         blk8_load_frags16(a, Tb.efrag, s.lane);
@@ -244,18 +308,19 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
         round_y<4>(s, Tb, b, a, g, acc); round_y<5>(s, Tb, b, a, g, acc); round_y<6>(s, Tb, b, a, g, acc); round_y<7>(s, Tb, b, a, g, acc);
     }
     __builtin_amdgcn_sched_barrier(0);
-    blk8_lane_rows<NLX>(s, Tb, b, last);
+    canonical::lane_rows<NLX>(s, Tb, b, last);
 }
 }  // namespace piped
 
 // The tables of "block rep & blkmask" (always block 0): as in a permutation's loop over its blocks the fragment addresses change from one pass to the
 // next, so the compiler cannot hoist all of them out of the repetition loop (it did, and spilled 200 registers for them).
 // efrag / lfrag / gfrag / rc: the unscaled family (blk8_*, rc_partial); sefrag / slfrag / sgfrag / src: the scaled one (blk8s_*, rc_partial_scaled);
-// unscale8: 1 / lambda_8 as a multiplier-table entry (block 0 ends at round 8; the product's table holds 1 / lambda_rp)
+// unscale8: 1 / lambda_8 as a multiplier-table entry (block 0 ends at round 8; the product's table holds 1 / lambda_rp);
+// src29: lambda_q c_q of rounds 0..7 as nine limbs each and a ninth entry of zeros (the block is followed by no round here: rc_partial_scaled29 of an rp = 8 set)
 struct ProtoTabs { const mfma_v4i* efrag; const mfma_v4i* lfrag; const mfma_v4i* unit; const mfma_v4i* gfrag; const uint32_t* sparse29; const uint32_t* gamma8_29; const fr_t* rc;
-                   const mfma_v4i* sefrag; const mfma_v4i* slfrag; const mfma_v4i* sgfrag; const fr_t* src; const uint32_t* unscale8; int blkmask; };
+                   const mfma_v4i* sefrag; const mfma_v4i* slfrag; const mfma_v4i* sgfrag; const fr_t* src; const uint32_t* src29; const uint32_t* unscale8; int blkmask; };
 
-template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>; YG = -2: unscaled::pair_block8<NLX>
+template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>; YG = -2: unscaled::pair_block8<NLX>; YG = -3: canonical::pair_block8<NLX>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_block8(ProtoTabs Tp, const fr_t* __restrict__ X, fr_t* __restrict__ Y, int reps) {
     extern __shared__ uint4 lds[];
     PairState s = pair_setup(lds);
@@ -270,11 +335,17 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
             const former::Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sparse29, Tp.gamma8_29, Tp.rc};
             former::pair_block8<YG, NLX>(s, Tb, s0, true);  // last: the lanes end canonical in their slots
         } else if constexpr (YG == -2) {
-            const Blk8Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.gfrag + (size_t)blk * 28 * 64, Tp.rc};
+            const canonical::Tabs Tb{Tp.efrag + (size_t)blk * 8 * 16 * 64, Tp.lfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.gfrag + (size_t)blk * 28 * 64, Tp.rc};
             unscaled::pair_block8<NLX>(s, Tb, Tp.sparse29, s0, true);
+        } else if constexpr (YG == 0) {
+            const Blk8Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, c29(Tp.src29, 1)};
+            fr29_t u = fr29_unpack(s0);
+            if (!s.isY) u = lazy29_add_c29(u.l, c29(Tp.src29, 0));          // as pair_permute enters the partial rounds
+            pair_block8<NLX>(s, Tb, u, true);
+            if (rep == 0 && !s.isY) s0 = fr29_pack_reduce<PF>(fr29_mul_c29(Tp.unscale8, u).l);      // lambda_8 X_8 (lazy) -> X_8
         } else {
-            const Blk8Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, Tp.src};
-            if constexpr (YG == 0) pair_block8<NLX>(s, Tb, s0, true); else piped::pair_block8<NLX>(s, Tb, s0, true);
+            const canonical::Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, Tp.src};
+            if constexpr (YG == -3) canonical::pair_block8<NLX>(s, Tb, s0, true); else piped::pair_block8<NLX>(s, Tb, s0, true);
             if (rep == 0 && !s.isY) s0 = fr_mul_c29(Tp.unscale8, s0);      // lambda_8 X_8 -> X_8
         }
         if (rep == 0) {
@@ -318,6 +389,7 @@ int main() {
     g_tb.sparse29 = to_dev<uint32_t>(K.sparse29.data(), K.sparse29.size() * 4); g_tb.gamma8_29 = to_dev<uint32_t>(K.gamma8_29.data(), K.gamma8_29.size() * 4);
     g_tb.sefrag = to_dev<mfma_v4i>(K.blk8s_efrag.data(), K.blk8s_efrag.size()); g_tb.slfrag = to_dev<mfma_v4i>(K.blk8s_lfrag.data(), K.blk8s_lfrag.size());
     g_tb.sgfrag = to_dev<mfma_v4i>(K.blk8s_gfrag.data(), K.blk8s_gfrag.size()); g_tb.src = to_dev<fr_t>(K.rc_partial_scaled.data(), K.rc_partial_scaled.size() * sizeof(fr_t));
+    { std::vector<uint32_t> c29v(K.rc_partial_scaled29.begin(), K.rc_partial_scaled29.begin() + 9 * 9); for (int i = 0; i < 9; ++i) c29v[72 + i] = 0; g_tb.src29 = to_dev<uint32_t>(c29v.data(), c29v.size() * 4); }
     { uint32_t u8[9]; fr29_const_from<host::PF>(fr_inv<host::PF>(K.blk8_lambda[8]), u8); g_tb.unscale8 = to_dev<uint32_t>(u8, sizeof u8); }
     g_tb.blkmask = 0;
     g_tb.rc = to_dev<fr_t>(K.rc_partial.data(), K.rc_partial.size() * sizeof(fr_t));
@@ -339,14 +411,11 @@ int main() {
         {"block4 x 2 (shipped pair_permute<17>, rf = 0, rp = 8)", launch4},
         {"block8, Gamma terms on the vector ALU, YG=5 NLX=8 (the former product form)", launch8<5, 8>},
         {"block8, Gamma K-steps, chain unscaled (a_q y_q product per round), NLX=8 (the former product form)", launch8<-2, 8>},
-        {"block8, Gamma K-steps, chain scaled, NLX=8", launch8<0, 8>},
-        {"block8, Gamma K-steps, chain scaled, NLX=8, wave Y pipelined across the round barrier", launch8<-1, 8>},
-        {"block8, Gamma K-steps, chain scaled, NLX=6", launch8<0, 6>},
-        {"block8, Gamma K-steps, chain scaled, NLX=7", launch8<0, 7>},
-        {"block8, Gamma K-steps, chain scaled, NLX=9", launch8<0, 9>},
-        {"block8, Gamma K-steps, chain scaled, NLX=10", launch8<0, 10>},
-        {"block8, Gamma K-steps, chain unscaled, NLX=7", launch8<-2, 7>},
-        {"block8, Gamma K-steps, chain unscaled, NLX=9", launch8<-2, 9>},
+        {"block8, Gamma K-steps, chain scaled, canonical value in every round, NLX=8 (the former product form)", launch8<-3, 8>},
+        {"block8, Gamma K-steps, chain scaled, lazy residues, NLX=8", launch8<0, 8>},
+        {"block8, Gamma K-steps, chain scaled, canonical, NLX=8, wave Y pipelined across the round barrier", launch8<-1, 8>},
+        {"block8, Gamma K-steps, chain scaled, lazy residues, NLX=7", launch8<0, 7>},
+        {"block8, Gamma K-steps, chain scaled, lazy residues, NLX=9", launch8<0, 9>},
     };
     const int nforms = (int)(sizeof forms / sizeof forms[0]);
     // reference: the sparse rounds in the portable field code, sampled batches
