@@ -288,7 +288,7 @@ int32_t hc_blk8_row23_max(int reset) { return reset ? g_blk8_row23_max.exchange(
 // recoded yt_0..yt_{q-1}), the SCALED chain as a LAZY residue (u = lambda_q X_q + lambda_q c_q as nine limbs; x5 = pow5_lazy29(u), yt_q recoded unreduced; u <- x5 + the finish limbs of
 // H_q + lambda_{q+1} c_{q+1} through the mailbox slot's layout; no field element inside a block, no a_q y_q product; one product by
 // 1 / lambda_rp after the last block), lane rows with the unit fragment as the ninth K-step — with blk8s_efrag / blk8s_gfrag / blk8s_lfrag, rc_partial_scaled and
-// blk8_unscale29 as uploaded; between two blocks the lanes are the digits of their signed residue (mfma_finish_recoded), the fused rows' S-box outputs are recoded
+// blk8_unscale29 as uploaded; between two blocks the lanes are the digits of their signed residue (mfma_finish_bytes on the word columns), the fused rows' S-box outputs are recoded
 // unreduced.  -1: the set has no block-8 tables; -2: a digit sum out of range; -4: a chain limb outside pow5_lazy29's contract.
 int hc_permute_block8(void* h, uint64_t* states, size_t n) {
     HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc; const int t = k.t, half = k.rf / 2;
@@ -340,7 +340,7 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
                 if (b == nb - 1) {          // the last block: the lane goes from its finish limbs through the next full round's S-box, like a fused product row
                     int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; }
                     uint32_t l[9]; blk8_finish_sums_limbs(S, l); xd[j] = sbox_lazy29_recoded(l, &k.rc_full29[((size_t)half * t + j) * 9]);
-                } else { int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; } int64_t col[9]; mfma_cols_of_sums(S, col); rec[j] = mfma_finish_recoded(col); }      // the signed residue's digits
+                } else { int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; } int64_t col[8]; mfma_word_cols_of_sums(S, col); rec[j] = mfma_finish_bytes(col); }      // the signed residue's digits, finished in the byte domain
             }
         }
         const fr29_t x0 = fr29_mul_c29(k.blk8_unscale29.data(), u);                                // lambda_rp X_rp (lazy) -> X_rp (below 1.04 r), once per permutation
@@ -397,6 +397,20 @@ int hc_mfma_finish_recoded(const int32_t* sums, size_t n, uint32_t* limbs, int8_
         for (int i = 0; i < 32; ++i) if (S[i] >= (1 << 24) || S[i] <= -(1 << 24)) return -1;
         int64_t col[9]; mfma_cols_of_sums(S, col); mfma_finish_limbs_floor(col, limbs + 9 * s);
         mfma_cols_of_sums(S, col); const fr_t d = mfma_finish_recoded(col); memcpy(digits + 32 * s, d.v, 32);
+    }
+    return 0;
+}
+// The byte-domain finish of the same lanes: n cases of 32 digit sums -> the eight word columns as the lane pair folds them (wide != 0: pairs formed in 64 bits,
+// rows of up to 17 K-steps; else the int32 pairs of the 9-K-step lane rows), the quotient estimate, the carry out of word 7 and the 32 signed digits.
+// -1: a sum outside the form's domain (|S_c| <= 9 * 32 * 128 * 128, wide: 17 * 32 * 128 * 128).
+int hc_mfma_finish_bytes(const int32_t* sums, size_t n, int wide, int64_t* cols, int32_t* qh, int64_t* carry, int8_t* digits) {
+    const int32_t lim = (wide ? 17 : 9) * 32 * 128 * 128;
+    for (size_t s = 0; s < n; ++s) {
+        const int32_t* S = sums + 32 * s;
+        for (int i = 0; i < 32; ++i) if (S[i] > lim || S[i] < -lim) return -1;
+        int64_t* col = cols + 8 * s;
+        if (wide) mfma_word_cols_of_sums<true>(S, col); else mfma_word_cols_of_sums<false>(S, col);
+        const fr_t d = mfma_finish_bytes(col, qh + s, carry + s); memcpy(digits + 32 * s, d.v, 32);
     }
     return 0;
 }

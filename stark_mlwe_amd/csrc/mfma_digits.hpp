@@ -3,7 +3,7 @@
 // in limb form and the lazy chain of the 8-round blocks (slot layout, limb adds, unreduced recode).
 // poseidon_pair.hpp includes it for the t = 17 wave-pair kernels (exchange and tile handling stay there); hostcheck.cpp and tools/mfma_finish_check.cpp
 // run the same statements on the CPU against the L*U rows and against big integers (tests/test_hostcheck.py,
-// tests/test_full_round_residue_tables_host.py, tests/test_limb_handover_host.py, tests/test_lazy_residue_host.py).  The host-only part at the end: the row-order entry of the fold
+// tests/test_full_round_residue_tables_host.py, tests/test_limb_handover_host.py, tests/test_lazy_residue_host.py, tests/test_byte_finish_host.py).  The host-only part at the end: the row-order entry of the fold
 // (mfma_cols_of_sums) and the 128-bit column census of the S-box (Lazy29Wide).
 #pragma once
 #include "fr.hpp"
@@ -145,7 +145,8 @@ FR_HD fr_t recode_lazy29(const fr29_t& x5) { return recode_signed(fr29_pack(x5.l
 // the fused rows' S-box with the output recoded unreduced: what a slot holds when the next product reads it as a B operand
 FR_HD fr_t sbox_lazy29_recoded(const uint32_t* l, const uint32_t* __restrict__ c) { return recode_lazy29(pow5_lazy29(lazy29_add_c29(l, c))); }
 // ---- the lanes between two 8-round blocks from the SIGNED residue (poseidon_pair.hpp blk8_lane_rows): a B operand needs signed bytes of SOME integer
-// congruent to the lane, not the canonical one.  The finish with the FLOOR quotient:
+// congruent to the lane, not the canonical one.  First the form through nine limbs (the kernels' form until the byte-domain finish below; the host checks and
+// tools/partial_block8.hip keep it as the comparison).  The finish with the FLOOR quotient:
 //   q           floor(V / 2^254) = top >> 22, |q| < 2^18.02 + 1;
 //   W           V - q r = (V mod 2^254) - q t in (-2^144.02, 2^254 + 2^144.02): limbs 0..7 in [0, 2^29), the top limb in [-1, 2^22] as a signed word.
 // fr29_pack takes bits 232..255 from the low 24 bits of the top limb, so the eight words are W's two's complement (sign-extended), and recode_signed on it
@@ -165,6 +166,41 @@ FR_HD void mfma_finish_limbs_floor(int64_t* col, uint32_t* l) {
     for (int i = 5; i < 9; ++i) { const int32_t d = (int32_t)l[i] + c32; if (i < 8) { l[i] = (uint32_t)d & FR_M29; c32 = d >> 29; } else l[8] = (uint32_t)d; }
 }
 FR_HD fr_t mfma_finish_recoded(int64_t* col) { uint32_t l[9]; mfma_finish_limbs_floor(col, l); return recode_signed(fr29_pack(l)); }
+// ---- the same lanes finished in the BYTE domain (what blk8_lane_rows runs between two blocks): the digit sums are byte-indexed and so is the consumer, so
+// the row never passes through 29-bit limbs.  Same contract as mfma_finish_recoded: eight words whose bytes, read as signed digits, sum to some W == V (mod r).
+//   fold        word column k = P0 + 2^16 P1 with P0 = S_{4k} + 256 S_{4k+1}, P1 = S_{4k+2} + 256 S_{4k+3}, V = sum_k col_k 2^(32k).  The four sums of a word
+//               are registers 4q..4q+3 of ONE lane's tile (rows 8q + 4h + 0..3, h = the lane's half: word 2q + h), so a lane folds what it holds and only
+//               finished columns are exchanged.  Lane rows (9 K-steps): |S_c| <= 9 * 32 * 128 * 128 = 4 718 592 < 2^22.17, |P| <= 257 |S| < 2^30.18: an int32;
+//               |col| <= 65537 |P| < 2^46.2.  WIDE (rows of up to 17 K-steps): |S_c| <= 8 912 896 < 2^23.09, |P| < 2^31.1: pairs in 64 bits, |col| < 2^47.1.
+//   quotient    x = col_7 + (col_6 >> 32), V / 2^224 = x + f, where f in (-2^-17, 1 + 2^-17) is what the columns below contribute (col_6's low word
+//               below 1, col_5 and lower |col_k| 2^(32k - 224) < 2^(47.1 - 64) each); q^ = (x + 2) >> 30.  With q = floor(V / 2^254): q <= q^ <= q + 1, and
+//               |q^| < 2^17.2 (WIDE: 2^18.2).
+//   one pass    t = col_k + carry + 0x80808080 - q^ t_k (k < 4: r = 2^254 + t, t below 2^126, t_k its words) - q^ 2^30 (k = 7); word_k = lo32(t) ^ 0x80808080,
+//               carry = t >> 32.  |q^ t_k| < 2^50.2, |carry| < 2^19: every t inside an int64.  W = V - q^ r is in (-r - 2^145, 2^254 + 2^145), so with
+//               K = 0x8080...80 > 2^255, W + K is in [0, 2^256): no carry leaves word 7 and the digits byte - 128 sum to W exactly.
+// qh / carry_out (host checks): the quotient estimate and the carry out of word 7 (zero by the bound above).
+template <bool WIDE = false, class V> FR_HD void mfma_word_cols(const V& a, int64_t* wc) {      // one tile's 16 sums in a lane -> its four word columns
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if constexpr (WIDE) wc[q] = ((int64_t)a[4 * q] + (int64_t)a[4 * q + 1] * 256) + ((int64_t)a[4 * q + 2] + (int64_t)a[4 * q + 3] * 256) * 65536;
+        else { const int32_t p0 = a[4 * q] + a[4 * q + 1] * 256, p1 = a[4 * q + 2] + a[4 * q + 3] * 256; wc[q] = (int64_t)p0 + (int64_t)p1 * 65536; }
+    }
+}
+FR_HD fr_t mfma_finish_bytes(const int64_t* col, int32_t* qh_out = nullptr, int64_t* carry_out = nullptr) {
+    const int64_t x = col[7] + (col[6] >> 32);
+    const int32_t qh = (int32_t)((x + 2) >> 30);
+    fr_t z; int64_t carry = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        int64_t t = col[k] + carry + (int64_t)0x80808080u;
+        if (k < 4) t -= (int64_t)qh * (int64_t)PF::P(k);
+        if (k == 7) t -= (int64_t)qh * ((int64_t)1 << 30);
+        z.v[k] = (uint32_t)t ^ 0x80808080u; carry = t >> 32;
+    }
+    if (qh_out) *qh_out = qh;
+    if (carry_out) *carry_out = carry;
+    return z;
+}
 // c * u for a multiplier-table entry c (nine limbs of c R' mod r, fr29_const_from) and a lazy u (limbs below 2^30, below 4 r): a column holds nine products
 // below 2^59 and the reduction's 6 * 2^58: below 2^63; the result is below (4 / 128 + 1) r < 1.04 r with limbs below 2^29.
 FR_HD fr29_t fr29_mul_c29(const uint32_t* __restrict__ c, const fr29_t& u) { fr_wide29 w; fr_wide29_zero(w); fr_wide29_mac(w, c, u); fr29_t r; fr_wide29_mont<PF>(w, r.l); return r; }
@@ -178,6 +214,16 @@ inline void mfma_cols_of_sums(const int32_t* S, int64_t* col, const uint32_t* c2
     for (int k = 0; k < 9; ++k) col[k] = 0;
     mfma_fold_rows(col, lo, hi);
     if (c29) { int64_t cc[9]; mfma_cols_set(cc, c29); for (int k = 0; k < 9; ++k) col[k] += cc[k]; }
+}
+// 32 digit sums in ROW order -> the eight word columns of the byte-domain finish, as the two lanes of a sponge form them: each lane folds the 16 registers of
+// its own tile (h = 0 the lower lane, h = 1 the upper one), the lanes then exchange finished columns (word 2q + h from half h)
+template <bool WIDE = false> inline void mfma_word_cols_of_sums(const int32_t* S, int64_t* col) {
+    for (int h = 0; h < 2; ++h) {
+        int32_t a[16]; int64_t wc[4];
+        for (int reg = 0; reg < 16; ++reg) a[reg] = S[(reg & 3) + 8 * (reg >> 2) + 4 * h];
+        mfma_word_cols<WIDE>(a, wc);
+        for (int q = 0; q < 4; ++q) col[2 * q + h] = wc[q];
+    }
 }
 // sbox_lazy29's three steps with 128-bit columns, statement by statement after fr29_sqr_mont / fr29_mul_mont / fr_wide29_mont, recording the largest value any
 // column holds when it is consumed (a column only grows until then): what the 64-bit columns of the kernels have to hold.  Returns x5's limbs.

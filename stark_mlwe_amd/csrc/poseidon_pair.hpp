@@ -147,6 +147,20 @@ __device__ __forceinline__ fr_t mfma_post(const mfma_v16i (&acc)[2]) {
     mfma_post_cols(acc, col);
     return mfma_finish_cols(col);
 }
+// fold, exchange, byte-domain finish: -> the signed residue's digits of the lane's sponge (mfma_digits.hpp mfma_finish_bytes).  Each lane folds the registers it
+// holds — four word columns per tile: words 0, 2, 4, 6 of its sponges in the lower lane, 1, 3, 5, 7 in the upper one — and only the four 64-bit columns of
+// each tile cross the lane pair: 8 v_permlane32_swap against the 16 of mfma_post_cols.  Rows of at most 9 K-steps (the int32 pairs of mfma_word_cols).
+__device__ __forceinline__ fr_t mfma_post_bytes(const mfma_v16i (&acc)[2]) {
+    int64_t c0[4], c1[4], col[8];
+    mfma_word_cols(acc[0], c0); mfma_word_cols(acc[1], c1);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)(uint64_t)c0[q], (unsigned)(uint64_t)c1[q], false, false);
+        const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)((uint64_t)c0[q] >> 32), (unsigned)((uint64_t)c1[q] >> 32), false, false);
+        col[2 * q] = (int64_t)((uint64_t)lo[0] | ((uint64_t)hi[0] << 32)); col[2 * q + 1] = (int64_t)((uint64_t)lo[1] | ((uint64_t)hi[1] << 32));
+    }
+    return mfma_finish_bytes(col);
+}
 // The limb-form hand-over of a row: its nine finish limbs l (mfma_finish_limbs) go straight through the next full round's S-box (rc29: that round's constant
 // for element j, nine limbs) and into slot j as the next product's operand (recoded; canonical, not recoded, in front of the squeeze round).  No canonical value
 // in between.  The finish itself stays at the two call sites: taken in here as well, k_node16_pair<true> holds one VGPR more than before the merge (245).
@@ -284,8 +298,8 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
 // the lane product: s_j <- s_j + sum_p w_{p,j} y_p for this wave's share of the lanes (X lanes 1..NLX, Y the rest), b: y_0..y_7 as B operands.  Ends with a barrier.
 // rc29_next != nullptr (FUSE, the permutation's last block): the constants of the full round that follows, 17 x 9 limbs; lane j then goes from its nine finish
 // limbs through that round's S-box (sbox_lazy29) and is stored as the round's operand (recoded unless that round is the squeeze round), like a fused product row.
-// LAZY (the FUSE kernels): between two blocks a lane is stored as the digits of its SIGNED residue (mfma_finish_recoded: floor quotient, sign-extended pack, no
-// conditional subtraction).  k_hash_ds2 keeps canonical lanes: with the signed form k_hash_ds2<17, DsBatchStream, true> spilled 6 VGPRs (28 B of scratch).
+// LAZY (the FUSE kernels): between two blocks a lane is stored as the digits of its SIGNED residue, finished in the byte domain (mfma_post_bytes: word columns
+// folded where the sums sit, a quotient estimate, one pass over eight words; no 29-bit limbs, no conditional subtraction).  k_hash_ds2 keeps canonical lanes: with the signed form k_hash_ds2<17, DsBatchStream, true> spilled 6 VGPRs (28 B of scratch).
 template <int NLX, bool LAZY = false>
 __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], bool last, const uint32_t* rc29_next = nullptr, bool recode_next = true) {
     static_assert(NLX >= 1 && NLX <= 15, "shares");
@@ -310,7 +324,7 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
         // slot j is read by this wave alone, before this write
         if (rc29_next) { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); mfma_finish_limbs(col, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
-        else if (LAZY && !last) { int64_t col[9]; mfma_post_cols(acc, col); s.sto(j, mfma_finish_recoded(col)); }
+        else if (LAZY && !last) s.sto(j, mfma_post_bytes(acc));
         else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }      // between two blocks: the signed residue's digits, no canonical value
     }
     __syncthreads();

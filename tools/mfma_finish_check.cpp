@@ -1,7 +1,7 @@
 // tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds, of
 // the lane product of the 8-round partial blocks with the base lane in the tile (finish with base), and of the blocks' H rows of up to 16 + 7 K-steps:
 // the fragment tables (host_util.hpp mfma_frags), the fold + finishing step and the limb-form hand-over to the next S-box (mfma_digits.hpp, the
-// statements the kernels compile: finish to limbs, S-box on lazy limbs, the lazy chain's finish with a constant, slot and chain step, the signed-residue lanes),
+// statements the kernels compile: finish to limbs, S-box on lazy limbs, the lazy chain's finish with a constant, slot and chain step, the signed-residue lanes through nine limbs and by the byte-domain finish),
 // against the portable field code.  Meant for a
 // sanitizer build; tools/mfma_finish_sanitize.sh builds it with AddressSanitizer + UBSan and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I stark_mlwe_amd/csrc tools/mfma_finish_check.cpp -o tools/bin/mfma_finish_check
@@ -204,6 +204,28 @@ int main() {
         mfma_cols_of_sums(cases[ci].data(), col); const fr_t d = mfma_finish_recoded(col);
         int64_t U[32] = {0}; kstep(unit, d, U); int32_t S[32]; for (int c = 0; c < 32; ++c) S[c] = (int32_t)U[c];
         ++n; if (!ok || !fr_eq(finish(S), finish(cases[ci].data()))) { if (bad < 5) fprintf(stderr, "signed-residue lane: case %zu\n", ci); ++bad; }
+    }
+    // ---- the same lanes by the byte-domain finish (mfma_word_cols / mfma_finish_bytes: what blk8_lane_rows runs).  The form with 64-bit pairs on every case
+    // above (it holds for any |S_c| < 2^24); the form with int32 pairs, the lane rows' own, on every case inside its domain |S_c| <= 9 * 32 * 128 * 128 and on
+    // 20 000 random cases and the extreme patterns drawn inside it.  No carry out of word 7, and the digits, taken through the unit fragment's K-step and the
+    // canonical finish, give the canonical value of the row.
+    {
+        const int32_t L9 = 9 * 32 * 128 * 128;
+        std::vector<std::vector<int32_t>> narrow;
+        for (const auto& s : cases) { bool in = true; for (int32_t v : s) in = in && v <= L9 && v >= -L9; if (in) narrow.push_back(s); }
+        narrow.push_back(std::vector<int32_t>(32, L9)); narrow.push_back(std::vector<int32_t>(32, -L9));
+        { std::vector<int32_t> a(32), b(32); for (int c = 0; c < 32; ++c) { a[c] = c & 1 ? -L9 : L9; b[c] = -a[c]; } narrow.push_back(a); narrow.push_back(b); }
+        for (int32_t k : {-(1 << 16), 1 << 16}) for (int d : {-1, 0, 1}) { std::vector<int32_t> s(32, 0); s[31] = k * 64; s[0] = d; narrow.push_back(s); }
+        for (int i = 0; i < 20000; ++i) { std::vector<int32_t> s(32); for (auto& v : s) v = (int32_t)(rnd() % (2 * (uint64_t)L9 + 1)) - L9; narrow.push_back(s); }
+        auto check_bytes = [&](const std::vector<int32_t>& s, bool wide, size_t ci) {
+            int64_t col[8]; int32_t qh; int64_t carry;
+            if (wide) mfma_word_cols_of_sums<true>(s.data(), col); else mfma_word_cols_of_sums<false>(s.data(), col);
+            const fr_t d = mfma_finish_bytes(col, &qh, &carry);
+            int64_t U[32] = {0}; kstep(unit, d, U); int32_t S[32]; for (int c = 0; c < 32; ++c) S[c] = (int32_t)U[c];
+            ++n; if (carry != 0 || qh >= (1 << 19) || qh <= -(1 << 19) || !fr_eq(finish(S), finish(s.data()))) { if (bad < 5) fprintf(stderr, "byte-domain finish (%s pairs): case %zu\n", wide ? "64-bit" : "int32", ci); ++bad; }
+        };
+        for (size_t ci = 0; ci < cases.size(); ++ci) check_bytes(cases[ci], true, ci);
+        for (size_t ci = 0; ci < narrow.size(); ++ci) { check_bytes(narrow[ci], false, ci); check_bytes(narrow[ci], true, ci); }
     }
     printf("{\"check\": \"residue tables and finishing step against the portable field code\", \"cases\": %ld, \"mismatches\": %ld}\n", n, bad);
     return bad ? 1 : 0;

@@ -13,6 +13,9 @@
 //   unscaled 8  : the same schedule with the chain unscaled, a_q y_q as a nine-limb product in every round of X (namespace unscaled below: the product's
 //                 form until the chain was scaled; kept here as the comparison; tables blk8_*);
 //   form 8 piped: the scaled form with wave Y software-pipelined across the round barrier (namespace piped below), measured and not adopted.
+//   between two blocks: form 8 as a block that is NOT the permutation's last, its lanes left as the digits of their signed residue — the product's byte-domain
+//                 finish (mfma_post_bytes: word columns folded per lane, 8 swaps, one pass over eight words) beside the finish through nine 29-bit limbs
+//                 (namespace limbfinish below: the product's form until the byte finish; kept here as the comparison).  The host decodes the digits.
 //   LDS stays at PairCfg<17>::lds_bytes() = 40 KiB.  The host checks every form against the sparse rounds in the portable field code (0 and r - 1 among
 //   the inputs) and requires zero mismatches; then the forms are timed alternately in one process, the state reloaded from memory for every repetition.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I stark_mlwe_amd/csrc tools/partial_block8.hip -o tools/bin/partial_block8
@@ -312,6 +315,51 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const canonical:
 }
 }  // namespace piped
 
+// ---- the lanes between two blocks finished through NINE 29-BIT LIMBS, kept here as the comparison: exchange of all 32 sums (16 swaps), fold into nine
+// columns, carry pass, floor quotient, pack and recode (mfma_finish_recoded).  The rounds are the product's.  The product no longer runs it on the device.
+namespace limbfinish {
+template <int NLX>
+__device__ __forceinline__ void lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2]) {
+    const int lane = s.lane;
+    const int j0 = s.isY ? NLX + 1 : 1, j1 = s.isY ? 16 : NLX;
+    const mfma_v4i aunit = Tb.unit[lane];
+    mfma_v4i a[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(j0 - 1) * 8 + p) * 64)[lane];
+#pragma unroll 1
+    for (int j = j0; j <= j1; ++j) {
+        mfma_v16i acc[2];
+        mfma_zero_tile(acc);
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], b[p][ct], acc[ct], 0, 0, 0);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aunit, blk8_b_of_slot(s, j, ct), acc[ct], 0, 0, 0);
+        const int jn = j < j1 ? j + 1 : j1;                // the last row fetches its own fragments again: in bounds, unused
+#pragma unroll
+        for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
+        int64_t col[9]; mfma_post_cols(acc, col); s.sto(j, mfma_finish_recoded(col));      // slot j is read by this wave alone, before this write
+    }
+    __syncthreads();
+}
+template <int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr29_t& u) {
+    mfma_v4i b[8][2];
+    if (!s.isY) {
+        blk8_round_x<0>(s, Tb, u, b); blk8_round_x<1>(s, Tb, u, b); blk8_round_x<2>(s, Tb, u, b); blk8_round_x<3>(s, Tb, u, b);
+        blk8_round_x<4>(s, Tb, u, b); blk8_round_x<5>(s, Tb, u, b); blk8_round_x<6>(s, Tb, u, b); blk8_round_x<7>(s, Tb, u, b);
+    } else {
+        mfma_v4i a[16], g[7];
+        blk8_load_frags16(a, Tb.efrag, s.lane);
+        blk8_round_y<0>(s, Tb, b, a, g); blk8_round_y<1>(s, Tb, b, a, g); blk8_round_y<2>(s, Tb, b, a, g); blk8_round_y<3>(s, Tb, b, a, g);
+        blk8_round_y<4>(s, Tb, b, a, g); blk8_round_y<5>(s, Tb, b, a, g); blk8_round_y<6>(s, Tb, b, a, g); blk8_round_y<7>(s, Tb, b, a, g);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    lane_rows<NLX>(s, Tb, b);
+}
+}  // namespace limbfinish
+
 // The tables of "block rep & blkmask" (always block 0): as in a permutation's loop over its blocks the fragment addresses change from one pass to the
 // next, so the compiler cannot hoist all of them out of the repetition loop (it did, and spilled 200 registers for them).
 // efrag / lfrag / gfrag / rc: the unscaled family (blk8_*, rc_partial); sefrag / slfrag / sgfrag / src: the scaled one (blk8s_*, rc_partial_scaled);
@@ -320,7 +368,7 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const canonical:
 struct ProtoTabs { const mfma_v4i* efrag; const mfma_v4i* lfrag; const mfma_v4i* unit; const mfma_v4i* gfrag; const uint32_t* sparse29; const uint32_t* gamma8_29; const fr_t* rc;
                    const mfma_v4i* sefrag; const mfma_v4i* slfrag; const mfma_v4i* sgfrag; const fr_t* src; const uint32_t* src29; const uint32_t* unscale8; int blkmask; };
 
-template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>; YG = -2: unscaled::pair_block8<NLX>; YG = -3: canonical::pair_block8<NLX>
+template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>; YG = -2: unscaled::pair_block8<NLX>; YG = -3: canonical::pair_block8<NLX>; YG = -4 / -5: a block between two blocks (lanes left as signed digits), limbfinish::pair_block8<NLX> / the product's pair_block8<NLX, true> with last = false
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_block8(ProtoTabs Tp, const fr_t* __restrict__ X, fr_t* __restrict__ Y, int reps) {
     extern __shared__ uint4 lds[];
     PairState s = pair_setup(lds);
@@ -343,6 +391,12 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
             if (!s.isY) u = lazy29_add_c29(u.l, c29(Tp.src29, 0));          // as pair_permute enters the partial rounds
             pair_block8<NLX>(s, Tb, u, true);
             if (rep == 0 && !s.isY) s0 = fr29_pack_reduce<PF>(fr29_mul_c29(Tp.unscale8, u).l);      // lambda_8 X_8 (lazy) -> X_8
+        } else if constexpr (YG == -4 || YG == -5) {
+            const Blk8Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, c29(Tp.src29, 1)};
+            fr29_t u = fr29_unpack(s0);
+            if (!s.isY) u = lazy29_add_c29(u.l, c29(Tp.src29, 0));
+            if constexpr (YG == -5) pair_block8<NLX, true>(s, Tb, u, false); else limbfinish::pair_block8<NLX>(s, Tb, u);
+            if (rep == 0 && !s.isY) s0 = fr29_pack_reduce<PF>(fr29_mul_c29(Tp.unscale8, u).l);
         } else {
             const canonical::Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, Tp.src};
             if constexpr (YG == -3) canonical::pair_block8<NLX>(s, Tb, s0, true); else piped::pair_block8<NLX>(s, Tb, s0, true);
@@ -372,7 +426,17 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
 static fr_t canon(fr_t x) { for (int k = 0; k < 3; ++k) fr_cond_sub<host::PF>(x.v, 0u); return x; }   // form 4 leaves its lanes below 2.7 r (pair_lane_update)
 template <class Tp> static Tp* to_dev(const void* p, size_t bytes) { void* d = nullptr; if (hipMalloc(&d, bytes) != hipSuccess || hipMemcpy(d, p, bytes, hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "device copy failed\n"); exit(1); } return (Tp*)d; }
 
-struct Form { const char* name; void (*launch)(int batches, int reps); };
+struct Form { const char* name; void (*launch)(int batches, int reps); bool digits = false; };      // digits: lanes 1..16 come back as signed digits of a residue
+// 32 signed digits -> the canonical value of sum_b d_b 256^b mod r, through the field code
+static fr_t of_digits(const fr_t& d) {
+    const int8_t* b = reinterpret_cast<const int8_t*>(d.v);
+    fr_t acc = host::h_zero(), w = host::h_one(); const fr_t k256 = fr_from_u64<host::PF>(256);
+    for (int c = 0; c < 32; ++c, w = host::h_mul(w, k256)) {
+        const fr_t term = host::h_mul(fr_from_u64<host::PF>((uint64_t)(b[c] < 0 ? -(int)b[c] : (int)b[c])), w);
+        acc = b[c] < 0 ? host::h_sub(acc, term) : host::h_add(acc, term);
+    }
+    return fr_to_canonical<host::PF>(acc);
+}
 static ProtoTabs g_tb; static PoseidonDev g_p; static const fr_t* g_x; static fr_t* g_y;
 template <int YG, int NLX> static void launch8(int batches, int reps) { hipLaunchKernelGGL((k_block8<YG, NLX>), dim3(batches), dim3(128), PairCfg<17>::lds_bytes(), 0, g_tb, g_x, g_y, reps); }
 static void launch4(int batches, int reps) { hipLaunchKernelGGL(k_block4x2, dim3(batches), dim3(128), PairCfg<17>::lds_bytes(), 0, g_p, g_x, g_y, reps); }
@@ -416,6 +480,8 @@ int main() {
         {"block8, Gamma K-steps, chain scaled, canonical, NLX=8, wave Y pipelined across the round barrier", launch8<-1, 8>},
         {"block8, Gamma K-steps, chain scaled, lazy residues, NLX=7", launch8<0, 7>},
         {"block8, Gamma K-steps, chain scaled, lazy residues, NLX=9", launch8<0, 9>},
+        {"block8 between two blocks, lanes as signed digits through nine 29-bit limbs, NLX=8 (the former product form)", launch8<-4, 8>, true},
+        {"block8 between two blocks, lanes as signed digits by the byte-domain finish, NLX=8", launch8<-5, 8>, true},
     };
     const int nforms = (int)(sizeof forms / sizeof forms[0]);
     // reference: the sparse rounds in the portable field code, sampled batches
@@ -441,7 +507,7 @@ int main() {
         if (hipMemcpy(Y.data(), g_y, Y.size() * sizeof(fr_t), hipMemcpyDeviceToHost) != hipSuccess) return 1;
         long bad = 0;
         for (size_t si = 0; si < sample.size(); ++si) for (int n = 0; n < 64; ++n) for (int e = 0; e < T; ++e)
-            if (!fr_eq(ref[(si * T + e) * 64 + n], canon(Y[((size_t)sample[si] * T + e) * 64 + n]))) { if (bad < 5) fprintf(stderr, "%s: mismatch batch %d sponge %d element %d\n", forms[f].name, sample[si], n, e); ++bad; }
+            if (!fr_eq(ref[(si * T + e) * 64 + n], (forms[f].digits && e > 0) ? of_digits(Y[((size_t)sample[si] * T + e) * 64 + n]) : canon(Y[((size_t)sample[si] * T + e) * 64 + n]))) { if (bad < 5) fprintf(stderr, "%s: mismatch batch %d sponge %d element %d\n", forms[f].name, sample[si], n, e); ++bad; }
         printf("{\"check\": \"8 partial rounds of 64 sponges against the sparse rounds in the portable field code, sampled batches, incl. states of 0 and r-1\", \"form\": \"%s\", \"mismatches\": %ld}\n", forms[f].name, bad);
         if (bad) return 1;
     }
