@@ -275,18 +275,19 @@ static int blk8_tile_sums(const int8_t* const* frag, const fr_t* xd, int K, int3
 }
 // a tile's 32 digit sums -> the row's value: the kernels' fold and finish (mfma_digits.hpp), canonical or stopped at the nine limbs
 static fr_t blk8_finish_sums(const int32_t* S) { int64_t col[9]; mfma_cols_of_sums(S, col); return mfma_finish_cols(col); }
-static void blk8_finish_sums_limbs(const int32_t* S, uint32_t* l) { int64_t col[9]; mfma_cols_of_sums(S, col); mfma_finish_limbs(col, l); }
+// to nine limbs as the kernels' mfma_post_limbs does: word columns folded per lane half, exchanged, a constant's words added (c29, or none), one pass
+static void blk8_finish_sums_limbs(const int32_t* S, uint32_t* l, const uint32_t* c29 = nullptr) { int64_t col[8]; mfma_word_cols_mad_of_sums(S, col, c29); mfma_finish_words(col, l); }
 static int blk8_tile(const int8_t* const* frag, const fr_t* xd, int K, fr_t& out) { int32_t S[32]; const int rc = blk8_tile_sums(frag, xd, K, S); if (rc) return rc; out = blk8_finish_sums(S); return 0; }
 // the largest |digit sum| hc_permute_block8 has seen in a row of 16 + 7 K-steps (the longest tile of the block form) since the last reset
 static std::atomic<int32_t> g_blk8_row23_max{0};
 int32_t hc_blk8_row23_max(int reset) { return reset ? g_blk8_row23_max.exchange(0) : g_blk8_row23_max.load(); }
 // A whole t = 17 permutation in the wave-pair kernels' block-8 form: full rounds through the residue tables of M and B_1 M — every product that is followed
-// by a full round hands its rows over in limb form (finish to limbs, the next round's constant from rc_full29, sbox_lazy29), the products in front of the
-// partial rounds and at the end finish canonical, the first round's S-box stands alone, the last block's lane rows feed the S-box of the round after the partial rounds the same way (element 0 from
+// by a full round hands its rows over in limb form (word-column finish to limbs, the next round's constant from rc_full29, sbox_lazy29), the products in front of the
+// partial rounds and at the end finish canonical from the same word columns (two conditional subtractions), the first round's S-box stands alone, the last block's lane rows feed the S-box of the round after the partial rounds the same way (element 0 from
 // the chain value) —, the partial rounds in
 // blocks of 8 — lanes recoded, row q = H_q = E_q + sum Gamma y_p as ONE tile of 16 + q K-steps (E fragments against the lanes, blk8_gfrag against the
 // recoded yt_0..yt_{q-1}), the SCALED chain as a LAZY residue (u = lambda_q X_q + lambda_q c_q as nine limbs; x5 = pow5_lazy29(u), yt_q recoded unreduced; u <- x5 + the finish limbs of
-// H_q + lambda_{q+1} c_{q+1} through the mailbox slot's layout; no field element inside a block, no a_q y_q product; one product by
+// H_q + lambda_{q+1} c_{q+1} (word columns, the constant's words in front of the quotient: mfma_finish_words) through the mailbox slot's layout; no field element inside a block, no a_q y_q product; one product by
 // 1 / lambda_rp after the last block), lane rows with the unit fragment as the ninth K-step — with blk8s_efrag / blk8s_gfrag / blk8s_lfrag, rc_partial_scaled and
 // blk8_unscale29 as uploaded; between two blocks the lanes are the digits of their signed residue (mfma_finish_bytes on the word columns), the fused rows' S-box outputs are recoded
 // unreduced.  -1: the set has no block-8 tables; -2: a digit sum out of range; -4: a chain limb outside pow5_lazy29's contract.
@@ -302,7 +303,7 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
         for (int i = 0; i < t; ++i) {
             const int8_t* fr[17]; for (int e = 0; e < t; ++e) fr[e] = &F[((size_t)i * t + e) * 1024];
             int32_t S[32]; const int rc = blk8_tile_sums(fr, xd.data(), t, S); if (rc) return rc;
-            if (next < 0) o[i] = blk8_finish_sums(S);
+            if (next < 0) { int64_t col[8]; mfma_word_cols_mad_of_sums(S, col); o[i] = mfma_finish_words_canonical(col); }      // the same word columns, two conditional subtractions
             else { uint32_t l[9]; blk8_finish_sums_limbs(S, l); o[i] = sbox_lazy29_recoded(l, &k.rc_full29[((size_t)next * t + i) * 9]); }
         }
         if (next < 0) st = o; else xd = o;
@@ -326,7 +327,7 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
                 if (q == 7) { int32_t m = 0; for (int c = 0; c < 32; ++c) m = std::max(m, S[c] < 0 ? -S[c] : S[c]);
                               int32_t seen = g_blk8_row23_max.load(); while (m > seen && !g_blk8_row23_max.compare_exchange_weak(seen, m)) {} }
                 // Y: the row's finish with the next round's scaled constant in its columns (zero after the last round), posted as the slot's words
-                int64_t col[9]; uint32_t l[9]; mfma_cols_of_sums(S, col, &k.rc_partial_scaled29[(size_t)9 * (8 * b + q + 1)]); mfma_finish_limbs(col, l);
+                uint32_t l[9]; blk8_finish_sums_limbs(S, l, &k.rc_partial_scaled29[(size_t)9 * (8 * b + q + 1)]);
                 const fr_t slot = lazy29_to_slot(l);
                 // X: the S-box on the lazy value, yt_q recoded unreduced, the slot's limbs added to x5's
                 const fr29_t x5 = pow5_lazy29(u);
@@ -411,6 +412,24 @@ int hc_mfma_finish_bytes(const int32_t* sums, size_t n, int wide, int64_t* cols,
         int64_t* col = cols + 8 * s;
         if (wide) mfma_word_cols_of_sums<true>(S, col); else mfma_word_cols_of_sums<false>(S, col);
         const fr_t d = mfma_finish_bytes(col, qh + s, carry + s); memcpy(digits + 32 * s, d.v, 32);
+    }
+    return 0;
+}
+// The word-column finish to nine limbs (mfma_word_cols_mad / mfma_finish_words: the fused full-round rows, the H_q rows, the last block's lane rows): n cases
+// of 32 digit sums and, with c != nullptr, nine limbs of a stored constant each -> the eight word columns as the lane pair folds them (the constant's words in),
+// the quotient estimate, the carry out of word 7, the nine limbs of W == V + c (mod r) and (canon != nullptr) the canonical value by the two conditional
+// subtractions of mfma_finish_words_canonical, as the products that end canonical take it.  -1: a sum outside |S_c| <= 23 * 32 * 128 * 128 or a limb of c
+// outside a stored value's.
+int hc_mfma_finish_words(const int32_t* sums, const uint32_t* c, size_t n, int64_t* cols, int32_t* qh, int64_t* carry, uint32_t* limbs, uint64_t* canon) {
+    const int32_t lim = 23 * 32 * 128 * 128;
+    for (size_t s = 0; s < n; ++s) {
+        const int32_t* S = sums + 32 * s; const uint32_t* cs = c ? c + 9 * s : nullptr;
+        for (int i = 0; i < 32; ++i) if (S[i] > lim || S[i] < -lim) return -1;
+        if (cs) for (int i = 0; i < 9; ++i) if (cs[i] >= (i < 8 ? 1u << 29 : 1u << 23)) return -1;
+        int64_t* col = cols + 8 * s;
+        mfma_word_cols_mad_of_sums(S, col, cs);
+        mfma_finish_words(col, limbs + 9 * s, qh + s, carry + s);
+        if (canon) st4(canon + 4 * s, mfma_finish_words_canonical(col));
     }
     return 0;
 }

@@ -3,8 +3,8 @@
 // in limb form and the lazy chain of the 8-round blocks (slot layout, limb adds, unreduced recode).
 // poseidon_pair.hpp includes it for the t = 17 wave-pair kernels (exchange and tile handling stay there); hostcheck.cpp and tools/mfma_finish_check.cpp
 // run the same statements on the CPU against the L*U rows and against big integers (tests/test_hostcheck.py,
-// tests/test_full_round_residue_tables_host.py, tests/test_limb_handover_host.py, tests/test_lazy_residue_host.py, tests/test_byte_finish_host.py).  The host-only part at the end: the row-order entry of the fold
-// (mfma_cols_of_sums) and the 128-bit column census of the S-box (Lazy29Wide).
+// tests/test_full_round_residue_tables_host.py, tests/test_limb_handover_host.py, tests/test_lazy_residue_host.py, tests/test_byte_finish_host.py, tests/test_word_fold_host.py).  The host-only part at the end: the row-order entry of the fold
+// (mfma_cols_of_sums, mfma_word_cols_of_sums, mfma_word_cols_mad_of_sums) and the 128-bit column census of the S-box (Lazy29Wide).
 #pragma once
 #include "fr.hpp"
 #include "fr29.hpp"
@@ -74,13 +74,13 @@ FR_HD fr_t mfma_finish_cols(int64_t* col) {
     return z;
 }
 // The S-box on the finish's nine limbs, with no canonical value in between: u = W + c limb by limb (c = the next round's constant as nine 29-bit limbs
-// of its stored value, PoseidonDev::rc_full29), then x^5 as in fr_pow5_r29.  Bounds, for ANY u of value below 4r whose limbs are below 2^30 (here W < 3r
-// with limbs below 2^29 and c < r with limbs below 2^29):
+// of its stored value, PoseidonDev::rc_full29), then x^5 as in fr_pow5_r29.  Bounds, for ANY u of value below 4.25 r whose limbs are below 2^30 (here
+// W < 3 r + 2^146 with limbs below 2^29, the wider of the two finishes' ranges (mfma_finish_words below), and c < r with limbs below 2^29: u < 4.0001 r):
 //   u^2     a doubled limb is below 2^31 (fits the 32-bit operand), a doubled cross product below 2^61, a square below 2^60; the fullest column (8) holds
 //           four doubled cross products and one square: 4 * 2^61 + 2^60 = 2^63 + 2^60, and the reduction adds at most 6 * 2^58 (five non-zero limbs of r
-//           above limb 0, the carry): below 2^63 + 2^60 + 2^60.6 < 2^64.  The Montgomery step leaves x2 < u^2 / 2^261 + r < (16 / 128 + 1) r < 1.13 r.
-//   x2^2    limbs below 2^29: the bounds of fr29.hpp; x4 < 1.01 r.
-//   u * x4  nine products below 2^30 * 2^29 per column: 9 * 2^59 + 6 * 2^58 < 2^63; x5 < (4 * 1.01 / 128 + 1) r < 1.04 r: fr29_pack_reduce's ONE conditional
+//           above limb 0, the carry): below 2^63 + 2^60 + 2^60.6 < 2^64.  The Montgomery step leaves x2 < u^2 / 2^261 + r < (4.25^2 / 128 + 1) r < 1.15 r.
+//   x2^2    limbs below 2^29: the bounds of fr29.hpp; x4 < (1.15^2 / 128 + 1) r < 1.02 r.
+//   u * x4  nine products below 2^30 * 2^29 per column: 9 * 2^59 + 6 * 2^58 < 2^63; x5 < (4.25 * 1.02 / 128 + 1) r < 1.04 r: fr29_pack_reduce's ONE conditional
 //           subtraction returns the canonical x^5 / 2^20 of fr_pow5_r29.
 FR_HD fr29_t pow5_lazy29(const fr29_t& u) {                  // the three products alone: x5 as nine limbs, below 1.04 r, limbs below 2^29, the top limb below 2^23
     const fr29_t x2 = fr29_sqr_mont<PF>(u), x4 = fr29_sqr_mont<PF>(x2);
@@ -109,7 +109,9 @@ FR_HD fr_t sbox_lazy29(const uint32_t* l, const uint32_t* __restrict__ c) { retu
 //   q1          floor((V + c) / 2^254) - 1, |q1| < 2^18.02 + 1;
 //   W'          V + c - q1 r = ((V + c) mod 2^254) + 2^254 - q1 t: the range of W above, (2^254 - 2^144.02, 2^255 + 2^144.02), below 2.0001 r and below 2^256,
 //               limbs 0..7 below 2^29, the top limb below 2^24.
-// mfma_finish_limbs is the finish as it stands: only the columns it starts from differ.
+// mfma_finish_limbs is the finish as it stands: only the columns it starts from differ.  (The kernels have since moved H_q to WORD columns — mfma_finish_words
+// below, the constant's eight words in front of the quotient, W' below 3 r; this limb-column form stays for the host checks and as the comparison in
+// tools/partial_block8.hip.  The slot and X's side are unchanged.)
 // The mailbox slot (32 bytes) holds W' as its nine limbs: limb k in bits 0..28 of word k, bits 3k..3k+2 of the top limb (24 bits = 8 x 3) in bits 29..31 of
 // word k.  Two instructions per word on either side (bit-field extract + shift-or; and + shift-or), against a pack (8 words of two or three shift-ors) and an
 // unpack (nine limbs of two shifts, an or and a mask) for the packed 256-bit form: the cheaper of the two layouts.
@@ -129,8 +131,9 @@ FR_HD fr_t lazy29_to_slot(const uint32_t* l) {               // limbs 0..7 below
     for (int k = 0; k < 8; ++k) z.v[k] = l[k] | (((l[8] >> (3 * k)) & 7u) << 29);
     return z;
 }
-// X's side of the hand-over: u = x5 + W' limb by limb.  x5 < 1.04 r (limbs below 2^29, top below 2^23) and W' < 2.0001 r: u < 3.05 r with limbs below 2^30,
-// inside pow5_lazy29's contract (below 4 r, limbs below 2^30); then x2 < (3.05^2 / 128 + 1) r < 1.08 r, x4 < 1.01 r, x5 < (3.05 * 1.01 / 128 + 1) r < 1.03 r.
+// X's side of the hand-over: u = x5 + W' limb by limb.  x5 < 1.04 r (limbs below 2^29, top below 2^23) and W' < 3.0001 r from the word-column finish
+// (mfma_finish_words; 2.0001 r from mfma_finish_limbs): u < 4.05 r with limbs below 2^30, inside pow5_lazy29's contract (below 4.25 r, limbs below 2^30);
+// then x2 < (4.05^2 / 128 + 1) r < 1.13 r, x4 < 1.01 r, x5 < (4.05 * 1.01 / 128 + 1) r < 1.04 r.
 FR_HD fr29_t lazy29_add_slot(const fr29_t& x5, const fr_t& slot) {
     fr29_t u; uint32_t top = 0;
 #pragma unroll
@@ -201,6 +204,79 @@ FR_HD fr_t mfma_finish_bytes(const int64_t* col, int32_t* qh_out = nullptr, int6
     if (carry_out) *carry_out = carry;
     return z;
 }
+// ---- rows that end as nine limbs for an S-box, from WORD columns (poseidon_pair.hpp mfma_post_limbs: the fused full-round rows, the H_q rows, the last
+// block's lane rows): folded where the sums sit like the byte-domain rows, so only finished columns cross the lane pair, and finished in one pass.
+//   fold        word column k = ((S_{4k+3} 2^24 + S_{4k+2} 2^16) + S_{4k+1} 2^8) + S_{4k} as a chain of 64-bit multiply-adds (v_mad_i64_i32 on the device).  The three
+//               multipliers are made opaque to the device compiler (an empty asm on scalar registers); with plain constants it rewrites the products into
+//               sign extensions and 64-bit shift-adds, which is what mfma_word_cols<true> compiles to.  Rows of up to 16 + 7 K-steps:
+//               |S_c| <= 23 * 32 * 128 * 128 = 12 058 624 < 2^23.53, |col| <= 16 843 009 |S| < 2^47.6.
+//   constant    (the H_q rows) the eight words of a stored constant c < r are added to the columns in front of the quotient: |col| < 2^47.6 + 2^32.
+//   quotient    x = col_7 + (col_6 >> 32), q^ = (x + 2) >> 30 as in mfma_finish_bytes: (V + c) / 2^224 = x + f with f in (-2^-16, 1 + 2^-16), so q <= q^ <= q + 1
+//               for q = floor((V + c) / 2^254); q1 = q^ - 2 in {q - 2, q - 1}, |q1| < 2^18.6.
+//   one pass    t = col_k + carry - q1 t_k (k < 4: r = 2^254 + t, t_k its words) - q1 2^30 (k = 7); word_k = lo32(t), carry = t >> 32.  |q1 t_k| < 2^50.6,
+//               |q1 2^30| < 2^48.6, |carry| < 2^19.6: every t inside an int64.
+//   W           V + c - q1 r = ((V + c) mod 2^254) - q t + (q - q1) r with q - q1 in {1, 2} and |q t| < 2^145: W in (r - 2^146, 3 r + 2^146), inside [0, 2^256)
+//               (3 r + 2^146 = 3 * 2^254 + 3 t + 2^146 < 2^256): no carry leaves word 7 and the eight words are W itself.  fr29_unpack: limbs 0..7 below 2^29, the
+//               top limb (bits 232..255) below 2^24.  One r wider at the top than mfma_finish_limbs' range; the consumers' bounds with it:
+//   S-box       a fused row adds a constant below r: u < 4 r + 2^146 < 4.0001 r; the chain forms u = x5 + W' < 1.04 r + 3.0001 r < 4.05 r; limbs below 2^30
+//               either way.  pow5_lazy29's column bounds depend on the limb sizes alone (unchanged); its values for ANY u below 4.25 r:
+//               x2 < (4.25^2 / 128 + 1) r < 1.15 r, x4 < (1.15^2 / 128 + 1) r < 1.02 r, x5 < (4.25 * 1.02 / 128 + 1) r < 1.04 r: the packed x5's top byte is still
+//               at most 0x42 (recode_lazy29) and fr29_pack_reduce's one conditional subtraction still returns the canonical value.
+// qh / carry_out (host checks): the quotient estimate and the carry out of word 7 (zero by the range above).
+template <class V> FR_HD void mfma_word_cols_mad(const V& a, int64_t* wc) {      // one tile's 16 sums in a lane -> its four word columns
+    int32_t m8 = 1 << 8, m16 = 1 << 16, m24 = 1 << 24;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(m8), "+s"(m16), "+s"(m24));
+#endif
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        wc[q] = (((int64_t)a[4 * q + 3] * m24 + (int64_t)a[4 * q + 2] * m16) + (int64_t)a[4 * q + 1] * m8) + (int64_t)a[4 * q];
+}
+FR_HD void mfma_words_add_c29(int64_t* col, const uint32_t* __restrict__ c_) {      // col += the eight words of a stored constant given as its nine 29-bit limbs
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) uint32_t* cptr_t;      // wave-uniform: the pack runs on the scalar unit
+    cptr_t c = (cptr_t)c_;
+#else
+    const uint32_t* c = c_;
+#endif
+    uint32_t l[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) l[i] = c[i];
+    const fr_t w = fr29_pack(l);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) col[k] += (int64_t)w.v[k];
+}
+FR_HD fr_t mfma_finish_words_packed(const int64_t* col, int32_t* qh_out = nullptr, int64_t* carry_out = nullptr) {      // -> the eight words of W
+    const int64_t x = col[7] + (col[6] >> 32);
+    const int32_t qh = (int32_t)((x + 2) >> 30), q1 = qh - 2;
+    fr_t z; int64_t carry = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        int64_t t = col[k] + carry;
+        if (k < 4) t -= (int64_t)q1 * (int64_t)PF::P(k);
+        if (k == 7) t -= (int64_t)q1 * ((int64_t)1 << 30);
+        z.v[k] = (uint32_t)t; carry = t >> 32;
+    }
+    if (qh_out) *qh_out = qh;
+    if (carry_out) *carry_out = carry;
+    return z;
+}
+FR_HD void mfma_finish_words(const int64_t* col, uint32_t* l, int32_t* qh_out = nullptr, int64_t* carry_out = nullptr) {
+    const fr29_t u = fr29_unpack(mfma_finish_words_packed(col, qh_out, carry_out));
+#pragma unroll
+    for (int i = 0; i < 9; ++i) l[i] = u.l[i];
+}
+// the same -> the canonical representative (the products that end canonical: one fold and exchange serves both ends of a row).  The range above is the coarse
+// one; the estimate's two outcomes taken apart give W below 3 r, so TWO conditional subtractions suffice, as in mfma_finish_cols:
+//   q^ = q + 1   W = (V mod 2^254) - q t + r < 2^254 + 2^145 + r < 3 r;
+//   q^ = q       (x + 2) >> 30 = q means x <= (q + 1) 2^30 - 3, so V / 2^224 = x + f < (q + 1) 2^30 - 2 + 2^-16 and V mod 2^254 < 2^254 - 2^224 (2 - 2^-16);
+//                W = (V mod 2^254) - q t + 2 r < 2^254 - 2^225 + 2^209 + 2^145 + 2 r < 3 r.
+// (At the other end W is above 2 r - 2^226: q^ = q + 1 needs x >= (q + 1) 2^30 - 2, i.e. V mod 2^254 > 2^254 - 2^224 (2 + 2^-16).)
+FR_HD fr_t mfma_finish_words_canonical(const int64_t* col) {
+    fr_t z = mfma_finish_words_packed(col);
+    fr_cond_sub<PF>(z.v, 0u); fr_cond_sub<PF>(z.v, 0u);
+    return z;
+}
 // c * u for a multiplier-table entry c (nine limbs of c R' mod r, fr29_const_from) and a lazy u (limbs below 2^30, below 4 r): a column holds nine products
 // below 2^59 and the reduction's 6 * 2^58: below 2^63; the result is below (4 / 128 + 1) r < 1.04 r with limbs below 2^29.
 FR_HD fr29_t fr29_mul_c29(const uint32_t* __restrict__ c, const fr29_t& u) { fr_wide29 w; fr_wide29_zero(w); fr_wide29_mac(w, c, u); fr29_t r; fr_wide29_mont<PF>(w, r.l); return r; }
@@ -224,6 +300,17 @@ template <bool WIDE = false> inline void mfma_word_cols_of_sums(const int32_t* S
         mfma_word_cols<WIDE>(a, wc);
         for (int q = 0; q < 4; ++q) col[2 * q + h] = wc[q];
     }
+}
+// 32 digit sums in ROW order -> the eight word columns of the word-column finish to limbs (mfma_finish_words), in the lanes' own order: each half folds its 16
+// registers by the multiply-add chain, the finished columns are exchanged, then a constant's words (c29: its nine limbs; nullptr: none) are added
+inline void mfma_word_cols_mad_of_sums(const int32_t* S, int64_t* col, const uint32_t* c29 = nullptr) {
+    for (int h = 0; h < 2; ++h) {
+        int32_t a[16]; int64_t wc[4];
+        for (int reg = 0; reg < 16; ++reg) a[reg] = S[(reg & 3) + 8 * (reg >> 2) + 4 * h];
+        mfma_word_cols_mad(a, wc);
+        for (int q = 0; q < 4; ++q) col[2 * q + h] = wc[q];
+    }
+    if (c29) mfma_words_add_c29(col, c29);
 }
 // sbox_lazy29's three steps with 128-bit columns, statement by statement after fr29_sqr_mont / fr29_mul_mont / fr_wide29_mont, recording the largest value any
 // column holds when it is consumed (a column only grows until then): what the 64-bit columns of the kernels have to hold.  Returns x5's limbs.

@@ -112,10 +112,12 @@ __device__ __forceinline__ void pair_sbox_full(const PairState& s, const fr_t* r
 //   * D layout: lane l, register r = row (r & 3) + 8 (r >> 2) + 4 (l >> 5) of column l & 31: a sponge's 32 digit sums sit in lanes l and l + 32.
 //     v_permlane32_swap(tile of sponges 0..31, tile of sponges 32..63) hands the lower lane the upper lane's rows of ITS sponge and vice versa, so
 //     that afterwards lane l owns sponge l (the kernels' lane <-> sponge map) with the rows in a lane-uniform order.
-//   * fold and finish: mfma_digits.hpp (mfma_fold_rows, mfma_finish_limbs / mfma_finish_cols, sbox_lazy29), the statements the host checks run, with the
-//     bound of every intermediate; they hold for any |digit sum| < 2^24, here |S_c| <= 17 * 32 * 128 * 128 = 8 912 896.
-// One row pipeline serves this product and the two of the 8-round blocks: zeroed tile -> MFMAs -> mfma_post_cols -> a canonical finish (mfma_post) or the
-// limb-form hand-over to the next S-box (pair_sto_sbox29).
+//   * fold and finish: mfma_digits.hpp, the statements the host checks run, with the bound of every intermediate.  This product's rows and the rows of the
+//     8-round blocks that end as limbs: word columns folded in the lane that holds the sums, exchanged afterwards (mfma_word_cols_mad, mfma_finish_words,
+//     sbox_lazy29; mfma_post_words / mfma_post_limbs below), |S_c| <= 17 * 32 * 128 * 128 = 8 912 896 here.  The older pipeline — exchange of all 32 sums, nine
+//     limb columns (mfma_fold_rows, mfma_finish_limbs / mfma_finish_cols; any |digit sum| < 2^24) — serves the rows that end canonical elsewhere (mfma_post).
+// One row pipeline serves this product and the two of the 8-round blocks: zeroed tile -> MFMAs -> fold, exchange -> a canonical finish or the limb-form
+// hand-over to the next S-box (pair_sto_sbox29).
 typedef int mfma_v4i __attribute__((ext_vector_type(4)));
 typedef int mfma_v16i __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ void mfma_zero_tile(mfma_v16i (&acc)[2]) {
@@ -125,8 +127,8 @@ __device__ __forceinline__ void mfma_zero_tile(mfma_v16i (&acc)[2]) {
         for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
 }
 // exchange and fold: the two accumulator tiles of a row -> the nine columns of the lane's sponge
-// c29 != nullptr: the columns start from that constant's nine limbs.  No caller passes one (blk8_round_y adds its constant after the fold); the branch stays
-// because without it k_hash_ds2<17, DsBatchStream, true> spills 2 VGPRs (mfma_digits.hpp).
+// c29 != nullptr: the columns start from that constant's nine limbs.  No caller passes one (blk8_round_y takes its constant into word columns now,
+// mfma_post_limbs); the branch stays as the resource table was taken with it (without it k_hash_ds2<17, DsBatchStream, true> once spilled 2 VGPRs: DESIGN 7a).
 __device__ __forceinline__ void mfma_post_cols(const mfma_v16i (&acc)[2], int64_t* col, const uint32_t* c29 = nullptr) {
     mfma_v16i lo, hi;
 #pragma unroll
@@ -161,7 +163,26 @@ __device__ __forceinline__ fr_t mfma_post_bytes(const mfma_v16i (&acc)[2]) {
     }
     return mfma_finish_bytes(col);
 }
-// The limb-form hand-over of a row: its nine finish limbs l (mfma_finish_limbs) go straight through the next full round's S-box (rc29: that round's constant
+// fold, exchange, word-column finish: -> nine limbs of some W == V (+ c) (mod r) for an S-box (mfma_digits.hpp mfma_word_cols_mad, mfma_finish_words: W below
+// 3 r + 2^146, limbs 0..7 below 2^29, the top limb below 2^24).  The same exchange as mfma_post_bytes — four finished 64-bit columns per tile, 8 swaps — for rows
+// of up to 16 + 7 K-steps.  c29 != nullptr: a stored constant's nine limbs; its eight words enter the columns in front of the quotient.
+__device__ __forceinline__ void mfma_post_words(const mfma_v16i (&acc)[2], int64_t* col, const uint32_t* c29 = nullptr) {
+    int64_t c0[4], c1[4];
+    mfma_word_cols_mad(acc[0], c0); mfma_word_cols_mad(acc[1], c1);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)(uint64_t)c0[q], (unsigned)(uint64_t)c1[q], false, false);
+        const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)((uint64_t)c0[q] >> 32), (unsigned)((uint64_t)c1[q] >> 32), false, false);
+        col[2 * q] = (int64_t)((uint64_t)lo[0] | ((uint64_t)hi[0] << 32)); col[2 * q + 1] = (int64_t)((uint64_t)lo[1] | ((uint64_t)hi[1] << 32));
+    }
+    if (c29) mfma_words_add_c29(col, c29);
+}
+__device__ __forceinline__ void mfma_post_limbs(const mfma_v16i (&acc)[2], uint32_t* l, const uint32_t* c29 = nullptr) {
+    int64_t col[8];
+    mfma_post_words(acc, col, c29);
+    mfma_finish_words(col, l);
+}
+// The limb-form hand-over of a row: its nine finish limbs l (mfma_finish_words) go straight through the next full round's S-box (rc29: that round's constant
 // for element j, nine limbs) and into slot j as the next product's operand (recoded; canonical, not recoded, in front of the squeeze round).  No canonical value
 // in between.  The finish itself stays at the two call sites: taken in here as well, k_node16_pair<true> holds one VGPR more than before the merge (245).
 __device__ __forceinline__ void pair_sto_sbox29(const PairState& s, int j, const uint32_t* l, const uint32_t* rc29, bool recode) {
@@ -192,10 +213,11 @@ __device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const voi
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
         }
-        int64_t col[9];
-        mfma_post_cols(acc, col);
-        if (rc29) { uint32_t l[9]; mfma_finish_limbs(col, l); pair_sto_sbox29(s, i, l, c29(rc29, i), recode); }
-        else s.sto(i, mfma_finish_cols(col));
+        // one fold and exchange in front of both ends: with the canonical end on its own path (mfma_post) the FUSE kernels spill
+        int64_t col[8];
+        mfma_post_words(acc, col);
+        if (rc29) { uint32_t l[9]; mfma_finish_words(col, l); pair_sto_sbox29(s, i, l, c29(rc29, i), recode); }
+        else s.sto(i, mfma_finish_words_canonical(col));
     }
     __syncthreads();
 }
@@ -291,7 +313,7 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
 #pragma unroll
         for (int p = 0; p <= Q; ++p) g[p] = (Tb.gfrag + (size_t)((Q + 1) * Q / 2 + p) * 64)[lane];
     }
-    { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); { int64_t cc[9]; mfma_cols_set(cc, c29(Tb.rc29, Q)); _Pragma("unroll") for (int k = 0; k < 9; ++k) col[k] += cc[k]; } mfma_finish_limbs(col, l); s.sto(Blk8Cfg::hmail(Q), lazy29_to_slot(l)); }
+    { uint32_t l[9]; mfma_post_limbs(acc, l, c29(Tb.rc29, Q)); s.sto(Blk8Cfg::hmail(Q), lazy29_to_slot(l)); }
     __syncthreads();                                       // barrier_Q: y_Q is posted
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
@@ -323,7 +345,7 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
 #pragma unroll
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
         // slot j is read by this wave alone, before this write
-        if (rc29_next) { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); mfma_finish_limbs(col, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
+        if (rc29_next) { uint32_t l[9]; mfma_post_limbs(acc, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
         else if (LAZY && !last) s.sto(j, mfma_post_bytes(acc));
         else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }      // between two blocks: the signed residue's digits, no canonical value
     }

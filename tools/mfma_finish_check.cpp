@@ -1,7 +1,7 @@
 // tools/mfma_finish_check.cpp — stand-alone host check (its own main, no GPU, no Python) of the residue-table form of the t = 17 full rounds, of
 // the lane product of the 8-round partial blocks with the base lane in the tile (finish with base), and of the blocks' H rows of up to 16 + 7 K-steps:
 // the fragment tables (host_util.hpp mfma_frags), the fold + finishing step and the limb-form hand-over to the next S-box (mfma_digits.hpp, the
-// statements the kernels compile: finish to limbs, S-box on lazy limbs, the lazy chain's finish with a constant, slot and chain step, the signed-residue lanes through nine limbs and by the byte-domain finish),
+// statements the kernels compile: finish to limbs, S-box on lazy limbs, the lazy chain's finish with a constant, slot and chain step, the signed-residue lanes through nine limbs and by the byte-domain finish, the word-column finish to nine limbs),
 // against the portable field code.  Meant for a
 // sanitizer build; tools/mfma_finish_sanitize.sh builds it with AddressSanitizer + UBSan and runs it:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -I stark_mlwe_amd/csrc tools/mfma_finish_check.cpp -o tools/bin/mfma_finish_check
@@ -226,6 +226,25 @@ int main() {
         };
         for (size_t ci = 0; ci < cases.size(); ++ci) check_bytes(cases[ci], true, ci);
         for (size_t ci = 0; ci < narrow.size(); ++ci) { check_bytes(narrow[ci], false, ci); check_bytes(narrow[ci], true, ci); }
+    }
+    // ---- the word-column finish to nine limbs (mfma_word_cols_mad / mfma_words_add_c29 / mfma_finish_words: what the fused full-round rows, the H_q rows and
+    // the last block's lane rows run) on every case above, with no constant and with 0 / 1 / r - 1 / a scaled round constant in the columns: no carry out of
+    // word 7, limbs 0..7 below 2^29 and the top limb below 2^24, the value inside (r - 2^147, 3 r + 2^147) (top limb in [2^22 - 1, 3 * 2^22]; the cases reach
+    // |S_c| = 2^24 - 1, beyond the 23-K-step rows), the canonical form equal to the finishing step's (+ the constant), also by the two conditional
+    // subtractions of mfma_finish_words_canonical, and the S-box on the limbs plus a round constant equal to fr_pow5_r29 of the canonical sum.
+    for (size_t ci = 0; ci < cases.size(); ++ci) for (int k = -1; k < (ci < ncraft ? 4 : 1); ++k) {
+        const int kk = k < 0 ? -1 : ci < ncraft ? k : (int)(ci & 3);
+        const fr_t cst = kk <= 0 ? host::h_zero() : kk == 1 ? one : kk == 2 ? rm1 : kc.rc_partial_scaled[ci % 64];
+        const fr29_t c29l = fr29_unpack(cst);
+        int64_t col[8]; uint32_t l[9]; int32_t qh; int64_t carry;
+        mfma_word_cols_mad_of_sums(cases[ci].data(), col, kk < 0 ? nullptr : c29l.l); mfma_finish_words(col, l, &qh, &carry);
+        bool ok = carry == 0 && qh < (1 << 20) && qh > -(1 << 20) && l[8] >= (1u << 22) - 1 && l[8] <= 3u * (1u << 22);
+        for (int i = 0; i < 8; ++i) ok = ok && l[i] <= FR_M29;
+        fr_t z = fr29_pack_reduce<PF>(l); fr_cond_sub<PF>(z.v, 0u); fr_cond_sub<PF>(z.v, 0u);
+        const fr_t canon = fr_add<PF>(finish(cases[ci].data()), cst);
+        ++n; if (!ok || !fr_eq(z, canon) || !fr_eq(mfma_finish_words_canonical(col), canon)) { if (bad < 5) fprintf(stderr, "word-column finish: case %zu constant %d\n", ci, kk); ++bad; }
+        const size_t idx = (ci * 7 + (size_t)(kk + 1) * 17) % (8 * 17);
+        ++n; if (!fr_eq(sbox_lazy29(l, &kc.rc_full29[9 * idx]), fr_pow5_r29<PF>(fr_add<PF>(canon, kc.rc_full[idx])))) { if (bad < 5) fprintf(stderr, "S-box on word-finish limbs: case %zu constant %zu\n", ci, idx); ++bad; }
     }
     printf("{\"check\": \"residue tables and finishing step against the portable field code\", \"cases\": %ld, \"mismatches\": %ld}\n", n, bad);
     return bad ? 1 : 0;

@@ -1,4 +1,4 @@
-// tools/partial_block8.hip — PROTOTYPE, not product code: 8 partial rounds of the t = 17 Poseidon permutation for 64 sponges per wave pair, in six forms.
+// tools/partial_block8.hip — PROTOTYPE, not product code: 8 partial rounds of the t = 17 Poseidon permutation for 64 sponges per wave pair, in several forms.
 //   form 4      : the shipped block-of-4 code, twice — pair_permute<17> of poseidon_pair.hpp itself, run with rf = 0 and rp = 8 (no full rounds);
 //   former 8    : one block of 8 rounds whose E-product (8 rows x 16 lanes) and lane product (16 rows x 8 S-box outputs, plus the base lane as a ninth
 //                 K-step) run on the matrix cores through residue tables, the 28 Gamma terms of the block on the vector ALU (namespace former below: the
@@ -16,6 +16,9 @@
 //   between two blocks: form 8 as a block that is NOT the permutation's last, its lanes left as the digits of their signed residue — the product's byte-domain
 //                 finish (mfma_post_bytes: word columns folded per lane, 8 swaps, one pass over eight words) beside the finish through nine 29-bit limbs
 //                 (namespace limbfinish below: the product's form until the byte finish; kept here as the comparison).  The host decodes the digits.
+//   word columns: the rows that end as nine limbs — wave Y's H_q rows and, in a permutation's last block, the lane rows handed to the next S-box — by the product's
+//                 mfma_post_limbs (multiply-add fold per lane, 8 swaps, one pass over eight words) beside the finish through nine limb columns (namespace limbrows
+//                 below: the product's form until then; kept here as the comparison), as a block between two blocks and as a permutation's last block.
 //   LDS stays at PairCfg<17>::lds_bytes() = 40 KiB.  The host checks every form against the sparse rounds in the portable field code (0 and r - 1 among
 //   the inputs) and requires zero mismatches; then the forms are timed alternately in one process, the state reloaded from memory for every repetition.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I stark_mlwe_amd/csrc tools/partial_block8.hip -o tools/bin/partial_block8
@@ -360,15 +363,91 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
 }
 }  // namespace limbfinish
 
+// ---- the rows that end as nine limbs finished through NINE 29-BIT COLUMNS, kept here as the comparison: wave Y's H_q rows and the last block's fused lane rows
+// by the exchange of all 32 sums (16 swaps), zeroed columns, mfma_fold_rows, the constant's limbs into the columns, carry pass and mfma_finish_limbs (the
+// product's form until the word-column finish, mfma_post_limbs).  Wave X's rounds and the lane rows between two blocks are the product's.
+namespace limbrows {
+template <int Q>
+__device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs& Tb, mfma_v4i (&b)[8][2], mfma_v4i (&a)[16], mfma_v4i (&g)[7]) {
+    __builtin_amdgcn_sched_barrier(0);
+    const int lane = s.lane;
+    mfma_v16i acc[2];
+    mfma_zero_tile(acc);
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[e], blk8_b_of_slot(s, e + 1, ct), acc[ct], 0, 0, 0);
+    if constexpr (Q > 0) {
+#pragma unroll
+        for (int p = 0; p < Q; ++p)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(g[p], b[p][ct], acc[ct], 0, 0, 0);
+    }
+    if constexpr (Q < 7) {
+        blk8_load_frags16(a, Tb.efrag + (size_t)(Q + 1) * 16 * 64, lane);
+#pragma unroll
+        for (int p = 0; p <= Q; ++p) g[p] = (Tb.gfrag + (size_t)((Q + 1) * Q / 2 + p) * 64)[lane];
+    }
+    { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); { int64_t cc[9]; mfma_cols_set(cc, c29(Tb.rc29, Q)); _Pragma("unroll") for (int k = 0; k < 9; ++k) col[k] += cc[k]; } mfma_finish_limbs(col, l); s.sto(Blk8Cfg::hmail(Q), lazy29_to_slot(l)); }
+    __syncthreads();                                       // barrier_Q: y_Q is posted
+    b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
+}
+template <int NLX>
+__device__ __forceinline__ void lane_rows_fused(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], const uint32_t* rc29_next, bool recode_next) {
+    const int lane = s.lane;
+    const int j0 = s.isY ? NLX + 1 : 1, j1 = s.isY ? 16 : NLX;
+    const mfma_v4i aunit = Tb.unit[lane];
+    mfma_v4i a[8];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(j0 - 1) * 8 + p) * 64)[lane];
+#pragma unroll 1
+    for (int j = j0; j <= j1; ++j) {
+        mfma_v16i acc[2];
+        mfma_zero_tile(acc);
+#pragma unroll
+        for (int p = 0; p < 8; ++p)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], b[p][ct], acc[ct], 0, 0, 0);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(aunit, blk8_b_of_slot(s, j, ct), acc[ct], 0, 0, 0);
+        const int jn = j < j1 ? j + 1 : j1;                // the last row fetches its own fragments again: in bounds, unused
+#pragma unroll
+        for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
+        { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); mfma_finish_limbs(col, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
+    }
+    __syncthreads();
+}
+// rc29_next == nullptr: a block between two blocks (the product's lane rows, byte-domain finish); else the permutation's last block, fused with the next S-box
+template <int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr29_t& u, const uint32_t* rc29_next, const uint32_t* unscale29) {
+    mfma_v4i b[8][2];
+    if (!s.isY) {
+        blk8_round_x<0>(s, Tb, u, b); blk8_round_x<1>(s, Tb, u, b); blk8_round_x<2>(s, Tb, u, b); blk8_round_x<3>(s, Tb, u, b);
+        blk8_round_x<4>(s, Tb, u, b); blk8_round_x<5>(s, Tb, u, b); blk8_round_x<6>(s, Tb, u, b); blk8_round_x<7>(s, Tb, u, b);
+    } else {
+        mfma_v4i a[16], g[7];
+        blk8_load_frags16(a, Tb.efrag, s.lane);
+        limbrows::blk8_round_y<0>(s, Tb, b, a, g); limbrows::blk8_round_y<1>(s, Tb, b, a, g); limbrows::blk8_round_y<2>(s, Tb, b, a, g); limbrows::blk8_round_y<3>(s, Tb, b, a, g);
+        limbrows::blk8_round_y<4>(s, Tb, b, a, g); limbrows::blk8_round_y<5>(s, Tb, b, a, g); limbrows::blk8_round_y<6>(s, Tb, b, a, g); limbrows::blk8_round_y<7>(s, Tb, b, a, g);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (rc29_next) {
+        if (!s.isY) { const fr29_t x = fr29_mul_c29(unscale29, u); pair_sto_sbox29(s, 0, x.l, c29(rc29_next, 0), false); }
+        lane_rows_fused<NLX>(s, Tb, b, rc29_next, false);
+    } else blk8_lane_rows<NLX, true>(s, Tb, b, false);
+}
+}  // namespace limbrows
+
 // The tables of "block rep & blkmask" (always block 0): as in a permutation's loop over its blocks the fragment addresses change from one pass to the
 // next, so the compiler cannot hoist all of them out of the repetition loop (it did, and spilled 200 registers for them).
 // efrag / lfrag / gfrag / rc: the unscaled family (blk8_*, rc_partial); sefrag / slfrag / sgfrag / src: the scaled one (blk8s_*, rc_partial_scaled);
 // unscale8: 1 / lambda_8 as a multiplier-table entry (block 0 ends at round 8; the product's table holds 1 / lambda_rp);
+// zero29: 17 x 9 zero limbs, the constants of the S-box that follows a block run as a permutation's last;
 // src29: lambda_q c_q of rounds 0..7 as nine limbs each and a ninth entry of zeros (the block is followed by no round here: rc_partial_scaled29 of an rp = 8 set)
 struct ProtoTabs { const mfma_v4i* efrag; const mfma_v4i* lfrag; const mfma_v4i* unit; const mfma_v4i* gfrag; const uint32_t* sparse29; const uint32_t* gamma8_29; const fr_t* rc;
-                   const mfma_v4i* sefrag; const mfma_v4i* slfrag; const mfma_v4i* sgfrag; const fr_t* src; const uint32_t* src29; const uint32_t* unscale8; int blkmask; };
+                   const mfma_v4i* sefrag; const mfma_v4i* slfrag; const mfma_v4i* sgfrag; const fr_t* src; const uint32_t* src29; const uint32_t* unscale8; const uint32_t* zero29; int blkmask; };
 
-template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>; YG = -2: unscaled::pair_block8<NLX>; YG = -3: canonical::pair_block8<NLX>; YG = -4 / -5: a block between two blocks (lanes left as signed digits), limbfinish::pair_block8<NLX> / the product's pair_block8<NLX, true> with last = false
+template <int YG, int NLX>                                 // YG > 0: the former form with these shares; YG = 0: the product's pair_block8<NLX>; YG = -1: piped::pair_block8<NLX>; YG = -2: unscaled::pair_block8<NLX>; YG = -3: canonical::pair_block8<NLX>; YG = -4 / -5: a block between two blocks (lanes left as signed digits), limbfinish::pair_block8<NLX> / the product's pair_block8<NLX, true> with last = false; YG = -6: the same with the H_q rows through nine limb columns (limbrows); YG = -7 / -8: the block as a permutation's LAST, every slot ending as fr_pow5_r29 of its element (the next S-box with zero constants, not recoded), limbrows / the product
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_block8(ProtoTabs Tp, const fr_t* __restrict__ X, fr_t* __restrict__ Y, int reps) {
     extern __shared__ uint4 lds[];
     PairState s = pair_setup(lds);
@@ -397,6 +476,14 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
             if (!s.isY) u = lazy29_add_c29(u.l, c29(Tp.src29, 0));
             if constexpr (YG == -5) pair_block8<NLX, true>(s, Tb, u, false); else limbfinish::pair_block8<NLX>(s, Tb, u);
             if (rep == 0 && !s.isY) s0 = fr29_pack_reduce<PF>(fr29_mul_c29(Tp.unscale8, u).l);
+        } else if constexpr (YG == -6 || YG == -7 || YG == -8) {
+            const Blk8Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, c29(Tp.src29, 1)};
+            fr29_t u = fr29_unpack(s0);
+            if (!s.isY) u = lazy29_add_c29(u.l, c29(Tp.src29, 0));
+            if constexpr (YG == -8) pair_block8<NLX, true>(s, Tb, u, true, Tp.zero29, false, Tp.unscale8);
+            else limbrows::pair_block8<NLX>(s, Tb, u, YG == -7 ? Tp.zero29 : nullptr, Tp.unscale8);
+            if constexpr (YG == -6) { if (rep == 0 && !s.isY) s0 = fr29_pack_reduce<PF>(fr29_mul_c29(Tp.unscale8, u).l); }
+            else if (rep == 0 && !s.isY) s0 = s.ld(0);          // the closing barrier of the lane rows published slot 0
         } else {
             const canonical::Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, Tp.src};
             if constexpr (YG == -3) canonical::pair_block8<NLX>(s, Tb, s0, true); else piped::pair_block8<NLX>(s, Tb, s0, true);
@@ -426,7 +513,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
 static fr_t canon(fr_t x) { for (int k = 0; k < 3; ++k) fr_cond_sub<host::PF>(x.v, 0u); return x; }   // form 4 leaves its lanes below 2.7 r (pair_lane_update)
 template <class Tp> static Tp* to_dev(const void* p, size_t bytes) { void* d = nullptr; if (hipMalloc(&d, bytes) != hipSuccess || hipMemcpy(d, p, bytes, hipMemcpyHostToDevice) != hipSuccess) { fprintf(stderr, "device copy failed\n"); exit(1); } return (Tp*)d; }
 
-struct Form { const char* name; void (*launch)(int batches, int reps); bool digits = false; };      // digits: lanes 1..16 come back as signed digits of a residue
+struct Form { const char* name; void (*launch)(int batches, int reps); bool digits = false; bool sbox = false; };      // digits: lanes 1..16 come back as signed digits of a residue; sbox: every element comes back as fr_pow5_r29 of its value
 // 32 signed digits -> the canonical value of sum_b d_b 256^b mod r, through the field code
 static fr_t of_digits(const fr_t& d) {
     const int8_t* b = reinterpret_cast<const int8_t*>(d.v);
@@ -455,6 +542,7 @@ int main() {
     g_tb.sgfrag = to_dev<mfma_v4i>(K.blk8s_gfrag.data(), K.blk8s_gfrag.size()); g_tb.src = to_dev<fr_t>(K.rc_partial_scaled.data(), K.rc_partial_scaled.size() * sizeof(fr_t));
     { std::vector<uint32_t> c29v(K.rc_partial_scaled29.begin(), K.rc_partial_scaled29.begin() + 9 * 9); for (int i = 0; i < 9; ++i) c29v[72 + i] = 0; g_tb.src29 = to_dev<uint32_t>(c29v.data(), c29v.size() * 4); }
     { uint32_t u8[9]; fr29_const_from<host::PF>(fr_inv<host::PF>(K.blk8_lambda[8]), u8); g_tb.unscale8 = to_dev<uint32_t>(u8, sizeof u8); }
+    { const std::vector<uint32_t> z(17 * 9, 0u); g_tb.zero29 = to_dev<uint32_t>(z.data(), z.size() * 4); }
     g_tb.blkmask = 0;
     g_tb.rc = to_dev<fr_t>(K.rc_partial.data(), K.rc_partial.size() * sizeof(fr_t));
     memset(&g_p, 0, sizeof g_p);
@@ -481,7 +569,10 @@ int main() {
         {"block8, Gamma K-steps, chain scaled, lazy residues, NLX=7", launch8<0, 7>},
         {"block8, Gamma K-steps, chain scaled, lazy residues, NLX=9", launch8<0, 9>},
         {"block8 between two blocks, lanes as signed digits through nine 29-bit limbs, NLX=8 (the former product form)", launch8<-4, 8>, true},
-        {"block8 between two blocks, lanes as signed digits by the byte-domain finish, NLX=8", launch8<-5, 8>, true},
+        {"block8 between two blocks, byte-domain lanes, H rows through nine limb columns, NLX=8 (the former product form)", launch8<-6, 8>, true},
+        {"block8 between two blocks, byte-domain lanes, H rows from word columns, NLX=8", launch8<-5, 8>, true},
+        {"block8 as the last block, fused with the next S-box, H and lane rows through nine limb columns, NLX=8 (the former product form)", launch8<-7, 8>, false, true},
+        {"block8 as the last block, fused with the next S-box, H and lane rows from word columns, NLX=8", launch8<-8, 8>, false, true},
     };
     const int nforms = (int)(sizeof forms / sizeof forms[0]);
     // reference: the sparse rounds in the portable field code, sampled batches
@@ -507,7 +598,7 @@ int main() {
         if (hipMemcpy(Y.data(), g_y, Y.size() * sizeof(fr_t), hipMemcpyDeviceToHost) != hipSuccess) return 1;
         long bad = 0;
         for (size_t si = 0; si < sample.size(); ++si) for (int n = 0; n < 64; ++n) for (int e = 0; e < T; ++e)
-            if (!fr_eq(ref[(si * T + e) * 64 + n], (forms[f].digits && e > 0) ? of_digits(Y[((size_t)sample[si] * T + e) * 64 + n]) : canon(Y[((size_t)sample[si] * T + e) * 64 + n]))) { if (bad < 5) fprintf(stderr, "%s: mismatch batch %d sponge %d element %d\n", forms[f].name, sample[si], n, e); ++bad; }
+            if (!fr_eq(forms[f].sbox ? fr_pow5_r29<host::PF>(ref[(si * T + e) * 64 + n]) : ref[(si * T + e) * 64 + n], (forms[f].digits && e > 0) ? of_digits(Y[((size_t)sample[si] * T + e) * 64 + n]) : canon(Y[((size_t)sample[si] * T + e) * 64 + n]))) { if (bad < 5) fprintf(stderr, "%s: mismatch batch %d sponge %d element %d\n", forms[f].name, sample[si], n, e); ++bad; }
         printf("{\"check\": \"8 partial rounds of 64 sponges against the sparse rounds in the portable field code, sampled batches, incl. states of 0 and r-1\", \"form\": \"%s\", \"mismatches\": %ld}\n", forms[f].name, bad);
         if (bad) return 1;
     }
