@@ -204,6 +204,18 @@ int32_t stark_merkle_free(stark_tree_t* t);
 int32_t stark_merkle_build_batch_dev(stark_ctx_t* ctx, stark_params_t* p, size_t arity, size_t batch, const uint64_t* tree_labels /* host, batch */,
                                      const uint64_t* const* leaves /* host array of batch DEVICE pointers */, size_t n, int32_t pairs,
                                      const uint64_t* const* cp /* as leaves; NULL iff !pairs; a NULL entry = zeros */, stark_tree_t** out /* host, batch handles */);
+/* The same of `batch` trees of DIFFERENT lengths: tree i has n[i] >= 1 leaves (one arity, one parameter set, pairs or not for all).  out[i] equals
+ * stark_merkle_build_dev of tree i alone, level by level and byte for byte.  Level v of the call is ONE pooled block, the slices of the trees that
+ * have more than v levels back to back in tree order (a tree of one leaf has its one level and no hash; trees drop out as they reach their root);
+ * level 0 is one launch (a ragged copy, or the pair leaves) and every level above one launch over the trees that still have it, its kernel form
+ * chosen for the launch's total number of hashes.  The handles are ordinary trees that may be freed in any order; the blocks go back to the pool with
+ * the last one.  Stream-ordered with no host synchronisation: n, the labels and the pointer tables may die on return.  batch == 0 returns STARK_OK.
+ * STARK_ERR_INVALID_ARG, before any launch: a null ctx, params, table, n or out; a null leaves[i]; an n[i] == 0; pairs without a cp table; an arity
+ * incompatible with the parameter width; a sum of n above 2^31 - 1.  Arity 1 with some n[i] > 1 is STARK_ERR_UNSUPPORTED.  On any error every out[i]
+ * is NULL and stark_ctx_cached_bytes is what it was. */
+int32_t stark_merkle_build_mixed_batch_dev(stark_ctx_t* ctx, stark_params_t* p, size_t arity, size_t batch, const uint64_t* tree_labels /* host, batch */,
+                                           const uint64_t* const* leaves /* host array of batch DEVICE pointers */, const size_t* n /* host, batch */, int32_t pairs,
+                                           const uint64_t* const* cp /* as leaves; NULL iff !pairs; a NULL entry = zeros */, stark_tree_t** out /* host, batch handles */);
 /* the batch roots with ONE download (MerkleTree::root, merkle/src/lib.rs:195-197) */
 int32_t stark_merkle_roots_batch(stark_tree_t* const* trees, size_t batch, uint64_t* roots /* host, batch x 4 */);
 /* open_union_of_paths (merkle/src/lib.rs:246-315) of every tree: tree i opens idx[idx_off[i] .. idx_off[i+1]) */
@@ -391,6 +403,9 @@ int32_t stark_commitment_commit(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_
 /* MerkleCommitment::commit (commitment/src/lib.rs:80-90) of `batch` DEVICE vectors of n leaves: arity 16, "POSEIDON-T17-X5-SEED", tree_label = ds_tags[i];
  * stark_merkle_build_batch_dev with those parameters (same contract; out[i] equals stark_commitment_commit's tree on vector i). */
 int32_t stark_commitment_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* ds_tags, const uint64_t* const* leaves, size_t n, stark_tree_t** out);
+/* The same of `batch` DEVICE vectors of n[i] leaves each: stark_merkle_build_mixed_batch_dev with those parameters (same contract). */
+int32_t stark_commitment_commit_mixed_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* ds_tags, const uint64_t* const* leaves, const size_t* n /* host, batch */,
+                                                stark_tree_t** out);
 int32_t stark_commitment_verify(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* root4, const size_t* indices, size_t k, const uint64_t* values,
                                 const uint8_t* proof, size_t len, int32_t* accepted);
 /* Mle::evaluate (channel/src/lib.rs:279-295): the multilinear extension of a 2^k table at r (k elements); host pointers. */
@@ -422,6 +437,16 @@ int32_t stark_sumcheck_prove_plain_batch_dev(stark_ctx_t* ctx, size_t batch, con
 /* prove_mf (:1130-1172), same contract, one queries_per_round for the batch; one host synchronisation per round (the query indices). */
 int32_t stark_sumcheck_prove_mf_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k,
                                           const uint64_t* tree_labels, size_t queries_per_round, stark_proof_t** out);
+/* The same of witnesses of DIFFERENT sizes in one pass: witnesses[i] has 2^k[i] elements (k: host array).  out[i] = what
+ * stark_sumcheck_prove_{plain,mf}_dev returns for witness i under k[i] alone, byte for byte.  The rounds are aligned at the end: with
+ * K = max k, instance i joins at step K - k[i], so every step runs one launch of each kind over the instances active in it and the whole batch
+ * takes K steps, not the sum over the distinct sizes; only the commit of the witnesses is ragged (as stark_merkle_build_mixed_batch_dev).
+ * plain: no host round trip inside the loop; mf: one host synchronisation per step, K in all.  k[i] = 0: claim = final = witnesses[i][0].
+ * Errors as the batch forms, plus a null k and any k[i] > 40.  On any error every out[i] is NULL. */
+int32_t stark_sumcheck_prove_plain_mixed_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, const size_t* k /* host, batch */,
+                                                   const uint64_t* tree_labels, stark_proof_t** out);
+int32_t stark_sumcheck_prove_mf_mixed_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, const size_t* k /* host, batch */,
+                                                const uint64_t* tree_labels, size_t queries_per_round, stark_proof_t** out);
 /* verify_plain (:1080-1128) over `batch` proofs at once; accepted[i] == what stark_sumcheck_verify_plain answers for proofs[i] alone, for
  * every input (honest, tampered, truncated, extended, empty, a proof of another k).  Like the single verifier this reads neither k nor the
  * labels: both are carried for signature parity, tree_labels may be NULL, and proofs of different round counts may share a batch.  The

@@ -192,6 +192,22 @@ pub mod merkle {
         ctx.chk(stark_commitment_commit_batch_dev(ctx.raw, leaves.len(), ds_tags.as_ptr(), leaves.as_ptr(), n, raw.as_mut_ptr()));
         raw.into_iter().zip(ds_tags).map(|(raw, &tree_label)| Tree { raw, arity: 16, tree_label }).collect()
     }
+    /// `build_batch_dev` for columns of different lengths: column i has `n[i] >= 1` leaves; one launch per level over the trees that still have
+    /// that level.  Element i == the single build of column i.  Safety: as `build_batch_dev`, pointer i being device memory of `n[i]` elements.
+    pub unsafe fn build_mixed_batch_dev(ctx: &Ctx, leaves: &[*const u64], cp: Option<&[*const u64]>, n: &[usize], arity: usize, tree_labels: &[u64], params: &Params) -> Vec<Tree> {
+        assert!(tree_labels.len() == leaves.len() && n.len() == leaves.len() && cp.map_or(true, |c| c.len() == leaves.len()), "one label, one length (and one cp entry) per tree");
+        let mut raw: Vec<*mut stark_tree_t> = vec![ptr::null_mut(); leaves.len()];
+        ctx.chk(stark_merkle_build_mixed_batch_dev(ctx.raw, params.raw, arity, leaves.len(), tree_labels.as_ptr(), leaves.as_ptr(), n.as_ptr(), cp.is_some() as i32,
+                                                   cp.map_or(ptr::null(), |c| c.as_ptr()), raw.as_mut_ptr()));
+        raw.into_iter().zip(tree_labels).map(|(raw, &tree_label)| Tree { raw, arity, tree_label }).collect()
+    }
+    /// `MerkleCommitment::commit` of many DEVICE vectors of different lengths in one pass; same contract as `build_mixed_batch_dev`.
+    pub unsafe fn commit_mixed_batch_dev(ctx: &Ctx, leaves: &[*const u64], n: &[usize], ds_tags: &[u64]) -> Vec<Tree> {
+        assert!(ds_tags.len() == leaves.len() && n.len() == leaves.len(), "one ds_tag and one length per vector");
+        let mut raw: Vec<*mut stark_tree_t> = vec![ptr::null_mut(); leaves.len()];
+        ctx.chk(stark_commitment_commit_mixed_batch_dev(ctx.raw, leaves.len(), ds_tags.as_ptr(), leaves.as_ptr(), n.as_ptr(), raw.as_mut_ptr()));
+        raw.into_iter().zip(ds_tags).map(|(raw, &tree_label)| Tree { raw, arity: 16, tree_label }).collect()
+    }
     /// The roots of many trees with one download.
     pub fn roots_batch(ctx: &Ctx, trees: &[&Tree]) -> Vec<F> {
         let raw: Vec<*mut stark_tree_t> = trees.iter().map(|t| t.raw).collect();
@@ -541,6 +557,21 @@ pub mod channel {
         assert!(tree_labels.len() == witnesses.len(), "one tree label per witness");
         let mut raw: Vec<*mut stark_proof_t> = vec![ptr::null_mut(); witnesses.len()];
         ctx.chk(stark_sumcheck_prove_mf_batch_dev(ctx.raw(), witnesses.len(), witnesses.as_ptr(), k, tree_labels.as_ptr(), queries_per_round, raw.as_mut_ptr()));
+        raw.into_iter().map(|h| take(ctx, h)).collect()
+    }
+    /// `prove_plain` of witnesses of different sizes in one device pass of max(k) steps: `witnesses[i]` is a DEVICE pointer to 2^k[i] elements;
+    /// element i == `prove_plain(ctx, k[i], tree_labels[i], <witness i>)`, byte for byte.
+    pub unsafe fn prove_plain_mixed_batch_dev(ctx: &Ctx, k: &[usize], tree_labels: &[u64], witnesses: &[*const u64]) -> Vec<Vec<u8>> {
+        assert!(tree_labels.len() == witnesses.len() && k.len() == witnesses.len(), "one tree label and one k per witness");
+        let mut raw: Vec<*mut stark_proof_t> = vec![ptr::null_mut(); witnesses.len()];
+        ctx.chk(stark_sumcheck_prove_plain_mixed_batch_dev(ctx.raw(), witnesses.len(), witnesses.as_ptr(), k.as_ptr(), tree_labels.as_ptr(), raw.as_mut_ptr()));
+        raw.into_iter().map(|h| take(ctx, h)).collect()
+    }
+    /// `prove_mf` of witnesses of different sizes in one device pass; same contract as `prove_plain_mixed_batch_dev`.
+    pub unsafe fn prove_mf_mixed_batch_dev(ctx: &Ctx, k: &[usize], tree_labels: &[u64], queries_per_round: usize, witnesses: &[*const u64]) -> Vec<Vec<u8>> {
+        assert!(tree_labels.len() == witnesses.len() && k.len() == witnesses.len(), "one tree label and one k per witness");
+        let mut raw: Vec<*mut stark_proof_t> = vec![ptr::null_mut(); witnesses.len()];
+        ctx.chk(stark_sumcheck_prove_mf_mixed_batch_dev(ctx.raw(), witnesses.len(), witnesses.as_ptr(), k.as_ptr(), tree_labels.as_ptr(), queries_per_round, raw.as_mut_ptr()));
         raw.into_iter().map(|h| take(ctx, h)).collect()
     }
     /// `verify_mf(vk, proof)` — :1176-1240.

@@ -68,6 +68,7 @@ SIGNATURES = {
     "stark_merkle_open": (i32, [vp, vp, sz, vp, sz, szp]),
     "stark_merkle_free": (i32, [vp]),
     "stark_merkle_build_batch_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, i32, vp, vp]),
+    "stark_merkle_build_mixed_batch_dev": (i32, [vp, vp, sz, sz, vp, vp, vp, i32, vp, vp]),
     "stark_merkle_roots_batch": (i32, [vp, sz, vp]),
     "stark_merkle_open_batch": (i32, [vp, sz, vp, vp, vp]),
     "stark_merkle_verify_many_ds_batch": (i32, [vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -112,6 +113,7 @@ SIGNATURES = {
     "stark_merkle_verify_pairs_ds": (i32, [vp, sz, u64, vp, vp, sz, vp, vp, vp, sz, C.POINTER(i32)]),
     "stark_commitment_commit": (i32, [vp, u64, vp, sz, vpp]),
     "stark_commitment_commit_batch_dev": (i32, [vp, sz, vp, vp, sz, vp]),
+    "stark_commitment_commit_mixed_batch_dev": (i32, [vp, sz, vp, vp, vp, vp]),
     "stark_commitment_verify": (i32, [vp, u64, vp, vp, sz, vp, vp, sz, C.POINTER(i32)]),
     "stark_mle_evaluate": (i32, [vp, vp, sz, vp, vp]),
     "stark_mle_evaluate_dev": (i32, [vp, vp, sz, vp, vp]),
@@ -124,6 +126,8 @@ SIGNATURES = {
     "stark_sumcheck_verify_mf": (i32, [vp, sz, u64, sz, vp, sz, C.POINTER(i32)]),
     "stark_sumcheck_prove_plain_batch_dev": (i32, [vp, sz, vp, sz, vp, vp]),
     "stark_sumcheck_prove_mf_batch_dev": (i32, [vp, sz, vp, sz, vp, sz, vp]),
+    "stark_sumcheck_prove_plain_mixed_batch_dev": (i32, [vp, sz, vp, vp, vp, vp]),
+    "stark_sumcheck_prove_mf_mixed_batch_dev": (i32, [vp, sz, vp, vp, vp, sz, vp]),
     "stark_sumcheck_verify_plain_batch": (i32, [vp, sz, vp, vp, sz, vp, vp]),
     "stark_sumcheck_verify_mf_batch": (i32, [vp, sz, vp, vp, sz, vp, sz, vp]),
     "stark_ali_merge_shard_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, u64, sz, vp, vp]),

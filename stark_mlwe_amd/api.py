@@ -461,6 +461,34 @@ class Context:
         self._chk(self.lib.stark_commitment_commit_batch_dev(self.h, B, _ptr(lab), tab, n, out))
         return [MerkleTree(self, C.c_void_p(out[b]), MerkleChannelCfg(16, None, int(lab[b]))) for b in range(B)]
 
+    def merkle_build_mixed_batch_dev(self, leaves, n, cfg_arity, tree_labels, params, cp=None):
+        """merkle_build_batch_dev for trees of different lengths: `n` is a list, tree i has n[i] >= 1 leaves; one launch per level over the trees
+        that still have that level.  Stream-ordered, no synchronisation.  -> list of MerkleTree, each equal to the single build of that column
+        (stark_merkle_build_mixed_batch_dev)."""
+        B = len(leaves)
+        if len(tree_labels) != B or len(n) != B or (cp is not None and len(cp) != B):
+            raise StarkError(-1, "one tree label, one length (and one cp entry) per tree")
+        tab = (C.c_void_p * max(B, 1))(*[None if x is None else int(x) for x in leaves])
+        ctab = None if cp is None else (C.c_void_p * max(B, 1))(*[None if x is None else int(x) for x in cp])
+        lab = np.ascontiguousarray(tree_labels, dtype=np.uint64)
+        ns = (C.c_size_t * max(B, 1))(*[int(x) for x in n])
+        out = (C.c_void_p * max(B, 1))()
+        self._chk(self.lib.stark_merkle_build_mixed_batch_dev(self.h, params.h, cfg_arity, B, _ptr(lab), tab, ns, 0 if cp is None else 1, ctab, out))
+        return [MerkleTree(self, C.c_void_p(out[b]), MerkleChannelCfg(cfg_arity, params, int(lab[b]))) for b in range(B)]
+
+    def commitment_commit_mixed_batch_dev(self, ds_tags, leaves, n):
+        """MerkleCommitment::commit of each of the DEVICE vectors `leaves` (ints; vector i has n[i] elements) in one pass -> list of MerkleTree
+        (stark_commitment_commit_mixed_batch_dev)."""
+        B = len(leaves)
+        if len(ds_tags) != B or len(n) != B:
+            raise StarkError(-1, "one ds_tag and one length per vector")
+        tab = (C.c_void_p * max(B, 1))(*[None if x is None else int(x) for x in leaves])
+        lab = np.ascontiguousarray(ds_tags, dtype=np.uint64)
+        ns = (C.c_size_t * max(B, 1))(*[int(x) for x in n])
+        out = (C.c_void_p * max(B, 1))()
+        self._chk(self.lib.stark_commitment_commit_mixed_batch_dev(self.h, B, _ptr(lab), tab, ns, out))
+        return [MerkleTree(self, C.c_void_p(out[b]), MerkleChannelCfg(16, None, int(lab[b]))) for b in range(B)]
+
     def merkle_roots_batch(self, trees):
         """The roots of `trees` (MerkleTree, one context) as a (B, 4) array with one download (stark_merkle_roots_batch)."""
         B = len(trees)
@@ -846,16 +874,31 @@ class Context:
         """prove_mf of each witness in one pass (stark_sumcheck_prove_mf_batch_dev) -> list of proof bytes."""
         return self._sumcheck_batch(1, k, tree_labels, queries_per_round, witness_ptrs)
 
+    def prove_plain_mixed_batch_dev(self, ks, tree_labels, witness_ptrs) -> list:
+        """prove_plain of witnesses of different sizes (DEVICE pointers; witness i has 2^ks[i] elements) in one pass of max(ks) steps
+        (stark_sumcheck_prove_plain_mixed_batch_dev) -> list of proof bytes, each equal to prove_plain of that witness alone."""
+        return self._sumcheck_batch(0, list(ks), tree_labels, 0, witness_ptrs)
+
+    def prove_mf_mixed_batch_dev(self, ks, tree_labels, queries_per_round, witness_ptrs) -> list:
+        """prove_mf of witnesses of different sizes in one pass (stark_sumcheck_prove_mf_mixed_batch_dev) -> list of proof bytes."""
+        return self._sumcheck_batch(1, list(ks), tree_labels, queries_per_round, witness_ptrs)
+
     def _sumcheck_batch(self, mf, k, tree_labels, q, witness_ptrs):
         B = len(witness_ptrs)
-        if len(tree_labels) != B:
-            raise StarkError(-1, "one tree label per witness")
+        if len(tree_labels) != B or (isinstance(k, list) and len(k) != B):
+            raise StarkError(-1, "one tree label (and one k) per witness")
         if B == 0:
             return []
         w = (C.c_void_p * B)(*[None if p is None else int(p) for p in witness_ptrs])
         lab = np.ascontiguousarray(tree_labels, dtype=np.uint64)
         out = (C.c_void_p * B)()
-        if mf:
+        if isinstance(k, list):                                            # a k per witness: the mixed-size entry points
+            kk = (C.c_size_t * B)(*[int(x) for x in k])
+            if mf:
+                self._chk(self.lib.stark_sumcheck_prove_mf_mixed_batch_dev(self.h, B, w, kk, _ptr(lab), q, out))
+            else:
+                self._chk(self.lib.stark_sumcheck_prove_plain_mixed_batch_dev(self.h, B, w, kk, _ptr(lab), out))
+        elif mf:
             self._chk(self.lib.stark_sumcheck_prove_mf_batch_dev(self.h, B, w, k, _ptr(lab), q, out))
         else:
             self._chk(self.lib.stark_sumcheck_prove_plain_batch_dev(self.h, B, w, k, _ptr(lab), out))

@@ -288,6 +288,7 @@ int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
+int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsRaggedStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 // The full 160 KiB of LDS per workgroup for the kernels that stage through it: every instantiation the launchers of this file can reach (a DS
 // kernel: once per stream type hash_ds_on takes).  Not listed: the one-wave and wide kernels (k_*_coop, k_hash_ds_wave, k_tr_stream, k_tr_batch), whose
 // coop_lds_bytes / wave_lds_bytes stay below the 64 KiB a kernel may use without the attribute.
@@ -297,7 +298,7 @@ static void ds_attrs() {
     lds_attr((const void*)k_hash_ds<DS>); lds_attr((const void*)k_hash_ds2<17, DS>); lds_attr((const void*)k_hash_ds2<17, DS, true>); lds_attr((const void*)k_hash_ds2<9, DS>); lds_attr((const void*)k_hash_ds_chain<DS>);
 }
 void stark::poseidon_set_attrs() {
-    ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>(); ds_attrs<DsBatchPairPtrStream>();
+    ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>(); ds_attrs<DsBatchPairPtrStream>(); ds_attrs<DsRaggedStream>();
     for (const void* k : {(const void*)k_leaf_pair, (const void*)k_permute_batch, (const void*)k_tr_hash, (const void*)k_hash_stream, (const void*)k_leaf_pair2<false>, (const void*)k_leaf_pair2<true>, (const void*)k_node16_pair<false>, (const void*)k_node16_pair<true>,
                           (const void*)k_tr_hash_chain, (const void*)k_tr_hash_chain_ragged, (const void*)k_tr_hash_ragged, (const void*)k_leaf_pair_chain, (const void*)k_tr_stream_chain, (const void*)k_tr_batch_chain})
         lds_attr(k);
@@ -510,6 +511,39 @@ int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, siz
     for (size_t b = 0; b < batch; ++b) out[b] = trees[b].release();                      // the single success point
     return STARK_OK;
 }
+// The device executor of merkle_build_mixed_batch: the batch executor's blocks and arena, one staged upload for every segment table of the call.
+struct MerkleMixedDevExec : MerkleBatchDevExec {
+    using MerkleBatchDevExec::MerkleBatchDevExec;
+    int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x) { DsRaggedStream::Seg* d = nullptr; STARK_TRY(mem.put(h, &d)); *x = d; return STARK_OK; }
+    int32_t copy_ragged(const DsRaggedStream& D, fr_t* dst) {
+        hipLaunchKernelGGL(k_copy_ragged, dim3((unsigned)((D.n_out + 255) / 256)), dim3(256), 0, ctx->stream, D, dst);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t ragged_level(const DsRaggedStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, p, D, out); }
+};
+int32_t merkle_build_mixed_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, size_t batch, const uint64_t* labels, const uint64_t* const* leaves, const size_t* n, int pairs,
+                                    const uint64_t* const* cp, stark_tree** out) {
+    for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (arity == 0 || host::width_for_arity(arity) != p->dev.t) return ctx->fail(STARK_ERR_INVALID_ARG, "arity incompatible with Poseidon width");   // :155-161
+    size_t sum = 0;
+    for (size_t b = 0; b < batch; ++b) {
+        if (!leaves[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "null leaves entry");
+        if (n[b] == 0) return ctx->fail(STARK_ERR_INVALID_ARG, "no leaves");                                          // merkle/src/lib.rs:148
+        if (n[b] > 0x7fffffffu - sum) return ctx->fail(STARK_ERR_INVALID_ARG, "the sum of n exceeds 2^31 - 1 leaves: one level of the batch is one launch");
+        sum += n[b];
+    }
+    if (arity == 1 && sum > batch) return ctx->fail(STARK_ERR_UNSUPPORTED, "arity 1 with more than one leaf never terminates in the reference");
+    MerkleMixedDevExec X(ctx, p);
+    std::vector<std::vector<size_t>> lens, at; std::vector<fr_t*> base;
+    STARK_TRY(merkle_build_mixed_batch(X, arity, batch, labels, reinterpret_cast<const fr_t* const*>(leaves), n, pairs, reinterpret_cast<const fr_t* const*>(cp), lens, at, base));
+    std::vector<std::unique_ptr<stark_tree>> trees(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        trees[b].reset(new stark_tree(ctx, p, arity, labels[b])); trees[b]->shared = X.blocks;
+        for (size_t v = 0; v < lens[b].size(); ++v) { trees[b]->levels.push_back(base[v] + at[b][v]); trees[b]->lens.push_back(lens[b][v]); }
+    }
+    for (size_t b = 0; b < batch; ++b) out[b] = trees[b].release();                      // the single success point
+    return STARK_OK;
+}
 // THE row gather (declared in ctx.hpp): stark_merkle_gather, stark_merkle_roots_batch, every Merkle open and every DEEP-FRI query phase end here.
 int32_t gather_rows(stark_ctx* ctx, const MerkleGatherList& G, fr_t* out_dev, void* out_host) {
     const size_t k = G.size(), nb = G.base.size();
@@ -549,6 +583,15 @@ int32_t stark_merkle_build_batch_dev(stark_ctx_t* ctx, stark_params_t* p, size_t
     if (!ctx || !p || !tree_labels || !leaves || (pairs && !cp)) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad merkle batch args") : STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
     return merkle_build_batch_on(ctx, p, arity, batch, tree_labels, leaves, n, pairs, pairs ? cp : nullptr, out);
+}
+int32_t stark_merkle_build_mixed_batch_dev(stark_ctx_t* ctx, stark_params_t* p, size_t arity, size_t batch, const uint64_t* tree_labels, const uint64_t* const* leaves, const size_t* n,
+                                           int32_t pairs, const uint64_t* const* cp, stark_tree_t** out) {
+    if (!batch) return STARK_OK;
+    if (!out) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad merkle batch args") : STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (!ctx || !p || !tree_labels || !leaves || !n || (pairs && !cp)) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad merkle batch args") : STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    return merkle_build_mixed_batch_on(ctx, p, arity, batch, tree_labels, leaves, n, pairs, pairs ? cp : nullptr, out);
 }
 int32_t stark_merkle_roots_batch(stark_tree_t* const* trees, size_t batch, uint64_t* roots) {
     if (!batch) return STARK_OK;

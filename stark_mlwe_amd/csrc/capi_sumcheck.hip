@@ -59,13 +59,14 @@ __global__ void __launch_bounds__(256) k_sc_coeffs_batch(const fr_t* const* __re
     const uint64_t b = b0 + blockIdx.y;
     sc_coeffs_block(ptrs ? ptrs[b] : layers + b * len, len / 2, part + 2 * (uint64_t)gridDim.x * b);
 }
-// one block per instance: c01[2b] = sum of its partial c0, c01[2b+1] = of c1; claim != nullptr: claim[b] = 2 c0 + c1 (send_claim, :434-446)
-__global__ void __launch_bounds__(64) k_sc_coeffs_final_batch(const fr_t* __restrict__ part, uint64_t nblocks, fr_t* __restrict__ c01, fr_t* __restrict__ claim) {
+// one block per instance: c01[2b] = sum of its partial c0, c01[2b+1] = of c1; claim != nullptr: claim[b] = 2 c0 + c1 (send_claim, :434-446) for the
+// instances b >= claim_from (the ones whose first round this is; an earlier instance's claim is never written again)
+__global__ void __launch_bounds__(64) k_sc_coeffs_final_batch(const fr_t* __restrict__ part, uint64_t nblocks, fr_t* __restrict__ c01, fr_t* __restrict__ claim, uint64_t claim_from) {
     const uint64_t b = blockIdx.x; const fr_t* p = part + 2 * nblocks * b;
     fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
     for (uint64_t i = threadIdx.x; i < nblocks; i += 64) { c0 = fr_add<PF>(c0, ldg(p + 2 * i)); c1 = fr_add<PF>(c1, ldg(p + 2 * i + 1)); }
     for (int sft = 1; sft < 64; sft <<= 1) { c0 = fr_add<PF>(c0, shfl_xor_fr(c0, sft)); c1 = fr_add<PF>(c1, shfl_xor_fr(c1, sft)); }
-    if (threadIdx.x == 0) { stg(c01 + 2 * b, c0); stg(c01 + 2 * b + 1, c1); if (claim) stg(claim + b, fr_add<PF>(fr_add<PF>(c0, c0), c1)); }
+    if (threadIdx.x == 0) { stg(c01 + 2 * b, c0); stg(c01 + 2 * b + 1, c1); if (claim && b >= claim_from) stg(claim + b, fr_add<PF>(fr_add<PF>(c0, c0), c1)); }
 }
 // next[b len/2 + j] = a + r_b (b - a) with r_b = r[b], the instance's challenge as the transcript kernel left it in device memory
 __global__ void __launch_bounds__(256) k_sc_fold_batch(const fr_t* const* __restrict__ ptrs, const fr_t* __restrict__ layers, uint64_t len, uint64_t b0, const fr_t* __restrict__ r,
@@ -144,12 +145,13 @@ struct ScDevExec : DevArena {
     stark_params* cp; stark_params* tp;
     ScDevExec(stark_ctx* c, stark_params* commit, stark_params* tr) : DevArena(c, true), cp(commit), tp(tr) {}
     int32_t ds_level(const DsBatchStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, cp, D, out); }
-    int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim) {
+    int32_t ragged_level(const DsRaggedStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, cp, D, out); }
+    int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim, size_t claim_from) {
         const uint64_t np = len / 2; const unsigned grid = (unsigned)std::min<uint64_t>((np + 255) / 256, 1024);
         DevBuf part; STARK_HIP(ctx, part.alloc(ctx, (size_t)grid * 2 * B * sizeof(fr_t)));
         for (size_t b0 = 0; b0 < B; b0 += 65535)
             hipLaunchKernelGGL(k_sc_coeffs_batch, dim3(grid, (unsigned)std::min<size_t>(65535, B - b0)), dim3(256), 0, ctx->stream, ptrs, layers, (uint64_t)len, (uint64_t)b0, part.fr());
-        hipLaunchKernelGGL(k_sc_coeffs_final_batch, dim3((unsigned)B), dim3(64), 0, ctx->stream, (const fr_t*)part.fr(), (uint64_t)grid, c01, claim);
+        hipLaunchKernelGGL(k_sc_coeffs_final_batch, dim3((unsigned)B), dim3(64), 0, ctx->stream, (const fr_t*)part.fr(), (uint64_t)grid, c01, claim, (uint64_t)claim_from);
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
     int32_t fold(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, const fr_t* r, fr_t* next) {
@@ -164,11 +166,11 @@ struct ScDevExec : DevArena {
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
 };
-// prove_plain (mf = 0, :1045-1076) / prove_mf (mf = 1, :1130-1172) of `B` device-resident witnesses of 2^k elements: out[b] = the proof of
-// witness b alone.  The single entry points are this with B = 1.
-static int32_t prove_sumcheck_batch_impl(stark_ctx* ctx, int mf, size_t B, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, size_t qpr, stark_proof** out) {
+// prove_plain (mf = 0, :1045-1076) / prove_mf (mf = 1, :1130-1172) of `B` device-resident witnesses, witness b of 2^k[b] elements: out[b] = the
+// proof of witness b alone.  The same-size batch entry points are this with every k[b] equal, the single ones with B = 1.
+static int32_t prove_sumcheck_mixed_impl(stark_ctx* ctx, int mf, size_t B, const uint64_t* const* witnesses, const size_t* k, const uint64_t* tree_labels, size_t qpr, stark_proof** out) {
     for (size_t b = 0; b < B; ++b) out[b] = nullptr;
-    if (k > 40) return ctx->fail(STARK_ERR_INVALID_ARG, "k too large");
+    for (size_t b = 0; b < B; ++b) if (k[b] > 40) return ctx->fail(STARK_ERR_INVALID_ARG, "k too large");
     if (!B) return STARK_OK;
     stark_params *cp = nullptr, *tp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp)); STARK_TRY(ctx_transcript_params(ctx, &tp));
     std::vector<const fr_t*> w(B); for (size_t b = 0; b < B; ++b) w[b] = as_fr(witnesses[b]);
@@ -210,7 +212,7 @@ static int32_t run_sc_verify_batch(stark_ctx* ctx, const ScVerifyPlan& V, int32_
     for (const ScVerifyPlan::Stream& S : V.tr) {
         TrBatchStream T; T.state = (fr_t*)(base + o_state); T.pos = (uint32_t*)(base + o_pos); T.inst = nullptr; T.inst0 = S.inst0; T.n_active = S.n; T.nseg = S.nseg;
         T.el_off = (const uint32_t*)(base + o_toff) + S.seg0; T.idx = (const uint32_t*)(base + o_tidx); T.pool0 = pool; T.pool1 = (const fr_t*)(base + o_con);
-        T.out = pool + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = 1; T.finish_last = 1;
+        T.out = pool + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset_from = 0; T.finish_last = 1;
         for (size_t a0 = 0; a0 < S.n; a0 += 0x7fffffffu / 2) {                       // (a grid's x dimension)
             TrBatchStream Ta = T; Ta.inst0 = S.inst0 + a0; Ta.n_active = std::min<size_t>(S.n - a0, 0x7fffffffu / 2); Ta.el_off = T.el_off + a0 * S.nseg; Ta.out = T.out + a0 * S.nseg;
             STARK_TRY(tr_batch_on(ctx, tp, Ta, Ta.n_active));                            // the form that many instances take
@@ -382,6 +384,16 @@ int32_t stark_commitment_commit_batch_dev(stark_ctx_t* ctx, size_t batch, const 
     stark_params* cp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp));
     return merkle_build_batch_on(ctx, cp, 16, batch, ds_tags, leaves, n, 0, nullptr, out);
 }
+// commit of `batch` DEVICE vectors of n[i] leaves each (merkle_build_mixed_batch_on): stream-ordered, no host synchronisation
+int32_t stark_commitment_commit_mixed_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* ds_tags, const uint64_t* const* leaves, const size_t* n, stark_tree_t** out) {
+    if (!batch) return STARK_OK;
+    if (!out) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad commitment batch args") : STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (!ctx || !ds_tags || !leaves || !n) return ctx ? ctx->fail(STARK_ERR_INVALID_ARG, "bad commitment batch args") : STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    stark_params* cp = nullptr; STARK_TRY(ctx_commit_params(ctx, &cp));
+    return merkle_build_mixed_batch_on(ctx, cp, 16, batch, ds_tags, leaves, n, 0, nullptr, out);
+}
 // verify (:96-113): verify_many_ds with the static t = 17 parameters lifted to the dynamic form
 int32_t stark_commitment_verify(stark_ctx_t* ctx, uint64_t ds_tag, const uint64_t* root4, const size_t* indices, size_t k, const uint64_t* values, const uint8_t* proof, size_t len, int32_t* accepted) {
     if (!ctx || !root4 || (!indices && k) || (!values && k) || (!proof && len) || !accepted) return STARK_ERR_INVALID_ARG;
@@ -418,12 +430,12 @@ int32_t stark_mle_evaluate_dev(stark_ctx_t* ctx, const uint64_t* table, size_t k
 int32_t stark_sumcheck_prove_plain_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out) {
     if (!ctx || !witness || !out) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return prove_sumcheck_batch_impl(ctx, 0, 1, &witness, k, &tree_label, 0, out);
+    return prove_sumcheck_mixed_impl(ctx, 0, 1, &witness, &k, &tree_label, 0, out);
 }
 int32_t stark_sumcheck_prove_mf_dev(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, size_t queries_per_round, stark_proof_t** out) {
     if (!ctx || !witness || !out) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return prove_sumcheck_batch_impl(ctx, 1, 1, &witness, k, &tree_label, queries_per_round, out);
+    return prove_sumcheck_mixed_impl(ctx, 1, 1, &witness, &k, &tree_label, queries_per_round, out);
 }
 int32_t stark_sumcheck_prove_plain(stark_ctx_t* ctx, const uint64_t* witness, size_t k, uint64_t tree_label, stark_proof_t** out) {
     if (!ctx || !witness || !out || k > 40) return STARK_ERR_INVALID_ARG;
@@ -443,7 +455,23 @@ static int32_t prove_batch_dev(stark_ctx_t* ctx, int mf, size_t batch, const uin
     if (!ctx || !out || !witnesses || !tree_labels || k > 40) return STARK_ERR_INVALID_ARG;
     for (size_t b = 0; b < batch; ++b) if (!witnesses[b]) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    return prove_sumcheck_batch_impl(ctx, mf, batch, witnesses, k, tree_labels, qpr, out);
+    const std::vector<size_t> ks(batch, k);
+    return prove_sumcheck_mixed_impl(ctx, mf, batch, witnesses, ks.data(), tree_labels, qpr, out);
+}
+static int32_t prove_mixed_batch_dev(stark_ctx_t* ctx, int mf, size_t batch, const uint64_t* const* witnesses, const size_t* k, const uint64_t* tree_labels, size_t qpr, stark_proof_t** out) {
+    if (!batch) return STARK_OK;
+    if (out) for (size_t b = 0; b < batch; ++b) out[b] = nullptr;
+    if (!ctx || !out || !witnesses || !tree_labels || !k) return STARK_ERR_INVALID_ARG;
+    for (size_t b = 0; b < batch; ++b) if (!witnesses[b] || k[b] > 40) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    return prove_sumcheck_mixed_impl(ctx, mf, batch, witnesses, k, tree_labels, qpr, out);
+}
+int32_t stark_sumcheck_prove_plain_mixed_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, const size_t* k, const uint64_t* tree_labels, stark_proof_t** out) {
+    return prove_mixed_batch_dev(ctx, 0, batch, witnesses, k, tree_labels, 0, out);
+}
+int32_t stark_sumcheck_prove_mf_mixed_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, const size_t* k, const uint64_t* tree_labels, size_t queries_per_round,
+                                                stark_proof_t** out) {
+    return prove_mixed_batch_dev(ctx, 1, batch, witnesses, k, tree_labels, queries_per_round, out);
 }
 int32_t stark_sumcheck_prove_plain_batch_dev(stark_ctx_t* ctx, size_t batch, const uint64_t* const* witnesses, size_t k, const uint64_t* tree_labels, stark_proof_t** out) {
     return prove_batch_dev(ctx, 0, batch, witnesses, k, tree_labels, 0, out);

@@ -12,6 +12,7 @@
 #include "fr.hpp"
 #include "dev_common.hpp"
 #include "ntt_dev.hpp"   // PowTable / pow_lookup
+#include "poseidon_streams.hpp"   // DsRaggedStream: the segment table of k_copy_ragged
 
 namespace stark {
 
@@ -161,6 +162,14 @@ __global__ void __launch_bounds__(256) k_ali_merge_batch(const fr_t* const* __re
 static __global__ void __launch_bounds__(256) k_copy_rows(const fr_t* const* __restrict__ src, uint64_t n, fr_t* __restrict__ dst) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (i < n) stg(dst + b * n + i, ldg(src[b] + i));
+}
+// dst[first_s + j] = in0_s[j], j < n_in_s, for every segment s of a pair-leaf table (DsRaggedStream mode 1: `first` counts elements): level 0 of a
+// batch of plain trees of different lengths, back to back, in one launch.
+static __global__ void __launch_bounds__(256) k_copy_ragged(DsRaggedStream D, fr_t* __restrict__ dst) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= D.n_out) return;
+    const DsRaggedStream::Seg& S = D.segs[D.seg(i)];
+    stg(dst + i, ldg(S.in0 + (i - S.first)));
 }
 // out[b] = scale * sum_{i<n} v[b * n + i] for b = blockIdx.x   (one 256-thread block per sum; n is a few thousand block partials; a grid of one
 // block is the single sum).

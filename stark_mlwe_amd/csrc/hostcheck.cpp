@@ -700,11 +700,16 @@ struct ScHostExec : HostArena {
         for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, cp->dev, D, k); }
         return 0;
     }
-    int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim) {
+    int32_t ragged_level(const DsRaggedStream& D, fr_t* out) {
+        std::vector<fr_t> st(cp->dev.t);
+        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, cp->dev, D, k); }
+        return 0;
+    }
+    int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim, size_t claim_from) {
         for (size_t b = 0; b < B; ++b) {
             const fr_t* l = ptrs ? ptrs[b] : layers + b * len; fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
             for (size_t j = 0; j < len / 2; ++j) { c0 = fr_add<PF>(c0, l[2 * j]); c1 = fr_add<PF>(c1, fr_sub<PF>(l[2 * j + 1], l[2 * j])); }
-            c01[2 * b] = c0; c01[2 * b + 1] = c1; if (claim) claim[b] = fr_add<PF>(fr_add<PF>(c0, c0), c1);
+            c01[2 * b] = c0; c01[2 * b + 1] = c1; if (claim && b >= claim_from) claim[b] = fr_add<PF>(fr_add<PF>(c0, c0), c1);
         }
         return 0;
     }
@@ -736,7 +741,7 @@ int hc_tr_batch(void* tparams, uint64_t* state, uint32_t* pos, size_t n_inst, co
     for (size_t i = 0; i < st.size(); ++i) st[i] = ld4(state + 4 * i);
     for (size_t i = 0; i < n0; ++i) p0[i] = ld4(pool0 + 4 * i); for (size_t i = 0; i < n1; ++i) p1[i] = ld4(pool1 + 4 * i);
     TrBatchStream T; T.state = st.data(); T.pos = pos; T.inst = inst; T.inst0 = inst0; T.n_active = n_active; T.nseg = nseg; T.el_off = el_off; T.idx = idx;
-    T.pool0 = p0.data(); T.pool1 = p1.data(); T.out = o.data(); T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = reset; T.finish_last = finish_last;
+    T.pool0 = p0.data(); T.pool1 = p1.data(); T.out = o.data(); T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset_from = reset ? 0 : n_active; T.finish_last = finish_last;
     fr_t s17[17]; for (size_t a = 0; a < n_active; ++a) { ArrayState s{s17}; tr_batch_body(s, P->dev, T, a); }
     for (size_t i = 0; i < st.size(); ++i) st4(state + 4 * i, st[i]);
     for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
@@ -749,6 +754,25 @@ size_t hc_sumcheck_prove_batch(void* tparams, void* cparams, int mf, size_t B, c
     const size_t n = (size_t)1 << k;
     std::vector<std::vector<fr_t>> w(B, std::vector<fr_t>(n)); std::vector<const fr_t*> wp(B);
     for (size_t b = 0; b < B; ++b) { for (size_t i = 0; i < n; ++i) w[b][i] = ld4(witnesses[b] + 4 * i); wp[b] = w[b].data(); }
+    ScHostExec X((HcParams*)cparams, (HcParams*)tparams);
+    const std::vector<size_t> ks(B, k);
+    ScBatch<ScHostExec> S(X, B, wp.data(), ks.data(), labels);
+    std::vector<std::vector<uint8_t>> pr;
+    if (mf ? S.prove_mf(q, pr) : S.prove_plain(pr)) return 0;
+    size_t tot = 0; for (size_t b = 0; b < B; ++b) { lens[b] = pr[b].size(); tot += pr[b].size(); }
+    if (buf && cap >= tot) { size_t o = 0; for (auto& p : pr) { memcpy(buf + o, p.data(), p.size()); o += p.size(); } }
+    return tot;
+}
+// The same of witnesses of different sizes: witness b has 2^k[b] elements (k[b] <= 40).  As hc_sumcheck_prove_batch otherwise.
+size_t hc_sumcheck_prove_mixed_batch(void* tparams, void* cparams, int mf, size_t B, const uint64_t* const* witnesses, const size_t* k, const uint64_t* labels, size_t q,
+                                     uint8_t* buf, size_t cap, size_t* lens) {
+    std::vector<std::vector<fr_t>> w(B); std::vector<const fr_t*> wp(B);
+    for (size_t b = 0; b < B; ++b) {
+        if (k[b] > 40) return 0;
+        const size_t n = (size_t)1 << k[b]; w[b].resize(n);
+        for (size_t i = 0; i < n; ++i) w[b][i] = ld4(witnesses[b] + 4 * i);
+        wp[b] = w[b].data();
+    }
     ScHostExec X((HcParams*)cparams, (HcParams*)tparams);
     ScBatch<ScHostExec> S(X, B, wp.data(), k, labels);
     std::vector<std::vector<uint8_t>> pr;
@@ -781,7 +805,7 @@ static void run_sc_plan_host(ScVerifyPlan& V, HcParams* tp, HcParams* cp, int32_
     std::vector<fr_t> state = hc_fr_block(17 * std::max<size_t>(V.n_inst, 1)); std::vector<uint32_t> pos(std::max<size_t>(V.n_inst, 1), 0x01010101u * (uint32_t)g_alloc_fill);
     for (const ScVerifyPlan::Stream& S : V.tr) {
         TrBatchStream T; T.state = state.data(); T.pos = pos.data(); T.inst = nullptr; T.inst0 = S.inst0; T.n_active = S.n; T.nseg = S.nseg; T.el_off = V.tr_off.data() + S.seg0;
-        T.idx = V.tr_idx.data(); T.pool0 = pool.data(); T.pool1 = V.consts.data(); T.out = pool.data() + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset = 1; T.finish_last = 1;
+        T.idx = V.tr_idx.data(); T.pool0 = pool.data(); T.pool1 = V.consts.data(); T.out = pool.data() + V.n_dec + S.seg0; T.init_cap = host::h_tag("FSv1-TRANSCRIPT-INIT"); T.reset_from = 0; T.finish_last = 1;
         fr_t st[17]; for (size_t a = 0; a < S.n; ++a) { ArrayState s{st}; tr_batch_body(s, tp->dev, T, a); }
     }
     for (const VerifyBatchPlan::Group& G : V.ds.groups) {
@@ -1109,6 +1133,10 @@ struct MerkleHostExec : HostArena {
     }
     int32_t pair_level(const DsBatchPairPtrStream& D, fr_t* out) { return ds(D, out); }
     int32_t ds_level(const DsBatchStream& D, fr_t* out) { return ds(D, out); }
+    // merkle_build_mixed_batch
+    int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x) { DsRaggedStream::Seg* d = nullptr; put(h, &d); *x = d; return 0; }
+    int32_t copy_ragged(const DsRaggedStream& D, fr_t* dst) { for (size_t i = 0; i < D.n_out; ++i) { const DsRaggedStream::Seg& S = D.segs[D.seg(i)]; dst[i] = S.in0[i - S.first]; } return 0; }
+    int32_t ragged_level(const DsRaggedStream& D, fr_t* out) { return ds(D, out); }
 };
 struct MerkleOpenHostExec { int32_t gather(const MerkleGatherList& G, fr_t* out) { for (size_t i = 0; i < G.size(); ++i) out[G.row_of(i)] = G.base[G.src[i]][G.index[i]]; return 0; } };
 static std::vector<size_t> total_lens(const std::vector<size_t>& lens, size_t B) { std::vector<size_t> o(lens.size() + 1, 0); for (size_t v = 0; v < lens.size(); ++v) o[v + 1] = o[v] + B * lens[v]; return o; }
@@ -1132,6 +1160,53 @@ int hc_merkle_build_batch(void* params, size_t arity, size_t B, const uint64_t* 
     if (lens.size() > 64 || at.back() > cap_fr) return -1;
     for (size_t v = 0; v < lens.size(); ++v) { lens_out[v] = lens[v]; for (size_t i = 0; i < B * lens[v]; ++i) st4(out + 4 * (at[v] + i), base[v][i]); }
     return (int)lens.size();
+}
+// One launch of a DsRaggedStream (mode 0 node level / 1 pair leaf): segment s reads in0[s] (in1[s], pair leaves; a null table or entry = zeros), n_in[s]
+// elements under labels[s]; out receives the segments' hashes back to back.  Returns the number of hashes, or -1 on an empty segment.
+long hc_hash_ds_ragged_level(void* params, int mode, size_t arity, uint32_t level, uint64_t pos0, size_t n_seg, const uint64_t* labels, const uint64_t* const* in0,
+                             const uint64_t* const* in1, const size_t* n_in, uint64_t* out) {
+    HcParams* P = (HcParams*)params;
+    std::vector<std::vector<fr_t>> a(n_seg), b(n_seg); DsRaggedTable T;
+    for (size_t s = 0; s < n_seg; ++s) {
+        if (!n_in[s]) return -1;
+        a[s].resize(n_in[s]); for (size_t i = 0; i < n_in[s]; ++i) a[s][i] = ld4(in0[s] + 4 * i);
+        if (mode == 1 && in1 && in1[s]) { b[s].resize(n_in[s]); for (size_t i = 0; i < n_in[s]; ++i) b[s][i] = ld4(in1[s] + 4 * i); }
+        T.add(mode, arity, a[s].data(), b[s].empty() ? nullptr : b[s].data(), n_in[s], labels[s]);
+    }
+    const DsRaggedStream D = DsRaggedStream::make(mode, arity, level, pos0, T.segs.data(), n_seg, T.n_out);
+    std::vector<fr_t> st(P->dev.t);
+    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, D, k)); }
+    return (long)D.n_out;
+}
+// MerkleTree::new / new_pairs of B trees of n[b] leaves through the mixed-size driver.  out (cap_fr elements) receives the level blocks back to back,
+// level v the slices of the trees with more than v levels in tree order.  nlev_out[b]: the levels of tree b, lens_out[64 b + v] their lengths.
+// Returns the number of level blocks, or -1 on a refused shape.
+int hc_merkle_build_mixed_batch(void* params, size_t arity, size_t B, const uint64_t* labels, const uint64_t* const* leaves, const size_t* n, int pairs, const uint64_t* const* cp,
+                                uint64_t* out, size_t cap_fr, size_t* nlev_out, size_t* lens_out) {
+    HcParams* P = (HcParams*)params;
+    if (!B || !arity || host::width_for_arity(arity) != P->dev.t || (pairs && !cp)) return -1;
+    for (size_t b = 0; b < B; ++b) if (!n[b] || !leaves[b] || (arity == 1 && n[b] > 1)) return -1;
+    std::vector<std::vector<fr_t>> col(B), cc(B); std::vector<const fr_t*> lp(B), cpp(B, nullptr);
+    for (size_t b = 0; b < B; ++b) {
+        col[b].resize(n[b]); for (size_t i = 0; i < n[b]; ++i) col[b][i] = ld4(leaves[b] + 4 * i);
+        lp[b] = col[b].data();
+        if (pairs && cp[b]) { cc[b].resize(n[b]); for (size_t i = 0; i < n[b]; ++i) cc[b][i] = ld4(cp[b] + 4 * i); cpp[b] = cc[b].data(); }
+    }
+    MerkleHostExec X(P); std::vector<std::vector<size_t>> lens, at; std::vector<fr_t*> base;
+    if (merkle_build_mixed_batch(X, arity, B, labels, lp.data(), n, pairs, pairs ? cpp.data() : nullptr, lens, at, base)) return -1;
+    std::vector<size_t> block(base.size(), 0);
+    for (size_t b = 0; b < B; ++b) {
+        if (lens[b].size() > 64) return -1;
+        nlev_out[b] = lens[b].size();
+        for (size_t v = 0; v < lens[b].size(); ++v) { lens_out[64 * b + v] = lens[b][v]; block[v] += lens[b][v]; }
+    }
+    size_t o = 0;
+    for (size_t v = 0; v < base.size(); ++v) {
+        if (o + block[v] > cap_fr) return -1;
+        for (size_t i = 0; i < block[v]; ++i) st4(out + 4 * (o + i), base[v][i]);
+        o += block[v];
+    }
+    return (int)base.size();
 }
 // open_union_of_paths of B trees through the batch driver.  Tree b: arity[b], nlev[b] levels; the levels of all trees are listed tree by tree in
 // levels / lens.  Tree b opens idx[idx_off[b] .. idx_off[b + 1]).  The proofs are written back to back into buf when cap suffices, their lengths

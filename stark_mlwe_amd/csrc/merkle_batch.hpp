@@ -4,6 +4,7 @@
 //
 //   build   `batch` trees of one shape (arity, n, pairs).  Level v of all trees is ONE block of batch x lens[v] elements, tree b's level the slice at
 //           b * lens[v]: level 0 is one copy (or one pair-leaf launch) through the pointer tables, every level above one DsBatchStream launch.
+//           Trees of different lengths: merkle_build_mixed_batch, level v one block of the slices of the trees that still have it (DsRaggedStream).
 //   open    any trees of one context: every tree is planned on the host (merkle_open_from over a recording source), all siblings of all trees and
 //           levels come back with ONE gather, and each proof is encoded with enc_mproof.  stark_merkle_open is this with one tree.
 //   verify  every opening is parsed (dec_mproof) and walked over pool slots (DsJobPlanner) into the plan shape of fri_verify_batch.hpp; what runs the
@@ -52,6 +53,40 @@ inline int32_t merkle_build_batch(X& x, size_t arity, size_t B, const uint64_t* 
         MB_TRY(x.level_block(B * lens[v], &base[v]));
         MB_TRY(x.ds_level(DsBatchStream::make(arity, (uint32_t)(v - 1), 0, labels_x, nullptr, base[v - 1], lens[v - 1], B), base[v]));
     }
+    return 0;
+}
+
+// ---- build, trees of different lengths ------------------------------------------------------------------------------------------------------------
+// `B` trees of one arity and parameter set, tree b of n[b] >= 1 leaves.  Level v of the call is ONE block: the slices of the trees that have more
+// than v levels, back to back in tree order (a tree of one leaf has its one level and no hash; trees drop out as they reach their root).  Level 0 is
+// one ragged copy (or one ragged pair-leaf launch), every level above one DsRaggedStream launch over the trees that still have it.  All blocks are
+// taken first, so every segment table of the call is built on the host and goes up as ONE table.
+// An executor X provides (level_block as above):
+//   int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x)   the table in X's memory; `h` may die on return
+//   int32_t copy_ragged(const DsRaggedStream& D, fr_t* dst)                                      dst[first_s + j] = in0_s[j] (D of mode 1)
+//   int32_t ragged_level(const DsRaggedStream& D, fr_t* out)
+// lens[b]: the level lengths of tree b; at[b][v]: where its level v starts in base[v].  The argument checks are the caller's.
+template <class X>
+inline int32_t merkle_build_mixed_batch(X& x, size_t arity, size_t B, const uint64_t* labels, const fr_t* const* leaves, const size_t* n, int pairs, const fr_t* const* cp,
+                                        std::vector<std::vector<size_t>>& lens, std::vector<std::vector<size_t>>& at, std::vector<fr_t*>& base) {
+    lens.assign(B, {}); at.assign(B, {}); size_t depth = 0;
+    for (size_t b = 0; b < B; ++b) { lens[b] = merkle_level_lens(n[b], arity); at[b].assign(lens[b].size(), 0); depth = std::max(depth, lens[b].size()); }
+    std::vector<size_t> block(depth, 0);
+    for (size_t v = 0; v < depth; ++v) for (size_t b = 0; b < B; ++b) if (lens[b].size() > v) { at[b][v] = block[v]; block[v] += lens[b][v]; }
+    base.assign(depth, nullptr);
+    for (size_t v = 0; v < depth; ++v) MB_TRY(x.level_block(block[v], &base[v]));
+    // table 0: the leaves (pair-leaf mode; the plain copy reads the same table), table v >= 1: the node level that turns level v - 1 into level v
+    std::vector<DsRaggedTable> T(depth);
+    for (size_t b = 0; b < B; ++b) T[0].add(1, arity, leaves[b], pairs ? cp[b] : nullptr, n[b], labels[b]);
+    for (size_t v = 1; v < depth; ++v) for (size_t b = 0; b < B; ++b) if (lens[b].size() > v) T[v].add(0, arity, base[v - 1] + at[b][v - 1], nullptr, lens[b][v - 1], labels[b]);
+    std::vector<DsRaggedStream::Seg> all; std::vector<size_t> t0(depth);
+    for (size_t v = 0; v < depth; ++v) { t0[v] = all.size(); all.insert(all.end(), T[v].segs.begin(), T[v].segs.end()); }
+    const DsRaggedStream::Seg* sx = nullptr; MB_TRY(x.segments(all, &sx));
+    const DsRaggedStream L0 = DsRaggedStream::make(1, arity, 0xFFFFFFFFu, 0, sx, B, T[0].n_out);
+    if (pairs) MB_TRY(x.ragged_level(L0, base[0]));                                                                   // new_pairs (:380-388, 392-414)
+    else MB_TRY(x.copy_ragged(L0, base[0]));                                                                          // new: the leaves are level 0
+    for (size_t v = 1; v < depth; ++v)                                                                                // :163-179
+        MB_TRY(x.ragged_level(DsRaggedStream::make(0, arity, (uint32_t)(v - 1), 0, sx + t0[v], T[v].segs.size(), T[v].n_out), base[v]));
     return 0;
 }
 

@@ -160,9 +160,9 @@ template <class S> FR_HD fr_t tr_hash_body(const S& s, const PoseidonDev& P, con
 // Active instance a of a TrBatchStream: the stored (or reset) state, the lazy permute before absorbing into a full rate, one permutation
 // and squeeze per finished segment; state and cursor written back.
 template <class S> FR_HD void tr_batch_body(const S& s, const PoseidonDev& P, const TrBatchStream& T, size_t a) {
-    const size_t b = T.instance(a);
-    for (int j = 0; j < 17; ++j) s.st(j, T.reset ? (j == 16 ? T.init_cap : fr_zero<PF>()) : T.state[17 * b + j]);
-    uint32_t pos = T.reset ? 0u : T.pos[b];
+    const size_t b = T.instance(a); const bool fresh = T.resets(a);
+    for (int j = 0; j < 17; ++j) s.st(j, fresh ? (j == 16 ? T.init_cap : fr_zero<PF>()) : T.state[17 * b + j]);
+    uint32_t pos = fresh ? 0u : T.pos[b];
     for (size_t sg = 0; sg < T.nseg; ++sg) {
         const size_t seg = a * T.nseg + sg;
         for (uint32_t j = T.el_off[seg]; j < T.el_off[seg + 1]; ++j) {

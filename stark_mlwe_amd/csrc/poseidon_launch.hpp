@@ -11,12 +11,14 @@ void poseidon_set_attrs();                                           // per-devi
 
 // One launch of hash_with_ds_dynamic over the hashes of a DS stream on `st`, in the form the selector picks for a Merkle level of D.n_out nodes
 // (DsStream: a Merkle level / pair-leaf level; DsGatherStream: one (width, depth) step of the batch verifiers; DsBatchStream: one level of B trees;
-// DsBatchPairStream: the pair leaves of B unhashed FRI layers; DsBatchPairPtrStream: the pair leaves of B trees read through pointer tables).
+// DsBatchPairStream: the pair leaves of B unhashed FRI layers; DsBatchPairPtrStream: the pair leaves of B trees read through pointer tables;
+// DsRaggedStream: one level, node or pair leaf, of trees of different lengths).
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out);
+int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsRaggedStream& D, fr_t* out);
 int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h);
 // level0_block: a pooled block holding the leaves, moved into the tree as level 0; an empty one: level 0 is a copy of `leaves` (capi_poseidon.hip)
 int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t arity, uint64_t label, const fr_t* leaves, size_t n, int pairs, const fr_t* cp, size_t cp_div,
@@ -25,6 +27,9 @@ int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t 
 // (cp: nullptr iff !pairs; a null entry = zeros).  Stream-ordered, no host synchronisation.  out: `batch` handles, all null on any error.
 int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, size_t batch, const uint64_t* labels, const uint64_t* const* leaves, size_t n, int pairs,
                               const uint64_t* const* cp, stark_tree** out);
+// The same of trees of DIFFERENT lengths n[b] >= 1 (merkle_build_mixed_batch): one launch per level over the trees that still have it.
+int32_t merkle_build_mixed_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, size_t batch, const uint64_t* labels, const uint64_t* const* leaves, const size_t* n, int pairs,
+                                    const uint64_t* const* cp, stark_tree** out);
 
 int32_t tr_hash_dev(stark_ctx* ctx, const char* tag, const fr_t* fields_dev, size_t k, size_t n, fr_t* out_dev);
 int32_t tr_hash_columns4_dev(stark_ctx* ctx, const char* const tags[4], const fr_t* const cols[4], size_t n0, fr_t* out4_dev);

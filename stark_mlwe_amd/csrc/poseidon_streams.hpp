@@ -132,19 +132,67 @@ struct DsBatchPairPtrStream {
     }
 };
 
+// One Merkle level of trees of DIFFERENT lengths in one launch (the mixed-size batch build, merkle_batch.hpp): DsStream per segment.  Segment s is
+// one tree that still has this level: its input pointer(s), its own n_in and label, and `first`, the index of its first hash in the launch (the
+// prefix sums of the segments' hash counts; a segment has at least one hash).  Hash k belongs to the segment whose range [first, next first) holds
+// k and is node or leaf j = k - first of that tree, position pos0 + j; out[k] is written, so a launch's block is the trees' slices back to back.
+//   mode 0 (node level): hash k = hash_with_ds_dynamic([arity, level, pos0 + j, label_s] || in0_s[j*arity .. min((j+1)*arity, n_in_s)) || 1)
+//   mode 1 (pair leaf) : hash k = hash_with_ds_dynamic([arity, level, pos0 + j, label_s] || in0_s[j], in1_s ? in1_s[j] : 0 || 1)
+// eager sponge, zero padded, cap 0: per hash what DsStream mode 0 / DsBatchPairPtrStream give on that tree alone.  The segment of a hash is found by
+// a binary search over `first` (n_seg <= the number of trees of the call; the table stays in cache over the 21 reads of a hash).
+struct DsRaggedStream {
+    struct Seg { const fr_t* in0; const fr_t* in1; uint64_t n_in, label, first; };
+    fr_t arity_f, level_f; uint64_t pos0; size_t arity, n_seg, n_out; int mode; const Seg* segs;
+    // the number of hashes a tree of n_in inputs has in a launch of this mode
+    static inline size_t hashes(int mode, size_t arity, size_t n_in) { return mode == 1 ? n_in : (n_in + arity - 1) / arity; }
+    // segs: the table in the memory the kernels read (n_seg entries); n_out: the sum of the segments' hash counts (what the table's `first` add up to)
+    static inline DsRaggedStream make(int mode, size_t arity, uint32_t level, uint64_t pos0, const Seg* segs, size_t n_seg, size_t n_out) {
+        DsRaggedStream D;
+        D.arity_f = fr_from_u64<PF>(arity); D.level_f = fr_from_u64<PF>(level); D.pos0 = pos0; D.arity = arity; D.n_seg = n_seg; D.n_out = n_out; D.mode = mode; D.segs = segs;
+        return D;
+    }
+    FR_HD size_t seg(size_t k) const {                                 // the last segment whose first hash is <= k
+        size_t lo = 0, hi = n_seg;
+        while (hi - lo > 1) { const size_t mid = (lo + hi) >> 1; if ((size_t)segs[mid].first <= k) lo = mid; else hi = mid; }
+        return lo;
+    }
+    FR_HD static size_t children(const Seg& S, size_t j, int mode, size_t arity) { return mode == 1 ? 2 : ((j + 1) * arity <= (size_t)S.n_in ? arity : (size_t)S.n_in - j * arity); }
+    FR_HD uint64_t position(size_t k) const { return pos0 + (k - (size_t)segs[seg(k)].first); }
+    FR_HD size_t total(size_t k) const { const Seg& S = segs[seg(k)]; return 4 + children(S, k - (size_t)S.first, mode, arity) + 1; }
+    FR_HD size_t max_total() const { return 4 + (mode == 1 ? 2 : arity) + 1; }
+    FR_HD fr_t elem(size_t k, size_t q) const {
+        if (q < 2) return q == 0 ? arity_f : level_f;
+        const Seg& S = segs[seg(k)]; const size_t j = k - (size_t)S.first;
+        if (q < 4) return q == 2 ? fr_from_u64<PF>(pos0 + j) : fr_from_u64<PF>(S.label);
+        if (q == 4 + children(S, j, mode, arity)) return fr_one<PF>();
+        const size_t c = q - 4;
+        if (mode == 1) return c == 0 ? ldg(S.in0 + j) : (S.in1 ? ldg(S.in1 + j) : fr_zero<PF>());
+        return ldg(S.in0 + j * arity + c);
+    }
+};
+// The segment table of one launch, built on the host: add() the participating trees in order, then hand `segs` to the executor's memory.
+struct DsRaggedTable {
+    std::vector<DsRaggedStream::Seg> segs; size_t n_out = 0;
+    void add(int mode, size_t arity, const fr_t* in0, const fr_t* in1, size_t n_in, uint64_t label) {
+        segs.push_back(DsRaggedStream::Seg{in0, in1, (uint64_t)n_in, label, (uint64_t)n_out}); n_out += DsRaggedStream::hashes(mode, arity, n_in);
+    }
+};
+
 // B streaming transcripts (transcript/src/lib.rs:79-101, lazy duplex) advanced in one launch, one workgroup per active instance
 // (the batched sum-check provers, sumcheck_batch.hpp).  Instance b keeps state[17 b .. 17 b + 16] and its rate cursor pos[b] in
 // device memory between launches; active a runs instance inst[a] (inst == nullptr: inst0 + a).  Active a runs nseg segments: segment
 // s = a * nseg + s' absorbs the elements idx[el_off[s] .. el_off[s + 1]) gathered from the pools (an index with bit 31 set reads
 // pool1, else pool0), then — every segment but an unfinished last one — permutes and squeezes state[0] into out[s] (a challenge).
-//   reset       : the instance starts from Transcript::new's state (zeros, capacity `init_cap`, cursor 0) instead of the stored one
+//   reset_from  : the active instances a >= reset_from start from Transcript::new's state (zeros, capacity `init_cap`, cursor 0) instead of the
+//                 stored one (0: all of them; n_active: none).  The mixed-size provers' joiners are the tail of a launch's active instances.
 //   finish_last : 0 leaves the last segment absorbed but not permuted (the cursor then records where the next absorb goes)
 struct TrBatchStream {
     fr_t* state; uint32_t* pos; const uint32_t* inst; size_t inst0, n_active, nseg;
     const uint32_t* el_off; const uint32_t* idx; const fr_t* pool0; const fr_t* pool1; fr_t* out;
-    fr_t init_cap; int reset, finish_last;
+    fr_t init_cap; size_t reset_from; int finish_last;
     static constexpr uint32_t kPool1 = 0x80000000u;
     FR_HD size_t instance(size_t a) const { return inst ? (size_t)inst[a] : inst0 + a; }
+    FR_HD bool resets(size_t a) const { return a >= reset_from; }
     FR_HD bool finishes(size_t s) const { return finish_last || s + 1 < nseg; }
     FR_HD fr_t elem(size_t j) const { const uint32_t x = idx[j]; return x & kPool1 ? ldg(pool1 + (x & ~kPool1)) : ldg(pool0 + x); }
 };

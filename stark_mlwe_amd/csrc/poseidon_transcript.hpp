@@ -46,9 +46,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
     extern __shared__ uint4 lds[];
     CoopLds L = coop_setup<17>(lds, P);
     const int lane = threadIdx.x;
-    const size_t a = blockIdx.x, b = T.instance(a);
-    fr_t s = T.reset ? (lane == 16 ? T.init_cap : fr_zero<PF>()) : (lane < 17 ? ldg(T.state + 17 * b + lane) : fr_zero<PF>());
-    uint32_t pos = T.reset ? 0u : T.pos[b];
+    const size_t a = blockIdx.x, b = T.instance(a); const bool fresh = T.resets(a);
+    fr_t s = fresh ? (lane == 16 ? T.init_cap : fr_zero<PF>()) : (lane < 17 ? ldg(T.state + 17 * b + lane) : fr_zero<PF>());
+    uint32_t pos = fresh ? 0u : T.pos[b];
     for (size_t sg = 0; sg < T.nseg; ++sg) {
         const size_t seg = a * T.nseg + sg;
         const uint64_t e0 = T.el_off[seg], n = T.el_off[seg + 1] - e0;
@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
 __global__ void __launch_bounds__(320) __attribute__((amdgpu_waves_per_eu(1, 2))) k_tr_batch_chain(PoseidonDev P, row::Consts RK, TrBatchStream T, uint32_t sg) {
     extern __shared__ uint4 lds[];
     const size_t a = blockIdx.x, b = T.instance(a), seg = a * T.nseg + sg;
-    const bool fresh = T.reset && sg == 0;
+    const bool fresh = T.resets(a) && sg == 0;
     fr_t* st = T.state + 17 * b;
     const uint32_t lead = fresh ? 0u : T.pos[b];                                            // every thread reads it before thread 0 writes it back (barriers in between)
     const uint32_t e0 = T.el_off[seg];
