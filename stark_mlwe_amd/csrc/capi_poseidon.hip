@@ -75,21 +75,19 @@ static inline row::Consts row_consts_of(const stark_ctx* ctx) {
 // leaf template of hash_leaf_pair (fri.rs:38-44)
 static int32_t ctx_leaf_init(stark_ctx* ctx, fr_t** out) {
     if (!ctx->leaf_init) {
-        const fr_t AB = host::h_tag("FSv1-ABSORB-BYTES"), CH = host::h_tag("FSv1-CHALLENGE");
-        fr_t init[17]; for (auto& x : init) x = host::h_zero();
-        init[0] = AB; init[1] = host::h_words("FRI/leaf/poseidon")[0]; init[2] = AB; init[3] = host::h_words("FRI/leaf")[0];
-        /* lanes 4,5 = (f, s) */ init[6] = CH; init[7] = AB; init[8] = host::h_words("leaf")[0]; init[16] = host::h_tag("FSv1-TRANSCRIPT-INIT");
-        // closed form of round 0 for the wave-pair kernel: K_i = sum_{j != 4,5} M[i][j] * (init_j + rc0_j)^5, then columns 4 and 5 of M
+        fr_t init[17]; host::leaf_template(init);      // lanes 4,5 = (f, s)
+        // closed form of round 0 for the wave-pair kernels (host_util.hpp leaf_round0_consts): K_i = sum_{j != 4,5} M[i][j] * (init_j + rc0_j)^5, then columns 4 and 5 of M
         stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
         const host::PoseidonConsts& c = tp->ref;
-        fr_t blob[17 + 51 + 40];                       // + columns 4, 5 of M as 34 x 9 words in radix 2^29 (306 words = 38.25 elements)
+        // + columns 4, 5 of M as 34 x 9 words in radix 2^29 (306 words = 38.25 elements: k_leaf_pair2<false>) + (K_i + round 1's constant) as 17 x 9 limbs
+        // (153 words = 19.125 elements: k_leaf_pair2<true>, kLeafKrcOff elements behind K)
+        fr_t blob[17 + 51 + 40 + 20];
+        static_assert(kLeafKrcOff == 51 + 40, "k_leaf_pair2<true> reads its table at leafc + kLeafKrcOff");
         for (auto& x : blob) x = host::h_zero();
         for (int j = 0; j < 17; ++j) blob[j] = init[j];
-        fr_t x[17]; for (int j = 0; j < 17; ++j) x[j] = fr_pow5<PallasFr>(host::h_add(init[j], c.rc_full[j]));
+        host::leaf_round0_consts(c, init, &blob[17], reinterpret_cast<uint32_t*>(&blob[17 + kLeafKrcOff]));
         for (int i = 0; i < 17; ++i) {
-            fr_t k = host::h_zero();
-            for (int j = 0; j < 17; ++j) if (j != 4 && j != 5) k = host::h_add(k, host::h_mul(c.mds[(size_t)i * 17 + j], x[j]));
-            blob[17 + i] = k; blob[34 + i] = c.mds[(size_t)i * 17 + 4]; blob[51 + i] = c.mds[(size_t)i * 17 + 5];
+            blob[34 + i] = c.mds[(size_t)i * 17 + 4]; blob[51 + i] = c.mds[(size_t)i * 17 + 5];
             uint32_t* m45 = reinterpret_cast<uint32_t*>(&blob[68]);
             const fr_t k20 = fr_from_u64<PallasFr>(1ull << FR29_SBOX_SHIFT);     // the S-box outputs x4, x5 arrive divided by 2^20 (fr_pow5_r29)
             fr29_const_from<PallasFr>(host::h_mul(c.mds[(size_t)i * 17 + 4], k20), m45 + 9 * i); fr29_const_from<PallasFr>(host::h_mul(c.mds[(size_t)i * 17 + 5], k20), m45 + 9 * (17 + i));
@@ -243,7 +241,7 @@ int32_t stark_poseidon_hash_with_ds(stark_ctx_t* ctx, stark_params_t* p, const u
 // The 8-round partial blocks of the t = 17 wave-pair kernels: option poseidon_block8 (default 1) and a parameter set with rp % 8 == 0.  Such a set
 // without its tables on the device is an error, never a quiet return to blocks of 4.
 static int32_t pair_block8_form(stark_ctx* ctx, const stark_params* p, bool* on) {
-    *on = ctx->opt.poseidon_block8 && p->dev.t == 17 && p->dev.rp % 8 == 0;
+    *on = ctx->opt.poseidon_block8 && p->dev.t == 17 && p->dev.rp % 8 == 0 && p->dev.rf >= 2;      // rf >= 2: the fused kernels enter the blocks from the product of round rf / 2 - 1
     if (*on && (!p->dev.blk8_efrag || !p->dev.blk8_lfrag || !p->dev.blk8_unit_frag || !p->dev.blk8_gfrag || !p->dev.rc_partial_scaled29)) return ctx->fail(STARK_ERR_UNSUPPORTED, "poseidon_block8: the parameter set has no block-8 tables");
     return STARK_OK;
 }
@@ -336,6 +334,7 @@ int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const f
     fr_t* init = nullptr; STARK_TRY(ctx_leaf_init(ctx, &init));
     const LeafStream L{init, f, f_next, m, n};
     bool b8 = false; STARK_TRY(pair_block8_form(ctx, tp, &b8));
+    if (tp->ref.rf < 4) b8 = false;      // k_leaf_pair2<true> hands round 0's rows to round 1's S-box: a full-round product must follow (the transcript set has rf = 8)
     switch (poseidon_form(ctx, tp, PoseidonOp::LeafLayer, n)) {
     case PoseidonForm::FiveWave: hipLaunchKernelGGL(k_leaf_pair_chain, dim3((unsigned)n), dim3(320), chain_lds_bytes(), st, tp->dev, row_consts_of(ctx), L, h); break;
     case PoseidonForm::OneWave: hipLaunchKernelGGL(k_leaf_pair_coop, dim3((unsigned)n), dim3(64), coop_lds_bytes(17), st, tp->dev, L, h); break;

@@ -434,6 +434,28 @@ inline KernelConsts make_kernel_consts(const PoseidonConsts& c) {
     return k;
 }
 
+// hash_leaf_pair's 17-lane template (fri.rs:38-44): lanes 4 and 5 take (f, s), the other fifteen are constants.
+inline void leaf_template(fr_t init[17]) {
+    const fr_t AB = h_tag("FSv1-ABSORB-BYTES"), CH = h_tag("FSv1-CHALLENGE");
+    for (int j = 0; j < 17; ++j) init[j] = h_zero();
+    init[0] = AB; init[1] = h_words("FRI/leaf/poseidon")[0]; init[2] = AB; init[3] = h_words("FRI/leaf")[0];
+    init[6] = CH; init[7] = AB; init[8] = h_words("leaf")[0]; init[16] = h_tag("FSv1-TRANSCRIPT-INIT");
+}
+// Round 0 of that permutation in closed form: after ARK and S-box the MDS output is K_i + M[i][4] x4 + M[i][5] x5 with
+//     K_i = sum_{j != 4,5} M[i][j] (init_j + rc0_j)^5.
+// krc29 (17 x 9 words): (K_i + rc_full[17 + i]) mod r, round 1's constant folded in, as the nine 29-bit limbs of the stored value (fr29_unpack, like rc_full29:
+// an addend): what the leaf kernel's two-K-step round-0 rows add in front of round 1's S-box (poseidon_pair.hpp pair_leaf_round0_mfma).
+inline void leaf_round0_consts(const PoseidonConsts& c, const fr_t* init, fr_t* K, uint32_t* krc29) {
+    fr_t x[17]; for (int j = 0; j < 17; ++j) x[j] = fr_pow5<PF>(h_add(init[j], c.rc_full[j]));
+    for (int i = 0; i < 17; ++i) {
+        fr_t k = h_zero();
+        for (int j = 0; j < 17; ++j) if (j != 4 && j != 5) k = h_add(k, h_mul(c.mds[(size_t)i * 17 + j], x[j]));
+        K[i] = k;
+        const fr29_t u = fr29_unpack(h_add(k, c.rc_full[17 + i]));
+        for (int j = 0; j < 9; ++j) krc29[9 * i + j] = u.l[j];
+    }
+}
+
 // Reference-form permutation on the host (dense MDS every round; poseidon/src/lib.rs:31-68,219-258).
 // Used only by the host-check library to validate the kernel-form constants on CPU.
 inline void permute_dense(fr_t* s, const PoseidonConsts& c) {

@@ -282,8 +282,8 @@ static int blk8_tile(const int8_t* const* frag, const fr_t* xd, int K, fr_t& out
 static std::atomic<int32_t> g_blk8_row23_max{0};
 int32_t hc_blk8_row23_max(int reset) { return reset ? g_blk8_row23_max.exchange(0) : g_blk8_row23_max.load(); }
 // A whole t = 17 permutation in the wave-pair kernels' block-8 form: full rounds through the residue tables of M and B_1 M — every product that is followed
-// by a full round hands its rows over in limb form (word-column finish to limbs, the next round's constant from rc_full29, sbox_lazy29), the products in front of the
-// partial rounds and at the end finish canonical from the same word columns (two conditional subtractions), the first round's S-box stands alone, the last block's lane rows feed the S-box of the round after the partial rounds the same way (element 0 from
+// by a full round hands its rows over in limb form (word-column finish to limbs, the next round's constant from rc_full29, sbox_lazy29), the product in front of the
+// partial rounds ends as the first block takes its rows (the lanes as digits of their signed residue by the byte-domain finish, row 0 as its nine finish limbs plus lambda_0 c_0: no canonical value at the entry) and the one at the end finishes canonical, all from the same word columns, the first round's S-box stands alone, the last block's lane rows feed the S-box of the round after the partial rounds the same way (element 0 from
 // the chain value) —, the partial rounds in
 // blocks of 8 — lanes recoded, row q = H_q = E_q + sum Gamma y_p as ONE tile of 16 + q K-steps (E fragments against the lanes, blk8_gfrag against the
 // recoded yt_0..yt_{q-1}), the SCALED chain as a LAZY residue (u = lambda_q X_q + lambda_q c_q as nine limbs; x5 = pow5_lazy29(u), yt_q recoded unreduced; u <- x5 + the finish limbs of
@@ -298,23 +298,28 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
     std::vector<fr_t> st(t), xd(t), o(t);
     // pair_sbox_full<17, true>: st (canonical) -> xd
     auto sbox = [&](int r) { for (int j = 0; j < t; ++j) xd[j] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(st[j], k.rc_full[(size_t)r * t + j]))); };
-    // pair_mds_sbox_mfma: xd -> st (canonical) when next < 0, else xd -> xd = the recoded S-box outputs of round `next`
-    auto product = [&](const std::vector<int8_t>& F, int next) -> int {
+    // pair_mds_sbox_mfma: xd -> st (canonical) when next < 0, else xd -> xd = the recoded S-box outputs of round `next`; entry (the product in front of the
+    // partial rounds): rows 1..16 -> rec, the digits of their signed residue (mfma_finish_bytes on the same word columns), row 0 -> l0, its nine finish limbs
+    fr_t rec[17]; uint32_t l0[9];
+    auto product = [&](const std::vector<int8_t>& F, int next, bool entry) -> int {
         for (int i = 0; i < t; ++i) {
             const int8_t* fr[17]; for (int e = 0; e < t; ++e) fr[e] = &F[((size_t)i * t + e) * 1024];
             int32_t S[32]; const int rc = blk8_tile_sums(fr, xd.data(), t, S); if (rc) return rc;
-            if (next < 0) { int64_t col[8]; mfma_word_cols_mad_of_sums(S, col); o[i] = mfma_finish_words_canonical(col); }      // the same word columns, two conditional subtractions
+            if (next < 0 && entry) { int64_t col[8]; mfma_word_cols_mad_of_sums(S, col); if (i == 0) mfma_finish_words(col, l0); else rec[i] = mfma_finish_bytes(col); }
+            else if (next < 0) { int64_t col[8]; mfma_word_cols_mad_of_sums(S, col); o[i] = mfma_finish_words_canonical(col); }      // the same word columns, two conditional subtractions
             else { uint32_t l[9]; blk8_finish_sums_limbs(S, l); o[i] = sbox_lazy29_recoded(l, &k.rc_full29[((size_t)next * t + i) * 9]); }
         }
-        if (next < 0) st = o; else xd = o;
+        if (next >= 0) xd = o; else if (!entry) st = o;
         return 0; };
     for (size_t s = 0; s < n; ++s) {
         for (int j = 0; j < t; ++j) st[j] = ld4(states + 4 * (s * t + j));
         sbox(0);
-        for (int r = 0; r < half; ++r) { const int rc = product(r == half - 1 ? k.mds_pre_frag : k.mds_frag, r == half - 1 ? -1 : r + 1); if (rc) return rc; }
-        fr_t rec[17], yd[9], kx[23];
-        fr29_t u = lazy29_add_c29(fr29_unpack(st[0]).l, &k.rc_partial_scaled29[0]);              // the chain as a lazy residue: lambda_0 X_0 + lambda_0 c_0
-        for (int j = 1; j < t; ++j) rec[j] = recode_signed(st[j]);
+        for (int r = 0; r < half; ++r) { const int rc = product(r == half - 1 ? k.mds_pre_frag : k.mds_frag, r == half - 1 ? -1 : r + 1, r == half - 1); if (rc) return rc; }
+        fr_t yd[9], kx[23];
+        fr29_t zero9; for (int i = 0; i < 9; ++i) zero9.l[i] = 0;
+        // the chain as a lazy residue: row 0's finish limbs through the mailbox slot's layout, plus lambda_0 c_0 — no canonical value at the entry
+        fr29_t u = lazy29_add_c29(lazy29_add_slot(zero9, lazy29_to_slot(l0)).l, &k.rc_partial_scaled29[0]);
+        for (int i = 0; i < 9; ++i) if (u.l[i] >= (1u << 30)) return -4;
         const int nb = k.rp / 8;
         for (int b = 0; b < nb; ++b) {
             const int8_t* ef = k.blk8s_efrag.data() + (size_t)b * 8 * 16 * 1024; const int8_t* lf = k.blk8s_lfrag.data() + (size_t)b * 16 * 8 * 1024;
@@ -346,7 +351,7 @@ int hc_permute_block8(void* h, uint64_t* states, size_t n) {
         }
         const fr29_t x0 = fr29_mul_c29(k.blk8_unscale29.data(), u);                                // lambda_rp X_rp (lazy) -> X_rp (below 1.04 r), once per permutation
         xd[0] = sbox_lazy29_recoded(x0.l, &k.rc_full29[((size_t)half * t) * 9]);            // element 0 of that S-box from the chain's final value
-        for (int r = half; r < k.rf; ++r) { const int rc = product(k.mds_frag, r == k.rf - 1 ? -1 : r + 1); if (rc) return rc; }
+        for (int r = half; r < k.rf; ++r) { const int rc = product(k.mds_frag, r == k.rf - 1 ? -1 : r + 1, false); if (rc) return rc; }
         for (int j = 0; j < t; ++j) st4(states + 4 * (s * t + j), st[j]);
     }
     return 0;
@@ -411,6 +416,20 @@ int hc_mfma_finish_bytes(const int32_t* sums, size_t n, int wide, int64_t* cols,
         for (int i = 0; i < 32; ++i) if (S[i] > lim || S[i] < -lim) return -1;
         int64_t* col = cols + 8 * s;
         if (wide) mfma_word_cols_of_sums<true>(S, col); else mfma_word_cols_of_sums<false>(S, col);
+        const fr_t d = mfma_finish_bytes(col, qh + s, carry + s); memcpy(digits + 32 * s, d.v, 32);
+    }
+    return 0;
+}
+// The byte-domain finish on word columns folded by the MULTIPLY-ADD chain (mfma_word_cols_mad, then mfma_finish_bytes): what the FUSE kernels' product in front
+// of the partial rounds runs for rows 1..16 (pair_mds_sbox_mfma, entry), rows of 17 K-steps.  Outputs as hc_mfma_finish_bytes.  -1: a sum outside
+// |S_c| <= 17 * 32 * 128 * 128.
+int hc_mfma_finish_bytes_mad(const int32_t* sums, size_t n, int64_t* cols, int32_t* qh, int64_t* carry, int8_t* digits) {
+    const int32_t lim = 17 * 32 * 128 * 128;
+    for (size_t s = 0; s < n; ++s) {
+        const int32_t* S = sums + 32 * s;
+        for (int i = 0; i < 32; ++i) if (S[i] > lim || S[i] < -lim) return -1;
+        int64_t* col = cols + 8 * s;
+        mfma_word_cols_mad_of_sums(S, col);
         const fr_t d = mfma_finish_bytes(col, qh + s, carry + s); memcpy(digits + 32 * s, d.v, 32);
     }
     return 0;
@@ -518,13 +537,58 @@ int hc_permute_dense(void* h, uint64_t* states, size_t n) {
 // kernel bodies on the host ---------------------------------------------------------------------------
 }  // extern "C"
 // the 17-lane template of hash_leaf_pair (capi_poseidon.hip ctx_leaf_init)
-static void leaf_init(fr_t init[17]) {
-    const fr_t AB = host::h_tag("FSv1-ABSORB-BYTES"), CH = host::h_tag("FSv1-CHALLENGE");
-    for (int j = 0; j < 17; ++j) init[j] = host::h_zero();
-    init[0] = AB; init[1] = host::h_words("FRI/leaf/poseidon")[0]; init[2] = AB; init[3] = host::h_words("FRI/leaf")[0];
-    init[6] = CH; init[7] = AB; init[8] = host::h_words("leaf")[0]; init[16] = host::h_tag("FSv1-TRANSCRIPT-INIT");
-}
+static void leaf_init(fr_t init[17]) { host::leaf_template(init); }
 extern "C" {
+// Round 0 of the leaf permutation as k_leaf_pair2<true> runs it (poseidon_pair.hpp pair_leaf_round0_mfma), re-enacted: x4 = fr_pow5_r29(f + rc[4]) and
+// x5 = fr_pow5_r29(f_next + rc[5]) (f_next == nullptr: the zero input) recoded, one emulated tile of TWO K-steps per element — fragments (i, 4), (i, 5) of
+// mds_frag —, the kernels' fold and finish to nine limbs (word columns, mfma_finish_words), then round 1's S-box on the limbs plus the table entry.  n leaves, one
+// f and one f_next each.  Out (each optional): the template (17 stored elements), the table (K_i + rc_full[17 + i]) mod r as 17 x 9 limbs (host_util.hpp
+// leaf_round0_consts, what ctx_leaf_init uploads), x4 and x5 as stored (n x 2 elements), the rows' finish limbs (n x 17 x 9) and the canonical S-box outputs of
+// round 1 (n x 17 elements).  -1: not a t = 17 set with fragment tables; -2: a digit sum beyond two K-steps' bound.
+int hc_leaf_round0(void* tparams, const uint64_t* f, const uint64_t* f_next, size_t n, uint64_t* init_out, uint32_t* table_out, uint64_t* x45_out, uint32_t* limbs_out, uint64_t* sbox_out) {
+    HcParams* P = (HcParams*)tparams; const host::KernelConsts& k = P->kc;
+    if (k.t != 17 || k.mds_frag.empty() || k.rf < 2) return -1;
+    fr_t init[17], K[17]; uint32_t krc29[17 * 9];
+    leaf_init(init); host::leaf_round0_consts(P->ref, init, K, krc29);
+    if (init_out) for (int j = 0; j < 17; ++j) st4(init_out + 4 * j, init[j]);
+    if (table_out) memcpy(table_out, krc29, sizeof(krc29));
+    for (size_t s = 0; s < n; ++s) {
+        fr_t x[2], xd[2];
+        x[0] = fr_pow5_r29<PF>(fr_add<PF>(ld4(f + 4 * s), k.rc_full[4]));
+        x[1] = fr_pow5_r29<PF>(fr_add<PF>(f_next ? ld4(f_next + 4 * s) : host::h_zero(), k.rc_full[5]));
+        for (int e = 0; e < 2; ++e) { xd[e] = recode_signed(x[e]); if (x45_out) st4(x45_out + 4 * (2 * s + e), x[e]); }
+        for (int i = 0; i < 17; ++i) {
+            const int8_t* fr[2] = {&k.mds_frag[((size_t)i * 17 + 4) * 1024], &k.mds_frag[((size_t)i * 17 + 5) * 1024]};
+            int32_t S[32]; if (blk8_tile_sums(fr, xd, 2, S)) return -2;
+            for (int c = 0; c < 32; ++c) if (S[c] > 2 * 32 * 128 * 128 || S[c] < -2 * 32 * 128 * 128) return -2;
+            uint32_t l[9]; blk8_finish_sums_limbs(S, l);
+            if (limbs_out) memcpy(limbs_out + 9 * (17 * s + i), l, sizeof(l));
+            if (sbox_out) st4(sbox_out + 4 * (17 * s + i), sbox_lazy29(l, &krc29[9 * i]));
+        }
+    }
+    return 0;
+}
+// the squeeze round's field row (KernelConsts::row0 = M[0][*], stored elements); copies at most cap elements out, returns the row's length
+size_t hc_row0_table(void* h, uint64_t* out, size_t cap) {
+    const std::vector<fr_t>& v = ((HcParams*)h)->kc.row0;
+    if (out) for (size_t i = 0; i < v.size() && i < cap; ++i) st4(out + 4 * i, v[i]);
+    return v.size();
+}
+// The squeeze row as the t = 17 wave-pair kernels run it (poseidon_pair.hpp pair_squeeze_row_mfma), re-enacted: n states of 17 canonical S-box outputs, recoded,
+// one emulated tile of 17 K-steps against fragments (0, e) of mds_frag, the word-column fold and the canonical finish -> element 0 of M x.
+// -1: not a t = 17 set with fragment tables; -2: a digit sum out of range.
+int hc_squeeze_row(void* h, const uint64_t* states, size_t n, uint64_t* out) {
+    HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc;
+    if (k.t != 17 || k.mds_frag.empty()) return -1;
+    const int8_t* fr[17]; for (int e = 0; e < 17; ++e) fr[e] = &k.mds_frag[(size_t)e * 1024];
+    for (size_t s = 0; s < n; ++s) {
+        fr_t xd[17]; for (int e = 0; e < 17; ++e) xd[e] = recode_signed(ld4(states + 4 * (17 * s + e)));
+        int32_t S[32]; if (blk8_tile_sums(fr, xd, 17, S)) return -2;
+        int64_t col[8]; mfma_word_cols_mad_of_sums(S, col);
+        st4(out + 4 * s, mfma_finish_words_canonical(col));
+    }
+    return 0;
+}
 int hc_leaf_pair(void* tparams, const uint64_t* f, const uint64_t* f_next, size_t n, size_t m, uint64_t* hout) {
     HcParams* P = (HcParams*)tparams;
     fr_t init[17]; leaf_init(init);

@@ -3,7 +3,7 @@
 // in limb form and the lazy chain of the 8-round blocks (slot layout, limb adds, unreduced recode).
 // poseidon_pair.hpp includes it for the t = 17 wave-pair kernels (exchange and tile handling stay there); hostcheck.cpp and tools/mfma_finish_check.cpp
 // run the same statements on the CPU against the L*U rows and against big integers (tests/test_hostcheck.py,
-// tests/test_full_round_residue_tables_host.py, tests/test_limb_handover_host.py, tests/test_lazy_residue_host.py, tests/test_byte_finish_host.py, tests/test_word_fold_host.py).  The host-only part at the end: the row-order entry of the fold
+// tests/test_full_round_residue_tables_host.py, tests/test_limb_handover_host.py, tests/test_lazy_residue_host.py, tests/test_byte_finish_host.py, tests/test_word_fold_host.py, tests/test_permutation_edges_host.py).  The host-only part at the end: the row-order entry of the fold
 // (mfma_cols_of_sums, mfma_word_cols_of_sums, mfma_word_cols_mad_of_sums) and the 128-bit column census of the S-box (Lazy29Wide).
 #pragma once
 #include "fr.hpp"

@@ -54,6 +54,7 @@ template <int T> struct PairCfg {
     __host__ __device__ static constexpr int dslot(int q) { return 1 + (q % NXD); }
     __host__ __device__ static constexpr size_t lds_bytes() { return (size_t)(T + EXTRA) * 2 * 64 * 16; }
 };
+constexpr int kLeafKrcOff = 51 + 40;      // k_leaf_pair2's constant blob (capi_poseidon.hip ctx_leaf_init): elements from K to the table of (K_i + round 1's constant) as 17 x 9 limbs
 static inline size_t pair_lds_bytes(int t) { return t == 17 ? PairCfg<17>::lds_bytes() : PairCfg<9>::lds_bytes(); }
 
 struct PairState {
@@ -183,16 +184,22 @@ __device__ __forceinline__ void mfma_post_limbs(const mfma_v16i (&acc)[2], uint3
     mfma_finish_words(col, l);
 }
 // The limb-form hand-over of a row: its nine finish limbs l (mfma_finish_words) go straight through the next full round's S-box (rc29: that round's constant
-// for element j, nine limbs) and into slot j as the next product's operand (recoded; canonical, not recoded, in front of the squeeze round).  No canonical value
-// in between.  The finish itself stays at the two call sites: taken in here as well, k_node16_pair<true> holds one VGPR more than before the merge (245).
-__device__ __forceinline__ void pair_sto_sbox29(const PairState& s, int j, const uint32_t* l, const uint32_t* rc29, bool recode) {
-    const fr29_t x5 = pow5_lazy29(lazy29_add_c29(l, rc29));
-    s.sto(j, recode ? recode_lazy29(x5) : fr29_pack_reduce<PF>(x5.l));      // recoded from the unreduced x5 (below 1.04 r); canonical for the squeeze round's dot product
+// for element j, nine limbs) and into slot j as the next product's operand, recoded — the squeeze round's too: its row runs on the matrix cores
+// (pair_squeeze_row_mfma).  No canonical value in between.  The finish itself stays at the two call sites: taken in here as well, k_node16_pair<true> holds one VGPR more than before the merge (245).
+__device__ __forceinline__ void pair_sto_sbox29(const PairState& s, int j, const uint32_t* l, const uint32_t* rc29) {
+    s.sto(j, recode_lazy29(pow5_lazy29(lazy29_add_c29(l, rc29))));      // recoded from the unreduced x5 (below 1.04 r)
 }
 // The product.  Precondition: every state slot holds a recoded S-box output and a barrier has passed.  rc29 == nullptr: ends with the state canonical and
 // consistent.  Otherwise rc29 = the NEXT full round's constants (17 x 9 limbs) and every row is handed to that round's S-box in the wave that formed it
 // (pair_sto_sbox29) — X the even elements, Y the odd ones, nothing crosses waves: no LDS round trip, no standalone S-box pass and one barrier less per round.
-__device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const void* frag, const uint32_t* rc29, bool recode) {
+// entry (rc29 == nullptr; the FUSE kernels' product in front of the partial rounds, frag = mds_pre_frag): the rows end as the 8-round blocks take them, no
+// canonical value, no recode pass and no further barrier — rows 1..16, the lanes, as the digits of their signed residue (mfma_finish_bytes on the same word
+// columns: rows of 17 K-steps, |S_c| <= 8 912 896, |col| <= 16 843 009 |S| < 2^47.1, the bound stated there for the wide rows); row 0, the chain value, as its
+// nine finish limbs in the mailbox layout (lazy29_to_slot) in slot kEntrySlot, which wave X — the wave that formed it — reads back as the chain's start.  That
+// slot is H's mailbox of the ODD rounds: Y first writes it in round 1, behind barrier_0, which X passes after its read.  (Slot 0, the even rounds' mailbox, is
+// written by Y inside round 0: a read of it with no barrier in between would race.)
+constexpr int kEntrySlot = 17 + 2;
+__device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const void* frag, const uint32_t* rc29, bool entry = false) {
     constexpr int T = 17;
     const int lane = s.lane, h = lane >> 5;
     mfma_v4i b[T][2];
@@ -216,10 +223,49 @@ __device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const voi
         // one fold and exchange in front of both ends: with the canonical end on its own path (mfma_post) the FUSE kernels spill
         int64_t col[8];
         mfma_post_words(acc, col);
-        if (rc29) { uint32_t l[9]; mfma_finish_words(col, l); pair_sto_sbox29(s, i, l, c29(rc29, i), recode); }
+        if (rc29) { uint32_t l[9]; mfma_finish_words(col, l); pair_sto_sbox29(s, i, l, c29(rc29, i)); }
+        else if (entry) {
+            if (i == 0) { uint32_t l[9]; mfma_finish_words(col, l); s.sto(kEntrySlot, lazy29_to_slot(l)); }
+            else s.sto(i, mfma_finish_bytes(col));
+        }
         else s.sto(i, mfma_finish_words_canonical(col));
     }
     __syncthreads();
+}
+
+// slot j (recoded) as the B operand of column tile ct: half (lane >> 5) of the element of sponge 32 ct + (lane & 31)
+__device__ __forceinline__ mfma_v4i blk8_b_of_slot(const PairState& s, int j, int ct) {
+    const uint4 u = s.st[(2 * j + (s.lane >> 5)) * 64 + 32 * ct + (s.lane & 31)];
+    return mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
+}
+// The squeeze round's product when only element 0 is wanted: ROW 0 of the same product, one row of the pipeline in the calling wave alone — 34 MFMAs with the
+// B operands read from the slots as they are consumed, one fold and exchange, the canonical finish (|S_c| <= 17 * 32 * 128 * 128, the full rounds' bound; W below
+// 3 r: mfma_finish_words_canonical).  Precondition as for the product: every slot a recoded S-box output, a barrier since.  No barrier inside: the caller runs it
+// in wave X between two barriers that both waves pass.
+__device__ __forceinline__ fr_t pair_squeeze_row_mfma(const PairState& s, const void* frag) {
+    constexpr int T = 17;
+    const mfma_v4i* A = reinterpret_cast<const mfma_v4i*>(frag) + s.lane;      // fragments (0, e)
+    mfma_v16i acc[2];
+    mfma_zero_tile(acc);
+    // eight fragments in flight at a time: with all 17 fragments and 34 operands hoisted above the MFMAs every k_hash_ds2<17> instantiation spilled
+#pragma unroll 1
+    for (int e0 = 0; e0 < 16; e0 += 8) {
+        mfma_v4i a[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] = A[(size_t)(e0 + k) * 64];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[k], blk8_b_of_slot(s, e0 + k, ct), acc[ct], 0, 0, 0);
+    }
+    {
+        const mfma_v4i a = A[(size_t)16 * 64];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, blk8_b_of_slot(s, 16, ct), acc[ct], 0, 0, 0);
+    }
+    int64_t col[8];
+    mfma_post_words(acc, col);
+    return mfma_finish_words_canonical(col);
 }
 
 // ---- partial rounds in BLOCKS OF 8, both long products on the matrix cores (T = 17, rp % 8 == 0) ------------------------------------------------------
@@ -270,15 +316,44 @@ struct Blk8Cfg {
     __host__ __device__ static constexpr int ymail(int q) { return 17 + (q & 1); }
     __host__ __device__ static constexpr int hmail(int q) { return (q & 1) ? 19 : 0; }
 };
+static_assert(kEntrySlot == Blk8Cfg::hmail(1) && kEntrySlot != Blk8Cfg::hmail(0) && kEntrySlot != Blk8Cfg::ymail(0), "the entry row's slot is untouched until barrier_0");
 // A is wave-uniform and the lane is added at the load: a scalar base plus one 32-bit lane offset
 __device__ __forceinline__ void blk8_load_frags16(mfma_v4i (&a)[16], const mfma_v4i* A, int lane) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) a[e] = (A + (size_t)e * 64)[lane];
 }
-// slot j (recoded) as the B operand of column tile ct: half (lane >> 5) of the element of sponge 32 ct + (lane & 31)
-__device__ __forceinline__ mfma_v4i blk8_b_of_slot(const PairState& s, int j, int ct) {
-    const uint4 u = s.st[(2 * j + (s.lane >> 5)) * 64 + 32 * ct + (s.lane & 31)];
-    return mfma_v4i{(int)u.x, (int)u.y, (int)u.z, (int)u.w};
+// Round 0 of the leaf permutation through the same row pipeline with TWO K-steps: 15 of the 17 lanes of hash_leaf_pair's template are constants, so round 0's
+// product is K_i + M[i][4] x4 + M[i][5] x5 (host_util.hpp leaf_round0_consts), a dense row with two live columns and a constant.  Precondition: slots 4 and 5 hold
+// x4 and x5 RECODED and a barrier has passed.  Row i = fragments (i, 4), (i, 5) of the full rounds' table against the two operands, fold and exchange and finish
+// as every fused row (mfma_post_limbs), and the hand-over to round 1's S-box with krc29[i] = (K_i + rc_full[17 + i]) mod r as its constant — X the even rows,
+// Y the odd ones.  Ends like pair_sbox_full<17, true> of round 1: every slot a recoded S-box output, behind a barrier.
+//   digit sums  |S_c| <= 2 * 32 * 128 * 128 = 1 048 576 = 2^20, far inside mfma_word_cols_mad's domain (23 K-steps);
+//   S-box input u = W + krc29[i] with W < 3 r + 2^146 (mfma_finish_words) and the constant canonical: u < 4 r + 2^146 < 4.0001 r, limbs below 2^30 — the fused
+//               rows' bound, inside pow5_lazy29's 4.25 r.
+__device__ __forceinline__ void pair_leaf_round0_mfma(const PairState& s, const void* frag, const uint32_t* krc29) {
+    constexpr int T = 17;
+    mfma_v4i b[2][2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) b[e][ct] = blk8_b_of_slot(s, 4 + e, ct);
+    __syncthreads();                                   // both waves hold x4 and x5: slots 4 and 5 may be overwritten
+    const mfma_v4i* A = reinterpret_cast<const mfma_v4i*>(frag) + s.lane;
+#pragma unroll 1
+    for (int i = s.isY ? 1 : 0; i < T; i += 2) {
+        mfma_v16i acc[2];
+        mfma_zero_tile(acc);
+        const mfma_v4i* Ai = A + ((size_t)i * T + 4) * 64;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const mfma_v4i a = Ai[(size_t)e * 64];
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
+        }
+        uint32_t l[9]; mfma_post_limbs(acc, l);
+        pair_sto_sbox29(s, i, l, c29(krc29, i));
+    }
+    __syncthreads();
 }
 // round Q in wave X: u = lambda_Q X_Q + lambda_Q c_Q on entry, the same of round Q + 1 on exit, as a LAZY residue (nine limbs below 2^30, below 3.05 r:
 // mfma_digits.hpp); no field element is formed.  b[Q]: yt_Q as B operands on exit
@@ -319,11 +394,11 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
 }
 // the lane product: s_j <- s_j + sum_p w_{p,j} y_p for this wave's share of the lanes (X lanes 1..NLX, Y the rest), b: y_0..y_7 as B operands.  Ends with a barrier.
 // rc29_next != nullptr (FUSE, the permutation's last block): the constants of the full round that follows, 17 x 9 limbs; lane j then goes from its nine finish
-// limbs through that round's S-box (sbox_lazy29) and is stored as the round's operand (recoded unless that round is the squeeze round), like a fused product row.
+// limbs through that round's S-box (sbox_lazy29) and is stored recoded as the round's operand, like a fused product row.
 // LAZY (the FUSE kernels): between two blocks a lane is stored as the digits of its SIGNED residue, finished in the byte domain (mfma_post_bytes: word columns
 // folded where the sums sit, a quotient estimate, one pass over eight words; no 29-bit limbs, no conditional subtraction).  k_hash_ds2 keeps canonical lanes: with the signed form k_hash_ds2<17, DsBatchStream, true> spilled 6 VGPRs (28 B of scratch).
 template <int NLX, bool LAZY = false>
-__device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], bool last, const uint32_t* rc29_next = nullptr, bool recode_next = true) {
+__device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], bool last, const uint32_t* rc29_next = nullptr) {
     static_assert(NLX >= 1 && NLX <= 15, "shares");
     const int lane = s.lane;
     const int j0 = s.isY ? NLX + 1 : 1, j1 = s.isY ? 16 : NLX;
@@ -345,7 +420,7 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
 #pragma unroll
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
         // slot j is read by this wave alone, before this write
-        if (rc29_next) { uint32_t l[9]; mfma_post_limbs(acc, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
+        if (rc29_next) { uint32_t l[9]; mfma_post_limbs(acc, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j)); }
         else if (LAZY && !last) s.sto(j, mfma_post_bytes(acc));
         else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }      // between two blocks: the signed residue's digits, no canonical value
     }
@@ -356,7 +431,7 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
 // With rc29_next (FUSE, last block): every slot ends as the next full round's S-box output instead — the lanes through blk8_lane_rows, element 0 from the chain's
 // final value (lazy, no constant in it), brought back from lambda_rp X_rp by one product with unscale29 = 1 / lambda_rp first and handed to the S-box as limbs.
 template <int NLX, bool LAZY = false>
-__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr29_t& u, bool last, const uint32_t* rc29_next = nullptr, bool recode_next = true,
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr29_t& u, bool last, const uint32_t* rc29_next = nullptr,
                                             const uint32_t* unscale29 = nullptr) {
     mfma_v4i b[8][2];
     if (!s.isY) {
@@ -370,8 +445,8 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
     }
     __builtin_amdgcn_sched_barrier(0);
     // slot 0 was H's mailbox in the even rounds, last read by X after barrier_6; the lane rows' closing barrier publishes the store
-    if (rc29_next && !s.isY) { const fr29_t x = fr29_mul_c29(unscale29, u); pair_sto_sbox29(s, 0, x.l, c29(rc29_next, 0), recode_next); }
-    blk8_lane_rows<NLX, LAZY>(s, Tb, b, last, rc29_next, recode_next);
+    if (rc29_next && !s.isY) { const fr29_t x = fr29_mul_c29(unscale29, u); pair_sto_sbox29(s, 0, x.l, c29(rc29_next, 0)); }
+    blk8_lane_rows<NLX, LAZY>(s, Tb, b, last, rc29_next);
 }
 
 // s_j += w_{0,j} x0 + w_{1,j} x1 + w_{2,j} x2 + w_{3,j} x3   (one reduction)
@@ -388,46 +463,61 @@ __device__ __forceinline__ fr_t pair_lane_update(const uint32_t* sp, int j, cons
 }
 
 // One permutation by the wave pair.  Precondition: state consistent (a barrier since the last write).
-// Returns lane 0 of the result in BOTH waves; with only0 the rest of the state is dead afterwards.
+// Returns lane 0 of the result; with only0 in wave X ALONE (every caller stores it from there), and the rest of the state is dead afterwards.
 // BLK8 (T = 17, a parameter set with blk8 tables): the partial rounds in blocks of 8 (pair_block8) instead of blocks of 4.
-// Precondition of BLK8: when the partial rounds are entered, lanes 1..16 are CANONICAL (recode_signed needs x < r).  The full round before them leaves
-// them so (mfma_finish_cols); with r_begin >= rf / 2 no full round runs first and the caller's stores must be canonical (today's callers store fr_add
-// results and field elements from memory).
+// Precondition of BLK8 without FUSE: when the partial rounds are entered, lanes 1..16 are CANONICAL (recode_signed needs x < r).  The full round before them
+// leaves them so (mfma_finish_words_canonical); with r_begin >= rf / 2 no full round runs first and the caller's stores must be canonical (today's callers
+// store fr_add results and field elements from memory).  With FUSE the product of round rf / 2 - 1 leaves the lanes and the chain value as the first block
+// takes them (pair_mds_sbox_mfma, entry), so r_begin < rf / 2 is required: the launchers only pick the 8-round form for sets with rf >= 2.
 // FUSE (BLK8 only, its default): every full-round product that is followed by a full round hands its rows to that round's S-box in limb form
 // (pair_mds_sbox_mfma), and the last block's lane rows hand theirs to the S-box after the partial rounds (blk8_lane_rows).  k_hash_ds2 turns it off: its generic stream state is live across the permutation, and with the S-box's columns beside the product's
 // operand registers three of its instantiations took 88 / 36 / 52 B of scratch against 44 / 12 / 28 B without (the two fixed-shape kernels hold 244 VGPRs, none spilled).
-template <int T, bool BLK8 = false, bool FUSE = BLK8>
+// SBOXED (FUSE only; k_leaf_pair2<true>): the caller's own product in front of round r_begin has handed its rows to that round's S-box already
+// (pair_leaf_round0_mfma), so every slot holds a recoded S-box output behind a barrier and the standalone S-box is skipped.  Needs r_begin < rf / 2: a full-round
+// product follows.
+template <int T, bool BLK8 = false, bool FUSE = BLK8, bool SBOXED = false>
 __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonDev& P, bool only0, int r_begin = 0) {
     static_assert(!BLK8 || T == 17, "8-round blocks exist for t = 17");
     static_assert(!FUSE || BLK8, "the fused hand-over belongs to the 8-round form");
+    static_assert(!SBOXED || FUSE, "entering behind an S-box belongs to the fused form");
     typedef PairCfg<T> Cfg;
     constexpr int NXD = Cfg::NXD, NXU = Cfg::NXU, W = 2 * T - 1;
     const int half = P.rf / 2;
     if constexpr (FUSE) {
-        // one standalone S-box, then every product hands its rows to the next round's S-box in limb form; the product in front of the partial rounds ends canonical
-        if (r_begin < half) pair_sbox_full<T, true>(s, P.rc_full + r_begin * T);
+        // one standalone S-box, then every product hands its rows to the next round's S-box in limb form; the product in front of the partial rounds ends as the
+        // first block takes its rows (entry): needs r_begin < rf / 2, which the launchers see to (pair_block8_form)
+        if constexpr (!SBOXED) { if (r_begin < half) pair_sbox_full<T, true>(s, P.rc_full + r_begin * T); }
         for (int r = r_begin; r < half; ++r)
-            pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, (r == half - 1) ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T), true);
+            pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, (r == half - 1) ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T), r == half - 1);
     } else
     for (int r = r_begin; r < half; ++r) {
-        if constexpr (T == 17) { pair_sbox_full<T, true>(s, P.rc_full + r * T); pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, nullptr, true); }
+        if constexpr (T == 17) { pair_sbox_full<T, true>(s, P.rc_full + r * T); pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, nullptr); }
         else { pair_sbox_full<T>(s, P.rc_full + r * T); pair_apply_lu<T>(s, (r == half - 1) ? P.lu_pre29 : P.lu29); }
     }
     fr_t s0 = fr_zero<PF>();
-    if (!s.isY) s0 = s.ld(0);
+    if constexpr (!FUSE) { if (!s.isY) s0 = s.ld(0); }
     if constexpr (BLK8) {
         // the chain as nine limbs from here to the unscale product; the first constant (lambda_0 = 1) enters here, every later one in Y's finish
-        fr29_t u = fr29_unpack(s0);
-        if (!s.isY) u = lazy29_add_c29(u.l, c29(P.rc_partial_scaled29, 0));      // canonical + canonical: below 2 r, limbs below 2^30
-        for (int j = s.isY ? 9 : 1; j <= (s.isY ? 16 : 8); ++j) s.sto(j, recode_signed(s.ld(j)));        // canonical since the full round's finish
-        __syncthreads();
+        fr29_t u;
+        if constexpr (FUSE) {
+            // the entry product left the lanes as digits and row 0 as its finish limbs W (below 3 r + 2^146, limbs below 2^29) behind its closing barrier:
+            // u = W + lambda_0 c_0 below 4 r + 2^146 < 4.0001 r with limbs below 2^30, the fused rows' bound, inside pow5_lazy29's 4.25 r
+#pragma unroll
+            for (int i = 0; i < 9; ++i) u.l[i] = 0;
+            if (!s.isY) { u = lazy29_add_slot(u, s.ld(kEntrySlot)); u = lazy29_add_c29(u.l, c29(P.rc_partial_scaled29, 0)); }
+        } else {
+            u = fr29_unpack(s0);
+            if (!s.isY) u = lazy29_add_c29(u.l, c29(P.rc_partial_scaled29, 0));      // canonical + canonical: below 2 r, limbs below 2^30
+            for (int j = s.isY ? 9 : 1; j <= (s.isY ? 16 : 8); ++j) s.sto(j, recode_signed(s.ld(j)));        // canonical since the full round's finish
+            __syncthreads();
+        }
         const int nb = P.rp / 8;
 #pragma unroll 1
         for (int b = 0; b < nb; ++b) {
             const Blk8Tabs Tb{reinterpret_cast<const mfma_v4i*>(P.blk8_efrag) + (size_t)b * 8 * 16 * 64, reinterpret_cast<const mfma_v4i*>(P.blk8_lfrag) + (size_t)b * 16 * 8 * 64,
                               reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), reinterpret_cast<const mfma_v4i*>(P.blk8_gfrag) + (size_t)b * 28 * 64,
                               c29(P.rc_partial_scaled29, (size_t)8 * b + 1)};
-            if constexpr (FUSE) pair_block8<Blk8Cfg::NLX, true>(s, Tb, u, b == nb - 1, b == nb - 1 ? c29(P.rc_full29, (size_t)half * T) : nullptr, !(only0 && half == P.rf - 1), P.blk8_unscale29());
+            if constexpr (FUSE) pair_block8<Blk8Cfg::NLX, true>(s, Tb, u, b == nb - 1, b == nb - 1 ? c29(P.rc_full29, (size_t)half * T) : nullptr, P.blk8_unscale29());
             else pair_block8<Blk8Cfg::NLX>(s, Tb, u, b == nb - 1);
         }
         // FUSE: the chain value was unscaled inside the last block, in front of element 0's S-box; otherwise the state's element 0 ends canonical here
@@ -489,12 +579,20 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
     if constexpr (!FUSE) {
         if (!s.isY) s.sto(0, s0);
         __syncthreads();
-    }   // FUSE: the last block left round half's S-box outputs in every slot (recoded unless it is the squeeze round), behind its closing barrier
+    }   // FUSE: the last block left round half's S-box outputs recoded in every slot, behind its closing barrier
     for (int r = half; r < P.rf; ++r) {
         const bool squeeze = only0 && r == P.rf - 1;
         if constexpr (FUSE) { /* this round's S-box ran with the row that fed it */ }
-        else if constexpr (T == 17) { if (squeeze) pair_sbox_full<T>(s, P.rc_full + r * T); else pair_sbox_full<T, true>(s, P.rc_full + r * T); }
+        else if constexpr (T == 17) pair_sbox_full<T, true>(s, P.rc_full + r * T);
         else pair_sbox_full<T>(s, P.rc_full + r * T);
+        if constexpr (T == 17) {
+            if (squeeze) {                                  // squeeze: row 0 only, one matrix-core row in wave X (X-only work between two barriers both waves pass)
+                fr_t out = fr_zero<PF>();
+                if (!s.isY) out = pair_squeeze_row_mfma(s, P.mds_frag);
+                __syncthreads();                            // the slots are reused by the next permutation
+                return out;
+            }
+        } else
         if (squeeze) {                                      // squeeze: row 0 only, split over the two waves
             const int j0 = s.isY ? Cfg::NX : 0, j1 = s.isY ? T : Cfg::NX;
             DotAcc acc; acc.init();
@@ -506,8 +604,8 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
             __syncthreads();                                 // the slots are reused by the next permutation
             return out;
         }
-        if constexpr (FUSE) pair_mds_sbox_mfma(s, P.mds_frag, r == P.rf - 1 ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T), !(only0 && r + 1 == P.rf - 1));
-        else if constexpr (T == 17) pair_mds_sbox_mfma(s, P.mds_frag, nullptr, true); else pair_apply_lu<T>(s, P.lu29);
+        if constexpr (FUSE) pair_mds_sbox_mfma(s, P.mds_frag, r == P.rf - 1 ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T));
+        else if constexpr (T == 17) pair_mds_sbox_mfma(s, P.mds_frag, nullptr); else pair_apply_lu<T>(s, P.lu29);
     }
     return s.ld(0);
 }
@@ -527,7 +625,18 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
     const size_t i = (size_t)blockIdx.x * 64 + s.lane; const bool live = i < n; const size_t ii = live ? i : n - 1;   // tail lanes recompute the last leaf
     // Round 0 in closed form: 15 of the 17 lanes of the transcript template are constants, so after ARK and
     // S-box the MDS output is  K_i + M[i][4]*x4 + M[i][5]*x5  with K precomputed on the host
-    // (leafc = [K(17) | M[:,4](17) | M[:,5](17)]).  Both waves compute x4, x5; each fills its own lanes.
+    // (leafc = [K(17) | M[:,4](17) | M[:,5](17) | the two columns in radix 2^29 | (K + round 1's constants)(17 x 9 limbs)]).
+    if constexpr (BLK8) {
+        // The 8-round form: X computes x4, Y x5 (the zero input without f_next), each stored recoded; the product is a two-K-step row per element on the
+        // matrix cores, handed to round 1's S-box in limb form (pair_leaf_round0_mfma), and the permutation is entered behind that S-box.
+        const fr_t in = s.isY ? (f_next ? ldg(f_next + ii / m) : fr_zero<PF>()) : ldg(f + ii);
+        s.sto(s.isY ? 5 : 4, recode_signed(fr_pow5_r29<PF>(fr_add<PF>(in, P.rc_full[s.isY ? 5 : 4]))));
+        __syncthreads();
+        pair_leaf_round0_mfma(s, P.mds_frag, reinterpret_cast<const uint32_t*>(leafc + kLeafKrcOff));
+        const fr_t out = pair_permute<17, true, true, true>(s, P, true, 1);
+        if (live && !s.isY) stg(h + i, out);
+    } else {
+    // The blocks of 4 (the comparison form): both waves compute x4, x5; each fills its own lanes on the vector ALU.
     const fr_t x4 = fr_pow5_r29<PF>(fr_add<PF>(ldg(f + ii), P.rc_full[4]));
     const fr_t x5 = fr_pow5_r29<PF>(fr_add<PF>(f_next ? ldg(f_next + ii / m) : fr_zero<PF>(), P.rc_full[5]));
     const int j0 = s.isY ? PairCfg<17>::NX : 0, j1 = s.isY ? 17 : PairCfg<17>::NX;
@@ -541,6 +650,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
     __syncthreads();
     fr_t out = pair_permute<17, BLK8>(s, P, true, 1);
     if (live && !s.isY) stg(h + i, out);
+    }
 }
 
 // K4 (pair form): one Merkle level / the pair-leaf level.

@@ -246,6 +246,56 @@ int main() {
         const size_t idx = (ci * 7 + (size_t)(kk + 1) * 17) % (8 * 17);
         ++n; if (!fr_eq(sbox_lazy29(l, &kc.rc_full29[9 * idx]), fr_pow5_r29<PF>(fr_add<PF>(canon, kc.rc_full[idx])))) { if (bad < 5) fprintf(stderr, "S-box on word-finish limbs: case %zu constant %zu\n", ci, idx); ++bad; }
     }
+    // ---- the once-per-permutation edges on the row pipeline (poseidon_pair.hpp pair_leaf_round0_mfma, pair_squeeze_row_mfma, and the byte-domain finish on
+    // rows of 17 K-steps folded by the multiply-add chain).
+    // (i) The leaf's round 0: rows of TWO K-steps — fragments (i, 4), (i, 5) of mds_frag against x4, x5 (r - 1 / 0 / mixed / random) —, the word-column finish to
+    // limbs and round 1's S-box with the table (K_i + rc_full[17 + i]) of host_util.hpp leaf_round0_consts, against fr_pow5_r29 of K_i + M[i][4] x4 + M[i][5] x5
+    // + rc in the field code; the digit sums inside two K-steps' bound.
+    {
+        const host::PoseidonConsts tc = host::consts_transcript();
+        fr_t init[17], K[17]; uint32_t krc29[17 * 9]; host::leaf_template(init); host::leaf_round0_consts(tc, init, K, krc29);
+        for (int rep = 0; rep < 16; ++rep) {
+            const fr_t x[2] = {rep == 0 ? rm1 : rep == 1 ? host::h_zero() : rep == 2 ? rm1 : rep == 3 ? host::h_zero() : rand_fr(),
+                               rep == 0 ? rm1 : rep == 1 ? host::h_zero() : rep == 2 ? host::h_zero() : rep == 3 ? rm1 : rand_fr()};
+            for (int i = 0; i < 17; ++i) {
+                int64_t S64[32] = {0};
+                for (int e = 0; e < 2; ++e) kstep(&kc.mds_frag[((size_t)i * 17 + 4 + e) * 1024], recode_signed(x[e]), S64);
+                int32_t S[32]; for (int c = 0; c < 32; ++c) { if (S64[c] > 2 * 32 * 128 * 128 || S64[c] < -2 * 32 * 128 * 128) { fprintf(stderr, "round-0 row beyond its bound\n"); return 1; } S[c] = (int32_t)S64[c]; }
+                int64_t col[8]; uint32_t l[9]; mfma_word_cols_mad_of_sums(S, col); mfma_finish_words(col, l);
+                fr_t want = K[i];
+                for (int e = 0; e < 2; ++e) want = host::h_add(want, host::h_mul(host::h_mul(tc.mds[(size_t)i * 17 + 4 + e], k20), x[e]));
+                ++n; if (!fr_eq(sbox_lazy29(l, &krc29[9 * i]), fr_pow5_r29<PF>(fr_add<PF>(want, tc.rc_full[17 + i])))) { if (bad < 5) fprintf(stderr, "leaf round 0: rep %d row %d\n", rep, i); ++bad; }
+            }
+        }
+    }
+    // (ii) The squeeze row: row 0 of mds_frag, 17 K-steps, the word-column fold and the canonical finish against the row0 dot product in the field code.
+    for (int rep = 0; rep < 12; ++rep) {
+        fr_t st[17]; int64_t S64[32] = {0};
+        for (int e = 0; e < 17; ++e) st[e] = rep == 0 ? rm1 : rep == 1 ? host::h_zero() : rep == 2 ? ((e & 1) ? rm1 : host::h_zero()) : rep == 3 ? ((e & 1) ? host::h_zero() : rm1) : rand_fr();
+        fr_t want = host::h_zero();
+        for (int e = 0; e < 17; ++e) { kstep(&kc.mds_frag[(size_t)e * 1024], recode_signed(st[e]), S64); want = host::h_add(want, host::h_mul(host::h_mul(kc.row0[e], k20), st[e])); }
+        int32_t S[32]; for (int c = 0; c < 32; ++c) { if (S64[c] > 17 * 32 * 128 * 128 || S64[c] < -17 * 32 * 128 * 128) { fprintf(stderr, "squeeze row beyond its bound\n"); return 1; } S[c] = (int32_t)S64[c]; }
+        int64_t col[8]; mfma_word_cols_mad_of_sums(S, col);
+        ++n; if (!fr_eq(mfma_finish_words_canonical(col), want)) { if (bad < 5) fprintf(stderr, "squeeze row: rep %d\n", rep); ++bad; }
+    }
+    // (iii) The entry to the partial rounds: the byte-domain finish on columns folded by the multiply-add chain, rows of 17 K-steps — the extremes
+    // |S_c| = 8 912 896, every case above inside that domain (k r +- 1 and k 2^254 +- 1 up to |k| = 2^17 among them) and 20 000 random rows: no carry out of word
+    // 7, and the digits, taken through the unit fragment's K-step and the canonical finish, give the canonical value of the row.
+    {
+        const int32_t L17 = 17 * 32 * 128 * 128;
+        std::vector<std::vector<int32_t>> rows;
+        rows.push_back(std::vector<int32_t>(32, L17)); rows.push_back(std::vector<int32_t>(32, -L17));
+        { std::vector<int32_t> a(32), b(32); for (int c = 0; c < 32; ++c) { a[c] = c & 1 ? -L17 : L17; b[c] = -a[c]; } rows.push_back(a); rows.push_back(b); }
+        for (const auto& s : cases) { bool in = true; for (int32_t v : s) in = in && v <= L17 && v >= -L17; if (in) rows.push_back(s); }
+        for (int i = 0; i < 20000; ++i) { std::vector<int32_t> s(32); for (auto& v : s) v = (int32_t)(rnd() % (2 * (uint64_t)L17 + 1)) - L17; rows.push_back(s); }
+        for (size_t ci = 0; ci < rows.size(); ++ci) {
+            int64_t col[8]; int32_t qh; int64_t carry;
+            mfma_word_cols_mad_of_sums(rows[ci].data(), col);
+            const fr_t d = mfma_finish_bytes(col, &qh, &carry);
+            int64_t U[32] = {0}; kstep(unit, d, U); int32_t S[32]; for (int c = 0; c < 32; ++c) S[c] = (int32_t)U[c];
+            ++n; if (carry != 0 || qh >= (1 << 19) || qh <= -(1 << 19) || !fr_eq(finish(S), finish(rows[ci].data()))) { if (bad < 5) fprintf(stderr, "byte-domain finish on multiply-add columns: case %zu\n", ci); ++bad; }
+        }
+    }
     printf("{\"check\": \"residue tables and finishing step against the portable field code\", \"cases\": %ld, \"mismatches\": %ld}\n", n, bad);
     return bad ? 1 : 0;
 }

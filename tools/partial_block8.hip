@@ -392,6 +392,19 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
     __syncthreads();                                       // barrier_Q: y_Q is posted
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
+// a slot as the shipped hand-over leaves it (recode_lazy29: the signed digits of an unreduced S-box output below 1.04 r) -> the canonical value, for the comparison
+__device__ __forceinline__ fr_t unrecode_reduce(const fr_t& y) {
+    fr_t x; int64_t b = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const int64_t t = (int64_t)(y.v[i] ^ 0x80808080u) - (int64_t)0x80808080u + b; x.v[i] = (uint32_t)t; b = t >> 32; }
+    fr_cond_sub<PF>(x.v, 0u);
+    return x;
+}
+// the hand-over with the canonical store this comparison form measures (the shipped pair_sto_sbox29 always recodes: the squeeze row runs on the matrix cores now)
+__device__ __forceinline__ void proto_sto_sbox29(const PairState& s, int j, const uint32_t* l, const uint32_t* rc29, bool recode) {
+    const fr29_t x5 = pow5_lazy29(lazy29_add_c29(l, rc29));
+    s.sto(j, recode ? recode_lazy29(x5) : fr29_pack_reduce<PF>(x5.l));
+}
 template <int NLX>
 __device__ __forceinline__ void lane_rows_fused(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], const uint32_t* rc29_next, bool recode_next) {
     const int lane = s.lane;
@@ -413,7 +426,7 @@ __device__ __forceinline__ void lane_rows_fused(const PairState& s, const Blk8Ta
         const int jn = j < j1 ? j + 1 : j1;                // the last row fetches its own fragments again: in bounds, unused
 #pragma unroll
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
-        { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); mfma_finish_limbs(col, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
+        { int64_t col[9]; uint32_t l[9]; mfma_post_cols(acc, col); mfma_finish_limbs(col, l); proto_sto_sbox29(s, j, l, c29(rc29_next, j), recode_next); }
     }
     __syncthreads();
 }
@@ -432,7 +445,7 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
     }
     __builtin_amdgcn_sched_barrier(0);
     if (rc29_next) {
-        if (!s.isY) { const fr29_t x = fr29_mul_c29(unscale29, u); pair_sto_sbox29(s, 0, x.l, c29(rc29_next, 0), false); }
+        if (!s.isY) { const fr29_t x = fr29_mul_c29(unscale29, u); proto_sto_sbox29(s, 0, x.l, c29(rc29_next, 0), false); }
         lane_rows_fused<NLX>(s, Tb, b, rc29_next, false);
     } else blk8_lane_rows<NLX, true>(s, Tb, b, false);
 }
@@ -480,8 +493,10 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
             const Blk8Tabs Tb{Tp.sefrag + (size_t)blk * 8 * 16 * 64, Tp.slfrag + (size_t)blk * 16 * 8 * 64, Tp.unit, Tp.sgfrag + (size_t)blk * 28 * 64, c29(Tp.src29, 1)};
             fr29_t u = fr29_unpack(s0);
             if (!s.isY) u = lazy29_add_c29(u.l, c29(Tp.src29, 0));
-            if constexpr (YG == -8) pair_block8<NLX, true>(s, Tb, u, true, Tp.zero29, false, Tp.unscale8);
-            else limbrows::pair_block8<NLX>(s, Tb, u, YG == -7 ? Tp.zero29 : nullptr, Tp.unscale8);
+            if constexpr (YG == -8) {
+                pair_block8<NLX, true>(s, Tb, u, true, Tp.zero29, Tp.unscale8);
+                if (rep == 0) for (int j = s.isY ? 9 : 0; j <= (s.isY ? 16 : 8); ++j) s.sto(j, limbrows::unrecode_reduce(s.ld(j)));      // each wave its own slots, read back by itself below
+            } else limbrows::pair_block8<NLX>(s, Tb, u, YG == -7 ? Tp.zero29 : nullptr, Tp.unscale8);
             if constexpr (YG == -6) { if (rep == 0 && !s.isY) s0 = fr29_pack_reduce<PF>(fr29_mul_c29(Tp.unscale8, u).l); }
             else if (rep == 0 && !s.isY) s0 = s.ld(0);          // the closing barrier of the lane rows published slot 0
         } else {
