@@ -72,30 +72,15 @@ static inline row::Consts row_consts_of(const stark_ctx* ctx) {
     const RowConstsHost h = row_consts_host(); row::Consts RK; for (int i = 0; i < 9; ++i) RK.ni[i] = h.ni[i]; for (int i = 0; i < 5; ++i) RK.t[i] = h.t[i]; RK.dbg = (uint32_t)ctx->opt.sponge_debug; return RK;
 }
 
-// leaf template of hash_leaf_pair (fri.rs:38-44)
-static int32_t ctx_leaf_init(stark_ctx* ctx, fr_t** out) {
+// the leaf constants of hash_leaf_pair (fri.rs:38-44) on the device: the template and round 0 in closed form (LeafConsts)
+static int32_t ctx_leaf_init(stark_ctx* ctx, const LeafConsts** out) {
     if (!ctx->leaf_init) {
-        fr_t init[17]; host::leaf_template(init);      // lanes 4,5 = (f, s)
-        // closed form of round 0 for the wave-pair kernels (host_util.hpp leaf_round0_consts): K_i = sum_{j != 4,5} M[i][j] * (init_j + rc0_j)^5, then columns 4 and 5 of M
         stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
-        const host::PoseidonConsts& c = tp->ref;
-        // + columns 4, 5 of M as 34 x 9 words in radix 2^29 (306 words = 38.25 elements: k_leaf_pair2<false>) + (K_i + round 1's constant) as 17 x 9 limbs
-        // (153 words = 19.125 elements: k_leaf_pair2<true>, kLeafKrcOff elements behind K)
-        fr_t blob[17 + 51 + 40 + 20];
-        static_assert(kLeafKrcOff == 51 + 40, "k_leaf_pair2<true> reads its table at leafc + kLeafKrcOff");
-        for (auto& x : blob) x = host::h_zero();
-        for (int j = 0; j < 17; ++j) blob[j] = init[j];
-        host::leaf_round0_consts(c, init, &blob[17], reinterpret_cast<uint32_t*>(&blob[17 + kLeafKrcOff]));
-        for (int i = 0; i < 17; ++i) {
-            blob[34 + i] = c.mds[(size_t)i * 17 + 4]; blob[51 + i] = c.mds[(size_t)i * 17 + 5];
-            uint32_t* m45 = reinterpret_cast<uint32_t*>(&blob[68]);
-            const fr_t k20 = fr_from_u64<PallasFr>(1ull << FR29_SBOX_SHIFT);     // the S-box outputs x4, x5 arrive divided by 2^20 (fr_pow5_r29)
-            fr29_const_from<PallasFr>(host::h_mul(c.mds[(size_t)i * 17 + 4], k20), m45 + 9 * i); fr29_const_from<PallasFr>(host::h_mul(c.mds[(size_t)i * 17 + 5], k20), m45 + 9 * (17 + i));
-        }
-        DevMem d; STARK_TRY(d.fill_sync(ctx, blob, sizeof(blob)));
+        LeafConsts lc; host::leaf_consts(tp->ref, lc);
+        DevMem d; STARK_TRY(d.fill_sync(ctx, &lc, sizeof lc));
         ctx->leaf_init = std::move(d);
     }
-    *out = ctx->leaf_init.fr(); return STARK_OK;
+    *out = ctx->leaf_init.as<LeafConsts>(); return STARK_OK;
 }
 
 namespace stark {
@@ -331,16 +316,16 @@ static bool same_consts(const host::PoseidonConsts& a, const host::PoseidonConst
 int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h) {
     if (!n) return STARK_OK;
     stark_params* tp = nullptr; STARK_TRY(ctx_transcript_params(ctx, &tp));
-    fr_t* init = nullptr; STARK_TRY(ctx_leaf_init(ctx, &init));
-    const LeafStream L{init, f, f_next, m, n};
+    const LeafConsts* lc = nullptr; STARK_TRY(ctx_leaf_init(ctx, &lc));
+    const LeafStream L{reinterpret_cast<const fr_t*>(reinterpret_cast<const char*>(lc) + offsetof(LeafConsts, init)), f, f_next, m, n};      // LeafConsts::init on the device
     bool b8 = false; STARK_TRY(pair_block8_form(ctx, tp, &b8));
     if (tp->ref.rf < 4) b8 = false;      // k_leaf_pair2<true> hands round 0's rows to round 1's S-box: a full-round product must follow (the transcript set has rf = 8)
     switch (poseidon_form(ctx, tp, PoseidonOp::LeafLayer, n)) {
     case PoseidonForm::FiveWave: hipLaunchKernelGGL(k_leaf_pair_chain, dim3((unsigned)n), dim3(320), chain_lds_bytes(), st, tp->dev, row_consts_of(ctx), L, h); break;
     case PoseidonForm::OneWave: hipLaunchKernelGGL(k_leaf_pair_coop, dim3((unsigned)n), dim3(64), coop_lds_bytes(17), st, tp->dev, L, h); break;
     case PoseidonForm::WavePair:
-        if (b8) hipLaunchKernelGGL(k_leaf_pair2<true>, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, init + 17, f, f_next, n, m, h);
-        else hipLaunchKernelGGL(k_leaf_pair2<false>, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, init + 17, f, f_next, n, m, h);
+        if (b8) hipLaunchKernelGGL(k_leaf_pair2<true>, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, lc, f, f_next, n, m, h);
+        else hipLaunchKernelGGL(k_leaf_pair2<false>, dim3((unsigned)((n + 63) / 64)), dim3(128), pair_lds_bytes(17), st, tp->dev, lc, f, f_next, n, m, h);
         break;
     default: hipLaunchKernelGGL(k_leaf_pair, dim3((unsigned)((n + 63) / 64)), dim3(64), poseidon_lds(17, 64), st, tp->dev, L, h);
     }

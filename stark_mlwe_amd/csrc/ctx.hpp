@@ -77,7 +77,7 @@ struct stark_ctx {
     // lazily created constants
     std::unique_ptr<stark_params> tparams;           // transcript params (t=17, "POSEIDON-T17-X5-TRANSCRIPT")
     std::map<int, std::unique_ptr<stark_params>> merkle_params;   // poseidon_params_for_width(t)
-    stark::DevMem leaf_init;                         // 17-lane template of hash_leaf_pair (device)
+    stark::DevMem leaf_init;                         // one LeafConsts: the 17-lane template of hash_leaf_pair and round 0 in closed form (device)
     std::map<std::string, stark::DevMem> tr_frames;  // per-tag transcript prefix/suffix frames (device): [prefix.., suffix..]
     std::map<std::string, std::pair<int, int>> tr_frame_dims;
     // scratch

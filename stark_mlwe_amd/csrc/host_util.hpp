@@ -17,6 +17,7 @@
 #include <vector>
 #include "fr.hpp"
 #include "fr29.hpp"
+#include "poseidon_params.hpp"
 
 namespace stark {
 namespace host {
@@ -453,6 +454,17 @@ inline void leaf_round0_consts(const PoseidonConsts& c, const fr_t* init, fr_t* 
         K[i] = k;
         const fr29_t u = fr29_unpack(h_add(k, c.rc_full[17 + i]));
         for (int j = 0; j < 9; ++j) krc29[9 * i + j] = u.l[j];
+    }
+}
+// every leaf constant of a parameter set (poseidon_params.hpp LeafConsts): what the context uploads and the host checks read
+inline void leaf_consts(const PoseidonConsts& c, LeafConsts& lc) {
+    memset(&lc, 0, sizeof lc);
+    leaf_template(lc.init);      // lanes 4,5 = (f, s)
+    leaf_round0_consts(c, lc.init, lc.K, lc.krc29);
+    const fr_t k20 = fr_from_u64<PF>(1ull << FR29_SBOX_SHIFT);     // the S-box outputs x4, x5 arrive divided by 2^20 (fr_pow5_r29)
+    for (int i = 0; i < 17; ++i) {
+        lc.m4[i] = c.mds[(size_t)i * 17 + 4]; lc.m5[i] = c.mds[(size_t)i * 17 + 5];
+        fr29_const_from<PF>(h_mul(lc.m4[i], k20), lc.m45_29 + 9 * i); fr29_const_from<PF>(h_mul(lc.m5[i], k20), lc.m45_29 + 9 * (17 + i));
     }
 }
 

@@ -281,78 +281,99 @@ static int blk8_tile(const int8_t* const* frag, const fr_t* xd, int K, fr_t& out
 // the largest |digit sum| hc_permute_block8 has seen in a row of 16 + 7 K-steps (the longest tile of the block form) since the last reset
 static std::atomic<int32_t> g_blk8_row23_max{0};
 int32_t hc_blk8_row23_max(int reset) { return reset ? g_blk8_row23_max.exchange(0) : g_blk8_row23_max.load(); }
-// A whole t = 17 permutation in the wave-pair kernels' block-8 form: full rounds through the residue tables of M and B_1 M — every product that is followed
-// by a full round hands its rows over in limb form (word-column finish to limbs, the next round's constant from rc_full29, sbox_lazy29), the product in front of the
-// partial rounds ends as the first block takes its rows (the lanes as digits of their signed residue by the byte-domain finish, row 0 as its nine finish limbs plus lambda_0 c_0: no canonical value at the entry) and the one at the end finishes canonical, all from the same word columns, the first round's S-box stands alone, the last block's lane rows feed the S-box of the round after the partial rounds the same way (element 0 from
-// the chain value) —, the partial rounds in
-// blocks of 8 — lanes recoded, row q = H_q = E_q + sum Gamma y_p as ONE tile of 16 + q K-steps (E fragments against the lanes, blk8_gfrag against the
-// recoded yt_0..yt_{q-1}), the SCALED chain as a LAZY residue (u = lambda_q X_q + lambda_q c_q as nine limbs; x5 = pow5_lazy29(u), yt_q recoded unreduced; u <- x5 + the finish limbs of
-// H_q + lambda_{q+1} c_{q+1} (word columns, the constant's words in front of the quotient: mfma_finish_words) through the mailbox slot's layout; no field element inside a block, no a_q y_q product; one product by
-// 1 / lambda_rp after the last block), lane rows with the unit fragment as the ninth K-step — with blk8s_efrag / blk8s_gfrag / blk8s_lfrag, rc_partial_scaled and
-// blk8_unscale29 as uploaded; between two blocks the lanes are the digits of their signed residue (mfma_finish_bytes on the word columns), the fused rows' S-box outputs are recoded
-// unreduced.  -1: the set has no block-8 tables; -2: a digit sum out of range; -4: a chain limb outside pow5_lazy29's contract.
+// A whole t = 17 permutation as pair_permute_fused runs it (poseidon_pair.hpp), stage by stage under the same names, with the tables as uploaded (blk8s_efrag /
+// blk8s_gfrag / blk8s_lfrag, rc_partial_scaled29, blk8_unscale29, rc_full29).  The state of one sponge between the stages:
+struct HcPair {
+    const host::KernelConsts& k;
+    fr_t st[17];        // canonical elements (in, and out behind RowEnd::Canonical)
+    fr_t xd[17];        // the slots as operands: recoded S-box outputs; lanes 1..16 as digits of their signed residue inside the partial rounds
+    uint32_t l0[9];     // kEntrySlot: row 0 of the entry product as its nine finish limbs
+    fr29_t u;           // the chain in wave X
+};
+// pair_sbox_full<17>: st (canonical) -> xd
+static void pair_sbox_full(HcPair& s, int r) { for (int j = 0; j < 17; ++j) s.xd[j] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(s.st[j], s.k.rc_full[(size_t)r * 17 + j]))); }
+// pair_mds_sbox_mfma: one fold (the word columns) in front of the three ends.  Canonical: xd -> st; NextSbox: xd -> xd, the recoded S-box outputs of round
+// `next`; BlockEntry: rows 1..16 -> xd, the digits of their signed residue (mfma_finish_bytes on the same word columns), row 0 -> l0
+static int pair_mds_sbox_mfma(HcPair& s, const std::vector<int8_t>& F, RowEnd end, int next) {
+    fr_t o[17] = {};      // BlockEntry forms no o[0]: slot 0 is dead during the blocks (xd[0] is zeroed here; the last block's NextSbox end rewrites it)
+    for (int i = 0; i < 17; ++i) {
+        const int8_t* fr[17]; for (int e = 0; e < 17; ++e) fr[e] = &F[((size_t)i * 17 + e) * 1024];
+        int32_t S[32]; const int rc = blk8_tile_sums(fr, s.xd, 17, S); if (rc) return rc;
+        int64_t col[8]; mfma_word_cols_mad_of_sums(S, col);
+        if (end == RowEnd::NextSbox) { uint32_t l[9]; mfma_finish_words(col, l); o[i] = sbox_lazy29_recoded(l, &s.k.rc_full29[((size_t)next * 17 + i) * 9]); }
+        else if (end == RowEnd::BlockEntry) { if (i == 0) mfma_finish_words(col, s.l0); else o[i] = mfma_finish_bytes(col); }
+        else o[i] = mfma_finish_words_canonical(col);      // two conditional subtractions
+    }
+    for (int i = 0; i < 17; ++i) (end == RowEnd::Canonical ? s.st : s.xd)[i] = o[i];
+    return 0;
+}
+// pair_block8, block b: rounds blk8_round_y / blk8_round_x, then blk8_lane_rows.  Row q = H_q = E_q + sum Gamma y_p as ONE tile of 16 + q K-steps (E fragments
+// against the lanes, blk8_gfrag against the recoded yt_0..yt_{q-1}); the SCALED chain as a LAZY residue: no field element inside a block, no a_q y_q product.
+static int pair_block8(HcPair& s, int b, LaneEnd end) {
+    const host::KernelConsts& k = s.k; const int half = k.rf / 2;
+    const int8_t* ef = k.blk8s_efrag.data() + (size_t)b * 8 * 16 * 1024; const int8_t* lf = k.blk8s_lfrag.data() + (size_t)b * 16 * 8 * 1024;
+    const int8_t* gf = k.blk8s_gfrag.data() + (size_t)b * 28 * 1024; const int8_t* unit = k.blk8_lfrag.data() + k.blk8_lfrag.size() - 1024;
+    fr_t yd[9], kx[23];
+    for (int j = 0; j < 16; ++j) kx[j] = s.xd[1 + j];
+    for (int q = 0; q < 8; ++q) {
+        const int8_t* fr[23]; for (int j = 0; j < 16; ++j) fr[j] = ef + ((size_t)q * 16 + j) * 1024;
+        for (int p2 = 0; p2 < q; ++p2) { fr[16 + p2] = gf + ((size_t)q * (q - 1) / 2 + p2) * 1024; kx[16 + p2] = yd[p2]; }
+        int32_t S[32]; { const int rc = blk8_tile_sums(fr, kx, 16 + q, S); if (rc) return rc; }
+        if (q == 7) { int32_t m = 0; for (int c = 0; c < 32; ++c) m = std::max(m, S[c] < 0 ? -S[c] : S[c]);
+                      int32_t seen = g_blk8_row23_max.load(); while (m > seen && !g_blk8_row23_max.compare_exchange_weak(seen, m)) {} }
+        // blk8_round_y: the row's finish with the next round's scaled constant in its columns (zero after the last round), posted as the slot's words
+        uint32_t l[9]; blk8_finish_sums_limbs(S, l, &k.rc_partial_scaled29[(size_t)9 * (8 * b + q + 1)]);
+        const fr_t slot = lazy29_to_slot(l);
+        // blk8_round_x: the S-box on the lazy value, yt_q recoded unreduced, the slot's limbs added to x5's
+        const fr29_t x5 = pow5_lazy29(s.u);
+        yd[q] = recode_lazy29(x5);
+        s.u = lazy29_add_slot(x5, slot);
+        for (int i = 0; i < 9; ++i) if (s.u.l[i] >= (1u << 30)) return -4;             // pow5_lazy29's contract
+    }
+    // NextSbox: element 0 of the next full round's S-box from the chain's final value, lambda_rp X_rp (lazy) -> X_rp (below 1.04 r) once per permutation
+    if (end == LaneEnd::NextSbox) { const fr29_t x0 = fr29_mul_c29(k.blk8_unscale29.data(), s.u); s.xd[0] = sbox_lazy29_recoded(x0.l, &k.rc_full29[((size_t)half * 17) * 9]); }
+    // blk8_lane_rows, the unit fragment as the ninth K-step
+    for (int j = 1; j < 17; ++j) {
+        const int8_t* fr[9]; for (int p2 = 0; p2 < 8; ++p2) fr[p2] = lf + ((size_t)(j - 1) * 8 + p2) * 1024; fr[8] = unit;
+        yd[8] = s.xd[j];
+        int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; }
+        if (end == LaneEnd::NextSbox) { uint32_t l[9]; blk8_finish_sums_limbs(S, l); s.xd[j] = sbox_lazy29_recoded(l, &k.rc_full29[((size_t)half * 17 + j) * 9]); }      // like a fused product row
+        else if (end == LaneEnd::Bytes) { int64_t col[8]; mfma_word_cols_of_sums(S, col); s.xd[j] = mfma_finish_bytes(col); }      // the signed residue's digits, finished in the byte domain
+        else { const fr_t z = blk8_finish_sums(S); s.xd[j] = end == LaneEnd::Canonical ? z : recode_signed(z); }
+    }
+    return 0;
+}
+static int pair_blocks8(HcPair& s, LaneEnd mid, LaneEnd last) {
+    const int nb = s.k.rp / 8;
+    for (int b = 0; b < nb; ++b) { const int rc = pair_block8(s, b, b == nb - 1 ? last : mid); if (rc) return rc; }
+    return 0;
+}
+// pair_last_rounds<17, true>, the whole state kept (only0 = false)
+static int pair_last_rounds(HcPair& s) {
+    for (int r = s.k.rf / 2; r < s.k.rf; ++r) { const bool last = r == s.k.rf - 1; const int rc = pair_mds_sbox_mfma(s, s.k.mds_frag, last ? RowEnd::Canonical : RowEnd::NextSbox, r + 1); if (rc) return rc; }
+    return 0;
+}
+// pair_permute_fused<false>(s, P, false, 0)
+static int pair_permute_fused(HcPair& s) {
+    const host::KernelConsts& k = s.k; const int half = k.rf / 2;
+    pair_sbox_full(s, 0);
+    for (int r = 0; r < half; ++r) { const bool pre = r == half - 1; const int rc = pair_mds_sbox_mfma(s, pre ? k.mds_pre_frag : k.mds_frag, pre ? RowEnd::BlockEntry : RowEnd::NextSbox, r + 1); if (rc) return rc; }
+    // the chain as a lazy residue: row 0's finish limbs through the mailbox slot's layout, plus lambda_0 c_0 — no canonical value at the entry
+    fr29_t zero9; for (int i = 0; i < 9; ++i) zero9.l[i] = 0;
+    s.u = lazy29_add_c29(lazy29_add_slot(zero9, lazy29_to_slot(s.l0)).l, &k.rc_partial_scaled29[0]);
+    for (int i = 0; i < 9; ++i) if (s.u.l[i] >= (1u << 30)) return -4;
+    { const int rc = pair_blocks8(s, LaneEnd::Bytes, LaneEnd::NextSbox); if (rc) return rc; }
+    return pair_last_rounds(s);
+}
+// n states through pair_permute_fused.  -1: the set has no block-8 tables; -2: a digit sum out of range; -4: a chain limb outside pow5_lazy29's contract.
 int hc_permute_block8(void* h, uint64_t* states, size_t n) {
-    HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc; const int t = k.t, half = k.rf / 2;
-    if (t != 17 || k.blk8s_efrag.empty() || k.blk8s_gfrag.empty() || k.blk8_unscale29.empty() || k.mds_frag.empty()) return -1;
-    const int8_t* unit = k.blk8_lfrag.data() + k.blk8_lfrag.size() - 1024;
-    std::vector<fr_t> st(t), xd(t), o(t);
-    // pair_sbox_full<17, true>: st (canonical) -> xd
-    auto sbox = [&](int r) { for (int j = 0; j < t; ++j) xd[j] = recode_signed(fr_pow5_r29<PF>(fr_add<PF>(st[j], k.rc_full[(size_t)r * t + j]))); };
-    // pair_mds_sbox_mfma: xd -> st (canonical) when next < 0, else xd -> xd = the recoded S-box outputs of round `next`; entry (the product in front of the
-    // partial rounds): rows 1..16 -> rec, the digits of their signed residue (mfma_finish_bytes on the same word columns), row 0 -> l0, its nine finish limbs
-    fr_t rec[17]; uint32_t l0[9];
-    auto product = [&](const std::vector<int8_t>& F, int next, bool entry) -> int {
-        for (int i = 0; i < t; ++i) {
-            const int8_t* fr[17]; for (int e = 0; e < t; ++e) fr[e] = &F[((size_t)i * t + e) * 1024];
-            int32_t S[32]; const int rc = blk8_tile_sums(fr, xd.data(), t, S); if (rc) return rc;
-            if (next < 0 && entry) { int64_t col[8]; mfma_word_cols_mad_of_sums(S, col); if (i == 0) mfma_finish_words(col, l0); else rec[i] = mfma_finish_bytes(col); }
-            else if (next < 0) { int64_t col[8]; mfma_word_cols_mad_of_sums(S, col); o[i] = mfma_finish_words_canonical(col); }      // the same word columns, two conditional subtractions
-            else { uint32_t l[9]; blk8_finish_sums_limbs(S, l); o[i] = sbox_lazy29_recoded(l, &k.rc_full29[((size_t)next * t + i) * 9]); }
-        }
-        if (next >= 0) xd = o; else if (!entry) st = o;
-        return 0; };
-    for (size_t s = 0; s < n; ++s) {
-        for (int j = 0; j < t; ++j) st[j] = ld4(states + 4 * (s * t + j));
-        sbox(0);
-        for (int r = 0; r < half; ++r) { const int rc = product(r == half - 1 ? k.mds_pre_frag : k.mds_frag, r == half - 1 ? -1 : r + 1, r == half - 1); if (rc) return rc; }
-        fr_t yd[9], kx[23];
-        fr29_t zero9; for (int i = 0; i < 9; ++i) zero9.l[i] = 0;
-        // the chain as a lazy residue: row 0's finish limbs through the mailbox slot's layout, plus lambda_0 c_0 — no canonical value at the entry
-        fr29_t u = lazy29_add_c29(lazy29_add_slot(zero9, lazy29_to_slot(l0)).l, &k.rc_partial_scaled29[0]);
-        for (int i = 0; i < 9; ++i) if (u.l[i] >= (1u << 30)) return -4;
-        const int nb = k.rp / 8;
-        for (int b = 0; b < nb; ++b) {
-            const int8_t* ef = k.blk8s_efrag.data() + (size_t)b * 8 * 16 * 1024; const int8_t* lf = k.blk8s_lfrag.data() + (size_t)b * 16 * 8 * 1024;
-            const int8_t* gf = k.blk8s_gfrag.data() + (size_t)b * 28 * 1024;
-            for (int j = 0; j < 16; ++j) kx[j] = rec[1 + j];
-            for (int q = 0; q < 8; ++q) {
-                const int8_t* fr[23]; for (int j = 0; j < 16; ++j) fr[j] = ef + ((size_t)q * 16 + j) * 1024;
-                for (int p2 = 0; p2 < q; ++p2) { fr[16 + p2] = gf + ((size_t)q * (q - 1) / 2 + p2) * 1024; kx[16 + p2] = yd[p2]; }
-                int32_t S[32]; { const int rc = blk8_tile_sums(fr, kx, 16 + q, S); if (rc) return rc; }
-                if (q == 7) { int32_t m = 0; for (int c = 0; c < 32; ++c) m = std::max(m, S[c] < 0 ? -S[c] : S[c]);
-                              int32_t seen = g_blk8_row23_max.load(); while (m > seen && !g_blk8_row23_max.compare_exchange_weak(seen, m)) {} }
-                // Y: the row's finish with the next round's scaled constant in its columns (zero after the last round), posted as the slot's words
-                uint32_t l[9]; blk8_finish_sums_limbs(S, l, &k.rc_partial_scaled29[(size_t)9 * (8 * b + q + 1)]);
-                const fr_t slot = lazy29_to_slot(l);
-                // X: the S-box on the lazy value, yt_q recoded unreduced, the slot's limbs added to x5's
-                const fr29_t x5 = pow5_lazy29(u);
-                yd[q] = recode_lazy29(x5);
-                u = lazy29_add_slot(x5, slot);
-                for (int i = 0; i < 9; ++i) if (u.l[i] >= (1u << 30)) return -4;             // pow5_lazy29's contract
-            }
-            for (int j = 1; j < t; ++j) {
-                const int8_t* fr[9]; for (int p2 = 0; p2 < 8; ++p2) fr[p2] = lf + ((size_t)(j - 1) * 8 + p2) * 1024; fr[8] = unit;
-                yd[8] = rec[j];
-                if (b == nb - 1) {          // the last block: the lane goes from its finish limbs through the next full round's S-box, like a fused product row
-                    int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; }
-                    uint32_t l[9]; blk8_finish_sums_limbs(S, l); xd[j] = sbox_lazy29_recoded(l, &k.rc_full29[((size_t)half * t + j) * 9]);
-                } else { int32_t S[32]; { const int rc = blk8_tile_sums(fr, yd, 9, S); if (rc) return rc; } int64_t col[8]; mfma_word_cols_of_sums(S, col); rec[j] = mfma_finish_bytes(col); }      // the signed residue's digits, finished in the byte domain
-            }
-        }
-        const fr29_t x0 = fr29_mul_c29(k.blk8_unscale29.data(), u);                                // lambda_rp X_rp (lazy) -> X_rp (below 1.04 r), once per permutation
-        xd[0] = sbox_lazy29_recoded(x0.l, &k.rc_full29[((size_t)half * t) * 9]);            // element 0 of that S-box from the chain's final value
-        for (int r = half; r < k.rf; ++r) { const int rc = product(k.mds_frag, r == k.rf - 1 ? -1 : r + 1, false); if (rc) return rc; }
-        for (int j = 0; j < t; ++j) st4(states + 4 * (s * t + j), st[j]);
+    HcParams* P = (HcParams*)h; const host::KernelConsts& k = P->kc;
+    if (k.t != 17 || k.blk8s_efrag.empty() || k.blk8s_gfrag.empty() || k.blk8_unscale29.empty() || k.mds_frag.empty()) return -1;
+    HcPair s{k};
+    for (size_t i = 0; i < n; ++i) {
+        for (int j = 0; j < 17; ++j) s.st[j] = ld4(states + 4 * (i * 17 + j));
+        const int rc = pair_permute_fused(s); if (rc) return rc;
+        for (int j = 0; j < 17; ++j) st4(states + 4 * (i * 17 + j), s.st[j]);
     }
     return 0;
 }
@@ -536,7 +557,7 @@ int hc_permute_dense(void* h, uint64_t* states, size_t n) {
 }
 // kernel bodies on the host ---------------------------------------------------------------------------
 }  // extern "C"
-// the 17-lane template of hash_leaf_pair (capi_poseidon.hip ctx_leaf_init)
+// the 17-lane template of hash_leaf_pair (LeafConsts::init) where a check needs nothing else of the leaf constants
 static void leaf_init(fr_t init[17]) { host::leaf_template(init); }
 extern "C" {
 // Round 0 of the leaf permutation as k_leaf_pair2<true> runs it (poseidon_pair.hpp pair_leaf_round0_mfma), re-enacted: x4 = fr_pow5_r29(f + rc[4]) and
@@ -548,10 +569,9 @@ extern "C" {
 int hc_leaf_round0(void* tparams, const uint64_t* f, const uint64_t* f_next, size_t n, uint64_t* init_out, uint32_t* table_out, uint64_t* x45_out, uint32_t* limbs_out, uint64_t* sbox_out) {
     HcParams* P = (HcParams*)tparams; const host::KernelConsts& k = P->kc;
     if (k.t != 17 || k.mds_frag.empty() || k.rf < 2) return -1;
-    fr_t init[17], K[17]; uint32_t krc29[17 * 9];
-    leaf_init(init); host::leaf_round0_consts(P->ref, init, K, krc29);
-    if (init_out) for (int j = 0; j < 17; ++j) st4(init_out + 4 * j, init[j]);
-    if (table_out) memcpy(table_out, krc29, sizeof(krc29));
+    LeafConsts lc; host::leaf_consts(P->ref, lc);      // what ctx_leaf_init uploads
+    if (init_out) for (int j = 0; j < 17; ++j) st4(init_out + 4 * j, lc.init[j]);
+    if (table_out) memcpy(table_out, lc.krc29, sizeof(lc.krc29));
     for (size_t s = 0; s < n; ++s) {
         fr_t x[2], xd[2];
         x[0] = fr_pow5_r29<PF>(fr_add<PF>(ld4(f + 4 * s), k.rc_full[4]));
@@ -563,7 +583,7 @@ int hc_leaf_round0(void* tparams, const uint64_t* f, const uint64_t* f_next, siz
             for (int c = 0; c < 32; ++c) if (S[c] > 2 * 32 * 128 * 128 || S[c] < -2 * 32 * 128 * 128) return -2;
             uint32_t l[9]; blk8_finish_sums_limbs(S, l);
             if (limbs_out) memcpy(limbs_out + 9 * (17 * s + i), l, sizeof(l));
-            if (sbox_out) st4(sbox_out + 4 * (17 * s + i), sbox_lazy29(l, &krc29[9 * i]));
+            if (sbox_out) st4(sbox_out + 4 * (17 * s + i), sbox_lazy29(l, &lc.krc29[9 * i]));
         }
     }
     return 0;
@@ -591,11 +611,11 @@ int hc_squeeze_row(void* h, const uint64_t* states, size_t n, uint64_t* out) {
 }
 int hc_leaf_pair(void* tparams, const uint64_t* f, const uint64_t* f_next, size_t n, size_t m, uint64_t* hout) {
     HcParams* P = (HcParams*)tparams;
-    fr_t init[17]; leaf_init(init);
+    LeafConsts lc; host::leaf_consts(P->ref, lc);
     std::vector<fr_t> fv(n), nv(f_next ? (n + m - 1) / m : 0);
     for (size_t i = 0; i < fv.size(); ++i) fv[i] = ld4(f + 4 * i);
     for (size_t i = 0; i < nv.size(); ++i) nv[i] = ld4(f_next + 4 * i);
-    const LeafStream L{init, fv.data(), f_next ? nv.data() : nullptr, m, n};
+    const LeafStream L{lc.init, fv.data(), f_next ? nv.data() : nullptr, m, n};
     fr_t st[17];
     for (size_t i = 0; i < n; ++i) { ArrayState s{st}; st4(hout + 4 * i, leaf_pair_body(s, P->dev, L, i)); }
     return 0;

@@ -12,6 +12,10 @@
 namespace stark {
 
 typedef PallasFr PF;
+// How a row of the pipeline ends, named once for the kernels (poseidon_pair.hpp, where each end is described at its site) and their host mirror (hostcheck.cpp):
+// RowEnd for the full rounds' product (pair_mds_sbox_mfma), LaneEnd for the lane rows of an 8-round block (blk8_lane_rows).  Wave-uniform runtime values.
+enum class RowEnd { Canonical, NextSbox, BlockEntry };
+enum class LaneEnd { Bytes, Recoded, NextSbox, Canonical };
 static_assert(fr_p29<PF>(4) < (1u << 10) && fr_p29<PF>(5) == 0 && fr_p29<PF>(6) == 0 && fr_p29<PF>(7) == 0 && fr_p29<PF>(8) == (1u << 22), "r = 2^254 + t with t below 2^126");
 
 // x (canonical) -> signed radix-256 digits in place of its bytes: add 0x80 to every byte with carries, flip every byte's top bit
@@ -104,7 +108,7 @@ FR_HD fr_t sbox_lazy29(const uint32_t* l, const uint32_t* __restrict__ c) { retu
 // lambda_{q+1} c_{q+1}, KernelConsts::rc_partial_scaled29; limbs below 2^29, c < r), so the constant is off the chain.  It is added to the folded columns in
 // front of the carry pass (from a temporary filled by mfma_cols_set), which is the same sum as columns that start from c.  The register allocator decides the
 // form: with c as the columns' initial value, and also with the nine adds written straight from the scalars, k_hash_ds2<17, DsBatchStream, true> held 256 VGPRs
-// with 2 spilled (12 B of scratch); in this form — mfma_post_cols keeping its start-from-a-constant branch, unused — it holds 252 and spills none.
+// with 2 spilled (12 B of scratch); in this form it held 252 and spilled none.
 //   column      |col| < 2^61.01 + 2^29, with the carry still < 2^62; top = floor((V + c) / 2^232), |top| < 2^40.01 + 1;
 //   q1          floor((V + c) / 2^254) - 1, |q1| < 2^18.02 + 1;
 //   W'          V + c - q1 r = ((V + c) mod 2^254) + 2^254 - q1 t: the range of W above, (2^254 - 2^144.02, 2^255 + 2^144.02), below 2.0001 r and below 2^256,
@@ -115,13 +119,7 @@ FR_HD fr_t sbox_lazy29(const uint32_t* l, const uint32_t* __restrict__ c) { retu
 // The mailbox slot (32 bytes) holds W' as its nine limbs: limb k in bits 0..28 of word k, bits 3k..3k+2 of the top limb (24 bits = 8 x 3) in bits 29..31 of
 // word k.  Two instructions per word on either side (bit-field extract + shift-or; and + shift-or), against a pack (8 words of two or three shift-ors) and an
 // unpack (nine limbs of two shifts, an or and a mask) for the packed 256-bit form: the cheaper of the two layouts.
-FR_HD void mfma_cols_set(int64_t* col, const uint32_t* __restrict__ c_) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef const __attribute__((address_space(4))) uint32_t* cptr_t;
-    cptr_t c = (cptr_t)c_;
-#else
-    const uint32_t* c = c_;
-#endif
+FR_HD void mfma_cols_set(int64_t* col, const uint32_t* __restrict__ c) {      // the host checks' form of the limb-column finish with a constant; no kernel calls it
 #pragma unroll
     for (int k = 0; k < 9; ++k) col[k] = (int64_t)c[k];
 }

@@ -6,22 +6,20 @@
 // waves per SIMD).  Here a workgroup is a pair of waves (X, Y) that share the 64 LDS-resident states of
 // the batch: lane l of both waves works on state l, each wave on its own part of the linear algebra.
 // Same LDS per state, twice the waves per SIMD (4 workgroups of 40 KiB per CU for t = 17).
-//   * full rounds : S-box on the wave's own elements; the dense MDS product
-//                   - t = 17: on the MATRIX CORES (pair_mds_sbox_mfma below): int8 MFMA of the matrix's residue table with the state's signed radix-256 digits, X the even
-//                     output rows, Y the odd ones, each wave holding the whole state as operand registers;
-//                   - t = 9: as in-place L*(U*x) on the VALU, X taking the even rows and Y the odd rows of each step (rows
-//                     2k/2k+1 read only slots >= 2k, so a single barrier between the step's reads and its two writes keeps it race-free);
-//   * partial rounds, t = 17 with the context option poseidon_block8 (the default): in blocks of 8 whose u-rows and lane updates are two matrix-core
-//     products (pair_block8 below), wave X's S-box chain scaled so that no round multiplies by a_q (one product per permutation undoes the scale);
-//   * partial rounds otherwise, in blocks of 4 (see permute_core in poseidon_dev.hpp for the algebra):
-//       phase 1  X runs the S-box chain: x_q, then a_q x_q + sum_{p<q} gamma x_p + its share (lanes 1..NXD) of the
-//                lane dot product from registers; Y computes the other lanes' part of every round's
-//                dot product from the block-start state and posts it in an LDS mailbox (one barrier per round);
-//       phase 2  both waves bring their half of the lanes up to date, s_j += sum_p w_{p,j} x_p (one
-//                reduction per lane), X from registers, Y from the x mailboxes.
-//     The mailboxes reuse state slots that are dead during the block (slot 0: X holds s0 in registers;
-//     slots 1..NXD: X preloads those lanes), so the LDS budget stays at 4 workgroups per CU.
 // Results are the same field values as poseidon_dev.hpp / the reference's dense rounds.
+//
+// The file by layer; each permutation can be read from its entry down without the other two:
+//   state and config   PairCfg, PairState, pair_setup;
+//   full rounds        S-box on the wave's own elements (pair_sbox_full); the dense product for t = 9 as in-place L*(U*x) on the VALU (pair_apply_lu), for t = 17 on
+//                      the MATRIX CORES through the row pipeline: zeroed tile -> int8 MFMAs of a residue table with the operands' signed radix-256 digits -> fold,
+//                      exchange -> a named row end (RowEnd of pair_mds_sbox_mfma, LaneEnd of blk8_lane_rows);
+//   8-round block      t = 17 partial rounds whose u-rows and lane updates are two matrix-core products (pair_block8), wave X's S-box chain scaled and lazy;
+//   block of 4         partial rounds on the vector ALU (pair_blocks4; permute_core in poseidon_dev.hpp has the algebra);
+//   the permutations   three entries over shared stages (pair_first_rounds, pair_blocks4, pair_blocks8, pair_last_rounds):
+//       pair_permute_blk4<T>        full rounds with canonical ends, partial rounds in blocks of 4: t = 9, and t = 17 with the context option poseidon_block8 off;
+//       pair_permute_blk8           t = 17: the same full rounds, 8-round blocks with canonical hand-overs at both ends of the partial rounds (k_hash_ds2);
+//       pair_permute_fused<SBOXED>  t = 17: 8-round blocks, every row handed on in limb, byte or entry form (k_leaf_pair2, k_node16_pair);
+//   kernels            k_leaf_pair2, k_hash_ds2, k_node16_pair.
 #pragma once
 #include "fr.hpp"
 #include "dev_common.hpp"
@@ -54,7 +52,6 @@ template <int T> struct PairCfg {
     __host__ __device__ static constexpr int dslot(int q) { return 1 + (q % NXD); }
     __host__ __device__ static constexpr size_t lds_bytes() { return (size_t)(T + EXTRA) * 2 * 64 * 16; }
 };
-constexpr int kLeafKrcOff = 51 + 40;      // k_leaf_pair2's constant blob (capi_poseidon.hip ctx_leaf_init): elements from K to the table of (K_i + round 1's constant) as 17 x 9 limbs
 static inline size_t pair_lds_bytes(int t) { return t == 17 ? PairCfg<17>::lds_bytes() : PairCfg<9>::lds_bytes(); }
 
 struct PairState {
@@ -69,8 +66,15 @@ struct PairState {
         st[(2 * j + 1) * 64 + lane] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
     }
 };
+__device__ __forceinline__ PairState pair_setup(uint4* lds) {
+    PairState s; s.st = lds; s.lane = threadIdx.x & 63;
+    s.isY = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0;      // wave-uniform by construction: tell the compiler (scalar branches, scalar constant loads)
+    return s;
+}
 
-// In-place y = L*(U*x) over the shared state; one barrier per step.  Ends with the state consistent.
+// ---- full rounds: the S-box pass and the dense product on the VALU (t = 9) ------------------------------------------------------------------------
+// In-place y = L*(U*x) over the shared state, X taking the even rows and Y the odd rows of each step (rows 2k / 2k + 1 read only slots >= 2k, so a single barrier
+// between the step's reads and its two writes keeps it race-free); one barrier per step.  Ends with the state consistent.
 template <int T>
 __device__ __forceinline__ void pair_apply_lu(const PairState& s, const uint32_t* lu) {
     const int yo = s.isY ? 1 : 0;
@@ -93,14 +97,15 @@ __device__ __forceinline__ void pair_apply_lu(const PairState& s, const uint32_t
     }
     __syncthreads();
 }
-template <int T, bool RECODE = false>
+// The standalone S-box pass of a full round, each wave on its own elements.  t = 17 stores the outputs RECODED: the matrix-core product reads them as operands.
+template <int T>
 __device__ __forceinline__ void pair_sbox_full(const PairState& s, const fr_t* rc) {
     const int j0 = s.isY ? PairCfg<T>::NX : 0, j1 = s.isY ? T : PairCfg<T>::NX;
-    for (int j = j0; j < j1; ++j) { const fr_t x = fr_pow5_r29<PF>(fr_add<PF>(s.ld(j), rc[j])); s.sto(j, RECODE ? recode_signed(x) : x); }
+    for (int j = j0; j < j1; ++j) { const fr_t x = fr_pow5_r29<PF>(fr_add<PF>(s.ld(j), rc[j])); s.sto(j, T == 17 ? recode_signed(x) : x); }
     __syncthreads();
 }
 
-// ---- the dense full-round product on the matrix cores (T = 17) ---------------------------------------------------------------------
+// ---- the row pipeline: the dense full-round product on the matrix cores (T = 17) ---------------------------------------------------------------------
 // y = M * x for the 64 sponges of the pair, x = the S-box outputs, stored RECODED (signed digits) in the state slots.  The left factor is the
 // RESIDUE TABLE of the matrix (host_util.hpp mfma_frags): for every entry (i, e) and input digit position b the 32 signed radix-256 digits of
 // C[i][e][b] = (M[i][e] * 2^20 * 256^b) mod r.  The digit sums S[(i,c)][n] = sum_{e,b} d_{i,e,b}[c] * xd_e[n][b], c = 0..31, are one dense int8
@@ -127,32 +132,23 @@ __device__ __forceinline__ void mfma_zero_tile(mfma_v16i (&acc)[2]) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[ct][r] = 0;
 }
-// exchange and fold: the two accumulator tiles of a row -> the nine columns of the lane's sponge
-// c29 != nullptr: the columns start from that constant's nine limbs.  No caller passes one (blk8_round_y takes its constant into word columns now,
-// mfma_post_limbs); the branch stays as the resource table was taken with it (without it k_hash_ds2<17, DsBatchStream, true> once spilled 2 VGPRs: DESIGN 7a).
-__device__ __forceinline__ void mfma_post_cols(const mfma_v16i (&acc)[2], int64_t* col, const uint32_t* c29 = nullptr) {
+// exchange of all 32 sums, fold into the nine limb columns of the lane's sponge, finish: -> the canonical field element
+__device__ __forceinline__ fr_t mfma_post(const mfma_v16i (&acc)[2]) {
     mfma_v16i lo, hi;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const auto sw = __builtin_amdgcn_permlane32_swap((unsigned)acc[0][r], (unsigned)acc[1][r], false, false);
         lo[r] = (int)sw[0]; hi[r] = (int)sw[1];
     }
-    if (c29) mfma_cols_set(col, c29);
-    else {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) col[k] = 0;
-    }
-    mfma_fold_rows(col, lo, hi);
-}
-// exchange, fold, finish: -> the canonical field element of the lane's sponge
-__device__ __forceinline__ fr_t mfma_post(const mfma_v16i (&acc)[2]) {
     int64_t col[9];
-    mfma_post_cols(acc, col);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) col[k] = 0;
+    mfma_fold_rows(col, lo, hi);
     return mfma_finish_cols(col);
 }
 // fold, exchange, byte-domain finish: -> the signed residue's digits of the lane's sponge (mfma_digits.hpp mfma_finish_bytes).  Each lane folds the registers it
 // holds — four word columns per tile: words 0, 2, 4, 6 of its sponges in the lower lane, 1, 3, 5, 7 in the upper one — and only the four 64-bit columns of
-// each tile cross the lane pair: 8 v_permlane32_swap against the 16 of mfma_post_cols.  Rows of at most 9 K-steps (the int32 pairs of mfma_word_cols).
+// each tile cross the lane pair: 8 v_permlane32_swap against the 16 of mfma_post.  Rows of at most 9 K-steps (the int32 pairs of mfma_word_cols).
 __device__ __forceinline__ fr_t mfma_post_bytes(const mfma_v16i (&acc)[2]) {
     int64_t c0[4], c1[4], col[8];
     mfma_word_cols(acc[0], c0); mfma_word_cols(acc[1], c1);
@@ -189,17 +185,19 @@ __device__ __forceinline__ void mfma_post_limbs(const mfma_v16i (&acc)[2], uint3
 __device__ __forceinline__ void pair_sto_sbox29(const PairState& s, int j, const uint32_t* l, const uint32_t* rc29) {
     s.sto(j, recode_lazy29(pow5_lazy29(lazy29_add_c29(l, rc29))));      // recoded from the unreduced x5 (below 1.04 r)
 }
-// The product.  Precondition: every state slot holds a recoded S-box output and a barrier has passed.  rc29 == nullptr: ends with the state canonical and
-// consistent.  Otherwise rc29 = the NEXT full round's constants (17 x 9 limbs) and every row is handed to that round's S-box in the wave that formed it
-// (pair_sto_sbox29) — X the even elements, Y the odd ones, nothing crosses waves: no LDS round trip, no standalone S-box pass and one barrier less per round.
-// entry (rc29 == nullptr; the FUSE kernels' product in front of the partial rounds, frag = mds_pre_frag): the rows end as the 8-round blocks take them, no
-// canonical value, no recode pass and no further barrier — rows 1..16, the lanes, as the digits of their signed residue (mfma_finish_bytes on the same word
-// columns: rows of 17 K-steps, |S_c| <= 8 912 896, |col| <= 16 843 009 |S| < 2^47.1, the bound stated there for the wide rows); row 0, the chain value, as its
-// nine finish limbs in the mailbox layout (lazy29_to_slot) in slot kEntrySlot, which wave X — the wave that formed it — reads back as the chain's start.  That
-// slot is H's mailbox of the ODD rounds: Y first writes it in round 1, behind barrier_0, which X passes after its read.  (Slot 0, the even rounds' mailbox, is
-// written by Y inside round 0: a read of it with no barrier in between would race.)
+// How a row of the full rounds' product ends (wave-uniform, a runtime value):
+//   Canonical   the state canonical and consistent (mfma_finish_words_canonical);
+//   NextSbox    handed to the NEXT full round's S-box in the wave that formed it (pair_sto_sbox29 with rc29 = that round's constants, 17 x 9 limbs) — X the even
+//               elements, Y the odd ones, nothing crosses waves: no LDS round trip, no standalone S-box pass and one barrier less per round;
+//   BlockEntry  (the product in front of the partial rounds of pair_permute_fused, frag = mds_pre_frag) as the 8-round blocks take them, no canonical value, no
+//               recode pass and no further barrier — rows 1..16, the lanes, as the digits of their signed residue (mfma_finish_bytes on the same word columns:
+//               rows of 17 K-steps, |S_c| <= 8 912 896, |col| <= 16 843 009 |S| < 2^47.1, the bound stated there for the wide rows); row 0, the chain value, as
+//               its nine finish limbs in the mailbox layout (lazy29_to_slot) in slot kEntrySlot, which wave X — the wave that formed it — reads back as the
+//               chain's start.  That slot is H's mailbox of the ODD rounds: Y first writes it in round 1, behind barrier_0, which X passes after its read.
+//               (Slot 0, the even rounds' mailbox, is written by Y inside round 0: a read of it with no barrier in between would race.)
 constexpr int kEntrySlot = 17 + 2;
-__device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const void* frag, const uint32_t* rc29, bool entry = false) {
+// The product.  Precondition: every state slot holds a recoded S-box output and a barrier has passed.  Ends with a barrier.  rc29 is read by NextSbox alone.
+__device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const void* frag, RowEnd end, const uint32_t* rc29 = nullptr) {
     constexpr int T = 17;
     const int lane = s.lane, h = lane >> 5;
     mfma_v4i b[T][2];
@@ -220,11 +218,11 @@ __device__ __forceinline__ void pair_mds_sbox_mfma(const PairState& s, const voi
 #pragma unroll
             for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
         }
-        // one fold and exchange in front of both ends: with the canonical end on its own path (mfma_post) the FUSE kernels spill
+        // one fold and exchange in front of all three ends: with the canonical end on its own path (mfma_post) the fused kernels spill
         int64_t col[8];
         mfma_post_words(acc, col);
-        if (rc29) { uint32_t l[9]; mfma_finish_words(col, l); pair_sto_sbox29(s, i, l, c29(rc29, i)); }
-        else if (entry) {
+        if (end == RowEnd::NextSbox) { uint32_t l[9]; mfma_finish_words(col, l); pair_sto_sbox29(s, i, l, c29(rc29, i)); }
+        else if (end == RowEnd::BlockEntry) {
             if (i == 0) { uint32_t l[9]; mfma_finish_words(col, l); s.sto(kEntrySlot, lazy29_to_slot(l)); }
             else s.sto(i, mfma_finish_bytes(col));
         }
@@ -266,6 +264,39 @@ __device__ __forceinline__ fr_t pair_squeeze_row_mfma(const PairState& s, const 
     int64_t col[8];
     mfma_post_words(acc, col);
     return mfma_finish_words_canonical(col);
+}
+// Round 0 of the leaf permutation through the same row pipeline with TWO K-steps: 15 of the 17 lanes of hash_leaf_pair's template are constants, so round 0's
+// product is K_i + M[i][4] x4 + M[i][5] x5 (host_util.hpp leaf_round0_consts), a dense row with two live columns and a constant.  Precondition: slots 4 and 5 hold
+// x4 and x5 RECODED and a barrier has passed.  Row i = fragments (i, 4), (i, 5) of the full rounds' table against the two operands, fold and exchange and finish
+// as every fused row (mfma_post_limbs), and the hand-over to round 1's S-box with krc29[i] = (K_i + rc_full[17 + i]) mod r as its constant — X the even rows,
+// Y the odd ones.  Ends like pair_sbox_full<17> of round 1: every slot a recoded S-box output, behind a barrier.
+//   digit sums  |S_c| <= 2 * 32 * 128 * 128 = 1 048 576 = 2^20, far inside mfma_word_cols_mad's domain (23 K-steps);
+//   S-box input u = W + krc29[i] with W < 3 r + 2^146 (mfma_finish_words) and the constant canonical: u < 4 r + 2^146 < 4.0001 r, limbs below 2^30 — the fused
+//               rows' bound, inside pow5_lazy29's 4.25 r.
+__device__ __forceinline__ void pair_leaf_round0_mfma(const PairState& s, const void* frag, const uint32_t* krc29) {
+    constexpr int T = 17;
+    mfma_v4i b[2][2];
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) b[e][ct] = blk8_b_of_slot(s, 4 + e, ct);
+    __syncthreads();                                   // both waves hold x4 and x5: slots 4 and 5 may be overwritten
+    const mfma_v4i* A = reinterpret_cast<const mfma_v4i*>(frag) + s.lane;
+#pragma unroll 1
+    for (int i = s.isY ? 1 : 0; i < T; i += 2) {
+        mfma_v16i acc[2];
+        mfma_zero_tile(acc);
+        const mfma_v4i* Ai = A + ((size_t)i * T + 4) * 64;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const mfma_v4i a = Ai[(size_t)e * 64];
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
+        }
+        uint32_t l[9]; mfma_post_limbs(acc, l);
+        pair_sto_sbox29(s, i, l, c29(krc29, i));
+    }
+    __syncthreads();
 }
 
 // ---- partial rounds in BLOCKS OF 8, both long products on the matrix cores (T = 17, rp % 8 == 0) ------------------------------------------------------
@@ -322,39 +353,6 @@ __device__ __forceinline__ void blk8_load_frags16(mfma_v4i (&a)[16], const mfma_
 #pragma unroll
     for (int e = 0; e < 16; ++e) a[e] = (A + (size_t)e * 64)[lane];
 }
-// Round 0 of the leaf permutation through the same row pipeline with TWO K-steps: 15 of the 17 lanes of hash_leaf_pair's template are constants, so round 0's
-// product is K_i + M[i][4] x4 + M[i][5] x5 (host_util.hpp leaf_round0_consts), a dense row with two live columns and a constant.  Precondition: slots 4 and 5 hold
-// x4 and x5 RECODED and a barrier has passed.  Row i = fragments (i, 4), (i, 5) of the full rounds' table against the two operands, fold and exchange and finish
-// as every fused row (mfma_post_limbs), and the hand-over to round 1's S-box with krc29[i] = (K_i + rc_full[17 + i]) mod r as its constant — X the even rows,
-// Y the odd ones.  Ends like pair_sbox_full<17, true> of round 1: every slot a recoded S-box output, behind a barrier.
-//   digit sums  |S_c| <= 2 * 32 * 128 * 128 = 1 048 576 = 2^20, far inside mfma_word_cols_mad's domain (23 K-steps);
-//   S-box input u = W + krc29[i] with W < 3 r + 2^146 (mfma_finish_words) and the constant canonical: u < 4 r + 2^146 < 4.0001 r, limbs below 2^30 — the fused
-//               rows' bound, inside pow5_lazy29's 4.25 r.
-__device__ __forceinline__ void pair_leaf_round0_mfma(const PairState& s, const void* frag, const uint32_t* krc29) {
-    constexpr int T = 17;
-    mfma_v4i b[2][2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) b[e][ct] = blk8_b_of_slot(s, 4 + e, ct);
-    __syncthreads();                                   // both waves hold x4 and x5: slots 4 and 5 may be overwritten
-    const mfma_v4i* A = reinterpret_cast<const mfma_v4i*>(frag) + s.lane;
-#pragma unroll 1
-    for (int i = s.isY ? 1 : 0; i < T; i += 2) {
-        mfma_v16i acc[2];
-        mfma_zero_tile(acc);
-        const mfma_v4i* Ai = A + ((size_t)i * T + 4) * 64;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const mfma_v4i a = Ai[(size_t)e * 64];
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b[e][ct], acc[ct], 0, 0, 0);
-        }
-        uint32_t l[9]; mfma_post_limbs(acc, l);
-        pair_sto_sbox29(s, i, l, c29(krc29, i));
-    }
-    __syncthreads();
-}
 // round Q in wave X: u = lambda_Q X_Q + lambda_Q c_Q on entry, the same of round Q + 1 on exit, as a LAZY residue (nine limbs below 2^30, below 3.05 r:
 // mfma_digits.hpp); no field element is formed.  b[Q]: yt_Q as B operands on exit
 template <int Q>
@@ -392,13 +390,18 @@ __device__ __forceinline__ void blk8_round_y(const PairState& s, const Blk8Tabs&
     __syncthreads();                                       // barrier_Q: y_Q is posted
     b[Q][0] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 0); b[Q][1] = blk8_b_of_slot(s, Blk8Cfg::ymail(Q), 1);
 }
+// How a lane row of an 8-round block ends (wave-uniform, a runtime value).  Between two blocks:
+//   Bytes      (pair_permute_fused) the digits of the lane's SIGNED residue, finished in the byte domain (mfma_post_bytes: word columns folded where the sums sit,
+//              a quotient estimate, one pass over eight words; no 29-bit limbs, no conditional subtraction);
+//   Recoded    (pair_permute_blk8) the canonical value, recoded.  k_hash_ds2 keeps it: with the signed form k_hash_ds2<17, DsBatchStream, true> spilled 6 VGPRs
+//              (28 B of scratch);
+// in the permutation's last block:
+//   NextSbox   (pair_permute_fused) lane j goes from its nine finish limbs through the S-box of the full round that follows (rc29_next: that round's constants,
+//              17 x 9 limbs) and is stored recoded as the round's operand, like a fused product row;
+//   Canonical  (pair_permute_blk8) the canonical value.
 // the lane product: s_j <- s_j + sum_p w_{p,j} y_p for this wave's share of the lanes (X lanes 1..NLX, Y the rest), b: y_0..y_7 as B operands.  Ends with a barrier.
-// rc29_next != nullptr (FUSE, the permutation's last block): the constants of the full round that follows, 17 x 9 limbs; lane j then goes from its nine finish
-// limbs through that round's S-box (sbox_lazy29) and is stored recoded as the round's operand, like a fused product row.
-// LAZY (the FUSE kernels): between two blocks a lane is stored as the digits of its SIGNED residue, finished in the byte domain (mfma_post_bytes: word columns
-// folded where the sums sit, a quotient estimate, one pass over eight words; no 29-bit limbs, no conditional subtraction).  k_hash_ds2 keeps canonical lanes: with the signed form k_hash_ds2<17, DsBatchStream, true> spilled 6 VGPRs (28 B of scratch).
-template <int NLX, bool LAZY = false>
-__device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], bool last, const uint32_t* rc29_next = nullptr) {
+template <int NLX>
+__device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tabs& Tb, const mfma_v4i (&b)[8][2], LaneEnd end, const uint32_t* rc29_next = nullptr) {
     static_assert(NLX >= 1 && NLX <= 15, "shares");
     const int lane = s.lane;
     const int j0 = s.isY ? NLX + 1 : 1, j1 = s.isY ? 16 : NLX;
@@ -420,18 +423,18 @@ __device__ __forceinline__ void blk8_lane_rows(const PairState& s, const Blk8Tab
 #pragma unroll
         for (int p = 0; p < 8; ++p) a[p] = (Tb.lfrag + ((size_t)(jn - 1) * 8 + p) * 64)[lane];
         // slot j is read by this wave alone, before this write
-        if (rc29_next) { uint32_t l[9]; mfma_post_limbs(acc, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j)); }
-        else if (LAZY && !last) s.sto(j, mfma_post_bytes(acc));
-        else { const fr_t z = mfma_post(acc); s.sto(j, last ? z : recode_signed(z)); }      // between two blocks: the signed residue's digits, no canonical value
+        if (end == LaneEnd::NextSbox) { uint32_t l[9]; mfma_post_limbs(acc, l); pair_sto_sbox29(s, j, l, c29(rc29_next, j)); }
+        else if (end == LaneEnd::Bytes) s.sto(j, mfma_post_bytes(acc));
+        else { const fr_t z = mfma_post(acc); s.sto(j, end == LaneEnd::Canonical ? z : recode_signed(z)); }
     }
     __syncthreads();
 }
-// One block.  Precondition: lanes 1..16 RECODED in their slots and a barrier since; u = lambda_0 X_0 + lambda_0 c_0 of the block's first round as nine limbs in wave X.  Ends with a barrier, the lanes recoded again (LAZY: as digits of their signed residue),
-// or canonical after the permutation's last block.
-// With rc29_next (FUSE, last block): every slot ends as the next full round's S-box output instead — the lanes through blk8_lane_rows, element 0 from the chain's
-// final value (lazy, no constant in it), brought back from lambda_rp X_rp by one product with unscale29 = 1 / lambda_rp first and handed to the S-box as limbs.
-template <int NLX, bool LAZY = false>
-__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr29_t& u, bool last, const uint32_t* rc29_next = nullptr,
+// One block.  Precondition: lanes 1..16 RECODED in their slots (canonical values or digits of a signed residue) and a barrier since; u = lambda_0 X_0 + lambda_0 c_0
+// of the block's first round as nine limbs in wave X.  Ends with a barrier, the lanes as `end` names.
+// With LaneEnd::NextSbox every slot ends as the next full round's S-box output — the lanes through blk8_lane_rows, element 0 from the chain's final value
+// (lazy, no constant in it), brought back from lambda_rp X_rp by one product with unscale29 = 1 / lambda_rp first and handed to the S-box as limbs.
+template <int NLX>
+__device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& Tb, fr29_t& u, LaneEnd end, const uint32_t* rc29_next = nullptr,
                                             const uint32_t* unscale29 = nullptr) {
     mfma_v4i b[8][2];
     if (!s.isY) {
@@ -445,10 +448,27 @@ __device__ __forceinline__ void pair_block8(const PairState& s, const Blk8Tabs& 
     }
     __builtin_amdgcn_sched_barrier(0);
     // slot 0 was H's mailbox in the even rounds, last read by X after barrier_6; the lane rows' closing barrier publishes the store
-    if (rc29_next && !s.isY) { const fr29_t x = fr29_mul_c29(unscale29, u); pair_sto_sbox29(s, 0, x.l, c29(rc29_next, 0)); }
-    blk8_lane_rows<NLX, LAZY>(s, Tb, b, last, rc29_next);
+    if (end == LaneEnd::NextSbox && !s.isY) { const fr29_t x = fr29_mul_c29(unscale29, u); pair_sto_sbox29(s, 0, x.l, c29(rc29_next, 0)); }
+    blk8_lane_rows<NLX>(s, Tb, b, end, rc29_next);
+}
+// The partial rounds in rp / 8 blocks, the lanes ending as `mid` names between two blocks and as `last` names after the last one.
+__device__ __forceinline__ void pair_blocks8(const PairState& s, const PoseidonDev& P, fr29_t& u, LaneEnd mid, LaneEnd last) {
+    const int nb = P.rp / 8;
+#pragma unroll 1
+    for (int b = 0; b < nb; ++b) {
+        const Blk8Tabs Tb{reinterpret_cast<const mfma_v4i*>(P.blk8_efrag) + (size_t)b * 8 * 16 * 64, reinterpret_cast<const mfma_v4i*>(P.blk8_lfrag) + (size_t)b * 16 * 8 * 64,
+                          reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), reinterpret_cast<const mfma_v4i*>(P.blk8_gfrag) + (size_t)b * 28 * 64,
+                          c29(P.rc_partial_scaled29, (size_t)8 * b + 1)};
+        pair_block8<Blk8Cfg::NLX>(s, Tb, u, b == nb - 1 ? last : mid, c29(P.rc_full29, (size_t)(P.rf / 2) * 17), P.blk8_unscale29());
+    }
 }
 
+// ---- partial rounds in BLOCKS OF 4 on the vector ALU (permute_core in poseidon_dev.hpp has the algebra) ---------------------------------------------------
+//   phase 1  X runs the S-box chain: x_q, then a_q x_q + sum_{p<q} gamma x_p + its share (lanes 1..NXD) of the lane dot product from registers; Y computes the
+//            other lanes' part of every round's dot product from the block-start state and posts it in an LDS mailbox (one barrier per round);
+//   phase 2  both waves bring their half of the lanes up to date, s_j += sum_p w_{p,j} x_p (one reduction per lane), X from registers, Y from the x mailboxes.
+// The mailboxes reuse state slots that are dead during the block (slot 0: X holds s0 in registers; slots 1..NXD: X preloads those lanes), so the LDS budget
+// stays at 4 workgroups per CU.
 // s_j += w_{0,j} x0 + w_{1,j} x1 + w_{2,j} x2 + w_{3,j} x3   (one reduction)
 template <int T>
 __device__ __forceinline__ fr_t pair_lane_update(const uint32_t* sp, int j, const fr_t& base, const fr29_t& x0, const fr29_t& x1, const fr29_t& x2, const fr29_t& x3) {
@@ -462,67 +482,13 @@ __device__ __forceinline__ fr_t pair_lane_update(const uint32_t* sp, int j, cons
     return fr_add<PF>(base, fr_wide29_reduce_lazy<PF>(u));
 }
 
-// One permutation by the wave pair.  Precondition: state consistent (a barrier since the last write).
-// Returns lane 0 of the result; with only0 in wave X ALONE (every caller stores it from there), and the rest of the state is dead afterwards.
-// BLK8 (T = 17, a parameter set with blk8 tables): the partial rounds in blocks of 8 (pair_block8) instead of blocks of 4.
-// Precondition of BLK8 without FUSE: when the partial rounds are entered, lanes 1..16 are CANONICAL (recode_signed needs x < r).  The full round before them
-// leaves them so (mfma_finish_words_canonical); with r_begin >= rf / 2 no full round runs first and the caller's stores must be canonical (today's callers
-// store fr_add results and field elements from memory).  With FUSE the product of round rf / 2 - 1 leaves the lanes and the chain value as the first block
-// takes them (pair_mds_sbox_mfma, entry), so r_begin < rf / 2 is required: the launchers only pick the 8-round form for sets with rf >= 2.
-// FUSE (BLK8 only, its default): every full-round product that is followed by a full round hands its rows to that round's S-box in limb form
-// (pair_mds_sbox_mfma), and the last block's lane rows hand theirs to the S-box after the partial rounds (blk8_lane_rows).  k_hash_ds2 turns it off: its generic stream state is live across the permutation, and with the S-box's columns beside the product's
-// operand registers three of its instantiations took 88 / 36 / 52 B of scratch against 44 / 12 / 28 B without (the two fixed-shape kernels hold 244 VGPRs, none spilled).
-// SBOXED (FUSE only; k_leaf_pair2<true>): the caller's own product in front of round r_begin has handed its rows to that round's S-box already
-// (pair_leaf_round0_mfma), so every slot holds a recoded S-box output behind a barrier and the standalone S-box is skipped.  Needs r_begin < rf / 2: a full-round
-// product follows.
-template <int T, bool BLK8 = false, bool FUSE = BLK8, bool SBOXED = false>
-__device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonDev& P, bool only0, int r_begin = 0) {
-    static_assert(!BLK8 || T == 17, "8-round blocks exist for t = 17");
-    static_assert(!FUSE || BLK8, "the fused hand-over belongs to the 8-round form");
-    static_assert(!SBOXED || FUSE, "entering behind an S-box belongs to the fused form");
+// All rp partial rounds.  Precondition: state consistent.  Ends with the state consistent; the lanes 1..T-1 are NOT canonical (pair_lane_update), element 0 is.
+template <int T>
+__device__ __forceinline__ void pair_blocks4(const PairState& s, const PoseidonDev& P) {
     typedef PairCfg<T> Cfg;
     constexpr int NXD = Cfg::NXD, NXU = Cfg::NXU, W = 2 * T - 1;
-    const int half = P.rf / 2;
-    if constexpr (FUSE) {
-        // one standalone S-box, then every product hands its rows to the next round's S-box in limb form; the product in front of the partial rounds ends as the
-        // first block takes its rows (entry): needs r_begin < rf / 2, which the launchers see to (pair_block8_form)
-        if constexpr (!SBOXED) { if (r_begin < half) pair_sbox_full<T, true>(s, P.rc_full + r_begin * T); }
-        for (int r = r_begin; r < half; ++r)
-            pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, (r == half - 1) ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T), r == half - 1);
-    } else
-    for (int r = r_begin; r < half; ++r) {
-        if constexpr (T == 17) { pair_sbox_full<T, true>(s, P.rc_full + r * T); pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, nullptr); }
-        else { pair_sbox_full<T>(s, P.rc_full + r * T); pair_apply_lu<T>(s, (r == half - 1) ? P.lu_pre29 : P.lu29); }
-    }
     fr_t s0 = fr_zero<PF>();
-    if constexpr (!FUSE) { if (!s.isY) s0 = s.ld(0); }
-    if constexpr (BLK8) {
-        // the chain as nine limbs from here to the unscale product; the first constant (lambda_0 = 1) enters here, every later one in Y's finish
-        fr29_t u;
-        if constexpr (FUSE) {
-            // the entry product left the lanes as digits and row 0 as its finish limbs W (below 3 r + 2^146, limbs below 2^29) behind its closing barrier:
-            // u = W + lambda_0 c_0 below 4 r + 2^146 < 4.0001 r with limbs below 2^30, the fused rows' bound, inside pow5_lazy29's 4.25 r
-#pragma unroll
-            for (int i = 0; i < 9; ++i) u.l[i] = 0;
-            if (!s.isY) { u = lazy29_add_slot(u, s.ld(kEntrySlot)); u = lazy29_add_c29(u.l, c29(P.rc_partial_scaled29, 0)); }
-        } else {
-            u = fr29_unpack(s0);
-            if (!s.isY) u = lazy29_add_c29(u.l, c29(P.rc_partial_scaled29, 0));      // canonical + canonical: below 2 r, limbs below 2^30
-            for (int j = s.isY ? 9 : 1; j <= (s.isY ? 16 : 8); ++j) s.sto(j, recode_signed(s.ld(j)));        // canonical since the full round's finish
-            __syncthreads();
-        }
-        const int nb = P.rp / 8;
-#pragma unroll 1
-        for (int b = 0; b < nb; ++b) {
-            const Blk8Tabs Tb{reinterpret_cast<const mfma_v4i*>(P.blk8_efrag) + (size_t)b * 8 * 16 * 64, reinterpret_cast<const mfma_v4i*>(P.blk8_lfrag) + (size_t)b * 16 * 8 * 64,
-                              reinterpret_cast<const mfma_v4i*>(P.blk8_unit_frag), reinterpret_cast<const mfma_v4i*>(P.blk8_gfrag) + (size_t)b * 28 * 64,
-                              c29(P.rc_partial_scaled29, (size_t)8 * b + 1)};
-            if constexpr (FUSE) pair_block8<Blk8Cfg::NLX, true>(s, Tb, u, b == nb - 1, b == nb - 1 ? c29(P.rc_full29, (size_t)half * T) : nullptr, P.blk8_unscale29());
-            else pair_block8<Blk8Cfg::NLX>(s, Tb, u, b == nb - 1);
-        }
-        // FUSE: the chain value was unscaled inside the last block, in front of element 0's S-box; otherwise the state's element 0 ends canonical here
-        if constexpr (!FUSE) { if (!s.isY) s0 = fr29_pack_reduce<PF>(fr29_mul_c29(P.blk8_unscale29(), u).l); }
-    } else
+    if (!s.isY) s0 = s.ld(0);
     for (int b = 0; b < P.rp / 4; ++b) {
         const uint32_t* sp = c29(P.sparse29, (size_t)(4 * b) * W);
         const uint32_t* g = c29(P.gamma29, (size_t)b * 6);
@@ -576,79 +542,142 @@ __device__ __forceinline__ fr_t pair_permute(const PairState& s, const PoseidonD
         }
         __syncthreads();                                               // E: lanes 1..T-1 consistent, mailboxes free
     }
-    if constexpr (!FUSE) {
-        if (!s.isY) s.sto(0, s0);
-        __syncthreads();
-    }   // FUSE: the last block left round half's S-box outputs recoded in every slot, behind its closing barrier
-    for (int r = half; r < P.rf; ++r) {
-        const bool squeeze = only0 && r == P.rf - 1;
-        if constexpr (FUSE) { /* this round's S-box ran with the row that fed it */ }
-        else if constexpr (T == 17) pair_sbox_full<T, true>(s, P.rc_full + r * T);
-        else pair_sbox_full<T>(s, P.rc_full + r * T);
-        if constexpr (T == 17) {
-            if (squeeze) {                                  // squeeze: row 0 only, one matrix-core row in wave X (X-only work between two barriers both waves pass)
-                fr_t out = fr_zero<PF>();
-                if (!s.isY) out = pair_squeeze_row_mfma(s, P.mds_frag);
-                __syncthreads();                            // the slots are reused by the next permutation
-                return out;
-            }
-        } else
-        if (squeeze) {                                      // squeeze: row 0 only, split over the two waves
-            const int j0 = s.isY ? Cfg::NX : 0, j1 = s.isY ? T : Cfg::NX;
-            DotAcc acc; acc.init();
+    if (!s.isY) s.sto(0, s0);
+    __syncthreads();
+}
+
+// ---- the permutations -------------------------------------------------------------------------------------------------------------------------------
+// Every entry: one permutation by the wave pair.  Precondition: state consistent (a barrier since the last write).  Returns lane 0 of the result; with only0 in
+// wave X ALONE (every caller stores it from there), and the rest of the state is dead afterwards; without only0 the state ends canonical behind a barrier.
+// The first full rounds with canonical ends, rounds r_begin .. rf / 2 - 1: the standalone S-box pass, then the dense product (the last one with B_1 folded in).
+template <int T>
+__device__ __forceinline__ void pair_first_rounds(const PairState& s, const PoseidonDev& P, int r_begin) {
+    const int half = P.rf / 2;
+    for (int r = r_begin; r < half; ++r) {
+        pair_sbox_full<T>(s, P.rc_full + r * T);
+        if constexpr (T == 17) pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, RowEnd::Canonical);
+        else pair_apply_lu<T>(s, (r == half - 1) ? P.lu_pre29 : P.lu29);
+    }
+}
+// The squeeze round's product when only element 0 is wanted: row 0 alone.  Returned in wave X alone for t = 17.
+template <int T>
+__device__ __forceinline__ fr_t pair_squeeze(const PairState& s, const PoseidonDev& P) {
+    fr_t out = fr_zero<PF>();
+    if constexpr (T == 17) {                        // one matrix-core row in wave X (X-only work between two barriers both waves pass)
+        if (!s.isY) out = pair_squeeze_row_mfma(s, P.mds_frag);
+    } else {                                        // split over the two waves
+        const int j0 = s.isY ? PairCfg<T>::NX : 0, j1 = s.isY ? T : PairCfg<T>::NX;
+        DotAcc acc; acc.init();
 #pragma unroll 1
-            for (int j = j0; j < j1; ++j) acc.mac(c29(P.row0_29, j), s.ld(j));
-            s.sto(T + (s.isY ? 1 : 0), acc.finish());                // two of the extra slots: not part of the state
-            __syncthreads();
-            fr_t out = fr_add<PF>(s.ld(T + 0), s.ld(T + 1));
-            __syncthreads();                                 // the slots are reused by the next permutation
-            return out;
-        }
-        if constexpr (FUSE) pair_mds_sbox_mfma(s, P.mds_frag, r == P.rf - 1 ? nullptr : c29(P.rc_full29, (size_t)(r + 1) * T));
-        else if constexpr (T == 17) pair_mds_sbox_mfma(s, P.mds_frag, nullptr); else pair_apply_lu<T>(s, P.lu29);
+        for (int j = j0; j < j1; ++j) acc.mac(c29(P.row0_29, j), s.ld(j));
+        s.sto(T + (s.isY ? 1 : 0), acc.finish());                // two of the extra slots: not part of the state
+        __syncthreads();
+        out = fr_add<PF>(s.ld(T + 0), s.ld(T + 1));
+    }
+    __syncthreads();                                // the slots are reused by the next permutation
+    return out;
+}
+// The last full rounds, rf / 2 .. rf - 1, and the squeeze.  HANDED (pair_permute_fused): every slot already holds the recoded S-box output of round rf / 2 behind
+// a barrier, and every product but the last hands its rows to the next round's S-box, so no standalone S-box pass runs; otherwise the state is consistent and the
+// ends canonical.  The last round stands outside the loop, so every product's end is known where it is inlined: with one loop and a runtime end
+// k_leaf_pair2<true> and k_node16_pair<true> spilled 4 VGPRs.
+template <int T, bool HANDED>
+__device__ __forceinline__ fr_t pair_last_rounds(const PairState& s, const PoseidonDev& P, bool only0) {
+    for (int r = P.rf / 2; r < P.rf - 1; ++r) {
+        if constexpr (!HANDED) pair_sbox_full<T>(s, P.rc_full + r * T);
+        if constexpr (HANDED) pair_mds_sbox_mfma(s, P.mds_frag, RowEnd::NextSbox, c29(P.rc_full29, (size_t)(r + 1) * T));
+        else if constexpr (T == 17) pair_mds_sbox_mfma(s, P.mds_frag, RowEnd::Canonical);
+        else pair_apply_lu<T>(s, P.lu29);
+    }
+    if (P.rf > 0) {                                     // the last round: the squeeze, or a product that ends canonical
+        if constexpr (!HANDED) pair_sbox_full<T>(s, P.rc_full + (P.rf - 1) * T);
+        if (only0) return pair_squeeze<T>(s, P);
+        if constexpr (T == 17) pair_mds_sbox_mfma(s, P.mds_frag, RowEnd::Canonical);
+        else pair_apply_lu<T>(s, P.lu29);
     }
     return s.ld(0);
 }
-
-__device__ __forceinline__ PairState pair_setup(uint4* lds) {
-    PairState s; s.st = lds; s.lane = threadIdx.x & 63;
-    s.isY = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0;      // wave-uniform by construction: tell the compiler (scalar branches, scalar constant loads)
-    return s;
+// Full rounds on the VALU (t = 9) or on the matrix cores with canonical ends (t = 17), partial rounds in blocks of 4.  With r_begin > 0 the caller has run the
+// rounds before r_begin itself and left their output consistent in the state.
+template <int T>
+__device__ __forceinline__ fr_t pair_permute_blk4(const PairState& s, const PoseidonDev& P, bool only0, int r_begin = 0) {
+    pair_first_rounds<T>(s, P, r_begin);
+    pair_blocks4<T>(s, P);
+    return pair_last_rounds<T, false>(s, P, only0);
 }
+// t = 17 (a parameter set with blk8 tables), 8-round blocks with canonical hand-overs at both ends of the partial rounds.  The full round in front of them leaves
+// lanes 1..16 CANONICAL (mfma_finish_words_canonical), which recode_signed needs (x < r); with rf = 0 the caller's stores must be canonical.
+// k_hash_ds2 runs this form and not the fused one: its generic stream state is live across the permutation, and with the S-box's columns beside the product's
+// operand registers three of its instantiations took 88 / 36 / 52 B of scratch against 44 / 12 / 28 B without.
+__device__ __forceinline__ fr_t pair_permute_blk8(const PairState& s, const PoseidonDev& P, bool only0) {
+    pair_first_rounds<17>(s, P, 0);
+    // the chain as nine limbs from here to the unscale product; the first constant (lambda_0 = 1) enters here, every later one in Y's finish
+    fr_t s0 = fr_zero<PF>();
+    if (!s.isY) s0 = s.ld(0);
+    fr29_t u = fr29_unpack(s0);
+    if (!s.isY) u = lazy29_add_c29(u.l, c29(P.rc_partial_scaled29, 0));      // canonical + canonical: below 2 r, limbs below 2^30
+    for (int j = s.isY ? 9 : 1; j <= (s.isY ? 16 : 8); ++j) s.sto(j, recode_signed(s.ld(j)));
+    __syncthreads();
+    pair_blocks8(s, P, u, LaneEnd::Recoded, LaneEnd::Canonical);
+    if (!s.isY) s.sto(0, fr29_pack_reduce<PF>(fr29_mul_c29(P.blk8_unscale29(), u).l));      // lambda_rp X_rp (lazy) -> X_rp, canonical
+    __syncthreads();
+    return pair_last_rounds<17, false>(s, P, only0);
+}
+// t = 17, 8-round blocks, no canonical value between the first S-box and the last product: every full-round product that is followed by a full round hands its
+// rows to that round's S-box in limb form (RowEnd::NextSbox), the product of round rf / 2 - 1 leaves the lanes and the chain value as the first block takes them
+// (RowEnd::BlockEntry), and the last block's lane rows hand theirs to the S-box after the partial rounds (LaneEnd::NextSbox).  Needs r_begin < rf / 2 (the entry
+// product must run), which the launchers see to: they pick this form only for sets with rf >= 2, k_leaf_pair2 (r_begin = 1) for rf >= 4.
+// SBOXED (k_leaf_pair2<true>): the caller's own product in front of round r_begin has handed its rows to that round's S-box already (pair_leaf_round0_mfma), so
+// every slot holds a recoded S-box output behind a barrier and the standalone S-box is skipped.
+template <bool SBOXED>
+__device__ __forceinline__ fr_t pair_permute_fused(const PairState& s, const PoseidonDev& P, bool only0, int r_begin) {
+    const int half = P.rf / 2;
+    if constexpr (!SBOXED) { if (r_begin < half) pair_sbox_full<17>(s, P.rc_full + r_begin * 17); }
+    for (int r = r_begin; r < half; ++r)
+        pair_mds_sbox_mfma(s, (r == half - 1) ? P.mds_pre_frag : P.mds_frag, (r == half - 1) ? RowEnd::BlockEntry : RowEnd::NextSbox, c29(P.rc_full29, (size_t)(r + 1) * 17));
+    // the entry product left the lanes as digits and row 0 as its finish limbs W (below 3 r + 2^146, limbs below 2^29) behind its closing barrier:
+    // u = W + lambda_0 c_0 below 4 r + 2^146 < 4.0001 r with limbs below 2^30, the fused rows' bound, inside pow5_lazy29's 4.25 r
+    fr29_t u;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) u.l[i] = 0;
+    if (!s.isY) { u = lazy29_add_slot(u, s.ld(kEntrySlot)); u = lazy29_add_c29(u.l, c29(P.rc_partial_scaled29, 0)); }
+    pair_blocks8(s, P, u, LaneEnd::Bytes, LaneEnd::NextSbox);      // the chain value is unscaled inside the last block, in front of element 0's S-box
+    return pair_last_rounds<17, true>(s, P, only0);
+}
+
+// ---- kernels ------------------------------------------------------------------------------------------------------------------------------------------
 
 // K3 (pair form): h[i] = hash_leaf_pair(f[i], f_next[i/m] or 0).  Block = 128 threads = 64 states.
 template <bool BLK8>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_leaf_pair2(PoseidonDev P, const fr_t* __restrict__ leafc, const fr_t* __restrict__ f,
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k_leaf_pair2(PoseidonDev P, const LeafConsts* __restrict__ lc, const fr_t* __restrict__ f,
                                                     const fr_t* __restrict__ f_next, size_t n, size_t m, fr_t* __restrict__ h) {
     extern __shared__ uint4 lds[];
     PairState s = pair_setup(lds);
     const size_t i = (size_t)blockIdx.x * 64 + s.lane; const bool live = i < n; const size_t ii = live ? i : n - 1;   // tail lanes recompute the last leaf
     // Round 0 in closed form: 15 of the 17 lanes of the transcript template are constants, so after ARK and
-    // S-box the MDS output is  K_i + M[i][4]*x4 + M[i][5]*x5  with K precomputed on the host
-    // (leafc = [K(17) | M[:,4](17) | M[:,5](17) | the two columns in radix 2^29 | (K + round 1's constants)(17 x 9 limbs)]).
+    // S-box the MDS output is  K_i + M[i][4]*x4 + M[i][5]*x5  with K precomputed on the host (LeafConsts).
     if constexpr (BLK8) {
         // The 8-round form: X computes x4, Y x5 (the zero input without f_next), each stored recoded; the product is a two-K-step row per element on the
         // matrix cores, handed to round 1's S-box in limb form (pair_leaf_round0_mfma), and the permutation is entered behind that S-box.
         const fr_t in = s.isY ? (f_next ? ldg(f_next + ii / m) : fr_zero<PF>()) : ldg(f + ii);
         s.sto(s.isY ? 5 : 4, recode_signed(fr_pow5_r29<PF>(fr_add<PF>(in, P.rc_full[s.isY ? 5 : 4]))));
         __syncthreads();
-        pair_leaf_round0_mfma(s, P.mds_frag, reinterpret_cast<const uint32_t*>(leafc + kLeafKrcOff));
-        const fr_t out = pair_permute<17, true, true, true>(s, P, true, 1);
+        pair_leaf_round0_mfma(s, P.mds_frag, lc->krc29);
+        const fr_t out = pair_permute_fused<true>(s, P, true, 1);
         if (live && !s.isY) stg(h + i, out);
     } else {
     // The blocks of 4 (the comparison form): both waves compute x4, x5; each fills its own lanes on the vector ALU.
     const fr_t x4 = fr_pow5_r29<PF>(fr_add<PF>(ldg(f + ii), P.rc_full[4]));
     const fr_t x5 = fr_pow5_r29<PF>(fr_add<PF>(f_next ? ldg(f_next + ii / m) : fr_zero<PF>(), P.rc_full[5]));
     const int j0 = s.isY ? PairCfg<17>::NX : 0, j1 = s.isY ? 17 : PairCfg<17>::NX;
-    const uint32_t* m45 = reinterpret_cast<const uint32_t*>(leafc + 51);   // columns 4 and 5 of M in radix 2^29 (17 + 17 entries)
     const fr29_t x4u = fr29_unpack(x4), x5u = fr29_unpack(x5);
     for (int j = j0; j < j1; ++j) {
         fr_wide29 w; fr_wide29_zero(w);
-        fr_wide29_mac(w, c29(m45, j), x4u); fr_wide29_mac(w, c29(m45, 17 + j), x5u);
-        s.sto(j, fr_add<PF>(leafc[j], fr_wide29_reduce<PF>(w)));
+        fr_wide29_mac(w, c29(lc->m45_29, j), x4u); fr_wide29_mac(w, c29(lc->m45_29, 17 + j), x5u);
+        s.sto(j, fr_add<PF>(lc->K[j], fr_wide29_reduce<PF>(w)));
     }
     __syncthreads();
-    fr_t out = pair_permute<17, BLK8>(s, P, true, 1);
+    fr_t out = pair_permute_blk4<17>(s, P, true, 1);
     if (live && !s.isY) stg(h + i, out);
     }
 }
@@ -681,7 +710,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
             }
         }
         __syncthreads();
-        res = pair_permute<T, BLK8, false>(s, P, pidx + 1 == max_perm);
+        if constexpr (BLK8) res = pair_permute_blk8(s, P, pidx + 1 == max_perm);
+        else res = pair_permute_blk4<T>(s, P, pidx + 1 == max_perm);
         __syncthreads();
     }
     if (live && !s.isY) stg(out + k0, res);
@@ -713,7 +743,7 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
         s.sto(16, fr_zero<PF>());
     }
     __syncthreads();
-    pair_permute<17, BLK8>(s, P, false);           // ends with a barrier: the state is consistent
+    if constexpr (BLK8) pair_permute_fused<false>(s, P, false, 0); else pair_permute_blk4<17>(s, P, false);      // ends with a barrier: the state is consistent
     // perm 2: children 12..15 and the closing 1 into elements 0..4 (X's)
     if (!s.isY) {
 #pragma unroll
@@ -721,7 +751,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) k
         s.sto(4, fr_add<PF>(s.ld(4), fr_one<PF>()));
     }
     __syncthreads();
-    const fr_t res = pair_permute<17, BLK8>(s, P, true);
+    fr_t res;
+    if constexpr (BLK8) res = pair_permute_fused<false>(s, P, true, 0); else res = pair_permute_blk4<17>(s, P, true);
     if (live && !s.isY) stg(out + k0, res);
 }
 

@@ -1,5 +1,7 @@
 // stark_mlwe_amd/csrc/poseidon_params.hpp — device view of the Poseidon constants (kernel form).
 #pragma once
+#include <cstddef>
+#include <type_traits>
 #include "fr.hpp"
 namespace stark {
 struct PoseidonDev {           // device pointers to kernel-form constants (see host_util.hpp KernelConsts)
@@ -31,5 +33,17 @@ struct PoseidonDev {           // device pointers to kernel-form constants (see 
     // added limb by limb to a product row that stays in limbs up to its S-box (poseidon_pair.hpp sbox_lazy29)
     const uint32_t* rc_full29;
 };
+
+// The leaf constants of hash_leaf_pair on the device (capi_poseidon.hip ctx_leaf_init fills it): the 17-lane template, of which lanes 4, 5 = (f, s) are the only
+// inputs, and round 0 in closed form for the wave-pair kernels (host_util.hpp leaf_round0_consts): the MDS output is K_i + M[i][4] x4 + M[i][5] x5.
+struct LeafConsts {
+    fr_t init[17];                              // the template (every leaf kernel; LeafStream::init)
+    fr_t K[17];                                 // K_i = sum_{j != 4, 5} M[i][j] (init_j + rc0_j)^5
+    fr_t m4[17], m5[17];                        // columns 4 and 5 of M
+    alignas(16) uint32_t m45_29[2 * 17 * 9];    // the two columns times 2^20 as multiplier-table entries in radix 2^29, m4 then m5 (k_leaf_pair2<false>)
+    alignas(16) uint32_t krc29[17 * 9];         // (K_i + round 1's constant) mod r as nine limbs of the stored value (k_leaf_pair2<true>, pair_leaf_round0_mfma)
+};
+static_assert(std::is_trivially_copyable<LeafConsts>::value, "uploaded byte for byte");
+static_assert(offsetof(LeafConsts, m45_29) % 16 == 0 && offsetof(LeafConsts, krc29) % 16 == 0, "the 32-bit tables start at 16 bytes, as the field elements in front of them do");
 
 }  // namespace stark

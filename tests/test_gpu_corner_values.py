@@ -9,13 +9,13 @@ chosen digits.  tests/test_corner_values_host.py checks the construction itself 
 Chosen words in EVERY round: stark_poseidon_params_upload takes arbitrary round constants and the S-box input of every round is state + rc, so
 for one chosen node the constants are picked (corner_values.steered_params / steered_node) such that all 8 t full-round S-box outputs and all rp
 partial-round outputs x_q on its trajectory are chosen stored values: the recoding sees chosen digits in all eight full rounds, the carry-free
-radix-2^29 accumulations of pair_permute's four-round blocks and the five-wave form's chain tables see chosen x_q at every block position, and the
+radix-2^29 accumulations of pair_permute_blk4's four-round blocks and the five-wave form's chain tables see chosen x_q at every block position, and the
 uniform schedules make every term of every accumulation the same extreme at once.  Expected values under such a set come from pyref; the oracle
 library knows only the fixed sets.  The wide widths t = 33 / 65 / 129 (k_hash_ds_wave and the lane form with 32-lane blocks) get the crafted
 round-0 levels, and t = 33 / 65 steered sets as well; there is no steered set for t = 129, whose table derivation takes minutes.
 
 Not steerable: tr_hash, the leaf hash and the transcripts run the context's fixed transcript set (ctx_transcript_params; stark_leaf_pair_hash_dev
-rejects other constants).  They share pair_permute / coop_permute / chain_sponge_ex with the DS kernels, which is how they are covered; their own
+rejects other constants).  They share pair_permute_blk4 / pair_permute_blk8 / pair_permute_fused / coop_permute / chain_sponge_ex with the DS kernels, which is how they are covered; their own
 inputs stay at round-0 corners.  A full node's second permutation cannot be steered for GIVEN children (its input depends on every constant); it is
 steered by choosing the children so that it repeats the first one's trajectory, at the price of one forced target (steered_node).
 

@@ -1,7 +1,7 @@
 """The lazy chain of the 8-round partial blocks on the device (poseidon_pair.hpp blk8_round_x / blk8_round_y, mfma_digits.hpp: wave Y hands H_q over as
 its nine finish limbs with the next round's scaled constant in them, wave X adds them to the S-box output's limbs and never forms a field element inside
 a block, y_q is posted recoded from the unreduced x5) at the smallest shapes the launchers send to the three wave-pair kernels WITHOUT any option:
-k_leaf_pair2 from 4097 leaves, k_node16_pair for a level of 4097 full nodes, k_hash_ds2<17> (FUSE off, the same block internals) for 4100 nodes whose last
+k_leaf_pair2 from 4097 leaves, k_node16_pair for a level of 4097 full nodes, k_hash_ds2<17> (pair_permute_blk8, the same block internals) for 4100 nodes whose last
 has 5 children.  Against the oracle and against the context option "poseidon_block8" = 0 (blocks of 4 on the vector ALU, untouched); an uploaded rf = 2
 set (no fused product, a standalone squeeze S-box) and one steered level per uniform corner and per block position, every node against the reference's
 dense rounds under the steered constants.  Needs an MI355X: `pytest -m gpu`."""

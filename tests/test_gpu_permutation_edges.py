@@ -75,7 +75,7 @@ def hc_transcript_rc0():
     return [cv.raw_to_int(x) for x in rcf[:17]]
 
 
-@pytest.mark.parametrize("nodes,last", [(4097, None), (4100, 5)])        # k_node16_pair<true>; a ragged last node of 5 children: k_hash_ds2<17>, the non-FUSE squeeze
+@pytest.mark.parametrize("nodes,last", [(4097, None), (4100, 5)])        # k_node16_pair<true>; a ragged last node of 5 children: k_hash_ds2<17>, the squeeze of pair_permute_blk8
 def test_merkle_level_equals_blocks_of_4_and_oracle(gpu_ctx, oracle, nodes, last):
     """every node against the blocks of 4, and the oracle on the first, last and workgroup-boundary nodes"""
     p17 = gpu_ctx.poseidon_params_for_width(17)

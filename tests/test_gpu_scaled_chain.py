@@ -22,7 +22,7 @@ PAIR = {"merkle_wave_pair": (1, 0)}
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 129])         # one live lane; one tail lane; a full workgroup; two and three workgroups
 def test_leaf_kernel_equals_oracle_and_blocks_of_4(gpu_ctx, oracle, n):
-    """k_leaf_pair2 (the FUSE path: the unscale in front of element 0's fused S-box), m = 16, with f_next and without"""
+    """k_leaf_pair2 (pair_permute_fused: the unscale in front of element 0's fused S-box), m = 16, with f_next and without"""
     m = 16
     f = leaves(5000 + n, n); fn = leaves(6000 + n, (n + m - 1) // m)[::-1].copy()
     want = oracle.leaf_pair_hash(f, fn, m); want_plain = oracle.leaf_pair_hash(f, None, m)
@@ -52,7 +52,7 @@ def test_node16_kernel_equals_oracle_and_blocks_of_4(gpu_ctx, oracle, nodes):
 
 @pytest.mark.parametrize("n_in", [17, 1041])                # 2 and 66 nodes, the last one of a single child: its lane sits out the first permutation
 def test_ragged_level_equals_oracle_and_blocks_of_4(gpu_ctx, oracle, n_in):
-    """k_hash_ds2<17, DsStream, true> (no FUSE: the unscale in front of the store of element 0) over a stream of two permutations, the dead
+    """k_hash_ds2<17, DsStream, true> (pair_permute_blk8: the unscale in front of the store of element 0) over a stream of two permutations, the dead
     permutation of the short node included: every permutation must be unscaled"""
     p17 = gpu_ctx.poseidon_params_for_width(17)
     nodes = (n_in + 15) // 16
