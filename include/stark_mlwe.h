@@ -569,6 +569,23 @@ int32_t stark_lde_dev(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals,
 int32_t stark_ntt_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, uint64_t* const* data, size_t log_n, int32_t inverse, const uint64_t* coset4);
 int32_t stark_lde_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, const uint64_t* const* evals, size_t log_n, size_t log_blowup,
                             const uint64_t* coset4, uint64_t* const* out);
+/* The same with a length per column: log_n is a HOST array of `batch` entries, column i has 2^log_n[i] elements and is extended onto
+ * coset4 * <w_{N_i}>, N_i = 2^(log_n[i] + log_blowup); one log_blowup and one coset for the call.  Column i equals what stark_ntt_dev /
+ * stark_lde_dev returns for it alone under log_n[i], byte for byte.
+ * Stream-ordered with no host synchronisation; log_n, both tables and coset4 may be overwritten or freed the moment the call returns.  Inputs may
+ * repeat, and evals[i] may be out[i]; inputs are otherwise left intact; an input that overlaps ANOTHER column's output is not supported.
+ * batch == 0 is STARK_OK.  A column with log_n[i] == 0 takes no part in the transform; its extension is 2^log_blowup copies of its point.
+ * STARK_ERR_INVALID_ARG, checked on the host before anything is launched or allocated (the outputs stay untouched): a null ctx, table, entry or
+ * log_n; any log_n[i] or log_n[i] + log_blowup above 30; an unknown field; two `out` ranges (two `data` ranges), now of different lengths, that overlap.
+ * The batch is cut into consecutive passes of at most "ntt_batch_max_elems" output elements, in the caller's order (a greedy run over the sum of
+ * N_i); a pass of one column is the single call itself.  Inside a pass the passes of all transforms are aligned at the end of a three-step
+ * schedule and every step is one launch per kernel form for all columns, whatever their sizes: at most 5 launches for the transforms and
+ * 3 + 1 + 5 for the extensions (inverse transforms, one pad launch, forward transforms), independent of `batch` and of the sizes that occur.
+ * Scratch of a pass: the sum of N_i + 2^log_n[i] elements. */
+int32_t stark_ntt_mixed_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, uint64_t* const* data, const size_t* log_n, int32_t inverse,
+                                  const uint64_t* coset4);
+int32_t stark_lde_mixed_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, const uint64_t* const* evals, const size_t* log_n, size_t log_blowup,
+                                  const uint64_t* coset4, uint64_t* const* out);
 /* Building blocks of the multi-GPU six-step NTT (one process per GPU; the exchange between the two
  * is an all-to-all done by the caller, see stark_mlwe_amd/dist.py):
  *   phase A: `ncols` column NTTs of size 2^log_rows on a row-major [2^log_rows][ncols] slab, then the

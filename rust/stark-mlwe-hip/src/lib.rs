@@ -480,6 +480,18 @@ pub mod fft {
     pub unsafe fn ntt_batch_dev(ctx: &Ctx, datas: &[*mut u64], log_n: usize, inverse: bool) {
         ctx.chk(stark_ntt_batch_dev(ctx.raw, STARK_FIELD_BLS12_381_FR, datas.len(), datas.as_ptr(), log_n, inverse as i32, ptr::null()));
     }
+    /// `lde_batch_dev` with a length per column: column i has 2^log_n[i] elements and `outs[i]` 2^(log_n[i] + log_blowup); one blow-up and one
+    /// coset for the call, columns of any lengths in the same launches.  Safety: as `lde_batch_dev`.
+    pub unsafe fn lde_mixed_batch_dev(ctx: &Ctx, evals: &[*const u64], log_n: &[usize], log_blowup: usize, coset: Option<F>, outs: &[*mut u64]) {
+        assert!(evals.len() == outs.len() && evals.len() == log_n.len());
+        let c = coset.as_ref().map(limb1).unwrap_or(ptr::null());
+        ctx.chk(stark_lde_mixed_batch_dev(ctx.raw, STARK_FIELD_PALLAS_FR, evals.len(), evals.as_ptr(), log_n.as_ptr(), log_blowup, c, outs.as_ptr()));
+    }
+    /// `ntt_batch_dev` with a length per vector (BLS12-381 Fr, 2^log_n[i] elements each).  Safety: as `ntt_batch_dev`.
+    pub unsafe fn ntt_mixed_batch_dev(ctx: &Ctx, datas: &[*mut u64], log_n: &[usize], inverse: bool) {
+        assert_eq!(datas.len(), log_n.len());
+        ctx.chk(stark_ntt_mixed_batch_dev(ctx.raw, STARK_FIELD_BLS12_381_FR, datas.len(), datas.as_ptr(), log_n.as_ptr(), inverse as i32, ptr::null()));
+    }
 }
 
 pub mod transcript {

@@ -157,6 +157,8 @@ SIGNATURES = {
     "stark_lde_dev": (i32, [vp, i32, vp, sz, sz, vp, vp]),
     "stark_ntt_batch_dev": (i32, [vp, i32, sz, vp, sz, i32, vp]),
     "stark_lde_batch_dev": (i32, [vp, i32, sz, vp, sz, sz, vp, vp]),
+    "stark_ntt_mixed_batch_dev": (i32, [vp, i32, sz, vp, vp, i32, vp]),
+    "stark_lde_mixed_batch_dev": (i32, [vp, i32, sz, vp, vp, sz, vp, vp]),
     "stark_ntt_columns_dev": (i32, [vp, i32, vp, sz, sz, sz, sz, i32]),
     "stark_ntt_rows_dev": (i32, [vp, i32, vp, sz, sz, i32, vp]),
     "stark_ntt_rows_coset_dev": (i32, [vp, i32, vp, vp, sz, sz, sz, sz, vp]),

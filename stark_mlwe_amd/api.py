@@ -682,6 +682,24 @@ class Context:
         otab = (C.c_void_p * max(B, 1))(*[int(x) for x in outs])
         self._chk(self.lib.stark_lde_batch_dev(self.h, field, B, tab, log_n, log_blowup, _ptr(None if coset is None else _arr(coset)), otab))
 
+    def ntt_mixed_batch_dev(self, field, datas, log_ns, inverse=False, coset=None):
+        """stark_ntt_dev of each of the DEVICE vectors `datas` (ints; vector i has 2^log_ns[i] elements, transformed in place) with one coset: vectors
+        of any lengths share the launches of a three-step schedule; stream-ordered, no synchronisation (stark_ntt_mixed_batch_dev)."""
+        B = len(datas)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in datas])
+        lg = (C.c_size_t * max(B, 1))(*[int(x) for x in log_ns])
+        self._chk(self.lib.stark_ntt_mixed_batch_dev(self.h, field, B, tab, lg, 1 if inverse else 0, _ptr(None if coset is None else _arr(coset))))
+
+    def lde_mixed_batch_dev(self, field, evals, log_ns, log_blowup, outs, coset=None):
+        """stark_lde_dev of each of the DEVICE columns `evals` (ints; column i has 2^log_ns[i] elements) into the DEVICE vectors `outs`
+        (2^(log_ns[i] + log_blowup) elements) with one blow-up and one coset, columns of any lengths in the same launches; stream-ordered, no
+        synchronisation (stark_lde_mixed_batch_dev)."""
+        B = len(evals)
+        tab = (C.c_void_p * max(B, 1))(*[int(x) for x in evals])
+        otab = (C.c_void_p * max(B, 1))(*[int(x) for x in outs])
+        lg = (C.c_size_t * max(B, 1))(*[int(x) for x in log_ns])
+        self._chk(self.lib.stark_lde_mixed_batch_dev(self.h, field, B, tab, lg, log_blowup, _ptr(None if coset is None else _arr(coset)), otab))
+
     def deep_fri_verify(self, params: DeepFriParams, proof: bytes) -> bool:
         """deep_fri_verify (fri.rs:643-762) on canonical proof bytes."""
         sch = np.ascontiguousarray(params.schedule, dtype=np.uint64)

@@ -5,7 +5,7 @@
 #include <cstring>
 #include <memory>
 #include "pow_table.hpp"
-#include "ntt_batch_plan.hpp"
+#include "ntt_mixed_plan.hpp"
 #include "fri_dev.hpp"
 #include "shard_coll.hpp"
 
@@ -67,9 +67,7 @@ static int32_t get_plan(stark_ctx* ctx, int log_n, bool inverse, NttPlan** out) 
     auto it = ctx->plans.find(key);
     if (it != ctx->plans.end()) { *out = it->second; return STARK_OK; }
     std::unique_ptr<NttPlan> p(new NttPlan()); p->field = F::ID; p->log_n = log_n; p->inverse = inverse;
-    if (log_n <= 10) { p->P = 1; p->log_b[0] = log_n; }
-    else if (log_n <= 20) { p->P = 2; p->log_b[0] = (log_n + 1) / 2; p->log_b[1] = log_n - p->log_b[0]; }
-    else { p->P = 3; p->log_b[0] = (log_n + 2) / 3; p->log_b[1] = (log_n - p->log_b[0] + 1) / 2; p->log_b[2] = log_n - p->log_b[0] - p->log_b[1]; }
+    p->P = ntt_split(log_n, p->log_b);
     fr_t w = fr_root_of_unity<F>((unsigned)log_n); if (inverse) w = fr_inv<F>(w);
     STARK_TRY(p->root.fill<F>(ctx, w, x32<F>(fr_one<F>()), tab_lo(log_n), tab_hi(log_n)));
     for (int i = 0; i < p->P; ++i) {
@@ -92,18 +90,13 @@ static int32_t get_plan(stark_ctx* ctx, int log_n, bool inverse, NttPlan** out) 
     *out = ctx->plans[key] = p.release(); return STARK_OK;
 }
 
-static inline size_t ntt_lds_bytes(int log_b, int log_c) { return ntt_tile_words((size_t)1 << (log_b + log_c), log_b > 0 ? (size_t)1 << (log_b - 1) : 1) * 4; }
 // one workgroup per CU (tile > 80 KiB of LDS) => 512 threads so that every SIMD still holds 2 waves
 static inline unsigned ntt_threads(size_t lds) { return lds > 80 * 1024 ? 512u : 256u; }
 // tile elements E = B*C: 2^11 by default (64 KiB + twiddles => 2 workgroups per CU); option "ntt_log_tile" overrides for tuning
 static inline int ntt_minw(const stark_ctx* ctx) { return ctx->opt.ntt_min_waves; }
 // total_log: log2 of all elements the launch covers; small launches take smaller tiles so that the grid still fills the chip
-static inline int pick_log_c(const stark_ctx* ctx, int log_b, int cap, int total_log = 30) {
-    int le = ctx->opt.ntt_log_tile; if (!ctx->opt.ntt_log_tile_forced && total_log - le < 9) le = std::max(8, std::min(le, total_log - 8));
-    int lc = std::max(2, le - log_b); lc = std::max(0, std::min(lc, cap));
-    while (lc > 0 && ntt_lds_bytes(log_b, lc) > kMaxLds) --lc;      // 2^10-point sub-NTTs: two columns per tile (36 B per element in LDS)
-    return lc;
-}
+static inline NttTileOpts tile_opts(const stark_ctx* ctx) { NttTileOpts o; o.log_tile = ctx->opt.ntt_log_tile; o.forced = ctx->opt.ntt_log_tile_forced; o.max_lds = kMaxLds; return o; }
+static inline int pick_log_c(const stark_ctx* ctx, int log_b, int cap, int total_log = 30) { return ntt_pick_log_c(tile_opts(ctx), log_b, cap, total_log); }
 
 // Bt: the vectors' addresses of a batched pass (the NttBatchAddr instantiations of the pass kernels); nullptr: the plain kernels
 template <class F, int MINW, bool STRIDED>
@@ -164,6 +157,37 @@ static int32_t build_coset(stark_ctx* ctx, NttPlan* p, const fr_t& g, NttCoset& 
     }
     return STARK_OK;
 }
+// the plan's tables for the coset g: a plan holds ONE coset and rebuilds its tables when another one is asked for
+template <class F> static int32_t use_coset(stark_ctx* ctx, NttPlan* p, const fr_t& g) {
+    if (!p->coset.have || !fr_eq(p->coset.g, g)) { NttCoset C; STARK_TRY(build_coset<F>(ctx, p, g, C)); p->coset = std::move(C); }
+    return STARK_OK;
+}
+// Pass i of plan p at tile width 2^log_c as kernel arguments (all but ntiles, which the launch sets).  coset: the transform runs on the plan's current
+// coset (use_coset) — the pre-scale on load in the first pass of a forward plan, the post-scale in the last pass of an inverse one.
+template <class F>
+static NttPassArgs pass_args(const NttPlan* p, int i, int log_c, bool coset, const fr_t* scale_override_dev, int log_nonzero) {
+    const int log_n = p->log_n; const bool inverse = p->inverse; const NttCoset& C = p->coset;
+    NttPassArgs A; memset(&A, 0, sizeof(A)); ntt29_offset<F>(A.dlimb);
+    A.log_n = log_n; A.root = p->root.view(); A.log_vec = log_n;
+    A.log_b = p->log_b[i]; A.log_c = log_c; A.stage_tw = p->stage_tw[i].fr();
+    const bool pre = coset && !inverse && i == 0;
+    if (pre) A.pre = C.tab.view();
+    if (i + 1 < p->P) {                    // strided pass
+        int rem = log_n; for (int q = 0; q < i; ++q) rem -= p->log_b[q];       // log2 of the sub-problem this pass splits
+        A.log_m = rem; A.stride = 1ull << (rem - A.log_b); A.tw_direct = p->tw_direct[i].fr();
+        if (pre) {
+            A.pre_direct = C.direct.fr();
+            if (C.small && C.tw_direct) { A.pre_small = C.small.fr(); A.tw_direct = C.tw_direct.fr(); }       // merged form
+        }
+        // zero-padded input (LDE): element j is non-zero only for j < 2^log_nonzero; in the first strided pass that is the points p < 2^log_nonzero / stride
+        A.nz_points = (i == 0 && log_nonzero >= 0 && log_nonzero < log_n && (1ull << log_nonzero) >= A.stride) ? (uint32_t)((1ull << log_nonzero) / A.stride) : 0u;
+    } else {
+        A.log_b1 = p->P >= 2 ? p->log_b[0] : 0; A.log_b2 = p->P == 3 ? p->log_b[1] : 0;
+        if (coset && inverse) A.post = C.tab.view();
+        A.scale = A.post.lo ? nullptr : (scale_override_dev ? scale_override_dev : (inverse ? p->scale.fr() : nullptr));
+    }
+    return A;
+}
 // Where the vectors of a transform start and end.  Plain (ntt_run): contiguous at `src` == `dst`, 2^log_n apart, transformed in place through the
 // context's scratch by the plain kernels.  Batched (`batch` set; the NttBatchAddr instantiations): vector v is read at src_tab[v] or src + v * src_pitch
 // and leaves at dst_tab[v] or dst + v * dst_pitch (tables of DEVICE pointers in device memory, pitches in elements); `work` holds the [B][2^log_n]
@@ -179,41 +203,21 @@ static inline int floor_log2(uint64_t x) { int k = 0; while (x >> (k + 1)) ++k; 
 template <class F>
 static int32_t ntt_passes(stark_ctx* ctx, const NttEnds& E, int log_n, uint64_t batch, bool inverse, const fr_t* coset, const fr_t* scale_override_dev, int log_nonzero) {
     NttPlan* p = nullptr; STARK_TRY(get_plan<F>(ctx, log_n, inverse, &p));
-    PowTable none{nullptr, nullptr, 0};
-    PowTable pre = none, post = none;
-    if (coset) {
-        if (!p->coset.have || !fr_eq(p->coset.g, *coset)) { NttCoset C; STARK_TRY(build_coset<F>(ctx, p, *coset, C)); p->coset = std::move(C); }
-        if (!inverse) pre = p->coset.tab.view(); else post = p->coset.tab.view();
-    }
-    const NttCoset& C = p->coset;
-    const fr_t* pre_direct = (coset && !inverse) ? C.direct.fr() : nullptr;
-    const bool merged = coset && !inverse && C.small && C.tw_direct;
+    if (coset) STARK_TRY(use_coset<F>(ctx, p, *coset));
     const uint64_t total = batch << log_n, n = 1ull << log_n;
     // tile width: a plain call sizes its tiles by one vector (what it has always done), a batched pass by all the elements its launches cover
     const int total_log = E.batch ? floor_log2(total) : log_n;
     fr_t* scratch = E.work;
     if (p->P > 1 && !E.batch) { void* s = nullptr; STARK_TRY(ctx_scratch(ctx, total * sizeof(fr_t), &s)); scratch = (fr_t*)s; }
     const NttBatchAddr first{E.src_tab, nullptr, E.src_pitch, n}, middle{nullptr, nullptr, n, n}, last{p->P == 1 ? E.src_tab : nullptr, E.dst_tab, p->P == 1 ? E.src_pitch : n, E.dst_pitch};
-    NttPassArgs A; memset(&A, 0, sizeof(A)); ntt29_offset<F>(A.dlimb);
-    A.log_n = log_n; A.root = p->root.view(); A.pre = none; A.post = none; A.scale = nullptr; A.rest0 = 0; A.log_vec = log_n;
     const fr_t* src = E.src;
     int rem = log_n;                       // log2 of the current sub-problem size
     for (int i = 0; i + 1 < p->P; ++i) {   // strided passes
-        A.log_b = p->log_b[i]; A.log_m = rem; A.stride = 1ull << (rem - A.log_b);
-        A.log_c = pick_log_c(ctx, A.log_b, rem - A.log_b, total_log);
-        A.stage_tw = p->stage_tw[i].fr(); A.pre = (i == 0) ? pre : none; A.pre_direct = (i == 0) ? pre_direct : nullptr; A.tw_direct = p->tw_direct[i].fr();
-        A.pre_small = nullptr;
-        if (i == 0 && merged) { A.pre_small = C.small.fr(); A.tw_direct = C.tw_direct.fr(); }
-        // zero-padded input (LDE): element j is non-zero only for j < 2^log_nonzero; in the first strided pass that is the points p < 2^log_nonzero / stride
-        A.nz_points = (i == 0 && log_nonzero >= 0 && log_nonzero < log_n && (1ull << log_nonzero) >= A.stride) ? (uint32_t)((1ull << log_nonzero) / A.stride) : 0u;
+        const NttPassArgs A = pass_args<F>(p, i, pick_log_c(ctx, p->log_b[i], rem - p->log_b[i], total_log), coset != nullptr, nullptr, log_nonzero);
         STARK_TRY(launch_strided<F>(ctx, A, total, src, scratch, E.batch ? (i == 0 ? &first : &middle) : nullptr));
         src = scratch; rem -= A.log_b;
     }
-    A.pre = (p->P == 1) ? pre : none; A.pre_direct = nullptr; A.pre_small = nullptr; A.tw_direct = nullptr; A.nz_points = 0;
-    A.log_b = p->log_b[p->P - 1]; A.stage_tw = p->stage_tw[p->P - 1].fr();
-    A.log_b1 = p->P >= 2 ? p->log_b[0] : 0; A.log_b2 = p->P == 3 ? p->log_b[1] : 0;
-    A.log_c = p->P == 1 ? 0 : pick_log_c(ctx, A.log_b, A.log_b1, total_log);
-    A.post = post; A.scale = post.lo ? nullptr : (scale_override_dev ? scale_override_dev : (inverse ? p->scale.fr() : nullptr));
+    const NttPassArgs A = pass_args<F>(p, p->P - 1, p->P == 1 ? 0 : pick_log_c(ctx, p->log_b[p->P - 1], p->log_b[0], total_log), coset != nullptr, scale_override_dev, -1);
     STARK_TRY(launch_last<F>(ctx, A, total, src, E.dst, E.batch ? &last : nullptr));
     return STARK_OK;
 }
@@ -319,6 +323,85 @@ static int32_t lde_batch_run(stark_ctx* ctx, size_t batch, const uint64_t* const
     return STARK_OK;
 }
 
+// ---- stark_ntt_mixed_batch_dev / stark_lde_mixed_batch_dev: columns of any lengths in one device pass (the plan: ntt_mixed_plan.hpp) -------------------
+template <class F, int MINW, bool STRIDED>
+static void launch_ragged(bool pre, unsigned th, size_t lds, hipStream_t st, uint32_t ntiles, const NttRaggedAddr& R) {
+    const dim3 grid(ntiles), block(th); NttPassArgs none; memset(&none, 0, sizeof(none));        // the ragged kernels take every argument from R.shapes
+    const fr_t* const s0 = nullptr; fr_t* const d0 = nullptr;
+    if (STRIDED) { if (pre) hipLaunchKernelGGL((k_ntt_strided<F, MINW, true, NttRaggedAddr>), grid, block, lds, st, none, s0, d0, R); else hipLaunchKernelGGL((k_ntt_strided<F, MINW, false, NttRaggedAddr>), grid, block, lds, st, none, s0, d0, R); }
+    else { if (pre) hipLaunchKernelGGL((k_ntt_last<F, MINW, true, NttRaggedAddr>), grid, block, lds, st, none, s0, d0, R); else hipLaunchKernelGGL((k_ntt_last<F, MINW, false, NttRaggedAddr>), grid, block, lds, st, none, s0, d0, R); }
+}
+// The launches of one pass.  in / out: the caller's tables for the columns of this pass (the same table for in-place transforms); g_inv / g_fwd: the
+// coset of the inverse / forward transforms (nullptr: none).  All device tables of the pass — per launch the shape records, the column records and the
+// first-tile list — go up as ONE staged upload into one pooled block.
+template <class F>
+static int32_t mixed_pass_run(stark_ctx* ctx, const NttMixedPlan& plan, const uint64_t* const* in, uint64_t* const* out, const fr_t* g_inv, const fr_t* g_fwd) {
+    void* w = nullptr; if (plan.scratch_elems) STARK_TRY(ctx_scratch(ctx, plan.scratch_elems * sizeof(fr_t), &w));
+    fr_t* const scratch = (fr_t*)w;
+    auto at = [&](const NttMixedRef& r, uint32_t col) -> fr_t* { return r.mem == NTT_MEM_IN ? const_cast<fr_t*>(as_fr(in[col])) : r.mem == NTT_MEM_OUT ? as_fr(out[col]) : scratch + r.off; };
+    std::vector<uint64_t> blob; std::vector<size_t> off_shapes, off_cols, off_first;                 // offsets in 8-byte words
+    auto put = [&](const void* src, size_t bytes) { const size_t o = blob.size(); blob.resize(o + (bytes + 7) / 8); memcpy(blob.data() + o, src, bytes); return o; };
+    for (const NttMixedLaunch& L : plan.launches) {
+        std::vector<uint32_t> first; for (const NttMixedCol& c : L.cols) first.push_back(c.first_tile);
+        if (L.kind == NTT_MIXED_PAD) {
+            std::vector<NttPadCol> cols; for (const NttMixedCol& c : L.cols) cols.push_back(NttPadCol{at(c.src, c.col), at(c.dst, c.col), c.first, c.head, c.len});
+            off_shapes.push_back(0); off_cols.push_back(put(cols.data(), cols.size() * sizeof(NttPadCol)));
+        } else {
+            const bool inverse = L.kind == NTT_MIXED_INVERSE; const fr_t* g = inverse ? g_inv : g_fwd;
+            std::vector<NttPassArgs> shapes;
+            for (const NttMixedShape& s : L.shapes) {
+                NttPlan* p = nullptr; STARK_TRY(get_plan<F>(ctx, s.log_n, inverse, &p));
+                if (g) STARK_TRY(use_coset<F>(ctx, p, *g));
+                NttPassArgs A = pass_args<F>(p, s.pass, s.log_c, g != nullptr, nullptr, s.log_nonzero); A.ntiles = s.tiles;
+                shapes.push_back(A);
+            }
+            std::vector<NttRaggedCol> cols; for (const NttMixedCol& c : L.cols) cols.push_back(NttRaggedCol{at(c.src, c.col), at(c.dst, c.col), c.shape, c.first_tile});
+            off_shapes.push_back(put(shapes.data(), shapes.size() * sizeof(NttPassArgs))); off_cols.push_back(put(cols.data(), cols.size() * sizeof(NttRaggedCol)));
+        }
+        off_first.push_back(put(first.data(), first.size() * sizeof(uint32_t)));
+    }
+    if (blob.empty()) return STARK_OK;
+    DevBuf dtab; STARK_HIP(ctx, dtab.alloc(ctx, blob.size() * 8)); STARK_TRY(ctx_upload_staged(ctx, dtab.p, blob.data(), blob.size() * 8));
+    const uint64_t* const base = (const uint64_t*)dtab.p;
+    for (size_t l = 0; l < plan.launches.size(); ++l) {
+        const NttMixedLaunch& L = plan.launches[l]; const uint32_t ncols = (uint32_t)L.cols.size();
+        const uint32_t* const first = (const uint32_t*)(base + off_first[l]);
+        if (L.kind == NTT_MIXED_PAD) {
+            hipLaunchKernelGGL(k_pad_fill_ragged<F>, dim3(L.ntiles), dim3(NTT_PAD_BLOCK), 0, ctx->stream, (const NttPadCol*)(base + off_cols[l]), first, ncols);
+        } else {
+            if (L.lds > kMaxLds) return ctx->fail(STARK_ERR_UNSUPPORTED, "NTT tile exceeds LDS");
+            const NttRaggedAddr R{(const NttPassArgs*)(base + off_shapes[l]), (const NttRaggedCol*)(base + off_cols[l]), first, ncols};
+            const bool w4 = ntt_minw(ctx) > 2 && L.lds <= 40 * 1024; const unsigned th = w4 ? 256u : ntt_threads(L.lds);
+            if (L.strided) { if (w4) launch_ragged<F, 4, true>(L.pre, th, L.lds, ctx->stream, L.ntiles, R); else launch_ragged<F, 2, true>(L.pre, th, L.lds, ctx->stream, L.ntiles, R); }
+            else { if (w4) launch_ragged<F, 4, false>(L.pre, th, L.lds, ctx->stream, L.ntiles, R); else launch_ragged<F, 2, false>(L.pre, th, L.lds, ctx->stream, L.ntiles, R); }
+        }
+        STARK_HIP(ctx, hipGetLastError());
+    }
+    return STARK_OK;
+}
+template <class F>
+static int32_t ntt_mixed_run(stark_ctx* ctx, size_t batch, uint64_t* const* data, const size_t* log_n, bool inverse, const fr_t* coset) {
+    size_t b0 = 0;
+    for (size_t Bp : ntt_mixed_passes(batch, log_n, ctx->opt.ntt_batch_max_elems)) {
+        if (Bp == 1) STARK_TRY(ntt_run<F>(ctx, as_fr(data[b0]), (int)log_n[b0], 1, inverse, coset, nullptr));
+        else STARK_TRY(mixed_pass_run<F>(ctx, ntt_mixed_ntt_plan(log_n + b0, Bp, inverse, coset != nullptr, tile_opts(ctx)), data + b0, data + b0, inverse ? coset : nullptr, inverse ? nullptr : coset));
+        b0 += Bp;
+    }
+    return STARK_OK;
+}
+template <class F>
+static int32_t lde_mixed_run(stark_ctx* ctx, size_t batch, const uint64_t* const* evals, uint64_t* const* out, const size_t* log_n, int log_blowup, const fr_t* coset) {
+    const fr_t one = fr_one<F>(); const bool unit = !coset || fr_eq(*coset, one);
+    std::vector<size_t> log_out(log_n, log_n + batch); for (size_t& l : log_out) l += (size_t)log_blowup;
+    size_t b0 = 0;
+    for (size_t Bp : ntt_mixed_passes(batch, log_out.data(), ctx->opt.ntt_batch_max_elems)) {
+        if (Bp == 1) STARK_TRY(lde_run<F>(ctx, as_fr(evals[b0]), (int)log_n[b0], log_blowup, coset, as_fr(out[b0])));
+        else STARK_TRY(mixed_pass_run<F>(ctx, ntt_mixed_lde_plan(log_n + b0, Bp, log_blowup, !unit, tile_opts(ctx)), evals + b0, out + b0, nullptr, unit ? nullptr : coset));
+        b0 += Bp;
+    }
+    return STARK_OK;
+}
+
 void stark::ntt_plans_free(stark_ctx* ctx) { for (auto& kv : ctx->plans) delete kv.second; ctx->plans.clear(); }
 
 // Per-DEVICE kernel attributes (the default tile is 64 KiB + twiddles, above the 64 KiB a kernel may use without opting in):
@@ -332,6 +415,10 @@ template <class F> static void set_attrs_for() {
     (void)hipFuncSetAttribute((const void*)k_ntt_strided<F, 2, true, NttBatchAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_ntt_last<F, 2, false, NttBatchAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
     (void)hipFuncSetAttribute((const void*)k_ntt_last<F, 2, true, NttBatchAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_ntt_strided<F, 2, false, NttRaggedAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_ntt_strided<F, 2, true, NttRaggedAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_ntt_last<F, 2, false, NttRaggedAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
+    (void)hipFuncSetAttribute((const void*)k_ntt_last<F, 2, true, NttRaggedAddr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLds);
 }
 void stark::ntt_set_attrs() { set_attrs_for<PallasFr>(); set_attrs_for<Bls12381Fr>(); }
 
@@ -509,6 +596,32 @@ int32_t stark_lde_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, co
     if (ntt_batch_ranges_overlap((const void* const*)out, batch, sizeof(fr_t) << (log_n + log_blowup))) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_batch: outputs overlap");
     fr_t cs; if (coset4) cs = load_fr(coset4);
     return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return lde_batch_run<F>(ctx, batch, evals, out, (int)log_n, (int)log_blowup, coset4 ? &cs : nullptr); });
+}
+int32_t stark_ntt_mixed_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, uint64_t* const* data, const size_t* log_n, int32_t inverse, const uint64_t* coset4) {
+    if (!ctx || (batch && (!data || !log_n))) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    std::vector<size_t> bytes(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        if (!data[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_mixed_batch: null column");
+        if (log_n[b] > 30) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_mixed_batch: log_n out of range");
+        bytes[b] = sizeof(fr_t) << log_n[b];
+    }
+    if (ntt_batch_ranges_overlap((const void* const*)data, batch, bytes.data())) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_mixed_batch: columns overlap");
+    fr_t cs; if (coset4) cs = load_fr(coset4);
+    return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return ntt_mixed_run<F>(ctx, batch, data, log_n, inverse != 0, coset4 ? &cs : nullptr); });
+}
+int32_t stark_lde_mixed_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, const uint64_t* const* evals, const size_t* log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* const* out) {
+    if (!ctx || (batch && (!evals || !out || !log_n)) || log_blowup > 30) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    std::vector<size_t> bytes(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        if (!evals[b] || !out[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_mixed_batch: null column");
+        if (log_n[b] > 30 || log_n[b] + log_blowup > 30) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_mixed_batch: log_n + log_blowup out of range");
+        bytes[b] = sizeof(fr_t) << (log_n[b] + log_blowup);
+    }
+    if (ntt_batch_ranges_overlap((const void* const*)out, batch, bytes.data())) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_mixed_batch: outputs overlap");
+    fr_t cs; if (coset4) cs = load_fr(coset4);
+    return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return lde_mixed_run<F>(ctx, batch, evals, out, log_n, (int)log_blowup, coset4 ? &cs : nullptr); });
 }
 int32_t stark_lde(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* out) {
     if (!ctx || !evals || !out || log_n + log_blowup > 30) return STARK_ERR_INVALID_ARG;

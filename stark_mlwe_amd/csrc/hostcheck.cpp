@@ -18,7 +18,7 @@
 #include "mfma_digits.hpp"
 #include "poseidon_chain.hpp"
 #include "fri_batch.hpp"
-#include "ntt_batch_plan.hpp"
+#include "ntt_mixed_plan.hpp"    // includes ntt_batch_plan.hpp
 #include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
 #include "mle_dev.hpp"
 #include "merkle_batch.hpp"
@@ -997,6 +997,36 @@ size_t hc_ntt_batch_passes(size_t batch, int log_out, size_t max_elems, size_t* 
 int hc_ntt_batch_ranges_overlap(const uint64_t* starts, size_t batch, size_t bytes) {
     std::vector<const void*> p(batch); for (size_t i = 0; i < batch; ++i) p[i] = (const void*)(uintptr_t)starts[i];
     return ntt_batch_ranges_overlap(p.data(), batch, bytes) ? 1 : 0;
+}
+}  // extern "C"
+
+// ---- stark_ntt_mixed_batch_dev / stark_lde_mixed_batch_dev (ntt_mixed_plan.hpp): tile lookup, pass cutting, overlap check and the launch plan --------
+extern "C" {
+uint32_t hc_ntt_ragged_locate(const uint32_t* first_tile, uint32_t ncols, uint32_t t) { return ntt_ragged_locate(first_tile, ncols, t); }
+size_t hc_ntt_mixed_passes(size_t batch, const size_t* log_out, size_t max_elems, size_t* out, size_t cap) {
+    const std::vector<size_t> p = ntt_mixed_passes(batch, log_out, max_elems);
+    for (size_t i = 0; i < p.size() && i < cap; ++i) out[i] = p[i];
+    return p.size();
+}
+int hc_ntt_mixed_ranges_overlap(const uint64_t* starts, const size_t* bytes, size_t batch) {
+    std::vector<const void*> p(batch); for (size_t i = 0; i < batch; ++i) p[i] = (const void*)(uintptr_t)starts[i];
+    return ntt_batch_ranges_overlap(p.data(), batch, bytes) ? 1 : 0;
+}
+// The plan of one pass as a stream of int64 (returns the words the whole plan takes; only the first `cap` are written):
+//   scratch_elems, launches, then per launch  kind, step, strided, pre, ntiles, lds, nshapes, ncols,
+//   nshapes x (log_n, P, pass, log_b, log_c, log_m, log_nonzero, tiles),  ncols x (col, shape, first_tile, src.mem, src.off, dst.mem, dst.off, first, head, len).
+// lde == 0: in-place transforms (log_blowup unused); lde != 0: extensions (inverse unused; coset: the shift is given and not one).
+size_t hc_ntt_mixed_plan(size_t ncols, const size_t* log_n, int lde, int inverse, int coset, size_t log_blowup, int log_tile, int tile_forced, int64_t* out, size_t cap) {
+    NttTileOpts o; o.log_tile = log_tile; o.forced = tile_forced != 0;
+    const NttMixedPlan plan = lde ? ntt_mixed_lde_plan(log_n, ncols, (int)log_blowup, coset != 0, o) : ntt_mixed_ntt_plan(log_n, ncols, inverse != 0, coset != 0, o);
+    std::vector<int64_t> w{(int64_t)plan.scratch_elems, (int64_t)plan.launches.size()};
+    for (const NttMixedLaunch& L : plan.launches) {
+        w.insert(w.end(), {L.kind, L.step, L.strided, L.pre, (int64_t)L.ntiles, (int64_t)L.lds, (int64_t)L.shapes.size(), (int64_t)L.cols.size()});
+        for (const NttMixedShape& s : L.shapes) w.insert(w.end(), {s.log_n, s.P, s.pass, s.log_b, s.log_c, s.log_m, s.log_nonzero, (int64_t)s.tiles});
+        for (const NttMixedCol& c : L.cols) w.insert(w.end(), {c.col, c.shape, c.first_tile, c.src.mem, (int64_t)c.src.off, c.dst.mem, (int64_t)c.dst.off, (int64_t)c.first, (int64_t)c.head, (int64_t)c.len});
+    }
+    for (size_t i = 0; i < w.size() && i < cap; ++i) out[i] = w[i];
+    return w.size();
 }
 }  // extern "C"
 

@@ -26,6 +26,7 @@
 #include "fr.hpp"
 #include "fr29.hpp"
 #include "dev_common.hpp"
+#include "ntt_mixed_plan.hpp"     // ntt_tile_words, ntt_ragged_locate
 
 namespace stark {
 
@@ -82,8 +83,7 @@ __device__ __forceinline__ void t29_st(const Tile29& T, int slot, const fr29_t& 
     T.lo[slot] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]); T.mid[slot] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]); T.top[slot] = x.l[8];
 }
 __device__ __forceinline__ uint32_t bitrev(uint32_t x, int bits) { return bits == 0 ? 0u : (__brev(x) >> (32 - bits)); }
-// LDS words of a tile with E elements and NT stage twiddles (both SoA blocks 16-byte aligned)
-__host__ __device__ constexpr size_t ntt_tile_words(size_t E, size_t NT) { return ((9 * E + 3) & ~(size_t)3) + ((9 * NT + 3) & ~(size_t)3); }
+// (LDS words of a tile: ntt_tile_words, ntt_mixed_plan.hpp)
 struct TileLds { Tile29 data, tw; };
 __device__ __forceinline__ TileLds tile_lds(uint4* lds, int E, int NT) {
     uint32_t* w = reinterpret_cast<uint32_t*>(lds);
@@ -197,17 +197,45 @@ __device__ __forceinline__ TileEnds last_ends(const NttPassArgs& A, uint64_t vec
 __device__ __forceinline__ TileEnds last_ends(const NttPassArgs&, uint64_t vec, const fr_t* src, fr_t* dst, const NttBatchAddr& Bt) {
     return TileEnds{Bt.src_tab ? Bt.src_tab[vec] : src + vec * Bt.src_pitch, Bt.dst_tab ? Bt.dst_tab[vec] : dst + vec * Bt.dst_pitch};
 }
+// RAGGED passes (the NttRaggedAddr instantiations; stark_ntt_mixed_batch_dev / stark_lde_mixed_batch_dev): the tiles of a launch belong to transforms of
+// different sizes.  A workgroup takes ONE tile (the grid is the launch's tile count): it locates the tile's column (ntt_ragged_locate), takes that
+// column's shape record from the device table `shapes` IN PLACE of the kernel argument (PassOf overwrites the kernel's copy) — tile width, tables,
+// nz_points and all: everything inside a vector is the single transform's — and reads and writes at the column's own addresses.  The launch's LDS
+// size and thread count are those of its largest tile; a shape's `ntiles` is the tile count of ONE column.
+struct NttRaggedCol { const fr_t* src; fr_t* dst; uint32_t shape, first_tile; };
+struct NttRaggedAddr { const NttPassArgs* shapes; const NttRaggedCol* cols; const uint32_t* first_tile; uint32_t ncols; };
+// The pass a workgroup runs and its first tile.  Plain and batched instantiations: the kernel argument and blockIdx.x, nothing stored.
+template <class... BT> struct PassOf {
+    __device__ __forceinline__ PassOf(NttPassArgs&, const BT&...) {}
+    __device__ __forceinline__ uint64_t first_tile() const { return blockIdx.x; }
+    __device__ __forceinline__ TileEnds strided(const NttPassArgs& A, TileJob& J, const fr_t* src, fr_t* dst, const BT&... bt) const { return strided_ends(A, J, src, dst, bt...); }
+    __device__ __forceinline__ TileEnds last(const NttPassArgs& A, uint64_t vec, const fr_t* src, fr_t* dst, const BT&... bt) const { return last_ends(A, vec, src, dst, bt...); }
+};
+// Ragged: the column's shape and the tile's index inside the column.  The tile loop of the kernels then runs once: the stride gridDim.x is the launch's
+// tile count, which is at least the column's.
+template <> struct PassOf<NttRaggedAddr> {
+    TileEnds ends; uint32_t tile;
+    __device__ __forceinline__ PassOf(NttPassArgs& A, const NttRaggedAddr& R) {
+        const uint32_t c = ntt_ragged_locate(R.first_tile, R.ncols, blockIdx.x);
+        const NttRaggedCol col = R.cols[c];
+        A = R.shapes[col.shape]; ends = TileEnds{col.src, col.dst}; tile = blockIdx.x - col.first_tile;
+    }
+    __device__ __forceinline__ uint64_t first_tile() const { return tile; }
+    __device__ __forceinline__ TileEnds strided(const NttPassArgs&, TileJob&, const fr_t*, fr_t*, const NttRaggedAddr&) const { return ends; }     // J.base is the offset inside the vector already
+    __device__ __forceinline__ TileEnds last(const NttPassArgs&, uint64_t, const fr_t*, fr_t*, const NttRaggedAddr&) const { return ends; }        // vec == 0
+};
 template <class F, int MINW, bool PRE, class... BT>
 __global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_strided(NttPassArgs A, const fr_t* src0, fr_t* dst0, BT... bt) {
     extern __shared__ uint4 lds[];
+    const PassOf<BT...> W{A, bt...};          // ragged: A becomes the shape record of this workgroup's tile
     const int B = 1 << A.log_b, C = 1 << A.log_c, E = B << A.log_c, NT = B > 1 ? B >> 1 : 1;
     const TileLds L = tile_lds(lds, E, NT);
     const uint64_t tiles_per_outer = A.stride >> A.log_c;
     auto job = [&](uint64_t t) { const uint64_t outer = t / tiles_per_outer, tile = t % tiles_per_outer; return TileJob{(outer << A.log_m) + (tile << A.log_c), tile}; };
     load_stage_tw<F>(L.tw, A.stage_tw, NT);
-    for (uint64_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {
+    for (uint64_t t = W.first_tile(); t < A.ntiles; t += gridDim.x) {
         TileJob J = job(t);
-        const TileEnds V = strided_ends(A, J, src0, dst0, bt...);
+        const TileEnds V = W.strided(A, J, src0, dst0, bt...);
         const fr_t* const src = V.src; fr_t* const dst = V.dst;
         int head;
         if (PRE && A.nz_points && A.log_b >= 3 && A.nz_points <= (uint32_t)(B >> 3)) {
@@ -278,15 +306,16 @@ __global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_strided(NttP
 template <class F, int MINW, bool PRE, class... BT>
 __global__ void __launch_bounds__(MINW > 2 ? 256 : 512, MINW) k_ntt_last(NttPassArgs A, const fr_t* src0, fr_t* dst0, BT... bt) {
     extern __shared__ uint4 lds[];
+    const PassOf<BT...> W{A, bt...};          // ragged: A becomes the shape record of this workgroup's tile
     const int B = 1 << A.log_b, E = B << A.log_c, NT = B > 1 ? B >> 1 : 1;
     const TileLds L = tile_lds(lds, E, NT);
     // tile -> (vector, k2, k1 block): consecutive tiles walk k1 blocks first
     const uint64_t k1_blocks = (1ull << A.log_b1) >> A.log_c;                  // >= 1 (C divides B1)
     const uint64_t tiles_per_vec = k1_blocks << A.log_b2;
     load_stage_tw<F>(L.tw, A.stage_tw, NT);
-    for (uint64_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {
+    for (uint64_t t = W.first_tile(); t < A.ntiles; t += gridDim.x) {
         const uint64_t vec = t / tiles_per_vec, vt = t % tiles_per_vec, k2 = vt / k1_blocks, k1_0 = (vt % k1_blocks) << A.log_c;
-        const TileEnds V = last_ends(A, vec, src0, dst0, bt...);
+        const TileEnds V = W.last(A, vec, src0, dst0, bt...);
         const fr_t* const src = V.src; fr_t* const dst = V.dst;
         int head;
         if (PRE) {
@@ -390,6 +419,18 @@ __global__ void k_pad_fill_batch(const fr_t* const* src_tab, const fr_t* src, ui
     if (v >= B) return;
     fr_t* d = dst_tab ? dst_tab[v] : dst + v * dst_pitch;
     if (i < head) stg(d + i, ldg((src_tab ? src_tab[v] : src + v * src_pitch) + i)); else stg(d + i, fr_zero<F>());
+}
+// The padding of a RAGGED pass in one launch: column c takes the blocks first_tile[c] .. of NTT_PAD_BLOCK elements each and writes
+// dst_c[i] = i < head_c ? src_c[i] : 0 over first_c <= i < len_c — the zero tails of the coefficient vectors whose padding the forward transform reads,
+// and the one-point columns (head 1), whose interpolation is the point itself.
+struct NttPadCol { const fr_t* src; fr_t* dst; uint64_t first, head, len; };
+template <class F>
+__global__ void k_pad_fill_ragged(const NttPadCol* cols, const uint32_t* first_tile, uint32_t ncols) {
+    const uint32_t c = ntt_ragged_locate(first_tile, ncols, blockIdx.x);
+    const NttPadCol P = cols[c];
+    const uint64_t i = P.first + (uint64_t)(blockIdx.x - first_tile[c]) * NTT_PAD_BLOCK + threadIdx.x;
+    if (i >= P.len) return;
+    if (i < P.head) stg(P.dst + i, ldg(P.src + i)); else stg(P.dst + i, fr_zero<F>());
 }
 
 }  // namespace stark
