@@ -98,26 +98,28 @@ static inline int ntt_minw(const stark_ctx* ctx) { return ctx->opt.ntt_min_waves
 static inline NttTileOpts tile_opts(const stark_ctx* ctx) { NttTileOpts o; o.log_tile = ctx->opt.ntt_log_tile; o.forced = ctx->opt.ntt_log_tile_forced; o.max_lds = kMaxLds; return o; }
 static inline int pick_log_c(const stark_ctx* ctx, int log_b, int cap, int total_log = 30) { return ntt_pick_log_c(tile_opts(ctx), log_b, cap, total_log); }
 
-// Bt: the vectors' addresses of a batched pass (the NttBatchAddr instantiations of the pass kernels); nullptr: the plain kernels
-template <class F, int MINW, bool STRIDED>
-static void launch_pass(bool pre, unsigned th, size_t lds, hipStream_t st, const NttPassArgs& A, const fr_t* src, fr_t* dst, const NttBatchAddr* Bt) {
-    const dim3 grid(A.ntiles), block(th);
-    if (Bt) {
-        if (STRIDED) { if (pre) hipLaunchKernelGGL((k_ntt_strided<F, MINW, true, NttBatchAddr>), grid, block, lds, st, A, src, dst, *Bt); else hipLaunchKernelGGL((k_ntt_strided<F, MINW, false, NttBatchAddr>), grid, block, lds, st, A, src, dst, *Bt); }
-        else { if (pre) hipLaunchKernelGGL((k_ntt_last<F, MINW, true, NttBatchAddr>), grid, block, lds, st, A, src, dst, *Bt); else hipLaunchKernelGGL((k_ntt_last<F, MINW, false, NttBatchAddr>), grid, block, lds, st, A, src, dst, *Bt); }
-        return;
-    }
-    if (STRIDED) { if (pre) hipLaunchKernelGGL((k_ntt_strided<F, MINW, true>), grid, block, lds, st, A, src, dst); else hipLaunchKernelGGL((k_ntt_strided<F, MINW, false>), grid, block, lds, st, A, src, dst); }
-    else { if (pre) hipLaunchKernelGGL((k_ntt_last<F, MINW, true>), grid, block, lds, st, A, src, dst); else hipLaunchKernelGGL((k_ntt_last<F, MINW, false>), grid, block, lds, st, A, src, dst); }
+// One launch of a pass kernel.  addr: nothing (the plain kernels: contiguous vectors at src / dst), or how a batched launch finds its vectors —
+// NttBatchAddr (one shape: A is the pass of every column) or NttRaggedAddr (A, src and dst unused: every argument comes from the shape table).
+template <class F, int MINW, bool STRIDED, class... BT>
+static void launch_pass(bool pre, unsigned th, size_t lds, hipStream_t st, uint32_t ntiles, const NttPassArgs& A, const fr_t* src, fr_t* dst, const BT&... addr) {
+    const dim3 grid(ntiles), block(th);
+    if (STRIDED) { if (pre) hipLaunchKernelGGL((k_ntt_strided<F, MINW, true, BT...>), grid, block, lds, st, A, src, dst, addr...); else hipLaunchKernelGGL((k_ntt_strided<F, MINW, false, BT...>), grid, block, lds, st, A, src, dst, addr...); }
+    else { if (pre) hipLaunchKernelGGL((k_ntt_last<F, MINW, true, BT...>), grid, block, lds, st, A, src, dst, addr...); else hipLaunchKernelGGL((k_ntt_last<F, MINW, false, BT...>), grid, block, lds, st, A, src, dst, addr...); }
 }
+// ... with the wave count and the threads that go with a tile of `lds` bytes
+template <class F, bool STRIDED, class... BT>
+static int32_t launch_sized(stark_ctx* ctx, bool pre, size_t lds, uint32_t ntiles, const NttPassArgs& A, const fr_t* src, fr_t* dst, const BT&... addr) {
+    if (lds > kMaxLds) return ctx->fail(STARK_ERR_UNSUPPORTED, "NTT tile exceeds LDS");
+    if (ntt_minw(ctx) > 2 && lds <= 40 * 1024) launch_pass<F, 4, STRIDED>(pre, 256u, lds, ctx->stream, ntiles, A, src, dst, addr...);
+    else launch_pass<F, 2, STRIDED>(pre, ntt_threads(lds), lds, ctx->stream, ntiles, A, src, dst, addr...);
+    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+}
+// Bt: the vectors' addresses of a same-size batched pass; nullptr: the plain kernels
 template <class F, bool STRIDED>
 static int32_t launch_any(stark_ctx* ctx, NttPassArgs A, uint64_t total_elems, bool pre, const fr_t* src, fr_t* dst, const NttBatchAddr* Bt) {
-    size_t lds = ntt_lds_bytes(A.log_b, A.log_c);
-    if (lds > kMaxLds) return ctx->fail(STARK_ERR_UNSUPPORTED, "NTT tile exceeds LDS");
     A.ntiles = (uint32_t)(total_elems >> (A.log_b + A.log_c));
-    if (ntt_minw(ctx) > 2 && lds <= 40 * 1024) launch_pass<F, 4, STRIDED>(pre, 256u, lds, ctx->stream, A, src, dst, Bt);
-    else launch_pass<F, 2, STRIDED>(pre, ntt_threads(lds), lds, ctx->stream, A, src, dst, Bt);
-    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    const size_t lds = ntt_lds_bytes(A.log_b, A.log_c);
+    return Bt ? launch_sized<F, STRIDED>(ctx, pre, lds, A.ntiles, A, src, dst, *Bt) : launch_sized<F, STRIDED>(ctx, pre, lds, A.ntiles, A, src, dst);
 }
 template <class F> static int32_t launch_strided(stark_ctx* ctx, const NttPassArgs& A, uint64_t total_elems, const fr_t* src, fr_t* dst, const NttBatchAddr* Bt = nullptr) { return launch_any<F, true>(ctx, A, total_elems, A.pre_direct || A.pre.lo, src, dst, Bt); }
 template <class F> static int32_t launch_last(stark_ctx* ctx, const NttPassArgs& A, uint64_t total_elems, const fr_t* src, fr_t* dst, const NttBatchAddr* Bt = nullptr) { return launch_any<F, false>(ctx, A, total_elems, A.pre.lo != nullptr, src, dst, Bt); }
@@ -198,7 +200,6 @@ struct NttEnds {
     fr_t* const* dst_tab = nullptr; fr_t* dst = nullptr; uint64_t dst_pitch = 0;
     fr_t* work = nullptr;
 };
-static inline int floor_log2(uint64_t x) { int k = 0; while (x >> (k + 1)) ++k; return k; }
 // The passes of `batch` transforms of 2^log_n points (1 <= log_n <= 30, batch >= 1) between the ends E.
 template <class F>
 static int32_t ntt_passes(stark_ctx* ctx, const NttEnds& E, int log_n, uint64_t batch, bool inverse, const fr_t* coset, const fr_t* scale_override_dev, int log_nonzero) {
@@ -206,7 +207,7 @@ static int32_t ntt_passes(stark_ctx* ctx, const NttEnds& E, int log_n, uint64_t 
     if (coset) STARK_TRY(use_coset<F>(ctx, p, *coset));
     const uint64_t total = batch << log_n, n = 1ull << log_n;
     // tile width: a plain call sizes its tiles by one vector (what it has always done), a batched pass by all the elements its launches cover
-    const int total_log = E.batch ? floor_log2(total) : log_n;
+    const int total_log = E.batch ? ntt_floor_log2(total) : log_n;
     fr_t* scratch = E.work;
     if (p->P > 1 && !E.batch) { void* s = nullptr; STARK_TRY(ctx_scratch(ctx, total * sizeof(fr_t), &s)); scratch = (fr_t*)s; }
     const NttBatchAddr first{E.src_tab, nullptr, E.src_pitch, n}, middle{nullptr, nullptr, n, n}, last{p->P == 1 ? E.src_tab : nullptr, E.dst_tab, p->P == 1 ? E.src_pitch : n, E.dst_pitch};
@@ -239,14 +240,9 @@ static int32_t lde_run(stark_ctx* ctx, const fr_t* evals, int log_n, int log_blo
     STARK_HIP(ctx, hipMemcpyAsync(out, evals, n * sizeof(fr_t), hipMemcpyDeviceToDevice, ctx->stream));
     STARK_TRY(ntt_run<F>(ctx, out, log_n, 1, true, nullptr, nullptr));                       // evaluations on H -> coefficients
     fr_t one = fr_one<F>(); bool unit = !coset || fr_eq(*coset, one);
-    // The zero padding is never written when the big transform has a strided first pass whose stride divides n: that pass reads
-    // only the n coefficient rows and takes the rest as zero (NttPassArgs::nz_points).  Otherwise (tiny transforms) pad for real.
-    // (first-pass size taken from the plan itself, so that a retuned split can never leave out[n..N) unwritten AND unread-as-zero)
-    const int big = log_n + log_blowup;
-    NttPlan* bp = nullptr; STARK_TRY(get_plan<F>(ctx, big, false, &bp));
-    const bool skip = N > n && bp->P > 1 && (big - bp->log_b[0]) <= log_n;
+    const bool skip = ntt_lde_skips_padding(log_n, log_blowup);                              // the padding is taken as zero, never written
     if (N > n && !skip) { hipLaunchKernelGGL(k_zero_fill<F>, dim3((unsigned)((N - n + 255) / 256)), dim3(256), 0, ctx->stream, out + n, N - n); STARK_HIP(ctx, hipGetLastError()); }
-    return ntt_run<F>(ctx, out, big, 1, false, unit ? nullptr : coset, nullptr, skip ? log_n : -1);   // coefficients -> coset evaluations on the larger domain
+    return ntt_run<F>(ctx, out, log_n + log_blowup, 1, false, unit ? nullptr : coset, nullptr, skip ? log_n : -1);   // coefficients -> coset evaluations on the larger domain
 }
 
 // ---- stark_ntt_batch_dev / stark_lde_batch_dev: many columns of one shape and one coset per device pass ---------------------------------------
@@ -275,7 +271,7 @@ static int32_t ntt_batch_pass(stark_ctx* ctx, uint64_t* const* data, size_t B, i
 template <class F>
 static int32_t ntt_batch_run(stark_ctx* ctx, size_t batch, uint64_t* const* data, int log_n, bool inverse, const fr_t* coset) {
     size_t b0 = 0;
-    for (size_t Bp : ntt_batch_passes(batch, log_n, ctx->opt.ntt_batch_max_elems)) {
+    for (size_t Bp : ntt_mixed_passes(batch, std::vector<size_t>(batch, (size_t)log_n).data(), ctx->opt.ntt_batch_max_elems)) {
         if (Bp == 1) STARK_TRY(ntt_run<F>(ctx, as_fr(data[b0]), log_n, 1, inverse, coset, nullptr));
         else STARK_TRY(ntt_batch_pass<F>(ctx, data + b0, Bp, log_n, inverse, coset));
         b0 += Bp;
@@ -292,8 +288,7 @@ static int32_t lde_batch_pass(stark_ctx* ctx, const uint64_t* const* evals, uint
     const int big = log_n + log_blowup;
     const uint64_t n = 1ull << log_n, N = 1ull << big;
     const fr_t one = fr_one<F>(); const bool unit = !coset || fr_eq(*coset, one);
-    bool skip = false;
-    if (big > 0) { NttPlan* bp = nullptr; STARK_TRY(get_plan<F>(ctx, big, false, &bp)); skip = N > n && bp->P > 1 && (big - bp->log_b[0]) <= log_n; }
+    const bool skip = ntt_lde_skips_padding(log_n, log_blowup);
     void* w = nullptr; STARK_TRY(ctx_scratch(ctx, B * (N + n) * sizeof(fr_t), &w));
     fr_t* const X = (fr_t*)w; fr_t* const Cs = X + B * N;
     std::vector<const void*> tab(2 * B);
@@ -315,7 +310,7 @@ static int32_t lde_batch_pass(stark_ctx* ctx, const uint64_t* const* evals, uint
 template <class F>
 static int32_t lde_batch_run(stark_ctx* ctx, size_t batch, const uint64_t* const* evals, uint64_t* const* out, int log_n, int log_blowup, const fr_t* coset) {
     size_t b0 = 0;
-    for (size_t Bp : ntt_batch_passes(batch, log_n + log_blowup, ctx->opt.ntt_batch_max_elems)) {
+    for (size_t Bp : ntt_mixed_passes(batch, std::vector<size_t>(batch, (size_t)(log_n + log_blowup)).data(), ctx->opt.ntt_batch_max_elems)) {
         if (Bp == 1) STARK_TRY(lde_run<F>(ctx, as_fr(evals[b0]), log_n, log_blowup, coset, as_fr(out[b0])));
         else STARK_TRY(lde_batch_pass<F>(ctx, evals + b0, out + b0, Bp, log_n, log_blowup, coset));
         b0 += Bp;
@@ -324,28 +319,30 @@ static int32_t lde_batch_run(stark_ctx* ctx, size_t batch, const uint64_t* const
 }
 
 // ---- stark_ntt_mixed_batch_dev / stark_lde_mixed_batch_dev: columns of any lengths in one device pass (the plan: ntt_mixed_plan.hpp) -------------------
-template <class F, int MINW, bool STRIDED>
-static void launch_ragged(bool pre, unsigned th, size_t lds, hipStream_t st, uint32_t ntiles, const NttRaggedAddr& R) {
-    const dim3 grid(ntiles), block(th); NttPassArgs none; memset(&none, 0, sizeof(none));        // the ragged kernels take every argument from R.shapes
-    const fr_t* const s0 = nullptr; fr_t* const d0 = nullptr;
-    if (STRIDED) { if (pre) hipLaunchKernelGGL((k_ntt_strided<F, MINW, true, NttRaggedAddr>), grid, block, lds, st, none, s0, d0, R); else hipLaunchKernelGGL((k_ntt_strided<F, MINW, false, NttRaggedAddr>), grid, block, lds, st, none, s0, d0, R); }
-    else { if (pre) hipLaunchKernelGGL((k_ntt_last<F, MINW, true, NttRaggedAddr>), grid, block, lds, st, none, s0, d0, R); else hipLaunchKernelGGL((k_ntt_last<F, MINW, false, NttRaggedAddr>), grid, block, lds, st, none, s0, d0, R); }
-}
 // The launches of one pass.  in / out: the caller's tables for the columns of this pass (the same table for in-place transforms); g_inv / g_fwd: the
-// coset of the inverse / forward transforms (nullptr: none).  All device tables of the pass — per launch the shape records, the column records and the
-// first-tile list — go up as ONE staged upload into one pooled block.
+// coset of the inverse / forward transforms (nullptr: none).  A launch of one shape (ntt_mixed_one_shape: the 2^12 columns' strided pass beside 2^5 ones)
+// takes its pass as the kernel argument and finds its vectors through NttBatchAddr: a table of the caller's pointers in launch order, or base + pitch
+// in the scratch.  Any other launch is ragged: shape records, column records and the first-tile list.  All device tables of the pass go up as ONE
+// staged upload into one pooled block.
 template <class F>
 static int32_t mixed_pass_run(stark_ctx* ctx, const NttMixedPlan& plan, const uint64_t* const* in, uint64_t* const* out, const fr_t* g_inv, const fr_t* g_fwd) {
     void* w = nullptr; if (plan.scratch_elems) STARK_TRY(ctx_scratch(ctx, plan.scratch_elems * sizeof(fr_t), &w));
     fr_t* const scratch = (fr_t*)w;
     auto at = [&](const NttMixedRef& r, uint32_t col) -> fr_t* { return r.mem == NTT_MEM_IN ? const_cast<fr_t*>(as_fr(in[col])) : r.mem == NTT_MEM_OUT ? as_fr(out[col]) : scratch + r.off; };
-    std::vector<uint64_t> blob; std::vector<size_t> off_shapes, off_cols, off_first;                 // offsets in 8-byte words
+    struct Staged { bool one = false; NttOneShape ends; NttPassArgs A; size_t shapes = 0, cols = 0, first = 0, src_tab = 0, dst_tab = 0; };   // offsets in 8-byte words
+    std::vector<uint64_t> blob; std::vector<Staged> staged;
     auto put = [&](const void* src, size_t bytes) { const size_t o = blob.size(); blob.resize(o + (bytes + 7) / 8); memcpy(blob.data() + o, src, bytes); return o; };
+    std::vector<const void*> tab, last_tab; size_t last_off = 0;
+    auto table = [&](const NttMixedLaunch& L, int mem) {                         // an in-place transform reads and writes through one table
+        tab.clear(); for (const NttMixedCol& c : L.cols) tab.push_back(mem == NTT_MEM_IN ? (const void*)in[c.col] : (const void*)out[c.col]);
+        if (tab != last_tab) { last_off = put(tab.data(), tab.size() * sizeof(void*)); last_tab = tab; }
+        return last_off;
+    };
     for (const NttMixedLaunch& L : plan.launches) {
-        std::vector<uint32_t> first; for (const NttMixedCol& c : L.cols) first.push_back(c.first_tile);
+        Staged S;
         if (L.kind == NTT_MIXED_PAD) {
             std::vector<NttPadCol> cols; for (const NttMixedCol& c : L.cols) cols.push_back(NttPadCol{at(c.src, c.col), at(c.dst, c.col), c.first, c.head, c.len});
-            off_shapes.push_back(0); off_cols.push_back(put(cols.data(), cols.size() * sizeof(NttPadCol)));
+            S.cols = put(cols.data(), cols.size() * sizeof(NttPadCol));
         } else {
             const bool inverse = L.kind == NTT_MIXED_INVERSE; const fr_t* g = inverse ? g_inv : g_fwd;
             std::vector<NttPassArgs> shapes;
@@ -355,27 +352,41 @@ static int32_t mixed_pass_run(stark_ctx* ctx, const NttMixedPlan& plan, const ui
                 NttPassArgs A = pass_args<F>(p, s.pass, s.log_c, g != nullptr, nullptr, s.log_nonzero); A.ntiles = s.tiles;
                 shapes.push_back(A);
             }
+            S.one = ntt_mixed_one_shape(L, &S.ends);
+            if (S.one) {
+                S.A = shapes[0]; S.A.ntiles = L.ntiles;
+                if (S.ends.src.mem != NTT_MEM_SCRATCH) S.src_tab = table(L, S.ends.src.mem);
+                if (S.ends.dst.mem != NTT_MEM_SCRATCH) S.dst_tab = table(L, S.ends.dst.mem);
+                staged.push_back(S); continue;
+            }
             std::vector<NttRaggedCol> cols; for (const NttMixedCol& c : L.cols) cols.push_back(NttRaggedCol{at(c.src, c.col), at(c.dst, c.col), c.shape, c.first_tile});
-            off_shapes.push_back(put(shapes.data(), shapes.size() * sizeof(NttPassArgs))); off_cols.push_back(put(cols.data(), cols.size() * sizeof(NttRaggedCol)));
+            S.shapes = put(shapes.data(), shapes.size() * sizeof(NttPassArgs)); S.cols = put(cols.data(), cols.size() * sizeof(NttRaggedCol));
         }
-        off_first.push_back(put(first.data(), first.size() * sizeof(uint32_t)));
+        std::vector<uint32_t> first; for (const NttMixedCol& c : L.cols) first.push_back(c.first_tile);
+        S.first = put(first.data(), first.size() * sizeof(uint32_t));
+        staged.push_back(S);
     }
-    if (blob.empty()) return STARK_OK;
+    if (blob.empty()) return STARK_OK;                                           // no launch (the first launch of a plan reads the caller's columns through a table)
     DevBuf dtab; STARK_HIP(ctx, dtab.alloc(ctx, blob.size() * 8)); STARK_TRY(ctx_upload_staged(ctx, dtab.p, blob.data(), blob.size() * 8));
     const uint64_t* const base = (const uint64_t*)dtab.p;
     for (size_t l = 0; l < plan.launches.size(); ++l) {
-        const NttMixedLaunch& L = plan.launches[l]; const uint32_t ncols = (uint32_t)L.cols.size();
-        const uint32_t* const first = (const uint32_t*)(base + off_first[l]);
+        const NttMixedLaunch& L = plan.launches[l]; const Staged& S = staged[l]; const uint32_t ncols = (uint32_t)L.cols.size();
+        const uint32_t* const first = (const uint32_t*)(base + S.first);
         if (L.kind == NTT_MIXED_PAD) {
-            hipLaunchKernelGGL(k_pad_fill_ragged<F>, dim3(L.ntiles), dim3(NTT_PAD_BLOCK), 0, ctx->stream, (const NttPadCol*)(base + off_cols[l]), first, ncols);
+            hipLaunchKernelGGL(k_pad_fill_ragged<F>, dim3(L.ntiles), dim3(NTT_PAD_BLOCK), 0, ctx->stream, (const NttPadCol*)(base + S.cols), first, ncols);
+            STARK_HIP(ctx, hipGetLastError());
+        } else if (S.one) {
+            const bool stab = S.ends.src.mem != NTT_MEM_SCRATCH, dtb = S.ends.dst.mem != NTT_MEM_SCRATCH;
+            const NttBatchAddr Bt{stab ? (const fr_t* const*)(base + S.src_tab) : nullptr, dtb ? (fr_t* const*)(base + S.dst_tab) : nullptr, S.ends.src.pitch, S.ends.dst.pitch};
+            const fr_t* const src = stab ? nullptr : scratch + S.ends.src.off; fr_t* const dst = dtb ? nullptr : scratch + S.ends.dst.off;
+            if (L.strided) STARK_TRY((launch_sized<F, true>(ctx, L.pre, L.lds, L.ntiles, S.A, src, dst, Bt)));
+            else STARK_TRY((launch_sized<F, false>(ctx, L.pre, L.lds, L.ntiles, S.A, src, dst, Bt)));
         } else {
-            if (L.lds > kMaxLds) return ctx->fail(STARK_ERR_UNSUPPORTED, "NTT tile exceeds LDS");
-            const NttRaggedAddr R{(const NttPassArgs*)(base + off_shapes[l]), (const NttRaggedCol*)(base + off_cols[l]), first, ncols};
-            const bool w4 = ntt_minw(ctx) > 2 && L.lds <= 40 * 1024; const unsigned th = w4 ? 256u : ntt_threads(L.lds);
-            if (L.strided) { if (w4) launch_ragged<F, 4, true>(L.pre, th, L.lds, ctx->stream, L.ntiles, R); else launch_ragged<F, 2, true>(L.pre, th, L.lds, ctx->stream, L.ntiles, R); }
-            else { if (w4) launch_ragged<F, 4, false>(L.pre, th, L.lds, ctx->stream, L.ntiles, R); else launch_ragged<F, 2, false>(L.pre, th, L.lds, ctx->stream, L.ntiles, R); }
+            const NttRaggedAddr R{(const NttPassArgs*)(base + S.shapes), (const NttRaggedCol*)(base + S.cols), first, ncols};
+            NttPassArgs none; memset(&none, 0, sizeof(none));                    // the ragged kernels take every argument from R.shapes
+            if (L.strided) STARK_TRY((launch_sized<F, true>(ctx, L.pre, L.lds, L.ntiles, none, nullptr, nullptr, R)));
+            else STARK_TRY((launch_sized<F, false>(ctx, L.pre, L.lds, L.ntiles, none, nullptr, nullptr, R)));
         }
-        STARK_HIP(ctx, hipGetLastError());
     }
     return STARK_OK;
 }
@@ -581,47 +592,48 @@ int32_t stark_lde_dev(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals,
     fr_t cs; if (coset4) cs = load_fr(coset4);
     return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return lde_run<F>(ctx, as_fr(evals), (int)log_n, (int)log_blowup, coset4 ? &cs : nullptr, as_fr(out)); });
 }
-int32_t stark_ntt_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, uint64_t* const* data, size_t log_n, int32_t inverse, const uint64_t* coset4) {
-    if (!ctx || (batch && !data) || log_n > 30) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    for (size_t b = 0; b < batch; ++b) if (!data[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_batch: null column");
-    if (ntt_batch_ranges_overlap((const void* const*)data, batch, sizeof(fr_t) << log_n)) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_batch: columns overlap");
-    fr_t cs; if (coset4) cs = load_fr(coset4);
-    return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return ntt_batch_run<F>(ctx, batch, data, (int)log_n, inverse != 0, coset4 ? &cs : nullptr); });
-}
-int32_t stark_lde_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, const uint64_t* const* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* const* out) {
-    if (!ctx || (batch && (!evals || !out)) || log_n > 30 || log_blowup > 30 || log_n + log_blowup > 30) return STARK_ERR_INVALID_ARG;
-    STARK_TRY(ctx_enter(ctx));
-    for (size_t b = 0; b < batch; ++b) if (!evals[b] || !out[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_batch: null column");
-    if (ntt_batch_ranges_overlap((const void* const*)out, batch, sizeof(fr_t) << (log_n + log_blowup))) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_batch: outputs overlap");
-    fr_t cs; if (coset4) cs = load_fr(coset4);
-    return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return lde_batch_run<F>(ctx, batch, evals, out, (int)log_n, (int)log_blowup, coset4 ? &cs : nullptr); });
+// What the four batched calls refuse after ctx_enter, under the call's name: a null column, an output longer than 2^30, two outputs that overlap.
+// evals: the inputs of an extension (nullptr: a transform in place, whose outputs are its columns); output b has 2^(log_n[b] + log_blowup) elements.
+static int32_t batch_check(stark_ctx* ctx, const std::string& call, size_t batch, const uint64_t* const* evals, uint64_t* const* out, const size_t* log_n, size_t log_blowup) {
+    std::vector<size_t> bytes(batch);
+    for (size_t b = 0; b < batch; ++b) {
+        if (!out[b] || (evals && !evals[b])) return ctx->fail(STARK_ERR_INVALID_ARG, call + ": null column");
+        if (log_n[b] > 30 || log_n[b] + log_blowup > 30) return ctx->fail(STARK_ERR_INVALID_ARG, call + (evals ? ": log_n + log_blowup out of range" : ": log_n out of range"));
+        bytes[b] = sizeof(fr_t) << (log_n[b] + log_blowup);
+    }
+    if (ntt_batch_ranges_overlap((const void* const*)out, batch, bytes.data())) return ctx->fail(STARK_ERR_INVALID_ARG, call + (evals ? ": outputs overlap" : ": columns overlap"));
+    return STARK_OK;
 }
 int32_t stark_ntt_mixed_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, uint64_t* const* data, const size_t* log_n, int32_t inverse, const uint64_t* coset4) {
     if (!ctx || (batch && (!data || !log_n))) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    std::vector<size_t> bytes(batch);
-    for (size_t b = 0; b < batch; ++b) {
-        if (!data[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_mixed_batch: null column");
-        if (log_n[b] > 30) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_mixed_batch: log_n out of range");
-        bytes[b] = sizeof(fr_t) << log_n[b];
-    }
-    if (ntt_batch_ranges_overlap((const void* const*)data, batch, bytes.data())) return ctx->fail(STARK_ERR_INVALID_ARG, "ntt_mixed_batch: columns overlap");
+    STARK_TRY(batch_check(ctx, "ntt_mixed_batch", batch, nullptr, data, log_n, 0));
     fr_t cs; if (coset4) cs = load_fr(coset4);
     return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return ntt_mixed_run<F>(ctx, batch, data, log_n, inverse != 0, coset4 ? &cs : nullptr); });
 }
 int32_t stark_lde_mixed_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, const uint64_t* const* evals, const size_t* log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* const* out) {
     if (!ctx || (batch && (!evals || !out || !log_n)) || log_blowup > 30) return STARK_ERR_INVALID_ARG;
     STARK_TRY(ctx_enter(ctx));
-    std::vector<size_t> bytes(batch);
-    for (size_t b = 0; b < batch; ++b) {
-        if (!evals[b] || !out[b]) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_mixed_batch: null column");
-        if (log_n[b] > 30 || log_n[b] + log_blowup > 30) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_mixed_batch: log_n + log_blowup out of range");
-        bytes[b] = sizeof(fr_t) << (log_n[b] + log_blowup);
-    }
-    if (ntt_batch_ranges_overlap((const void* const*)out, batch, bytes.data())) return ctx->fail(STARK_ERR_INVALID_ARG, "lde_mixed_batch: outputs overlap");
+    STARK_TRY(batch_check(ctx, "lde_mixed_batch", batch, evals, out, log_n, log_blowup));
     fr_t cs; if (coset4) cs = load_fr(coset4);
     return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return lde_mixed_run<F>(ctx, batch, evals, out, log_n, (int)log_blowup, coset4 ? &cs : nullptr); });
+}
+// The same-size calls keep drivers of their own (on the plan they measured slower at some shapes); the checks are the shared ones.
+int32_t stark_ntt_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, uint64_t* const* data, size_t log_n, int32_t inverse, const uint64_t* coset4) {
+    if (!ctx || (batch && !data) || log_n > 30) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    const std::vector<size_t> lns(batch, log_n);
+    STARK_TRY(batch_check(ctx, "ntt_batch", batch, nullptr, data, lns.data(), 0));
+    fr_t cs; if (coset4) cs = load_fr(coset4);
+    return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return ntt_batch_run<F>(ctx, batch, data, (int)log_n, inverse != 0, coset4 ? &cs : nullptr); });
+}
+int32_t stark_lde_batch_dev(stark_ctx_t* ctx, int32_t field_id, size_t batch, const uint64_t* const* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* const* out) {
+    if (!ctx || (batch && (!evals || !out)) || log_n > 30 || log_blowup > 30 || log_n + log_blowup > 30) return STARK_ERR_INVALID_ARG;
+    STARK_TRY(ctx_enter(ctx));
+    const std::vector<size_t> lns(batch, log_n);
+    STARK_TRY(batch_check(ctx, "lde_batch", batch, evals, out, lns.data(), log_blowup));
+    fr_t cs; if (coset4) cs = load_fr(coset4);
+    return with_field(ctx, field_id, [&](auto f) { using F = decltype(f); return lde_batch_run<F>(ctx, batch, evals, out, (int)log_n, (int)log_blowup, coset4 ? &cs : nullptr); });
 }
 int32_t stark_lde(stark_ctx_t* ctx, int32_t field_id, const uint64_t* evals, size_t log_n, size_t log_blowup, const uint64_t* coset4, uint64_t* out) {
     if (!ctx || !evals || !out || log_n + log_blowup > 30) return STARK_ERR_INVALID_ARG;

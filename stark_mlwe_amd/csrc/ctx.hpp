@@ -116,7 +116,7 @@ struct stark_ctx {
         bool merkle_wave_pair = false;   // Merkle levels of t = 9, 17 in the wave-pair form at EVERY size, as under side_commit (diagnostic: the wave-pair kernels at their smallest shapes)
         bool fri_side_pair = true;       // fri_build: the small layers' commitments on the side stream in the wave-pair form at every size (see side_commit); 0 = the latency forms (comparison)
         size_t sumcheck_verify_batch_max_slots = (size_t)1 << 25;   // a plan of the batched sum-check verifiers is run once it holds this many pool slots (1 GiB of field elements): device memory stays bounded whatever the batch
-        size_t ntt_batch_max_elems = (size_t)1 << 24;    // stark_ntt_batch_dev / stark_lde_batch_dev cut a batch into passes of at most this many output elements (ntt_batch_plan.hpp): 512 MiB of outputs and as much scratch per pass
+        size_t ntt_batch_max_elems = (size_t)1 << 24;    // the batched NTT / LDE calls cut a batch into passes of at most this many output elements (ntt_mixed_passes, ntt_mixed_plan.hpp): 512 MiB of outputs and as much scratch per pass
         size_t prove_batch_max_rows = (size_t)1 << 22;   // the batched DEEP-FRI provers cut a batch into passes of at most this many rows (traces x n0) whose tails run side by side (fri_batch.hpp); device memory per pass stays near 70 B per row
         int mle_log_tile = -1;           // log2 of the elements one workgroup of k_mle_fold_pass folds to one (3..12); -1 = the default of mle_dev.hpp
         int mle_lane_contiguous = -1;    // a lane of k_mle_fold_pass owns consecutive (1) or interleaved (0) elements; -1 = the default of mle_dev.hpp (comparison)

@@ -18,7 +18,7 @@
 #include "mfma_digits.hpp"
 #include "poseidon_chain.hpp"
 #include "fri_batch.hpp"
-#include "ntt_mixed_plan.hpp"    // includes ntt_batch_plan.hpp
+#include "ntt_mixed_plan.hpp"
 #include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
 #include "mle_dev.hpp"
 #include "merkle_batch.hpp"
@@ -986,17 +986,18 @@ int hc_fri_commit_batch(void* tparams, size_t B, const uint64_t* const* f0, size
 }
 }  // extern "C"
 
-// ---- the pass cutting of stark_ntt_batch_dev / stark_lde_batch_dev (ntt_batch_plan.hpp) --------------------------------------------------------
+// ---- the pass cutting and the overlap check of stark_ntt_batch_dev / stark_lde_batch_dev: the rules of ntt_mixed_plan.hpp on equal lengths -------------
 extern "C" {
 // columns per pass into out[0 .. cap); returns the number of passes
 size_t hc_ntt_batch_passes(size_t batch, int log_out, size_t max_elems, size_t* out, size_t cap) {
-    const std::vector<size_t> p = ntt_batch_passes(batch, log_out, max_elems);
+    const std::vector<size_t> lg(batch, (size_t)log_out), p = ntt_mixed_passes(batch, lg.data(), max_elems);
     for (size_t i = 0; i < p.size() && i < cap; ++i) out[i] = p[i];
     return p.size();
 }
 int hc_ntt_batch_ranges_overlap(const uint64_t* starts, size_t batch, size_t bytes) {
     std::vector<const void*> p(batch); for (size_t i = 0; i < batch; ++i) p[i] = (const void*)(uintptr_t)starts[i];
-    return ntt_batch_ranges_overlap(p.data(), batch, bytes) ? 1 : 0;
+    const std::vector<size_t> len(batch, bytes);
+    return ntt_batch_ranges_overlap(p.data(), batch, len.data()) ? 1 : 0;
 }
 }  // extern "C"
 
@@ -1027,6 +1028,20 @@ size_t hc_ntt_mixed_plan(size_t ncols, const size_t* log_n, int lde, int inverse
     }
     for (size_t i = 0; i < w.size() && i < cap; ++i) out[i] = w[i];
     return w.size();
+}
+// ntt_mixed_one_shape of every launch of the same plan, seven int64 per launch: holds, then (zeros unless it holds) src.mem, src.off, src.pitch, dst.mem,
+// dst.off, dst.pitch.  Returns the number of launches; only the first `cap` words are written.
+size_t hc_ntt_mixed_one_shape(size_t ncols, const size_t* log_n, int lde, int inverse, int coset, size_t log_blowup, int log_tile, int tile_forced, int64_t* out, size_t cap) {
+    NttTileOpts o; o.log_tile = log_tile; o.forced = tile_forced != 0;
+    const NttMixedPlan plan = lde ? ntt_mixed_lde_plan(log_n, ncols, (int)log_blowup, coset != 0, o) : ntt_mixed_ntt_plan(log_n, ncols, inverse != 0, coset != 0, o);
+    std::vector<int64_t> w;
+    for (const NttMixedLaunch& L : plan.launches) {
+        NttOneShape S; const bool one = ntt_mixed_one_shape(L, &S);
+        if (one) w.insert(w.end(), {1, S.src.mem, (int64_t)S.src.off, (int64_t)S.src.pitch, S.dst.mem, (int64_t)S.dst.off, (int64_t)S.dst.pitch});
+        else w.insert(w.end(), {0, 0, 0, 0, 0, 0, 0});
+    }
+    for (size_t i = 0; i < w.size() && i < cap; ++i) out[i] = w[i];
+    return plan.launches.size();
 }
 }  // extern "C"
 

@@ -181,9 +181,10 @@ __device__ __forceinline__ fr_t finish29_plain(fr29_t y) { fr29_partial_reduce<F
 // PRE: the pass applies a coset pre-scale on load (first pass of a coset transform): the scaled points go to LDS first and the head
 // works from there — eight inlined table products would not unroll.
 struct TileJob { uint64_t base, tile; };     // strided: element offset of the tile, tile index inside its outer block
-// Where the vectors of a BATCHED pass live (the NttBatchAddr instantiations of the pass kernels; stark_ntt_batch_dev / stark_lde_batch_dev): vector v is read at src_tab[v] (the
-// caller's columns, first pass of a transform) or src + v * src_pitch, and written at dst_tab[v] (the caller's outputs, last pass) or
-// dst + v * dst_pitch; pitches in elements.  Inside a vector every index — tile offsets, table exponents — is the single transform's.
+// Where the vectors of a batched launch of ONE shape live (the NttBatchAddr instantiations of the pass kernels; every launch of stark_ntt_batch_dev /
+// stark_lde_batch_dev, and the launches of the mixed calls for which ntt_mixed_one_shape, ntt_mixed_plan.hpp, holds): vector v is read at src_tab[v] (the caller's columns,
+// first pass of a transform) or src + v * src_pitch, and written at dst_tab[v] (the caller's outputs, last pass) or dst + v * dst_pitch; tables of
+// DEVICE pointers in device memory, pitches in elements.  Inside a vector every index — tile offsets, table exponents — is the single transform's.
 struct NttBatchAddr { const fr_t* const* src_tab; fr_t* const* dst_tab; uint64_t src_pitch, dst_pitch; };
 // Where a tile's vector starts.  The pass kernels take the batch addressing as an optional trailing kernel argument (BT... is empty or NttBatchAddr): the
 // plain instantiations pick the first overload of each pair at compile time and keep the signature and the one spacing, v << log_n, they always had.
@@ -197,8 +198,8 @@ __device__ __forceinline__ TileEnds last_ends(const NttPassArgs& A, uint64_t vec
 __device__ __forceinline__ TileEnds last_ends(const NttPassArgs&, uint64_t vec, const fr_t* src, fr_t* dst, const NttBatchAddr& Bt) {
     return TileEnds{Bt.src_tab ? Bt.src_tab[vec] : src + vec * Bt.src_pitch, Bt.dst_tab ? Bt.dst_tab[vec] : dst + vec * Bt.dst_pitch};
 }
-// RAGGED passes (the NttRaggedAddr instantiations; stark_ntt_mixed_batch_dev / stark_lde_mixed_batch_dev): the tiles of a launch belong to transforms of
-// different sizes.  A workgroup takes ONE tile (the grid is the launch's tile count): it locates the tile's column (ntt_ragged_locate), takes that
+// RAGGED passes (the NttRaggedAddr instantiations; every other launch of a batched call): the tiles of a launch belong to transforms of
+// different sizes. A workgroup takes ONE tile (the grid is the launch's tile count): it locates the tile's column (ntt_ragged_locate), takes that
 // column's shape record from the device table `shapes` IN PLACE of the kernel argument (PassOf overwrites the kernel's copy) — tile width, tables,
 // nz_points and all: everything inside a vector is the single transform's — and reads and writes at the column's own addresses.  The launch's LDS
 // size and thread count are those of its largest tile; a shape's `ntiles` is the tile count of ONE column.

@@ -1,4 +1,5 @@
-// stark_mlwe_amd/csrc/ntt_mixed_plan.hpp — the launch plan of stark_ntt_mixed_batch_dev / stark_lde_mixed_batch_dev: columns of any lengths in one pass.
+// stark_mlwe_amd/csrc/ntt_mixed_plan.hpp — the launch plan of stark_ntt_mixed_batch_dev / stark_lde_mixed_batch_dev: columns of any lengths in one pass;
+// and the rules every batched NTT / LDE call shares (pass cutting, overlap check, which extensions skip their padding).
 // Host-only C++ (no HIP) apart from the inline pieces the kernels share (NTT_HD), so the CPU diagnostic build (hostcheck.cpp) compiles the identical
 // rules: the split of a transform into passes, the tile width, the tile lookup of a ragged launch, the pass cutting, the overlap check and the plan.
 //
@@ -6,12 +7,13 @@
 // steps 0 and 1 hold strided passes only and step 2 every column's last pass.  A step is one RAGGED launch per kernel instantiation it needs (strided or
 // last, with or without the load-time pre-scale): at most 1 + 2 + 2 = 5 launches for a mixed transform, whatever the batch and however many distinct
 // sizes occur.  A mixed LDE is the inverse transforms (at most 3 launches: none is pre-scaled), one ragged pad/copy launch and the forward transforms.
+// A launch whose columns all have one shape (every launch of a batch of equal lengths, and often the strided launches of a mixed one) needs no lookup:
+// ntt_mixed_one_shape says how the NttBatchAddr kernels address it instead.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
-#include "ntt_batch_plan.hpp"
 
 #if defined(__HIPCC__)
 #define NTT_HD __host__ __device__ inline
@@ -54,7 +56,7 @@ NTT_HD uint32_t ntt_ragged_locate(const uint32_t* first_tile, uint32_t ncols, ui
     return lo;
 }
 
-// Two of the `batch` byte ranges [p[i], p[i] + bytes[i]) overlap (ranges of different lengths; an empty range overlaps nothing).
+// Two of the `batch` byte ranges [p[i], p[i] + bytes[i]) overlap (the outputs of a batched call must not; an empty range overlaps nothing).
 inline bool ntt_batch_ranges_overlap(const void* const* p, size_t batch, const size_t* bytes) {
     std::vector<std::pair<uintptr_t, size_t>> a;
     for (size_t i = 0; i < batch; ++i) if (bytes[i]) a.emplace_back((uintptr_t)p[i], bytes[i]);
@@ -63,9 +65,10 @@ inline bool ntt_batch_ranges_overlap(const void* const* p, size_t batch, const s
     return false;
 }
 
-// `batch` columns of 2^log_out[i] output elements, in the caller's order, cut into consecutive passes of at most `max_elems` output elements: a greedy
-// run over the sum.  A column larger than the limit is a pass of its own (the drivers run a pass of one column through the single-column path).
-// Returns the columns per pass.
+// `batch` columns of 2^log_out[i] output elements, in the caller's order, cut into consecutive passes of at most `max_elems` output elements (context
+// option "ntt_batch_max_elems"): a greedy run over the sum, which on equal lengths is max(1, max_elems >> log_out) columns per pass and what is left in
+// the last (the same-size drivers cut with this rule too).  A column larger than the limit is a pass of its own (the drivers run a pass of one column
+// through the single-column path).  Returns the columns per pass.
 inline std::vector<size_t> ntt_mixed_passes(size_t batch, const size_t* log_out, size_t max_elems) {
     std::vector<size_t> passes; size_t cols = 0; uint64_t sum = 0;
     for (size_t i = 0; i < batch; ++i) {
@@ -149,6 +152,28 @@ inline void ntt_mixed_add_transforms(NttMixedPlan& plan, int kind, const std::ve
     }
 }
 
+// One end (all sources or all destinations) of a launch whose columns share ONE shape record, as the NttBatchAddr kernels address it: mem NTT_MEM_IN /
+// NTT_MEM_OUT: the caller's vectors of the launch's columns, in launch order; NTT_MEM_SCRATCH: the k-th column of the launch at off + k * pitch.
+struct NttMixedEnd { int mem = NTT_MEM_SCRATCH; uint64_t off = 0, pitch = 0; };
+struct NttOneShape { NttMixedEnd src, dst; };
+// A transform launch needs neither the tile lookup nor the shape table: one shape, and each end wholly the caller's memory of one kind or wholly scratch
+// at one pitch.  Then its k-th column owns the tiles [k * tiles, (k + 1) * tiles), which is the order of the NttBatchAddr kernels.
+inline bool ntt_mixed_one_shape(const NttMixedLaunch& L, NttOneShape* out) {
+    if (L.kind == NTT_MIXED_PAD || L.shapes.size() != 1 || L.cols.empty()) return false;
+    NttOneShape S;
+    for (int e = 0; e < 2; ++e) {
+        auto ref = [&](size_t k) -> const NttMixedRef& { return e ? L.cols[k].dst : L.cols[k].src; };
+        NttMixedEnd& E = e ? S.dst : S.src; E.mem = ref(0).mem;
+        for (size_t k = 1; k < L.cols.size(); ++k) if (ref(k).mem != E.mem) return false;
+        if (E.mem != NTT_MEM_SCRATCH) continue;
+        E.off = ref(0).off;
+        if (L.cols.size() > 1) { if (ref(1).off < E.off) return false; E.pitch = ref(1).off - E.off; }
+        for (size_t k = 1; k < L.cols.size(); ++k) if (ref(k).off != E.off + k * E.pitch) return false;
+    }
+    if (out) *out = S;
+    return true;
+}
+
 // ncols in-place transforms of 2^log_n[i] points (columns with log_n[i] == 0 take no part).  Scratch: the intermediates of the columns of several passes.
 inline NttMixedPlan ntt_mixed_ntt_plan(const size_t* log_n, size_t ncols, bool inverse, bool coset, const NttTileOpts& o) {
     NttMixedPlan plan; std::vector<NttMixedItem> items;
@@ -162,7 +187,8 @@ inline NttMixedPlan ntt_mixed_ntt_plan(const size_t* log_n, size_t ncols, bool i
     return plan;
 }
 
-// The big forward transform of an LDE 2^log_n -> 2^(log_n + lb) takes its padding as zero without reading it (lde_run's `skip`, capi_ntt.hip)
+// The big forward transform of an LDE 2^log_n -> 2^(log_n + lb) takes its padding as zero without reading it: it has a strided first pass whose stride
+// divides n, which reads only the n coefficient rows (NttPassArgs::nz_points).  Otherwise (tiny transforms) the padding is written for real.
 inline bool ntt_lde_skips_padding(int log_n, int lb) {
     int b[3]; const int big = log_n + lb, P = ntt_split(big, b);
     return lb > 0 && P > 1 && big - b[0] <= log_n;

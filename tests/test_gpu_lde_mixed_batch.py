@@ -170,6 +170,81 @@ def test_lde_mixed_pass_cutting_on_the_device(gpu_ctx, oracle, columns):
         same(host(ys[c]), oracle.ntt(0, cols[c], inverse=False, coset=shift), "transform passes {10, 10, 11} {3}, column %d" % c)
 
 
+# ---- launches of one shape inside the mixed calls: addressed by pointer table or base + pitch instead of the ragged lookup ---------------------------
+def test_ntt_mixed_one_shape_launch_over_a_subset_of_the_table(gpu_ctx, oracle):
+    """[5, 12, 3, 12]: the first launch is the strided pass of caller columns 1 and 3 alone (one shape over a non-prefix subset of the table), the
+    last is ragged.  Forward on the generator's coset (Bls12-381 too) and inverse, against stark_ntt_dev and the oracle"""
+    lns = [5, 12, 3, 12]
+    for field, inverse, with_coset in ((0, False, True), (1, False, True), (0, True, False), (0, True, True)):
+        coset = oracle.from_u64(GEN[field], field) if with_coset else None
+        cols = [oracle.synth_column(0x51B5 + ln, c, 0, 1 << ln) for c, ln in enumerate(lns)]
+        xs = [dev(x) for x in cols]; ys = [dev(x) for x in cols]
+        sync(gpu_ctx)
+        gpu_ctx.ntt_mixed_batch_dev(field, [x.data_ptr() for x in xs], lns, inverse, coset)
+        for y, ln in zip(ys, lns):
+            gpu_ctx._chk(gpu_ctx.lib.stark_ntt_dev(gpu_ctx.h, field, C.c_void_p(y.data_ptr()), ln, int(inverse), _ptr(coset)))
+        sync(gpu_ctx)
+        for c, ln in enumerate(lns):
+            what = "field %d, column %d (2^%d), inverse %d, coset %s" % (field, c, ln, inverse, with_coset)
+            same(host(xs[c]), oracle.ntt(field, cols[c], inverse=inverse, coset=coset), what + " against the oracle")
+            same(host(xs[c]), host(ys[c]), what + " against stark_ntt_dev")
+
+
+@pytest.mark.parametrize("ln,B,lb", [(8, 4, 3), (4, 3, 1), (0, 3, 2)], ids=["skip-route", "padded-route", "one-point"])
+def test_equal_lengths_through_the_mixed_and_the_same_size_call(gpu_ctx, oracle, columns, ln, B, lb):
+    """B columns of 2^ln through stark_lde_mixed_batch_dev and stark_lde_batch_dev into separate outputs: byte-equal, the oracle's and stark_lde_dev's
+    per column; then with every input the head of its own output.  (4, 1): pad launch between the transforms; (0, 2): pad launch, then a forward pass
+    of one shape reading the scratch at pitch N + n.  Bls12-381 once, on the first case"""
+    import torch
+    for field in [0] + ([1] if ln == 8 else []):
+        for sname in ("none", "generator"):
+            shift = shift_of(oracle, field, sname)
+            ins = [columns(field, ln, lb, c, sname) for c in range(B)]
+            xs = [dev(x) for x, _ in ins]
+            for alias in (False, True):
+                om = [torch.full((1 << (ln + lb), 4), SENTINEL, dtype=torch.int64, device="cuda") for _ in xs]
+                ob = [torch.full((1 << (ln + lb), 4), SENTINEL, dtype=torch.int64, device="cuda") for _ in xs]
+                if alias:
+                    for o, x in zip(om + ob, xs + xs):
+                        o[:1 << ln] = x
+                im, ib = ([o.data_ptr() for o in om], [o.data_ptr() for o in ob]) if alias else ([x.data_ptr() for x in xs],) * 2
+                sync(gpu_ctx)
+                gpu_ctx.lde_mixed_batch_dev(field, im, [ln] * B, lb, [o.data_ptr() for o in om], shift)
+                gpu_ctx.lde_batch_dev(field, ib, ln, lb, [o.data_ptr() for o in ob], shift)
+                sync(gpu_ctx)
+                for c in range(B):
+                    what = "field %d, (%d, %d), shift '%s', aliased %d, column %d" % (field, ln, lb, sname, alias, c)
+                    same(host(om[c]), host(ob[c]), what + ": mixed call against stark_lde_batch_dev")
+                    same(host(ob[c]), ins[c][1], what + " against the oracle")
+                    if not alias:
+                        same(host(ob[c]), lde_single(gpu_ctx, field, xs[c], ln, lb, shift), what + " against stark_lde_dev")
+            for x, (xin, _) in zip(xs, ins):
+                assert (host(x) == xin).all(), "an input was modified"
+
+
+def test_equal_lengths_pass_cutting_on_the_device(gpu_ctx, oracle):
+    """three vectors of 2^11 points with passes of at most 2 * 2^11 elements, through stark_ntt_mixed_batch_dev ({11, 11} as one-shape launches, {11}
+    through the single path) and through stark_ntt_batch_dev (its own driver, cut by the same rule): both against the oracle and stark_ntt_dev"""
+    coset = oracle.from_u64(GEN[0], 0)
+    cols = [oracle.synth_column(0x9A57, c, 0, 1 << 11) for c in range(3)]
+    ms = [dev(x) for x in cols]; ys = [dev(x) for x in cols]
+    gpu_ctx.set_option("ntt_batch_max_elems", 2 << 11)
+    try:
+        gpu_ctx.ntt_mixed_batch_dev(0, [m.data_ptr() for m in ms], [11] * 3, False, coset)
+        gpu_ctx.ntt_batch_dev(0, [y.data_ptr() for y in ys], 11, False, coset); sync(gpu_ctx)
+    finally:
+        gpu_ctx.set_option("ntt_batch_max_elems", DEFAULT_MAX_ELEMS)
+    zs = [dev(x) for x in cols]
+    for z in zs:
+        gpu_ctx._chk(gpu_ctx.lib.stark_ntt_dev(gpu_ctx.h, 0, C.c_void_p(z.data_ptr()), 11, 0, _ptr(coset)))
+    sync(gpu_ctx)
+    for c in range(3):
+        want = oracle.ntt(0, cols[c], inverse=False, coset=coset)
+        for name, got in (("mixed", ms[c]), ("same-size", ys[c])):
+            same(host(got), want, "%s call, passes {11, 11} {11}, column %d against the oracle" % (name, c))
+            same(host(got), host(zs[c]), "%s call, passes {11, 11} {11}, column %d against stark_ntt_dev" % (name, c))
+
+
 def test_lde_mixed_option_matrix(gpu_ctx, oracle, columns):
     """{8, 5, 11} at blow-up 3, generator shift under every pre-scale form, tile width and launch shape of the single call's option matrix"""
     ins, xs, shift = small_case(oracle, columns)

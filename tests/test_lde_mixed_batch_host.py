@@ -152,6 +152,36 @@ def lib_plan(lib, log_ns, lde, inverse, coset, lb):
     return scratch, launches
 
 
+def ref_one_shape(launch):
+    """ntt_mixed_one_shape restated: None, or (src.mem, src.off, src.pitch, dst.mem, dst.off, dst.pitch) — one shape record, and each end wholly the
+    caller's memory of one kind or wholly scratch at off + k * pitch for the k-th column in launch order"""
+    (kind, *_), shapes, cols = launch
+    if kind == PAD or len(shapes) != 1:
+        return None
+    ends = []
+    for m, o in ((3, 4), (5, 6)):
+        if len({c[m] for c in cols}) != 1:
+            return None
+        offs = [c[o] for c in cols]
+        if cols[0][m] != SCRATCH:
+            ends += [cols[0][m], 0, 0]; continue
+        pitch = offs[1] - offs[0] if len(offs) > 1 else 0
+        if pitch < 0 or offs != [offs[0] + k * pitch for k in range(len(offs))]:
+            return None
+        ends += [SCRATCH, offs[0], pitch]
+    return tuple(ends)
+
+
+def lib_one_shape(lib, log_ns, lde, inverse, coset, lb):
+    lg = (C.c_size_t * max(len(log_ns), 1))(*log_ns)
+    lib.hc_ntt_mixed_one_shape.restype = C.c_size_t
+    args = (C.c_size_t(len(log_ns)), lg, int(lde), int(inverse), int(coset), C.c_size_t(lb), 11, 0)
+    nl = lib.hc_ntt_mixed_one_shape(*args, None, C.c_size_t(0))
+    buf = (C.c_int64 * max(7 * nl, 1))()
+    assert lib.hc_ntt_mixed_one_shape(*args, buf, C.c_size_t(7 * nl)) == nl
+    return [tuple(buf[7 * k + 1:7 * k + 7]) if buf[7 * k] else None for k in range(nl)]
+
+
 def check_transform_launches(launches, sizes, pre_first, what):
     """sizes: {col: log_n} of the transforms these launches run"""
     seen = {c: [] for c in sizes}
@@ -230,6 +260,7 @@ def test_plan_equals_a_plain_restatement_and_keeps_its_promises():
                 what = "transform %s, inverse %d, coset %d" % (log_ns, inverse, coset)
                 scratch, launches = lib_plan(lib, log_ns, 0, inverse, coset, 0)
                 assert (scratch, launches) == ref_plan(log_ns, 0, inverse, coset, 0), what
+                assert lib_one_shape(lib, log_ns, 0, inverse, coset, 0) == [ref_one_shape(l) for l in launches], what
                 assert len(launches) <= 5, what
                 assert all(k == (INVERSE if inverse else FORWARD) for (k, *_), _, _ in launches)
                 check_transform_launches(launches, {i: ln for i, ln in enumerate(log_ns) if ln}, bool(coset and not inverse), what)
@@ -239,6 +270,7 @@ def test_plan_equals_a_plain_restatement_and_keeps_its_promises():
                 what = "LDE %s, blow-up %d, coset %d" % (log_ns, lb, coset)
                 scratch, launches = lib_plan(lib, log_ns, 1, 0, coset, lb)
                 assert (scratch, launches) == ref_plan(log_ns, 1, 0, coset, lb), what
+                assert lib_one_shape(lib, log_ns, 1, 0, coset, lb) == [ref_one_shape(l) for l in launches], what
                 assert scratch == sum((1 << (ln + lb)) + (1 << ln) for ln in log_ns), what
                 kinds = [k for (k, *_), _, _ in launches]
                 assert kinds == sorted(kinds) and kinds.count(PAD) <= 1 and kinds.count(INVERSE) <= 3 and kinds.count(FORWARD) <= 5 and len(launches) <= 9, what
@@ -257,6 +289,77 @@ def test_plan_equals_a_plain_restatement_and_keeps_its_promises():
                     assert got == ls.route(ln, lb, coset), (what, i, got)
                     routes.add(got[1])
     assert {ls.NO_EXTENSION, ls.PADDED, ls.UNIT} <= routes and routes & set(ls.SKIP_COSET), routes       # padded, skipping and unextended columns all occurred
+
+
+def same_size_launches(B, log_n):
+    """(strided, log_b, log_c, ntiles) per launch of B transforms of 2^log_n points as a same-size driver cuts them: the split of one transform, tile
+    widths picked over all B << log_n elements"""
+    b = ls.split(log_n); total, rem, out = B << log_n, log_n, []
+    for i in range(len(b) - 1):
+        lc = pick_log_c(b[i], rem - b[i], total.bit_length() - 1); out.append((1, b[i], lc, total >> (b[i] + lc))); rem -= b[i]
+    lc = 0 if len(b) == 1 else pick_log_c(b[-1], b[0], total.bit_length() - 1)
+    return out + [(0, b[-1], lc, total >> (b[-1] + lc))]
+
+
+def check_equal_lengths(lib, log_ns, lde, inverse, coset, lb):
+    """every transform launch of a batch of equal lengths has one shape at one pitch, and the launches are the same-size driver's"""
+    B, ln = len(log_ns), log_ns[0]; what = (log_ns, lde, inverse, coset, lb)
+    scratch, launches = lib_plan(lib, log_ns, lde, inverse, coset, lb)
+    assert (scratch, launches) == ref_plan(log_ns, lde, inverse, coset, lb), what
+    one = lib_one_shape(lib, log_ns, lde, inverse, coset, lb)
+    assert one == [ref_one_shape(l) for l in launches], what
+    pitch = (1 << (ln + lb)) + (1 << ln) if lde else 1 << ln
+    got = {INVERSE: [], FORWARD: []}
+    for ((kind, step, strided, pre, ntiles, lds), shapes, cols), ends in zip(launches, one):
+        if kind == PAD:
+            assert ends is None, what
+            continue
+        assert ends is not None and len(shapes) == 1 and [c[0] for c in cols] == list(range(B)), what
+        for mem, off, p in (ends[:3], ends[3:]):
+            assert p == pitch if mem == SCRATCH else (off, p) == (0, 0), (what, ends)
+        assert ntiles == B * shapes[0][7] and lds == lds_bytes(shapes[0][3], shapes[0][4]), what
+        got[kind].append((strided, shapes[0][3], shapes[0][4], ntiles))
+    if not lde:
+        want = {INVERSE if inverse else FORWARD: same_size_launches(B, ln) if ln else [], FORWARD if inverse else INVERSE: []}
+    else:
+        want = {INVERSE: same_size_launches(B, ln) if ln else [], FORWARD: same_size_launches(B, ln + lb) if ln + lb else []}
+    assert got == want, (what, got, want)
+    return launches
+
+
+def test_equal_lengths_are_one_shape_launches_with_the_same_size_drivers_tiles():
+    lib = C.CDLL(hostcheck_lib.PATH)
+    for coset in (0, 1):
+        for inverse in (0, 1):
+            assert len(check_equal_lengths(lib, [11] * 3, 0, inverse, coset, 0)) == 2
+        kinds = lambda launches: [l[0][0] for l in launches]
+        assert kinds(check_equal_lengths(lib, [8] * 4, 1, 0, coset, 3)) == [INVERSE, FORWARD, FORWARD]             # skip route: no pad launch
+        assert kinds(check_equal_lengths(lib, [4] * 3, 1, 0, coset, 1)) == [INVERSE, PAD, FORWARD]                 # padded route
+        assert kinds(check_equal_lengths(lib, [0] * 3, 1, 0, coset, 0)) == [PAD]                                   # one point, no extension: a copy
+        launches = check_equal_lengths(lib, [0] * 3, 1, 0, coset, 2)
+        assert kinds(launches) == [PAD, FORWARD] and ref_one_shape(launches[1]) == (SCRATCH, 0, 5, OUT, 0, 0)      # reads the padded points at N + n
+
+
+def test_mixed_lengths_one_shape_launches_inside_ragged_calls():
+    lib = C.CDLL(hostcheck_lib.PATH)
+    for coset in (0, 1):
+        for inverse in (0, 1):
+            # (b) step 1 holds the first pass of the two 2^12 columns only: one shape over a subset of the caller's table; step 2 has three shapes
+            _, launches = lib_plan(lib, [5, 12, 3, 12], 0, inverse, coset, 0)
+            one = lib_one_shape(lib, [5, 12, 3, 12], 0, inverse, coset, 0)
+            assert [(l[0][1], [c[0] for c in l[2]]) for l in launches][0] == (1, [1, 3]), launches
+            assert one[0] == (IN, 0, 0, SCRATCH, 0, 1 << 12) and len(launches[0][1]) == 1
+            assert all(l[0][1] == 2 and (o is None) == (len(l[1]) > 1) for l, o in zip(launches[1:], one[1:]))
+            if coset and not inverse:                                      # the pre-scaled form is a launch of its own: the one-pass columns
+                assert [(l[0][3], len(l[1])) for l in launches[1:]] == [(0, 1), (1, 2)] and one[1] == (SCRATCH, 0, 1 << 12, OUT, 0, 0)
+            else:
+                assert [len(l[1]) for l in launches[1:]] == [3] and one[1:] == [None]
+        # (c) no launch with two shapes is a one-shape launch
+        _, launches = lib_plan(lib, [9, 9, 10], 1, 0, coset, 2)
+        one = lib_one_shape(lib, [9, 9, 10], 1, 0, coset, 2)
+        assert one == [ref_one_shape(l) for l in launches] and any(len(l[1]) == 2 for l in launches)
+        for l, o in zip(launches, one):
+            assert o is None or len(l[1]) == 1, l
 
 
 def test_launch_count_does_not_grow_with_the_batch_or_the_sizes():

@@ -212,7 +212,7 @@ def test_mle_passes(hostcheck, oracle, B):
 
 
 def test_lde_pass_cutting_allocates_nothing(hostcheck):
-    """the host part of the batched NTT / LDE is the pass cutting alone (ntt_batch_plan.hpp): the same passes under both fills; the scratch vector it
+    """the host part of the batched NTT / LDE is the pass cutting and the launch plan (ntt_mixed_plan.hpp), neither of which takes a pooled block: the same passes under both fills; the scratch vector it
     sizes is the device's (ctx_scratch), filled there by "pool_poison\""""
     import test_lde_batch_host as lb
     for fill in FILLS:

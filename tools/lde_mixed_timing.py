@@ -3,8 +3,8 @@
     python tools/lde_mixed_timing.py LIB [OUT.jsonl]     (default profiles/lde_mixed_timing.jsonl)
 
 Rows: eight columns per size 2^8 .. 2^14 (the mixed call against the seven per-size calls, and against the 2^14 group alone: the floor); one column
-per size 2^11 .. 2^16 (against the six per-size calls); 64 columns all 2^8 -> 2^11 (against stark_lde_batch_dev: the cost of the ragged lookup on
-equal shapes).  Each row checks the outputs byte-equal, warms both sides and reports the medians of ten alternating repetitions (host wall clock
+per size 2^11 .. 2^16 (against the six per-size calls); 64 columns all 2^8 -> 2^11 (against stark_lde_batch_dev: on equal shapes both calls
+launch the NttBatchAddr kernels, the mixed call from its plan and the batch call from its own driver).  Each row checks the outputs byte-equal, warms both sides and reports the medians of ten alternating repetitions (host wall clock
 around call + synchronise: the launches are what is being compared)."""
 import ctypes as C, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -2,7 +2,8 @@
 
     python tools/lde_timing.py LIB                      the single-column line (any library, also one without the batch entry points)
     python tools/lde_timing.py LIB --batch [OUT.jsonl]  stark_lde_batch_dev against B single calls (default profiles/lde_batch_timing.jsonl):
-        grid log_n in {8, 10, 13, 17}, blow-up 8, B in {4, 16, 64}; each point checks the outputs byte-equal, warms both sides and reports the
+        grid log_n in {8, 10, 13, 17}, blow-up 8, B in {4, 16, 64}, and log_n 8, blow-up 4, B 64 (the padded route: a pad launch between the
+        transforms); each point checks the outputs byte-equal, warms both sides and reports the
         medians of seven alternating pairs (host wall clock around call + synchronise: the launches are what is being compared);
         then option ntt_batch_max_elems from 2^12 to 2^26 at B = 64 for log_n = 8 and 13."""
 import ctypes as C, hashlib, json, os, statistics, sys, time
@@ -42,6 +43,7 @@ if "--batch" in sys.argv:
     for lg in (8, 10, 13, 17):
         for B in (4, 16, 64):
             rows.append(dict(batch_point(lg, 3, B, coset), kind="grid")); print(json.dumps(rows[-1]), flush=True)
+    rows.append(dict(batch_point(8, 2, 64, coset), kind="grid")); print(json.dumps(rows[-1]), flush=True)
     for lg in (8, 13):
         for le in range(12, 27, 2):
             ctx.set_option("ntt_batch_max_elems", 1 << le)
