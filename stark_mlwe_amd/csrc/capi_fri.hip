@@ -348,8 +348,7 @@ struct FriDevExec : DevArena {
     int32_t zpows(const fr_t& z, size_t m, fr_t* zp) { return zpows_launch(ctx, main_st, z, m, zp); }
     int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out) { return fold_launch(ctx, main_st, f, n, zp, m, out); }
     int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h) { return leaf_pair_hash_on(ctx, cur, f, f_next, n, m, h); }
-    int32_t pair_level(size_t arity, const DsBatchPairStream& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
-    int32_t ds_level(size_t arity, const DsBatchStream& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
+    template <class DS> int32_t hash_level(size_t arity, const DS& D, fr_t* out) { stark_params* mp = nullptr; STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(arity), &mp)); return hash_ds_on(ctx, cur, mp, D, out); }
     int32_t fork() { return fk.fork(); }
     void side(bool on) { cur = on && fk.side ? fk.side : main_st; }
     int32_t join() { return fk.join(); }

@@ -473,8 +473,7 @@ struct MerkleBatchDevExec {
             hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<size_t>(65535, B - b0)), dim3(256), 0, ctx->stream, src_x + b0, (uint64_t)n, dst + b0 * n);
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
-    int32_t pair_level(const DsBatchPairPtrStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, p, D, out); }
-    int32_t ds_level(const DsBatchStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, p, D, out); }
+    template <class DS> int32_t hash_level(const DS& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, p, D, out); }
 };
 int32_t merkle_build_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, size_t batch, const uint64_t* labels, const uint64_t* const* leaves, size_t n, int pairs,
                               const uint64_t* const* cp, stark_tree** out) {
@@ -503,7 +502,6 @@ struct MerkleMixedDevExec : MerkleBatchDevExec {
         hipLaunchKernelGGL(k_copy_ragged, dim3((unsigned)((D.n_out + 255) / 256)), dim3(256), 0, ctx->stream, D, dst);
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
-    int32_t ragged_level(const DsRaggedStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, p, D, out); }
 };
 int32_t merkle_build_mixed_batch_on(stark_ctx* ctx, stark_params* p, size_t arity, size_t batch, const uint64_t* labels, const uint64_t* const* leaves, const size_t* n, int pairs,
                                     const uint64_t* const* cp, stark_tree** out) {

@@ -144,8 +144,7 @@ static int32_t fold(stark_ctx* ctx, const fr_t* layer, size_t len, const fr_t& r
 struct ScDevExec : DevArena {
     stark_params* cp; stark_params* tp;
     ScDevExec(stark_ctx* c, stark_params* commit, stark_params* tr) : DevArena(c, true), cp(commit), tp(tr) {}
-    int32_t ds_level(const DsBatchStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, cp, D, out); }
-    int32_t ragged_level(const DsRaggedStream& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, cp, D, out); }
+    template <class DS> int32_t hash_level(const DS& D, fr_t* out) { return hash_ds_on(ctx, ctx->stream, cp, D, out); }
     int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim, size_t claim_from) {
         const uint64_t np = len / 2; const unsigned grid = (unsigned)std::min<uint64_t>((np + 255) / 256, 1024);
         DevBuf part; STARK_HIP(ctx, part.alloc(ctx, (size_t)grid * 2 * B * sizeof(fr_t)));

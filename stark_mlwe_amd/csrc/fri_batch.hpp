@@ -9,8 +9,8 @@
 //     exact: the fold challenge z_l depends only on (seed_z, l, n_l) (fri.rs:250), so all traces share it, and every m_l divides n_l, so
 //     neither a fold group (b m_l .. (b + 1) m_l) nor a leaf's partner index i / m_l crosses from one trace's slice into the next;
 //   * the pair leaves of an unhashed arity (4 and 2; every prove has one: the last layer is arity 2 with zero partners, fri.rs:266, 289) are
-//     one DsBatchPairStream launch, and every Merkle level of the Bp same-shape trees is one DsBatchStream launch under a per-tree label
-//     array holding l; the top level writes the Bp roots of layer l into roots[l * Bp ..];
+//     one DsBatchPairStream launch, and the Merkle levels of the Bp same-shape trees are merkle_climb (merkle_batch.hpp): one DsBatchStream launch
+//     per level under a per-tree label array holding l; the top level writes the Bp roots of layer l into roots[l * Bp ..];
 //   * layers 1..L are committed between fork() and side(false) — the device runs them on its side stream underneath layer 0, as fri_build does.
 // A pass of ONE trace does not come here: its commit is fri_build_impl (capi_fri.hip: PassCommit::run chooses), whose levels are DsStreams and
 // reach k_node16_pair and the "fri_side_pair" form; everything before and after the commit phase is shared by both forms.
@@ -24,6 +24,7 @@
 #include "host_util.hpp"
 #include "poseidon_streams.hpp"
 #include "fri_plan.hpp"
+#include "merkle_batch.hpp"
 
 namespace stark {
 
@@ -48,8 +49,7 @@ inline fr_t fri_z_from_fused(const fr_t& fused, uint64_t seed_z, size_t level, s
 //   int32_t zpows(const fr_t& z, size_t m, fr_t* zp)            zp[t] = z^t, t < m
 //   int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out)              fri_fold_layer over n elements
 //   int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h)      hash_leaf_pair(f[i], f_next[i / m]) (f_next == nullptr: zero)
-//   int32_t pair_level(size_t arity, const DsBatchPairStream& D, fr_t* out)                 (the Merkle parameters of `arity`)
-//   int32_t ds_level(size_t arity, const DsBatchStream& D, fr_t* out)
+//   template <class DS> int32_t hash_level(size_t arity, const DS& D, fr_t* out)            one launch over the hashes of D (the Merkle parameters of `arity`)
 //   int32_t fork() / void side(bool on) / int32_t join()        work issued while side(true) may run concurrently with what follows side(false) until join()
 template <class X> struct FriBatchCommit {
     X& x; size_t Bp = 0, L = 0;
@@ -61,6 +61,12 @@ template <class X> struct FriBatchCommit {
     uint64_t* labels = nullptr; std::vector<uint64_t> labels_host;              // (L + 1) x Bp: labels[l * Bp + b] = l
     explicit FriBatchCommit(X& x_) : x(x_) {}
 
+    // The executor the climb of one layer sees: X's memory, and X's hashes under the Merkle parameters of that layer's arity.
+    struct AtArity {
+        FriBatchCommit& c; size_t arity;
+        int32_t level_block(size_t k, fr_t** out) { return c.alloc_fr(k, out); }
+        template <class DS> int32_t hash_level(const DS& D, fr_t* out) { return c.x.hash_level(arity, D, out); }
+    };
     int32_t alloc_fr(size_t k, fr_t** out) { void* p = nullptr; FB_TRY(x.alloc((k ? k : 1) * sizeof(fr_t), &p)); *out = (fr_t*)p; return 0; }
     // The shapes of a pass (fri_layers).  -1: an empty layer or a schedule that does not divide; -2: a layer with arity 1.
     int32_t shape(size_t Bp_, size_t n0, const size_t* schedule, size_t L_, std::string& err) {
@@ -81,23 +87,15 @@ template <class X> struct FriBatchCommit {
         return x.upload(labels, labels_host.data(), labels_host.size() * sizeof(uint64_t));
     }
     // The commitment of layer l of every trace: leaf digests (hash_leaf_pair for a hashed arity, fri.rs:283; pair leaves otherwise, fri.rs:289),
-    // then MerkleTree::new's levels up to the Bp roots.
+    // then MerkleTree::new's levels up to the Bp roots (a layer of one element: the leaf digests are the roots).
     int32_t commit_layer(size_t l) {
         const size_t a = arity[l], nl = n[l], m = l < L ? sched[l] : 1;
         const fr_t* f_next = l < L ? f[l + 1] : nullptr;                                                        // zero partners on the last layer (fri.rs:266)
-        Tree& T = trees[l]; T.levels.clear(); T.lens.clear();
-        fr_t* cur = roots + l * Bp; if (nl > 1) FB_TRY(alloc_fr(Bp * nl, &cur));
-        if (hashed_arity(a)) FB_TRY(x.leaf_pairs(f[l], f_next, Bp * nl, m, cur));
-        else FB_TRY(x.pair_level(a, DsBatchPairStream::make(a, labels + l * Bp, f[l], f_next, nl, m, Bp), cur));
-        T.levels.push_back(cur); T.lens.push_back(nl);
-        uint32_t level = 0;
-        for (size_t len = nl; len > 1; ++level) {
-            const size_t nn = (len + a - 1) / a;
-            fr_t* nx = roots + l * Bp; if (nn > 1) FB_TRY(alloc_fr(Bp * nn, &nx));
-            FB_TRY(x.ds_level(a, DsBatchStream::make(a, level, 0, labels + l * Bp, nullptr, cur, len, Bp), nx));
-            T.levels.push_back(nx); T.lens.push_back(nn); cur = nx; len = nn;
-        }
-        return 0;
+        AtArity xa{*this, a};
+        fr_t* leaves = roots + l * Bp; if (nl > 1) FB_TRY(xa.level_block(Bp * nl, &leaves));
+        if (hashed_arity(a)) FB_TRY(x.leaf_pairs(f[l], f_next, Bp * nl, m, leaves));
+        else FB_TRY(xa.hash_level(DsBatchPairStream::make(a, labels + l * Bp, f[l], f_next, nl, m, Bp), leaves));
+        return merkle_climb(xa, a, Bp, labels + l * Bp, nullptr, leaves, nl, roots + l * Bp, trees[l].lens, trees[l].levels);
     }
     int32_t run() {
         size_t zp_total = 0; for (size_t l = 0; l < L; ++l) zp_total += sched[l];

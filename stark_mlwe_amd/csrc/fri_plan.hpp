@@ -41,6 +41,13 @@ inline size_t pick_arity_for_layer(size_t n, size_t m) {    // fri.rs:220-229
 }
 inline bool hashed_arity(size_t a) { return a == 128 || a == 64 || a == 32 || a == 16 || a == 8; }   // fri.rs:275
 inline int ilog2_ceil(size_t x) { int k = 0; while (((size_t)1 << k) < x) ++k; return k; }
+// The level lengths of a tree of n leaves (merkle/src/lib.rs:166-190), the one place this rule is written for whole trees; n = 1 is the one level
+// whose only element is the root.  (merkle_build_on, capi_poseidon.hip, walks the same rule level by level: it may stop early, at stop_at_len.)
+inline std::vector<size_t> merkle_level_lens(size_t n, size_t arity) {
+    std::vector<size_t> lens(1, n);
+    while (lens.back() > 1) lens.push_back((lens.back() + arity - 1) / arity);
+    return lens;
+}
 
 // The layers of a commit phase: their sizes under the schedule (fri.rs:150) and their Merkle arities (fri.rs:220-229), written once.  Every user maps
 // the result to its own return code and message (layer_shape_text has the wording they share).  arity_one: some layer of more than one leaf gets
@@ -88,8 +95,7 @@ struct FriShape {
         hashed.clear(); lens.clear();
         for (size_t l = 0; l <= L; ++l) {
             const size_t a = arity[l]; hashed.push_back(hashed_arity(a) ? 1 : 0);
-            std::vector<size_t> lv(1, n[l]); while (lv.back() > 1) lv.push_back((lv.back() + a - 1) / a);                       // merkle/src/lib.rs:166-190
-            lens.push_back(lv);
+            lens.push_back(merkle_level_lens(n[l], a));
         }
         roots.assign(roots_, roots_ + L + 1);
         return true;

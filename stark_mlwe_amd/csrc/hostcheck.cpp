@@ -57,6 +57,27 @@ static void bind(HcParams* P) {
     P->dev.chain_a = P->kc.chain_a.empty() ? nullptr : P->kc.chain_a.data(); P->dev.chain_g = P->kc.chain_g.empty() ? nullptr : P->kc.chain_g.data(); P->dev.chain_w = P->kc.chain_w.empty() ? nullptr : P->kc.chain_w.data();
 }
 
+// One launch of a DS stream on the host: hash_ds_body over every hash of D under P — the body every executor's hash_level and every hc_hash_ds_* export runs.
+template <class DS, class Put> static void hash_ds_stream(const HcParams* P, const DS& D, Put put) {
+    std::vector<fr_t> st(P->dev.t);
+    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; put(k, hash_ds_body(s, P->dev, D, k)); }
+}
+// The recording side of the host executors: while a log is open (hc_climb_launches), every hash_level records its launch — which stream, its DS level
+// number, its hashes, where they go — and writes zeros where the hashes would go (what is launched depends on the shapes alone).
+struct HcLaunch { int kind; uint32_t level; size_t n_out; const fr_t* out; };
+enum { kHcBatchPitch = 1, kHcBatchPtrs = 2, kHcBatchPairs = 3, kHcRaggedNodes = 4, kHcRaggedPairs = 5, kHcBatchPairPtrs = 6 };
+static thread_local std::vector<HcLaunch>* g_launch_log = nullptr;
+static int ds_kind(const DsBatchStream& D) { return D.in_ptrs ? kHcBatchPtrs : kHcBatchPitch; }
+static int ds_kind(const DsBatchPairStream&) { return kHcBatchPairs; }
+static int ds_kind(const DsBatchPairPtrStream&) { return kHcBatchPairPtrs; }
+static int ds_kind(const DsRaggedStream& D) { return D.mode == 1 ? kHcRaggedPairs : kHcRaggedNodes; }
+template <class DS> static int32_t hash_ds_stream(const HcParams* P, const DS& D, fr_t* out) {
+    if (g_launch_log) { g_launch_log->push_back(HcLaunch{ds_kind(D), fr_to_canonical<PF>(D.level_f).v[0], D.n_out, out}); std::fill(out, out + D.n_out, fr_zero<PF>()); return 0; }
+    hash_ds_stream(P, D, [&](size_t k, const fr_t& h) { out[k] = h; }); return 0;
+}
+static int32_t hash_ds_stream(const HcParams* P, const DsGatherStream& D, fr_t* out) { hash_ds_stream(P, D, [&](size_t k, const fr_t& h) { out[k] = h; }); return 0; }
+template <class DS> static int hash_ds_stream(const HcParams* P, const DS& D, uint64_t* out4) { hash_ds_stream(P, D, [&](size_t k, const fr_t& h) { st4(out4 + 4 * k, h); }); return 0; }
+
 extern "C" {
 
 // The byte of every block the host executors allocate from here on (process-wide; 0 = the default).  Returns the previous one; -1: not a byte.
@@ -622,11 +643,9 @@ int hc_leaf_pair(void* tparams, const uint64_t* f, const uint64_t* f_next, size_
 }
 int hc_hash_ds_level(void* params, int mode, size_t arity, uint32_t level, uint64_t pos0, uint64_t label, const uint64_t* in0, const uint64_t* in1, size_t n_in, uint64_t* out) {
     HcParams* P = (HcParams*)params;
-    std::vector<fr_t> a(n_in), b(in1 ? n_in : 0), st(P->dev.t);
+    std::vector<fr_t> a(n_in), b(in1 ? n_in : 0);
     for (size_t i = 0; i < n_in; ++i) { a[i] = ld4(in0 + 4 * i); if (in1) b[i] = ld4(in1 + 4 * i); }
-    const DsStream D = DsStream::make(mode, arity, level, pos0, label, a.data(), in1 ? b.data() : nullptr, n_in);
-    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, D, k)); }
-    return 0;
+    return hash_ds_stream(P, DsStream::make(mode, arity, level, pos0, label, a.data(), in1 ? b.data() : nullptr, n_in), out);
 }
 int hc_tr_hash(void* tparams, const char* tag, const uint64_t* fields, size_t k, size_t n, uint64_t* out) {
     HcParams* P = (HcParams*)tparams;
@@ -732,9 +751,7 @@ static void run_plan_host(VerifyBatchPlan V, const HcParams* tparams, int32_t* a
         fr_t st[17]; for (size_t j = 0; j < V.nl; ++j) { ArrayState s{st}; V.pool[V.leaf_out0 + j] = leaf_pair_body(s, tparams->dev, LS, j); }
     }
     for (const VerifyBatchPlan::Group& G : V.groups) {
-        HcParams* P = hc_param_cache().params((size_t)G.t - 1); std::vector<fr_t> st(P->dev.t);
-        const DsGatherStream D{V.hdr.data() + 4 * G.job0, V.off.data() + G.job0, V.idx.data(), V.pool.data(), G.n, G.max_children};
-        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; V.pool[G.out0 + k] = hash_ds_body(s, P->dev, D, k); }
+        hash_ds_stream(hc_param_cache().params((size_t)G.t - 1), DsGatherStream{V.hdr.data() + 4 * G.job0, V.off.data() + G.job0, V.idx.data(), V.pool.data(), G.n, G.max_children}, V.pool.data() + G.out0);
     }
     for (size_t b = 0; b < V.batch; ++b) {
         int32_t acc = V.flag[b];
@@ -779,16 +796,7 @@ int hc_merkle_verify(void* tparams, int pairs, size_t cfg_arity, uint64_t label,
 struct ScHostExec : HostArena {
     HcParams* cp; HcParams* tp;
     ScHostExec(HcParams* c, HcParams* t) : cp(c), tp(t) {}
-    int32_t ds_level(const DsBatchStream& D, fr_t* out) {
-        std::vector<fr_t> st(cp->dev.t);
-        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, cp->dev, D, k); }
-        return 0;
-    }
-    int32_t ragged_level(const DsRaggedStream& D, fr_t* out) {
-        std::vector<fr_t> st(cp->dev.t);
-        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, cp->dev, D, k); }
-        return 0;
-    }
+    template <class DS> int32_t hash_level(const DS& D, fr_t* out) { return hash_ds_stream(cp, D, out); }
     int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim, size_t claim_from) {
         for (size_t b = 0; b < B; ++b) {
             const fr_t* l = ptrs ? ptrs[b] : layers + b * len; fr_t c0 = fr_zero<PF>(), c1 = fr_zero<PF>();
@@ -811,11 +819,9 @@ extern "C" {
 // One Merkle level of B same-shape trees (DsBatchStream): in = B x n_in contiguous (by_ptrs: read through a pointer per tree), labels[b]
 int hc_hash_ds_batch_level(void* params, size_t arity, uint32_t level, uint64_t pos0, const uint64_t* labels, const uint64_t* in, size_t n_in, size_t trees, int by_ptrs, uint64_t* out) {
     HcParams* P = (HcParams*)params;
-    std::vector<fr_t> a(n_in * trees), st(P->dev.t); for (size_t i = 0; i < a.size(); ++i) a[i] = ld4(in + 4 * i);
+    std::vector<fr_t> a(n_in * trees); for (size_t i = 0; i < a.size(); ++i) a[i] = ld4(in + 4 * i);
     std::vector<const fr_t*> ptrs(trees); for (size_t b = 0; b < trees; ++b) ptrs[b] = a.data() + b * n_in;
-    const DsBatchStream D = DsBatchStream::make(arity, level, pos0, labels, by_ptrs ? ptrs.data() : nullptr, by_ptrs ? nullptr : a.data(), n_in, trees);
-    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, D, k)); }
-    return 0;
+    return hash_ds_stream(P, DsBatchStream::make(arity, level, pos0, labels, by_ptrs ? ptrs.data() : nullptr, by_ptrs ? nullptr : a.data(), n_in, trees), out);
 }
 // One launch of a TrBatchStream: state (17 per instance) and pos updated in place; out[a * nseg + s] per finished segment.
 int hc_tr_batch(void* tparams, uint64_t* state, uint32_t* pos, size_t n_inst, const uint32_t* inst, size_t inst0, size_t n_active, size_t nseg, const uint32_t* el_off,
@@ -893,9 +899,7 @@ static void run_sc_plan_host(ScVerifyPlan& V, HcParams* tp, HcParams* cp, int32_
         fr_t st[17]; for (size_t a = 0; a < S.n; ++a) { ArrayState s{st}; tr_batch_body(s, tp->dev, T, a); }
     }
     for (const VerifyBatchPlan::Group& G : V.ds.groups) {
-        std::vector<fr_t> st(cp->dev.t);
-        const DsGatherStream D{V.ds.hdr.data() + 4 * G.job0, V.ds.off.data() + G.job0, V.ds.idx.data(), pool.data(), G.n, G.max_children};
-        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; pool[G.out0 + k] = hash_ds_body(s, cp->dev, D, k); }
+        hash_ds_stream(cp, DsGatherStream{V.ds.hdr.data() + 4 * G.job0, V.ds.off.data() + G.job0, V.ds.idx.data(), pool.data(), G.n, G.max_children}, pool.data() + G.out0);
     }
     for (size_t j = 0; j < V.n_rec(); ++j) {
         const uint32_t* r = V.rec.data() + 8 * j;
@@ -946,13 +950,7 @@ struct FriHostExec : HostArena {
         fr_t st[17]; for (size_t i = 0; i < n; ++i) { ArrayState s{st}; h[i] = leaf_pair_body(s, tp->dev, LS, i); }
         return 0;
     }
-    template <class DS> int32_t ds(size_t arity, const DS& D, fr_t* out) {
-        HcParams* P = mp.params(arity); std::vector<fr_t> st(P->dev.t);
-        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, P->dev, D, k); }
-        return 0;
-    }
-    int32_t pair_level(size_t arity, const DsBatchPairStream& D, fr_t* out) { return ds(arity, D, out); }
-    int32_t ds_level(size_t arity, const DsBatchStream& D, fr_t* out) { return ds(arity, D, out); }
+    template <class DS> int32_t hash_level(size_t arity, const DS& D, fr_t* out) { return hash_ds_stream(mp.params(arity), D, out); }
     int32_t fork() { return 0; }
     void side(bool) {}
     int32_t join() { return 0; }
@@ -962,12 +960,10 @@ extern "C" {
 int hc_hash_ds_batch_pairs_level(void* params, size_t arity, const uint64_t* labels, const uint64_t* f, const uint64_t* cp, size_t n, size_t cp_div, size_t trees, uint64_t* out) {
     HcParams* P = (HcParams*)params;
     if (!cp_div || n % cp_div) return -1;
-    std::vector<fr_t> a(n * trees), b(cp ? n / cp_div * trees : 0), st(P->dev.t);
+    std::vector<fr_t> a(n * trees), b(cp ? n / cp_div * trees : 0);
     for (size_t i = 0; i < a.size(); ++i) a[i] = ld4(f + 4 * i);
     for (size_t i = 0; i < b.size(); ++i) b[i] = ld4(cp + 4 * i);
-    const DsBatchPairStream D = DsBatchPairStream::make(arity, labels, a.data(), cp ? b.data() : nullptr, n, cp_div, trees);
-    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, D, k)); }
-    return 0;
+    return hash_ds_stream(P, DsBatchPairStream::make(arity, labels, a.data(), cp ? b.data() : nullptr, n, cp_div, trees), out);
 }
 // The commit phase of B traces side by side (FriBatchCommit): roots[(b (L + 1) + l) * 4 ..] = root of layer l of trace b.  0 on success.
 int hc_fri_commit_batch(void* tparams, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z, uint64_t* roots) {
@@ -1255,17 +1251,10 @@ struct MerkleHostExec : HostArena {
         *lx = dl; *vx = dv; *cx = dc; return 0;
     }
     int32_t copy_rows(const fr_t* const* src, size_t n, size_t B, fr_t* dst) { for (size_t b = 0; b < B; ++b) for (size_t i = 0; i < n; ++i) dst[b * n + i] = src[b][i]; return 0; }
-    template <class DS> int32_t ds(const DS& D, fr_t* out) {
-        std::vector<fr_t> st(p->dev.t);
-        for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; out[k] = hash_ds_body(s, p->dev, D, k); }
-        return 0;
-    }
-    int32_t pair_level(const DsBatchPairPtrStream& D, fr_t* out) { return ds(D, out); }
-    int32_t ds_level(const DsBatchStream& D, fr_t* out) { return ds(D, out); }
+    template <class DS> int32_t hash_level(const DS& D, fr_t* out) { return hash_ds_stream(p, D, out); }
     // merkle_build_mixed_batch
     int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x) { DsRaggedStream::Seg* d = nullptr; put(h, &d); *x = d; return 0; }
     int32_t copy_ragged(const DsRaggedStream& D, fr_t* dst) { for (size_t i = 0; i < D.n_out; ++i) { const DsRaggedStream::Seg& S = D.segs[D.seg(i)]; dst[i] = S.in0[i - S.first]; } return 0; }
-    int32_t ragged_level(const DsRaggedStream& D, fr_t* out) { return ds(D, out); }
 };
 struct MerkleOpenHostExec { int32_t gather(const MerkleGatherList& G, fr_t* out) { for (size_t i = 0; i < G.size(); ++i) out[G.row_of(i)] = G.base[G.src[i]][G.index[i]]; return 0; } };
 static std::vector<size_t> total_lens(const std::vector<size_t>& lens, size_t B) { std::vector<size_t> o(lens.size() + 1, 0); for (size_t v = 0; v < lens.size(); ++v) o[v + 1] = o[v] + B * lens[v]; return o; }
@@ -1302,10 +1291,8 @@ long hc_hash_ds_ragged_level(void* params, int mode, size_t arity, uint32_t leve
         if (mode == 1 && in1 && in1[s]) { b[s].resize(n_in[s]); for (size_t i = 0; i < n_in[s]; ++i) b[s][i] = ld4(in1[s] + 4 * i); }
         T.add(mode, arity, a[s].data(), b[s].empty() ? nullptr : b[s].data(), n_in[s], labels[s]);
     }
-    const DsRaggedStream D = DsRaggedStream::make(mode, arity, level, pos0, T.segs.data(), n_seg, T.n_out);
-    std::vector<fr_t> st(P->dev.t);
-    for (size_t k = 0; k < D.n_out; ++k) { ArrayState s{st.data()}; st4(out + 4 * k, hash_ds_body(s, P->dev, D, k)); }
-    return (long)D.n_out;
+    hash_ds_stream(P, DsRaggedStream::make(mode, arity, level, pos0, T.segs.data(), n_seg, T.n_out), out);
+    return (long)T.n_out;
 }
 // MerkleTree::new / new_pairs of B trees of n[b] leaves through the mixed-size driver.  out (cap_fr elements) receives the level blocks back to back,
 // level v the slices of the trees with more than v levels in tree order.  nlev_out[b]: the levels of tree b, lens_out[64 b + v] their lengths.
@@ -1364,5 +1351,69 @@ int hc_merkle_verify_batch(size_t cfg_arity, size_t batch, const uint64_t* label
     if (host::width_for_arity(cfg_arity) < 0 || cfg_arity == 0) return -1;
     auto run = [](const VerifyBatchPlan& V, int32_t* acc) { run_plan_host(V, nullptr, acc); return 0; };
     return merkle_verify_batch(run, cfg_arity, batch, labels, roots, indices, idx_off, values, proofs, lens, max_slots ? max_slots : (size_t)1 << 25, accepted);
+}
+}  // extern "C"
+
+// ---- the climbs of merkle_batch.hpp on their own: the ragged plan as data, and the launches of each call site -------------------------------------
+extern "C" {
+// merkle_ragged_plan of B trees of n[b] leaves.  Per tree: nlev[b], lens[64 b + v], at[64 b + v]; per level v < depth (at most 64): block[v], t0[v],
+// n_seg[v], n_out[v]; per segment of the one table (at most cap written): first, n_in, label, tree.  *depth_out = depth; returns the number of
+// segments, or -1 on refused arguments (no tree, an empty tree, arity 0 or arity 1 with more than one leaf) or a tree of more than 64 levels.
+long hc_merkle_ragged_plan(size_t arity, size_t B, const size_t* n, const uint64_t* labels, int leaf_table, size_t* depth_out, size_t* nlev, size_t* lens, size_t* at,
+                           size_t* block, size_t* t0, size_t* n_seg, size_t* n_out, uint64_t* seg_first, uint64_t* seg_n_in, uint64_t* seg_label, uint32_t* seg_tree, size_t cap) {
+    if (!B || !arity) return -1;
+    for (size_t b = 0; b < B; ++b) if (!n[b] || (arity == 1 && n[b] > 1)) return -1;
+    const MerkleRaggedPlan P = merkle_ragged_plan(arity, B, n, labels, leaf_table != 0);
+    if (P.depth > 64) return -1;
+    *depth_out = P.depth;
+    for (size_t b = 0; b < B; ++b) { nlev[b] = P.lens[b].size(); for (size_t v = 0; v < P.lens[b].size(); ++v) { lens[64 * b + v] = P.lens[b][v]; at[64 * b + v] = P.at[b][v]; } }
+    for (size_t v = 0; v < P.depth; ++v) { block[v] = P.block[v]; t0[v] = P.t0[v]; n_seg[v] = P.n_seg[v]; n_out[v] = P.n_out[v]; }
+    for (size_t s = 0; s < P.segs.size() && s < cap; ++s) { seg_first[s] = P.segs[s].first; seg_n_in[s] = P.segs[s].n_in; seg_label[s] = P.segs[s].label; seg_tree[s] = P.tree[s]; }
+    return (long)P.segs.size();
+}
+// The DS launches of one call site of the climbs over zero-valued inputs of the given shapes, in launch order: out[4 i ..] = (stream kind: 1 DsBatchStream
+// at a pitch, 2 behind a pointer table, 3 DsBatchPairStream, 4 DsRaggedStream node level, 5 pair leaves, 6 DsBatchPairPtrStream; DS level number; hashes; 1 when they go into
+// the caller's top slots, else 0).  Returns their number (at most cap written), or -1 on a refused shape.
+//   site 0  merkle_build_batch: B trees of n[0] leaves, flag = pairs                  site 1  merkle_build_mixed_batch: tree b of n[b] leaves, flag = pairs
+//   site 2  FriBatchCommit::run: B traces of n[0] rows under schedule[0 .. L); the top slots are the (L + 1) x B roots
+//   site 3  ScBatch::commit_layers: B layers of n[0] elements, flag = behind a pointer table; the top slots are B roots
+//   site 4  ScBatch::commit_witnesses: witness b of n[b] = 2^k elements; the top slots are B roots
+long hc_climb_launches(int site, size_t arity, size_t B, const size_t* n, int flag, const size_t* schedule, size_t L, int64_t* out, size_t cap) {
+    if (!B || !arity) return -1;
+    const size_t nb = site == 1 || site == 4 ? B : 1;
+    for (size_t b = 0; b < nb; ++b) if (!n[b] || (arity == 1 && n[b] > 1)) return -1;
+    std::vector<std::vector<fr_t>> col(B); std::vector<const fr_t*> cp(B); std::vector<uint64_t> labels(B); std::vector<size_t> k(B, 0);
+    for (size_t b = 0; b < B; ++b) { const size_t nn = n[nb == 1 ? 0 : b]; col[b].assign(nn, fr_zero<PF>()); cp[b] = col[b].data(); labels[b] = 100 + b; while (((size_t)1 << k[b]) < nn) ++k[b]; }
+    std::vector<HcLaunch> log; const fr_t* top = nullptr; size_t n_top = 0; int32_t rc = 0;
+    struct Open { Open(std::vector<HcLaunch>* l) { g_launch_log = l; } ~Open() { g_launch_log = nullptr; } };
+    // the executors (and with them the top slots) live until the log is classified
+    HcParams* P = hc_param_cache().params(site >= 3 ? 16 : arity);
+    MerkleHostExec XM(P); FriHostExec XF(P); FriBatchCommit<FriHostExec> C(XF); ScHostExec XS(P, P); ScBatch<ScHostExec> S(XS, B, cp.data(), k.data(), labels.data());
+    if (site == 0) {
+        std::vector<size_t> lens; std::vector<fr_t*> base; Open o(&log);
+        rc = merkle_build_batch(XM, arity, B, labels.data(), cp.data(), n[0], flag, flag ? cp.data() : nullptr, lens, base);
+    } else if (site == 1) {
+        std::vector<std::vector<size_t>> lens, at; std::vector<fr_t*> base; Open o(&log);
+        rc = merkle_build_mixed_batch(XM, arity, B, labels.data(), cp.data(), n, flag, flag ? cp.data() : nullptr, lens, at, base);
+    } else if (site == 2) {
+        std::string err; if (C.shape(B, n[0], schedule, L, err)) return -1;
+        const std::vector<fr_t> z(L, host::h_u64(3)); if (C.init(z.data())) return -1;
+        for (size_t i = 0; i < B * n[0]; ++i) C.f[0][i] = fr_zero<PF>();
+        Open o(&log); rc = C.run(); top = C.roots; n_top = (L + 1) * B;
+    } else if (site == 3 || site == 4) {
+        if (site == 4) for (size_t b = 0; b < B; ++b) if (n[b] != (size_t)1 << k[b]) return -1;
+        if (S.setup()) return -1;
+        fr_t* roots = nullptr; if (S.alloc_fr(B, &roots)) return -1;
+        std::vector<ScBatch<ScHostExec>::Tree> T; Open o(&log);
+        if (site == 4) rc = S.commit_witnesses(roots, T);
+        else if (flag) rc = S.commit_layers(S.wit_x, S.wit_s.data(), nullptr, n[0], B, roots, T);
+        else { fr_t* layers = nullptr; if (S.alloc_fr(B * n[0], &layers)) return -1; for (size_t i = 0; i < B * n[0]; ++i) layers[i] = fr_zero<PF>(); rc = S.commit_layers(nullptr, nullptr, layers, n[0], B, roots, T); }
+        top = roots; n_top = B;
+    } else return -1;
+    if (rc) return -1;
+    for (size_t i = 0; i < log.size() && i < cap; ++i) {
+        out[4 * i] = log[i].kind; out[4 * i + 1] = log[i].level; out[4 * i + 2] = (int64_t)log[i].n_out; out[4 * i + 3] = top && log[i].out >= top && log[i].out < top + n_top ? 1 : 0;
+    }
+    return (long)log.size();
 }
 }  // extern "C"

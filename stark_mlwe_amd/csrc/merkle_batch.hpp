@@ -5,6 +5,7 @@
 //   build   `batch` trees of one shape (arity, n, pairs).  Level v of all trees is ONE block of batch x lens[v] elements, tree b's level the slice at
 //           b * lens[v]: level 0 is one copy (or one pair-leaf launch) through the pointer tables, every level above one DsBatchStream launch.
 //           Trees of different lengths: merkle_build_mixed_batch, level v one block of the slices of the trees that still have it (DsRaggedStream).
+//           The loop over the levels is merkle_climb / merkle_climb_ragged, which the batched FRI and sum-check commits run too.
 //   open    any trees of one context: every tree is planned on the host (merkle_open_from over a recording source), all siblings of all trees and
 //           levels come back with ONE gather, and each proof is encoded with enc_mproof.  stark_merkle_open is this with one tree.
 //   verify  every opening is parsed (dec_mproof) and walked over pool slots (DsJobPlanner) into the plan shape of fri_verify_batch.hpp; what runs the
@@ -23,70 +24,111 @@ namespace stark {
 
 #define MB_TRY(e) do { int32_t rc__ = (e); if (rc__) return rc__; } while (0)
 
-// The level lengths of a tree of n leaves (merkle/src/lib.rs:166-190); n = 1 is the one level whose only element is the root.
-inline std::vector<size_t> merkle_level_lens(size_t n, size_t arity) {
-    std::vector<size_t> lens(1, n);
-    while (lens.back() > 1) lens.push_back((lens.back() + arity - 1) / arity);
-    return lens;
-}
-
-// ---- build ------------------------------------------------------------------------------------------------------------------------------------
-// An executor X provides (pointers are its own memory: device pointers on the GPU, host pointers in the host check):
-//   int32_t level_block(size_t n_fr, fr_t** out)      the block of one level of all trees; it lives as long as the trees do
-//   int32_t tables(const uint64_t* labels, const fr_t* const* leaves, const fr_t* const* cp, size_t B,
-//                  const uint64_t** labels_x, const fr_t* const** leaves_x, const fr_t* const** cp_x)
-//                                                      the labels and pointer tables in X's memory (cp == nullptr: *cp_x = nullptr); the caller's arrays may die on return
-//   int32_t copy_rows(const fr_t* const* src_x, size_t n, size_t B, fr_t* dst)          dst[b n + i] = src[b][i]
-//   int32_t pair_level(const DsBatchPairPtrStream& D, fr_t* out)
-//   int32_t ds_level(const DsBatchStream& D, fr_t* out)
-// lens[v] / base[v]: the length of level v and the block that holds it for all trees.  The argument checks are the caller's (merkle_build_on's).
+// ---- the climb: level v of all trees hashed into level v + 1 until every tree has its root (merkle/src/lib.rs:163-179) ---------------------------------
+// Written here once for every batched builder (merkle_build_batch / merkle_build_mixed_batch below, FriBatchCommit::commit_layer in fri_batch.hpp,
+// ScBatch::commit_layers / commit_witnesses in sumcheck_batch.hpp).  The rules: level v - 1 is the DS level number of the launch that writes level v,
+// positions start at 0, the last node of a level may be ragged, a tree of one leaf has its one level and no hash (the pair leaves, DS level 2^32 - 1,
+// are a level 0 and so the caller's).  An executor X provides (pointers are its own memory: device pointers on the GPU, host pointers in the host check):
+//   int32_t level_block(size_t n_fr, fr_t** out)                     the block of one level of all trees; it lives as long as the trees do
+//   template <class DS> int32_t hash_level(const DS& D, fr_t* out)   one launch of hash_with_ds_dynamic over the hashes of D
+//
+// `B` trees of one shape: tree b's level 0 is in_ptrs[b][0 .. n) (a pointer table in X's memory) or in[b n .. (b + 1) n); labels_x: the per-tree
+// labels in X's memory.  Level v >= 1 of all trees is ONE block of B x lens[v] elements written by ONE DsBatchStream launch, tree b's level the slice
+// at base[v] + b lens[v]; base[0] = in (null behind a pointer table).  top: where the top level (the B roots) goes instead of a block of its own, or null.
 template <class X>
-inline int32_t merkle_build_batch(X& x, size_t arity, size_t B, const uint64_t* labels, const fr_t* const* leaves, size_t n, int pairs, const fr_t* const* cp,
-                                  std::vector<size_t>& lens, std::vector<fr_t*>& base) {
-    lens = merkle_level_lens(n, arity); base.assign(lens.size(), nullptr);
-    const uint64_t* labels_x = nullptr; const fr_t* const* leaves_x = nullptr; const fr_t* const* cp_x = nullptr;
-    MB_TRY(x.tables(labels, leaves, pairs ? cp : nullptr, B, &labels_x, &leaves_x, &cp_x));
-    MB_TRY(x.level_block(B * n, &base[0]));
-    if (pairs) MB_TRY(x.pair_level(DsBatchPairPtrStream::make(arity, labels_x, leaves_x, cp_x, n, B), base[0]));     // new_pairs (:380-388, 392-414)
-    else MB_TRY(x.copy_rows(leaves_x, n, B, base[0]));                                                                // new: the leaves are level 0
-    for (size_t v = 1; v < lens.size(); ++v) {                                                                        // :163-179
-        MB_TRY(x.level_block(B * lens[v], &base[v]));
-        MB_TRY(x.ds_level(DsBatchStream::make(arity, (uint32_t)(v - 1), 0, labels_x, nullptr, base[v - 1], lens[v - 1], B), base[v]));
+inline int32_t merkle_climb(X& x, size_t arity, size_t B, const uint64_t* labels_x, const fr_t* const* in_ptrs, const fr_t* in, size_t n, fr_t* top,
+                            std::vector<size_t>& lens, std::vector<fr_t*>& base) {
+    lens = merkle_level_lens(n, arity); base.assign(lens.size(), nullptr); base[0] = const_cast<fr_t*>(in);
+    for (size_t v = 1; v < lens.size(); ++v) {
+        if (top && v + 1 == lens.size()) base[v] = top; else MB_TRY(x.level_block(B * lens[v], &base[v]));
+        MB_TRY(x.hash_level(DsBatchStream::make(arity, (uint32_t)(v - 1), 0, labels_x, v == 1 ? in_ptrs : nullptr, v == 1 ? in : base[v - 1], lens[v - 1], B), base[v]));
     }
     return 0;
 }
 
-// ---- build, trees of different lengths ------------------------------------------------------------------------------------------------------------
-// `B` trees of one arity and parameter set, tree b of n[b] >= 1 leaves.  Level v of the call is ONE block: the slices of the trees that have more
-// than v levels, back to back in tree order (a tree of one leaf has its one level and no hash; trees drop out as they reach their root).  Level 0 is
-// one ragged copy (or one ragged pair-leaf launch), every level above one DsRaggedStream launch over the trees that still have it.  All blocks are
-// taken first, so every segment table of the call is built on the host and goes up as ONE table.
-// An executor X provides (level_block as above):
+// Trees of different lengths, tree b of n[b] >= 1 leaves: level v of the call is ONE block, the slices of the trees that have more than v levels back
+// to back in tree order (trees drop out as they reach their root), written by ONE DsRaggedStream launch over a segment table of those trees.
+// The plan is everything about such a call that the lengths decide, as host data with no executor in it: lens[b] the level lengths of tree b,
+// at[b][v] where its level v starts in the block of level v, block[v] that block's length, and every segment table of the call as ONE table: table v
+// (n_seg[v] segments from segs[t0[v]], n_out[v] hashes) is the launch that writes level v, segment s of it tree tree[t0[v] + s] with its label, the
+// length of its level v - 1 and `first`.  Table 0, only with leaf_table, is the launch that makes level 0 of every tree out of n[b] inputs
+// each (the caller's: pair leaves or a copy).  in0 / in1 are left null: the climb points in0 of the tables v >= 1 at the blocks, table 0 is the caller's.
+struct MerkleRaggedPlan {
+    size_t arity = 0, depth = 0;
+    std::vector<std::vector<size_t>> lens, at; std::vector<size_t> block;
+    std::vector<DsRaggedStream::Seg> segs; std::vector<uint32_t> tree; std::vector<size_t> t0, n_seg, n_out;
+};
+inline MerkleRaggedPlan merkle_ragged_plan(size_t arity, size_t B, const size_t* n, const uint64_t* labels, bool leaf_table) {
+    MerkleRaggedPlan P; P.arity = arity; P.lens.assign(B, {}); P.at.assign(B, {});
+    for (size_t b = 0; b < B; ++b) { P.lens[b] = merkle_level_lens(n[b], arity); P.at[b].assign(P.lens[b].size(), 0); P.depth = std::max(P.depth, P.lens[b].size()); }
+    P.block.assign(P.depth, 0); P.t0.assign(P.depth, 0); P.n_seg.assign(P.depth, 0); P.n_out.assign(P.depth, 0);
+    for (size_t v = 0; v < P.depth; ++v) {
+        P.t0[v] = P.segs.size();
+        for (size_t b = 0; b < B; ++b) if (P.lens[b].size() > v) {
+            P.at[b][v] = P.block[v]; P.block[v] += P.lens[b][v];
+            if (!v && !leaf_table) continue;
+            P.segs.push_back(DsRaggedStream::Seg{nullptr, nullptr, (uint64_t)(v ? P.lens[b][v - 1] : n[b]), labels[b], (uint64_t)P.n_out[v]}); P.tree.push_back((uint32_t)b);
+            P.n_out[v] += P.lens[b][v];
+        }
+        P.n_seg[v] = P.segs.size() - P.t0[v];
+    }
+    return P;
+}
+// The climb over a plan.  level0[b]: where tree b's level 0 is (a host array of pointers in X's memory); top: where the top level goes instead of a
+// block of its own, or null.  The blocks of the levels 1 .. depth - 1 are taken first, then the whole table goes up ONCE (x.segments), then
+// level0_launch(table 0 in X's memory) runs what makes level 0 — it must return 0 without a launch where level 0 exists already — and then the levels,
+// one launch each.  base[v]: the block of level v (base[0] stays null: level 0 is wherever the caller has it).  Besides level_block and hash_level, X provides
 //   int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x)   the table in X's memory; `h` may die on return
+template <class X, class L0>
+inline int32_t merkle_climb_ragged(X& x, MerkleRaggedPlan& P, const fr_t* const* level0, fr_t* top, std::vector<fr_t*>& base, L0 level0_launch) {
+    base.assign(P.depth, nullptr);
+    for (size_t v = 1; v < P.depth; ++v) { if (top && v + 1 == P.depth) base[v] = top; else MB_TRY(x.level_block(P.block[v], &base[v])); }
+    for (size_t v = 1; v < P.depth; ++v) for (size_t s = P.t0[v]; s < P.t0[v] + P.n_seg[v]; ++s) {
+        const size_t b = P.tree[s]; P.segs[s].in0 = v == 1 ? level0[b] : base[v - 1] + P.at[b][v - 1];
+    }
+    if (P.segs.empty()) return 0;
+    const DsRaggedStream::Seg* sx = nullptr; MB_TRY(x.segments(P.segs, &sx));
+    MB_TRY(level0_launch(sx));
+    for (size_t v = 1; v < P.depth; ++v) MB_TRY(x.hash_level(DsRaggedStream::make(0, P.arity, (uint32_t)(v - 1), 0, sx + P.t0[v], P.n_seg[v], P.n_out[v]), base[v]));
+    return 0;
+}
+
+// ---- build ------------------------------------------------------------------------------------------------------------------------------------
+// `batch` trees of one shape.  Besides the climb's level_block and hash_level, an executor X provides:
+//   int32_t tables(const uint64_t* labels, const fr_t* const* leaves, const fr_t* const* cp, size_t B,
+//                  const uint64_t** labels_x, const fr_t* const** leaves_x, const fr_t* const** cp_x)
+//                                                      the labels and pointer tables in X's memory (cp == nullptr: *cp_x = nullptr); the caller's arrays may die on return
+//   int32_t copy_rows(const fr_t* const* src_x, size_t n, size_t B, fr_t* dst)          dst[b n + i] = src[b][i]
+// lens[v] / base[v]: the length of level v and the block that holds it for all trees.  The argument checks are the caller's (merkle_build_on's).
+template <class X>
+inline int32_t merkle_build_batch(X& x, size_t arity, size_t B, const uint64_t* labels, const fr_t* const* leaves, size_t n, int pairs, const fr_t* const* cp,
+                                  std::vector<size_t>& lens, std::vector<fr_t*>& base) {
+    const uint64_t* labels_x = nullptr; const fr_t* const* leaves_x = nullptr; const fr_t* const* cp_x = nullptr;
+    MB_TRY(x.tables(labels, leaves, pairs ? cp : nullptr, B, &labels_x, &leaves_x, &cp_x));
+    fr_t* l0 = nullptr; MB_TRY(x.level_block(B * n, &l0));
+    if (pairs) MB_TRY(x.hash_level(DsBatchPairPtrStream::make(arity, labels_x, leaves_x, cp_x, n, B), l0));          // new_pairs (:380-388, 392-414)
+    else MB_TRY(x.copy_rows(leaves_x, n, B, l0));                                                                     // new: the leaves are level 0
+    return merkle_climb(x, arity, B, labels_x, nullptr, l0, n, nullptr, lens, base);
+}
+
+// ---- build, trees of different lengths ------------------------------------------------------------------------------------------------------------
+// `B` trees of one arity and parameter set, tree b of n[b] >= 1 leaves.  Level 0 is one ragged copy (or one ragged pair-leaf launch) over table 0 of
+// the plan, which goes up with the climb's tables.  Besides the climb's three, an executor X provides:
 //   int32_t copy_ragged(const DsRaggedStream& D, fr_t* dst)                                      dst[first_s + j] = in0_s[j] (D of mode 1)
-//   int32_t ragged_level(const DsRaggedStream& D, fr_t* out)
 // lens[b]: the level lengths of tree b; at[b][v]: where its level v starts in base[v].  The argument checks are the caller's.
 template <class X>
 inline int32_t merkle_build_mixed_batch(X& x, size_t arity, size_t B, const uint64_t* labels, const fr_t* const* leaves, const size_t* n, int pairs, const fr_t* const* cp,
                                         std::vector<std::vector<size_t>>& lens, std::vector<std::vector<size_t>>& at, std::vector<fr_t*>& base) {
-    lens.assign(B, {}); at.assign(B, {}); size_t depth = 0;
-    for (size_t b = 0; b < B; ++b) { lens[b] = merkle_level_lens(n[b], arity); at[b].assign(lens[b].size(), 0); depth = std::max(depth, lens[b].size()); }
-    std::vector<size_t> block(depth, 0);
-    for (size_t v = 0; v < depth; ++v) for (size_t b = 0; b < B; ++b) if (lens[b].size() > v) { at[b][v] = block[v]; block[v] += lens[b][v]; }
-    base.assign(depth, nullptr);
-    for (size_t v = 0; v < depth; ++v) MB_TRY(x.level_block(block[v], &base[v]));
-    // table 0: the leaves (pair-leaf mode; the plain copy reads the same table), table v >= 1: the node level that turns level v - 1 into level v
-    std::vector<DsRaggedTable> T(depth);
-    for (size_t b = 0; b < B; ++b) T[0].add(1, arity, leaves[b], pairs ? cp[b] : nullptr, n[b], labels[b]);
-    for (size_t v = 1; v < depth; ++v) for (size_t b = 0; b < B; ++b) if (lens[b].size() > v) T[v].add(0, arity, base[v - 1] + at[b][v - 1], nullptr, lens[b][v - 1], labels[b]);
-    std::vector<DsRaggedStream::Seg> all; std::vector<size_t> t0(depth);
-    for (size_t v = 0; v < depth; ++v) { t0[v] = all.size(); all.insert(all.end(), T[v].segs.begin(), T[v].segs.end()); }
-    const DsRaggedStream::Seg* sx = nullptr; MB_TRY(x.segments(all, &sx));
-    const DsRaggedStream L0 = DsRaggedStream::make(1, arity, 0xFFFFFFFFu, 0, sx, B, T[0].n_out);
-    if (pairs) MB_TRY(x.ragged_level(L0, base[0]));                                                                   // new_pairs (:380-388, 392-414)
-    else MB_TRY(x.copy_ragged(L0, base[0]));                                                                          // new: the leaves are level 0
-    for (size_t v = 1; v < depth; ++v)                                                                                // :163-179
-        MB_TRY(x.ragged_level(DsRaggedStream::make(0, arity, (uint32_t)(v - 1), 0, sx + t0[v], T[v].segs.size(), T[v].n_out), base[v]));
+    MerkleRaggedPlan P = merkle_ragged_plan(arity, B, n, labels, true);
+    fr_t* l0 = nullptr; MB_TRY(x.level_block(P.block[0], &l0));
+    std::vector<const fr_t*> level0(B);
+    for (size_t b = 0; b < B; ++b) { P.segs[b].in0 = leaves[b]; P.segs[b].in1 = pairs ? cp[b] : nullptr; level0[b] = l0 + P.at[b][0]; }
+    MB_TRY(merkle_climb_ragged(x, P, level0.data(), nullptr, base, [&](const DsRaggedStream::Seg* t0) {
+        const DsRaggedStream L0 = DsRaggedStream::make(1, arity, 0xFFFFFFFFu, 0, t0, B, P.n_out[0]);
+        return pairs ? x.hash_level(L0, l0)                                                                           // new_pairs (:380-388, 392-414)
+                     : x.copy_ragged(L0, l0);                                                                         // new: the leaves are level 0
+    }));
+    base[0] = l0; lens = std::move(P.lens); at = std::move(P.at);
     return 0;
 }
 

@@ -4,7 +4,7 @@
 //
 // Every per-round step is ONE operation for the whole batch, whatever B:
 //   * the Merkle commits (MerkleCommitment: arity 16, label per witness, commitment/src/lib.rs:85-90) run one DS level of all B trees per
-//     launch (DsBatchStream); the top level writes the B roots straight into their slots of the value pool;
+//     launch (merkle_climb / merkle_climb_ragged, merkle_batch.hpp); the top level writes the B roots straight into their slots of the value pool;
 //   * the round coefficients write c0, c1 (and at round 0 the claim 2 c0 + c1) into the pool, the fold reads r_i from it;
 //   * the Fiat-Shamir transcripts are B device-resident transcripts advanced by one launch (TrBatchStream): the host lays out once what
 //     every instance absorbs as pool indices (labels, round indices, tags: constants; roots, c0, c1, claims, openings: value slots the
@@ -24,6 +24,7 @@
 #include "host_util.hpp"
 #include "poseidon_streams.hpp"
 #include "fri_plan.hpp"
+#include "merkle_batch.hpp"
 
 namespace stark {
 
@@ -89,8 +90,8 @@ struct ScSeg {                                                          // the a
 
 // An executor X is an arena (alloc / upload / put / download: DevArena in ctx.hpp on the GPU, HostArena in hostcheck.cpp; pointers are its own
 // memory) plus:
-//   int32_t ds_level(const DsBatchStream& D, fr_t* out)        one Merkle level of all trees (MerkleCommitment's parameters)
-//   int32_t ragged_level(const DsRaggedStream& D, fr_t* out)   one Merkle level of trees of different lengths (the witnesses' commit)
+//   template <class DS> int32_t hash_level(const DS& D, fr_t* out)   one Merkle level of all trees (MerkleCommitment's parameters): DsBatchStream,
+//           or DsRaggedStream for trees of different lengths (the witnesses' commit)
 //   int32_t coeffs(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, fr_t* c01, fr_t* claim, size_t claim_from)
 //           c01[2b], c01[2b+1] = (c0, c1) of layer b (ptrs[b] or layers + b len); claim != nullptr: claim[b] = 2 c0 + c1 for b >= claim_from
 //   int32_t fold(const fr_t* const* ptrs, const fr_t* layers, size_t len, size_t B, const fr_t* r, fr_t* next)   next + b len/2 with r[b]
@@ -154,53 +155,48 @@ template <class X> struct ScBatch {
         std::vector<size_t> lens; std::vector<const fr_t*> lv;
         const fr_t* addr(size_t level, size_t i) const { return lv[level] + i; }
     };
+    static constexpr size_t kArity = 16;                                   // MerkleCommitment's (commitment/src/lib.rs:85-90)
+    // The executor the climbs see (merkle_batch.hpp): X's memory and hashes, the segment tables through put().
+    struct Levels {
+        ScBatch& s;
+        int32_t level_block(size_t n_fr, fr_t** out) { return s.alloc_fr(n_fr, out); }
+        template <class DS> int32_t hash_level(const DS& D, fr_t* out) { return s.x.hash_level(D, out); }
+        int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** o) { DsRaggedStream::Seg* d = nullptr; SC_TRY(s.put(h, &d)); *o = d; return 0; }
+    };
     // MerkleProver::commit_vector of the layers of the first `A` instances, all of `len` elements, at layers + b len or behind a pointer table
-    // (ptrs_x in X's memory, ptrs_host its host copy) (merkle_build_on: level 0, positions from 0); roots[b] = root of tree b.  One DS level of all
-    // trees per launch.
+    // (ptrs_x in X's memory, ptrs_host its host copy), read in place as level 0; roots[b] = root of tree b: the top level is the root slots (never
+    // opened), and the root of a one-leaf tree, its leaf, comes by a gather.
     int32_t commit_layers(const fr_t* const* ptrs_x, const fr_t* const* ptrs_host, const fr_t* layers, size_t len, size_t A_, fr_t* roots, std::vector<Tree>& T) {
         T.assign(A_, Tree());
-        for (size_t b = 0; b < A_; ++b) { T[b].lens.assign(1, len); T[b].lv.assign(1, ptrs_host ? ptrs_host[b] : layers + b * len); }
-        if (len == 1) { std::vector<const fr_t*> a(A_); for (size_t b = 0; b < A_; ++b) a[b] = T[b].addr(0, 0); return gather(a, roots); }
-        const fr_t* const* in_ptrs = ptrs_x; const fr_t* in = layers; uint32_t level = 0;
-        while (len > 1) {
-            const size_t nn = (len + 15) / 16;
-            fr_t* dst = roots; if (nn > 1) SC_TRY(alloc_fr(A_ * nn, &dst));
-            SC_TRY(x.ds_level(DsBatchStream::make(16, level, 0, labels_x, in_ptrs, in, len, A_), dst));
-            for (size_t b = 0; b < A_; ++b) { T[b].lens.push_back(nn); T[b].lv.push_back(dst + b * nn); }   // the top level is the root slots (never opened)
-            in_ptrs = nullptr; in = dst; len = nn; ++level;
+        if (len == 1) {
+            std::vector<const fr_t*> a(A_);
+            for (size_t b = 0; b < A_; ++b) { T[b].lens.assign(1, 1); T[b].lv.assign(1, ptrs_host ? ptrs_host[b] : layers + b); a[b] = T[b].lv[0]; }
+            return gather(a, roots);
+        }
+        Levels xl{*this}; std::vector<size_t> lens; std::vector<fr_t*> base;
+        SC_TRY(merkle_climb(xl, kArity, A_, labels_x, ptrs_x, layers, len, roots, lens, base));
+        for (size_t b = 0; b < A_; ++b) {
+            T[b].lens = lens; T[b].lv.assign(1, ptrs_host ? ptrs_host[b] : layers + b * len);
+            for (size_t v = 1; v < lens.size(); ++v) T[b].lv.push_back(base[v] + b * lens[v]);
         }
         return 0;
     }
-    // The same of all B witnesses, tree b of 2^ks[b] leaves: the level loop of merkle_build_mixed_batch (merkle_batch.hpp) over DsRaggedStream, level v
-    // one launch over the trees that have it — a prefix, the trees being ordered by size.  The top level (the largest trees' roots) is written
-    // straight into the root slots; the roots of the trees that end below it, and of the one-leaf trees, follow with one gather.  Witnesses of ONE size
-    // take the same-shape stream (a division finds the tree of a hash where the ragged stream searches its table: measured).
+    // The same of all B witnesses, tree b of 2^ks[b] leaves, read in place: merkle_climb_ragged, level v one launch over the trees that have it — a
+    // prefix, the trees being ordered by size.  The top level (the largest trees' roots) is written straight into the root slots; the roots of the
+    // trees that end below it, and of the one-leaf trees, follow with one gather.  Witnesses of ONE size take the same-shape stream (a division finds
+    // the tree of a hash where the ragged stream searches its table: measured).
     int32_t commit_witnesses(fr_t* roots, std::vector<Tree>& W) {
         if (B && ks.front() == ks.back()) return commit_layers(wit_x, wit_s.data(), nullptr, (size_t)1 << ks[0], B, roots, W);
-        W.assign(B, Tree()); size_t depth = 0;
+        std::vector<size_t> n(B); for (size_t b = 0; b < B; ++b) n[b] = (size_t)1 << ks[b];
+        MerkleRaggedPlan P = merkle_ragged_plan(kArity, B, n.data(), labels_s.data(), false);
+        Levels xl{*this}; std::vector<fr_t*> base;
+        SC_TRY(merkle_climb_ragged(xl, P, wit_s.data(), roots, base, [](const DsRaggedStream::Seg*) { return 0; }));
+        W.assign(B, Tree()); std::vector<const fr_t*> a; size_t first = 0;
         for (size_t b = 0; b < B; ++b) {
-            Tree& t = W[b]; t.lens.assign(1, (size_t)1 << ks[b]);
-            while (t.lens.back() > 1) t.lens.push_back((t.lens.back() + 15) / 16);
-            t.lv.assign(t.lens.size(), nullptr); t.lv[0] = wit_s[b]; depth = std::max(depth, t.lens.size());
+            W[b].lens = P.lens[b]; W[b].lv.assign(1, wit_s[b]);
+            for (size_t v = 1; v < P.lens[b].size(); ++v) W[b].lv.push_back(base[v] + P.at[b][v]);
+            if (P.depth > 1 && P.lens[b].size() == P.depth) first = b + 1; else a.push_back(W[b].lv.back());
         }
-        std::vector<size_t> P(depth, 0), block(depth, 0);
-        for (size_t v = 1; v < depth; ++v) for (size_t b = 0; b < B && W[b].lens.size() > v; ++b) { ++P[v]; block[v] += W[b].lens[v]; }
-        std::vector<fr_t*> base(depth, nullptr);
-        for (size_t v = 1; v < depth; ++v) {
-            if (v + 1 == depth) base[v] = roots; else SC_TRY(alloc_fr(block[v], &base[v]));
-            size_t o = 0; for (size_t b = 0; b < P[v]; ++b) { W[b].lv[v] = base[v] + o; o += W[b].lens[v]; }
-        }
-        if (depth > 1) {
-            std::vector<DsRaggedTable> T(depth); std::vector<DsRaggedStream::Seg> all; std::vector<size_t> t0(depth, 0);
-            for (size_t v = 1; v < depth; ++v) {
-                for (size_t b = 0; b < P[v]; ++b) T[v].add(0, 16, W[b].lv[v - 1], nullptr, W[b].lens[v - 1], labels_s[b]);
-                t0[v] = all.size(); all.insert(all.end(), T[v].segs.begin(), T[v].segs.end());
-            }
-            DsRaggedStream::Seg* sx = nullptr; SC_TRY(put(all, &sx));
-            for (size_t v = 1; v < depth; ++v) SC_TRY(x.ragged_level(DsRaggedStream::make(0, 16, (uint32_t)(v - 1), 0, sx + t0[v], P[v], block[v]), base[v]));
-        }
-        const size_t first = depth > 1 ? P[depth - 1] : 0;
-        std::vector<const fr_t*> a; for (size_t b = first; b < B; ++b) a.push_back(W[b].lv.back());
         return gather(a, roots + first);
     }
     TrBatchStream stream(fr_t* state, uint32_t* pos, size_t inst0, const uint32_t* inst, size_t n_active, size_t nseg, const uint32_t* el_off, const uint32_t* idx,
@@ -362,9 +358,9 @@ template <class X> struct ScBatch {
                     M.next_indices.assign(qs[b].begin(), qs[b].end());
                     AddrSource src_b(&cur[b], &nxt[b], addr);
                     for (size_t ix : M.cur_indices) addr.push_back(cur[b].addr(0, ix));
-                    if (merkle_open_from(src_b, 0, cur[b].lens, 16, M.cur_indices, M.cur_proof)) return -1;
+                    if (merkle_open_from(src_b, 0, cur[b].lens, kArity, M.cur_indices, M.cur_proof)) return -1;
                     for (size_t ix : M.next_indices) addr.push_back(nxt[b].addr(0, ix));
-                    if (merkle_open_from(src_b, 1, nxt[b].lens, 16, M.next_indices, M.next_proof)) return -1;
+                    if (merkle_open_from(src_b, 1, nxt[b].lens, kArity, M.next_indices, M.next_proof)) return -1;
                 }
                 O.n = addr.size();
                 midx.clear(); moff.assign(1, 0); ScConsts C2((uint32_t)O.n, TrBatchStream::kPool1);
