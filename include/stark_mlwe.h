@@ -98,6 +98,9 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  * Changing an option synchronises the stream and drops the cached NTT plans. */
 int32_t stark_ctx_set_option(stark_ctx_t* ctx, const char* key, int64_t value);
 size_t  stark_ctx_cached_bytes(stark_ctx_t* ctx);
+/* The text of the context's last error.  One kind of SUCCESSFUL call also writes here: an NTT / LDE call that could not allocate one of its optional
+ * direct tables returns STARK_OK, runs on the two-level lookup, and leaves a note that starts with "optional NTT table " (it replaces an older error
+ * text).  Read the text right after the call whose status it explains. */
 const char* stark_last_error(stark_ctx_t* ctx);
 int32_t stark_malloc(stark_ctx_t* ctx, size_t bytes, void** dptr);
 int32_t stark_free(stark_ctx_t* ctx, void* dptr);
@@ -106,6 +109,21 @@ int32_t stark_memcpy_d2h(stark_ctx_t* ctx, void* dst_host, const void* src_dev, 
 /* Diagnostic: lane-level v_mad_u64_u32 (32x32+64 multiply-accumulate) issue rate of this device, measured live with every
  * SIMD saturated — the roofline `peak` of the integer-VALU-bound Poseidon kernels (bench.py "poseidon.roofline"). */
 int32_t stark_diag_mac_rate(stark_ctx_t* ctx, double* lane_macs_per_s);
+/* Diagnostic, FOR TESTS ONLY: refuse one device allocation of the library's own, so that the error paths behind every allocation can be run
+ * without exhausting a device.  An allocation REQUEST is every request for a pooled block (temporaries, layers, tree levels: served from the
+ * context's cache or by hipMalloc) and every allocation of a long-lived table (NTT plans and their tables, parameter sets, transcript frames, the
+ * NTT scratch vector); stark_malloc is the caller's own and is not counted.
+ *   mode 1: requests are counted from 1 and request number nth fails as a real out-of-memory condition does (the call returns STARK_ERR_OOM with
+ *           every output handle NULL, or degrades where a table is optional); nth = 0 counts without refusing.
+ *   mode 2: the requests the cache could not serve are counted, and for number nth the FIRST hipMalloc attempt is refused: the library hands its
+ *           cached blocks back to the driver, tries again and the call succeeds.
+ *   mode 3: as mode 2 with the second attempt refused as well: the cached blocks are handed back and the request still fails (STARK_ERR_OOM).
+ *   mode 0: off, the default (counting stops).   mode -1: read the numbers, change nothing.
+ * A hook that fired disarms itself and goes on counting.  stats (NULL, or FIVE words) receives, BEFORE the new mode is applied: the requests counted
+ * since the last arming, the refusals fired since then, the pooled blocks currently held by handles and calls, their bytes, and the cached bytes the
+ * library's accounting showed right after its last hand-back of the cache since the arming (all ones: none happened).  Neither
+ * synchronises nor drops the NTT plans (stark_ctx_set_option does both). */
+int32_t stark_diag_alloc_refusal(stark_ctx_t* ctx, int32_t mode, uint64_t nth, uint64_t* stats);
 /* HIP-event timing on the context's stream (bench.py measures kernels with these). */
 int32_t stark_timer_start(stark_ctx_t* ctx);
 int32_t stark_timer_stop_ms(stark_ctx_t* ctx, float* ms);

@@ -39,6 +39,7 @@ SIGNATURES = {
     "stark_memcpy_h2d": (i32, [vp, vp, vp, sz]),
     "stark_memcpy_d2h": (i32, [vp, vp, vp, sz]),
     "stark_diag_mac_rate": (i32, [vp, C.POINTER(C.c_double)]),
+    "stark_diag_alloc_refusal": (i32, [vp, i32, C.c_uint64, C.POINTER(C.c_uint64)]),
     "stark_timer_start": (i32, [vp]),
     "stark_timer_stop_ms": (i32, [vp, C.POINTER(C.c_float)]),
     "stark_poseidon_params_upload": (i32, [vp, i32, i32, i32, vp, vp, vp, vpp]),

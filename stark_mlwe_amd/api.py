@@ -330,6 +330,19 @@ class Context:
         """Return the context's cached device blocks to the driver."""
         self._chk(self.lib.stark_ctx_trim(self.h))
 
+    def cached_bytes(self):
+        return int(self.lib.stark_ctx_cached_bytes(self.h))
+
+    def diag_alloc_refusal(self, mode=-1, nth=0):
+        """TESTS ONLY (stark_diag_alloc_refusal).  mode 1: the nth allocation request of the library from here on fails as out of memory (nth = 0: count
+        only); mode 2: the first hipMalloc attempt of the nth request the pool cannot serve fails, so the pool gives its cached blocks back and retries;
+        mode 3: both attempts of that request fail (the give-back runs and the call still fails); mode 0: off; mode -1: read only.  -> (requests counted
+        since the last arming, refusals fired, live pooled blocks, live pooled bytes, cached bytes right after the last give-back or 2^64 - 1), read
+        BEFORE the new mode is applied."""
+        st = (C.c_uint64 * 5)()
+        self._chk(self.lib.stark_diag_alloc_refusal(self.h, mode, nth, st))
+        return tuple(int(x) for x in st)
+
     # ---- constants ------------------------------------------------------------------------------
     def poseidon_params_for_width(self, t):
         if t not in self._mparams:

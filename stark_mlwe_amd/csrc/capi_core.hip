@@ -21,7 +21,7 @@ static int32_t pool_poison_fill(stark_ctx* ctx, void* p, size_t bytes) {
 int32_t ctx_scratch(stark_ctx* ctx, size_t bytes, void** out) {
     if (bytes > ctx->scratch_bytes) {
         if (ctx->scratch) STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->scratch_bytes = 0; STARK_HIP(ctx, ctx->scratch.alloc(bytes)); ctx->scratch_bytes = bytes;      // alloc frees the smaller block first
+        ctx->scratch_bytes = 0; STARK_HIP(ctx, ctx->scratch.alloc(ctx, bytes)); ctx->scratch_bytes = bytes;      // alloc frees the smaller block first
     }
     if (ctx->opt.pool_poison >= 0 && ctx->scratch_bytes) STARK_TRY(pool_poison_fill(ctx, ctx->scratch.p, ctx->scratch_bytes));
     *out = ctx->scratch.p; return STARK_OK;
@@ -49,22 +49,41 @@ static inline size_t pool_round(size_t bytes) {
     if (bytes <= (1u << 20)) { size_t r = 256; while (r < bytes) r <<= 1; return r; }       // small: powers of two
     return (bytes + (1u << 20) - 1) & ~(size_t)((1u << 20) - 1);                             // large: whole MiB (layer / level sizes repeat exactly)
 }
+// The refusal hook (TESTS ONLY, stark_ctx::alloc_hook; called only while it is on).  `counted`: this event is one the current mode counts.
+// True: the event is the armed one and is refused; the hook disarms itself and goes on counting.
+static bool alloc_hook_fires(stark_ctx* ctx, bool counted) {
+    stark_ctx::AllocHook& h = ctx->alloc_hook;
+    if (!counted || ++h.requests != h.at) return false;
+    h.at = 0; ++h.fired; return true;
+}
+hipError_t dev_malloc(stark_ctx* ctx, void** out, size_t bytes, DevMallocKind kind) {
+    *out = nullptr;
+    if (ctx->alloc_hook.mode) {
+        stark_ctx::AllocHook& h = ctx->alloc_hook;
+        if (kind == kDevPoolRetry) { if (h.refuse_retry) { h.refuse_retry = false; return hipErrorOutOfMemory; } }      // mode 3: the second attempt of the refused miss
+        else if (alloc_hook_fires(ctx, h.mode == 1 ? kind == kDevTable : kind == kDevPoolFirst)) { h.refuse_retry = h.mode == 3; return hipErrorOutOfMemory; }
+    }
+    const hipError_t e = hipMalloc(out, bytes);
+    if (e != hipSuccess) { *out = nullptr; (void)hipGetLastError(); }      // nothing stays behind for the hipGetLastError of a later launch
+    return e;
+}
 int32_t ctx_alloc(stark_ctx* ctx, size_t bytes, void** out) {
     const size_t sz = pool_round(bytes);
+    // a refused request fails as the second attempt below does, without the give-back (which synchronises the stream: the refusal is also used behind a busy one)
+    if (ctx->alloc_hook.mode == 1 && alloc_hook_fires(ctx, true)) return ctx->fail(STARK_ERR_OOM, "device allocation of " + std::to_string(sz) + " bytes failed");
     auto it = ctx->pool_free.find(sz);
     if (it != ctx->pool_free.end() && !it->second.empty()) {
         void* p = it->second.back(); it->second.pop_back(); ctx->pool_cached_bytes -= sz;
         ctx->pool_live[p] = sz; *out = p;
         return ctx->opt.pool_poison >= 0 ? pool_poison_fill(ctx, p, sz) : STARK_OK;       // the whole rounded block, not only `bytes`
     }
-    void* p = nullptr; hipError_t e = hipMalloc(&p, sz);
+    void* p = nullptr; hipError_t e = dev_malloc(ctx, &p, sz, kDevPoolFirst);
     if (e != hipSuccess) {                                       // out of memory: give the cached blocks back and retry once
-        (void)hipGetLastError();
         (void)hipStreamSynchronize(ctx->stream);
-        for (auto& kv : ctx->pool_free) { for (void* q : kv.second) (void)hipFree(q); kv.second.clear(); }
-        ctx->pool_cached_bytes = 0;
-        e = hipMalloc(&p, sz);
-        if (e != hipSuccess) { (void)hipGetLastError(); return ctx->fail(STARK_ERR_OOM, "device allocation of " + std::to_string(sz) + " bytes failed"); }
+        for (auto& kv : ctx->pool_free) { for (void* q : kv.second) { (void)hipFree(q); ctx->pool_cached_bytes -= kv.first; } kv.second.clear(); }
+        if (ctx->alloc_hook.mode) ctx->alloc_hook.cached_after_give_back = ctx->pool_cached_bytes;       // the accounting's own result: 0 when every cached block was counted once
+        e = dev_malloc(ctx, &p, sz, kDevPoolRetry);
+        if (e != hipSuccess) return ctx->fail(STARK_ERR_OOM, "device allocation of " + std::to_string(sz) + " bytes failed");
     }
     ctx->pool_live[p] = sz; *out = p;
     return ctx->opt.pool_poison >= 0 ? pool_poison_fill(ctx, p, sz) : STARK_OK;
@@ -319,6 +338,21 @@ int32_t stark_diag_mac_rate(stark_ctx_t* ctx, double* lane_macs_per_s) {
     STARK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream)); STARK_HIP(ctx, hipEventSynchronize(ctx->ev1));
     float ms = 0; STARK_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     *lane_macs_per_s = (double)blocks * threads * 8.0 * STARK_DIAG_ITERS / (ms * 1e-3);
+    return STARK_OK;
+}
+
+// TESTS ONLY: the allocation-refusal hook (stark_ctx::alloc_hook).  stats (optional) first receives requests counted since the last arming, refusals
+// fired since then, live pooled blocks, live pooled bytes, the cached bytes right after the last give-back (~0: none yet); then mode 1 / 2 / 3 arm the hook for event number nth (0: count only), 0 disarms and stops
+// counting, -1 leaves the hook as it is (a read).  Touches neither the stream nor the NTT plans.
+int32_t stark_diag_alloc_refusal(stark_ctx_t* ctx, int32_t mode, uint64_t nth, uint64_t* stats) {
+    if (!ctx) return STARK_ERR_INVALID_ARG;
+    if (mode < -1 || mode > 3) return ctx->fail(STARK_ERR_INVALID_ARG, "alloc refusal mode: -1 (read), 0 (off), 1 (refuse request nth), 2 (refuse the first attempt of pool miss nth), 3 (refuse both attempts of pool miss nth)");
+    if (stats) {
+        stats[0] = ctx->alloc_hook.requests; stats[1] = ctx->alloc_hook.fired; stats[2] = ctx->pool_live.size(); stats[3] = 0;
+        for (const auto& kv : ctx->pool_live) stats[3] += kv.second;
+        stats[4] = ctx->alloc_hook.cached_after_give_back;
+    }
+    if (mode >= 0) { ctx->alloc_hook = stark_ctx::AllocHook(); ctx->alloc_hook.mode = mode; ctx->alloc_hook.at = mode ? nth : 0; }
     return STARK_OK;
 }
 

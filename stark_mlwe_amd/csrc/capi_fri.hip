@@ -132,7 +132,7 @@ static int32_t fri_build_impl(stark_ctx* ctx, const fr_t* f0_dev, size_t n0, con
     S->f.resize(L + 1);
     for (size_t l = 0; l <= L; ++l) STARK_TRY(S->f[l].take(ctx, S->n[l] * sizeof(fr_t)));
     if (hipMemcpyAsync(S->f[0].p, f0_dev, n0 * sizeof(fr_t), hipMemcpyDeviceToDevice, main_stream) != hipSuccess) return ctx->fail(STARK_ERR_HIP, "copy f0");
-    DevBuf zp; if (L && zp.alloc(ctx, zp_total * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "z powers");
+    DevBuf zp; if (L && zp.alloc(ctx, zp_total * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "z powers: " + ctx->err);
     { size_t off = 0;
       for (size_t l = 0; l < L; ++l) {
           STARK_TRY(zpows_launch(ctx, main_stream, S->z[l], schedule[l], zp.fr() + off));
@@ -468,7 +468,7 @@ struct PassCommit {
         if (Bp == 1) {
             DevBuf merged; const fr_t* f = f0 ? as_fr(f0[0]) : nullptr;
             if (!f) {
-                if (merged.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "f0");
+                if (merged.alloc(ctx, n0 * sizeof(fr_t)) != hipSuccess) return ctx->fail(STARK_ERR_OOM, "f0: " + ctx->err);
                 STARK_TRY(ali_merge_dev_impl(ctx, as_fr(cols[0][0]), as_fr(cols[1][0]), as_fr(cols[2][0]), as_fr(cols[3][0]), nullptr, host::h_zero(), omega, zs[0], n0, merged.fr(), nullptr));
                 f = merged.fr();
             }

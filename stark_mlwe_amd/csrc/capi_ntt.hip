@@ -61,6 +61,12 @@ struct DevWord {
     int32_t set(stark_ctx* ctx, const fr_t& v) { STARK_HIP(ctx, dev.alloc(ctx, sizeof(fr_t))); return ctx_upload_staged(ctx, dev.p, &v, sizeof(fr_t)); }
 };
 
+// THE optional allocations of the library: the direct tables of a plan (get_plan: tw_direct[i]) and of its coset (build_coset: small, tw_direct,
+// direct).  One that cannot be had does not fail the transform — the pass kernels fall back to the two-level lookup — and leaves this note, not
+// an error, where stark_last_error reads: the call still returns STARK_OK.  Every other allocation of the library fails its call.
+static void optional_table_note(stark_ctx* ctx, const char* which, int log_n) {
+    ctx->err = std::string("optional NTT table ") + which + " of 2^" + std::to_string(log_n) + " points not allocated: the transform uses the two-level lookup";
+}
 template <class F>
 static int32_t get_plan(stark_ctx* ctx, int log_n, bool inverse, NttPlan** out) {
     uint64_t key = ((uint64_t)F::ID << 40) | ((uint64_t)log_n << 8) | (inverse ? 1 : 0);
@@ -78,7 +84,7 @@ static int32_t get_plan(stark_ctx* ctx, int log_n, bool inverse, NttPlan** out) 
     if (ntt_direct_max(ctx) >= log_n) {       // direct twiddle tables: 2^log_m entries per strided pass
         int rem = log_n;
         for (int i = 0; i + 1 < p->P; ++i) {
-            if (p->tw_direct[i].alloc(((size_t)1 << rem) * sizeof(fr_t)) != hipSuccess) { (void)hipGetLastError(); break; }   // no memory: keep the two-level lookup
+            if (p->tw_direct[i].alloc(ctx, ((size_t)1 << rem) * sizeof(fr_t)) != hipSuccess) { optional_table_note(ctx, i ? "plan.tw_direct[1]" : "plan.tw_direct[0]", log_n); break; }   // no memory: keep the two-level lookup
             hipLaunchKernelGGL(k_fill_tw_direct<F>, dim3((unsigned)((((uint64_t)1 << rem) + 255) / 256)), dim3(256), 0, ctx->stream, p->root.view(), log_n, rem, p->log_b[i], p->tw_direct[i].fr());
             rem -= p->log_b[i];
         }
@@ -132,7 +138,7 @@ template <class F> static int32_t plain_table(stark_ctx* ctx, NttPlan* big, cons
 // current coset whole; a plain table of g that a failed build already put into plain_tabs stays there, valid under its own key).  The pre-scale
 // of a forward plan takes the first form that can be had: merged into the first pass's twiddle table (option ntt_merged_coset, and
 // tw_direct[0] exists), else one direct table, else the two-level lookup.  An optional table that cannot be allocated
-// clears the HIP error and degrades; it never fails the transform.  The price of building beside the current coset: its tables (up to two of
+// degrades (dev_malloc leaves no runtime error behind); it never fails the transform.  The price of building beside the current coset: its tables (up to two of
 // 2^log_n entries) are still allocated meanwhile, so close to the device's memory limit an optional table that used to fit may degrade, and
 // that form then stays until the coset next changes.
 template <class F>
@@ -146,16 +152,20 @@ static int32_t build_coset(stark_ctx* ctx, NttPlan* p, const fr_t& g, NttCoset& 
         // merged tables: the pre-scale's g^rest goes into the first pass's twiddle table, what is left is (g^S)^p by point index
         PowTable gplain; STARK_TRY(plain_table<F>(ctx, p, g, &gplain));
         const int lb0 = p->log_b[0], ls = log_n - lb0;
-        if (C.small.alloc(((size_t)1 << lb0) * sizeof(fr_t)) == hipSuccess && C.tw_direct.alloc(((size_t)1 << log_n) * sizeof(fr_t)) == hipSuccess) {
+        if (C.small.alloc(ctx, ((size_t)1 << lb0) * sizeof(fr_t)) != hipSuccess) optional_table_note(ctx, "coset.small", log_n);
+        else if (C.tw_direct.alloc(ctx, ((size_t)1 << log_n) * sizeof(fr_t)) != hipSuccess) optional_table_note(ctx, "coset.tw_direct", log_n);
+        else {
             hipLaunchKernelGGL(k_fill_coset_merged<F>, dim3((unsigned)((((uint64_t)1 << log_n) + 255) / 256)), dim3(256), 0, ctx->stream, C.tab.view(), gplain, (const fr_t*)p->tw_direct[0].fr(), ls, lb0, C.small.fr(), C.tw_direct.fr());
             merged = hipGetLastError() == hipSuccess;
         }
-        if (!merged) { (void)hipGetLastError(); C.small.reset(); C.tw_direct.reset(); }
+        if (!merged) { C.small.reset(); C.tw_direct.reset(); }
     }
     if (!merged) {
-        if (!inverse && ntt_direct_max(ctx) >= log_n && C.direct.alloc(((size_t)1 << log_n) * sizeof(fr_t)) == hipSuccess)
-            hipLaunchKernelGGL(k_fill_pow_direct<F>, dim3((unsigned)((((uint64_t)1 << log_n) + 255) / 256)), dim3(256), 0, ctx->stream, C.tab.view(), 1ull << log_n, C.direct.fr());
-        else (void)hipGetLastError();
+        if (!inverse && ntt_direct_max(ctx) >= log_n) {
+            if (C.direct.alloc(ctx, ((size_t)1 << log_n) * sizeof(fr_t)) == hipSuccess)
+                hipLaunchKernelGGL(k_fill_pow_direct<F>, dim3((unsigned)((((uint64_t)1 << log_n) + 255) / 256)), dim3(256), 0, ctx->stream, C.tab.view(), 1ull << log_n, C.direct.fr());
+            else optional_table_note(ctx, "coset.direct", log_n);
+        }
     }
     return STARK_OK;
 }

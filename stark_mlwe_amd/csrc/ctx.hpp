@@ -32,7 +32,13 @@ struct CtxRef {
 };
 
 namespace stark {
-// Owner of ONE unpooled device allocation (hipMalloc on alloc, hipFree on reset / destruction; move-only): the long-lived tables and constants.
+// THE device allocation of the library proper (capi_core.hip): hipMalloc for the unpooled tables (DevMem::alloc, a request of its own) and for the two
+// attempts of a pool miss (ctx_alloc, which counts its request itself).  A failure leaves *out NULL and the runtime's last error CLEARED: the
+// launches are checked with hipGetLastError, which reports the last error any earlier call on the thread returned, so an out-of-memory status left
+// behind would be reported by the next, innocent call.  The refusal hook (stark_ctx::alloc_hook) lives here.
+enum DevMallocKind { kDevTable, kDevPoolFirst, kDevPoolRetry };
+hipError_t dev_malloc(stark_ctx* ctx, void** out, size_t bytes, DevMallocKind kind);
+// Owner of ONE unpooled device allocation (dev_malloc on alloc, hipFree on reset / destruction; move-only): the long-lived tables and constants.
 // They stay outside the context's pool, so stark_ctx_trim and the out-of-memory retry of ctx_alloc never touch them.  An owner is destroyed
 // with its context's device current (see ctx_teardown); DevBuf below is the pooled, per-call counterpart.
 struct DevMem {
@@ -41,7 +47,7 @@ struct DevMem {
     DevMem(DevMem&& o) noexcept : p(o.p) { o.p = nullptr; }
     DevMem& operator=(DevMem&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
     ~DevMem() { reset(); }
-    hipError_t alloc(size_t bytes) { reset(); const hipError_t e = hipMalloc(&p, bytes); if (e != hipSuccess) p = nullptr; return e; }
+    hipError_t alloc(stark_ctx* ctx, size_t bytes) { reset(); return dev_malloc(ctx, &p, bytes, kDevTable); }
     // THE one-off fill of a long-lived table: alloc(bytes), the copy from host memory on the context's stream, and the synchronisation right behind it
     // (src may die on return).  The static form copies into device memory somebody else owns.  Defined below stark_ctx.
     int32_t fill_sync(stark_ctx* ctx, const void* src, size_t bytes);
@@ -126,6 +132,14 @@ struct stark_ctx {
         int pool_poison = -1;            // TESTS ONLY: 0..255 = ctx_alloc fills every block it hands out (the whole rounded block, recycled or fresh) and ctx_scratch the scratch vector
                                          // with this byte, so a read of a temporary nobody wrote shows; each fill synchronises the stream.  -1 = off (one branch per allocation, no HIP call)
     } opt;
+    // TESTS ONLY (stark_diag_alloc_refusal): refuses one chosen allocation request, so that the error paths behind every allocation can be run.
+    // mode 0 = off (one branch per request, no HIP call).  mode 1: requests are counted — every ctx_alloc call, pool hit or miss, and every
+    // DevMem::alloc — and request number `at` (from 1; 0 = count only) is refused as a failed allocation is: STARK_ERR_OOM from ctx_alloc,
+    // hipErrorOutOfMemory from DevMem::alloc.  mode 2: pool misses are counted and the FIRST hipMalloc attempt of miss number `at` is refused, so
+    // ctx_alloc gives its cached blocks back and tries again.  A hook that fired disarms itself (counting goes on).
+    // mode 3: as mode 2 with the SECOND attempt refused as well: the give-back runs and the request still fails, the last branch of a real failure.
+    // cached_after_give_back: pool_cached_bytes as the give-back's own accounting left it (~0 until a give-back ran while the hook was on).
+    struct AllocHook { int mode = 0; uint64_t at = 0, requests = 0, fired = 0, cached_after_give_back = ~(uint64_t)0; bool refuse_retry = false; } alloc_hook;
     bool side_commit = false;            // set while fri_build enqueues work that runs underneath the 2^n-leaf launch: Merkle levels and leaf layers of t = 9, 17 take the
                                          // wave-pair form (64 sponges per two waves) instead of one wave or five waves per sponge, which would hold many wave slots at lone-wave speed
 
@@ -184,7 +198,7 @@ namespace stark {
 inline int32_t DevMem::fill_sync(stark_ctx* ctx, void* dst, const void* src, size_t bytes) {
     STARK_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream)); return STARK_OK;
 }
-inline int32_t DevMem::fill_sync(stark_ctx* ctx, const void* src, size_t bytes) { STARK_HIP(ctx, alloc(bytes)); return fill_sync(ctx, p, src, bytes); }
+inline int32_t DevMem::fill_sync(stark_ctx* ctx, const void* src, size_t bytes) { STARK_HIP(ctx, alloc(ctx, bytes)); return fill_sync(ctx, p, src, bytes); }
 
 inline const fr_t* as_fr(const uint64_t* p) { return reinterpret_cast<const fr_t*>(p); }
 inline fr_t* as_fr(uint64_t* p) { return reinterpret_cast<fr_t*>(p); }

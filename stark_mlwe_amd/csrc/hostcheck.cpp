@@ -34,14 +34,21 @@ static void st4(uint64_t* p, const fr_t& x) { for (int i = 0; i < 4; ++i) p[i] =
 static int g_alloc_fill = 0;
 static std::vector<uint64_t> hc_block(size_t bytes) { std::vector<uint64_t> v((bytes + 7) / 8 + 1); memset(v.data(), g_alloc_fill, v.size() * sizeof(uint64_t)); return v; }
 static std::vector<fr_t> hc_fr_block(size_t n) { std::vector<fr_t> v(n); if (n) memset((void*)v.data(), g_alloc_fill, n * sizeof(fr_t)); return v; }
+// The refusal countdown of the host executors (hc_set_alloc_refuse_at; process-wide like the fill), the twin of the device allocator's hook
+// (stark_ctx::alloc_hook): allocation requests are counted from the arming, and request number g_refuse_at (0: none) fails with kHcOom, once.
+static const int32_t kHcOom = -4;                                        // STARK_ERR_OOM
+static uint64_t g_refuse_at = 0, g_alloc_requests = 0, g_alloc_refused = 0;
+static bool hc_alloc_refused() { if (++g_alloc_requests != g_refuse_at) return false; g_refuse_at = 0; ++g_alloc_refused; return true; }
+// what an export returns for a driver's status: the out-of-memory code as it is, -1 for everything else (as before)
+static int hc_rc(int32_t rc) { return rc == kHcOom ? (int)kHcOom : -1; }
 // THE memory of the host executors, the twin of DevArena (ctx.hpp): blocks of hc_block that live as long as it, upload and download = memcpy.
 struct HostArena {
     std::vector<std::vector<uint64_t>> mem;
-    int32_t alloc(size_t bytes, void** out) { mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
+    int32_t alloc(size_t bytes, void** out) { if (hc_alloc_refused()) { *out = nullptr; return kHcOom; } mem.push_back(hc_block(bytes)); *out = mem.back().data(); return 0; }
     int32_t upload(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
     template <class T> int32_t put(const std::vector<T>& h, T** out) {
-        void* p = nullptr; alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p);
-        if (!h.empty()) upload(p, h.data(), h.size() * sizeof(T));
+        void* p = nullptr; if (int32_t rc = alloc(std::max<size_t>(h.size(), 1) * sizeof(T), &p)) return rc;
+        if (!h.empty()) if (int32_t rc = upload(p, h.data(), h.size() * sizeof(T))) return rc;
         *out = (T*)p; return 0;
     }
     int32_t download(void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return 0; }
@@ -82,6 +89,11 @@ extern "C" {
 
 // The byte of every block the host executors allocate from here on (process-wide; 0 = the default).  Returns the previous one; -1: not a byte.
 int hc_set_alloc_fill(int byte) { if (byte < 0 || byte > 255) return -1; const int old = g_alloc_fill; g_alloc_fill = byte; return old; }
+// Arms the refusal countdown of the host executors: allocation request number n from here on (HostArena::alloc, put and the Merkle executor's level
+// blocks) fails with STARK_ERR_OOM, once; n = 0 disarms.  The counters restart either way.  hc_alloc_refusal_stats: requests counted and refusals
+// fired since the last call of this function.
+int hc_set_alloc_refuse_at(uint64_t n) { g_refuse_at = n; g_alloc_requests = 0; g_alloc_refused = 0; return 0; }
+int hc_alloc_refusal_stats(uint64_t* out2) { out2[0] = g_alloc_requests; out2[1] = g_alloc_refused; return 0; }
 // A block of `bytes` through the executors' allocation path, copied out: what a driver would read from a slot nothing wrote.
 int hc_alloc_probe(size_t bytes, uint8_t* out) { const std::vector<uint64_t> v = hc_block(bytes); memcpy(out, v.data(), bytes); return 0; }
 
@@ -1190,7 +1202,7 @@ static int hc_lag_block(size_t ncols, const uint64_t* const* cols, const LagBloc
     for (size_t p = 0; p < npoints; ++p) zs[p] = ld4(z + 4 * p);
     std::vector<fr_t> o = hc_fr_block(npoints * ncols);
     LagHostExec X;
-    if (lagrange_eval_batch(X, ncols, ptrs.data(), B, w, npoints, zs.data(), max_partials ? max_partials : kLagDefaultMaxPartials, col_groups, o.data(), passes)) return -1;
+    if (int32_t rc = lagrange_eval_batch(X, ncols, ptrs.data(), B, w, npoints, zs.data(), max_partials ? max_partials : kLagDefaultMaxPartials, col_groups, o.data(), passes)) return hc_rc(rc);
     for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
     return 0;
 }
@@ -1219,7 +1231,7 @@ int hc_lagrange_eval_from_partials(size_t nparts, const uint64_t* partials, size
     for (size_t i = 0; i < part.size(); ++i) part[i] = ld4(partials + 4 * i);
     for (size_t p = 0; p < npoints; ++p) zs[p] = ld4(z + 4 * p);
     LagHostExec X;
-    if (lagrange_combine(X, nparts, part.data(), ncols, n_global, npoints, zs.data(), o.data())) return -1;
+    if (int32_t rc = lagrange_combine(X, nparts, part.data(), ncols, n_global, npoints, zs.data(), o.data())) return hc_rc(rc);
     for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
     return 0;
 }
@@ -1243,17 +1255,20 @@ struct MerkleHostExec : HostArena {
     HcParams* p;
     explicit MerkleHostExec(HcParams* p_) : p(p_) {}
     int32_t level_block(size_t n_fr, fr_t** out) {                                   // a block that held something before: the fill of hc_set_alloc_fill, and never zeros
+        if (hc_alloc_refused()) { *out = nullptr; return kHcOom; }
         mem.emplace_back(4 * n_fr + 1, g_alloc_fill ? 0x0101010101010101ull * (uint64_t)g_alloc_fill : 0xA5A5A5A5A5A5A5A5ull); *out = (fr_t*)mem.back().data(); return 0;
     }
     int32_t tables(const uint64_t* l, const fr_t* const* leaves, const fr_t* const* cp, size_t B, const uint64_t** lx, const fr_t* const** vx, const fr_t* const** cx) {
         uint64_t* dl = nullptr; const fr_t** dv = nullptr; const fr_t** dc = nullptr;
-        put(std::vector<uint64_t>(l, l + B), &dl); put(std::vector<const fr_t*>(leaves, leaves + B), &dv); if (cp) put(std::vector<const fr_t*>(cp, cp + B), &dc);
+        if (int32_t rc = put(std::vector<uint64_t>(l, l + B), &dl)) return rc;
+        if (int32_t rc = put(std::vector<const fr_t*>(leaves, leaves + B), &dv)) return rc;
+        if (cp) if (int32_t rc = put(std::vector<const fr_t*>(cp, cp + B), &dc)) return rc;
         *lx = dl; *vx = dv; *cx = dc; return 0;
     }
     int32_t copy_rows(const fr_t* const* src, size_t n, size_t B, fr_t* dst) { for (size_t b = 0; b < B; ++b) for (size_t i = 0; i < n; ++i) dst[b * n + i] = src[b][i]; return 0; }
     template <class DS> int32_t hash_level(const DS& D, fr_t* out) { return hash_ds_stream(p, D, out); }
     // merkle_build_mixed_batch
-    int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x) { DsRaggedStream::Seg* d = nullptr; put(h, &d); *x = d; return 0; }
+    int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x) { DsRaggedStream::Seg* d = nullptr; if (int32_t rc = put(h, &d)) return rc; *x = d; return 0; }
     int32_t copy_ragged(const DsRaggedStream& D, fr_t* dst) { for (size_t i = 0; i < D.n_out; ++i) { const DsRaggedStream::Seg& S = D.segs[D.seg(i)]; dst[i] = S.in0[i - S.first]; } return 0; }
 };
 struct MerkleOpenHostExec { int32_t gather(const MerkleGatherList& G, fr_t* out) { for (size_t i = 0; i < G.size(); ++i) out[G.row_of(i)] = G.base[G.src[i]][G.index[i]]; return 0; } };
@@ -1273,7 +1288,7 @@ int hc_merkle_build_batch(void* params, size_t arity, size_t B, const uint64_t* 
         if (pairs && cp[b]) { cc[b].resize(n); for (size_t i = 0; i < n; ++i) cc[b][i] = ld4(cp[b] + 4 * i); cpp[b] = cc[b].data(); }
     }
     MerkleHostExec X(P); std::vector<size_t> lens; std::vector<fr_t*> base;
-    if (merkle_build_batch(X, arity, B, labels, lp.data(), n, pairs, pairs ? cpp.data() : nullptr, lens, base)) return -1;
+    if (int32_t rc = merkle_build_batch(X, arity, B, labels, lp.data(), n, pairs, pairs ? cpp.data() : nullptr, lens, base)) return hc_rc(rc);
     const std::vector<size_t> at = total_lens(lens, B);
     if (lens.size() > 64 || at.back() > cap_fr) return -1;
     for (size_t v = 0; v < lens.size(); ++v) { lens_out[v] = lens[v]; for (size_t i = 0; i < B * lens[v]; ++i) st4(out + 4 * (at[v] + i), base[v][i]); }
@@ -1309,7 +1324,7 @@ int hc_merkle_build_mixed_batch(void* params, size_t arity, size_t B, const uint
         if (pairs && cp[b]) { cc[b].resize(n[b]); for (size_t i = 0; i < n[b]; ++i) cc[b][i] = ld4(cp[b] + 4 * i); cpp[b] = cc[b].data(); }
     }
     MerkleHostExec X(P); std::vector<std::vector<size_t>> lens, at; std::vector<fr_t*> base;
-    if (merkle_build_mixed_batch(X, arity, B, labels, lp.data(), n, pairs, pairs ? cpp.data() : nullptr, lens, at, base)) return -1;
+    if (int32_t rc = merkle_build_mixed_batch(X, arity, B, labels, lp.data(), n, pairs, pairs ? cpp.data() : nullptr, lens, at, base)) return hc_rc(rc);
     std::vector<size_t> block(base.size(), 0);
     for (size_t b = 0; b < B; ++b) {
         if (lens[b].size() > 64) return -1;

@@ -16,7 +16,7 @@ struct DevPowTable {
     // and the fill is launched: a fill that fails leaves the table as it was.
     template <class F> int32_t fill(stark_ctx* ctx, const fr_t& g, const fr_t& c0, int lo_bits_, int hi_bits) {
         DevMem l, h;
-        STARK_HIP(ctx, l.alloc(((size_t)1 << lo_bits_) * sizeof(fr_t))); STARK_HIP(ctx, h.alloc(((size_t)1 << hi_bits) * sizeof(fr_t)));
+        STARK_HIP(ctx, l.alloc(ctx, ((size_t)1 << lo_bits_) * sizeof(fr_t))); STARK_HIP(ctx, h.alloc(ctx, ((size_t)1 << hi_bits) * sizeof(fr_t)));
         const uint64_t tot = (1ull << lo_bits_) + (1ull << hi_bits);
         hipLaunchKernelGGL(k_fill_pow_table<F>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ctx->stream, l.fr(), h.fr(), lo_bits_, hi_bits, g, c0);
         STARK_HIP(ctx, hipGetLastError());

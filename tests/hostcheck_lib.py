@@ -26,6 +26,14 @@ class HostCheck:
         """the byte every block of the host executors holds from here on (process-wide; 0 is the default) -> the previous one"""
         old = self.l.hc_set_alloc_fill(C.c_int(byte)); assert old >= 0, byte; return old
 
+    def set_alloc_refuse_at(self, n):
+        """arms the refusal countdown of the host executors: their n-th allocation request from here on fails with STARK_ERR_OOM, once (0: disarmed); the counters restart"""
+        assert self.l.hc_set_alloc_refuse_at(C.c_uint64(n)) == 0
+
+    def alloc_refusal_stats(self):
+        """-> (allocation requests counted, refusals fired) since the last set_alloc_refuse_at"""
+        out = (C.c_uint64 * 2)(); assert self.l.hc_alloc_refusal_stats(out) == 0; return int(out[0]), int(out[1])
+
     def alloc_probe(self, nbytes):
         """a block of the host executors' allocation path as a driver would first see it"""
         out = (C.c_uint8 * nbytes)(); assert self.l.hc_alloc_probe(C.c_size_t(nbytes), out) == 0; return bytes(out)

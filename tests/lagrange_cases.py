@@ -114,8 +114,8 @@ def third_power_domain(oracle, v):
     return oracle.pow(omega_of(oracle, n), 3), u
 
 
-def hc_eval(hostcheck, cols, n, zs, omega=None, max_partials=0):
-    """hc_lagrange_eval_batch: the driver of stark_lagrange_eval_on_h_batch_dev, every workgroup in lockstep on the host -> ((P, C, 4), passes).
+def hc_eval_rc(hostcheck, cols, n, zs, omega=None, max_partials=0):
+    """hc_lagrange_eval_batch: the driver of stark_lagrange_eval_on_h_batch_dev, every workgroup in lockstep on the host -> (rc, (P, C, 4), passes).
     A column object that repeats in `cols` is passed as a repeated pointer.  max_partials 0: the default."""
     f = hostcheck.l.hc_lagrange_eval_batch
     f.argtypes = [C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, C.POINTER(C.c_size_t)]; f.restype = C.c_int
@@ -126,8 +126,14 @@ def hc_eval(hostcheck, cols, n, zs, omega=None, max_partials=0):
     w = None if omega is None else np.ascontiguousarray(omega, dtype=np.uint64)
     out = np.full((npts, len(cols), 4), 0x5A5A5A5A5A5A5A5A, np.uint64); passes = C.c_size_t(99)
     rc = f(len(cols), ptrs, n, None if w is None else w.ctypes.data_as(vp), npts, z.ctypes.data_as(vp) if npts else None, max_partials, out.ctypes.data_as(vp), C.byref(passes))
+    return rc, out, passes.value
+
+
+def hc_eval(hostcheck, cols, n, zs, omega=None, max_partials=0):
+    """hc_eval_rc of a call that succeeds -> ((P, C, 4), passes)"""
+    rc, out, passes = hc_eval_rc(hostcheck, cols, n, zs, omega=omega, max_partials=max_partials)
     assert rc == 0, rc
-    return out, passes.value
+    return out, passes
 
 
 def hc_refused(hostcheck, n, omega):

@@ -13,6 +13,15 @@ import torch.multiprocessing as mp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def free_port():
+    """a rendezvous port the system just handed out on the loopback interface (a port worked out from the process id may be taken).  The port is
+    free again before the ranks bind it: a small window remains, far smaller than that of a fixed port"""
+    import socket
+    with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
 class CpuStandIn:
     """Provider with the same methods as dist.HipProvider, on CPU tensors, computing with the oracle
     (NTT) and the host-check build of the product's kernel body (Merkle level)."""
@@ -162,7 +171,7 @@ def _worker(rank, world, port, log_n, log_rows, inverse, q):
 def test_six_step_ntt_and_sharded_merkle_world2(log_n, log_rows, inverse):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29500 + (os.getpid() % 2000) + log_n * 3 + log_rows + (7 if inverse else 0)
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, log_n, log_rows, inverse, q)) for r in range(2)]
     for p in procs: p.start()
     res = [q.get(timeout=240) for _ in procs]
@@ -195,7 +204,7 @@ def test_sharded_prove_world2_matches_reference_bytes(log_n0, schedule, r, world
     """One trace block-sharded over 2 (and 4) ranks -> the SAME canonical proof bytes as the oracle's prove of the whole trace."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 31500 + (os.getpid() % 2000) + log_n0 + 10 * world
+    port = free_port()
     procs = [ctx.Process(target=_prove_worker, args=(r_, world, port, log_n0, schedule, r, q)) for r_ in range(world)]
     for p in procs: p.start()
     res = [q.get(timeout=400) for _ in procs]
@@ -242,7 +251,7 @@ def test_sharded_lde_and_chained_step_world2(log_n, log_rows, world):
     oracle's LDE of the whole column, and LDE -> merge -> sharded commit gives the oracle's roots for the whole trace."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 33500 + (os.getpid() % 2000) + log_n + 10 * world
+    port = free_port()
     procs = [ctx.Process(target=_lde_worker, args=(r_, world, port, log_n, log_rows, q)) for r_ in range(world)]
     for p in procs: p.start()
     res = [q.get(timeout=600) for _ in procs]

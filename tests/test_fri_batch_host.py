@@ -31,13 +31,19 @@ def tparams(hostcheck):
     hostcheck.params_free(h)
 
 
-def commit_batch(hostcheck, tparams, f0s, n0, sched, seed_z):
+def commit_batch_rc(hostcheck, tparams, f0s, n0, sched, seed_z):
+    """-> (the export's status, (B, L + 1, 4) roots)"""
     B, L = len(f0s), len(sched)
     fs = [np.ascontiguousarray(f, dtype=np.uint64) for f in f0s]
     tab = (vp * B)(*[ptr(f) for f in fs])
     sch = np.ascontiguousarray(sched, dtype=np.uint64)
     roots = np.zeros((B, L + 1, 4), np.uint64)
     rc = hostcheck.l.hc_fri_commit_batch(tparams, C.c_size_t(B), tab, C.c_size_t(n0), ptr(sch), C.c_size_t(L), C.c_uint64(seed_z), ptr(roots))
+    return rc, roots
+
+
+def commit_batch(hostcheck, tparams, f0s, n0, sched, seed_z):
+    rc, roots = commit_batch_rc(hostcheck, tparams, f0s, n0, sched, seed_z)
     assert rc == 0, rc
     return roots
 

@@ -30,8 +30,8 @@ def hc_params(hostcheck):
         hostcheck.params_free(h)
 
 
-def hc_build(hostcheck, params, arity, labels, cols, n, cps=None):
-    """-> (lens, [levels of tree b]) through hc_merkle_build_batch, or None when the shape is refused"""
+def hc_build_rc(hostcheck, params, arity, labels, cols, n, cps=None):
+    """-> (the export's return value, (lens, [levels of tree b]) or None when it is negative) through hc_merkle_build_batch"""
     B = len(cols); lens = np.zeros(64, np.uint64)
     tab = (vp * B)(*[c.ctypes.data for c in cols])
     ctab = None if cps is None else (vp * B)(*[None if c is None else c.ctypes.data for c in cps])
@@ -39,13 +39,18 @@ def hc_build(hostcheck, params, arity, labels, cols, n, cps=None):
     out = np.zeros((cap, 4), np.uint64); lab = np.ascontiguousarray(labels, dtype=np.uint64)
     nl = hostcheck.l.hc_merkle_build_batch(params, C.c_size_t(arity), C.c_size_t(B), P(lab), tab, C.c_size_t(n), 0 if cps is None else 1, ctab, P(out), C.c_size_t(cap), P(lens))
     if nl < 0:
-        return None
+        return nl, None
     lens = [int(x) for x in lens[:nl]]; trees = [[] for _ in range(B)]; at = 0
     for ln in lens:
         for b in range(B):
             trees[b].append(out[at + b * ln: at + (b + 1) * ln].copy())
         at += B * ln
-    return lens, trees
+    return nl, (lens, trees)
+
+
+def hc_build(hostcheck, params, arity, labels, cols, n, cps=None):
+    """-> (lens, [levels of tree b]) through hc_merkle_build_batch, or None when the shape is refused"""
+    return hc_build_rc(hostcheck, params, arity, labels, cols, n, cps)[1]
 
 
 def hc_open(hostcheck, arities, trees, index_lists):

@@ -34,8 +34,8 @@ def ragged_level(hostcheck, params, mode, arity, level, pos0, labels, ins, in1s=
     return out
 
 
-def hc_build_mixed(hostcheck, params, arity, labels, cols, cps=None):
-    """-> [levels of tree b] through hc_merkle_build_mixed_batch, or None when the shapes are refused"""
+def hc_build_mixed_rc(hostcheck, params, arity, labels, cols, cps=None):
+    """-> (the export's return value, [levels of tree b] or None when it is negative) through hc_merkle_build_mixed_batch"""
     B = len(cols); ns = np.array([c.shape[0] for c in cols], np.uint64)
     tab = (vp * B)(*[c.ctypes.data for c in cols])
     ctab = None if cps is None else (vp * B)(*[None if c is None else c.ctypes.data for c in cps])
@@ -44,14 +44,19 @@ def hc_build_mixed(hostcheck, params, arity, labels, cols, cps=None):
     nlev = np.zeros(B, np.uint64); lens = np.zeros(64 * B, np.uint64)
     depth = hostcheck.l.hc_merkle_build_mixed_batch(params, C.c_size_t(arity), C.c_size_t(B), P(lab), tab, P(ns), 0 if cps is None else 1, ctab, P(out), C.c_size_t(cap), P(nlev), P(lens))
     if depth < 0:
-        return None
+        return depth, None
     trees = [[] for _ in range(B)]; at = 0
     for v in range(depth):                                                  # level v: the slices of the trees that have it, in tree order
         for b in range(B):
             if v < int(nlev[b]):
                 ln = int(lens[64 * b + v]); trees[b].append(out[at:at + ln].copy()); at += ln
     assert depth == max(int(x) for x in nlev)
-    return trees
+    return depth, trees
+
+
+def hc_build_mixed(hostcheck, params, arity, labels, cols, cps=None):
+    """-> [levels of tree b] through hc_merkle_build_mixed_batch, or None when the shapes are refused"""
+    return hc_build_mixed_rc(hostcheck, params, arity, labels, cols, cps)[1]
 
 
 def mixed_inputs(oracle, arity, ns, pairs):
