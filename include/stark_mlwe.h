@@ -91,6 +91,9 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  *   "lagrange_wide_acc" (0 | 1, default 1; -1 restores the default: a lane's products of a column go through the lazy accumulator; comparison),
  *   "lagrange_col_groups" (1..65535, default -1 = automatic; -1 restores the default: the column groups of a launch of the lagrange_eval kernel;
  *   1 = one group, g > 1 = min(g, ncols) groups; every value gives the same bytes).
+ *   "mixed_prove_tail" (0 | 1, default 0; -1 restores the default: stark_deep_fri_prove_mixed_batch_dev runs the tail — merge, commit phase, query phase —
+ *   once per group of equal (n0, schedule, r) (0) or once per class of equal schedule, whatever the n0 and r in it (1: the ragged tail); every value gives
+ *   the same bytes).
  *   "pool_poison" (0..255, default -1 = off; FOR TESTS ONLY: every pooled block the library hands to itself, recycled or fresh, and the NTT scratch vector are
  *   filled with this byte first, so a result that depends on a temporary nobody wrote changes with the byte.  Each fill synchronises the stream: the
  *   calls that promise "no synchronisation" do synchronise while it is set.  The long-lived tables are not filled).
@@ -357,6 +360,11 @@ int32_t stark_deep_fri_prove_batch_dev(stark_ctx_t* ctx, size_t batch, const uin
  * the largest trace's costs instead of the sum over the traces.  Traces of equal (n0, schedule, r) then form a group — groups in order of first
  * appearance, traces in the caller's order — and each group takes the tail of stark_deep_fri_prove_batch_dev: passes of at most
  * "prove_batch_max_rows" rows, a pass of one trace the single tail.
+ * Under the option "mixed_prove_tail" = 1 the traces of equal SCHEDULE (same L, same entries; n0 and r free) form a class instead — classes in order of
+ * first appearance, traces in the caller's order — and a class is cut into passes of consecutive traces whose n0 sum to at most "prove_batch_max_rows"
+ * (at least one trace a pass; a pass of one trace is the single tail).  A pass runs ONE merge launch, one commit phase (one fold launch per layer over
+ * all its traces, one leaf launch and one launch per tree level per layer) and one query phase with four host synchronisations, whatever the sizes
+ * and query counts in it.  Results, stage times, errors and everything below are the same under either value.
  * Proof i is byte-identical to stark_deep_fri_prove_dev on trace i alone under (n0[i], its schedule, r[i]).  stage_ms 0 of a proof is the sponge
  * stage of the whole batch + its pass's merge; 1 and 2 are its pass's, as in stark_deep_fri_prove_batch_dev.  batch == 0 returns STARK_OK.
  * STARK_ERR_INVALID_ARG, before any launch: a null ctx, table, entry, n0, r, sched_off or out; a decreasing sched_off; a null schedule with a

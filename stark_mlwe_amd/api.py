@@ -323,7 +323,7 @@ class Context:
         self._chk(self.lib.stark_ctx_sync(self.h))
 
     def set_option(self, key: str, value: int):
-        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "poseidon_block8", "merkle_wave_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous", "lagrange_max_partials", "lagrange_wide_acc", "lagrange_col_groups", "pool_poison" (tests only: fills the library's pooled temporaries, synchronises).  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
+        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "poseidon_block8", "merkle_wave_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous", "lagrange_max_partials", "lagrange_wide_acc", "lagrange_col_groups", "mixed_prove_tail", "pool_poison" (tests only: fills the library's pooled temporaries, synchronises).  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
         self._chk(self.lib.stark_ctx_set_option(self.h, key.encode(), value))
 
     def trim(self):
@@ -620,7 +620,8 @@ class Context:
     def deep_fri_prove_mixed_batch_dev(self, traces, shapes, seed_z):
         """`traces`: list of (a, s, e, t) DEVICE pointers (ints) of independent traces of ANY sizes; `shapes`: per trace (n0, schedule, r) ->
         list of (proof bytes, size estimate, stage ms), each equal to deep_fri_prove of that trace alone under its own shape.  All column sponges
-        run in one launch; traces of equal shape share the batched tail (stark_deep_fri_prove_mixed_batch_dev)."""
+        run in one launch; traces of equal shape share the batched tail — under set_option("mixed_prove_tail", 1) traces of equal schedule share one
+        ragged tail whatever their n0 and r (stark_deep_fri_prove_mixed_batch_dev)."""
         B = len(traces)
         cols = [(C.c_void_p * max(B, 1))(*[int(tr[c]) if tr[c] else None for tr in traces]) for c in range(4)]
         n0 = (C.c_size_t * max(B, 1))(*[int(sh[0]) for sh in shapes])

@@ -5,8 +5,9 @@
 // One trace is a batch of one.  Every prove — stark_deep_fri_prove_dev from columns or from f0, and the two batch entry points — is
 //   challenge_stage (columns only: all column sponges and Fiat-Shamir hashes of the batch, three synchronisations)
 //   -> prove_pass per pass of traces: PassCommit::run (layer 0 + commit phase, no synchronisation) -> batch_queries (four synchronisations).
-// Each of these is written once.  Only the commit phase has two forms — fri_build_impl for a pass of one trace, FriDevBatch (fri_batch.hpp) side
-// by side — and PassCommit::run is the one place that chooses; what follows reads either through a view (StateArrays / BatchArrays).  The
+// Each of these is written once.  Only the commit phase has three forms — fri_build_impl for a pass of one trace, FriDevBatch (fri_batch.hpp) side
+// by side for traces of one n0, FriDevMixed (fri_mixed.hpp) for traces of one schedule and any n0 (the classes of "mixed_prove_tail") — and
+// PassCommit::run is the one place that chooses; what follows reads any of them through a view (StateArrays / BatchArrays / MixedArrays).  The
 // sharded prover (fri_shard_impl.hpp) shares the plan, the assembly and the row gather (merkle_batch.hpp: MerkleGatherList; gather_rows).
 #include <algorithm>
 #include <chrono>
@@ -17,6 +18,7 @@
 #include "pow_table.hpp"
 #include "fri_dev.hpp"
 #include "fri_batch.hpp"
+#include "fri_mixed.hpp"
 #include "merkle_batch.hpp"
 #include "lagrange_dev.hpp"
 #include "shard_coll.hpp"
@@ -315,23 +317,25 @@ static int32_t add_opening(stark_ctx* ctx, MerkleGatherList& G, const fr_t* from
     G.add(from, index, to_row); return STARK_OK;
 }
 // Where a request of trace b reads when the whole commit phase of its pass is on this GPU: `c` names the layers and tree levels
-// (layers(); layer(b, l, &len); levels(l); level(b, l, v, &len)), and the range checks are written here.
+// (layers(); layer(b, l, &len); levels(b, l); level(b, l, v, &len)), and the range checks are written here.
 template <class Commit> static int32_t resolve_opening(stark_ctx* ctx, const Commit& c, size_t b, const FriRequest& q, const fr_t** from, size_t* len) {
     if (q.kind == 0) {
         if (q.which >= c.layers()) return ctx->fail(STARK_ERR_INVALID_ARG, "layer out of range");
         *from = c.layer(b, q.which, len); return STARK_OK;
     }
-    if (q.which >= c.layers() || q.level >= c.levels(q.which)) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
+    if (q.which >= c.layers() || q.level >= c.levels(b, q.which)) return ctx->fail(STARK_ERR_INVALID_ARG, "tree level out of range");
     *from = c.level(b, q.which, q.level, len); return STARK_OK;
 }
-// The two views the query phase reads a commit phase through.  Besides the arrays each says how its (L + 1) x traces() roots reach the host
-// (roots_host: rt[b (L + 1) + l], one download and one synchronisation).
+// The three views the query phase reads a commit phase through.  Besides the arrays each gives a proof's own shape (n0(b), r(b): constants of the
+// pass in the first two) and says how its (L + 1) x traces() roots reach the host (roots_host: rt[b (L + 1) + l], one download and one synchronisation).
 struct StateArrays {                                    // a stark_fri_state: one trace
-    stark_fri_state* S;
+    stark_fri_state* S; size_t r_;
     size_t traces() const { return 1; }
+    size_t n0(size_t) const { return S->n[0]; }
+    size_t r(size_t) const { return r_; }
     size_t layers() const { return S->f.size(); }
     const fr_t* layer(size_t, size_t l, size_t* len) const { *len = S->n[l]; return S->f[l].fr(); }
-    size_t levels(size_t l) const { return S->trees[l]->levels.size(); }
+    size_t levels(size_t, size_t l) const { return S->trees[l]->levels.size(); }
     const fr_t* level(size_t, size_t l, size_t v, size_t* len) const { *len = S->trees[l]->lens[v]; return S->trees[l]->levels[v]; }
     int32_t roots_host(stark_ctx*, std::vector<fr_t>& rt) const { STARK_TRY(state_roots(S)); rt = S->roots; return STARK_OK; }
 };
@@ -398,11 +402,13 @@ struct ReseedOnlyHasher : TrHasher {
     }
 };
 struct BatchArrays {                                    // the traces of a side-by-side pass
-    const FriDevBatch& C;
+    const FriDevBatch& C; size_t r_;
     size_t traces() const { return C.Bp; }
+    size_t n0(size_t) const { return C.n[0]; }
+    size_t r(size_t) const { return r_; }
     size_t layers() const { return C.L + 1; }
     const fr_t* layer(size_t b, size_t l, size_t* len) const { *len = C.n[l]; return C.layer_at(b, l); }
-    size_t levels(size_t l) const { return C.trees[l].levels.size(); }
+    size_t levels(size_t, size_t l) const { return C.trees[l].levels.size(); }
     const fr_t* level(size_t b, size_t l, size_t v, size_t* len) const { *len = C.trees[l].lens[v]; return C.level_at(b, l, v); }
     int32_t roots_host(stark_ctx* ctx, std::vector<fr_t>& rt) const {
         const size_t Bp = C.Bp, R = C.L + 1; std::vector<fr_t> rl(R * Bp);                                               // C.roots is layer-major
@@ -411,16 +417,58 @@ struct BatchArrays {                                    // the traces of a side-
         return STARK_OK;
     }
 };
+// The executor of FriMixedCommit (fri_mixed.hpp) on the device: FriDevExec's arena, streams and launches, plus the ragged fold, the tables of a whole
+// pass and the segment tables of the ragged climbs (as MerkleMixedDevExec has them).  Uploads run on the context's stream: one made while the side
+// stream is current is followed by a fork of its own, so that the side stream's next launch waits for it.
+struct FriMixedDevExec : FriDevExec {
+    using FriDevExec::FriDevExec;
+    int32_t zpows_many(const ZpowJob* jobs, size_t n_jobs, size_t max_m, fr_t* zp) {
+        if (!n_jobs || !max_m) return STARK_OK;
+        hipLaunchKernelGGL(k_zpows_many<PallasFr>, dim3((unsigned)((max_m + 63) / 64), (unsigned)n_jobs), dim3(64), 0, main_st, jobs, zp);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t fold_ragged(const fr_t* f, size_t n, const FoldSeg* segs, size_t n_seg, const fr_t* zp, size_t m, fr_t* out) {
+        if (!is_pow2(m)) return ctx->fail(STARK_ERR_UNSUPPORTED, "ragged fold: m must be a power of two");     // every m divides a power-of-two n0
+        const int log_m = ilog2(m), log_g = std::min(log_m, 4);
+        const uint64_t lanes = (uint64_t)n >> (log_m - log_g);
+        hipLaunchKernelGGL(k_fri_fold_ragged<PallasFr>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, main_st, f, (uint64_t)n, segs, (uint32_t)n_seg, zp, log_m, log_g, out);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x) {
+        DsRaggedStream::Seg* d = nullptr; STARK_TRY(put(h, &d)); *x = d;
+        return cur != main_st ? fk.fork() : STARK_OK;
+    }
+    int32_t gather(const MerkleGatherList& G, fr_t* out) { return gather_rows(ctx, G, out, nullptr); }
+};
+typedef FriMixedCommit<FriMixedDevExec> FriDevMixed;
+struct MixedArrays {                                    // the traces of a ragged pass: every proof has its own shape
+    const FriDevMixed& C; const size_t* r_;
+    size_t traces() const { return C.Bp; }
+    size_t n0(size_t b) const { return C.n[b][0]; }
+    size_t r(size_t b) const { return r_[b]; }
+    size_t layers() const { return C.L + 1; }
+    const fr_t* layer(size_t b, size_t l, size_t* len) const { *len = C.n[b][l]; return C.layer_at(b, l); }
+    size_t levels(size_t b, size_t l) const { return C.levels(b, l); }
+    const fr_t* level(size_t b, size_t l, size_t v, size_t* len) const { return C.level_at(b, l, v, len); }
+    int32_t roots_host(stark_ctx* ctx, std::vector<fr_t>& rt) const {                                                    // C.roots is trace-major already
+        rt.resize((C.L + 1) * C.Bp);
+        STARK_HIP(ctx, hipMemcpyAsync(rt.data(), C.roots, rt.size() * sizeof(fr_t), hipMemcpyDeviceToHost, ctx->stream)); STARK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return STARK_OK;
+    }
+};
 // THE query phase: fri_prove_queries + payload assembly + canonical encoding (fri.rs:355-466, 613-640) of every proof of a pass, read through the
-// view V of its commit phase (one trace: StateArrays; side by side: BatchArrays).  The indices of every opened value depend only on the roots, so
+// view V of its commit phase (one trace: StateArrays; side by side: BatchArrays; ragged: MixedArrays), which also gives every proof's own n0 and r
+// (the seed and index arrays are sized by the sum of r_b * L, proof b's at its own offset; with equal shapes that is B r L as before).  The indices of every opened value depend only on the roots, so
 // the phase first RECORDS what it will read (fri_plan.hpp: the same code against a recording source), fetches all of it — layer elements and tree
 // nodes spread over every layer and level of every proof — with ONE gather, and then assembles the proofs from that list.  FOUR host
 // synchronisations, whatever the number of traces: the roots; the "FRI/seed" hashes (one launch); the r * L "FRI/index" hashes per proof (one
 // launch; none when r * L = 0); the opened values (one gather launch; none when nothing is opened).  Seeds and index seeds are pre-loaded into each
 // proof's MemoHasher, so fri_plan_make and assemble_proof run per proof without touching the device (ReseedOnlyHasher).
-template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V, size_t n0, const size_t* schedule, size_t L, size_t r, std::unique_ptr<stark_proof>* out) {
-    const size_t Bp = V.traces(), R = L + 1, q = r * L;
-    std::vector<fr_t> rt, seed(Bp), in(3 * q * Bp), idx(q * Bp);
+template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V, const size_t* schedule, size_t L, std::unique_ptr<stark_proof>* out) {
+    const size_t Bp = V.traces(), R = L + 1;
+    std::vector<size_t> q0(Bp + 1, 0); for (size_t b = 0; b < Bp; ++b) q0[b + 1] = q0[b] + V.r(b) * L;                   // proof b's index seeds: [q0[b], q0[b + 1])
+    const size_t q = q0[Bp];
+    std::vector<fr_t> rt, seed(Bp), in(3 * q), idx(q);
     STARK_TRY(V.roots_host(ctx, rt));
     DevBuf d_rt, d_seed, d_in, d_idx;
     STARK_HIP(ctx, d_rt.alloc(ctx, rt.size() * sizeof(fr_t))); STARK_HIP(ctx, d_seed.alloc(ctx, Bp * sizeof(fr_t)));
@@ -428,11 +476,11 @@ template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V
     STARK_TRY(tr_hash_dev(ctx, "FRI/seed", d_rt.fr(), R, Bp, d_seed.fr()));                                               // fs_seed_from_roots, fri.rs:178
     STARK_HIP(ctx, d_seed.download_sync(seed.data(), Bp * sizeof(fr_t)));
     if (q) {                                                                                                             // the index seeds of all (proof, query, layer): fri.rs:374, :189-191
-        for (size_t b = 0; b < Bp; ++b) for (size_t j = 0; j < r; ++j) for (size_t l = 0; l < L; ++l) { fr_t* p = &in[3 * (b * q + j * L + l)]; p[0] = seed[b]; p[1] = host::h_u64(l); p[2] = host::h_u64(j); }
-        STARK_HIP(ctx, d_in.alloc(ctx, in.size() * sizeof(fr_t))); STARK_HIP(ctx, d_idx.alloc(ctx, q * Bp * sizeof(fr_t)));
+        for (size_t b = 0; b < Bp; ++b) for (size_t j = 0; j < V.r(b); ++j) for (size_t l = 0; l < L; ++l) { fr_t* p = &in[3 * (q0[b] + j * L + l)]; p[0] = seed[b]; p[1] = host::h_u64(l); p[2] = host::h_u64(j); }
+        STARK_HIP(ctx, d_in.alloc(ctx, in.size() * sizeof(fr_t))); STARK_HIP(ctx, d_idx.alloc(ctx, q * sizeof(fr_t)));
         STARK_TRY(ctx_upload_staged(ctx, d_in.p, in.data(), in.size() * sizeof(fr_t)));
-        STARK_TRY(tr_hash_dev(ctx, "FRI/index", d_in.fr(), 3, q * Bp, d_idx.fr()));
-        STARK_HIP(ctx, d_idx.download_sync(idx.data(), q * Bp * sizeof(fr_t)));
+        STARK_TRY(tr_hash_dev(ctx, "FRI/index", d_in.fr(), 3, q, d_idx.fr()));
+        STARK_HIP(ctx, d_idx.download_sync(idx.data(), q * sizeof(fr_t)));
     }
     ReseedOnlyHasher H0(ctx); std::vector<std::unique_ptr<MemoHasher>> H(Bp); std::vector<FriPlan> plan(Bp);
     std::vector<size_t> row0(Bp + 1, 0);
@@ -440,8 +488,8 @@ template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V
     for (size_t b = 0; b < Bp; ++b) {
         H[b].reset(new MemoHasher(H0));
         H[b]->preload("FRI/seed", &rt[b * R], R, 1, &seed[b]);
-        if (q) H[b]->preload("FRI/index", &in[3 * q * b], 3, q, &idx[q * b]);
-        STARK_TRY(make_query_plan(ctx, plan[b], n0, schedule, L, &rt[b * R], r, *H[b]));
+        if (q0[b + 1] > q0[b]) H[b]->preload("FRI/index", &in[3 * q0[b]], 3, q0[b + 1] - q0[b], &idx[q0[b]]);
+        STARK_TRY(make_query_plan(ctx, plan[b], V.n0(b), schedule, L, &rt[b * R], V.r(b), *H[b]));
         for (const FriRequest& rq : plan[b].req) { const fr_t* from; size_t len; STARK_TRY(resolve_opening(ctx, V, b, rq, &from, &len)); STARK_TRY(add_opening(ctx, G, from, len, rq.index, G.size())); }
         row0[b + 1] = G.size();
     }
@@ -449,21 +497,72 @@ template <class View> static int32_t batch_queries(stark_ctx* ctx, const View& V
     STARK_TRY(gather_rows(ctx, G, nullptr, vals.data()));                                                                // ONE gather over all proofs' requests, one download
     for (size_t b = 0; b < Bp; ++b) {
         out[b].reset(new stark_proof());
-        STARK_TRY(assemble_from_values(ctx, plan[b].shape, r, *H[b], vals.data() + row0[b], row0[b + 1] - row0[b], out[b].get()));
+        STARK_TRY(assemble_from_values(ctx, plan[b].shape, V.r(b), *H[b], vals.data() + row0[b], row0[b + 1] - row0[b], out[b].get()));
     }
     return STARK_OK;
 }
-// Layer 0 and the commit phase of one pass of Bp >= 1 traces, in the two forms of the commit, chosen HERE and nowhere else:
+// All fold challenges of a ragged pass (fri.rs:250; FriMixedCommit::zkeys) before its first kernel: the "FRI/z/l" hashes of the keys the context has not seen
+// yet are ONE tr_hash launch and one download; with every key cached nothing is launched.
+static int32_t sample_z_many(stark_ctx* ctx, uint64_t seed_z, const std::vector<FriDevMixed::ZKey>& keys, std::vector<fr_t>& z) {
+    std::vector<size_t> miss; std::vector<fr_t> in;
+    z.assign(keys.size(), host::h_zero());
+    for (size_t k = 0; k < keys.size(); ++k) {
+        auto it = ctx->z_cache.find(stark_ctx::ZKey{seed_z, keys[k].l, keys[k].n});
+        if (it != ctx->z_cache.end()) { z[k] = it->second; continue; }
+        miss.push_back(k); in.push_back(host::h_u64(seed_z)); in.push_back(host::h_u64(keys[k].l)); in.push_back(host::h_u64(keys[k].n));
+    }
+    if (miss.empty()) return STARK_OK;
+    DevBuf d_in, d_out; std::vector<fr_t> fused(miss.size());
+    STARK_HIP(ctx, d_in.alloc(ctx, in.size() * sizeof(fr_t))); STARK_HIP(ctx, d_out.alloc(ctx, miss.size() * sizeof(fr_t)));
+    STARK_TRY(ctx_upload_staged(ctx, d_in.p, in.data(), in.size() * sizeof(fr_t)));
+    STARK_TRY(tr_hash_dev(ctx, "FRI/z/l", d_in.fr(), 3, miss.size(), d_out.fr()));
+    STARK_HIP(ctx, d_out.download_sync(fused.data(), miss.size() * sizeof(fr_t)));
+    for (size_t i = 0; i < miss.size(); ++i) {
+        const FriDevMixed::ZKey& K = keys[miss[i]];
+        z[miss[i]] = fri_z_from_fused(fused[i], seed_z, K.l, K.n); ctx->z_cache[stark_ctx::ZKey{seed_z, K.l, K.n}] = z[miss[i]];
+    }
+    return STARK_OK;
+}
+// Shapes, constants, challenges and buffers of a ragged pass: everything that may upload constants or synchronise, before the first launch.
+static int32_t mixed_commit_begin(stark_ctx* ctx, FriDevMixed& M, size_t Bp, const size_t* n0, const size_t* schedule, size_t L, uint64_t seed_z) {
+    std::string err; const int32_t rc = M.shape(Bp, n0, schedule, L, err);
+    if (rc == -2) return ctx->fail(STARK_ERR_UNSUPPORTED, err); if (rc) return ctx->fail(STARK_ERR_INVALID_ARG, err);
+    stark_params* p = nullptr; STARK_TRY(ctx_transcript_params(ctx, &p));
+    for (const auto& layer : M.parts) for (const auto& part : layer) STARK_TRY(ctx_merkle_params(ctx, host::width_for_arity(part.arity), &p));
+    std::vector<fr_t> z; STARK_TRY(sample_z_many(ctx, seed_z, M.zkeys, z));
+    return M.init(z.data());
+}
+// deep_ali_merge_evals_blinded (no blinding) of Bp traces of DIFFERENT lengths in one launch (k_ali_merge_ragged): trace b of n0[b] rows with its own z and
+// generator goes to f0 + at0[b].  One power table, the largest domain's.  The check of every z against its own H (lib.rs:78) is the caller's.
+static int32_t ali_merge_ragged_launch(stark_ctx* ctx, DevArena& X, size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const size_t* n0, const size_t* at0, fr_t* f0) {
+    const size_t n_max = *std::max_element(n0, n0 + Bp);
+    PowTable wp; STARK_TRY(omega_table(ctx, fr_root_of_unity<PallasFr>((unsigned)ilog2(n_max)), n_max, &wp));
+    const unsigned block = 256; unsigned grid = 1;
+    std::vector<AliRaggedJob> jobs(Bp);
+    for (size_t b = 0; b < Bp; ++b) {
+        const uint64_t lanes = (n0[b] + ALI_K - 1) / ALI_K, blocks = (lanes + block - 1) / block;
+        const fr_t w_step = fr_pow_u64<PallasFr>(fr_root_of_unity<PallasFr>((unsigned)ilog2(n0[b])), blocks * block);
+        jobs[b] = AliRaggedJob{as_fr(cols[0][b]), as_fr(cols[1][b]), as_fr(cols[2][b]), as_fr(cols[3][b]), zs[b], w_step, fr_inv<PallasFr>(w_step), (uint64_t)n0[b], (uint64_t)at0[b], (uint64_t)(n_max / n0[b])};
+        grid = std::max(grid, (unsigned)blocks);
+    }
+    AliRaggedJob* d = nullptr; STARK_TRY(X.put(jobs, &d));
+    hipLaunchKernelGGL(k_ali_merge_ragged<PallasFr>, dim3(grid, (unsigned)Bp), dim3(block), 0, ctx->stream, (const AliRaggedJob*)d, wp, f0);
+    STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+}
+// Layer 0 and the commit phase of one pass of Bp >= 1 traces, in the three forms of the commit, chosen HERE and nowhere else:
 //   one trace      fri_build_impl — the stark_fri_state that stark_fri_build_dev hands out and the benchmark step runs through, and the only
 //                  commit whose levels are DsStreams (k_node16_pair, the "fri_side_pair" form); layer 0 is the caller's f0 or ali_merge_dev_impl's;
-//   side by side   FriDevBatch (fri_batch.hpp) — layer 0 of every trace from one copy kernel or the batched merge.
-// Neither form synchronises the host.  Whatever reads the result goes through with_view and does not know which form ran.
+//   side by side   FriDevBatch (fri_batch.hpp) — traces of one n0; layer 0 of every trace from one copy kernel or the batched merge;
+//   ragged         FriDevMixed (fri_mixed.hpp) — traces of one schedule and any n0 (`ragged`: the classes of "mixed_prove_tail"); layer 0 from the ragged merge.
+// No form synchronises the host after its prelude.  Whatever reads the result goes through with_view and does not know which form ran.
 struct PassCommit {
-    stark_ctx* ctx; FriDevExec X; FriDevBatch C; std::unique_ptr<stark_fri_state> S;
-    explicit PassCommit(stark_ctx* c) : ctx(c), X(c), C(X) {}
-    // cols: host tables of device pointers a, s, e, t with the traces' z on the host (zs), or f0: a host table of device pointers.  *t_layer0 (optional): when layer 0 was enqueued.
-    int32_t run(size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, uint64_t seed_z,
+    stark_ctx* ctx; FriDevExec X; FriDevBatch C; std::unique_ptr<stark_fri_state> S; FriMixedDevExec XM; FriDevMixed M; bool ragged_ran = false;
+    explicit PassCommit(stark_ctx* c) : ctx(c), X(c), C(X), XM(c), M(XM) {}
+    // cols: host tables of device pointers a, s, e, t with the traces' z on the host (zs), or f0: a host table of device pointers.  n0s: the traces' rows, all
+    // equal unless `ragged` (which needs cols).  *t_layer0 (optional): when layer 0 was enqueued.
+    int32_t run(size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, const size_t* n0s, bool ragged, const size_t* schedule, size_t L, uint64_t seed_z,
                 Clock::time_point* t_layer0) {
+        const size_t n0 = n0s[0];
         const fr_t omega = fr_root_of_unity<PallasFr>((unsigned)ilog2(n0));
         if (Bp == 1) {
             DevBuf merged; const fr_t* f = f0 ? as_fr(f0[0]) : nullptr;
@@ -474,6 +573,15 @@ struct PassCommit {
             }
             if (t_layer0) *t_layer0 = Clock::now();
             return fri_build_impl(ctx, f, n0, schedule, L, seed_z, S);       // copies f: `merged` returns to the pool behind that copy
+        }
+        if (ragged) {
+            if (!cols) return ctx->fail(STARK_ERR_INVALID_ARG, "ragged pass: columns needed");
+            for (size_t b = 0; b < Bp; ++b) if (fr_eq(fr_pow_u64<PallasFr>(zs[b], n0s[b]), host::h_one())) return ctx->fail(STARK_ERR_INVALID_ARG, "z must be outside H");   // lib.rs:78, before any launch
+            STARK_TRY(mixed_commit_begin(ctx, M, Bp, n0s, schedule, L, seed_z));
+            ragged_ran = true;
+            STARK_TRY(ali_merge_ragged_launch(ctx, XM, Bp, cols, zs, n0s, M.at[0].data(), M.f[0]));
+            if (t_layer0) *t_layer0 = Clock::now();
+            return M.run();
         }
         STARK_TRY(batch_commit_begin(ctx, C, Bp, n0, schedule, L, seed_z));
         if (f0) STARK_TRY(batch_fill_layer0(ctx, X, C, f0));
@@ -486,17 +594,19 @@ struct PassCommit {
         if (t_layer0) *t_layer0 = Clock::now();
         return C.run();
     }
-    template <class F> int32_t with_view(F f) const { return S ? f(StateArrays{S.get()}) : f(BatchArrays{C}); }
+    // rs: the traces' query counts (all equal unless the ragged form ran)
+    template <class F> int32_t with_view(const size_t* rs, F f) const { return S ? f(StateArrays{S.get(), rs[0]}) : ragged_ran ? f(MixedArrays{M, rs}) : f(BatchArrays{C, rs[0]}); }
 };
 // One pass of a batch prove: layer 0 -> commit phase -> query phase -> stage times.  Host synchronisations per pass: the FOUR of batch_queries, whatever
 // Bp (layer 0 and the commit phase only enqueue).  stage_ms of every proof of the pass: shared_ms + the pass's layer 0, its commit, its queries.
-static int32_t prove_pass(stark_ctx* ctx, size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, size_t n0,
-                          const size_t* schedule, size_t L, size_t r, uint64_t seed_z, double shared_ms, std::unique_ptr<stark_proof>* out) {
+// n0s / rs: the traces' rows and query counts, all equal unless `ragged`.
+static int32_t prove_pass(stark_ctx* ctx, size_t Bp, const uint64_t* const* const cols[4], const fr_t* zs, const uint64_t* const* f0, const size_t* n0s, bool ragged,
+                          const size_t* schedule, size_t L, const size_t* rs, uint64_t seed_z, double shared_ms, std::unique_ptr<stark_proof>* out) {
     const auto u0 = Clock::now(); auto u1 = u0;
     PassCommit P(ctx);
-    STARK_TRY(P.run(Bp, cols, zs, f0, n0, schedule, L, seed_z, &u1));
+    STARK_TRY(P.run(Bp, cols, zs, f0, n0s, ragged, schedule, L, seed_z, &u1));
     const auto u2 = Clock::now();
-    const int32_t rc = P.with_view([&](const auto& V) { return batch_queries(ctx, V, n0, schedule, L, r, out); });
+    const int32_t rc = P.with_view(rs, [&](const auto& V) { return batch_queries(ctx, V, schedule, L, out); });
     P.S.reset();                                                                            // a single state's layers and trees go back to the pool here, before the proofs are handed out
     if (rc) return rc;
     const auto u3 = Clock::now();
@@ -505,9 +615,9 @@ static int32_t prove_pass(stark_ctx* ctx, size_t Bp, const uint64_t* const* cons
 }
 // stark_deep_fri_prove_f0_batch_dev, and stark_deep_fri_prove_dev given f0 with B = 1: the batch cut into passes of at most "prove_batch_max_rows" rows.
 static int32_t prove_f0_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* f0, size_t n0, const size_t* schedule, size_t L, size_t r, uint64_t seed_z, stark_proof** out) {
-    const size_t per = pass_traces(ctx, n0);
+    const size_t per = pass_traces(ctx, n0); const std::vector<size_t> nn(std::min(per, B), n0), rr(std::min(per, B), r);
     std::vector<std::unique_ptr<stark_proof>> pf(B);
-    for (size_t p0 = 0; p0 < B; p0 += per) STARK_TRY(prove_pass(ctx, std::min(per, B - p0), nullptr, nullptr, f0 + p0, n0, schedule, L, r, seed_z, 0.0, pf.data() + p0));
+    for (size_t p0 = 0; p0 < B; p0 += per) STARK_TRY(prove_pass(ctx, std::min(per, B - p0), nullptr, nullptr, f0 + p0, nn.data(), false, schedule, L, rr.data(), seed_z, 0.0, pf.data() + p0));
     hand_out(pf, out); return STARK_OK;
 }
 // stark_fri_commit_batch_dev: the roots of fri_build of every trace, roots[(b (L + 1) + l) * 4 ..]; one synchronisation per pass.
@@ -515,9 +625,9 @@ static int32_t commit_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const
     const size_t per = pass_traces(ctx, n0), R = L + 1;
     for (size_t p0 = 0; p0 < B; p0 += per) {
         const size_t Bp = std::min(per, B - p0);
-        PassCommit P(ctx); std::vector<fr_t> rt;
-        STARK_TRY(P.run(Bp, nullptr, nullptr, f0 + p0, n0, schedule, L, seed_z, nullptr));
-        STARK_TRY(P.with_view([&](const auto& V) { return V.roots_host(ctx, rt); }));
+        PassCommit P(ctx); std::vector<fr_t> rt; const std::vector<size_t> nn(Bp, n0); const size_t no_queries = 0;
+        STARK_TRY(P.run(Bp, nullptr, nullptr, f0 + p0, nn.data(), false, schedule, L, seed_z, nullptr));
+        STARK_TRY(P.with_view(&no_queries, [&](const auto& V) { return V.roots_host(ctx, rt); }));
         for (size_t i = 0; i < Bp * R; ++i) store_fr(roots + 4 * (p0 * R + i), rt[i]);
     }
     return STARK_OK;
@@ -652,20 +762,24 @@ static int32_t prove_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const*
     for (size_t p = 0; p < B; ++p) { ptrs[4 * p] = as_fr(a[p]); ptrs[4 * p + 1] = as_fr(s[p]); ptrs[4 * p + 2] = as_fr(e[p]); ptrs[4 * p + 3] = as_fr(t[p]); }
     AliChallenges ch; STARK_TRY(challenge_stage(ctx, B, ptrs.data(), n0, ch));
     const double shared_ms = ms_between(t0, Clock::now());
-    const size_t per = pass_traces(ctx, n0);
+    const size_t per = pass_traces(ctx, n0); const std::vector<size_t> nn(std::min(per, B), n0), rr(std::min(per, B), r);
     std::vector<std::unique_ptr<stark_proof>> pf(B);
     for (size_t p0 = 0; p0 < B; p0 += per) {
         const uint64_t* const* const cols[4] = {a + p0, s + p0, e + p0, t + p0};
-        STARK_TRY(prove_pass(ctx, std::min(per, B - p0), cols, ch.z.data() + p0, nullptr, n0, schedule, L, r, seed_z, shared_ms, pf.data() + p0));
+        STARK_TRY(prove_pass(ctx, std::min(per, B - p0), cols, ch.z.data() + p0, nullptr, nn.data(), false, schedule, L, rr.data(), seed_z, shared_ms, pf.data() + p0));
     }
     hand_out(pf, out); return STARK_OK;
 }
 
 // B independent proofs of ANY shapes (stark_deep_fri_prove_mixed_batch_dev): trace i has n0[i] rows, folds by schedule[sched_off[i] .. sched_off[i + 1])
 // and answers r[i] queries.  The challenge stage of all traces at once — the 4 B column sponges side by side in one Ragged launch, which is where
-// the time of a prove is — then the traces of equal (n0, schedule, r) together (mixed_prove_groups, fri_plan.hpp), each group through the passes of
-// the equal-shape batch: prove_pass, cut by "prove_batch_max_rows"; a group (or pass) of one trace takes the single commit.  No merge, commit or query
-// code of its own.  stage_ms[0] of a proof: the challenge stage of the whole batch + its pass's layer 0; [1], [2]: its pass's commit and queries.
+// the time of a prove is — then, chosen HERE by the option "mixed_prove_tail":
+//   0 (default)  the traces of equal (n0, schedule, r) together (mixed_prove_groups, fri_plan.hpp), each group through the passes of the equal-shape batch;
+//   1            the traces of equal SCHEDULE together (mixed_prove_classes), each class through ragged passes (fri_mixed.hpp): one merge, one commit
+//                phase and one query phase per pass whatever the sizes and query counts in it.
+// Either way a group or class is cut into passes of consecutive traces of at most "prove_batch_max_rows" rows (mixed_prove_passes) that go through
+// prove_pass, and a pass of one trace takes the single commit.  No merge, commit or query code of its own.
+// stage_ms[0] of a proof: the challenge stage of the whole batch + its pass's layer 0; [1], [2]: its pass's commit and queries.
 // The arguments were checked by the entry point.  Every proof is byte-for-byte what stark_deep_fri_prove_dev returns for that trace alone.
 static int32_t prove_mixed_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* const* a, const uint64_t* const* s, const uint64_t* const* e, const uint64_t* const* t, const size_t* n0,
                                       const size_t* schedule, const size_t* sched_off, const size_t* r, uint64_t seed_z, stark_proof** out) {
@@ -675,14 +789,17 @@ static int32_t prove_mixed_batch_impl(stark_ctx* ctx, size_t B, const uint64_t* 
     AliChallenges ch; STARK_TRY(challenge_stage(ctx, B, ptrs.data(), n0, ch));
     const double shared_ms = ms_between(t0, Clock::now());
     std::vector<std::unique_ptr<stark_proof>> pf(B);
-    for (const std::vector<size_t>& G : mixed_prove_groups(B, n0, schedule, sched_off, r)) {
-        const size_t g0 = G[0], Bg = G.size(), L = sched_off[g0 + 1] - sched_off[g0], per = pass_traces(ctx, n0[g0]);
+    const bool ragged = ctx->opt.mixed_prove_tail;
+    for (const std::vector<size_t>& G : ragged ? mixed_prove_classes(B, schedule, sched_off) : mixed_prove_groups(B, n0, schedule, sched_off, r)) {
+        const size_t g0 = G[0], Bg = G.size(), L = sched_off[g0 + 1] - sched_off[g0];
         const size_t* sched = L ? schedule + sched_off[g0] : nullptr;
-        std::vector<const uint64_t*> tab[4]; std::vector<fr_t> zs(Bg); std::vector<std::unique_ptr<stark_proof>> gp(Bg);
-        for (size_t j = 0; j < Bg; ++j) { tab[0].push_back(a[G[j]]); tab[1].push_back(s[G[j]]); tab[2].push_back(e[G[j]]); tab[3].push_back(t[G[j]]); zs[j] = ch.z[G[j]]; }
-        for (size_t p0 = 0; p0 < Bg; p0 += per) {
+        std::vector<const uint64_t*> tab[4]; std::vector<fr_t> zs(Bg); std::vector<size_t> nn(Bg), rr(Bg); std::vector<std::unique_ptr<stark_proof>> gp(Bg);
+        for (size_t j = 0; j < Bg; ++j) { tab[0].push_back(a[G[j]]); tab[1].push_back(s[G[j]]); tab[2].push_back(e[G[j]]); tab[3].push_back(t[G[j]]); zs[j] = ch.z[G[j]]; nn[j] = n0[G[j]]; rr[j] = r[G[j]]; }
+        size_t p0 = 0;
+        for (const size_t Bp : mixed_prove_passes(Bg, nn.data(), ctx->opt.prove_batch_max_rows, kMaxPassTraces)) {
             const uint64_t* const* const cols[4] = {tab[0].data() + p0, tab[1].data() + p0, tab[2].data() + p0, tab[3].data() + p0};
-            STARK_TRY(prove_pass(ctx, std::min(per, Bg - p0), cols, zs.data() + p0, nullptr, n0[g0], sched, L, r[g0], seed_z, shared_ms, gp.data() + p0));
+            STARK_TRY(prove_pass(ctx, Bp, cols, zs.data() + p0, nullptr, nn.data() + p0, ragged, sched, L, rr.data() + p0, seed_z, shared_ms, gp.data() + p0));
+            p0 += Bp;
         }
         for (size_t j = 0; j < Bg; ++j) pf[G[j]] = std::move(gp[j]);
     }

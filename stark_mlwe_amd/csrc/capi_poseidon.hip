@@ -272,6 +272,7 @@ int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsRaggedStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
+int32_t stark::hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsRaggedPairStream& D, fr_t* out) { return launch_ds(ctx, st, p, D, out); }
 // The full 160 KiB of LDS per workgroup for the kernels that stage through it: every instantiation the launchers of this file can reach (a DS
 // kernel: once per stream type hash_ds_on takes).  Not listed: the one-wave and wide kernels (k_*_coop, k_hash_ds_wave, k_tr_stream, k_tr_batch), whose
 // coop_lds_bytes / wave_lds_bytes stay below the 64 KiB a kernel may use without the attribute.
@@ -281,7 +282,7 @@ static void ds_attrs() {
     lds_attr((const void*)k_hash_ds<DS>); lds_attr((const void*)k_hash_ds2<17, DS>); lds_attr((const void*)k_hash_ds2<17, DS, true>); lds_attr((const void*)k_hash_ds2<9, DS>); lds_attr((const void*)k_hash_ds_chain<DS>);
 }
 void stark::poseidon_set_attrs() {
-    ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>(); ds_attrs<DsBatchPairPtrStream>(); ds_attrs<DsRaggedStream>();
+    ds_attrs<DsStream>(); ds_attrs<DsGatherStream>(); ds_attrs<DsBatchStream>(); ds_attrs<DsBatchPairStream>(); ds_attrs<DsBatchPairPtrStream>(); ds_attrs<DsRaggedStream>(); ds_attrs<DsRaggedPairStream>();
     for (const void* k : {(const void*)k_leaf_pair, (const void*)k_permute_batch, (const void*)k_tr_hash, (const void*)k_hash_stream, (const void*)k_leaf_pair2<false>, (const void*)k_leaf_pair2<true>, (const void*)k_node16_pair<false>, (const void*)k_node16_pair<true>,
                           (const void*)k_tr_hash_chain, (const void*)k_tr_hash_chain_ragged, (const void*)k_tr_hash_ragged, (const void*)k_leaf_pair_chain, (const void*)k_tr_stream_chain, (const void*)k_tr_batch_chain})
         lds_attr(k);

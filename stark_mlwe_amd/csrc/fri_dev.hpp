@@ -13,6 +13,7 @@
 #include "dev_common.hpp"
 #include "ntt_dev.hpp"   // PowTable / pow_lookup
 #include "poseidon_streams.hpp"   // DsRaggedStream: the segment table of k_copy_ragged
+#include "fri_mixed.hpp"          // FoldSeg, ZpowJob: the tables of k_fri_fold_ragged and k_zpows_many
 
 namespace stark {
 
@@ -33,6 +34,36 @@ __global__ void __launch_bounds__(256) k_fri_fold_pow2(const fr_t* __restrict__ 
     }
     for (int s = 0; s < log_g; ++s) acc = fr_add<F>(acc, shfl_xor_fr(acc, 1 << s));
     if (live && (tid & ((1u << log_g) - 1)) == 0) stg(out + (first >> log_m), acc);
+}
+// The fold of layers of DIFFERENT lengths that share m, back to back (the ragged commit phase, fri_mixed.hpp): k_fri_fold_pow2 with the power table
+// looked up per output.  segs: runs of outputs under one challenge, (first_out, zp_off), first_out ascending from 0; output j folds under
+// zp[zp_off_s ..] for the last run s with first_out_s <= j.  A run holds whole outputs, so the G lanes of an output share the run; the lanes of a
+// wave need not.  Lanes past n take part in the butterfly with zero and store nothing.  (FoldSeg, fold_seg_of: fri_mixed.hpp.)
+template <class F>
+__global__ void __launch_bounds__(256) k_fri_fold_ragged(const fr_t* __restrict__ f, uint64_t n, const FoldSeg* __restrict__ segs, uint32_t n_seg, const fr_t* __restrict__ zp_all, int log_m, int log_g,
+                                                         fr_t* __restrict__ out) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int per = 1 << (log_m - log_g);
+    const uint64_t first = tid << (log_m - log_g);
+    const bool live = first < n;
+    fr_t acc = fr_zero<F>();
+    if (live) {
+        const fr_t* zp = zp_all + segs[fold_seg_of(segs, n_seg, first >> log_m)].zp_off;
+        const uint32_t t0 = (uint32_t)(first & ((1ull << log_m) - 1));
+        for (int u = 0; u < per; ++u) acc = fr_add<F>(acc, fr_mul<F>(ldg(f + first + u), ldg(zp + t0 + u)));
+    }
+    for (int s = 0; s < log_g; ++s) acc = fr_add<F>(acc, shfl_xor_fr(acc, 1 << s));
+    if (live && (tid & ((1u << log_g) - 1)) == 0) stg(out + (first >> log_m), acc);
+}
+// The z^t tables of a whole pass in one launch: job s = blockIdx.y (ZpowJob, fri_mixed.hpp) fills zp[off_s + t] = z_s^t, t < m_s (gridDim.x covers the largest m).
+template <class F>
+__global__ void __launch_bounds__(64) k_zpows_many(const ZpowJob* __restrict__ job, fr_t* __restrict__ zp) {
+    const ZpowJob* J = job + blockIdx.y;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= J->m) return;
+    fr_t acc = fr_one<F>(), b = ldg(&J->z);
+    for (uint64_t e = t; e; e >>= 1) { if (e & 1) acc = fr_mul<F>(acc, b); b = fr_sqr<F>(b); }
+    stg(zp + J->off + t, acc);
 }
 // zp[t] = z^t, t < m (square-and-multiply per lane; m is a fold arity, at most a few hundred).
 template <class F>
@@ -60,16 +91,19 @@ __global__ void __launch_bounds__(256) k_fri_fold_any(const fr_t* __restrict__ f
 // on how they are obtained.
 // Also accumulates the barycentric partial sum  sum_j phi_j w^j / (z - w^j)  per block (for c*).
 #define ALI_K 8
-// The work of one workgroup (blockIdx.x of gridDim.x) on one trace: k_ali_merge runs it for its only trace, k_ali_merge_batch for trace blockIdx.y.
-// block_sum: where this workgroup's barycentric partial goes (nullptr: c* is not asked for).
+// The work of one workgroup (blockIdx.x) on one trace: k_ali_merge runs it for its only trace, k_ali_merge_batch and k_ali_merge_ragged for trace blockIdx.y.
+// block_sum: where this workgroup's barycentric partial goes (nullptr: c* is not asked for).  T: the lanes that work on this trace (its workgroups x
+// blockDim.x; the grid's own where every trace has the grid's length).  stride: the power table is that of a generator g with w = g^stride (1: the
+// table is w's own).
 template <class F>
 __device__ __forceinline__ void ali_merge_block(const fr_t* __restrict__ a, const fr_t* __restrict__ s, const fr_t* __restrict__ e, const fr_t* __restrict__ t,
                                                 const fr_t* __restrict__ r_opt, const fr_t& beta, const PowTable& wpow, const fr_t& w_step /* w^T */, const fr_t& w_step_inv, const fr_t& z, uint64_t n,
-                                                uint64_t j0 /* global position of element 0 */, fr_t* __restrict__ f0, fr_t* __restrict__ block_sum) {
+                                                uint64_t j0 /* global position of element 0 */, fr_t* __restrict__ f0, fr_t* __restrict__ block_sum,
+                                                uint64_t T /* the lanes of THIS trace's merge */, uint64_t stride /* w = wpow's generator ^ stride */) {
     __shared__ uint4 red[2 * 4];
-    const uint64_t T = (uint64_t)gridDim.x * blockDim.x, tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     fr_t phi[ALI_K], pre[ALI_K];
-    fr_t w = tid < n ? pow_lookup<F>(wpow, j0 + tid) : fr_one<F>();     // w^(j0 + tid)
+    fr_t w = tid < n ? pow_lookup<F>(wpow, (j0 + tid) * stride) : fr_one<F>();     // w^(j0 + tid)
     fr_t run = fr_one<F>();
 #pragma unroll
     for (int u = 0; u < ALI_K; ++u) {                              // forward: phi_j and prefix products of (w^j - z)
@@ -143,7 +177,7 @@ template <class F>
 __global__ void __launch_bounds__(256) k_ali_merge(const fr_t* __restrict__ a, const fr_t* __restrict__ s, const fr_t* __restrict__ e, const fr_t* __restrict__ t,
                                                    const fr_t* __restrict__ r_opt, fr_t beta, PowTable wpow, fr_t w_step /* w^T */, fr_t w_step_inv, fr_t z, uint64_t n, uint64_t j0 /* global position of element 0 */,
                                                    fr_t* __restrict__ f0, fr_t* __restrict__ block_sums) {
-    ali_merge_block<F>(a, s, e, t, r_opt, beta, wpow, w_step, w_step_inv, z, n, j0, f0, block_sums ? block_sums + blockIdx.x : (fr_t*)nullptr);
+    ali_merge_block<F>(a, s, e, t, r_opt, beta, wpow, w_step, w_step_inv, z, n, j0, f0, block_sums ? block_sums + blockIdx.x : (fr_t*)nullptr, (uint64_t)gridDim.x * blockDim.x, 1);
 }
 // The merges of gridDim.y traces of n elements over one domain in ONE launch: trace b = blockIdx.y reads its columns through the pointer tables
 // (r_opt == nullptr, or r_opt[b] == nullptr: no blinding term for that trace), its own z[b] and beta[b] from device arrays, and writes
@@ -156,7 +190,19 @@ __global__ void __launch_bounds__(256) k_ali_merge_batch(const fr_t* const* __re
     const fr_t* r = r_opt ? r_opt[b] : (const fr_t*)nullptr;
     const fr_t bt = r ? ldg(beta + b) : fr_zero<F>();
     ali_merge_block<F>(a[b], s[b], e[b], t[b], r, bt, wpow, w_step, w_step_inv, ldg(z + b), n, 0, out_base ? out_base + b * n : out_ptrs[b],
-                       block_sums ? block_sums + b * gridDim.x + blockIdx.x : (fr_t*)nullptr);
+                       block_sums ? block_sums + b * gridDim.x + blockIdx.x : (fr_t*)nullptr, (uint64_t)gridDim.x * blockDim.x, 1);
+}
+// The merges of gridDim.y traces of DIFFERENT lengths in ONE launch (the ragged prove tail, fri_mixed.hpp): trace b = blockIdx.y is job[b] — its
+// columns, its own n, z, w_step = w_b^T_b and inverse (T_b = its own workgroups x blockDim.x) — and writes f0 + out_off (layer 0 of the pass, the
+// traces back to back).  wpow is the table of the LARGEST domain's generator g; trace b's generator is g^stride, stride = n_max / n_b.  gridDim.x is
+// sized for the largest trace: a workgroup beyond trace b's own count leaves before any barrier.  No c*.
+struct AliRaggedJob { const fr_t *a, *s, *e, *t; fr_t z, w_step, w_step_inv; uint64_t n, out_off, stride; };
+template <class F>
+__global__ void __launch_bounds__(256) k_ali_merge_ragged(const AliRaggedJob* __restrict__ job, PowTable wpow, fr_t* __restrict__ f0) {
+    const AliRaggedJob* J = job + blockIdx.y;
+    const uint64_t n = J->n, lanes = (n + ALI_K - 1) / ALI_K, blocks = (lanes + blockDim.x - 1) / blockDim.x;
+    if (blockIdx.x >= blocks) return;                              // the whole workgroup: nothing of it reaches a barrier
+    ali_merge_block<F>(J->a, J->s, J->e, J->t, nullptr, fr_zero<F>(), wpow, ldg(&J->w_step), ldg(&J->w_step_inv), ldg(&J->z), n, 0, f0 + J->out_off, nullptr, blocks * blockDim.x, J->stride);
 }
 // dst[b * n + i] = src[b][i] for b = blockIdx.y: layer 0 of a batch from a table of per-trace pointers (one launch instead of one copy per trace).
 static __global__ void __launch_bounds__(256) k_copy_rows(const fr_t* const* __restrict__ src, uint64_t n, fr_t* __restrict__ dst) {

@@ -83,6 +83,34 @@ inline std::vector<std::vector<size_t>> mixed_prove_groups(size_t B, const size_
     return groups;
 }
 
+// The classes of a mixed-size batch prove under the option "mixed_prove_tail": traces of equal schedule (same L, same entries) form a class and share
+// the ragged tail (fri_mixed.hpp); n0 and r are free.  Classes in order of first appearance, the traces of a class in the caller's order.
+inline std::vector<std::vector<size_t>> mixed_prove_classes(size_t B, const size_t* schedule, const size_t* sched_off) {
+    std::vector<std::vector<size_t>> classes;
+    for (size_t i = 0; i < B; ++i) {
+        const size_t Li = sched_off[i + 1] - sched_off[i];
+        size_t g = 0;
+        for (; g < classes.size(); ++g) {
+            const size_t j = classes[g][0];
+            if (sched_off[j + 1] - sched_off[j] == Li && std::equal(schedule + sched_off[i], schedule + sched_off[i] + Li, schedule + sched_off[j])) break;
+        }
+        if (g == classes.size()) classes.emplace_back();
+        classes[g].push_back(i);
+    }
+    return classes;
+}
+// The passes of a group or class: consecutive traces whose n0 sum to at most max_rows, at least one trace and at most max_traces a pass.  Returns the
+// traces per pass.  On equal n0 this is max(max_rows / n0, 1) traces a pass, the rule of the equal-shape batch.
+inline std::vector<size_t> mixed_prove_passes(size_t B, const size_t* n0, size_t max_rows, size_t max_traces) {
+    std::vector<size_t> passes;
+    for (size_t i = 0; i < B;) {
+        size_t k = 1, rows = n0[i];
+        while (i + k < B && k < max_traces && n0[i + k] <= max_rows && rows <= max_rows - n0[i + k]) { rows += n0[i + k]; ++k; }
+        passes.push_back(k); i += k;
+    }
+    return passes;
+}
+
 // Shapes of the L+1 committed layers: sizes, Merkle arities, leaf kinds, level lengths; plus the roots.
 struct FriShape {
     size_t n0 = 0; std::vector<size_t> schedule, n, arity; std::vector<char> hashed;

@@ -18,6 +18,7 @@
 #include "mfma_digits.hpp"
 #include "poseidon_chain.hpp"
 #include "fri_batch.hpp"
+#include "fri_mixed.hpp"
 #include "ntt_mixed_plan.hpp"
 #include "sumcheck_impl.hpp"     // the provers' transcript labels, sumcheck_batch.hpp and sumcheck_verify_batch.hpp (host-only)
 #include "mle_dev.hpp"
@@ -72,12 +73,13 @@ template <class DS, class Put> static void hash_ds_stream(const HcParams* P, con
 // The recording side of the host executors: while a log is open (hc_climb_launches), every hash_level records its launch — which stream, its DS level
 // number, its hashes, where they go — and writes zeros where the hashes would go (what is launched depends on the shapes alone).
 struct HcLaunch { int kind; uint32_t level; size_t n_out; const fr_t* out; };
-enum { kHcBatchPitch = 1, kHcBatchPtrs = 2, kHcBatchPairs = 3, kHcRaggedNodes = 4, kHcRaggedPairs = 5, kHcBatchPairPtrs = 6 };
+enum { kHcBatchPitch = 1, kHcBatchPtrs = 2, kHcBatchPairs = 3, kHcRaggedNodes = 4, kHcRaggedPairs = 5, kHcBatchPairPtrs = 6, kHcRaggedFriPairs = 7 };
 static thread_local std::vector<HcLaunch>* g_launch_log = nullptr;
 static int ds_kind(const DsBatchStream& D) { return D.in_ptrs ? kHcBatchPtrs : kHcBatchPitch; }
 static int ds_kind(const DsBatchPairStream&) { return kHcBatchPairs; }
 static int ds_kind(const DsBatchPairPtrStream&) { return kHcBatchPairPtrs; }
 static int ds_kind(const DsRaggedStream& D) { return D.mode == 1 ? kHcRaggedPairs : kHcRaggedNodes; }
+static int ds_kind(const DsRaggedPairStream&) { return kHcRaggedFriPairs; }
 template <class DS> static int32_t hash_ds_stream(const HcParams* P, const DS& D, fr_t* out) {
     if (g_launch_log) { g_launch_log->push_back(HcLaunch{ds_kind(D), fr_to_canonical<PF>(D.level_f).v[0], D.n_out, out}); std::fill(out, out + D.n_out, fr_zero<PF>()); return 0; }
     hash_ds_stream(P, D, [&](size_t k, const fr_t& h) { out[k] = h; }); return 0;
@@ -1430,5 +1432,96 @@ long hc_climb_launches(int site, size_t arity, size_t B, const size_t* n, int fl
         out[4 * i] = log[i].kind; out[4 * i + 1] = log[i].level; out[4 * i + 2] = (int64_t)log[i].n_out; out[4 * i + 3] = top && log[i].out >= top && log[i].out < top + n_top ? 1 : 0;
     }
     return (long)log.size();
+}
+}  // extern "C"
+
+// ---- the ragged commit phase (fri_mixed.hpp) through the host instantiation of the stream bodies -------------------------------------------------------
+// FriHostExec plus the ragged steps, counting what the driver asks for by kind (the census of hc_fri_commit_mixed_steps).  dry: count only — nothing is
+// folded or hashed (what the driver launches depends on the shapes alone).
+struct FriMixedHostExec : FriHostExec {
+    bool dry = false; size_t n_fold = 0, n_leaf_pairs = 0, n_pair_streams = 0, n_levels = 0, n_blocks = 0, n_zpows = 0, n_gathers = 0;
+    using FriHostExec::FriHostExec;
+    int32_t alloc(size_t bytes, void** out) { ++n_blocks; return HostArena::alloc(bytes, out); }
+    template <class T> int32_t put(const std::vector<T>& h, T** out) { ++n_blocks; return HostArena::put(h, out); }
+    int32_t zpows_many(const ZpowJob* jobs, size_t n_jobs, size_t, fr_t* zp) {
+        ++n_zpows; if (dry) return 0;
+        for (size_t s = 0; s < n_jobs; ++s) FriHostExec::zpows(jobs[s].z, jobs[s].m, zp + jobs[s].off);
+        return 0;
+    }
+    int32_t fold(const fr_t* f, size_t n, const fr_t* zp, size_t m, fr_t* out) { ++n_fold; return dry ? 0 : FriHostExec::fold(f, n, zp, m, out); }
+    int32_t fold_ragged(const fr_t* f, size_t n, const FoldSeg* segs, size_t n_seg, const fr_t* zp, size_t m, fr_t* out) { ++n_fold; if (!dry) fri_fold_ragged_host(f, n, segs, n_seg, zp, m, out); return 0; }
+    int32_t leaf_pairs(const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h) { ++n_leaf_pairs; return dry ? 0 : FriHostExec::leaf_pairs(f, f_next, n, m, h); }
+    int32_t hash_level(size_t arity, const DsRaggedPairStream& D, fr_t* out) { ++n_pair_streams; return dry ? 0 : hash_ds_stream(mp.params(arity), D, out); }
+    int32_t hash_level(size_t arity, const DsRaggedStream& D, fr_t* out) { ++n_levels; return dry ? 0 : hash_ds_stream(mp.params(arity), D, out); }
+    int32_t segments(const std::vector<DsRaggedStream::Seg>& h, const DsRaggedStream::Seg** x) { DsRaggedStream::Seg* d = nullptr; if (int32_t rc = put(h, &d)) return rc; *x = d; return 0; }
+    int32_t gather(const MerkleGatherList& G, fr_t* out) { ++n_gathers; if (!dry) for (size_t i = 0; i < G.size(); ++i) out[G.row_of(i)] = G.base[G.src[i]][G.index[i]]; return 0; }
+};
+extern "C" {
+// The commit phase of B traces of one schedule and any n0[b] through FriMixedCommit: roots[(b (L + 1) + l) * 4 ..] = root of layer l of trace b.  All
+// "FRI/z/l" hashes of the pass are one hash call.  0 on success, the driver's refusal (-1, -2, -3) or the out-of-memory code otherwise.
+int hc_fri_commit_mixed(void* tparams, size_t B, const uint64_t* const* f0, const size_t* n0, const size_t* schedule, size_t L, uint64_t seed_z, uint64_t* roots) {
+    FriMixedHostExec X((HcParams*)tparams); FriMixedCommit<FriMixedHostExec> C(X);
+    std::string err; if (int rc = C.shape(B, n0, schedule, L, err)) return rc;
+    const size_t K = C.zkeys.size(); std::vector<fr_t> in(3 * K), fused(K), z(K);
+    for (size_t k = 0; k < K; ++k) { in[3 * k] = host::h_u64(seed_z); in[3 * k + 1] = host::h_u64(C.zkeys[k].l); in[3 * k + 2] = host::h_u64(C.zkeys[k].n); }
+    HcHasher H(tparams); if (K && H.hash("FRI/z/l", in.data(), 3, K, fused.data())) return -4;
+    for (size_t k = 0; k < K; ++k) z[k] = fri_z_from_fused(fused[k], seed_z, C.zkeys[k].l, C.zkeys[k].n);
+    if (int32_t rc = C.init(z.data())) return hc_rc(rc);
+    for (size_t b = 0; b < B; ++b) for (size_t i = 0; i < n0[b]; ++i) C.f[0][C.at[0][b] + i] = ld4(f0[b] + 4 * i);
+    if (int32_t rc = C.run()) return hc_rc(rc);
+    for (size_t i = 0; i < B * (L + 1); ++i) st4(roots + 4 * i, C.roots[i]);
+    return 0;
+}
+// The driver's census over shapes alone: out7 = (folds, leaf-pair launches, pair-stream launches, level launches, blocks, z-power launches, gathers).
+int hc_fri_commit_mixed_steps(size_t B, const size_t* n0, const size_t* schedule, size_t L, size_t* out7) {
+    FriMixedHostExec X(nullptr); X.dry = true; FriMixedCommit<FriMixedHostExec> C(X);
+    std::string err; if (int rc = C.shape(B, n0, schedule, L, err)) return rc;
+    const std::vector<fr_t> z(C.zkeys.size(), host::h_u64(3));
+    if (int32_t rc = C.init(z.data())) return hc_rc(rc);
+    if (int32_t rc = C.run()) return hc_rc(rc);
+    out7[0] = X.n_fold; out7[1] = X.n_leaf_pairs; out7[2] = X.n_pair_streams; out7[3] = X.n_levels; out7[4] = X.n_blocks; out7[5] = X.n_zpows; out7[6] = X.n_gathers;
+    return 0;
+}
+// One launch of a DsRaggedPairStream: segment s reads in0[s] (n_in[s] elements) under labels[s]; in1 (n_in1 elements, or null: zero partners) is the ONE
+// partner array of the launch, read at (hash index) / cp_div.  out receives the segments' hashes back to back.  Returns their number, or -1 on an empty
+// segment or a partner index out of range.
+long hc_hash_ds_ragged_pairs_level(void* params, size_t arity, size_t n_seg, const uint64_t* labels, const uint64_t* const* in0, const size_t* n_in, const uint64_t* in1, size_t n_in1,
+                                   size_t cp_div, uint64_t* out) {
+    HcParams* P = (HcParams*)params;
+    std::vector<std::vector<fr_t>> a(n_seg); std::vector<fr_t> b(in1 ? n_in1 : 0); DsRaggedTable T;
+    for (size_t s = 0; s < n_seg; ++s) {
+        if (!n_in[s]) return -1;
+        a[s].resize(n_in[s]); for (size_t i = 0; i < n_in[s]; ++i) a[s][i] = ld4(in0[s] + 4 * i);
+        T.add(1, arity, a[s].data(), nullptr, n_in[s], labels[s]);
+    }
+    for (size_t i = 0; i < b.size(); ++i) b[i] = ld4(in1 + 4 * i);
+    if (!cp_div || (in1 && T.n_out && (T.n_out - 1) / cp_div >= n_in1)) return -1;
+    hash_ds_stream(P, DsRaggedPairStream::make(arity, T.segs.data(), n_seg, T.n_out, in1 ? b.data() : nullptr, cp_div), out);
+    return (long)T.n_out;
+}
+// The ragged fold's host restatement (fri_fold_ragged_host): n inputs, runs (first_out[s], zp_off[s]) over a table of n_zp elements.  -1: refused arguments.
+int hc_fri_fold_ragged(const uint64_t* f, size_t n, const uint64_t* first_out, const uint64_t* zp_off, size_t n_seg, const uint64_t* zp, size_t n_zp, size_t m, uint64_t* out) {
+    if (m < 2 || n % m || !n_seg || first_out[0] != 0) return -1;
+    std::vector<FoldSeg> segs(n_seg);
+    for (size_t s = 0; s < n_seg; ++s) { if ((s && first_out[s] <= first_out[s - 1]) || zp_off[s] + m > n_zp) return -1; segs[s] = FoldSeg{first_out[s], zp_off[s]}; }
+    std::vector<fr_t> fv(n), zv(n_zp), o(n / m);
+    for (size_t i = 0; i < n; ++i) fv[i] = ld4(f + 4 * i);
+    for (size_t i = 0; i < n_zp; ++i) zv[i] = ld4(zp + 4 * i);
+    fri_fold_ragged_host(fv.data(), n, segs.data(), n_seg, zv.data(), m, o.data());
+    for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
+    return 0;
+}
+// mixed_prove_classes (fri_plan.hpp): class_of[i] = the class of trace i, order = the traces class by class; returns the number of classes
+size_t hc_mixed_prove_classes(size_t B, const size_t* schedule, const size_t* sched_off, size_t* class_of, size_t* order) {
+    const std::vector<std::vector<size_t>> G = mixed_prove_classes(B, schedule, sched_off);
+    size_t pos = 0;
+    for (size_t g = 0; g < G.size(); ++g) for (size_t i : G[g]) { class_of[i] = g; order[pos++] = i; }
+    return G.size();
+}
+// mixed_prove_passes (fri_plan.hpp): the traces per pass into out[0 .. cap); returns the number of passes
+size_t hc_mixed_prove_passes(size_t B, const size_t* n0, size_t max_rows, size_t max_traces, size_t* out, size_t cap) {
+    const std::vector<size_t> p = mixed_prove_passes(B, n0, max_rows, max_traces);
+    for (size_t i = 0; i < p.size() && i < cap; ++i) out[i] = p[i];
+    return p.size();
 }
 }  // extern "C"

@@ -12,13 +12,14 @@ void poseidon_set_attrs();                                           // per-devi
 // One launch of hash_with_ds_dynamic over the hashes of a DS stream on `st`, in the form the selector picks for a Merkle level of D.n_out nodes
 // (DsStream: a Merkle level / pair-leaf level; DsGatherStream: one (width, depth) step of the batch verifiers; DsBatchStream: one level of B trees;
 // DsBatchPairStream: the pair leaves of B unhashed FRI layers; DsBatchPairPtrStream: the pair leaves of B trees read through pointer tables;
-// DsRaggedStream: one level, node or pair leaf, of trees of different lengths).
+// DsRaggedStream: one level, node or pair leaf, of trees of different lengths; DsRaggedPairStream: the pair leaves of unhashed FRI layers of different lengths).
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsGatherStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsBatchPairPtrStream& D, fr_t* out);
 int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsRaggedStream& D, fr_t* out);
+int32_t hash_ds_on(stark_ctx* ctx, hipStream_t st, stark_params* p, const DsRaggedPairStream& D, fr_t* out);
 int32_t leaf_pair_hash_on(stark_ctx* ctx, hipStream_t st, const fr_t* f, const fr_t* f_next, size_t n, size_t m, fr_t* h);
 // level0_block: a pooled block holding the leaves, moved into the tree as level 0; an empty one: level 0 is a copy of `leaves` (capi_poseidon.hip)
 int32_t merkle_build_on(stark_ctx* ctx, hipStream_t st, stark_params* p, size_t arity, uint64_t label, const fr_t* leaves, size_t n, int pairs, const fr_t* cp, size_t cp_div,

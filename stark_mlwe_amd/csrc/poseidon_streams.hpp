@@ -170,6 +170,37 @@ struct DsRaggedStream {
         return ldg(S.in0 + j * arity + c);
     }
 };
+// The pair leaves of unhashed FRI layers of DIFFERENT lengths in one launch (the ragged commit phase, fri_mixed.hpp): DsBatchPairStream with a segment
+// per tree.  Segment s (DsRaggedStream's table type; its in1 is not read) is the layer of one trace: in0_s its n_in_s elements, its label, and `first`,
+// the index of its first hash.  Hash k is leaf j = k - first_s of that tree, position j:
+//   hash k = hash_with_ds_dynamic([arity, 2^32 - 1, j, label_s] || in0_s[j], in1 ? in1[k / cp_div] : 0 || 1), eager sponge, cap 0
+// with in1 ONE array for the launch, indexed by the launch's own hash index k: the next layers of the same trees back to back.  That is exact when
+// cp_div divides every n_in_s (then first_s / cp_div is where tree s starts in in1, and k / cp_div never leaves its slice).  in1 == nullptr: zero
+// partners (the last layer, fri.rs:266).
+struct DsRaggedPairStream {
+    typedef DsRaggedStream::Seg Seg;
+    fr_t arity_f, level_f; size_t n_seg, n_out, cp_div; const Seg* segs; const fr_t* in1;
+    static inline DsRaggedPairStream make(size_t arity, const Seg* segs, size_t n_seg, size_t n_out, const fr_t* in1, size_t cp_div) {
+        DsRaggedPairStream D;
+        D.arity_f = fr_from_u64<PF>(arity); D.level_f = fr_from_u64<PF>(0xFFFFFFFFu); D.n_seg = n_seg; D.n_out = n_out; D.cp_div = cp_div ? cp_div : 1; D.segs = segs; D.in1 = in1;
+        return D;
+    }
+    FR_HD size_t seg(size_t k) const {                                 // the last segment whose first hash is <= k
+        size_t lo = 0, hi = n_seg;
+        while (hi - lo > 1) { const size_t mid = (lo + hi) >> 1; if ((size_t)segs[mid].first <= k) lo = mid; else hi = mid; }
+        return lo;
+    }
+    FR_HD uint64_t position(size_t k) const { return k - (size_t)segs[seg(k)].first; }
+    FR_HD size_t total(size_t) const { return 7; }
+    FR_HD size_t max_total() const { return 7; }
+    FR_HD fr_t elem(size_t k, size_t q) const {
+        if (q < 2) return q == 0 ? arity_f : level_f;
+        if (q == 6) return fr_one<PF>();
+        if (q == 5) return in1 ? ldg(in1 + k / cp_div) : fr_zero<PF>();
+        const Seg& S = segs[seg(k)]; const size_t j = k - (size_t)S.first;
+        return q == 2 ? fr_from_u64<PF>(j) : (q == 3 ? fr_from_u64<PF>(S.label) : ldg(S.in0 + j));
+    }
+};
 // The segment table of one launch, built on the host: add() the participating trees in order, then hand `segs` to the executor's memory.
 struct DsRaggedTable {
     std::vector<DsRaggedStream::Seg> segs; size_t n_out = 0;
