@@ -91,6 +91,14 @@ int32_t stark_ctx_trim(stark_ctx_t* ctx);     /* also drops the NTT plans (direc
  *   "lagrange_wide_acc" (0 | 1, default 1; -1 restores the default: a lane's products of a column go through the lazy accumulator; comparison),
  *   "lagrange_col_groups" (1..65535, default -1 = automatic; -1 restores the default: the column groups of a launch of the lagrange_eval kernel;
  *   1 = one group, g > 1 = min(g, ncols) groups; every value gives the same bytes).
+ *   "lagrange_shared_inverse" (0 | 1, default 0; -1 restores the default: 1 = a pass of the lagrange_eval driver multiplies the workgroups' products,
+ *   inverts those of a point together with ONE Fermat inversion and hands every workgroup its inverse, instead of one inversion per workgroup; two
+ *   more launches, two pooled tables of pass points x workgroups elements, still stream-ordered and without a host synchronisation; every value
+ *   gives the same bytes, errors and refusals on every stark_lagrange_eval_* entry point),
+ *   "lagrange_share_cosets" (0 | 1, default 0; -1 restores the default: 1 = points of one coset of H — z and z w^s, such as the DEEP pair (z, z w), in
+ *   any order, duplicates included — share the weights of the first of them and read the columns at their shift; the whole-domain calls only: the
+ *   block forms (stark_lagrange_eval_shard_dev, the sharded and emulated calls) ignore it, because a rotation leaves the block; every value gives
+ *   the same bytes).
  *   "mixed_prove_tail" (0 | 1, default 0; -1 restores the default: stark_deep_fri_prove_mixed_batch_dev runs the tail — merge, commit phase, query phase —
  *   once per group of equal (n0, schedule, r) (0) or once per class of equal schedule, whatever the n0 and r in it (1: the ragged tail); every value gives
  *   the same bytes).

@@ -323,7 +323,7 @@ class Context:
         self._chk(self.lib.stark_ctx_sync(self.h))
 
     def set_option(self, key: str, value: int):
-        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "poseidon_block8", "merkle_wave_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous", "lagrange_max_partials", "lagrange_wide_acc", "lagrange_col_groups", "mixed_prove_tail", "pool_poison" (tests only: fills the library's pooled temporaries, synchronises).  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
+        """stark_ctx_set_option: "ntt_direct_max_log", "ntt_merged_coset", "ntt_log_tile", "ntt_min_waves", "poseidon_lane_only", "sponge_one_wave", "merkle_node16_pair", "poseidon_block8", "merkle_wave_pair", "fri_side_pair", "prove_batch_max_rows", "ntt_batch_max_elems", "mle_log_tile", "mle_lane_contiguous", "lagrange_max_partials", "lagrange_wide_acc", "lagrange_col_groups", "lagrange_shared_inverse", "lagrange_share_cosets", "mixed_prove_tail", "pool_poison" (tests only: fills the library's pooled temporaries, synchronises).  An unknown key raises StarkError (INVALID_ARG) listing the known ones."""
         self._chk(self.lib.stark_ctx_set_option(self.h, key.encode(), value))
 
     def trim(self):

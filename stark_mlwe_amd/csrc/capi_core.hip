@@ -280,6 +280,8 @@ static const OptionDef kOptions[] = {
     {"lagrange_max_partials", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v != -1 && (v < 1 || v > ((int64_t)1 << 28))) return "1..2^28, or -1 for the default"; o.lagrange_max_partials = v == -1 ? (size_t)1 << 21 : (size_t)v; return nullptr; }},
     {"lagrange_wide_acc", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 1) return "0 or 1, or -1 for the default"; o.lagrange_wide_acc = (int)v; return nullptr; }},
     {"lagrange_col_groups", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v != -1 && (v < 1 || v > 65535)) return "1..65535, or -1 for automatic"; o.lagrange_col_groups = (int)v; return nullptr; }},
+    {"lagrange_shared_inverse", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 1) return "0 or 1, or -1 for the default"; o.lagrange_shared_inverse = v == 1; return nullptr; }},
+    {"lagrange_share_cosets", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 1) return "0 or 1, or -1 for the default"; o.lagrange_share_cosets = v == 1; return nullptr; }},
     {"mixed_prove_tail", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 1) return "0 or 1, or -1 for the default"; o.mixed_prove_tail = v == 1; return nullptr; }},
     {"pool_poison", [](stark_ctx::Options& o, int64_t v) -> const char* { if (v < -1 || v > 255) return "0..255, or -1 for off"; o.pool_poison = (int)v; return nullptr; }},
 };

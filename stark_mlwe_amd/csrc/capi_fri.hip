@@ -674,12 +674,37 @@ struct LagDevExec : DevArena {
         hipLaunchKernelGGL(k_lagrange_gather, dim3((unsigned)((cnt * ncols + 255) / 256)), dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, j, slot, (uint64_t)cnt, out);
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
-    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n_local, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, unsigned groups,
-                     unsigned col_groups, size_t group_cols, unsigned grid, fr_t* part) {
+    int32_t totals(size_t n_local, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t* zs, size_t npts, unsigned grid, fr_t* tot) {
+        hipLaunchKernelGGL(k_lagrange_totals, dim3(grid, (unsigned)std::min<size_t>(npts, 65535)), dim3(256), 0, ctx->stream, (uint64_t)n_local, j0, wp, w_step, zs, (uint64_t)npts, tot);
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    int32_t invert(const fr_t* tot, size_t npts, unsigned grid, fr_t* inv) {
+        hipLaunchKernelGGL(k_lagrange_invert, dim3((unsigned)npts), dim3(256), 0, ctx->stream, tot, (uint64_t)grid, inv);       // one workgroup per point; a pass has at most 2^28 ("lagrange_max_partials")
+        STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
+    }
+    template <bool WIDE, bool SHARED, bool COSETS>
+    void launch_partials(const dim3& g, const fr_t* const* cols, size_t ncols, size_t n_local, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts,
+                         const LagEntries& E, const fr_t* inv, size_t group_cols, fr_t* part) {
+        hipLaunchKernelGGL((k_lagrange_partials<WIDE, SHARED, COSETS>), g, dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n_local, j0, wp, w_step, w_step_inv, zs, (uint64_t)npts, E, inv,
+                           (uint64_t)group_cols, part);
+    }
+    // zs: the npts classes of the launch (E.off null: every class one point); inv null: every workgroup inverts its own product, else the table of `invert`
+    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n_local, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, const LagEntries& E,
+                     const fr_t* inv, unsigned groups, unsigned col_groups, size_t group_cols, unsigned grid, fr_t* part) {
         const bool wide = ctx->opt.lagrange_wide_acc < 0 ? kLagWideAcc : ctx->opt.lagrange_wide_acc != 0;
         const dim3 g(grid, groups, col_groups);
-        if (wide) hipLaunchKernelGGL(k_lagrange_partials<true>, g, dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n_local, j0, wp, w_step, w_step_inv, zs, (uint64_t)npts, (uint64_t)group_cols, part);
-        else hipLaunchKernelGGL(k_lagrange_partials<false>, g, dim3(256), 0, ctx->stream, cols, (uint64_t)ncols, (uint64_t)n_local, j0, wp, w_step, w_step_inv, zs, (uint64_t)npts, (uint64_t)group_cols, part);
+#define STARK_LAG_PARTIALS(W, S, C) launch_partials<W, S, C>(g, cols, ncols, n_local, j0, wp, w_step, w_step_inv, zs, npts, E, inv, group_cols, part)
+        switch ((wide ? 4 : 0) | (inv ? 2 : 0) | (E.off ? 1 : 0)) {
+            case 0: STARK_LAG_PARTIALS(false, false, false); break;
+            case 1: STARK_LAG_PARTIALS(false, false, true); break;
+            case 2: STARK_LAG_PARTIALS(false, true, false); break;
+            case 3: STARK_LAG_PARTIALS(false, true, true); break;
+            case 4: STARK_LAG_PARTIALS(true, false, false); break;
+            case 5: STARK_LAG_PARTIALS(true, false, true); break;
+            case 6: STARK_LAG_PARTIALS(true, true, false); break;
+            default: STARK_LAG_PARTIALS(true, true, true); break;
+        }
+#undef STARK_LAG_PARTIALS
         STARK_HIP(ctx, hipGetLastError()); return STARK_OK;
     }
     int32_t finish(const fr_t* part, unsigned grid, const fr_t* scale, const uint64_t* slot, size_t npts, size_t ncols, fr_t* out) {
@@ -715,7 +740,7 @@ static std::vector<fr_t> lagrange_points(size_t npoints, const uint64_t* z) { st
 static int32_t lagrange_eval_block_impl(stark_ctx* ctx, size_t ncols, const uint64_t* const* cols, const LagBlock& B, const fr_t& omega, const std::vector<fr_t>& zs, fr_t* out) {
     std::vector<const fr_t*> cp(ncols); for (size_t c = 0; c < ncols; ++c) cp[c] = as_fr(cols[c]);
     LagDevExec X(ctx);
-    return lagrange_eval_batch(X, ncols, cp.data(), B, omega, zs.size(), zs.data(), ctx->opt.lagrange_max_partials, ctx->opt.lagrange_col_groups, out, nullptr);
+    return lagrange_eval_batch(X, ncols, cp.data(), B, omega, zs.size(), zs.data(), ctx->opt.lagrange_max_partials, ctx->opt.lagrange_col_groups, ctx->opt.lagrange_shared_inverse, ctx->opt.lagrange_share_cosets, out, nullptr);
 }
 
 // ---- lagrange_eval_on_h of columns block-sharded over the ranks of a ShardColl: block partials, ONE all-gather of the W tables, the combine --------

@@ -129,6 +129,8 @@ struct stark_ctx {
         size_t lagrange_max_partials = (size_t)1 << 21;  // stark_lagrange_eval_on_h_batch_dev cuts the points of a call into passes of at most this many block partials (points x columns x workgroups per column; lagrange_dev.hpp): 64 MiB of scratch per pass; a pass of one point is always allowed
         int lagrange_wide_acc = -1;      // k_lagrange_partials: a lane's K products of a column in the lazy accumulator (1) or as K products and additions (0); -1 = the default of lagrange_dev.hpp (comparison)
         int lagrange_col_groups = -1;    // k_lagrange_partials: the column groups of a launch (blockIdx.z): 1 = one group, g > 1 = min(g, ncols) groups; -1 = automatic (lag_col_groups, lagrange_dev.hpp).  Every value gives the same bytes
+        int lagrange_shared_inverse = 0; // lagrange_eval_batch: 1 = one Fermat inversion per point and pass (k_lagrange_totals, k_lagrange_invert, the shared form of k_lagrange_partials) instead of one per workgroup; 0 = the default.  Every value gives the same bytes
+        int lagrange_share_cosets = 0;   // lagrange_eval_batch, whole-domain form: 1 = points of one coset of H (z, z w^s) share the weights of the first of them, the columns read at the shift; 0 = the default; the block form ignores it.  Every value gives the same bytes
         bool mixed_prove_tail = false;   // stark_deep_fri_prove_mixed_batch_dev: 0 = traces of equal (n0, schedule, r) share a tail (mixed_prove_groups); 1 = traces of equal schedule share ONE ragged tail whatever their n0 and r (mixed_prove_classes, fri_mixed.hpp).  Every value gives the same bytes
         int pool_poison = -1;            // TESTS ONLY: 0..255 = ctx_alloc fills every block it hands out (the whole rounded block, recycled or fresh) and ctx_scratch the scratch vector
                                          // with this byte, so a read of a temporary nobody wrote shows; each fill synchronises the stream.  -1 = off (one branch per allocation, no HIP call)

@@ -1131,31 +1131,69 @@ struct LagHostExec : HostArena {
         for (size_t q = 0; q < cnt; ++q) for (size_t c = 0; c < ncols; ++c) out[slot[q] * ncols + c] = j[q] == kLagNoRow ? fr_zero<PF>() : cols[c][j[q]];
         return 0;
     }
-    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, unsigned groups,
-                     unsigned col_groups, size_t group_cols, unsigned grid, fr_t* part) {
+    // the census of a call: Fermat inversions; weight sets of k_lagrange_partials (workgroup x class evaluations of lag_prefix followed by a peel); products of
+    // k_lagrange_totals (workgroup x point evaluations of lag_prefix); member walks of k_lagrange_partials (workgroup x member: what a weight set served)
+    uint64_t census[4] = {0, 0, 0, 0};
+    // the wave scan of 256 lanes' products: tot[v] = the product of wave v, others[t] = the product of the other lanes of t's wave
+    static void scan(const std::vector<fr_t>& run, fr_t (&tot)[4], std::vector<fr_t>& others) {
+        for (int v = 0; v < 4; ++v) { tot[v] = fr_one<PF>(); for (int l = 0; l < 64; ++l) tot[v] = fr_mul<PF>(tot[v], run[64 * v + l]); }
+        for (int t = 0; t < 256; ++t) {
+            const int v = t >> 6, l = t & 63; fr_t before = fr_one<PF>(), after = fr_one<PF>();
+            for (int q = 0; q < l; ++q) before = fr_mul<PF>(before, run[64 * v + q]);
+            for (int q = l + 1; q < 64; ++q) after = fr_mul<PF>(after, run[64 * v + q]);
+            others[t] = fr_mul<PF>(before, after);
+        }
+    }
+    int32_t totals(size_t n, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t* zs, size_t npts, unsigned grid, fr_t* totals) {      // k_lagrange_totals
+        const uint32_t T = grid * 256, n32 = (uint32_t)n; fr_t pre[kLagK], t4[4];
+        for (size_t p = 0; p < npts; ++p) for (unsigned blk = 0; blk < grid; ++blk) {
+            for (int v = 0; v < 4; ++v) t4[v] = fr_one<PF>();
+            for (int t = 0; t < 256; ++t) {
+                const uint32_t tid = blk * 256 + t; fr_t w = tid < n32 ? lag_pow(wp, j0 + tid) : fr_one<PF>();
+                t4[t >> 6] = fr_mul<PF>(t4[t >> 6], lag_prefix(zs[p], w, w_step, tid, T, n32, pre));
+            }
+            totals[p * grid + blk] = lag_mul4(t4); ++census[2];
+        }
+        return 0;
+    }
+    int32_t invert(const fr_t* totals, size_t npts, unsigned grid, fr_t* inv) {                                                                   // k_lagrange_invert
+        std::vector<fr_t> run(256), others(256); fr_t tot[4];
+        for (size_t p = 0; p < npts; ++p) {
+            const fr_t* t = totals + p * grid; fr_t* o = inv + p * grid;
+            for (int l = 0; l < 256; ++l) run[l] = lag_chunk_prefix(t, lag_chunk((uint32_t)l, grid), o);
+            scan(run, tot, others);
+            const fr_t Pinv = fr_inv<PF>(lag_mul4(tot)); ++census[0];
+            for (int l = 0; l < 256; ++l) lag_chunk_peel(t, lag_chunk((uint32_t)l, grid), lag_lane_inverse(Pinv, tot, l >> 6, others[l]), o);
+        }
+        return 0;
+    }
+    int32_t partials(const fr_t* const* cols, size_t ncols, size_t n, uint64_t j0, const LagPow& wp, const fr_t& w_step, const fr_t& w_step_inv, const fr_t* zs, size_t npts, const LagEntries& E,
+                     const fr_t* inv, unsigned groups, unsigned col_groups, size_t group_cols, unsigned grid, fr_t* part) {
         const uint32_t T = grid * 256, n32 = (uint32_t)n;
-        std::vector<fr_t> Wv(256 * kLagK), w(256), run(256), lane(256);
+        std::vector<fr_t> Wv(256 * kLagK), w(256), run(256), lane(256), others(256);
         auto W = [&](int t) -> fr_t (&)[kLagK] { return *reinterpret_cast<fr_t (*)[kLagK]>(&Wv[(size_t)t * kLagK]); };
         for (unsigned cg = 0; cg < col_groups; ++cg) for (unsigned g = 0; g < groups; ++g) for (unsigned blk = 0; blk < grid; ++blk) {      // a workgroup per (tile, point group, column group), as on the device
             const size_t c_lo = (size_t)cg * group_cols, c_hi = std::min(c_lo + group_cols, ncols);
             for (int t = 0; t < 256; ++t) { const uint32_t tid = blk * 256 + t; w[t] = tid < n32 ? lag_pow(wp, j0 + tid) : fr_one<PF>(); }
-            for (size_t p = g; p < npts; p += groups) {
+            for (size_t p = g; p < npts; p += groups) {                                                                                      // the classes of the point group
                 const fr_t z = zs[p];
                 for (int t = 0; t < 256; ++t) run[t] = lag_prefix(z, w[t], w_step, blk * 256 + (uint32_t)t, T, n32, W(t));
-                fr_t tot[4], P = fr_one<PF>();
-                for (int v = 0; v < 4; ++v) { tot[v] = fr_one<PF>(); for (int l = 0; l < 64; ++l) tot[v] = fr_mul<PF>(tot[v], run[64 * v + l]); P = fr_mul<PF>(P, tot[v]); }
-                const fr_t Pinv = fr_inv<PF>(P);
-                for (int t = 0; t < 256; ++t) {
-                    const int v = t >> 6, l = t & 63; fr_t before = fr_one<PF>(), after = fr_one<PF>();
-                    for (int q = 0; q < l; ++q) before = fr_mul<PF>(before, run[64 * v + q]);
-                    for (int q = l + 1; q < 64; ++q) after = fr_mul<PF>(after, run[64 * v + q]);
-                    lag_peel(z, w[t], w_step_inv, blk * 256 + (uint32_t)t, T, n32, lag_lane_inverse(Pinv, tot, v, fr_mul<PF>(before, after)), W(t));
-                }
-                for (size_t c = c_lo; c < c_hi; ++c) {
-                    for (int t = 0; t < 256; ++t) lane[t] = lag_lane_dot<kLagWideAcc>(cols[c], blk * 256 + (uint32_t)t, T, n32, W(t));
-                    fr_t w4[4];
-                    for (int v = 0; v < 4; ++v) { w4[v] = fr_zero<PF>(); for (int l = 0; l < 64; ++l) w4[v] = fr_add<PF>(w4[v], lane[64 * v + l]); }
-                    part[(p * ncols + c) * grid + blk] = lag_sum4(w4);
+                ++census[1];
+                fr_t tot[4]; scan(run, tot, others);
+                fr_t Pinv;
+                if (inv) Pinv = inv[p * grid + blk]; else { Pinv = fr_inv<PF>(lag_mul4(tot)); ++census[0]; }
+                for (int t = 0; t < 256; ++t) lag_peel(z, w[t], w_step_inv, blk * 256 + (uint32_t)t, T, n32, lag_lane_inverse(Pinv, tot, t >> 6, others[t]), W(t));
+                const uint32_t m_lo = E.off ? E.off[p] : 0, m_hi = E.off ? E.off[p + 1] : 1;
+                for (uint32_t m = m_lo; m < m_hi; ++m) {
+                    const size_t q = E.off ? (size_t)E.member[m] : p; const uint32_t shift = E.off ? E.shift[m] : 0;
+                    ++census[3];
+                    for (size_t c = c_lo; c < c_hi; ++c) {
+                        for (int t = 0; t < 256; ++t)
+                            lane[t] = E.off ? lag_lane_dot<kLagWideAcc, true>(cols[c], blk * 256 + (uint32_t)t, T, n32, W(t), shift) : lag_lane_dot<kLagWideAcc>(cols[c], blk * 256 + (uint32_t)t, T, n32, W(t));
+                        fr_t w4[4];
+                        for (int v = 0; v < 4; ++v) { w4[v] = fr_zero<PF>(); for (int l = 0; l < 64; ++l) w4[v] = fr_add<PF>(w4[v], lane[64 * v + l]); }
+                        part[(q * ncols + c) * grid + blk] = lag_sum4(w4);
+                    }
                 }
             }
         }
@@ -1190,7 +1228,8 @@ static bool hc_lag_domain(size_t n, const uint64_t* omega, fr_t* w) {
 }
 // THE driver on the block B of the columns (cols[c]: B.n_local rows) with the host executor
 static int hc_lag_block(size_t ncols, const uint64_t* const* cols, const LagBlock& B, const uint64_t* omega, size_t npoints, const uint64_t* z, size_t max_partials, int col_groups, uint64_t* out,
-                        size_t* passes) {
+                        size_t* passes, int shared_inverse = 0, int share_cosets = 0, uint64_t* census4 = nullptr) {
+    if (census4) for (int i = 0; i < 4; ++i) census4[i] = 0;
     if (passes) *passes = 0;
     if (!ncols || !npoints) return 0;
     fr_t w; if (!hc_lag_domain(B.n_global, omega, &w)) return -1;
@@ -1204,7 +1243,9 @@ static int hc_lag_block(size_t ncols, const uint64_t* const* cols, const LagBloc
     for (size_t p = 0; p < npoints; ++p) zs[p] = ld4(z + 4 * p);
     std::vector<fr_t> o = hc_fr_block(npoints * ncols);
     LagHostExec X;
-    if (int32_t rc = lagrange_eval_batch(X, ncols, ptrs.data(), B, w, npoints, zs.data(), max_partials ? max_partials : kLagDefaultMaxPartials, col_groups, o.data(), passes)) return hc_rc(rc);
+    if (int32_t rc = lagrange_eval_batch(X, ncols, ptrs.data(), B, w, npoints, zs.data(), max_partials ? max_partials : kLagDefaultMaxPartials, col_groups, shared_inverse, share_cosets, o.data(), passes))
+        return hc_rc(rc);
+    if (census4) for (int i = 0; i < 4; ++i) census4[i] = X.census[i];
     for (size_t i = 0; i < o.size(); ++i) st4(out + 4 * i, o[i]);
     return 0;
 }
@@ -1223,6 +1264,21 @@ int hc_lagrange_eval_shard(size_t ncols, const uint64_t* const* cols, size_t n_l
     if (!ncols || !npoints) return 0;
     if (!n_local || j0 > n_global || n_local > n_global - j0) return -1;
     return hc_lag_block(ncols, cols, LagBlock{n_local, j0, n_global, false}, omega, npoints, z, max_partials, col_groups, partials_out, passes);
+}
+// hc_lagrange_eval_batch and hc_lagrange_eval_shard under the options "lagrange_shared_inverse" and "lagrange_share_cosets" (0 | 1), with "lagrange_col_groups"
+// for both.  census4 (may be null) = LagHostExec::census of the call: Fermat inversions, weight sets of the partials kernel, products of the totals
+// kernel, member walks.
+int hc_lagrange_eval_batch_opt(size_t ncols, const uint64_t* const* cols, size_t n, const uint64_t* omega, size_t npoints, const uint64_t* z, size_t max_partials, int col_groups, int shared_inverse,
+                               int share_cosets, uint64_t* out, size_t* passes, uint64_t* census4) {
+    return hc_lag_block(ncols, cols, lag_whole(n), omega, npoints, z, max_partials, col_groups, out, passes, shared_inverse, share_cosets, census4);
+}
+int hc_lagrange_eval_shard_opt(size_t ncols, const uint64_t* const* cols, size_t n_local, uint64_t j0, size_t n_global, const uint64_t* omega, size_t npoints, const uint64_t* z, size_t max_partials,
+                               int col_groups, int shared_inverse, int share_cosets, uint64_t* partials_out, size_t* passes, uint64_t* census4) {
+    if (passes) *passes = 0;
+    if (census4) for (int i = 0; i < 4; ++i) census4[i] = 0;
+    if (!ncols || !npoints) return 0;
+    if (!n_local || j0 > n_global || n_local > n_global - j0) return -1;
+    return hc_lag_block(ncols, cols, LagBlock{n_local, j0, n_global, false}, omega, npoints, z, max_partials, col_groups, partials_out, passes, shared_inverse, share_cosets, census4);
 }
 // stark_lagrange_eval_from_partials_dev: out[p * ncols + c] = scale[p] * the sum of the nparts shares (lagrange_combine)
 int hc_lagrange_eval_from_partials(size_t nparts, const uint64_t* partials, size_t ncols, size_t n_global, const uint64_t* omega, size_t npoints, const uint64_t* z, uint64_t* out) {

@@ -3,7 +3,8 @@
 // (stark_mlwe_amd/csrc/hostcheck.cpp: the driver headers over HostArena, whose alloc fails on request with STARK_ERR_OOM) into this program and sweeps
 // the drivers that take memory from the arena: request N = 1, 2, ... of a call is refused until a call ends with nothing refused.  These are the six
 // exports of tests/test_alloc_refusal_host.py that refuse anything (hc_fri_commit_batch, hc_merkle_build_batch, hc_merkle_build_mixed_batch,
-// hc_lagrange_eval_batch, hc_lagrange_eval_shard, hc_lagrange_eval_from_partials) and, beyond that test, hc_sumcheck_prove_batch; the five exports
+// hc_lagrange_eval_batch, hc_lagrange_eval_shard, hc_lagrange_eval_from_partials) and, beyond that test, hc_sumcheck_prove_batch and
+// hc_lagrange_eval_batch_opt (the driver under "lagrange_shared_inverse" and "lagrange_share_cosets", with a coset pair among the points); the five exports
 // whose drivers take nothing from the arena (the verify plans, the MLE pass loop, the transcript stream) are not here: nothing in them can be refused.
 // A refused call must return the out-of-memory status, must stop at the refusal, and the unarmed repeat must give the bytes of the first, unarmed
 // run; what a driver leaves behind on the way out (a block it still writes to, a table it frees twice, one it never frees) is an error of the
@@ -77,6 +78,13 @@ int main() {
             for (size_t c = 0; c < ncols; ++c) { col[c] = column(n); cp[c] = col[c].data(); }
             std::vector<uint64_t> z = column(npts); { const fr_t one = fr_one<PF>(); st4(z.data() + 4, one); }        // the second point lies in H
             sweep("lagrange_eval_batch", [&](std::vector<uint64_t>& out) { out.assign(4 * npts * ncols, 0); return hc_lagrange_eval_batch(ncols, cp.data(), n, nullptr, npts, z.data(), mp, out.data(), nullptr); });
+            {   // the shared inverse and the coset classes: two more tables, four more uploads; the third point is the first times omega
+                unsigned lg = 0; while (((size_t)1 << lg) < n) ++lg;
+                std::vector<uint64_t> zc = z; st4(zc.data() + 8, fr_mul<PF>(ld4(zc.data()), fr_root_of_unity<PF>(lg)));
+                for (int opt = 1; opt < 4; ++opt)
+                    sweep("lagrange_eval_batch_opt", [&](std::vector<uint64_t>& out) { out.assign(4 * npts * ncols, 0);
+                        return hc_lagrange_eval_batch_opt(ncols, cp.data(), n, nullptr, npts, zc.data(), mp, 2, opt & 1, opt >> 1, out.data(), nullptr, nullptr); });
+            }
             if (n < 256) continue;
             const size_t j0 = n / 4, nl = n / 2 + 1; std::vector<const uint64_t*> rows(ncols); for (size_t c = 0; c < ncols; ++c) rows[c] = col[c].data() + 4 * j0;
             std::vector<uint64_t> w(4); st4(w.data(), fr_root_of_unity<PF>(n == 256 ? 8u : 12u));

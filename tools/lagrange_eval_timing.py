@@ -13,7 +13,16 @@ Each line carries the median and the spread (min, max) of every variant and the 
   mac_floor_ms   field products x 96 MACs over stark_diag_mac_rate measured in the same run; products = P n (5.75 + C) + P W 381, W the workgroups
                  per column: per (point, position) 7/8 prefix + 12/8 scan + 5/8 lane inverse + 22/8 peel, per (point, position, column) 1, and one
                  Fermat inversion (254 squarings + 127 products) per (point, workgroup);
-and the achieved fraction of the binding (larger) floor."""
+and the achieved fraction of the binding (larger) floor.
+
+    python tools/lagrange_eval_timing.py LIB OUT.jsonl shared     (profiles/lagrange_shared_timing.jsonl)
+
+measures the options "lagrange_shared_inverse" and "lagrange_share_cosets" instead: the arms opt_00, opt_10, opt_01, opt_11 (shared inverse, cosets) of
+one stark_lagrange_eval_on_h_batch_dev call, alternated, the results checked byte-equal first, for the four shapes above with random points
+(points "random"), for the two-point shapes with the DEEP pair (z, z w) (points "pair") and for n = 2^20, C = 4 at sixteen shifts z w^s of one z
+(points "shifts").  Each line carries the same two floors (the MAC floor is option 0's: it counts one inversion per workgroup and one weight set per
+point), over_opt_00 = median(arm) / median(opt_00) and slower_beyond_spread: the arms whose median exceeds opt_00's by more than the spread
+(max - min) of either arm."""
 import ctypes as C, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -80,6 +89,56 @@ def shape_row(lg, ncols, npoints):
     row["ratio_plain_over_wide"] = round(row["batch_plain"]["median_ms"] / row["batch_wide"]["median_ms"], 4)
     row["fraction_of_binding_floor"] = round(max(hbm_ms, mac_ms) / best, 4)
     return row
+
+R_MOD = ((1 << 256) - int.from_bytes(MONT_ONE.tobytes(), "little")) // 3                     # 2^256 = 3 r + (2^256 mod r): r is just above 2^254
+R_INV = pow(1 << 256, -1, R_MOD)
+ARMS = {"opt_00": (0, 0), "opt_10": (1, 0), "opt_01": (0, 1), "opt_11": (1, 1)}
+
+def fr_mul(a, b):
+    """the product of two stored (Montgomery) elements, on the host"""
+    x = int.from_bytes(np.ascontiguousarray(a, np.uint64).tobytes(), "little") * int.from_bytes(np.ascontiguousarray(b, np.uint64).tobytes(), "little") * R_INV % R_MOD
+    return np.frombuffer(x.to_bytes(32, "little"), np.uint64).copy()
+
+def shared_points(lg, npoints, kind):
+    zs = np.ascontiguousarray(rng.integers(0, 1 << 62, size=(npoints, 4), dtype=np.uint64))
+    if kind != "random":                                              # z w^s: consecutive shifts for the pair, spread ones for the sixteen
+        w = root_of_unity(lg); step = w if kind == "pair" else fr_mul(fr_mul(w, w), w)
+        for p in range(1, npoints): zs[p] = fr_mul(zs[p - 1], step)
+    return zs
+
+def shared_row(lg, ncols, npoints, kind):
+    n = 1 << lg
+    cols = [synth(0x1A64 + lg, c, n) for c in range(ncols)]; ptrs = [t.data_ptr() for t in cols]; zs = shared_points(lg, npoints, kind)
+    out = {v: torch.zeros((npoints * ncols, 4), dtype=torch.int64, device=dev) for v in ARMS}
+    times = {v: [] for v in ARMS}
+    for rep in range(REPS + 1):                                       # repetition 0 is the warm-up of this shape
+        for v, (inv, cos) in ARMS.items():
+            ctx.set_option("lagrange_shared_inverse", inv); ctx.set_option("lagrange_share_cosets", cos)
+            t = timed(lambda: ctx.lagrange_eval_on_h_batch_dev(ptrs, n, zs, out[v].data_ptr()))
+            if rep: times[v].append(t)
+        if not rep:
+            ctx.sync(); assert all(torch.equal(out[v], out["opt_00"]) for v in ARMS), (lg, ncols, npoints, kind)
+    ctx.set_option("lagrange_shared_inverse", -1); ctx.set_option("lagrange_share_cosets", -1)
+    W = -(-(-(-n // 8)) // 256)
+    products = npoints * n * (5.75 + ncols) + npoints * W * 381
+    hbm_ms = 1e3 * ncols * n * 32 / HBM_BPS; mac_ms = 1e3 * products * 96 / mac_rate.value
+    row = {"tool": "lagrange_eval_timing", "call": "batch", "log_n": lg, "ncols": ncols, "npoints": npoints, "points": kind, "reps": REPS, "outputs_byte_equal": True,
+           "lane_macs_per_s": mac_rate.value, "hbm_floor_ms": round(hbm_ms, 5), "mac_floor_ms": round(mac_ms, 5)}
+    for v in ARMS: row[v] = stats(times[v])
+    spread = lambda v: row[v]["max_ms"] - row[v]["min_ms"]
+    row["over_opt_00"] = {v: round(row[v]["median_ms"] / row["opt_00"]["median_ms"], 4) for v in ARMS if v != "opt_00"}
+    row["slower_beyond_spread"] = [v for v in ARMS if v != "opt_00" and row[v]["median_ms"] - row["opt_00"]["median_ms"] > max(spread(v), spread("opt_00"))]
+    row["fraction_of_mac_floor"] = {v: round(mac_ms / row[v]["median_ms"], 4) for v in ARMS}
+    return row
+
+if len(sys.argv) > 3 and sys.argv[3] == "shared":
+    rows = []
+    for lg, ncols, npoints, kind in [s + ("random",) for s in SHAPES] + [(20, 4, 2, "pair"), (16, 64, 2, "pair"), (20, 4, 16, "shifts")]:
+        rows.append(shared_row(lg, ncols, npoints, kind)); print(json.dumps(rows[-1]), flush=True)
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(sys.argv[2])), exist_ok=True)
+    open(sys.argv[2], "w").write("".join(json.dumps(r) + "\n" for r in rows))
+    ctx.close(); sys.exit(0)
 
 out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "lagrange_eval_timing.jsonl")
 rows = []

@@ -18,7 +18,14 @@ medians with the spread (min, max).
     real links is not measured by this tool.
 Each line carries the floors of lagrange_eval_timing.py for one group: hbm_floor_ms = C n 32 bytes over 6.29 TB/s; mac_floor_ms = (P n (5.75 + C) +
 P W 381) field products x 96 MACs over stark_diag_mac_rate read in the same run; with G column groups the weights are computed G times:
-mac_floor_groups_ms = (P n (5.75 G + C) + P W G 381) products."""
+mac_floor_groups_ms = (P n (5.75 G + C) + P W G 381) products.
+
+    python tools/lagrange_shard_timing.py LIB OUT.jsonl shared     (appends to OUT: profiles/lagrange_shared_timing.jsonl)
+
+measures the options "lagrange_shared_inverse" and "lagrange_share_cosets" on the shard-like shapes (2^17, 4, 2) and (2^17, 64, 2) instead: the arms
+opt_00, opt_10, opt_01, opt_11 (shared inverse, cosets), alternated, results checked byte-equal first, of the batch call on 2^17 rows (call "batch") and
+of stark_lagrange_eval_shard_dev on the rows [2^17, 2^18) of a 2^20-point domain (call "shard": the block form ignores the cosets).  The points are
+the pair (z, z w) of the call's own domain.  Lines as in lagrange_eval_timing.py's shared mode."""
 import ctypes as C, json, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,7 +33,7 @@ import numpy as np
 import torch
 import stark_mlwe_amd._abi as abi
 path = os.path.abspath(sys.argv[1]); abi.lib_path = lambda: path
-from stark_mlwe_amd.api import Context
+from stark_mlwe_amd.api import Context, root_of_unity
 dev = torch.device("cuda", 0)
 ctx = Context(0, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)); lib = ctx.lib
 rng = np.random.default_rng(0x1A64)
@@ -128,6 +135,51 @@ def sharded_row(lg, ncols, npoints, W):
     row["emulated_over_batch"] = round(row["emulated_w8"]["median_ms"] / row["batch"]["median_ms"], 3)
     row["shard_calls_over_batch"] = round(row["shard_calls_w8"]["median_ms"] / row["batch"]["median_ms"], 3)
     return row
+
+MONT_ONE = np.array([0x5b2b3e9cfffffffd, 0x992c350be3420567, 0xffffffffffffffff, 0x3fffffffffffffff], np.uint64)    # 2^256 mod r (Pallas Fr), csrc/fr.hpp
+R_MOD = ((1 << 256) - int.from_bytes(MONT_ONE.tobytes(), "little")) // 3                     # 2^256 = 3 r + (2^256 mod r): r is just above 2^254
+R_INV = pow(1 << 256, -1, R_MOD)
+ARMS = {"opt_00": (0, 0), "opt_10": (1, 0), "opt_01": (0, 1), "opt_11": (1, 1)}
+
+def fr_mul(a, b):
+    """the product of two stored (Montgomery) elements, on the host"""
+    x = int.from_bytes(np.ascontiguousarray(a, np.uint64).tobytes(), "little") * int.from_bytes(np.ascontiguousarray(b, np.uint64).tobytes(), "little") * R_INV % R_MOD
+    return np.frombuffer(x.to_bytes(32, "little"), np.uint64).copy()
+
+def shared_row(lg, ncols, call):
+    n = 1 << lg; lg_global = lg if call == "batch" else 20
+    cols = [synth(0x1A64 + lg, c, n) for c in range(ncols)]; ptrs = [t.data_ptr() for t in cols]
+    zs = points(2); zs[1] = fr_mul(zs[0], root_of_unity(lg_global))
+    out = {v: torch.zeros((2 * ncols, 4), dtype=torch.int64, device=dev) for v in ARMS}
+    def run(o):
+        if call == "batch": return lambda: ctx.lagrange_eval_on_h_batch_dev(ptrs, n, zs, o.data_ptr())
+        return lambda: ctx.lagrange_eval_shard_dev(ptrs, n, n, 1 << lg_global, zs, o.data_ptr())
+    times = {v: [] for v in ARMS}
+    for rep in range(REPS + 1):
+        for v, (inv, cos) in ARMS.items():
+            ctx.set_option("lagrange_shared_inverse", inv); ctx.set_option("lagrange_share_cosets", cos)
+            t = timed(run(out[v]))
+            if rep: times[v].append(t)
+        if not rep:
+            ctx.sync(); assert all(torch.equal(out[v], out["opt_00"]) for v in ARMS), (lg, ncols, call)
+    ctx.set_option("lagrange_shared_inverse", -1); ctx.set_option("lagrange_share_cosets", -1)
+    row = {"tool": "lagrange_shard_timing", "call": call, "log_n": lg, "log_n_global": lg_global, "ncols": ncols, "npoints": 2, "points": "pair", "reps": REPS, "outputs_byte_equal": True,
+           "groups": auto_groups(n, ncols, 2)}
+    row.update(floors(n, ncols, 2, row["groups"]))
+    for v in ARMS: row[v] = stats(times[v])
+    spread = lambda v: row[v]["max_ms"] - row[v]["min_ms"]
+    row["over_opt_00"] = {v: round(row[v]["median_ms"] / row["opt_00"]["median_ms"], 4) for v in ARMS if v != "opt_00"}
+    row["slower_beyond_spread"] = [v for v in ARMS if v != "opt_00" and row[v]["median_ms"] - row["opt_00"]["median_ms"] > max(spread(v), spread("opt_00"))]
+    return row
+
+if len(sys.argv) > 3 and sys.argv[3] == "shared":
+    rows = []
+    for lg, ncols in ((17, 4), (17, 64)):
+        for call in ("batch", "shard"):
+            rows.append(shared_row(lg, ncols, call)); print(json.dumps(rows[-1]), flush=True)
+            torch.cuda.empty_cache()
+    open(sys.argv[2], "a").write("".join(json.dumps(r) + "\n" for r in rows))
+    ctx.close(); sys.exit(0)
 
 out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "lagrange_shard_timing.jsonl")
 rows = []
